@@ -18,13 +18,19 @@ of the [mean | var] shards closes each step.  value = predictions of all ranks /
 `--workload c4` is BASELINE.json configs[3]: 1 048 576 queries in total sharded over the ranks, posterior means only,
 all-gather of the means (strong scaling).
 
-Prints ONE JSON line on rank 0 with the driver's contract fields plus
+A plain run does only what the headline figure needs: set-up, warm-up, the timed steps, and ONE JSON line on rank 0 with
+the driver's contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step, ...) and the workload's config.
+`--dump-outputs DIR` then writes what the timed path returned in its last step as DIR/<name>.npy (float32 / float64,
+64 MB at most; inputs are seeded, so two builds can be compared output for output).
+
+`--full` adds everything else to the line (each part measured outside the timed steps):
   "roofline":     the dominant kernel (the one GEMM launch behind |L^-1 k*|^2) against the matrix-pipe peak it
                   runs on, its duration measured live with HIP events on the launch stream over the timed steps;
   "cpu_baseline": the reference's CPU path (scikit-learn GaussianProcessRegressor, the library the reference
                   delegates to; falls back to the repo's NumPy oracle) on a bounded sample;
   "fit":          Gram GB/s vs the HBM roofline and Cholesky GFLOP/s of the set-up phase;
-  "parity":       the timed path's outputs against the fp64 path on the same batch (checked after the timed loop).
+  "parity":       the timed path's outputs against the fp64 path on the same batch (checked after the timed loop);
+and "host_api", "extras", "allgather_ms", the other workloads' per-kernel figures the same way.
 """
 import argparse
 import ctypes as C
@@ -54,8 +60,14 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=None, help="untimed steps (default: 2; train: 1)")
     ap.add_argument("--n-train", type=int, default=None, help="default: 65536; train: 10000; lml: 16384")
     ap.add_argument("--queries", type=int, default=10000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra timing of the other variance paths")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: CPU baselines, parity against the "
+                         "fp64 kernels and scikit-learn, fit-phase rates, roofline / per-kernel figures, board sensors, "
+                         "the host-boundary rate and the other variance paths")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the extra timing of the other variance paths")
     ap.add_argument("--workload", default="c3", choices=["c3", "c4", "gram", "train", "lml"],
                     help="c3 (default, the headline): mean+var for 10 000 queries per GPU per step, weak scaling; "
                          "c4: BASELINE configs[3] - 1 048 576 queries in total sharded over the GPUs, posterior means "
@@ -81,7 +93,26 @@ def parse_args(argv=None):
         args.warmup = {"train": 1}.get(wl, 2)
     if args.n_train is None:
         args.n_train = {"train": 10000, "lml": 16384}.get(wl, 65536)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     return args
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one .npy per array (float32 / float64 only, DUMP_MAX_BYTES in all)."""
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    for k, v in arrays.items():
+        if v.dtype not in (np.float32, np.float64):
+            raise TypeError(f"--dump-outputs: {k} is {v.dtype}, not float32 / float64")
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes, more than {DUMP_MAX_BYTES}")
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
 
 
 def launch_ranks(args):
@@ -326,20 +357,29 @@ def bench_gram(args, be, rank, world, use_dist, ranks_seen):
     evs = []
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
+        if args.full:
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
         step()
-        b.record()
-        evs.append((a, b))
+        if args.full:
+            b.record()
+            evs.append((a, b))
     sync_all()
     dt = time.perf_counter() - t0
-    mine = float(np.mean([a.elapsed_time(b) for a, b in evs])) * 1e-3
     if use_dist:
         t = torch.tensor([dt], dtype=torch.float64, device=be.device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    ok = bool(torch.isfinite(slab).all()) and (nrows == 0 or float(slab[0, row0]) == 1.0 + 0.1001)
-    assert ok, "Gram slab check failed"
+    if rank == 0 and args.dump_outputs:
+        # the slab is N_train x Np fp64 (34 GB at the default size): a fixed, seeded sample of 2^20 of its entries
+        rng = np.random.default_rng(0)
+        ri = torch.as_tensor(rng.integers(0, max(nrows, 1), 1 << 20), device=be.device)
+        ci = torch.as_tensor(rng.integers(0, N, 1 << 20), device=be.device)
+        dump_outputs(args.dump_outputs, {"gram_sample": slab[ri, ci].cpu().numpy() if nrows else np.zeros(0)})
+    if args.full:
+        mine = float(np.mean([a.elapsed_time(b) for a, b in evs])) * 1e-3
+        ok = bool(torch.isfinite(slab).all()) and (nrows == 0 or float(slab[0, row0]) == 1.0 + 0.1001)
+        assert ok, "Gram slab check failed"
     if rank == 0:
         total_bytes = float(Np) * Np * 8 + float(N) * D * 8          # N^2 s + N D s
         my_bytes = float(nrows) * Np * 8 + float(N) * D * 8
@@ -351,15 +391,16 @@ def bench_gram(args, be, rank, world, use_dist, ranks_seen):
                                        f"in 128-row tiles, no exchange", "n_train": N, "features": D,
                            "rows_of_rank0": nrows,
                            "kernel": "gram_strip_kernel (symmetric tiles computed once, written twice)" if world == 1
-                                     else "cross_t_kernel per slab (every entry computed directly: no mirroring across ranks)"},
-                "roofline": {"bound": "hbm" if world == 1 else "valu", "achieved": my_bytes / mine / 1e9, "peak": HBM_PEAK_GBPS,
-                             "unit": "GB/s", "frac": my_bytes / mine / 1e9 / HBM_PEAK_GBPS,
-                             "traffic": (pmc_workload_traffic("gram", N) or {}).get("bytes_per_step") if world == 1 else None,
-                             "traffic_source": (pmc_workload_traffic("gram", N) or {}).get("source") if world == 1 else None,
-                             "kernel_ms": mine * 1e3,
-                             "note": "rank 0's slab bytes over its own launch time (HIP events); a slab kernel computes every "
-                                     "entry (about 45 fp64 operations each), so from two ranks up it is bound by the "
-                                     "fp64 vector rate rather than by HBM"}}
+                                     else "cross_t_kernel per slab (every entry computed directly: no mirroring across ranks)"}}
+        if args.full:
+            line["roofline"] = {"bound": "hbm" if world == 1 else "valu", "achieved": my_bytes / mine / 1e9, "peak": HBM_PEAK_GBPS,
+                                "unit": "GB/s", "frac": my_bytes / mine / 1e9 / HBM_PEAK_GBPS,
+                                "traffic": (pmc_workload_traffic("gram", N) or {}).get("bytes_per_step") if world == 1 else None,
+                                "traffic_source": (pmc_workload_traffic("gram", N) or {}).get("source") if world == 1 else None,
+                                "kernel_ms": mine * 1e3,
+                                "note": "rank 0's slab bytes over its own launch time (HIP events); a slab kernel computes every "
+                                        "entry (about 45 fp64 operations each), so from two ranks up it is bound by the "
+                                        "fp64 vector rate rather than by HBM"}
         print(json.dumps(line), flush=True)
     if use_dist:
         dist.barrier()
@@ -400,7 +441,8 @@ def bench_train(args, be):
         evals.append((time.perf_counter() - t0, bool(eval_gradient)))
         return r
 
-    gpr_mod.GaussianProcessRegressor._lml_on_device = counted
+    if args.full:
+        gpr_mod.GaussianProcessRegressor._lml_on_device = counted
     res = {}
 
     def step():
@@ -419,7 +461,8 @@ def bench_train(args, be):
             step()
         torch.cuda.synchronize()
         evals.clear()
-        be.check(be.lib.gpk_timing(be.h, 1))
+        if args.full:
+            be.check(be.lib.gpk_timing(be.h, 1))
         t0 = time.perf_counter()
         for _ in range(args.steps):
             step()
@@ -427,12 +470,30 @@ def bench_train(args, be):
         dt = time.perf_counter() - t0
     finally:
         gpr_mod.GaussianProcessRegressor._lml_on_device = orig
+    gm = res["gp"].gp_model
+    if args.dump_outputs:
+        # the trained model of the last train_gp(): log-hyper-parameters, LML, alpha (N x P)
+        dump_outputs(args.dump_outputs, {"theta": np.asarray(gm.kernel_.theta, dtype=np.float64),
+                                         "lml": np.array([gm.log_marginal_likelihood_value_], dtype=np.float64),
+                                         "alpha": np.asarray(gm.alpha_, dtype=np.float64)})
+    line = {
+        "metric": "offline GP training wall time: SimpleQuadrotorGP.train_gp() (L-BFGS-B + 1 restart, LML + analytic gradient "
+                  "per evaluation) on N_train rows, D=10, P=6",
+        "value": dt / args.steps, "unit": "s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": False, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic flight-like rows (bench.synthetic_flight_problem), random restart seeded",
+        "config": {"workload": f"train: N_train={N}, D={D}, P={P}, kernel RBF(0.5)+White(0.1), alpha=1e-4, normalize_y, "
+                               "n_restarts_optimizer=1 (src/px4/train_gp_offline.py:124-140, simple_gp.py:156-185)"},
+    }
+    if not args.full:
+        line["peak_hbm_bytes_per_rank"] = int(torch.cuda.max_memory_allocated(be.device))
+        print(json.dumps(line), flush=True)
+        return
     ms = np.zeros(64)
     n = C.c_int(0)
     be.check(be.lib.gpk_kernel_times(be.h, _lib.GPK_TIMED_POTRF, ms.ctypes.data_as(_lib._dp), 64, C.byref(n)))
     potrf_ms = float(np.mean(ms[: n.value])) if n.value else None
     be.check(be.lib.gpk_timing(be.h, 0))
-    gm = res["gp"].gp_model
     ge = [t for t, g in evals if g]
     gv = [t for t, g in evals if not g]
     # the optimiser's two runs (start + one restart) execute one after the other at this size (side by side on two handles /
@@ -443,14 +504,7 @@ def bench_train(args, be):
     s_train = dt / args.steps
     s_eval = s_train / max(len(ge) / args.steps, 1)
     tr = pmc_workload_traffic("train", N)
-    line = {
-        "metric": "offline GP training wall time: SimpleQuadrotorGP.train_gp() (L-BFGS-B + 1 restart, LML + analytic gradient "
-                  "per evaluation) on N_train rows, D=10, P=6",
-        "value": dt / args.steps, "unit": "s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": False, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f64", "data": "synthetic flight-like rows (bench.synthetic_flight_problem), random restart seeded",
-        "config": {"workload": f"train: N_train={N}, D={D}, P={P}, kernel RBF(0.5)+White(0.1), alpha=1e-4, normalize_y, "
-                               "n_restarts_optimizer=1 (src/px4/train_gp_offline.py:124-140, simple_gp.py:156-185)"},
+    line.update({
         "lml_grad_evaluations_per_train": len(ge) / args.steps,
         "s_per_lml_grad_evaluation": s_eval,
         "s_per_lml_grad_evaluation_note": "train_gp() wall time / gradient evaluations (the optimiser's runs: one after the other above 7168 rows)",
@@ -467,7 +521,7 @@ def bench_train(args, be):
                              "K^-1 = W^T W; SURVEY 8d K6), 2 N^3 / 3 per value-only evaluation and for the final fit - over its "
                              "wall time, host side of the optimiser, Gram builds and reductions included"},
         "peak_hbm_bytes_per_rank": int(torch.cuda.max_memory_allocated(be.device)),
-    }
+    })
     if not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_train_baseline(N)
     print(json.dumps(line), flush=True)
@@ -526,12 +580,27 @@ def bench_lml(args, be):
         lml, grad = bg.log_marginal_likelihood(th, eval_gradient=True, fused=True)
     torch.cuda.synchronize()
     fbe = bg._fs["be"]
-    fbe.check(fbe.lib.gpk_timing(fbe.h, 1))
+    if args.full:
+        fbe.check(fbe.lib.gpk_timing(fbe.h, 1))
     t0 = time.perf_counter()
     for _ in range(args.steps):
         lml, grad = bg.log_marginal_likelihood(th, eval_gradient=True, fused=True)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"lml": np.asarray(lml, dtype=np.float64), "grad": np.asarray(grad, dtype=np.float64)})
+    step_s = dt / args.steps
+    line = {
+        "metric": "LML + gradient evaluations/s, three per-axis ARD GPs fused into one launch chain (BASELINE configs[4])",
+        "value": B / step_s, "unit": "GP evaluations/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": step_s * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
+        "data": "synthetic (SURVEY 8d generator), ARD l_d = 2.0 (1 + 0.1 d), noise 0.1, jitter 1e-4",
+        "config": {"workload": f"C5: N_train={N}, D={D}, B={B} single-output ARD GPs on shared inputs, LML + gradient"},
+    }
+    if not args.full:
+        line["peak_hbm_bytes_per_rank"] = int(torch.cuda.max_memory_allocated(be.device))
+        print(json.dumps(line), flush=True)
+        return
 
     def times(tag):
         ms = np.zeros(64)
@@ -542,7 +611,6 @@ def bench_lml(args, be):
     grad_ms, potrf_ms = times(_lib.GPK_TIMED_GRAD), times(_lib.GPK_TIMED_POTRF)
     fbe.check(fbe.lib.gpk_timing(fbe.h, 0))
     assert len(grad_ms) >= B and np.isfinite(lml).all() and np.isfinite(grad).all()
-    step_s = dt / args.steps
     flops = B * float(N) ** 3
     Np = (N + 127) // 128 * 128
     gk = float(np.mean(grad_ms)) * 1e-3
@@ -554,12 +622,7 @@ def bench_lml(args, be):
     alg_bytes = Np * (Np + 128) / 2 * 8
     tr = pmc_workload_traffic("lml", N)
     gkern = (tr or {}).get("by_kernel", {}).get("lml_grad_kernel")
-    line = {
-        "metric": "LML + gradient evaluations/s, three per-axis ARD GPs fused into one launch chain (BASELINE configs[4])",
-        "value": B / step_s, "unit": "GP evaluations/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": step_s * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
-        "data": "synthetic (SURVEY 8d generator), ARD l_d = 2.0 (1 + 0.1 d), noise 0.1, jitter 1e-4",
-        "config": {"workload": f"C5: N_train={N}, D={D}, B={B} single-output ARD GPs on shared inputs, LML + gradient"},
+    line.update({
         "roofline": {"bound": "mfma", "achieved": flops / step_s / 1e12, "peak": MFMA_F64_PEAK_TF, "unit": "TFLOP/s",
                      "frac": flops / step_s / 1e12 / MFMA_F64_PEAK_TF,
                      "traffic": tr["bytes_per_step"] if tr else None,
@@ -576,7 +639,7 @@ def bench_lml(args, be):
         "potrf_ms_all_models_one_launch": float(np.mean(potrf_ms)) if len(potrf_ms) else None,
         "lml": [float(v) for v in lml],
         "peak_hbm_bytes_per_rank": int(torch.cuda.max_memory_allocated(be.device)),
-    }
+    })
     if not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_lml_baseline(N)
     print(json.dumps(line), flush=True)
@@ -690,14 +753,16 @@ def main():
 
     def fit_model():
         dev = DeviceGP(X, Yn, be)
-        dev.timing(True)
+        if args.full:
+            dev.timing(True)
         dev.gram(ls, sf2, noise + jitter)            # warm-up of the Gram kernel + allocation
         torch.cuda.synchronize()
-        for _ in range(6):
-            dev.gram(ls, sf2, noise + jitter)
-        gram_times = dev.kernel_times(_lib.GPK_TIMED_GRAM)[-6:] * 1e-3     # HIP events around the Gram kernel launches
-        gram_s = float(np.mean(gram_times))                                 # the average (what a rocprofv3 --stats row shows)
-        gram_bytes = dev.Np * dev.Np * 8 + N * D * 8          # N^2 s + N D s (s = 8)
+        if args.full:                                # --full: six more (identical) Gram builds, bracketed, for `fit`
+            for _ in range(6):
+                dev.gram(ls, sf2, noise + jitter)
+            gram_times = dev.kernel_times(_lib.GPK_TIMED_GRAM)[-6:] * 1e-3     # HIP events around the Gram kernel launches
+            gram_s = float(np.mean(gram_times))                                 # the average (what a rocprofv3 --stats row shows)
+            gram_bytes = dev.Np * dev.Np * 8 + N * D * 8          # N^2 s + N D s (s = 8)
         info = C.c_int(0)
         t0 = time.perf_counter()
         be.check(be.lib.gpk_potrf(be.h, C.c_void_p(dev.K.data_ptr()), dev.Np, dev.Np, C.c_void_p(dev.winv.data_ptr()),
@@ -719,7 +784,7 @@ def main():
             warm.pop(1)
             warm.append(be.empty((dev.Np * dev.Np * (6 if method == "inverse_split" else 4),), torch.uint8))
             del warm
-            if method == "inverse_split2":
+            if method == "inverse_split2" and args.full:
                 # (and the split's two kernels once on one tile: a kernel's first launch in a process pays its lazy load,
                 # ~0.7 ms here - not part of what the split costs)
                 w1 = torch.eye(128, dtype=torch.float64, device=be.device)
@@ -755,6 +820,8 @@ def main():
             # (The fp64 variance of the parity check below then runs as the blocked solve with L - slower, untimed.)
             dev._Winv.pop("f64", None)
         torch.cuda.synchronize()
+        if not args.full:
+            return dev, None
         fit = {"n_train": N, "dtype": "f64",
                "gram_ms": gram_s * 1e3, "gram_ms_min_avg_max": [float(gram_times.min() * 1e3), gram_s * 1e3, float(gram_times.max() * 1e3)],
                "gram_launches_timed": int(len(gram_times)), "gram_GBps": gram_bytes / gram_s / 1e9,
@@ -788,13 +855,14 @@ def main():
         if rank != 0:
             dev = DeviceGP.from_serving_state(meta, tens, be)
             dev._f32_data()
-        else:
+        elif fit is not None:
             fit["replication"] = "broadcast"
             fit["broadcast_s"] = bcast_s
             fit["broadcast_bytes"] = int(sum(t.numel() * t.element_size() for t in tens.values()))
     else:
         dev, fit = fit_model()
-        fit["replication"] = "refit" if world > 1 else "none (one rank)"
+        if fit is not None:
+            fit["replication"] = "refit" if world > 1 else "none (one rank)"
 
     # ---------------------------------------------------------------- the timed hot path
     kss = sf2 + noise
@@ -807,6 +875,8 @@ def main():
     thr_low = dev.FP32_VAR_RECHECK_FRACTION * kss * float(y_std[0] ** 2)
 
     def gathered(rows):
+        if not args.full:
+            return all_gather_rows(rows, M * world)                                         # RCCL all-gather
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         g = all_gather_rows(rows, M * world)                                                # RCCL all-gather
@@ -852,10 +922,11 @@ def main():
     for _ in range(args.warmup):
         step()
     sync_all()
-    dev.timing(True)                               # restart the event ring: it now covers exactly the timed steps
+    if args.full:
+        dev.timing(True)                           # restart the event ring: it now covers exactly the timed steps
     ag_events.clear()
     low_patched[0] = 0
-    sensors = BoardSensors(be.device.index if be.device.index is not None else 0) if rank == 0 else None
+    sensors = BoardSensors(be.device.index if be.device.index is not None else 0) if rank == 0 and args.full else None
     if sensors:
         sensors.start()
     t0 = time.perf_counter()
@@ -864,12 +935,58 @@ def main():
     sync_all()
     dt = time.perf_counter() - t0
     board = sensors.stop() if sensors else None
-    k5_ms = dev.kernel_times(_lib.GPK_TIMED_K5)    # the dominant launch of every timed step (the last 64 of them)
-    dev.timing(False)
+    if args.full:
+        k5_ms = dev.kernel_times(_lib.GPK_TIMED_K5)    # the dominant launch of every timed step (the last 64 of them)
+        dev.timing(False)
     if use_dist:
         t = torch.tensor([dt], dtype=torch.float64, device=be.device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        # what the caller of the timed path receives: the (M, P) fp32 means (c4), or [mean | var] un-normalised in fp64 (c3),
+        # the ranks' shards gathered
+        o = out.cpu().numpy()
+        dump_outputs(args.dump_outputs, {"mean": o} if c4 else {"mean": o[:, :P], "var": o[:, P:]})
+
+    def headline():
+        total_pred = float(M) * world * args.steps
+        return {
+            "metric": "GP predictions/sec (mean+var) at N_train=65536, D=9" if not c4 else
+                      "GP predictions/sec (posterior means, 1M queries sharded) at N_train=65536, D=9",
+            "value": total_pred / dt, "unit": "predictions/s",
+            "n_gpus": world, "ranks_seen": ranks_seen, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "strong" if c4 else "weak",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": (f"C3: N_train={N}, D={D}, P={P}, batched predict mean+var over {M} query points "
+                                    f"per GPU per step (horizon 20 x 500 rollouts), fp32 predict on an fp64 factor")
+                                   if not c4 else
+                                   (f"C4: N_train={N}, D={D}, P={P}, {M * world} queries sharded over {world} GPU(s), "
+                                    f"posterior means, fp32, all-gather of the means"),
+                       "n_train": N, "features": D, "outputs": P, "queries_per_gpu_per_step": M,
+                       "variance_path": None if c4 else method,
+                       "arithmetic": "fp32 operands and accumulation" +
+                                     ("; products on the bf16 MFMA pipe from an exact 3-way bf16 split of every fp32 "
+                                      "operand (error class of the fp32 MFMA, checked under \"parity\")"
+                                      if (method == "inverse_split" and not c4) else
+                                      ("; products on the fp16 MFMA pipe: every fp32 operand as two round-to-nearest fp16 parts "
+                                       "(a0 + a1 = a to 2^-23 at worst), block products a1 b0 + a0 b1 + a0 b0 (the dropped a1 b1 "
+                                       "is below 2^-22 |a b|; measured error equal to the exact-fp32 MFMA launch's: checked under "
+                                       "\"parity\" and, for all three fp32 forms, under \"extras\")"
+                                       if (method == "inverse_split2" and not c4) else "")),
+                       "parallelism": f"query-sharded x{world}, model replicated (" +
+                                      ("rank 0 fits, RCCL broadcast of X, alpha and the split inverse factor" if by_broadcast
+                                       else "every rank fits redundantly") + ")" +
+                                      ((", RCCL all-gather of the means" if c4 else ", RCCL all-gather of [mean|var]")
+                                       if use_dist else "")}}
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps({**headline(), "peak_hbm_bytes_per_rank": int(torch.cuda.max_memory_allocated(be.device))}),
+                  flush=True)
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     assert bool(torch.isfinite(out).all()), "non-finite predictions"
     # the collective's own share of a step: HIP events around every all-gather of the timed steps (this rank's view; the MAX
     # over ranks is what bounds the step)
@@ -1080,35 +1197,8 @@ def main():
         dist.all_gather_object(gathered, peak_all[0])
         peak_all = [int(v) for v in gathered]
     if rank == 0:
-        total_pred = float(M) * world * args.steps
         line = {
-            "metric": "GP predictions/sec (mean+var) at N_train=65536, D=9" if not c4 else
-                      "GP predictions/sec (posterior means, 1M queries sharded) at N_train=65536, D=9",
-            "value": total_pred / dt, "unit": "predictions/s",
-            "n_gpus": world, "ranks_seen": ranks_seen, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "strong" if c4 else "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": (f"C3: N_train={N}, D={D}, P={P}, batched predict mean+var over {M} query points "
-                                    f"per GPU per step (horizon 20 x 500 rollouts), fp32 predict on an fp64 factor")
-                                   if not c4 else
-                                   (f"C4: N_train={N}, D={D}, P={P}, {M * world} queries sharded over {world} GPU(s), "
-                                    f"posterior means, fp32, all-gather of the means"),
-                       "n_train": N, "features": D, "outputs": P, "queries_per_gpu_per_step": M,
-                       "variance_path": None if c4 else method,
-                       "arithmetic": "fp32 operands and accumulation" +
-                                     ("; products on the bf16 MFMA pipe from an exact 3-way bf16 split of every fp32 "
-                                      "operand (error class of the fp32 MFMA, checked under \"parity\")"
-                                      if (method == "inverse_split" and not c4) else
-                                      ("; products on the fp16 MFMA pipe: every fp32 operand as two round-to-nearest fp16 parts "
-                                       "(a0 + a1 = a to 2^-23 at worst), block products a1 b0 + a0 b1 + a0 b0 (the dropped a1 b1 "
-                                       "is below 2^-22 |a b|; measured error equal to the exact-fp32 MFMA launch's: checked under "
-                                       "\"parity\" and, for all three fp32 forms, under \"extras\")"
-                                       if (method == "inverse_split2" and not c4) else "")),
-                       "parallelism": f"query-sharded x{world}, model replicated (" +
-                                      ("rank 0 fits, RCCL broadcast of X, alpha and the split inverse factor" if by_broadcast
-                                       else "every rank fits redundantly") + ")" +
-                                      ((", RCCL all-gather of the means" if c4 else ", RCCL all-gather of [mean|var]")
-                                       if use_dist else "")},
+            **headline(),
             "roofline": roof,
             "peak_hbm_bytes_per_rank": int(torch.cuda.max_memory_allocated(be.device)),
             "peak_hbm_bytes_all_ranks": peak_all,

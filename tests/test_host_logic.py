@@ -454,3 +454,24 @@ def test_library_reads_no_environment():
     src = "".join(open(os.path.join(ROOT, "unmanned_aerial_vehicles_amd", "csrc", f)).read()
                   for f in os.listdir(os.path.join(ROOT, "unmanned_aerial_vehicles_amd", "csrc")))
     assert "getenv(" not in src
+
+
+def test_bench_plain_run_options_and_dump(tmp_path):
+    """`bench.py` is a plain run unless `--full` is given, takes --steps / --warmup as given, and `--dump-outputs`
+    writes float32 / float64 .npy files within the 64 MB bound (anything else is refused)."""
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup, a.workload) == (False, None, 7, 3, "c3")
+    a = bench.parse_args(["--full", "--dump-outputs", str(tmp_path), "--workload", "lml"])
+    assert a.full and a.dump_outputs == str(tmp_path) and (a.steps, a.warmup) == (5, 2)
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+    m = np.arange(12, dtype=np.float64).reshape(4, 3)
+    bench.dump_outputs(str(tmp_path / "d"), {"mean": m[:, :2], "var": m[:, 2:].astype(np.float32)})
+    assert np.array_equal(np.load(tmp_path / "d" / "mean.npy"), m[:, :2])
+    assert np.load(tmp_path / "d" / "var.npy").dtype == np.float32
+    with pytest.raises(TypeError):
+        bench.dump_outputs(str(tmp_path / "e"), {"index": np.arange(3)})
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / "e"), {"big": np.zeros(bench.DUMP_MAX_BYTES // 8 + 1)})
+    assert not (tmp_path / "e").exists()

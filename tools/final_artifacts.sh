@@ -13,7 +13,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 part=${1:-a}
 stats() {   # stats NAME -- bench args: rocprofv3 --kernel-trace --stats of a bench command -> $out/NAME_kernel_stats.csv + the line
   local name=$1; shift
-  rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -- python3 bench.py "$@" > $out/bench_${name}_under_rocprof.json 2> $out/prof_$name.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -- python3 bench.py --full "$@" > $out/bench_${name}_under_rocprof.json 2> $out/prof_$name.err
   cp $(find $out/prof -name "*kernel_stats.csv" | head -1) $out/${name}_kernel_stats.csv; rm -rf $out/prof
 }
 if [[ $part == *p* ]]; then
@@ -27,15 +27,15 @@ for w in lml train gram c4; do bash tools/pmc_workload.sh $w $out/pmc_$w > $out/
 fi
 if [[ $part == *a* ]]; then
 python -c "import __graft_entry__ as g; g.build(); g.smoke()" > $out/smoke.log 2>&1; echo "smoke rc=$?"; tail -2 $out/smoke.log
-python bench.py > $out/bench_default.json 2> $out/bench_default.err; echo "bench rc=$?"
+python bench.py --full > $out/bench_default.json 2> $out/bench_default.err; echo "bench rc=$?"
 stats bench --no-cpu-baseline --no-extras
-python bench.py --workload lml > $out/bench_lml.json 2> $out/bench_lml.err; echo "lml rc=$?"
+python bench.py --full --workload lml > $out/bench_lml.json 2> $out/bench_lml.err; echo "lml rc=$?"
 stats lml --workload lml --no-cpu-baseline
-python bench.py --workload train > $out/bench_train.json 2> $out/bench_train.err; echo "train rc=$?"
+python bench.py --full --workload train > $out/bench_train.json 2> $out/bench_train.err; echo "train rc=$?"
 stats train --workload train --no-cpu-baseline --steps 1 --warmup 1
-python bench.py --workload c4 --steps 5 > $out/bench_c4.json 2> $out/bench_c4.err; echo "c4 rc=$?"
-python bench.py --workload gram --steps 6 > $out/bench_gram.json 2> $out/bench_gram.err; echo "gram rc=$?"
-python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $out/bench_torchrun_1rank.json 2> $out/bench_torchrun_1rank.err; echo "torchrun rc=$?"
+python bench.py --full --workload c4 --steps 5 > $out/bench_c4.json 2> $out/bench_c4.err; echo "c4 rc=$?"
+python bench.py --full --workload gram --steps 6 > $out/bench_gram.json 2> $out/bench_gram.err; echo "gram rc=$?"
+python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --steps 3 --warmup 1 --full --no-cpu-baseline --no-extras > $out/bench_torchrun_1rank.json 2> $out/bench_torchrun_1rank.err; echo "torchrun rc=$?"
 fi
 if [[ $part == *b* ]]; then
 (echo "# tools/exp_ptile.py: gpk_potrf by the recursive launch chain (ptile = 0) against the one-launch tile factorisation, same matrix, same box"; python tools/exp_ptile.py 512 1024 2048 4096 5120 8192 10112 16384 32768 2>&1 | grep N=) > $out/ptile_ab.log; cat $out/ptile_ab.log

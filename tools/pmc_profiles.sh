@@ -7,7 +7,7 @@
 # (counter passes use --kernel-trace only, as the GPU pool requires; the program after "--" is python3 itself)
 out=${1:-gpurun_out/prof2}; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-B="python3 bench.py --no-cpu-baseline --no-extras"
+B="python3 bench.py --full --no-cpu-baseline --no-extras"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -- $B --steps 10 --warmup 3 > $out/bench_under_rocprof.json 2> $out/prof.err
 cp $(find $out/prof -name "*kernel_stats.csv" | head -1) $out/kernel_stats.csv && echo "kernel stats ok"
 for c in FETCH_SIZE WRITE_SIZE; do
@@ -26,7 +26,7 @@ for c in ("FETCH_SIZE", "WRITE_SIZE"):
 names = sorted(res["FETCH_SIZE"][0], key=lambda k: -res["FETCH_SIZE"][0][k])[:16]
 with open(out + "/pmc_hbm_traffic.md", "w") as fo:
     fo.write("`rocprofv3 --kernel-trace --pmc FETCH_SIZE` and `--pmc WRITE_SIZE` (two separate passes) over "
-             "`python3 bench.py --no-cpu-baseline --no-extras --steps 2 --warmup 0`; values in KB as rocprofv3 reports them; "
+             "`python3 bench.py --full --no-cpu-baseline --no-extras --steps 2 --warmup 0`; values in KB as rocprofv3 reports them; "
              "corrected bytes = (2 x FETCH_SIZE + WRITE_SIZE) x 1024 (gfx950 FETCH_SIZE counts 64 B per 128-B request on "
              "16-byte-per-lane streams: MI355X_MICROARCH.md, HBM section).\n\n")
     fo.write("| kernel | calls | FETCH_SIZE max/launch (KB) | WRITE_SIZE max/launch (KB) | corrected bytes, largest launch |\n|---|---|---|---|---|\n")

@@ -1,13 +1,13 @@
 #!/bin/bash
 # Fabric/HBM bytes per STEP of a bench.py workload from rocprofv3 counter passes (tools/pmc_workload.sh WORKLOAD [outdir] [extra bench args]):
 # FETCH_SIZE and WRITE_SIZE (separate passes, --kernel-trace only as the GPU pool requires) over
-#     python3 bench.py --workload W --no-cpu-baseline --warmup 0 --steps S        for S = 1 and S = 3;
+#     python3 bench.py --full --workload W --no-cpu-baseline --warmup 0 --steps S        for S = 1 and S = 3;
 # bytes per step = (total at S = 3 - total at S = 1) / 2 - the set-up launches cancel -, corrected as MI355X_MICROARCH.md (HBM section)
 # prescribes: (2 x FETCH_SIZE + WRITE_SIZE) x 1024.  A third pass (S = 1) reads SQ_VALU_MFMA_BUSY_CYCLES / GRBM_GUI_ACTIVE and
 # TCC_HIT / TCC_MISS per kernel.  Writes <outdir>/pmc_<W>.md and <outdir>/pmc_<W>.json (an entry for profiles/pmc_traffic.json).
 w=${1:-lml}; out=${2:-gpurun_out/pmc_$w}; shift 2; extra="$@"; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-B="python3 bench.py --workload $w --no-cpu-baseline --warmup 0 $extra"
+B="python3 bench.py --full --workload $w --no-cpu-baseline --warmup 0 $extra"
 for c in FETCH_SIZE WRITE_SIZE; do
   for s in 1 3; do
     rocprofv3 --kernel-trace --pmc $c --output-format csv -d $out/${c}_$s -- $B --steps $s > $out/${c}_$s.json 2> $out/${c}_$s.err || { echo "pass $c S=$s failed"; tail -3 $out/${c}_$s.err; }
@@ -39,7 +39,7 @@ rows = sorted(per.items(), key=lambda kv: -(2 * kv[1][0] + kv[1][1]))
 step_bytes = sum((2 * f + wr) * 1024 for _, (f, wr, _) in rows)
 line = json.loads(open(f"{out}/FETCH_SIZE_3.json").read().strip().splitlines()[-1])
 with open(f"{out}/pmc_{w}.md", "w") as fo:
-    fo.write(f"`rocprofv3 --kernel-trace --pmc <counter>` over `python3 bench.py --workload {w} --no-cpu-baseline --warmup 0 {extra} --steps S` "
+    fo.write(f"`rocprofv3 --kernel-trace --pmc <counter>` over `python3 bench.py --full --workload {w} --no-cpu-baseline --warmup 0 {extra} --steps S` "
              f"(one pass per counter; S = 1 and S = 3: per-step figures are (S = 3 minus S = 1) / 2, so the set-up launches cancel).  "
              f"Corrected bytes = (2 x FETCH_SIZE + WRITE_SIZE) x 1024.  Workload: {line['config']['workload']}\n\n"
              f"**bytes per step: {step_bytes:.3e}**\n\n"
