@@ -148,15 +148,17 @@ def log_marginal_likelihood(st: FitState):
     return float(per_out.sum())
 
 
-def lml_gradient(st: FitState, ard=False):
+def lml_gradient(st: FitState, ard=False, with_sf2=False):
     """Gradient of the LML with respect to log-hyper-parameters
     (`sklearn/_gpr.py:615-647`; kernel gradients `sklearn/kernels.py:1571-1580`,
-    WhiteKernel `:1403-1408`).
+    WhiteKernel `:1403-1408`, `ConstantKernel.__call__`).
 
     theta layout (sklearn order for `[C(fixed) *] RBF + WhiteKernel`):
       iso: [log ls, log noise]; ARD: [log ls_0 .. log ls_{D-1}, log noise].
+    with_sf2 (the constant free, `C * RBF + WhiteKernel`): [log sf2] in front of that.
     d K / d log ls_d   = K_rbf * (x_id - x_jd)^2 / ls_d^2   (iso: summed over d)
     d K / d log noise  = noise * I
+    d K / d log sf2    = K_rbf
     grad_p = 1/2 sum_ij (sum_k alpha_ik alpha_jk - P * Kinv_ij) dK_ij/dtheta_p
     """
     X, L, alpha = st.X, st.L, st.alpha
@@ -170,9 +172,10 @@ def lml_gradient(st: FitState, ard=False):
         diff = A[:, d][:, None] - A[:, d][None, :]
         g_ls[d] = 0.5 * np.sum(Q * Krbf * diff * diff)
     g_noise = 0.5 * st.noise * np.trace(Q)
-    if ard:
-        return np.concatenate([g_ls, [g_noise]])
-    return np.array([g_ls.sum(), g_noise])
+    g = np.concatenate([g_ls, [g_noise]]) if ard else np.array([g_ls.sum(), g_noise])
+    if with_sf2:
+        g = np.concatenate([[0.5 * np.sum(Q * Krbf)], g])
+    return g
 
 
 # --------------------------------------------------------------------------------------
@@ -274,6 +277,25 @@ class PackageGPOracle:
         quad = sum(np.dot(self.Y[:, i], self.alpha[:, i]) for i in range(self.Y.shape[1]))
         n = len(self.X)
         return float(-0.5 * (log_det + quad + n * self.Y.shape[1] * np.log(2 * np.pi)))
+
+    def lml_gradient(self):
+        """Gradient of `log_marginal_likelihood` with respect to [log ls, log sf2, log noise] (the order of the
+        package optimiser's parameters, `:293-302`).  The log-determinant counts ONCE (not once per output, as in
+        scikit-learn's multi-output LML), so
+
+            Q = sum_p alpha_p alpha_p^T - K^-1
+            g_ls = 1/2 sum Q o K_rbf o d2 / ls^2,  g_sf2 = 1/2 sum Q o K_rbf,  g_noise = 1/2 noise tr Q
+
+        with d2 the kernel's own expanded, floored squared distance (`:38-39`)."""
+        N = len(self.X)
+        Kinv = cho_solve((self.L, True), np.eye(N))
+        Q = self.alpha @ self.alpha.T - Kinv
+        sq = np.sum(self.X ** 2, 1)
+        d2 = np.maximum(sq.reshape(-1, 1) + sq - 2 * np.dot(self.X, self.X.T), 0)
+        Krbf = self.kernel(self.X, self.X)
+        QK = Q * Krbf
+        return np.array([0.5 * np.sum(QK * d2) / self.length_scale ** 2, 0.5 * np.sum(QK),
+                         0.5 * self.noise_variance * np.trace(Q)])
 
 
 # --------------------------------------------------------------------------------------

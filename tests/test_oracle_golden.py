@@ -108,3 +108,108 @@ def test_c2_synthetic(ka):
     mean, std = O.predict(st, Xq, return_std=True)
     assert relerr(mean, ka["c2_mean"]) < 1e-9
     assert relerr(std, ka["c2_std"]) < 1e-8
+
+
+# ---- LML gradients: the sf2 slot of scikit-learn's theta and the package GP's own objective ------------------------------
+@pytest.fixture(scope="module")
+def grad_ref():
+    import os
+    from conftest import GOLDEN
+    d = np.load(os.path.join(GOLDEN, "grad_ref.npz"))
+    return {k: d[k] for k in d.files}
+
+
+def _fd4(f, x0, h):
+    """4th-order central difference of f along every coordinate of x0."""
+    g = np.empty(x0.size)
+    for i in range(x0.size):
+        e = np.zeros(x0.size)
+        e[i] = h
+        g[i] = (-f(x0 + 2 * e) + 8 * f(x0 + e) - 8 * f(x0 - e) + f(x0 - 2 * e)) / (12 * h)
+    return g
+
+
+def _sk_theta_split(theta, D, ard):
+    """scikit-learn theta of C * RBF + White -> (sf2, ls, noise)."""
+    t = np.exp(theta)
+    return t[0], (t[1:1 + D] if ard else t[1]), t[-1]
+
+
+@pytest.mark.parametrize("P", [1, 3])
+@pytest.mark.parametrize("ard", [False, True])
+def test_lml_gradient_with_sf2_finite_difference(P, ard):
+    rng = np.random.default_rng(40 + P + 10 * ard)
+    N, D = 150, 4
+    X = rng.standard_normal((N, D))
+    Y = np.sin(X @ rng.standard_normal((D, P))) + 0.1 * rng.standard_normal((N, P))
+    ls = 1.2 * (1.0 + 0.2 * np.arange(D)) if ard else 1.3
+    theta = np.log(np.concatenate([[0.7], np.atleast_1d(ls), [0.04]]))
+
+    def lml(th):
+        sf2, l_, noise = _sk_theta_split(th, D, ard)
+        return O.log_marginal_likelihood(O.fit_fixed(X, Y, l_, sf2, noise, 1e-4))
+
+    sf2, l_, noise = _sk_theta_split(theta, D, ard)
+    st = O.fit_fixed(X, Y, l_, sf2, noise, 1e-4)
+    an = O.lml_gradient(st, ard=ard, with_sf2=True)
+    assert an.shape == theta.shape
+    fd = _fd4(lml, theta, 1e-3)
+    assert np.max(np.abs(an - fd)) < 1e-7 * np.max(np.abs(an)), (an, fd)
+    # without the sf2 slot: the same numbers, leading term dropped
+    assert np.array_equal(O.lml_gradient(st, ard=ard), an[1:])
+
+
+@pytest.mark.parametrize("P", [1, 3])
+def test_package_oracle_lml_gradient_finite_difference(P):
+    rng = np.random.default_rng(70 + P)
+    N, D = 120, 5
+    X = rng.standard_normal((N, D))
+    Y = np.sin(X @ rng.standard_normal((D, P))) + 0.1 * rng.standard_normal((N, P))
+    theta = np.log([1.4, 0.8, 0.05])
+
+    def lml(th):
+        return O.PackageGPOracle(*np.exp(th)).fit(X, Y).log_marginal_likelihood()
+
+    an = O.PackageGPOracle(*np.exp(theta)).fit(X, Y).lml_gradient()
+    fd = _fd4(lml, theta, 1e-3)
+    assert np.max(np.abs(an - fd)) < 1e-7 * np.max(np.abs(an)), (an, fd)
+
+
+@pytest.mark.parametrize("P", [1, 3])
+@pytest.mark.parametrize("ard", [0, 1])
+def test_lml_gradient_with_sf2_against_sklearn(csv_data, grad_ref, ard, P):
+    rows = grad_ref["sk_rows"]
+    X = csv_data["X10"][rows, :9]
+    Y = csv_data["Y6"][rows, 3:3 + P]
+    tag = f"ard{ard}_P{P}"
+    for th, lml, grad in zip(grad_ref[f"sk_theta_{tag}"], grad_ref[f"sk_lml_{tag}"], grad_ref[f"sk_grad_{tag}"]):
+        sf2, ls, noise = _sk_theta_split(th, 9, ard)
+        st = O.fit_fixed(X, Y, ls, sf2, noise, float(grad_ref["sk_alpha"]))
+        assert abs(O.log_marginal_likelihood(st) - lml) < TOL * abs(lml)
+        assert relerr(O.lml_gradient(st, ard=bool(ard), with_sf2=True), grad) < 1e-8
+
+
+def _pk_data(csv_data, N, P):
+    """The rows tests/golden/make_golden_grad.py gave the reference's package GP."""
+    if P == 12:
+        X, Y, _ = O.synthetic_problem(N, 1, D=9, P=12)
+        return X, Y
+    return csv_data["X10"][:N, :9], csv_data["Y6"][:N, 3:3 + P]
+
+
+def _pk_reference_fd(grad_ref, N, P):
+    """The reference's own 4th-order central difference of its package LML, in [log ls, log sf2, log noise]."""
+    f = grad_ref[f"pk_lml_P{P}_N{N}"]
+    assert list(grad_ref["pk_ks"]) == [-2, -1, 1, 2]
+    return (f[:, 0] - 8 * f[:, 1] + 8 * f[:, 2] - f[:, 3]) / (12 * float(grad_ref["pk_h"]))
+
+
+@pytest.mark.parametrize("P", [1, 3, 12])
+@pytest.mark.parametrize("N", [120, 257, 1000])
+def test_package_oracle_lml_gradient_against_reference(csv_data, grad_ref, N, P):
+    X, Y = _pk_data(csv_data, N, P)
+    g = O.PackageGPOracle(*np.exp(grad_ref["pk_theta0"])).fit(X, Y)
+    lml0 = float(grad_ref[f"pk_lml0_P{P}_N{N}"])
+    assert abs(g.log_marginal_likelihood() - lml0) < TOL * abs(lml0)
+    an, fd = g.lml_gradient(), _pk_reference_fd(grad_ref, N, P)
+    assert np.max(np.abs(an - fd)) < 1e-6 * np.linalg.norm(an), (an, fd)

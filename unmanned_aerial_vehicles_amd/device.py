@@ -270,8 +270,13 @@ class DeviceGP:
                                           out.ctypes.data_as(_lib._dp)))
         return out[0], out[1:]
 
-    def lml_grad(self, noise):
-        """K6b: [dLML/dlog ls_d ..., dLML/dlog noise, dLML/dlog sf2] at the current factor/alpha."""
+    def lml_grad(self, noise, logdet_weight=None):
+        """K6b: [dLML/dlog ls_d ..., dLML/dlog noise, dLML/dlog sf2] at the current factor/alpha.
+
+        The kernel differentiates scikit-learn's multi-output LML, whose log-determinant counts once per output:
+        Q = sum_p alpha_p alpha_p^T - P K^-1.  `logdet_weight` w gives Q = sum_p alpha_p alpha_p^T - w K^-1 instead (the
+        package GP's LML counts it once: w = 1) with the same launch: alpha is scaled by sqrt(P / w), which makes the
+        kernel's Q equal to (P / w) times the wanted one, and the result by w / P."""
         torch = _torch()
         assert self.factored
         if self.D > 16:
@@ -281,13 +286,17 @@ class DeviceGP:
         W = self.inverse_factor(False)
         be = self.be
         g = np.zeros(self.D + 2)
+        ratio = 1.0 if logdet_weight is None else self.P / float(logdet_weight)
+        if not ratio > 0.0:
+            raise ValueError("logdet_weight must be positive")
+        alpha = self.alpha if ratio == 1.0 else self.alpha * float(np.sqrt(ratio))
         with be.lock:
             be.bind_stream()
             be.check(be.lib.gpk_wtw(be.h, _p(W), self.Np, self.Np, _p(self._Kinv), self.Np))
             be.check(be.lib.gpk_lml_grad(be.h, _p(self.X), self.N, self.D, self.ls.ctypes.data_as(_lib._dp),
-                                         self.sf2, float(noise), _p(self.alpha), self.P, _p(self._Kinv), self.Np,
+                                         self.sf2, float(noise), _p(alpha), self.P, _p(self._Kinv), self.Np,
                                          g.ctypes.data_as(_lib._dp)))
-        return g
+        return g if ratio == 1.0 else g / ratio
 
     def lml_eval(self, ls, sf2, diag_add, noise, eval_gradient=True):
         """One optimiser evaluation as one chain with one synchronisation (gpk_lml_eval): K1, K2, W = L^-1, alpha, K6a and -

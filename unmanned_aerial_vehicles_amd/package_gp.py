@@ -207,33 +207,42 @@ class GaussianProcess:
             return -np.inf
 
     # ---- hyper-parameters (gaussian_process.py:267-324) ----------------------------------------------
+    def _nll_and_grad(self, params, use_gradient=True):
+        """The optimiser's objective at log(length_scale, signal_variance, noise_variance): installs the trial
+        hyper-parameters and refits (as the reference does), returns -LML and - with `use_gradient` - its gradient in the
+        same order.  Non-finite likelihood restores the previous values and returns 1e6 (with a zero gradient).
+
+        The package LML counts the log-determinant once whatever `output_dim` (gaussian_process.py:250-261), so the
+        gradient is K6b's with K^-1 weighted by 1, not by the number of outputs (DeviceGP.lml_grad's logdet_weight)."""
+        D = self.X_train.shape[1]
+        old = (self.kernel.length_scale, self.kernel.signal_variance, self.noise_variance)
+        self.kernel.length_scale = float(np.exp(params[0]))
+        self.kernel.signal_variance = float(np.exp(params[1]))
+        self.noise_variance = float(np.exp(params[2]))
+        noise = self.noise_variance
+        self.fit()
+        nll = -self.log_marginal_likelihood()
+        if not np.isfinite(nll):
+            self.kernel.length_scale, self.kernel.signal_variance, self.noise_variance = old
+            return (1e6, np.zeros(3)) if use_gradient else 1e6
+        if not use_gradient:
+            return float(nll)
+        with self._swap:
+            model = self._model
+        g = model[0].lml_grad(noise, logdet_weight=1)     # d LML / d log [ls_d..., noise, sf2]
+        return float(nll), -np.array([np.sum(g[:D]), g[D + 1], g[D]])
+
     def optimize_hyperparameters(self, use_gradient=True):
         """L-BFGS-B over log(length_scale, signal_variance, noise_variance), maxiter 50.  As in the
         reference every objective evaluation installs the trial hyper-parameters and refits (so after an
         unsuccessful run the model sits at the last trial point); non-finite likelihood restores the
         previous values and returns 1e6.  The reference differentiates numerically; here the analytic
-        gradient from the fused K6b kernel is used unless `use_gradient=False`."""
+        gradient from the fused K6b kernel is used unless `use_gradient=False` (`_nll_and_grad`)."""
         if len(self.X_train) < 10:
             return
-        D = self.X_train.shape[1]
 
         def objective(params):
-            old = (self.kernel.length_scale, self.kernel.signal_variance, self.noise_variance)
-            self.kernel.length_scale = float(np.exp(params[0]))
-            self.kernel.signal_variance = float(np.exp(params[1]))
-            self.noise_variance = float(np.exp(params[2]))
-            noise = self.noise_variance
-            self.fit()
-            nll = -self.log_marginal_likelihood()
-            if not np.isfinite(nll):
-                self.kernel.length_scale, self.kernel.signal_variance, self.noise_variance = old
-                return (1e6, np.zeros(3)) if use_gradient else 1e6
-            if not use_gradient:
-                return float(nll)
-            with self._swap:
-                model = self._model
-            g = model[0].lml_grad(noise)                  # d LML / d log [ls_d..., noise, sf2]
-            return float(nll), -np.array([np.sum(g[:D]), g[D + 1], g[D]])
+            return self._nll_and_grad(params, use_gradient)
 
         x0 = np.log([self.kernel.length_scale, self.kernel.signal_variance, self.noise_variance])
         try:
