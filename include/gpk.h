@@ -64,7 +64,8 @@ GPK_API int64_t gpk_padded(int64_t n);
  * gpk_timing(h, 1): from now on the handle brackets its dominant launches with HIP events recorded on the
  * handle's stream - tag GPK_TIMED_K5: the one GEMM launch of gpk_predict_var_inv / gpk_predict_var_inv_split
  * (V = W K*^T with the column-norm epilogue); tag GPK_TIMED_GRAM: the Gram kernel of gpk_gram; tag GPK_TIMED_GRAD: the
- * streaming pass of gpk_lml_grad over K^-1; tag GPK_TIMED_POTRF: the launches of one gpk_potrf - and keeps the
+ * streaming pass of gpk_lml_grad over K^-1; tag GPK_TIMED_POTRF: the launches of one gpk_potrf; tag GPK_TIMED_COV: the
+ * symmetric product (K(Xq, Xq) + noise I - V^T V) of gpk_predict_cov_inv / gpk_predict_cov - and keeps the
  * last 64 pairs.  gpk_kernel_times synchronises the stream and returns the elapsed milliseconds of the bracketed
  * launches with that tag still in the ring, oldest first (*n_out of them, at most max_n).  bench.py uses it to
  * report the dominant kernel's duration over exactly the timed steps; rocprofv3's kernel trace of the same run is
@@ -93,7 +94,7 @@ GPK_API int64_t gpk_padded(int64_t n);
  * (debugging aid, tools/exp_ptile_trace.py).                                                                          */
 GPK_API int gpk_set_option(gpk_handle h, const char* name, int value);
 GPK_API int gpk_set_option_str(gpk_handle h, const char* name, const char* value);
-enum { GPK_TIMED_K5 = 1, GPK_TIMED_GRAM = 2, GPK_TIMED_GRAD = 3, GPK_TIMED_POTRF = 4 };
+enum { GPK_TIMED_K5 = 1, GPK_TIMED_GRAM = 2, GPK_TIMED_GRAD = 3, GPK_TIMED_POTRF = 4, GPK_TIMED_COV = 5 };
 GPK_API int gpk_timing(gpk_handle h, int enable);
 GPK_API int gpk_kernel_times(gpk_handle h, int tag, double* ms, int max_n, int* n_out);
 
@@ -341,6 +342,35 @@ GPK_API int gpk_predict_var_inv(gpk_handle h, int dtype, const void* X, int64_t 
                         double sf2, const void* W, int64_t Np, int64_t ldw, const void* Xq, int64_t M,
                         double kss, double floor, void* work, double* var);
 
+/* ---- K7: posterior covariance --------------------------------------------------------------------------------------
+ * cov (dev, Mp x ldc fp64, Mp = gpk_padded(M), ldc >= Mp) <- K(Xq, Xq) + noise I - V^T V, V = L^-1 K*^T, in units of the
+ * normalised targets (the caller scales output p by y_std[p]^2) and never clipped.  K(Xq, Xq) by exact differences of the
+ * queries divided by the length-scales; noise (the WhiteKernel level) only where the row index equals the column index, as
+ * WhiteKernel's k(X) does - never on duplicate rows.  Rows / columns >= M of the padded block are 0.  Symmetric bit for bit:
+ * ONE tile GEMM over the lower 128 x 128 tiles whose epilogue stores every tile and its transpose (diagonal tiles: the lower
+ * half, mirrored).  work: dev double[Np * Mp] (V); the handle's scratch holds the rest.  fp64 only (dtype = GPK_F64), D <= 16.
+ * gpk_predict_cov_inv: V = W K*^T with the explicit inverse factor W (dev Np x ldw, gpk_trtri): N^2 M + N M^2 flops.
+ * gpk_predict_cov: V by the blocked triangular solve with L and winv (gpk_potrf) - for models whose inverse factor is not formed.
+ * Replaces: sklearn/gaussian_process/_gpr.py:454-464 (solve_triangular, kernel_(X) - V.T @ V).                              */
+GPK_API int gpk_predict_cov_inv(gpk_handle h, int dtype, const void* X, int64_t N, int D, const double* ls, double sf2,
+                                const void* W, int64_t Np, int64_t ldw, const void* Xq, int64_t M, double noise, void* work,
+                                double* cov, int64_t ldc);
+GPK_API int gpk_predict_cov(gpk_handle h, int dtype, const void* X, int64_t N, int D, const double* ls, double sf2,
+                            const void* L, int64_t Np, int64_t ldl, const void* winv, const void* Xq, int64_t M, double noise,
+                            void* work, double* cov, int64_t ldc);
+/* One-call mean + covariance for small batches (fp64), the covariance analogue of gpk_predict_host: host queries in
+ * (M x D), host mean (M x P, un-normalised) and cov (M x M, normalised-target units) out, one synchronisation.  W: the
+ * inverse factor (dev Np x ldw).  Up to 32 queries (D, P <= 16, N <= 16384): two launches - small_cross_mean_kernel and
+ * small_cov_kernel (16 rows of W per workgroup on the fp64 MFMA, each workgroup's 32 x 32 share of V^T V added in a fixed
+ * two-level order: bit-identical from run to run, no floating-point atomics); 33 .. GPK_HOST_MAX_M queries: the fused mean
+ * and gpk_predict_cov_inv inside the same call.
+ * Replaces: sklearn/gaussian_process/_gpr.py:441-469 (predict(X, return_cov=True) before the un-normalisation of the
+ * covariance) for the GP-MPC horizon of src/px4/mpc.py:1490-1506.                                                           */
+GPK_API int gpk_predict_host_cov(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P,
+                                 const double* ls, double sf2, const double* y_mean, const double* y_std, const double* W,
+                                 int64_t Np, int64_t ldw, double noise, const double* Xq_host, int64_t M, double* mean_host,
+                                 double* cov_host);
+
 /* ---- K6a: log-marginal-likelihood terms -----------------------------------------------------
  * terms[0] = sum_{i<N} log L[i][i]; terms[1 + p] = sum_i Y[i][p] * alpha[i][p]  (host doubles).
  * Synchronises.  Replaces: sklearn/gaussian_process/_gpr.py:609-613; gaussian_process.py:250-261. */
@@ -431,6 +461,12 @@ GPK_API int gpk_export(gpk_handle h, int64_t* N, int* D, int* P, double* L, doub
 GPK_API int gpk_import(gpk_handle h, const double* X, int64_t N, int D, const double* L, const double* alpha, int P,
                const double* ls, int n_ls, double sf2, double noise, const double* y_mean, const double* y_std);
 GPK_API int gpk_model_release(gpk_handle h);
+/* gpk_predict_model_cov: posterior mean and covariance of the model of gpk_fit / gpk_import, fp64 host buffers: Xq (M x D),
+ * mean (M x P, un-normalised), cov (P x M x M: output p's block is y_std[p]^2 Sigma, Sigma = K(Xq, Xq) + noise I - V^T V with
+ * the model's WhiteKernel level as noise, not clipped).  Up to GPK_HOST_MAX_M queries one call of gpk_predict_host_cov; more
+ * (<= 16384) the fused mean and gpk_predict_cov_inv.  Forms the inverse factor if the model does not hold it yet.
+ * Replaces: GaussianProcessRegressor.predict(X, return_cov=True), sklearn/gaussian_process/_gpr.py:441-469.             */
+GPK_API int gpk_predict_model_cov(gpk_handle h, const double* Xq, int64_t M, double* mean, double* cov);
 
 /* ---- composite calls for B (<= GPK_MAX_BATCH) single-output models on shared inputs ----------------------------
  * The per-axis layout of src/px4/gp_trainer.py:139-179 (one scalar GP per residual component, each with its own ARD

@@ -1,0 +1,102 @@
+"""Timings of the posterior covariance (predict(X, return_cov=True)) against the variance path it extends.
+
+    python tools/exp_cov.py [--quick]
+
+1. Large route: gpk_predict_cov_inv (V = W K*^T, then the symmetric product) against gpk_predict_var_inv (the fp64
+   inverse-variance launch) for the same M = 4096 queries at N = 16 384 and 65 536; the symmetric product alone (event
+   bracket GPK_TIMED_COV) and its rate on its N M^2 flops.
+2. The MPC horizon: 25 rows at N = 1000, predict(return_cov=True) (mean + cov, one C call) against today's
+   predict(return_std=True) (mean + var, one C call), wall time per call.
+Medians over the repetitions; CUDA events around the device calls, perf_counter around the estimator calls."""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def dev_ms(fn, reps):
+    import torch
+    out = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        out.append(e0.elapsed_time(e1))
+    return float(np.median(out))
+
+
+def large(N, M, reps):
+    import torch
+    from unmanned_aerial_vehicles_amd import RBF, GaussianProcessRegressor, WhiteKernel
+    rng = np.random.default_rng(N)
+    D = 10
+    X = rng.standard_normal((N, D))
+    y = np.sin(X @ rng.standard_normal(D)) + 0.1 * rng.standard_normal(N)
+    gp = GaussianProcessRegressor(kernel=RBF(2.0) + WhiteKernel(0.1), alpha=1e-4, normalize_y=True, optimizer=None,
+                                  device=0).fit(X, y)
+    dev = gp._dev
+    dev.inverse_factor(False)
+    q = dev._as_queries(rng.standard_normal((M, D)), torch.float64)
+    kss, noise = 1.1, 0.1
+    dev_ms(lambda: dev.predict_var_dev(q, kss, 0.0, "float64", "inverse"), 2)
+    t_var = dev_ms(lambda: dev.predict_var_dev(q, kss, 0.0, "float64", "inverse"), reps)
+    dev_ms(lambda: dev.predict_cov_dev(q, noise, "inverse"), 2)
+    t_cov = dev_ms(lambda: dev.predict_cov_dev(q, noise, "inverse"), reps)
+    dev.timing(True)
+    for _ in range(reps):
+        dev.predict_cov_dev(q, noise, "inverse")
+    from unmanned_aerial_vehicles_amd import _lib
+    t_sym = float(np.median(dev.kernel_times(_lib.GPK_TIMED_COV)))
+    dev.timing(False)
+    Np, Mp = dev.Np, (M + 127) // 128 * 128
+    flops_sym = Np * Mp * (Mp + 128)             # lower tiles incl. the diagonal ones: Np Mp^2 (1 + 128 / Mp) flops
+    tf = flops_sym / (t_sym * 1e-3) / 1e12
+    print(f"N = {N:6d} M = {M}: var_inv {t_var:8.2f} ms  cov_inv {t_cov:8.2f} ms  ratio {t_cov / t_var:5.3f}  "
+          f"symmetric product {t_sym:7.2f} ms = {tf:5.1f} TFLOP/s on its N M^2 flops", flush=True)
+    del gp, dev
+    torch.cuda.empty_cache()
+
+
+def horizon(N, M, reps):
+    from unmanned_aerial_vehicles_amd import RBF, GaussianProcessRegressor, WhiteKernel
+    d = np.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "csv_170501.npz"))
+    X, Y = d["X10"][:N], d["Y6"][:N]
+    gp = GaussianProcessRegressor(kernel=RBF(0.5) + WhiteKernel(0.1), alpha=1e-4, normalize_y=True, optimizer=None,
+                                  device=0).fit(X, Y)
+    Xq = np.ascontiguousarray(d["Xq10"][:M])
+
+    def wall(fn):
+        for _ in range(20):
+            fn()
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            fn()
+            ts.append(time.perf_counter() - t0)
+        return 1e6 * float(np.median(ts)), 1e6 * float(np.percentile(ts, 99))
+
+    a = wall(lambda: gp.predict(Xq, return_std=True))
+    b = wall(lambda: gp.predict(Xq, return_cov=True))
+    print(f"N = {N} rows = {M}: predict() mean+std {a[0]:7.1f} us (p99 {a[1]:7.1f})   mean+cov {b[0]:7.1f} us "
+          f"(p99 {b[1]:7.1f})   ratio {b[0] / a[0]:5.3f}", flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--quick", action="store_true", help="N = 16 384 only, fewer repetitions")
+    a = ap.parse_args()
+    import torch
+    print(f"# tools/exp_cov.py on {torch.cuda.get_device_name(0)}; fp64; D = 10", flush=True)
+    horizon(1000, 25, 200 if a.quick else 1000)
+    for N in ((16384,) if a.quick else (16384, 65536)):
+        large(N, 4096, 3 if a.quick else 5)
+
+
+if __name__ == "__main__":
+    main()

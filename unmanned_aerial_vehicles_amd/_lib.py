@@ -17,6 +17,7 @@ GPK_OK, GPK_NOT_PD, GPK_BAD_ARG, GPK_HIP_ERROR = 0, 1, 2, 3
 GPK_TILE, GPK_MAX_D, GPK_MAX_P = 128, 64, 16
 GPK_HOST_MAX_M = 4096
 GPK_TIMED_K5, GPK_TIMED_GRAM, GPK_TIMED_GRAD, GPK_TIMED_POTRF = 1, 2, 3, 4
+GPK_TIMED_COV = 5
 
 _vp, _i64, _int, _dbl = C.c_void_p, C.c_int64, C.c_int, C.c_double
 _dp = C.POINTER(C.c_double)
@@ -82,6 +83,13 @@ SIGNATURES = {
     "gpk_tril_to_f32": (_int, [_vp, _vp, _i64, _i64, _vp, _i64]),
     "gpk_predict_var_inv": (_int, [_vp, _int, _vp, _i64, _int, _dp, _dbl, _vp, _i64, _i64, _vp, _i64, _dbl, _dbl,
                                    _vp, _vp]),
+    "gpk_predict_cov_inv": (_int, [_vp, _int, _vp, _i64, _int, _dp, _dbl, _vp, _i64, _i64, _vp, _i64, _dbl, _vp, _vp,
+                                   _i64]),
+    "gpk_predict_cov": (_int, [_vp, _int, _vp, _i64, _int, _dp, _dbl, _vp, _i64, _i64, _vp, _vp, _i64, _dbl, _vp, _vp,
+                               _i64]),
+    "gpk_predict_host_cov": (_int, [_vp, _vp, _vp, _i64, _int, _int, _vp, _dbl, _vp, _vp, _vp, _i64, _i64, _dbl, _vp, _i64,
+                                    _vp, _vp]),
+    "gpk_predict_model_cov": (_int, [_vp, _dp, _i64, _dp, _dp]),
     "gpk_lml_terms": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _int, _dp]),
     "gpk_potri": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),
     "gpk_lml_grad": (_int, [_vp, _vp, _i64, _int, _dp, _dbl, _dbl, _vp, _int, _vp, _i64, _dp]),

@@ -39,6 +39,7 @@ extern "C" void gpk_destroy(gpk_handle h) {
   if (h->scratch) (void)hipFree(h->scratch);
   if (h->d_info) (void)hipFree(h->d_info);
   if (h->d_count) (void)hipFree(h->d_count);
+  if (h->d_cov_count) (void)hipFree(h->d_cov_count);
   if (h->d_ptile) (void)hipFree(h->d_ptile);
   if (h->d_ptile_list) (void)hipFree(h->d_ptile_list);
   if (h->h_small) (void)hipHostFree(h->h_small);
@@ -257,6 +258,8 @@ static int serve_reserve(gpk_handle h, size_t host_need, size_t dev_need) {
   }
   return GPK_OK;
 }
+
+int gpk_serve_reserve(gpk_handle h, size_t host_need, size_t dev_need) { return serve_reserve(h, host_need, dev_need); }
 
 extern "C" int gpk_predict_host(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P,
                                 const double* ls, double sf2, const double* y_mean, const double* y_std,

@@ -11,6 +11,7 @@
 // interleaved over the 8 XCDs; small grids (which cannot fill 256 CUs with 128 x 128 tiles) use
 // 64 x 64 tiles for 4x the parallelism.
 #include "gpk_internal.h"
+#include "gpk_math.h"
 
 namespace {
 
@@ -45,6 +46,10 @@ struct KParams {
   // leading dimension ldc (C lies inside it), as the bits of a non-negative float (atomicMax)
   unsigned* amax;
   const char* amax_base;
+  // epilogue 3 (posterior covariance): cq = the queries divided by the length-scales (cm x cd, fp64)
+  const double* cq;
+  double csf2, cnoise;
+  int cd, cm;
 };
 
 typedef unsigned int V16 __attribute__((ext_vector_type(4)));   // one 16-byte register quad
@@ -318,6 +323,44 @@ __device__ __forceinline__ void sumsq_acc(char* lds, double* __restrict__ out, l
   }
 }
 
+// Epilogue 3 (posterior covariance, C = K(Xq, Xq) + noise I - V^T V on the lower tiles of a symmetric product): the prior
+// term of every element is computed here from the scaled queries staged in LDS (uq: the tile's TS rows, then its TS columns,
+// stride 17) by exact differences, as the Gram kernel does; the noise goes on the global diagonal only (WhiteKernel's k(X)).
+// Each element is stored at (row, col) and (col, row).  A diagonal tile stores only its lower half and mirrors it, so the
+// result is bit-exactly symmetric.  Rows / columns >= cm (padding) get -acc, which is 0: V is zero there.
+template <int AB, int NB, int TS>
+__device__ __forceinline__ void cov_store(double* __restrict__ C, long long ldc, int row0, int col0, int row_w, int col_w,
+                                          int lane, const d4 (&acc)[AB][NB], const double* uq, const KParams& p) {
+  const bool diag = row0 == col0;
+#pragma unroll
+  for (int a = 0; a < AB; ++a)
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int rl = row_w + 16 * a + (lane >> 4) + 4 * i;
+        const int cl = col_w + 16 * b + (lane & 15);
+        if (diag && rl < cl) continue;
+        const int row = row0 + rl, col = col0 + cl;
+        double k = 0.0;
+        if (row == col) {
+          if (row < p.cm) k = p.csf2 + p.cnoise;
+        } else if (row < p.cm && col < p.cm) {
+          double d2 = 0.0;
+#pragma unroll
+          for (int d = 0; d < 16; ++d)
+            if (d < p.cd) {
+              const double df = uq[rl * 17 + d] - uq[(TS + cl) * 17 + d];
+              d2 = __builtin_fma(df, df, d2);
+            }
+          k = p.csf2 * gpk_exp_neg(-0.5 * d2);
+        }
+        const double v = k - acc[a][b][i];
+        C[(long long)row * ldc + col] = v;
+        if (row != col) C[(long long)col * ldc + row] = v;
+      }
+}
+
 // accumulator block grid of one wave: (TS/WM) x (TS/2) elements in MFMA blocks
 template <typename T, int WM, int TS> struct AccT;
 template <int WM, int TS> struct AccT<double, WM, TS> {
@@ -565,6 +608,19 @@ __global__ __launch_bounds__(WM * 128, TS == 128 ? WM : 4) void gemm_kernel(KPar
       const long long rowabs = (reinterpret_cast<const char*>(C) - p.amax_base) / (p.ldc * 8) + row0 + row_w;
       if (lane == 0) atomicMax(p.amax + (rowabs >> 7), __float_as_uint(mx));
     }
+  } else if constexpr (EPI == 3) {
+    if constexpr (sizeof(T) == 8) {
+      // the k-loop ended with a barrier: the staging buffers are free for the scaled queries of the tile
+      static_assert(2 * TS * 17 * 8 <= 4 * LDS_OP_BYTES, "epilogue 3: the query images must fit the staging buffers");
+      double* uq = reinterpret_cast<double*>(lds);
+      for (int e = tid; e < 2 * TS * 16; e += NT) {
+        const int s = e / (TS * 16), r = (e >> 4) % TS, d = e & 15;
+        const int g = (s ? col0 : row0) + r;
+        uq[(s * TS + r) * 17 + d] = (d < p.cd && g < p.cm) ? p.cq[(long long)g * p.cd + d] : 0.0;
+      }
+      __syncthreads();
+      cov_store<AB, NB, TS>(C, p.ldc, row0, col0, row_w, col_w, lane, acc, uq, p);
+    }
   } else {
     // the k-loop ended with a barrier: the staging buffers are free for the reduction
     sumsq_acc<AB, NB, WM, TS>(lds, reinterpret_cast<double*>(C), p.ldc, tm, col0, wm, col_w, lane, tid, acc,
@@ -633,6 +689,22 @@ int launch(gpk_handle h, const GemmArgs& g) {
   }
   dim3 grid((unsigned)nblocks, ny), block(WM * 128);
   p.amax = g.amax; p.amax_base = (const char*)g.amax_base;
+  p.cq = g.cov_q; p.csf2 = g.cov_sf2; p.cnoise = g.cov_noise; p.cd = g.cov_d; p.cm = g.cov_m;
+  if (g.epilogue == 3) {
+    if constexpr (sizeof(T) == 8) {
+      if (!g.ta || !g.tb || !g.lower_only || g.m != g.n || !g.cov_q || g.cov_d < 1 || g.cov_d > 16 || g.cov_m > g.m ||
+          h->batch != 1 || g.nbatch > 0) {
+        h->err = "gemm: the covariance epilogue needs ta == tb == 1, lower_only, m == n, 1 <= D <= 16, one problem";
+        return GPK_BAD_ARG;
+      }
+      hipLaunchKernelGGL((gemm_kernel<T, true, true, 3, WM, TS>), grid, block, 0, h->stream, p);
+      GPK_LAUNCH_CHECK(h);
+      return GPK_OK;
+    } else {
+      h->err = "gemm: the covariance epilogue is fp64 only";
+      return GPK_BAD_ARG;
+    }
+  }
   if (g.epilogue == 2) {
     if constexpr (sizeof(T) == 8) {
       if (g.ta || !g.tb || g.beta != 0.0 || !g.amax || !g.amax_base || h->batch != 1) {

@@ -28,6 +28,7 @@ struct gpk_context {
   double* h_small = nullptr;    // 4 KiB of pinned, device-mapped host memory: the reductions' results (LML terms, gradient sums, status words)
   double* d_small = nullptr;    // ... its device address: the kernels write there, the host reads h_small after the synchronisation - no copy command
   unsigned* d_count = nullptr;  // 2 x 8 zero-initialised ticket counters (last-workgroup reductions, gpk_small.hip)
+  unsigned* d_cov_count = nullptr;   // zero-initialised ticket counters of the small covariance reduction (allocated on first use)
   // staging of gpk_predict_host: device block [Xq | mean | var | K* work] and its pinned host mirror [Xq | mean | var]
   void* serve_dev = nullptr;
   size_t serve_dev_bytes = 0;
@@ -208,8 +209,13 @@ struct GemmArgs {
                     // zero beyond each row's own range): the 64 workgroups of a super-tile then run in lockstep
   int epilogue;   // 0: store C;  1: C (fp64, ld = ldc) [tile_row][col] = sum over the tile's rows of (alpha*acc)^2
                   // 2: store C (beta = 0) and atomicMax |(float)C_ij| into amax[128-row block of the matrix at amax_base, ld = ldc]
+                  // 3: fp64, ta = tb = 1, lower_only, m == n: C_ij = C_ji = cov_sf2 exp(-|u_i - u_j|^2 / 2) + cov_noise [i == j] - acc_ij
+                  //    with u = cov_q (cov_m x cov_d, the queries divided by the length-scales); i or j >= cov_m: -acc_ij
   unsigned* amax;
   const void* amax_base;
+  const double* cov_q;
+  double cov_sf2, cov_noise;
+  int cov_d, cov_m;
   // nbatch > 0: that many independent products in one launch (second grid dimension), operand i at base + i * stride
   // (bytes); in the handle's batched mode every problem of the batch runs all of them.
   int nbatch;
@@ -222,6 +228,7 @@ inline GemmArgs gemm_args(const void* A, int64_t lda, int ta, const void* B, int
   g.m = m; g.n = n; g.k = k; g.ta = ta; g.tb = tb; g.alpha = alpha; g.beta = beta;
   g.lower_only = 0; g.kb0 = 0; g.kb_row = 0; g.kb_col = 0; g.ke0 = -1; g.ke_row = 0; g.ke_col = 0; g.epilogue = 0; g.heavy_first = 0; g.k_super = 0;
   g.nbatch = 0; g.sA = 0; g.sB = 0; g.sC = 0; g.amax = nullptr; g.amax_base = nullptr;
+  g.cov_q = nullptr; g.cov_sf2 = 0.0; g.cov_noise = 0.0; g.cov_d = 0; g.cov_m = 0;
   return g;
 }
 int gpk_gemm(gpk_handle h, int dtype, const GemmArgs& g);
@@ -236,6 +243,12 @@ size_t gpk_small_work_doubles(int64_t Np, int B);   // device work area: per mod
 // B models x P outputs each (B > 1: P == 1): mean (B, M, P) and, if var_out, variance (B, M) of M <= 32 fp64 queries
 // shared by the models; Xq / mean_out / var_out may be mapped host memory.  X / alpha / W: B device pointers;
 // ls: B x D; sf2, kss: B; y_mean, y_std: B * P.
+// posterior mean + covariance of M <= 32 queries of one model (small_cross_mean_kernel + small_cov_kernel)
+constexpr int GPK_SMALL_COV_COUNTERS = 128;   // ticket counters of its two-level reduction (h->d_cov_count)
+size_t gpk_small_cov_work_doubles(int64_t Np);
+int gpk_small_cov(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls, double sf2,
+                  const double* y_mean, const double* y_std, const double* W, int64_t Np, int64_t ldw, double noise,
+                  const double* Xq, int64_t M, double* work, double* mean_out, double* cov_out);
 int gpk_small_predict(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D, int P,
                       const double* ls, const double* sf2, const double* y_mean, const double* y_std,
                       const double* const* W, int64_t Np, int64_t ldw, const double* kss, double floor_,

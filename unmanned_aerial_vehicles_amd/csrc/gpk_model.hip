@@ -31,6 +31,8 @@ struct gpk_model {
   // query staging
   void *q = nullptr, *mean = nullptr, *work = nullptr, *work3 = nullptr, *q64 = nullptr;
   double* var = nullptr;
+  void* cov = nullptr;           // gpk_predict_model_cov beyond GPK_HOST_MAX_M queries: Sigma (Mp x Mp)
+  size_t cov_bytes = 0;
   size_t q_bytes = 0, mean_bytes = 0, work_bytes = 0, work3_bytes = 0, var_bytes = 0, q64_bytes = 0;
 };
 
@@ -38,7 +40,7 @@ namespace {
 
 void free_all(gpk_model* m) {
   void* ptrs[] = {m->X, m->Yn, m->K, m->winv, m->W, m->alpha, m->Xf, m->alphaf, m->W3, m->w_scales, m->w_absmax, m->sK, m->sW, m->sKinv, m->sT,
-                  m->swinv, m->salpha, m->q, m->mean, m->work, m->work3, m->q64, m->var};
+                  m->swinv, m->salpha, m->q, m->mean, m->work, m->work3, m->q64, m->var, m->cov};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
 }
@@ -427,6 +429,41 @@ extern "C" int gpk_predict(gpk_handle h, const void* Xq, int64_t M, void* mean, 
       }
     }
     GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));     // the staging blocks are reused by the next panel
+  }
+  return GPK_OK;
+}
+
+extern "C" int gpk_predict_model_cov(gpk_handle h, const double* Xq, int64_t M, double* mean, double* cov) {
+  if (!h) return GPK_BAD_ARG;
+  gpk_model* m = h->model;
+  GPK_REQUIRE(h, m && m->fitted, "predict_model_cov: no model (call gpk_fit or gpk_import first)");
+  GPK_REQUIRE(h, Xq && mean && cov && M >= 1 && M <= 16384, "predict_model_cov: null pointer or M outside [1, 16384]");
+  GPK_CHECK_HIP(h, hipSetDevice(h->device));
+  const int D = m->D, P = m->P;
+  for (int64_t i = 0; i < M * D; ++i) GPK_REQUIRE(h, std::isfinite(Xq[i]), "predict_model_cov: Xq contains NaN or infinity");
+  GPK_TRY(ensure_W(h, m));
+  std::vector<double> sig((size_t)M * M);
+  if (M <= GPK_HOST_MAX_M) {
+    GPK_TRY(gpk_predict_host_cov(h, m->X, m->alpha, m->N, D, P, m->ls, m->sf2, m->y_mean, m->y_std, m->W, m->Np, m->Np,
+                                 m->noise, Xq, M, mean, sig.data()));
+  } else {
+    GPK_TRY(gpk_predict(h, Xq, M, mean, nullptr, GPK_F64, 1));
+    const int64_t Mp = gpk_padded(M);
+    GPK_TRY(grow(h, &m->q, &m->q_bytes, (size_t)M * D * sizeof(double)));
+    GPK_TRY(grow(h, &m->work, &m->work_bytes, (size_t)m->Np * Mp * sizeof(double)));
+    GPK_TRY(grow(h, &m->cov, &m->cov_bytes, (size_t)Mp * Mp * sizeof(double)));
+    GPK_CHECK_HIP(h, hipMemcpyAsync(m->q, Xq, (size_t)M * D * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    GPK_TRY(gpk_predict_cov_inv(h, GPK_F64, m->X, m->N, D, m->ls, m->sf2, m->W, m->Np, m->Np, m->q, M, m->noise, m->work,
+                                (double*)m->cov, Mp));
+    GPK_CHECK_HIP(h, hipMemcpy2DAsync(sig.data(), (size_t)M * sizeof(double), m->cov, (size_t)Mp * sizeof(double),
+                                      (size_t)M * sizeof(double), (size_t)M, hipMemcpyDeviceToHost, h->stream));
+    GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  // output p: y_std[p]^2 Sigma (sklearn/_gpr.py:462-463)
+  for (int p = 0; p < P; ++p) {
+    const double s2 = m->y_std[p] * m->y_std[p];
+    double* out = cov + (size_t)p * M * M;
+    for (size_t i = 0; i < (size_t)M * M; ++i) out[i] = sig[i] * s2;
   }
   return GPK_OK;
 }

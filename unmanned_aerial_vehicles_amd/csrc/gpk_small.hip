@@ -12,6 +12,10 @@
 //                            16-byte pieces are k-contiguous), the k-range split over the 4 waves; squares
 //                            summed over the rows; the last workgroup adds the shares and writes
 //                            max(kss - sum, floor).
+//   small_cov_kernel         the same rows of V = W K*^T per workgroup; instead of squares it stores the workgroup's
+//                            share V_r^T V_r (lower triangle of the 32 x 32 block); the shares are added in a fixed
+//                            order in two levels - the last workgroup of each group of CG adds its group's, the last
+//                            of those adds the group sums - and K(Xq, Xq) + noise I - sum is written, mirrored.
 //
 // Both results land in the caller's (pinned, mapped) output block; the queries are read from it as well.
 #include "gpk_internal.h"
@@ -275,6 +279,119 @@ __global__ __launch_bounds__(64 * VW) void small_var_kernel(SmallK k, long long 
   }
 }
 
+// Every one of `count` workgroups has stored its part; true (in all its threads) for the last one: last_workgroup with
+// an explicit count, for the groups of the two-level reduction below.
+__device__ __forceinline__ bool last_of(unsigned* counter, unsigned count, int tid) {
+  __shared__ int is_last;
+  __syncthreads();
+  if (tid == 0) {
+    const unsigned t = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    is_last = (t == count - 1);
+    if (is_last) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __syncthreads();
+  return is_last != 0;
+}
+
+constexpr int CG = 16;                   // workgroups per first-level group of the covariance reduction
+constexpr int CE = SQ * (SQ + 1) / 2;    // packed lower-triangle entries of a 32 x 32 share
+
+// entry t of the packed lower triangle -> (i, j), i >= j
+__device__ __forceinline__ void tri_index(int t, int& i, int& j) {
+  i = (int)((__builtin_sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
+  while ((i + 1) * (i + 2) / 2 <= t) ++i;
+  while (i * (i + 1) / 2 > t) --i;
+  j = t - i * (i + 1) / 2;
+}
+
+// Posterior covariance of M <= 32 queries (one model): the k-loop of small_var_kernel, then the workgroup's share of V^T V.
+// counters: [0] the top level, [1 + g] group g; all left at zero.  pcov: gridDim.x x CE, gcov: groups x CE.
+template <int NMB>
+__global__ __launch_bounds__(64 * VW) void small_cov_kernel(SmallK k, long long ldw, long long Np, const double* Ks, int M,
+                                                            int D, int P, double noise, const double* Xq,
+                                                            const double* pmean, unsigned mean_shares, double* pcov,
+                                                            double* gcov, unsigned* counters, double* mean_out,
+                                                            double* cov_out) {
+  __shared__ double red[VW][NMB][16][17];
+  __shared__ double vt[NMB * 16][17];          // this workgroup's rows of V, transposed: [query][row]
+  __shared__ double qs[SQ][SD + 1];
+  const double* __restrict__ W = k.W[0];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, i = lane & 15, kq = lane >> 4;
+  const long long r0 = (long long)blockIdx.x * SR, row = r0 + i;
+  const long long kend = min(Np, (r0 + SR + 63) / 64 * 64);
+  const int nch = (int)(kend / 64);
+  const double* wp = W + row * ldw + 2 * kq;
+  const double* kp[NMB];
+#pragma unroll
+  for (int mb = 0; mb < NMB; ++mb) kp[mb] = Ks + (long long)min(16 * mb + i, M - 1) * Np + 2 * kq;
+  d4 acc[NMB];
+#pragma unroll
+  for (int mb = 0; mb < NMB; ++mb) acc[mb] = d4{0.0, 0.0, 0.0, 0.0};
+  VFrag<NMB> f0, f1;
+  if (w < nch) vload<NMB>(f0, wp, kp, (long long)w * 64);
+  for (int c = w; c < nch; c += 2 * VW) {
+    const bool n1 = c + VW < nch, n2 = c + 2 * VW < nch;
+    if (n1) vload<NMB>(f1, wp, kp, (long long)(c + VW) * 64);
+    vmul<NMB>(f0, (long long)c * 64, kq, row, acc);
+    if (n2) vload<NMB>(f0, wp, kp, (long long)(c + 2 * VW) * 64);
+    if (n1) vmul<NMB>(f1, (long long)(c + VW) * 64, kq, row, acc);
+  }
+#pragma unroll
+  for (int mb = 0; mb < NMB; ++mb)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) red[w][mb][kq + 4 * r][i] = acc[mb][r];
+  __syncthreads();
+  for (int e = tid; e < NMB * 256; e += 64 * VW) {
+    const int mb = e >> 8, r = (e >> 4) & 15, c = e & 15;
+    double v = 0.0;
+#pragma unroll
+    for (int u = 0; u < VW; ++u) v += red[u][mb][r][c];
+    vt[16 * mb + c][r] = (16 * mb + c < M) ? v : 0.0;     // (columns >= M repeat query M - 1: dropped)
+  }
+  __syncthreads();
+  // the share: lower triangle of V_r^T V_r over this workgroup's 16 rows, packed
+  constexpr int NE = NMB * 16 * (NMB * 16 + 1) / 2;
+  for (int t = tid; t < NE; t += 64 * VW) {
+    int a, b;
+    tri_index(t, a, b);
+    double s = 0.0;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s = __builtin_fma(vt[a][r], vt[b][r], s);
+    pcov[(long long)blockIdx.x * CE + t] = s;
+  }
+  // the mean shares are complete since the previous launch (as in small_var_kernel; scratch: the reduction buffer)
+  static_assert(VW * 16 * 17 >= 4 * SQ * SP, "the reduction buffer doubles as the mean scratch");
+  if (blockIdx.x == 0) finish_means(pmean, mean_shares, M, P, k.ymean, k.ystd, mean_out, tid, &red[0][0][0][0]);
+  const unsigned g = blockIdx.x / CG, g0 = g * CG, g1 = min(g0 + CG, gridDim.x), ng = (gridDim.x + CG - 1) / CG;
+  if (!last_of(counters + 1 + g, g1 - g0, tid)) return;
+  for (int t = tid; t < NE; t += 64 * VW) gcov[(long long)g * CE + t] = sum_shares(pcov + t, g0, 1, g1, CE);
+  if (!last_of(counters, ng, tid)) return;
+  for (int e = tid; e < M * D; e += 64 * VW) qs[e / D][e % D] = Xq[e] / k.ls[0][e % D];
+  __syncthreads();
+  for (int t = tid; t < NE; t += 64 * VW) {
+    int a, b;
+    tri_index(t, a, b);
+    if (a >= M) continue;
+    const double s = sum_shares(gcov + t, 0, 1, ng, CE);
+    double kv;
+    if (a == b) {
+      kv = k.sf2[0] + noise;
+    } else {
+      double d2 = 0.0;
+#pragma unroll
+      for (int d = 0; d < SD; ++d)
+        if (d < D) {
+          const double df = qs[a][d] - qs[b][d];
+          d2 = __builtin_fma(df, df, d2);
+        }
+      kv = k.sf2[0] * gpk_exp_neg(-0.5 * d2);
+    }
+    const double v = kv - s;
+    cov_out[(long long)a * M + b] = v;
+    cov_out[(long long)b * M + a] = v;
+  }
+}
+
 }  // namespace
 
 size_t gpk_small_work_doubles(int64_t Np, int B) { return (size_t)B * Np * (SQ + SQ * SP / SJ + SQ / SR); }
@@ -324,6 +441,51 @@ int gpk_small_predict(gpk_handle h, int B, const double* const* X, const double*
     hipLaunchKernelGGL(small_cross_mean_kernel<true>, dim3(ga, B), dim3(256), 0, h->stream, k, (long long)N, (long long)Np,
                        D, P, Xq, (int)M, (double*)nullptr, pmean, h->d_count, mean_out);
   }
+  GPK_LAUNCH_CHECK(h);
+  return GPK_OK;
+}
+
+size_t gpk_small_cov_work_doubles(int64_t Np) {
+  const size_t shares = (size_t)(Np / SR), groups = (shares + CG - 1) / CG;
+  return (size_t)Np * (SQ + SQ * SP / SJ) + (shares + groups) * CE;
+}
+
+// Posterior mean (M x P, un-normalised) and covariance (M x M, normalised-target units) of M <= 32 queries of one model:
+// small_cross_mean_kernel + small_cov_kernel, no synchronisation.  Xq, mean_out, cov_out may be pinned, mapped host memory.
+int gpk_small_cov(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls, double sf2,
+                  const double* y_mean, const double* y_std, const double* W, int64_t Np, int64_t ldw, double noise,
+                  const double* Xq, int64_t M, double* work, double* mean_out, double* cov_out) {
+  GPK_REQUIRE(h, gpk_small_ok(Np, D, P, M) && Np == gpk_padded(N), "small cov: shape outside the small-batch path");
+  GPK_REQUIRE(h, X && alpha && W && ldw >= Np && ldw % 2 == 0 && ((uintptr_t)W % 16) == 0,
+              "small cov: needs the (16-byte aligned) inverse factor");
+  if (!h->d_cov_count) {
+    GPK_CHECK_HIP(h, hipMalloc((void**)&h->d_cov_count, GPK_SMALL_COV_COUNTERS * sizeof(unsigned)));
+    GPK_CHECK_HIP(h, hipMemsetAsync(h->d_cov_count, 0, GPK_SMALL_COV_COUNTERS * sizeof(unsigned), h->stream));
+  }
+  SmallK k{};
+  k.X[0] = X; k.alpha[0] = alpha; k.W[0] = W;
+  for (int d = 0; d < 16; ++d) k.ls[0][d] = 1.0;
+  for (int d = 0; d < D; ++d) {
+    GPK_REQUIRE(h, ls[d] > 0.0, "length-scales must be positive");
+    k.ls[0][d] = ls[d];
+  }
+  k.sf2[0] = sf2;
+  for (int o = 0; o < P; ++o) { k.ymean[o] = y_mean[o]; k.ystd[o] = y_std[o]; }
+  const unsigned ga = (unsigned)(Np / SJ), gb = (unsigned)(Np / SR);
+  static_assert(GPK_SMALL_COV_COUNTERS >= 1 + GPK_SMALL_MAX_NP / SR / CG, "counters of the covariance reduction");
+  double* Ks = work;                                       // SQ x Np
+  double* pmean = Ks + (size_t)SQ * Np;                    // ga x (SQ * SP)
+  double* pcov = pmean + (size_t)ga * (SQ * SP);           // gb x CE
+  double* gcov = pcov + (size_t)gb * CE;                   // (gb / CG rounded up) x CE
+  hipLaunchKernelGGL(small_cross_mean_kernel<false>, dim3(ga, 1), dim3(256), 0, h->stream, k, (long long)N, (long long)Np, D, P,
+                     Xq, (int)M, Ks, pmean, h->d_count, mean_out);
+  GPK_LAUNCH_CHECK(h);
+  if (M <= 16)
+    hipLaunchKernelGGL(small_cov_kernel<1>, dim3(gb), dim3(64 * VW), 0, h->stream, k, (long long)ldw, (long long)Np, Ks, (int)M,
+                       D, P, noise, Xq, pmean, ga, pcov, gcov, h->d_cov_count, mean_out, cov_out);
+  else
+    hipLaunchKernelGGL(small_cov_kernel<2>, dim3(gb), dim3(64 * VW), 0, h->stream, k, (long long)ldw, (long long)Np, Ks, (int)M,
+                       D, P, noise, Xq, pmean, ga, pcov, gcov, h->d_cov_count, mean_out, cov_out);
   GPK_LAUNCH_CHECK(h);
   return GPK_OK;
 }

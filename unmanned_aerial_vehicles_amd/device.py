@@ -754,6 +754,80 @@ class DeviceGP:
                 out[m0:m1].copy_(var[: m1 - m0])
         return out
 
+    # ---- posterior covariance (K7) ----------------------------------------------------------------------------------
+    def cov_panel_check(self, M):
+        """The covariance is one panel: V (Np x Mp fp64) must fit VAR_PANEL_BYTES and M <= VAR_PANEL_MAX (no silent
+        panelling: every entry of Sigma needs the whole of V)."""
+        if M > self.VAR_PANEL_MAX:
+            raise ValueError(f"return_cov: at most VAR_PANEL_MAX = {self.VAR_PANEL_MAX} queries per call (got {M})")
+        need = self.Np * padded(M) * 8
+        if need > self.VAR_PANEL_BYTES:
+            raise ValueError(f"return_cov: V = L^-1 K*^T would take {need} bytes, more than VAR_PANEL_BYTES = "
+                             f"{self.VAR_PANEL_BYTES} (N = {self.N}, M = {M}): pass fewer queries per call")
+
+    def predict_cov_dev(self, Xq, noise, method="auto"):
+        """K7 on device tensors: the (M, M) float64 posterior covariance K(Xq, Xq) + noise I - V^T V in normalised-target
+        units (not clipped; exactly symmetric).  method "inverse": V = W K*^T with the explicit inverse factor; "solve": V by
+        the blocked triangular solve with L; "auto": as `_fp64_var_method` chooses.  fp64 whatever the model serves."""
+        torch = _torch()
+        assert self.factored
+        if method == "auto":
+            method = self._fp64_var_method()
+        if method not in ("inverse", "solve"):
+            raise ValueError("method must be 'auto', 'inverse' or 'solve'")
+        if self.replica:
+            raise RuntimeError("a serving replica holds no factor: covariances are computed on the rank that fitted the model")
+        q = self._as_queries(Xq, torch.float64)
+        M = q.shape[0]
+        if M == 0:
+            return self.be.empty((0, 0), torch.float64)
+        self.cov_panel_check(M)
+        Mp = padded(M)
+        work = self.be.empty((self.Np * Mp,), torch.float64)
+        cov = self.be.empty((Mp, Mp), torch.float64)
+        be = self.be
+        lsp = self.ls.ctypes.data_as(_lib._dp)
+        if method == "inverse":
+            W = self.inverse_factor(False)
+            with be.lock:
+                be.bind_stream()
+                be.check(be.lib.gpk_predict_cov_inv(be.h, GPK_F64, _p(self.X), self.N, self.D, lsp, self.sf2, _p(W), self.Np,
+                                                    self.Np, _p(q), M, float(noise), _p(work), _p(cov), Mp))
+        else:
+            with be.lock:
+                be.bind_stream()
+                be.check(be.lib.gpk_predict_cov(be.h, GPK_F64, _p(self.X), self.N, self.D, lsp, self.sf2, _p(self.K), self.Np,
+                                                self.Np, _p(self.winv), _p(q), M, float(noise), _p(work), _p(cov), Mp))
+        del work
+        return cov[:M, :M]
+
+    def predict_cov_host(self, Xq, y_mean, y_std, noise):
+        """One C call (gpk_predict_host_cov) for batches where `host_path_ok(M, True)` holds: host queries (M, D) ->
+        (mean (M, P) un-normalised, cov (M, M) in normalised-target units) as NumPy arrays.  Up to 32 queries two launches."""
+        assert self.factored
+        Xq = np.ascontiguousarray(Xq, dtype=np.float64)
+        if Xq.ndim != 2 or Xq.shape[1] != self.D:
+            raise ValueError(f"queries must be (M, {self.D})")
+        M = Xq.shape[0]
+        mean = np.empty((M, self.P))
+        cov = np.empty((M, M))
+        W = self.inverse_factor(False)
+        be = self.be
+        # (addresses cached per factorisation and target scaling, as in predict_host: this call runs at the control rate)
+        c = self._host_args
+        if (c is None or c[0] is not self.X or c[1] is not self.alpha or c[2] is not self.ls or c[3] is not y_mean
+                or c[4] is not y_std):
+            ym = np.ascontiguousarray(np.broadcast_to(np.asarray(y_mean, dtype=np.float64), (self.P,)))
+            ys = np.ascontiguousarray(np.broadcast_to(np.asarray(y_std, dtype=np.float64), (self.P,)))
+            c = self._host_args = (self.X, self.alpha, self.ls, y_mean, y_std, ym, ys, self.X.data_ptr(),
+                                   self.alpha.data_ptr(), self.ls.ctypes.data, ym.ctypes.data, ys.ctypes.data)
+        with be.lock:
+            be.bind_stream()
+            be.check(be.lib.gpk_predict_host_cov(be.h, c[7], c[8], self.N, self.D, self.P, c[9], self.sf2, c[10], c[11],
+                                                 W.data_ptr(), self.Np, self.Np, float(noise), Xq.ctypes.data, M,
+                                                 mean.ctypes.data, cov.ctypes.data))
+        return mean, cov
+
     # ---- gated serving: the one place every fp32 surface (estimator, sharded predictor, package GP, per-axis models) goes
     # through -------------------------------------------------------------------------------------------------------------
     def _rows64(self, Xq, q, rows):
@@ -868,3 +942,24 @@ class DeviceGP:
         """Debug/inspection helper: the (N, N) Gram matrix as a host array (overwrites the factor)."""
         self.gram(ls, sf2, diag_add)
         return self.K[: self.N, : self.N].cpu().numpy()
+
+
+def prior_cov(X, ls, sf2, noise, device=None):
+    """K(X, X) + noise I of an unfitted model's prior on the GPU (gpk_gram with diag_add = noise: exact differences, the
+    noise on the diagonal only), as a (M, M) host array."""
+    torch = _torch()
+    be = get_backend(device)
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    M, D = X.shape
+    if M == 0:
+        return np.zeros((0, 0))
+    if not 1 <= D <= _lib.GPK_MAX_D:
+        raise ValueError(f"D must be in [1, {_lib.GPK_MAX_D}]")
+    Mp = padded(M)
+    ls = np.ascontiguousarray(np.broadcast_to(np.asarray(ls, dtype=np.float64), (D,)))
+    q = be.upload(X)
+    K = be.empty((Mp, Mp), torch.float64)
+    with be.lock:
+        be.bind_stream()
+        be.check(be.lib.gpk_gram(be.h, GPK_F64, _p(q), M, D, ls.ctypes.data_as(_lib._dp), float(sf2), float(noise), _p(K), Mp))
+    return K[:M, :M].cpu().numpy()

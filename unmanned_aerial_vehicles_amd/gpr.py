@@ -244,9 +244,14 @@ class GaussianProcessRegressor:
 
     # ------------------------------------------------------------------ predict
     def predict(self, X, return_std=False, return_cov=False):
-        """`sklearn/gaussian_process/_gpr.py:367-496`."""
-        if return_cov:
-            raise NotImplementedError("return_cov is not part of the reference's GP-MPC path")
+        """`sklearn/gaussian_process/_gpr.py:367-496`.
+
+        return_cov=True returns (y_mean, y_cov), y_cov of shape (M, M) - (M, M, P) for 2-D targets with P > 1 - scaled by
+        the target std squared as scikit-learn does.  The covariance is always computed by the fp64 kernels (there is no
+        fp32 covariance): a model with predict_dtype="float32" serves it, and the mean that goes with it, in fp64.  One call
+        takes at most VAR_PANEL_MAX queries and a V = L^-1 K*^T that fits VAR_PANEL_BYTES (ValueError otherwise)."""
+        if return_std and return_cov:
+            raise RuntimeError("At most one of return_std or return_cov can be requested.")
         X = np.array(X, dtype=np.float64, ndmin=2)
         if not np.isfinite(X).all():       # scikit-learn's input validation (_gpr.py:404-412 -> check_array)
             raise ValueError("Input X contains NaN or infinity.")
@@ -256,12 +261,20 @@ class GaussianProcessRegressor:
                 ConstantKernel(1.0, constant_value_bounds="fixed") * RBF(1.0, length_scale_bounds="fixed"))
             comp = kern.components()
             mean = np.zeros((X.shape[0], n_t)).squeeze()
+            if return_cov:                 # kernel(X), _gpr.py:425-431: built on the device by the Gram kernel
+                from .device import prior_cov
+                cov = prior_cov(X, comp.ls_vector(X.shape[1]), comp.sf2, comp.noise or 0.0, self.device)
+                if n_t > 1:
+                    cov = np.repeat(np.expand_dims(cov, -1), repeats=n_t, axis=-1)
+                return mean, cov
             if return_std:
                 var = np.full((X.shape[0], n_t), comp.sf2 + (comp.noise or 0.0)).squeeze()
                 return mean, np.sqrt(var)
             return mean
         self._ensure_device()
         dev = self._dev
+        if return_cov:
+            return self._predict_cov(X)
         if (self.predict_dtype != "float32" and self.var_method in ("auto", "inverse")
                 and dev.host_path_ok(X.shape[0], return_std)):
             # small batches (the control loop's 1..25 rows): one C call, one synchronisation
@@ -296,6 +309,41 @@ class GaussianProcessRegressor:
         if mean.shape[1] == 1:
             mean, var = mean[:, 0], var[:, 0]
         return mean, np.sqrt(var)
+
+    def _predict_cov(self, X):
+        """Fitted model, return_cov=True: `_gpr.py:441-469` - the mean and Sigma = kernel_(X) - V^T V, un-normalised."""
+        dev = self._dev
+        comp = self.kernel_.components()
+        noise = comp.noise or 0.0
+        M = X.shape[0]
+        dev.cov_panel_check(M)
+        method = {"inverse": "inverse", "solve": "solve"}.get(self.var_method, "auto")
+        if method != "solve" and dev.host_path_ok(M, True):
+            # small batches (the MPC horizon): one C call, one synchronisation; up to 32 rows two launches
+            mean, cov = dev.predict_cov_host(X, self._y_train_mean, self._y_train_std, noise)
+        else:
+            q = dev._as_queries(X, __import__("torch").float64)
+            mean = dev.predict_mean_dev(q, self._y_train_mean, self._y_train_std, "float64").cpu().numpy()
+            cov = dev.predict_cov_dev(q, noise, method).contiguous().cpu().numpy()
+        if mean.shape[1] == 1:
+            mean = mean[:, 0]
+        # undo normalisation (_gpr.py:462-467): y_cov[i, j, p] = Sigma[i, j] y_std[p]^2, squeezed for one output
+        std2 = self._y_train_std ** 2
+        if std2.shape[0] == 1:
+            return mean, cov * std2[0]
+        return mean, cov[:, :, None] * std2[None, None, :]
+
+    def sample_y(self, X, n_samples=1, random_state=0):
+        """`sklearn/gaussian_process/_gpr.py:498-535`: draws from the joint posterior (or the prior, unfitted) at X - the
+        mean and covariance from `predict(X, return_cov=True)` (GPU), the draw by NumPy's `multivariate_normal` (an SVD of
+        the M x M covariance on the host), one target at a time.  Shape (M, n_samples), or (M, P, n_samples)."""
+        rng = _rng_from(random_state)
+        y_mean, y_cov = self.predict(X, return_cov=True)
+        if y_mean.ndim == 1:
+            return rng.multivariate_normal(y_mean, y_cov, n_samples).T
+        y_samples = [rng.multivariate_normal(y_mean[:, t], y_cov[..., t], n_samples).T[:, np.newaxis]
+                     for t in range(y_mean.shape[1])]
+        return np.hstack(y_samples)
 
     # ------------------------------------------------------------------ host views / persistence
     @property
