@@ -153,6 +153,7 @@ int main(int argc, char** argv) {
   EXPECT(isinf(lml) && lml < 0 && grad[0] == 0.0 && grad[1] == 0.0, "not-PD trial point: -inf / zero gradient, got %g", lml);
   Xd[3] = NAN;
   EXPECT(gpk_fit(h, Xd, 40, D, Yd, P, &one, 1, 1.0, 0.05, 0.0, 1) == GPK_BAD_ARG, "NaN inputs");
+  EXPECT(gpk_set_option(h, "ptile_xcd", 1) == GPK_BAD_ARG, "unknown option names must be refused");
   CHECK_GPK(gpk_model_release(h));
   gpk_destroy(h);
   printf("C ABI composite: OK\n");

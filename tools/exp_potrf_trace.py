@@ -11,7 +11,7 @@ import torch  # noqa: E402
 from unmanned_aerial_vehicles_amd.device import DeviceGP, get_backend  # noqa: E402
 from tools import gpk_opts  # noqa: E402
 
-gpk_opts.install()                # GPK_OPTS=ptile_xcd=1,... : A/B switches
+gpk_opts.install()                # GPK_OPTS=ptile_single_max_nt=0,... : A/B switches
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
 be = get_backend(0)

@@ -32,31 +32,14 @@ def run(n, be, torch, _lib):
     nt = n // 128
     t0 = t[:, 0].min()
     us = lambda v: (v - t0) / 100.0
-    # which tile each task was: a listed launch stamps its list word (i | j << 9 | problem << 18) into slot 15 (the diagonal tasks
-    # overwrite it with a cycle stamp, but they are the tasks with an end stamp in slot 10, and any list keeps them in column
-    # order); an unlisted launch is column-major.  (Update tasks of a chunked launch stamp the same word: the tile's own task is
-    # the LAST one listed for it.)
+    # which tile each task was: the tasks are taken in column-major order; the diagonal tasks are the ones with an end stamp in slot 10
     isd = t[:, 10] > 0
-    e = t[:, 15].astype(np.int64)
     where = {}
-    if (e[~isd] != 0).any():
-        for k in np.nonzero(~isd)[0]:
-            where[(int(e[k] & 511), int((e[k] >> 9) & 511))] = k
-    else:
-        k = 0
-        for j in range(nt):
-            for i in range(j, nt):
-                where[(i, j)] = k; k += 1
+    k = 0
+    for j in range(nt):
+        for i in range(j, nt):
+            where[(i, j)] = k; k += 1
     D = t[isd]
-    if (e[~isd] != 0).any():                       # a chunked launch: every listing of a tile but the last is an update task
-        last = set(where.values())
-        u = np.array([k for k in np.nonzero(~isd)[0] if k not in last], dtype=np.int64)
-        if len(u):
-            o = np.array(sorted(last), dtype=np.int64)
-            du = (t[u, 5] - t[u, 0]) / 100.0; ku = (t[u, 1] - t[u, 0]) / 100.0
-            do = (t[o, 5] - t[o, 0]) / 100.0; ko = (t[o, 1] - t[o, 0]) / 100.0
-            print(f"  {len(u)} update tasks: {du.mean():.1f} us each (k-loop {ku.mean():.1f}, store + publish {(du - ku).mean():.1f}), "
-                  f"sum {du.sum() / 1e3:.1f} ms of workgroup time; {len(o)} own tasks: {do.mean():.1f} us each (k-loop {ko.mean():.1f}), sum {do.sum() / 1e3:.1f} ms")
     assert len(D) == nt
     F = np.array([t[where[(j + 1, j)]] for j in range(nt - 1)])
     d_done = us(D[:, 10]); d_start = us(D[:, 0]); d_avail = us(D[:, 11]); d_kend = us(D[:, 1])

@@ -41,7 +41,6 @@ extern "C" void gpk_destroy(gpk_handle h) {
   if (h->d_count) (void)hipFree(h->d_count);
   if (h->d_cov_count) (void)hipFree(h->d_cov_count);
   if (h->d_ptile) (void)hipFree(h->d_ptile);
-  if (h->d_ptile_list) (void)hipFree(h->d_ptile_list);
   if (h->h_small) (void)hipHostFree(h->h_small);
   if (h->serve_dev) (void)hipFree(h->serve_dev);
   if (h->serve_host) (void)hipHostFree(h->serve_host);
@@ -74,7 +73,6 @@ extern "C" int gpk_set_option(gpk_handle h, const char* name, int value) {
   GPK_REQUIRE(h, name, "set_option: null name");
   const std::string n(name);
   if (n == "k5_split2_tile") h->k5_split2_tile = (value >= 0 && value <= 2) ? value : 0;
-  else if (n == "k5_super") h->k5_super = value;
   else if (n == "small_path") h->small_path = value;
   else if (n == "trsm256") h->trsm256 = value;
   else if (n == "trtri_levels") h->trtri_levels = value;
@@ -83,20 +81,13 @@ extern "C" int gpk_set_option(gpk_handle h, const char* name, int value) {
   else if (n == "gemm_balanced") h->gemm_balanced = value;
   else if (n == "gemm_balanced_max_tiles") h->gemm_balanced_max_tiles = value;
   else if (n == "k3_stream_min_np") h->k3_stream_min_np = value;
-  else if (n == "gemm_wm_f64") h->gemm_wm_f64 = value == 2 ? 2 : 4;
-  else if (n == "gemm_wm_f32") h->gemm_wm_f32 = value == 2 ? 2 : 4;
   else if (n == "gemm_log") h->gemm_log = value;
   else if (n == "debug_fill") h->debug_fill = value ? 1 : 0;
-  else if (n == "ptile_slots") h->ptile_slots_override = value > 0 ? value : 0;
   else if (n == "ptile") h->ptile = value;
   else if (n == "ptile_max_np") h->ptile_max_np = value;
   else if (n == "ptile_prog_max_nt") h->ptile_prog_max_nt = value;
   else if (n == "ptile_inv_max_np") h->ptile_inv_max_np = value;
   else if (n == "ptile_single_max_nt") h->ptile_single_max_nt = value;
-  else if (n == "ptile_xcd") h->ptile_xcd = value;
-  else if (n == "ptile_grp_rows") h->ptile_grp_rows = value;
-  else if (n == "ptile_grp_cols") h->ptile_grp_cols = value;
-  else if (n == "ptile_xcd_min_nt") h->ptile_xcd_min_nt = value;
   else if (n == "ptile_sr") h->ptile_sr = value;
   else if (n == "ptile_sr_max_nt") h->ptile_sr_max_nt = value;
   else if (n == "ptile_prog_rows") h->ptile_prog_rows = value >= 8 ? 8 : value >= 1 ? value : 1;
@@ -223,7 +214,7 @@ extern "C" int gpk_predict_var_inv(gpk_handle h, int dtype, const void* X, int64
   g.ke0 = GPK_TILE;
   g.ke_row = GPK_TILE;
   g.epilogue = 1;
-  g.k_super = h->k5_super;   // W is zero right of the diagonal for GPK_ZERO_BAND_TILES - 1 tiles (gpk_trtri, gpk_tril_to_f32)
+  g.k_super = 1;            // W is zero right of the diagonal for GPK_ZERO_BAND_TILES - 1 tiles (gpk_trtri, gpk_tril_to_f32)
   g.heavy_first = 1;   // row tile tm costs (tm + 1) k-blocks: start the long ones first
   const int ntm = (int)(Np / gpk_gemm_tile(h, g));       // one partial row per tile row of the launch
   void* partial = nullptr;

@@ -76,7 +76,7 @@ extern "C" int gpk_predict_cov_inv(gpk_handle h, int dtype, const void* X, int64
   GemmArgs g = gemm_args(W, ldw, 0, kq, Np, 0, work, Mp, (int)Np, (int)Mp, (int)Np, 1.0, 0.0);
   g.ke0 = GPK_TILE;
   g.ke_row = GPK_TILE;
-  g.k_super = h->k5_super;   // W is zero right of the diagonal for GPK_ZERO_BAND_TILES - 1 tiles (gpk_trtri)
+  g.k_super = 1;            // W is zero right of the diagonal for GPK_ZERO_BAND_TILES - 1 tiles (gpk_trtri)
   g.heavy_first = 1;
   GPK_TRY(gpk_gemm(h, GPK_F64, g));
   return cov_from_v(h, (const double*)work, Np, (const double*)Xq, M, D, ls, sf2, noise, cov, ldc);

@@ -660,8 +660,8 @@ int launch(gpk_handle h, const GemmArgs& g) {
   p.nsc = (p.ntn + sc - 1) / sc;
   p.nst = g.lower_only ? nsr * (nsr - 1) / 2 + (36 * nsr + 63) / 64 : (int)(((long long)p.ntm * p.ntn + 63) / 64);
   // k_super widens a tile's k-range to that of its super-tile, which spans at most two bands of sr tile rows:
-  // allowed only while that stays inside the zero band the producers of triangular operands guarantee
-  p.k_super = (g.k_super && 2 * p.sr * (TS / 64) <= 2 * GPK_ZERO_BAND_TILES) ? 1 : 0;
+  // allowed only while those rows stay inside the zero band (of 128-row tiles) the producers of triangular operands guarantee
+  p.k_super = (g.k_super && 2 * p.sr * TS <= 128 * GPK_ZERO_BAND_TILES) ? 1 : 0;
   long long nblocks = p.direct ? (long long)p.ntm * p.ntn : (long long)((p.nst + 7) / 8) * 512;
   if (nblocks >= (1ll << 31)) { h->err = "gemm: grid too large"; return GPK_BAD_ARG; }
   // Tiles that differ in k-range, few enough residency rounds for the placement of the long ones to matter: the balanced
@@ -770,12 +770,7 @@ int gpk_gemm(gpk_handle h, int dtype, const GemmArgs& g) {
   const int tile = gpk_gemm_tile(h, g);
   const bool small = tile == 64;
   if (tile == 32 && dtype == GPK_F64) return launch<double, 2, 32>(h, g);
-  // wave rows per 128-tile workgroup (2 -> 256 threads, 4 -> 512 threads), per dtype; tuned on MI355X,
-  // overridable through the options gemm_wm_f64 / gemm_wm_f32
-  if (dtype == GPK_F64) {
-    if (small) return launch<double, 2, 64>(h, g);
-    return h->gemm_wm_f64 == 2 ? launch<double, 2, 128>(h, g) : launch<double, 4, 128>(h, g);
-  }
-  if (small) return launch<float, 2, 64>(h, g);
-  return h->gemm_wm_f32 == 2 ? launch<float, 2, 128>(h, g) : launch<float, 4, 128>(h, g);
+  // 128-tile workgroups: four wave rows (512 threads)
+  if (dtype == GPK_F64) return small ? launch<double, 2, 64>(h, g) : launch<double, 4, 128>(h, g);
+  return small ? launch<float, 2, 64>(h, g) : launch<float, 4, 128>(h, g);
 }

@@ -34,8 +34,6 @@ struct gpk_context {
   size_t serve_dev_bytes = 0;
   void* serve_host = nullptr;
   size_t serve_host_bytes = 0;
-  int gemm_wm_f64 = 4;          // wave rows per GEMM workgroup (2 or 4); 4 = 512 threads, 4 waves/SIMD
-  int gemm_wm_f32 = 4;
   int gemm_small_tiles = 1024;   // launches with fewer 128 x 128 tiles than this run on 64 x 64 tiles
   int gemm_tiny_tiles = 320;     // fp64 launches with fewer 128 x 128 tiles than this run on 32 x 32 tiles (option gemm_tiny_tiles; 0: never);
                                  // measured (profiles/r05_gemm_tiny_ab.log): W^T W at N = 1024 59 -> 33 us, 2048 108 -> 84 us, trtri 1024 117 -> 74 us;
@@ -46,7 +44,6 @@ struct gpk_context {
   int trtri_levels = 1;      // gpk_trtri: one batched launch per level for power-of-two tile counts
   int trsm256 = 1;           // potrf: fused 256-wide base of the triangular solve
   int small_path = 1;        // gpk_predict_host: two-launch small-batch kernels (option small_path = 0 disables)
-  int k5_super = 1;          // K5: lockstep super-tiles (option k5_super = 0 disables)
   int k3_stream_min_np = 512;    // gpk_potrs_inv: streaming matrix-vector passes from this padded size up (P <= 6); measured faster than the two
                                  // 128-column tile GEMMs from there on (N = 4096: 0.11 against 0.35 ms, profiles/r04_k3_ab.log)
   int k5_split2_tile = 0;    // fp16 x 2 variance launch: 0 = the tallest tile (512 / 256 / 128 x 128) that still comes in >= 512
@@ -64,18 +61,8 @@ struct gpk_context {
   int ptile_sr = 1, ptile_sr_max_nt = 36;   // ... and up to this many tile columns the 256-register build (two k-tiles in flight in the off-diagonal
                              // k-loops: gpk_ptile.hip, SR); ptile_sr = 0: the 128-register build for everything
   int ptile_single_max_nt = 96;   // ... up to this many tile columns the launch keeps ONE workgroup per CU
-  int ptile_xcd = 0;         // 1: one task queue per XCD, tile rows dealt round-robin; 2: groups of rows x columns tiles per queue; 0: ONE
-                             // global ticket counter - the default: measured, neither dealing raises the L2 hit rate (the tasks of an XCD
-                             // do not walk k in step) and both are 0-4 % slower (profiles/r05_ptile_xcd_ab.log)
-  int ptile_xcd_min_nt = 56; // ... from this many tile columns up (below, the launch is bound by the diagonal chain, not by L2 traffic)
-  int ptile_grp_rows = 8, ptile_grp_cols = 4;   // ptile_xcd = 2: groups of rows x columns tiles per queue entry block
-  int* d_ptile_list = nullptr;         // the queues' task lists (device), kept for the last shape
-  size_t ptile_list_cap = 0;
-  std::vector<int> ptile_list_host;
-  long long ptile_list_key = -1;
   int ptile_launches = 0;    // one-launch factorisations issued by the current gpk_potrf (their abort words are checked at its end)
   std::string ptile_trace_request;   // option "ptile_trace_path" (debugging aid): the NEXT one-launch factorisation writes its per-task time stamps there
-  int ptile_slots_override = 0;      // option "ptile_slots" (experiments): resident workgroups of the launch, 0 = the rule below
   std::string ptile_trace_path;   // ... while that launch is in flight
   long long ptile_trace_n = 0;
   int debug_fill = 0;        // option debug_fill: the handle's scratch is overwritten with 0xFF bytes (NaN) at every request
