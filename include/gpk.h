@@ -65,7 +65,8 @@ GPK_API int64_t gpk_padded(int64_t n);
  * handle's stream - tag GPK_TIMED_K5: the one GEMM launch of gpk_predict_var_inv / gpk_predict_var_inv_split
  * (V = W K*^T with the column-norm epilogue); tag GPK_TIMED_GRAM: the Gram kernel of gpk_gram; tag GPK_TIMED_GRAD: the
  * streaming pass of gpk_lml_grad over K^-1; tag GPK_TIMED_POTRF: the launches of one gpk_potrf; tag GPK_TIMED_COV: the
- * symmetric product (K(Xq, Xq) + noise I - V^T V) of gpk_predict_cov_inv / gpk_predict_cov - and keeps the
+ * symmetric product (K(Xq, Xq) + noise I - V^T V) of gpk_predict_cov_inv / gpk_predict_cov; tag GPK_TIMED_JAC: the second
+ * triangular product (C = W^T V) of gpk_predict_var_grad_inv - and keeps the
  * last 64 pairs.  gpk_kernel_times synchronises the stream and returns the elapsed milliseconds of the bracketed
  * launches with that tag still in the ring, oldest first (*n_out of them, at most max_n).  bench.py uses it to
  * report the dominant kernel's duration over exactly the timed steps; rocprofv3's kernel trace of the same run is
@@ -90,7 +91,7 @@ GPK_API int64_t gpk_padded(int64_t n);
  * (debugging aid, tools/exp_ptile_trace.py).                                                                          */
 GPK_API int gpk_set_option(gpk_handle h, const char* name, int value);
 GPK_API int gpk_set_option_str(gpk_handle h, const char* name, const char* value);
-enum { GPK_TIMED_K5 = 1, GPK_TIMED_GRAM = 2, GPK_TIMED_GRAD = 3, GPK_TIMED_POTRF = 4, GPK_TIMED_COV = 5 };
+enum { GPK_TIMED_K5 = 1, GPK_TIMED_GRAM = 2, GPK_TIMED_GRAD = 3, GPK_TIMED_POTRF = 4, GPK_TIMED_COV = 5, GPK_TIMED_JAC = 6 };
 GPK_API int gpk_timing(gpk_handle h, int enable);
 GPK_API int gpk_kernel_times(gpk_handle h, int tag, double* ms, int max_n, int* n_out);
 
@@ -366,6 +367,45 @@ GPK_API int gpk_predict_host_cov(gpk_handle h, const double* X, const double* al
                                  const double* ls, double sf2, const double* y_mean, const double* y_std, const double* W,
                                  int64_t Np, int64_t ldw, double noise, const double* Xq_host, int64_t M, double* mean_host,
                                  double* cov_host);
+
+/* ---- K8: input gradients of the posterior (fp64) ------------------------------------------------------------------
+ * With u_jd = (x_jd - xq_md) / ls_d^2 (exact differences):
+ *   dmean[m][p][d] = y_std[p] sum_j k(xq_m, x_j) u_jd alpha[j][p]                  (un-normalised, like gpk_predict_mean)
+ *   dvar[m][d]     = -2 sum_j k(xq_m, x_j) u_jd c_j,   c = K^-1 k* = W^T (W k*)    (normalised-target units)
+ * The N x M x D tensor of kernel derivatives is never stored.  dvar is the gradient of the UNCLIPPED kss - |W k*|^2; var is
+ * clipped exactly as gpk_predict_var_inv clips it.  The gradient of the standard deviation is dvar / (2 std).
+ * gpk_predict_mean_grad: one fused launch in the tiling of gpk_predict_mean (training rows through LDS, one exp per pair,
+ *   D x P running sums per query split into output groups of <= 4) + the fixed-order reduction of the training chunks.
+ *   X dev (N x D), alpha dev (N x P), Xq dev (M x D), dmean dev (M x P x D); ls, y_std host.  D, P <= 16.
+ * gpk_predict_var_grad_inv: K* (gpk_cross_gram_t), V = W K* and C = W^T V (two tile GEMMs on the fp64 matrix cores, W's zero
+ *   triangle skipped in both: 2 N^2 M flops), then ONE streaming pass over the three Np x Mp panels.  W: the inverse factor
+ *   (dev Np x ldw, gpk_trtri); work: dev double[3 * Np * Mp], Mp = gpk_padded(M); var: dev double[M] or NULL; dvar: dev (M x D).
+ *   Queries are independent: a caller panels them as it likes (there is no solve route and no fp32 form).
+ * gpk_predict_host_grad: the one-call serving form - host queries in (M x D), host results out, one synchronisation, queries
+ *   and results through the handle's pinned, mapped block.  mean_host (M x P) and dmean_host (M x P x D) un-normalised;
+ *   var_host (M) and dvar_host (M x D) in normalised-target units, or both NULL: mean + Jacobian only (W may then be NULL).
+ *   Up to 32 queries (D, P <= 16, N <= 16384): mean + Jacobian in ONE launch (the Jacobian's shares ride in
+ *   small_cross_mean_kernel), all four results in three (+ small_var_kernel storing V, + small_wtv_grad_kernel), every
+ *   reduction by the last workgroup in a fixed order: bit-identical from run to run.  33 .. GPK_HOST_MAX_M queries: the two
+ *   building blocks above inside the same call, the variance gradient in query panels of <= 6 GiB.
+ * gpk_predict_model_grad: the composite - the model of gpk_fit / gpk_import, host fp64 buffers: Xq (M x D), mean (M x P),
+ *   dmean (M x P x D), and var (M x P) / dvar (M x P x D) per output (already multiplied by y_std[p]^2), or both NULL;
+ *   var_includes_noise as in gpk_predict.  Forms the inverse factor if the model does not hold it yet.  Any M.
+ * Replaces: nothing in the reference - scikit-learn has no gradient call.  A caller would take central differences of
+ *   GaussianProcessRegressor.predict (sklearn/gaussian_process/_gpr.py:441-494), 2 D (fourth order: 4 D) calls per horizon,
+ *   around the loop of src/px4/mpc.py:1490-1506; the consumer is the linearisation of
+ *   quadrotor_gp_mpc/quadrotor_gp_mpc/mpc_controller.py:318 (linearize_dynamics).                                          */
+GPK_API int gpk_predict_mean_grad(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
+                                  double sf2, const double* y_std, const double* Xq, int64_t M, double* dmean);
+GPK_API int gpk_predict_var_grad_inv(gpk_handle h, const double* X, int64_t N, int D, const double* ls, double sf2,
+                                     const double* W, int64_t Np, int64_t ldw, const double* Xq, int64_t M, double kss,
+                                     double floor, double* work, double* var, double* dvar);
+GPK_API int gpk_predict_host_grad(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
+                                  double sf2, const double* y_mean, const double* y_std, const double* W, int64_t Np,
+                                  int64_t ldw, double kss, double floor, const double* Xq_host, int64_t M, double* mean_host,
+                                  double* var_host, double* dmean_host, double* dvar_host);
+GPK_API int gpk_predict_model_grad(gpk_handle h, const double* Xq, int64_t M, double* mean, double* var, double* dmean,
+                                   double* dvar, int var_includes_noise);
 
 /* ---- K6a: log-marginal-likelihood terms -----------------------------------------------------
  * terms[0] = sum_{i<N} log L[i][i]; terms[1 + p] = sum_i Y[i][p] * alpha[i][p]  (host doubles).

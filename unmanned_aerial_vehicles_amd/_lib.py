@@ -18,6 +18,7 @@ GPK_TILE, GPK_MAX_D, GPK_MAX_P = 128, 64, 16
 GPK_HOST_MAX_M = 4096
 GPK_TIMED_K5, GPK_TIMED_GRAM, GPK_TIMED_GRAD, GPK_TIMED_POTRF = 1, 2, 3, 4
 GPK_TIMED_COV = 5
+GPK_TIMED_JAC = 6
 
 _vp, _i64, _int, _dbl = C.c_void_p, C.c_int64, C.c_int, C.c_double
 _dp = C.POINTER(C.c_double)
@@ -90,6 +91,12 @@ SIGNATURES = {
     "gpk_predict_host_cov": (_int, [_vp, _vp, _vp, _i64, _int, _int, _vp, _dbl, _vp, _vp, _vp, _i64, _i64, _dbl, _vp, _i64,
                                     _vp, _vp]),
     "gpk_predict_model_cov": (_int, [_vp, _dp, _i64, _dp, _dp]),
+    "gpk_predict_mean_grad": (_int, [_vp, _vp, _vp, _i64, _int, _int, _dp, _dbl, _dp, _vp, _i64, _vp]),
+    "gpk_predict_var_grad_inv": (_int, [_vp, _vp, _i64, _int, _dp, _dbl, _vp, _i64, _i64, _vp, _i64, _dbl, _dbl, _vp, _vp, _vp]),
+    # (host pointers as void*, as gpk_predict_host)
+    "gpk_predict_host_grad": (_int, [_vp, _vp, _vp, _i64, _int, _int, _vp, _dbl, _vp, _vp, _vp, _i64, _i64, _dbl, _dbl, _vp,
+                                     _i64, _vp, _vp, _vp, _vp]),
+    "gpk_predict_model_grad": (_int, [_vp, _dp, _i64, _dp, _dp, _dp, _dp, _int]),
     "gpk_lml_terms": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _int, _dp]),
     "gpk_potri": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),
     "gpk_lml_grad": (_int, [_vp, _vp, _i64, _int, _dp, _dbl, _dbl, _vp, _int, _vp, _i64, _dp]),

@@ -236,6 +236,12 @@ size_t gpk_small_cov_work_doubles(int64_t Np);
 int gpk_small_cov(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls, double sf2,
                   const double* y_mean, const double* y_std, const double* W, int64_t Np, int64_t ldw, double noise,
                   const double* Xq, int64_t M, double* work, double* mean_out, double* cov_out);
+// posterior mean + its Jacobian (one launch) and, with var_out / dvar_out, variance + its gradient (three launches) of M <= 32 queries
+size_t gpk_small_grad_work_doubles(int64_t Np, int M, int D, int P);
+int gpk_small_grad(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls, double sf2,
+                   const double* y_mean, const double* y_std, const double* W, int64_t Np, int64_t ldw, double kss, double floor_,
+                   const double* Xq, int64_t M, double* work, double* mean_out, double* var_out, double* dmean_out,
+                   double* dvar_out);
 int gpk_small_predict(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D, int P,
                       const double* ls, const double* sf2, const double* y_mean, const double* y_std,
                       const double* const* W, int64_t Np, int64_t ldw, const double* kss, double floor_,

@@ -468,6 +468,37 @@ extern "C" int gpk_predict_model_cov(gpk_handle h, const double* Xq, int64_t M, 
   return GPK_OK;
 }
 
+extern "C" int gpk_predict_model_grad(gpk_handle h, const double* Xq, int64_t M, double* mean, double* var, double* dmean,
+                                      double* dvar, int var_includes_noise) {
+  if (!h) return GPK_BAD_ARG;
+  gpk_model* m = h->model;
+  GPK_REQUIRE(h, m && m->fitted, "predict_model_grad: no model (call gpk_fit or gpk_import first)");
+  GPK_REQUIRE(h, Xq && mean && dmean && M >= 1, "predict_model_grad: null pointer or empty batch");
+  GPK_REQUIRE(h, (var == nullptr) == (dvar == nullptr), "predict_model_grad: var and dvar come together (both or neither)");
+  GPK_CHECK_HIP(h, hipSetDevice(h->device));
+  const int D = m->D, P = m->P;
+  for (int64_t i = 0; i < M * D; ++i) GPK_REQUIRE(h, std::isfinite(Xq[i]), "predict_model_grad: Xq contains NaN or infinity");
+  // k** and the clip as gpk_predict: sklearn surface sf2 + noise, clipped at 0; package surface sf2, floored at 1e-10
+  const double kss = m->sf2 + (var_includes_noise ? m->noise : 0.0), floor_ = var_includes_noise ? 0.0 : 1e-10;
+  if (var) GPK_TRY(ensure_W(h, m));
+  std::vector<double> v1, g1;
+  for (int64_t m0 = 0; m0 < M; m0 += GPK_HOST_MAX_M) {
+    const int64_t mc = M - m0 < GPK_HOST_MAX_M ? M - m0 : GPK_HOST_MAX_M;
+    if (var) { v1.resize((size_t)mc); g1.resize((size_t)mc * D); }
+    GPK_TRY(gpk_predict_host_grad(h, m->X, m->alpha, m->N, D, P, m->ls, m->sf2, m->y_mean, m->y_std, var ? m->W : nullptr, m->Np,
+                                  m->Np, kss, floor_, Xq + m0 * D, mc, mean + m0 * P, var ? v1.data() : nullptr,
+                                  dmean + m0 * P * D, var ? g1.data() : nullptr));
+    if (var)      // undo the normalisation (sklearn/_gpr.py:487-489): output p carries y_std[p]^2
+      for (int64_t i = 0; i < mc; ++i)
+        for (int p = 0; p < P; ++p) {
+          const double s2 = m->y_std[p] * m->y_std[p];
+          var[(m0 + i) * P + p] = v1[(size_t)i] * s2;
+          for (int d = 0; d < D; ++d) dvar[((m0 + i) * P + p) * D + d] = g1[(size_t)i * D + d] * s2;
+        }
+  }
+  return GPK_OK;
+}
+
 extern "C" int gpk_lml(gpk_handle h, const double* theta, int n_theta, double* lml, double* grad) {
   if (!h) return GPK_BAD_ARG;
   gpk_model* m = h->model;

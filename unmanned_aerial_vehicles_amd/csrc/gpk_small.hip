@@ -17,6 +17,13 @@
 //                            order in two levels - the last workgroup of each group of CG adds its group's, the last
 //                            of those adds the group sums - and K(Xq, Xq) + noise I - sum is written, mirrored.
 //
+//   input gradients (K8)     small_cross_mean_jac_kernel adds the workgroup's share of the mean Jacobian
+//                            sum_j k*_mj alpha_jp (x_jd - q_md) / ls_d to the same launch (mean + Jacobian: still ONE launch,
+//                            the last workgroup adds both kinds of shares in a fixed order); for the variance gradient
+//                            small_var_grad_kernel also stores its rows of V = W K*^T, and small_wtv_grad_kernel - 16
+//                            columns of W per workgroup - forms C = W^T V, its share of sum_j k*_mj C_jm (x_jd - q_md) / ls_d
+//                            and, in the last workgroup, -2 / ls_d times the fixed-order sum of the shares.
+//
 // Both results land in the caller's (pinned, mapped) output block; the queries are read from it as well.
 #include "gpk_internal.h"
 #include "gpk_math.h"
@@ -97,12 +104,49 @@ __device__ __forceinline__ void finish_means(const double* pmean, unsigned share
   }
 }
 
+// The fixed-order sum of the mean-Jacobian shares (pjac: shares x M * P * D, entry t = (m * P + p) * D + d), by one workgroup
+// once every share is complete: dmean[m][p][d] = y_std[p] / ls_d * sum.
+__device__ __forceinline__ void finish_jac(const double* pjac, unsigned shares, int M, int P, int D, const double* ystd,
+                                           const double* ls, double* dmean_out, int tid, int nthreads) {
+  const int MPD = M * P * D;
+  // four entries per thread and eight shares of each in flight (the workgroup reads the shares from memory: with one entry
+  // at a time the miss latencies of M P D / nthreads entries would queue up behind each other); every entry's shares are
+  // added in share order whatever the grouping
+  for (int base = 0; base < MPD; base += 4 * nthreads) {
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (unsigned g = 0; g < shares; g += 8) {
+      double v[4][8];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int t = min(base + tid + e * nthreads, MPD - 1);
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          v[e][u] = pjac[(long long)min(g + u, shares - 1) * MPD + t];
+          if (g + u >= shares) v[e][u] = 0.0;
+        }
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int u = 0; u < 8; ++u) s[e] += v[e][u];
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int t = base + tid + e * nthreads;
+      if (t < MPD) dmean_out[t] = ystd[(t / D) % P] / ls[t % D] * s[e];
+    }
+  }
+}
+
 // FINISH: this launch is the only one (mean-only call) and elects the workgroup that writes the means; otherwise
 // small_var_kernel's last workgroup does it.
-template <bool FINISH>
-__global__ __launch_bounds__(256) void small_cross_mean_kernel(SmallK k, long long N, long long Np, int D, int P,
+// JAC (one model; small_cross_mean_jac_kernel): the launch also forms the mean Jacobian's shares (pjac) and - FINISH - the
+// Jacobian itself (dmean_out).  The body is shared; small_cross_mean_kernel keeps its signature and its launches.
+template <bool FINISH, bool JAC>
+__device__ __forceinline__ void small_cross_mean_body(SmallK k, long long N, long long Np, int D, int P,
                                                                const double* __restrict__ Xq, int M, double* Ks,
-                                                               double* pmean, unsigned* counter, double* mean_out) {
+                                                               double* pmean, unsigned* counter, double* mean_out,
+                                                               double* pjac, double* dmean_out) {
   __shared__ double q[SQ][SD + 1];
   __shared__ double ks[SQ][SJ + 1];
   __shared__ double al[SJ][SP + 1];
@@ -154,6 +198,15 @@ __global__ __launch_bounds__(256) void small_cross_mean_kernel(SmallK k, long lo
       if (Ks) Ks[(long long)m * Np + j] = v;
     }
   }
+  double (*xs)[SD + 1] = nullptr;                   // JAC: the staged training rows, divided by the length-scales
+  if constexpr (JAC) {
+    __shared__ double xs_s[SJ][SD + 1];
+    xs = xs_s;
+    if (mg == 0) {
+#pragma unroll
+      for (int d = 0; d < SD; ++d) xs[jl][d] = xr[d];
+    }
+  }
   __syncthreads();
   for (int t = tid; t < M * P; t += 256) {
     const int m = t / P, p = t - m * P;
@@ -162,12 +215,39 @@ __global__ __launch_bounds__(256) void small_cross_mean_kernel(SmallK k, long lo
     for (int jj = 0; jj < SJ; ++jj) s = __builtin_fma(ks[m][jj], al[jj][p], s);
     pmean[(long long)blockIdx.x * (SQ * SP) + t] = s;
   }
+  if constexpr (JAC) {
+    // share of sum_j k*_mj alpha_jp (x_jd - q_md) / ls_d, entry t = (m * P + p) * D + d
+    const int MPD = M * P * D;
+    for (int t = tid; t < MPD; t += 256) {
+      const int d = t % D, mp = t / D, p = mp % P, m = mp / P;
+      const double qd = q[m][d];
+      double s = 0.0;
+#pragma unroll 8
+      for (int jj = 0; jj < SJ; ++jj) s = __builtin_fma(ks[m][jj] * al[jj][p], xs[jj][d] - qd, s);
+      pjac[(long long)blockIdx.x * MPD + t] = s;
+    }
+  }
   if constexpr (FINISH) {
     if (last_workgroup(counter, tid)) {
       __shared__ double fin[4 * SQ * SP];
       finish_means(pmean, gridDim.x, M, P, k.ymean + b * P, k.ystd + b * P, mean_out, tid, fin);
+      if constexpr (JAC) finish_jac(pjac, gridDim.x, M, P, D, k.ystd + b * P, ls, dmean_out, tid, 256);
     }
   }
+}
+
+template <bool FINISH>
+__global__ __launch_bounds__(256) void small_cross_mean_kernel(SmallK k, long long N, long long Np, int D, int P,
+                                                               const double* __restrict__ Xq, int M, double* Ks,
+                                                               double* pmean, unsigned* counter, double* mean_out) {
+  small_cross_mean_body<FINISH, false>(k, N, Np, D, P, Xq, M, Ks, pmean, counter, mean_out, nullptr, nullptr);
+}
+template <bool FINISH>
+__global__ __launch_bounds__(256) void small_cross_mean_jac_kernel(SmallK k, long long N, long long Np, int D, int P,
+                                                                   const double* __restrict__ Xq, int M, double* Ks,
+                                                                   double* pmean, unsigned* counter, double* mean_out,
+                                                                   double* pjac, double* dmean_out) {
+  small_cross_mean_body<FINISH, true>(k, N, Np, D, P, Xq, M, Ks, pmean, counter, mean_out, pjac, dmean_out);
 }
 
 // NMB = 1: up to 16 queries, 2: up to 32.  8 waves: wave w takes the 64-wide k-chunks w, w + 8, ..., the loads of
@@ -202,11 +282,15 @@ __device__ __forceinline__ void vmul(const VFrag<NMB>& f, long long kc, int kq, 
   }
 }
 
-template <int NMB>
-__global__ __launch_bounds__(64 * VW) void small_var_kernel(SmallK k, long long ldw, long long Np, const double* Ks,
+// GRAD (one model; small_var_grad_kernel): the launch also stores its rows of V (Vs: Np x SQ, columns < 16 NMB written) for
+// small_wtv_grad_kernel, and workgroup 1 adds the mean Jacobian's shares of the previous launch.  The body is shared;
+// small_var_kernel keeps its signature and its launches.
+template <int NMB, bool GRAD>
+__device__ __forceinline__ void small_var_body(SmallK k, long long ldw, long long Np, const double* Ks,
                                                             int M, int P, double floor_, const double* pmean,
                                                             unsigned mean_shares, double* pvar, unsigned* counter,
-                                                            double* mean_out, double* var_out) {
+                                                            double* mean_out, double* var_out, double* Vs,
+                                                            const double* pjac, int D, double* dmean_out) {
   __shared__ double red[VW][NMB][16][17];
   __shared__ double sq[NMB][16][17];
   const int b = blockIdx.y;
@@ -252,6 +336,7 @@ __global__ __launch_bounds__(64 * VW) void small_var_kernel(SmallK k, long long 
 #pragma unroll
     for (int u = 0; u < VW; ++u) v += red[u][mb][r][c];
     sq[mb][r][c] = v * v;
+    if constexpr (GRAD) Vs[(r0 + r) * SQ + 16 * mb + c] = v;
   }
   __syncthreads();
   if (tid < NMB * 16) {
@@ -265,6 +350,9 @@ __global__ __launch_bounds__(64 * VW) void small_var_kernel(SmallK k, long long 
   // the others are still multiplying, off the critical path (scratch: the reduction buffer, free by now).
   static_assert(VW * 16 * 17 >= 4 * SQ * SP, "the reduction buffer doubles as the mean scratch");
   if (blockIdx.x == 0) finish_means(pmean, mean_shares, M, P, k.ymean + b * P, k.ystd + b * P, mean_out, tid, &red[0][0][0][0]);
+  if constexpr (GRAD) {
+    if (blockIdx.x == 1) finish_jac(pjac, mean_shares, M, P, D, k.ystd, k.ls[0], dmean_out, tid, 64 * VW);
+  }
   if (last_workgroup(counter, tid)) {
     __shared__ double part[2 * VW][SQ];
     const int m = tid & 31, pt = tid >> 5;
@@ -277,6 +365,24 @@ __global__ __launch_bounds__(64 * VW) void small_var_kernel(SmallK k, long long 
       var_out[tid] = fmax(kss - t, floor_);
     }
   }
+}
+
+template <int NMB>
+__global__ __launch_bounds__(64 * VW) void small_var_kernel(SmallK k, long long ldw, long long Np, const double* Ks,
+                                                            int M, int P, double floor_, const double* pmean,
+                                                            unsigned mean_shares, double* pvar, unsigned* counter,
+                                                            double* mean_out, double* var_out) {
+  small_var_body<NMB, false>(k, ldw, Np, Ks, M, P, floor_, pmean, mean_shares, pvar, counter, mean_out, var_out, nullptr, nullptr, 0,
+                             nullptr);
+}
+template <int NMB>
+__global__ __launch_bounds__(64 * VW) void small_var_grad_kernel(SmallK k, long long ldw, long long Np, const double* Ks,
+                                                                 int M, int P, double floor_, const double* pmean,
+                                                                 unsigned mean_shares, double* pvar, unsigned* counter,
+                                                                 double* mean_out, double* var_out, double* Vs,
+                                                                 const double* pjac, int D, double* dmean_out) {
+  small_var_body<NMB, true>(k, ldw, Np, Ks, M, P, floor_, pmean, mean_shares, pvar, counter, mean_out, var_out, Vs, pjac, D,
+                            dmean_out);
 }
 
 // Every one of `count` workgroups has stored its part; true (in all its threads) for the last one: last_workgroup with
@@ -392,6 +498,118 @@ __global__ __launch_bounds__(64 * VW) void small_cov_kernel(SmallK k, long long 
   }
 }
 
+// Variance gradient of M <= 32 queries (one model), after small_cross_mean_kernel (K*: Ks, query-major) and
+// small_var_grad_kernel (V: Vs, Np x SQ): 16 columns of W per workgroup.  C[j][m] = sum_{r >= j} W[r][j] V[r][m] on the
+// vector ALU (thread = column jl, query half mh, row group rg of 16; the row groups are added in a fixed order through LDS),
+// then the workgroup's share of sum_j k*_mj C_jm (x_jd - q_md) / ls_d (pdv: gridDim.x x M * D); the last workgroup adds the
+// shares in order and writes dvar[m][d] = -2 / ls_d * sum.  pdv: gridDim.x * gridDim.y shares.
+constexpr unsigned WTV_MAX_ROW_CHUNKS = 4;
+constexpr int GW = 16, GRG = 16, GT = GW * 2 * GRG;      // 512 threads: column jl, query half mh, row group rg
+__global__ __launch_bounds__(GT) void small_wtv_grad_kernel(SmallK k, long long ldw, long long N, long long Np, int D,
+                                                            const double* __restrict__ Ks, const double* __restrict__ Vs,
+                                                            const double* __restrict__ Xq, int M, double* pdv,
+                                                            unsigned* counter, double* dvar_out) {
+  __shared__ double red[GRG][GW][17];
+  __shared__ double cm[GW][SQ + 1];
+  __shared__ double xs[GW][SD + 1];
+  __shared__ double qs[SQ][SD + 1];
+  __shared__ double half[2][SQ * SD];
+  const double* __restrict__ W = k.W[0];
+  const double* __restrict__ X = k.X[0];
+  const double* ls = k.ls[0];
+  const int tid = threadIdx.x, jl = tid & 15, mh = (tid >> 4) & 1, rg = tid >> 5;
+  const long long j0 = (long long)blockIdx.x * GW, j = j0 + jl;
+  // queries and this workgroup's training rows, divided by the length-scales
+  for (int e = tid; e < M * D; e += GT) qs[e / D][e % D] = Xq[e] / ls[e % D];
+  for (int e = tid; e < GW * D; e += GT) {
+    const int jj = e / D, d = e - jj * D;
+    xs[jj][d] = (j0 + jj < N) ? X[(j0 + jj) * D + d] / ls[d] : 0.0;
+  }
+  double acc[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) acc[i] = 0.0;
+  const bool active = 16 * mh < M;                    // (M <= 16: the second query half holds nothing)
+  if (active) {
+    // rows r = j0 + rg + GRG * it, four at a time: their loads go out together (the loop is a chain of L2 latencies);
+    // rows beyond the end are clamped to the last one and enter with weight zero
+    // (blockIdx.y: the rows below the diagonal cut into gridDim.y equal chunks - C is linear in them, so every chunk simply
+    // contributes its own share; small models have too few column blocks to fill the device otherwise)
+    const long long span = ((Np - j0 + gridDim.y - 1) / gridDim.y + GRG - 1) / GRG * GRG;
+    const long long rb = j0 + blockIdx.y * span, re = min(Np, rb + span);
+    for (long long r0 = rb + rg; r0 < re; r0 += 4 * GRG) {
+      double w[4];
+      d2v v[4][8];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const long long r = r0 + u * GRG, rc = min(r, Np - 1);
+        w[u] = W[rc * ldw + j];
+        if (r >= re || r < j) w[u] = 0.0;             // strictly-upper entries never enter
+        const d2v* vp = reinterpret_cast<const d2v*>(Vs + rc * SQ + 16 * mh);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[u][i] = vp[i];
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          acc[2 * i] = __builtin_fma(w[u], v[u][i].x, acc[2 * i]);
+          acc[2 * i + 1] = __builtin_fma(w[u], v[u][i].y, acc[2 * i + 1]);
+        }
+    }
+  }
+  // the row groups are added in order, one query half at a time (the buffer holds 16 queries)
+  for (int hq = 0; hq < 2; ++hq) {
+    __syncthreads();
+    if (mh == hq) {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) red[rg][jl][i] = acc[i];
+    }
+    __syncthreads();
+    if (tid < GW * 16) {
+      const int jj = tid >> 4, i = tid & 15, m = 16 * hq + i;
+      double v = 0.0;
+#pragma unroll
+      for (int u = 0; u < GRG; ++u) v += red[u][jj][i];
+      cm[jj][m] = (m < M) ? v : 0.0;                  // (columns >= M of V: duplicates of query M - 1 or unwritten)
+    }
+  }
+  __syncthreads();
+  const int MD = M * D;
+  for (int t = tid; t < MD; t += GT) {
+    const int m = t / D, d = t - m * D;
+    const double qd = qs[m][d];
+    double s = 0.0;
+#pragma unroll
+    for (int jj = 0; jj < GW; ++jj) s = __builtin_fma(Ks[(long long)m * Np + j0 + jj] * cm[jj][m], xs[jj][d] - qd, s);
+    pdv[((long long)blockIdx.y * gridDim.x + blockIdx.x) * MD + t] = s;
+  }
+  if (last_of(counter, gridDim.x * gridDim.y, tid)) {
+    // each entry's shares in two halves (thread halves), each half in share order with sixteen loads in flight - the chain
+    // of misses is the cost - then half 0 + half 1
+    const unsigned ns = gridDim.x * gridDim.y, h0 = (ns + 1) / 2;
+    for (int base = 0; base < MD; base += GT / 2) {
+      const int part = tid / (GT / 2), t = base + tid - part * (GT / 2);
+      const unsigned g0 = part ? h0 : 0, g1 = part ? ns : h0;
+      if (t < MD) {
+        double sum = 0.0;
+        for (unsigned g = g0; g < g1; g += 16) {
+          double v[16];
+#pragma unroll
+          for (int u = 0; u < 16; ++u) {
+            v[u] = pdv[(long long)min(g + u, g1 - 1) * MD + t];
+            if (g + u >= g1) v[u] = 0.0;
+          }
+#pragma unroll
+          for (int u = 0; u < 16; ++u) sum += v[u];
+        }
+        half[part][t] = sum;
+      }
+      __syncthreads();
+      if (part == 0 && t < MD) dvar_out[t] = -2.0 / ls[t % D] * (half[0][t] + half[1][t]);
+    }
+  }
+}
+
 }  // namespace
 
 size_t gpk_small_work_doubles(int64_t Np, int B) { return (size_t)B * Np * (SQ + SQ * SP / SJ + SQ / SR); }
@@ -445,6 +663,14 @@ int gpk_small_predict(gpk_handle h, int B, const double* const* X, const double*
   return GPK_OK;
 }
 
+// the zero-initialised ticket counters of the covariance reduction and of small_wtv_grad_kernel, allocated on first use
+static int ensure_cov_counters(gpk_handle h) {
+  if (h->d_cov_count) return GPK_OK;
+  GPK_CHECK_HIP(h, hipMalloc((void**)&h->d_cov_count, GPK_SMALL_COV_COUNTERS * sizeof(unsigned)));
+  GPK_CHECK_HIP(h, hipMemsetAsync(h->d_cov_count, 0, GPK_SMALL_COV_COUNTERS * sizeof(unsigned), h->stream));
+  return GPK_OK;
+}
+
 size_t gpk_small_cov_work_doubles(int64_t Np) {
   const size_t shares = (size_t)(Np / SR), groups = (shares + CG - 1) / CG;
   return (size_t)Np * (SQ + SQ * SP / SJ) + (shares + groups) * CE;
@@ -458,10 +684,7 @@ int gpk_small_cov(gpk_handle h, const double* X, const double* alpha, int64_t N,
   GPK_REQUIRE(h, gpk_small_ok(Np, D, P, M) && Np == gpk_padded(N), "small cov: shape outside the small-batch path");
   GPK_REQUIRE(h, X && alpha && W && ldw >= Np && ldw % 2 == 0 && ((uintptr_t)W % 16) == 0,
               "small cov: needs the (16-byte aligned) inverse factor");
-  if (!h->d_cov_count) {
-    GPK_CHECK_HIP(h, hipMalloc((void**)&h->d_cov_count, GPK_SMALL_COV_COUNTERS * sizeof(unsigned)));
-    GPK_CHECK_HIP(h, hipMemsetAsync(h->d_cov_count, 0, GPK_SMALL_COV_COUNTERS * sizeof(unsigned), h->stream));
-  }
+  GPK_TRY(ensure_cov_counters(h));
   SmallK k{};
   k.X[0] = X; k.alpha[0] = alpha; k.W[0] = W;
   for (int d = 0; d < 16; ++d) k.ls[0][d] = 1.0;
@@ -486,6 +709,69 @@ int gpk_small_cov(gpk_handle h, const double* X, const double* alpha, int64_t N,
   else
     hipLaunchKernelGGL(small_cov_kernel<2>, dim3(gb), dim3(64 * VW), 0, h->stream, k, (long long)ldw, (long long)Np, Ks, (int)M,
                        D, P, noise, Xq, pmean, ga, pcov, gcov, h->d_cov_count, mean_out, cov_out);
+  GPK_LAUNCH_CHECK(h);
+  return GPK_OK;
+}
+
+size_t gpk_small_grad_work_doubles(int64_t Np, int M, int D, int P) {
+  const size_t ga = (size_t)(Np / SJ), gb = (size_t)(Np / SR);
+  return gpk_small_work_doubles(Np, 1) + ga * (size_t)(M * P * D) + (size_t)Np * SQ + gb * WTV_MAX_ROW_CHUNKS * (size_t)(M * D);
+}
+
+// Posterior mean (M x P) and its Jacobian (M x P x D, un-normalised) of M <= 32 queries of one model in ONE launch
+// small_cross_mean_jac_kernel<true>; with var_out / dvar_out also the variance (M) and its gradient (M x D), normalised-target
+// units, in three launches (+ small_var_grad_kernel, small_wtv_grad_kernel).  No synchronisation; Xq and the outputs may be
+// pinned, mapped host memory.
+int gpk_small_grad(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls, double sf2,
+                   const double* y_mean, const double* y_std, const double* W, int64_t Np, int64_t ldw, double kss, double floor_,
+                   const double* Xq, int64_t M, double* work, double* mean_out, double* var_out, double* dmean_out,
+                   double* dvar_out) {
+  GPK_REQUIRE(h, gpk_small_ok(Np, D, P, M) && Np == gpk_padded(N), "small grad: shape outside the small-batch path");
+  GPK_REQUIRE(h, X && alpha && mean_out && dmean_out && (var_out == nullptr) == (dvar_out == nullptr), "small grad: null pointer");
+  GPK_REQUIRE(h, !var_out || (W && ldw >= Np && ldw % 2 == 0 && ((uintptr_t)W % 16) == 0),
+              "small grad: the variance gradient needs the (16-byte aligned) inverse factor");
+  if (var_out) GPK_TRY(ensure_cov_counters(h));
+  SmallK k{};
+  k.X[0] = X; k.alpha[0] = alpha; k.W[0] = var_out ? W : nullptr;
+  for (int d = 0; d < 16; ++d) k.ls[0][d] = 1.0;
+  for (int d = 0; d < D; ++d) {
+    GPK_REQUIRE(h, ls[d] > 0.0, "length-scales must be positive");
+    k.ls[0][d] = ls[d];
+  }
+  k.sf2[0] = sf2;
+  k.kss[0] = var_out ? kss : 0.0;
+  for (int o = 0; o < P; ++o) { k.ymean[o] = y_mean[o]; k.ystd[o] = y_std[o]; }
+  const unsigned ga = (unsigned)(Np / SJ), gb = (unsigned)(Np / SR);
+  static_assert(SR == GW, "small_wtv_grad_kernel takes as many columns of W per workgroup as small_var_kernel takes rows");
+  double* Ks = work;                                       // SQ x Np
+  double* pmean = Ks + (size_t)SQ * Np;                    // ga x (SQ * SP)
+  double* pvar = pmean + (size_t)ga * (SQ * SP);           // gb x SQ
+  double* pjac = pvar + (size_t)gb * SQ;                   // ga x (M * P * D)
+  double* Vs = pjac + (size_t)ga * (M * P * D);            // Np x SQ
+  double* pdv = Vs + (size_t)Np * SQ;                      // (gb x row chunks) x (M * D)
+  if (!var_out) {
+    hipLaunchKernelGGL((small_cross_mean_jac_kernel<true>), dim3(ga, 1), dim3(256), 0, h->stream, k, (long long)N,
+                       (long long)Np, D, P, Xq, (int)M, (double*)nullptr, pmean, h->d_count, mean_out, pjac, dmean_out);
+    GPK_LAUNCH_CHECK(h);
+    return GPK_OK;
+  }
+  hipLaunchKernelGGL(small_cross_mean_jac_kernel<false>, dim3(ga, 1), dim3(256), 0, h->stream, k, (long long)N,
+                     (long long)Np, D, P, Xq, (int)M, Ks, pmean, h->d_count, mean_out, pjac, dmean_out);
+  GPK_LAUNCH_CHECK(h);
+  if (M <= 16)
+    hipLaunchKernelGGL(small_var_grad_kernel<1>, dim3(gb, 1), dim3(64 * VW), 0, h->stream, k, (long long)ldw, (long long)Np,
+                       (const double*)Ks, (int)M, P, floor_, (const double*)pmean, ga, pvar, h->d_count + GPK_SMALL_MAX_MODELS,
+                       mean_out, var_out, Vs, (const double*)pjac, D, dmean_out);
+  else
+    hipLaunchKernelGGL(small_var_grad_kernel<2>, dim3(gb, 1), dim3(64 * VW), 0, h->stream, k, (long long)ldw, (long long)Np,
+                       (const double*)Ks, (int)M, P, floor_, (const double*)pmean, ga, pvar, h->d_count + GPK_SMALL_MAX_MODELS,
+                       mean_out, var_out, Vs, (const double*)pjac, D, dmean_out);
+  GPK_LAUNCH_CHECK(h);
+  // up to 4 row chunks per column block while that keeps the launch within one workgroup per CU (Np = 1024: 64 x 4)
+  unsigned rc = 256 / gb;
+  rc = rc < 1 ? 1 : (rc > WTV_MAX_ROW_CHUNKS ? WTV_MAX_ROW_CHUNKS : rc);
+  hipLaunchKernelGGL(small_wtv_grad_kernel, dim3(gb, rc), dim3(GT), 0, h->stream, k, (long long)ldw, (long long)N, (long long)Np, D,
+                     (const double*)Ks, (const double*)Vs, Xq, (int)M, pdv, h->d_cov_count + GPK_SMALL_COV_COUNTERS - 1, dvar_out);
   GPK_LAUNCH_CHECK(h);
   return GPK_OK;
 }

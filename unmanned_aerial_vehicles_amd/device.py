@@ -462,6 +462,19 @@ class DeviceGP:
             return False
         return (not want_var) or ("f64" in self._Winv) or self.Np <= self.INVERSE_EAGER_NP
 
+    def _host_call_args(self, y_mean, y_std):
+        """The argument addresses of the one-call serving entries (gpk_predict_host / _host_cov / _host_grad) that do not
+        change between calls, looked up once per (factorisation, target scaling): the X, alpha, ls, y_mean, y_std addresses
+        are entries [7:12].  These calls run at the control rate and every ctypes conversion costs about a microsecond."""
+        c = self._host_args
+        if (c is None or c[0] is not self.X or c[1] is not self.alpha or c[2] is not self.ls or c[3] is not y_mean
+                or c[4] is not y_std):
+            ym = np.ascontiguousarray(np.broadcast_to(np.asarray(y_mean, dtype=np.float64), (self.P,)))
+            ys = np.ascontiguousarray(np.broadcast_to(np.asarray(y_std, dtype=np.float64), (self.P,)))
+            c = self._host_args = (self.X, self.alpha, self.ls, y_mean, y_std, ym, ys, self.X.data_ptr(),
+                                   self.alpha.data_ptr(), self.ls.ctypes.data, ym.ctypes.data, ys.ctypes.data)
+        return c
+
     def predict_host(self, Xq, y_mean, y_std, kss=None, floor=0.0):
         """One C call per batch: host queries (M, D) float64 -> (mean (M, P), var (M,) or None) as NumPy arrays
         (mean un-normalised, var in normalised-target units); kss=None skips the variance."""
@@ -474,15 +487,7 @@ class DeviceGP:
         var = np.empty((M,)) if kss is not None else None
         W = self.inverse_factor(False) if kss is not None else None
         be = self.be
-        # the addresses that do not change between calls are looked up once per (factorisation, target scaling):
-        # this call runs at the control rate and every ctypes conversion costs about a microsecond
-        c = self._host_args
-        if (c is None or c[0] is not self.X or c[1] is not self.alpha or c[2] is not self.ls or c[3] is not y_mean
-                or c[4] is not y_std):
-            ym = np.ascontiguousarray(np.broadcast_to(np.asarray(y_mean, dtype=np.float64), (self.P,)))
-            ys = np.ascontiguousarray(np.broadcast_to(np.asarray(y_std, dtype=np.float64), (self.P,)))
-            c = self._host_args = (self.X, self.alpha, self.ls, y_mean, y_std, ym, ys, self.X.data_ptr(),
-                                   self.alpha.data_ptr(), self.ls.ctypes.data, ym.ctypes.data, ys.ctypes.data)
+        c = self._host_call_args(y_mean, y_std)
         with be.lock:
             be.bind_stream()
             be.check(be.lib.gpk_predict_host(be.h, c[7], c[8], self.N, self.D, self.P, c[9], self.sf2, c[10], c[11],
@@ -813,20 +818,106 @@ class DeviceGP:
         cov = np.empty((M, M))
         W = self.inverse_factor(False)
         be = self.be
-        # (addresses cached per factorisation and target scaling, as in predict_host: this call runs at the control rate)
-        c = self._host_args
-        if (c is None or c[0] is not self.X or c[1] is not self.alpha or c[2] is not self.ls or c[3] is not y_mean
-                or c[4] is not y_std):
-            ym = np.ascontiguousarray(np.broadcast_to(np.asarray(y_mean, dtype=np.float64), (self.P,)))
-            ys = np.ascontiguousarray(np.broadcast_to(np.asarray(y_std, dtype=np.float64), (self.P,)))
-            c = self._host_args = (self.X, self.alpha, self.ls, y_mean, y_std, ym, ys, self.X.data_ptr(),
-                                   self.alpha.data_ptr(), self.ls.ctypes.data, ym.ctypes.data, ys.ctypes.data)
+        c = self._host_call_args(y_mean, y_std)
         with be.lock:
             be.bind_stream()
             be.check(be.lib.gpk_predict_host_cov(be.h, c[7], c[8], self.N, self.D, self.P, c[9], self.sf2, c[10], c[11],
                                                  W.data_ptr(), self.Np, self.Np, float(noise), Xq.ctypes.data, M,
                                                  mean.ctypes.data, cov.ctypes.data))
         return mean, cov
+
+    # ---- input gradients of the posterior (K8) ----------------------------------------------------------------------
+    def predict_grad_dev(self, Xq, y_std, kss=None, floor=0.0):
+        """K8 on device tensors: (dmean (M, P, D), var (M,) or None, dvar (M, D) or None), float64.  dmean is the Jacobian of
+        the un-normalised mean (times y_std[p]); var / dvar - computed when `kss` is given - are in normalised-target units,
+        var clipped at `floor` as `predict_var_dev` clips it, dvar the gradient of the unclipped expression.  Always the fp64
+        kernels through the explicit inverse factor; a serving replica serves the mean Jacobian only."""
+        torch = _torch()
+        if kss is not None and self.replica:
+            raise RuntimeError("a serving replica holds no fp64 inverse factor: variance gradients are computed on the rank "
+                               "that fitted the model (the mean Jacobian is served here: kss=None)")
+        q = self._as_queries(Xq, torch.float64)
+        dmean = self.predict_mean_grad_dev(q, y_std)
+        if kss is None:
+            return dmean, None, None
+        var, dvar = self.predict_var_grad_dev(q, kss, floor)
+        return dmean, var, dvar
+
+    def predict_mean_grad_dev(self, Xq, y_std):
+        """gpk_predict_mean_grad on device tensors: the (M, P, D) Jacobian of the un-normalised posterior mean."""
+        torch = _torch()
+        assert self.factored
+        q = self._as_queries(Xq, torch.float64)
+        M = q.shape[0]
+        dmean = self.be.empty((M, self.P, self.D), torch.float64)
+        if M == 0:
+            return dmean
+        ys = np.ascontiguousarray(np.broadcast_to(np.asarray(y_std, dtype=np.float64), (self.P,)))
+        be = self.be
+        with be.lock:
+            be.bind_stream()
+            be.check(be.lib.gpk_predict_mean_grad(be.h, _p(self.X), _p(self.alpha), self.N, self.D, self.P,
+                                                  self.ls.ctypes.data_as(_lib._dp), self.sf2, ys.ctypes.data_as(_lib._dp),
+                                                  _p(q), M, _p(dmean)))
+        return dmean
+
+    def predict_var_grad_dev(self, Xq, kss, floor=0.0):
+        """gpk_predict_var_grad_inv on device tensors: (var (M,), dvar (M, D)) in normalised-target units.  The queries go in
+        panels whose three Np x Mp work panels fit VAR_PANEL_BYTES, so there is no limit on M."""
+        torch = _torch()
+        assert self.factored
+        if self.replica:
+            raise RuntimeError("a serving replica holds no fp64 inverse factor: variance gradients are computed on the rank "
+                               "that fitted the model (the mean Jacobian is served here: kss=None)")
+        q = self._as_queries(Xq, torch.float64)
+        M = q.shape[0]
+        var = self.be.empty((M,), torch.float64)
+        dvar = self.be.empty((M, self.D), torch.float64)
+        if M == 0:
+            return var, dvar
+        W = self.inverse_factor(False)
+        panel = max(128, min(self.VAR_PANEL_MAX, (self.VAR_PANEL_BYTES // (3 * self.Np * 8)) // 128 * 128))
+        panel = min(panel, padded(M))
+        work = self.be.empty((3 * self.Np * panel,), torch.float64)
+        be = self.be
+        lsp = self.ls.ctypes.data_as(_lib._dp)
+        with be.lock:
+            be.bind_stream()
+            for m0 in range(0, M, panel):
+                m1 = min(M, m0 + panel)
+                be.check(be.lib.gpk_predict_var_grad_inv(be.h, _p(self.X), self.N, self.D, lsp, self.sf2, _p(W), self.Np,
+                                                         self.Np, _p(q[m0:m1]), m1 - m0, float(kss), float(floor),
+                                                         _p(work), _p(var[m0:m1]), _p(dvar[m0:m1])))
+        del work
+        return var, dvar
+
+    def predict_grad_host(self, Xq, y_mean, y_std, kss=None, floor=0.0):
+        """One C call (gpk_predict_host_grad) for batches where `host_path_ok(M, kss is not None)` holds: host queries
+        (M, D) -> (mean (M, P), var (M,) or None, dmean (M, P, D), dvar (M, D) or None) as NumPy arrays, units as
+        `predict_grad_dev`.  Up to 32 queries: mean + Jacobian ONE launch, all four results three."""
+        assert self.factored
+        Xq = np.ascontiguousarray(Xq, dtype=np.float64)
+        if Xq.ndim != 2 or Xq.shape[1] != self.D:
+            raise ValueError(f"queries must be (M, {self.D})")
+        if kss is not None and self.replica:
+            raise RuntimeError("a serving replica holds no fp64 inverse factor: variance gradients are computed on the rank "
+                               "that fitted the model (the mean Jacobian is served here: kss=None)")
+        M = Xq.shape[0]
+        mean = np.empty((M, self.P))
+        dmean = np.empty((M, self.P, self.D))
+        var = np.empty((M,)) if kss is not None else None
+        dvar = np.empty((M, self.D)) if kss is not None else None
+        W = self.inverse_factor(False) if kss is not None else None
+        be = self.be
+        c = self._host_call_args(y_mean, y_std)
+        with be.lock:
+            be.bind_stream()
+            be.check(be.lib.gpk_predict_host_grad(be.h, c[7], c[8], self.N, self.D, self.P, c[9], self.sf2, c[10], c[11],
+                                                  W.data_ptr() if W is not None else None, self.Np, self.Np,
+                                                  float(kss) if kss is not None else 0.0, float(floor), Xq.ctypes.data, M,
+                                                  mean.ctypes.data, var.ctypes.data if var is not None else None,
+                                                  dmean.ctypes.data, dvar.ctypes.data if dvar is not None else None))
+        return mean, var, dmean, dvar
 
     # ---- gated serving: the one place every fp32 surface (estimator, sharded predictor, package GP, per-axis models) goes
     # through -------------------------------------------------------------------------------------------------------------

@@ -333,6 +333,65 @@ class GaussianProcessRegressor:
             return mean, cov * std2[0]
         return mean, cov[:, :, None] * std2[None, None, :]
 
+    def predict_jacobian(self, X, return_var=False):
+        """Posterior mean and its Jacobian with respect to the inputs - the first-order terms a model-predictive controller
+        linearises with - and, with return_var=True, the posterior variance and its input gradient.  scikit-learn has no such
+        call; both gradients are the closed forms of the RBF kernel, evaluated on the GPU (K8):
+
+            dmean[m, p, d] = y_std[p] sum_j k(x_m, x_j) (x_jd - x_md) / ls_d^2 alpha_jp
+            dvar[m, p, d]  = -2 y_std[p]^2 sum_j k(x_m, x_j) (x_jd - x_md) / ls_d^2 (K^-1 k_m)_j
+
+        Returns (y_mean, dmean) or (y_mean, dmean, y_var, dvar).  Shapes follow `predict`'s squeezing: y_mean (M, P) / (M,),
+        dmean (M, P, D) / (M, D) for one target; y_var = predict(X, return_std=True)[1] ** 2 (clipped at 0 like it), shaped
+        as y_mean; dvar shaped as dmean - the gradient of the unclipped variance.  The gradient of the standard deviation is
+        dvar / (2 std) (not returned: it is singular where std = 0).  Always computed by the fp64 kernels: a model with
+        predict_dtype="float32" serves them, and the mean and variance that go with them, in fp64.  Same input validation as
+        `predict`; an unfitted model returns the prior mean / variance and zero gradients."""
+        X = np.array(X, dtype=np.float64, ndmin=2)
+        if not np.isfinite(X).all():
+            raise ValueError("Input X contains NaN or infinity.")
+        M, D = X.shape
+        if not hasattr(self, "X_train_"):  # prior: constant mean and variance, zero gradients
+            n_t = self.n_targets if self.n_targets is not None else 1
+            kern = self.kernel if self.kernel is not None else (
+                ConstantKernel(1.0, constant_value_bounds="fixed") * RBF(1.0, length_scale_bounds="fixed"))
+            comp = kern.components()
+            mean = np.zeros((M, n_t))
+            dmean = np.zeros((M, n_t, D))
+            if n_t == 1:
+                mean, dmean = mean[:, 0], dmean[:, 0]
+            if not return_var:
+                return mean, dmean
+            return mean, dmean, np.full(mean.shape, comp.sf2 + (comp.noise or 0.0)), np.zeros(dmean.shape)
+        self._ensure_device()
+        dev = self._dev
+        kss = None
+        if return_var:
+            comp = self.kernel_.components()
+            kss = comp.sf2 + (comp.noise or 0.0)
+        if dev.host_path_ok(M, return_var):
+            # small batches (the MPC horizon): one C call, one synchronisation; up to 32 rows one launch (three with the variance)
+            mean, var, dmean, dvar = dev.predict_grad_host(X, self._y_train_mean, self._y_train_std, kss, 0.0)
+        else:
+            import torch
+            q = dev._as_queries(X, torch.float64)
+            mean = dev.predict_mean_dev(q, self._y_train_mean, self._y_train_std, "float64").cpu().numpy()
+            dmean_d, var_d, dvar_d = dev.predict_grad_dev(q, self._y_train_std, kss, 0.0)
+            dmean = dmean_d.cpu().numpy()
+            var = var_d.cpu().numpy() if return_var else None
+            dvar = dvar_d.cpu().numpy() if return_var else None
+        one = mean.shape[1] == 1
+        if one:
+            mean, dmean = mean[:, 0], dmean[:, 0]
+        if not return_var:
+            return mean, dmean
+        std2 = self._y_train_std ** 2       # undo normalisation (_gpr.py:487-489)
+        y_var = np.outer(var, std2)
+        dvar = dvar[:, None, :] * std2[None, :, None]
+        if one:
+            y_var, dvar = y_var[:, 0], dvar[:, 0]
+        return mean, dmean, y_var, dvar
+
     def sample_y(self, X, n_samples=1, random_state=0):
         """`sklearn/gaussian_process/_gpr.py:498-535`: draws from the joint posterior (or the prior, unfitted) at X - the
         mean and covariance from `predict(X, return_cov=True)` (GPU), the draw by NumPy's `multivariate_normal` (an SVD of

@@ -190,6 +190,34 @@ class GaussianProcess:
             self.get_logger().error(f"Error in GP prediction: {e}")
             return prior
 
+    def predict_jacobian(self, X_test):
+        """`predict` with the input gradients an MPC linearises with: (mean (M, P), var (M, P), dmean (M, P, D),
+        dvar (M, D)).  The package conventions of `predict`: no target normalisation, k** = signal_variance without noise,
+        variance floored at 1e-10 and tiled over the outputs (one variance, hence one dvar row, per query); dvar is the
+        gradient of the unfloored variance.  fp64 kernels whatever `predict_dtype`.  Unfitted / failed fit / any error:
+        the prior and zero gradients, never raising."""
+        X_test = np.atleast_2d(np.asarray(X_test, dtype=np.float64))
+        M = len(X_test)
+        prior = (np.zeros((M, self.output_dim)), np.ones((M, self.output_dim)) * self.kernel.signal_variance,
+                 np.zeros((M, self.output_dim, X_test.shape[1])), np.zeros((M, X_test.shape[1])))
+        if len(self.X_train) == 0 or self.alpha is None:
+            return prior
+        with self._swap:
+            model = self._model
+        if model is None:
+            return prior
+        try:
+            dev, sf2, zeros, ones = model
+            if dev.host_path_ok(M, True):
+                mean, var, dmean, dvar = dev.predict_grad_host(X_test, zeros, ones, sf2, 1e-10)
+            else:
+                mean = dev.predict_mean_dev(X_test, zeros, ones, "float64").cpu().numpy()
+                dmean, var, dvar = (t.cpu().numpy() for t in dev.predict_grad_dev(X_test, ones, sf2, 1e-10))
+            return mean, np.tile(var.reshape(-1, 1), (1, self.output_dim)), dmean, dvar
+        except Exception as e:  # noqa: BLE001
+            self.get_logger().error(f"Error in GP prediction: {e}")
+            return prior
+
     # ---- LML (gaussian_process.py:243-265) --------------------------------------------------------
     def log_marginal_likelihood(self):
         if len(self.X_train) < 2 or self.L is None:

@@ -130,6 +130,21 @@ class SimpleQuadrotorGP:
             print(f"GP prediction failed: {e}")
             return np.zeros(6), np.ones(6)
 
+    def predict_residual_jacobian(self, state, control):
+        """One row -> (mean (6,), J (6, 10)): the residual and its Jacobian with respect to [state(6), control(4)], one
+        launch (`GaussianProcessRegressor.predict_jacobian`); untrained/failed -> (zeros(6), zeros((6, 10))), never raising
+        into the control loop."""
+        if not self.is_trained:
+            return np.zeros(6), np.zeros((6, 10))
+        try:
+            x = np.concatenate([state, control]).reshape(1, -1)
+            mean, J = self.gp_model.predict_jacobian(x)
+            self.prediction_count += 1
+            return mean.reshape(-1), J.reshape(mean.size, -1)
+        except Exception as e:  # noqa: BLE001
+            print(f"GP prediction failed: {e}")
+            return np.zeros(6), np.zeros((6, 10))
+
     def predict_residual_batch(self, X, return_var=True):
         """M rows [state(6), control(4)] in one kernel call -> (mean (M,P), variance (M,P))."""
         X = np.atleast_2d(np.asarray(X, dtype=float))
@@ -168,6 +183,41 @@ class SimpleQuadrotorGP:
                 acc = gain * (mean / dt)[:, 3:6].reshape(R, N, 3)
                 D[:, 3:6, :] = acc.transpose(0, 2, 1)
         return D[0] if single else D
+
+    def linearize_gp_residuals(self, X_guess, U_guess, dt, gain=0.1, n_states=6):
+        """First-order companion of `build_gp_residuals`: the frozen residual D and its linearisation around the guess,
+        for an MPC that builds A, B per stage (quadrotor_gp_mpc/quadrotor_gp_mpc/mpc_controller.py:318).  Returns
+        (D, A, B): D (6, N) as `build_gp_residuals` returns it; A (N, 6, 6) and B (N, 6, 4), zero except rows 3:6 =
+        gain / dt * J_k[3:6, :6] and gain / dt * J_k[3:6, 6:10], J_k the Jacobian of the residual mean at stage k - from
+        ONE call for the whole horizon.  (R, ...) leading axis for R rollouts as in `build_gp_residuals`; untrained or a
+        failed prediction: zeros."""
+        X_guess = np.asarray(X_guess, dtype=float)
+        U_guess = np.asarray(U_guess, dtype=float)
+        single = X_guess.ndim == 2
+        if single:
+            X_guess, U_guess = X_guess[None], U_guess[None]
+        R, _, N = U_guess.shape
+        D = np.zeros((R, n_states, N))
+        A = np.zeros((R, N, n_states, 6))
+        B = np.zeros((R, N, n_states, 4))
+        if self.is_trained:
+            rows = np.concatenate([X_guess[:, :6, :N], U_guess[:, :4, :]], axis=1)    # (R, 10, N)
+            rows = rows.transpose(0, 2, 1).reshape(R * N, -1)
+            try:
+                mean, J = self.gp_model.predict_jacobian(rows)
+                self.prediction_count += len(rows)
+                mean = mean.reshape(R * N, -1)
+                J = J.reshape(R * N, mean.shape[1], -1)
+                if mean.shape[1] >= n_states:
+                    D[:, 3:6, :] = (gain * (mean / dt)[:, 3:6]).reshape(R, N, 3).transpose(0, 2, 1)
+                    A[:, :, 3:6, :] = (gain / dt * J[:, 3:6, :6]).reshape(R, N, 3, 6)
+                    B[:, :, 3:6, :] = (gain / dt * J[:, 3:6, 6:10]).reshape(R, N, 3, 4)
+            except Exception as e:  # noqa: BLE001
+                print(f"GP prediction failed: {e}")
+                D[:], A[:], B[:] = 0.0, 0.0, 0.0
+        if single:
+            return D[0], A[0], B[0]
+        return D, A, B
 
     def predict_horizon_gated(self, X_guess, U_guess, confidence_threshold, n_states=6):
         """Batched counterpart of `_get_gp_predictions_for_horizon`
