@@ -406,6 +406,40 @@ GPK_API int gpk_predict_host_grad(gpk_handle h, const double* X, const double* a
                                   double* var_host, double* dmean_host, double* dvar_host);
 GPK_API int gpk_predict_model_grad(gpk_handle h, const double* Xq, int64_t M, double* mean, double* var, double* dmean,
                                    double* dvar, int var_includes_noise);
+/* K8 for B (<= 8) single-output ARD models on one query batch - the per-axis layout of src/px4/gp_trainer.py:139-179 as
+ * gpk_predict_host_multi / gpk_predict_mean_multi serve it; formulas and units as above, model by model.
+ * gpk_predict_host_multi_grad: the one-call serving form, arguments as gpk_predict_host_multi (X / alpha / W: host arrays of B
+ *   device pointers; ls host B x D; sf2, y_mean, y_std, kss host double[B]), 1 <= M <= 32, D <= 16, N <= 16384.  mean_host
+ *   (B x M) and dmean_host (B x M x D) un-normalised; var_host (B x M) and dvar_host (B x M x D) in normalised-target units,
+ *   or both NULL (W and kss may then be NULL too).  The three gradient launches of gpk_predict_host_grad with the model as a
+ *   grid dimension: mean + Jacobian of ALL models in ONE launch, all four results in THREE, one synchronisation, queries and
+ *   results through the pinned, mapped block; every model has its own shares and ticket counters, every reduction is done by
+ *   the last workgroup in a fixed order (no floating-point atomics): bit-identical from run to run, and for B = 1 the bits of
+ *   gpk_predict_host_grad.  With option small_path = 0: the general building blocks, model by model (a cross-check).
+ *   Replaces: nothing in the reference, which has no gradient call - a caller of PreTrainedGP.predict_residual
+ *   (src/px4/pretrained_gp.py:52-98) would take central differences, 4 D calls of six scikit-learn predictions each; within
+ *   this library, B gpk_predict_host_grad calls with B synchronisations.
+ * gpk_predict_mean_grad_multi: the Jacobian companion of gpk_predict_mean_multi for any M, all device pointers: X (N x D),
+ *   alpha (N x B, column b = model b), Xq (M x D), dmean (M x B x D); ls host (B x D); sf2, y_std host double[B].  One fused
+ *   launch: the raw feature differences of a (query, training point) pair are formed once and serve every model's distance
+ *   and every model's D gradient sums; models in groups of <= 4 over the third grid dimension (<= 64 fp64 accumulators per
+ *   thread, no scratch); the training chunks are added in chunk order.
+ *   Replaces: B gpk_predict_mean_grad launches (the differences formed B times); in the reference, as above.
+ * gpk_predict_batched_grad: the composite on the object of gpk_fit_batched, host fp64 buffers: Xq (M x D), mean (M x B),
+ *   dmean (M x B x D), and var (M x B) / dvar (M x B x D) in target units (already multiplied by y_std[b]^2), or both NULL;
+ *   var_includes_noise as in gpk_predict.  Up to 32 queries (N <= 16384): gpk_predict_host_multi_grad; larger batches in
+ *   panels: gpk_predict_mean_multi + gpk_predict_mean_grad_multi and one gpk_predict_var_grad_inv per model.  Any M.
+ *   Replaces: central differences around PreTrainedGP.predict_residual's loop, src/px4/pretrained_gp.py:52-98.          */
+GPK_API int gpk_predict_host_multi_grad(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N,
+                                        int D, const double* ls, const double* sf2, const double* y_mean, const double* y_std,
+                                        const double* const* W, int64_t Np, int64_t ldw, const double* kss, double floor,
+                                        const double* Xq_host, int64_t M, double* mean_host, double* var_host,
+                                        double* dmean_host, double* dvar_host);
+GPK_API int gpk_predict_mean_grad_multi(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int B,
+                                        const double* ls, const double* sf2, const double* y_std, const double* Xq, int64_t M,
+                                        double* dmean);
+GPK_API int gpk_predict_batched_grad(gpk_handle h, const double* Xq, int64_t M, double* mean, double* var, double* dmean,
+                                     double* dvar, int var_includes_noise);
 
 /* ---- K6a: log-marginal-likelihood terms -----------------------------------------------------
  * terms[0] = sum_{i<N} log L[i][i]; terms[1 + p] = sum_i Y[i][p] * alpha[i][p]  (host doubles).

@@ -97,6 +97,11 @@ SIGNATURES = {
     "gpk_predict_host_grad": (_int, [_vp, _vp, _vp, _i64, _int, _int, _vp, _dbl, _vp, _vp, _vp, _i64, _i64, _dbl, _dbl, _vp,
                                      _i64, _vp, _vp, _vp, _vp]),
     "gpk_predict_model_grad": (_int, [_vp, _dp, _i64, _dp, _dp, _dp, _dp, _int]),
+    # (host pointers as void*, as gpk_predict_host_multi)
+    "gpk_predict_host_multi_grad": (_int, [_vp, _int, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _dbl, _vp,
+                                           _i64, _vp, _vp, _vp, _vp]),
+    "gpk_predict_mean_grad_multi": (_int, [_vp, _vp, _vp, _i64, _int, _int, _dp, _dp, _dp, _vp, _i64, _vp]),
+    "gpk_predict_batched_grad": (_int, [_vp, _dp, _i64, _dp, _dp, _dp, _dp, _int]),
     "gpk_lml_terms": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _int, _dp]),
     "gpk_potri": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),
     "gpk_lml_grad": (_int, [_vp, _vp, _i64, _int, _dp, _dbl, _dbl, _vp, _int, _vp, _i64, _dp]),

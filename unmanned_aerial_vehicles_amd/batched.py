@@ -40,6 +40,7 @@ class BatchedARDGP:
         st = self.__dict__.copy()
         st["_workers"], st["_fused"], st["_fs"] = [], None, None   # handles, streams, device tensors: rebuilt lazily
         st["_serve"] = None
+        st["_shared_x"] = None
         return st
 
     # ------------------------------------------------------------------ workers
@@ -295,13 +296,14 @@ class BatchedARDGP:
     # ------------------------------------------------------------------ control-loop batches
     SERVE_MAX_M = 32
 
-    def _serve_state(self, want_std):
+    def _serve_state(self, want_std, any_dtype=False):
         """Argument block of `gpk_predict_host_multi` (one call, two launches for all models), or None when the
         models do not qualify: fp64 serving, single-output models on one device with the same training-set size,
-        D <= 16, N <= 16384, at most 8 of them.  Rebuilt when a model has been refitted."""
+        D <= 16, N <= 16384, at most 8 of them.  Rebuilt when a model has been refitted.  any_dtype: the caller runs
+        the fp64 kernels whatever `predict_dtype` says (the input gradients)."""
         import torch
         ms = self.models
-        if self.predict_dtype == "float32" or not (1 <= len(ms) <= 8):
+        if (self.predict_dtype == "float32" and not any_dtype) or not (1 <= len(ms) <= 8):
             return None
         for m in ms:
             m._ensure_device()
@@ -363,6 +365,120 @@ class BatchedARDGP:
         if not return_std:
             return mean.T, None
         return mean.T, (np.sqrt(var) * sv["ys"][:, None]).T
+
+    # ------------------------------------------------------------------ input gradients (K8, per-axis batch)
+    def predict_host_grad(self, Xq, return_var=False):
+        """<= 32 rows, all models, one C call (`gpk_predict_host_multi_grad`: mean + Jacobian of every model in ONE launch,
+        with the variances and their gradients three): (mean (M, B), dmean (M, B, D), var (M, B) or None, dvar (M, B, D) or
+        None), var / dvar in target units (times y_std^2), dvar the gradient of the unclipped variance.  None if the models
+        do not qualify (the conditions of `_serve_state`).  Always the fp64 kernels: an fp32-serving batch is served too."""
+        sv = self._serve_state(return_var, any_dtype=True)
+        if sv is None:
+            return None
+        Xq = np.ascontiguousarray(Xq, dtype=np.float64)
+        d0 = sv["dev0"]
+        if Xq.ndim != 2 or Xq.shape[1] != d0.D:
+            raise ValueError(f"queries must be (M, {d0.D})")
+        M, B, D = Xq.shape[0], sv["B"], d0.D
+        if not (1 <= M <= self.SERVE_MAX_M):
+            return None
+        mean, dmean = np.empty((B, M)), np.empty((B, M, D))
+        var = np.empty((B, M)) if return_var else None
+        dvar = np.empty((B, M, D)) if return_var else None
+        be = d0.be
+        with be.lock:
+            be.bind_stream()
+            be.check(be.lib.gpk_predict_host_multi_grad(
+                be.h, B, sv["X"], sv["alpha"], d0.N, D, sv["ls"].ctypes.data, sv["sf2"].ctypes.data,
+                sv["ym"].ctypes.data, sv["ys"].ctypes.data, sv["W"] if return_var else None, d0.Np, d0.Np,
+                sv["kss"].ctypes.data, 0.0, Xq.ctypes.data, M, mean.ctypes.data,
+                var.ctypes.data if return_var else None, dmean.ctypes.data, dvar.ctypes.data if return_var else None))
+        mean, dmean = mean.T, dmean.transpose(1, 0, 2)
+        if not return_var:
+            return mean, dmean, None, None
+        s2 = sv["ys"] ** 2
+        return mean, dmean, (var * s2[:, None]).T, (dvar * s2[:, None, None]).transpose(1, 0, 2)
+
+    def _fused64(self):
+        """The fp64 buffers of the fused launches (shared X, alpha as one column per model) - `_fused` itself unless the
+        batch serves in fp32."""
+        import torch
+        if self._fused is None:
+            self._build_fused()
+        f = self._fused
+        if f["code"] == _lib.GPK_F64:
+            return f
+        if f.get("f64") is None:
+            be = get_backend(self.device)
+            with torch.cuda.device(be.device):
+                torch.cuda.synchronize()
+                alpha = torch.stack([m._dev.alpha[:, 0].to(be.device) for m in self.models], dim=1).double().contiguous()
+                X = self.models[0]._dev.X.to(be.device).double().contiguous()
+            f["f64"] = dict(f, X=X, alpha=alpha, tdt=torch.float64, code=_lib.GPK_F64)
+        return f["f64"]
+
+    def predict_jacobian(self, Xq, return_var=False):
+        """Posterior means of all B models and their Jacobians with respect to the inputs, and with return_var=True the
+        variances and their input gradients: (mean (M, B), dmean (M, B, D)[, var (M, B), dvar (M, B, D)]).  var equals
+        `predict(return_std=True)[1] ** 2`; dvar is the gradient of the unclipped variance (the gradient of the standard
+        deviation is dvar / (2 std)).  Up to 32 rows: one C call (`predict_host_grad`); larger batches: the fused mean
+        launch and the fused mean-Jacobian launch (`gpk_predict_mean_grad_multi`: the feature differences of a pair formed
+        once for all models) plus one variance-gradient chain per model.  Always fp64, as
+        `GaussianProcessRegressor.predict_jacobian`."""
+        Xq = np.array(Xq, dtype=np.float64, ndmin=2)
+        if not np.isfinite(Xq).all():
+            raise ValueError("Input X contains NaN or infinity.")
+        if 1 <= Xq.shape[0] <= self.SERVE_MAX_M:
+            out = self.predict_host_grad(Xq, return_var)
+            if out is not None:
+                return out if return_var else out[:2]
+        return self._predict_jacobian_large(Xq, return_var)
+
+    def _shared_inputs(self):
+        """True when every model was fitted on the same training inputs - what the fused launches assume (they read model 0's
+        X); checked once per set of fitted models."""
+        key = tuple(id(m._dev) for m in self.models)
+        c = getattr(self, "_shared_x", None)
+        if c is None or c[0] != key:
+            x0 = self.models[0].X_train_
+            same = all(m.X_train_.shape == x0.shape and np.array_equal(m.X_train_, x0) for m in self.models[1:])
+            c = self._shared_x = (key, same)
+        return c[1]
+
+    def _predict_jacobian_large(self, Xq, return_var=False):
+        import torch
+        for m in self.models:
+            m._ensure_device()
+        if not self._shared_inputs():
+            # models on different inputs: nothing to fuse, one call per model (the one-call path takes each model's own X)
+            outs = [m.predict_jacobian(Xq, return_var=return_var) for m in self.models]
+            return tuple(np.stack([o[i] for o in outs], axis=1) for i in range(4 if return_var else 2))
+        f = self._fused64()
+        be = get_backend(self.device)
+        q = be.upload(np.ascontiguousarray(Xq, dtype=np.float64), torch.float64)
+        M, B, D = q.shape[0], len(self.models), f["D"]
+        mean_d, dmean_d = be.empty((M, B), torch.float64), be.empty((M, B, D), torch.float64)
+        if M > 0:
+            dp = _lib._dp
+            p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+            with be.lock:
+                be.bind_stream()
+                be.check(be.lib.gpk_predict_mean_multi(
+                    be.h, _lib.GPK_F64, p(f["X"]), p(f["alpha"]), f["N"], D, B, f["ls"].ctypes.data_as(dp),
+                    f["sf2"].ctypes.data_as(dp), f["ym"].ctypes.data_as(dp), f["ys"].ctypes.data_as(dp), p(q), M, p(mean_d)))
+                be.check(be.lib.gpk_predict_mean_grad_multi(
+                    be.h, p(f["X"]), p(f["alpha"]), f["N"], D, B, f["ls"].ctypes.data_as(dp), f["sf2"].ctypes.data_as(dp),
+                    f["ys"].ctypes.data_as(dp), p(q), M, p(dmean_d)))
+        mean, dmean = mean_d.cpu().numpy(), dmean_d.cpu().numpy()
+        if not return_var:
+            return mean, dmean
+        var, dvar = np.empty((M, B)), np.empty((M, B, D))
+        for b, m in enumerate(self.models):      # W and the length-scales differ per model: nothing to share
+            comp = m.kernel_.components()
+            v, g = m._dev.predict_var_grad_dev(Xq, comp.sf2 + (comp.noise or 0.0), 0.0)
+            s2 = float(m._y_train_std[0]) ** 2
+            var[:, b], dvar[:, b, :] = v.cpu().numpy() * s2, g.cpu().numpy() * s2
+        return mean, dmean, var, dvar
 
     def predict(self, Xq, return_std=False):
         Xq = np.atleast_2d(np.asarray(Xq, dtype=np.float64))

@@ -231,13 +231,19 @@ size_t gpk_small_work_doubles(int64_t Np, int B);   // device work area: per mod
 // shared by the models; Xq / mean_out / var_out may be mapped host memory.  X / alpha / W: B device pointers;
 // ls: B x D; sf2, kss: B; y_mean, y_std: B * P.
 // posterior mean + covariance of M <= 32 queries of one model (small_cross_mean_kernel + small_cov_kernel)
-constexpr int GPK_SMALL_COV_COUNTERS = 128;   // ticket counters of its two-level reduction (h->d_cov_count)
+constexpr int GPK_SMALL_COV_COUNTERS = 128;   // ticket counters of its two-level reduction (h->d_cov_count); the last
+                                              // GPK_SMALL_MAX_MODELS are small_wtv_grad_kernel's, one per model
 size_t gpk_small_cov_work_doubles(int64_t Np);
 int gpk_small_cov(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls, double sf2,
                   const double* y_mean, const double* y_std, const double* W, int64_t Np, int64_t ldw, double noise,
                   const double* Xq, int64_t M, double* work, double* mean_out, double* cov_out);
 // posterior mean + its Jacobian (one launch) and, with var_out / dvar_out, variance + its gradient (three launches) of M <= 32 queries
-size_t gpk_small_grad_work_doubles(int64_t Np, int M, int D, int P);
+size_t gpk_small_grad_work_doubles(int64_t Np, int M, int D, int P, int B = 1);
+// ... of B models on one query batch (B > 1: P == 1; arguments as gpk_small_predict; outputs (B, M, P), (B, M), (B, M, P, D), (B, M, D))
+int gpk_small_grad_multi(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D, int P,
+                         const double* ls, const double* sf2, const double* y_mean, const double* y_std, const double* const* W,
+                         int64_t Np, int64_t ldw, const double* kss, double floor_, const double* Xq, int64_t M, double* work,
+                         double* mean_out, double* var_out, double* dmean_out, double* dvar_out);
 int gpk_small_grad(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls, double sf2,
                    const double* y_mean, const double* y_std, const double* W, int64_t Np, int64_t ldw, double kss, double floor_,
                    const double* Xq, int64_t M, double* work, double* mean_out, double* var_out, double* dmean_out,

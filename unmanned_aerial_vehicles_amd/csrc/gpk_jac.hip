@@ -19,6 +19,12 @@
 //                             training rows; var_grad_finalize_kernel adds the chunks in order and writes
 //                             dvar = -2 / ls_d * sum and var = max(kss - sum V^2, floor).
 //
+//   predict_mean_grad_multi_kernel  the Jacobian companion of predict_mean_multi_kernel (gpk_gram.hip) for B <= 8 single-output
+//                             ARD models on shared inputs (the per-axis batch): rows staged raw with the B alpha columns, the raw
+//                             feature differences of a pair formed ONCE and used by every model's distance (its 1 / ls^2 weights
+//                             in LDS) and every model's D running sums; the models in groups of <= 4 over the third grid
+//                             dimension (<= 64 accumulators, no scratch), the training set in chunks added in chunk order.
+//
 // No reference counterpart: scikit-learn has no gradient call.  A caller of the reference would difference
 // GaussianProcessRegressor.predict (sklearn/gaussian_process/_gpr.py:441-494) around the horizon loop of
 // src/px4/mpc.py:1490-1506; the consumer is the linearisation of quadrotor_gp_mpc/quadrotor_gp_mpc/mpc_controller.py:318.
@@ -114,6 +120,116 @@ __global__ void mean_grad_reduce_kernel(const double* __restrict__ partial, int 
   double s = 0.0;
   for (int k = 0; k < S; ++k) s += partial[(long long)k * tot + e];
   dmean[e] = -(ystd.v[p] * sf2 / ls.v[d]) * s;
+}
+
+// ---- mean Jacobian of B single-output models on shared inputs ---------------------------------------------------------
+struct W128 { double v[8 * 16]; };      // [model][feature]
+
+// partial[chunk][m][b][d] = sum_{j in chunk} exp(-sum_d' (x_jd' - q_md')^2 w_bd' / 2) alpha_jb (x_jd - q_md),  w_bd = 1 / ls_bd^2
+template <int D4, int BS>
+__global__ __launch_bounds__(256) void predict_mean_grad_multi_kernel(const double* __restrict__ X,
+                                                                      const double* __restrict__ alpha, long long N, int D, int B,
+                                                                      W128 wt, const double* __restrict__ Xq, long long M,
+                                                                      long long chunk, double* __restrict__ partial) {
+  constexpr int DD = 4 * D4, RS = DD + 4;
+  __shared__ __attribute__((aligned(32))) double rows[JG_TJ * RS];
+  __shared__ double wl[BS * DD];          // this group's weights (0 in the padding)
+  const int tid = threadIdx.x;
+  const int b0 = blockIdx.z * BS;
+  for (int e = tid; e < BS * DD; e += 256) {
+    const int b = e / DD, d = e - b * DD;
+    wl[e] = (b0 + b < B && d < D) ? wt.v[(b0 + b) * 16 + d] : 0.0;
+  }
+  const long long qm = (long long)blockIdx.x * 256 + tid;
+  double xq[DD], acc[BS][DD];
+#pragma unroll
+  for (int d = 0; d < DD; ++d) {
+    xq[d] = 0.0;
+    if (d < D && qm < M) xq[d] = Xq[qm * D + d];
+#pragma unroll
+    for (int b = 0; b < BS; ++b) acc[b][d] = 0.0;
+  }
+  const long long n0 = (long long)blockIdx.y * chunk;
+  const long long n1 = min(N, n0 + chunk);
+  for (long long jb = n0; jb < n1; jb += JG_TJ) {
+    const int nj = (int)min((long long)JG_TJ, n1 - jb);
+    __syncthreads();
+    // stage [x | 0.. | alpha of this group's models | 0..] for the nj rows of this round
+    for (int e = tid; e < nj * RS; e += 256) {
+      const int j = e / RS, c = e - j * RS;
+      double v = 0.0;
+      if (c < DD) { if (c < D) v = X[(jb + j) * D + c]; }
+      else if (c - DD < BS && b0 + (c - DD) < B) v = alpha[(jb + j) * B + b0 + (c - DD)];
+      rows[e] = v;
+    }
+    __syncthreads();
+    // (one row at a time: two in flight spill at D4 = BS = 4)
+#pragma unroll 1
+    for (int j = 0; j < nj; ++j) {
+      const double4* row = reinterpret_cast<const double4*>(rows + j * RS);
+      double df[DD], al[4];
+#pragma unroll
+      for (int g = 0; g < D4; ++g) {
+        const double4 v = row[g];
+        df[4 * g] = v.x - xq[4 * g]; df[4 * g + 1] = v.y - xq[4 * g + 1];
+        df[4 * g + 2] = v.z - xq[4 * g + 2]; df[4 * g + 3] = v.w - xq[4 * g + 3];
+      }
+      {
+        const double4 v = row[D4];
+        al[0] = v.x; al[1] = v.y; al[2] = v.z; al[3] = v.w;
+      }
+#pragma unroll
+      for (int b = 0; b < BS; ++b) {
+        double d2 = 0.0;
+#pragma unroll
+        for (int d = 0; d < DD; ++d) d2 = __builtin_fma(df[d] * df[d], wl[b * DD + d], d2);
+        const double w = gpk_exp_neg(-0.5 * d2) * al[b];
+#pragma unroll
+        for (int d = 0; d < DD; ++d) acc[b][d] = __builtin_fma(w, df[d], acc[b][d]);
+      }
+    }
+  }
+  if (qm < M) {
+#pragma unroll
+    for (int b = 0; b < BS; ++b)
+      if (b0 + b < B) {
+        double* out = partial + (((long long)blockIdx.y * M + qm) * B + b0 + b) * D;
+#pragma unroll
+        for (int d = 0; d < DD; ++d)
+          if (d < D) out[d] = acc[b][d];
+      }
+  }
+}
+
+// dmean[m][b][d] = y_std[b] sf2[b] / ls_bd^2 * sum_chunks partial  (scale: [model][feature]); the chunks in order
+__global__ void mean_grad_reduce_multi_kernel(const double* __restrict__ partial, int S, long long M, int D, int B, W128 scale,
+                                              double* __restrict__ dmean) {
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long tot = M * B * D;
+  if (e >= tot) return;
+  const int d = (int)(e % D), b = (int)((e / D) % B);
+  double s = 0.0;
+  for (int k = 0; k < S; ++k) s += partial[(long long)k * tot + e];
+  dmean[e] = scale.v[b * 16 + d] * s;
+}
+
+using mgm_fn = void (*)(const double*, const double*, long long, int, int, W128, const double*, long long, long long, double*);
+template <int D4>
+mgm_fn mgm_pick_b(int bs) {
+  switch (bs) {
+    case 1: return predict_mean_grad_multi_kernel<D4, 1>;
+    case 2: return predict_mean_grad_multi_kernel<D4, 2>;
+    case 3: return predict_mean_grad_multi_kernel<D4, 3>;
+    default: return predict_mean_grad_multi_kernel<D4, 4>;
+  }
+}
+mgm_fn mgm_pick(int d4, int bs) {
+  switch (d4) {
+    case 1: return mgm_pick_b<1>(bs);
+    case 2: return mgm_pick_b<2>(bs);
+    case 3: return mgm_pick_b<3>(bs);
+    default: return mgm_pick_b<4>(bs);
+  }
 }
 
 using mg_fn = void (*)(const double*, const double*, long long, int, int, Ls16, const double*, long long, long long, double*);
@@ -274,6 +390,50 @@ extern "C" int gpk_predict_mean_grad(gpk_handle h, const double* X, const double
   return GPK_OK;
 }
 
+extern "C" int gpk_predict_mean_grad_multi(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int B,
+                                           const double* ls, const double* sf2, const double* y_std, const double* Xq, int64_t M,
+                                           double* dmean) {
+  if (!h) return GPK_BAD_ARG;
+  GPK_REQUIRE(h, X && alpha && Xq && dmean && ls && sf2 && y_std, "predict_mean_grad_multi: null pointer");
+  GPK_REQUIRE(h, N >= 1 && M >= 1, "predict_mean_grad_multi: empty input");
+  GPK_REQUIRE(h, D >= 1 && D <= GPK_MAX_D_PREDICT, "predict_mean_grad_multi: D must be in [1, 16]");
+  GPK_REQUIRE(h, B >= 1 && B <= 8, "predict_mean_grad_multi: B must be in [1, 8]");
+  W128 wt{}, sc{};
+  for (int b = 0; b < B; ++b)
+    for (int d = 0; d < D; ++d) {
+      const double l = ls[b * D + d];
+      GPK_REQUIRE(h, l > 0.0, "predict_mean_grad_multi: length-scales must be positive");
+      wt.v[b * 16 + d] = 1.0 / (l * l);
+      sc.v[b * 16 + d] = y_std[b] * sf2[b] / (l * l);
+    }
+  // model groups of BS <= 4: the fewest groups, evenly filled (B = 6: two groups of 3)
+  const int ng = (B + 3) / 4, bs = (B + ng - 1) / ng, d4 = (D + 3) / 4;
+  for (int64_t m0 = 0; m0 < M; m0 += MG_PANEL) {
+    const int64_t mc = M - m0 < MG_PANEL ? M - m0 : MG_PANEL;
+    const int64_t nqb = (mc + 255) / 256;
+    // the chunking of gpk_predict_mean_grad
+    const int64_t gran = (mc <= 512 && N <= 16384) ? 32 : JG_TJ;
+    int64_t S = (2048 + nqb * ng - 1) / (nqb * ng);
+    const int64_t maxS = (N + gran - 1) / gran;
+    if (S > maxS) S = maxS;
+    if (S < 1) S = 1;
+    if (S > 65535) S = 65535;
+    int64_t chunk = (N + S - 1) / S;
+    chunk = (chunk + gran - 1) / gran * gran;
+    S = (N + chunk - 1) / chunk;
+    void* partial = nullptr;
+    GPK_TRY(gpk_scratch(h, (size_t)S * mc * B * D * sizeof(double), &partial));
+    hipLaunchKernelGGL(mgm_pick(d4, bs), dim3((unsigned)nqb, (unsigned)S, (unsigned)ng), dim3(256), 0, h->stream, X, alpha,
+                       (long long)N, D, B, wt, Xq + m0 * D, (long long)mc, (long long)chunk, (double*)partial);
+    GPK_LAUNCH_CHECK(h);
+    const int64_t tot = mc * B * D;
+    hipLaunchKernelGGL(mean_grad_reduce_multi_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream,
+                       (const double*)partial, (int)S, (long long)mc, D, B, sc, dmean + m0 * B * D);
+    GPK_LAUNCH_CHECK(h);
+  }
+  return GPK_OK;
+}
+
 extern "C" int gpk_predict_var_grad_inv(gpk_handle h, const double* X, int64_t N, int D, const double* ls, double sf2,
                                         const double* W, int64_t Np, int64_t ldw, const double* Xq, int64_t M, double kss,
                                         double floor_, double* work, double* var, double* dvar) {
@@ -383,6 +543,65 @@ extern "C" int gpk_predict_host_grad(gpk_handle h, const double* X, const double
   if (want_var) {
     memcpy(var_host, hvar, nv * sizeof(double));
     memcpy(dvar_host, hdv, njv * sizeof(double));
+  }
+  return GPK_OK;
+}
+
+extern "C" int gpk_predict_host_multi_grad(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N,
+                                           int D, const double* ls, const double* sf2, const double* y_mean,
+                                           const double* y_std, const double* const* W, int64_t Np, int64_t ldw,
+                                           const double* kss, double floor_, const double* Xq_host, int64_t M,
+                                           double* mean_host, double* var_host, double* dmean_host, double* dvar_host) {
+  if (!h) return GPK_BAD_ARG;
+  GPK_REQUIRE(h, X && alpha && ls && sf2 && y_mean && y_std && Xq_host && mean_host && dmean_host,
+              "predict_host_multi_grad: null pointer");
+  GPK_REQUIRE(h, B >= 1 && B <= GPK_SMALL_MAX_MODELS, "predict_host_multi_grad: 1..8 models");
+  GPK_REQUIRE(h, N >= 1 && gpk_small_ok(gpk_padded(N), D, 1, M), "predict_host_multi_grad: needs M <= 32, D <= 16, N <= 16384");
+  GPK_REQUIRE(h, (var_host == nullptr) == (dvar_host == nullptr),
+              "predict_host_multi_grad: var and dvar come together (both or neither)");
+  const bool want_var = var_host != nullptr;
+  GPK_REQUIRE(h, !want_var || (W && kss && Np == gpk_padded(N) && ldw >= Np),
+              "predict_host_multi_grad: the variance gradient needs the inverse factors");
+  GPK_REQUIRE(h, h->batch == 1, "predict_host_multi_grad: not available in batched mode");
+  for (int b = 0; b < B; ++b)
+    GPK_REQUIRE(h, X[b] && alpha[b] && (!want_var || W[b]), "predict_host_multi_grad: null model pointer");
+  const int64_t Npad = gpk_padded(N), Mp = gpk_padded(M);
+  const bool small = h->small_path != 0;
+  // pinned host block [Xq | pad][mean (B x M) | var (B x M) | dmean (B x M x D) | dvar (B x M x D) | pad]; device block [Xq | pad][work]
+  const size_t nq = ((size_t)M * D + 15) & ~(size_t)15, nm = (size_t)B * M, nj = (size_t)B * M * D;
+  const size_t nout_pad = (2 * nm + 2 * nj + 15) & ~(size_t)15;
+  const size_t work_need = small ? gpk_small_grad_work_doubles(Npad, (int)M, D, 1, B) : (want_var ? (size_t)3 * Npad * Mp : 0);
+  GPK_TRY(gpk_serve_reserve(h, (nq + nout_pad) * sizeof(double), (nq + work_need) * sizeof(double)));
+  double* hq = (double*)h->serve_host;
+  double* hmean = hq + nq;
+  double* hvar = hmean + nm;
+  double* hdm = hvar + nm;
+  double* hdv = hdm + nj;
+  double* dq = (double*)h->serve_dev;
+  double* dwork = dq + nq;
+  if (h->debug_fill && work_need > 0) GPK_CHECK_HIP(h, hipMemsetAsync(dwork, 0xFF, work_need * sizeof(double), h->stream));
+  memcpy(hq, Xq_host, (size_t)M * D * sizeof(double));
+  if (small) {
+    // all models in one launch (mean + Jacobian) or three (all four results); results straight into the pinned, mapped block
+    GPK_TRY(gpk_small_grad_multi(h, B, X, alpha, N, D, 1, ls, sf2, y_mean, y_std, want_var ? W : nullptr, Npad, ldw, kss, floor_,
+                                 hq, M, dwork, hmean, want_var ? hvar : nullptr, hdm, want_var ? hdv : nullptr));
+  } else {
+    // option small_path = 0 (the cross-check of the small-batch kernels): the general building blocks, model by model
+    GPK_CHECK_HIP(h, hipMemcpyAsync(dq, hq, (size_t)M * D * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    for (int b = 0; b < B; ++b) {
+      GPK_TRY(gpk_predict_mean(h, GPK_F64, X[b], alpha[b], N, D, 1, ls + b * D, sf2[b], y_mean + b, y_std + b, dq, M, hmean + b * M));
+      GPK_TRY(gpk_predict_mean_grad(h, X[b], alpha[b], N, D, 1, ls + b * D, sf2[b], y_std + b, dq, M, hdm + (size_t)b * M * D));
+      if (want_var)
+        GPK_TRY(gpk_predict_var_grad_inv(h, X[b], N, D, ls + b * D, sf2[b], W[b], Np, ldw, dq, M, kss[b], floor_, dwork, hvar + b * M,
+                                         hdv + (size_t)b * M * D));
+    }
+  }
+  GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
+  memcpy(mean_host, hmean, nm * sizeof(double));
+  memcpy(dmean_host, hdm, nj * sizeof(double));
+  if (want_var) {
+    memcpy(var_host, hvar, nm * sizeof(double));
+    memcpy(dvar_host, hdv, nj * sizeof(double));
   }
   return GPK_OK;
 }

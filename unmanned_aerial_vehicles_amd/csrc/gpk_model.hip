@@ -642,6 +642,17 @@ __global__ void scale_var_col_kernel(const double* __restrict__ var, long long M
   if (i < M) out[i * B + b] = var[i] * s2;
 }
 
+// out[m][b] = var[m] * s2 and out_g[m][b][d] = dvar[m][d] * s2  (column b of the M x B variance / M x B x D gradient blocks)
+__global__ void scale_var_grad_col_kernel(const double* __restrict__ var, const double* __restrict__ dvar, long long M, int D, int B,
+                                          int b, double s2, double* __restrict__ out, double* __restrict__ out_g) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= M * (D + 1)) return;
+  const long long m = i / (D + 1);
+  const int d = (int)(i - m * (D + 1));
+  if (d < D) out_g[(m * B + b) * D + d] = dvar[m * D + d] * s2;
+  else out[m * B + b] = var[m] * s2;
+}
+
 // K2 + W = L^-1 + K3 (+ K^-1 = W^T W) for all models in one launch chain; info[b] != 0: model b is not positive definite
 int batched_chain(gpk_handle h, gpk_bmodel* m, double* K, double* winv, double* W, double* T, double* alpha, double* Kinv,
                   int* info) {
@@ -812,6 +823,84 @@ extern "C" int gpk_predict_batched(gpk_handle h, const double* Xq, int64_t M, do
         GPK_LAUNCH_CHECK(h);
       }
       GPK_CHECK_HIP(h, hipMemcpyAsync(var + (size_t)m0 * B, d_varout, (size_t)mc * B * 8, hipMemcpyDeviceToHost, h->stream));
+    }
+    GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  return GPK_OK;
+}
+
+extern "C" int gpk_predict_batched_grad(gpk_handle h, const double* Xq, int64_t M, double* mean, double* var, double* dmean,
+                                        double* dvar, int var_includes_noise) {
+  if (!h) return GPK_BAD_ARG;
+  gpk_bmodel* m = h->bmodel;
+  GPK_REQUIRE(h, m && m->fitted, "predict_batched_grad: no model (call gpk_fit_batched first)");
+  GPK_REQUIRE(h, Xq && mean && dmean && M >= 1, "predict_batched_grad: null pointer or empty batch");
+  GPK_REQUIRE(h, (var == nullptr) == (dvar == nullptr), "predict_batched_grad: var and dvar come together (both or neither)");
+  GPK_CHECK_HIP(h, hipSetDevice(h->device));
+  const int B = m->B, D = m->D;
+  for (int64_t i = 0; i < M * D; ++i) GPK_REQUIRE(h, std::isfinite(Xq[i]), "predict_batched_grad: Xq contains NaN or infinity");
+  double kss[GPK_MAX_BATCH];
+  for (int b = 0; b < B; ++b) kss[b] = m->sf2[b] + (var_includes_noise ? m->noise[b] : 0.0);
+  const double floor_ = var_includes_noise ? 0.0 : 1e-10;
+  double lsBD[GPK_MAX_BATCH * GPK_MAX_D_PREDICT];
+  for (int b = 0; b < B; ++b)
+    for (int d = 0; d < D; ++d) lsBD[b * D + d] = m->ls[b][d];
+  // control-loop batches: one call for all models, one launch (three with the variances)
+  if (M <= 32 && m->Np <= GPK_SMALL_MAX_NP) {
+    const double *Xs[GPK_MAX_BATCH], *as[GPK_MAX_BATCH], *Ws[GPK_MAX_BATCH];
+    for (int b = 0; b < B; ++b) { Xs[b] = m->X; as[b] = m->alpha + (size_t)b * m->Ne; Ws[b] = m->W + (size_t)b * m->nn(); }
+    std::vector<double> mb((size_t)B * M), jb((size_t)B * M * D), vb(var ? (size_t)B * M : 0), gb(var ? (size_t)B * M * D : 0);
+    GPK_TRY(gpk_predict_host_multi_grad(h, B, Xs, as, m->N, D, lsBD, m->sf2, m->y_mean, m->y_std, var ? Ws : nullptr, m->Np, m->Np,
+                                        var ? kss : nullptr, floor_, Xq, M, mb.data(), var ? vb.data() : nullptr, jb.data(),
+                                        var ? gb.data() : nullptr));
+    for (int64_t i = 0; i < M; ++i)
+      for (int b = 0; b < B; ++b) {
+        const double s2 = m->y_std[b] * m->y_std[b];
+        mean[i * B + b] = mb[(size_t)b * M + i];
+        if (var) var[i * B + b] = vb[(size_t)b * M + i] * s2;
+        for (int d = 0; d < D; ++d) {
+          dmean[(i * B + b) * D + d] = jb[((size_t)b * M + i) * D + d];
+          if (var) dvar[(i * B + b) * D + d] = gb[((size_t)b * M + i) * D + d] * s2;
+        }
+      }
+    return GPK_OK;
+  }
+  // larger batches in query panels: the two fused launches for means and Jacobians of all models; per model the variance
+  // gradient (its three Np x panel work panels within 6 GiB)
+  int64_t panel = (int64_t)((6ull << 30) / ((size_t)3 * m->Np * 8)) / GPK_TILE * GPK_TILE;
+  if (panel > 16384) panel = 16384;
+  if (panel < GPK_TILE) panel = GPK_TILE;
+  if (panel > gpk_padded(M)) panel = gpk_padded(M);
+  GPK_TRY(grow(h, &m->q, &m->q_bytes, (size_t)panel * D * 8));
+  GPK_TRY(grow(h, &m->mean, &m->mean_bytes, (size_t)panel * B * (D + 1) * 8));
+  if (var) {
+    GPK_TRY(grow(h, &m->work, &m->work_bytes, (size_t)3 * m->Np * panel * 8));
+    GPK_TRY(grow(h, (void**)&m->var, &m->var_bytes, (size_t)panel * (D + 1) * 8 + (size_t)panel * B * (D + 1) * 8));
+  }
+  double* d_mean = (double*)m->mean;
+  double* d_dmean = d_mean + (size_t)panel * B;
+  double* d_v1 = var ? m->var : nullptr;                               // one model: var (panel) | dvar (panel x D)
+  double* d_g1 = var ? d_v1 + panel : nullptr;
+  double* d_varout = var ? d_g1 + (size_t)panel * D : nullptr;         // (panel x B) | (panel x B x D)
+  double* d_dvarout = var ? d_varout + (size_t)panel * B : nullptr;
+  for (int64_t m0 = 0; m0 < M; m0 += panel) {
+    const int64_t mc = M - m0 < panel ? M - m0 : panel;
+    GPK_CHECK_HIP(h, hipMemcpyAsync(m->q, Xq + (size_t)m0 * D, (size_t)mc * D * 8, hipMemcpyHostToDevice, h->stream));
+    GPK_TRY(gpk_predict_mean_multi(h, GPK_F64, m->X, m->alphaT, m->N, D, B, lsBD, m->sf2, m->y_mean, m->y_std, m->q, mc, d_mean));
+    GPK_TRY(gpk_predict_mean_grad_multi(h, m->X, m->alphaT, m->N, D, B, lsBD, m->sf2, m->y_std, (const double*)m->q, mc, d_dmean));
+    GPK_CHECK_HIP(h, hipMemcpyAsync(mean + (size_t)m0 * B, d_mean, (size_t)mc * B * 8, hipMemcpyDeviceToHost, h->stream));
+    GPK_CHECK_HIP(h, hipMemcpyAsync(dmean + (size_t)m0 * B * D, d_dmean, (size_t)mc * B * D * 8, hipMemcpyDeviceToHost, h->stream));
+    if (var) {
+      for (int b = 0; b < B; ++b) {          // K*, W and the length-scales differ per model: one variance-gradient chain each
+        GPK_TRY(gpk_predict_var_grad_inv(h, m->X, m->N, D, m->ls[b], m->sf2[b], m->W + (size_t)b * m->nn(), m->Np, m->Np,
+                                         (const double*)m->q, mc, kss[b], floor_, (double*)m->work, d_v1, d_g1));
+        const long long tot = (long long)mc * (D + 1);
+        hipLaunchKernelGGL(scale_var_grad_col_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, d_v1, d_g1,
+                           (long long)mc, D, B, b, m->y_std[b] * m->y_std[b], d_varout, d_dvarout);
+        GPK_LAUNCH_CHECK(h);
+      }
+      GPK_CHECK_HIP(h, hipMemcpyAsync(var + (size_t)m0 * B, d_varout, (size_t)mc * B * 8, hipMemcpyDeviceToHost, h->stream));
+      GPK_CHECK_HIP(h, hipMemcpyAsync(dvar + (size_t)m0 * B * D, d_dvarout, (size_t)mc * B * D * 8, hipMemcpyDeviceToHost, h->stream));
     }
     GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
   }

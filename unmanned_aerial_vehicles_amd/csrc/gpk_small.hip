@@ -23,6 +23,10 @@
 //                            small_var_grad_kernel also stores its rows of V = W K*^T, and small_wtv_grad_kernel - 16
 //                            columns of W per workgroup - forms C = W^T V, its share of sum_j k*_mj C_jm (x_jd - q_md) / ls_d
 //                            and, in the last workgroup, -2 / ls_d times the fixed-order sum of the shares.
+//                            All three take the model as a grid dimension (blockIdx.y, y, z) like the mean and the variance:
+//                            the per-axis batch (B <= 8 single-output models on one query batch) gets mean + Jacobian of
+//                            every model in ONE launch and all four results in three (gpk_small_grad_multi), each model
+//                            with its own shares and its own ticket counters.
 //
 // Both results land in the caller's (pinned, mapped) output block; the queries are read from it as well.
 #include "gpk_internal.h"
@@ -140,7 +144,7 @@ __device__ __forceinline__ void finish_jac(const double* pjac, unsigned shares, 
 
 // FINISH: this launch is the only one (mean-only call) and elects the workgroup that writes the means; otherwise
 // small_var_kernel's last workgroup does it.
-// JAC (one model; small_cross_mean_jac_kernel): the launch also forms the mean Jacobian's shares (pjac) and - FINISH - the
+// JAC (small_cross_mean_jac_kernel; model = blockIdx.y as for the mean): the launch also forms the mean Jacobian's shares (pjac) and - FINISH - the
 // Jacobian itself (dmean_out).  The body is shared; small_cross_mean_kernel keeps its signature and its launches.
 template <bool FINISH, bool JAC>
 __device__ __forceinline__ void small_cross_mean_body(SmallK k, long long N, long long Np, int D, int P,
@@ -159,6 +163,10 @@ __device__ __forceinline__ void small_cross_mean_body(SmallK k, long long N, lon
   pmean += (long long)b * gridDim.x * (SQ * SP);
   mean_out += (long long)b * M * P;
   counter += b;
+  if constexpr (JAC) {
+    pjac += (long long)b * gridDim.x * (M * P * D);
+    dmean_out += (long long)b * M * P * D;
+  }
   const int tid = threadIdx.x, jl = tid & 31, mg = tid >> 5;
   const long long j0 = (long long)blockIdx.x * SJ, j = j0 + jl;
   const bool valid = j < N;
@@ -282,7 +290,7 @@ __device__ __forceinline__ void vmul(const VFrag<NMB>& f, long long kc, int kq, 
   }
 }
 
-// GRAD (one model; small_var_grad_kernel): the launch also stores its rows of V (Vs: Np x SQ, columns < 16 NMB written) for
+// GRAD (small_var_grad_kernel): the launch also stores its rows of V (Vs: per model Np x SQ, columns < 16 NMB written) for
 // small_wtv_grad_kernel, and workgroup 1 adds the mean Jacobian's shares of the previous launch.  The body is shared;
 // small_var_kernel keeps its signature and its launches.
 template <int NMB, bool GRAD>
@@ -302,6 +310,11 @@ __device__ __forceinline__ void small_var_body(SmallK k, long long ldw, long lon
   mean_out += (long long)b * M * P;
   var_out += (long long)b * M;
   counter += b;
+  if constexpr (GRAD) {
+    Vs += (long long)b * Np * SQ;
+    pjac += (long long)b * mean_shares * (M * P * D);
+    dmean_out += (long long)b * M * P * D;
+  }
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, i = lane & 15, kq = lane >> 4;
   const long long r0 = (long long)blockIdx.x * SR, row = r0 + i;
   const long long kend = min(Np, (r0 + SR + 63) / 64 * 64);   // the rows' diagonal, rounded up to the chunk
@@ -351,7 +364,7 @@ __device__ __forceinline__ void small_var_body(SmallK k, long long ldw, long lon
   static_assert(VW * 16 * 17 >= 4 * SQ * SP, "the reduction buffer doubles as the mean scratch");
   if (blockIdx.x == 0) finish_means(pmean, mean_shares, M, P, k.ymean + b * P, k.ystd + b * P, mean_out, tid, &red[0][0][0][0]);
   if constexpr (GRAD) {
-    if (blockIdx.x == 1) finish_jac(pjac, mean_shares, M, P, D, k.ystd, k.ls[0], dmean_out, tid, 64 * VW);
+    if (blockIdx.x == 1) finish_jac(pjac, mean_shares, M, P, D, k.ystd + b * P, k.ls[b], dmean_out, tid, 64 * VW);
   }
   if (last_workgroup(counter, tid)) {
     __shared__ double part[2 * VW][SQ];
@@ -498,15 +511,15 @@ __global__ __launch_bounds__(64 * VW) void small_cov_kernel(SmallK k, long long 
   }
 }
 
-// Variance gradient of M <= 32 queries (one model), after small_cross_mean_kernel (K*: Ks, query-major) and
+// Variance gradient of M <= 32 queries (model = blockIdx.z), after small_cross_mean_kernel (K*: Ks, query-major) and
 // small_var_grad_kernel (V: Vs, Np x SQ): 16 columns of W per workgroup.  C[j][m] = sum_{r >= j} W[r][j] V[r][m] on the
 // vector ALU (thread = column jl, query half mh, row group rg of 16; the row groups are added in a fixed order through LDS),
 // then the workgroup's share of sum_j k*_mj C_jm (x_jd - q_md) / ls_d (pdv: gridDim.x x M * D); the last workgroup adds the
-// shares in order and writes dvar[m][d] = -2 / ls_d * sum.  pdv: gridDim.x * gridDim.y shares.
+// shares in order and writes dvar[m][d] = -2 / ls_d * sum.  pdv: gridDim.x * gridDim.y shares per model; counter: one per model.
 constexpr unsigned WTV_MAX_ROW_CHUNKS = 4;
 constexpr int GW = 16, GRG = 16, GT = GW * 2 * GRG;      // 512 threads: column jl, query half mh, row group rg
 __global__ __launch_bounds__(GT) void small_wtv_grad_kernel(SmallK k, long long ldw, long long N, long long Np, int D,
-                                                            const double* __restrict__ Ks, const double* __restrict__ Vs,
+                                                            const double* __restrict__ Ks_all, const double* __restrict__ Vs_all,
                                                             const double* __restrict__ Xq, int M, double* pdv,
                                                             unsigned* counter, double* dvar_out) {
   __shared__ double red[GRG][GW][17];
@@ -514,9 +527,15 @@ __global__ __launch_bounds__(GT) void small_wtv_grad_kernel(SmallK k, long long 
   __shared__ double xs[GW][SD + 1];
   __shared__ double qs[SQ][SD + 1];
   __shared__ double half[2][SQ * SD];
-  const double* __restrict__ W = k.W[0];
-  const double* __restrict__ X = k.X[0];
-  const double* ls = k.ls[0];
+  const int b = blockIdx.z;
+  const double* __restrict__ W = k.W[b];
+  const double* __restrict__ X = k.X[b];
+  const double* ls = k.ls[b];
+  const double* __restrict__ Ks = Ks_all + (long long)b * SQ * Np;
+  const double* __restrict__ Vs = Vs_all + (long long)b * Np * SQ;
+  pdv += (long long)b * gridDim.x * gridDim.y * (M * D);
+  dvar_out += (long long)b * M * D;
+  counter += b;
   const int tid = threadIdx.x, jl = tid & 15, mh = (tid >> 4) & 1, rg = tid >> 5;
   const long long j0 = (long long)blockIdx.x * GW, j = j0 + jl;
   // queries and this workgroup's training rows, divided by the length-scales
@@ -713,65 +732,86 @@ int gpk_small_cov(gpk_handle h, const double* X, const double* alpha, int64_t N,
   return GPK_OK;
 }
 
-size_t gpk_small_grad_work_doubles(int64_t Np, int M, int D, int P) {
+size_t gpk_small_grad_work_doubles(int64_t Np, int M, int D, int P, int B) {
   const size_t ga = (size_t)(Np / SJ), gb = (size_t)(Np / SR);
-  return gpk_small_work_doubles(Np, 1) + ga * (size_t)(M * P * D) + (size_t)Np * SQ + gb * WTV_MAX_ROW_CHUNKS * (size_t)(M * D);
+  return gpk_small_work_doubles(Np, B) +
+         (size_t)B * (ga * (size_t)(M * P * D) + (size_t)Np * SQ + gb * WTV_MAX_ROW_CHUNKS * (size_t)(M * D));
 }
 
-// Posterior mean (M x P) and its Jacobian (M x P x D, un-normalised) of M <= 32 queries of one model in ONE launch
-// small_cross_mean_jac_kernel<true>; with var_out / dvar_out also the variance (M) and its gradient (M x D), normalised-target
-// units, in three launches (+ small_var_grad_kernel, small_wtv_grad_kernel).  No synchronisation; Xq and the outputs may be
-// pinned, mapped host memory.
-int gpk_small_grad(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls, double sf2,
-                   const double* y_mean, const double* y_std, const double* W, int64_t Np, int64_t ldw, double kss, double floor_,
-                   const double* Xq, int64_t M, double* work, double* mean_out, double* var_out, double* dmean_out,
-                   double* dvar_out) {
+// the ticket counters of small_wtv_grad_kernel (one per model): the last GPK_SMALL_MAX_MODELS of h->d_cov_count
+constexpr int WTV_COUNTER0 = GPK_SMALL_COV_COUNTERS - GPK_SMALL_MAX_MODELS;
+static_assert(WTV_COUNTER0 >= 1 + GPK_SMALL_MAX_NP / SR / CG, "the covariance reduction's counters come first");
+
+// Posterior mean (B, M, P) and its Jacobian (B, M, P, D; un-normalised) of M <= 32 queries of B models (B > 1: P == 1, the
+// per-axis batch) in ONE launch small_cross_mean_jac_kernel<true>; with var_out / dvar_out also the variance (B, M) and its
+// gradient (B, M, D), normalised-target units, in three launches (+ small_var_grad_kernel, small_wtv_grad_kernel).  No
+// synchronisation; Xq and the outputs may be pinned, mapped host memory.  Arguments as gpk_small_predict.
+int gpk_small_grad_multi(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D, int P,
+                         const double* ls, const double* sf2, const double* y_mean, const double* y_std, const double* const* W,
+                         int64_t Np, int64_t ldw, const double* kss, double floor_, const double* Xq, int64_t M, double* work,
+                         double* mean_out, double* var_out, double* dmean_out, double* dvar_out) {
+  GPK_REQUIRE(h, B >= 1 && B <= GPK_SMALL_MAX_MODELS && (B == 1 || P == 1), "small grad: 1 model, or up to 8 single-output models");
   GPK_REQUIRE(h, gpk_small_ok(Np, D, P, M) && Np == gpk_padded(N), "small grad: shape outside the small-batch path");
   GPK_REQUIRE(h, X && alpha && mean_out && dmean_out && (var_out == nullptr) == (dvar_out == nullptr), "small grad: null pointer");
-  GPK_REQUIRE(h, !var_out || (W && ldw >= Np && ldw % 2 == 0 && ((uintptr_t)W % 16) == 0),
+  GPK_REQUIRE(h, !var_out || (W && kss && ldw >= Np && ldw % 2 == 0),
               "small grad: the variance gradient needs the (16-byte aligned) inverse factor");
   if (var_out) GPK_TRY(ensure_cov_counters(h));
   SmallK k{};
-  k.X[0] = X; k.alpha[0] = alpha; k.W[0] = var_out ? W : nullptr;
-  for (int d = 0; d < 16; ++d) k.ls[0][d] = 1.0;
-  for (int d = 0; d < D; ++d) {
-    GPK_REQUIRE(h, ls[d] > 0.0, "length-scales must be positive");
-    k.ls[0][d] = ls[d];
+  for (int b = 0; b < B; ++b) {
+    GPK_REQUIRE(h, X[b] && alpha[b], "small grad: null pointer");
+    GPK_REQUIRE(h, !var_out || (W[b] && ((uintptr_t)W[b] % 16) == 0),
+                "small grad: the variance gradient needs the (16-byte aligned) inverse factor");
+    k.X[b] = X[b]; k.alpha[b] = alpha[b]; k.W[b] = var_out ? W[b] : nullptr;
+    for (int d = 0; d < 16; ++d) k.ls[b][d] = 1.0;
+    for (int d = 0; d < D; ++d) {
+      GPK_REQUIRE(h, ls[b * D + d] > 0.0, "length-scales must be positive");
+      k.ls[b][d] = ls[b * D + d];
+    }
+    k.sf2[b] = sf2[b];
+    k.kss[b] = var_out ? kss[b] : 0.0;
   }
-  k.sf2[0] = sf2;
-  k.kss[0] = var_out ? kss : 0.0;
-  for (int o = 0; o < P; ++o) { k.ymean[o] = y_mean[o]; k.ystd[o] = y_std[o]; }
+  for (int o = 0; o < B * P; ++o) { k.ymean[o] = y_mean[o]; k.ystd[o] = y_std[o]; }
   const unsigned ga = (unsigned)(Np / SJ), gb = (unsigned)(Np / SR);
   static_assert(SR == GW, "small_wtv_grad_kernel takes as many columns of W per workgroup as small_var_kernel takes rows");
-  double* Ks = work;                                       // SQ x Np
-  double* pmean = Ks + (size_t)SQ * Np;                    // ga x (SQ * SP)
-  double* pvar = pmean + (size_t)ga * (SQ * SP);           // gb x SQ
-  double* pjac = pvar + (size_t)gb * SQ;                   // ga x (M * P * D)
-  double* Vs = pjac + (size_t)ga * (M * P * D);            // Np x SQ
-  double* pdv = Vs + (size_t)Np * SQ;                      // (gb x row chunks) x (M * D)
+  double* Ks = work;                                       // B x SQ x Np
+  double* pmean = Ks + (size_t)B * SQ * Np;                // B x ga x (SQ * SP)
+  double* pvar = pmean + (size_t)B * ga * (SQ * SP);       // B x gb x SQ
+  double* pjac = pvar + (size_t)B * gb * SQ;               // B x ga x (M * P * D)
+  double* Vs = pjac + (size_t)B * ga * (M * P * D);        // B x Np x SQ
+  double* pdv = Vs + (size_t)B * Np * SQ;                  // B x (gb x row chunks) x (M * D)
   if (!var_out) {
-    hipLaunchKernelGGL((small_cross_mean_jac_kernel<true>), dim3(ga, 1), dim3(256), 0, h->stream, k, (long long)N,
+    hipLaunchKernelGGL((small_cross_mean_jac_kernel<true>), dim3(ga, B), dim3(256), 0, h->stream, k, (long long)N,
                        (long long)Np, D, P, Xq, (int)M, (double*)nullptr, pmean, h->d_count, mean_out, pjac, dmean_out);
     GPK_LAUNCH_CHECK(h);
     return GPK_OK;
   }
-  hipLaunchKernelGGL(small_cross_mean_jac_kernel<false>, dim3(ga, 1), dim3(256), 0, h->stream, k, (long long)N,
+  hipLaunchKernelGGL(small_cross_mean_jac_kernel<false>, dim3(ga, B), dim3(256), 0, h->stream, k, (long long)N,
                      (long long)Np, D, P, Xq, (int)M, Ks, pmean, h->d_count, mean_out, pjac, dmean_out);
   GPK_LAUNCH_CHECK(h);
   if (M <= 16)
-    hipLaunchKernelGGL(small_var_grad_kernel<1>, dim3(gb, 1), dim3(64 * VW), 0, h->stream, k, (long long)ldw, (long long)Np,
+    hipLaunchKernelGGL(small_var_grad_kernel<1>, dim3(gb, B), dim3(64 * VW), 0, h->stream, k, (long long)ldw, (long long)Np,
                        (const double*)Ks, (int)M, P, floor_, (const double*)pmean, ga, pvar, h->d_count + GPK_SMALL_MAX_MODELS,
                        mean_out, var_out, Vs, (const double*)pjac, D, dmean_out);
   else
-    hipLaunchKernelGGL(small_var_grad_kernel<2>, dim3(gb, 1), dim3(64 * VW), 0, h->stream, k, (long long)ldw, (long long)Np,
+    hipLaunchKernelGGL(small_var_grad_kernel<2>, dim3(gb, B), dim3(64 * VW), 0, h->stream, k, (long long)ldw, (long long)Np,
                        (const double*)Ks, (int)M, P, floor_, (const double*)pmean, ga, pvar, h->d_count + GPK_SMALL_MAX_MODELS,
                        mean_out, var_out, Vs, (const double*)pjac, D, dmean_out);
   GPK_LAUNCH_CHECK(h);
-  // up to 4 row chunks per column block while that keeps the launch within one workgroup per CU (Np = 1024: 64 x 4)
-  unsigned rc = 256 / gb;
+  // up to 4 row chunks per column block while that keeps the launch within one workgroup per CU (Np = 1024: 64 x 4 for one
+  // model, 64 x 1 x 6 for six)
+  unsigned rc = 256 / (gb * (unsigned)B);
   rc = rc < 1 ? 1 : (rc > WTV_MAX_ROW_CHUNKS ? WTV_MAX_ROW_CHUNKS : rc);
-  hipLaunchKernelGGL(small_wtv_grad_kernel, dim3(gb, rc), dim3(GT), 0, h->stream, k, (long long)ldw, (long long)N, (long long)Np, D,
-                     (const double*)Ks, (const double*)Vs, Xq, (int)M, pdv, h->d_cov_count + GPK_SMALL_COV_COUNTERS - 1, dvar_out);
+  hipLaunchKernelGGL(small_wtv_grad_kernel, dim3(gb, rc, B), dim3(GT), 0, h->stream, k, (long long)ldw, (long long)N, (long long)Np, D,
+                     (const double*)Ks, (const double*)Vs, Xq, (int)M, pdv, h->d_cov_count + WTV_COUNTER0, dvar_out);
   GPK_LAUNCH_CHECK(h);
   return GPK_OK;
+}
+
+// one model with P <= 16 outputs: the same launches on a (., 1) grid
+int gpk_small_grad(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls, double sf2,
+                   const double* y_mean, const double* y_std, const double* W, int64_t Np, int64_t ldw, double kss, double floor_,
+                   const double* Xq, int64_t M, double* work, double* mean_out, double* var_out, double* dmean_out,
+                   double* dvar_out) {
+  return gpk_small_grad_multi(h, 1, &X, &alpha, N, D, P, ls, &sf2, y_mean, y_std, &W, Np, ldw, &kss, floor_, Xq, M, work, mean_out,
+                              var_out, dmean_out, dvar_out);
 }

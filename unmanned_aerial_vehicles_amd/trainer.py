@@ -322,6 +322,119 @@ class PreTrainedGP:
                 mean[:, i], std[:, i] = 0.0, 1e6
         return mean, std
 
+    # ---- input gradients: the first-order terms of the per-axis models in raw units ---------------------------------
+    def predict_residual_jacobian_batch(self, X, return_std=False):
+        """Residual means of a batch of raw [state(6), control(4)] rows and their Jacobians with respect to those raw
+        inputs - what an MPC linearises with (quadrotor_gp_mpc/quadrotor_gp_mpc/mpc_controller.py:318) - and, with
+        return_std=True, the standard deviations `predict_residual_batch` returns and their gradients:
+        (mean (M, 6), J (M, 6, 10)[, std (M, 6), dstd (M, 6, 10)]).  With z = (x - sx.mean_) / sx.scale_, mu_b / var_b model
+        b's posterior on the scaled inputs and sy_b its target scaler:
+
+            J[m, b, d]    = sy_b.scale_ / sx.scale_[d] * d mu_b / d z_d
+            dstd[m, b, d] = |sy_b.scale_| / sx.scale_[d] * (d var_b / d z_d) / (2 sigma_b)        (0 where sigma_b = 0)
+
+        Models that share inputs and scaler (those `GPTrainer` writes): ONE call for all of them
+        (`BatchedARDGP.predict_jacobian`; up to 32 rows one launch for means + Jacobians, three with the variances); otherwise
+        one `predict_jacobian` per model with its own scalers.  The reference has no counterpart: a caller would difference
+        `pretrained_gp.py:52-98`.  Missing or failing components: mean 0, J 0, std 1e6, dstd 0.  Never raises."""
+        try:
+            X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+            M = len(X)
+        except Exception as e:  # noqa: BLE001
+            print(f"GP prediction failed: {e}")
+            X, M = None, 1
+        mean, J = np.zeros((M, 6)), np.zeros((M, 6, 10))
+        std, dstd = np.full((M, 6), 1e6), np.zeros((M, 6, 10))
+        done = set()
+
+        def put(i, name, sx, mu, dmu, var, dvar):
+            sy = self.scalers_y[name]
+            scale_y = float(np.ravel(sy.scale_)[0])
+            m_i = sy.inverse_transform(np.asarray(mu, dtype=np.float64).reshape(-1, 1)).ravel()
+            J_i = scale_y * np.asarray(dmu, dtype=np.float64).reshape(M, -1) / sx.scale_[None, :]
+            if return_std:
+                sig = np.sqrt(np.asarray(var, dtype=np.float64).reshape(M))
+                pos = sig > 0.0
+                g = np.zeros((M, J_i.shape[1]))
+                g[pos] = np.asarray(dvar, dtype=np.float64).reshape(M, -1)[pos] / (2.0 * sig[pos, None])
+                s_i, ds_i = np.abs(sig * scale_y), abs(scale_y) * g / sx.scale_[None, :]
+                if not (np.isfinite(s_i).all() and np.isfinite(ds_i).all()):
+                    raise FloatingPointError("non-finite standard deviation or gradient")
+            if not (np.isfinite(m_i).all() and np.isfinite(J_i).all()):
+                raise FloatingPointError("non-finite mean or Jacobian")
+            mean[:, i], J[:, i, :] = m_i, J_i
+            if return_std:
+                std[:, i], dstd[:, i, :] = s_i, ds_i
+
+        if X is not None and self.is_loaded and X.shape[1] == 10:
+            fused = self._fused()
+            if fused:
+                bg, names = fused
+                try:
+                    sx = self.scalers_X[names[0]]
+                    out = bg.predict_jacobian(sx.transform(X), return_var=return_std)
+                    mu, dmu = out[0], out[1]
+                    var, dvar = (out[2], out[3]) if return_std else (None, None)
+                    for j, n in enumerate(names):
+                        put(OUTPUT_NAMES.index(n), n, sx, mu[:, j], dmu[:, j], var[:, j] if return_std else None,
+                            dvar[:, j] if return_std else None)
+                        done.add(n)
+                except Exception as e:  # noqa: BLE001 - as predict_residual_batch: the per-model loop below still serves
+                    print(f"GP prediction failed: {e}")
+            for i, name in enumerate(OUTPUT_NAMES):
+                if name not in self.gp_models or name in done:
+                    continue
+                try:
+                    sx = self.scalers_X[name]
+                    out = self.gp_models[name].predict_jacobian(sx.transform(X), return_var=return_std)
+                    put(i, name, sx, out[0], out[1], out[2] if return_std else None, out[3] if return_std else None)
+                except Exception as e:  # noqa: BLE001
+                    print(f"GP prediction failed for {name}: {e}")
+                    mean[:, i], J[:, i], std[:, i], dstd[:, i] = 0.0, 0.0, 1e6, 0.0
+        if return_std:
+            return mean, J, std, dstd
+        return mean, J
+
+    def predict_residual_jacobian(self, state, control):
+        """One query -> (mean (6,), J (6, 10)), J = d mean / d [state(6), control(4)]; not loaded or failed: zeros."""
+        try:
+            row = np.concatenate([np.asarray(state, float)[:6], np.asarray(control, float)[:4]]).reshape(1, -1)
+            mean, J = self.predict_residual_jacobian_batch(row)
+            return mean[0], J[0]
+        except Exception as e:  # noqa: BLE001
+            print(f"GP prediction failed: {e}")
+            return np.zeros(6), np.zeros((6, 10))
+
+    def linearize_residuals(self, X_guess, U_guess, dt, gain=0.1, n_states=6):
+        """`SimpleQuadrotorGP.linearize_gp_residuals` for the per-axis models: the frozen residual D (6, N) and its
+        linearisation A (N, 6, 6), B (N, 6, 4) around the guess X_guess (6+, N+1), U_guess (4, N) - zero except rows 3:6 =
+        gain / dt * J_k[3:6, :6] and gain / dt * J_k[3:6, 6:10] - from ONE call for the whole horizon; (R, ...) leading axis
+        for R rollouts.  Not loaded or a failed prediction: zeros."""
+        X_guess = np.asarray(X_guess, dtype=float)
+        U_guess = np.asarray(U_guess, dtype=float)
+        single = X_guess.ndim == 2
+        if single:
+            X_guess, U_guess = X_guess[None], U_guess[None]
+        R, _, N = U_guess.shape
+        D = np.zeros((R, n_states, N))
+        A = np.zeros((R, N, n_states, 6))
+        B = np.zeros((R, N, n_states, 4))
+        if self.is_loaded:
+            try:
+                rows = np.concatenate([X_guess[:, :6, :N], U_guess[:, :4, :]], axis=1)    # (R, 10, N)
+                rows = rows.transpose(0, 2, 1).reshape(R * N, -1)
+                mean, J = self.predict_residual_jacobian_batch(rows)
+                if n_states >= 6:
+                    D[:, 3:6, :] = (gain * (mean / dt)[:, 3:6]).reshape(R, N, 3).transpose(0, 2, 1)
+                    A[:, :, 3:6, :] = (gain / dt * J[:, 3:6, :6]).reshape(R, N, 3, 6)
+                    B[:, :, 3:6, :] = (gain / dt * J[:, 3:6, 6:10]).reshape(R, N, 3, 4)
+            except Exception as e:  # noqa: BLE001
+                print(f"GP prediction failed: {e}")
+                D[:], A[:], B[:] = 0.0, 0.0, 0.0
+        if single:
+            return D[0], A[0], B[0]
+        return D, A, B
+
     def get_uncertainty(self, state, control):
         return float(np.mean(self.predict_residual(state, control)[1]))
 
