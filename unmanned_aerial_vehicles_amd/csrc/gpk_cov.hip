@@ -94,48 +94,3 @@ extern "C" int gpk_predict_cov(gpk_handle h, int dtype, const void* X, int64_t N
   GPK_TRY(gpk_trsm_lower_left(h, GPK_F64, L, Np, ldl, winv, work, Mp, Mp));
   return cov_from_v(h, (const double*)work, Np, (const double*)Xq, M, D, ls, sf2, noise, cov, ldc);
 }
-
-// staging of the one-call covariance: the handle's serving blocks (gpk_api.hip)
-int gpk_serve_reserve(gpk_handle h, size_t host_need, size_t dev_need);
-
-extern "C" int gpk_predict_host_cov(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P,
-                                    const double* ls, double sf2, const double* y_mean, const double* y_std, const double* W,
-                                    int64_t Np, int64_t ldw, double noise, const double* Xq_host, int64_t M, double* mean_host,
-                                    double* cov_host) {
-  if (!h) return GPK_BAD_ARG;
-  GPK_REQUIRE(h, X && alpha && ls && y_mean && y_std && W && Xq_host && mean_host && cov_host, "predict_host_cov: null pointer");
-  GPK_REQUIRE(h, N >= 1 && M >= 1 && M <= GPK_HOST_MAX_M, "predict_host_cov: M must be in [1, GPK_HOST_MAX_M]");
-  GPK_REQUIRE(h, Np == gpk_padded(N) && ldw >= Np, "predict_host_cov: Np must equal gpk_padded(N), ldw >= Np");
-  GPK_REQUIRE(h, D >= 1 && D <= GPK_MAX_D_PREDICT && P >= 1 && P <= GPK_MAX_P, "predict_host_cov: D <= 16, P <= 16");
-  GPK_REQUIRE(h, h->batch == 1, "predict_host_cov: not available in batched mode");
-  const int64_t Mp = gpk_padded(M);
-  const bool small = h->small_path && gpk_small_ok(Np, D, P, M);
-  // pinned host block [Xq | pad][mean | cov (small batches) | pad]; device block [Xq | pad][work]: the small kernels' K* and
-  // shares, or V (Np x Mp) and Sigma (Mp x Mp)
-  const size_t nq = ((size_t)M * D + 15) & ~(size_t)15, nm = (size_t)M * P, nc = small ? (size_t)M * M : 0;
-  const size_t host_need = (nq + ((nm + nc + 15) & ~(size_t)15)) * sizeof(double);
-  const size_t work_need = small ? gpk_small_cov_work_doubles(Np) : (size_t)Np * Mp + (size_t)Mp * Mp;
-  GPK_TRY(gpk_serve_reserve(h, host_need, (nq + work_need) * sizeof(double)));
-  double* hq = (double*)h->serve_host;
-  double* hout = hq + nq;                      // [mean | cov]
-  double* dq = (double*)h->serve_dev;
-  double* dwork = dq + nq;
-  if (h->debug_fill) GPK_CHECK_HIP(h, hipMemsetAsync(dwork, 0xFF, work_need * sizeof(double), h->stream));
-  memcpy(hq, Xq_host, (size_t)M * D * sizeof(double));
-  if (small) {
-    GPK_TRY(gpk_small_cov(h, X, alpha, N, D, P, ls, sf2, y_mean, y_std, W, Np, ldw, noise, hq, M, dwork, hout, hout + nm));
-    GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
-    memcpy(cov_host, hout + nm, nc * sizeof(double));
-  } else {
-    double* dV = dwork;
-    double* dcov = dwork + (size_t)Np * Mp;
-    GPK_CHECK_HIP(h, hipMemcpyAsync(dq, hq, (size_t)M * D * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    GPK_TRY(gpk_predict_mean(h, GPK_F64, X, alpha, N, D, P, ls, sf2, y_mean, y_std, dq, M, hout));
-    GPK_TRY(gpk_predict_cov_inv(h, GPK_F64, X, N, D, ls, sf2, W, Np, ldw, dq, M, noise, dV, dcov, Mp));
-    GPK_CHECK_HIP(h, hipMemcpy2DAsync(cov_host, (size_t)M * sizeof(double), dcov, (size_t)Mp * sizeof(double),
-                                      (size_t)M * sizeof(double), (size_t)M, hipMemcpyDeviceToHost, h->stream));
-    GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
-  }
-  memcpy(mean_host, hout, nm * sizeof(double));
-  return GPK_OK;
-}

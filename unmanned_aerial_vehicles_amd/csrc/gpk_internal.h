@@ -29,7 +29,7 @@ struct gpk_context {
   double* d_small = nullptr;    // ... its device address: the kernels write there, the host reads h_small after the synchronisation - no copy command
   unsigned* d_count = nullptr;  // 2 x 8 zero-initialised ticket counters (last-workgroup reductions, gpk_small.hip)
   unsigned* d_cov_count = nullptr;   // zero-initialised ticket counters of the small covariance reduction (allocated on first use)
-  // staging of gpk_predict_host: device block [Xq | mean | var | K* work] and its pinned host mirror [Xq | mean | var]
+  // staging of the one-call serving entries (gpk_serve.hip): device block [Xq | work] and pinned, mapped host block [Xq | outputs]
   void* serve_dev = nullptr;
   size_t serve_dev_bytes = 0;
   void* serve_host = nullptr;
@@ -222,36 +222,33 @@ int gpk_gemm(gpk_handle h, int dtype, const GemmArgs& g);
 int gpk_gemm_tile(gpk_handle h, const GemmArgs& g);   // 128 or 64: the tile edge gpk_gemm will pick
 
 // ---- small-batch serving kernels (gpk_small.hip) -------------------------------------
+// M <= 32 fp64 queries against B models x P outputs each (B > 1: P == 1, the per-axis batch), all models on one query
+// batch.  X / alpha / W: B device pointers; ls: B x D; sf2, kss: B; y_mean, y_std: B * P.  No call synchronises; Xq and
+// the outputs may be pinned, mapped host memory.  Means are un-normalised, variances / covariances in normalised-target units.
 constexpr int GPK_SMALL_MAX_M = 32;          // queries per call
 constexpr int64_t GPK_SMALL_MAX_NP = 16384;  // padded training rows
 constexpr int GPK_SMALL_MAX_MODELS = 8;      // single-output models served by one call
+constexpr int GPK_SMALL_COV_COUNTERS = 128;  // h->d_cov_count: ticket counters of the covariance's two-level reduction; the last
+                                             // GPK_SMALL_MAX_MODELS are small_wtv_grad_kernel's, one per model
 bool gpk_small_ok(int64_t Np, int D, int P, int64_t M);
-size_t gpk_small_work_doubles(int64_t Np, int B);   // device work area: per model K* (32 x Np) + the workgroups' shares
-// B models x P outputs each (B > 1: P == 1): mean (B, M, P) and, if var_out, variance (B, M) of M <= 32 fp64 queries
-// shared by the models; Xq / mean_out / var_out may be mapped host memory.  X / alpha / W: B device pointers;
-// ls: B x D; sf2, kss: B; y_mean, y_std: B * P.
-// posterior mean + covariance of M <= 32 queries of one model (small_cross_mean_kernel + small_cov_kernel)
-constexpr int GPK_SMALL_COV_COUNTERS = 128;   // ticket counters of its two-level reduction (h->d_cov_count); the last
-                                              // GPK_SMALL_MAX_MODELS are small_wtv_grad_kernel's, one per model
-size_t gpk_small_cov_work_doubles(int64_t Np);
-int gpk_small_cov(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls, double sf2,
-                  const double* y_mean, const double* y_std, const double* W, int64_t Np, int64_t ldw, double noise,
-                  const double* Xq, int64_t M, double* work, double* mean_out, double* cov_out);
-// posterior mean + its Jacobian (one launch) and, with var_out / dvar_out, variance + its gradient (three launches) of M <= 32 queries
-size_t gpk_small_grad_work_doubles(int64_t Np, int M, int D, int P, int B = 1);
-// ... of B models on one query batch (B > 1: P == 1; arguments as gpk_small_predict; outputs (B, M, P), (B, M), (B, M, P, D), (B, M, D))
-int gpk_small_grad_multi(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D, int P,
-                         const double* ls, const double* sf2, const double* y_mean, const double* y_std, const double* const* W,
-                         int64_t Np, int64_t ldw, const double* kss, double floor_, const double* Xq, int64_t M, double* work,
-                         double* mean_out, double* var_out, double* dmean_out, double* dvar_out);
-int gpk_small_grad(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls, double sf2,
-                   const double* y_mean, const double* y_std, const double* W, int64_t Np, int64_t ldw, double kss, double floor_,
-                   const double* Xq, int64_t M, double* work, double* mean_out, double* var_out, double* dmean_out,
-                   double* dvar_out);
+// doubles of device work area (`work`) that a call of the given kind needs: per model K* (32 x Np) + the workgroups' shares
+enum { GPK_SMALL_PREDICT, GPK_SMALL_COV, GPK_SMALL_GRAD };
+size_t gpk_small_work_doubles(int call, int64_t Np, int B, int64_t M, int D, int P);
+// mean (B, M, P) and, if var_out, variance (B, M): one launch, or two (small_cross_mean_kernel + small_var_kernel)
 int gpk_small_predict(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D, int P,
                       const double* ls, const double* sf2, const double* y_mean, const double* y_std,
                       const double* const* W, int64_t Np, int64_t ldw, const double* kss, double floor_,
                       const double* Xq, int64_t M, double* work, double* mean_out, double* var_out);
+// mean (M, P) and covariance (M, M) of one model: two launches (small_cross_mean_kernel + small_cov_kernel)
+int gpk_small_cov(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls, double sf2,
+                  const double* y_mean, const double* y_std, const double* W, int64_t Np, int64_t ldw, double noise,
+                  const double* Xq, int64_t M, double* work, double* mean_out, double* cov_out);
+// mean (B, M, P) and its Jacobian (B, M, P, D; un-normalised) in ONE launch (small_cross_mean_jac_kernel); with var_out /
+// dvar_out also the variance (B, M) and its gradient (B, M, D) in three (+ small_var_grad_kernel, small_wtv_grad_kernel)
+int gpk_small_grad_multi(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D, int P,
+                         const double* ls, const double* sf2, const double* y_mean, const double* y_std, const double* const* W,
+                         int64_t Np, int64_t ldw, const double* kss, double floor_, const double* Xq, int64_t M, double* work,
+                         double* mean_out, double* var_out, double* dmean_out, double* dvar_out);
 
 // K* straight into the fragment-order fp16 x 2 split layout (gpk_gram.hip); D <= 16
 int gpk_cross_split2(gpk_handle h, const float* Xq, int64_t M, const float* X, int64_t N, int D, const double* ls,

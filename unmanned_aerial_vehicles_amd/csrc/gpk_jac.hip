@@ -485,123 +485,3 @@ extern "C" int gpk_predict_var_grad_inv(gpk_handle h, const double* X, int64_t N
   GPK_LAUNCH_CHECK(h);
   return GPK_OK;
 }
-
-// staging of the one-call serving entries: the handle's serving blocks (gpk_api.hip)
-int gpk_serve_reserve(gpk_handle h, size_t host_need, size_t dev_need);
-
-extern "C" int gpk_predict_host_grad(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P,
-                                     const double* ls, double sf2, const double* y_mean, const double* y_std, const double* W,
-                                     int64_t Np, int64_t ldw, double kss, double floor_, const double* Xq_host, int64_t M,
-                                     double* mean_host, double* var_host, double* dmean_host, double* dvar_host) {
-  if (!h) return GPK_BAD_ARG;
-  GPK_REQUIRE(h, X && alpha && ls && y_mean && y_std && Xq_host && mean_host && dmean_host, "predict_host_grad: null pointer");
-  GPK_REQUIRE(h, N >= 1 && M >= 1 && M <= GPK_HOST_MAX_M, "predict_host_grad: M must be in [1, GPK_HOST_MAX_M]");
-  GPK_REQUIRE(h, D >= 1 && D <= GPK_MAX_D_PREDICT && P >= 1 && P <= GPK_MAX_P, "predict_host_grad: D <= 16, P <= 16");
-  GPK_REQUIRE(h, (var_host == nullptr) == (dvar_host == nullptr), "predict_host_grad: var and dvar come together (both or neither)");
-  const bool want_var = var_host != nullptr;
-  GPK_REQUIRE(h, !want_var || (W && Np == gpk_padded(N) && ldw >= Np), "predict_host_grad: the variance gradient needs the inverse factor");
-  GPK_REQUIRE(h, h->batch == 1, "predict_host_grad: not available in batched mode");
-  const int64_t Npad = gpk_padded(N);
-  const bool small = h->small_path && gpk_small_ok(Npad, D, P, M);
-  // query panel of the large route: the three Np x Mp panels within 6 GiB (DeviceGP.VAR_PANEL_BYTES)
-  int64_t panel = (int64_t)((6ull << 30) / ((size_t)3 * Npad * sizeof(double))) / GPK_TILE * GPK_TILE;
-  if (panel < GPK_TILE) panel = GPK_TILE;
-  if (panel > gpk_padded(M)) panel = gpk_padded(M);
-  // pinned host block [Xq | pad][mean | var | dmean | dvar | pad]; device block [Xq | pad][work]
-  const size_t nq = ((size_t)M * D + 15) & ~(size_t)15, nm = (size_t)M * P, nv = (size_t)M, njm = (size_t)M * P * D,
-               njv = (size_t)M * D;
-  const size_t nout_pad = (nm + nv + njm + njv + 15) & ~(size_t)15;
-  const size_t work_need = small ? gpk_small_grad_work_doubles(Npad, (int)M, D, P) : (want_var ? (size_t)3 * Npad * panel : 0);
-  GPK_TRY(gpk_serve_reserve(h, (nq + nout_pad) * sizeof(double), (nq + work_need) * sizeof(double)));
-  double* hq = (double*)h->serve_host;
-  double* hmean = hq + nq;
-  double* hvar = hmean + nm;
-  double* hdm = hvar + nv;
-  double* hdv = hdm + njm;
-  double* dq = (double*)h->serve_dev;
-  double* dwork = dq + nq;
-  if (h->debug_fill && work_need > 0) GPK_CHECK_HIP(h, hipMemsetAsync(dwork, 0xFF, work_need * sizeof(double), h->stream));
-  memcpy(hq, Xq_host, (size_t)M * D * sizeof(double));
-  // the results are written by the kernels straight into the pinned, mapped block: no download command, one synchronisation
-  if (small) {
-    GPK_TRY(gpk_small_grad(h, X, alpha, N, D, P, ls, sf2, y_mean, y_std, want_var ? W : nullptr, Npad, ldw, kss, floor_, hq, M,
-                           dwork, hmean, want_var ? hvar : nullptr, hdm, want_var ? hdv : nullptr));
-  } else {
-    GPK_CHECK_HIP(h, hipMemcpyAsync(dq, hq, (size_t)M * D * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    GPK_TRY(gpk_predict_mean(h, GPK_F64, X, alpha, N, D, P, ls, sf2, y_mean, y_std, dq, M, hmean));
-    GPK_TRY(gpk_predict_mean_grad(h, X, alpha, N, D, P, ls, sf2, y_std, dq, M, hdm));
-    if (want_var)
-      for (int64_t m0 = 0; m0 < M; m0 += panel) {
-        const int64_t mc = M - m0 < panel ? M - m0 : panel;
-        GPK_TRY(gpk_predict_var_grad_inv(h, X, N, D, ls, sf2, W, Np, ldw, dq + m0 * D, mc, kss, floor_, dwork, hvar + m0,
-                                         hdv + m0 * D));
-      }
-  }
-  GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
-  memcpy(mean_host, hmean, nm * sizeof(double));
-  memcpy(dmean_host, hdm, njm * sizeof(double));
-  if (want_var) {
-    memcpy(var_host, hvar, nv * sizeof(double));
-    memcpy(dvar_host, hdv, njv * sizeof(double));
-  }
-  return GPK_OK;
-}
-
-extern "C" int gpk_predict_host_multi_grad(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N,
-                                           int D, const double* ls, const double* sf2, const double* y_mean,
-                                           const double* y_std, const double* const* W, int64_t Np, int64_t ldw,
-                                           const double* kss, double floor_, const double* Xq_host, int64_t M,
-                                           double* mean_host, double* var_host, double* dmean_host, double* dvar_host) {
-  if (!h) return GPK_BAD_ARG;
-  GPK_REQUIRE(h, X && alpha && ls && sf2 && y_mean && y_std && Xq_host && mean_host && dmean_host,
-              "predict_host_multi_grad: null pointer");
-  GPK_REQUIRE(h, B >= 1 && B <= GPK_SMALL_MAX_MODELS, "predict_host_multi_grad: 1..8 models");
-  GPK_REQUIRE(h, N >= 1 && gpk_small_ok(gpk_padded(N), D, 1, M), "predict_host_multi_grad: needs M <= 32, D <= 16, N <= 16384");
-  GPK_REQUIRE(h, (var_host == nullptr) == (dvar_host == nullptr),
-              "predict_host_multi_grad: var and dvar come together (both or neither)");
-  const bool want_var = var_host != nullptr;
-  GPK_REQUIRE(h, !want_var || (W && kss && Np == gpk_padded(N) && ldw >= Np),
-              "predict_host_multi_grad: the variance gradient needs the inverse factors");
-  GPK_REQUIRE(h, h->batch == 1, "predict_host_multi_grad: not available in batched mode");
-  for (int b = 0; b < B; ++b)
-    GPK_REQUIRE(h, X[b] && alpha[b] && (!want_var || W[b]), "predict_host_multi_grad: null model pointer");
-  const int64_t Npad = gpk_padded(N), Mp = gpk_padded(M);
-  const bool small = h->small_path != 0;
-  // pinned host block [Xq | pad][mean (B x M) | var (B x M) | dmean (B x M x D) | dvar (B x M x D) | pad]; device block [Xq | pad][work]
-  const size_t nq = ((size_t)M * D + 15) & ~(size_t)15, nm = (size_t)B * M, nj = (size_t)B * M * D;
-  const size_t nout_pad = (2 * nm + 2 * nj + 15) & ~(size_t)15;
-  const size_t work_need = small ? gpk_small_grad_work_doubles(Npad, (int)M, D, 1, B) : (want_var ? (size_t)3 * Npad * Mp : 0);
-  GPK_TRY(gpk_serve_reserve(h, (nq + nout_pad) * sizeof(double), (nq + work_need) * sizeof(double)));
-  double* hq = (double*)h->serve_host;
-  double* hmean = hq + nq;
-  double* hvar = hmean + nm;
-  double* hdm = hvar + nm;
-  double* hdv = hdm + nj;
-  double* dq = (double*)h->serve_dev;
-  double* dwork = dq + nq;
-  if (h->debug_fill && work_need > 0) GPK_CHECK_HIP(h, hipMemsetAsync(dwork, 0xFF, work_need * sizeof(double), h->stream));
-  memcpy(hq, Xq_host, (size_t)M * D * sizeof(double));
-  if (small) {
-    // all models in one launch (mean + Jacobian) or three (all four results); results straight into the pinned, mapped block
-    GPK_TRY(gpk_small_grad_multi(h, B, X, alpha, N, D, 1, ls, sf2, y_mean, y_std, want_var ? W : nullptr, Npad, ldw, kss, floor_,
-                                 hq, M, dwork, hmean, want_var ? hvar : nullptr, hdm, want_var ? hdv : nullptr));
-  } else {
-    // option small_path = 0 (the cross-check of the small-batch kernels): the general building blocks, model by model
-    GPK_CHECK_HIP(h, hipMemcpyAsync(dq, hq, (size_t)M * D * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    for (int b = 0; b < B; ++b) {
-      GPK_TRY(gpk_predict_mean(h, GPK_F64, X[b], alpha[b], N, D, 1, ls + b * D, sf2[b], y_mean + b, y_std + b, dq, M, hmean + b * M));
-      GPK_TRY(gpk_predict_mean_grad(h, X[b], alpha[b], N, D, 1, ls + b * D, sf2[b], y_std + b, dq, M, hdm + (size_t)b * M * D));
-      if (want_var)
-        GPK_TRY(gpk_predict_var_grad_inv(h, X[b], N, D, ls + b * D, sf2[b], W[b], Np, ldw, dq, M, kss[b], floor_, dwork, hvar + b * M,
-                                         hdv + (size_t)b * M * D));
-    }
-  }
-  GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
-  memcpy(mean_host, hmean, nm * sizeof(double));
-  memcpy(dmean_host, hdm, nj * sizeof(double));
-  if (want_var) {
-    memcpy(var_host, hvar, nm * sizeof(double));
-    memcpy(dvar_host, hdv, nj * sizeof(double));
-  }
-  return GPK_OK;
-}

@@ -49,17 +49,17 @@ struct SmallK {
 typedef double d4 __attribute__((ext_vector_type(4)));
 typedef double d2v __attribute__((ext_vector_type(2)));
 
-// Every workgroup has stored its share; true (in all its threads) for the last one to get here.  The barrier
-// orders the workgroup's stores before thread 0's ticket; the ticket is one acquire-release atomic at device scope
-// (release: the shares are written back before it; acquire: the last workgroup drops its cached lines before it
+// Every one of `count` workgroups has stored its share; true (in all its threads) for the last one to get here.  The
+// barrier orders the workgroup's stores before thread 0's ticket; the ticket is one acquire-release atomic at device
+// scope (release: the shares are written back before it; acquire: the last workgroup drops its cached lines before it
 // reads the others' shares) -- one cache write-back per workgroup instead of one per wave.  The counter is left at
 // zero for the next launch.
-__device__ __forceinline__ bool last_workgroup(unsigned* counter, int tid) {
+__device__ __forceinline__ bool last_of(unsigned* counter, unsigned count, int tid) {
   __shared__ int is_last;
   __syncthreads();
   if (tid == 0) {
     const unsigned t = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    is_last = (t == gridDim.x - 1);
+    is_last = (t == count - 1);
     if (is_last) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   __syncthreads();
@@ -236,7 +236,7 @@ __device__ __forceinline__ void small_cross_mean_body(SmallK k, long long N, lon
     }
   }
   if constexpr (FINISH) {
-    if (last_workgroup(counter, tid)) {
+    if (last_of(counter, gridDim.x, tid)) {
       __shared__ double fin[4 * SQ * SP];
       finish_means(pmean, gridDim.x, M, P, k.ymean + b * P, k.ystd + b * P, mean_out, tid, fin);
       if constexpr (JAC) finish_jac(pjac, gridDim.x, M, P, D, k.ystd + b * P, ls, dmean_out, tid, 256);
@@ -290,31 +290,11 @@ __device__ __forceinline__ void vmul(const VFrag<NMB>& f, long long kc, int kq, 
   }
 }
 
-// GRAD (small_var_grad_kernel): the launch also stores its rows of V (Vs: per model Np x SQ, columns < 16 NMB written) for
-// small_wtv_grad_kernel, and workgroup 1 adds the mean Jacobian's shares of the previous launch.  The body is shared;
-// small_var_kernel keeps its signature and its launches.
-template <int NMB, bool GRAD>
-__device__ __forceinline__ void small_var_body(SmallK k, long long ldw, long long Np, const double* Ks,
-                                                            int M, int P, double floor_, const double* pmean,
-                                                            unsigned mean_shares, double* pvar, unsigned* counter,
-                                                            double* mean_out, double* var_out, double* Vs,
-                                                            const double* pjac, int D, double* dmean_out) {
-  __shared__ double red[VW][NMB][16][17];
-  __shared__ double sq[NMB][16][17];
-  const int b = blockIdx.y;
-  const double* __restrict__ W = k.W[b];
-  const double kss = k.kss[b];
-  Ks += (long long)b * SQ * Np;
-  pmean += (long long)b * mean_shares * (SQ * SP);
-  pvar += (long long)b * gridDim.x * SQ;
-  mean_out += (long long)b * M * P;
-  var_out += (long long)b * M;
-  counter += b;
-  if constexpr (GRAD) {
-    Vs += (long long)b * Np * SQ;
-    pjac += (long long)b * mean_shares * (M * P * D);
-    dmean_out += (long long)b * M * P * D;
-  }
+// This workgroup's 16 rows of V = W K*^T (rows blockIdx.x * SR ..), one partial per wave: red[w][mb][row][query].  The
+// barrier after the stores is the last thing it does.
+template <int NMB>
+__device__ __forceinline__ void small_v_rows(const double* __restrict__ W, long long ldw, long long Np, const double* Ks, int M,
+                                             double (&red)[VW][NMB][16][17]) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, i = lane & 15, kq = lane >> 4;
   const long long r0 = (long long)blockIdx.x * SR, row = r0 + i;
   const long long kend = min(Np, (r0 + SR + 63) / 64 * 64);   // the rows' diagonal, rounded up to the chunk
@@ -343,11 +323,48 @@ __device__ __forceinline__ void small_var_body(SmallK k, long long ldw, long lon
 #pragma unroll
     for (int r = 0; r < 4; ++r) red[w][mb][kq + 4 * r][i] = acc[mb][r];
   __syncthreads();
+}
+
+// V[row r][query 16 mb + c] of this workgroup: the waves' partials, added in wave order
+template <int NMB>
+__device__ __forceinline__ double small_v_sum(const double (&red)[VW][NMB][16][17], int mb, int r, int c) {
+  double v = 0.0;
+#pragma unroll
+  for (int u = 0; u < VW; ++u) v += red[u][mb][r][c];
+  return v;
+}
+
+// GRAD (small_var_grad_kernel): the launch also stores its rows of V (Vs: per model Np x SQ, columns < 16 NMB written) for
+// small_wtv_grad_kernel, and workgroup 1 adds the mean Jacobian's shares of the previous launch.  The body is shared;
+// small_var_kernel keeps its signature and its launches.
+template <int NMB, bool GRAD>
+__device__ __forceinline__ void small_var_body(SmallK k, long long ldw, long long Np, const double* Ks,
+                                                            int M, int P, double floor_, const double* pmean,
+                                                            unsigned mean_shares, double* pvar, unsigned* counter,
+                                                            double* mean_out, double* var_out, double* Vs,
+                                                            const double* pjac, int D, double* dmean_out) {
+  __shared__ double red[VW][NMB][16][17];
+  __shared__ double sq[NMB][16][17];
+  const int b = blockIdx.y;
+  const double* __restrict__ W = k.W[b];
+  const double kss = k.kss[b];
+  Ks += (long long)b * SQ * Np;
+  pmean += (long long)b * mean_shares * (SQ * SP);
+  pvar += (long long)b * gridDim.x * SQ;
+  mean_out += (long long)b * M * P;
+  var_out += (long long)b * M;
+  counter += b;
+  if constexpr (GRAD) {
+    Vs += (long long)b * Np * SQ;
+    pjac += (long long)b * mean_shares * (M * P * D);
+    dmean_out += (long long)b * M * P * D;
+  }
+  const int tid = threadIdx.x;
+  const long long r0 = (long long)blockIdx.x * SR;
+  small_v_rows<NMB>(W, ldw, Np, Ks, M, red);
   for (int e = tid; e < NMB * 256; e += 64 * VW) {
     const int mb = e >> 8, r = (e >> 4) & 15, c = e & 15;
-    double v = 0.0;
-#pragma unroll
-    for (int u = 0; u < VW; ++u) v += red[u][mb][r][c];
+    const double v = small_v_sum<NMB>(red, mb, r, c);
     sq[mb][r][c] = v * v;
     if constexpr (GRAD) Vs[(r0 + r) * SQ + 16 * mb + c] = v;
   }
@@ -366,7 +383,7 @@ __device__ __forceinline__ void small_var_body(SmallK k, long long ldw, long lon
   if constexpr (GRAD) {
     if (blockIdx.x == 1) finish_jac(pjac, mean_shares, M, P, D, k.ystd + b * P, k.ls[b], dmean_out, tid, 64 * VW);
   }
-  if (last_workgroup(counter, tid)) {
+  if (last_of(counter, gridDim.x, tid)) {
     __shared__ double part[2 * VW][SQ];
     const int m = tid & 31, pt = tid >> 5;
     part[pt][m] = (m < NMB * 16) ? sum_shares(pvar + m, pt, 2 * VW, gridDim.x, SQ) : 0.0;
@@ -398,20 +415,6 @@ __global__ __launch_bounds__(64 * VW) void small_var_grad_kernel(SmallK k, long 
                             dmean_out);
 }
 
-// Every one of `count` workgroups has stored its part; true (in all its threads) for the last one: last_workgroup with
-// an explicit count, for the groups of the two-level reduction below.
-__device__ __forceinline__ bool last_of(unsigned* counter, unsigned count, int tid) {
-  __shared__ int is_last;
-  __syncthreads();
-  if (tid == 0) {
-    const unsigned t = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    is_last = (t == count - 1);
-    if (is_last) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __syncthreads();
-  return is_last != 0;
-}
-
 constexpr int CG = 16;                   // workgroups per first-level group of the covariance reduction
 constexpr int CE = SQ * (SQ + 1) / 2;    // packed lower-triangle entries of a 32 x 32 share
 
@@ -423,7 +426,7 @@ __device__ __forceinline__ void tri_index(int t, int& i, int& j) {
   j = t - i * (i + 1) / 2;
 }
 
-// Posterior covariance of M <= 32 queries (one model): the k-loop of small_var_kernel, then the workgroup's share of V^T V.
+// Posterior covariance of M <= 32 queries (one model): the rows of V as in small_var_kernel, then the workgroup's share of V^T V.
 // counters: [0] the top level, [1 + g] group g; all left at zero.  pcov: gridDim.x x CE, gcov: groups x CE.
 template <int NMB>
 __global__ __launch_bounds__(64 * VW) void small_cov_kernel(SmallK k, long long ldw, long long Np, const double* Ks, int M,
@@ -435,36 +438,11 @@ __global__ __launch_bounds__(64 * VW) void small_cov_kernel(SmallK k, long long 
   __shared__ double vt[NMB * 16][17];          // this workgroup's rows of V, transposed: [query][row]
   __shared__ double qs[SQ][SD + 1];
   const double* __restrict__ W = k.W[0];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, i = lane & 15, kq = lane >> 4;
-  const long long r0 = (long long)blockIdx.x * SR, row = r0 + i;
-  const long long kend = min(Np, (r0 + SR + 63) / 64 * 64);
-  const int nch = (int)(kend / 64);
-  const double* wp = W + row * ldw + 2 * kq;
-  const double* kp[NMB];
-#pragma unroll
-  for (int mb = 0; mb < NMB; ++mb) kp[mb] = Ks + (long long)min(16 * mb + i, M - 1) * Np + 2 * kq;
-  d4 acc[NMB];
-#pragma unroll
-  for (int mb = 0; mb < NMB; ++mb) acc[mb] = d4{0.0, 0.0, 0.0, 0.0};
-  VFrag<NMB> f0, f1;
-  if (w < nch) vload<NMB>(f0, wp, kp, (long long)w * 64);
-  for (int c = w; c < nch; c += 2 * VW) {
-    const bool n1 = c + VW < nch, n2 = c + 2 * VW < nch;
-    if (n1) vload<NMB>(f1, wp, kp, (long long)(c + VW) * 64);
-    vmul<NMB>(f0, (long long)c * 64, kq, row, acc);
-    if (n2) vload<NMB>(f0, wp, kp, (long long)(c + 2 * VW) * 64);
-    if (n1) vmul<NMB>(f1, (long long)(c + VW) * 64, kq, row, acc);
-  }
-#pragma unroll
-  for (int mb = 0; mb < NMB; ++mb)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) red[w][mb][kq + 4 * r][i] = acc[mb][r];
-  __syncthreads();
+  const int tid = threadIdx.x;
+  small_v_rows<NMB>(W, ldw, Np, Ks, M, red);
   for (int e = tid; e < NMB * 256; e += 64 * VW) {
     const int mb = e >> 8, r = (e >> 4) & 15, c = e & 15;
-    double v = 0.0;
-#pragma unroll
-    for (int u = 0; u < VW; ++u) v += red[u][mb][r][c];
+    const double v = small_v_sum<NMB>(red, mb, r, c);
     vt[16 * mb + c][r] = (16 * mb + c < M) ? v : 0.0;     // (columns >= M repeat query M - 1: dropped)
   }
   __syncthreads();
@@ -629,16 +607,85 @@ __global__ __launch_bounds__(GT) void small_wtv_grad_kernel(SmallK k, long long 
   }
 }
 
+// The device work area of one call: offsets (in doubles) of the sub-buffers the launches below hand to the kernels, and
+// their total - the one place that lays it out.  Every call has K* and the mean shares; the rest follows what it computes.
+struct SmallWork {
+  size_t Ks;             // B x SQ x Np
+  size_t pmean;          // B x ga x (SQ * SP)
+  size_t pvar;           // B x gb x SQ                             (predict, grad)
+  size_t pjac;           // B x ga x (M * P * D)                    (grad)
+  size_t Vs;             // B x Np x SQ                             (grad)
+  size_t pdv;            // B x (gb x row chunks) x (M * D)         (grad)
+  size_t pcov, gcov;     // gb x CE, (gb / CG rounded up) x CE      (cov)
+  size_t total;
+};
+SmallWork small_work(int call, int64_t Np, int B, int64_t M, int D, int P) {
+  const size_t ga = (size_t)(Np / SJ), gb = (size_t)(Np / SR);
+  SmallWork w{};
+  size_t at = 0;
+  auto take = [&at](size_t doubles) { const size_t off = at; at += doubles; return off; };
+  w.Ks = take((size_t)B * SQ * Np);
+  w.pmean = take((size_t)B * ga * (SQ * SP));
+  if (call == GPK_SMALL_COV) {
+    w.pcov = take(gb * CE);
+    w.gcov = take((gb + CG - 1) / CG * CE);
+  } else {
+    w.pvar = take((size_t)B * gb * SQ);
+  }
+  if (call == GPK_SMALL_GRAD) {
+    w.pjac = take((size_t)B * ga * (size_t)(M * P * D));
+    w.Vs = take((size_t)B * Np * SQ);
+    w.pdv = take((size_t)B * gb * WTV_MAX_ROW_CHUNKS * (size_t)(M * D));
+  }
+  w.total = at;
+  return w;
+}
+
+// Checks the B models' pointers and length-scales and fills the kernels' parameter block.  W: null when the call forms
+// no V = W K*^T; kss: null when it has no variance.  `who` prefixes the messages.
+int small_params(gpk_handle h, const char* who, int B, int D, int P, const double* const* X, const double* const* alpha,
+                 const double* const* W, const double* ls, const double* sf2, const double* kss, const double* y_mean,
+                 const double* y_std, SmallK& k) {
+  const std::string name(who);
+  for (int b = 0; b < B; ++b) {
+    GPK_REQUIRE(h, X[b] && alpha[b] && (!W || W[b]), name + ": null model pointer");
+    GPK_REQUIRE(h, !W || ((uintptr_t)W[b] % 16) == 0, name + ": the inverse factor must be 16-byte aligned");
+    k.X[b] = X[b]; k.alpha[b] = alpha[b]; k.W[b] = W ? W[b] : nullptr;
+    for (int d = 0; d < 16; ++d) k.ls[b][d] = 1.0;
+    for (int d = 0; d < D; ++d) {
+      GPK_REQUIRE(h, ls[b * D + d] > 0.0, "length-scales must be positive");
+      k.ls[b][d] = ls[b * D + d];
+    }
+    k.sf2[b] = sf2[b];
+    k.kss[b] = kss ? kss[b] : 0.0;
+  }
+  for (int o = 0; o < B * P; ++o) { k.ymean[o] = y_mean[o]; k.ystd[o] = y_std[o]; }
+  return GPK_OK;
+}
+
+// the zero-initialised ticket counters of the covariance reduction and of small_wtv_grad_kernel, allocated on first use
+int ensure_cov_counters(gpk_handle h) {
+  if (h->d_cov_count) return GPK_OK;
+  GPK_CHECK_HIP(h, hipMalloc((void**)&h->d_cov_count, GPK_SMALL_COV_COUNTERS * sizeof(unsigned)));
+  GPK_CHECK_HIP(h, hipMemsetAsync(h->d_cov_count, 0, GPK_SMALL_COV_COUNTERS * sizeof(unsigned), h->stream));
+  return GPK_OK;
+}
+static_assert(GPK_SMALL_COV_COUNTERS >= 1 + GPK_SMALL_MAX_NP / SR / CG, "counters of the covariance reduction");
+// the ticket counters of small_wtv_grad_kernel (one per model): the last GPK_SMALL_MAX_MODELS of h->d_cov_count
+constexpr int WTV_COUNTER0 = GPK_SMALL_COV_COUNTERS - GPK_SMALL_MAX_MODELS;
+static_assert(WTV_COUNTER0 >= 1 + GPK_SMALL_MAX_NP / SR / CG, "the covariance reduction's counters come first");
+static_assert(SR == GW, "small_wtv_grad_kernel takes as many columns of W per workgroup as small_var_kernel takes rows");
+
 }  // namespace
 
-size_t gpk_small_work_doubles(int64_t Np, int B) { return (size_t)B * Np * (SQ + SQ * SP / SJ + SQ / SR); }
+size_t gpk_small_work_doubles(int call, int64_t Np, int B, int64_t M, int D, int P) {
+  return small_work(call, Np, B, M, D, P).total;
+}
 
 bool gpk_small_ok(int64_t Np, int D, int P, int64_t M) {
   return M >= 1 && M <= SQ && D >= 1 && D <= SD && P >= 1 && P <= SP && Np <= GPK_SMALL_MAX_NP;
 }
 
-// B models (blockIdx.y) x P outputs each (B > 1 requires P == 1).  X / alpha / W: B device pointers; ls: B x D;
-// sf2, kss: B; y_mean, y_std: B * P.  mean_out: (B, M, P), var_out: (B, M) or null.
 int gpk_small_predict(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D, int P,
                       const double* ls, const double* sf2, const double* y_mean, const double* y_std,
                       const double* const* W, int64_t Np, int64_t ldw, const double* kss, double floor_,
@@ -647,23 +694,11 @@ int gpk_small_predict(gpk_handle h, int B, const double* const* X, const double*
   GPK_REQUIRE(h, gpk_small_ok(Np, D, P, M) && Np == gpk_padded(N), "small predict: shape outside the small-batch path");
   GPK_REQUIRE(h, !var_out || (W && ldw >= Np && ldw % 2 == 0), "small predict: variance needs the inverse factor");
   SmallK k{};
-  for (int b = 0; b < B; ++b) {
-    GPK_REQUIRE(h, X[b] && alpha[b] && (!var_out || W[b]), "small predict: null model pointer");
-    GPK_REQUIRE(h, !var_out || ((uintptr_t)W[b] % 16) == 0, "small predict: the inverse factor must be 16-byte aligned");
-    k.X[b] = X[b]; k.alpha[b] = alpha[b]; k.W[b] = var_out ? W[b] : nullptr;
-    for (int d = 0; d < 16; ++d) k.ls[b][d] = 1.0;
-    for (int d = 0; d < D; ++d) {
-      GPK_REQUIRE(h, ls[b * D + d] > 0.0, "length-scales must be positive");
-      k.ls[b][d] = ls[b * D + d];
-    }
-    k.sf2[b] = sf2[b];
-    k.kss[b] = var_out ? kss[b] : 0.0;
-  }
-  for (int o = 0; o < B * P; ++o) { k.ymean[o] = y_mean[o]; k.ystd[o] = y_std[o]; }
+  GPK_TRY(small_params(h, "small predict", B, D, P, X, alpha, var_out ? W : nullptr, ls, sf2, var_out ? kss : nullptr, y_mean,
+                       y_std, k));
   const unsigned ga = (unsigned)(Np / SJ), gb = (unsigned)(Np / SR);
-  double* Ks = work;                                       // B x SQ x Np
-  double* pmean = Ks + (size_t)B * SQ * Np;                // B x ga x (SQ * SP)
-  double* pvar = pmean + (size_t)B * ga * (SQ * SP);       // B x gb x SQ
+  const SmallWork wk = small_work(GPK_SMALL_PREDICT, Np, B, M, D, P);
+  double *Ks = work + wk.Ks, *pmean = work + wk.pmean, *pvar = work + wk.pvar;
   if (var_out) {
     hipLaunchKernelGGL(small_cross_mean_kernel<false>, dim3(ga, B), dim3(256), 0, h->stream, k, (long long)N, (long long)Np,
                        D, P, Xq, (int)M, Ks, pmean, h->d_count, mean_out);
@@ -682,43 +717,17 @@ int gpk_small_predict(gpk_handle h, int B, const double* const* X, const double*
   return GPK_OK;
 }
 
-// the zero-initialised ticket counters of the covariance reduction and of small_wtv_grad_kernel, allocated on first use
-static int ensure_cov_counters(gpk_handle h) {
-  if (h->d_cov_count) return GPK_OK;
-  GPK_CHECK_HIP(h, hipMalloc((void**)&h->d_cov_count, GPK_SMALL_COV_COUNTERS * sizeof(unsigned)));
-  GPK_CHECK_HIP(h, hipMemsetAsync(h->d_cov_count, 0, GPK_SMALL_COV_COUNTERS * sizeof(unsigned), h->stream));
-  return GPK_OK;
-}
-
-size_t gpk_small_cov_work_doubles(int64_t Np) {
-  const size_t shares = (size_t)(Np / SR), groups = (shares + CG - 1) / CG;
-  return (size_t)Np * (SQ + SQ * SP / SJ) + (shares + groups) * CE;
-}
-
-// Posterior mean (M x P, un-normalised) and covariance (M x M, normalised-target units) of M <= 32 queries of one model:
-// small_cross_mean_kernel + small_cov_kernel, no synchronisation.  Xq, mean_out, cov_out may be pinned, mapped host memory.
 int gpk_small_cov(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls, double sf2,
                   const double* y_mean, const double* y_std, const double* W, int64_t Np, int64_t ldw, double noise,
                   const double* Xq, int64_t M, double* work, double* mean_out, double* cov_out) {
   GPK_REQUIRE(h, gpk_small_ok(Np, D, P, M) && Np == gpk_padded(N), "small cov: shape outside the small-batch path");
-  GPK_REQUIRE(h, X && alpha && W && ldw >= Np && ldw % 2 == 0 && ((uintptr_t)W % 16) == 0,
-              "small cov: needs the (16-byte aligned) inverse factor");
+  GPK_REQUIRE(h, W && ldw >= Np && ldw % 2 == 0, "small cov: needs the inverse factor");
   GPK_TRY(ensure_cov_counters(h));
   SmallK k{};
-  k.X[0] = X; k.alpha[0] = alpha; k.W[0] = W;
-  for (int d = 0; d < 16; ++d) k.ls[0][d] = 1.0;
-  for (int d = 0; d < D; ++d) {
-    GPK_REQUIRE(h, ls[d] > 0.0, "length-scales must be positive");
-    k.ls[0][d] = ls[d];
-  }
-  k.sf2[0] = sf2;
-  for (int o = 0; o < P; ++o) { k.ymean[o] = y_mean[o]; k.ystd[o] = y_std[o]; }
+  GPK_TRY(small_params(h, "small cov", 1, D, P, &X, &alpha, &W, ls, &sf2, nullptr, y_mean, y_std, k));
   const unsigned ga = (unsigned)(Np / SJ), gb = (unsigned)(Np / SR);
-  static_assert(GPK_SMALL_COV_COUNTERS >= 1 + GPK_SMALL_MAX_NP / SR / CG, "counters of the covariance reduction");
-  double* Ks = work;                                       // SQ x Np
-  double* pmean = Ks + (size_t)SQ * Np;                    // ga x (SQ * SP)
-  double* pcov = pmean + (size_t)ga * (SQ * SP);           // gb x CE
-  double* gcov = pcov + (size_t)gb * CE;                   // (gb / CG rounded up) x CE
+  const SmallWork wk = small_work(GPK_SMALL_COV, Np, 1, M, D, P);
+  double *Ks = work + wk.Ks, *pmean = work + wk.pmean, *pcov = work + wk.pcov, *gcov = work + wk.gcov;
   hipLaunchKernelGGL(small_cross_mean_kernel<false>, dim3(ga, 1), dim3(256), 0, h->stream, k, (long long)N, (long long)Np, D, P,
                      Xq, (int)M, Ks, pmean, h->d_count, mean_out);
   GPK_LAUNCH_CHECK(h);
@@ -732,20 +741,6 @@ int gpk_small_cov(gpk_handle h, const double* X, const double* alpha, int64_t N,
   return GPK_OK;
 }
 
-size_t gpk_small_grad_work_doubles(int64_t Np, int M, int D, int P, int B) {
-  const size_t ga = (size_t)(Np / SJ), gb = (size_t)(Np / SR);
-  return gpk_small_work_doubles(Np, B) +
-         (size_t)B * (ga * (size_t)(M * P * D) + (size_t)Np * SQ + gb * WTV_MAX_ROW_CHUNKS * (size_t)(M * D));
-}
-
-// the ticket counters of small_wtv_grad_kernel (one per model): the last GPK_SMALL_MAX_MODELS of h->d_cov_count
-constexpr int WTV_COUNTER0 = GPK_SMALL_COV_COUNTERS - GPK_SMALL_MAX_MODELS;
-static_assert(WTV_COUNTER0 >= 1 + GPK_SMALL_MAX_NP / SR / CG, "the covariance reduction's counters come first");
-
-// Posterior mean (B, M, P) and its Jacobian (B, M, P, D; un-normalised) of M <= 32 queries of B models (B > 1: P == 1, the
-// per-axis batch) in ONE launch small_cross_mean_jac_kernel<true>; with var_out / dvar_out also the variance (B, M) and its
-// gradient (B, M, D), normalised-target units, in three launches (+ small_var_grad_kernel, small_wtv_grad_kernel).  No
-// synchronisation; Xq and the outputs may be pinned, mapped host memory.  Arguments as gpk_small_predict.
 int gpk_small_grad_multi(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D, int P,
                          const double* ls, const double* sf2, const double* y_mean, const double* y_std, const double* const* W,
                          int64_t Np, int64_t ldw, const double* kss, double floor_, const double* Xq, int64_t M, double* work,
@@ -753,32 +748,15 @@ int gpk_small_grad_multi(gpk_handle h, int B, const double* const* X, const doub
   GPK_REQUIRE(h, B >= 1 && B <= GPK_SMALL_MAX_MODELS && (B == 1 || P == 1), "small grad: 1 model, or up to 8 single-output models");
   GPK_REQUIRE(h, gpk_small_ok(Np, D, P, M) && Np == gpk_padded(N), "small grad: shape outside the small-batch path");
   GPK_REQUIRE(h, X && alpha && mean_out && dmean_out && (var_out == nullptr) == (dvar_out == nullptr), "small grad: null pointer");
-  GPK_REQUIRE(h, !var_out || (W && kss && ldw >= Np && ldw % 2 == 0),
-              "small grad: the variance gradient needs the (16-byte aligned) inverse factor");
+  GPK_REQUIRE(h, !var_out || (W && kss && ldw >= Np && ldw % 2 == 0), "small grad: the variance gradient needs the inverse factor");
   if (var_out) GPK_TRY(ensure_cov_counters(h));
   SmallK k{};
-  for (int b = 0; b < B; ++b) {
-    GPK_REQUIRE(h, X[b] && alpha[b], "small grad: null pointer");
-    GPK_REQUIRE(h, !var_out || (W[b] && ((uintptr_t)W[b] % 16) == 0),
-                "small grad: the variance gradient needs the (16-byte aligned) inverse factor");
-    k.X[b] = X[b]; k.alpha[b] = alpha[b]; k.W[b] = var_out ? W[b] : nullptr;
-    for (int d = 0; d < 16; ++d) k.ls[b][d] = 1.0;
-    for (int d = 0; d < D; ++d) {
-      GPK_REQUIRE(h, ls[b * D + d] > 0.0, "length-scales must be positive");
-      k.ls[b][d] = ls[b * D + d];
-    }
-    k.sf2[b] = sf2[b];
-    k.kss[b] = var_out ? kss[b] : 0.0;
-  }
-  for (int o = 0; o < B * P; ++o) { k.ymean[o] = y_mean[o]; k.ystd[o] = y_std[o]; }
+  GPK_TRY(small_params(h, "small grad", B, D, P, X, alpha, var_out ? W : nullptr, ls, sf2, var_out ? kss : nullptr, y_mean, y_std,
+                       k));
   const unsigned ga = (unsigned)(Np / SJ), gb = (unsigned)(Np / SR);
-  static_assert(SR == GW, "small_wtv_grad_kernel takes as many columns of W per workgroup as small_var_kernel takes rows");
-  double* Ks = work;                                       // B x SQ x Np
-  double* pmean = Ks + (size_t)B * SQ * Np;                // B x ga x (SQ * SP)
-  double* pvar = pmean + (size_t)B * ga * (SQ * SP);       // B x gb x SQ
-  double* pjac = pvar + (size_t)B * gb * SQ;               // B x ga x (M * P * D)
-  double* Vs = pjac + (size_t)B * ga * (M * P * D);        // B x Np x SQ
-  double* pdv = Vs + (size_t)B * Np * SQ;                  // B x (gb x row chunks) x (M * D)
+  const SmallWork wk = small_work(GPK_SMALL_GRAD, Np, B, M, D, P);
+  double *Ks = work + wk.Ks, *pmean = work + wk.pmean, *pvar = work + wk.pvar, *pjac = work + wk.pjac, *Vs = work + wk.Vs,
+         *pdv = work + wk.pdv;
   if (!var_out) {
     hipLaunchKernelGGL((small_cross_mean_jac_kernel<true>), dim3(ga, B), dim3(256), 0, h->stream, k, (long long)N,
                        (long long)Np, D, P, Xq, (int)M, (double*)nullptr, pmean, h->d_count, mean_out, pjac, dmean_out);
@@ -805,13 +783,4 @@ int gpk_small_grad_multi(gpk_handle h, int B, const double* const* X, const doub
                      (const double*)Ks, (const double*)Vs, Xq, (int)M, pdv, h->d_cov_count + WTV_COUNTER0, dvar_out);
   GPK_LAUNCH_CHECK(h);
   return GPK_OK;
-}
-
-// one model with P <= 16 outputs: the same launches on a (., 1) grid
-int gpk_small_grad(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls, double sf2,
-                   const double* y_mean, const double* y_std, const double* W, int64_t Np, int64_t ldw, double kss, double floor_,
-                   const double* Xq, int64_t M, double* work, double* mean_out, double* var_out, double* dmean_out,
-                   double* dvar_out) {
-  return gpk_small_grad_multi(h, 1, &X, &alpha, N, D, P, ls, &sf2, y_mean, y_std, &W, Np, ldw, &kss, floor_, Xq, M, work, mean_out,
-                              var_out, dmean_out, dvar_out);
 }
