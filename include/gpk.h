@@ -367,6 +367,28 @@ GPK_API int gpk_predict_host_cov(gpk_handle h, const double* X, const double* al
                                  const double* ls, double sf2, const double* y_mean, const double* y_std, const double* W,
                                  int64_t Np, int64_t ldw, double noise, const double* Xq_host, int64_t M, double* mean_host,
                                  double* cov_host);
+/* K7 for B (<= 8) single-output ARD models on one query batch - the per-axis layout of src/px4/gp_trainer.py:139-179: the joint
+ * posterior of every model over the same rows (a consistent residual trajectory per axis along the horizon).
+ * gpk_predict_host_multi_cov: the one-call serving form, arguments and limits as gpk_predict_host_multi_grad (X / alpha / W:
+ *   host arrays of B device pointers; ls host B x D; sf2, y_mean, y_std host double[B]), 1 <= M <= 32, D <= 16, N <= 16384.
+ *   noise host double[B]: model b's WhiteKernel level, added only where row = column.  mean_host (B x M) un-normalised;
+ *   cov_host (B x M x M) in normalised-target units, not clipped.  The two launches of gpk_predict_host_cov with the model as a
+ *   grid dimension: all B covariances in TWO launches and one synchronisation, queries and results through the pinned, mapped
+ *   block; every model has its own shares, group sums and ticket counters and the order of every sum depends on Np and M
+ *   only: model b's block has the bits of gpk_predict_host_cov on that model alone, symmetric bit for bit, the same from run
+ *   to run.  With option small_path = 0: the general building blocks (fused mean, gpk_predict_cov_inv), model by model, one
+ *   strided download each (a cross-check).
+ *   Replaces: six times sklearn/gaussian_process/_gpr.py:441-469 (predict(X, return_cov=True)) around the per-axis loop of
+ *   src/px4/pretrained_gp.py:52-98; within this library, B gpk_predict_host_cov calls with 2 B launches and B synchronisations.
+ * gpk_predict_batched_cov: the composite on the object of gpk_fit_batched, host fp64 buffers: Xq (M x D), mean (M x B), cov
+ *   (B x M x M) in target units (already multiplied by y_std[b]^2), model b's own noise level on its diagonal.  Up to 32
+ *   queries (N <= 16384): one gpk_predict_host_multi_cov; larger batches (M <= 16384): gpk_predict_mean_multi and one
+ *   gpk_predict_cov_inv per model, one synchronisation.  Checks that the queries are finite.                              */
+GPK_API int gpk_predict_host_multi_cov(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N,
+                                       int D, const double* ls, const double* sf2, const double* y_mean, const double* y_std,
+                                       const double* const* W, int64_t Np, int64_t ldw, const double* noise,
+                                       const double* Xq_host, int64_t M, double* mean_host, double* cov_host);
+GPK_API int gpk_predict_batched_cov(gpk_handle h, const double* Xq, int64_t M, double* mean, double* cov);
 
 /* ---- K8: input gradients of the posterior (fp64) ------------------------------------------------------------------
  * With u_jd = (x_jd - xq_md) / ls_d^2 (exact differences):

@@ -7,6 +7,11 @@
    bracket GPK_TIMED_COV) and its rate on its N M^2 flops.
 2. The MPC horizon: 25 rows at N = 1000, predict(return_cov=True) (mean + cov, one C call) against today's
    predict(return_std=True) (mean + var, one C call), wall time per call.
+--axis: the per-axis batch instead (six single-output ARD models on shared inputs, BatchedARDGP), the 25-row horizon at
+   N = 1000 and N = 4096, three routes alternated call by call in the same run, a host clock around calls that end in their
+   own synchronisation: (a) the one call, gpk_predict_host_multi_cov (TWO launches, one synchronisation); (b) six
+   gpk_predict_host_cov calls on the same handle (twelve launches, six synchronisations) - the route to the same numbers
+   before the kernel had a model dimension; (c) gpk_predict_host_multi with variances, the floor.
 Medians over the repetitions; CUDA events around the device calls, perf_counter around the estimator calls."""
 import argparse
 import os
@@ -87,12 +92,62 @@ def horizon(N, M, reps):
           f"(p99 {b[1]:7.1f})   ratio {b[0] / a[0]:5.3f}", flush=True)
 
 
+def axis_horizon(N, M, reps, B=6, D=10, only="abc"):
+    from unmanned_aerial_vehicles_amd import RBF, ConstantKernel, GaussianProcessRegressor, WhiteKernel
+    from unmanned_aerial_vehicles_amd.batched import BatchedARDGP
+    rng = np.random.default_rng(N)
+    X = rng.standard_normal((N, D))
+    Y = np.sin(X @ rng.standard_normal((D, B))) + 0.1 * rng.standard_normal((N, B))
+    bg = BatchedARDGP(optimizer=None, device=0)
+    for b in range(B):
+        k = ConstantKernel(1.0, constant_value_bounds="fixed") * RBF(np.roll(np.linspace(1.2, 3.0, D), b)) + WhiteKernel(0.02 * (b + 1))
+        bg.models.append(GaussianProcessRegressor(kernel=k, alpha=1e-6, normalize_y=False, optimizer=None, device=0).fit(X, Y[:, b]))
+    Xq = np.ascontiguousarray(rng.standard_normal((M, D)))
+    assert bg.predict_host_cov(Xq) is not None and bg.predict_host(Xq, True) is not None
+    singles = [(m._dev, m._y_train_mean, m._y_train_std, m.kernel_.components().noise) for m in bg.models]
+    routes = {
+        "a": lambda: bg.predict_host_cov(Xq),
+        "b": lambda: [d.predict_cov_host(Xq, ym, ys, nz) for d, ym, ys, nz in singles],
+        "c": lambda: bg.predict_host(Xq, True),
+    }
+    # the two routes to the covariance return the same bits
+    one, six = routes["a"](), routes["b"]()
+    routes = {k: fn for k, fn in routes.items() if k in only}        # (--routes: a kernel trace of one route alone)
+    same = all(np.array_equal(one[1][..., b], six[b][1]) and np.array_equal(one[0][:, b], six[b][0][:, 0]) for b in range(B))
+    for _ in range(20):
+        for fn in routes.values():
+            fn()
+    ts = {k: [] for k in routes}
+    for _ in range(reps):
+        for k, fn in routes.items():
+            t0 = time.perf_counter()
+            fn()
+            ts[k].append(time.perf_counter() - t0)
+    med = {k: 1e6 * float(np.median(v)) for k, v in ts.items()}
+    p99 = {k: 1e6 * float(np.percentile(v, 99)) for k, v in ts.items()}
+    if len(routes) < 3:
+        print(f"per-axis B = {B}, N = {N} rows = {M}: " + "   ".join(f"({k}) {med[k]:7.1f} us (p99 {p99[k]:7.1f})" for k in routes)
+              + f"   bits of (a) == bits of (b): {same}", flush=True)
+        return
+    print(f"per-axis B = {B}, N = {N} rows = {M}: (a) one-call mean+cov {med['a']:7.1f} us (p99 {p99['a']:7.1f})   (b) six "
+          f"gpk_predict_host_cov calls {med['b']:7.1f} us (p99 {p99['b']:7.1f}): {med['b'] / med['a']:5.2f} x the one call   (c) "
+          f"host_multi mean+std {med['c']:7.1f} us (p99 {p99['c']:7.1f}): (a) / (c) {med['a'] / med['c']:5.3f}   "
+          f"bits of (a) == bits of (b): {same}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true", help="N = 16 384 only, fewer repetitions")
+    ap.add_argument("--axis", action="store_true", help="the per-axis batch (six single-output models) on the 25-row horizon")
+    ap.add_argument("--n", type=int, nargs="*", default=[1000, 4096], help="--axis: training-set sizes")
+    ap.add_argument("--routes", default="abc", help="--axis: the routes to time, e.g. a (for a kernel trace of the one call alone)")
     a = ap.parse_args()
     import torch
     print(f"# tools/exp_cov.py on {torch.cuda.get_device_name(0)}; fp64; D = 10", flush=True)
+    if a.axis:
+        for N in a.n:
+            axis_horizon(N, 25, 200 if a.quick else 1000, only=a.routes)
+        return
     horizon(1000, 25, 200 if a.quick else 1000)
     for N in ((16384,) if a.quick else (16384, 65536)):
         large(N, 4096, 3 if a.quick else 5)

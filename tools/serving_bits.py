@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""SHA-256 of everything the five one-call serving entries return (gpk_predict_host, _host_multi, _host_cov, _host_grad,
-_host_multi_grad) on seeded inputs: one line per entry, model, row count, request and small_path setting.  Two builds of the
+"""SHA-256 of everything the six one-call serving entries return (gpk_predict_host, _host_multi, _host_cov, _host_grad,
+_host_multi_grad, _host_multi_cov) on seeded inputs: one line per entry, model, row count, request and small_path setting.  Two builds of the
 library compute the same bits exactly when the two outputs are equal:
     python tools/serving_bits.py > new.txt;  GPK_LIBRARY=/path/to/other/libgpk.so python tools/serving_bits.py > old.txt
     python tools/serving_bits.py --compare old.txt new.txt
@@ -50,7 +50,8 @@ def multi_args(gps):
             "sf2": np.ascontiguousarray([d.sf2 for d in devs], dtype=np.float64),
             "ym": np.ascontiguousarray([g._y_train_mean[0] for g, _, _ in gps], dtype=np.float64),
             "ys": np.ascontiguousarray([g._y_train_std[0] for g, _, _ in gps], dtype=np.float64),
-            "kss": np.ascontiguousarray([k for _, k, _ in gps], dtype=np.float64)}
+            "kss": np.ascontiguousarray([k for _, k, _ in gps], dtype=np.float64),
+            "noise": np.ascontiguousarray([n for _, _, n in gps], dtype=np.float64)}
 
 
 def multi(a, Xq, want_var, grad):
@@ -69,6 +70,19 @@ def multi(a, Xq, want_var, grad):
         dmean, dvar = np.empty((B, M, D)), np.empty((B, M, D)) if want_var else None
         be.check(be.lib.gpk_predict_host_multi_grad(*head, p(dmean), p(dvar)))
         return mean, var, dmean, dvar
+
+
+def multi_cov(a, Xq):
+    B, d0 = a["B"], a["d0"]
+    M, D = Xq.shape
+    be = d0.be
+    mean, cov = np.empty((B, M)), np.empty((B, M, M))
+    with be.lock:
+        be.bind_stream()
+        be.check(be.lib.gpk_predict_host_multi_cov(be.h, B, a["X"], a["alpha"], d0.N, D, a["ls"].ctypes.data, a["sf2"].ctypes.data,
+                                                   a["ym"].ctypes.data, a["ys"].ctypes.data, a["W"], d0.Np, d0.Np,
+                                                   a["noise"].ctypes.data, Xq.ctypes.data, M, mean.ctypes.data, cov.ctypes.data))
+    return mean, cov
 
 
 def run():
@@ -98,16 +112,20 @@ def run():
                     for v in (False, True):
                         print(f"predict_host_multi {tag} B={B} M={M} var={v}", digest(*multi(a, Q[:M], v, False)))
                         print(f"predict_host_multi_grad {tag} B={B} M={M} var={v}", digest(*multi(a, Q[:M], v, True)))
+                    print(f"predict_host_multi_cov {tag} B={B} M={M}", digest(*multi_cov(a, Q[:M])))
         dev.be.set_options(small_path=1)
 
 
 def compare(old, new):
     a, b = (dict(line.rsplit(" ", 1) for line in open(f).read().splitlines() if line) for f in (old, new))
-    bad = sorted(k for k in set(a) | set(b) if a.get(k) != b.get(k))
+    bad = sorted(k for k in a if a[k] != b.get(k))
     for k in sorted(a):
         print(("DIFFERENT " if k in bad else "equal     ") + k, a[k][:16], b.get(k, "missing")[:16])
-    print(f"{len(a)} digests, {len(bad)} different")
-    return 1 if bad or len(a) != len(b) else 0
+    only_new = sorted(k for k in b if k not in a)
+    for k in only_new:
+        print("new only  " + k, b[k][:16])
+    print(f"{len(a)} digests of the old build, {len(bad)} different; {len(only_new)} lines only the new build prints")
+    return 1 if bad else 0
 
 
 if __name__ == "__main__":

@@ -91,6 +91,10 @@ SIGNATURES = {
     "gpk_predict_host_cov": (_int, [_vp, _vp, _vp, _i64, _int, _int, _vp, _dbl, _vp, _vp, _vp, _i64, _i64, _dbl, _vp, _i64,
                                     _vp, _vp]),
     "gpk_predict_model_cov": (_int, [_vp, _dp, _i64, _dp, _dp]),
+    # (host pointers as void*, as gpk_predict_host_multi)
+    "gpk_predict_host_multi_cov": (_int, [_vp, _int, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64,
+                                          _vp, _vp]),
+    "gpk_predict_batched_cov": (_int, [_vp, _dp, _i64, _dp, _dp]),
     "gpk_predict_mean_grad": (_int, [_vp, _vp, _vp, _i64, _int, _int, _dp, _dbl, _dp, _vp, _i64, _vp]),
     "gpk_predict_var_grad_inv": (_int, [_vp, _vp, _i64, _int, _dp, _dbl, _vp, _i64, _i64, _vp, _i64, _dbl, _dbl, _vp, _vp, _vp]),
     # (host pointers as void*, as gpk_predict_host)

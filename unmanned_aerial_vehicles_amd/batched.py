@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _lib
 from .device import Backend, get_backend
-from .gpr import GaussianProcessRegressor
+from .gpr import GaussianProcessRegressor, cholesky_draws
 from .kernels import RBF, ConstantKernel, WhiteKernel
 
 
@@ -480,7 +480,89 @@ class BatchedARDGP:
             var[:, b], dvar[:, b, :] = v.cpu().numpy() * s2, g.cpu().numpy() * s2
         return mean, dmean, var, dvar
 
-    def predict(self, Xq, return_std=False):
+    # ------------------------------------------------------------------ joint posterior (K7, per-axis batch)
+    def predict_host_cov(self, Xq):
+        """<= 32 rows, all models, one C call (`gpk_predict_host_multi_cov`: two launches and one synchronisation for all of
+        them): (mean (M, B), cov (M, M, B)), cov in target units (times y_std^2), each model's WhiteKernel level on its own
+        diagonal, not clipped, symmetric bit for bit.  None if the models do not qualify (the conditions of `_serve_state`).
+        Always the fp64 kernels: an fp32-serving batch is served too."""
+        sv = self._serve_state(True, any_dtype=True)
+        if sv is None:
+            return None
+        Xq = np.ascontiguousarray(Xq, dtype=np.float64)
+        d0 = sv["dev0"]
+        if Xq.ndim != 2 or Xq.shape[1] != d0.D:
+            raise ValueError(f"queries must be (M, {d0.D})")
+        M, B = Xq.shape[0], sv["B"]
+        if not (1 <= M <= self.SERVE_MAX_M):
+            return None
+        if sv.get("noise") is None:
+            sv["noise"] = np.ascontiguousarray([m.kernel_.components().noise or 0.0 for m in self.models], dtype=np.float64)
+        mean, cov = np.empty((B, M)), np.empty((B, M, M))
+        be = d0.be
+        with be.lock:
+            be.bind_stream()
+            be.check(be.lib.gpk_predict_host_multi_cov(
+                be.h, B, sv["X"], sv["alpha"], d0.N, d0.D, sv["ls"].ctypes.data, sv["sf2"].ctypes.data,
+                sv["ym"].ctypes.data, sv["ys"].ctypes.data, sv["W"], d0.Np, d0.Np, sv["noise"].ctypes.data,
+                Xq.ctypes.data, M, mean.ctypes.data, cov.ctypes.data))
+        return mean.T, (cov * (sv["ys"] ** 2)[:, None, None]).transpose(1, 2, 0)
+
+    def _predict_cov(self, Xq):
+        """return_cov=True: up to 32 rows the one call; larger batches the fused mean launch plus each model's
+        `predict_cov_dev`; models that do not qualify for either (different N, different devices, more than 8, different
+        inputs): each model's own `predict(return_cov=True)`."""
+        M, B = Xq.shape[0], len(self.models)
+        if 1 <= M <= self.SERVE_MAX_M:
+            out = self.predict_host_cov(Xq)
+            if out is not None:
+                return out
+        for m in self.models:
+            m._ensure_device()
+        devs = [m._dev for m in self.models]
+        fused = (1 <= B <= 8 and M >= 1 and all(d.factored and d.P == 1 and d.N == devs[0].N and d.D == devs[0].D
+                                                 and d.be.device == devs[0].be.device for d in devs)
+                 and self._shared_inputs())
+        if not fused:
+            outs = [m.predict(Xq, return_cov=True) for m in self.models]
+            return np.stack([o[0] for o in outs], axis=1), np.stack([o[1] for o in outs], axis=2)
+        import torch
+        f = self._fused64()
+        be = get_backend(self.device)
+        q = be.upload(np.ascontiguousarray(Xq, dtype=np.float64), torch.float64)
+        mean_d = be.empty((M, B), torch.float64)
+        dp = _lib._dp
+        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        with be.lock:
+            be.bind_stream()
+            be.check(be.lib.gpk_predict_mean_multi(
+                be.h, _lib.GPK_F64, p(f["X"]), p(f["alpha"]), f["N"], f["D"], B, f["ls"].ctypes.data_as(dp),
+                f["sf2"].ctypes.data_as(dp), f["ym"].ctypes.data_as(dp), f["ys"].ctypes.data_as(dp), p(q), M, p(mean_d)))
+        mean = mean_d.cpu().numpy()
+        cov = np.empty((M, M, B))
+        for b, m in enumerate(self.models):      # K*, W and the length-scales differ per model: nothing to share
+            c = m._dev.predict_cov_dev(Xq, m.kernel_.components().noise or 0.0)
+            cov[..., b] = c.contiguous().cpu().numpy() * float(m._y_train_std[0]) ** 2
+        return mean, cov
+
+    def sample_y(self, Xq, n_samples=1, random_state=0):
+        """Draws from every model's joint posterior at the rows Xq: (M, B, n_samples).  Mean and covariance from
+        `predict(Xq, return_cov=True)` (GPU); the draw on the host through the Cholesky factor of each covariance
+        (`gpr.cholesky_draws`: one standard-normal block for all models, a stable function of the covariance)."""
+        mean, cov = self.predict(Xq, return_cov=True)
+        return cholesky_draws(mean, cov, n_samples, random_state)
+
+    def predict(self, Xq, return_std=False, return_cov=False):
+        """Means (M, B); with return_std the standard deviations (M, B); with return_cov=True every model's joint posterior
+        covariance over the rows, (mean (M, B), cov (M, M, B)) in target units as scikit-learn scales it
+        (`sklearn/gaussian_process/_gpr.py:441-469`, model by model).  The covariance always comes from the fp64 kernels."""
+        if return_std and return_cov:
+            raise RuntimeError("At most one of return_std or return_cov can be requested.")
+        if return_cov:
+            Xq = np.array(Xq, dtype=np.float64, ndmin=2)
+            if not np.isfinite(Xq).all():
+                raise ValueError("Input X contains NaN or infinity.")
+            return self._predict_cov(Xq)
         Xq = np.atleast_2d(np.asarray(Xq, dtype=np.float64))
         if 1 <= Xq.shape[0] <= self.SERVE_MAX_M:
             out = self.predict_host(Xq, return_std)

@@ -228,8 +228,10 @@ int gpk_gemm_tile(gpk_handle h, const GemmArgs& g);   // 128 or 64: the tile edg
 constexpr int GPK_SMALL_MAX_M = 32;          // queries per call
 constexpr int64_t GPK_SMALL_MAX_NP = 16384;  // padded training rows
 constexpr int GPK_SMALL_MAX_MODELS = 8;      // single-output models served by one call
-constexpr int GPK_SMALL_COV_COUNTERS = 128;  // h->d_cov_count: ticket counters of the covariance's two-level reduction; the last
-                                             // GPK_SMALL_MAX_MODELS are small_wtv_grad_kernel's, one per model
+constexpr int GPK_SMALL_COV_COUNTERS = GPK_SMALL_MAX_MODELS * 65 + GPK_SMALL_MAX_MODELS;
+                                             // h->d_cov_count: ticket counters of the covariance's two-level reduction, per model
+                                             // 1 + GPK_SMALL_MAX_NP / 16 / 16 = 65; the last GPK_SMALL_MAX_MODELS are
+                                             // small_wtv_grad_kernel's, one per model
 bool gpk_small_ok(int64_t Np, int D, int P, int64_t M);
 // doubles of device work area (`work`) that a call of the given kind needs: per model K* (32 x Np) + the workgroups' shares
 enum { GPK_SMALL_PREDICT, GPK_SMALL_COV, GPK_SMALL_GRAD };
@@ -239,10 +241,12 @@ int gpk_small_predict(gpk_handle h, int B, const double* const* X, const double*
                       const double* ls, const double* sf2, const double* y_mean, const double* y_std,
                       const double* const* W, int64_t Np, int64_t ldw, const double* kss, double floor_,
                       const double* Xq, int64_t M, double* work, double* mean_out, double* var_out);
-// mean (M, P) and covariance (M, M) of one model: two launches (small_cross_mean_kernel + small_cov_kernel)
-int gpk_small_cov(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls, double sf2,
-                  const double* y_mean, const double* y_std, const double* W, int64_t Np, int64_t ldw, double noise,
-                  const double* Xq, int64_t M, double* work, double* mean_out, double* cov_out);
+// mean (B, M, P) and covariance (B, M, M; noise[b] on model b's diagonal): two launches for all models
+// (small_cross_mean_kernel + small_cov_kernel)
+int gpk_small_cov_multi(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D, int P,
+                        const double* ls, const double* sf2, const double* y_mean, const double* y_std, const double* const* W,
+                        int64_t Np, int64_t ldw, const double* noise, const double* Xq, int64_t M, double* work,
+                        double* mean_out, double* cov_out);
 // mean (B, M, P) and its Jacobian (B, M, P, D; un-normalised) in ONE launch (small_cross_mean_jac_kernel); with var_out /
 // dvar_out also the variance (B, M) and its gradient (B, M, D) in three (+ small_var_grad_kernel, small_wtv_grad_kernel)
 int gpk_small_grad_multi(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D, int P,

@@ -623,7 +623,8 @@ struct gpk_bmodel {
   double *sK = nullptr, *sW = nullptr, *sKinv = nullptr, *sT = nullptr, *swinv = nullptr, *salpha = nullptr;   // gpk_lml_batched
   void *q = nullptr, *mean = nullptr, *work = nullptr;
   double* var = nullptr;
-  size_t q_bytes = 0, mean_bytes = 0, work_bytes = 0, var_bytes = 0;
+  void* cov = nullptr;           // gpk_predict_batched_cov beyond 32 queries: one model's Sigma (Mp x Mp)
+  size_t q_bytes = 0, mean_bytes = 0, work_bytes = 0, var_bytes = 0, cov_bytes = 0;
   size_t nn() const { return (size_t)Np * Np; }
   size_t tsz() const { return (size_t)(Np / 2 + 128) * (Np / 2 + 128); }
 };
@@ -676,7 +677,7 @@ int batched_chain(gpk_handle h, gpk_bmodel* m, double* K, double* winv, double* 
 
 void bfree_all(gpk_bmodel* m) {
   void* ptrs[] = {m->X, m->Yn, m->alpha, m->alphaT, m->K, m->winv, m->W, m->sK, m->sW, m->sKinv, m->sT, m->swinv,
-                  m->salpha, m->q, m->mean, m->work, m->var};
+                  m->salpha, m->q, m->mean, m->work, m->var, m->cov};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
 }
@@ -903,6 +904,55 @@ extern "C" int gpk_predict_batched_grad(gpk_handle h, const double* Xq, int64_t 
       GPK_CHECK_HIP(h, hipMemcpyAsync(dvar + (size_t)m0 * B * D, d_dvarout, (size_t)mc * B * D * 8, hipMemcpyDeviceToHost, h->stream));
     }
     GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  return GPK_OK;
+}
+
+extern "C" int gpk_predict_batched_cov(gpk_handle h, const double* Xq, int64_t M, double* mean, double* cov) {
+  if (!h) return GPK_BAD_ARG;
+  gpk_bmodel* m = h->bmodel;
+  GPK_REQUIRE(h, m && m->fitted, "predict_batched_cov: no model (call gpk_fit_batched first)");
+  GPK_REQUIRE(h, Xq && mean && cov && M >= 1 && M <= 16384, "predict_batched_cov: null pointer or M outside [1, 16384]");
+  GPK_CHECK_HIP(h, hipSetDevice(h->device));
+  const int B = m->B, D = m->D;
+  for (int64_t i = 0; i < M * D; ++i) GPK_REQUIRE(h, std::isfinite(Xq[i]), "predict_batched_cov: Xq contains NaN or infinity");
+  double lsBD[GPK_MAX_BATCH * GPK_MAX_D_PREDICT];
+  for (int b = 0; b < B; ++b)
+    for (int d = 0; d < D; ++d) lsBD[b * D + d] = m->ls[b][d];
+  const size_t nc = (size_t)M * M;
+  if (M <= 32 && m->Np <= GPK_SMALL_MAX_NP) {
+    // the horizon: one call, two launches for all models
+    const double *Xs[GPK_MAX_BATCH], *as[GPK_MAX_BATCH], *Ws[GPK_MAX_BATCH];
+    for (int b = 0; b < B; ++b) { Xs[b] = m->X; as[b] = m->alpha + (size_t)b * m->Ne; Ws[b] = m->W + (size_t)b * m->nn(); }
+    std::vector<double> mb((size_t)B * M);
+    GPK_TRY(gpk_predict_host_multi_cov(h, B, Xs, as, m->N, D, lsBD, m->sf2, m->y_mean, m->y_std, Ws, m->Np, m->Np, m->noise, Xq, M,
+                                       mb.data(), cov));
+    for (int64_t i = 0; i < M; ++i)
+      for (int b = 0; b < B; ++b) mean[i * B + b] = mb[(size_t)b * M + i];
+  } else {
+    // larger batches: the fused mean launch, then per model V = W K*^T and Sigma (K*, W and the length-scales differ per
+    // model); the work buffers are reused, the stream orders the models; one synchronisation
+    const int64_t Mp = gpk_padded(M);
+    GPK_TRY(grow(h, &m->q, &m->q_bytes, (size_t)M * D * 8));
+    GPK_TRY(grow(h, &m->mean, &m->mean_bytes, (size_t)M * B * 8));
+    GPK_TRY(grow(h, &m->work, &m->work_bytes, (size_t)m->Np * Mp * 8));
+    GPK_TRY(grow(h, &m->cov, &m->cov_bytes, (size_t)Mp * Mp * 8));
+    GPK_CHECK_HIP(h, hipMemcpyAsync(m->q, Xq, (size_t)M * D * 8, hipMemcpyHostToDevice, h->stream));
+    GPK_TRY(gpk_predict_mean_multi(h, GPK_F64, m->X, m->alphaT, m->N, D, B, lsBD, m->sf2, m->y_mean, m->y_std, m->q, M, m->mean));
+    GPK_CHECK_HIP(h, hipMemcpyAsync(mean, m->mean, (size_t)M * B * 8, hipMemcpyDeviceToHost, h->stream));
+    for (int b = 0; b < B; ++b) {
+      GPK_TRY(gpk_predict_cov_inv(h, GPK_F64, m->X, m->N, D, m->ls[b], m->sf2[b], m->W + (size_t)b * m->nn(), m->Np, m->Np, m->q, M,
+                                  m->noise[b], m->work, (double*)m->cov, Mp));
+      GPK_CHECK_HIP(h, hipMemcpy2DAsync(cov + b * nc, (size_t)M * sizeof(double), m->cov, (size_t)Mp * sizeof(double),
+                                        (size_t)M * sizeof(double), (size_t)M, hipMemcpyDeviceToHost, h->stream));
+    }
+    GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  // model b: y_std[b]^2 Sigma_b (sklearn/_gpr.py:462-463)
+  for (int b = 0; b < B; ++b) {
+    const double s2 = m->y_std[b] * m->y_std[b];
+    double* out = cov + b * nc;
+    for (size_t i = 0; i < nc; ++i) out[i] = out[i] * s2;
   }
   return GPK_OK;
 }

@@ -1,7 +1,7 @@
 // One-call serving for the control loop: host queries in, host results out, one stream synchronisation per call.
 //
 //   gpk_predict_host, gpk_predict_host_multi             mean (+ variance)             of one model / of B per-axis models
-//   gpk_predict_host_cov                                 mean + covariance             of one model
+//   gpk_predict_host_cov, gpk_predict_host_multi_cov     mean + covariance             of one model / of B per-axis models
 //   gpk_predict_host_grad, gpk_predict_host_multi_grad   mean + Jacobian (+ variance + its gradient)
 //
 // The staging block is pinned, coherent host memory mapped into the device's address space: the kernels write their
@@ -11,7 +11,7 @@
 //
 // An entry checks its arguments, decides the route and calls one of serve_predict / serve_cov / serve_grad.  Those take
 // B models x P outputs each: the single-model entries are B = 1, the per-axis entries P = 1, and the outputs are laid out
-// (B, M, P), (B, M), (B, M, P, D), (B, M, D) either way.
+// (B, M, P), (B, M), (B, M, M), (B, M, P, D), (B, M, D) either way.
 #include "gpk_internal.h"
 
 namespace {
@@ -137,27 +137,33 @@ int serve_predict(gpk_handle h, const ServeModels& m, bool small, const double* 
   return s.finish();
 }
 
-// Mean (M, P) and covariance (M, M) of one model.  small: the two small-batch launches, the covariance through the pinned
-// block; otherwise V (Np x Mp) and Sigma (Mp x Mp) in the work area and one strided download.
-int serve_cov(gpk_handle h, const ServeModels& m, bool small, double noise, const double* Xq_host, int64_t M, double* mean_host,
-              double* cov_host) {
+// Mean (B, M, P) and covariance (B, M, M), noise[b] on model b's diagonal.  small: the two small-batch launches for all
+// models, the covariances through the pinned block; otherwise the general blocks model by model: V (Np x Mp) and Sigma
+// (Mp x Mp) in the work area (reused: the stream orders the models) and one strided download per model.
+int serve_cov(gpk_handle h, const ServeModels& m, bool small, const double* noise, const double* Xq_host, int64_t M,
+              double* mean_host, double* cov_host) {
   const int64_t Mp = gpk_padded(M);
+  const size_t nm = (size_t)M * m.P, nc = (size_t)M * M;       // per model
   double *hmean, *hcov = nullptr;
   Serve s(h, Xq_host, M, m.D);
-  s.out(mean_host, (size_t)M * m.P, &hmean);
-  if (small) s.out(cov_host, (size_t)M * M, &hcov);
-  GPK_TRY(s.begin(small ? gpk_small_work_doubles(GPK_SMALL_COV, m.Np, 1, M, m.D, m.P) : (size_t)m.Np * Mp + (size_t)Mp * Mp));
+  s.out(mean_host, m.B * nm, &hmean);
+  if (small) s.out(cov_host, m.B * nc, &hcov);
+  GPK_TRY(s.begin(small ? gpk_small_work_doubles(GPK_SMALL_COV, m.Np, m.B, M, m.D, m.P) : (size_t)m.Np * Mp + (size_t)Mp * Mp));
   if (small) {
-    GPK_TRY(gpk_small_cov(h, m.X[0], m.alpha[0], m.N, m.D, m.P, m.ls, m.sf2[0], m.y_mean, m.y_std, m.W[0], m.Np, m.ldw, noise, s.hq,
-                          M, s.dwork, hmean, hcov));
+    GPK_TRY(gpk_small_cov_multi(h, m.B, m.X, m.alpha, m.N, m.D, m.P, m.ls, m.sf2, m.y_mean, m.y_std, m.W, m.Np, m.ldw, noise, s.hq,
+                                M, s.dwork, hmean, hcov));
   } else {
     double* dV = s.dwork;
     double* dcov = s.dwork + (size_t)m.Np * Mp;
     GPK_TRY(s.upload());
-    GPK_TRY(gpk_predict_mean(h, GPK_F64, m.X[0], m.alpha[0], m.N, m.D, m.P, m.ls, m.sf2[0], m.y_mean, m.y_std, s.dq, M, hmean));
-    GPK_TRY(gpk_predict_cov_inv(h, GPK_F64, m.X[0], m.N, m.D, m.ls, m.sf2[0], m.W[0], m.Np, m.ldw, s.dq, M, noise, dV, dcov, Mp));
-    GPK_CHECK_HIP(h, hipMemcpy2DAsync(cov_host, (size_t)M * sizeof(double), dcov, (size_t)Mp * sizeof(double),
-                                      (size_t)M * sizeof(double), (size_t)M, hipMemcpyDeviceToHost, h->stream));
+    for (int b = 0; b < m.B; ++b) {
+      const double* ls = m.ls + b * m.D;
+      GPK_TRY(gpk_predict_mean(h, GPK_F64, m.X[b], m.alpha[b], m.N, m.D, m.P, ls, m.sf2[b], m.y_mean + b * m.P, m.y_std + b * m.P,
+                               s.dq, M, hmean + b * nm));
+      GPK_TRY(gpk_predict_cov_inv(h, GPK_F64, m.X[b], m.N, m.D, ls, m.sf2[b], m.W[b], m.Np, m.ldw, s.dq, M, noise[b], dV, dcov, Mp));
+      GPK_CHECK_HIP(h, hipMemcpy2DAsync(cov_host + b * nc, (size_t)M * sizeof(double), dcov, (size_t)Mp * sizeof(double),
+                                        (size_t)M * sizeof(double), (size_t)M, hipMemcpyDeviceToHost, h->stream));
+    }
   }
   return s.finish();
 }
@@ -245,7 +251,24 @@ extern "C" int gpk_predict_host_cov(gpk_handle h, const double* X, const double*
   GPK_REQUIRE(h, D >= 1 && D <= GPK_MAX_D_PREDICT && P >= 1 && P <= GPK_MAX_P, "predict_host_cov: D <= 16, P <= 16");
   GPK_REQUIRE(h, h->batch == 1, "predict_host_cov: not available in batched mode");
   const ServeModels m{1, P, &X, &alpha, N, D, ls, &sf2, y_mean, y_std, &W, Np, ldw, nullptr, 0.0};
-  return serve_cov(h, m, h->small_path && gpk_small_ok(Np, D, P, M), noise, Xq_host, M, mean_host, cov_host);
+  return serve_cov(h, m, h->small_path && gpk_small_ok(Np, D, P, M), &noise, Xq_host, M, mean_host, cov_host);
+}
+
+extern "C" int gpk_predict_host_multi_cov(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N,
+                                          int D, const double* ls, const double* sf2, const double* y_mean, const double* y_std,
+                                          const double* const* W, int64_t Np, int64_t ldw, const double* noise,
+                                          const double* Xq_host, int64_t M, double* mean_host, double* cov_host) {
+  if (!h) return GPK_BAD_ARG;
+  GPK_REQUIRE(h, X && alpha && ls && sf2 && y_mean && y_std && W && noise && Xq_host && mean_host && cov_host,
+              "predict_host_multi_cov: null pointer");
+  GPK_REQUIRE(h, B >= 1 && B <= GPK_SMALL_MAX_MODELS, "predict_host_multi_cov: 1..8 models");
+  GPK_REQUIRE(h, N >= 1 && gpk_small_ok(gpk_padded(N), D, 1, M), "predict_host_multi_cov: needs 1 <= M <= 32, D <= 16, N <= 16384");
+  GPK_REQUIRE(h, Np == gpk_padded(N) && ldw >= Np, "predict_host_multi_cov: Np must equal gpk_padded(N), ldw >= Np");
+  GPK_REQUIRE(h, h->batch == 1, "predict_host_multi_cov: not available in batched mode");
+  for (int b = 0; b < B; ++b) GPK_REQUIRE(h, X[b] && alpha[b] && W[b], "predict_host_multi_cov: null model pointer");
+  // (option small_path = 0, the cross-check of the small-batch kernels: the general building blocks, model by model)
+  const ServeModels m{B, 1, X, alpha, N, D, ls, sf2, y_mean, y_std, W, Np, ldw, nullptr, 0.0};
+  return serve_cov(h, m, h->small_path != 0, noise, Xq_host, M, mean_host, cov_host);
 }
 
 extern "C" int gpk_predict_host_grad(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P,

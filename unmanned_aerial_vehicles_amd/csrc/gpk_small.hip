@@ -16,6 +16,8 @@
 //                            share V_r^T V_r (lower triangle of the 32 x 32 block); the shares are added in a fixed
 //                            order in two levels - the last workgroup of each group of CG adds its group's, the last
 //                            of those adds the group sums - and K(Xq, Xq) + noise I - sum is written, mirrored.
+//                            The model is blockIdx.y as in the other two: the per-axis batch gets the B joint covariances
+//                            in the same two launches, each model with its own shares, group sums and ticket counters.
 //
 //   input gradients (K8)     small_cross_mean_jac_kernel adds the workgroup's share of the mean Jacobian
 //                            sum_j k*_mj alpha_jp (x_jd - q_md) / ls_d to the same launch (mean + Jacobian: still ONE launch,
@@ -45,6 +47,7 @@ struct SmallK {
   double ls[GPK_SMALL_MAX_MODELS][16];
   double sf2[GPK_SMALL_MAX_MODELS], kss[GPK_SMALL_MAX_MODELS];
   double ymean[16], ystd[16];
+  double noise[GPK_SMALL_MAX_MODELS];   // the WhiteKernel level (covariance only)
 };
 typedef double d4 __attribute__((ext_vector_type(4)));
 typedef double d2v __attribute__((ext_vector_type(2)));
@@ -426,18 +429,31 @@ __device__ __forceinline__ void tri_index(int t, int& i, int& j) {
   j = t - i * (i + 1) / 2;
 }
 
-// Posterior covariance of M <= 32 queries (one model): the rows of V as in small_var_kernel, then the workgroup's share of V^T V.
-// counters: [0] the top level, [1 + g] group g; all left at zero.  pcov: gridDim.x x CE, gcov: groups x CE.
+// Posterior covariance of M <= 32 queries (model y = blockIdx.y): the rows of V as in small_var_kernel, then the workgroup's
+// share of V^T V.  Per model: COV_COUNTERS ticket counters ([0] the top level, [1 + g] group g; all left at zero), pcov
+// (gridDim.x x CE), gcov (groups x CE), cov_out (M x M).  A model's sums are grouped by Np and M alone: its block has the
+// bits of that model served on its own.
+constexpr int COV_COUNTERS = 1 + (int)(GPK_SMALL_MAX_NP / SR / CG);
 template <int NMB>
 __global__ __launch_bounds__(64 * VW) void small_cov_kernel(SmallK k, long long ldw, long long Np, const double* Ks, int M,
-                                                            int D, int P, double noise, const double* Xq,
+                                                            int D, int P, const double* Xq,
                                                             const double* pmean, unsigned mean_shares, double* pcov,
                                                             double* gcov, unsigned* counters, double* mean_out,
                                                             double* cov_out) {
   __shared__ double red[VW][NMB][16][17];
   __shared__ double vt[NMB * 16][17];          // this workgroup's rows of V, transposed: [query][row]
   __shared__ double qs[SQ][SD + 1];
-  const double* __restrict__ W = k.W[0];
+  const int y = blockIdx.y;
+  const unsigned ng = (gridDim.x + CG - 1) / CG;
+  const double* __restrict__ W = k.W[y];
+  const double sf2 = k.sf2[y], noise = k.noise[y];
+  Ks += (long long)y * SQ * Np;
+  pmean += (long long)y * mean_shares * (SQ * SP);
+  pcov += (long long)y * gridDim.x * CE;
+  gcov += (long long)y * ng * CE;
+  counters += y * COV_COUNTERS;
+  mean_out += (long long)y * M * P;
+  cov_out += (long long)y * M * M;
   const int tid = threadIdx.x;
   small_v_rows<NMB>(W, ldw, Np, Ks, M, red);
   for (int e = tid; e < NMB * 256; e += 64 * VW) {
@@ -458,12 +474,12 @@ __global__ __launch_bounds__(64 * VW) void small_cov_kernel(SmallK k, long long 
   }
   // the mean shares are complete since the previous launch (as in small_var_kernel; scratch: the reduction buffer)
   static_assert(VW * 16 * 17 >= 4 * SQ * SP, "the reduction buffer doubles as the mean scratch");
-  if (blockIdx.x == 0) finish_means(pmean, mean_shares, M, P, k.ymean, k.ystd, mean_out, tid, &red[0][0][0][0]);
-  const unsigned g = blockIdx.x / CG, g0 = g * CG, g1 = min(g0 + CG, gridDim.x), ng = (gridDim.x + CG - 1) / CG;
+  if (blockIdx.x == 0) finish_means(pmean, mean_shares, M, P, k.ymean + y * P, k.ystd + y * P, mean_out, tid, &red[0][0][0][0]);
+  const unsigned g = blockIdx.x / CG, g0 = g * CG, g1 = min(g0 + CG, gridDim.x);
   if (!last_of(counters + 1 + g, g1 - g0, tid)) return;
   for (int t = tid; t < NE; t += 64 * VW) gcov[(long long)g * CE + t] = sum_shares(pcov + t, g0, 1, g1, CE);
   if (!last_of(counters, ng, tid)) return;
-  for (int e = tid; e < M * D; e += 64 * VW) qs[e / D][e % D] = Xq[e] / k.ls[0][e % D];
+  for (int e = tid; e < M * D; e += 64 * VW) qs[e / D][e % D] = Xq[e] / k.ls[y][e % D];
   __syncthreads();
   for (int t = tid; t < NE; t += 64 * VW) {
     int a, b;
@@ -472,7 +488,7 @@ __global__ __launch_bounds__(64 * VW) void small_cov_kernel(SmallK k, long long 
     const double s = sum_shares(gcov + t, 0, 1, ng, CE);
     double kv;
     if (a == b) {
-      kv = k.sf2[0] + noise;
+      kv = sf2 + noise;
     } else {
       double d2 = 0.0;
 #pragma unroll
@@ -481,7 +497,7 @@ __global__ __launch_bounds__(64 * VW) void small_cov_kernel(SmallK k, long long 
           const double df = qs[a][d] - qs[b][d];
           d2 = __builtin_fma(df, df, d2);
         }
-      kv = k.sf2[0] * gpk_exp_neg(-0.5 * d2);
+      kv = sf2 * gpk_exp_neg(-0.5 * d2);
     }
     const double v = kv - s;
     cov_out[(long long)a * M + b] = v;
@@ -616,7 +632,7 @@ struct SmallWork {
   size_t pjac;           // B x ga x (M * P * D)                    (grad)
   size_t Vs;             // B x Np x SQ                             (grad)
   size_t pdv;            // B x (gb x row chunks) x (M * D)         (grad)
-  size_t pcov, gcov;     // gb x CE, (gb / CG rounded up) x CE      (cov)
+  size_t pcov, gcov;     // B x gb x CE, B x (gb / CG rounded up) x CE   (cov)
   size_t total;
 };
 SmallWork small_work(int call, int64_t Np, int B, int64_t M, int D, int P) {
@@ -627,8 +643,8 @@ SmallWork small_work(int call, int64_t Np, int B, int64_t M, int D, int P) {
   w.Ks = take((size_t)B * SQ * Np);
   w.pmean = take((size_t)B * ga * (SQ * SP));
   if (call == GPK_SMALL_COV) {
-    w.pcov = take(gb * CE);
-    w.gcov = take((gb + CG - 1) / CG * CE);
+    w.pcov = take((size_t)B * gb * CE);
+    w.gcov = take((size_t)B * ((gb + CG - 1) / CG) * CE);
   } else {
     w.pvar = take((size_t)B * gb * SQ);
   }
@@ -642,10 +658,10 @@ SmallWork small_work(int call, int64_t Np, int B, int64_t M, int D, int P) {
 }
 
 // Checks the B models' pointers and length-scales and fills the kernels' parameter block.  W: null when the call forms
-// no V = W K*^T; kss: null when it has no variance.  `who` prefixes the messages.
+// no V = W K*^T; kss: null when it has no variance; noise: null except for the covariance.  `who` prefixes the messages.
 int small_params(gpk_handle h, const char* who, int B, int D, int P, const double* const* X, const double* const* alpha,
                  const double* const* W, const double* ls, const double* sf2, const double* kss, const double* y_mean,
-                 const double* y_std, SmallK& k) {
+                 const double* y_std, SmallK& k, const double* noise = nullptr) {
   const std::string name(who);
   for (int b = 0; b < B; ++b) {
     GPK_REQUIRE(h, X[b] && alpha[b] && (!W || W[b]), name + ": null model pointer");
@@ -658,6 +674,7 @@ int small_params(gpk_handle h, const char* who, int B, int D, int P, const doubl
     }
     k.sf2[b] = sf2[b];
     k.kss[b] = kss ? kss[b] : 0.0;
+    k.noise[b] = noise ? noise[b] : 0.0;
   }
   for (int o = 0; o < B * P; ++o) { k.ymean[o] = y_mean[o]; k.ystd[o] = y_std[o]; }
   return GPK_OK;
@@ -670,10 +687,11 @@ int ensure_cov_counters(gpk_handle h) {
   GPK_CHECK_HIP(h, hipMemsetAsync(h->d_cov_count, 0, GPK_SMALL_COV_COUNTERS * sizeof(unsigned), h->stream));
   return GPK_OK;
 }
-static_assert(GPK_SMALL_COV_COUNTERS >= 1 + GPK_SMALL_MAX_NP / SR / CG, "counters of the covariance reduction");
+static_assert(COV_COUNTERS == 65, "one top-level counter and one per group of CG workgroups at GPK_SMALL_MAX_NP");
+static_assert(GPK_SMALL_COV_COUNTERS >= GPK_SMALL_MAX_MODELS * COV_COUNTERS, "counters of the covariance reduction, per model");
 // the ticket counters of small_wtv_grad_kernel (one per model): the last GPK_SMALL_MAX_MODELS of h->d_cov_count
 constexpr int WTV_COUNTER0 = GPK_SMALL_COV_COUNTERS - GPK_SMALL_MAX_MODELS;
-static_assert(WTV_COUNTER0 >= 1 + GPK_SMALL_MAX_NP / SR / CG, "the covariance reduction's counters come first");
+static_assert(WTV_COUNTER0 >= GPK_SMALL_MAX_MODELS * COV_COUNTERS, "the covariance reduction's counters come first");
 static_assert(SR == GW, "small_wtv_grad_kernel takes as many columns of W per workgroup as small_var_kernel takes rows");
 
 }  // namespace
@@ -717,26 +735,29 @@ int gpk_small_predict(gpk_handle h, int B, const double* const* X, const double*
   return GPK_OK;
 }
 
-int gpk_small_cov(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls, double sf2,
-                  const double* y_mean, const double* y_std, const double* W, int64_t Np, int64_t ldw, double noise,
-                  const double* Xq, int64_t M, double* work, double* mean_out, double* cov_out) {
+int gpk_small_cov_multi(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D, int P,
+                        const double* ls, const double* sf2, const double* y_mean, const double* y_std, const double* const* W,
+                        int64_t Np, int64_t ldw, const double* noise, const double* Xq, int64_t M, double* work,
+                        double* mean_out, double* cov_out) {
+  GPK_REQUIRE(h, B >= 1 && B <= GPK_SMALL_MAX_MODELS && (B == 1 || P == 1), "small cov: 1 model, or up to 8 single-output models");
   GPK_REQUIRE(h, gpk_small_ok(Np, D, P, M) && Np == gpk_padded(N), "small cov: shape outside the small-batch path");
+  GPK_REQUIRE(h, X && alpha && noise && mean_out && cov_out, "small cov: null pointer");
   GPK_REQUIRE(h, W && ldw >= Np && ldw % 2 == 0, "small cov: needs the inverse factor");
   GPK_TRY(ensure_cov_counters(h));
   SmallK k{};
-  GPK_TRY(small_params(h, "small cov", 1, D, P, &X, &alpha, &W, ls, &sf2, nullptr, y_mean, y_std, k));
+  GPK_TRY(small_params(h, "small cov", B, D, P, X, alpha, W, ls, sf2, nullptr, y_mean, y_std, k, noise));
   const unsigned ga = (unsigned)(Np / SJ), gb = (unsigned)(Np / SR);
-  const SmallWork wk = small_work(GPK_SMALL_COV, Np, 1, M, D, P);
+  const SmallWork wk = small_work(GPK_SMALL_COV, Np, B, M, D, P);
   double *Ks = work + wk.Ks, *pmean = work + wk.pmean, *pcov = work + wk.pcov, *gcov = work + wk.gcov;
-  hipLaunchKernelGGL(small_cross_mean_kernel<false>, dim3(ga, 1), dim3(256), 0, h->stream, k, (long long)N, (long long)Np, D, P,
+  hipLaunchKernelGGL(small_cross_mean_kernel<false>, dim3(ga, B), dim3(256), 0, h->stream, k, (long long)N, (long long)Np, D, P,
                      Xq, (int)M, Ks, pmean, h->d_count, mean_out);
   GPK_LAUNCH_CHECK(h);
   if (M <= 16)
-    hipLaunchKernelGGL(small_cov_kernel<1>, dim3(gb), dim3(64 * VW), 0, h->stream, k, (long long)ldw, (long long)Np, Ks, (int)M,
-                       D, P, noise, Xq, pmean, ga, pcov, gcov, h->d_cov_count, mean_out, cov_out);
+    hipLaunchKernelGGL(small_cov_kernel<1>, dim3(gb, B), dim3(64 * VW), 0, h->stream, k, (long long)ldw, (long long)Np, Ks, (int)M,
+                       D, P, Xq, pmean, ga, pcov, gcov, h->d_cov_count, mean_out, cov_out);
   else
-    hipLaunchKernelGGL(small_cov_kernel<2>, dim3(gb), dim3(64 * VW), 0, h->stream, k, (long long)ldw, (long long)Np, Ks, (int)M,
-                       D, P, noise, Xq, pmean, ga, pcov, gcov, h->d_cov_count, mean_out, cov_out);
+    hipLaunchKernelGGL(small_cov_kernel<2>, dim3(gb, B), dim3(64 * VW), 0, h->stream, k, (long long)ldw, (long long)Np, Ks, (int)M,
+                       D, P, Xq, pmean, ga, pcov, gcov, h->d_cov_count, mean_out, cov_out);
   GPK_LAUNCH_CHECK(h);
   return GPK_OK;
 }

@@ -39,6 +39,32 @@ def _rng_from(random_state):
     return random_state
 
 
+def cholesky_draws(mean, cov, n_samples=1, random_state=0, active=None):
+    """Draws from B independent Gaussians over the same M rows: mean (M, B), cov (M, M, B) -> (M, B, n_samples).  Pure NumPy.
+
+    ONE z = standard_normal((B, M, n_samples)) from `_rng_from(random_state)`, then samples[:, b, :] = mean[:, b, None] +
+    cholesky(cov[..., b]) @ z[b]: a stable function of the covariance, unlike `multivariate_normal`'s SVD draw (repeated
+    singular values let a 1e-12 perturbation of the covariance rotate it).  A covariance that does not factorise gets
+    1e-10 * max(diag) added to its diagonal once; a second failure raises `np.linalg.LinAlgError`.  active: boolean (B,) -
+    models marked False are skipped and return zeros (z is drawn for all B either way, so a model's draw does not depend on
+    which others are present)."""
+    mean = np.asarray(mean, dtype=np.float64)
+    cov = np.asarray(cov, dtype=np.float64)
+    M, B = mean.shape
+    z = _rng_from(random_state).standard_normal((B, M, n_samples))
+    out = np.zeros((M, B, n_samples))
+    for b in range(B):
+        if active is not None and not active[b]:
+            continue
+        c = cov[..., b]
+        try:
+            L = np.linalg.cholesky(c)
+        except np.linalg.LinAlgError:
+            L = np.linalg.cholesky(c + 1e-10 * np.max(np.diag(c)) * np.eye(M))
+        out[:, b, :] = mean[:, b, None] + L @ z[b]
+    return out
+
+
 class GaussianProcessRegressor:
     def __init__(self, kernel=None, *, alpha=1e-10, optimizer="fmin_l_bfgs_b", n_restarts_optimizer=0,
                  normalize_y=False, copy_X_train=True, n_targets=None, random_state=None, device=None,

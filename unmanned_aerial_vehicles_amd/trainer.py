@@ -395,6 +395,74 @@ class PreTrainedGP:
             return mean, J, std, dstd
         return mean, J
 
+    # ---- joint posterior along a batch of rows: covariances and draws in raw units ---------------------------------------
+    FALLBACK_VAR = 1e12        # the square of the 1e6 this class reports as the std of a missing component
+
+    def _residual_cov(self, X):
+        """(mean (M, 6), cov (M, M, 6), served (6,) bool) of `predict_residual_cov_batch`."""
+        try:
+            X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+            M = len(X)
+        except Exception as e:  # noqa: BLE001
+            print(f"GP prediction failed: {e}")
+            X, M = None, 1
+        mean = np.zeros((M, 6))
+        cov = np.repeat((self.FALLBACK_VAR * np.eye(M))[:, :, None], 6, axis=2)
+        served = np.zeros(6, dtype=bool)
+
+        def put(i, name, mu, sig):
+            sy = self.scalers_y[name]
+            m_i = sy.inverse_transform(np.asarray(mu, dtype=np.float64).reshape(-1, 1)).ravel()
+            c_i = float(np.ravel(sy.scale_)[0]) ** 2 * np.asarray(sig, dtype=np.float64).reshape(M, M)
+            if not (np.isfinite(m_i).all() and np.isfinite(c_i).all()):
+                raise FloatingPointError("non-finite mean or covariance")
+            mean[:, i], cov[:, :, i], served[i] = m_i, c_i, True
+
+        if X is not None and self.is_loaded:
+            fused = self._fused()
+            if fused:
+                bg, names = fused
+                try:
+                    mu, sig = bg.predict(self.scalers_X[names[0]].transform(X), return_cov=True)
+                    for j, n in enumerate(names):
+                        put(OUTPUT_NAMES.index(n), n, mu[:, j], sig[:, :, j])
+                except Exception as e:  # noqa: BLE001 - the per-model loop below still serves
+                    print(f"GP prediction failed: {e}")
+            for i, name in enumerate(OUTPUT_NAMES):
+                if name not in self.gp_models or served[i]:
+                    continue
+                try:
+                    mu, sig = self.gp_models[name].predict(self.scalers_X[name].transform(X), return_cov=True)
+                    put(i, name, mu, sig)
+                except Exception as e:  # noqa: BLE001
+                    print(f"GP prediction failed for {name}: {e}")
+                    mean[:, i], cov[:, :, i], served[i] = 0.0, self.FALLBACK_VAR * np.eye(M), False
+        return mean, cov, served
+
+    def predict_residual_cov_batch(self, X):
+        """Joint posterior of the six residuals over a batch of raw [state(6), control(4)] rows - a consistent residual
+        trajectory per axis along the horizon: (mean (M, 6), cov (M, M, 6)) in raw units, cov[..., i] = sy_i.scale_^2 Sigma_i
+        with Sigma_i model i's posterior covariance on the scaled inputs (its WhiteKernel level on the diagonal, not clipped).
+        Models that share inputs and scaler (those `GPTrainer` writes): ONE call for all of them
+        (`BatchedARDGP.predict(return_cov=True)`; up to 32 rows two launches and one synchronisation); otherwise one
+        `predict(return_cov=True)` per model with its own scalers.  The reference has no counterpart: a caller would make
+        six scikit-learn `predict(return_cov=True)` calls around `pretrained_gp.py:52-98`.  Missing or failing components, or
+        nothing loaded: mean 0, cov[..., i] = 1e12 I.  Never raises."""
+        mean, cov, _ = self._residual_cov(X)
+        return mean, cov
+
+    def sample_residuals(self, X, n_samples=1, random_state=0):
+        """Draws from that joint posterior: (M, 6, n_samples) in raw units, through the Cholesky factor of each covariance
+        (`gpr.cholesky_draws`).  One standard-normal block of shape (6, M, n_samples) is drawn whatever is loaded, so a
+        component's draw does not depend on which others are present.  Missing or failing components: zeros.  Never raises."""
+        from .gpr import cholesky_draws
+        mean, cov, served = self._residual_cov(X)
+        try:
+            return cholesky_draws(mean, cov, n_samples, random_state, active=served)
+        except Exception as e:  # noqa: BLE001
+            print(f"GP sampling failed: {e}")
+            return np.zeros((mean.shape[0], 6, int(n_samples)))
+
     def predict_residual_jacobian(self, state, control):
         """One query -> (mean (6,), J (6, 10)), J = d mean / d [state(6), control(4)]; not loaded or failed: zeros."""
         try:
