@@ -85,7 +85,8 @@ GPK_API int64_t gpk_padded(int64_t n);
  * level-by-level products of gpk_trtri; same values to rounding), "gemm_balanced" (tile GEMMs whose tiles differ in k-range - the
  * products with triangular operands of gpk_trtri / gpk_wtw / gpk_potrs_inv: 1 = the balanced persistent tile schedule, 0 = the
  * static tile mapping; bit-identical results), "gemm_balanced_max_tiles", "gemm_log" (1: every tile-GEMM launch to stderr),
- * "debug_fill" (1: the handle's scratch and serving work area are overwritten with NaN bytes at every request - the test
+ * "sparse_panel" / "sparse_slabs" (the statistics pass of the sparse model, K9:
+ * rows per panel and k-slabs per panel product; 0 = the built-in rule), "debug_fill" (1: the handle's scratch and serving work area are overwritten with NaN bytes at every request - the test
  * suite runs with it).  Used by the A/B timings and by the tests that pin a fast path to its plain form.
  * gpk_set_option_str: "ptile_trace_path" - the NEXT one-launch factorisation writes its per-task time stamps to that file
  * (debugging aid, tools/exp_ptile_trace.py).                                                                          */
@@ -585,6 +586,72 @@ GPK_API int gpk_fit_batched(gpk_handle h, int B, const double* X, int64_t N, int
                     const double* sf2, const double* noise, double jitter, int normalize_y, int* info);
 GPK_API int gpk_predict_batched(gpk_handle h, const double* Xq, int64_t M, double* mean, double* var, int var_includes_noise);
 GPK_API int gpk_lml_batched(gpk_handle h, const double* thetas, int n_theta, double* lml, double* grad);
+
+/* ---- K9: sparse inducing-point GP - fit on every row, serve through m inducing inputs -----------------------------------
+ * The Titsias / DTC ("projected process") predictor of GPflow's SGPR (the reference's src/px4/gp.py is a GPflow model): one
+ * kernel sf2 RBF(ls) shared by P outputs, noise sigma^2 = noise (the WhiteKernel level) + jitter (the regressor's alpha),
+ * targets normalised with a y_mean / y_std FIXED when the object is created - only then are the statistics additive.  With m
+ * inducing inputs Z (mp = gpk_padded(m)) the training rows enter through fp64 statistics of size m x m,
+ *     G = Kuf Kfu (m x m),  g = Kuf Yn (m x P),  yy[p] = sum Yn[:, p]^2,  N,
+ * kept on the device as ONE symmetric matrix S = F^T F, F = [Kfu | Yn] (rows x (mp + 128)): S[0:mp, 0:mp] = G,
+ * S[mp + p][0:mp] = S[0:mp][mp + p] = g[:, p], S[mp + p][mp + p] = yy[p], zero in the padding.  Appending n rows costs n m^2
+ * flops and an m x m refactorisation; serving costs what an exact model of m rows costs.  A third object behind the handle,
+ * next to the single model and the batch; gpk_model_release and gpk_destroy free it.  HOST pointers and fp64 throughout,
+ * except gpk_sparse_accumulate.
+ * Replaces: the row caps the reference needs because its exact models cannot train on what a flight log holds -
+ *   src/px4/gp_trainer.py:95-96 (a random max_samples), src/px4/train_gp_offline.py:124 (max_data_points = 10000),
+ *   quadrotor_gp_mpc/quadrotor_gp_mpc/gaussian_process.py:146-149 and src/px4/simple_gp.py (the oldest rows past 1000 dropped).
+ *
+ * gpk_sparse_accumulate: the statistics pass, the device-pointer building block: S (dev, nt x ld, nt = mp + 128, even
+ *   ld >= nt, 16-byte aligned; symmetric on entry - zero to begin with - and on return) += F^T F over the n rows X (dev n x D),
+ *   Yn (dev n x P, normalised targets) against Z (dev m x D); ls host double[D].  Rows go in panels of at most "sparse_panel"
+ *   rows (gpk_set_option; 0, the default: F within 128 MiB - half of the Infinity Cache, so that the panel the cross kernel
+ *   wrote is still on the chip when the product reads it - between 1024 and 16384 rows).  Per panel: F by exact differences (as
+ *   gpk_cross_gram_t), the lower tiles of F^T F on the fp64 matrix cores with the panel's rows cut into k-slabs (independent
+ *   products of one launch, one partial matrix each), and one launch that adds the partials IN SLAB ORDER into S and mirrors it
+ *   to both halves; a one-slab panel accumulates straight into the lower tiles and one mirror pass ends the call.  No
+ *   floating-point atomics: the same sequence of calls gives the same bits; S is symmetric bit for bit.  The slab count is a
+ *   function of (mp, panel rows) only - one from 256 lower 128-tiles (the CU count) on, below that the fewest that give 1024
+ *   tiles, at most 16, never under 512 rows each - or option "sparse_slabs" (1 .. 64).  Asynchronous; work area: the handle's scratch.  1 <= m <= 16384, D <= 16, P <= GPK_MAX_P.
+ * gpk_sparse_begin: creates the object with zero statistics.  Z host (m x D); ls: n_ls = 1 or D values; jitter_uu: absolute,
+ *   on the diagonal of Kuu.  1 <= m <= 16384, D <= 16, P <= GPK_MAX_P, noise + jitter > 0.
+ * gpk_sparse_update: appends n >= 1 raw rows X (n x D), Y (n x P): checks that they are finite, normalises the targets, runs
+ *   the panel loop and synchronises once.
+ * gpk_sparse_finalize: assembles the model; any number of updates may precede it, none included (the model is then the
+ *   prior), and the statistics stay valid for further updates.
+ *       Luu Luu^T = Kuu + jitter_uu I,  Wuu = Luu^-1            (gpk_gram, gpk_potrf, gpk_trtri)
+ *       B = I + Wuu G Wuu^T / sigma^2,  LB LB^T = B             (two tile GEMMs; gpk_potrf)
+ *       r = Wuu g / sigma^2,  alpha_u = Wuu^T B^-1 r            (tile GEMMs on 128-column panels)
+ *       WSigma = LB^-1 Wuu                                      (lower tiles + zeros to their right: the inverse-factor
+ *                                                                layout of gpk_predict_var_inv)
+ *       bound = sum_p [ -N/2 log(2 pi sigma^2) - sum log diag LB - (N sf2 - sigma^2 (tr B - m)) / (2 sigma^2)
+ *                       - yy[p] / (2 sigma^2) + r_p^T B^-1 r_p / 2 ]          (gpk_lml_terms on (LB, r, B^-1 r))
+ *   the collapsed lower bound on the log-marginal likelihood in normalised-target units; the exact value when Z = X.
+ *   Returns GPK_NOT_PD with *info = the 1-based pivot, as gpk_potrf, if Kuu + jitter_uu I or B is not positive definite.
+ * gpk_sparse_predict: the semantics of gpk_predict at GPK_F64: Xq (M x D), mean (M x P, un-normalised),
+ *       mean(x) = y_mean + y_std k_u(x)^T alpha_u,   var_f(x) = sf2 - |Wuu k_u(x)|^2 + |WSigma k_u(x)|^2,
+ *   var (M x P: variance times y_std^2; NULL = means only); var_includes_noise != 0: + the WhiteKernel level, clipped at 0;
+ *   == 0: floored at 1e-10.  Checks that the queries are finite.  No kernel of its own: the model is two "models" on the
+ *   shared inputs Z, (alpha_u, Wuu, kss) and (any alpha, WSigma, 0).  Up to 32 queries: gpk_predict_host_multi with B = 2 and
+ *   a floor of -DBL_MAX (one call, two launches, one synchronisation; P > 1: gpk_predict_host once per inverse factor, four
+ *   launches); more, or option small_path = 0: panels of the fused mean and two gpk_predict_var_inv launches.
+ * gpk_sparse_bound: the bound of the last gpk_sparse_finalize and the rows seen so far.
+ * gpk_sparse_export / gpk_sparse_import: Z (m x D), the statistics G (m x m), g (m x P), yy (P), n_rows and the
+ *   hyper-parameters - ls (n_ls values), hyper = [sf2, noise, jitter, jitter_uu], y_mean, y_std (P) - as host arrays; NULL
+ *   outputs are skipped.  The importer then only finalises (and may go on updating).                                        */
+GPK_API int gpk_sparse_accumulate(gpk_handle h, const double* X, const double* Yn, int64_t n, const double* Z, int64_t m, int D,
+                                  int P, const double* ls, double sf2, double* S, int64_t ld);
+GPK_API int gpk_sparse_begin(gpk_handle h, const double* Z, int64_t m, int D, int P, const double* ls, int n_ls, double sf2,
+                             double noise, double jitter, double jitter_uu, const double* y_mean, const double* y_std);
+GPK_API int gpk_sparse_update(gpk_handle h, const double* X, const double* Y, int64_t n);
+GPK_API int gpk_sparse_finalize(gpk_handle h, int* info);
+GPK_API int gpk_sparse_predict(gpk_handle h, const double* Xq, int64_t M, double* mean, double* var, int var_includes_noise);
+GPK_API int gpk_sparse_bound(gpk_handle h, double* bound, int64_t* n_rows);
+GPK_API int gpk_sparse_export(gpk_handle h, int64_t* m, int* D, int* P, int* n_ls, double* Z, double* G, double* g, double* yy,
+                              int64_t* n_rows, double* ls, double* hyper, double* y_mean, double* y_std);
+GPK_API int gpk_sparse_import(gpk_handle h, const double* Z, int64_t m, int D, int P, const double* ls, int n_ls, double sf2,
+                              double noise, double jitter, double jitter_uu, const double* y_mean, const double* y_std,
+                              const double* G, const double* g, const double* yy, int64_t n_rows);
 
 /* ---- building block: whole-tile GEMM on the matrix cores ---------------------------------------
  * C[m x n] = alpha * opA(A) * opB(B)^T + beta * C, m and n multiples of 128, k a multiple of 16

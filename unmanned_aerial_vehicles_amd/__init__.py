@@ -7,6 +7,7 @@ kernels).  Public surface mirrors the reference's seams:
     SimpleQuadrotorGP, SimpleGPEnhancedMPC                        (model seam, simple_gp.py)
     GaussianProcess                                               (ROS-package GP, package_gp.py)
     GPTrainer, PreTrainedGP                                       (per-output ARD GPs, trainer.py)
+    SparseGP                                                      (inducing-point GP: every row, m points; sparse.py)
     evaluate_gp, ShardedPredictor, sharded_gram
 """
 from .kernels import RBF, ConstantKernel, WhiteKernel  # noqa: F401
@@ -15,9 +16,10 @@ from .simple_gp import SimpleGPEnhancedMPC, SimpleQuadrotorGP  # noqa: F401
 from .package_gp import GaussianProcess  # noqa: F401
 from .trainer import GPTrainer, PreTrainedGP  # noqa: F401
 from .batched import BatchedARDGP  # noqa: F401
+from .sparse import SparseGP  # noqa: F401
 from .evaluate import evaluate_gp  # noqa: F401
 from .sharded import ShardedPredictor, gram_slab_bounds, shard_bounds, sharded_gram, sharded_predict  # noqa: F401
 
 __all__ = ["GaussianProcessRegressor", "RBF", "WhiteKernel", "ConstantKernel", "SimpleQuadrotorGP",
            "SimpleGPEnhancedMPC", "GaussianProcess", "GPTrainer", "PreTrainedGP", "evaluate_gp",
-           "ShardedPredictor", "shard_bounds", "sharded_predict", "sharded_gram", "gram_slab_bounds", "BatchedARDGP"]
+           "ShardedPredictor", "shard_bounds", "sharded_predict", "sharded_gram", "gram_slab_bounds", "BatchedARDGP", "SparseGP"]

@@ -111,6 +111,15 @@ SIGNATURES = {
     "gpk_lml_grad": (_int, [_vp, _vp, _i64, _int, _dp, _dbl, _dbl, _vp, _int, _vp, _i64, _dp]),
     "gpk_lml_eval": (_int, [_vp, _vp, _i64, _int, _dp, _dbl, _dbl, _dbl, _vp, _int, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _dp, _dp,
                             C.POINTER(C.c_int)]),
+    "gpk_sparse_accumulate": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _int, _int, _dp, _dbl, _vp, _i64]),
+    "gpk_sparse_begin": (_int, [_vp, _dp, _i64, _int, _int, _dp, _int, _dbl, _dbl, _dbl, _dbl, _dp, _dp]),
+    "gpk_sparse_update": (_int, [_vp, _dp, _dp, _i64]),
+    "gpk_sparse_finalize": (_int, [_vp, C.POINTER(_int)]),
+    "gpk_sparse_predict": (_int, [_vp, _dp, _i64, _dp, _dp, _int]),
+    "gpk_sparse_bound": (_int, [_vp, _dp, C.POINTER(_i64)]),
+    "gpk_sparse_export": (_int, [_vp, C.POINTER(_i64), C.POINTER(_int), C.POINTER(_int), C.POINTER(_int), _dp, _dp, _dp, _dp,
+                                 C.POINTER(_i64), _dp, _dp, _dp, _dp]),
+    "gpk_sparse_import": (_int, [_vp, _dp, _i64, _int, _int, _dp, _int, _dbl, _dbl, _dbl, _dbl, _dp, _dp, _dp, _dp, _dp, _i64]),
     "gpk_gemm_tiles": (_int, [_vp, _int, _int, _int, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _dbl,
                               _dbl, _int]),
 }

@@ -12,11 +12,13 @@
 
 struct gpk_model;    // the composite calls' model (gpk_model.hip)
 struct gpk_bmodel;   // B single-output models on shared inputs (gpk_fit_batched, gpk_model.hip)
+struct gpk_sparse;   // the sparse inducing-point model (gpk_sparse_begin, gpk_sparse.hip)
 
 struct gpk_context {
   int device = 0;
   gpk_model* model = nullptr;        // owned: gpk_fit / gpk_import create it, gpk_destroy / gpk_model_release free it
   gpk_bmodel* bmodel = nullptr;      // owned: gpk_fit_batched creates it, gpk_destroy / gpk_model_release free it
+  gpk_sparse* sparse = nullptr;      // owned: gpk_sparse_begin / gpk_sparse_import create it, gpk_destroy / gpk_model_release free it
   hipStream_t stream = nullptr;      // stream kernels are launched on
   hipStream_t own_stream = nullptr;  // created by gpk_create
   bool user_stream = false;
@@ -65,6 +67,8 @@ struct gpk_context {
   std::string ptile_trace_request;   // option "ptile_trace_path" (debugging aid): the NEXT one-launch factorisation writes its per-task time stamps there
   std::string ptile_trace_path;   // ... while that launch is in flight
   long long ptile_trace_n = 0;
+  int sparse_panel = 0;      // gpk_sparse_update / gpk_sparse_accumulate: rows per panel (0: F = [Kfu | Yn] within 128 MiB, 1024 .. 16384 rows)
+  int sparse_slabs = 0;      // ... k-slabs of a panel's product F^T F (0: a function of (mp, panel rows), gpk_sparse.hip; 1 .. 64)
   int debug_fill = 0;        // option debug_fill: the handle's scratch is overwritten with 0xFF bytes (NaN) at every request
   int gemm_log = 0;          // option gemm_log = 1: log every tile-GEMM launch to stderr (profiling aid)
   // gpk_timing: HIP-event brackets around the dominant launches (K5 variance GEMM, K1 Gram kernel), a ring of pairs
@@ -125,6 +129,7 @@ int gpk_potrf_ptile(gpk_handle h, double* A, int64_t Np, int64_t lda, double* wi
                     double* wband = nullptr, int64_t ldw = 0, int zero_info = 0);
 int gpk_potrf_ptile_check(gpk_handle h, int gave_up = -1);
 void gpk_model_free(gpk_handle h);   // gpk_model.hip
+void gpk_sparse_free(gpk_handle h);  // gpk_sparse.hip
 // the launches of gpk_potrf / gpk_lml_terms / gpk_lml_grad without their synchronisations (gpk_lml_eval)
 int gpk_potrf_enqueue(gpk_handle h, double* A, int64_t Np, int64_t lda, double* winv);
 int gpk_potrf_finish(gpk_handle h, const int* hinfo_all, int* info, int gave_up = -1);

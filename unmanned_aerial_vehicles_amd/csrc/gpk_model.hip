@@ -232,6 +232,7 @@ void gpk_bmodel_free(gpk_handle h);
 void gpk_model_free(gpk_handle h) {
   if (h->model) { free_all(h->model); delete h->model; h->model = nullptr; }
   gpk_bmodel_free(h);
+  gpk_sparse_free(h);
 }
 
 extern "C" int gpk_model_release(gpk_handle h) {

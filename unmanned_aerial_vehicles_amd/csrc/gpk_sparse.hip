@@ -1,0 +1,661 @@
+// K9: sparse inducing-point GP (Titsias / DTC "projected process" predictor, the form of GPflow's SGPR) - fit on every row,
+// serve through m inducing inputs Z.
+//
+// The training rows enter through ADDITIVE fp64 statistics of size m x m, kept as ONE symmetric matrix
+//   S = F^T F,  F = [Kfu | Yn]  (rows x (mp + 128); mp = m rounded up to 128; zero in the padding)
+//   S[0:mp, 0:mp] = G = Kuf Kfu,   S[mp + p, 0:mp] = g[:, p] = Kuf Yn[:, p],   S[mp + p, mp + q] = Yn[:, p] . Yn[:, q]
+// so that appending rows is S += F_new^T F_new.  The statistics pass is this file's hot path (N m^2 flops):
+//   per panel of rows   sparse_panel_kernel   F (exact differences of the length-scale-divided coordinates, as
+//                                             gpk_cross_gram_t; the normalised targets ride in the last 128 columns)
+//                       tile GEMM             the lower tiles of F^T F on the fp64 matrix cores.  The product is tall and
+//                                             skinny (m = 1024: 45 lower 128-tiles for 256 CUs), so the panel's rows are cut
+//                                             into `slabs` k-slabs, each an independent product of the GEMM's explicit batch
+//                                             mode writing its own partial matrix ...
+//                       sparse_reduce_kernel  ... which are added IN SLAB ORDER into S and mirrored to both halves: no
+//                                             floating-point atomics, the same sequence of updates gives the same bits.
+//   One slab: the GEMM accumulates straight into the lower tiles of S (beta = 1) and one mirror pass ends the call.
+// The slab count depends on (mp, panel rows) only (sparse_slabs_for), overridable by option "sparse_slabs"; the panel by
+// option "sparse_panel" (sparse_panel_for: F within half of the 256 MB Infinity Cache).
+//
+// The assembly (gpk_sparse_finalize) and the serving (gpk_sparse_predict) are host code over entries that exist: gpk_gram /
+// gpk_potrf / gpk_trtri, tile GEMMs with triangular k-ranges, gpk_lml_terms, gpk_predict_host_multi (the sparse model is
+// two "models" on the shared inputs Z: (alpha_u, Wuu, kss = sf2) and (any alpha, WSigma, kss = 0)), gpk_predict_mean and
+// gpk_predict_var_inv.  DESIGN.md, K9.
+#include <cfloat>
+#include <cmath>
+#include <limits>
+
+#include "gpk_internal.h"
+#include "gpk_math.h"
+
+namespace {
+
+constexpr int NB = GPK_TILE;
+constexpr int SP_TS = 64;             // sparse_panel_kernel: rows x columns of F per workgroup
+constexpr int SP_MAX_SLABS = 64;
+constexpr int64_t SP_MAX_M = 16384;   // inducing inputs (the small-batch serving kernels' limit on the padded size)
+
+struct SpLs { double v[GPK_MAX_D_PREDICT]; };
+struct SpP { double v[GPK_MAX_P]; };
+
+// F[i][j] = sf2 exp(-0.5 |(x_i - z_j) / ls|^2) for i < n, j < m;  F[i][mp + p] = Yn[i][p] for i < n, p < P;  0 elsewhere in
+// the (gridDim.y * 64) x (mp + 128) block.  64 x 64 entries per workgroup, a 4 x 4 micro-tile per thread whose columns are
+// the two pairs {2 tx, 2 tx + 1} and {32 + 2 tx, 33 + 2 tx}: every 16-byte store of 16 neighbouring lanes covers 256
+// contiguous bytes.  D <= 16: rows and inducing inputs are staged once, divided by the length-scales.
+__global__ __launch_bounds__(256) void sparse_panel_kernel(const double* __restrict__ X, const double* __restrict__ Yn,
+                                                           long long n, const double* __restrict__ Z, int m, int D, int P,
+                                                           SpLs ls, double sf2, double* __restrict__ F, long long ldf,
+                                                           int mp) {
+  __shared__ __attribute__((aligned(16))) double xi[GPK_MAX_D_PREDICT * SP_TS];
+  __shared__ __attribute__((aligned(16))) double zj[GPK_MAX_D_PREDICT * SP_TS];
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+  const long long i0 = (long long)blockIdx.y * SP_TS;
+  const int j0 = blockIdx.x * SP_TS;
+  if (j0 >= mp) {      // the targets' 128 columns
+    for (int e = tid; e < SP_TS * SP_TS; e += 256) {
+      const int r = e >> 6, c = e & 63, p = j0 - mp + c;
+      const long long gi = i0 + r;
+      F[gi * ldf + j0 + c] = (gi < n && p < P) ? Yn[gi * P + p] : 0.0;
+    }
+    return;
+  }
+  for (int e = tid; e < SP_TS * D; e += 256) {
+    const int i = e / D, d = e - i * D;
+    const long long gi = i0 + i;
+    const int gj = j0 + i;
+    xi[d * SP_TS + i] = gi < n ? X[gi * D + d] / ls.v[d] : 0.0;
+    zj[d * SP_TS + i] = gj < m ? Z[(long long)gj * D + d] / ls.v[d] : 0.0;
+  }
+  __syncthreads();
+  double d2[4][4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) d2[r][c] = 0.0;
+  for (int d = 0; d < D; ++d) {
+    double a[4], b[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) a[r] = xi[d * SP_TS + 4 * ty + r];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) b[c] = zj[d * SP_TS + (c >> 1) * 32 + 2 * tx + (c & 1)];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const double df = a[r] - b[c];
+        d2[r][c] = __builtin_fma(df, df, d2[r][c]);
+      }
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const long long gi = i0 + 4 * ty + r;
+    double v[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int gj = j0 + (c >> 1) * 32 + 2 * tx + (c & 1);
+      v[c] = (gi < n && gj < m) ? sf2 * gpk_exp_neg(-0.5 * d2[r][c]) : 0.0;
+    }
+    double* row = F + gi * ldf + j0 + 2 * tx;
+    *reinterpret_cast<double2*>(row) = make_double2(v[0], v[1]);
+    *reinterpret_cast<double2*>(row + 32) = make_double2(v[2], v[3]);
+  }
+}
+
+// S[i][j] = S[j][i] = S[i][j] + sum_{s < nslabs, in slab order} partial[s][i][j] for i >= j (nt x nt, 32 x 32 entries per
+// workgroup over the lower triangle; the transposed half goes through LDS so that both stores are contiguous).  nslabs == 0:
+// the mirror alone.  Only entries i >= j of S and of the partials are read.
+__global__ __launch_bounds__(256) void sparse_reduce_kernel(double* __restrict__ S, long long ld,
+                                                            const double* __restrict__ partial, int nslabs,
+                                                            long long pstride, int nt) {
+  __shared__ double t[32][33];
+  const long long id = blockIdx.x;
+  long long bi = (long long)((__builtin_sqrt(8.0 * (double)id + 1.0) - 1.0) * 0.5);
+  while ((bi + 1) * (bi + 2) / 2 <= id) ++bi;
+  while (bi * (bi + 1) / 2 > id) --bi;
+  const long long bj = id - bi * (bi + 1) / 2;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int li = ty + 8 * r;
+    const long long i = bi * 32 + li, j = bj * 32 + tx;
+    if (i >= j) {
+      double v = S[i * ld + j];
+      for (int s = 0; s < nslabs; ++s) v += partial[s * pstride + i * nt + j];
+      S[i * ld + j] = v;
+      t[li][tx] = v;
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int li = ty + 8 * r;
+    const long long gi = bj * 32 + li, gj = bi * 32 + tx;
+    if (gj > gi) S[gi * ld + gj] = t[tx][li];
+  }
+}
+
+// out[0] = sum_{i < mp} B[i][i] (= tr(Wuu G Wuu^T) / sigma^2, added in a fixed order), then B[i][i] += 1;
+// out[1 + p] = S[mp + p][mp + p] = yy[p].  One workgroup.
+__global__ __launch_bounds__(256) void sparse_diag_kernel(double* __restrict__ B, long long ldb, int mp,
+                                                          const double* __restrict__ S, long long lds_, int P,
+                                                          double* __restrict__ out) {
+  __shared__ double red[256];
+  const int tid = threadIdx.x;
+  double s = 0.0;
+  for (int i = tid; i < mp; i += 256) {
+    const double v = B[(long long)i * ldb + i];
+    s += v;
+    B[(long long)i * ldb + i] = v + 1.0;
+  }
+  red[tid] = s;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (tid < w) red[tid] += red[tid + w];
+    __syncthreads();
+  }
+  if (tid == 0) out[0] = red[0];
+  if (tid < P) out[1 + tid] = S[(long long)(mp + tid) * lds_ + mp + tid];
+}
+
+// the first P columns of three (m x 128) panels as compact (m x P) arrays
+__global__ void sparse_unpack_kernel(const double* __restrict__ p0, const double* __restrict__ p1,
+                                     const double* __restrict__ p2, long long m, int P, double* __restrict__ o0,
+                                     double* __restrict__ o1, double* __restrict__ o2) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= m * P) return;
+  const long long i = e / P;
+  const int p = (int)(e - i * P);
+  o0[e] = p0[i * NB + p];
+  o1[e] = p1[i * NB + p];
+  o2[e] = p2[i * NB + p];
+}
+
+// out[i][p] = max(v0[i] - v1[i], floor) y_std[p]^2   (v0 = kss - |Wuu k|^2, v1 = -|WSigma k|^2)
+__global__ void sparse_var_kernel(const double* __restrict__ v0, const double* __restrict__ v1, long long M, int P, SpP ys,
+                                  double floor_, double* __restrict__ out) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= M * P) return;
+  const long long i = e / P;
+  const int p = (int)(e - i * P);
+  out[e] = fmax(v0[i] - v1[i], floor_) * ys.v[p] * ys.v[p];
+}
+
+int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
+
+// Rows of a panel: F = rows x (mp + 128) doubles within 128 MiB - half of the 256 MB Infinity Cache, so that the panel the
+// cross kernel has just written is still on the chip while the (mp / 128 + 1) tile columns of the product read it again -
+// between 1024 and 16384 rows, a multiple of 256.  Measured (N = 262 144, ms at 2048 / 4096 / 8192 / 16384 rows,
+// profiles/r11_exp_sparse_second_rule.log): m = 256 4.75 / 3.10 / 2.28 / 1.72 and m = 1024 12.09 / 9.33 / 7.92 / 7.18 (F = 50 /
+// 151 MB at 16384 rows: the longer panel wins), m = 4096 with one slab 94.5 / 94.0 / 96.2 / 107.6 (F = 138 MB at 4096 rows, 554 MB
+// at 16384: it falls out of the cache).  Option "sparse_panel" overrides.
+int64_t sparse_panel_for(gpk_handle h, int64_t mp) {
+  if (h->sparse_panel > 0) return h->sparse_panel;
+  int64_t rows = (int64_t)((128ll << 20) / ((mp + NB) * 8)) / 256 * 256;
+  if (rows > 16384) rows = 16384;
+  if (rows < 1024) rows = 1024;
+  return rows;
+}
+
+// k-slabs of a panel's product: a function of (mp, rows) only.  From 256 lower 128-tiles on (the CU count) one product
+// fills the chip: ONE slab, accumulated straight into S.  Below that, the fewest slabs that bring the launch to 1024 tiles
+// (two rounds of the 512 resident workgroups, from where on the tile GEMM keeps its 128 x 128 tiles), at most 16, never
+// slabs of fewer than 512 rows.  Measured (profiles/r11_exp_sparse_first_rule.log; ms at 1 / 2 / 4 / 8 / 16 / 32 slabs): m = 256 (6 tiles) 4.92 / 3.07 / 2.21 /
+// 1.70 / 1.71 / 1.96, m = 1024 (45 tiles) 9.98 / 9.42 / 9.19 / 7.72 / 7.40 / 8.62, m = 4096 (561 tiles) 96.7 / 125.4 / 129.0 /
+// 147.4 / 167.1 / 203.7 - there every slab is a pass over a 143 MB partial matrix and buys nothing.  Option "sparse_slabs"
+// overrides (1 .. 64).
+int sparse_slabs_for(gpk_handle h, int64_t mp, int64_t rows) {
+  if (h->sparse_slabs > 0) return h->sparse_slabs < SP_MAX_SLABS ? h->sparse_slabs : SP_MAX_SLABS;
+  const int64_t T = mp / NB + 1, tiles = T * (T + 1) / 2;
+  if (tiles >= 256) return 1;
+  int64_t s = (1024 + tiles - 1) / tiles;
+  if (s > 16) s = 16;
+  if (s > rows / 512) s = rows / 512;
+  return s < 1 ? 1 : (int)s;
+}
+
+struct PanelPlan { int slabs; int64_t slab_rows, rows_p; };
+PanelPlan plan_panel(gpk_handle h, int64_t mp, int64_t rows) {
+  PanelPlan p;
+  p.slabs = sparse_slabs_for(h, mp, rows);
+  p.slab_rows = round_up((rows + p.slabs - 1) / p.slabs, SP_TS);
+  p.rows_p = p.slab_rows * p.slabs;
+  return p;
+}
+
+// S (nt x ld, nt = mp + 128; symmetric on entry and on return) += F^T F over the n rows of X / Yn, panel by panel.
+int accumulate(gpk_handle h, const double* X, const double* Yn, int64_t n, const double* Z, int64_t m, int D, int P,
+               const double* ls, double sf2, double* S, int64_t ld) {
+  const int64_t mp = gpk_padded(m), nt = mp + NB;
+  SpLs l;
+  for (int d = 0; d < D; ++d) {
+    GPK_REQUIRE(h, ls[d] > 0.0 && std::isfinite(ls[d]), "sparse: length-scales must be positive");
+    l.v[d] = ls[d];
+  }
+  const int64_t panel = sparse_panel_for(h, mp);
+  // the work area: F for the largest panel and the partial products of the launch with the most slabs
+  int64_t f_rows = 0, max_slabs = 0;
+  const int64_t last = n - (n - 1) / panel * panel;       // rows of the last panel; the others are full
+  for (const int64_t rows : {n < panel ? n : panel, last}) {
+    const PanelPlan p = plan_panel(h, mp, rows);
+    if (p.rows_p > f_rows) f_rows = p.rows_p;
+    if (p.slabs > 1 && p.slabs > max_slabs) max_slabs = p.slabs;
+  }
+  void* ws = nullptr;
+  GPK_TRY(gpk_scratch(h, ((size_t)f_rows * nt + (size_t)max_slabs * nt * nt) * sizeof(double), &ws));
+  double* F = (double*)ws;
+  double* partial = F + (size_t)f_rows * nt;
+  const unsigned nb32 = (unsigned)(nt / 32);
+  const unsigned red_blocks = nb32 * (nb32 + 1) / 2;
+  bool direct = false;
+  for (int64_t r0 = 0; r0 < n; r0 += panel) {
+    const int64_t nr = n - r0 < panel ? n - r0 : panel;
+    const PanelPlan p = plan_panel(h, mp, nr);
+    hipLaunchKernelGGL(sparse_panel_kernel, dim3((unsigned)(nt / SP_TS), (unsigned)(p.rows_p / SP_TS)), dim3(256), 0,
+                       h->stream, X + r0 * D, Yn + r0 * P, (long long)nr, Z, (int)m, D, P, l, sf2, F, (long long)nt,
+                       (int)mp);
+    GPK_LAUNCH_CHECK(h);
+    if (p.slabs > 1) {
+      GemmArgs g = gemm_args(F, nt, 1, F, nt, 1, partial, nt, (int)nt, (int)nt, (int)p.slab_rows, 1.0, 0.0);
+      g.lower_only = 1;
+      g.nbatch = p.slabs;
+      g.sA = g.sB = (long long)p.slab_rows * nt * 8;
+      g.sC = (long long)nt * nt * 8;
+      GPK_TRY(gpk_gemm(h, GPK_F64, g));
+      hipLaunchKernelGGL(sparse_reduce_kernel, dim3(red_blocks), dim3(256), 0, h->stream, S, (long long)ld, partial,
+                         p.slabs, (long long)nt * nt, (int)nt);
+      GPK_LAUNCH_CHECK(h);
+    } else {
+      GemmArgs g = gemm_args(F, nt, 1, F, nt, 1, S, ld, (int)nt, (int)nt, (int)p.slab_rows, 1.0, 1.0);
+      g.lower_only = 1;
+      GPK_TRY(gpk_gemm(h, GPK_F64, g));
+      direct = true;
+    }
+  }
+  if (direct) {
+    hipLaunchKernelGGL(sparse_reduce_kernel, dim3(red_blocks), dim3(256), 0, h->stream, S, (long long)ld, partial, 0,
+                       (long long)nt * nt, (int)nt);
+    GPK_LAUNCH_CHECK(h);
+  }
+  return GPK_OK;
+}
+
+}  // namespace
+
+// ---- the object behind the handle ---------------------------------------------------------------------------------
+struct gpk_sparse {
+  int64_t m = 0, mp = 0, nt = 0, n_rows = 0;
+  int D = 0, P = 0, n_ls = 0;
+  double sf2 = 1.0, noise = 0.0, jitter = 0.0, jitter_uu = 0.0, sigma2 = 0.0, bound = 0.0;
+  double ls[GPK_MAX_D_PREDICT] = {0}, ls_in[GPK_MAX_D_PREDICT] = {0}, y_mean[GPK_MAX_P] = {0}, y_std[GPK_MAX_P] = {0};
+  bool finalized = false;
+  // Z (m x D); S (nt x nt) the statistics; Kuu -> Luu, Wuu = Luu^-1, A1 = Wuu G, Bm = B -> LB, WB = LB^-1, WS = WB Wuu
+  // (mp x mp each); winv (mp x 128); T: the scratch of gpk_trtri; pan: four (mp x 128) right-hand-side panels;
+  // r, c, alpha (m x P): Wuu g / sigma^2, B^-1 r, alpha_u
+  double *Z = nullptr, *S = nullptr, *Kuu = nullptr, *Wuu = nullptr, *A1 = nullptr, *Bm = nullptr, *WB = nullptr,
+         *WS = nullptr, *winv = nullptr, *T = nullptr, *pan = nullptr, *r = nullptr, *c = nullptr, *alpha = nullptr;
+  // staging of gpk_sparse_update (rows) and of gpk_sparse_predict's panel path
+  void *rows = nullptr, *q = nullptr, *work = nullptr;
+  size_t rows_bytes = 0, q_bytes = 0, work_bytes = 0;
+};
+
+namespace {
+
+void sfree_all(gpk_sparse* s) {
+  void* ptrs[] = {s->Z, s->S, s->Kuu, s->Wuu, s->A1, s->Bm, s->WB, s->WS, s->winv, s->T, s->pan, s->r, s->c, s->alpha,
+                  s->rows, s->q, s->work};
+  for (void* p : ptrs)
+    if (p) (void)hipFree(p);
+}
+
+int dev_alloc(gpk_handle h, double** p, size_t count) {
+  GPK_CHECK_HIP(h, hipMalloc((void**)p, count * sizeof(double)));
+  if (h->debug_fill) GPK_CHECK_HIP(h, hipMemsetAsync(*p, 0xFF, count * sizeof(double), h->stream));
+  return GPK_OK;
+}
+
+int grow(gpk_handle h, void** p, size_t* have, size_t need) {
+  if (need > *have) {
+    GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
+    if (*p) GPK_CHECK_HIP(h, hipFree(*p));
+    *p = nullptr; *have = 0;
+    GPK_CHECK_HIP(h, hipMalloc(p, need));
+    *have = need;
+  }
+  if (h->debug_fill && need) GPK_CHECK_HIP(h, hipMemsetAsync(*p, 0xFF, need, h->stream));
+  return GPK_OK;
+}
+
+int sparse_new(gpk_handle h, const double* Z, int64_t m, int D, int P, const double* ls, int n_ls, double sf2, double noise,
+               double jitter, double jitter_uu, const double* y_mean, const double* y_std, gpk_sparse** out) {
+  GPK_REQUIRE(h, Z && ls && y_mean && y_std, "sparse_begin: null pointer");
+  GPK_REQUIRE(h, m >= 1 && m <= SP_MAX_M, "sparse_begin: 1 <= m <= 16384 inducing inputs");
+  GPK_REQUIRE(h, D >= 1 && D <= GPK_MAX_D_PREDICT && P >= 1 && P <= GPK_MAX_P, "sparse_begin: need 1 <= D <= 16, 1 <= P <= GPK_MAX_P");
+  GPK_REQUIRE(h, n_ls == 1 || n_ls == D, "sparse_begin: n_ls must be 1 (isotropic) or D (ARD)");
+  GPK_REQUIRE(h, sf2 > 0.0 && std::isfinite(sf2) && noise >= 0.0 && jitter >= 0.0 && jitter_uu >= 0.0 &&
+                     std::isfinite(noise + jitter + jitter_uu),
+              "sparse_begin: sf2 must be positive, noise and the jitters non-negative");
+  GPK_REQUIRE(h, noise + jitter > 0.0, "sparse_begin: the noise sigma^2 = noise + jitter must be positive");
+  for (int d = 0; d < n_ls; ++d) GPK_REQUIRE(h, ls[d] > 0.0 && std::isfinite(ls[d]), "sparse_begin: length-scales must be positive");
+  for (int p = 0; p < P; ++p)
+    GPK_REQUIRE(h, std::isfinite(y_mean[p]) && y_std[p] > 0.0 && std::isfinite(y_std[p]), "sparse_begin: y_std must be positive");
+  for (int64_t i = 0; i < m * D; ++i) GPK_REQUIRE(h, std::isfinite(Z[i]), "sparse_begin: Z contains NaN or infinity");
+  GPK_REQUIRE(h, h->batch == 1, "composite calls are not available in batched mode");
+  GPK_CHECK_HIP(h, hipSetDevice(h->device));
+  GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
+  if (h->sparse) { sfree_all(h->sparse); delete h->sparse; h->sparse = nullptr; }
+  gpk_sparse* s = new gpk_sparse();
+  h->sparse = s;
+  s->m = m; s->mp = gpk_padded(m); s->nt = s->mp + NB; s->D = D; s->P = P; s->n_ls = n_ls;
+  s->sf2 = sf2; s->noise = noise; s->jitter = jitter; s->jitter_uu = jitter_uu; s->sigma2 = noise + jitter;
+  for (int d = 0; d < D; ++d) s->ls[d] = ls[n_ls == 1 ? 0 : d];
+  for (int d = 0; d < n_ls; ++d) s->ls_in[d] = ls[d];
+  for (int p = 0; p < P; ++p) { s->y_mean[p] = y_mean[p]; s->y_std[p] = y_std[p]; }
+  const size_t mm = (size_t)s->mp * s->mp;
+  GPK_TRY(dev_alloc(h, &s->Z, (size_t)m * D));
+  GPK_TRY(dev_alloc(h, &s->S, (size_t)s->nt * s->nt));
+  GPK_TRY(dev_alloc(h, &s->Kuu, mm));
+  GPK_TRY(dev_alloc(h, &s->Wuu, mm));
+  GPK_TRY(dev_alloc(h, &s->A1, mm));
+  GPK_TRY(dev_alloc(h, &s->Bm, mm));
+  GPK_TRY(dev_alloc(h, &s->WB, mm));
+  GPK_TRY(dev_alloc(h, &s->WS, mm));
+  GPK_TRY(dev_alloc(h, &s->winv, (size_t)s->mp * NB));
+  GPK_TRY(dev_alloc(h, &s->T, (size_t)(s->mp / 2 + NB) * (s->mp / 2 + NB)));
+  GPK_TRY(dev_alloc(h, &s->pan, (size_t)4 * s->mp * NB));
+  GPK_TRY(dev_alloc(h, &s->r, (size_t)m * P));
+  GPK_TRY(dev_alloc(h, &s->c, (size_t)m * P));
+  GPK_TRY(dev_alloc(h, &s->alpha, (size_t)m * P));
+  GPK_CHECK_HIP(h, hipMemcpyAsync(s->Z, Z, (size_t)m * D * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  GPK_CHECK_HIP(h, hipMemsetAsync(s->S, 0, (size_t)s->nt * s->nt * sizeof(double), h->stream));
+  GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
+  *out = s;
+  return GPK_OK;
+}
+
+}  // namespace
+
+void gpk_sparse_free(gpk_handle h) {
+  if (h->sparse) { sfree_all(h->sparse); delete h->sparse; h->sparse = nullptr; }
+}
+
+extern "C" int gpk_sparse_accumulate(gpk_handle h, const double* X, const double* Yn, int64_t n, const double* Z, int64_t m,
+                                     int D, int P, const double* ls, double sf2, double* S, int64_t ld) {
+  if (!h) return GPK_BAD_ARG;
+  GPK_REQUIRE(h, X && Yn && Z && ls && S, "sparse_accumulate: null pointer");
+  GPK_REQUIRE(h, n >= 1 && n < (1ll << 40) && m >= 1 && m <= SP_MAX_M, "sparse_accumulate: need n >= 1, 1 <= m <= 16384");
+  GPK_REQUIRE(h, D >= 1 && D <= GPK_MAX_D_PREDICT && P >= 1 && P <= GPK_MAX_P, "sparse_accumulate: need 1 <= D <= 16, 1 <= P <= GPK_MAX_P");
+  GPK_REQUIRE(h, ld >= gpk_padded(m) + NB && ld % 2 == 0 && ((uintptr_t)S % 16) == 0,
+              "sparse_accumulate: S must be 16-byte aligned with an even ld >= gpk_padded(m) + 128");
+  GPK_REQUIRE(h, sf2 > 0.0 && std::isfinite(sf2), "sparse_accumulate: sf2 must be positive");
+  GPK_REQUIRE(h, h->batch == 1, "sparse_accumulate: not available in batched mode");
+  return accumulate(h, X, Yn, n, Z, m, D, P, ls, sf2, S, ld);
+}
+
+extern "C" int gpk_sparse_begin(gpk_handle h, const double* Z, int64_t m, int D, int P, const double* ls, int n_ls, double sf2,
+                                double noise, double jitter, double jitter_uu, const double* y_mean, const double* y_std) {
+  if (!h) return GPK_BAD_ARG;
+  gpk_sparse* s = nullptr;
+  return sparse_new(h, Z, m, D, P, ls, n_ls, sf2, noise, jitter, jitter_uu, y_mean, y_std, &s);
+}
+
+extern "C" int gpk_sparse_update(gpk_handle h, const double* X, const double* Y, int64_t n) {
+  if (!h) return GPK_BAD_ARG;
+  gpk_sparse* s = h->sparse;
+  GPK_REQUIRE(h, s, "sparse_update: no sparse model (call gpk_sparse_begin first)");
+  GPK_REQUIRE(h, X && Y && n >= 1, "sparse_update: null pointer or no rows");
+  GPK_REQUIRE(h, h->batch == 1, "composite calls are not available in batched mode");
+  const int D = s->D, P = s->P;
+  for (int64_t i = 0; i < n * D; ++i) GPK_REQUIRE(h, std::isfinite(X[i]), "sparse_update: X contains NaN or infinity");
+  for (int64_t i = 0; i < n * P; ++i) GPK_REQUIRE(h, std::isfinite(Y[i]), "sparse_update: Y contains NaN or infinity");
+  GPK_CHECK_HIP(h, hipSetDevice(h->device));
+  // the normalisation is the object's, fixed at gpk_sparse_begin: only then are the statistics additive
+  std::vector<double> yn((size_t)n * P);
+  for (int64_t i = 0; i < n; ++i)
+    for (int p = 0; p < P; ++p) yn[(size_t)i * P + p] = (Y[i * P + p] - s->y_mean[p]) / s->y_std[p];
+  GPK_TRY(grow(h, &s->rows, &s->rows_bytes, (size_t)n * (D + P) * sizeof(double)));
+  double* dX = (double*)s->rows;
+  double* dY = dX + (size_t)n * D;
+  GPK_CHECK_HIP(h, hipMemcpyAsync(dX, X, (size_t)n * D * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  GPK_CHECK_HIP(h, hipMemcpyAsync(dY, yn.data(), (size_t)n * P * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  s->finalized = false;
+  int rc = accumulate(h, dX, dY, n, s->Z, s->m, D, P, s->ls, s->sf2, s->S, s->nt);
+  if (hipStreamSynchronize(h->stream) != hipSuccess && rc == GPK_OK) {     // (yn leaves scope)
+    h->err = "sparse_update: the statistics pass failed";
+    rc = GPK_HIP_ERROR;
+  }
+  GPK_TRY(rc);
+  s->n_rows += n;
+  return GPK_OK;
+}
+
+extern "C" int gpk_sparse_finalize(gpk_handle h, int* info) {
+  if (!h) return GPK_BAD_ARG;
+  gpk_sparse* s = h->sparse;
+  GPK_REQUIRE(h, s, "sparse_finalize: no sparse model (call gpk_sparse_begin first)");
+  GPK_REQUIRE(h, info, "sparse_finalize: null pointer");
+  GPK_REQUIRE(h, h->batch == 1, "composite calls are not available in batched mode");
+  GPK_CHECK_HIP(h, hipSetDevice(h->device));
+  const int64_t mp = s->mp;
+  const int imp = (int)mp, P = s->P;
+  const double is2 = 1.0 / s->sigma2;
+  *info = 0;
+  s->finalized = false;
+  // Luu Luu^T = Kuu + jitter_uu I (identity in the padding), Wuu = Luu^-1
+  GPK_TRY(gpk_gram(h, GPK_F64, s->Z, s->m, s->D, s->ls, s->sf2, s->jitter_uu, s->Kuu, mp));
+  int rc = gpk_potrf(h, s->Kuu, mp, mp, s->winv, info);
+  if (rc == GPK_NOT_PD) h->err = "sparse_finalize: Kuu + jitter_uu I is not positive definite; " + h->err;
+  GPK_TRY(rc);
+  GPK_TRY(gpk_trtri(h, s->Kuu, mp, mp, s->winv, s->Wuu, mp, s->T));
+  // A1 = Wuu G (Wuu lower: k < row-tile end), B = I + A1 Wuu^T / sigma^2 (k < column-tile end; every tile, so that the
+  // factorisation finds whole diagonal tiles).  G is zero in the padding, so B is the identity there.
+  {
+    GemmArgs g = gemm_args(s->Wuu, mp, 0, s->S, s->nt, 1, s->A1, mp, imp, imp, imp, 1.0, 0.0);
+    g.ke0 = NB; g.ke_row = NB; g.heavy_first = 1;
+    GPK_TRY(gpk_gemm(h, GPK_F64, g));
+  }
+  {
+    GemmArgs g = gemm_args(s->A1, mp, 0, s->Wuu, mp, 0, s->Bm, mp, imp, imp, imp, is2, 0.0);
+    g.ke0 = NB; g.ke_col = NB;
+    GPK_TRY(gpk_gemm(h, GPK_F64, g));
+  }
+  double* d_out = h->d_small + 400;     // [tr(B) - mp, yy[0 .. P)]: free doubles of the pinned block (gpk_internal.h)
+  hipLaunchKernelGGL(sparse_diag_kernel, dim3(1), dim3(256), 0, h->stream, s->Bm, (long long)mp, imp, s->S, (long long)s->nt,
+                     P, d_out);
+  GPK_LAUNCH_CHECK(h);
+  rc = gpk_potrf(h, s->Bm, mp, mp, s->winv, info);      // LB LB^T = B
+  if (rc == GPK_NOT_PD) h->err = "sparse_finalize: B = I + Wuu G Wuu^T / sigma^2 is not positive definite; " + h->err;
+  GPK_TRY(rc);
+  const double tr_a = h->h_small[400];
+  double yy[GPK_MAX_P];
+  for (int p = 0; p < P; ++p) yy[p] = h->h_small[401 + p];
+  GPK_TRY(gpk_trtri(h, s->Bm, mp, mp, s->winv, s->WB, mp, s->T));
+  // WSigma = LB^-1 Wuu: lower tiles (column-tile start <= k < row-tile end) of a zeroed matrix - the inverse-factor layout
+  // of gpk_predict_var_inv (lower tiles, zeros right of the diagonal)
+  GPK_CHECK_HIP(h, hipMemsetAsync(s->WS, 0, (size_t)mp * mp * sizeof(double), h->stream));
+  {
+    GemmArgs g = gemm_args(s->WB, mp, 0, s->Wuu, mp, 1, s->WS, mp, imp, imp, imp, 1.0, 0.0);
+    g.kb_col = NB; g.ke0 = NB; g.ke_row = NB; g.lower_only = 1;
+    GPK_TRY(gpk_gemm(h, GPK_F64, g));
+  }
+  // r = Wuu g / sigma^2, c = B^-1 r = WB^T (WB r), alpha_u = Wuu^T c: four products on 128-column panels (the targets'
+  // columns of S are g, zero beyond P)
+  double *Rp = s->pan, *Cz = Rp + (size_t)mp * NB, *Cp = Cz + (size_t)mp * NB, *Ap = Cp + (size_t)mp * NB;
+  {
+    GemmArgs g = gemm_args(s->Wuu, mp, 0, s->S + mp, s->nt, 1, Rp, NB, imp, NB, imp, is2, 0.0);
+    g.ke0 = NB; g.ke_row = NB; g.heavy_first = 1;
+    GPK_TRY(gpk_gemm(h, GPK_F64, g));
+    GemmArgs g2 = gemm_args(s->WB, mp, 0, Rp, NB, 1, Cz, NB, imp, NB, imp, 1.0, 0.0);
+    g2.ke0 = NB; g2.ke_row = NB; g2.heavy_first = 1;
+    GPK_TRY(gpk_gemm(h, GPK_F64, g2));
+    GemmArgs g3 = gemm_args(s->WB, mp, 1, Cz, NB, 1, Cp, NB, imp, NB, imp, 1.0, 0.0);
+    g3.kb_row = NB;
+    GPK_TRY(gpk_gemm(h, GPK_F64, g3));
+    GemmArgs g4 = gemm_args(s->Wuu, mp, 1, Cp, NB, 1, Ap, NB, imp, NB, imp, 1.0, 0.0);
+    g4.kb_row = NB;
+    GPK_TRY(gpk_gemm(h, GPK_F64, g4));
+  }
+  const long long tot = (long long)s->m * P;
+  hipLaunchKernelGGL(sparse_unpack_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, Rp, Cp, Ap,
+                     (long long)s->m, P, s->r, s->c, s->alpha);
+  GPK_LAUNCH_CHECK(h);
+  // terms[0] = sum log diag LB, terms[1 + p] = r_p^T B^-1 r_p (synchronises)
+  double terms[1 + GPK_MAX_P];
+  GPK_TRY(gpk_lml_terms(h, s->Bm, s->m, mp, s->r, s->c, P, terms));
+  const double N = (double)s->n_rows, s2 = s->sigma2;
+  double bound = 0.0;
+  for (int p = 0; p < P; ++p)
+    bound += -0.5 * N * std::log(2.0 * M_PI * s2) - terms[0] - 0.5 * (N * s->sf2 - s2 * tr_a) / s2 - 0.5 * yy[p] / s2 +
+             0.5 * terms[1 + p];
+  s->bound = bound;
+  s->finalized = true;
+  return GPK_OK;
+}
+
+extern "C" int gpk_sparse_bound(gpk_handle h, double* bound, int64_t* n_rows) {
+  if (!h) return GPK_BAD_ARG;
+  gpk_sparse* s = h->sparse;
+  GPK_REQUIRE(h, s && s->finalized, "sparse_bound: no finalised sparse model (call gpk_sparse_finalize first)");
+  if (bound) *bound = s->bound;
+  if (n_rows) *n_rows = s->n_rows;
+  return GPK_OK;
+}
+
+extern "C" int gpk_sparse_predict(gpk_handle h, const double* Xq, int64_t M, double* mean, double* var,
+                                  int var_includes_noise) {
+  if (!h) return GPK_BAD_ARG;
+  gpk_sparse* s = h->sparse;
+  GPK_REQUIRE(h, s && s->finalized, "sparse_predict: no finalised sparse model (call gpk_sparse_finalize first)");
+  GPK_REQUIRE(h, Xq && mean && M >= 1, "sparse_predict: null pointer or empty batch");
+  GPK_REQUIRE(h, h->batch == 1, "composite calls are not available in batched mode");
+  GPK_CHECK_HIP(h, hipSetDevice(h->device));
+  const int D = s->D, P = s->P;
+  for (int64_t i = 0; i < M * D; ++i) GPK_REQUIRE(h, std::isfinite(Xq[i]), "sparse_predict: Xq contains NaN or infinity");
+  // as gpk_predict: k** = sf2 + the WhiteKernel level, clipped at 0 - or sf2, floored at 1e-10
+  const double kss = s->sf2 + (var_includes_noise ? s->noise : 0.0), floor_ = var_includes_noise ? 0.0 : 1e-10;
+  const double none = -std::numeric_limits<double>::max();
+  const int64_t m = s->m, mp = s->mp;
+  if (h->small_path && M <= GPK_SMALL_MAX_M && gpk_small_ok(mp, D, P, M)) {
+    if (P == 1) {
+      // two "models" on the shared inputs Z, one call: two launches, one synchronisation
+      const double *Xs[2] = {s->Z, s->Z}, *as[2] = {s->alpha, s->alpha}, *Ws[2] = {s->Wuu, s->WS};
+      double ls2[2 * GPK_MAX_D_PREDICT];
+      for (int d = 0; d < D; ++d) ls2[d] = ls2[D + d] = s->ls[d];
+      const double sf2s[2] = {s->sf2, s->sf2}, ym[2] = {s->y_mean[0], 0.0}, ys[2] = {s->y_std[0], 1.0}, ks[2] = {kss, 0.0};
+      std::vector<double> mb((size_t)2 * M), vb(var ? (size_t)2 * M : 0);
+      GPK_TRY(gpk_predict_host_multi(h, 2, Xs, as, m, D, ls2, sf2s, ym, ys, var ? Ws : nullptr, mp, mp, var ? ks : nullptr,
+                                     none, Xq, M, mb.data(), var ? vb.data() : nullptr));
+      for (int64_t i = 0; i < M; ++i) {
+        mean[i] = mb[(size_t)i];
+        if (var) var[i] = std::fmax(vb[(size_t)i] - vb[(size_t)(M + i)], floor_) * s->y_std[0] * s->y_std[0];
+      }
+      return GPK_OK;
+    }
+    // several outputs share the two inverse factors: the one-model entry twice (four launches)
+    std::vector<double> v0(var ? (size_t)M : 0), v1(var ? (size_t)M : 0), m2(var ? (size_t)M * P : 0);
+    GPK_TRY(gpk_predict_host(h, s->Z, s->alpha, m, D, P, s->ls, s->sf2, s->y_mean, s->y_std, var ? s->Wuu : nullptr, mp, mp, kss,
+                             none, Xq, M, mean, var ? v0.data() : nullptr));
+    if (var) {
+      GPK_TRY(gpk_predict_host(h, s->Z, s->alpha, m, D, P, s->ls, s->sf2, s->y_mean, s->y_std, s->WS, mp, mp, 0.0, none, Xq, M,
+                               m2.data(), v1.data()));
+      for (int64_t i = 0; i < M; ++i)
+        for (int p = 0; p < P; ++p)
+          var[i * P + p] = std::fmax(v0[(size_t)i] - v1[(size_t)i], floor_) * s->y_std[p] * s->y_std[p];
+    }
+    return GPK_OK;
+  }
+  // query panels: the fused mean and two variance launches (one per inverse factor), combined on the device
+  int64_t panel = GPK_HOST_MAX_M;
+  if (panel > gpk_padded(M)) panel = gpk_padded(M);
+  const size_t nq = (size_t)panel * D, nm = (size_t)panel * P;
+  GPK_TRY(grow(h, &s->q, &s->q_bytes, (nq + nm + (var ? 2 * (size_t)panel + nm : 0)) * sizeof(double)));
+  if (var) GPK_TRY(grow(h, &s->work, &s->work_bytes, (size_t)mp * panel * sizeof(double)));
+  double *dq = (double*)s->q, *dmean = dq + nq, *dv0 = dmean + nm, *dv1 = dv0 + panel, *dvar = dv1 + panel;
+  SpP ys;
+  for (int p = 0; p < GPK_MAX_P; ++p) ys.v[p] = p < P ? s->y_std[p] : 1.0;
+  for (int64_t m0 = 0; m0 < M; m0 += panel) {
+    const int64_t mc = M - m0 < panel ? M - m0 : panel;
+    GPK_CHECK_HIP(h, hipMemcpyAsync(dq, Xq + m0 * D, (size_t)mc * D * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    GPK_TRY(gpk_predict_mean(h, GPK_F64, s->Z, s->alpha, m, D, P, s->ls, s->sf2, s->y_mean, s->y_std, dq, mc, dmean));
+    GPK_CHECK_HIP(h, hipMemcpyAsync(mean + m0 * P, dmean, (size_t)mc * P * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (var) {
+      GPK_TRY(gpk_predict_var_inv(h, GPK_F64, s->Z, m, D, s->ls, s->sf2, s->Wuu, mp, mp, dq, mc, kss, none, s->work, dv0));
+      GPK_TRY(gpk_predict_var_inv(h, GPK_F64, s->Z, m, D, s->ls, s->sf2, s->WS, mp, mp, dq, mc, 0.0, none, s->work, dv1));
+      const long long tot = (long long)mc * P;
+      hipLaunchKernelGGL(sparse_var_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, dv0, dv1,
+                         (long long)mc, P, ys, floor_, dvar);
+      GPK_LAUNCH_CHECK(h);
+      GPK_CHECK_HIP(h, hipMemcpyAsync(var + m0 * P, dvar, (size_t)mc * P * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    }
+    GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));      // the staging block is reused by the next panel
+  }
+  return GPK_OK;
+}
+
+extern "C" int gpk_sparse_export(gpk_handle h, int64_t* m, int* D, int* P, int* n_ls, double* Z, double* G, double* g, double* yy,
+                                 int64_t* n_rows, double* ls, double* hyper, double* y_mean, double* y_std) {
+  if (!h) return GPK_BAD_ARG;
+  gpk_sparse* s = h->sparse;
+  GPK_REQUIRE(h, s, "sparse_export: no sparse model");
+  GPK_CHECK_HIP(h, hipSetDevice(h->device));
+  if (m) *m = s->m;
+  if (D) *D = s->D;
+  if (P) *P = s->P;
+  if (n_ls) *n_ls = s->n_ls;
+  if (n_rows) *n_rows = s->n_rows;
+  if (ls) for (int d = 0; d < s->n_ls; ++d) ls[d] = s->ls_in[d];
+  if (hyper) { hyper[0] = s->sf2; hyper[1] = s->noise; hyper[2] = s->jitter; hyper[3] = s->jitter_uu; }
+  for (int p = 0; p < s->P; ++p) {
+    if (y_mean) y_mean[p] = s->y_mean[p];
+    if (y_std) y_std[p] = s->y_std[p];
+  }
+  const size_t pitch = (size_t)s->nt * sizeof(double), mrow = (size_t)s->m * sizeof(double);
+  if (Z) GPK_CHECK_HIP(h, hipMemcpyAsync(Z, s->Z, (size_t)s->m * s->D * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (G) GPK_CHECK_HIP(h, hipMemcpy2DAsync(G, mrow, s->S, pitch, mrow, (size_t)s->m, hipMemcpyDeviceToHost, h->stream));
+  std::vector<double> gt, yt;
+  if (g) {      // rows mp .. mp + P - 1 of S hold g^T
+    gt.resize((size_t)s->P * s->m);
+    GPK_CHECK_HIP(h, hipMemcpy2DAsync(gt.data(), mrow, s->S + (size_t)s->mp * s->nt, pitch, mrow, (size_t)s->P,
+                                      hipMemcpyDeviceToHost, h->stream));
+  }
+  if (yy) {
+    yt.resize((size_t)s->P);
+    GPK_CHECK_HIP(h, hipMemcpy2DAsync(yt.data(), sizeof(double), s->S + (size_t)s->mp * s->nt + s->mp, pitch + sizeof(double),
+                                      sizeof(double), (size_t)s->P, hipMemcpyDeviceToHost, h->stream));
+  }
+  GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
+  if (g)
+    for (int64_t j = 0; j < s->m; ++j)
+      for (int p = 0; p < s->P; ++p) g[j * s->P + p] = gt[(size_t)p * s->m + j];
+  if (yy) for (int p = 0; p < s->P; ++p) yy[p] = yt[(size_t)p];
+  return GPK_OK;
+}
+
+extern "C" int gpk_sparse_import(gpk_handle h, const double* Z, int64_t m, int D, int P, const double* ls, int n_ls, double sf2,
+                                 double noise, double jitter, double jitter_uu, const double* y_mean, const double* y_std,
+                                 const double* G, const double* g, const double* yy, int64_t n_rows) {
+  if (!h) return GPK_BAD_ARG;
+  GPK_REQUIRE(h, G && g && yy && n_rows >= 0, "sparse_import: null pointer or negative row count");
+  if (m >= 1 && m <= SP_MAX_M && P >= 1 && P <= GPK_MAX_P) {
+    for (int64_t i = 0; i < m * m; ++i) GPK_REQUIRE(h, std::isfinite(G[i]), "sparse_import: G contains NaN or infinity");
+    for (int64_t i = 0; i < m * P; ++i) GPK_REQUIRE(h, std::isfinite(g[i]), "sparse_import: g contains NaN or infinity");
+    for (int p = 0; p < P; ++p) GPK_REQUIRE(h, std::isfinite(yy[p]), "sparse_import: yy contains NaN or infinity");
+  }
+  gpk_sparse* s = nullptr;
+  GPK_TRY(sparse_new(h, Z, m, D, P, ls, n_ls, sf2, noise, jitter, jitter_uu, y_mean, y_std, &s));
+  // S (zeroed by sparse_new): G, then g as the targets' rows and columns, yy on their diagonal (the cross moments of
+  // different outputs are not part of the model: they stay zero)
+  const size_t pitch = (size_t)s->nt * sizeof(double), mrow = (size_t)m * sizeof(double);
+  std::vector<double> gt((size_t)P * m);
+  for (int64_t j = 0; j < m; ++j)
+    for (int p = 0; p < P; ++p) gt[(size_t)p * m + j] = g[j * P + p];
+  GPK_CHECK_HIP(h, hipMemcpy2DAsync(s->S, pitch, G, mrow, mrow, (size_t)m, hipMemcpyHostToDevice, h->stream));
+  GPK_CHECK_HIP(h, hipMemcpy2DAsync(s->S + (size_t)s->mp * s->nt, pitch, gt.data(), mrow, mrow, (size_t)P, hipMemcpyHostToDevice,
+                                    h->stream));
+  GPK_CHECK_HIP(h, hipMemcpy2DAsync(s->S + s->mp, pitch, g, (size_t)P * sizeof(double), (size_t)P * sizeof(double), (size_t)m,
+                                    hipMemcpyHostToDevice, h->stream));
+  GPK_CHECK_HIP(h, hipMemcpy2DAsync(s->S + (size_t)s->mp * s->nt + s->mp, pitch + sizeof(double), yy, sizeof(double),
+                                    sizeof(double), (size_t)P, hipMemcpyHostToDevice, h->stream));
+  GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
+  s->n_rows = n_rows;
+  return GPK_OK;
+}

@@ -1,0 +1,243 @@
+"""Sparse inducing-point GP: fit on every row of a flight log, serve through m inducing inputs.
+
+The Titsias / DTC predictor of GPflow's SGPR on this package's kernel `[C *] RBF [+ WhiteKernel]`, shared by all outputs.
+The training rows enter through additive fp64 statistics of size m x m (`gpk_sparse_update`: N m^2 flops on the fp64
+matrix cores), so `partial_fit` appends rows at any time; the model is assembled from them lazily at the next `predict`
+(`gpk_sparse_finalize`: an m x m factorisation) and served at the cost of an exact model of m rows
+(`gpk_sparse_predict`: two launches for up to 32 rows).  Hyper-parameters are not optimised here: they come from an exact
+fit on a subset (`SparseGP.from_exact`), which is what the reference trains anyway.
+
+The class keeps one libgpk handle of its own: the sparse model is the object behind that handle (include/gpk.h), the
+arrays that cross the boundary are host NumPy arrays.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import copy
+
+import numpy as np
+
+from . import _lib
+from .device import Backend, get_backend
+
+_dp = _lib._dp
+
+
+def _ptr(a):
+    return a.ctypes.data_as(_dp)
+
+
+class SparseGP:
+    def __init__(self, kernel, inducing, *, alpha=1e-10, jitter_uu=None, y_mean=None, y_std=None, device=None):
+        self.kernel = kernel
+        self.kernel_ = copy.deepcopy(kernel)
+        comp = self.kernel_.components()          # rejects anything but [C *] RBF [+ WhiteKernel], as gpr.py does
+        Z = np.array(inducing, dtype=np.float64, ndmin=2)
+        if Z.ndim != 2 or Z.shape[0] < 1 or Z.shape[1] < 1:
+            raise ValueError("inducing inputs must be (m, D)")
+        if not np.isfinite(Z).all():
+            raise ValueError("Input contains NaN or infinity")
+        if np.iterable(alpha):
+            raise ValueError("per-sample alpha is not supported by the MI355X path")
+        self.inducing_ = np.ascontiguousarray(Z)
+        self.n_features_in_ = Z.shape[1]
+        comp.ls_vector(self.n_features_in_)       # anisotropic kernels must match the inputs
+        self.alpha = float(alpha)
+        self.jitter_uu = 1e-8 * comp.sf2 if jitter_uu is None else float(jitter_uu)
+        self.y_mean = None if y_mean is None else np.atleast_1d(np.asarray(y_mean, dtype=np.float64)).copy()
+        self.y_std = None if y_std is None else np.atleast_1d(np.asarray(y_std, dtype=np.float64)).copy()
+        self.device = device
+        self._be = None
+        self._live = False          # the object behind the handle exists
+        self._final = False         # ... and is assembled from the current statistics
+        self._P = None
+        self._y_1d = True
+        self._state = None          # statistics waiting to be imported (after unpickling)
+
+    # ------------------------------------------------------------------ construction from an exact model
+    @classmethod
+    def from_exact(cls, gpr, inducing=None, random_state=0, jitter_uu=None):
+        """Kernel, `alpha` and target normalisation of a fitted `GaussianProcessRegressor`; inducing inputs: an array, an
+        integer (that many of its training rows, picked by a seeded permutation) or None (all of them).  The sparse model
+        starts with no rows: `partial_fit` the flight log (the exact model's own rows included, if they are to count)."""
+        if not hasattr(gpr, "X_train_"):
+            raise RuntimeError("This GaussianProcessRegressor instance is not fitted yet.")
+        X = gpr.X_train_
+        if inducing is None:
+            Z = X
+        elif isinstance(inducing, (int, np.integer)):
+            if not 1 <= int(inducing) <= len(X):
+                raise ValueError(f"inducing must be in [1, {len(X)}]")
+            Z = X[np.sort(np.random.default_rng(random_state).permutation(len(X))[:int(inducing)])]
+        else:
+            Z = inducing
+        out = cls(gpr.kernel_, Z, alpha=gpr.alpha, jitter_uu=jitter_uu, y_mean=gpr._y_train_mean, y_std=gpr._y_train_std, device=gpr.device)
+        out._y_1d = bool(getattr(gpr, "_y_1d", True))
+        return out
+
+    # ------------------------------------------------------------------ the object behind the handle
+    def _backend(self):
+        if self._be is None:
+            main = get_backend(self.device)
+            self._be = main if isinstance(self.device, Backend) else Backend(main.device_index)
+        return self._be
+
+    def _hyper(self):
+        comp = self.kernel_.components()
+        ls = np.ascontiguousarray(comp.ls, dtype=np.float64)
+        return comp, ls
+
+    def _begin(self, P):
+        if not 1 <= P <= _lib.GPK_MAX_P:
+            raise ValueError(f"P must be in [1, {_lib.GPK_MAX_P}]")
+        ym = np.zeros(P) if self.y_mean is None else self.y_mean
+        ys = np.ones(P) if self.y_std is None else self.y_std
+        if ym.shape != (P,) or ys.shape != (P,):
+            raise ValueError(f"y_mean / y_std must have {P} entries")
+        self._ym, self._ys = np.ascontiguousarray(ym), np.ascontiguousarray(ys)
+        comp, ls = self._hyper()
+        be = self._backend()
+        Z = self.inducing_
+        with be.lock:
+            be.bind_stream()
+            st = self._state
+            if st is None:
+                be.check(be.lib.gpk_sparse_begin(be.h, _ptr(Z), Z.shape[0], Z.shape[1], P, _ptr(ls), ls.size, comp.sf2,
+                                                 comp.noise or 0.0, self.alpha, self.jitter_uu, _ptr(self._ym), _ptr(self._ys)))
+            else:
+                be.check(be.lib.gpk_sparse_import(be.h, _ptr(Z), Z.shape[0], Z.shape[1], P, _ptr(ls), ls.size, comp.sf2,
+                                                  comp.noise or 0.0, self.alpha, self.jitter_uu, _ptr(self._ym), _ptr(self._ys),
+                                                  _ptr(st["G"]), _ptr(st["g"]), _ptr(st["yy"]), int(st["n_rows"])))
+                self._state = None
+        self._P, self._live, self._final = P, True, False
+
+    def _ensure(self):
+        """The assembled model: created (the prior, if no row was ever given) and finalised."""
+        if not self._live:
+            P = self._P if self._P is not None else (1 if self.y_mean is None else self.y_mean.size)
+            self._begin(P)
+        if not self._final:
+            be = self._backend()
+            info = C.c_int(0)
+            with be.lock:
+                be.bind_stream()
+                be.check(be.lib.gpk_sparse_finalize(be.h, C.byref(info)))      # GPK_NOT_PD raises LinAlgError
+            self._final = True
+
+    # ------------------------------------------------------------------ rows
+    def partial_fit(self, X, y):
+        """Appends the rows X (n, D), y (n,) or (n, P) to the statistics; the model is reassembled at the next predict."""
+        X = np.array(X, dtype=np.float64, ndmin=2)
+        y = np.asarray(y, dtype=np.float64)
+        if X.shape[0] != y.shape[0]:
+            raise ValueError("X and y have inconsistent numbers of samples")
+        if X.shape[1] != self.n_features_in_:
+            raise ValueError(f"X must be (N, {self.n_features_in_})")
+        if not (np.isfinite(X).all() and np.isfinite(y).all()):
+            raise ValueError("Input contains NaN or infinity")
+        y2 = y.reshape(X.shape[0], -1)
+        if self._P is None and self._state is None:
+            self._y_1d = y.ndim == 1
+        if not self._live:
+            self._begin(y2.shape[1] if self._P is None else self._P)
+        if y2.shape[1] != self._P:
+            raise ValueError(f"y must have {self._P} columns")
+        if X.shape[0] == 0:
+            return self
+        X, y2 = np.ascontiguousarray(X), np.ascontiguousarray(y2)
+        be = self._backend()
+        with be.lock:
+            be.bind_stream()
+            be.check(be.lib.gpk_sparse_update(be.h, _ptr(X), _ptr(y2), X.shape[0]))
+        self._final = False
+        return self
+
+    def fit(self, X, y):
+        """Forgets the rows seen so far, then `partial_fit(X, y)`."""
+        self._live, self._final, self._P, self._state = False, False, None, None
+        return self.partial_fit(X, y)
+
+    # ------------------------------------------------------------------ predict
+    def predict(self, X, return_std=False):
+        """Posterior mean (and standard deviation, with the WhiteKernel level as scikit-learn's `predict` has it) at the rows
+        X.  Up to 32 rows: one call, two launches, one synchronisation."""
+        X = np.array(X, dtype=np.float64, ndmin=2)
+        if not np.isfinite(X).all():
+            raise ValueError("Input X contains NaN or infinity.")
+        if X.ndim != 2 or X.shape[1] != self.n_features_in_:
+            raise ValueError(f"queries must be (M, {self.n_features_in_})")
+        self._ensure()
+        M, P = X.shape[0], self._P
+        mean = np.empty((M, P))
+        var = np.empty((M, P)) if return_std else None
+        if M > 0:
+            X = np.ascontiguousarray(X)
+            be = self._backend()
+            with be.lock:
+                be.bind_stream()
+                be.check(be.lib.gpk_sparse_predict(be.h, _ptr(X), M, _ptr(mean), _ptr(var) if return_std else None, 1))
+        squeeze = P == 1 and self._y_1d
+        if not return_std:
+            return mean[:, 0] if squeeze else mean
+        std = np.sqrt(var)
+        return (mean[:, 0], std[:, 0]) if squeeze else (mean, std)
+
+    def bound(self):
+        """The collapsed lower bound on the log-marginal likelihood of the rows seen so far, in normalised-target units (the
+        exact log-marginal likelihood when the inducing inputs are the training inputs)."""
+        self._ensure()
+        be = self._backend()
+        b, n = C.c_double(0.0), C.c_int64(0)
+        with be.lock:
+            be.check(be.lib.gpk_sparse_bound(be.h, C.byref(b), C.byref(n)))
+        return float(b.value)
+
+    @property
+    def n_rows_(self):
+        if self._state is not None:
+            return int(self._state["n_rows"])
+        if not self._live:
+            return 0
+        be = self._backend()
+        n = C.c_int64(0)
+        with be.lock:
+            be.check(be.lib.gpk_sparse_export(be.h, None, None, None, None, None, None, None, None, C.byref(n), None, None,
+                                              None, None))
+        return int(n.value)
+
+    def statistics(self):
+        """The additive statistics as host arrays: {"G" (m, m), "g" (m, P), "yy" (P,), "n_rows"}."""
+        if self._state is not None:
+            return dict(self._state)
+        if not self._live:
+            return None
+        m, P = self.inducing_.shape[0], self._P
+        G, g, yy = np.empty((m, m)), np.empty((m, P)), np.empty(P)
+        n = C.c_int64(0)
+        be = self._backend()
+        with be.lock:
+            be.bind_stream()
+            be.check(be.lib.gpk_sparse_export(be.h, None, None, None, None, None, _ptr(G), _ptr(g), _ptr(yy), C.byref(n), None,
+                                              None, None, None))
+        return {"G": G, "g": g, "yy": yy, "n_rows": int(n.value)}
+
+    # ------------------------------------------------------------------ pickling: Z, the statistics, the hyper-parameters
+    def __getstate__(self):
+        st = self.__dict__.copy()
+        st["_state"] = self.statistics()
+        st["_be"], st["_live"], st["_final"] = None, False, False
+        if isinstance(st["device"], Backend):
+            st["device"] = st["device"].device_index
+        return st
+
+    def __setstate__(self, st):
+        self.__dict__.update(st)
+
+    def __del__(self):
+        be = self.__dict__.get("_be")
+        if be is not None and not isinstance(self.__dict__.get("device"), Backend) and be.h:
+            try:
+                be.lib.gpk_destroy(be.h)
+            except Exception:
+                pass
+            be.h = None
