@@ -11,7 +11,7 @@
 #include "../../include/gpk.h"
 
 struct gpk_model;    // the composite calls' model (gpk_model.hip)
-struct gpk_bmodel;   // B single-output models on shared inputs (gpk_fit_batched, gpk_model.hip)
+struct gpk_bmodel;   // B single-output models on shared inputs (gpk_fit_batched, gpk_bmodel.hip)
 struct gpk_sparse;   // the sparse inducing-point model (gpk_sparse_begin, gpk_sparse.hip)
 
 struct gpk_context {
@@ -128,7 +128,8 @@ constexpr size_t GPK_PTILE_CTRL_INTS = 16 + 8 * 512 + 1024 + 10 * 8 * 512;   // 
 int gpk_potrf_ptile(gpk_handle h, double* A, int64_t Np, int64_t lda, double* winv, int row0, int* used, double* wt = nullptr,
                     double* wband = nullptr, int64_t ldw = 0, int zero_info = 0);
 int gpk_potrf_ptile_check(gpk_handle h, int gave_up = -1);
-void gpk_model_free(gpk_handle h);   // gpk_model.hip
+void gpk_model_free(gpk_handle h);   // gpk_model.hip: all three models of the handle
+void gpk_bmodel_free(gpk_handle h);  // gpk_bmodel.hip
 void gpk_sparse_free(gpk_handle h);  // gpk_sparse.hip
 // the launches of gpk_potrf / gpk_lml_terms / gpk_lml_grad without their synchronisations (gpk_lml_eval)
 int gpk_potrf_enqueue(gpk_handle h, double* A, int64_t Np, int64_t lda, double* winv);

@@ -20,12 +20,11 @@
 // The assembly (gpk_sparse_finalize) and the serving (gpk_sparse_predict) are host code over entries that exist: gpk_gram /
 // gpk_potrf / gpk_trtri, tile GEMMs with triangular k-ranges, gpk_lml_terms, gpk_predict_host_multi (the sparse model is
 // two "models" on the shared inputs Z: (alpha_u, Wuu, kss = sf2) and (any alpha, WSigma, kss = 0)), gpk_predict_mean and
-// gpk_predict_var_inv.  DESIGN.md, K9.
+// gpk_predict_var_inv; the buffers are gpk_dev members of the object and the serving goes through the query-panel loop
+// (gpk_compose.h, shared with gpk_model.hip and gpk_bmodel.hip).  DESIGN.md, K9.
 #include <cfloat>
-#include <cmath>
-#include <limits>
 
-#include "gpk_internal.h"
+#include "gpk_compose.h"
 #include "gpk_math.h"
 
 namespace {
@@ -291,39 +290,13 @@ struct gpk_sparse {
   // Z (m x D); S (nt x nt) the statistics; Kuu -> Luu, Wuu = Luu^-1, A1 = Wuu G, Bm = B -> LB, WB = LB^-1, WS = WB Wuu
   // (mp x mp each); winv (mp x 128); T: the scratch of gpk_trtri; pan: four (mp x 128) right-hand-side panels;
   // r, c, alpha (m x P): Wuu g / sigma^2, B^-1 r, alpha_u
-  double *Z = nullptr, *S = nullptr, *Kuu = nullptr, *Wuu = nullptr, *A1 = nullptr, *Bm = nullptr, *WB = nullptr,
-         *WS = nullptr, *winv = nullptr, *T = nullptr, *pan = nullptr, *r = nullptr, *c = nullptr, *alpha = nullptr;
+  gpk_dev<double> Z, S, Kuu, Wuu, A1, Bm, WB, WS, winv, T, pan, r, c, alpha;
   // staging of gpk_sparse_update (rows) and of gpk_sparse_predict's panel path
-  void *rows = nullptr, *q = nullptr, *work = nullptr;
-  size_t rows_bytes = 0, q_bytes = 0, work_bytes = 0;
+  gpk_dev<double> rows, q;
+  gpk_dev<void> work;
 };
 
 namespace {
-
-void sfree_all(gpk_sparse* s) {
-  void* ptrs[] = {s->Z, s->S, s->Kuu, s->Wuu, s->A1, s->Bm, s->WB, s->WS, s->winv, s->T, s->pan, s->r, s->c, s->alpha,
-                  s->rows, s->q, s->work};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-}
-
-int dev_alloc(gpk_handle h, double** p, size_t count) {
-  GPK_CHECK_HIP(h, hipMalloc((void**)p, count * sizeof(double)));
-  if (h->debug_fill) GPK_CHECK_HIP(h, hipMemsetAsync(*p, 0xFF, count * sizeof(double), h->stream));
-  return GPK_OK;
-}
-
-int grow(gpk_handle h, void** p, size_t* have, size_t need) {
-  if (need > *have) {
-    GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
-    if (*p) GPK_CHECK_HIP(h, hipFree(*p));
-    *p = nullptr; *have = 0;
-    GPK_CHECK_HIP(h, hipMalloc(p, need));
-    *have = need;
-  }
-  if (h->debug_fill && need) GPK_CHECK_HIP(h, hipMemsetAsync(*p, 0xFF, need, h->stream));
-  return GPK_OK;
-}
 
 int sparse_new(gpk_handle h, const double* Z, int64_t m, int D, int P, const double* ls, int n_ls, double sf2, double noise,
                double jitter, double jitter_uu, const double* y_mean, const double* y_std, gpk_sparse** out) {
@@ -338,33 +311,32 @@ int sparse_new(gpk_handle h, const double* Z, int64_t m, int D, int P, const dou
   for (int d = 0; d < n_ls; ++d) GPK_REQUIRE(h, ls[d] > 0.0 && std::isfinite(ls[d]), "sparse_begin: length-scales must be positive");
   for (int p = 0; p < P; ++p)
     GPK_REQUIRE(h, std::isfinite(y_mean[p]) && y_std[p] > 0.0 && std::isfinite(y_std[p]), "sparse_begin: y_std must be positive");
-  for (int64_t i = 0; i < m * D; ++i) GPK_REQUIRE(h, std::isfinite(Z[i]), "sparse_begin: Z contains NaN or infinity");
+  GPK_TRY(gpk_require_finite(h, Z, m * D, "sparse_begin", "Z"));
   GPK_REQUIRE(h, h->batch == 1, "composite calls are not available in batched mode");
   GPK_CHECK_HIP(h, hipSetDevice(h->device));
   GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
-  if (h->sparse) { sfree_all(h->sparse); delete h->sparse; h->sparse = nullptr; }
-  gpk_sparse* s = new gpk_sparse();
-  h->sparse = s;
+  gpk_sparse_free(h);
+  gpk_sparse* s = h->sparse = new gpk_sparse();
   s->m = m; s->mp = gpk_padded(m); s->nt = s->mp + NB; s->D = D; s->P = P; s->n_ls = n_ls;
   s->sf2 = sf2; s->noise = noise; s->jitter = jitter; s->jitter_uu = jitter_uu; s->sigma2 = noise + jitter;
   for (int d = 0; d < D; ++d) s->ls[d] = ls[n_ls == 1 ? 0 : d];
   for (int d = 0; d < n_ls; ++d) s->ls_in[d] = ls[d];
   for (int p = 0; p < P; ++p) { s->y_mean[p] = y_mean[p]; s->y_std[p] = y_std[p]; }
   const size_t mm = (size_t)s->mp * s->mp;
-  GPK_TRY(dev_alloc(h, &s->Z, (size_t)m * D));
-  GPK_TRY(dev_alloc(h, &s->S, (size_t)s->nt * s->nt));
-  GPK_TRY(dev_alloc(h, &s->Kuu, mm));
-  GPK_TRY(dev_alloc(h, &s->Wuu, mm));
-  GPK_TRY(dev_alloc(h, &s->A1, mm));
-  GPK_TRY(dev_alloc(h, &s->Bm, mm));
-  GPK_TRY(dev_alloc(h, &s->WB, mm));
-  GPK_TRY(dev_alloc(h, &s->WS, mm));
-  GPK_TRY(dev_alloc(h, &s->winv, (size_t)s->mp * NB));
-  GPK_TRY(dev_alloc(h, &s->T, (size_t)(s->mp / 2 + NB) * (s->mp / 2 + NB)));
-  GPK_TRY(dev_alloc(h, &s->pan, (size_t)4 * s->mp * NB));
-  GPK_TRY(dev_alloc(h, &s->r, (size_t)m * P));
-  GPK_TRY(dev_alloc(h, &s->c, (size_t)m * P));
-  GPK_TRY(dev_alloc(h, &s->alpha, (size_t)m * P));
+  GPK_TRY(s->Z.alloc(h, (size_t)m * D));
+  GPK_TRY(s->S.alloc(h, (size_t)s->nt * s->nt));
+  GPK_TRY(s->Kuu.alloc(h, mm));
+  GPK_TRY(s->Wuu.alloc(h, mm));
+  GPK_TRY(s->A1.alloc(h, mm));
+  GPK_TRY(s->Bm.alloc(h, mm));
+  GPK_TRY(s->WB.alloc(h, mm));
+  GPK_TRY(s->WS.alloc(h, mm));
+  GPK_TRY(s->winv.alloc(h, (size_t)s->mp * NB));
+  GPK_TRY(s->T.alloc(h, gpk_trtri_work(s->mp)));
+  GPK_TRY(s->pan.alloc(h, (size_t)4 * s->mp * NB));
+  GPK_TRY(s->r.alloc(h, (size_t)m * P));
+  GPK_TRY(s->c.alloc(h, (size_t)m * P));
+  GPK_TRY(s->alpha.alloc(h, (size_t)m * P));
   GPK_CHECK_HIP(h, hipMemcpyAsync(s->Z, Z, (size_t)m * D * sizeof(double), hipMemcpyHostToDevice, h->stream));
   GPK_CHECK_HIP(h, hipMemsetAsync(s->S, 0, (size_t)s->nt * s->nt * sizeof(double), h->stream));
   GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
@@ -375,7 +347,8 @@ int sparse_new(gpk_handle h, const double* Z, int64_t m, int D, int P, const dou
 }  // namespace
 
 void gpk_sparse_free(gpk_handle h) {
-  if (h->sparse) { sfree_all(h->sparse); delete h->sparse; h->sparse = nullptr; }
+  delete h->sparse;
+  h->sparse = nullptr;
 }
 
 extern "C" int gpk_sparse_accumulate(gpk_handle h, const double* X, const double* Yn, int64_t n, const double* Z, int64_t m,
@@ -405,15 +378,15 @@ extern "C" int gpk_sparse_update(gpk_handle h, const double* X, const double* Y,
   GPK_REQUIRE(h, X && Y && n >= 1, "sparse_update: null pointer or no rows");
   GPK_REQUIRE(h, h->batch == 1, "composite calls are not available in batched mode");
   const int D = s->D, P = s->P;
-  for (int64_t i = 0; i < n * D; ++i) GPK_REQUIRE(h, std::isfinite(X[i]), "sparse_update: X contains NaN or infinity");
-  for (int64_t i = 0; i < n * P; ++i) GPK_REQUIRE(h, std::isfinite(Y[i]), "sparse_update: Y contains NaN or infinity");
+  GPK_TRY(gpk_require_finite(h, X, n * D, "sparse_update", "X"));
+  GPK_TRY(gpk_require_finite(h, Y, n * P, "sparse_update", "Y"));
   GPK_CHECK_HIP(h, hipSetDevice(h->device));
   // the normalisation is the object's, fixed at gpk_sparse_begin: only then are the statistics additive
   std::vector<double> yn((size_t)n * P);
   for (int64_t i = 0; i < n; ++i)
     for (int p = 0; p < P; ++p) yn[(size_t)i * P + p] = (Y[i * P + p] - s->y_mean[p]) / s->y_std[p];
-  GPK_TRY(grow(h, &s->rows, &s->rows_bytes, (size_t)n * (D + P) * sizeof(double)));
-  double* dX = (double*)s->rows;
+  GPK_TRY(s->rows.reserve(h, (size_t)n * (D + P) * sizeof(double)));
+  double* dX = s->rows;
   double* dY = dX + (size_t)n * D;
   GPK_CHECK_HIP(h, hipMemcpyAsync(dX, X, (size_t)n * D * sizeof(double), hipMemcpyHostToDevice, h->stream));
   GPK_CHECK_HIP(h, hipMemcpyAsync(dY, yn.data(), (size_t)n * P * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -529,9 +502,8 @@ extern "C" int gpk_sparse_predict(gpk_handle h, const double* Xq, int64_t M, dou
   GPK_REQUIRE(h, h->batch == 1, "composite calls are not available in batched mode");
   GPK_CHECK_HIP(h, hipSetDevice(h->device));
   const int D = s->D, P = s->P;
-  for (int64_t i = 0; i < M * D; ++i) GPK_REQUIRE(h, std::isfinite(Xq[i]), "sparse_predict: Xq contains NaN or infinity");
-  // as gpk_predict: k** = sf2 + the WhiteKernel level, clipped at 0 - or sf2, floored at 1e-10
-  const double kss = s->sf2 + (var_includes_noise ? s->noise : 0.0), floor_ = var_includes_noise ? 0.0 : 1e-10;
+  GPK_TRY(gpk_require_finite(h, Xq, M * D, "sparse_predict", "Xq"));
+  const double kss = gpk_kss(s->sf2, s->noise, var_includes_noise), floor_ = gpk_var_floor(var_includes_noise);
   const double none = -std::numeric_limits<double>::max();
   const int64_t m = s->m, mp = s->mp;
   if (h->small_path && M <= GPK_SMALL_MAX_M && gpk_small_ok(mp, D, P, M)) {
@@ -552,7 +524,7 @@ extern "C" int gpk_sparse_predict(gpk_handle h, const double* Xq, int64_t M, dou
     }
     // several outputs share the two inverse factors: the one-model entry twice (four launches)
     std::vector<double> v0(var ? (size_t)M : 0), v1(var ? (size_t)M : 0), m2(var ? (size_t)M * P : 0);
-    GPK_TRY(gpk_predict_host(h, s->Z, s->alpha, m, D, P, s->ls, s->sf2, s->y_mean, s->y_std, var ? s->Wuu : nullptr, mp, mp, kss,
+    GPK_TRY(gpk_predict_host(h, s->Z, s->alpha, m, D, P, s->ls, s->sf2, s->y_mean, s->y_std, var ? s->Wuu.p : nullptr, mp, mp, kss,
                              none, Xq, M, mean, var ? v0.data() : nullptr));
     if (var) {
       GPK_TRY(gpk_predict_host(h, s->Z, s->alpha, m, D, P, s->ls, s->sf2, s->y_mean, s->y_std, s->WS, mp, mp, 0.0, none, Xq, M,
@@ -564,17 +536,14 @@ extern "C" int gpk_sparse_predict(gpk_handle h, const double* Xq, int64_t M, dou
     return GPK_OK;
   }
   // query panels: the fused mean and two variance launches (one per inverse factor), combined on the device
-  int64_t panel = GPK_HOST_MAX_M;
-  if (panel > gpk_padded(M)) panel = gpk_padded(M);
+  const int64_t panel = gpk_panel_rows(GPK_HOST_MAX_M, 1, M);      // (no byte budget: at most GPK_HOST_MAX_M rows)
   const size_t nq = (size_t)panel * D, nm = (size_t)panel * P;
-  GPK_TRY(grow(h, &s->q, &s->q_bytes, (nq + nm + (var ? 2 * (size_t)panel + nm : 0)) * sizeof(double)));
-  if (var) GPK_TRY(grow(h, &s->work, &s->work_bytes, (size_t)mp * panel * sizeof(double)));
-  double *dq = (double*)s->q, *dmean = dq + nq, *dv0 = dmean + nm, *dv1 = dv0 + panel, *dvar = dv1 + panel;
+  GPK_TRY(s->q.reserve(h, (nq + nm + (var ? 2 * (size_t)panel + nm : 0)) * sizeof(double)));
+  if (var) GPK_TRY(s->work.reserve(h, (size_t)mp * panel * sizeof(double)));
+  double *dq = s->q, *dmean = dq + nq, *dv0 = dmean + nm, *dv1 = dv0 + panel, *dvar = dv1 + panel;
   SpP ys;
   for (int p = 0; p < GPK_MAX_P; ++p) ys.v[p] = p < P ? s->y_std[p] : 1.0;
-  for (int64_t m0 = 0; m0 < M; m0 += panel) {
-    const int64_t mc = M - m0 < panel ? M - m0 : panel;
-    GPK_CHECK_HIP(h, hipMemcpyAsync(dq, Xq + m0 * D, (size_t)mc * D * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  return gpk_query_panels(h, Xq, M, D * sizeof(double), panel, dq, [&](int64_t m0, int64_t mc) -> int {
     GPK_TRY(gpk_predict_mean(h, GPK_F64, s->Z, s->alpha, m, D, P, s->ls, s->sf2, s->y_mean, s->y_std, dq, mc, dmean));
     GPK_CHECK_HIP(h, hipMemcpyAsync(mean + m0 * P, dmean, (size_t)mc * P * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (var) {
@@ -586,9 +555,8 @@ extern "C" int gpk_sparse_predict(gpk_handle h, const double* Xq, int64_t M, dou
       GPK_LAUNCH_CHECK(h);
       GPK_CHECK_HIP(h, hipMemcpyAsync(var + m0 * P, dvar, (size_t)mc * P * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     }
-    GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));      // the staging block is reused by the next panel
-  }
-  return GPK_OK;
+    return GPK_OK;
+  });
 }
 
 extern "C" int gpk_sparse_export(gpk_handle h, int64_t* m, int* D, int* P, int* n_ls, double* Z, double* G, double* g, double* yy,
@@ -636,9 +604,9 @@ extern "C" int gpk_sparse_import(gpk_handle h, const double* Z, int64_t m, int D
   if (!h) return GPK_BAD_ARG;
   GPK_REQUIRE(h, G && g && yy && n_rows >= 0, "sparse_import: null pointer or negative row count");
   if (m >= 1 && m <= SP_MAX_M && P >= 1 && P <= GPK_MAX_P) {
-    for (int64_t i = 0; i < m * m; ++i) GPK_REQUIRE(h, std::isfinite(G[i]), "sparse_import: G contains NaN or infinity");
-    for (int64_t i = 0; i < m * P; ++i) GPK_REQUIRE(h, std::isfinite(g[i]), "sparse_import: g contains NaN or infinity");
-    for (int p = 0; p < P; ++p) GPK_REQUIRE(h, std::isfinite(yy[p]), "sparse_import: yy contains NaN or infinity");
+    GPK_TRY(gpk_require_finite(h, G, m * m, "sparse_import", "G"));
+    GPK_TRY(gpk_require_finite(h, g, m * P, "sparse_import", "g"));
+    GPK_TRY(gpk_require_finite(h, yy, P, "sparse_import", "yy"));
   }
   gpk_sparse* s = nullptr;
   GPK_TRY(sparse_new(h, Z, m, D, P, ls, n_ls, sf2, noise, jitter, jitter_uu, y_mean, y_std, &s));
