@@ -92,7 +92,8 @@ GPK_API int64_t gpk_padded(int64_t n);
  * (debugging aid, tools/exp_ptile_trace.py).                                                                          */
 GPK_API int gpk_set_option(gpk_handle h, const char* name, int value);
 GPK_API int gpk_set_option_str(gpk_handle h, const char* name, const char* value);
-enum { GPK_TIMED_K5 = 1, GPK_TIMED_GRAM = 2, GPK_TIMED_GRAD = 3, GPK_TIMED_POTRF = 4, GPK_TIMED_COV = 5, GPK_TIMED_JAC = 6 };
+enum { GPK_TIMED_K5 = 1, GPK_TIMED_GRAM = 2, GPK_TIMED_GRAD = 3, GPK_TIMED_POTRF = 4, GPK_TIMED_COV = 5, GPK_TIMED_JAC = 6,
+       GPK_TIMED_SPARSE_STATS = 7, GPK_TIMED_SPARSE_PASS = 8 };
 GPK_API int gpk_timing(gpk_handle h, int enable);
 GPK_API int gpk_kernel_times(gpk_handle h, int tag, double* ms, int max_n, int* n_out);
 
@@ -638,11 +639,49 @@ GPK_API int gpk_lml_batched(gpk_handle h, const double* thetas, int n_theta, dou
  * gpk_sparse_bound: the bound of the last gpk_sparse_finalize and the rows seen so far.
  * gpk_sparse_export / gpk_sparse_import: Z (m x D), the statistics G (m x m), g (m x P), yy (P), n_rows and the
  *   hyper-parameters - ls (n_ls values), hyper = [sf2, noise, jitter, jitter_uu], y_mean, y_std (P) - as host arrays; NULL
- *   outputs are skipped.  The importer then only finalises (and may go on updating).                                        */
+ *   outputs are skipped.  The importer then only finalises (and may go on updating).
+ *
+ * Training: the gradient of the bound L with respect to log [ls .., noise, sf2] (jitter and jitter_uu do not depend on them).
+ * Replaces: the optimiser loop of GPflow's SGPR behind the reference's src/px4/gp.py (gpflow.optimizers.Scipy().minimize on
+ *   model.training_loss, which differentiates the same collapsed bound by reverse mode over the N x m cross-covariance), and
+ *   the exact-model fits on capped rows that stand in for it (src/px4/gp_trainer.py:163-180, GaussianProcessRegressor with
+ *   n_restarts_optimizer on max_samples rows).
+ * With Kuu^-1, Sigma~ = (Kuu + G / s2)^-1, alpha_u = Sigma~ g / s2 the partial derivatives are
+ *       dL/dg = alpha_u / s2,   dL/dG = P / (2 s2) (Kuu^-1 - Sigma~) - alpha_u alpha_u^T / (2 s2),
+ *       dL/dKuu = P / 2 (Kuu^-1 - Sigma~) - P / (2 s2) Kuu^-1 G Kuu^-1 - alpha_u alpha_u^T / 2
+ *   and with F = [Kfu | Yn], C = [2 dL/dG ; dL/dg^T] ((m + P) x m), Q = F C (N x m)
+ *       dL/dlog ls_d = sum_ni Q_ni Kfu_ni ((x_nd - z_id) / ls_d)^2 + sum_ij dL/dKuu_ij Kuu0_ij ((z_id - z_jd) / ls_d)^2
+ *       dL/dlog sf2  = sum Q o Kfu + sum dL/dKuu o Kuu0 - P N sf2 / (2 s2)        (Kuu0 = Kuu without jitter_uu)
+ *       dL/dlog noise = noise [ P (-N / (2 s2) + N sf2 / (2 s2^2) - tr(Kuu^-1 G) / (2 s2^2) + tr(Sigma~ G) / (2 s2^2))
+ *                               + sum yy / (2 s2^2) - sum alpha_u o g / s2^2 + tr(alpha_u^T G alpha_u) / (2 s2^2) ].
+ * gpk_sparse_grad_pass: the sums over the rows, the device-pointer building block beside gpk_sparse_accumulate: sums (dev
+ *   double[17]) [d] = sum_ni Q_ni Kfu_ni ((x_nd - z_id) / ls_d)^2 for d < D, [16] = sum_ni Q_ni Kfu_ni, Q = [Kfu | Yn] Cm; Cm dev
+ *   (mp + 128) x ldc (even ldc >= mp, 16-byte aligned): rows [0, m) and [mp, mp + P), columns [0, m), ZERO elsewhere.  Per
+ *   panel of rows (the panel rule of gpk_sparse_accumulate): F again, ONE tile GEMM on the fp64 matrix cores (rows x mp, k =
+ *   mp + 128) whose epilogue never stores Q - each tile multiplies its accumulators by the matching entries of F and by the
+ *   squared scaled differences recomputed from X and Z, and writes 17 sums - and a fixed-order reduction of the tiles' sums into
+ *   the running sums.  No floating-point atomics: the same calls give the same bits.  Asynchronous; work area: the handle's
+ *   scratch.  The limits of gpk_sparse_accumulate.
+ * gpk_sparse_hold: n raw rows X (n x D), Y (n x P), host: checked to be finite, normalised with the object's y_mean / y_std and
+ *   kept on the device; the statistics are REPLACED by those of these rows.  n == 0 releases the held rows (the statistics
+ *   stay); so does a later gpk_sparse_update (they would no longer be the statistics' rows).
+ * gpk_sparse_eval: sets the hyper-parameters (ls: n_ls values, n_ls as at gpk_sparse_begin; jitter, jitter_uu, y_mean, y_std
+ *   stay), accumulates the statistics of the held rows again, assembles the model as gpk_sparse_finalize does (same return
+ *   codes: GPK_NOT_PD with *info = the pivot) and returns the bound; grad != NULL: also its gradient, grad[n_ls + 2] =
+ *   d/dlog [ls .., noise, sf2] (n_ls == 1: the features' sum).  The gradient forms Kuu^-1, Sigma~ (gpk_wtw), Kuu^-1 G Kuu^-1 and
+ *   G alpha_u (tile GEMMs) in buffers of the assembly that the served model does not need, runs the row pass and takes the Kuu
+ *   term from gpk_lml_grad's pass on (Z, alpha_u, Kuu^-1 - Sigma~ - Kuu^-1 G Kuu^-1 / s2): one synchronisation more than the
+ *   assembly.  After a successful call the object is the finalised model at these hyper-parameters.
+ *   GPK_BAD_ARG without held rows.                                                                                          */
 GPK_API int gpk_sparse_accumulate(gpk_handle h, const double* X, const double* Yn, int64_t n, const double* Z, int64_t m, int D,
                                   int P, const double* ls, double sf2, double* S, int64_t ld);
+GPK_API int gpk_sparse_grad_pass(gpk_handle h, const double* X, const double* Yn, int64_t n, const double* Z, int64_t m, int D,
+                                 int P, const double* ls, double sf2, const double* Cm, int64_t ldc, double* sums);
 GPK_API int gpk_sparse_begin(gpk_handle h, const double* Z, int64_t m, int D, int P, const double* ls, int n_ls, double sf2,
                              double noise, double jitter, double jitter_uu, const double* y_mean, const double* y_std);
+GPK_API int gpk_sparse_hold(gpk_handle h, const double* X, const double* Y, int64_t n);
+GPK_API int gpk_sparse_eval(gpk_handle h, const double* ls, int n_ls, double sf2, double noise, double* bound, double* grad,
+                            int* info);
 GPK_API int gpk_sparse_update(gpk_handle h, const double* X, const double* Y, int64_t n);
 GPK_API int gpk_sparse_finalize(gpk_handle h, int* info);
 GPK_API int gpk_sparse_predict(gpk_handle h, const double* Xq, int64_t M, double* mean, double* var, int var_includes_noise);

@@ -19,6 +19,7 @@ GPK_HOST_MAX_M = 4096
 GPK_TIMED_K5, GPK_TIMED_GRAM, GPK_TIMED_GRAD, GPK_TIMED_POTRF = 1, 2, 3, 4
 GPK_TIMED_COV = 5
 GPK_TIMED_JAC = 6
+GPK_TIMED_SPARSE_STATS, GPK_TIMED_SPARSE_PASS = 7, 8
 
 _vp, _i64, _int, _dbl = C.c_void_p, C.c_int64, C.c_int, C.c_double
 _dp = C.POINTER(C.c_double)
@@ -112,6 +113,9 @@ SIGNATURES = {
     "gpk_lml_eval": (_int, [_vp, _vp, _i64, _int, _dp, _dbl, _dbl, _dbl, _vp, _int, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _dp, _dp,
                             C.POINTER(C.c_int)]),
     "gpk_sparse_accumulate": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _int, _int, _dp, _dbl, _vp, _i64]),
+    "gpk_sparse_grad_pass": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _int, _int, _dp, _dbl, _vp, _i64, _vp]),
+    "gpk_sparse_hold": (_int, [_vp, _dp, _dp, _i64]),
+    "gpk_sparse_eval": (_int, [_vp, _dp, _int, _dbl, _dbl, _dp, _dp, C.POINTER(_int)]),
     "gpk_sparse_begin": (_int, [_vp, _dp, _i64, _int, _int, _dp, _int, _dbl, _dbl, _dbl, _dbl, _dp, _dp]),
     "gpk_sparse_update": (_int, [_vp, _dp, _dp, _i64]),
     "gpk_sparse_finalize": (_int, [_vp, C.POINTER(_int)]),

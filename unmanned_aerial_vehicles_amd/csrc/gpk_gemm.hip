@@ -50,7 +50,14 @@ struct KParams {
   const double* cq;
   double csf2, cnoise;
   int cd, cm;
+  // epilogue 4 (row pass of the sparse bound's gradient): gx = the panel's rows (gn x gd), gz = the inducing inputs (gmz x gd),
+  // gls = the length-scales; C receives GRAD_W partial sums per tile
+  const double* gx;
+  const double* gz;
+  int gn, gmz, gd;
+  double gls[16];
 };
+constexpr int GRAD_W = GPK_GRAD_W;    // per-tile partial: 16 per-feature sums + the unweighted one
 
 typedef unsigned int V16 __attribute__((ext_vector_type(4)));   // one 16-byte register quad
 template <int V> struct IntC { static constexpr int value = V; };
@@ -361,6 +368,67 @@ __device__ __forceinline__ void cov_store(double* __restrict__ C, long long ldc,
       }
 }
 
+// Epilogue 4 (row pass of the sparse bound's gradient, Q^T = F C with F = [Kfu | Yn] the A operand): Q is not stored.  Each
+// accumulator is multiplied by the matching entry of F (the cross-covariance Kfu, read back from the A operand) and, per
+// feature d, by ((x_nd - z_id) / ls_d)^2 recomputed by exact differences of the divided coordinates staged in LDS (ux: the
+// tile's TS rows, then its TS inducing inputs, stride 17), as sparse_panel_kernel forms them.  The tile writes GRAD_W sums
+// - [0, 16) per feature, [16] unweighted - at out[tile * GRAD_W ..]; lanes, waves and tiles are added in a fixed order.
+// Rows >= gn and columns >= gmz are padding: F is zero there, and so is the product.
+template <int AB, int NB, int TS, int NW>
+__device__ __forceinline__ void grad_sums(double* __restrict__ out, long long tile, const double* __restrict__ F,
+                                          long long ldf, int row0, int col0, int row_w, int col_w, int lane, int wave,
+                                          int tid, d4 (&acc)[AB][NB], const double* ux, double* red, int D) {
+  double un = 0.0;
+#pragma unroll
+  for (int a = 0; a < AB; ++a)
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int rl = row_w + 16 * a + (lane >> 4) + 4 * i;
+        const int cl = col_w + 16 * b + (lane & 15);
+        const double t = acc[a][b][i] * F[(long long)(row0 + rl) * ldf + col0 + cl];
+        acc[a][b][i] = t;
+        un += t;
+      }
+  auto wave_sum = [](double v) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+  };
+  un = wave_sum(un);
+  if (lane == 0) red[wave * GRAD_W + 16] = un;
+  for (int d = 0; d < 16; ++d) {
+    double s = 0.0;
+    if (d < D) {
+      double xr[AB][4], zc[NB];
+#pragma unroll
+      for (int a = 0; a < AB; ++a)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) xr[a][i] = ux[(row_w + 16 * a + (lane >> 4) + 4 * i) * 17 + d];
+#pragma unroll
+      for (int b = 0; b < NB; ++b) zc[b] = ux[(TS + col_w + 16 * b + (lane & 15)) * 17 + d];
+#pragma unroll
+      for (int a = 0; a < AB; ++a)
+#pragma unroll
+        for (int b = 0; b < NB; ++b)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const double df = xr[a][i] - zc[b];
+            s = __builtin_fma(acc[a][b][i], df * df, s);
+          }
+      s = wave_sum(s);
+    }
+    if (lane == 0) red[wave * GRAD_W + d] = s;
+  }
+  __syncthreads();
+  if (tid < GRAD_W) {
+    double t = 0.0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) t += red[w * GRAD_W + tid];
+    out[tile * GRAD_W + tid] = t;
+  }
+}
+
 // accumulator block grid of one wave: (TS/WM) x (TS/2) elements in MFMA blocks
 template <typename T, int WM, int TS> struct AccT;
 template <int WM, int TS> struct AccT<double, WM, TS> {
@@ -621,6 +689,26 @@ __global__ __launch_bounds__(WM * 128, TS == 128 ? WM : 4) void gemm_kernel(KPar
       __syncthreads();
       cov_store<AB, NB, TS>(C, p.ldc, row0, col0, row_w, col_w, lane, acc, uq, p);
     }
+  } else if constexpr (EPI == 4) {
+    if constexpr (sizeof(T) == 8) {
+      // the k-loop ended with a barrier: the staging buffers are free for the scaled rows and inducing inputs of the tile
+      static_assert((2 * TS * 17 + (NT / 64) * GRAD_W) * 8 <= 4 * LDS_OP_BYTES, "epilogue 4: the images must fit the staging buffers");
+      double* ux = reinterpret_cast<double*>(lds);
+      for (int e = tid; e < 2 * TS * 16; e += NT) {
+        const int s = e / (TS * 16), r = (e >> 4) % TS, d = e & 15;
+        const int g = (s ? col0 : row0) + r;
+        double v = 0.0;
+        if (d < p.gd) {
+          if (s == 0) { if (g < p.gn) v = p.gx[(long long)g * p.gd + d] / p.gls[d]; }
+          else if (g < p.gmz) v = p.gz[(long long)g * p.gd + d] / p.gls[d];
+        }
+        ux[(s * TS + r) * 17 + d] = v;
+      }
+      __syncthreads();
+      grad_sums<AB, NB, TS, NT / 64>(reinterpret_cast<double*>(C), (long long)tm * p.ntn + tn, reinterpret_cast<const double*>(A), p.lda,
+                                     row0, col0, row_w, col_w, lane, wave, tid, acc, ux, ux + 2 * TS * 17, p.gd);
+      __syncthreads();          // (the sums used the staging buffers: the next tile of a persistent walk refills them)
+    }
   } else {
     // the k-loop ended with a barrier: the staging buffers are free for the reduction
     sumsq_acc<AB, NB, WM, TS>(lds, reinterpret_cast<double*>(C), p.ldc, tm, col0, wm, col_w, lane, tid, acc,
@@ -690,6 +778,23 @@ int launch(gpk_handle h, const GemmArgs& g) {
   dim3 grid((unsigned)nblocks, ny), block(WM * 128);
   p.amax = g.amax; p.amax_base = (const char*)g.amax_base;
   p.cq = g.cov_q; p.csf2 = g.cov_sf2; p.cnoise = g.cov_noise; p.cd = g.cov_d; p.cm = g.cov_m;
+  p.gx = g.grad_x; p.gz = g.grad_z; p.gn = g.grad_n; p.gmz = g.grad_m; p.gd = g.grad_d;
+  for (int d = 0; d < 16; ++d) p.gls[d] = g.grad_ls[d];
+  if (g.epilogue == 4) {
+    if constexpr (sizeof(T) == 8) {
+      if (g.ta || !g.tb || g.lower_only || !g.grad_x || !g.grad_z || g.grad_d < 1 || g.grad_d > 16 || g.grad_n < 1 || g.grad_n > g.m ||
+          g.grad_m < 1 || g.grad_m > g.n || g.lda < g.n || p.balanced || h->batch != 1 || g.nbatch > 0) {
+        h->err = "gemm: the gradient-sum epilogue needs ta == 0, tb == 1, every tile, 1 <= D <= 16, one problem";
+        return GPK_BAD_ARG;
+      }
+      hipLaunchKernelGGL((gemm_kernel<T, false, true, 4, WM, TS>), grid, block, 0, h->stream, p);
+      GPK_LAUNCH_CHECK(h);
+      return GPK_OK;
+    } else {
+      h->err = "gemm: the gradient-sum epilogue is fp64 only";
+      return GPK_BAD_ARG;
+    }
+  }
   if (g.epilogue == 3) {
     if constexpr (sizeof(T) == 8) {
       if (!g.ta || !g.tb || !g.lower_only || g.m != g.n || !g.cov_q || g.cov_d < 1 || g.cov_d > 16 || g.cov_m > g.m ||

@@ -187,6 +187,8 @@ inline long long gpk_bstride(gpk_handle h, const void* p) {
 // beyond a row's own k-range (a super-tile spans at most two bands of 8 tile rows)
 constexpr int GPK_ZERO_BAND_TILES = 16;
 
+constexpr int GPK_GRAD_W = 17;   // doubles per tile written by epilogue 4
+
 struct GemmArgs {
   const void* A;
   const void* B;
@@ -204,11 +206,18 @@ struct GemmArgs {
                   // 2: store C (beta = 0) and atomicMax |(float)C_ij| into amax[128-row block of the matrix at amax_base, ld = ldc]
                   // 3: fp64, ta = tb = 1, lower_only, m == n: C_ij = C_ji = cov_sf2 exp(-|u_i - u_j|^2 / 2) + cov_noise [i == j] - acc_ij
                   //    with u = cov_q (cov_m x cov_d, the queries divided by the length-scales); i or j >= cov_m: -acc_ij
+                  // 4: fp64, ta = 0, tb = 1, every tile: nothing of the product Q = A B is stored; C (fp64) [tile_row * (n / tile) + tile_col][17]
+                  //    = sum over the tile of Q_ni A_ni ((x_nd - z_id) / ls_d)^2 for d < grad_d (entries [0, 16)) and of Q_ni A_ni ([16]),
+                  //    x = grad_x (grad_n x grad_d, rows of A), z = grad_z (grad_m x grad_d, columns of C); A's first n columns are read back
   unsigned* amax;
   const void* amax_base;
   const double* cov_q;
   double cov_sf2, cov_noise;
   int cov_d, cov_m;
+  const double* grad_x;
+  const double* grad_z;
+  int grad_n, grad_m, grad_d;
+  double grad_ls[16];
   // nbatch > 0: that many independent products in one launch (second grid dimension), operand i at base + i * stride
   // (bytes); in the handle's batched mode every problem of the batch runs all of them.
   int nbatch;

@@ -17,6 +17,11 @@
 // The slab count depends on (mp, panel rows) only (sparse_slabs_for), overridable by option "sparse_slabs"; the panel by
 // option "sparse_panel" (sparse_panel_for: F within half of the 256 MB Infinity Cache).
 //
+// Training (gpk_sparse_hold / gpk_sparse_eval): the rows stay on the device, an evaluation accumulates S again, assembles the
+// model and, for the gradient of the bound, runs ONE more pass over the rows (grad_pass: F again, a tile GEMM Q = F C whose
+// epilogue reduces Q o Kfu o ((x - z) / ls)^2 per tile without storing Q, a fixed-order sum of the tiles); the m x m part is
+// gpk_wtw, tile GEMMs and gpk_lml_grad's pass on Z.  include/gpk.h has the formulas.
+//
 // The assembly (gpk_sparse_finalize) and the serving (gpk_sparse_predict) are host code over entries that exist: gpk_gram /
 // gpk_potrf / gpk_trtri, tile GEMMs with triangular k-ranges, gpk_lml_terms, gpk_predict_host_multi (the sparse model is
 // two "models" on the shared inputs Z: (alpha_u, Wuu, kss = sf2) and (any alpha, WSigma, kss = 0)), gpk_predict_mean and
@@ -278,6 +283,125 @@ int accumulate(gpk_handle h, const double* X, const double* Yn, int64_t n, const
   return GPK_OK;
 }
 
+// out[c] (+)= sum_{b < n} partial[b * W + c]: one workgroup per component, a fixed-order strided sum and a tree (as
+// grad_reduce_kernel); accumulate != 0 adds to what out[c] holds (the running sums of the row pass, panel after panel)
+__global__ __launch_bounds__(256) void sparse_sum_kernel(const double* __restrict__ partial, long long n, int W,
+                                                         double* __restrict__ out, int accumulate) {
+  __shared__ double red[256];
+  const int c = blockIdx.x, tid = threadIdx.x;
+  double s = 0.0;
+  for (long long b = tid; b < n; b += 256) s += partial[b * W + c];
+  red[tid] = s;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (tid < off) red[tid] += red[tid + off];
+    __syncthreads();
+  }
+  if (tid == 0) out[c] = accumulate ? out[c] + red[0] : red[0];
+}
+
+// The coefficient matrix of the row pass and the matrix of the Kuu term, from Ki = Kuu^-1, Si = Sigma~ (both full, mp x mp),
+// M3 = Kuu^-1 G Kuu^-1 (lower tiles) and alpha_u (m x P):
+//   Cm[i][j] = (P / s2) (Ki - Si)_ij - alpha_i . alpha_j / s2  (i, j < m),  Cm[mp + p][j] = alpha_jp / s2  (p < P, j < m),  0 elsewhere
+//   M3[i][j] <- (Ki - Si)_ij - M3_ij / s2                      (the lower tiles, in place)
+__global__ __launch_bounds__(256) void sparse_coef_kernel(const double* __restrict__ Ki, const double* __restrict__ Si,
+                                                          double* __restrict__ M3, const double* __restrict__ alpha, int m,
+                                                          int mp, int P, double is2, double* __restrict__ Cm) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (long long)(mp + NB) * mp) return;
+  const int i = (int)(e / mp), j = (int)(e - (long long)i * mp);
+  double v = 0.0;
+  if (i < mp) {
+    const double df = Ki[e] - Si[e];
+    if (i < m && j < m) {
+      double aa = 0.0;
+      for (int p = 0; p < P; ++p) aa = __builtin_fma(alpha[(long long)i * P + p], alpha[(long long)j * P + p], aa);
+      v = (double)P * is2 * df - aa * is2;
+    }
+    if (i / NB >= j / NB) M3[e] = df - M3[e] * is2;
+  } else if (i - mp < P && j < m) {
+    v = alpha[(long long)j * P + (i - mp)] * is2;
+  }
+  Cm[e] = v;
+}
+
+// part[i][0 .. 3] for the inducing input i < m (one workgroup each): sum_j Ki_ij G_ij, sum_j Si_ij G_ij, alpha_i . g_i,
+// alpha_i . (G alpha)_i;  G and g are blocks of S (leading dimension lds_), GA = G alpha is an (mp x 128) panel
+__global__ __launch_bounds__(256) void sparse_dots_kernel(const double* __restrict__ Ki, const double* __restrict__ Si,
+                                                          const double* __restrict__ S, long long lds_, const double* __restrict__ alpha,
+                                                          const double* __restrict__ GA, int m, int mp, int P,
+                                                          double* __restrict__ part) {
+  __shared__ double red[2][256];
+  const int i = blockIdx.x, tid = threadIdx.x;
+  double a = 0.0, b = 0.0;
+  for (int j = tid; j < m; j += 256) {
+    const double g = S[(long long)i * lds_ + j];
+    a = __builtin_fma(Ki[(long long)i * mp + j], g, a);
+    b = __builtin_fma(Si[(long long)i * mp + j], g, b);
+  }
+  red[0][tid] = a;
+  red[1][tid] = b;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (tid < off) { red[0][tid] += red[0][tid + off]; red[1][tid] += red[1][tid + off]; }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    double c = 0.0, d = 0.0;
+    for (int p = 0; p < P; ++p) {
+      const double al = alpha[(long long)i * P + p];
+      c = __builtin_fma(al, S[(long long)i * lds_ + mp + p], c);
+      d = __builtin_fma(al, GA[(long long)i * NB + p], d);
+    }
+    part[4 * i] = red[0][0];
+    part[4 * i + 1] = red[1][0];
+    part[4 * i + 2] = c;
+    part[4 * i + 3] = d;
+  }
+}
+
+// The row pass of the bound's gradient: sums[d] = sum_ni Q_ni Kfu_ni ((x_nd - z_id) / ls_d)^2 (d < D), sums[16] = sum_ni
+// Q_ni Kfu_ni with Q = F Cm, F = [Kfu | Yn], panel by panel with the panel rule of `accumulate`.  Per panel: sparse_panel_kernel
+// regenerates F, ONE tile GEMM (rows_p x mp, k = nt: no k-slabs, a 14 336-row panel at m = 1024 is 896 tiles) whose epilogue
+// keeps Q in registers and writes GPK_GRAD_W sums per tile, and sparse_sum_kernel adds the tiles' sums in tile order to the
+// running sums.  No floating-point atomics.
+int grad_pass(gpk_handle h, const double* X, const double* Yn, int64_t n, const double* Z, int64_t m, int D, int P,
+              const double* ls, double sf2, const double* Cm, int64_t ldc, double* sums) {
+  const int64_t mp = gpk_padded(m), nt = mp + NB;
+  SpLs l;
+  for (int d = 0; d < D; ++d) {
+    GPK_REQUIRE(h, ls[d] > 0.0 && std::isfinite(ls[d]), "sparse: length-scales must be positive");
+    l.v[d] = ls[d];
+  }
+  const int64_t panel = sparse_panel_for(h, mp);
+  const int64_t f_rows = round_up(n < panel ? n : panel, NB);
+  const size_t max_tiles = (size_t)(f_rows / 64) * (size_t)(mp / 64);
+  void* ws = nullptr;
+  GPK_TRY(gpk_scratch(h, ((size_t)f_rows * nt + max_tiles * GPK_GRAD_W) * sizeof(double), &ws));
+  double* F = (double*)ws;
+  double* partial = F + (size_t)f_rows * nt;
+  gpk_time_begin(h, GPK_TIMED_SPARSE_PASS);
+  for (int64_t r0 = 0; r0 < n; r0 += panel) {
+    const int64_t nr = n - r0 < panel ? n - r0 : panel;
+    const int64_t rows_p = round_up(nr, NB);
+    hipLaunchKernelGGL(sparse_panel_kernel, dim3((unsigned)(nt / SP_TS), (unsigned)(rows_p / SP_TS)), dim3(256), 0, h->stream,
+                       X + r0 * D, Yn + r0 * P, (long long)nr, Z, (int)m, D, P, l, sf2, F, (long long)nt, (int)mp);
+    GPK_LAUNCH_CHECK(h);
+    GemmArgs g = gemm_args(F, nt, 0, Cm, ldc, 1, partial, GPK_GRAD_W, (int)rows_p, (int)mp, (int)nt, 1.0, 0.0);
+    g.epilogue = 4;
+    g.grad_x = X + r0 * D; g.grad_z = Z; g.grad_n = (int)nr; g.grad_m = (int)m; g.grad_d = D;
+    for (int d = 0; d < D; ++d) g.grad_ls[d] = ls[d];
+    const int64_t tile = gpk_gemm_tile(h, g), ntiles = (rows_p / tile) * (mp / tile);
+    GPK_REQUIRE(h, (size_t)ntiles <= max_tiles, "sparse: tile count of the row pass");
+    GPK_TRY(gpk_gemm(h, GPK_F64, g));
+    hipLaunchKernelGGL(sparse_sum_kernel, dim3(GPK_GRAD_W), dim3(256), 0, h->stream, (const double*)partial, (long long)ntiles,
+                       GPK_GRAD_W, sums, r0 > 0 ? 1 : 0);
+    GPK_LAUNCH_CHECK(h);
+  }
+  gpk_time_end(h);
+  return GPK_OK;
+}
+
 }  // namespace
 
 // ---- the object behind the handle ---------------------------------------------------------------------------------
@@ -286,6 +410,8 @@ struct gpk_sparse {
   int D = 0, P = 0, n_ls = 0;
   double sf2 = 1.0, noise = 0.0, jitter = 0.0, jitter_uu = 0.0, sigma2 = 0.0, bound = 0.0;
   double ls[GPK_MAX_D_PREDICT] = {0}, ls_in[GPK_MAX_D_PREDICT] = {0}, y_mean[GPK_MAX_P] = {0}, y_std[GPK_MAX_P] = {0};
+  double yy_sum = 0.0;        // sum_p yy[p] of the last assembly
+  int64_t held_n = 0;         // rows kept on the device by gpk_sparse_hold (0: none)
   bool finalized = false;
   // Z (m x D); S (nt x nt) the statistics; Kuu -> Luu, Wuu = Luu^-1, A1 = Wuu G, Bm = B -> LB, WB = LB^-1, WS = WB Wuu
   // (mp x mp each); winv (mp x 128); T: the scratch of gpk_trtri; pan: four (mp x 128) right-hand-side panels;
@@ -293,6 +419,9 @@ struct gpk_sparse {
   gpk_dev<double> Z, S, Kuu, Wuu, A1, Bm, WB, WS, winv, T, pan, r, c, alpha;
   // staging of gpk_sparse_update (rows) and of gpk_sparse_predict's panel path
   gpk_dev<double> rows, q;
+  // gpk_sparse_hold: the held rows X (held_n x D) and their normalised targets (held_n x P); gpk_sparse_eval's gradient: the
+  // coefficient matrix of the row pass ((mp + 128) x mp) and the per-row sums of sparse_dots_kernel (m x 4)
+  gpk_dev<double> hX, hY, Cm, dots;
   gpk_dev<void> work;
 };
 
@@ -391,6 +520,12 @@ extern "C" int gpk_sparse_update(gpk_handle h, const double* X, const double* Y,
   GPK_CHECK_HIP(h, hipMemcpyAsync(dX, X, (size_t)n * D * sizeof(double), hipMemcpyHostToDevice, h->stream));
   GPK_CHECK_HIP(h, hipMemcpyAsync(dY, yn.data(), (size_t)n * P * sizeof(double), hipMemcpyHostToDevice, h->stream));
   s->finalized = false;
+  if (s->held_n) {      // the statistics stop being those of the held rows
+    GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
+    s->hX.reset();
+    s->hY.reset();
+    s->held_n = 0;
+  }
   int rc = accumulate(h, dX, dY, n, s->Z, s->m, D, P, s->ls, s->sf2, s->S, s->nt);
   if (hipStreamSynchronize(h->stream) != hipSuccess && rc == GPK_OK) {     // (yn leaves scope)
     h->err = "sparse_update: the statistics pass failed";
@@ -401,13 +536,10 @@ extern "C" int gpk_sparse_update(gpk_handle h, const double* X, const double* Y,
   return GPK_OK;
 }
 
-extern "C" int gpk_sparse_finalize(gpk_handle h, int* info) {
-  if (!h) return GPK_BAD_ARG;
-  gpk_sparse* s = h->sparse;
-  GPK_REQUIRE(h, s, "sparse_finalize: no sparse model (call gpk_sparse_begin first)");
-  GPK_REQUIRE(h, info, "sparse_finalize: null pointer");
-  GPK_REQUIRE(h, h->batch == 1, "composite calls are not available in batched mode");
-  GPK_CHECK_HIP(h, hipSetDevice(h->device));
+namespace {
+
+// The assembly of the model from the statistics (gpk_sparse_finalize, gpk_sparse_eval): include/gpk.h, gpk_sparse_finalize.
+int sparse_assemble(gpk_handle h, gpk_sparse* s, int* info) {
   const int64_t mp = s->mp;
   const int imp = (int)mp, P = s->P;
   const double is2 = 1.0 / s->sigma2;
@@ -480,7 +612,180 @@ extern "C" int gpk_sparse_finalize(gpk_handle h, int* info) {
     bound += -0.5 * N * std::log(2.0 * M_PI * s2) - terms[0] - 0.5 * (N * s->sf2 - s2 * tr_a) / s2 - 0.5 * yy[p] / s2 +
              0.5 * terms[1 + p];
   s->bound = bound;
+  s->yy_sum = 0.0;
+  for (int p = 0; p < P; ++p) s->yy_sum += yy[p];
   s->finalized = true;
+  return GPK_OK;
+}
+
+// The gradient of the bound of the model just assembled, with respect to log [ls_0 .. ls_{D-1}, noise, sf2] (g: D + 2 values).
+// Buffers of the assembly that the served model does not need are reused: Kuu (Luu) <- Kuu^-1, Bm (LB) <- Sigma~, WB <-
+// Kuu^-1 G, A1 <- Kuu^-1 G Kuu^-1 and then the matrix of the Kuu term, pan[1] <- G alpha_u.  One synchronisation.
+int sparse_gradient(gpk_handle h, gpk_sparse* s, double* g) {
+  const int64_t m = s->m, mp = s->mp, nt = s->nt;
+  const int imp = (int)mp, P = s->P, D = s->D;
+  const double s2 = s->sigma2, is2 = 1.0 / s2;
+  if (!s->Cm) GPK_TRY(s->Cm.alloc(h, (size_t)nt * mp));
+  if (!s->dots) GPK_TRY(s->dots.alloc(h, (size_t)m * 4));
+  double *Ki = s->Kuu, *Si = s->Bm, *H = s->WB, *M3 = s->A1;
+  double *Ap = s->pan + (size_t)3 * mp * NB, *GA = s->pan + (size_t)mp * NB;
+  const unsigned nb32 = (unsigned)(mp / 32), mirror_blocks = nb32 * (nb32 + 1) / 2;
+  // Kuu^-1 = Wuu^T Wuu and Sigma~ = WSigma^T WSigma: the lower tiles, mirrored to full matrices
+  GPK_TRY(gpk_wtw(h, s->Wuu, mp, mp, Ki, mp));
+  hipLaunchKernelGGL(sparse_reduce_kernel, dim3(mirror_blocks), dim3(256), 0, h->stream, Ki, (long long)mp, (const double*)Ki, 0,
+                     0ll, imp);
+  GPK_LAUNCH_CHECK(h);
+  // H = Kuu^-1 G = Wuu^T A1 (Wuu lower: k >= row-tile start)
+  {
+    GemmArgs a = gemm_args(s->Wuu, mp, 1, s->A1, mp, 1, H, mp, imp, imp, imp, 1.0, 0.0);
+    a.kb_row = NB;
+    GPK_TRY(gpk_gemm(h, GPK_F64, a));
+  }
+  GPK_TRY(gpk_wtw(h, s->WS, mp, mp, Si, mp));
+  hipLaunchKernelGGL(sparse_reduce_kernel, dim3(mirror_blocks), dim3(256), 0, h->stream, Si, (long long)mp, (const double*)Si, 0,
+                     0ll, imp);
+  GPK_LAUNCH_CHECK(h);
+  // M3 = H Kuu^-1: the lower tiles
+  {
+    GemmArgs a = gemm_args(H, mp, 0, Ki, mp, 0, M3, mp, imp, imp, imp, 1.0, 0.0);
+    a.lower_only = 1;
+    GPK_TRY(gpk_gemm(h, GPK_F64, a));
+  }
+  {
+    const long long tot = (long long)nt * mp;
+    hipLaunchKernelGGL(sparse_coef_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, (const double*)Ki,
+                       (const double*)Si, M3, (const double*)s->alpha, (int)m, imp, P, is2, s->Cm.p);
+    GPK_LAUNCH_CHECK(h);
+  }
+  // G alpha_u on the 128-column panel of alpha_u (zero beyond P and m)
+  {
+    GemmArgs a = gemm_args(s->S, nt, 0, Ap, NB, 1, GA, NB, imp, NB, imp, 1.0, 0.0);
+    GPK_TRY(gpk_gemm(h, GPK_F64, a));
+  }
+  double *d_kuu = h->d_small + 64, *d_rows = h->d_small + 96, *d_dots = h->d_small + 128;   // free doubles of the pinned block
+  hipLaunchKernelGGL(sparse_dots_kernel, dim3((unsigned)m), dim3(256), 0, h->stream, (const double*)Ki, (const double*)Si,
+                     (const double*)s->S, (long long)nt, (const double*)s->alpha, (const double*)GA, (int)m, imp, P, s->dots.p);
+  GPK_LAUNCH_CHECK(h);
+  hipLaunchKernelGGL(sparse_sum_kernel, dim3(4), dim3(256), 0, h->stream, (const double*)s->dots, (long long)m, 4, d_dots, 0);
+  GPK_LAUNCH_CHECK(h);
+  // the Kuu term: gpk_lml_grad's sums on (Z, alpha_u, Kuu^-1 - Sigma~ - M3 / s2) are -2 sum GammaK o Kuu0 o (...)
+  GPK_TRY(gpk_lml_grad_enqueue(h, s->Z, m, D, s->ls, s->sf2, s->alpha, P, M3, mp, d_kuu));
+  GPK_TRY(grad_pass(h, s->hX, s->hY, s->held_n, s->Z, m, D, P, s->ls, s->sf2, s->Cm, mp, d_rows));
+  GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
+  const double *kuu = h->h_small + 64, *rows = h->h_small + 96, *dots = h->h_small + 128;
+  const double N = (double)s->n_rows, Pd = (double)P, sf2 = s->sf2;
+  for (int d = 0; d < D; ++d) g[d] = rows[d] - 0.5 * kuu[d];
+  g[D] = s->noise * (Pd * (-N / (2.0 * s2) + N * sf2 / (2.0 * s2 * s2) - dots[0] / (2.0 * s2 * s2) + dots[1] / (2.0 * s2 * s2)) +
+                     s->yy_sum / (2.0 * s2 * s2) - dots[2] / (s2 * s2) + dots[3] / (2.0 * s2 * s2));
+  g[D + 1] = rows[16] - 0.5 * kuu[17] - Pd * N * sf2 / (2.0 * s2);
+  return GPK_OK;
+}
+
+}  // namespace
+
+extern "C" int gpk_sparse_finalize(gpk_handle h, int* info) {
+  if (!h) return GPK_BAD_ARG;
+  gpk_sparse* s = h->sparse;
+  GPK_REQUIRE(h, s, "sparse_finalize: no sparse model (call gpk_sparse_begin first)");
+  GPK_REQUIRE(h, info, "sparse_finalize: null pointer");
+  GPK_REQUIRE(h, h->batch == 1, "composite calls are not available in batched mode");
+  GPK_CHECK_HIP(h, hipSetDevice(h->device));
+  return sparse_assemble(h, s, info);
+}
+
+extern "C" int gpk_sparse_grad_pass(gpk_handle h, const double* X, const double* Yn, int64_t n, const double* Z, int64_t m, int D,
+                                    int P, const double* ls, double sf2, const double* Cm, int64_t ldc, double* sums) {
+  if (!h) return GPK_BAD_ARG;
+  GPK_REQUIRE(h, X && Yn && Z && ls && Cm && sums, "sparse_grad_pass: null pointer");
+  GPK_REQUIRE(h, n >= 1 && n < (1ll << 40) && m >= 1 && m <= SP_MAX_M, "sparse_grad_pass: need n >= 1, 1 <= m <= 16384");
+  GPK_REQUIRE(h, D >= 1 && D <= GPK_MAX_D_PREDICT && P >= 1 && P <= GPK_MAX_P, "sparse_grad_pass: need 1 <= D <= 16, 1 <= P <= GPK_MAX_P");
+  GPK_REQUIRE(h, ldc >= gpk_padded(m) && ldc % 2 == 0 && ((uintptr_t)Cm % 16) == 0,
+              "sparse_grad_pass: Cm must be 16-byte aligned with an even ldc >= gpk_padded(m)");
+  GPK_REQUIRE(h, sf2 > 0.0 && std::isfinite(sf2), "sparse_grad_pass: sf2 must be positive");
+  GPK_REQUIRE(h, h->batch == 1, "sparse_grad_pass: not available in batched mode");
+  return grad_pass(h, X, Yn, n, Z, m, D, P, ls, sf2, Cm, ldc, sums);
+}
+
+extern "C" int gpk_sparse_hold(gpk_handle h, const double* X, const double* Y, int64_t n) {
+  if (!h) return GPK_BAD_ARG;
+  gpk_sparse* s = h->sparse;
+  GPK_REQUIRE(h, s, "sparse_hold: no sparse model (call gpk_sparse_begin first)");
+  GPK_REQUIRE(h, n >= 0 && (n == 0 || (X && Y)), "sparse_hold: null pointer or negative row count");
+  GPK_REQUIRE(h, h->batch == 1, "composite calls are not available in batched mode");
+  GPK_CHECK_HIP(h, hipSetDevice(h->device));
+  const int D = s->D, P = s->P;
+  if (n > 0) {
+    GPK_TRY(gpk_require_finite(h, X, n * D, "sparse_hold", "X"));
+    GPK_TRY(gpk_require_finite(h, Y, n * P, "sparse_hold", "Y"));
+  }
+  GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
+  s->hX.reset();
+  s->hY.reset();
+  s->held_n = 0;
+  if (n == 0) return GPK_OK;
+  std::vector<double> yn((size_t)n * P);
+  for (int64_t i = 0; i < n; ++i)
+    for (int p = 0; p < P; ++p) yn[(size_t)i * P + p] = (Y[i * P + p] - s->y_mean[p]) / s->y_std[p];
+  GPK_TRY(s->hX.alloc(h, (size_t)n * D));
+  GPK_TRY(s->hY.alloc(h, (size_t)n * P));
+  GPK_CHECK_HIP(h, hipMemcpyAsync(s->hX, X, (size_t)n * D * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  GPK_CHECK_HIP(h, hipMemcpyAsync(s->hY, yn.data(), (size_t)n * P * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  // the statistics become those of these rows
+  s->finalized = false;
+  s->n_rows = 0;
+  GPK_CHECK_HIP(h, hipMemsetAsync(s->S, 0, (size_t)s->nt * s->nt * sizeof(double), h->stream));
+  int rc = accumulate(h, s->hX, s->hY, n, s->Z, s->m, D, P, s->ls, s->sf2, s->S, s->nt);
+  if (hipStreamSynchronize(h->stream) != hipSuccess && rc == GPK_OK) {     // (yn leaves scope)
+    h->err = "sparse_hold: the statistics pass failed";
+    rc = GPK_HIP_ERROR;
+  }
+  GPK_TRY(rc);
+  s->n_rows = n;
+  s->held_n = n;
+  return GPK_OK;
+}
+
+extern "C" int gpk_sparse_eval(gpk_handle h, const double* ls, int n_ls, double sf2, double noise, double* bound, double* grad,
+                               int* info) {
+  if (!h) return GPK_BAD_ARG;
+  gpk_sparse* s = h->sparse;
+  GPK_REQUIRE(h, s, "sparse_eval: no sparse model (call gpk_sparse_begin first)");
+  GPK_REQUIRE(h, s->held_n > 0, "sparse_eval: no held rows (call gpk_sparse_hold; gpk_sparse_update releases them)");
+  GPK_REQUIRE(h, ls && bound && info, "sparse_eval: null pointer");
+  GPK_REQUIRE(h, n_ls == s->n_ls, "sparse_eval: n_ls must be that of gpk_sparse_begin");
+  GPK_REQUIRE(h, sf2 > 0.0 && std::isfinite(sf2) && noise >= 0.0 && std::isfinite(noise) && noise + s->jitter > 0.0,
+              "sparse_eval: sf2 and the noise sigma^2 = noise + jitter must be positive");
+  for (int d = 0; d < n_ls; ++d) GPK_REQUIRE(h, ls[d] > 0.0 && std::isfinite(ls[d]), "sparse_eval: length-scales must be positive");
+  GPK_REQUIRE(h, h->batch == 1, "composite calls are not available in batched mode");
+  GPK_CHECK_HIP(h, hipSetDevice(h->device));
+  const int D = s->D;
+  *info = 0;
+  s->finalized = false;
+  s->sf2 = sf2; s->noise = noise; s->sigma2 = noise + s->jitter;
+  for (int d = 0; d < D; ++d) s->ls[d] = ls[n_ls == 1 ? 0 : d];
+  for (int d = 0; d < n_ls; ++d) s->ls_in[d] = ls[d];
+  // the statistics of the held rows at these hyper-parameters
+  GPK_CHECK_HIP(h, hipMemsetAsync(s->S, 0, (size_t)s->nt * s->nt * sizeof(double), h->stream));
+  gpk_time_begin(h, GPK_TIMED_SPARSE_STATS);
+  int rc = accumulate(h, s->hX, s->hY, s->held_n, s->Z, s->m, D, s->P, s->ls, s->sf2, s->S, s->nt);
+  gpk_time_end(h);
+  GPK_TRY(rc);
+  s->n_rows = s->held_n;
+  GPK_TRY(sparse_assemble(h, s, info));
+  *bound = s->bound;
+  if (!grad) return GPK_OK;
+  double g[GPK_MAX_D_PREDICT + 2];
+  rc = sparse_gradient(h, s, g);
+  if (rc != GPK_OK) { s->finalized = false; return rc; }
+  if (n_ls == 1) {
+    double t = 0.0;
+    for (int d = 0; d < D; ++d) t += g[d];
+    grad[0] = t;
+  } else {
+    for (int d = 0; d < D; ++d) grad[d] = g[d];
+  }
+  grad[n_ls] = g[D];
+  grad[n_ls + 1] = g[D + 1];
   return GPK_OK;
 }
 

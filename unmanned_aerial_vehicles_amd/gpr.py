@@ -65,6 +65,19 @@ def cholesky_draws(mean, cov, n_samples=1, random_state=0, active=None):
     return out
 
 
+def constrained_optimization(optimizer, obj, theta0, bounds):
+    """`sklearn/gaussian_process/_gpr.py:654-670`: one run of the optimiser on obj(theta) -> (value, gradient), both to be
+    minimised, from theta0 within bounds; returns (theta, value).  Shared with `SparseGP.train`."""
+    if optimizer == "fmin_l_bfgs_b":
+        res = scipy.optimize.minimize(obj, theta0, method="L-BFGS-B", jac=True, bounds=bounds)
+        if res.status != 0 and "CONVERGENCE" not in str(res.message):
+            warnings.warn(f"lbfgs failed to converge (status={res.status}): {res.message}")
+        return res.x, res.fun
+    if callable(optimizer):
+        return optimizer(obj, theta0, bounds=bounds)
+    raise ValueError(f"Unknown optimizer {optimizer}.")
+
+
 class GaussianProcessRegressor:
     def __init__(self, kernel=None, *, alpha=1e-10, optimizer="fmin_l_bfgs_b", n_restarts_optimizer=0,
                  normalize_y=False, copy_X_train=True, n_targets=None, random_state=None, device=None,
@@ -205,15 +218,7 @@ class GaussianProcessRegressor:
         return comp
 
     def _constrained_optimization(self, obj, theta0, bounds):
-        """`sklearn/gaussian_process/_gpr.py:654-670`."""
-        if self.optimizer == "fmin_l_bfgs_b":
-            res = scipy.optimize.minimize(obj, theta0, method="L-BFGS-B", jac=True, bounds=bounds)
-            if res.status != 0 and "CONVERGENCE" not in str(res.message):
-                warnings.warn(f"lbfgs failed to converge (status={res.status}): {res.message}")
-            return res.x, res.fun
-        if callable(self.optimizer):
-            return self.optimizer(obj, theta0, bounds=bounds)
-        raise ValueError(f"Unknown optimizer {self.optimizer}.")
+        return constrained_optimization(self.optimizer, obj, theta0, bounds)
 
     # ------------------------------------------------------------------ LML
     def _lml_on_device(self, theta, eval_gradient, dev=None):

@@ -4,8 +4,11 @@ The Titsias / DTC predictor of GPflow's SGPR on this package's kernel `[C *] RBF
 The training rows enter through additive fp64 statistics of size m x m (`gpk_sparse_update`: N m^2 flops on the fp64
 matrix cores), so `partial_fit` appends rows at any time; the model is assembled from them lazily at the next `predict`
 (`gpk_sparse_finalize`: an m x m factorisation) and served at the cost of an exact model of m rows
-(`gpk_sparse_predict`: two launches for up to 32 rows).  Hyper-parameters are not optimised here: they come from an exact
-fit on a subset (`SparseGP.from_exact`), which is what the reference trains anyway.
+(`gpk_sparse_predict`: two launches for up to 32 rows).  `fit` / `partial_fit` do not optimise: the hyper-parameters are the
+kernel's, e.g. those of an exact fit on a subset (`SparseGP.from_exact`).  `train` does: it keeps the rows on the device
+(`hold`, `gpk_sparse_hold`) and maximises the collapsed bound over the kernel's free parameters with L-BFGS-B, as GPflow's
+SGPR does; every evaluation (`log_bound`, `gpk_sparse_eval`) is the statistics pass, the m x m assembly and, for the
+gradient, one more pass over the rows - the inducing inputs stay where they are.
 
 The class keeps one libgpk handle of its own: the sparse model is the object behind that handle (include/gpk.h), the
 arrays that cross the boundary are host NumPy arrays.
@@ -25,6 +28,20 @@ _dp = _lib._dp
 
 def _ptr(a):
     return a.ctypes.data_as(_dp)
+
+
+def hyper_from_theta(kernel, theta):
+    """theta (the kernel's layout: log-parameters, fixed ones excluded) -> (the kernel at theta, its components, the
+    length-scales as `gpk_sparse_eval` takes them: one value for an isotropic kernel, D for ARD)."""
+    kern = kernel.clone_with_theta(np.asarray(theta, dtype=np.float64))
+    comp = kern.components()
+    return kern, comp, np.ascontiguousarray(comp.ls, dtype=np.float64)
+
+
+def gradient_to_theta(comp, g):
+    """`gpk_sparse_eval`'s gradient [ls .. (n_ls values; isotropic: already summed over the features), noise, sf2] -> the
+    gradient in theta's layout (fixed parameters dropped)."""
+    return comp.map_gradient(np.asarray(g, dtype=np.float64), len(g) - 2)
 
 
 class SparseGP:
@@ -53,6 +70,7 @@ class SparseGP:
         self._P = None
         self._y_1d = True
         self._state = None          # statistics waiting to be imported (after unpickling)
+        self._held = False          # the rows behind the statistics are on the device (hold)
 
     # ------------------------------------------------------------------ construction from an exact model
     @classmethod
@@ -109,7 +127,7 @@ class SparseGP:
                                                   comp.noise or 0.0, self.alpha, self.jitter_uu, _ptr(self._ym), _ptr(self._ys),
                                                   _ptr(st["G"]), _ptr(st["g"]), _ptr(st["yy"]), int(st["n_rows"])))
                 self._state = None
-        self._P, self._live, self._final = P, True, False
+        self._P, self._live, self._final, self._held = P, True, False, False
 
     def _ensure(self):
         """The assembled model: created (the prior, if no row was ever given) and finalised."""
@@ -125,8 +143,7 @@ class SparseGP:
             self._final = True
 
     # ------------------------------------------------------------------ rows
-    def partial_fit(self, X, y):
-        """Appends the rows X (n, D), y (n,) or (n, P) to the statistics; the model is reassembled at the next predict."""
+    def _check_rows(self, X, y):
         X = np.array(X, dtype=np.float64, ndmin=2)
         y = np.asarray(y, dtype=np.float64)
         if X.shape[0] != y.shape[0]:
@@ -135,27 +152,106 @@ class SparseGP:
             raise ValueError(f"X must be (N, {self.n_features_in_})")
         if not (np.isfinite(X).all() and np.isfinite(y).all()):
             raise ValueError("Input contains NaN or infinity")
-        y2 = y.reshape(X.shape[0], -1)
+        return np.ascontiguousarray(X), np.ascontiguousarray(y.reshape(X.shape[0], -1)), y.ndim == 1
+
+    def partial_fit(self, X, y):
+        """Appends the rows X (n, D), y (n,) or (n, P) to the statistics; the model is reassembled at the next predict."""
+        X, y2, y_1d = self._check_rows(X, y)
         if self._P is None and self._state is None:
-            self._y_1d = y.ndim == 1
+            self._y_1d = y_1d
         if not self._live:
             self._begin(y2.shape[1] if self._P is None else self._P)
         if y2.shape[1] != self._P:
             raise ValueError(f"y must have {self._P} columns")
         if X.shape[0] == 0:
             return self
-        X, y2 = np.ascontiguousarray(X), np.ascontiguousarray(y2)
         be = self._backend()
         with be.lock:
             be.bind_stream()
             be.check(be.lib.gpk_sparse_update(be.h, _ptr(X), _ptr(y2), X.shape[0]))
-        self._final = False
+        self._final, self._held = False, False
         return self
 
     def fit(self, X, y):
         """Forgets the rows seen so far, then `partial_fit(X, y)`."""
         self._live, self._final, self._P, self._state = False, False, None, None
         return self.partial_fit(X, y)
+
+    # ------------------------------------------------------------------ training
+    def hold(self, X, y):
+        """Forgets the rows seen so far and keeps X (n, D), y (n,) or (n, P) on the device: the statistics are theirs, and
+        `log_bound` can evaluate the bound of exactly these rows at any hyper-parameters.  A later `partial_fit` releases
+        them."""
+        X, y2, y_1d = self._check_rows(X, y)
+        if X.shape[0] == 0:
+            raise ValueError("hold needs at least one row")
+        self._live, self._final, self._P, self._state = False, False, None, None
+        self._y_1d = y_1d
+        self._begin(y2.shape[1])
+        be = self._backend()
+        with be.lock:
+            be.bind_stream()
+            be.check(be.lib.gpk_sparse_hold(be.h, _ptr(X), _ptr(y2), X.shape[0]))
+        self._held = True
+        return self
+
+    def log_bound(self, theta=None, eval_gradient=False):
+        """The collapsed bound of the held rows at theta (the kernel's own layout: log-parameters, fixed ones excluded), and
+        its gradient: the semantics of `GaussianProcessRegressor.log_marginal_likelihood`.  theta=None: the bound of the
+        current model.  A matrix that is not positive definite gives -inf and a zero gradient.  After the call the object is
+        the model at theta (`kernel_` follows)."""
+        if theta is None:
+            if eval_gradient:
+                raise ValueError("Gradient can only be evaluated for theta!=None")
+            return self.bound()
+        if not (self._live and getattr(self, "_held", False)):
+            raise RuntimeError("log_bound(theta) needs held rows: call hold(X, y) first")
+        theta = np.asarray(theta, dtype=np.float64)
+        kern, comp, ls = hyper_from_theta(self.kernel_, theta)
+        b, info = C.c_double(0.0), C.c_int(0)
+        g = np.zeros(ls.size + 2)
+        be = self._backend()
+        with be.lock:
+            be.bind_stream()
+            rc = be.lib.gpk_sparse_eval(be.h, _ptr(ls), ls.size, comp.sf2, comp.noise or 0.0, C.byref(b),
+                                        _ptr(g) if eval_gradient else None, C.byref(info))
+            self.kernel_ = kern
+            if rc == _lib.GPK_NOT_PD:
+                self._final = False
+                return (-np.inf, np.zeros_like(theta)) if eval_gradient else -np.inf
+            be.check(rc)
+        self._final = True
+        value = float(b.value)
+        return (value, gradient_to_theta(comp, g)) if eval_gradient else value
+
+    def train(self, X, y, n_restarts_optimizer=0, optimizer="fmin_l_bfgs_b", random_state=None):
+        """Holds the rows and maximises the bound over the kernel's free parameters within its bounds (L-BFGS-B, as
+        `GaussianProcessRegressor.fit`; restarts start from draws within finite bounds and run one after the other).  Sets
+        `kernel_` and `bound_value_` and leaves the finalised model at the optimum."""
+        from .gpr import _rng_from, constrained_optimization
+        if self.kernel_.n_dims == 0:
+            raise ValueError("train: the kernel has no free parameter")
+        self.hold(X, y)
+
+        def obj(theta):
+            value, grad = self.log_bound(theta, eval_gradient=True)
+            return -value, -grad
+
+        bounds = self.kernel_.bounds
+        starts = [self.kernel_.theta]
+        if n_restarts_optimizer > 0:
+            if not np.isfinite(bounds).all():
+                raise ValueError("Multiple optimizer restarts (n_restarts_optimizer>0) requires that all bounds are finite.")
+            rng = _rng_from(random_state)
+            starts += [rng.uniform(bounds[:, 0], bounds[:, 1]) for _ in range(n_restarts_optimizer)]
+        optima = [constrained_optimization(optimizer, obj, t0, bounds) for t0 in starts]
+        vals = [o[1] for o in optima]
+        best = optima[int(np.argmin(vals))][0]
+        value = self.log_bound(best)            # the model at the optimum (the last evaluation need not be the best one)
+        if not np.isfinite(value):
+            raise np.linalg.LinAlgError("train: the model at the optimum is not positive definite")
+        self.bound_value_ = value
+        return self
 
     # ------------------------------------------------------------------ predict
     def predict(self, X, return_std=False):
@@ -225,7 +321,7 @@ class SparseGP:
     def __getstate__(self):
         st = self.__dict__.copy()
         st["_state"] = self.statistics()
-        st["_be"], st["_live"], st["_final"] = None, False, False
+        st["_be"], st["_live"], st["_final"], st["_held"] = None, False, False, False
         if isinstance(st["device"], Backend):
             st["device"] = st["device"].device_index
         return st
