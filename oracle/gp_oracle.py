@@ -202,8 +202,23 @@ def predict(st: FitState, Xq, return_std=False, diag_includes_noise=True):
     return mean, np.sqrt(var)
 
 
+def predict_cov(st: FitState, Xq, noise):
+    """`sklearn/_gpr.py:454-469` (`return_cov=True`) in normalised-target units (times `y_std**2` per output for the
+    estimator's):  cov = K(Xq, Xq) + noise * I - V^T V,  V = L^-1 K*^T.
+
+    Every kernel entry comes from exact differences of the length-scale-divided coordinates (`sqdist`), so the prior's
+    diagonal is exactly sf2 and a query row that occurs twice gets exactly sf2 off the diagonal: `noise` (WhiteKernel's
+    `k(X)`, `sklearn/kernels.py:1402`) goes on the diagonal of the batch only, never on duplicated rows."""
+    Xq = np.atleast_2d(np.asarray(Xq, dtype=np.float64))
+    Ks = rbf_cross(Xq, st.X, st.length_scale, st.signal_variance)
+    V = solve_triangular(st.L, Ks.T, lower=True, check_finite=False)
+    K = rbf_cross(Xq, Xq, st.length_scale, st.signal_variance)
+    K[np.diag_indices_from(K)] += float(noise)
+    return K - V.T @ V
+
+
 # --------------------------------------------------------------------------------------
-# R9: SimpleQuadrotorGP.predict_residual semantics
+# R9:SimpleQuadrotorGP.predict_residual semantics
 # --------------------------------------------------------------------------------------
 def predict_residual(st: FitState, state, control):
     """`src/px4/simple_gp.py:187-201`: one row [state(6), control(4)] -> (mean(P,), std^2 (P,))."""
