@@ -85,6 +85,8 @@ GPK_API int64_t gpk_padded(int64_t n);
  * level-by-level products of gpk_trtri; same values to rounding), "gemm_balanced" (tile GEMMs whose tiles differ in k-range - the
  * products with triangular operands of gpk_trtri / gpk_wtw / gpk_potrs_inv: 1 = the balanced persistent tile schedule, 0 = the
  * static tile mapping; bit-identical results), "gemm_balanced_max_tiles", "gemm_log" (1: every tile-GEMM launch to stderr),
+ * "gram_log" (1: the form of every gpk_gram launch - `GPKGRAM f64|f32 N Np D strip|sym gsG ntT gridNNN` - and of every gpk_predict_mean /
+ * gpk_predict_mean_multi launch - `GPKMEAN f64|f32 N M D P|B d4 p4 granG sS chunkC` - to stderr, one line per launch),
  * "sparse_panel" / "sparse_slabs" (the statistics pass of the sparse model, K9:
  * rows per panel and k-slabs per panel product; 0 = the built-in rule), "debug_fill" (1: the handle's scratch and serving work area are overwritten with NaN bytes at every request - the test
  * suite runs with it).  Used by the A/B timings and by the tests that pin a fast path to its plain form.

@@ -82,6 +82,7 @@ extern "C" int gpk_set_option(gpk_handle h, const char* name, int value) {
   else if (n == "gemm_balanced_max_tiles") h->gemm_balanced_max_tiles = value;
   else if (n == "k3_stream_min_np") h->k3_stream_min_np = value;
   else if (n == "gemm_log") h->gemm_log = value;
+  else if (n == "gram_log") h->gram_log = value;
   else if (n == "debug_fill") h->debug_fill = value ? 1 : 0;
   else if (n == "sparse_panel") h->sparse_panel = value <= 0 ? 0 : value > (1 << 20) ? (1 << 20) : value;
   else if (n == "sparse_slabs") h->sparse_slabs = value <= 0 ? 0 : value > 64 ? 64 : value;

@@ -708,8 +708,10 @@ extern "C" int gpk_gram(gpk_handle h, int dtype, const void* X, int64_t N, int D
   if (!h) return GPK_BAD_ARG;
   GPK_REQUIRE(h, N >= 1 && X && K, "gram: null pointer or N < 1");
   const int64_t Np = gpk_padded(N);
-  GPK_REQUIRE(h, ldk >= Np && ldk % 2 == 0, "gram: ldk must be >= gpk_padded(N)");
   GPK_REQUIRE(h, dtype == GPK_F32 || dtype == GPK_F64, "gram: bad dtype");
+  // every store is 16 bytes: row starts must keep that alignment (two doubles, four floats)
+  GPK_REQUIRE(h, ldk >= Np && ldk % (dtype == GPK_F32 ? 4 : 2) == 0,
+              "gram: ldk must be >= gpk_padded(N) and a multiple of 2 (fp64) / 4 (fp32)");
   LsArr l;
   GPK_TRY(fill_ls(h, ls, D, l));
   const int64_t nt = Np / TS;
@@ -739,6 +741,9 @@ extern "C" int gpk_gram(gpk_handle h, int dtype, const void* X, int64_t N, int D
       hipLaunchKernelGGL((gram_sym_kernel<T, NT>), grid, block, 0, h->stream, (const T*)X, (long long)N, D, l,  \
                          (T)sf2, (T)diag_add, (T*)K, (long long)ldk);                                       \
   } while (0)
+  if (h->gram_log)   // option gram_log = 1: the form this launch takes (the tests assert it per case)
+    fprintf(stderr, "GPKGRAM %s %lld %lld %d %s gs%d nt%lld grid%u\n", dtype == GPK_F64 ? "f64" : "f32", (long long)N, (long long)Np, D,
+            strip ? "strip" : "sym", strip ? gs : 0, (long long)nt, grid.x);
   gpk_time_begin(h, GPK_TIMED_GRAM);
   if (dtype == GPK_F64) { if (stream_nt) GPK_GRAM_LAUNCH(double, true); else GPK_GRAM_LAUNCH(double, false); }
   else { if (stream_nt) GPK_GRAM_LAUNCH(float, true); else GPK_GRAM_LAUNCH(float, false); }
@@ -870,6 +875,9 @@ extern "C" int gpk_predict_mean(gpk_handle h, int dtype, const void* X, const vo
   dim3 grid((unsigned)nqb, (unsigned)S);
   const int64_t tot = M * P;
   const int d4 = (D + 3) / 4, p4 = (P + 3) / 4;
+  if (h->gram_log)
+    fprintf(stderr, "GPKMEAN %s %lld %lld %d P%d d%d p%d gran%lld s%lld chunk%lld\n", dtype == GPK_F64 ? "f64" : "f32", (long long)N,
+            (long long)M, D, P, d4, p4, (long long)gran, (long long)S, (long long)chunk);
   if (dtype == GPK_F64) {
     hipLaunchKernelGGL(pm_pick<double>(d4, p4), grid, dim3(256), 0, h->stream, (const double*)X,
                        (const double*)alpha, (long long)N, D, P, l16, (const double*)Xq, (long long)M,
@@ -929,6 +937,9 @@ extern "C" int gpk_predict_mean_multi(gpk_handle h, int dtype, const void* X, co
   dim3 grid((unsigned)nqb, (unsigned)S);
   const int64_t tot = M * B;
   const int d4 = (D + 3) / 4, b4 = (B + 3) / 4;
+  if (h->gram_log)
+    fprintf(stderr, "GPKMEAN %s %lld %lld %d B%d d%d p%d gran%d s%lld chunk%lld\n", dtype == GPK_F64 ? "f64" : "f32", (long long)N,
+            (long long)M, D, B, d4, b4 <= 1 ? 1 : 2, PM_TJ, (long long)S, (long long)chunk);
   if (dtype == GPK_F64) {
     hipLaunchKernelGGL(pmm_pick<double>(d4, b4), grid, dim3(256), 0, h->stream, (const double*)X,
                        (const double*)alpha, (long long)N, D, B, (const double*)w_dev, (const double*)Xq,
