@@ -674,16 +674,44 @@ GPK_API int gpk_lml_batched(gpk_handle h, const double* thetas, int n_theta, dou
  *   G alpha_u (tile GEMMs) in buffers of the assembly that the served model does not need, runs the row pass and takes the Kuu
  *   term from gpk_lml_grad's pass on (Z, alpha_u, Kuu^-1 - Sigma~ - Kuu^-1 G Kuu^-1 / s2): one synchronisation more than the
  *   assembly.  After a successful call the object is the finalised model at these hyper-parameters.
- *   GPK_BAD_ARG without held rows.                                                                                          */
+ *   GPK_BAD_ARG without held rows.
+ *
+ * Training the inducing inputs: the gradient of the bound with respect to Z.
+ * Replaces: GPflow's SGPR behind the reference's src/px4/gp.py keeps inducing_variable.Z a trainable parameter, and the same
+ *   gpflow.optimizers.Scipy().minimize differentiates the collapsed bound with respect to it together with the kernel - that is
+ *   how a small m summarises many rows.
+ * With T = Q o Kfu (Q = F C as above), GammaK = dL/dKuu = (P / 2) M - alpha_u alpha_u^T / 2, M = Kuu^-1 - Sigma~ - Kuu^-1 G Kuu^-1 / s2:
+ *       dL/dz_id = (U_id + V_id) / ls_d,
+ *       U_id = sum_n T_ni (x_nd / ls_d - z_id / ls_d),          V_id = 2 sum_j GammaK_ij Kuu0_ij (z_jd / ls_d - z_id / ls_d)
+ *   by differences of the length-scale-divided coordinates (never T^T X - z sum T: two large sums that cancel).  y_mean / y_std,
+ *   jitter and jitter_uu do not depend on Z; an isotropic kernel uses the same formula with equal ls_d.
+ * gpk_sparse_zgrad_pass: the column pass, the device-pointer building block beside gpk_sparse_grad_pass (same operands, same
+ *   limits, same panel loop and scratch, asynchronous): R (dev, gpk_padded(m) x 17) [i][d] = U_id for d < D (zero for D <= d <
+ *   16), [i][16] = sum_n T_ni; rows i >= m are zero.  Per panel of rows: F again, ONE tile GEMM whose epilogue never stores Q -
+ *   each tile multiplies its accumulators by the matching entries of F and by the scaled differences, sums them over its rows
+ *   (lane, lane groups, waves: a fixed order) and writes 17 sums per column - and a launch that adds the row-tiles' sums in
+ *   tile order into R, panel after panel.  No floating-point atomics: the same calls give the same bits.
+ * gpk_sparse_eval_z: gpk_sparse_eval with the inducing inputs as arguments.  Z != NULL (host m x D; m and D are the object's;
+ *   checked to be finite) replaces the object's inducing inputs, Z == NULL keeps them; then gpk_sparse_eval: the statistics of
+ *   the held rows are accumulated again (against the new Z), the model is assembled (same return codes: GPK_NOT_PD with *info =
+ *   the pivot), bound and grad as there.  gradZ != NULL (host m x D): dL/dZ in raw coordinates - behind the launches of the
+ *   hyper-parameter gradient the matrix M is mirrored to a full matrix, one m x m kernel forms V (one inducing input per
+ *   workgroup, j in index order, Kuu0 recomputed by exact differences) and the column pass U; still one synchronisation.
+ *   After a successful call the object is the finalised model at these hyper-parameters and this Z, and gpk_sparse_export
+ *   returns it.  With Z == NULL and gradZ == NULL the launches and the bits are gpk_sparse_eval's.                       */
 GPK_API int gpk_sparse_accumulate(gpk_handle h, const double* X, const double* Yn, int64_t n, const double* Z, int64_t m, int D,
                                   int P, const double* ls, double sf2, double* S, int64_t ld);
 GPK_API int gpk_sparse_grad_pass(gpk_handle h, const double* X, const double* Yn, int64_t n, const double* Z, int64_t m, int D,
                                  int P, const double* ls, double sf2, const double* Cm, int64_t ldc, double* sums);
+GPK_API int gpk_sparse_zgrad_pass(gpk_handle h, const double* X, const double* Yn, int64_t n, const double* Z, int64_t m, int D,
+                                  int P, const double* ls, double sf2, const double* Cm, int64_t ldc, double* R);
 GPK_API int gpk_sparse_begin(gpk_handle h, const double* Z, int64_t m, int D, int P, const double* ls, int n_ls, double sf2,
                              double noise, double jitter, double jitter_uu, const double* y_mean, const double* y_std);
 GPK_API int gpk_sparse_hold(gpk_handle h, const double* X, const double* Y, int64_t n);
 GPK_API int gpk_sparse_eval(gpk_handle h, const double* ls, int n_ls, double sf2, double noise, double* bound, double* grad,
                             int* info);
+GPK_API int gpk_sparse_eval_z(gpk_handle h, const double* Z, const double* ls, int n_ls, double sf2, double noise, double* bound,
+                              double* grad, double* gradZ, int* info);
 GPK_API int gpk_sparse_update(gpk_handle h, const double* X, const double* Y, int64_t n);
 GPK_API int gpk_sparse_finalize(gpk_handle h, int* info);
 GPK_API int gpk_sparse_predict(gpk_handle h, const double* Xq, int64_t M, double* mean, double* var, int var_includes_noise);

@@ -114,8 +114,10 @@ SIGNATURES = {
                             C.POINTER(C.c_int)]),
     "gpk_sparse_accumulate": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _int, _int, _dp, _dbl, _vp, _i64]),
     "gpk_sparse_grad_pass": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _int, _int, _dp, _dbl, _vp, _i64, _vp]),
+    "gpk_sparse_zgrad_pass": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _int, _int, _dp, _dbl, _vp, _i64, _vp]),
     "gpk_sparse_hold": (_int, [_vp, _dp, _dp, _i64]),
     "gpk_sparse_eval": (_int, [_vp, _dp, _int, _dbl, _dbl, _dp, _dp, C.POINTER(_int)]),
+    "gpk_sparse_eval_z": (_int, [_vp, _dp, _dp, _int, _dbl, _dbl, _dp, _dp, _dp, C.POINTER(_int)]),
     "gpk_sparse_begin": (_int, [_vp, _dp, _i64, _int, _int, _dp, _int, _dbl, _dbl, _dbl, _dbl, _dp, _dp]),
     "gpk_sparse_update": (_int, [_vp, _dp, _dp, _i64]),
     "gpk_sparse_finalize": (_int, [_vp, C.POINTER(_int)]),

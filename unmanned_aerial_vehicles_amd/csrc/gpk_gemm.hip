@@ -51,7 +51,7 @@ struct KParams {
   double csf2, cnoise;
   int cd, cm;
   // epilogue 4 (row pass of the sparse bound's gradient): gx = the panel's rows (gn x gd), gz = the inducing inputs (gmz x gd),
-  // gls = the length-scales; C receives GRAD_W partial sums per tile
+  // gls = the length-scales; C receives GRAD_W partial sums per tile (epilogue 5, the column pass: per column of every tile)
   const double* gx;
   const double* gz;
   int gn, gmz, gd;
@@ -429,6 +429,78 @@ __device__ __forceinline__ void grad_sums(double* __restrict__ out, long long ti
   }
 }
 
+// Epilogue 5 (column pass of the sparse bound's gradient with respect to the inducing inputs): the operands and the staging of
+// epilogue 4, but the sums run over the tile's ROWS only, one set per column: with t = acc * F[row][col],
+//   out[(tile * TS + c) * GRAD_W + d] = sum_rows t (x_d - z_d)   (d < D; zero for D <= d < 16),   [.. + 16] = sum_rows t.
+// In the accumulator layout a lane owns the column lane & 15 of each of its NB blocks and the rows (lane >> 4) + 4 i + 16 a: the
+// sum goes over (a, i) in the lane, then over the four lane groups (two xor shuffles), then over the wave rows through two
+// LDS images (wave rows 0 / 1 store, 2 / 3 add to the image of their parity, the images are added on the way out): a fixed
+// order, no atomics.  Differences are taken, never products x sum(t) - z sum(t).  Padding: F is zero there, and so is t.
+template <int AB, int NB, int TS, int WM>
+__device__ __forceinline__ void col_sums(double* __restrict__ out, long long tile, const double* __restrict__ F,
+                                         long long ldf, int row0, int col0, int row_w, int col_w, int lane, int wm, int tid,
+                                         d4 (&acc)[AB][NB], const double* ux, double* red, int D) {
+#pragma unroll
+  for (int a = 0; a < AB; ++a)
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int rl = row_w + 16 * a + (lane >> 4) + 4 * i;
+        const int cl = col_w + 16 * b + (lane & 15);
+        acc[a][b][i] *= F[(long long)(row0 + rl) * ldf + col0 + cl];
+      }
+  auto groups_sum = [](double v) {
+    v += __shfl_xor(v, 16, 64);
+    v += __shfl_xor(v, 32, 64);
+    return v;
+  };
+  for (int r = 0; r < WM; r += 2) {
+    if ((wm >> 1) == (r >> 1)) {          // (wave-uniform)
+      double* img = red + (wm & 1) * TS * GRAD_W;
+      for (int d = 0; d <= 16; ++d) {
+        double s[NB];
+#pragma unroll
+        for (int b = 0; b < NB; ++b) s[b] = 0.0;
+        if (d == 16) {
+#pragma unroll
+          for (int b = 0; b < NB; ++b) {
+#pragma unroll
+            for (int a = 0; a < AB; ++a)
+#pragma unroll
+              for (int i = 0; i < 4; ++i) s[b] += acc[a][b][i];
+            s[b] = groups_sum(s[b]);
+          }
+        } else if (d < D) {
+          double xr[AB][4];
+#pragma unroll
+          for (int a = 0; a < AB; ++a)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) xr[a][i] = ux[(row_w + 16 * a + (lane >> 4) + 4 * i) * 17 + d];
+#pragma unroll
+          for (int b = 0; b < NB; ++b) {
+            const double zc = ux[(TS + col_w + 16 * b + (lane & 15)) * 17 + d];
+#pragma unroll
+            for (int a = 0; a < AB; ++a)
+#pragma unroll
+              for (int i = 0; i < 4; ++i) s[b] = __builtin_fma(acc[a][b][i], xr[a][i] - zc, s[b]);
+            s[b] = groups_sum(s[b]);
+          }
+        }
+        if (lane < 16) {
+#pragma unroll
+          for (int b = 0; b < NB; ++b) {
+            double* q = img + (col_w + 16 * b + lane) * GRAD_W + d;
+            *q = r ? *q + s[b] : s[b];
+          }
+        }
+      }
+    }
+    __syncthreads();
+  }
+  for (int e = tid; e < TS * GRAD_W; e += WM * 128) out[tile * (TS * GRAD_W) + e] = red[e] + red[TS * GRAD_W + e];
+}
+
 // accumulator block grid of one wave: (TS/WM) x (TS/2) elements in MFMA blocks
 template <typename T, int WM, int TS> struct AccT;
 template <int WM, int TS> struct AccT<double, WM, TS> {
@@ -709,6 +781,29 @@ __global__ __launch_bounds__(WM * 128, TS == 128 ? WM : 4) void gemm_kernel(KPar
                                      row0, col0, row_w, col_w, lane, wave, tid, acc, ux, ux + 2 * TS * 17, p.gd);
       __syncthreads();          // (the sums used the staging buffers: the next tile of a persistent walk refills them)
     }
+  } else if constexpr (EPI == 5) {
+    if constexpr (sizeof(T) == 8) {
+      // the staging of epilogue 4, repeated here and not shared: moving the loop into a helper changed epilogue 4's register
+      // allocation (124 -> 122 VGPRs at 64-wide tiles, 236 -> 228 bytes of scratch at 128-wide), and that instantiation is to stay
+      // what it was.  Padding is WRITTEN as zeros, never read (0 * NaN is not zero).  Behind the two images of coordinates, two
+      // images of TS x GRAD_W column sums.
+      static_assert(4 * TS * 17 * 8 <= 4 * LDS_OP_BYTES && GRAD_W == 17, "epilogue 5: the images must fit the staging buffers");
+      double* ux = reinterpret_cast<double*>(lds);
+      for (int e = tid; e < 2 * TS * 16; e += NT) {
+        const int s = e / (TS * 16), r = (e >> 4) % TS, d = e & 15;
+        const int g = (s ? col0 : row0) + r;
+        double v = 0.0;
+        if (d < p.gd) {
+          if (s == 0) { if (g < p.gn) v = p.gx[(long long)g * p.gd + d] / p.gls[d]; }
+          else if (g < p.gmz) v = p.gz[(long long)g * p.gd + d] / p.gls[d];
+        }
+        ux[(s * TS + r) * 17 + d] = v;
+      }
+      __syncthreads();
+      col_sums<AB, NB, TS, WM>(reinterpret_cast<double*>(C), (long long)tm * p.ntn + tn, reinterpret_cast<const double*>(A), p.lda,
+                               row0, col0, row_w, col_w, lane, wm, tid, acc, ux, ux + 2 * TS * 17, p.gd);
+      __syncthreads();          // (the sums used the staging buffers: the next tile of a persistent walk refills them)
+    }
   } else {
     // the k-loop ended with a barrier: the staging buffers are free for the reduction
     sumsq_acc<AB, NB, WM, TS>(lds, reinterpret_cast<double*>(C), p.ldc, tm, col0, wm, col_w, lane, tid, acc,
@@ -780,14 +875,15 @@ int launch(gpk_handle h, const GemmArgs& g) {
   p.cq = g.cov_q; p.csf2 = g.cov_sf2; p.cnoise = g.cov_noise; p.cd = g.cov_d; p.cm = g.cov_m;
   p.gx = g.grad_x; p.gz = g.grad_z; p.gn = g.grad_n; p.gmz = g.grad_m; p.gd = g.grad_d;
   for (int d = 0; d < 16; ++d) p.gls[d] = g.grad_ls[d];
-  if (g.epilogue == 4) {
+  if (g.epilogue == 4 || g.epilogue == 5) {
     if constexpr (sizeof(T) == 8) {
       if (g.ta || !g.tb || g.lower_only || !g.grad_x || !g.grad_z || g.grad_d < 1 || g.grad_d > 16 || g.grad_n < 1 || g.grad_n > g.m ||
           g.grad_m < 1 || g.grad_m > g.n || g.lda < g.n || p.balanced || h->batch != 1 || g.nbatch > 0) {
         h->err = "gemm: the gradient-sum epilogue needs ta == 0, tb == 1, every tile, 1 <= D <= 16, one problem";
         return GPK_BAD_ARG;
       }
-      hipLaunchKernelGGL((gemm_kernel<T, false, true, 4, WM, TS>), grid, block, 0, h->stream, p);
+      if (g.epilogue == 4) hipLaunchKernelGGL((gemm_kernel<T, false, true, 4, WM, TS>), grid, block, 0, h->stream, p);
+      else hipLaunchKernelGGL((gemm_kernel<T, false, true, 5, WM, TS>), grid, block, 0, h->stream, p);
       GPK_LAUNCH_CHECK(h);
       return GPK_OK;
     } else {

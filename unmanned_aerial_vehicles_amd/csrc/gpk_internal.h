@@ -188,7 +188,7 @@ inline long long gpk_bstride(gpk_handle h, const void* p) {
 // beyond a row's own k-range (a super-tile spans at most two bands of 8 tile rows)
 constexpr int GPK_ZERO_BAND_TILES = 16;
 
-constexpr int GPK_GRAD_W = 17;   // doubles per tile written by epilogue 4
+constexpr int GPK_GRAD_W = 17;   // doubles per tile written by epilogue 4, and per COLUMN of a tile by epilogue 5
 
 struct GemmArgs {
   const void* A;
@@ -210,6 +210,8 @@ struct GemmArgs {
                   // 4: fp64, ta = 0, tb = 1, every tile: nothing of the product Q = A B is stored; C (fp64) [tile_row * (n / tile) + tile_col][17]
                   //    = sum over the tile of Q_ni A_ni ((x_nd - z_id) / ls_d)^2 for d < grad_d (entries [0, 16)) and of Q_ni A_ni ([16]),
                   //    x = grad_x (grad_n x grad_d, rows of A), z = grad_z (grad_m x grad_d, columns of C); A's first n columns are read back
+                  // 5: the operands of 4; C (fp64) [tile_row * (n / tile) + tile_col][column of the tile][17] = sum over the tile's ROWS of
+                  //    Q_ni A_ni (x_nd / ls_d - z_id / ls_d) for d < grad_d (entries [0, 16)) and of Q_ni A_ni ([16])
   unsigned* amax;
   const void* amax_base;
   const double* cov_q;

@@ -18,9 +18,11 @@
 // option "sparse_panel" (sparse_panel_for: F within half of the 256 MB Infinity Cache).
 //
 // Training (gpk_sparse_hold / gpk_sparse_eval): the rows stay on the device, an evaluation accumulates S again, assembles the
-// model and, for the gradient of the bound, runs ONE more pass over the rows (grad_pass: F again, a tile GEMM Q = F C whose
+// model and, for the gradient of the bound, runs ONE more pass over the rows (rows_pass: F again, a tile GEMM Q = F C whose
 // epilogue reduces Q o Kfu o ((x - z) / ls)^2 per tile without storing Q, a fixed-order sum of the tiles); the m x m part is
-// gpk_wtw, tile GEMMs and gpk_lml_grad's pass on Z.  include/gpk.h has the formulas.
+// gpk_wtw, tile GEMMs and gpk_lml_grad's pass on Z.  gpk_sparse_eval_z also moves Z and differentiates with respect to it: the
+// same loop once more with the epilogue that reduces Q o Kfu o (x - z) / ls per column, and sparse_kuu_z_kernel for the Kuu
+// term.  include/gpk.h has the formulas.
 //
 // The assembly (gpk_sparse_finalize) and the serving (gpk_sparse_predict) are host code over entries that exist: gpk_gram /
 // gpk_potrf / gpk_trtri, tile GEMMs with triangular k-ranges, gpk_lml_terms, gpk_predict_host_multi (the sparse model is
@@ -360,13 +362,77 @@ __global__ __launch_bounds__(256) void sparse_dots_kernel(const double* __restri
   }
 }
 
-// The row pass of the bound's gradient: sums[d] = sum_ni Q_ni Kfu_ni ((x_nd - z_id) / ls_d)^2 (d < D), sums[16] = sum_ni
-// Q_ni Kfu_ni with Q = F Cm, F = [Kfu | Yn], panel by panel with the panel rule of `accumulate`.  Per panel: sparse_panel_kernel
-// regenerates F, ONE tile GEMM (rows_p x mp, k = nt: no k-slabs, a 14 336-row panel at m = 1024 is 896 tiles) whose epilogue
-// keeps Q in registers and writes GPK_GRAD_W sums per tile, and sparse_sum_kernel adds the tiles' sums in tile order to the
-// running sums.  No floating-point atomics.
-int grad_pass(gpk_handle h, const double* X, const double* Yn, int64_t n, const double* Z, int64_t m, int D, int P,
-              const double* ls, double sf2, const double* Cm, int64_t ldc, double* sums) {
+// R[c][w] (+)= sum over the tile rows tm, in tile order, of the column sums of epilogue 5,
+// partial[((tm * ntn + c / ts) * ts + c % ts) * GPK_GRAD_W + w]: 64 entries of R per workgroup, four interleaved strided sums
+// each and a fixed-order sum of the four; accumulate != 0 adds to what R holds (panel after panel)
+__global__ __launch_bounds__(256) void sparse_colsum_kernel(const double* __restrict__ partial, int ntm, int ntn, int ts,
+                                                            double* __restrict__ R, int accumulate) {
+  __shared__ double red[4][64];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const long long e = (long long)blockIdx.x * 64 + tx;        // (mp * GPK_GRAD_W is a multiple of 64)
+  const int c = (int)(e / GPK_GRAD_W), w = (int)(e - (long long)c * GPK_GRAD_W);
+  const int tn = c / ts, cl = c - tn * ts;
+  double s = 0.0;
+  for (int tm = ty; tm < ntm; tm += 4) s += partial[(((long long)tm * ntn + tn) * ts + cl) * GPK_GRAD_W + w];
+  red[ty][tx] = s;
+  __syncthreads();
+  if (ty == 0) {
+    const double v = (red[0][tx] + red[1][tx]) + (red[2][tx] + red[3][tx]);
+    R[e] = accumulate ? R[e] + v : v;
+  }
+}
+
+// V[i][d] = 2 sum_j GammaK_ij Kuu0_ij (z_jd / ls_d - z_id / ls_d) for d < D, GammaK_ij = (P / 2) M_ij - alpha_i . alpha_j / 2,
+// Kuu0_ij = sf2 exp(-0.5 |(z_i - z_j) / ls|^2) recomputed by exact differences of the divided coordinates (as
+// sparse_panel_kernel): the inducing input i < m per workgroup, M = Kuu^-1 - Sigma~ - Kuu^-1 G Kuu^-1 / s2 full (ld = mp), thread t
+// takes j = t, t + 256, .. in index order, then a tree.  V is m x 16 (zero for d >= D).  Bound by the m^2 doubles of M.
+__global__ __launch_bounds__(256) void sparse_kuu_z_kernel(const double* __restrict__ Z, int m, int D, int P, SpLs ls, double sf2,
+                                                           const double* __restrict__ M, int mp, const double* __restrict__ alpha,
+                                                           double* __restrict__ V) {
+  __shared__ double red[256 * 17];
+  __shared__ double zi[GPK_MAX_D_PREDICT], ai[GPK_MAX_P];
+  const int i = blockIdx.x, tid = threadIdx.x;
+  if (tid < D) zi[tid] = Z[(long long)i * D + tid] / ls.v[tid];
+  if (tid >= 64 && tid - 64 < P) ai[tid - 64] = alpha[(long long)i * P + tid - 64];
+  __syncthreads();
+  double v[GPK_MAX_D_PREDICT];
+#pragma unroll
+  for (int d = 0; d < GPK_MAX_D_PREDICT; ++d) v[d] = 0.0;
+  for (int j = tid; j < m; j += 256) {
+    double df[GPK_MAX_D_PREDICT], d2 = 0.0;
+#pragma unroll
+    for (int d = 0; d < GPK_MAX_D_PREDICT; ++d) {
+      df[d] = d < D ? Z[(long long)j * D + d] / ls.v[d] - zi[d] : 0.0;
+      d2 = __builtin_fma(df[d], df[d], d2);
+    }
+    double aa = 0.0;
+    for (int p = 0; p < P; ++p) aa = __builtin_fma(ai[p], alpha[(long long)j * P + p], aa);
+    const double w = ((double)P * M[(long long)i * mp + j] - aa) * (sf2 * gpk_exp_neg(-0.5 * d2));     // 2 GammaK_ij Kuu0_ij
+#pragma unroll
+    for (int d = 0; d < GPK_MAX_D_PREDICT; ++d) v[d] = __builtin_fma(w, df[d], v[d]);
+  }
+#pragma unroll
+  for (int d = 0; d < GPK_MAX_D_PREDICT; ++d) red[tid * 17 + d] = v[d];
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (tid < off)
+#pragma unroll
+      for (int d = 0; d < GPK_MAX_D_PREDICT; ++d) red[tid * 17 + d] += red[(tid + off) * 17 + d];
+    __syncthreads();
+  }
+  if (tid < GPK_MAX_D_PREDICT) V[(long long)i * GPK_MAX_D_PREDICT + tid] = red[tid];
+}
+
+// The passes over the rows behind the bound's gradient, panel by panel with the panel rule of `accumulate`.  Per panel:
+// sparse_panel_kernel regenerates F = [Kfu | Yn], ONE tile GEMM Q = F Cm (rows_p x mp, k = nt: no k-slabs, a 14 336-row panel at
+// m = 1024 is 896 tiles) keeps Q in registers and its epilogue reduces T = Q o Kfu, and one launch adds the tiles' sums in tile
+// order to the running sums.  No floating-point atomics.
+//   epilogue 4, the row pass (hyper-parameters): out = sums (17): [d] = sum_ni T_ni ((x_nd - z_id) / ls_d)^2 (d < D), [16] =
+//     sum_ni T_ni; GPK_GRAD_W sums per tile, sparse_sum_kernel;
+//   epilogue 5, the column pass (inducing inputs): out = R (mp x 17): [i][d] = sum_n T_ni (x_nd / ls_d - z_id / ls_d) (d < D),
+//     [i][16] = sum_n T_ni; GPK_GRAD_W sums per column of every tile, sparse_colsum_kernel.
+int rows_pass(gpk_handle h, int epilogue, const double* X, const double* Yn, int64_t n, const double* Z, int64_t m, int D, int P,
+              const double* ls, double sf2, const double* Cm, int64_t ldc, double* out) {
   const int64_t mp = gpk_padded(m), nt = mp + NB;
   SpLs l;
   for (int d = 0; d < D; ++d) {
@@ -376,8 +442,9 @@ int grad_pass(gpk_handle h, const double* X, const double* Yn, int64_t n, const 
   const int64_t panel = sparse_panel_for(h, mp);
   const int64_t f_rows = round_up(n < panel ? n : panel, NB);
   const size_t max_tiles = (size_t)(f_rows / 64) * (size_t)(mp / 64);
+  const size_t per_tile = epilogue == 4 ? (size_t)GPK_GRAD_W : (size_t)64 * GPK_GRAD_W;    // (of a 64-tile: the larger total)
   void* ws = nullptr;
-  GPK_TRY(gpk_scratch(h, ((size_t)f_rows * nt + max_tiles * GPK_GRAD_W) * sizeof(double), &ws));
+  GPK_TRY(gpk_scratch(h, ((size_t)f_rows * nt + max_tiles * per_tile) * sizeof(double), &ws));
   double* F = (double*)ws;
   double* partial = F + (size_t)f_rows * nt;
   gpk_time_begin(h, GPK_TIMED_SPARSE_PASS);
@@ -388,14 +455,19 @@ int grad_pass(gpk_handle h, const double* X, const double* Yn, int64_t n, const 
                        X + r0 * D, Yn + r0 * P, (long long)nr, Z, (int)m, D, P, l, sf2, F, (long long)nt, (int)mp);
     GPK_LAUNCH_CHECK(h);
     GemmArgs g = gemm_args(F, nt, 0, Cm, ldc, 1, partial, GPK_GRAD_W, (int)rows_p, (int)mp, (int)nt, 1.0, 0.0);
-    g.epilogue = 4;
+    g.epilogue = epilogue;
     g.grad_x = X + r0 * D; g.grad_z = Z; g.grad_n = (int)nr; g.grad_m = (int)m; g.grad_d = D;
     for (int d = 0; d < D; ++d) g.grad_ls[d] = ls[d];
     const int64_t tile = gpk_gemm_tile(h, g), ntiles = (rows_p / tile) * (mp / tile);
-    GPK_REQUIRE(h, (size_t)ntiles <= max_tiles, "sparse: tile count of the row pass");
+    GPK_REQUIRE(h, (size_t)ntiles * (epilogue == 4 ? 1 : (size_t)tile) <= max_tiles * (epilogue == 4 ? 1 : 64),
+                "sparse: tile count of the pass over the rows");
     GPK_TRY(gpk_gemm(h, GPK_F64, g));
-    hipLaunchKernelGGL(sparse_sum_kernel, dim3(GPK_GRAD_W), dim3(256), 0, h->stream, (const double*)partial, (long long)ntiles,
-                       GPK_GRAD_W, sums, r0 > 0 ? 1 : 0);
+    if (epilogue == 4)
+      hipLaunchKernelGGL(sparse_sum_kernel, dim3(GPK_GRAD_W), dim3(256), 0, h->stream, (const double*)partial, (long long)ntiles,
+                         GPK_GRAD_W, out, r0 > 0 ? 1 : 0);
+    else
+      hipLaunchKernelGGL(sparse_colsum_kernel, dim3((unsigned)(mp * GPK_GRAD_W / 64)), dim3(256), 0, h->stream,
+                         (const double*)partial, (int)(rows_p / tile), (int)(mp / tile), (int)tile, out, r0 > 0 ? 1 : 0);
     GPK_LAUNCH_CHECK(h);
   }
   gpk_time_end(h);
@@ -421,7 +493,8 @@ struct gpk_sparse {
   gpk_dev<double> rows, q;
   // gpk_sparse_hold: the held rows X (held_n x D) and their normalised targets (held_n x P); gpk_sparse_eval's gradient: the
   // coefficient matrix of the row pass ((mp + 128) x mp) and the per-row sums of sparse_dots_kernel (m x 4)
-  gpk_dev<double> hX, hY, Cm, dots;
+  // gradient with respect to Z: the column pass' sums (mp x 17), then the Kuu term (m x 16)
+  gpk_dev<double> hX, hY, Cm, dots, zg;
   gpk_dev<void> work;
 };
 
@@ -621,7 +694,9 @@ int sparse_assemble(gpk_handle h, gpk_sparse* s, int* info) {
 // The gradient of the bound of the model just assembled, with respect to log [ls_0 .. ls_{D-1}, noise, sf2] (g: D + 2 values).
 // Buffers of the assembly that the served model does not need are reused: Kuu (Luu) <- Kuu^-1, Bm (LB) <- Sigma~, WB <-
 // Kuu^-1 G, A1 <- Kuu^-1 G Kuu^-1 and then the matrix of the Kuu term, pan[1] <- G alpha_u.  One synchronisation.
-int sparse_gradient(gpk_handle h, gpk_sparse* s, double* g) {
+// gradZ != NULL (host m x D): also dL/dZ in raw coordinates, (U + V) / ls - behind the launches above, the matrix of the Kuu
+// term is mirrored to a full matrix, sparse_kuu_z_kernel forms V and the column pass U (include/gpk.h, gpk_sparse_eval_z).
+int sparse_gradient(gpk_handle h, gpk_sparse* s, double* g, double* gradZ) {
   const int64_t m = s->m, mp = s->mp, nt = s->nt;
   const int imp = (int)mp, P = s->P, D = s->D;
   const double s2 = s->sigma2, is2 = 1.0 / s2;
@@ -670,8 +745,29 @@ int sparse_gradient(gpk_handle h, gpk_sparse* s, double* g) {
   GPK_LAUNCH_CHECK(h);
   // the Kuu term: gpk_lml_grad's sums on (Z, alpha_u, Kuu^-1 - Sigma~ - M3 / s2) are -2 sum GammaK o Kuu0 o (...)
   GPK_TRY(gpk_lml_grad_enqueue(h, s->Z, m, D, s->ls, s->sf2, s->alpha, P, M3, mp, d_kuu));
-  GPK_TRY(grad_pass(h, s->hX, s->hY, s->held_n, s->Z, m, D, P, s->ls, s->sf2, s->Cm, mp, d_rows));
+  GPK_TRY(rows_pass(h, 4, s->hX, s->hY, s->held_n, s->Z, m, D, P, s->ls, s->sf2, s->Cm, mp, d_rows));
+  std::vector<double> zg;
+  if (gradZ) {
+    const size_t nr = (size_t)mp * GPK_GRAD_W, nv = (size_t)m * GPK_MAX_D_PREDICT;
+    if (!s->zg) GPK_TRY(s->zg.alloc(h, nr + nv));
+    double *R = s->zg, *V = R + nr;
+    SpLs l;
+    for (int d = 0; d < D; ++d) l.v[d] = s->ls[d];
+    hipLaunchKernelGGL(sparse_reduce_kernel, dim3(mirror_blocks), dim3(256), 0, h->stream, M3, (long long)mp, (const double*)M3, 0,
+                       0ll, imp);
+    GPK_LAUNCH_CHECK(h);
+    hipLaunchKernelGGL(sparse_kuu_z_kernel, dim3((unsigned)m), dim3(256), 0, h->stream, (const double*)s->Z, (int)m, D, P, l, s->sf2,
+                       (const double*)M3, imp, (const double*)s->alpha, V);
+    GPK_LAUNCH_CHECK(h);
+    GPK_TRY(rows_pass(h, 5, s->hX, s->hY, s->held_n, s->Z, m, D, P, s->ls, s->sf2, s->Cm, mp, R));
+    zg.resize(nr + nv);      // (pageable: the runtime stages this copy; the small sums above come through the pinned block)
+    GPK_CHECK_HIP(h, hipMemcpyAsync(zg.data(), R, (nr + nv) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  }
   GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
+  if (gradZ)
+    for (int64_t i = 0; i < m; ++i)
+      for (int d = 0; d < D; ++d)
+        gradZ[i * D + d] = (zg[(size_t)i * GPK_GRAD_W + d] + zg[(size_t)mp * GPK_GRAD_W + (size_t)i * GPK_MAX_D_PREDICT + d]) / s->ls[d];
   const double *kuu = h->h_small + 64, *rows = h->h_small + 96, *dots = h->h_small + 128;
   const double N = (double)s->n_rows, Pd = (double)P, sf2 = s->sf2;
   for (int d = 0; d < D; ++d) g[d] = rows[d] - 0.5 * kuu[d];
@@ -703,7 +799,20 @@ extern "C" int gpk_sparse_grad_pass(gpk_handle h, const double* X, const double*
               "sparse_grad_pass: Cm must be 16-byte aligned with an even ldc >= gpk_padded(m)");
   GPK_REQUIRE(h, sf2 > 0.0 && std::isfinite(sf2), "sparse_grad_pass: sf2 must be positive");
   GPK_REQUIRE(h, h->batch == 1, "sparse_grad_pass: not available in batched mode");
-  return grad_pass(h, X, Yn, n, Z, m, D, P, ls, sf2, Cm, ldc, sums);
+  return rows_pass(h, 4, X, Yn, n, Z, m, D, P, ls, sf2, Cm, ldc, sums);
+}
+
+extern "C" int gpk_sparse_zgrad_pass(gpk_handle h, const double* X, const double* Yn, int64_t n, const double* Z, int64_t m, int D,
+                                     int P, const double* ls, double sf2, const double* Cm, int64_t ldc, double* R) {
+  if (!h) return GPK_BAD_ARG;
+  GPK_REQUIRE(h, X && Yn && Z && ls && Cm && R, "sparse_zgrad_pass: null pointer");
+  GPK_REQUIRE(h, n >= 1 && n < (1ll << 40) && m >= 1 && m <= SP_MAX_M, "sparse_zgrad_pass: need n >= 1, 1 <= m <= 16384");
+  GPK_REQUIRE(h, D >= 1 && D <= GPK_MAX_D_PREDICT && P >= 1 && P <= GPK_MAX_P, "sparse_zgrad_pass: need 1 <= D <= 16, 1 <= P <= GPK_MAX_P");
+  GPK_REQUIRE(h, ldc >= gpk_padded(m) && ldc % 2 == 0 && ((uintptr_t)Cm % 16) == 0,
+              "sparse_zgrad_pass: Cm must be 16-byte aligned with an even ldc >= gpk_padded(m)");
+  GPK_REQUIRE(h, sf2 > 0.0 && std::isfinite(sf2), "sparse_zgrad_pass: sf2 must be positive");
+  GPK_REQUIRE(h, h->batch == 1, "sparse_zgrad_pass: not available in batched mode");
+  return rows_pass(h, 5, X, Yn, n, Z, m, D, P, ls, sf2, Cm, ldc, R);
 }
 
 extern "C" int gpk_sparse_hold(gpk_handle h, const double* X, const double* Y, int64_t n) {
@@ -745,9 +854,11 @@ extern "C" int gpk_sparse_hold(gpk_handle h, const double* X, const double* Y, i
   return GPK_OK;
 }
 
-extern "C" int gpk_sparse_eval(gpk_handle h, const double* ls, int n_ls, double sf2, double noise, double* bound, double* grad,
-                               int* info) {
-  if (!h) return GPK_BAD_ARG;
+namespace {
+
+// gpk_sparse_eval (Z == NULL, gradZ == NULL: its launches) and gpk_sparse_eval_z
+int sparse_eval(gpk_handle h, const double* Z, const double* ls, int n_ls, double sf2, double noise, double* bound, double* grad,
+                double* gradZ, int* info) {
   gpk_sparse* s = h->sparse;
   GPK_REQUIRE(h, s, "sparse_eval: no sparse model (call gpk_sparse_begin first)");
   GPK_REQUIRE(h, s->held_n > 0, "sparse_eval: no held rows (call gpk_sparse_hold; gpk_sparse_update releases them)");
@@ -757,10 +868,15 @@ extern "C" int gpk_sparse_eval(gpk_handle h, const double* ls, int n_ls, double 
               "sparse_eval: sf2 and the noise sigma^2 = noise + jitter must be positive");
   for (int d = 0; d < n_ls; ++d) GPK_REQUIRE(h, ls[d] > 0.0 && std::isfinite(ls[d]), "sparse_eval: length-scales must be positive");
   GPK_REQUIRE(h, h->batch == 1, "composite calls are not available in batched mode");
+  if (Z) GPK_TRY(gpk_require_finite(h, Z, s->m * s->D, "sparse_eval", "Z"));
   GPK_CHECK_HIP(h, hipSetDevice(h->device));
   const int D = s->D;
   *info = 0;
   s->finalized = false;
+  if (Z) {      // (the caller's array is read before the call goes on: no return path leaves the copy in flight)
+    GPK_CHECK_HIP(h, hipMemcpyAsync(s->Z, Z, (size_t)s->m * D * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
+  }
   s->sf2 = sf2; s->noise = noise; s->sigma2 = noise + s->jitter;
   for (int d = 0; d < D; ++d) s->ls[d] = ls[n_ls == 1 ? 0 : d];
   for (int d = 0; d < n_ls; ++d) s->ls_in[d] = ls[d];
@@ -773,10 +889,11 @@ extern "C" int gpk_sparse_eval(gpk_handle h, const double* ls, int n_ls, double 
   s->n_rows = s->held_n;
   GPK_TRY(sparse_assemble(h, s, info));
   *bound = s->bound;
-  if (!grad) return GPK_OK;
+  if (!grad && !gradZ) return GPK_OK;
   double g[GPK_MAX_D_PREDICT + 2];
-  rc = sparse_gradient(h, s, g);
+  rc = sparse_gradient(h, s, g, gradZ);
   if (rc != GPK_OK) { s->finalized = false; return rc; }
+  if (!grad) return GPK_OK;
   if (n_ls == 1) {
     double t = 0.0;
     for (int d = 0; d < D; ++d) t += g[d];
@@ -787,6 +904,20 @@ extern "C" int gpk_sparse_eval(gpk_handle h, const double* ls, int n_ls, double 
   grad[n_ls] = g[D];
   grad[n_ls + 1] = g[D + 1];
   return GPK_OK;
+}
+
+}  // namespace
+
+extern "C" int gpk_sparse_eval(gpk_handle h, const double* ls, int n_ls, double sf2, double noise, double* bound, double* grad,
+                               int* info) {
+  if (!h) return GPK_BAD_ARG;
+  return sparse_eval(h, nullptr, ls, n_ls, sf2, noise, bound, grad, nullptr, info);
+}
+
+extern "C" int gpk_sparse_eval_z(gpk_handle h, const double* Z, const double* ls, int n_ls, double sf2, double noise, double* bound,
+                                 double* grad, double* gradZ, int* info) {
+  if (!h) return GPK_BAD_ARG;
+  return sparse_eval(h, Z, ls, n_ls, sf2, noise, bound, grad, gradZ, info);
 }
 
 extern "C" int gpk_sparse_bound(gpk_handle h, double* bound, int64_t* n_rows) {

@@ -8,7 +8,9 @@ matrix cores), so `partial_fit` appends rows at any time; the model is assembled
 kernel's, e.g. those of an exact fit on a subset (`SparseGP.from_exact`).  `train` does: it keeps the rows on the device
 (`hold`, `gpk_sparse_hold`) and maximises the collapsed bound over the kernel's free parameters with L-BFGS-B, as GPflow's
 SGPR does; every evaluation (`log_bound`, `gpk_sparse_eval`) is the statistics pass, the m x m assembly and, for the
-gradient, one more pass over the rows - the inducing inputs stay where they are.
+gradient, one more pass over the rows.  `train(train_inducing=True)` optimises the inducing inputs together with the kernel,
+as SGPR does: `gpk_sparse_eval_z` moves Z and adds the bound's gradient with respect to it (a second pass over the rows and
+an m x m kernel); by default the inducing inputs stay where they are.
 
 The class keeps one libgpk handle of its own: the sparse model is the object behind that handle (include/gpk.h), the
 arrays that cross the boundary are host NumPy arrays.
@@ -44,6 +46,19 @@ def gradient_to_theta(comp, g):
     return comp.map_gradient(np.asarray(g, dtype=np.float64), len(g) - 2)
 
 
+def pack_inducing(theta, Z):
+    """The optimisation vector of `train(train_inducing=True)`: [theta, Z.ravel()] (Z row-major, raw coordinates)."""
+    return np.concatenate([np.asarray(theta, dtype=np.float64).ravel(), np.asarray(Z, dtype=np.float64).ravel()])
+
+
+def unpack_inducing(v, n_theta, shape):
+    """[theta, Z.ravel()] -> (theta, Z of `shape`), copies."""
+    v = np.asarray(v, dtype=np.float64)
+    if v.shape != (n_theta + shape[0] * shape[1],):
+        raise ValueError(f"expected {n_theta} + {shape[0]} x {shape[1]} values, got {v.shape}")
+    return v[:n_theta].copy(), v[n_theta:].reshape(shape).copy()
+
+
 class SparseGP:
     def __init__(self, kernel, inducing, *, alpha=1e-10, jitter_uu=None, y_mean=None, y_std=None, device=None):
         self.kernel = kernel
@@ -57,6 +72,7 @@ class SparseGP:
         if np.iterable(alpha):
             raise ValueError("per-sample alpha is not supported by the MI355X path")
         self.inducing_ = np.ascontiguousarray(Z)
+        self._inducing0 = self.inducing_.copy()       # where train(train_inducing=True) starts Z from, every time
         self.n_features_in_ = Z.shape[1]
         comp.ls_vector(self.n_features_in_)       # anisotropic kernels must match the inputs
         self.alpha = float(alpha)
@@ -195,47 +211,78 @@ class SparseGP:
         self._held = True
         return self
 
-    def log_bound(self, theta=None, eval_gradient=False):
+    def log_bound(self, theta=None, eval_gradient=False, inducing=None, eval_inducing_gradient=False):
         """The collapsed bound of the held rows at theta (the kernel's own layout: log-parameters, fixed ones excluded), and
         its gradient: the semantics of `GaussianProcessRegressor.log_marginal_likelihood`.  theta=None: the bound of the
-        current model.  A matrix that is not positive definite gives -inf and a zero gradient.  After the call the object is
-        the model at theta (`kernel_` follows)."""
+        current model.  `inducing` (m, D) moves the inducing inputs there first (`inducing_` follows);
+        `eval_inducing_gradient` returns (value, grad_theta, grad_Z), grad_Z (m, D) in raw coordinates.  A matrix that is not
+        positive definite gives -inf and zero gradients.  After the call the object is the model at theta (`kernel_` follows)
+        and at these inducing inputs.  Without the two inducing arguments the call is `gpk_sparse_eval`, launch for launch."""
         if theta is None:
-            if eval_gradient:
+            if eval_gradient or eval_inducing_gradient or inducing is not None:
                 raise ValueError("Gradient can only be evaluated for theta!=None")
             return self.bound()
         if not (self._live and getattr(self, "_held", False)):
             raise RuntimeError("log_bound(theta) needs held rows: call hold(X, y) first")
         theta = np.asarray(theta, dtype=np.float64)
         kern, comp, ls = hyper_from_theta(self.kernel_, theta)
+        Z = None
+        if inducing is not None:
+            Z = np.ascontiguousarray(np.array(inducing, dtype=np.float64, ndmin=2))
+            if Z.shape != self.inducing_.shape:
+                raise ValueError(f"inducing inputs must be {self.inducing_.shape}")
+            if not np.isfinite(Z).all():
+                raise ValueError("Input contains NaN or infinity")
         b, info = C.c_double(0.0), C.c_int(0)
         g = np.zeros(ls.size + 2)
+        gZ = np.zeros(self.inducing_.shape) if eval_inducing_gradient else None
         be = self._backend()
         with be.lock:
             be.bind_stream()
-            rc = be.lib.gpk_sparse_eval(be.h, _ptr(ls), ls.size, comp.sf2, comp.noise or 0.0, C.byref(b),
-                                        _ptr(g) if eval_gradient else None, C.byref(info))
+            if Z is None and gZ is None:
+                rc = be.lib.gpk_sparse_eval(be.h, _ptr(ls), ls.size, comp.sf2, comp.noise or 0.0, C.byref(b),
+                                            _ptr(g) if eval_gradient else None, C.byref(info))
+            else:
+                rc = be.lib.gpk_sparse_eval_z(be.h, None if Z is None else _ptr(Z), _ptr(ls), ls.size, comp.sf2, comp.noise or 0.0,
+                                              C.byref(b), _ptr(g) if eval_gradient or gZ is not None else None,
+                                              None if gZ is None else _ptr(gZ), C.byref(info))
             self.kernel_ = kern
+            if Z is not None:
+                self.inducing_ = Z
             if rc == _lib.GPK_NOT_PD:
                 self._final = False
+                if gZ is not None:
+                    return -np.inf, np.zeros_like(theta), np.zeros_like(gZ)
                 return (-np.inf, np.zeros_like(theta)) if eval_gradient else -np.inf
             be.check(rc)
         self._final = True
         value = float(b.value)
+        if gZ is not None:
+            return value, gradient_to_theta(comp, g), gZ
         return (value, gradient_to_theta(comp, g)) if eval_gradient else value
 
-    def train(self, X, y, n_restarts_optimizer=0, optimizer="fmin_l_bfgs_b", random_state=None):
+    def train(self, X, y, n_restarts_optimizer=0, optimizer="fmin_l_bfgs_b", random_state=None, train_inducing=False):
         """Holds the rows and maximises the bound over the kernel's free parameters within its bounds (L-BFGS-B, as
         `GaussianProcessRegressor.fit`; restarts start from draws within finite bounds and run one after the other).  Sets
-        `kernel_` and `bound_value_` and leaves the finalised model at the optimum."""
+        `kernel_` and `bound_value_` and leaves the finalised model at the optimum.  `train_inducing=True`: the optimisation
+        vector is [theta, Z.ravel()] with Z unbounded, as GPflow's SGPR trains its inducing variable; every start begins
+        at the constructor's inducing inputs (restarts redraw theta only), and `inducing_` is the trained Z afterwards."""
         from .gpr import _rng_from, constrained_optimization
         if self.kernel_.n_dims == 0:
             raise ValueError("train: the kernel has no free parameter")
+        Z0 = self.__dict__.get("_inducing0", self.inducing_).copy() if train_inducing else self.inducing_
         self.hold(X, y)
+        nt = self.kernel_.n_dims
 
-        def obj(theta):
-            value, grad = self.log_bound(theta, eval_gradient=True)
-            return -value, -grad
+        if train_inducing:
+            def obj(v):
+                theta, Z = unpack_inducing(v, nt, Z0.shape)
+                value, grad, gZ = self.log_bound(theta, eval_gradient=True, inducing=Z, eval_inducing_gradient=True)
+                return -value, -pack_inducing(grad, gZ)
+        else:
+            def obj(theta):
+                value, grad = self.log_bound(theta, eval_gradient=True)
+                return -value, -grad
 
         bounds = self.kernel_.bounds
         starts = [self.kernel_.theta]
@@ -244,10 +291,18 @@ class SparseGP:
                 raise ValueError("Multiple optimizer restarts (n_restarts_optimizer>0) requires that all bounds are finite.")
             rng = _rng_from(random_state)
             starts += [rng.uniform(bounds[:, 0], bounds[:, 1]) for _ in range(n_restarts_optimizer)]
+        if train_inducing:
+            starts = [pack_inducing(t0, Z0) for t0 in starts]
+            bounds = np.vstack([bounds, np.tile([-np.inf, np.inf], (Z0.size, 1))])
         optima = [constrained_optimization(optimizer, obj, t0, bounds) for t0 in starts]
         vals = [o[1] for o in optima]
         best = optima[int(np.argmin(vals))][0]
-        value = self.log_bound(best)            # the model at the optimum (the last evaluation need not be the best one)
+        # the model at the optimum (the last evaluation need not be the best one)
+        if train_inducing:
+            theta, Z = unpack_inducing(best, nt, Z0.shape)
+            value = self.log_bound(theta, inducing=Z)
+        else:
+            value = self.log_bound(best)
         if not np.isfinite(value):
             raise np.linalg.LinAlgError("train: the model at the optimum is not positive definite")
         self.bound_value_ = value
