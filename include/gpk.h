@@ -634,10 +634,39 @@ GPK_API int gpk_lml_batched(gpk_handle h, const double* thetas, int n_theta, dou
  * gpk_sparse_predict: the semantics of gpk_predict at GPK_F64: Xq (M x D), mean (M x P, un-normalised),
  *       mean(x) = y_mean + y_std k_u(x)^T alpha_u,   var_f(x) = sf2 - |Wuu k_u(x)|^2 + |WSigma k_u(x)|^2,
  *   var (M x P: variance times y_std^2; NULL = means only); var_includes_noise != 0: + the WhiteKernel level, clipped at 0;
- *   == 0: floored at 1e-10.  Checks that the queries are finite.  No kernel of its own: the model is two "models" on the
- *   shared inputs Z, (alpha_u, Wuu, kss) and (any alpha, WSigma, 0).  Up to 32 queries: gpk_predict_host_multi with B = 2 and
- *   a floor of -DBL_MAX (one call, two launches, one synchronisation; P > 1: gpk_predict_host once per inverse factor, four
- *   launches); more, or option small_path = 0: panels of the fused mean and two gpk_predict_var_inv launches.
+ *   == 0: floored at 1e-10.  Checks that the queries are finite.  Up to 32 queries (D, P <= 16): the two-factor form of the
+ *   small-batch kernels - small_cross_mean_kernel with ONE model (one K*, all P outputs), then small_var2_kernel with the
+ *   inverse factor (0: Wuu, 1: WSigma) as its second grid dimension; the last workgroup overall adds each factor's shares in the
+ *   one-factor kernel's order and writes max((kss - t0) - (0 - t1), floor) y_std[p]^2: the mean one launch, mean + variance
+ *   two, one synchronisation, for every P, and the bits of the route it replaces (gpk_predict_host_multi with B = 2, for
+ *   P > 1 two gpk_predict_host calls, combined on the host).  More queries, or option small_path = 0: panels of the fused
+ *   mean and two gpk_predict_var_inv launches.
+ * gpk_sparse_predict_grad: the semantics and units of gpk_predict_model_grad on the sparse posterior, host fp64 buffers: Xq
+ *   (M x D), mean (M x P), dmean (M x P x D) un-normalised; var (M x P) and dvar (M x P x D) already multiplied by
+ *   y_std[p]^2, or both NULL.  With k = k_u(x), u_jd = (z_jd - x_d) / ls_d^2:
+ *       dmean[m][p][d] = y_std[p] sum_j k_mj u_jd alpha_u[j][p]
+ *       dvar[m][d]     = -2 sum_j k_mj u_jd (c0 - c1)_jm,   c0 = Wuu^T (Wuu k),  c1 = WSigma^T (WSigma k)
+ *   dvar is the gradient of the UNCLIPPED variance; var is clipped as gpk_sparse_predict clips it.  Any M >= 1.  Up to 32
+ *   queries: the two-factor small-batch kernels - mean + Jacobian ONE launch (small_cross_mean_jac_kernel), all four results
+ *   three (+ small_var2_grad_kernel, small_wtv2_grad_kernel: the factor is blockIdx.y / z, both read the same K*, each keeps
+ *   its own V and shares, one ticket count over both, dvar = -2 / ls_d (s0 - s1) by the last workgroup), one synchronisation,
+ *   queries and results through the pinned, mapped block.  More, or option small_path = 0: query panels of gpk_predict_mean,
+ *   gpk_predict_mean_grad and gpk_predict_var_grad_inv once per inverse factor (floor -DBL_MAX; kss = 0 for WSigma), combined
+ *   by one small launch; one synchronisation per panel.
+ *   Replaces: nothing in the reference (GPflow's SGPR behind src/px4/gp.py would differentiate predict_f by reverse mode; the
+ *   consumer is the linearisation of quadrotor_gp_mpc/quadrotor_gp_mpc/mpc_controller.py:318); within this library, what
+ *   gpk_predict_model_grad is to the exact model, without forming two "models" (two K*, two mean shares).
+ * gpk_sparse_predict_cov: the semantics of gpk_predict_model_cov on the sparse posterior: mean (M x P, un-normalised), cov
+ *   (P x M x M: output p's block is y_std[p]^2 Sigma),
+ *       Sigma = K(Xq, Xq) + noise I - V0^T V0 + V1^T V1,   V0 = Wuu K*^T,  V1 = WSigma K*^T,
+ *   the model's WhiteKernel level on the diagonal only, not clipped, symmetric bit for bit.  1 <= M <= 16384.  Up to 32
+ *   queries: two launches (small_cross_mean_kernel, small_cov2_kernel: the factor is blockIdx.y, group sums per factor, one top
+ *   ticket over the groups of both; (k(a, b) - s0) + s1, mirrored), one synchronisation.  More, or option small_path = 0: the
+ *   stacked panel [V0; V1] by two tile GEMMs, its copy [V0; -V1], and ONE symmetric tile GEMM of depth 2 mp with the
+ *   covariance epilogue (gpk_predict_cov_inv's).
+ *   Replaces: GPflow's predict_f(full_cov=True) of the SGPR model behind src/px4/gp.py; the consumer is the sampling of
+ *   sklearn/gaussian_process/_gpr.py:497-537 (sample_y).
+ *   Both entries check that a finalised model exists and that the queries are finite, and refuse batched mode.
  * gpk_sparse_bound: the bound of the last gpk_sparse_finalize and the rows seen so far.
  * gpk_sparse_export / gpk_sparse_import: Z (m x D), the statistics G (m x m), g (m x P), yy (P), n_rows and the
  *   hyper-parameters - ls (n_ls values), hyper = [sf2, noise, jitter, jitter_uu], y_mean, y_std (P) - as host arrays; NULL
@@ -715,6 +744,9 @@ GPK_API int gpk_sparse_eval_z(gpk_handle h, const double* Z, const double* ls, i
 GPK_API int gpk_sparse_update(gpk_handle h, const double* X, const double* Y, int64_t n);
 GPK_API int gpk_sparse_finalize(gpk_handle h, int* info);
 GPK_API int gpk_sparse_predict(gpk_handle h, const double* Xq, int64_t M, double* mean, double* var, int var_includes_noise);
+GPK_API int gpk_sparse_predict_grad(gpk_handle h, const double* Xq, int64_t M, double* mean, double* var, double* dmean,
+                                    double* dvar, int var_includes_noise);
+GPK_API int gpk_sparse_predict_cov(gpk_handle h, const double* Xq, int64_t M, double* mean, double* cov);
 GPK_API int gpk_sparse_bound(gpk_handle h, double* bound, int64_t* n_rows);
 GPK_API int gpk_sparse_export(gpk_handle h, int64_t* m, int* D, int* P, int* n_ls, double* Z, double* G, double* g, double* yy,
                               int64_t* n_rows, double* ls, double* hyper, double* y_mean, double* y_std);

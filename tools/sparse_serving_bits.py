@@ -1,0 +1,119 @@
+#!/usr/bin/env python3
+"""SHA-256 of what gpk_sparse_predict returns on seeded inputs - the counterpart of serving_bits.py for the sparse model: one
+line per (m, D, P, M, request, small_path).  Two builds of the library compute the same bits exactly when their outputs are
+equal:
+    python tools/sparse_serving_bits.py > new.txt;  GPK_LIBRARY=/path/to/other/libgpk.so python tools/sparse_serving_bits.py > old.txt
+    python tools/sparse_serving_bits.py --compare old.txt new.txt
+Models (m, D): (130, 4) - mp = 256: a partial tile plus padding - and (1024, 9) - the control loop's size; P = 1, 3, 6 outputs;
+M = 1, 16, 17, 32 (both tile forms of the small-batch kernels and their edges) and 40 (the panel route); mean only and mean +
+variance, with and without the noise level; option small_path 1 and 0.  A library that exports gpk_sparse_predict_grad and
+gpk_sparse_predict_cov also prints their digests (lines only the new build has).  Plain ctypes on the C ABI: no torch."""
+import ctypes as C
+import hashlib
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+
+MODELS = ((130, 4), (1024, 9))
+OUTPUTS = (1, 3, 6)
+ROWS = (1, 16, 17, 32, 40)
+_dp = C.POINTER(C.c_double)
+
+
+def load_library():
+    from unmanned_aerial_vehicles_amd._build import LIB_PATH
+    lib = C.CDLL(os.environ.get("GPK_LIBRARY") or LIB_PATH)
+    i64, dbl, vp = C.c_int64, C.c_double, C.c_void_p
+    sig = {"gpk_create": [C.POINTER(vp), C.c_int], "gpk_set_stream": [vp, vp], "gpk_set_option": [vp, C.c_char_p, C.c_int],
+           "gpk_sparse_begin": [vp, _dp, i64, C.c_int, C.c_int, _dp, C.c_int, dbl, dbl, dbl, dbl, _dp, _dp],
+           "gpk_sparse_update": [vp, _dp, _dp, i64], "gpk_sparse_finalize": [vp, C.POINTER(C.c_int)],
+           "gpk_sparse_predict": [vp, _dp, i64, _dp, _dp, C.c_int],
+           "gpk_sparse_predict_grad": [vp, _dp, i64, _dp, _dp, _dp, _dp, C.c_int], "gpk_sparse_predict_cov": [vp, _dp, i64, _dp, _dp]}
+    for name, args in sig.items():
+        if hasattr(lib, name):
+            getattr(lib, name).argtypes, getattr(lib, name).restype = args, C.c_int
+    lib.gpk_last_error.restype, lib.gpk_last_error.argtypes = C.c_char_p, [vp]
+    lib.gpk_destroy.restype, lib.gpk_destroy.argtypes = None, [vp]
+    return lib
+
+
+def ptr(a):
+    return None if a is None else a.ctypes.data_as(_dp)
+
+
+def digest(*arrays):
+    h = hashlib.sha256()
+    for a in arrays:
+        if a is not None:
+            h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()
+
+
+def sparse_model(lib, m, D, P, N=3000):
+    """A finalised sparse model behind a fresh handle; returns (handle, check, rng)."""
+    rng = np.random.default_rng(1000 * m + P)
+    X = rng.standard_normal((N, D))
+    Y = np.ascontiguousarray(np.sin(X @ rng.standard_normal((D, P))) + 0.1 * rng.standard_normal((N, P)))
+    Z = np.ascontiguousarray(X[:m])
+    ls = np.ascontiguousarray(1.5 * (1.0 + 0.05 * np.arange(D)))
+    ym, ys = np.ascontiguousarray(Y.mean(axis=0)), np.ascontiguousarray(Y.std(axis=0))
+    h = C.c_void_p()
+    assert lib.gpk_create(C.byref(h), 0) == 0
+
+    def ok(rc):
+        if rc != 0:
+            raise RuntimeError(lib.gpk_last_error(h).decode())
+
+    ok(lib.gpk_set_stream(h, C.c_void_p(-1)))      # GPK_OWN_STREAM
+    ok(lib.gpk_sparse_begin(h, ptr(Z), m, D, P, ptr(ls), D, 1.1, 0.02, 1e-6, 1e-6, ptr(ym), ptr(ys)))
+    ok(lib.gpk_sparse_update(h, ptr(X), ptr(Y), N))
+    info = C.c_int(0)
+    ok(lib.gpk_sparse_finalize(h, C.byref(info)))
+    Q = np.ascontiguousarray(1.1 * rng.standard_normal((64, D)))
+    Q[:3] = X[:3]                       # queries at training rows (inducing inputs too): variances near the noise level
+    return h, ok, Q
+
+
+def run():
+    lib = load_library()
+    has_new = hasattr(lib, "gpk_sparse_predict_grad") and hasattr(lib, "gpk_sparse_predict_cov")
+    for m, D in MODELS:
+        for P in OUTPUTS:
+            h, ok, Q = sparse_model(lib, m, D, P)
+            for sp in (1, 0):
+                ok(lib.gpk_set_option(h, b"small_path", sp))
+                for M in ROWS:
+                    q = np.ascontiguousarray(Q[:M])
+                    tag = f"m={m} D={D} P={P} M={M} small_path={sp}"
+                    for req, want_var, incl in (("mean", False, 1), ("mean+var", True, 1), ("mean+var(latent)", True, 0)):
+                        mean, var = np.empty((M, P)), np.empty((M, P)) if want_var else None
+                        ok(lib.gpk_sparse_predict(h, ptr(q), M, ptr(mean), ptr(var), incl))
+                        print(f"sparse_predict {tag} request={req}", digest(mean, var))
+                    if has_new:
+                        mean, var, dm, dv = np.empty((M, P)), np.empty((M, P)), np.empty((M, P, D)), np.empty((M, P, D))
+                        ok(lib.gpk_sparse_predict_grad(h, ptr(q), M, ptr(mean), None, ptr(dm), None, 1))
+                        print(f"sparse_predict_grad {tag} request=mean+jac", digest(mean, dm))
+                        ok(lib.gpk_sparse_predict_grad(h, ptr(q), M, ptr(mean), ptr(var), ptr(dm), ptr(dv), 1))
+                        print(f"sparse_predict_grad {tag} request=all-four", digest(mean, var, dm, dv))
+                        cov = np.empty((P, M, M))
+                        ok(lib.gpk_sparse_predict_cov(h, ptr(q), M, ptr(mean), ptr(cov)))
+                        print(f"sparse_predict_cov {tag} request=mean+cov", digest(mean, cov))
+            lib.gpk_destroy(h)
+
+
+def compare(old, new):
+    a, b = (dict(line.rsplit(" ", 1) for line in open(f).read().splitlines() if line) for f in (old, new))
+    bad = sorted(k for k in a if a[k] != b.get(k))
+    for k in sorted(a):
+        print(("DIFFERENT " if k in bad else "equal     ") + k, a[k][:16], b.get(k, "missing")[:16])
+    only_new = sorted(k for k in b if k not in a)
+    print(f"{len(a)} digests of the old build, {len(bad)} different; {len(only_new)} lines only the new build prints")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    if len(sys.argv) == 4 and sys.argv[1] == "--compare":
+        sys.exit(compare(sys.argv[2], sys.argv[3]))
+    run()

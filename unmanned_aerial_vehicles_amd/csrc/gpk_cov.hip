@@ -20,9 +20,12 @@ __global__ void scale_queries_kernel(const double* __restrict__ Xq, long long M,
   if (e < M * D) U[e] = Xq[e] / ls.v[e % D];
 }
 
-// Sigma (Mp x ldc) from V (Np x Mp, ld Mp) and the queries: the scaled queries go to the handle's scratch
-int cov_from_v(gpk_handle h, const double* V, int64_t Np, const double* Xq, int64_t M, int D, const double* ls, double sf2,
-               double noise, double* cov, int64_t ldc) {
+}  // namespace
+
+// Sigma (Mp x ldc) from V (Np x Mp, ld Mp; VA == VB for the exact model) and the queries: the scaled queries go to the
+// handle's scratch
+int gpk_cov_from_v(gpk_handle h, const double* VA, const double* VB, int64_t Np, const double* Xq, int64_t M, int D,
+                   const double* ls, double sf2, double noise, double* cov, int64_t ldc) {
   GPK_REQUIRE(h, D >= 1 && D <= 16, "predict_cov: D must be in [1, 16]");
   const int64_t Mp = gpk_padded(M);
   LsInv l{};
@@ -36,7 +39,7 @@ int cov_from_v(gpk_handle h, const double* V, int64_t Np, const double* Xq, int6
   hipLaunchKernelGGL(scale_queries_kernel, dim3((unsigned)((M * D + 255) / 256)), dim3(256), 0, h->stream, Xq, (long long)M, D,
                      l, (double*)u);
   GPK_LAUNCH_CHECK(h);
-  GemmArgs g = gemm_args(V, Mp, 1, V, Mp, 1, cov, ldc, (int)Mp, (int)Mp, (int)Np, 1.0, 0.0);
+  GemmArgs g = gemm_args(VA, Mp, 1, VB, Mp, 1, cov, ldc, (int)Mp, (int)Mp, (int)Np, 1.0, 0.0);
   g.lower_only = 1;
   g.epilogue = 3;
   g.cov_q = (const double*)u;
@@ -49,6 +52,8 @@ int cov_from_v(gpk_handle h, const double* V, int64_t Np, const double* Xq, int6
   gpk_time_end(h);
   return rc;
 }
+
+namespace {
 
 int cov_args_ok(gpk_handle h, int dtype, int64_t N, int64_t Np, int64_t M, int64_t ldc) {
   GPK_REQUIRE(h, dtype == GPK_F64, "predict_cov: fp64 only (there is no fp32 covariance)");
@@ -79,7 +84,7 @@ extern "C" int gpk_predict_cov_inv(gpk_handle h, int dtype, const void* X, int64
   g.k_super = 1;            // W is zero right of the diagonal for GPK_ZERO_BAND_TILES - 1 tiles (gpk_trtri)
   g.heavy_first = 1;
   GPK_TRY(gpk_gemm(h, GPK_F64, g));
-  return cov_from_v(h, (const double*)work, Np, (const double*)Xq, M, D, ls, sf2, noise, cov, ldc);
+  return gpk_cov_from_v(h, (const double*)work, (const double*)work, Np, (const double*)Xq, M, D, ls, sf2, noise, cov, ldc);
 }
 
 extern "C" int gpk_predict_cov(gpk_handle h, int dtype, const void* X, int64_t N, int D, const double* ls, double sf2,
@@ -92,5 +97,5 @@ extern "C" int gpk_predict_cov(gpk_handle h, int dtype, const void* X, int64_t N
   // B = K*^T (Np x Mp), V = L^-1 B in place (the variance path's solve)
   GPK_TRY(gpk_cross_gram_t(h, GPK_F64, X, N, Xq, M, D, ls, sf2, work, Mp));
   GPK_TRY(gpk_trsm_lower_left(h, GPK_F64, L, Np, ldl, winv, work, Mp, Mp));
-  return cov_from_v(h, (const double*)work, Np, (const double*)Xq, M, D, ls, sf2, noise, cov, ldc);
+  return gpk_cov_from_v(h, (const double*)work, (const double*)work, Np, (const double*)Xq, M, D, ls, sf2, noise, cov, ldc);
 }

@@ -271,6 +271,28 @@ int gpk_small_grad_multi(gpk_handle h, int B, const double* const* X, const doub
                          const double* ls, const double* sf2, const double* y_mean, const double* y_std, const double* const* W,
                          int64_t Np, int64_t ldw, const double* kss, double floor_, const double* Xq, int64_t M, double* work,
                          double* mean_out, double* var_out, double* dmean_out, double* dvar_out);
+// The two-factor form (the sparse model, gpk_sparse.hip): ONE model with P outputs on the inputs X (its inducing inputs) whose
+// variance terms are kss - |W0 k*|^2 + |W1 k*|^2.  One K* and one set of mean (and Jacobian) shares from the first launch -
+// small_cross_mean[_jac]_kernel with one model - then the inverse factor as the grid dimension of the variance, covariance and
+// W^T V launches, the two factors combined by the last workgroup overall: the launch counts of one model whatever P is.
+//   GPK_SMALL_PREDICT  mean (M x P); with var_out the variance (M x P, clipped at floor_, times y_std[p]^2): 1 or 2 launches
+//   GPK_SMALL_GRAD     + dmean (M x P x D); with var_out / dvar_out also dvar (M x D, normalised-target units): 1 or 3 launches
+//   GPK_SMALL_COV      mean and cov (M x M, normalised-target units, noise on the diagonal, not clipped): 2 launches
+// work: gpk_small_work_doubles(call, Np, 2, M, D, P) doubles.
+int gpk_small_two(gpk_handle h, int call, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
+                  double sf2, const double* y_mean, const double* y_std, const double* W0, const double* W1, int64_t Np,
+                  int64_t ldw, double kss, double floor_, double noise, const double* Xq, int64_t M, double* work,
+                  double* mean_out, double* var_out, double* dmean_out, double* dvar_out, double* cov_out);
+// ... as a one-call serving entry (gpk_serve.hip): host queries in, host results out through the pinned, mapped block, one
+// synchronisation.  Outputs that the call does not produce are NULL.
+int gpk_serve_two(gpk_handle h, int call, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
+                  double sf2, const double* y_mean, const double* y_std, const double* W0, const double* W1, int64_t Np,
+                  int64_t ldw, double kss, double floor_, double noise, const double* Xq_host, int64_t M, double* mean_host,
+                  double* var_host, double* dmean_host, double* dvar_host, double* cov_host);
+// Sigma (Mp x ldc, symmetric bit for bit) = K(Xq, Xq) + noise I - VA^T VB from two operands (rows x Mp each, ld Mp) whose
+// product is symmetric (gpk_cov.hip: the covariance epilogue of the tile GEMM; VA == VB: the exact model's covariance)
+int gpk_cov_from_v(gpk_handle h, const double* VA, const double* VB, int64_t rows, const double* Xq, int64_t M, int D,
+                   const double* ls, double sf2, double noise, double* cov, int64_t ldc);
 
 // K* straight into the fragment-order fp16 x 2 split layout (gpk_gram.hip); D <= 16
 int gpk_cross_split2(gpk_handle h, const float* Xq, int64_t M, const float* X, int64_t N, int D, const double* ls,

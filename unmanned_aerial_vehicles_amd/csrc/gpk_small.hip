@@ -30,6 +30,13 @@
 //                            every model in ONE launch and all four results in three (gpk_small_grad_multi), each model
 //                            with its own shares and its own ticket counters.
 //
+//   two factors (K9)         the sparse model's variance terms are kss - |Wuu k*|^2 + |WSigma k*|^2 on ONE K* with P outputs: the
+//                            first launch runs with one model, and small_var2[_grad]_kernel, small_cov2_kernel and
+//                            small_wtv2_grad_kernel - the same bodies, template parameter TWO - take the inverse FACTOR as the grid
+//                            dimension that is the model elsewhere: shared K*, mean and Jacobian shares, per-factor V and shares, one
+//                            ticket count over the workgroups of both, and the last workgroup overall writes the combination
+//                            (gpk_small_two): any P at the launch counts of one model.
+//
 // Both results land in the caller's (pinned, mapped) output block; the queries are read from it as well.
 #include "gpk_internal.h"
 #include "gpk_math.h"
@@ -86,6 +93,29 @@ __device__ __forceinline__ double sum_shares(const double* p, unsigned first, un
     for (int u = 0; u < 8; ++u) s += v[u];
   }
   return s;
+}
+
+// sum_shares for two share blocks at once (the two-factor kernels): both blocks' loads of a round go out together - the last
+// workgroup waits for one miss latency per round, not two - and each block's shares are added in sum_shares' order.
+__device__ __forceinline__ void sum_shares2(const double* p0, const double* p1, unsigned first, unsigned step, unsigned shares,
+                                            long long stride, double& s0, double& s1) {
+  s0 = 0.0;
+  s1 = 0.0;
+  for (unsigned g = first; g < shares; g += 8 * step) {
+    double v0[8], v1[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const unsigned gu = g + u * step;
+      const long long at = (long long)min(gu, shares - 1) * stride;
+      v0[u] = p0[at];
+      v1[u] = p1[at];
+      if (gu >= shares) { v0[u] = 0.0; v1[u] = 0.0; }
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) s0 += v0[u];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) s1 += v1[u];
+  }
 }
 
 // The fixed-order sum of the mean shares, by whichever workgroup finishes last.  `lds`: 4 * SQ * SP doubles.  The
@@ -340,7 +370,11 @@ __device__ __forceinline__ double small_v_sum(const double (&red)[VW][NMB][16][1
 // GRAD (small_var_grad_kernel): the launch also stores its rows of V (Vs: per model Np x SQ, columns < 16 NMB written) for
 // small_wtv_grad_kernel, and workgroup 1 adds the mean Jacobian's shares of the previous launch.  The body is shared;
 // small_var_kernel keeps its signature and its launches.
-template <int NMB, bool GRAD>
+// TWO (small_var2_kernel, small_var2_grad_kernel; the sparse model): blockIdx.y is the inverse FACTOR (0: Wuu, 1: WSigma) of ONE
+// model with P outputs.  Both factors read the same K* and the same mean / Jacobian shares (model slot 0); each has its own
+// shares (and rows of V); ONE ticket count runs over the workgroups of both, and the last one overall adds each factor's
+// shares in the order above and writes var[m][p] = max((kss - t0) - (0 - t1), floor) y_std[p]^2.
+template <int NMB, bool GRAD, bool TWO>
 __device__ __forceinline__ void small_var_body(SmallK k, long long ldw, long long Np, const double* Ks,
                                                             int M, int P, double floor_, const double* pmean,
                                                             unsigned mean_shares, double* pvar, unsigned* counter,
@@ -348,19 +382,22 @@ __device__ __forceinline__ void small_var_body(SmallK k, long long ldw, long lon
                                                             const double* pjac, int D, double* dmean_out) {
   __shared__ double red[VW][NMB][16][17];
   __shared__ double sq[NMB][16][17];
-  const int b = blockIdx.y;
+  const int b = blockIdx.y;                    // the model, or the factor
+  const int o = TWO ? 0 : b;                   // the model slot of everything but W and the factor's own shares
+  const bool lead = TWO ? b == 0 : true;       // the factor whose workgroups 0 and 1 finish the means and the Jacobian
   const double* __restrict__ W = k.W[b];
-  const double kss = k.kss[b];
-  Ks += (long long)b * SQ * Np;
-  pmean += (long long)b * mean_shares * (SQ * SP);
+  const double kss = k.kss[o];
+  Ks += (long long)o * SQ * Np;
+  pmean += (long long)o * mean_shares * (SQ * SP);
+  double* const pvar0 = pvar;
   pvar += (long long)b * gridDim.x * SQ;
-  mean_out += (long long)b * M * P;
-  var_out += (long long)b * M;
-  counter += b;
+  mean_out += (long long)o * M * P;
+  var_out += (long long)o * M;
+  counter += o;
   if constexpr (GRAD) {
     Vs += (long long)b * Np * SQ;
-    pjac += (long long)b * mean_shares * (M * P * D);
-    dmean_out += (long long)b * M * P * D;
+    pjac += (long long)o * mean_shares * (M * P * D);
+    dmean_out += (long long)o * M * P * D;
   }
   const int tid = threadIdx.x;
   const long long r0 = (long long)blockIdx.x * SR;
@@ -382,20 +419,40 @@ __device__ __forceinline__ void small_var_body(SmallK k, long long ldw, long lon
   // The mean shares are complete since the previous launch: the workgroup with the shortest rows adds them up while
   // the others are still multiplying, off the critical path (scratch: the reduction buffer, free by now).
   static_assert(VW * 16 * 17 >= 4 * SQ * SP, "the reduction buffer doubles as the mean scratch");
-  if (blockIdx.x == 0) finish_means(pmean, mean_shares, M, P, k.ymean + b * P, k.ystd + b * P, mean_out, tid, &red[0][0][0][0]);
+  if (blockIdx.x == 0 && lead) finish_means(pmean, mean_shares, M, P, k.ymean + o * P, k.ystd + o * P, mean_out, tid, &red[0][0][0][0]);
   if constexpr (GRAD) {
-    if (blockIdx.x == 1) finish_jac(pjac, mean_shares, M, P, D, k.ystd + b * P, k.ls[b], dmean_out, tid, 64 * VW);
+    if (blockIdx.x == 1 && lead) finish_jac(pjac, mean_shares, M, P, D, k.ystd + o * P, k.ls[o], dmean_out, tid, 64 * VW);
   }
-  if (last_of(counter, gridDim.x, tid)) {
-    __shared__ double part[2 * VW][SQ];
+  if (last_of(counter, (TWO ? 2u : 1u) * gridDim.x, tid)) {
+    constexpr int NF = TWO ? 2 : 1;
+    __shared__ double part[NF][2 * VW][SQ];
     const int m = tid & 31, pt = tid >> 5;
-    part[pt][m] = (m < NMB * 16) ? sum_shares(pvar + m, pt, 2 * VW, gridDim.x, SQ) : 0.0;
+    if constexpr (!TWO) {
+      part[0][pt][m] = (m < NMB * 16) ? sum_shares(pvar + m, pt, 2 * VW, gridDim.x, SQ) : 0.0;
+    } else {
+      double s0 = 0.0, s1 = 0.0;
+      if (m < NMB * 16) sum_shares2(pvar0 + m, pvar0 + (long long)gridDim.x * SQ + m, pt, 2 * VW, gridDim.x, SQ, s0, s1);
+      part[0][pt][m] = s0;
+      part[1][pt][m] = s1;
+    }
     __syncthreads();
-    if (tid < M) {
-      double t = 0.0;
+    if constexpr (!TWO) {
+      if (tid < M) {
+        double t = 0.0;
 #pragma unroll
-      for (int k = 0; k < 2 * VW; ++k) t += part[k][tid];
-      var_out[tid] = fmax(kss - t, floor_);
+        for (int k = 0; k < 2 * VW; ++k) t += part[0][k][tid];
+        var_out[tid] = fmax(kss - t, floor_);
+      }
+    } else {
+      for (int e = tid; e < M * P; e += 64 * VW) {
+        const int mq = e / P, p = e - mq * P;
+        double t0 = 0.0, t1 = 0.0;
+#pragma unroll
+        for (int k = 0; k < 2 * VW; ++k) t0 += part[0][k][mq];
+#pragma unroll
+        for (int k = 0; k < 2 * VW; ++k) t1 += part[1][k][mq];
+        var_out[e] = fmax((kss - t0) - (0.0 - t1), floor_) * k.ystd[p] * k.ystd[p];
+      }
     }
   }
 }
@@ -405,7 +462,7 @@ __global__ __launch_bounds__(64 * VW) void small_var_kernel(SmallK k, long long 
                                                             int M, int P, double floor_, const double* pmean,
                                                             unsigned mean_shares, double* pvar, unsigned* counter,
                                                             double* mean_out, double* var_out) {
-  small_var_body<NMB, false>(k, ldw, Np, Ks, M, P, floor_, pmean, mean_shares, pvar, counter, mean_out, var_out, nullptr, nullptr, 0,
+  small_var_body<NMB, false, false>(k, ldw, Np, Ks, M, P, floor_, pmean, mean_shares, pvar, counter, mean_out, var_out, nullptr, nullptr, 0,
                              nullptr);
 }
 template <int NMB>
@@ -414,8 +471,27 @@ __global__ __launch_bounds__(64 * VW) void small_var_grad_kernel(SmallK k, long 
                                                                  unsigned mean_shares, double* pvar, unsigned* counter,
                                                                  double* mean_out, double* var_out, double* Vs,
                                                                  const double* pjac, int D, double* dmean_out) {
-  small_var_body<NMB, true>(k, ldw, Np, Ks, M, P, floor_, pmean, mean_shares, pvar, counter, mean_out, var_out, Vs, pjac, D,
+  small_var_body<NMB, true, false>(k, ldw, Np, Ks, M, P, floor_, pmean, mean_shares, pvar, counter, mean_out, var_out, Vs, pjac, D,
                             dmean_out);
+}
+
+// the two-factor forms (the sparse model: blockIdx.y = inverse factor; var_out is M x P, already times y_std[p]^2)
+template <int NMB>
+__global__ __launch_bounds__(64 * VW) void small_var2_kernel(SmallK k, long long ldw, long long Np, const double* Ks,
+                                                             int M, int P, double floor_, const double* pmean,
+                                                             unsigned mean_shares, double* pvar, unsigned* counter,
+                                                             double* mean_out, double* var_out) {
+  small_var_body<NMB, false, true>(k, ldw, Np, Ks, M, P, floor_, pmean, mean_shares, pvar, counter, mean_out, var_out, nullptr, nullptr,
+                                   0, nullptr);
+}
+template <int NMB>
+__global__ __launch_bounds__(64 * VW) void small_var2_grad_kernel(SmallK k, long long ldw, long long Np, const double* Ks,
+                                                                  int M, int P, double floor_, const double* pmean,
+                                                                  unsigned mean_shares, double* pvar, unsigned* counter,
+                                                                  double* mean_out, double* var_out, double* Vs,
+                                                                  const double* pjac, int D, double* dmean_out) {
+  small_var_body<NMB, true, true>(k, ldw, Np, Ks, M, P, floor_, pmean, mean_shares, pvar, counter, mean_out, var_out, Vs, pjac, D,
+                                  dmean_out);
 }
 
 constexpr int CG = 16;                   // workgroups per first-level group of the covariance reduction
@@ -434,24 +510,32 @@ __device__ __forceinline__ void tri_index(int t, int& i, int& j) {
 // (gridDim.x x CE), gcov (groups x CE), cov_out (M x M).  A model's sums are grouped by Np and M alone: its block has the
 // bits of that model served on its own.
 constexpr int COV_COUNTERS = 1 + (int)(GPK_SMALL_MAX_NP / SR / CG);
-template <int NMB>
-__global__ __launch_bounds__(64 * VW) void small_cov_kernel(SmallK k, long long ldw, long long Np, const double* Ks, int M,
-                                                            int D, int P, const double* Xq,
-                                                            const double* pmean, unsigned mean_shares, double* pcov,
-                                                            double* gcov, unsigned* counters, double* mean_out,
-                                                            double* cov_out) {
+// TWO (small_cov2_kernel; the sparse model): blockIdx.y is the inverse factor of ONE model.  Both factors read the same K* and
+// mean shares; each has its own shares, group sums and group counters (factor f: counters[f * COV_COUNTERS + 1 + g]); the top
+// level is ONE count (counters[0]) over the groups of both factors, and the last group overall writes
+// (k(a, b) - s0) + s1, mirrored.  Two ticket levels, each with its own last_of: a group's last workgroup reads its group's
+// shares behind the group's ticket, the last group reads all group sums - of both factors - behind the top ticket.
+template <int NMB, bool TWO>
+__device__ __forceinline__ void small_cov_body(SmallK k, long long ldw, long long Np, const double* Ks, int M,
+                                               int D, int P, const double* Xq,
+                                               const double* pmean, unsigned mean_shares, double* pcov,
+                                               double* gcov, unsigned* counters, double* mean_out,
+                                               double* cov_out) {
   __shared__ double red[VW][NMB][16][17];
   __shared__ double vt[NMB * 16][17];          // this workgroup's rows of V, transposed: [query][row]
   __shared__ double qs[SQ][SD + 1];
-  const int y = blockIdx.y;
+  const int f = blockIdx.y;                    // the model, or the factor
+  const int y = TWO ? 0 : f;                   // the model slot of everything but W and the factor's own shares
   const unsigned ng = (gridDim.x + CG - 1) / CG;
-  const double* __restrict__ W = k.W[y];
+  const double* __restrict__ W = k.W[f];
   const double sf2 = k.sf2[y], noise = k.noise[y];
   Ks += (long long)y * SQ * Np;
   pmean += (long long)y * mean_shares * (SQ * SP);
-  pcov += (long long)y * gridDim.x * CE;
-  gcov += (long long)y * ng * CE;
-  counters += y * COV_COUNTERS;
+  double* const gcov0 = gcov;
+  pcov += (long long)f * gridDim.x * CE;
+  gcov += (long long)f * ng * CE;
+  unsigned* const top = counters + y * COV_COUNTERS;
+  counters += f * COV_COUNTERS;
   mean_out += (long long)y * M * P;
   cov_out += (long long)y * M * M;
   const int tid = threadIdx.x;
@@ -474,18 +558,20 @@ __global__ __launch_bounds__(64 * VW) void small_cov_kernel(SmallK k, long long 
   }
   // the mean shares are complete since the previous launch (as in small_var_kernel; scratch: the reduction buffer)
   static_assert(VW * 16 * 17 >= 4 * SQ * SP, "the reduction buffer doubles as the mean scratch");
-  if (blockIdx.x == 0) finish_means(pmean, mean_shares, M, P, k.ymean + y * P, k.ystd + y * P, mean_out, tid, &red[0][0][0][0]);
+  if (blockIdx.x == 0 && f == y) finish_means(pmean, mean_shares, M, P, k.ymean + y * P, k.ystd + y * P, mean_out, tid, &red[0][0][0][0]);
   const unsigned g = blockIdx.x / CG, g0 = g * CG, g1 = min(g0 + CG, gridDim.x);
   if (!last_of(counters + 1 + g, g1 - g0, tid)) return;
   for (int t = tid; t < NE; t += 64 * VW) gcov[(long long)g * CE + t] = sum_shares(pcov + t, g0, 1, g1, CE);
-  if (!last_of(counters, ng, tid)) return;
+  if (!last_of(top, (TWO ? 2u : 1u) * ng, tid)) return;
   for (int e = tid; e < M * D; e += 64 * VW) qs[e / D][e % D] = Xq[e] / k.ls[y][e % D];
   __syncthreads();
   for (int t = tid; t < NE; t += 64 * VW) {
     int a, b;
     tri_index(t, a, b);
     if (a >= M) continue;
-    const double s = sum_shares(gcov + t, 0, 1, ng, CE);
+    double s, s2 = 0.0;
+    if constexpr (TWO) sum_shares2(gcov0 + t, gcov0 + (long long)ng * CE + t, 0, 1, ng, CE, s, s2);
+    else s = sum_shares(gcov + t, 0, 1, ng, CE);
     double kv;
     if (a == b) {
       kv = sf2 + noise;
@@ -499,10 +585,28 @@ __global__ __launch_bounds__(64 * VW) void small_cov_kernel(SmallK k, long long 
         }
       kv = sf2 * gpk_exp_neg(-0.5 * d2);
     }
-    const double v = kv - s;
+    double v = kv - s;
+    if constexpr (TWO) v += s2;
     cov_out[(long long)a * M + b] = v;
     cov_out[(long long)b * M + a] = v;
   }
+}
+
+template <int NMB>
+__global__ __launch_bounds__(64 * VW) void small_cov_kernel(SmallK k, long long ldw, long long Np, const double* Ks, int M,
+                                                            int D, int P, const double* Xq,
+                                                            const double* pmean, unsigned mean_shares, double* pcov,
+                                                            double* gcov, unsigned* counters, double* mean_out,
+                                                            double* cov_out) {
+  small_cov_body<NMB, false>(k, ldw, Np, Ks, M, D, P, Xq, pmean, mean_shares, pcov, gcov, counters, mean_out, cov_out);
+}
+template <int NMB>
+__global__ __launch_bounds__(64 * VW) void small_cov2_kernel(SmallK k, long long ldw, long long Np, const double* Ks, int M,
+                                                             int D, int P, const double* Xq,
+                                                             const double* pmean, unsigned mean_shares, double* pcov,
+                                                             double* gcov, unsigned* counters, double* mean_out,
+                                                             double* cov_out) {
+  small_cov_body<NMB, true>(k, ldw, Np, Ks, M, D, P, Xq, pmean, mean_shares, pcov, gcov, counters, mean_out, cov_out);
 }
 
 // Variance gradient of M <= 32 queries (model = blockIdx.z), after small_cross_mean_kernel (K*: Ks, query-major) and
@@ -512,24 +616,30 @@ __global__ __launch_bounds__(64 * VW) void small_cov_kernel(SmallK k, long long 
 // shares in order and writes dvar[m][d] = -2 / ls_d * sum.  pdv: gridDim.x * gridDim.y shares per model; counter: one per model.
 constexpr unsigned WTV_MAX_ROW_CHUNKS = 4;
 constexpr int GW = 16, GRG = 16, GT = GW * 2 * GRG;      // 512 threads: column jl, query half mh, row group rg
-__global__ __launch_bounds__(GT) void small_wtv_grad_kernel(SmallK k, long long ldw, long long N, long long Np, int D,
-                                                            const double* __restrict__ Ks_all, const double* __restrict__ Vs_all,
-                                                            const double* __restrict__ Xq, int M, double* pdv,
-                                                            unsigned* counter, double* dvar_out) {
+// TWO (small_wtv2_grad_kernel; the sparse model): blockIdx.z is the inverse factor of ONE model: the same K*, inputs and
+// queries, its own V and shares; ONE ticket count over the workgroups of both factors, and the last one overall adds each
+// factor's shares as above and writes dvar[m][d] = -2 / ls_d * (s0 - s1).
+template <bool TWO>
+__device__ __forceinline__ void small_wtv_grad_body(SmallK k, long long ldw, long long N, long long Np, int D,
+                                                    const double* __restrict__ Ks_all, const double* __restrict__ Vs_all,
+                                                    const double* __restrict__ Xq, int M, double* pdv,
+                                                    unsigned* counter, double* dvar_out) {
   __shared__ double red[GRG][GW][17];
   __shared__ double cm[GW][SQ + 1];
   __shared__ double xs[GW][SD + 1];
   __shared__ double qs[SQ][SD + 1];
   __shared__ double half[2][SQ * SD];
-  const int b = blockIdx.z;
+  const int b = blockIdx.z;                    // the model, or the factor
+  const int o = TWO ? 0 : b;                   // the model slot of everything but W, V and the factor's own shares
   const double* __restrict__ W = k.W[b];
-  const double* __restrict__ X = k.X[b];
-  const double* ls = k.ls[b];
-  const double* __restrict__ Ks = Ks_all + (long long)b * SQ * Np;
+  const double* __restrict__ X = k.X[o];
+  const double* ls = k.ls[o];
+  const double* __restrict__ Ks = Ks_all + (long long)o * SQ * Np;
   const double* __restrict__ Vs = Vs_all + (long long)b * Np * SQ;
+  double* const pdv0 = pdv;
   pdv += (long long)b * gridDim.x * gridDim.y * (M * D);
-  dvar_out += (long long)b * M * D;
-  counter += b;
+  dvar_out += (long long)o * M * D;
+  counter += o;
   const int tid = threadIdx.x, jl = tid & 15, mh = (tid >> 4) & 1, rg = tid >> 5;
   const long long j0 = (long long)blockIdx.x * GW, j = j0 + jl;
   // queries and this workgroup's training rows, divided by the length-scales
@@ -596,31 +706,56 @@ __global__ __launch_bounds__(GT) void small_wtv_grad_kernel(SmallK k, long long 
     for (int jj = 0; jj < GW; ++jj) s = __builtin_fma(Ks[(long long)m * Np + j0 + jj] * cm[jj][m], xs[jj][d] - qd, s);
     pdv[((long long)blockIdx.y * gridDim.x + blockIdx.x) * MD + t] = s;
   }
-  if (last_of(counter, gridDim.x * gridDim.y, tid)) {
+  if (last_of(counter, (TWO ? 2u : 1u) * gridDim.x * gridDim.y, tid)) {
     // each entry's shares in two halves (thread halves), each half in share order with sixteen loads in flight - the chain
     // of misses is the cost - then half 0 + half 1
+    constexpr int NF = TWO ? 2 : 1;
+    static_assert(GRG * GW * 17 >= 2 * SQ * SD, "the row groups' buffer doubles as the second factor's halves");
+    double (*half1)[SQ * SD] = reinterpret_cast<double (*)[SQ * SD]>(&red[0][0][0]);     // (free since the barriers above)
     const unsigned ns = gridDim.x * gridDim.y, h0 = (ns + 1) / 2;
     for (int base = 0; base < MD; base += GT / 2) {
       const int part = tid / (GT / 2), t = base + tid - part * (GT / 2);
       const unsigned g0 = part ? h0 : 0, g1 = part ? ns : h0;
       if (t < MD) {
-        double sum = 0.0;
-        for (unsigned g = g0; g < g1; g += 16) {
-          double v[16];
 #pragma unroll
-          for (int u = 0; u < 16; ++u) {
-            v[u] = pdv[(long long)min(g + u, g1 - 1) * MD + t];
-            if (g + u >= g1) v[u] = 0.0;
+        for (int f = 0; f < NF; ++f) {
+          const double* pf = TWO ? pdv0 + (long long)f * ns * MD : pdv;
+          double sum = 0.0;
+          for (unsigned g = g0; g < g1; g += 16) {
+            double v[16];
+#pragma unroll
+            for (int u = 0; u < 16; ++u) {
+              v[u] = pf[(long long)min(g + u, g1 - 1) * MD + t];
+              if (g + u >= g1) v[u] = 0.0;
+            }
+#pragma unroll
+            for (int u = 0; u < 16; ++u) sum += v[u];
           }
-#pragma unroll
-          for (int u = 0; u < 16; ++u) sum += v[u];
+          (f ? half1 : half)[part][t] = sum;
         }
-        half[part][t] = sum;
       }
       __syncthreads();
-      if (part == 0 && t < MD) dvar_out[t] = -2.0 / ls[t % D] * (half[0][t] + half[1][t]);
+      if (part == 0 && t < MD) {
+        if constexpr (TWO)
+          dvar_out[t] = -2.0 / ls[t % D] * ((half[0][t] + half[1][t]) - (half1[0][t] + half1[1][t]));
+        else
+          dvar_out[t] = -2.0 / ls[t % D] * (half[0][t] + half[1][t]);
+      }
     }
   }
+}
+
+__global__ __launch_bounds__(GT) void small_wtv_grad_kernel(SmallK k, long long ldw, long long N, long long Np, int D,
+                                                            const double* __restrict__ Ks_all, const double* __restrict__ Vs_all,
+                                                            const double* __restrict__ Xq, int M, double* pdv,
+                                                            unsigned* counter, double* dvar_out) {
+  small_wtv_grad_body<false>(k, ldw, N, Np, D, Ks_all, Vs_all, Xq, M, pdv, counter, dvar_out);
+}
+__global__ __launch_bounds__(GT) void small_wtv2_grad_kernel(SmallK k, long long ldw, long long N, long long Np, int D,
+                                                             const double* __restrict__ Ks_all, const double* __restrict__ Vs_all,
+                                                             const double* __restrict__ Xq, int M, double* pdv,
+                                                             unsigned* counter, double* dvar_out) {
+  small_wtv_grad_body<true>(k, ldw, N, Np, D, Ks_all, Vs_all, Xq, M, pdv, counter, dvar_out);
 }
 
 // The device work area of one call: offsets (in doubles) of the sub-buffers the launches below hand to the kernels, and
@@ -692,6 +827,10 @@ static_assert(GPK_SMALL_COV_COUNTERS >= GPK_SMALL_MAX_MODELS * COV_COUNTERS, "co
 // the ticket counters of small_wtv_grad_kernel (one per model): the last GPK_SMALL_MAX_MODELS of h->d_cov_count
 constexpr int WTV_COUNTER0 = GPK_SMALL_COV_COUNTERS - GPK_SMALL_MAX_MODELS;
 static_assert(WTV_COUNTER0 >= GPK_SMALL_MAX_MODELS * COV_COUNTERS, "the covariance reduction's counters come first");
+// the two-factor forms (gpk_small_two): factor f takes model slot f of the parameter block, of the group counters of the
+// covariance and of the work area's per-model shares; the single ticket counts are those of slot 0
+static_assert(GPK_SMALL_MAX_MODELS >= 2, "the two-factor kernels use model slots 0 and 1");
+static_assert(GPK_SMALL_COV_COUNTERS >= 2 * COV_COUNTERS + GPK_SMALL_MAX_MODELS, "group counters of both factors, then small_wtv_grad_kernel's");
 static_assert(SR == GW, "small_wtv_grad_kernel takes as many columns of W per workgroup as small_var_kernel takes rows");
 
 }  // namespace
@@ -802,6 +941,86 @@ int gpk_small_grad_multi(gpk_handle h, int B, const double* const* X, const doub
   rc = rc < 1 ? 1 : (rc > WTV_MAX_ROW_CHUNKS ? WTV_MAX_ROW_CHUNKS : rc);
   hipLaunchKernelGGL(small_wtv_grad_kernel, dim3(gb, rc, B), dim3(GT), 0, h->stream, k, (long long)ldw, (long long)N, (long long)Np, D,
                      (const double*)Ks, (const double*)Vs, Xq, (int)M, pdv, h->d_cov_count + WTV_COUNTER0, dvar_out);
+  GPK_LAUNCH_CHECK(h);
+  return GPK_OK;
+}
+
+int gpk_small_two(gpk_handle h, int call, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
+                  double sf2, const double* y_mean, const double* y_std, const double* W0, const double* W1, int64_t Np,
+                  int64_t ldw, double kss, double floor_, double noise, const double* Xq, int64_t M, double* work,
+                  double* mean_out, double* var_out, double* dmean_out, double* dvar_out, double* cov_out) {
+  GPK_REQUIRE(h, gpk_small_ok(Np, D, P, M) && Np == gpk_padded(N), "small two-factor: shape outside the small-batch path");
+  GPK_REQUIRE(h, X && alpha && mean_out, "small two-factor: null pointer");
+  const bool grad = call == GPK_SMALL_GRAD, cov = call == GPK_SMALL_COV;
+  GPK_REQUIRE(h, call == GPK_SMALL_PREDICT || grad || cov, "small two-factor: unknown call");
+  GPK_REQUIRE(h, !grad || (dmean_out && (var_out == nullptr) == (dvar_out == nullptr)), "small two-factor: null pointer");
+  GPK_REQUIRE(h, !cov || cov_out, "small two-factor: null pointer");
+  const bool factors = cov || var_out;
+  GPK_REQUIRE(h, !factors || (W0 && W1 && ldw >= Np && ldw % 2 == 0), "small two-factor: needs both inverse factors");
+  if (cov || (grad && factors)) GPK_TRY(ensure_cov_counters(h));
+  const double* Ws[2] = {W0, W1};
+  SmallK k{};
+  GPK_TRY(small_params(h, "small two-factor", 1, D, P, &X, &alpha, factors ? Ws : nullptr, ls, &sf2, factors ? &kss : nullptr, y_mean,
+                       y_std, k, cov ? &noise : nullptr));
+  if (factors) {
+    GPK_REQUIRE(h, ((uintptr_t)W1 % 16) == 0, "small two-factor: the inverse factor must be 16-byte aligned");
+    k.W[1] = W1;
+  }
+  const unsigned ga = (unsigned)(Np / SJ), gb = (unsigned)(Np / SR);
+  // the layout of two models: K*, the mean and the Jacobian shares are used once (slot 0), every other share per factor
+  const SmallWork wk = small_work(call, Np, 2, M, D, P);
+  double *Ks = work + wk.Ks, *pmean = work + wk.pmean;
+  const dim3 g1(ga, 1), g2(gb, 2), b1(256), b2(64 * VW);
+  if (!factors) {      // the mean, or the mean and its Jacobian: one launch
+    if (grad)
+      hipLaunchKernelGGL((small_cross_mean_jac_kernel<true>), g1, b1, 0, h->stream, k, (long long)N, (long long)Np, D, P, Xq, (int)M,
+                         (double*)nullptr, pmean, h->d_count, mean_out, work + wk.pjac, dmean_out);
+    else
+      hipLaunchKernelGGL(small_cross_mean_kernel<true>, g1, b1, 0, h->stream, k, (long long)N, (long long)Np, D, P, Xq, (int)M,
+                         (double*)nullptr, pmean, h->d_count, mean_out);
+    GPK_LAUNCH_CHECK(h);
+    return GPK_OK;
+  }
+  unsigned* vcount = h->d_count + GPK_SMALL_MAX_MODELS;
+  if (grad) {
+    double *pvar = work + wk.pvar, *pjac = work + wk.pjac, *Vs = work + wk.Vs, *pdv = work + wk.pdv;
+    hipLaunchKernelGGL(small_cross_mean_jac_kernel<false>, g1, b1, 0, h->stream, k, (long long)N, (long long)Np, D, P, Xq, (int)M, Ks,
+                       pmean, h->d_count, mean_out, pjac, dmean_out);
+    GPK_LAUNCH_CHECK(h);
+    if (M <= 16)
+      hipLaunchKernelGGL(small_var2_grad_kernel<1>, g2, b2, 0, h->stream, k, (long long)ldw, (long long)Np, (const double*)Ks, (int)M,
+                         P, floor_, (const double*)pmean, ga, pvar, vcount, mean_out, var_out, Vs, (const double*)pjac, D, dmean_out);
+    else
+      hipLaunchKernelGGL(small_var2_grad_kernel<2>, g2, b2, 0, h->stream, k, (long long)ldw, (long long)Np, (const double*)Ks, (int)M,
+                         P, floor_, (const double*)pmean, ga, pvar, vcount, mean_out, var_out, Vs, (const double*)pjac, D, dmean_out);
+    GPK_LAUNCH_CHECK(h);
+    unsigned rc = 256 / (gb * 2u);      // row chunks as in gpk_small_grad_multi, the two factors counted as two models
+    rc = rc < 1 ? 1 : (rc > WTV_MAX_ROW_CHUNKS ? WTV_MAX_ROW_CHUNKS : rc);
+    hipLaunchKernelGGL(small_wtv2_grad_kernel, dim3(gb, rc, 2), dim3(GT), 0, h->stream, k, (long long)ldw, (long long)N, (long long)Np,
+                       D, (const double*)Ks, (const double*)Vs, Xq, (int)M, pdv, h->d_cov_count + WTV_COUNTER0, dvar_out);
+    GPK_LAUNCH_CHECK(h);
+    return GPK_OK;
+  }
+  hipLaunchKernelGGL(small_cross_mean_kernel<false>, g1, b1, 0, h->stream, k, (long long)N, (long long)Np, D, P, Xq, (int)M, Ks, pmean,
+                     h->d_count, mean_out);
+  GPK_LAUNCH_CHECK(h);
+  if (cov) {
+    double *pcov = work + wk.pcov, *gcov = work + wk.gcov;
+    if (M <= 16)
+      hipLaunchKernelGGL(small_cov2_kernel<1>, g2, b2, 0, h->stream, k, (long long)ldw, (long long)Np, (const double*)Ks, (int)M, D, P,
+                         Xq, (const double*)pmean, ga, pcov, gcov, h->d_cov_count, mean_out, cov_out);
+    else
+      hipLaunchKernelGGL(small_cov2_kernel<2>, g2, b2, 0, h->stream, k, (long long)ldw, (long long)Np, (const double*)Ks, (int)M, D, P,
+                         Xq, (const double*)pmean, ga, pcov, gcov, h->d_cov_count, mean_out, cov_out);
+  } else {
+    double* pvar = work + wk.pvar;
+    if (M <= 16)
+      hipLaunchKernelGGL(small_var2_kernel<1>, g2, b2, 0, h->stream, k, (long long)ldw, (long long)Np, (const double*)Ks, (int)M, P,
+                         floor_, (const double*)pmean, ga, pvar, vcount, mean_out, var_out);
+    else
+      hipLaunchKernelGGL(small_var2_kernel<2>, g2, b2, 0, h->stream, k, (long long)ldw, (long long)Np, (const double*)Ks, (int)M, P,
+                         floor_, (const double*)pmean, ga, pvar, vcount, mean_out, var_out);
+  }
   GPK_LAUNCH_CHECK(h);
   return GPK_OK;
 }

@@ -24,11 +24,13 @@
 // same loop once more with the epilogue that reduces Q o Kfu o (x - z) / ls per column, and sparse_kuu_z_kernel for the Kuu
 // term.  include/gpk.h has the formulas.
 //
-// The assembly (gpk_sparse_finalize) and the serving (gpk_sparse_predict) are host code over entries that exist: gpk_gram /
-// gpk_potrf / gpk_trtri, tile GEMMs with triangular k-ranges, gpk_lml_terms, gpk_predict_host_multi (the sparse model is
-// two "models" on the shared inputs Z: (alpha_u, Wuu, kss = sf2) and (any alpha, WSigma, kss = 0)), gpk_predict_mean and
-// gpk_predict_var_inv; the buffers are gpk_dev members of the object and the serving goes through the query-panel loop
-// (gpk_compose.h, shared with gpk_model.hip and gpk_bmodel.hip).  DESIGN.md, K9.
+// The assembly (gpk_sparse_finalize) is host code over entries that exist: gpk_gram / gpk_potrf / gpk_trtri, tile GEMMs with
+// triangular k-ranges, gpk_lml_terms.  The serving (gpk_sparse_predict, gpk_sparse_predict_grad, gpk_sparse_predict_cov): up to
+// 32 queries the two-factor form of the small-batch kernels (gpk_small.hip, gpk_small_two through gpk_serve_two: one K*, P
+// outputs, the inverse factors Wuu and WSigma as a grid dimension, combined by the last workgroup); larger batches the
+// query-panel loop (gpk_compose.h, shared with gpk_model.hip and gpk_bmodel.hip) over gpk_predict_mean, gpk_predict_var_inv,
+// gpk_predict_mean_grad and gpk_predict_var_grad_inv once per factor with a small combining launch, and for the covariance the
+// stacked panel [Wuu K*; WSigma K*] with ONE symmetric tile GEMM.  The buffers are gpk_dev members of the object.  DESIGN.md, K9.
 #include <cfloat>
 
 #include "gpk_compose.h"
@@ -184,6 +186,26 @@ __global__ void sparse_var_kernel(const double* __restrict__ v0, const double* _
   const long long i = e / P;
   const int p = (int)(e - i * P);
   out[e] = fmax(v0[i] - v1[i], floor_) * ys.v[p] * ys.v[p];
+}
+
+// the gradient panels' counterpart: var[i][p] as above and dvar[i][p][d] = (g0[i][d] - g1[i][d]) y_std[p]^2
+// (g0 = d/dx (kss - |Wuu k|^2), g1 = d/dx (-|WSigma k|^2), both unclipped)
+__global__ void sparse_var_grad_kernel(const double* __restrict__ v0, const double* __restrict__ v1, const double* __restrict__ g0,
+                                       const double* __restrict__ g1, long long M, int P, int D, SpP ys, double floor_,
+                                       double* __restrict__ var, double* __restrict__ dvar) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= M * P * D) return;
+  const long long ip = e / D, i = ip / P;
+  const int d = (int)(e - ip * D), p = (int)(ip - i * P);
+  dvar[e] = (g0[i * D + d] - g1[i * D + d]) * (ys.v[p] * ys.v[p]);
+  if (d == 0) var[ip] = fmax(v0[i] - v1[i], floor_) * ys.v[p] * ys.v[p];
+}
+
+// the second operand of the covariance product: rows < mp of the stacked panel [V0; V1] as they are, rows >= mp negated
+__global__ void sparse_stack_kernel(const double* __restrict__ VA, long long mp, long long cols, double* __restrict__ VB) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= 2 * mp * cols) return;
+  VB[e] = e < mp * cols ? VA[e] : -VA[e];
 }
 
 int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
@@ -943,33 +965,10 @@ extern "C" int gpk_sparse_predict(gpk_handle h, const double* Xq, int64_t M, dou
   const double none = -std::numeric_limits<double>::max();
   const int64_t m = s->m, mp = s->mp;
   if (h->small_path && M <= GPK_SMALL_MAX_M && gpk_small_ok(mp, D, P, M)) {
-    if (P == 1) {
-      // two "models" on the shared inputs Z, one call: two launches, one synchronisation
-      const double *Xs[2] = {s->Z, s->Z}, *as[2] = {s->alpha, s->alpha}, *Ws[2] = {s->Wuu, s->WS};
-      double ls2[2 * GPK_MAX_D_PREDICT];
-      for (int d = 0; d < D; ++d) ls2[d] = ls2[D + d] = s->ls[d];
-      const double sf2s[2] = {s->sf2, s->sf2}, ym[2] = {s->y_mean[0], 0.0}, ys[2] = {s->y_std[0], 1.0}, ks[2] = {kss, 0.0};
-      std::vector<double> mb((size_t)2 * M), vb(var ? (size_t)2 * M : 0);
-      GPK_TRY(gpk_predict_host_multi(h, 2, Xs, as, m, D, ls2, sf2s, ym, ys, var ? Ws : nullptr, mp, mp, var ? ks : nullptr,
-                                     none, Xq, M, mb.data(), var ? vb.data() : nullptr));
-      for (int64_t i = 0; i < M; ++i) {
-        mean[i] = mb[(size_t)i];
-        if (var) var[i] = std::fmax(vb[(size_t)i] - vb[(size_t)(M + i)], floor_) * s->y_std[0] * s->y_std[0];
-      }
-      return GPK_OK;
-    }
-    // several outputs share the two inverse factors: the one-model entry twice (four launches)
-    std::vector<double> v0(var ? (size_t)M : 0), v1(var ? (size_t)M : 0), m2(var ? (size_t)M * P : 0);
-    GPK_TRY(gpk_predict_host(h, s->Z, s->alpha, m, D, P, s->ls, s->sf2, s->y_mean, s->y_std, var ? s->Wuu.p : nullptr, mp, mp, kss,
-                             none, Xq, M, mean, var ? v0.data() : nullptr));
-    if (var) {
-      GPK_TRY(gpk_predict_host(h, s->Z, s->alpha, m, D, P, s->ls, s->sf2, s->y_mean, s->y_std, s->WS, mp, mp, 0.0, none, Xq, M,
-                               m2.data(), v1.data()));
-      for (int64_t i = 0; i < M; ++i)
-        for (int p = 0; p < P; ++p)
-          var[i * P + p] = std::fmax(v0[(size_t)i] - v1[(size_t)i], floor_) * s->y_std[p] * s->y_std[p];
-    }
-    return GPK_OK;
+    // the two-factor small-batch kernels (gpk_small.hip): one K*, P outputs, the two inverse factors combined on the device -
+    // the mean one launch, mean + variance two, one synchronisation, whatever P is
+    return gpk_serve_two(h, GPK_SMALL_PREDICT, s->Z, s->alpha, m, D, P, s->ls, s->sf2, s->y_mean, s->y_std, var ? s->Wuu.p : nullptr,
+                         var ? s->WS.p : nullptr, mp, mp, kss, floor_, 0.0, Xq, M, mean, var, nullptr, nullptr, nullptr);
   }
   // query panels: the fused mean and two variance launches (one per inverse factor), combined on the device
   const int64_t panel = gpk_panel_rows(GPK_HOST_MAX_M, 1, M);      // (no byte budget: at most GPK_HOST_MAX_M rows)
@@ -993,6 +992,119 @@ extern "C" int gpk_sparse_predict(gpk_handle h, const double* Xq, int64_t M, dou
     }
     return GPK_OK;
   });
+}
+
+extern "C" int gpk_sparse_predict_grad(gpk_handle h, const double* Xq, int64_t M, double* mean, double* var, double* dmean,
+                                       double* dvar, int var_includes_noise) {
+  if (!h) return GPK_BAD_ARG;
+  gpk_sparse* s = h->sparse;
+  GPK_REQUIRE(h, s && s->finalized, "sparse_predict_grad: no finalised sparse model (call gpk_sparse_finalize first)");
+  GPK_REQUIRE(h, Xq && mean && dmean && M >= 1, "sparse_predict_grad: null pointer or empty batch");
+  GPK_REQUIRE(h, (var == nullptr) == (dvar == nullptr), "sparse_predict_grad: var and dvar come together (both or neither)");
+  GPK_REQUIRE(h, h->batch == 1, "composite calls are not available in batched mode");
+  GPK_CHECK_HIP(h, hipSetDevice(h->device));
+  const int D = s->D, P = s->P;
+  GPK_TRY(gpk_require_finite(h, Xq, M * D, "sparse_predict_grad", "Xq"));
+  const double kss = gpk_kss(s->sf2, s->noise, var_includes_noise), floor_ = gpk_var_floor(var_includes_noise);
+  const double none = -std::numeric_limits<double>::max();
+  const int64_t m = s->m, mp = s->mp;
+  if (h->small_path && M <= GPK_SMALL_MAX_M && gpk_small_ok(mp, D, P, M)) {
+    // mean + Jacobian one launch, all four results three, one synchronisation (gpk_small.hip, the two-factor kernels)
+    std::vector<double> g1(var ? (size_t)M * D : 0);
+    GPK_TRY(gpk_serve_two(h, GPK_SMALL_GRAD, s->Z, s->alpha, m, D, P, s->ls, s->sf2, s->y_mean, s->y_std, var ? s->Wuu.p : nullptr,
+                          var ? s->WS.p : nullptr, mp, mp, kss, floor_, 0.0, Xq, M, mean, var, dmean, var ? g1.data() : nullptr,
+                          nullptr));
+    if (var)      // output p carries y_std[p]^2, as in gpk_predict_model_grad
+      for (int64_t i = 0; i < M; ++i)
+        for (int p = 0; p < P; ++p) {
+          const double s2 = s->y_std[p] * s->y_std[p];
+          for (int d = 0; d < D; ++d) dvar[(i * P + p) * D + d] = g1[(size_t)i * D + d] * s2;
+        }
+    return GPK_OK;
+  }
+  // query panels: the fused mean and its Jacobian, the variance gradient once per inverse factor (three mp x panel work panels
+  // within 6 GiB, as gpk_predict_host_grad keeps them), combined on the device
+  const int64_t panel = gpk_panel_rows(6ull << 30, (size_t)3 * mp * sizeof(double), M);
+  const size_t nq = (size_t)panel * D, nm = (size_t)panel * P, nj = nm * D;
+  GPK_TRY(s->q.reserve(h, (nq + nm + nj + (var ? 2 * (size_t)panel + 2 * nq + nm + nj : 0)) * sizeof(double)));
+  if (var) GPK_TRY(s->work.reserve(h, (size_t)3 * mp * panel * sizeof(double)));
+  double *dq = s->q, *dmn = dq + nq, *ddm = dmn + nm, *dv0 = ddm + nj, *dv1 = dv0 + panel, *dg0 = dv1 + panel, *dg1 = dg0 + nq,
+         *dvar_ = dg1 + nq, *ddv = dvar_ + nm;
+  SpP ys;
+  for (int p = 0; p < GPK_MAX_P; ++p) ys.v[p] = p < P ? s->y_std[p] : 1.0;
+  return gpk_query_panels(h, Xq, M, D * sizeof(double), panel, dq, [&](int64_t m0, int64_t mc) -> int {
+    GPK_TRY(gpk_predict_mean(h, GPK_F64, s->Z, s->alpha, m, D, P, s->ls, s->sf2, s->y_mean, s->y_std, dq, mc, dmn));
+    GPK_TRY(gpk_predict_mean_grad(h, s->Z, s->alpha, m, D, P, s->ls, s->sf2, s->y_std, dq, mc, ddm));
+    GPK_CHECK_HIP(h, hipMemcpyAsync(mean + m0 * P, dmn, (size_t)mc * P * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    GPK_CHECK_HIP(h, hipMemcpyAsync(dmean + m0 * P * D, ddm, (size_t)mc * P * D * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (var) {
+      GPK_TRY(gpk_predict_var_grad_inv(h, s->Z, m, D, s->ls, s->sf2, s->Wuu, mp, mp, dq, mc, kss, none, (double*)s->work.p, dv0, dg0));
+      GPK_TRY(gpk_predict_var_grad_inv(h, s->Z, m, D, s->ls, s->sf2, s->WS, mp, mp, dq, mc, 0.0, none, (double*)s->work.p, dv1, dg1));
+      const long long tot = (long long)mc * P * D;
+      hipLaunchKernelGGL(sparse_var_grad_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, dv0, dv1, dg0, dg1,
+                         (long long)mc, P, D, ys, floor_, dvar_, ddv);
+      GPK_LAUNCH_CHECK(h);
+      GPK_CHECK_HIP(h, hipMemcpyAsync(var + m0 * P, dvar_, (size_t)mc * P * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      GPK_CHECK_HIP(h, hipMemcpyAsync(dvar + m0 * P * D, ddv, (size_t)mc * P * D * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    }
+    return GPK_OK;
+  });
+}
+
+extern "C" int gpk_sparse_predict_cov(gpk_handle h, const double* Xq, int64_t M, double* mean, double* cov) {
+  if (!h) return GPK_BAD_ARG;
+  gpk_sparse* s = h->sparse;
+  GPK_REQUIRE(h, s && s->finalized, "sparse_predict_cov: no finalised sparse model (call gpk_sparse_finalize first)");
+  GPK_REQUIRE(h, Xq && mean && cov && M >= 1 && M <= 16384, "sparse_predict_cov: null pointer or M outside [1, 16384]");
+  GPK_REQUIRE(h, h->batch == 1, "composite calls are not available in batched mode");
+  GPK_CHECK_HIP(h, hipSetDevice(h->device));
+  const int D = s->D, P = s->P;
+  GPK_TRY(gpk_require_finite(h, Xq, M * D, "sparse_predict_cov", "Xq"));
+  const int64_t m = s->m, mp = s->mp;
+  std::vector<double> sig((size_t)M * M);
+  if (h->small_path && M <= GPK_SMALL_MAX_M && gpk_small_ok(mp, D, P, M)) {
+    // two launches, one synchronisation (gpk_small.hip, the two-factor kernels)
+    GPK_TRY(gpk_serve_two(h, GPK_SMALL_COV, s->Z, s->alpha, m, D, P, s->ls, s->sf2, s->y_mean, s->y_std, s->Wuu, s->WS, mp, mp, 0.0,
+                          0.0, s->noise, Xq, M, mean, nullptr, nullptr, nullptr, sig.data()));
+  } else {
+    // one panel: K* (training-major), the stacked panel [V0; V1] = [Wuu K*; WSigma K*] by two tile GEMMs (the inverse factors'
+    // zero triangles skipped), its copy [V0; -V1], and ONE symmetric product of depth 2 mp whose epilogue forms
+    // K(Xq, Xq) + noise I - (V0^T V0 - V1^T V1) and stores every tile and its transpose
+    const int64_t Mp = gpk_padded(M);
+    const size_t nq = (size_t)M * D, nm = (size_t)M * P, nv = (size_t)mp * Mp;
+    GPK_TRY(s->q.reserve(h, (nq + nm) * sizeof(double)));
+    GPK_TRY(s->work.reserve(h, (5 * nv + (size_t)Mp * Mp) * sizeof(double)));
+    double *dq = s->q, *dmn = dq + nq;
+    double *Kt = (double*)s->work.p, *VA = Kt + nv, *VB = VA + 2 * nv, *dcov = VB + 2 * nv;
+    GPK_TRY(gpk_query_panels(h, Xq, M, D * sizeof(double), M, dq, [&](int64_t, int64_t) -> int {
+      GPK_TRY(gpk_predict_mean(h, GPK_F64, s->Z, s->alpha, m, D, P, s->ls, s->sf2, s->y_mean, s->y_std, dq, M, dmn));
+      GPK_CHECK_HIP(h, hipMemcpyAsync(mean, dmn, nm * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      GPK_TRY(gpk_cross_gram_t(h, GPK_F64, s->Z, m, dq, M, D, s->ls, s->sf2, Kt, Mp));
+      for (int f = 0; f < 2; ++f) {
+        GemmArgs g = gemm_args(f ? s->WS.p : s->Wuu.p, mp, 0, Kt, Mp, 1, VA + (size_t)f * nv, Mp, (int)mp, (int)Mp, (int)mp, 1.0, 0.0);
+        g.ke0 = GPK_TILE;
+        g.ke_row = GPK_TILE;
+        g.k_super = 1;            // the inverse factors are zero right of the diagonal for GPK_ZERO_BAND_TILES - 1 tiles (gpk_trtri)
+        g.heavy_first = 1;
+        GPK_TRY(gpk_gemm(h, GPK_F64, g));
+      }
+      const long long tot = 2 * (long long)nv;
+      hipLaunchKernelGGL(sparse_stack_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, (const double*)VA,
+                         (long long)mp, (long long)Mp, VB);
+      GPK_LAUNCH_CHECK(h);
+      GPK_TRY(gpk_cov_from_v(h, VA, VB, 2 * mp, dq, M, D, s->ls, s->sf2, s->noise, dcov, Mp));
+      GPK_CHECK_HIP(h, hipMemcpy2DAsync(sig.data(), (size_t)M * sizeof(double), dcov, (size_t)Mp * sizeof(double),
+                                        (size_t)M * sizeof(double), (size_t)M, hipMemcpyDeviceToHost, h->stream));
+      return GPK_OK;
+    }));
+  }
+  // output p: y_std[p]^2 Sigma, as in gpk_predict_model_cov
+  for (int p = 0; p < P; ++p) {
+    const double s2 = s->y_std[p] * s->y_std[p];
+    double* out = cov + (size_t)p * M * M;
+    for (size_t i = 0; i < (size_t)M * M; ++i) out[i] = sig[i] * s2;
+  }
+  return GPK_OK;
 }
 
 extern "C" int gpk_sparse_export(gpk_handle h, int64_t* m, int* D, int* P, int* n_ls, double* Z, double* G, double* g, double* yy,

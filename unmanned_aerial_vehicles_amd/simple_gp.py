@@ -148,7 +148,7 @@ class SimpleQuadrotorGP:
     def predict_residual_batch(self, X, return_var=True):
         """M rows [state(6), control(4)] in one kernel call -> (mean (M,P), variance (M,P))."""
         X = np.atleast_2d(np.asarray(X, dtype=float))
-        P = 6 if self.gp_model is None else self.gp_model._yn.shape[1]
+        P = 6 if self.gp_model is None else int(np.size(self.gp_model._y_train_std))      # (exact and sparse models both)
         if not self.is_trained:
             return np.zeros((len(X), P)), np.ones((len(X), P))
         try:

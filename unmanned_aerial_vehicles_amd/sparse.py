@@ -4,7 +4,8 @@ The Titsias / DTC predictor of GPflow's SGPR on this package's kernel `[C *] RBF
 The training rows enter through additive fp64 statistics of size m x m (`gpk_sparse_update`: N m^2 flops on the fp64
 matrix cores), so `partial_fit` appends rows at any time; the model is assembled from them lazily at the next `predict`
 (`gpk_sparse_finalize`: an m x m factorisation) and served at the cost of an exact model of m rows
-(`gpk_sparse_predict`: two launches for up to 32 rows).  `fit` / `partial_fit` do not optimise: the hyper-parameters are the
+(`gpk_sparse_predict`: two launches for up to 32 rows; `predict_jacobian`, `predict(return_cov=True)` and `sample_y`
+serve the controller's linearisation and joint draws the same way).  `fit` / `partial_fit` do not optimise: the hyper-parameters are the
 kernel's, e.g. those of an exact fit on a subset (`SparseGP.from_exact`).  `train` does: it keeps the rows on the device
 (`hold`, `gpk_sparse_hold`) and maximises the collapsed bound over the kernel's free parameters with L-BFGS-B, as GPflow's
 SGPR does; every evaluation (`log_bound`, `gpk_sparse_eval`) is the statistics pass, the m x m assembly and, for the
@@ -309,29 +310,102 @@ class SparseGP:
         return self
 
     # ------------------------------------------------------------------ predict
-    def predict(self, X, return_std=False):
-        """Posterior mean (and standard deviation, with the WhiteKernel level as scikit-learn's `predict` has it) at the rows
-        X.  Up to 32 rows: one call, two launches, one synchronisation."""
+    def _queries(self, X):
         X = np.array(X, dtype=np.float64, ndmin=2)
         if not np.isfinite(X).all():
             raise ValueError("Input X contains NaN or infinity.")
         if X.ndim != 2 or X.shape[1] != self.n_features_in_:
             raise ValueError(f"queries must be (M, {self.n_features_in_})")
+        return np.ascontiguousarray(X)
+
+    @property
+    def n_outputs_(self):
+        """Output columns of the model (1 until rows or a target normalisation say otherwise)."""
+        if self._P is not None:
+            return self._P
+        return 1 if self.y_mean is None else self.y_mean.size
+
+    @property
+    def _y_train_std(self):
+        """The target scale per output, under the exact model's name (what `SimpleQuadrotorGP` reads the output count from)."""
+        return np.ones(self.n_outputs_) if self.y_std is None else self.y_std
+
+    def predict(self, X, return_std=False, return_cov=False):
+        """Posterior mean (and standard deviation, with the WhiteKernel level as scikit-learn's `predict` has it) at the rows
+        X.  Up to 32 rows: one call, two launches, one synchronisation, whatever the number of outputs.
+
+        return_cov=True returns (y_mean, y_cov) as `GaussianProcessRegressor.predict` does: y_cov of shape (M, M) - (M, M, P)
+        for 2-D targets - scaled by the target std squared, the WhiteKernel level on its diagonal
+        (`gpk_sparse_predict_cov`; at most 16 384 rows)."""
+        if return_std and return_cov:
+            raise RuntimeError("At most one of return_std or return_cov can be requested.")
+        X = self._queries(X)
         self._ensure()
         M, P = X.shape[0], self._P
+        squeeze = P == 1 and self._y_1d
         mean = np.empty((M, P))
+        if return_cov:
+            cov = np.empty((P, M, M))
+            if M > 0:
+                be = self._backend()
+                with be.lock:
+                    be.bind_stream()
+                    be.check(be.lib.gpk_sparse_predict_cov(be.h, _ptr(X), M, _ptr(mean), _ptr(cov)))
+            return (mean[:, 0], cov[0]) if squeeze else (mean, np.ascontiguousarray(np.moveaxis(cov, 0, -1)))
         var = np.empty((M, P)) if return_std else None
         if M > 0:
-            X = np.ascontiguousarray(X)
             be = self._backend()
             with be.lock:
                 be.bind_stream()
                 be.check(be.lib.gpk_sparse_predict(be.h, _ptr(X), M, _ptr(mean), _ptr(var) if return_std else None, 1))
-        squeeze = P == 1 and self._y_1d
         if not return_std:
             return mean[:, 0] if squeeze else mean
         std = np.sqrt(var)
         return (mean[:, 0], std[:, 0]) if squeeze else (mean, std)
+
+    def predict_jacobian(self, X, return_var=False):
+        """Posterior mean and its Jacobian with respect to the inputs and, with return_var=True, the posterior variance and
+        its input gradient: the call of `GaussianProcessRegressor.predict_jacobian` on the sparse posterior
+        (`gpk_sparse_predict_grad`), with k = k_u(x), u_jd = (z_jd - x_d) / ls_d^2:
+
+            dmean[m, p, d] = y_std[p] sum_j k_mj u_jd alpha_u[j, p]
+            dvar[m, p, d]  = -2 y_std[p]^2 sum_j k_mj u_jd (Kuu^-1 k_m - Sigma~ k_m)_j
+
+        Returns (y_mean, dmean) or (y_mean, dmean, y_var, dvar).  Shapes follow `predict`'s squeezing: y_mean (M, P) / (M,),
+        dmean (M, P, D) / (M, D) for one target; y_var = predict(X, return_std=True)[1] ** 2 (clipped at 0 like it), shaped
+        as y_mean; dvar shaped as dmean - the gradient of the unclipped variance.  Same input validation as `predict`; a model
+        without rows returns the prior mean / variance and zero gradients through the same call.  Up to 32 rows: one launch,
+        three with the variance, one synchronisation, whatever the number of outputs."""
+        X = self._queries(X)
+        self._ensure()
+        M, D, P = X.shape[0], X.shape[1], self._P
+        mean, dmean = np.empty((M, P)), np.empty((M, P, D))
+        var = np.empty((M, P)) if return_var else None
+        dvar = np.empty((M, P, D)) if return_var else None
+        if M > 0:
+            be = self._backend()
+            with be.lock:
+                be.bind_stream()
+                be.check(be.lib.gpk_sparse_predict_grad(be.h, _ptr(X), M, _ptr(mean), _ptr(var) if return_var else None, _ptr(dmean),
+                                                        _ptr(dvar) if return_var else None, 1))
+        if P == 1 and self._y_1d:
+            mean, dmean = mean[:, 0], dmean[:, 0]
+            if return_var:
+                var, dvar = var[:, 0], dvar[:, 0]
+        return (mean, dmean, var, dvar) if return_var else (mean, dmean)
+
+    def sample_y(self, X, n_samples=1, random_state=0):
+        """Draws from the joint posterior (the prior, without rows) at X, as `GaussianProcessRegressor.sample_y`: the mean and
+        covariance from `predict(X, return_cov=True)` (GPU), the draw by NumPy's `multivariate_normal`, one target at a time.
+        Shape (M, n_samples), or (M, P, n_samples)."""
+        from .gpr import _rng_from
+        rng = _rng_from(random_state)
+        y_mean, y_cov = self.predict(X, return_cov=True)
+        if y_mean.ndim == 1:
+            return rng.multivariate_normal(y_mean, y_cov, n_samples).T
+        y_samples = [rng.multivariate_normal(y_mean[:, t], y_cov[..., t], n_samples).T[:, np.newaxis]
+                     for t in range(y_mean.shape[1])]
+        return np.hstack(y_samples)
 
     def bound(self):
         """The collapsed lower bound on the log-marginal likelihood of the rows seen so far, in normalised-target units (the
