@@ -727,7 +727,41 @@ GPK_API int gpk_lml_batched(gpk_handle h, const double* thetas, int n_theta, dou
  *   hyper-parameter gradient the matrix M is mirrored to a full matrix, one m x m kernel forms V (one inducing input per
  *   workgroup, j in index order, Kuu0 recomputed by exact differences) and the column pass U; still one synchronisation.
  *   After a successful call the object is the finalised model at these hyper-parameters and this Z, and gpk_sparse_export
- *   returns it.  With Z == NULL and gradZ == NULL the launches and the bits are gpk_sparse_eval's.                       */
+ *   returns it.  With Z == NULL and gradZ == NULL the launches and the bits are gpk_sparse_eval's.
+ *
+ * Choosing the inducing inputs: greedy conditional-variance selection (Burt, Rasmussen, van der Wilk, JMLR 2020), a pivoted
+ * partial Cholesky factorisation of Kff = K(X, X) that never forms Kff.
+ * Replaces: the random caps the reference puts on its rows - src/px4/gp_trainer.py:95-96 (np.random.choice of max_samples
+ *   rows) and the deque caps quoted above - as the way to pick which rows stand for the log.
+ * With d_i = sf2 for every row, step t = 0, 1, .. takes j = the LOWEST index among the rows with the largest d and stops, with
+ * *selected = t, if t == m_max, or d_j <= min_var sf2, or (t >= 1 and sum_i d_i <= tol n sf2); otherwise dmax[t] = d_j,
+ * idx[t] = j and
+ *       c_i  = sf2 exp(-1/2 sum_d ((x_id - x_jd) / ls_d)^2) - sum_{s < t} l_is l_js        (s ascending)
+ *       l_it = c_i / sqrt(d_j),   d_i = max(d_i - l_it^2, 0),   d_j = 0 exactly,
+ *       trace[t] = sum_i d_i      ( = tr(Kff - Kfu Kuu^-1 Kuf) with Z = X[idx[0 .. t]]: the trace term of the collapsed bound).
+ * The kernel value is formed as gpk_cross_gram_t forms it; every sum runs in an order fixed by (n, m_max); no floating-point
+ * atomics: the same call gives the same bits.  Entries of idx / trace / dmax from *selected on are not written.
+ * gpk_greedy_select_bytes: the size of gpk_greedy_select's work area in bytes - the transposed panel (m_max x ldn doubles, ldn
+ *   = n rounded up to 32), the scaled coordinates (16 x ldn), d (ldn) and the workgroups' partials; 0 for sizes that
+ *   gpk_greedy_select refuses.
+ * gpk_greedy_select: the device-pointer building block.  X dev (n x D); ls host, n_ls = 1 or D values; work dev, 16-byte
+ *   aligned, gpk_greedy_select_bytes(n, m_max) bytes, supplied by the caller (262 144 rows x 4096 columns are 8.6 GB: not a
+ *   temporary of the handle); idx dev int64[m_max], trace and dmax dev double[m_max], selected dev int64[1].  One launch
+ *   per pivot between an initialising and a closing launch, m_max + 2 in all, on the handle's stream: every workgroup of step t
+ *   reduces the per-workgroup (largest d, lowest index, sum of d) that step t - 1 left, in the same order, so that all reach
+ *   the same pivot and the same stop decision - after a stop the remaining launches return at once; no host round trip, no
+ *   ticket, flag or spin: the launch boundary is the only hand-off.  Asynchronous.  1 <= m_max <= min(n, 16384), D <= 16.
+ * gpk_sparse_select: the host entry, with the kernel hyper-parameters of the sparse object behind the handle.  X host (n x D,
+ *   checked to be finite), or NULL: the rows that gpk_sparse_hold keeps on the device (n must be their count; GPK_BAD_ARG
+ *   without held rows).  idx (int64), trace, dmax: host arrays of m_max entries, of which the first *selected are written.
+ *   Allocates and frees its own work area (GPK_HIP_ERROR if the device cannot hold it), synchronises once and leaves the
+ *   object's model, statistics and inducing inputs untouched.  Refuses batched mode.                                     */
+GPK_API size_t gpk_greedy_select_bytes(int64_t n, int64_t m_max);
+GPK_API int gpk_greedy_select(gpk_handle h, const double* X, int64_t n, int D, const double* ls, int n_ls, double sf2,
+                              int64_t m_max, double min_var, double tol, void* work, int64_t* idx, double* trace, double* dmax,
+                              int64_t* selected);
+GPK_API int gpk_sparse_select(gpk_handle h, const double* X, int64_t n, int64_t m_max, double min_var, double tol, int64_t* idx,
+                              double* trace, double* dmax, int64_t* selected);
 GPK_API int gpk_sparse_accumulate(gpk_handle h, const double* X, const double* Yn, int64_t n, const double* Z, int64_t m, int D,
                                   int P, const double* ls, double sf2, double* S, int64_t ld);
 GPK_API int gpk_sparse_grad_pass(gpk_handle h, const double* X, const double* Yn, int64_t n, const double* Z, int64_t m, int D,

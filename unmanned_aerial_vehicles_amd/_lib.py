@@ -118,6 +118,9 @@ SIGNATURES = {
     "gpk_sparse_hold": (_int, [_vp, _dp, _dp, _i64]),
     "gpk_sparse_eval": (_int, [_vp, _dp, _int, _dbl, _dbl, _dp, _dp, C.POINTER(_int)]),
     "gpk_sparse_eval_z": (_int, [_vp, _dp, _dp, _int, _dbl, _dbl, _dp, _dp, _dp, C.POINTER(_int)]),
+    "gpk_greedy_select_bytes": (C.c_size_t, [_i64, _i64]),
+    "gpk_greedy_select": (_int, [_vp, _vp, _i64, _int, _dp, _int, _dbl, _i64, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp]),
+    "gpk_sparse_select": (_int, [_vp, _dp, _i64, _i64, _dbl, _dbl, C.POINTER(_i64), _dp, _dp, C.POINTER(_i64)]),
     "gpk_sparse_begin": (_int, [_vp, _dp, _i64, _int, _int, _dp, _int, _dbl, _dbl, _dbl, _dbl, _dp, _dp]),
     "gpk_sparse_update": (_int, [_vp, _dp, _dp, _i64]),
     "gpk_sparse_finalize": (_int, [_vp, C.POINTER(_int)]),

@@ -942,6 +942,59 @@ extern "C" int gpk_sparse_eval_z(gpk_handle h, const double* Z, const double* ls
   return sparse_eval(h, Z, ls, n_ls, sf2, noise, bound, grad, gradZ, info);
 }
 
+// Greedy conditional-variance selection (gpk_select.hip) under the object's kernel: host rows, or the held ones.  Everything
+// the call allocates is a local gpk_dev: every return frees it, and the object is only read.
+extern "C" int gpk_sparse_select(gpk_handle h, const double* X, int64_t n, int64_t m_max, double min_var, double tol, int64_t* idx,
+                                 double* trace, double* dmax, int64_t* selected) {
+  if (!h) return GPK_BAD_ARG;
+  gpk_sparse* s = h->sparse;
+  GPK_REQUIRE(h, s, "sparse_select: no sparse model (call gpk_sparse_begin first)");
+  GPK_REQUIRE(h, idx && trace && dmax && selected, "sparse_select: null pointer");
+  GPK_REQUIRE(h, h->batch == 1, "composite calls are not available in batched mode");
+  if (!X) {
+    GPK_REQUIRE(h, s->held_n > 0, "sparse_select: no held rows (call gpk_sparse_hold; gpk_sparse_update releases them)");
+    GPK_REQUIRE(h, n == s->held_n, "sparse_select: n must be the number of held rows");
+  }
+  GPK_REQUIRE(h, n >= 1 && m_max >= 1 && m_max <= n && m_max <= SP_MAX_M, "sparse_select: need 1 <= m_max <= min(n, 16384)");
+  GPK_REQUIRE(h, min_var >= 0.0 && tol >= 0.0 && std::isfinite(min_var) && std::isfinite(tol),
+              "sparse_select: min_var and tol must be non-negative");
+  const int D = s->D;
+  if (X) GPK_TRY(gpk_require_finite(h, X, n * D, "sparse_select", "X"));
+  const size_t bytes = gpk_greedy_select_bytes(n, m_max);
+  GPK_REQUIRE(h, bytes > 0, "sparse_select: n too large");
+  GPK_CHECK_HIP(h, hipSetDevice(h->device));
+  gpk_dev<double> work, rows, out;
+  gpk_dev<int64_t> iout;
+  GPK_TRY(work.alloc(h, bytes / sizeof(double)));
+  GPK_TRY(out.alloc(h, (size_t)2 * m_max));
+  GPK_TRY(iout.alloc(h, (size_t)m_max + 1));
+  const double* dX = s->hX;
+  if (X) {
+    GPK_TRY(rows.alloc(h, (size_t)n * D));
+    GPK_CHECK_HIP(h, hipMemcpyAsync(rows, X, (size_t)n * D * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    dX = rows;
+  }
+  int rc = gpk_greedy_select(h, dX, n, D, s->ls, D, s->sf2, m_max, min_var, tol, work, iout, out, out + m_max, iout + m_max);
+  // (the launches read the local buffers: drain the stream on every path before they are freed)
+  std::vector<int64_t> hi((size_t)m_max + 1);
+  std::vector<double> ho((size_t)2 * m_max);
+  if (rc == GPK_OK && (hipMemcpyAsync(hi.data(), iout, hi.size() * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+                       hipMemcpyAsync(ho.data(), out, ho.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream) != hipSuccess)) {
+    h->err = "sparse_select: copying the result failed";
+    rc = GPK_HIP_ERROR;
+  }
+  if (hipStreamSynchronize(h->stream) != hipSuccess && rc == GPK_OK) {
+    h->err = "sparse_select: the selection failed";
+    rc = GPK_HIP_ERROR;
+  }
+  GPK_TRY(rc);
+  const int64_t sel = hi[(size_t)m_max];
+  GPK_REQUIRE(h, sel >= 0 && sel <= m_max, "sparse_select: the selection returned an impossible count");
+  for (int64_t t = 0; t < sel; ++t) { idx[t] = hi[(size_t)t]; trace[t] = ho[(size_t)t]; dmax[t] = ho[(size_t)(m_max + t)]; }
+  *selected = sel;
+  return GPK_OK;
+}
+
 extern "C" int gpk_sparse_bound(gpk_handle h, double* bound, int64_t* n_rows) {
   if (!h) return GPK_BAD_ARG;
   gpk_sparse* s = h->sparse;

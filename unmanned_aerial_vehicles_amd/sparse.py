@@ -11,7 +11,9 @@ kernel's, e.g. those of an exact fit on a subset (`SparseGP.from_exact`).  `trai
 SGPR does; every evaluation (`log_bound`, `gpk_sparse_eval`) is the statistics pass, the m x m assembly and, for the
 gradient, one more pass over the rows.  `train(train_inducing=True)` optimises the inducing inputs together with the kernel,
 as SGPR does: `gpk_sparse_eval_z` moves Z and adds the bound's gradient with respect to it (a second pass over the rows and
-an m x m kernel); by default the inducing inputs stay where they are.
+an m x m kernel); by default the inducing inputs stay where they are.  Where they start is the caller's array, a seeded
+random subset of the rows, or the rows picked by greedy conditional variance (`select_inducing`, `gpk_sparse_select`:
+`from_exact(selection="greedy")`, `train(select_inducing="greedy")`).
 
 The class keeps one libgpk handle of its own: the sparse model is the object behind that handle (include/gpk.h), the
 arrays that cross the boundary are host NumPy arrays.
@@ -91,10 +93,14 @@ class SparseGP:
 
     # ------------------------------------------------------------------ construction from an exact model
     @classmethod
-    def from_exact(cls, gpr, inducing=None, random_state=0, jitter_uu=None):
+    def from_exact(cls, gpr, inducing=None, random_state=0, jitter_uu=None, selection="random"):
         """Kernel, `alpha` and target normalisation of a fitted `GaussianProcessRegressor`; inducing inputs: an array, an
         integer (that many of its training rows, picked by a seeded permutation) or None (all of them).  The sparse model
-        starts with no rows: `partial_fit` the flight log (the exact model's own rows included, if they are to count)."""
+        starts with no rows: `partial_fit` the flight log (the exact model's own rows included, if they are to count).
+        `selection="greedy"` picks the integer's rows by greedy conditional variance under the regressor's kernel instead
+        (`select_inducing`); ValueError if fewer than that many rows are usable (duplicates, say)."""
+        if selection not in ("random", "greedy"):
+            raise ValueError(f"selection must be 'random' or 'greedy', got {selection!r}")
         if not hasattr(gpr, "X_train_"):
             raise RuntimeError("This GaussianProcessRegressor instance is not fitted yet.")
         X = gpr.X_train_
@@ -103,9 +109,17 @@ class SparseGP:
         elif isinstance(inducing, (int, np.integer)):
             if not 1 <= int(inducing) <= len(X):
                 raise ValueError(f"inducing must be in [1, {len(X)}]")
+            if selection == "greedy":
+                probe = cls(gpr.kernel_, X[:1], alpha=gpr.alpha, jitter_uu=jitter_uu, device=gpr.device)
+                Z = X[probe._select_exactly(X, int(inducing))]
+                return cls._like(gpr, Z, jitter_uu)
             Z = X[np.sort(np.random.default_rng(random_state).permutation(len(X))[:int(inducing)])]
         else:
             Z = inducing
+        return cls._like(gpr, Z, jitter_uu)
+
+    @classmethod
+    def _like(cls, gpr, Z, jitter_uu):
         out = cls(gpr.kernel_, Z, alpha=gpr.alpha, jitter_uu=jitter_uu, y_mean=gpr._y_train_mean, y_std=gpr._y_train_std, device=gpr.device)
         out._y_1d = bool(getattr(gpr, "_y_1d", True))
         return out
@@ -262,17 +276,95 @@ class SparseGP:
             return value, gradient_to_theta(comp, g), gZ
         return (value, gradient_to_theta(comp, g)) if eval_gradient else value
 
-    def train(self, X, y, n_restarts_optimizer=0, optimizer="fmin_l_bfgs_b", random_state=None, train_inducing=False):
+    # ------------------------------------------------------------------ choosing the inducing inputs
+    def select_inducing(self, X=None, m=None, tol=0.0, min_var=1e-10):
+        """Greedy conditional-variance selection (`gpk_sparse_select`; Burt, Rasmussen, van der Wilk 2020) among the rows X
+        (n, D) - None: the held rows - under the current kernel: each step takes the row whose prior variance, conditioned
+        on the rows taken so far, is largest (the lowest index among equals).  At most m rows (None: as many as the object
+        has inducing inputs); stops early once the largest conditional variance is at most min_var sf2, or the trace
+        tr(Kff - Qff) at most tol n sf2.  Returns (indices, trace): trace[t] = tr(Kff - Qff) with Z = X[indices[:t + 1]].
+        The model, its statistics and `inducing_` stay as they are."""
+        if X is None:
+            if not (self._live and getattr(self, "_held", False)):
+                raise RuntimeError("select_inducing() needs held rows: call hold(X, y) first, or pass X")
+            n = self.n_rows_
+        else:
+            X = np.array(X, dtype=np.float64, ndmin=2)
+            if X.ndim != 2 or X.shape[1] != self.n_features_in_:
+                raise ValueError(f"X must be (n, {self.n_features_in_})")
+            if not np.isfinite(X).all():
+                raise ValueError("Input contains NaN or infinity")
+            X = np.ascontiguousarray(X)
+            n = X.shape[0]
+            if not self._live:
+                self._begin(self.n_outputs_)
+        m = self.inducing_.shape[0] if m is None else int(m)
+        if not 1 <= m <= n:
+            raise ValueError(f"m must be in [1, {n}]")
+        if not (tol >= 0.0 and min_var >= 0.0):
+            raise ValueError("tol and min_var must be non-negative")
+        idx = np.full(m, -1, dtype=np.int64)
+        trace, dmax = np.full(m, np.nan), np.full(m, np.nan)
+        sel = C.c_int64(0)
+        be = self._backend()
+        with be.lock:
+            be.bind_stream()
+            be.check(be.lib.gpk_sparse_select(be.h, None if X is None else _ptr(X), n, m, float(min_var), float(tol),
+                                              idx.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(trace), _ptr(dmax), C.byref(sel)))
+        return idx[:sel.value].copy(), trace[:sel.value].copy()
+
+    def _select_exactly(self, X, m, min_var=1e-10):
+        idx, _ = self.select_inducing(X, m, min_var=min_var)
+        if len(idx) < m:
+            raise ValueError(f"greedy selection found {len(idx)} usable rows, fewer than the {m} asked for "
+                             "(duplicate rows, or a kernel under which fewer rows explain all the variance)")
+        return idx
+
+    def train(self, X, y, n_restarts_optimizer=0, optimizer="fmin_l_bfgs_b", random_state=None, train_inducing=False,
+              select_inducing=None, selection_rounds=1):
         """Holds the rows and maximises the bound over the kernel's free parameters within its bounds (L-BFGS-B, as
         `GaussianProcessRegressor.fit`; restarts start from draws within finite bounds and run one after the other).  Sets
         `kernel_` and `bound_value_` and leaves the finalised model at the optimum.  `train_inducing=True`: the optimisation
         vector is [theta, Z.ravel()] with Z unbounded, as GPflow's SGPR trains its inducing variable; every start begins
-        at the constructor's inducing inputs (restarts redraw theta only), and `inducing_` is the trained Z afterwards."""
-        from .gpr import _rng_from, constrained_optimization
+        at the constructor's inducing inputs (restarts redraw theta only), and `inducing_` is the trained Z afterwards.
+        `select_inducing="greedy"`: each of the `selection_rounds` rounds first re-selects the inducing inputs among the held
+        rows under the current kernel (`select_inducing`), then trains the kernel with them fixed - the reselect-then-train
+        alternation of the literature; with `train_inducing=True` the last round trains Z as well, from the greedy Z.  The
+        object keeps its number of inducing inputs: a round takes rows below the variance floor too, and raises ValueError
+        only if fewer than that many rows have any conditional variance left (exact duplicates)."""
+        from .gpr import _rng_from
+        if select_inducing not in (None, "greedy"):
+            raise ValueError(f"select_inducing must be None or 'greedy', got {select_inducing!r}")
+        if select_inducing is not None and int(selection_rounds) < 1:
+            raise ValueError("selection_rounds must be at least 1")
         if self.kernel_.n_dims == 0:
             raise ValueError("train: the kernel has no free parameter")
         Z0 = self.__dict__.get("_inducing0", self.inducing_).copy() if train_inducing else self.inducing_
         self.hold(X, y)
+        rng = [None]
+
+        def draw():      # one generator for all rounds, made at the first restart as before
+            if rng[0] is None:
+                rng[0] = _rng_from(random_state)
+            return rng[0]
+
+        if select_inducing is None:
+            return self._maximise(optimizer, n_restarts_optimizer, draw, train_inducing, Z0)
+        rows = np.array(X, dtype=np.float64, ndmin=2)
+        m, rounds = self.inducing_.shape[0], int(selection_rounds)
+        for r in range(rounds):
+            # (min_var = 0: the object keeps its m inducing inputs, so rows under the variance floor are taken too, largest
+            # remainder first - a trained kernel with long length-scales leaves fewer than m above it; jitter_uu carries them)
+            Z = np.ascontiguousarray(rows[self._select_exactly(None, m, min_var=0.0)])
+            if not np.isfinite(self.log_bound(self.kernel_.theta, inducing=Z)):
+                raise np.linalg.LinAlgError("train: the model at the selected inducing inputs is not positive definite")
+            self._maximise(optimizer, n_restarts_optimizer, draw, train_inducing and r == rounds - 1, Z)
+        return self
+
+    def _maximise(self, optimizer, n_restarts_optimizer, draw, train_inducing, Z0):
+        """L-BFGS-B on the bound of the held rows from the current kernel (and Z0, with train_inducing); leaves the model at
+        the optimum."""
+        from .gpr import constrained_optimization
         nt = self.kernel_.n_dims
 
         if train_inducing:
@@ -290,7 +382,7 @@ class SparseGP:
         if n_restarts_optimizer > 0:
             if not np.isfinite(bounds).all():
                 raise ValueError("Multiple optimizer restarts (n_restarts_optimizer>0) requires that all bounds are finite.")
-            rng = _rng_from(random_state)
+            rng = draw()
             starts += [rng.uniform(bounds[:, 0], bounds[:, 1]) for _ in range(n_restarts_optimizer)]
         if train_inducing:
             starts = [pack_inducing(t0, Z0) for t0 in starts]
