@@ -781,6 +781,47 @@ GPK_API int gpk_sparse_predict(gpk_handle h, const double* Xq, int64_t M, double
 GPK_API int gpk_sparse_predict_grad(gpk_handle h, const double* Xq, int64_t M, double* mean, double* var, double* dmean,
                                     double* dvar, int var_includes_noise);
 GPK_API int gpk_sparse_predict_cov(gpk_handle h, const double* Xq, int64_t M, double* mean, double* cov);
+
+/* ---- K9, the per-axis batch: B single-output sparse models served on one query batch ----------------------------------------
+ * The model file a controller loads holds six scalar GPs, each with its own ARD length-scales and noise level; the exact models
+ * have gpk_predict_host_multi[_grad|_cov] for that shape.  These are the same for sparse objects: 1 <= B <= 8 handles, behind
+ * each a FINALISED sparse object with P = 1, all with the same m and D and on the same device - each with its own inducing
+ * inputs, alpha_u, length-scales, sf2, noise, target normalisation and factor pair (Wuu, WSigma).  h is the serving handle
+ * (it may be one of `models`): it supplies the stream, the pinned staging block, the work area and the ticket counters.
+ * Host fp64 buffers in the per-axis layout: Xq (M x D), mean and var (M x B), dmean and dvar (M x B x D), cov (B x M x M).
+ * Units, clipping and flooring PER MODEL exactly as gpk_sparse_predict / _grad / _cov: mean un-normalised; var, dvar and cov
+ * block b already times y_std_b^2; var_includes_noise != 0 adds model b's WhiteKernel level and clips at 0, == 0 floors at
+ * 1e-10; dvar is the gradient of the unclipped variance; cov block b has noise_b on its diagonal and is symmetric bit for bit.
+ * var == NULL: means only (multi_grad: var and dvar come together or not at all).
+ *
+ * Up to 32 queries (option small_path on): the two-factor small-batch kernels with a model dimension - the first launch
+ * (small_cross_mean[_jac]_kernel) takes the model as blockIdx.y: one K* and one set of mean / Jacobian shares per model; the
+ * variance, covariance and W^T V launches take 2 * model + factor as the grid dimension that is the factor in the single
+ * entries: per (model, factor) its own rows of V, shares, group sums and group counters, per model ONE ticket count over the
+ * workgroups of both of its factors, and that model's last workgroup writes max((kss - t0) - (0 - t1), floor) y_std^2,
+ * (k(a, b) - s0) + s1 mirrored, dvar = -2 / ls_d (s0 - s1).  For every B: means one launch, mean + variance two, mean +
+ * Jacobian one, all four gradient results three, mean + covariance two; one synchronisation per call.  No flags, spins or
+ * floating-point atomics; every sum runs in an order fixed by (mp, M) alone, so model b's block of every result has the bits
+ * of gpk_sparse_predict[_grad|_cov] on that model alone (B = 1 IS that route).  All ticket counters are left at zero.
+ * More queries, or option small_path = 0: model by model through the panel routes of the single entries on h's stream (one
+ * synchronisation per panel and model) - the cross-check of the kernels above.
+ *
+ * The entries read the models' device buffers across handles.  Those are stable once gpk_sparse_finalize, gpk_sparse_eval[_z]
+ * or gpk_sparse_import + gpk_sparse_finalize on that object have returned (they synchronise, through gpk_lml_terms), and stay
+ * so until the next call that changes that object; the entry synchronises nothing on the models' own streams, and no such
+ * call may run on a model while the entry does.
+ * GPK_BAD_ARG with a message, before anything is launched or read: B outside [1, 8], a NULL handle, an object that is missing,
+ * not finalised, on another device, with P != 1 or with another m or D, M < 1 (cov: M > 16384), non-finite queries, var
+ * without dvar, batched mode.
+ * Replaces: six gpk_sparse_predict* calls - six synchronisations - per control step for the six residual models of
+ *   src/px4/pretrained_gp.py:52-98 (predict_residual) once they are sparse; nothing in the reference serves a
+ *   sparse model.                                                                                                          */
+GPK_API int gpk_sparse_predict_multi(gpk_handle h, int B, const gpk_handle* models, const double* Xq, int64_t M, double* mean,
+                                     double* var, int var_includes_noise);
+GPK_API int gpk_sparse_predict_multi_grad(gpk_handle h, int B, const gpk_handle* models, const double* Xq, int64_t M, double* mean,
+                                          double* var, double* dmean, double* dvar, int var_includes_noise);
+GPK_API int gpk_sparse_predict_multi_cov(gpk_handle h, int B, const gpk_handle* models, const double* Xq, int64_t M, double* mean,
+                                         double* cov);
 GPK_API int gpk_sparse_bound(gpk_handle h, double* bound, int64_t* n_rows);
 GPK_API int gpk_sparse_export(gpk_handle h, int64_t* m, int* D, int* P, int* n_ls, double* Z, double* G, double* g, double* yy,
                               int64_t* n_rows, double* ls, double* hyper, double* y_mean, double* y_std);

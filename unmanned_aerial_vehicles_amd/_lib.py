@@ -127,6 +127,9 @@ SIGNATURES = {
     "gpk_sparse_predict": (_int, [_vp, _dp, _i64, _dp, _dp, _int]),
     "gpk_sparse_predict_grad": (_int, [_vp, _dp, _i64, _dp, _dp, _dp, _dp, _int]),
     "gpk_sparse_predict_cov": (_int, [_vp, _dp, _i64, _dp, _dp]),
+    "gpk_sparse_predict_multi": (_int, [_vp, _int, C.POINTER(_vp), _dp, _i64, _dp, _dp, _int]),
+    "gpk_sparse_predict_multi_grad": (_int, [_vp, _int, C.POINTER(_vp), _dp, _i64, _dp, _dp, _dp, _dp, _int]),
+    "gpk_sparse_predict_multi_cov": (_int, [_vp, _int, C.POINTER(_vp), _dp, _i64, _dp, _dp]),
     "gpk_sparse_bound": (_int, [_vp, _dp, C.POINTER(_i64)]),
     "gpk_sparse_export": (_int, [_vp, C.POINTER(_i64), C.POINTER(_int), C.POINTER(_int), C.POINTER(_int), _dp, _dp, _dp, _dp,
                                  C.POINTER(_i64), _dp, _dp, _dp, _dp]),

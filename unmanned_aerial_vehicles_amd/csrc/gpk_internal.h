@@ -246,14 +246,16 @@ int gpk_gemm_tile(gpk_handle h, const GemmArgs& g);   // 128 or 64: the tile edg
 constexpr int GPK_SMALL_MAX_M = 32;          // queries per call
 constexpr int64_t GPK_SMALL_MAX_NP = 16384;  // padded training rows
 constexpr int GPK_SMALL_MAX_MODELS = 8;      // single-output models served by one call
-constexpr int GPK_SMALL_COV_COUNTERS = GPK_SMALL_MAX_MODELS * 65 + GPK_SMALL_MAX_MODELS;
+constexpr int GPK_SMALL_COV_COUNTERS = GPK_SMALL_MAX_MODELS * 129 + GPK_SMALL_MAX_MODELS;
                                              // h->d_cov_count: ticket counters of the covariance's two-level reduction, per model
-                                             // 1 + GPK_SMALL_MAX_NP / 16 / 16 = 65; the last GPK_SMALL_MAX_MODELS are
+                                             // 1 + GPK_SMALL_MAX_NP / 16 / 16 = 65, in the two-factor form 1 + 2 * 64 = 129 (one
+                                             // top-level count and the groups of both factors); the last GPK_SMALL_MAX_MODELS are
                                              // small_wtv_grad_kernel's, one per model
 bool gpk_small_ok(int64_t Np, int D, int P, int64_t M);
 // doubles of device work area (`work`) that a call of the given kind needs: per model K* (32 x Np) + the workgroups' shares
 enum { GPK_SMALL_PREDICT, GPK_SMALL_COV, GPK_SMALL_GRAD };
-size_t gpk_small_work_doubles(int call, int64_t Np, int B, int64_t M, int D, int P);
+// (F: inverse factors per model - 2 for the two-factor form, whose K*, mean and Jacobian shares stay one set per model)
+size_t gpk_small_work_doubles(int call, int64_t Np, int B, int64_t M, int D, int P, int F = 1);
 // mean (B, M, P) and, if var_out, variance (B, M): one launch, or two (small_cross_mean_kernel + small_var_kernel)
 int gpk_small_predict(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D, int P,
                       const double* ls, const double* sf2, const double* y_mean, const double* y_std,
@@ -278,17 +280,32 @@ int gpk_small_grad_multi(gpk_handle h, int B, const double* const* X, const doub
 //   GPK_SMALL_PREDICT  mean (M x P); with var_out the variance (M x P, clipped at floor_, times y_std[p]^2): 1 or 2 launches
 //   GPK_SMALL_GRAD     + dmean (M x P x D); with var_out / dvar_out also dvar (M x D, normalised-target units): 1 or 3 launches
 //   GPK_SMALL_COV      mean and cov (M x M, normalised-target units, noise on the diagonal, not clipped): 2 launches
-// work: gpk_small_work_doubles(call, Np, 2, M, D, P) doubles.
+// work: gpk_small_work_doubles(call, Np, 1, M, D, P, 2) doubles.
 int gpk_small_two(gpk_handle h, int call, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
                   double sf2, const double* y_mean, const double* y_std, const double* W0, const double* W1, int64_t Np,
                   int64_t ldw, double kss, double floor_, double noise, const double* Xq, int64_t M, double* work,
                   double* mean_out, double* var_out, double* dmean_out, double* dvar_out, double* cov_out);
+// ... with a model dimension: B <= GPK_SMALL_MAX_MODELS such models (B > 1: P == 1) of equal N and D on one query batch, each with
+// its own inputs, alpha, kernel (ls: B x D; sf2, kss, noise: B), normalisation (y_mean, y_std: B * P) and factor pair (W0[b],
+// W1[b]).  The grid dimension that is the factor above is 2 * model + factor; one ticket count per model; the launch counts of
+// one model for every B.  Outputs (B, M, P), (B, M, P), (B, M, P, D), (B, M, D), (B, M, M); block b has the bits of model b
+// served alone.  work: gpk_small_work_doubles(call, Np, B, M, D, P, 2) doubles.  gpk_small_two is B = 1.
+int gpk_small_two_multi(gpk_handle h, int call, int B, const double* const* X, const double* const* alpha, int64_t N, int D, int P,
+                        const double* ls, const double* sf2, const double* y_mean, const double* y_std, const double* const* W0,
+                        const double* const* W1, int64_t Np, int64_t ldw, const double* kss, double floor_, const double* noise,
+                        const double* Xq, int64_t M, double* work, double* mean_out, double* var_out, double* dmean_out,
+                        double* dvar_out, double* cov_out);
 // ... as a one-call serving entry (gpk_serve.hip): host queries in, host results out through the pinned, mapped block, one
 // synchronisation.  Outputs that the call does not produce are NULL.
 int gpk_serve_two(gpk_handle h, int call, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
                   double sf2, const double* y_mean, const double* y_std, const double* W0, const double* W1, int64_t Np,
                   int64_t ldw, double kss, double floor_, double noise, const double* Xq_host, int64_t M, double* mean_host,
                   double* var_host, double* dmean_host, double* dvar_host, double* cov_host);
+int gpk_serve_two_multi(gpk_handle h, int call, int B, const double* const* X, const double* const* alpha, int64_t N, int D, int P,
+                        const double* ls, const double* sf2, const double* y_mean, const double* y_std, const double* const* W0,
+                        const double* const* W1, int64_t Np, int64_t ldw, const double* kss, double floor_, const double* noise,
+                        const double* Xq_host, int64_t M, double* mean_host, double* var_host, double* dmean_host, double* dvar_host,
+                        double* cov_host);
 // Sigma (Mp x ldc, symmetric bit for bit) = K(Xq, Xq) + noise I - VA^T VB from two operands (rows x Mp each, ld Mp) whose
 // product is symmetric (gpk_cov.hip: the covariance epilogue of the tile GEMM; VA == VB: the exact model's covariance)
 int gpk_cov_from_v(gpk_handle h, const double* VA, const double* VB, int64_t rows, const double* Xq, int64_t M, int D,

@@ -3,7 +3,7 @@
 //   gpk_predict_host, gpk_predict_host_multi             mean (+ variance)             of one model / of B per-axis models
 //   gpk_predict_host_cov, gpk_predict_host_multi_cov     mean + covariance             of one model / of B per-axis models
 //   gpk_predict_host_grad, gpk_predict_host_multi_grad   mean + Jacobian (+ variance + its gradient)
-//   gpk_serve_two (internal: the sparse model's entries)  any of the three on one model with two inverse factors
+//   gpk_serve_two[_multi] (internal: the sparse model's entries)  any of the three on one model / on B models with two inverse factors each
 //
 // The staging block is pinned, coherent host memory mapped into the device's address space: the kernels write their
 // results straight into it (a few hundred bytes over PCIe) - no download command.  Small batches (<= 32 queries): the
@@ -211,27 +211,36 @@ int serve_grad(gpk_handle h, const ServeModels& m, bool small, const double* Xq_
 
 }  // namespace
 
-int gpk_serve_two(gpk_handle h, int call, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
-                  double sf2, const double* y_mean, const double* y_std, const double* W0, const double* W1, int64_t Np,
-                  int64_t ldw, double kss, double floor_, double noise, const double* Xq_host, int64_t M, double* mean_host,
-                  double* var_host, double* dmean_host, double* dvar_host, double* cov_host) {
-  const size_t nm = (size_t)M * P;
+int gpk_serve_two_multi(gpk_handle h, int call, int B, const double* const* X, const double* const* alpha, int64_t N, int D, int P,
+                        const double* ls, const double* sf2, const double* y_mean, const double* y_std, const double* const* W0,
+                        const double* const* W1, int64_t Np, int64_t ldw, const double* kss, double floor_, const double* noise,
+                        const double* Xq_host, int64_t M, double* mean_host, double* var_host, double* dmean_host, double* dvar_host,
+                        double* cov_host) {
+  const size_t nm = (size_t)B * M * P;
   double *hmean, *hvar = nullptr, *hdm = nullptr, *hdv = nullptr, *hcov = nullptr;
   Serve s(h, Xq_host, M, D);
   s.out(mean_host, nm, &hmean);
   if (call == GPK_SMALL_COV) {
-    s.out(cov_host, (size_t)M * M, &hcov);
+    s.out(cov_host, (size_t)B * M * M, &hcov);
   } else {
     s.out(var_host, nm, &hvar);
     if (call == GPK_SMALL_GRAD) {
       s.out(dmean_host, nm * D, &hdm);
-      s.out(dvar_host, (size_t)M * D, &hdv);
+      s.out(dvar_host, (size_t)B * M * D, &hdv);
     }
   }
-  GPK_TRY(s.begin(gpk_small_work_doubles(call, Np, 2, M, D, P)));
-  GPK_TRY(gpk_small_two(h, call, X, alpha, N, D, P, ls, sf2, y_mean, y_std, W0, W1, Np, ldw, kss, floor_, noise, s.hq, M, s.dwork,
-                        hmean, var_host ? hvar : nullptr, hdm, dvar_host ? hdv : nullptr, hcov));
+  GPK_TRY(s.begin(gpk_small_work_doubles(call, Np, B, M, D, P, 2)));
+  GPK_TRY(gpk_small_two_multi(h, call, B, X, alpha, N, D, P, ls, sf2, y_mean, y_std, W0, W1, Np, ldw, kss, floor_, noise, s.hq, M,
+                              s.dwork, hmean, var_host ? hvar : nullptr, hdm, dvar_host ? hdv : nullptr, hcov));
   return s.finish();
+}
+
+int gpk_serve_two(gpk_handle h, int call, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
+                  double sf2, const double* y_mean, const double* y_std, const double* W0, const double* W1, int64_t Np,
+                  int64_t ldw, double kss, double floor_, double noise, const double* Xq_host, int64_t M, double* mean_host,
+                  double* var_host, double* dmean_host, double* dvar_host, double* cov_host) {
+  return gpk_serve_two_multi(h, call, 1, &X, &alpha, N, D, P, ls, &sf2, y_mean, y_std, W0 ? &W0 : nullptr, W1 ? &W1 : nullptr, Np, ldw,
+                             &kss, floor_, &noise, Xq_host, M, mean_host, var_host, dmean_host, dvar_host, cov_host);
 }
 
 extern "C" int gpk_predict_host(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P,

@@ -36,6 +36,12 @@
 //                            dimension that is the model elsewhere: shared K*, mean and Jacobian shares, per-factor V and shares, one
 //                            ticket count over the workgroups of both, and the last workgroup overall writes the combination
 //                            (gpk_small_two): any P at the launch counts of one model.
+//   ... with a model dimension  the same kernels serve B <= 8 sparse models (P = 1 each, equal m and D, each with its own Z, alpha_u,
+//                            kernel, noise, normalisation and factor pair) on one query batch: that grid dimension is 2 * model +
+//                            factor.  Per model one K* and one set of mean / Jacobian shares (the cross kernels' blockIdx.y), per
+//                            (model, factor) its own V and shares, per model ONE ticket count over the workgroups of both of its
+//                            factors, and that model's last workgroup writes its combination (gpk_small_two_multi; gpk_small_two
+//                            is B = 1).  A model's sums are grouped by (Np, M) alone: its block has the bits of that model served alone.
 //
 // Both results land in the caller's (pinned, mapped) output block; the queries are read from it as well.
 #include "gpk_internal.h"
@@ -45,17 +51,20 @@ namespace {
 
 constexpr int SQ = GPK_SMALL_MAX_M, SJ = 32, SD = 16, SP = 16, SR = 16;
 struct Arr16 { double v[16]; };
+constexpr size_t SMALLK_ARG_LIMIT = 2048;    // (kernel arguments: 4 KiB in all; the parameter block goes by value)
 // Per-model parameters (model = blockIdx.y).  One model with P <= 16 outputs, or B <= 8 single-output models that
 // share the query batch (the per-axis GPs of gp_trainer.py): output o = model * P + p indexes ymean / ystd.
 struct SmallK {
   const double* X[GPK_SMALL_MAX_MODELS];
   const double* alpha[GPK_SMALL_MAX_MODELS];
   const double* W[GPK_SMALL_MAX_MODELS];
+  const double* W2[GPK_SMALL_MAX_MODELS];   // the second inverse factor of a model (the two-factor kernels only)
   double ls[GPK_SMALL_MAX_MODELS][16];
   double sf2[GPK_SMALL_MAX_MODELS], kss[GPK_SMALL_MAX_MODELS];
   double ymean[16], ystd[16];
   double noise[GPK_SMALL_MAX_MODELS];   // the WhiteKernel level (covariance only)
 };
+static_assert(sizeof(SmallK) <= SMALLK_ARG_LIMIT, "the parameter block is a kernel argument");
 typedef double d4 __attribute__((ext_vector_type(4)));
 typedef double d2v __attribute__((ext_vector_type(2)));
 
@@ -370,10 +379,11 @@ __device__ __forceinline__ double small_v_sum(const double (&red)[VW][NMB][16][1
 // GRAD (small_var_grad_kernel): the launch also stores its rows of V (Vs: per model Np x SQ, columns < 16 NMB written) for
 // small_wtv_grad_kernel, and workgroup 1 adds the mean Jacobian's shares of the previous launch.  The body is shared;
 // small_var_kernel keeps its signature and its launches.
-// TWO (small_var2_kernel, small_var2_grad_kernel; the sparse model): blockIdx.y is the inverse FACTOR (0: Wuu, 1: WSigma) of ONE
-// model with P outputs.  Both factors read the same K* and the same mean / Jacobian shares (model slot 0); each has its own
-// shares (and rows of V); ONE ticket count runs over the workgroups of both, and the last one overall adds each factor's
-// shares in the order above and writes var[m][p] = max((kss - t0) - (0 - t1), floor) y_std[p]^2.
+// TWO (small_var2_kernel, small_var2_grad_kernel; the sparse model): blockIdx.y is 2 * model + the inverse FACTOR (0: Wuu,
+// 1: WSigma); one model with P outputs, or B models with one each.  Both factors of a model read its K* and its mean / Jacobian
+// shares (model slot o); each has its own shares (and rows of V, slot 2 o + f); ONE ticket count per model runs over the
+// workgroups of both, and the model's last one adds each factor's shares in the order above and writes
+// var[m][p] = max((kss - t0) - (0 - t1), floor) y_std[p]^2.
 template <int NMB, bool GRAD, bool TWO>
 __device__ __forceinline__ void small_var_body(SmallK k, long long ldw, long long Np, const double* Ks,
                                                             int M, int P, double floor_, const double* pmean,
@@ -382,17 +392,17 @@ __device__ __forceinline__ void small_var_body(SmallK k, long long ldw, long lon
                                                             const double* pjac, int D, double* dmean_out) {
   __shared__ double red[VW][NMB][16][17];
   __shared__ double sq[NMB][16][17];
-  const int b = blockIdx.y;                    // the model, or the factor
-  const int o = TWO ? 0 : b;                   // the model slot of everything but W and the factor's own shares
-  const bool lead = TWO ? b == 0 : true;       // the factor whose workgroups 0 and 1 finish the means and the Jacobian
-  const double* __restrict__ W = k.W[b];
+  const int b = blockIdx.y;                    // the model, or 2 * model + factor
+  const int o = TWO ? b >> 1 : b;              // the model slot of everything but W and the factor's own shares
+  const bool lead = TWO ? (b & 1) == 0 : true; // the factor whose workgroups 0 and 1 finish the means and the Jacobian
+  const double* __restrict__ W = (TWO && (b & 1)) ? k.W2[o] : k.W[o];
   const double kss = k.kss[o];
   Ks += (long long)o * SQ * Np;
   pmean += (long long)o * mean_shares * (SQ * SP);
-  double* const pvar0 = pvar;
+  double* const pvar0 = pvar + (long long)(2 * o) * gridDim.x * SQ;     // (TWO) the shares of this model's factor 0, then 1
   pvar += (long long)b * gridDim.x * SQ;
   mean_out += (long long)o * M * P;
-  var_out += (long long)o * M;
+  var_out += (long long)o * M * (TWO ? P : 1);
   counter += o;
   if constexpr (GRAD) {
     Vs += (long long)b * Np * SQ;
@@ -451,7 +461,8 @@ __device__ __forceinline__ void small_var_body(SmallK k, long long ldw, long lon
         for (int k = 0; k < 2 * VW; ++k) t0 += part[0][k][mq];
 #pragma unroll
         for (int k = 0; k < 2 * VW; ++k) t1 += part[1][k][mq];
-        var_out[e] = fmax((kss - t0) - (0.0 - t1), floor_) * k.ystd[p] * k.ystd[p];
+        const double ys = k.ystd[o * P + p];
+        var_out[e] = fmax((kss - t0) - (0.0 - t1), floor_) * ys * ys;
       }
     }
   }
@@ -509,11 +520,13 @@ __device__ __forceinline__ void tri_index(int t, int& i, int& j) {
 // share of V^T V.  Per model: COV_COUNTERS ticket counters ([0] the top level, [1 + g] group g; all left at zero), pcov
 // (gridDim.x x CE), gcov (groups x CE), cov_out (M x M).  A model's sums are grouped by Np and M alone: its block has the
 // bits of that model served on its own.
-constexpr int COV_COUNTERS = 1 + (int)(GPK_SMALL_MAX_NP / SR / CG);
-// TWO (small_cov2_kernel; the sparse model): blockIdx.y is the inverse factor of ONE model.  Both factors read the same K* and
-// mean shares; each has its own shares, group sums and group counters (factor f: counters[f * COV_COUNTERS + 1 + g]); the top
-// level is ONE count (counters[0]) over the groups of both factors, and the last group overall writes
-// (k(a, b) - s0) + s1, mirrored.  Two ticket levels, each with its own last_of: a group's last workgroup reads its group's
+constexpr int COV_GROUPS = (int)(GPK_SMALL_MAX_NP / SR / CG);
+constexpr int COV_COUNTERS = 1 + COV_GROUPS;
+constexpr int COV2_COUNTERS = 1 + 2 * COV_GROUPS;
+// TWO (small_cov2_kernel; the sparse model): blockIdx.y is 2 * model + inverse factor.  Both factors of a model read its K* and
+// mean shares; each has its own shares, group sums and group counters; per model COV2_COUNTERS counters ([0] the top level,
+// [1 + f * COV_GROUPS + g] group g of factor f): the top level is ONE count over the groups of both factors, and the model's
+// last group writes (k(a, b) - s0) + s1, mirrored.  Two ticket levels, each with its own last_of: a group's last workgroup reads its group's
 // shares behind the group's ticket, the last group reads all group sums - of both factors - behind the top ticket.
 template <int NMB, bool TWO>
 __device__ __forceinline__ void small_cov_body(SmallK k, long long ldw, long long Np, const double* Ks, int M,
@@ -524,18 +537,19 @@ __device__ __forceinline__ void small_cov_body(SmallK k, long long ldw, long lon
   __shared__ double red[VW][NMB][16][17];
   __shared__ double vt[NMB * 16][17];          // this workgroup's rows of V, transposed: [query][row]
   __shared__ double qs[SQ][SD + 1];
-  const int f = blockIdx.y;                    // the model, or the factor
-  const int y = TWO ? 0 : f;                   // the model slot of everything but W and the factor's own shares
+  const int f = blockIdx.y;                    // the model, or 2 * model + factor
+  const int y = TWO ? f >> 1 : f;              // the model slot of everything but W and the factor's own shares
+  const int fac = TWO ? f & 1 : 0;
   const unsigned ng = (gridDim.x + CG - 1) / CG;
-  const double* __restrict__ W = k.W[f];
+  const double* __restrict__ W = fac ? k.W2[y] : k.W[y];
   const double sf2 = k.sf2[y], noise = k.noise[y];
   Ks += (long long)y * SQ * Np;
   pmean += (long long)y * mean_shares * (SQ * SP);
-  double* const gcov0 = gcov;
+  double* const gcov0 = gcov + (long long)(2 * y) * ng * CE;      // (TWO) the group sums of this model's factor 0, then 1
   pcov += (long long)f * gridDim.x * CE;
   gcov += (long long)f * ng * CE;
-  unsigned* const top = counters + y * COV_COUNTERS;
-  counters += f * COV_COUNTERS;
+  unsigned* const top = counters + y * (TWO ? COV2_COUNTERS : COV_COUNTERS);
+  counters = top + fac * COV_GROUPS;
   mean_out += (long long)y * M * P;
   cov_out += (long long)y * M * M;
   const int tid = threadIdx.x;
@@ -558,7 +572,7 @@ __device__ __forceinline__ void small_cov_body(SmallK k, long long ldw, long lon
   }
   // the mean shares are complete since the previous launch (as in small_var_kernel; scratch: the reduction buffer)
   static_assert(VW * 16 * 17 >= 4 * SQ * SP, "the reduction buffer doubles as the mean scratch");
-  if (blockIdx.x == 0 && f == y) finish_means(pmean, mean_shares, M, P, k.ymean + y * P, k.ystd + y * P, mean_out, tid, &red[0][0][0][0]);
+  if (blockIdx.x == 0 && fac == 0) finish_means(pmean, mean_shares, M, P, k.ymean + y * P, k.ystd + y * P, mean_out, tid, &red[0][0][0][0]);
   const unsigned g = blockIdx.x / CG, g0 = g * CG, g1 = min(g0 + CG, gridDim.x);
   if (!last_of(counters + 1 + g, g1 - g0, tid)) return;
   for (int t = tid; t < NE; t += 64 * VW) gcov[(long long)g * CE + t] = sum_shares(pcov + t, g0, 1, g1, CE);
@@ -616,9 +630,9 @@ __global__ __launch_bounds__(64 * VW) void small_cov2_kernel(SmallK k, long long
 // shares in order and writes dvar[m][d] = -2 / ls_d * sum.  pdv: gridDim.x * gridDim.y shares per model; counter: one per model.
 constexpr unsigned WTV_MAX_ROW_CHUNKS = 4;
 constexpr int GW = 16, GRG = 16, GT = GW * 2 * GRG;      // 512 threads: column jl, query half mh, row group rg
-// TWO (small_wtv2_grad_kernel; the sparse model): blockIdx.z is the inverse factor of ONE model: the same K*, inputs and
-// queries, its own V and shares; ONE ticket count over the workgroups of both factors, and the last one overall adds each
-// factor's shares as above and writes dvar[m][d] = -2 / ls_d * (s0 - s1).
+// TWO (small_wtv2_grad_kernel; the sparse model): blockIdx.z is 2 * model + inverse factor: the model's K*, inputs and
+// queries, the factor's own V and shares; per model ONE ticket count over the workgroups of both factors, and the model's last
+// one adds each factor's shares as above and writes dvar[m][d] = -2 / ls_d * (s0 - s1).
 template <bool TWO>
 __device__ __forceinline__ void small_wtv_grad_body(SmallK k, long long ldw, long long N, long long Np, int D,
                                                     const double* __restrict__ Ks_all, const double* __restrict__ Vs_all,
@@ -629,14 +643,14 @@ __device__ __forceinline__ void small_wtv_grad_body(SmallK k, long long ldw, lon
   __shared__ double xs[GW][SD + 1];
   __shared__ double qs[SQ][SD + 1];
   __shared__ double half[2][SQ * SD];
-  const int b = blockIdx.z;                    // the model, or the factor
-  const int o = TWO ? 0 : b;                   // the model slot of everything but W, V and the factor's own shares
-  const double* __restrict__ W = k.W[b];
+  const int b = blockIdx.z;                    // the model, or 2 * model + factor
+  const int o = TWO ? b >> 1 : b;              // the model slot of everything but W, V and the factor's own shares
+  const double* __restrict__ W = (TWO && (b & 1)) ? k.W2[o] : k.W[o];
   const double* __restrict__ X = k.X[o];
   const double* ls = k.ls[o];
   const double* __restrict__ Ks = Ks_all + (long long)o * SQ * Np;
   const double* __restrict__ Vs = Vs_all + (long long)b * Np * SQ;
-  double* const pdv0 = pdv;
+  double* const pdv0 = pdv + (long long)(2 * o) * gridDim.x * gridDim.y * (M * D);     // (TWO) this model's factor 0, then 1
   pdv += (long long)b * gridDim.x * gridDim.y * (M * D);
   dvar_out += (long long)o * M * D;
   counter += o;
@@ -760,33 +774,34 @@ __global__ __launch_bounds__(GT) void small_wtv2_grad_kernel(SmallK k, long long
 
 // The device work area of one call: offsets (in doubles) of the sub-buffers the launches below hand to the kernels, and
 // their total - the one place that lays it out.  Every call has K* and the mean shares; the rest follows what it computes.
+// B models with F inverse factors each (F = 2: the two-factor kernels, slot 2 * model + factor): BF = B * F.
 struct SmallWork {
   size_t Ks;             // B x SQ x Np
   size_t pmean;          // B x ga x (SQ * SP)
-  size_t pvar;           // B x gb x SQ                             (predict, grad)
+  size_t pvar;           // BF x gb x SQ                            (predict, grad)
   size_t pjac;           // B x ga x (M * P * D)                    (grad)
-  size_t Vs;             // B x Np x SQ                             (grad)
-  size_t pdv;            // B x (gb x row chunks) x (M * D)         (grad)
-  size_t pcov, gcov;     // B x gb x CE, B x (gb / CG rounded up) x CE   (cov)
+  size_t Vs;             // BF x Np x SQ                            (grad)
+  size_t pdv;            // BF x (gb x row chunks) x (M * D)        (grad)
+  size_t pcov, gcov;     // BF x gb x CE, BF x (gb / CG rounded up) x CE   (cov)
   size_t total;
 };
-SmallWork small_work(int call, int64_t Np, int B, int64_t M, int D, int P) {
-  const size_t ga = (size_t)(Np / SJ), gb = (size_t)(Np / SR);
+SmallWork small_work(int call, int64_t Np, int B, int64_t M, int D, int P, int F = 1) {
+  const size_t ga = (size_t)(Np / SJ), gb = (size_t)(Np / SR), BF = (size_t)B * F;
   SmallWork w{};
   size_t at = 0;
   auto take = [&at](size_t doubles) { const size_t off = at; at += doubles; return off; };
   w.Ks = take((size_t)B * SQ * Np);
   w.pmean = take((size_t)B * ga * (SQ * SP));
   if (call == GPK_SMALL_COV) {
-    w.pcov = take((size_t)B * gb * CE);
-    w.gcov = take((size_t)B * ((gb + CG - 1) / CG) * CE);
+    w.pcov = take(BF * gb * CE);
+    w.gcov = take(BF * ((gb + CG - 1) / CG) * CE);
   } else {
-    w.pvar = take((size_t)B * gb * SQ);
+    w.pvar = take(BF * gb * SQ);
   }
   if (call == GPK_SMALL_GRAD) {
     w.pjac = take((size_t)B * ga * (size_t)(M * P * D));
-    w.Vs = take((size_t)B * Np * SQ);
-    w.pdv = take((size_t)B * gb * WTV_MAX_ROW_CHUNKS * (size_t)(M * D));
+    w.Vs = take(BF * Np * SQ);
+    w.pdv = take(BF * gb * WTV_MAX_ROW_CHUNKS * (size_t)(M * D));
   }
   w.total = at;
   return w;
@@ -823,20 +838,22 @@ int ensure_cov_counters(gpk_handle h) {
   return GPK_OK;
 }
 static_assert(COV_COUNTERS == 65, "one top-level counter and one per group of CG workgroups at GPK_SMALL_MAX_NP");
+static_assert(COV2_COUNTERS == 129, "two-factor form: one top-level counter per model and one per group of either factor");
 static_assert(GPK_SMALL_COV_COUNTERS >= GPK_SMALL_MAX_MODELS * COV_COUNTERS, "counters of the covariance reduction, per model");
 // the ticket counters of small_wtv_grad_kernel (one per model): the last GPK_SMALL_MAX_MODELS of h->d_cov_count
 constexpr int WTV_COUNTER0 = GPK_SMALL_COV_COUNTERS - GPK_SMALL_MAX_MODELS;
 static_assert(WTV_COUNTER0 >= GPK_SMALL_MAX_MODELS * COV_COUNTERS, "the covariance reduction's counters come first");
-// the two-factor forms (gpk_small_two): factor f takes model slot f of the parameter block, of the group counters of the
-// covariance and of the work area's per-model shares; the single ticket counts are those of slot 0
-static_assert(GPK_SMALL_MAX_MODELS >= 2, "the two-factor kernels use model slots 0 and 1");
-static_assert(GPK_SMALL_COV_COUNTERS >= 2 * COV_COUNTERS + GPK_SMALL_MAX_MODELS, "group counters of both factors, then small_wtv_grad_kernel's");
+// the two-factor forms (gpk_small_two_multi): model b takes slot b of the parameter block (its second factor: W2[b]), of the
+// single ticket counts and of the work area's per-model shares; (model b, factor f) takes slot 2 b + f of the per-factor shares
+// and the group counters [b * COV2_COUNTERS + 1 + f * COV_GROUPS + g] of the covariance
+static_assert(WTV_COUNTER0 >= GPK_SMALL_MAX_MODELS * COV2_COUNTERS,
+              "per model the top counter and the group counters of both factors, then small_wtv_grad_kernel's");
 static_assert(SR == GW, "small_wtv_grad_kernel takes as many columns of W per workgroup as small_var_kernel takes rows");
 
 }  // namespace
 
-size_t gpk_small_work_doubles(int call, int64_t Np, int B, int64_t M, int D, int P) {
-  return small_work(call, Np, B, M, D, P).total;
+size_t gpk_small_work_doubles(int call, int64_t Np, int B, int64_t M, int D, int P, int F) {
+  return small_work(call, Np, B, M, D, P, F).total;
 }
 
 bool gpk_small_ok(int64_t Np, int D, int P, int64_t M) {
@@ -945,32 +962,35 @@ int gpk_small_grad_multi(gpk_handle h, int B, const double* const* X, const doub
   return GPK_OK;
 }
 
-int gpk_small_two(gpk_handle h, int call, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
-                  double sf2, const double* y_mean, const double* y_std, const double* W0, const double* W1, int64_t Np,
-                  int64_t ldw, double kss, double floor_, double noise, const double* Xq, int64_t M, double* work,
-                  double* mean_out, double* var_out, double* dmean_out, double* dvar_out, double* cov_out) {
+int gpk_small_two_multi(gpk_handle h, int call, int B, const double* const* X, const double* const* alpha, int64_t N, int D, int P,
+                        const double* ls, const double* sf2, const double* y_mean, const double* y_std, const double* const* W0,
+                        const double* const* W1, int64_t Np, int64_t ldw, const double* kss, double floor_, const double* noise,
+                        const double* Xq, int64_t M, double* work, double* mean_out, double* var_out, double* dmean_out,
+                        double* dvar_out, double* cov_out) {
+  GPK_REQUIRE(h, B >= 1 && B <= GPK_SMALL_MAX_MODELS && (B == 1 || P == 1), "small two-factor: 1 model, or up to 8 single-output models");
   GPK_REQUIRE(h, gpk_small_ok(Np, D, P, M) && Np == gpk_padded(N), "small two-factor: shape outside the small-batch path");
   GPK_REQUIRE(h, X && alpha && mean_out, "small two-factor: null pointer");
   const bool grad = call == GPK_SMALL_GRAD, cov = call == GPK_SMALL_COV;
   GPK_REQUIRE(h, call == GPK_SMALL_PREDICT || grad || cov, "small two-factor: unknown call");
   GPK_REQUIRE(h, !grad || (dmean_out && (var_out == nullptr) == (dvar_out == nullptr)), "small two-factor: null pointer");
-  GPK_REQUIRE(h, !cov || cov_out, "small two-factor: null pointer");
+  GPK_REQUIRE(h, !cov || (cov_out && noise), "small two-factor: null pointer");
   const bool factors = cov || var_out;
   GPK_REQUIRE(h, !factors || (W0 && W1 && ldw >= Np && ldw % 2 == 0), "small two-factor: needs both inverse factors");
+  GPK_REQUIRE(h, cov || !factors || kss, "small two-factor: null pointer");
   if (cov || (grad && factors)) GPK_TRY(ensure_cov_counters(h));
-  const double* Ws[2] = {W0, W1};
   SmallK k{};
-  GPK_TRY(small_params(h, "small two-factor", 1, D, P, &X, &alpha, factors ? Ws : nullptr, ls, &sf2, factors ? &kss : nullptr, y_mean,
-                       y_std, k, cov ? &noise : nullptr));
-  if (factors) {
-    GPK_REQUIRE(h, ((uintptr_t)W1 % 16) == 0, "small two-factor: the inverse factor must be 16-byte aligned");
-    k.W[1] = W1;
-  }
+  GPK_TRY(small_params(h, "small two-factor", B, D, P, X, alpha, factors ? W0 : nullptr, ls, sf2, (factors && !cov) ? kss : nullptr,
+                       y_mean, y_std, k, cov ? noise : nullptr));
+  if (factors)
+    for (int b = 0; b < B; ++b) {
+      GPK_REQUIRE(h, W1[b] && ((uintptr_t)W1[b] % 16) == 0, "small two-factor: the inverse factor must be 16-byte aligned");
+      k.W2[b] = W1[b];
+    }
   const unsigned ga = (unsigned)(Np / SJ), gb = (unsigned)(Np / SR);
-  // the layout of two models: K*, the mean and the Jacobian shares are used once (slot 0), every other share per factor
-  const SmallWork wk = small_work(call, Np, 2, M, D, P);
+  // K*, the mean and the Jacobian shares once per model, every other share per (model, factor)
+  const SmallWork wk = small_work(call, Np, B, M, D, P, 2);
   double *Ks = work + wk.Ks, *pmean = work + wk.pmean;
-  const dim3 g1(ga, 1), g2(gb, 2), b1(256), b2(64 * VW);
+  const dim3 g1(ga, B), g2(gb, 2 * B), b1(256), b2(64 * VW);
   if (!factors) {      // the mean, or the mean and its Jacobian: one launch
     if (grad)
       hipLaunchKernelGGL((small_cross_mean_jac_kernel<true>), g1, b1, 0, h->stream, k, (long long)N, (long long)Np, D, P, Xq, (int)M,
@@ -994,9 +1014,12 @@ int gpk_small_two(gpk_handle h, int call, const double* X, const double* alpha, 
       hipLaunchKernelGGL(small_var2_grad_kernel<2>, g2, b2, 0, h->stream, k, (long long)ldw, (long long)Np, (const double*)Ks, (int)M,
                          P, floor_, (const double*)pmean, ga, pvar, vcount, mean_out, var_out, Vs, (const double*)pjac, D, dmean_out);
     GPK_LAUNCH_CHECK(h);
-    unsigned rc = 256 / (gb * 2u);      // row chunks as in gpk_small_grad_multi, the two factors counted as two models
+    // Row chunks: the rule of gpk_small_grad_multi with the two factors of ONE model counted as two models, whatever B is.  A
+    // share is not linear in its chunk's bits (C enters an fma chain), so a count that fell with B would give a model other
+    // bits inside a batch than alone; a function of Np alone keeps every sum's order fixed by (Np, M).
+    unsigned rc = 256 / (gb * 2u);
     rc = rc < 1 ? 1 : (rc > WTV_MAX_ROW_CHUNKS ? WTV_MAX_ROW_CHUNKS : rc);
-    hipLaunchKernelGGL(small_wtv2_grad_kernel, dim3(gb, rc, 2), dim3(GT), 0, h->stream, k, (long long)ldw, (long long)N, (long long)Np,
+    hipLaunchKernelGGL(small_wtv2_grad_kernel, dim3(gb, rc, 2 * B), dim3(GT), 0, h->stream, k, (long long)ldw, (long long)N, (long long)Np,
                        D, (const double*)Ks, (const double*)Vs, Xq, (int)M, pdv, h->d_cov_count + WTV_COUNTER0, dvar_out);
     GPK_LAUNCH_CHECK(h);
     return GPK_OK;
@@ -1023,4 +1046,12 @@ int gpk_small_two(gpk_handle h, int call, const double* X, const double* alpha, 
   }
   GPK_LAUNCH_CHECK(h);
   return GPK_OK;
+}
+
+int gpk_small_two(gpk_handle h, int call, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
+                  double sf2, const double* y_mean, const double* y_std, const double* W0, const double* W1, int64_t Np,
+                  int64_t ldw, double kss, double floor_, double noise, const double* Xq, int64_t M, double* work,
+                  double* mean_out, double* var_out, double* dmean_out, double* dvar_out, double* cov_out) {
+  return gpk_small_two_multi(h, call, 1, &X, &alpha, N, D, P, ls, &sf2, y_mean, y_std, W0 ? &W0 : nullptr, W1 ? &W1 : nullptr, Np, ldw,
+                             &kss, floor_, &noise, Xq, M, work, mean_out, var_out, dmean_out, dvar_out, cov_out);
 }

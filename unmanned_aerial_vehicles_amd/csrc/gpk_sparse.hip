@@ -1004,11 +1004,10 @@ extern "C" int gpk_sparse_bound(gpk_handle h, double* bound, int64_t* n_rows) {
   return GPK_OK;
 }
 
-extern "C" int gpk_sparse_predict(gpk_handle h, const double* Xq, int64_t M, double* mean, double* var,
-                                  int var_includes_noise) {
-  if (!h) return GPK_BAD_ARG;
-  gpk_sparse* s = h->sparse;
-  GPK_REQUIRE(h, s && s->finalized, "sparse_predict: no finalised sparse model (call gpk_sparse_finalize first)");
+// The serving bodies take the object apart from the handle: h supplies the stream, the pinned staging block and the work area,
+// s the model and its own panel staging (the single entries: s = h->sparse; the batch entries: one model of the list).
+static int sparse_predict(gpk_handle h, gpk_sparse* s, const double* Xq, int64_t M, double* mean, double* var,
+                          int var_includes_noise) {
   GPK_REQUIRE(h, Xq && mean && M >= 1, "sparse_predict: null pointer or empty batch");
   GPK_REQUIRE(h, h->batch == 1, "composite calls are not available in batched mode");
   GPK_CHECK_HIP(h, hipSetDevice(h->device));
@@ -1047,11 +1046,16 @@ extern "C" int gpk_sparse_predict(gpk_handle h, const double* Xq, int64_t M, dou
   });
 }
 
-extern "C" int gpk_sparse_predict_grad(gpk_handle h, const double* Xq, int64_t M, double* mean, double* var, double* dmean,
-                                       double* dvar, int var_includes_noise) {
+extern "C" int gpk_sparse_predict(gpk_handle h, const double* Xq, int64_t M, double* mean, double* var,
+                                  int var_includes_noise) {
   if (!h) return GPK_BAD_ARG;
   gpk_sparse* s = h->sparse;
-  GPK_REQUIRE(h, s && s->finalized, "sparse_predict_grad: no finalised sparse model (call gpk_sparse_finalize first)");
+  GPK_REQUIRE(h, s && s->finalized, "sparse_predict: no finalised sparse model (call gpk_sparse_finalize first)");
+  return sparse_predict(h, s, Xq, M, mean, var, var_includes_noise);
+}
+
+static int sparse_predict_grad(gpk_handle h, gpk_sparse* s, const double* Xq, int64_t M, double* mean, double* var, double* dmean,
+                               double* dvar, int var_includes_noise) {
   GPK_REQUIRE(h, Xq && mean && dmean && M >= 1, "sparse_predict_grad: null pointer or empty batch");
   GPK_REQUIRE(h, (var == nullptr) == (dvar == nullptr), "sparse_predict_grad: var and dvar come together (both or neither)");
   GPK_REQUIRE(h, h->batch == 1, "composite calls are not available in batched mode");
@@ -1104,10 +1108,15 @@ extern "C" int gpk_sparse_predict_grad(gpk_handle h, const double* Xq, int64_t M
   });
 }
 
-extern "C" int gpk_sparse_predict_cov(gpk_handle h, const double* Xq, int64_t M, double* mean, double* cov) {
+extern "C" int gpk_sparse_predict_grad(gpk_handle h, const double* Xq, int64_t M, double* mean, double* var, double* dmean,
+                                       double* dvar, int var_includes_noise) {
   if (!h) return GPK_BAD_ARG;
   gpk_sparse* s = h->sparse;
-  GPK_REQUIRE(h, s && s->finalized, "sparse_predict_cov: no finalised sparse model (call gpk_sparse_finalize first)");
+  GPK_REQUIRE(h, s && s->finalized, "sparse_predict_grad: no finalised sparse model (call gpk_sparse_finalize first)");
+  return sparse_predict_grad(h, s, Xq, M, mean, var, dmean, dvar, var_includes_noise);
+}
+
+static int sparse_predict_cov(gpk_handle h, gpk_sparse* s, const double* Xq, int64_t M, double* mean, double* cov) {
   GPK_REQUIRE(h, Xq && mean && cov && M >= 1 && M <= 16384, "sparse_predict_cov: null pointer or M outside [1, 16384]");
   GPK_REQUIRE(h, h->batch == 1, "composite calls are not available in batched mode");
   GPK_CHECK_HIP(h, hipSetDevice(h->device));
@@ -1157,6 +1166,138 @@ extern "C" int gpk_sparse_predict_cov(gpk_handle h, const double* Xq, int64_t M,
     double* out = cov + (size_t)p * M * M;
     for (size_t i = 0; i < (size_t)M * M; ++i) out[i] = sig[i] * s2;
   }
+  return GPK_OK;
+}
+
+extern "C" int gpk_sparse_predict_cov(gpk_handle h, const double* Xq, int64_t M, double* mean, double* cov) {
+  if (!h) return GPK_BAD_ARG;
+  gpk_sparse* s = h->sparse;
+  GPK_REQUIRE(h, s && s->finalized, "sparse_predict_cov: no finalised sparse model (call gpk_sparse_finalize first)");
+  return sparse_predict_cov(h, s, Xq, M, mean, cov);
+}
+
+// ---- the per-axis batch: B single-output sparse models on one query batch ---------------------------------------------------
+namespace {
+
+// The checks the three batch entries share, and the models' parameters in the layout of gpk_serve_two_multi.
+struct SparseBatch {
+  int B = 0, D = 0;
+  int64_t m = 0, mp = 0;
+  gpk_sparse* s[GPK_SMALL_MAX_MODELS] = {nullptr};
+  const double *Z[GPK_SMALL_MAX_MODELS], *alpha[GPK_SMALL_MAX_MODELS], *W0[GPK_SMALL_MAX_MODELS], *W1[GPK_SMALL_MAX_MODELS];
+  double ls[GPK_SMALL_MAX_MODELS * GPK_MAX_D_PREDICT], sf2[GPK_SMALL_MAX_MODELS], kss[GPK_SMALL_MAX_MODELS],
+      noise[GPK_SMALL_MAX_MODELS], y_mean[GPK_SMALL_MAX_MODELS], y_std[GPK_SMALL_MAX_MODELS];
+};
+int sparse_batch(gpk_handle h, const char* who, int B, const gpk_handle* models, const double* Xq, int64_t M, int64_t max_M,
+                 int var_includes_noise, SparseBatch& sb) {
+  const std::string name(who);
+  GPK_REQUIRE(h, B >= 1 && B <= GPK_SMALL_MAX_MODELS, name + ": 1..8 models");
+  GPK_REQUIRE(h, models && Xq && M >= 1, name + ": null pointer or empty batch");
+  GPK_REQUIRE(h, max_M <= 0 || M <= max_M, name + ": M outside [1, 16384]");
+  GPK_REQUIRE(h, h->batch == 1, "composite calls are not available in batched mode");
+  for (int b = 0; b < B; ++b) {
+    GPK_REQUIRE(h, models[b], name + ": null handle in the list of models");
+    gpk_sparse* s = models[b]->sparse;
+    GPK_REQUIRE(h, s && s->finalized, name + ": a model is not a finalised sparse model (call gpk_sparse_finalize first)");
+    GPK_REQUIRE(h, models[b]->device == h->device, name + ": every model must live on the serving handle's device");
+    GPK_REQUIRE(h, s->P == 1, name + ": every model must have one output");
+    GPK_REQUIRE(h, b == 0 || (s->m == sb.s[0]->m && s->D == sb.s[0]->D), name + ": the models must agree in m and D");
+    sb.s[b] = s;
+  }
+  sb.B = B; sb.D = sb.s[0]->D; sb.m = sb.s[0]->m; sb.mp = sb.s[0]->mp;
+  GPK_TRY(gpk_require_finite(h, Xq, M * sb.D, who, "Xq"));
+  for (int b = 0; b < B; ++b) {
+    const gpk_sparse* s = sb.s[b];
+    sb.Z[b] = s->Z; sb.alpha[b] = s->alpha; sb.W0[b] = s->Wuu; sb.W1[b] = s->WS;
+    for (int d = 0; d < sb.D; ++d) sb.ls[b * sb.D + d] = s->ls[d];
+    sb.sf2[b] = s->sf2; sb.noise[b] = s->noise; sb.kss[b] = gpk_kss(s->sf2, s->noise, var_includes_noise);
+    sb.y_mean[b] = s->y_mean[0]; sb.y_std[b] = s->y_std[0];
+  }
+  return GPK_OK;
+}
+bool sparse_batch_small(gpk_handle h, const SparseBatch& sb, int64_t M) {
+  return h->small_path && M <= GPK_SMALL_MAX_M && gpk_small_ok(sb.mp, sb.D, 1, M);
+}
+
+}  // namespace
+
+extern "C" int gpk_sparse_predict_multi(gpk_handle h, int B, const gpk_handle* models, const double* Xq, int64_t M, double* mean,
+                                        double* var, int var_includes_noise) {
+  if (!h) return GPK_BAD_ARG;
+  SparseBatch sb;
+  GPK_TRY(sparse_batch(h, "sparse_predict_multi", B, models, Xq, M, 0, var_includes_noise, sb));
+  GPK_REQUIRE(h, mean, "sparse_predict_multi: null pointer");
+  GPK_CHECK_HIP(h, hipSetDevice(h->device));
+  const size_t n = (size_t)B * M;
+  std::vector<double> mn(n), vr(var ? n : 0);
+  if (sparse_batch_small(h, sb, M)) {
+    GPK_TRY(gpk_serve_two_multi(h, GPK_SMALL_PREDICT, B, sb.Z, sb.alpha, sb.m, sb.D, 1, sb.ls, sb.sf2, sb.y_mean, sb.y_std,
+                                var ? sb.W0 : nullptr, var ? sb.W1 : nullptr, sb.mp, sb.mp, sb.kss, gpk_var_floor(var_includes_noise),
+                                sb.noise, Xq, M, mn.data(), var ? vr.data() : nullptr, nullptr, nullptr, nullptr));
+  } else {      // model by model through the panels of the single entry
+    for (int b = 0; b < B; ++b)
+      GPK_TRY(sparse_predict(h, sb.s[b], Xq, M, mn.data() + (size_t)b * M, var ? vr.data() + (size_t)b * M : nullptr, var_includes_noise));
+  }
+  gpk_interleave(mn.data(), B, M, 1, mean);
+  if (var) gpk_interleave(vr.data(), B, M, 1, var);
+  return GPK_OK;
+}
+
+extern "C" int gpk_sparse_predict_multi_grad(gpk_handle h, int B, const gpk_handle* models, const double* Xq, int64_t M, double* mean,
+                                             double* var, double* dmean, double* dvar, int var_includes_noise) {
+  if (!h) return GPK_BAD_ARG;
+  SparseBatch sb;
+  GPK_TRY(sparse_batch(h, "sparse_predict_multi_grad", B, models, Xq, M, 0, var_includes_noise, sb));
+  GPK_REQUIRE(h, mean && dmean, "sparse_predict_multi_grad: null pointer");
+  GPK_REQUIRE(h, (var == nullptr) == (dvar == nullptr), "sparse_predict_multi_grad: var and dvar come together (both or neither)");
+  GPK_CHECK_HIP(h, hipSetDevice(h->device));
+  const int D = sb.D;
+  const size_t n = (size_t)B * M, nd = n * D;
+  std::vector<double> mn(n), dm(nd), vr(var ? n : 0), dv(var ? nd : 0);
+  if (sparse_batch_small(h, sb, M)) {
+    GPK_TRY(gpk_serve_two_multi(h, GPK_SMALL_GRAD, B, sb.Z, sb.alpha, sb.m, D, 1, sb.ls, sb.sf2, sb.y_mean, sb.y_std,
+                                var ? sb.W0 : nullptr, var ? sb.W1 : nullptr, sb.mp, sb.mp, sb.kss, gpk_var_floor(var_includes_noise),
+                                sb.noise, Xq, M, mn.data(), var ? vr.data() : nullptr, dm.data(), var ? dv.data() : nullptr, nullptr));
+    if (var)      // model b carries y_std[b]^2, as in gpk_sparse_predict_grad
+      for (int b = 0; b < B; ++b) {
+        const double s2 = sb.y_std[b] * sb.y_std[b];
+        for (size_t i = 0; i < (size_t)M * D; ++i) dv[(size_t)b * M * D + i] = dv[(size_t)b * M * D + i] * s2;
+      }
+  } else {
+    for (int b = 0; b < B; ++b)
+      GPK_TRY(sparse_predict_grad(h, sb.s[b], Xq, M, mn.data() + (size_t)b * M, var ? vr.data() + (size_t)b * M : nullptr,
+                                  dm.data() + (size_t)b * M * D, var ? dv.data() + (size_t)b * M * D : nullptr, var_includes_noise));
+  }
+  gpk_interleave(mn.data(), B, M, 1, mean);
+  gpk_interleave(dm.data(), B, M, D, dmean);
+  if (var) {
+    gpk_interleave(vr.data(), B, M, 1, var);
+    gpk_interleave(dv.data(), B, M, D, dvar);
+  }
+  return GPK_OK;
+}
+
+extern "C" int gpk_sparse_predict_multi_cov(gpk_handle h, int B, const gpk_handle* models, const double* Xq, int64_t M, double* mean,
+                                            double* cov) {
+  if (!h) return GPK_BAD_ARG;
+  SparseBatch sb;
+  GPK_TRY(sparse_batch(h, "sparse_predict_multi_cov", B, models, Xq, M, 16384, 1, sb));
+  GPK_REQUIRE(h, mean && cov, "sparse_predict_multi_cov: null pointer");
+  GPK_CHECK_HIP(h, hipSetDevice(h->device));
+  const size_t n = (size_t)B * M, nc = (size_t)M * M;
+  std::vector<double> mn(n);
+  if (sparse_batch_small(h, sb, M)) {
+    GPK_TRY(gpk_serve_two_multi(h, GPK_SMALL_COV, B, sb.Z, sb.alpha, sb.m, sb.D, 1, sb.ls, sb.sf2, sb.y_mean, sb.y_std, sb.W0, sb.W1,
+                                sb.mp, sb.mp, nullptr, 0.0, sb.noise, Xq, M, mn.data(), nullptr, nullptr, nullptr, cov));
+    for (int b = 0; b < B; ++b) {      // block b: y_std[b]^2 Sigma_b, as in gpk_sparse_predict_cov
+      const double s2 = sb.y_std[b] * sb.y_std[b];
+      double* out = cov + (size_t)b * nc;
+      for (size_t i = 0; i < nc; ++i) out[i] = out[i] * s2;
+    }
+  } else {
+    for (int b = 0; b < B; ++b) GPK_TRY(sparse_predict_cov(h, sb.s[b], Xq, M, mn.data() + (size_t)b * M, cov + (size_t)b * nc));
+  }
+  gpk_interleave(mn.data(), B, M, 1, mean);
   return GPK_OK;
 }
 

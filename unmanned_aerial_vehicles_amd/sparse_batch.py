@@ -1,0 +1,160 @@
+"""The per-axis batch of sparse GPs (DESIGN.md, K9 "the per-axis batch"): up to eight single-output `SparseGP` models of equal
+m and D - each with its own kernel, noise, target normalisation and inducing inputs - served for one query batch in ONE C call
+(`gpk_sparse_predict_multi[_grad|_cov]`: up to 32 rows one to three launches and one synchronisation for all models).
+
+The class adds nothing to how one model is fitted or trained: every `SparseGP` keeps its own handle, statistics, pickling,
+`train` and `select_inducing`.  The serving calls return what `BatchedARDGP` returns for exact models - means (M, B),
+Jacobians (M, B, D), covariances (M, M, B) - so that `PreTrainedGP` uses either.
+"""
+from __future__ import annotations
+
+import contextlib
+import ctypes as C
+
+import numpy as np
+
+from .gpr import cholesky_draws
+from .sparse import SparseGP, _ptr
+
+MAX_MODELS = 8
+
+
+class BatchedSparseGP:
+    def __init__(self, models):
+        models = list(models)
+        if not 1 <= len(models) <= MAX_MODELS:
+            raise ValueError(f"a batch holds 1 to {MAX_MODELS} models, got {len(models)}")
+        for m in models:
+            if not isinstance(m, SparseGP):
+                raise ValueError(f"every model must be a SparseGP, got {type(m).__name__}")
+            if m.n_outputs_ != 1:
+                raise ValueError("every model of a batch must have one output")
+        shape = models[0].inducing_.shape
+        for m in models[1:]:
+            if m.inducing_.shape != shape:
+                raise ValueError(f"the models must agree in m and D: {m.inducing_.shape} against {shape}")
+        if len({id(m) for m in models}) != len(models):
+            raise ValueError("a model may appear once in a batch")
+        self.models = models
+
+    @classmethod
+    def from_exact(cls, gprs, inducing=None, selection="random", random_state=0):
+        """`SparseGP.from_exact` per model: gprs is a list of fitted single-output `GaussianProcessRegressor`s or a fitted
+        `BatchedARDGP`; `inducing` as there (an integer: that many of each model's own training rows)."""
+        gprs = getattr(gprs, "models", gprs)
+        return cls([SparseGP.from_exact(g, inducing, random_state=random_state, selection=selection) for g in gprs])
+
+    @property
+    def n_features_in_(self):
+        return self.models[0].n_features_in_
+
+    # ------------------------------------------------------------------ rows: column b of Y goes to model b
+    def _columns(self, Y):
+        Y = np.asarray(Y, dtype=np.float64)
+        if Y.ndim == 1 and len(self.models) == 1:
+            Y = Y.reshape(-1, 1)
+        if Y.ndim != 2 or Y.shape[1] != len(self.models):
+            raise ValueError(f"Y must be (n, {len(self.models)})")
+        return Y
+
+    def partial_fit(self, X, Y):
+        Y = self._columns(Y)
+        for b, m in enumerate(self.models):
+            m.partial_fit(X, np.ascontiguousarray(Y[:, b]))
+        return self
+
+    def fit(self, X, Y):
+        Y = self._columns(Y)
+        for b, m in enumerate(self.models):
+            m.fit(X, np.ascontiguousarray(Y[:, b]))
+        return self
+
+    def train(self, X, Y, **kw):
+        """`SparseGP.train(X, Y[:, b], **kw)` for each model in turn: sequential - nothing of the six trainings is fused."""
+        Y = self._columns(Y)
+        for b, m in enumerate(self.models):
+            m.train(X, np.ascontiguousarray(Y[:, b]), **kw)
+        return self
+
+    # ------------------------------------------------------------------ serving
+    def _queries(self, X):
+        X = np.array(X, dtype=np.float64, ndmin=2)
+        if not np.isfinite(X).all():
+            raise ValueError("Input X contains NaN or infinity.")
+        if X.ndim != 2 or X.shape[1] != self.n_features_in_:
+            raise ValueError(f"queries must be (M, {self.n_features_in_})")
+        return np.ascontiguousarray(X)
+
+    def _ensure(self):
+        """Every model assembled (lazily, as `SparseGP.predict` does); returns the serving backend - the first model's - and
+        the array of handles."""
+        for m in self.models:
+            m._ensure()
+            if m._P != 1:
+                raise ValueError("every model of a batch must have one output")
+        bes = [m._backend() for m in self.models]
+        if len({id(be) for be in bes}) != len(bes):
+            raise ValueError("the models of a batch need a handle each (do not share a Backend between them)")
+        handles = (C.c_void_p * len(bes))(*[be.h.value for be in bes])
+        return bes, handles
+
+    @contextlib.contextmanager
+    def _serving(self):
+        bes, handles = self._ensure()
+        with contextlib.ExitStack() as stack:
+            for be in bes:      # list order: two batches over the same models take the locks in the same order
+                stack.enter_context(be.lock)
+            bes[0].bind_stream()
+            yield bes[0], handles
+
+    def predict(self, Xq, return_std=False, return_cov=False):
+        """Means (M, B); with return_std the standard deviations (M, B), each model's WhiteKernel level included as
+        `SparseGP.predict` has it; with return_cov every model's joint covariance over the rows, (mean (M, B),
+        cov (M, M, B)) in target units (at most 16 384 rows).  Up to 32 rows: one C call, one launch for the means, two with
+        either second result, one synchronisation - for all models; column b has the bits of `models[b].predict`."""
+        if return_std and return_cov:
+            raise RuntimeError("At most one of return_std or return_cov can be requested.")
+        X = self._queries(Xq)
+        M, B = X.shape[0], len(self.models)
+        mean = np.full((M, B), np.nan)
+        if return_cov:
+            cov = np.full((B, M, M), np.nan)
+            if M > 0:
+                with self._serving() as (be, handles):
+                    be.check(be.lib.gpk_sparse_predict_multi_cov(be.h, B, handles, _ptr(X), M, _ptr(mean), _ptr(cov)))
+            return mean, np.ascontiguousarray(np.moveaxis(cov, 0, -1))
+        var = np.full((M, B), np.nan) if return_std else None
+        if M > 0:
+            with self._serving() as (be, handles):
+                be.check(be.lib.gpk_sparse_predict_multi(be.h, B, handles, _ptr(X), M, _ptr(mean),
+                                                         _ptr(var) if return_std else None, 1))
+        return (mean, np.sqrt(var)) if return_std else mean
+
+    def predict_jacobian(self, Xq, return_var=False):
+        """(mean (M, B), dmean (M, B, D)) and, with return_var, (var (M, B), dvar (M, B, D)): `SparseGP.predict_jacobian` of
+        every model in one call (`gpk_sparse_predict_multi_grad`; up to 32 rows one launch, three with the variances, one
+        synchronisation).  The shapes of `BatchedARDGP.predict_jacobian`."""
+        X = self._queries(Xq)
+        M, D, B = X.shape[0], X.shape[1], len(self.models)
+        mean, dmean = np.full((M, B), np.nan), np.full((M, B, D), np.nan)
+        var = np.full((M, B), np.nan) if return_var else None
+        dvar = np.full((M, B, D), np.nan) if return_var else None
+        if M > 0:
+            with self._serving() as (be, handles):
+                be.check(be.lib.gpk_sparse_predict_multi_grad(be.h, B, handles, _ptr(X), M, _ptr(mean),
+                                                              _ptr(var) if return_var else None, _ptr(dmean),
+                                                              _ptr(dvar) if return_var else None, 1))
+        return (mean, dmean, var, dvar) if return_var else (mean, dmean)
+
+    def sample_y(self, Xq, n_samples=1, random_state=0):
+        """Draws from every model's joint posterior at the rows Xq: (M, B, n_samples), through the Cholesky factor of each
+        covariance (`gpr.cholesky_draws`), as `BatchedARDGP.sample_y`."""
+        mean, cov = self.predict(Xq, return_cov=True)
+        return cholesky_draws(mean, cov, n_samples, random_state)
+
+    # ------------------------------------------------------------------ pickling: the models' own state
+    def __getstate__(self):
+        return {"models": self.models}
+
+    def __setstate__(self, st):
+        self.models = st["models"]

@@ -20,6 +20,7 @@ import numpy as np
 
 from .gpr import GaussianProcessRegressor
 from .kernels import RBF, ConstantKernel, WhiteKernel
+from .sparse import SparseGP
 
 OUTPUT_NAMES = ["x_residual", "y_residual", "z_residual", "vx_residual", "vy_residual", "vz_residual"]
 
@@ -174,6 +175,29 @@ class GPTrainer:
         self.training_stats = results
         return results
 
+    def sparsify(self, X, y, inducing, selection="greedy", train=False, **train_kw):
+        """Replaces every trained exact model by a sparse one that has seen ALL rows of X (n, 10), y (n, 6) - the rows a
+        `max_samples` cap (`load_training_data`, `src/px4/gp_trainer.py:95-96`) had thrown away included: per model
+        `SparseGP.from_exact(model, inducing, selection=...)` on that model's own (scaled) training inputs, then
+        `partial_fit` on all rows scaled with the stored scalers and, with train=True, `SparseGP.train(rows, **train_kw)`.
+        `save_models()` then writes a file that `PreTrainedGP` loads and serves through `BatchedSparseGP`: all models in one
+        call.  Models that are sparse already are left alone."""
+        X = np.asarray(X, dtype=np.float64)
+        y = np.asarray(y, dtype=np.float64)
+        for name, model in list(self.gp_models.items()):
+            if isinstance(model, SparseGP):
+                continue
+            i = OUTPUT_NAMES.index(name)
+            Xs = self.scalers_X[name].transform(X)
+            ys = self.scalers_y[name].transform(y[:, i].reshape(-1, 1)).ravel()
+            sp = SparseGP.from_exact(model, inducing, selection=selection)
+            if train:
+                sp.train(Xs, ys, **train_kw)
+            else:
+                sp.partial_fit(Xs, ys)
+            self.gp_models[name] = sp
+        return self
+
     def save_models(self, model_name=None):
         if model_name is None:
             model_name = f"gp_model_{datetime.now().strftime('%Y%m%d_%H%M%S')}"
@@ -188,7 +212,7 @@ class GPTrainer:
     def load_models(self, model_path):
         with open(model_path, "rb") as f:
             d = pickle.load(f)
-        self.gp_models = {n: (m if isinstance(m, GaussianProcessRegressor)
+        self.gp_models = {n: (m if isinstance(m, (GaussianProcessRegressor, SparseGP))
                               else GaussianProcessRegressor.from_sklearn(m, device=self.device))
                           for n, m in d["gp_models"].items()}
         self.scalers_X = {n: _as_scaler(v) for n, v in d["scalers_X"].items()}
@@ -220,12 +244,13 @@ class PreTrainedGP:
         by the reference's (`src/px4/gp_trainer.py:214-221`: scikit-learn regressors and scikit-learn
         `StandardScaler`s): foreign regressors are ingested with `GaussianProcessRegressor.from_sklearn`
         (X_train_, alpha_, L_, kernel_ and the target normalisation taken as they are), and any object carrying
-        `mean_` / `scale_` serves as a scaler.  A component that cannot be converted is dropped (its prediction is
+        `mean_` / `scale_` serves as a scaler.  A `SparseGP` (`GPTrainer.sparsify`) is kept as it is: its statistics are
+        imported on the device at the first prediction.  A component that cannot be converted is dropped (its prediction is
         then the reference's (0, 1e6) fallback, `pretrained_gp.py:93-96`)."""
         models, sxs, sys_ = {}, {}, {}
         for name, m in d["gp_models"].items():
             try:
-                if not isinstance(m, GaussianProcessRegressor):
+                if not isinstance(m, (GaussianProcessRegressor, SparseGP)):
                     m = GaussianProcessRegressor.from_sklearn(m, device=device)
                 models[name] = m
                 sxs[name] = _as_scaler(d["scalers_X"][name])
@@ -259,12 +284,21 @@ class PreTrainedGP:
 
     def _fused(self):
         """All loaded models share the input scaler and training inputs (they do when written by `GPTrainer`):
-        evaluate their means with one fused launch."""
+        evaluate their means with one fused launch.  Sparse models (`GPTrainer.sparsify`): single-output `SparseGP`s with
+        equal m, D and input scalers are served through `BatchedSparseGP`, all of them in one call."""
         if getattr(self, "_fused_bg", None) is None:
             self._fused_bg = False
             try:
                 names = [n for n in OUTPUT_NAMES if n in self.gp_models]
-                if 2 <= len(names) <= 8:
+                if 2 <= len(names) <= 8 and all(isinstance(self.gp_models[n], SparseGP) for n in names):
+                    sx0 = self.scalers_X[names[0]]
+                    ms = [self.gp_models[n] for n in names]
+                    if all(np.array_equal(self.scalers_X[n].mean_, sx0.mean_) and
+                           np.array_equal(self.scalers_X[n].scale_, sx0.scale_) for n in names) and all(
+                            m.n_outputs_ == 1 and m.inducing_.shape == ms[0].inducing_.shape for m in ms):
+                        from .sparse_batch import BatchedSparseGP
+                        self._fused_bg = (BatchedSparseGP(ms), names)
+                elif 2 <= len(names) <= 8:
                     sx0 = self.scalers_X[names[0]]
                     m0 = self.gp_models[names[0]]
                     x0 = getattr(m0, "X_train_", None)
