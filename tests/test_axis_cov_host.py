@@ -137,3 +137,165 @@ def test_not_loaded_returns_the_fallbacks(tmp_path):
     mean, cov = g.predict_residual_cov_batch(np.zeros((4, 7)))
     assert mean.shape == (4, 6) and cov.shape == (4, 4, 6)
     assert g.sample_residuals(np.zeros((4, 7)), 2).shape == (4, 6, 2)
+
+
+# ---- PreTrainedGP's three batch surfaces and the draws, route by route, on fakes with closed forms ------------------------------
+# Model k (its place in OUTPUT_NAMES) on scaled rows Z = (X - 0.5) / 2; the fused object answers differently from the models
+# (mean + 100, std + 1, Jacobians x 3, covariance x 2), so every expected array says which route filled it.
+def _own(k, Z):
+    M = len(Z)
+    mu, s = (k + 1) * Z.sum(axis=1), 0.25 * (k + 1) + np.abs(Z[:, 0])
+    return {"mu": mu, "s": s, "dmu": (k + 1) * np.tile(np.arange(1.0, 11.0), (M, 1)), "var": s ** 2,
+            "dvar": s[:, None] * np.arange(1.0, 11.0) / 10.0, "cov": (k + 1) * (np.eye(M) + 0.5 * np.outer(Z[:, 0], Z[:, 0]))}
+
+
+def _via_fused(k, Z):
+    o = _own(k, Z)
+    return {"mu": o["mu"] + 100.0, "s": o["s"] + 1.0, "dmu": 3.0 * o["dmu"], "var": (o["s"] + 1.0) ** 2, "dvar": 3.0 * o["dvar"],
+            "cov": 2.0 * o["cov"]}
+
+
+class _FakeModel:
+    def __init__(self, k):
+        self.k, self.fail = k, False
+
+    def _o(self, Z):
+        if self.fail:
+            raise RuntimeError(f"model {self.k} down")
+        return _own(self.k, np.asarray(Z, dtype=np.float64))
+
+    def predict(self, Z, return_std=False, return_cov=False):
+        o = self._o(Z)
+        return (o["mu"], o["cov"]) if return_cov else (o["mu"], o["s"]) if return_std else o["mu"]
+
+    def predict_jacobian(self, Z, return_var=False):
+        o = self._o(Z)
+        return (o["mu"], o["dmu"], o["var"], o["dvar"]) if return_var else (o["mu"], o["dmu"])
+
+
+class _FakeFused:
+    def __init__(self, ks):
+        self.ks, self.fail = ks, False
+
+    def _o(self, Z, key, axis=1):
+        if self.fail:
+            raise RuntimeError("fused down")
+        return np.stack([_via_fused(k, np.asarray(Z, dtype=np.float64))[key] for k in self.ks], axis=axis)
+
+    def predict(self, Z, return_std=False, return_cov=False):
+        if return_cov:
+            return self._o(Z, "mu"), self._o(Z, "cov", 2)
+        return (self._o(Z, "mu"), self._o(Z, "s")) if return_std else self._o(Z, "mu")
+
+    def predict_jacobian(self, Z, return_var=False):
+        out = (self._o(Z, "mu"), self._o(Z, "dmu"))
+        return out + (self._o(Z, "var"), self._o(Z, "dvar")) if return_var else out
+
+
+def _expected(X, routes):
+    """What the four surfaces return when component i is filled by routes[i]: "fused", "own" or None (the fallbacks)."""
+    M = len(X)
+    Z = (X - 0.5) / 2.0 if X.shape[1] == 10 else None
+    e = {"mean": np.zeros((M, 6)), "std": np.full((M, 6), 1e6), "J": np.zeros((M, 6, 10)), "dstd": np.zeros((M, 6, 10)),
+         "jmean": np.zeros((M, 6)), "jstd": np.full((M, 6), 1e6), "cmean": np.zeros((M, 6)),
+         "cov": np.repeat((1e12 * np.eye(M))[:, :, None], 6, axis=2), "draws": np.zeros((M, 6, 2))}
+    z = np.random.RandomState(0).standard_normal((6, M, 2))
+    for i, r in enumerate(routes):
+        if r is None:
+            continue
+        o = (_via_fused if r == "fused" else _own)(i, Z)
+        e["mean"][:, i] = e["jmean"][:, i] = e["cmean"][:, i] = 2.0 * o["mu"] + 0.5
+        e["std"][:, i] = 2.0 * o["s"]
+        sig = np.sqrt(o["var"])
+        e["J"][:, i], e["jstd"][:, i] = 2.0 * o["dmu"] / 2.0, 2.0 * sig
+        e["dstd"][:, i] = 2.0 * (o["dvar"] / (2.0 * sig[:, None])) / 2.0
+        e["cov"][:, :, i] = 4.0 * o["cov"]
+        e["draws"][:, i, :] = e["cmean"][:, i, None] + np.linalg.cholesky(e["cov"][:, :, i]) @ z[i]
+    return e
+
+
+def _fake_pretrained(tmp_path, present=range(6)):
+    from unmanned_aerial_vehicles_amd.trainer import OUTPUT_NAMES, PreTrainedGP, StandardScaler
+    g = PreTrainedGP(str(tmp_path / "no_such_model.pkl"))
+    for k in present:
+        n = OUTPUT_NAMES[k]
+        g.gp_models[n] = _FakeModel(k)
+        sx, sy = StandardScaler(), StandardScaler()
+        sx.mean_, sx.scale_ = np.full(10, 0.5), np.full(10, 2.0)
+        sy.mean_, sy.scale_ = np.full(1, 0.5), np.full(1, 2.0)
+        g.scalers_X[n], g.scalers_y[n] = sx, sy
+    g.is_loaded = True
+    g._fused_bg = (_FakeFused(list(present)), [OUTPUT_NAMES[k] for k in present])
+    return g
+
+
+def _close(a, b):
+    return a.shape == b.shape and np.allclose(a, b, rtol=1e-13, atol=0.0)
+
+
+def _check_surfaces(g, X, e, capsys, batch_std=True, batch_routes_e=None, lines=None):
+    """The four surfaces against `e`; `batch_routes_e`: predict_residual_batch's own expectation where it differs;
+    `lines`: the set of lines the four calls print between them."""
+    capsys.readouterr()
+    eb = e if batch_routes_e is None else batch_routes_e
+    mean, std = g.predict_residual_batch(X)
+    assert _close(mean, eb["mean"]) and _close(std, eb["std"])
+    out = g.predict_residual_jacobian_batch(X, return_std=True)
+    assert len(out) == 4
+    for got, key in zip(out, ("jmean", "J", "jstd", "dstd")):
+        assert _close(got, e[key]), key
+    mean2, J2 = g.predict_residual_jacobian_batch(X)
+    assert _close(mean2, e["jmean"]) and _close(J2, e["J"])
+    cmean, cov = g.predict_residual_cov_batch(X)
+    assert _close(cmean, e["cmean"]) and _close(cov, e["cov"])
+    draws = g.sample_residuals(X, n_samples=2)
+    assert _close(draws, e["draws"])
+    if lines is not None:
+        assert set(capsys.readouterr().out.splitlines()) == set(lines)
+
+
+def test_pretrained_batch_surfaces_route_by_route(tmp_path, capsys):
+    from unmanned_aerial_vehicles_amd.trainer import OUTPUT_NAMES
+    X = np.random.default_rng(5).standard_normal((3, 10))
+    # the fused call serves everything
+    g = _fake_pretrained(tmp_path)
+    e = _expected(X, ["fused"] * 6)
+    _check_surfaces(g, X, e, capsys, lines=[])
+    mean, std = g.predict_residual_batch(X, return_std=False)
+    assert _close(mean, e["mean"]) and std is None
+    # the fused call raises: every model's own call serves; without return_std predict_residual_batch ends with zeros
+    g._fused_bg[0].fail = True
+    e = _expected(X, ["own"] * 6)
+    _check_surfaces(g, X, e, capsys, lines=["GP prediction failed: fused down"])
+    mean, std = g.predict_residual_batch(X, return_std=False)
+    assert mean.shape == (3, 6) and not mean.any() and std is None
+    assert capsys.readouterr().out.splitlines() == ["GP prediction failed: fused down"]
+    # ... and one model's own call raises as well: that component is the fallback
+    g.gp_models["z_residual"].fail = True
+    e = _expected(X, ["own", "own", None, "own", "own", "own"])
+    _check_surfaces(g, X, e, capsys, lines=["GP prediction failed: fused down", "GP prediction failed for z_residual: model 2 down"])
+    # no fused object at all: the models' own calls, and predict_residual_batch hands back the stds it computed anyway
+    g._fused_bg = False
+    _check_surfaces(g, X, e, capsys, lines=["GP prediction failed for z_residual: model 2 down"])
+    mean, std = g.predict_residual_batch(X, return_std=False)
+    assert _close(mean, e["mean"]) and _close(std, e["std"])
+    # one model missing, the fused call serving the other five; then failing
+    g = _fake_pretrained(tmp_path, present=[0, 1, 2, 4, 5])
+    _check_surfaces(g, X, _expected(X, ["fused", "fused", "fused", None, "fused", "fused"]), capsys, lines=[])
+    g._fused_bg[0].fail = True
+    _check_surfaces(g, X, _expected(X, ["own", "own", "own", None, "own", "own"]), capsys,
+                    lines=["GP prediction failed: fused down"])
+    # rows of width 7: the fallbacks everywhere, nothing raises
+    g = _fake_pretrained(tmp_path)
+    X7 = np.random.default_rng(6).standard_normal((3, 7))
+    capsys.readouterr()
+    _check_surfaces(g, X7, _expected(X7, [None] * 6), capsys)
+    printed = capsys.readouterr().out.splitlines()
+    assert printed and all(ln.startswith("GP prediction failed") for ln in printed)
+    for n in OUTPUT_NAMES:      # (the Jacobian surface refuses the width before any call; the other two try every model)
+        assert sum(ln.startswith(f"GP prediction failed for {n}: ") for ln in printed) == 3
+    # nothing loaded
+    g.is_loaded = False
+    _check_surfaces(g, X, _expected(X, [None] * 6), capsys, lines=[])
+    mean, std = g.predict_residual_batch(X, return_std=False)
+    assert not mean.any() and np.array_equal(std, np.full((3, 6), 1e6))

@@ -23,6 +23,7 @@ GPK_TIMED_SPARSE_STATS, GPK_TIMED_SPARSE_PASS = 7, 8
 
 _vp, _i64, _int, _dbl = C.c_void_p, C.c_int64, C.c_int, C.c_double
 _dp = C.POINTER(C.c_double)
+_f64 = np.dtype(np.float64)      # (a dtype instance: comparing against the type object costs several times as much)
 
 # name -> (restype, argtypes); mirrors include/gpk.h one to one
 SIGNATURES = {
@@ -178,7 +179,20 @@ def load():
     return lib
 
 
-def dptr(a):
-    """Host double array -> POINTER(c_double) (the array must stay alive during the call)."""
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    return a, a.ctypes.data_as(_dp)
+def dev_ptr(t):
+    """Device tensor -> c_void_p (None: NULL).  The tensor must be contiguous and stay alive during the call."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def host_ptr(a):
+    """Host array -> POINTER(c_double) (None: NULL).  Only a C-contiguous float64 ndarray is taken - anything else would
+    hand the library an address it reads with the wrong strides or element size; the array must stay alive during the call."""
+    if a is None:
+        return None
+    if not (isinstance(a, np.ndarray) and a.dtype == _f64 and a.flags.c_contiguous):
+        raise TypeError("host_ptr takes a C-contiguous float64 ndarray, got "
+                        + (f"{a.dtype} with strides {a.strides}" if isinstance(a, np.ndarray) else type(a).__name__))
+    try:        # (through the buffer protocol: a third of the time of numpy's `ctypes.data_as`, and these run at the control rate)
+        return _dp(C.c_double.from_buffer(a))
+    except (TypeError, ValueError):     # a read-only or empty array has no writable buffer to export
+        return a.ctypes.data_as(_dp)

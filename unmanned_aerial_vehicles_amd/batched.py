@@ -16,7 +16,8 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 from . import _lib
-from .device import Backend, get_backend
+from ._lib import dev_ptr as _p, host_ptr as _hp
+from .device import Backend, check_queries, get_backend
 from .gpr import GaussianProcessRegressor, cholesky_draws
 from .kernels import RBF, ConstantKernel, WhiteKernel
 
@@ -186,31 +187,28 @@ class BatchedARDGP:
     def _lml_fused(self, thetas, eval_gradient):
         fs = self._fused_state()
         be, B, N, D, Np = fs["be"], fs["B"], fs["N"], fs["D"], fs["Np"]
-        lib, dp = be.lib, _lib._dp
         comps = [self.models[b].kernel_.clone_with_theta(thetas[b]).components() for b in range(B)]
         ls = [np.ascontiguousarray(c.ls_vector(D)) for c in comps]
-        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
         info = (C.c_int * B)()
-        with be.lock:
-            be.bind_stream()
+        with be.lock:            # (the batched chain and the per-model terms read the stacked buffers: one sequence)
             for b in range(B):       # K1 per model (one launch each)
-                be.check(lib.gpk_gram(be.h, _lib.GPK_F64, p(fs["X"]), N, D, ls[b].ctypes.data_as(dp), comps[b].sf2,
-                                      (comps[b].noise or 0.0) + float(self.alpha), p(fs["K"][b]), Np))
-            be.check(lib.gpk_batch_begin(be.h, B))
+                be.call("gpk_gram", _lib.GPK_F64, _p(fs["X"]), N, D, _hp(ls[b]), comps[b].sf2,
+                        (comps[b].noise or 0.0) + float(self.alpha), _p(fs["K"][b]), Np)
+            be.call("gpk_batch_begin", B)
             try:
                 for name, row_bytes in (("K", Np * Np * 8), ("winv", Np * 128 * 8), ("W", Np * Np * 8),
                                         ("Kinv", Np * Np * 8), ("T", fs["tsz"] * 8), ("Yn", fs["Ne"] * 8),
                                         ("alpha", fs["Ne"] * 8)):
-                    be.check(lib.gpk_batch_buffer(be.h, p(fs[name]), row_bytes))
-                rc = lib.gpk_potrf(be.h, p(fs["K"]), Np, Np, p(fs["winv"]), info)          # K2, B problems
-                if rc not in (_lib.GPK_OK, _lib.GPK_NOT_PD):
+                    be.call("gpk_batch_buffer", _p(fs[name]), row_bytes)
+                rc = be.status("gpk_potrf", _p(fs["K"]), Np, Np, _p(fs["winv"]), info)          # K2, B problems
+                if rc != _lib.GPK_NOT_PD:      # (a model that is not positive definite is a result: info[b] says which)
                     be.check(rc)
-                be.check(lib.gpk_trtri(be.h, p(fs["K"]), Np, Np, p(fs["winv"]), p(fs["W"]), Np, p(fs["T"])))
-                be.check(lib.gpk_potrs_inv(be.h, p(fs["W"]), Np, Np, p(fs["Yn"]), N, 1, p(fs["alpha"])))   # K3
+                be.call("gpk_trtri", _p(fs["K"]), Np, Np, _p(fs["winv"]), _p(fs["W"]), Np, _p(fs["T"]))
+                be.call("gpk_potrs_inv", _p(fs["W"]), Np, Np, _p(fs["Yn"]), N, 1, _p(fs["alpha"]))   # K3
                 if eval_gradient:
-                    be.check(lib.gpk_wtw(be.h, p(fs["W"]), Np, Np, p(fs["Kinv"]), Np))
+                    be.call("gpk_wtw", _p(fs["W"]), Np, Np, _p(fs["Kinv"]), Np)
             finally:
-                lib.gpk_batch_end(be.h)
+                be.status("gpk_batch_end")
             lml = np.full(B, -np.inf)
             grad = np.zeros((B, thetas.shape[1]))
             terms = np.zeros(2)
@@ -218,13 +216,11 @@ class BatchedARDGP:
             for b in range(B):
                 if info[b] != 0:       # not positive definite: (-inf, 0) as sklearn/_gpr.py:588-589
                     continue
-                be.check(lib.gpk_lml_terms(be.h, p(fs["K"][b]), N, Np, p(fs["Yn"][b]), p(fs["alpha"][b]), 1,
-                                           terms.ctypes.data_as(dp)))
+                be.call("gpk_lml_terms", _p(fs["K"][b]), N, Np, _p(fs["Yn"][b]), _p(fs["alpha"][b]), 1, _hp(terms))
                 lml[b] = -0.5 * terms[1] - terms[0] - 0.5 * N * np.log(2.0 * np.pi)
                 if eval_gradient:
-                    be.check(lib.gpk_lml_grad(be.h, p(fs["X"]), N, D, ls[b].ctypes.data_as(dp), comps[b].sf2,
-                                              comps[b].noise or 0.0, p(fs["alpha"][b]), 1, p(fs["Kinv"][b]), Np,
-                                              g.ctypes.data_as(dp)))
+                    be.call("gpk_lml_grad", _p(fs["X"]), N, D, _hp(ls[b]), comps[b].sf2, comps[b].noise or 0.0,
+                            _p(fs["alpha"][b]), 1, _p(fs["Kinv"][b]), Np, _hp(g))
                     grad[b] = comps[b].map_gradient(g, D)
         return (lml, grad) if eval_gradient else lml
 
@@ -274,27 +270,34 @@ class BatchedARDGP:
             q = Xq.to(device=be.device, dtype=f["tdt"]).contiguous()
         else:
             q = be.upload(np.ascontiguousarray(Xq, dtype=np.float64), f["tdt"])
-        M, B = q.shape[0], len(self.models)
-        out = be.empty((M, B), f["tdt"])
-        if M == 0:
-            return out
+        M = q.shape[0]
         if (f["code"] == _lib.GPK_F32 and M >= self.MFMA_MIN_QUERIES
                 and all(m._dev.mean_kernel_choice() == "mfma" for m in self.models)):
             # large fp32 batches: one matrix-core launch per model (distances on the bf16 MFMA pipe) beats the
             # fused vector-ALU kernel (0.115 vs 0.158 ms at N = 4096, 10 000 queries, B = 3)
             cols = [m._dev.predict_mean_dev(q, m._y_train_mean, m._y_train_std, "float32", "mfma") for m in self.models]
             return torch.cat(cols, dim=1)
-        dp = _lib._dp
-        with be.lock:
-            be.bind_stream()
-            be.check(be.lib.gpk_predict_mean_multi(
-                be.h, f["code"], C.c_void_p(f["X"].data_ptr()), C.c_void_p(f["alpha"].data_ptr()), f["N"], f["D"], B,
-                f["ls"].ctypes.data_as(dp), f["sf2"].ctypes.data_as(dp), f["ym"].ctypes.data_as(dp),
-                f["ys"].ctypes.data_as(dp), C.c_void_p(q.data_ptr()), M, C.c_void_p(out.data_ptr())))
+        return self._fused_mean(f, q)
+
+    def _fused_mean(self, f, q):
+        """`gpk_predict_mean_multi`: the posterior means of all B models at the rows q (a device tensor of f's dtype) in one
+        launch on the buffers f (`_fused` or `_fused64()`); returns the (M, B) tensor."""
+        be = get_backend(self.device)
+        M, B = q.shape[0], len(self.models)
+        out = be.empty((M, B), f["tdt"])
+        if M > 0:
+            be.call("gpk_predict_mean_multi", f["code"], _p(f["X"]), _p(f["alpha"]), f["N"], f["D"], B, _hp(f["ls"]),
+                    _hp(f["sf2"]), _hp(f["ym"]), _hp(f["ys"]), _p(q), M, _p(out))
         return out
 
     # ------------------------------------------------------------------ control-loop batches
     SERVE_MAX_M = 32
+
+    @staticmethod
+    def _alike(devs):
+        """The models can share a launch: all factored, one output each, the same N and D, on one device."""
+        d0 = devs[0]
+        return all(d.factored and d.P == 1 and d.N == d0.N and d.D == d0.D and d.be.device == d0.be.device for d in devs)
 
     def _serve_state(self, want_std, any_dtype=False):
         """Argument block of `gpk_predict_host_multi` (one call, two launches for all models), or None when the
@@ -312,8 +315,7 @@ class BatchedARDGP:
         sv = getattr(self, "_serve", None)
         if sv is None or sv["key"] != key:
             d0 = devs[0]
-            ok = all(d.factored and d.P == 1 and d.N == d0.N and d.D == d0.D and d.be.device == d0.be.device for d in devs)
-            if not ok or d0.D > 16 or d0.Np > 16384:
+            if not self._alike(devs) or d0.D > 16 or d0.Np > 16384:
                 self._serve = {"key": key, "ok": False}
                 return None
             comps = [m.kernel_.components() for m in ms]
@@ -345,26 +347,44 @@ class BatchedARDGP:
 
     def predict_host(self, Xq, return_std=False):
         """<= 32 rows, all models, one C call: (mean (M, B), std (M, B) or None); None if the models do not qualify."""
-        sv = self._serve_state(return_std)
-        if sv is None:
+        st = self._host_queries(Xq, want_W=return_std, any_dtype=False, row_gate=False)
+        if st is None:
             return None
-        Xq = np.ascontiguousarray(Xq, dtype=np.float64)
-        M, B, d0 = Xq.shape[0], sv["B"], sv["dev0"]
-        if Xq.ndim != 2 or Xq.shape[1] != d0.D:
-            raise ValueError(f"queries must be (M, {d0.D})")
+        sv, Xq, M = st
+        B = sv["B"]
         mean = np.empty((B, M))
         var = np.empty((B, M)) if return_std else None
-        be = d0.be
-        with be.lock:
-            be.bind_stream()
-            be.check(be.lib.gpk_predict_host_multi(
-                be.h, B, sv["X"], sv["alpha"], d0.N, d0.D, sv["ls"].ctypes.data, sv["sf2"].ctypes.data,
-                sv["ym"].ctypes.data, sv["ys"].ctypes.data, sv["W"] if return_std else None, d0.Np, d0.Np,
-                sv["kss"].ctypes.data, 0.0, Xq.ctypes.data, M, mean.ctypes.data,
-                var.ctypes.data if return_std else None))
+        self._host_call("gpk_predict_host_multi", sv, return_std, sv["kss"].ctypes.data, 0.0, _hp(Xq), M, _hp(mean), _hp(var))
         if not return_std:
             return mean.T, None
         return mean.T, (np.sqrt(var) * sv["ys"][:, None]).T
+
+    # What the one-call entries over all models (gpk_predict_host_multi / _multi_grad / _multi_cov) share, in two steps so that
+    # a caller can size its outputs in between.  They run at the control rate: no closure, no argument list built per call.
+    def _host_queries(self, Xq, want_W, any_dtype, row_gate):
+        """(the serve state of `_serve_state(want_W, any_dtype)`, the queries as a contiguous float64 (M, D) array, M) - or
+        None when the models do not qualify or, with `row_gate`, M is outside 1 .. SERVE_MAX_M."""
+        sv = self._serve_state(want_W, any_dtype)
+        if sv is None:
+            return None
+        Xq = np.ascontiguousarray(Xq, dtype=np.float64)
+        D = sv["dev0"].D
+        if Xq.ndim != 2 or Xq.shape[1] != D:
+            raise ValueError(f"queries must be (M, {D})")
+        M = Xq.shape[0]
+        if row_gate and not (1 <= M <= self.SERVE_MAX_M):
+            return None
+        return sv, Xq, M
+
+    def _host_call(self, entry, sv, want_W, *tail):
+        """`entry(handle, the models' argument block, W or NULL, Np, ldw, *tail)`: `tail` is what follows in the entry's own
+        order - its scalars, the queries' address, M, the outputs' addresses."""
+        d0 = sv["dev0"]
+        head = sv.get("head")
+        if head is None:        # (the leading arguments, addresses included, once per serve state: each conversion costs per call)
+            head = sv["head"] = (sv["B"], sv["X"], sv["alpha"], d0.N, d0.D, sv["ls"].ctypes.data, sv["sf2"].ctypes.data,
+                                 sv["ym"].ctypes.data, sv["ys"].ctypes.data)
+        d0.be.call(entry, *head, sv["W"] if want_W else None, d0.Np, d0.Np, *tail)
 
     # ------------------------------------------------------------------ input gradients (K8, per-axis batch)
     def predict_host_grad(self, Xq, return_var=False):
@@ -372,27 +392,15 @@ class BatchedARDGP:
         with the variances and their gradients three): (mean (M, B), dmean (M, B, D), var (M, B) or None, dvar (M, B, D) or
         None), var / dvar in target units (times y_std^2), dvar the gradient of the unclipped variance.  None if the models
         do not qualify (the conditions of `_serve_state`).  Always the fp64 kernels: an fp32-serving batch is served too."""
-        sv = self._serve_state(return_var, any_dtype=True)
-        if sv is None:
+        st = self._host_queries(Xq, want_W=return_var, any_dtype=True, row_gate=True)
+        if st is None:
             return None
-        Xq = np.ascontiguousarray(Xq, dtype=np.float64)
-        d0 = sv["dev0"]
-        if Xq.ndim != 2 or Xq.shape[1] != d0.D:
-            raise ValueError(f"queries must be (M, {d0.D})")
-        M, B, D = Xq.shape[0], sv["B"], d0.D
-        if not (1 <= M <= self.SERVE_MAX_M):
-            return None
+        sv, Xq, M = st
+        B, D = sv["B"], sv["dev0"].D
         mean, dmean = np.empty((B, M)), np.empty((B, M, D))
-        var = np.empty((B, M)) if return_var else None
-        dvar = np.empty((B, M, D)) if return_var else None
-        be = d0.be
-        with be.lock:
-            be.bind_stream()
-            be.check(be.lib.gpk_predict_host_multi_grad(
-                be.h, B, sv["X"], sv["alpha"], d0.N, D, sv["ls"].ctypes.data, sv["sf2"].ctypes.data,
-                sv["ym"].ctypes.data, sv["ys"].ctypes.data, sv["W"] if return_var else None, d0.Np, d0.Np,
-                sv["kss"].ctypes.data, 0.0, Xq.ctypes.data, M, mean.ctypes.data,
-                var.ctypes.data if return_var else None, dmean.ctypes.data, dvar.ctypes.data if return_var else None))
+        var, dvar = (np.empty((B, M)), np.empty((B, M, D))) if return_var else (None, None)
+        self._host_call("gpk_predict_host_multi_grad", sv, return_var, sv["kss"].ctypes.data, 0.0, _hp(Xq), M,
+                        _hp(mean), _hp(var), _hp(dmean), _hp(dvar))
         mean, dmean = mean.T, dmean.transpose(1, 0, 2)
         if not return_var:
             return mean, dmean, None, None
@@ -425,9 +433,7 @@ class BatchedARDGP:
         launch and the fused mean-Jacobian launch (`gpk_predict_mean_grad_multi`: the feature differences of a pair formed
         once for all models) plus one variance-gradient chain per model.  Always fp64, as
         `GaussianProcessRegressor.predict_jacobian`."""
-        Xq = np.array(Xq, dtype=np.float64, ndmin=2)
-        if not np.isfinite(Xq).all():
-            raise ValueError("Input X contains NaN or infinity.")
+        Xq = check_queries(Xq)
         if 1 <= Xq.shape[0] <= self.SERVE_MAX_M:
             out = self.predict_host_grad(Xq, return_var)
             if out is not None:
@@ -457,18 +463,10 @@ class BatchedARDGP:
         be = get_backend(self.device)
         q = be.upload(np.ascontiguousarray(Xq, dtype=np.float64), torch.float64)
         M, B, D = q.shape[0], len(self.models), f["D"]
-        mean_d, dmean_d = be.empty((M, B), torch.float64), be.empty((M, B, D), torch.float64)
+        mean_d, dmean_d = self._fused_mean(f, q), be.empty((M, B, D), torch.float64)
         if M > 0:
-            dp = _lib._dp
-            p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-            with be.lock:
-                be.bind_stream()
-                be.check(be.lib.gpk_predict_mean_multi(
-                    be.h, _lib.GPK_F64, p(f["X"]), p(f["alpha"]), f["N"], D, B, f["ls"].ctypes.data_as(dp),
-                    f["sf2"].ctypes.data_as(dp), f["ym"].ctypes.data_as(dp), f["ys"].ctypes.data_as(dp), p(q), M, p(mean_d)))
-                be.check(be.lib.gpk_predict_mean_grad_multi(
-                    be.h, p(f["X"]), p(f["alpha"]), f["N"], D, B, f["ls"].ctypes.data_as(dp), f["sf2"].ctypes.data_as(dp),
-                    f["ys"].ctypes.data_as(dp), p(q), M, p(dmean_d)))
+            be.call("gpk_predict_mean_grad_multi", _p(f["X"]), _p(f["alpha"]), f["N"], D, B, _hp(f["ls"]), _hp(f["sf2"]),
+                    _hp(f["ys"]), _p(q), M, _p(dmean_d))
         mean, dmean = mean_d.cpu().numpy(), dmean_d.cpu().numpy()
         if not return_var:
             return mean, dmean
@@ -486,26 +484,14 @@ class BatchedARDGP:
         them): (mean (M, B), cov (M, M, B)), cov in target units (times y_std^2), each model's WhiteKernel level on its own
         diagonal, not clipped, symmetric bit for bit.  None if the models do not qualify (the conditions of `_serve_state`).
         Always the fp64 kernels: an fp32-serving batch is served too."""
-        sv = self._serve_state(True, any_dtype=True)
-        if sv is None:
+        st = self._host_queries(Xq, want_W=True, any_dtype=True, row_gate=True)
+        if st is None:
             return None
-        Xq = np.ascontiguousarray(Xq, dtype=np.float64)
-        d0 = sv["dev0"]
-        if Xq.ndim != 2 or Xq.shape[1] != d0.D:
-            raise ValueError(f"queries must be (M, {d0.D})")
-        M, B = Xq.shape[0], sv["B"]
-        if not (1 <= M <= self.SERVE_MAX_M):
-            return None
+        sv, Xq, M = st
         if sv.get("noise") is None:
             sv["noise"] = np.ascontiguousarray([m.kernel_.components().noise or 0.0 for m in self.models], dtype=np.float64)
-        mean, cov = np.empty((B, M)), np.empty((B, M, M))
-        be = d0.be
-        with be.lock:
-            be.bind_stream()
-            be.check(be.lib.gpk_predict_host_multi_cov(
-                be.h, B, sv["X"], sv["alpha"], d0.N, d0.D, sv["ls"].ctypes.data, sv["sf2"].ctypes.data,
-                sv["ym"].ctypes.data, sv["ys"].ctypes.data, sv["W"], d0.Np, d0.Np, sv["noise"].ctypes.data,
-                Xq.ctypes.data, M, mean.ctypes.data, cov.ctypes.data))
+        mean, cov = np.empty((sv["B"], M)), np.empty((sv["B"], M, M))
+        self._host_call("gpk_predict_host_multi_cov", sv, True, sv["noise"].ctypes.data, _hp(Xq), M, _hp(mean), _hp(cov))
         return mean.T, (cov * (sv["ys"] ** 2)[:, None, None]).transpose(1, 2, 0)
 
     def _predict_cov(self, Xq):
@@ -520,9 +506,7 @@ class BatchedARDGP:
         for m in self.models:
             m._ensure_device()
         devs = [m._dev for m in self.models]
-        fused = (1 <= B <= 8 and M >= 1 and all(d.factored and d.P == 1 and d.N == devs[0].N and d.D == devs[0].D
-                                                 and d.be.device == devs[0].be.device for d in devs)
-                 and self._shared_inputs())
+        fused = 1 <= B <= 8 and M >= 1 and self._alike(devs) and self._shared_inputs()
         if not fused:
             outs = [m.predict(Xq, return_cov=True) for m in self.models]
             return np.stack([o[0] for o in outs], axis=1), np.stack([o[1] for o in outs], axis=2)
@@ -530,15 +514,7 @@ class BatchedARDGP:
         f = self._fused64()
         be = get_backend(self.device)
         q = be.upload(np.ascontiguousarray(Xq, dtype=np.float64), torch.float64)
-        mean_d = be.empty((M, B), torch.float64)
-        dp = _lib._dp
-        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        with be.lock:
-            be.bind_stream()
-            be.check(be.lib.gpk_predict_mean_multi(
-                be.h, _lib.GPK_F64, p(f["X"]), p(f["alpha"]), f["N"], f["D"], B, f["ls"].ctypes.data_as(dp),
-                f["sf2"].ctypes.data_as(dp), f["ym"].ctypes.data_as(dp), f["ys"].ctypes.data_as(dp), p(q), M, p(mean_d)))
-        mean = mean_d.cpu().numpy()
+        mean = self._fused_mean(f, q).cpu().numpy()
         cov = np.empty((M, M, B))
         for b, m in enumerate(self.models):      # K*, W and the length-scales differ per model: nothing to share
             c = m._dev.predict_cov_dev(Xq, m.kernel_.components().noise or 0.0)
@@ -559,10 +535,7 @@ class BatchedARDGP:
         if return_std and return_cov:
             raise RuntimeError("At most one of return_std or return_cov can be requested.")
         if return_cov:
-            Xq = np.array(Xq, dtype=np.float64, ndmin=2)
-            if not np.isfinite(Xq).all():
-                raise ValueError("Input X contains NaN or infinity.")
-            return self._predict_cov(Xq)
+            return self._predict_cov(check_queries(Xq))
         Xq = np.atleast_2d(np.asarray(Xq, dtype=np.float64))
         if 1 <= Xq.shape[0] <= self.SERVE_MAX_M:
             out = self.predict_host(Xq, return_std)

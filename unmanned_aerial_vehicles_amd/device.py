@@ -25,9 +25,15 @@ _backends = {}
 _backends_lock = threading.Lock()
 
 
+_torch_module = None
+
+
 def _torch():
-    import torch
-    return torch
+    global _torch_module
+    if _torch_module is None:      # (imported on first use, then kept: an `import` statement per call costs at the control rate)
+        import torch
+        _torch_module = torch
+    return _torch_module
 
 
 class Backend:
@@ -56,9 +62,10 @@ class Backend:
         self.low_seen = 0
 
     def bind_stream(self):
-        torch = _torch()
-        s = torch.cuda.current_stream(self.device).cuda_stream
-        self.check(self.lib.gpk_set_stream(self.h, C.c_void_p(s)))
+        # (runs in front of every call: the stream's address goes in as the integer it is, and `check` is entered on failure only)
+        rc = self.lib.gpk_set_stream(self.h, _torch().cuda.current_stream(self.device).cuda_stream)
+        if rc:
+            self.check(rc)
 
     def check(self, rc):
         if rc == _lib.GPK_OK:
@@ -67,6 +74,31 @@ class Backend:
         if rc == _lib.GPK_NOT_PD:
             raise NotPositiveDefinite(msg)
         raise GPKError(rc, msg)
+
+    def status(self, name, *args):
+        """`call` for the few sites where a status is a result (GPK_NOT_PD of a trial factorisation): returns the code
+        unchecked."""
+        with self.lock:
+            self.bind_stream()
+            return getattr(self.lib, name)(self.h, *args)
+
+    def call(self, name, *args):
+        """The one way into libgpk: `name(handle, *args)` under the handle's lock, on torch's current stream, the status
+        checked (NotPositiveDefinite / GPKError with the library's message).  The lock is re-entrant: a sequence of calls that
+        must not interleave with another thread's - a panel loop, a batched chain, a call plus the Python state that goes
+        with it - sits in its own `with be.lock:` and uses `call` inside."""
+        with self.lock:
+            self.bind_stream()
+            rc = getattr(self.lib, name)(self.h, *args)
+            if rc:
+                self.check(rc)
+        return rc
+
+    def close(self):
+        """Destroys the handle (for the owner of a private backend); the backend is unusable afterwards."""
+        h, self.h = self.h, None
+        if h:
+            self.lib.gpk_destroy(h)
 
     def sync(self):
         self.check(self.lib.gpk_synchronize(self.h))
@@ -131,8 +163,24 @@ def padded(n):
     return (int(n) + 127) // 128 * 128
 
 
-def _p(t):
-    return C.c_void_p(t.data_ptr())
+_p, _hp = _lib.dev_ptr, _lib.host_ptr
+
+
+def _vec(v, n):
+    """A scalar or (n,) value as the contiguous float64 (n,) array the library reads: length-scales over the features,
+    y_mean / y_std over the outputs."""
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (n,)))
+
+
+def check_queries(X, width=None):
+    """The estimators' query validation: X as a contiguous float64 array of at least two dimensions, finite (scikit-learn's
+    message, _gpr.py:404-412 -> check_array) and - where the caller fixes it - (M, width)."""
+    X = np.array(X, dtype=np.float64, ndmin=2)
+    if not np.isfinite(X).all():
+        raise ValueError("Input X contains NaN or infinity.")
+    if width is not None and (X.ndim != 2 or X.shape[1] != width):
+        raise ValueError(f"queries must be (M, {width})")
+    return np.ascontiguousarray(X)
 
 
 class DeviceGP:
@@ -193,12 +241,8 @@ class DeviceGP:
     def gram(self, ls, sf2, diag_add):
         """K1: build the padded Gram matrix in HBM."""
         self._ensure_K()
-        ls = np.ascontiguousarray(np.broadcast_to(np.asarray(ls, dtype=np.float64), (self.D,)))
-        be = self.be
-        with be.lock:
-            be.bind_stream()
-            be.check(be.lib.gpk_gram(be.h, GPK_F64, _p(self.X), self.N, self.D, ls.ctypes.data_as(_lib._dp),
-                                     float(sf2), float(diag_add), _p(self.K), self.Np))
+        ls = _vec(ls, self.D)
+        self.be.call("gpk_gram", GPK_F64, _p(self.X), self.N, self.D, _hp(ls), float(sf2), float(diag_add), _p(self.K), self.Np)
         self.ls, self.sf2 = ls, float(sf2)
         self.factored = False
         self._f32 = None
@@ -206,11 +250,10 @@ class DeviceGP:
 
     def factorize(self, ls, sf2, diag_add):
         """K1 + K2: Gram build and in-place blocked Cholesky.  Raises NotPositiveDefinite."""
-        self.gram(ls, sf2, diag_add)
-        be = self.be
         info = C.c_int(0)
-        with be.lock:
-            be.check(be.lib.gpk_potrf(be.h, _p(self.K), self.Np, self.Np, _p(self.winv), C.byref(info)))
+        with self.be.lock:      # (Gram and factorisation as one sequence: no other thread's call on this handle in between)
+            self.gram(ls, sf2, diag_add)
+            self.be.call("gpk_potrf", _p(self.K), self.Np, self.Np, _p(self.winv), C.byref(info))
         self.factored = True
 
     def load_factor(self, L, ls, sf2):
@@ -221,11 +264,8 @@ class DeviceGP:
         Kh = torch.eye(self.Np, dtype=torch.float64)
         Kh[: self.N, : self.N] = torch.from_numpy(np.tril(L))
         self.K.copy_(Kh)
-        be = self.be
-        with be.lock:
-            be.bind_stream()
-            be.check(be.lib.gpk_leaf_inverses(be.h, _p(self.K), self.Np, self.Np, _p(self.winv)))
-        self.ls = np.ascontiguousarray(np.broadcast_to(np.asarray(ls, dtype=np.float64), (self.D,)))
+        self.be.call("gpk_leaf_inverses", _p(self.K), self.Np, self.Np, _p(self.winv))
+        self.ls = _vec(ls, self.D)
         self.sf2 = float(sf2)
         self.factored = True
         self._f32 = None
@@ -241,15 +281,9 @@ class DeviceGP:
             method = "inverse" if ("f64" in self._Winv or self.Np <= self.INVERSE_EAGER_NP) else "chain"
         if method == "inverse":
             W = self.inverse_factor(False)
-            with be.lock:
-                be.bind_stream()
-                be.check(be.lib.gpk_potrs_inv(be.h, _p(W), self.Np, self.Np, _p(self.Yn), self.N, self.P,
-                                              _p(self.alpha)))
+            be.call("gpk_potrs_inv", _p(W), self.Np, self.Np, _p(self.Yn), self.N, self.P, _p(self.alpha))
         else:
-            with be.lock:
-                be.bind_stream()
-                be.check(be.lib.gpk_potrs(be.h, _p(self.K), self.Np, self.Np, _p(self.winv), _p(self.Yn), self.N,
-                                          self.P, _p(self.alpha)))
+            be.call("gpk_potrs", _p(self.K), self.Np, self.Np, _p(self.winv), _p(self.Yn), self.N, self.P, _p(self.alpha))
         self._amp = self._alpha_sq = None
         if self._f32:
             self._f32.pop("alpha", None)       # the fp32 copy of alpha is stale; X / L copies stay valid
@@ -262,12 +296,8 @@ class DeviceGP:
 
     def lml_terms(self):
         """K6a: (sum log diag L, [y_p . alpha_p])."""
-        be = self.be
         out = np.zeros(1 + self.P)
-        with be.lock:
-            be.bind_stream()
-            be.check(be.lib.gpk_lml_terms(be.h, _p(self.K), self.N, self.Np, _p(self.Yn), _p(self.alpha), self.P,
-                                          out.ctypes.data_as(_lib._dp)))
+        self.be.call("gpk_lml_terms", _p(self.K), self.N, self.Np, _p(self.Yn), _p(self.alpha), self.P, _hp(out))
         return out[0], out[1:]
 
     def lml_grad(self, noise, logdet_weight=None):
@@ -290,12 +320,10 @@ class DeviceGP:
         if not ratio > 0.0:
             raise ValueError("logdet_weight must be positive")
         alpha = self.alpha if ratio == 1.0 else self.alpha * float(np.sqrt(ratio))
-        with be.lock:
-            be.bind_stream()
-            be.check(be.lib.gpk_wtw(be.h, _p(W), self.Np, self.Np, _p(self._Kinv), self.Np))
-            be.check(be.lib.gpk_lml_grad(be.h, _p(self.X), self.N, self.D, self.ls.ctypes.data_as(_lib._dp),
-                                         self.sf2, float(noise), _p(alpha), self.P, _p(self._Kinv), self.Np,
-                                         g.ctypes.data_as(_lib._dp)))
+        with be.lock:           # (K^-1 written, then read: one sequence)
+            be.call("gpk_wtw", _p(W), self.Np, self.Np, _p(self._Kinv), self.Np)
+            be.call("gpk_lml_grad", _p(self.X), self.N, self.D, _hp(self.ls), self.sf2, float(noise), _p(alpha), self.P,
+                    _p(self._Kinv), self.Np, _hp(g))
         return g if ratio == 1.0 else g / ratio
 
     def lml_eval(self, ls, sf2, diag_add, noise, eval_gradient=True):
@@ -307,7 +335,7 @@ class DeviceGP:
         if eval_gradient and self.D > 16:
             raise ValueError("analytic LML gradients support D <= 16")
         self._ensure_K()
-        ls = np.ascontiguousarray(np.broadcast_to(np.asarray(ls, dtype=np.float64), (self.D,)))
+        ls = _vec(ls, self.D)
         be = self.be
         self._f32 = None
         self._Winv = {}
@@ -323,13 +351,10 @@ class DeviceGP:
         g = np.zeros(self.D + 2) if eval_gradient else None
         info = C.c_int(0)
         with be.lock:
-            be.bind_stream()
             self.ls, self.sf2 = ls, float(sf2)
-            be.check(be.lib.gpk_lml_eval(
-                be.h, _p(self.X), self.N, self.D, ls.ctypes.data_as(_lib._dp), float(sf2), float(diag_add), float(noise),
-                _p(self.Yn), self.P, _p(self.K), self.Np, _p(self.winv), _p(W), _p(work), _p(self.alpha),
-                _p(self._Kinv) if want_kinv else None, terms.ctypes.data_as(_lib._dp),
-                g.ctypes.data_as(_lib._dp) if eval_gradient else None, C.byref(info)))
+            be.call("gpk_lml_eval", _p(self.X), self.N, self.D, _hp(ls), float(sf2), float(diag_add), float(noise),
+                    _p(self.Yn), self.P, _p(self.K), self.Np, _p(self.winv), _p(W), _p(work), _p(self.alpha),
+                    _p(self._Kinv) if want_kinv else None, _hp(terms), _hp(g), C.byref(info))
         self.factored = True
         self._Winv["f64"] = W
         self._amp = self._alpha_sq = None
@@ -366,10 +391,7 @@ class DeviceGP:
             be = self.be
             Lf = be.empty((self.Np, self.Np), torch.float32)
             wf = be.empty((self.Np, 128), torch.float32)
-            with be.lock:
-                be.bind_stream()
-                be.check(be.lib.gpk_factor_to_f32(be.h, _p(self.K), self.Np, self.Np, _p(self.winv), _p(Lf),
-                                                  self.Np, _p(wf)))
+            be.call("gpk_factor_to_f32", _p(self.K), self.Np, self.Np, _p(self.winv), _p(Lf), self.Np, _p(wf))
             c["L"], c["winv"] = Lf, wf
         return c
 
@@ -385,17 +407,12 @@ class DeviceGP:
 
     def timing(self, enable=True):
         """Event brackets around the dominant launches (gpk_timing); `kernel_times(tag)` reads them back."""
-        be = self.be
-        with be.lock:
-            be.bind_stream()
-            be.check(be.lib.gpk_timing(be.h, 1 if enable else 0))
+        self.be.call("gpk_timing", 1 if enable else 0)
 
     def kernel_times(self, tag, max_n=64):
-        be = self.be
         ms = np.zeros(max_n)
         n = C.c_int(0)
-        with be.lock:
-            be.check(be.lib.gpk_kernel_times(be.h, int(tag), ms.ctypes.data_as(_lib._dp), max_n, C.byref(n)))
+        self.be.call("gpk_kernel_times", int(tag), _hp(ms), max_n, C.byref(n))
         return ms[: n.value].copy()
 
     # the fp32 MFMA mean kernel expands |a - b|^2 = |a|^2 + |b|^2 - 2 a.b around the training mean; it is used
@@ -432,24 +449,15 @@ class DeviceGP:
             Xd, ad = c["X"], c["alpha"]
         else:
             Xd, ad = self.X, (self.alpha if _alpha is None else _alpha)     # (_alpha: fp64 weights other than alpha)
-        ym = np.ascontiguousarray(np.broadcast_to(np.asarray(y_mean, dtype=np.float64), (self.P,)))
-        ys = np.ascontiguousarray(np.broadcast_to(np.asarray(y_std, dtype=np.float64), (self.P,)))
+        ym, ys = _vec(y_mean, self.P), _vec(y_std, self.P)
         be = self.be
         ls_, sf2_ = (self.ls, self.sf2) if _kernel is None else (np.ascontiguousarray(_kernel[0]), float(_kernel[1]))
         if kernel == "mfma":
-            with be.lock:
-                be.bind_stream()
-                be.check(be.lib.gpk_predict_mean_mfma(be.h, _p(Xd), _p(ad), self.N, self.D, self.P,
-                                                      self.ls.ctypes.data_as(_lib._dp), self.sf2,
-                                                      self._xc.ctypes.data_as(_lib._dp), ym.ctypes.data_as(_lib._dp),
-                                                      ys.ctypes.data_as(_lib._dp), _p(q), M, _p(out)))
+            be.call("gpk_predict_mean_mfma", _p(Xd), _p(ad), self.N, self.D, self.P, _hp(self.ls), self.sf2, _hp(self._xc),
+                    _hp(ym), _hp(ys), _p(q), M, _p(out))
             return out
-        with be.lock:
-            be.bind_stream()
-            be.check(be.lib.gpk_predict_mean(be.h, GPK_F32 if f32 else GPK_F64, _p(Xd), _p(ad), self.N, self.D,
-                                             self.P, ls_.ctypes.data_as(_lib._dp), sf2_,
-                                             ym.ctypes.data_as(_lib._dp), ys.ctypes.data_as(_lib._dp), _p(q), M,
-                                             _p(out)))
+        be.call("gpk_predict_mean", GPK_F32 if f32 else GPK_F64, _p(Xd), _p(ad), self.N, self.D, self.P, _hp(ls_), sf2_,
+                _hp(ym), _hp(ys), _p(q), M, _p(out))
         return out
 
     # queries per call up to which predict() goes through the one-call host path (gpk_predict_host)
@@ -469,8 +477,7 @@ class DeviceGP:
         c = self._host_args
         if (c is None or c[0] is not self.X or c[1] is not self.alpha or c[2] is not self.ls or c[3] is not y_mean
                 or c[4] is not y_std):
-            ym = np.ascontiguousarray(np.broadcast_to(np.asarray(y_mean, dtype=np.float64), (self.P,)))
-            ys = np.ascontiguousarray(np.broadcast_to(np.asarray(y_std, dtype=np.float64), (self.P,)))
+            ym, ys = _vec(y_mean, self.P), _vec(y_std, self.P)
             c = self._host_args = (self.X, self.alpha, self.ls, y_mean, y_std, ym, ys, self.X.data_ptr(),
                                    self.alpha.data_ptr(), self.ls.ctypes.data, ym.ctypes.data, ys.ctypes.data)
         return c
@@ -479,23 +486,30 @@ class DeviceGP:
         """One C call per batch: host queries (M, D) float64 -> (mean (M, P), var (M,) or None) as NumPy arrays
         (mean un-normalised, var in normalised-target units); kss=None skips the variance."""
         assert self.factored or kss is None
-        Xq = np.ascontiguousarray(Xq, dtype=np.float64)
-        M = Xq.shape[0]
-        if Xq.ndim != 2 or Xq.shape[1] != self.D:
-            raise ValueError(f"queries must be (M, {self.D})")
+        Xq, M = self._host_queries(Xq)
         mean = np.empty((M, self.P))
         var = np.empty((M,)) if kss is not None else None
-        W = self.inverse_factor(False) if kss is not None else None
-        be = self.be
-        c = self._host_call_args(y_mean, y_std)
-        with be.lock:
-            be.bind_stream()
-            be.check(be.lib.gpk_predict_host(be.h, c[7], c[8], self.N, self.D, self.P, c[9], self.sf2, c[10], c[11],
-                                             W.data_ptr() if W is not None else None, self.Np, self.Np,
-                                             float(kss) if kss is not None else 0.0, float(floor),
-                                             Xq.ctypes.data, M, mean.ctypes.data,
-                                             var.ctypes.data if var is not None else None))
+        self._host_call("gpk_predict_host", y_mean, y_std, kss is not None, float(kss) if kss is not None else 0.0, float(floor),
+                        _hp(Xq), M, _hp(mean), _hp(var))
         return mean, var
+
+    # What the one-call serving entries (gpk_predict_host / _host_cov / _host_grad) share, in two steps so that a caller can
+    # size its outputs in between: the query check, and the call on the cached argument block.  They run at the control rate:
+    # no closure, no argument list built per call; the queries and the outputs, new arrays every call, go through `host_ptr`
+    # (void* parameters take its pointers), which is cheaper than numpy's `ctypes.data`.
+    def _host_queries(self, Xq):
+        """Host queries as a contiguous float64 (M, D) array, and M."""
+        Xq = np.ascontiguousarray(Xq, dtype=np.float64)
+        if Xq.ndim != 2 or Xq.shape[1] != self.D:
+            raise ValueError(f"queries must be (M, {self.D})")
+        return Xq, Xq.shape[0]
+
+    def _host_call(self, entry, y_mean, y_std, want_W, *tail):
+        """`entry(handle, model and target scaling from the cached block, W or NULL, Np, ldw, *tail)`: `tail` is what follows
+        in the entry's own order - its scalars, the queries' address, M, the outputs' addresses."""
+        W = self.inverse_factor(False).data_ptr() if want_W else None
+        c = self._host_call_args(y_mean, y_std)
+        self.be.call(entry, c[7], c[8], self.N, self.D, self.P, c[9], self.sf2, c[10], c[11], W, self.Np, self.Np, *tail)
 
     def inverse_factor(self, f32):
         """W = L^-1 (lower, by tiles) on the fp64 MFMA; kept as fp64 or as an fp32 copy.  One-off
@@ -511,17 +525,12 @@ class DeviceGP:
                 work = be.empty(((self.Np // 2 + 128) ** 2,), torch.float64)
                 # (the row-block maxima the fp16 x 2 split needs come out of the products' epilogue: no pass over W for them)
                 absmax = be.empty((self.Np // 128,), torch.float32)
-                with be.lock:
-                    be.bind_stream()
-                    be.check(be.lib.gpk_trtri_absmax(be.h, _p(self.K), self.Np, self.Np, _p(self.winv), _p(W), self.Np,
-                                                     _p(work), _p(absmax)))
+                be.call("gpk_trtri_absmax", _p(self.K), self.Np, self.Np, _p(self.winv), _p(W), self.Np, _p(work), _p(absmax))
                 self._Winv["absmax"] = absmax
                 del work
             if f32:
                 Wf = be.empty((self.Np, self.Np), torch.float32)
-                with be.lock:
-                    be.bind_stream()
-                    be.check(be.lib.gpk_tril_to_f32(be.h, _p(W), self.Np, self.Np, _p(Wf), self.Np))
+                be.call("gpk_tril_to_f32", _p(W), self.Np, self.Np, _p(Wf), self.Np)
                 self._Winv["f32"] = Wf
             else:
                 self._Winv["f64"] = W
@@ -536,9 +545,7 @@ class DeviceGP:
             Wf = self.inverse_factor(True)
             be = self.be
             W3 = be.empty((self.Np * self.Np * 6,), torch.uint8)
-            with be.lock:
-                be.bind_stream()
-                be.check(be.lib.gpk_split3(be.h, _p(Wf), self.Np, self.Np, self.Np, _p(W3)))
+            be.call("gpk_split3", _p(Wf), self.Np, self.Np, self.Np, _p(W3))
             self._Winv["split"] = W3
             if not had_f32:
                 self._Winv.pop("f32", None)      # the plain fp32 copy only served as the source of the split
@@ -553,19 +560,15 @@ class DeviceGP:
             scales = be.empty((self.Np // 128,), torch.float32)
             W2 = be.empty((self.Np * self.Np * 4,), torch.uint8)
             if "f32" in self._Winv:              # an fp32 copy already exists (another variance form made it): split that
-                with be.lock:
-                    be.bind_stream()
-                    be.check(be.lib.gpk_split2_rows(be.h, _p(self._Winv["f32"]), self.Np, self.Np, _p(scales), _p(W2)))
+                be.call("gpk_split2_rows", _p(self._Winv["f32"]), self.Np, self.Np, _p(scales), _p(W2))
             else:                                # straight from the fp64 inverse factor: no fp32 copy, bit-identical parts
                 W = self.inverse_factor(False)
                 absmax = self._Winv.pop("absmax", None)
-                with be.lock:
-                    be.bind_stream()
-                    if absmax is not None:       # gpk_trtri_absmax left the block maxima: one pass over W instead of two
-                        scales = absmax
-                        be.check(be.lib.gpk_split2_rows_f64_absmax(be.h, _p(W), self.Np, self.Np, _p(scales), _p(W2)))
-                    else:
-                        be.check(be.lib.gpk_split2_rows_f64(be.h, _p(W), self.Np, self.Np, _p(scales), _p(W2)))
+                if absmax is not None:           # gpk_trtri_absmax left the block maxima: one pass over W instead of two
+                    scales = absmax
+                    be.call("gpk_split2_rows_f64_absmax", _p(W), self.Np, self.Np, _p(scales), _p(W2))
+                else:
+                    be.call("gpk_split2_rows_f64", _p(W), self.Np, self.Np, _p(scales), _p(W2))
             self._Winv["split2"] = (W2, scales)
         return self._Winv["split2"]
 
@@ -728,36 +731,36 @@ class DeviceGP:
             Ld, wd = c["L"], c["winv"]
         else:
             Ld, wd = self.K, self.winv
-        panel = max(128, min(self.VAR_PANEL_MAX, (self.VAR_PANEL_BYTES // (self.Np * es)) // 128 * 128))
-        panel = min(panel, padded(M))
+        panel = self._panel_rows(self.Np * es, M)
         work = self.be.empty((self.Np * panel,), tdt) if method != "inverse_split2" else None     # (K* only ever exists split)
         work3 = (self.be.empty((self.Np * panel * (6 if method == "inverse_split" else 4),), torch.uint8)
                  if method in ("inverse_split", "inverse_split2") else None)
         var = self.be.empty((panel,), torch.float64)
         be = self.be
-        lsp = self.ls.ctypes.data_as(_lib._dp)
-        with be.lock:
-            be.bind_stream()
+        lsp = _hp(self.ls)
+        with be.lock:           # (the panels share `var` and the work buffers: one sequence)
             for m0 in range(0, M, panel):
                 m1 = min(M, m0 + panel)
                 if method == "inverse_split":
-                    be.check(be.lib.gpk_predict_var_inv_split(be.h, _p(Xd), self.N, self.D, lsp, self.sf2, _p(W3),
-                                                              self.Np, _p(q[m0:m1]), m1 - m0, float(kss), float(floor),
-                                                              _p(work), _p(work3), _p(var)))
+                    be.call("gpk_predict_var_inv_split", _p(Xd), self.N, self.D, lsp, self.sf2, _p(W3), self.Np, _p(q[m0:m1]),
+                            m1 - m0, float(kss), float(floor), _p(work), _p(work3), _p(var))
                 elif method == "inverse_split2":
-                    be.check(be.lib.gpk_predict_var_inv_split2(be.h, _p(Xd), self.N, self.D, lsp, self.sf2, _p(W2),
-                                                               _p(w_scales), self.Np, _p(q[m0:m1]), m1 - m0, float(kss),
-                                                               float(floor), _p(work3), _p(var)))
+                    be.call("gpk_predict_var_inv_split2", _p(Xd), self.N, self.D, lsp, self.sf2, _p(W2), _p(w_scales), self.Np,
+                            _p(q[m0:m1]), m1 - m0, float(kss), float(floor), _p(work3), _p(var))
                 elif method == "inverse":
-                    be.check(be.lib.gpk_predict_var_inv(be.h, code, _p(Xd), self.N, self.D, lsp, self.sf2, _p(Wd),
-                                                        self.Np, self.Np, _p(q[m0:m1]), m1 - m0, float(kss),
-                                                        float(floor), _p(work), _p(var)))
+                    be.call("gpk_predict_var_inv", code, _p(Xd), self.N, self.D, lsp, self.sf2, _p(Wd), self.Np, self.Np,
+                            _p(q[m0:m1]), m1 - m0, float(kss), float(floor), _p(work), _p(var))
                 else:
-                    be.check(be.lib.gpk_predict_var(be.h, code, _p(Xd), self.N, self.D, lsp, self.sf2, _p(Ld),
-                                                    self.Np, self.Np, _p(wd), _p(q[m0:m1]), m1 - m0, float(kss),
-                                                    float(floor), _p(work), _p(var)))
+                    be.call("gpk_predict_var", code, _p(Xd), self.N, self.D, lsp, self.sf2, _p(Ld), self.Np, self.Np, _p(wd),
+                            _p(q[m0:m1]), m1 - m0, float(kss), float(floor), _p(work), _p(var))
                 out[m0:m1].copy_(var[: m1 - m0])
         return out
+
+    def _panel_rows(self, bytes_per_query, M):
+        """Queries per panel of a variance-side call: whole 128-row tiles whose work buffers (`bytes_per_query` each) fit
+        VAR_PANEL_BYTES - at least one tile, at most VAR_PANEL_MAX rows - and no more than the batch of M needs."""
+        panel = max(128, min(self.VAR_PANEL_MAX, (self.VAR_PANEL_BYTES // bytes_per_query) // 128 * 128))
+        return min(panel, padded(M))
 
     # ---- posterior covariance (K7) ----------------------------------------------------------------------------------
     def cov_panel_check(self, M):
@@ -791,18 +794,14 @@ class DeviceGP:
         work = self.be.empty((self.Np * Mp,), torch.float64)
         cov = self.be.empty((Mp, Mp), torch.float64)
         be = self.be
-        lsp = self.ls.ctypes.data_as(_lib._dp)
+        lsp = _hp(self.ls)
         if method == "inverse":
             W = self.inverse_factor(False)
-            with be.lock:
-                be.bind_stream()
-                be.check(be.lib.gpk_predict_cov_inv(be.h, GPK_F64, _p(self.X), self.N, self.D, lsp, self.sf2, _p(W), self.Np,
-                                                    self.Np, _p(q), M, float(noise), _p(work), _p(cov), Mp))
+            be.call("gpk_predict_cov_inv", GPK_F64, _p(self.X), self.N, self.D, lsp, self.sf2, _p(W), self.Np, self.Np, _p(q), M,
+                    float(noise), _p(work), _p(cov), Mp)
         else:
-            with be.lock:
-                be.bind_stream()
-                be.check(be.lib.gpk_predict_cov(be.h, GPK_F64, _p(self.X), self.N, self.D, lsp, self.sf2, _p(self.K), self.Np,
-                                                self.Np, _p(self.winv), _p(q), M, float(noise), _p(work), _p(cov), Mp))
+            be.call("gpk_predict_cov", GPK_F64, _p(self.X), self.N, self.D, lsp, self.sf2, _p(self.K), self.Np, self.Np,
+                    _p(self.winv), _p(q), M, float(noise), _p(work), _p(cov), Mp)
         del work
         return cov[:M, :M]
 
@@ -810,32 +809,25 @@ class DeviceGP:
         """One C call (gpk_predict_host_cov) for batches where `host_path_ok(M, True)` holds: host queries (M, D) ->
         (mean (M, P) un-normalised, cov (M, M) in normalised-target units) as NumPy arrays.  Up to 32 queries two launches."""
         assert self.factored
-        Xq = np.ascontiguousarray(Xq, dtype=np.float64)
-        if Xq.ndim != 2 or Xq.shape[1] != self.D:
-            raise ValueError(f"queries must be (M, {self.D})")
-        M = Xq.shape[0]
-        mean = np.empty((M, self.P))
-        cov = np.empty((M, M))
-        W = self.inverse_factor(False)
-        be = self.be
-        c = self._host_call_args(y_mean, y_std)
-        with be.lock:
-            be.bind_stream()
-            be.check(be.lib.gpk_predict_host_cov(be.h, c[7], c[8], self.N, self.D, self.P, c[9], self.sf2, c[10], c[11],
-                                                 W.data_ptr(), self.Np, self.Np, float(noise), Xq.ctypes.data, M,
-                                                 mean.ctypes.data, cov.ctypes.data))
+        Xq, M = self._host_queries(Xq)
+        mean, cov = np.empty((M, self.P)), np.empty((M, M))
+        self._host_call("gpk_predict_host_cov", y_mean, y_std, True, float(noise), _hp(Xq), M, _hp(mean), _hp(cov))
         return mean, cov
 
     # ---- input gradients of the posterior (K8) ----------------------------------------------------------------------
+    def _refuse_replica(self):
+        if self.replica:
+            raise RuntimeError("a serving replica holds no fp64 inverse factor: variance gradients are computed on the rank "
+                               "that fitted the model (the mean Jacobian is served here: kss=None)")
+
     def predict_grad_dev(self, Xq, y_std, kss=None, floor=0.0):
         """K8 on device tensors: (dmean (M, P, D), var (M,) or None, dvar (M, D) or None), float64.  dmean is the Jacobian of
         the un-normalised mean (times y_std[p]); var / dvar - computed when `kss` is given - are in normalised-target units,
         var clipped at `floor` as `predict_var_dev` clips it, dvar the gradient of the unclipped expression.  Always the fp64
         kernels through the explicit inverse factor; a serving replica serves the mean Jacobian only."""
         torch = _torch()
-        if kss is not None and self.replica:
-            raise RuntimeError("a serving replica holds no fp64 inverse factor: variance gradients are computed on the rank "
-                               "that fitted the model (the mean Jacobian is served here: kss=None)")
+        if kss is not None:
+            self._refuse_replica()
         q = self._as_queries(Xq, torch.float64)
         dmean = self.predict_mean_grad_dev(q, y_std)
         if kss is None:
@@ -852,13 +844,8 @@ class DeviceGP:
         dmean = self.be.empty((M, self.P, self.D), torch.float64)
         if M == 0:
             return dmean
-        ys = np.ascontiguousarray(np.broadcast_to(np.asarray(y_std, dtype=np.float64), (self.P,)))
-        be = self.be
-        with be.lock:
-            be.bind_stream()
-            be.check(be.lib.gpk_predict_mean_grad(be.h, _p(self.X), _p(self.alpha), self.N, self.D, self.P,
-                                                  self.ls.ctypes.data_as(_lib._dp), self.sf2, ys.ctypes.data_as(_lib._dp),
-                                                  _p(q), M, _p(dmean)))
+        self.be.call("gpk_predict_mean_grad", _p(self.X), _p(self.alpha), self.N, self.D, self.P, _hp(self.ls), self.sf2,
+                     _hp(_vec(y_std, self.P)), _p(q), M, _p(dmean))
         return dmean
 
     def predict_var_grad_dev(self, Xq, kss, floor=0.0):
@@ -866,9 +853,7 @@ class DeviceGP:
         panels whose three Np x Mp work panels fit VAR_PANEL_BYTES, so there is no limit on M."""
         torch = _torch()
         assert self.factored
-        if self.replica:
-            raise RuntimeError("a serving replica holds no fp64 inverse factor: variance gradients are computed on the rank "
-                               "that fitted the model (the mean Jacobian is served here: kss=None)")
+        self._refuse_replica()
         q = self._as_queries(Xq, torch.float64)
         M = q.shape[0]
         var = self.be.empty((M,), torch.float64)
@@ -876,18 +861,15 @@ class DeviceGP:
         if M == 0:
             return var, dvar
         W = self.inverse_factor(False)
-        panel = max(128, min(self.VAR_PANEL_MAX, (self.VAR_PANEL_BYTES // (3 * self.Np * 8)) // 128 * 128))
-        panel = min(panel, padded(M))
+        panel = self._panel_rows(3 * self.Np * 8, M)
         work = self.be.empty((3 * self.Np * panel,), torch.float64)
         be = self.be
-        lsp = self.ls.ctypes.data_as(_lib._dp)
-        with be.lock:
-            be.bind_stream()
+        lsp = _hp(self.ls)
+        with be.lock:           # (the panels share the work buffer: one sequence)
             for m0 in range(0, M, panel):
                 m1 = min(M, m0 + panel)
-                be.check(be.lib.gpk_predict_var_grad_inv(be.h, _p(self.X), self.N, self.D, lsp, self.sf2, _p(W), self.Np,
-                                                         self.Np, _p(q[m0:m1]), m1 - m0, float(kss), float(floor),
-                                                         _p(work), _p(var[m0:m1]), _p(dvar[m0:m1])))
+                be.call("gpk_predict_var_grad_inv", _p(self.X), self.N, self.D, lsp, self.sf2, _p(W), self.Np, self.Np,
+                        _p(q[m0:m1]), m1 - m0, float(kss), float(floor), _p(work), _p(var[m0:m1]), _p(dvar[m0:m1]))
         del work
         return var, dvar
 
@@ -896,27 +878,14 @@ class DeviceGP:
         (M, D) -> (mean (M, P), var (M,) or None, dmean (M, P, D), dvar (M, D) or None) as NumPy arrays, units as
         `predict_grad_dev`.  Up to 32 queries: mean + Jacobian ONE launch, all four results three."""
         assert self.factored
-        Xq = np.ascontiguousarray(Xq, dtype=np.float64)
-        if Xq.ndim != 2 or Xq.shape[1] != self.D:
-            raise ValueError(f"queries must be (M, {self.D})")
-        if kss is not None and self.replica:
-            raise RuntimeError("a serving replica holds no fp64 inverse factor: variance gradients are computed on the rank "
-                               "that fitted the model (the mean Jacobian is served here: kss=None)")
-        M = Xq.shape[0]
-        mean = np.empty((M, self.P))
-        dmean = np.empty((M, self.P, self.D))
-        var = np.empty((M,)) if kss is not None else None
-        dvar = np.empty((M, self.D)) if kss is not None else None
-        W = self.inverse_factor(False) if kss is not None else None
-        be = self.be
-        c = self._host_call_args(y_mean, y_std)
-        with be.lock:
-            be.bind_stream()
-            be.check(be.lib.gpk_predict_host_grad(be.h, c[7], c[8], self.N, self.D, self.P, c[9], self.sf2, c[10], c[11],
-                                                  W.data_ptr() if W is not None else None, self.Np, self.Np,
-                                                  float(kss) if kss is not None else 0.0, float(floor), Xq.ctypes.data, M,
-                                                  mean.ctypes.data, var.ctypes.data if var is not None else None,
-                                                  dmean.ctypes.data, dvar.ctypes.data if dvar is not None else None))
+        Xq, M = self._host_queries(Xq)
+        want = kss is not None
+        if want:
+            self._refuse_replica()
+        mean, dmean = np.empty((M, self.P)), np.empty((M, self.P, self.D))
+        var, dvar = (np.empty((M,)), np.empty((M, self.D))) if want else (None, None)
+        self._host_call("gpk_predict_host_grad", y_mean, y_std, want, float(kss) if want else 0.0, float(floor), _hp(Xq),
+                        M, _hp(mean), _hp(var), _hp(dmean), _hp(dvar))
         return mean, var, dmean, dvar
 
     # ---- gated serving: the one place every fp32 surface (estimator, sharded predictor, package GP, per-axis models) goes
@@ -959,10 +928,15 @@ class DeviceGP:
             return mean, None
         var = self.predict_var_dev(q, kss, floor, pd, vm)
         if gated and pd == "float32" and q.shape[0]:
-            low = torch.nonzero(var < self.FP32_VAR_RECHECK_FRACTION * kss).ravel()
-            if low.numel():
-                var[low] = self.predict_var_dev(self._rows64(Xq, q, low), kss, floor, "float64", self._fp64_var_method())
+            self._recheck_low_variances(Xq, q, var, kss, floor)
         return mean, var
+
+    def _recheck_low_variances(self, Xq, q, var, kss, floor):
+        """The fp32 variance gate: the entries of `var` (fp32 launch, rows `q` of the caller's `Xq`) below
+        FP32_VAR_RECHECK_FRACTION of the prior's are overwritten by the fp64 launch's."""
+        low = _torch().nonzero(var < self.FP32_VAR_RECHECK_FRACTION * kss).ravel()
+        if low.numel():
+            var[low] = self.predict_var_dev(self._rows64(Xq, q, low), kss, floor, "float64", self._fp64_var_method())
 
     def predict_packed_dev(self, Xq, y_mean, y_std, kss, floor=0.0, dtype="float32", var_method="auto", gated=True,
                            mean_gate=None):
@@ -981,40 +955,31 @@ class DeviceGP:
         out = self.be.empty((M, 2 * self.P), torch.float64)
         if M == 0:
             return out
-        ym = np.ascontiguousarray(np.broadcast_to(np.asarray(y_mean, dtype=np.float64), (self.P,)))
-        ys = np.ascontiguousarray(np.broadcast_to(np.asarray(y_std, dtype=np.float64), (self.P,)))
+        ym, ys = _vec(y_mean, self.P), _vec(y_std, self.P)
         be = self.be
         if not (f32 and vm == "inverse_split2"):
             mean = self.predict_mean_dev(q, ym, ys, pd)
             var = self.predict_var_dev(q, kss, floor, pd, vm)
             if gated and f32:
-                low = torch.nonzero(var < self.FP32_VAR_RECHECK_FRACTION * kss).ravel()
-                if low.numel():
-                    var[low] = self.predict_var_dev(self._rows64(Xq, q, low), kss, floor, "float64", self._fp64_var_method())
-            with be.lock:
-                be.bind_stream()
-                be.check(be.lib.gpk_pack_mean_var(be.h, GPK_F32 if f32 else GPK_F64, _p(mean), _p(var), M, self.P,
-                                                  ys.ctypes.data_as(_lib._dp), _p(out)))
+                self._recheck_low_variances(Xq, q, var, kss, floor)
+            be.call("gpk_pack_mean_var", GPK_F32 if f32 else GPK_F64, _p(mean), _p(var), M, self.P, _hp(ys), _p(out))
             return out
         c = self._f32_data()
         W2, w_scales = self.split2_inverse_factor()
-        center = self._xc.ctypes.data_as(_lib._dp) if self.mean_kernel_choice() == "mfma" else None
-        panel = max(128, min(self.VAR_PANEL_MAX, (self.VAR_PANEL_BYTES // (self.Np * 4)) // 128 * 128))
-        panel = min(panel, padded(M))
+        center = _hp(self._xc) if self.mean_kernel_choice() == "mfma" else None
+        panel = self._panel_rows(self.Np * 4, M)
         work2 = be.empty((self.Np * panel * 4,), torch.uint8)
         mean_tmp = be.empty((panel * self.P,), torch.float32)
         thr = self.FP32_VAR_RECHECK_FRACTION * kss if gated else 0.0
         nlow = 0
-        with be.lock:
-            be.bind_stream()
+        with be.lock:           # (the panels and the counter's read-back: one sequence)
             try:
                 for m0 in range(0, M, panel):
                     m1 = min(M, m0 + panel)
-                    be.check(be.lib.gpk_predict_mean_var_split2(
-                        be.h, _p(c["X"]), _p(c["alpha"]), self.N, self.D, self.P, self.ls.ctypes.data_as(_lib._dp), self.sf2,
-                        center, ym.ctypes.data_as(_lib._dp), ys.ctypes.data_as(_lib._dp), _p(W2), _p(w_scales), self.Np,
-                        _p(q[m0:m1]), m1 - m0, float(kss), float(floor), _p(work2), _p(mean_tmp), float(thr),
-                        _p(be.low_count) if gated else None, _p(out[m0:m1])))
+                    be.call("gpk_predict_mean_var_split2", _p(c["X"]), _p(c["alpha"]), self.N, self.D, self.P, _hp(self.ls),
+                            self.sf2, center, _hp(ym), _hp(ys), _p(W2), _p(w_scales), self.Np, _p(q[m0:m1]), m1 - m0,
+                            float(kss), float(floor), _p(work2), _p(mean_tmp), float(thr),
+                            _p(be.low_count) if gated else None, _p(out[m0:m1]))
             finally:
                 if gated:                        # (a 4-byte read-back on every exit path: the running counter and its host
                     seen = int(be.low_count.item()) & 0xFFFFFFFF     #  mirror stay in step even when a panel failed)
@@ -1047,10 +1012,7 @@ def prior_cov(X, ls, sf2, noise, device=None):
     if not 1 <= D <= _lib.GPK_MAX_D:
         raise ValueError(f"D must be in [1, {_lib.GPK_MAX_D}]")
     Mp = padded(M)
-    ls = np.ascontiguousarray(np.broadcast_to(np.asarray(ls, dtype=np.float64), (D,)))
     q = be.upload(X)
     K = be.empty((Mp, Mp), torch.float64)
-    with be.lock:
-        be.bind_stream()
-        be.check(be.lib.gpk_gram(be.h, GPK_F64, _p(q), M, D, ls.ctypes.data_as(_lib._dp), float(sf2), float(noise), _p(K), Mp))
+    be.call("gpk_gram", GPK_F64, _p(q), M, D, _hp(_vec(ls, D)), float(sf2), float(noise), _p(K), Mp)
     return K[:M, :M].cpu().numpy()

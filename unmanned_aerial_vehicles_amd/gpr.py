@@ -21,7 +21,7 @@ import warnings
 import numpy as np
 import scipy.optimize
 
-from .device import DeviceGP, get_backend
+from .device import DeviceGP, check_queries, get_backend
 from .kernels import RBF, ConstantKernel, Kernel, KernelComponents, WhiteKernel  # noqa: F401
 from ._lib import NotPositiveDefinite
 
@@ -283,9 +283,7 @@ class GaussianProcessRegressor:
         takes at most VAR_PANEL_MAX queries and a V = L^-1 K*^T that fits VAR_PANEL_BYTES (ValueError otherwise)."""
         if return_std and return_cov:
             raise RuntimeError("At most one of return_std or return_cov can be requested.")
-        X = np.array(X, dtype=np.float64, ndmin=2)
-        if not np.isfinite(X).all():       # scikit-learn's input validation (_gpr.py:404-412 -> check_array)
-            raise ValueError("Input X contains NaN or infinity.")
+        X = check_queries(X)               # scikit-learn's input validation (_gpr.py:404-412 -> check_array)
         if not hasattr(self, "X_train_"):  # prior (unfitted) prediction, _gpr.py:416-440
             n_t = self.n_targets if self.n_targets is not None else 1
             kern = self.kernel if self.kernel is not None else (
@@ -378,9 +376,7 @@ class GaussianProcessRegressor:
         dvar / (2 std) (not returned: it is singular where std = 0).  Always computed by the fp64 kernels: a model with
         predict_dtype="float32" serves them, and the mean and variance that go with them, in fp64.  Same input validation as
         `predict`; an unfitted model returns the prior mean / variance and zero gradients."""
-        X = np.array(X, dtype=np.float64, ndmin=2)
-        if not np.isfinite(X).all():
-            raise ValueError("Input X contains NaN or infinity.")
+        X = check_queries(X)
         M, D = X.shape
         if not hasattr(self, "X_train_"):  # prior: constant mean and variance, zero gradients
             n_t = self.n_targets if self.n_targets is not None else 1

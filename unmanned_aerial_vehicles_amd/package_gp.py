@@ -43,9 +43,7 @@ class RBFKernel:
         self.device = device
 
     def _evaluate(self, X1, X2, want_q):
-        import ctypes as C
-
-        from . import _lib
+        from ._lib import dev_ptr as _p, host_ptr as _hp
         from .device import _torch
         torch = _torch()
         X1 = np.ascontiguousarray(np.atleast_2d(X1), dtype=np.float64)
@@ -60,14 +58,11 @@ class RBFKernel:
         be = get_backend(self.device)
         ls = np.full(D, float(self.length_scale))
         with be.lock:
-            be.bind_stream()
             a = be.upload(X1)
             b = a if X2 is X1 else be.upload(X2)
             K = be.empty((n1, n2), torch.float64)
             Q = be.empty((n1, n2), torch.float64) if want_q else None
-            be.check(be.lib.gpk_rbf_kernel_grad(be.h, C.c_void_p(a.data_ptr()), n1, C.c_void_p(b.data_ptr()), n2, D,
-                                                ls.ctypes.data_as(_lib._dp), float(self.signal_variance),
-                                                C.c_void_p(K.data_ptr()), C.c_void_p(Q.data_ptr()) if want_q else None, n2))
+            be.call("gpk_rbf_kernel_grad", _p(a), n1, _p(b), n2, D, _hp(ls), float(self.signal_variance), _p(K), _p(Q), n2)
             Kh = K.cpu().numpy()
             Qh = Q.cpu().numpy() if want_q else None
         return Kh, Qh

@@ -65,13 +65,12 @@ def sharded_gram(X, ls, sf2, diag_add, world_size=None, rank=None, backend=None,
     """This rank's row slab of K = sf2 exp(-d^2/2) + diag_add I (the Gram build shards by row blocks
     with no exchange).  X: (N, D) array or device tensor, identical on every rank.  Returns (slab tensor
     (nrows, Np), row0); an empty slab (ranks beyond the tile count) has zero rows.  `out`: a tensor to reuse."""
-    import ctypes as C
-
     import torch
     import torch.distributed as dist
 
     from . import _lib
-    from .device import get_backend
+    from ._lib import dev_ptr as _p, host_ptr as _hp
+    from .device import _vec, get_backend
     if world_size is None:
         on = dist.is_available() and dist.is_initialized()
         world_size, rank = (dist.get_world_size(), dist.get_rank()) if on else (1, 0)
@@ -83,20 +82,13 @@ def sharded_gram(X, ls, sf2, diag_add, world_size=None, rank=None, backend=None,
     Np = (N + 127) // 128 * 128
     row0, nrows = gram_slab_bounds(N, world_size, rank)
     slab = out if out is not None else be.empty((nrows, Np), tdt)
-    lsv = np.ascontiguousarray(np.broadcast_to(np.asarray(ls, dtype=np.float64), (D,)))
+    lsv = _vec(ls, D)
+    code = _lib.GPK_F64 if f64 else _lib.GPK_F32
     if world_size == 1:
         # one rank owns every row: the fused kernel (each symmetric tile computed once and written to both halves)
-        with be.lock:
-            be.bind_stream()
-            be.check(be.lib.gpk_gram(be.h, _lib.GPK_F64 if f64 else _lib.GPK_F32, C.c_void_p(Xd.data_ptr()), N, D,
-                                     lsv.ctypes.data_as(_lib._dp), float(sf2), float(diag_add),
-                                     C.c_void_p(slab.data_ptr()), Np))
+        be.call("gpk_gram", code, _p(Xd), N, D, _hp(lsv), float(sf2), float(diag_add), _p(slab), Np)
     elif nrows:
-        with be.lock:
-            be.bind_stream()
-            be.check(be.lib.gpk_gram_rows(be.h, _lib.GPK_F64 if f64 else _lib.GPK_F32, C.c_void_p(Xd.data_ptr()), N, D,
-                                          lsv.ctypes.data_as(_lib._dp), float(sf2), float(diag_add), row0, nrows,
-                                          C.c_void_p(slab.data_ptr()), Np))
+        be.call("gpk_gram_rows", code, _p(Xd), N, D, _hp(lsv), float(sf2), float(diag_add), row0, nrows, _p(slab), Np)
     return slab, row0
 
 

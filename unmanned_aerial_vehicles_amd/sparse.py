@@ -26,13 +26,9 @@ import copy
 import numpy as np
 
 from . import _lib
-from .device import Backend, get_backend
+from .device import Backend, check_queries, get_backend
 
-_dp = _lib._dp
-
-
-def _ptr(a):
-    return a.ctypes.data_as(_dp)
+_ptr = _lib.host_ptr
 
 
 def hyper_from_theta(kernel, theta):
@@ -147,16 +143,15 @@ class SparseGP:
         comp, ls = self._hyper()
         be = self._backend()
         Z = self.inducing_
-        with be.lock:
-            be.bind_stream()
+        with be.lock:            # (the call and the state it consumes: one step)
             st = self._state
             if st is None:
-                be.check(be.lib.gpk_sparse_begin(be.h, _ptr(Z), Z.shape[0], Z.shape[1], P, _ptr(ls), ls.size, comp.sf2,
-                                                 comp.noise or 0.0, self.alpha, self.jitter_uu, _ptr(self._ym), _ptr(self._ys)))
+                be.call("gpk_sparse_begin", _ptr(Z), Z.shape[0], Z.shape[1], P, _ptr(ls), ls.size, comp.sf2, comp.noise or 0.0,
+                        self.alpha, self.jitter_uu, _ptr(self._ym), _ptr(self._ys))
             else:
-                be.check(be.lib.gpk_sparse_import(be.h, _ptr(Z), Z.shape[0], Z.shape[1], P, _ptr(ls), ls.size, comp.sf2,
-                                                  comp.noise or 0.0, self.alpha, self.jitter_uu, _ptr(self._ym), _ptr(self._ys),
-                                                  _ptr(st["G"]), _ptr(st["g"]), _ptr(st["yy"]), int(st["n_rows"])))
+                be.call("gpk_sparse_import", _ptr(Z), Z.shape[0], Z.shape[1], P, _ptr(ls), ls.size, comp.sf2, comp.noise or 0.0,
+                        self.alpha, self.jitter_uu, _ptr(self._ym), _ptr(self._ys), _ptr(st["G"]), _ptr(st["g"]),
+                        _ptr(st["yy"]), int(st["n_rows"]))
                 self._state = None
         self._P, self._live, self._final, self._held = P, True, False, False
 
@@ -166,11 +161,8 @@ class SparseGP:
             P = self._P if self._P is not None else (1 if self.y_mean is None else self.y_mean.size)
             self._begin(P)
         if not self._final:
-            be = self._backend()
             info = C.c_int(0)
-            with be.lock:
-                be.bind_stream()
-                be.check(be.lib.gpk_sparse_finalize(be.h, C.byref(info)))      # GPK_NOT_PD raises LinAlgError
+            self._backend().call("gpk_sparse_finalize", C.byref(info))      # GPK_NOT_PD raises LinAlgError
             self._final = True
 
     # ------------------------------------------------------------------ rows
@@ -196,10 +188,7 @@ class SparseGP:
             raise ValueError(f"y must have {self._P} columns")
         if X.shape[0] == 0:
             return self
-        be = self._backend()
-        with be.lock:
-            be.bind_stream()
-            be.check(be.lib.gpk_sparse_update(be.h, _ptr(X), _ptr(y2), X.shape[0]))
+        self._backend().call("gpk_sparse_update", _ptr(X), _ptr(y2), X.shape[0])
         self._final, self._held = False, False
         return self
 
@@ -219,10 +208,7 @@ class SparseGP:
         self._live, self._final, self._P, self._state = False, False, None, None
         self._y_1d = y_1d
         self._begin(y2.shape[1])
-        be = self._backend()
-        with be.lock:
-            be.bind_stream()
-            be.check(be.lib.gpk_sparse_hold(be.h, _ptr(X), _ptr(y2), X.shape[0]))
+        self._backend().call("gpk_sparse_hold", _ptr(X), _ptr(y2), X.shape[0])
         self._held = True
         return self
 
@@ -252,15 +238,13 @@ class SparseGP:
         g = np.zeros(ls.size + 2)
         gZ = np.zeros(self.inducing_.shape) if eval_inducing_gradient else None
         be = self._backend()
-        with be.lock:
-            be.bind_stream()
+        with be.lock:            # (the evaluation and the Python state that follows it: one step)
             if Z is None and gZ is None:
-                rc = be.lib.gpk_sparse_eval(be.h, _ptr(ls), ls.size, comp.sf2, comp.noise or 0.0, C.byref(b),
-                                            _ptr(g) if eval_gradient else None, C.byref(info))
+                rc = be.status("gpk_sparse_eval", _ptr(ls), ls.size, comp.sf2, comp.noise or 0.0, C.byref(b),
+                               _ptr(g) if eval_gradient else None, C.byref(info))
             else:
-                rc = be.lib.gpk_sparse_eval_z(be.h, None if Z is None else _ptr(Z), _ptr(ls), ls.size, comp.sf2, comp.noise or 0.0,
-                                              C.byref(b), _ptr(g) if eval_gradient or gZ is not None else None,
-                                              None if gZ is None else _ptr(gZ), C.byref(info))
+                rc = be.status("gpk_sparse_eval_z", _ptr(Z), _ptr(ls), ls.size, comp.sf2, comp.noise or 0.0, C.byref(b),
+                               _ptr(g) if eval_gradient or gZ is not None else None, _ptr(gZ), C.byref(info))
             self.kernel_ = kern
             if Z is not None:
                 self.inducing_ = Z
@@ -306,11 +290,8 @@ class SparseGP:
         idx = np.full(m, -1, dtype=np.int64)
         trace, dmax = np.full(m, np.nan), np.full(m, np.nan)
         sel = C.c_int64(0)
-        be = self._backend()
-        with be.lock:
-            be.bind_stream()
-            be.check(be.lib.gpk_sparse_select(be.h, None if X is None else _ptr(X), n, m, float(min_var), float(tol),
-                                              idx.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(trace), _ptr(dmax), C.byref(sel)))
+        self._backend().call("gpk_sparse_select", _ptr(X), n, m, float(min_var), float(tol),
+                             idx.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(trace), _ptr(dmax), C.byref(sel))
         return idx[:sel.value].copy(), trace[:sel.value].copy()
 
     def _select_exactly(self, X, m, min_var=1e-10):
@@ -403,12 +384,7 @@ class SparseGP:
 
     # ------------------------------------------------------------------ predict
     def _queries(self, X):
-        X = np.array(X, dtype=np.float64, ndmin=2)
-        if not np.isfinite(X).all():
-            raise ValueError("Input X contains NaN or infinity.")
-        if X.ndim != 2 or X.shape[1] != self.n_features_in_:
-            raise ValueError(f"queries must be (M, {self.n_features_in_})")
-        return np.ascontiguousarray(X)
+        return check_queries(X, self.n_features_in_)
 
     @property
     def n_outputs_(self):
@@ -439,17 +415,11 @@ class SparseGP:
         if return_cov:
             cov = np.empty((P, M, M))
             if M > 0:
-                be = self._backend()
-                with be.lock:
-                    be.bind_stream()
-                    be.check(be.lib.gpk_sparse_predict_cov(be.h, _ptr(X), M, _ptr(mean), _ptr(cov)))
+                self._backend().call("gpk_sparse_predict_cov", _ptr(X), M, _ptr(mean), _ptr(cov))
             return (mean[:, 0], cov[0]) if squeeze else (mean, np.ascontiguousarray(np.moveaxis(cov, 0, -1)))
         var = np.empty((M, P)) if return_std else None
         if M > 0:
-            be = self._backend()
-            with be.lock:
-                be.bind_stream()
-                be.check(be.lib.gpk_sparse_predict(be.h, _ptr(X), M, _ptr(mean), _ptr(var) if return_std else None, 1))
+            self._backend().call("gpk_sparse_predict", _ptr(X), M, _ptr(mean), _ptr(var), 1)
         if not return_std:
             return mean[:, 0] if squeeze else mean
         std = np.sqrt(var)
@@ -475,11 +445,7 @@ class SparseGP:
         var = np.empty((M, P)) if return_var else None
         dvar = np.empty((M, P, D)) if return_var else None
         if M > 0:
-            be = self._backend()
-            with be.lock:
-                be.bind_stream()
-                be.check(be.lib.gpk_sparse_predict_grad(be.h, _ptr(X), M, _ptr(mean), _ptr(var) if return_var else None, _ptr(dmean),
-                                                        _ptr(dvar) if return_var else None, 1))
+            self._backend().call("gpk_sparse_predict_grad", _ptr(X), M, _ptr(mean), _ptr(var), _ptr(dmean), _ptr(dvar), 1)
         if P == 1 and self._y_1d:
             mean, dmean = mean[:, 0], dmean[:, 0]
             if return_var:
@@ -503,10 +469,8 @@ class SparseGP:
         """The collapsed lower bound on the log-marginal likelihood of the rows seen so far, in normalised-target units (the
         exact log-marginal likelihood when the inducing inputs are the training inputs)."""
         self._ensure()
-        be = self._backend()
         b, n = C.c_double(0.0), C.c_int64(0)
-        with be.lock:
-            be.check(be.lib.gpk_sparse_bound(be.h, C.byref(b), C.byref(n)))
+        self._backend().call("gpk_sparse_bound", C.byref(b), C.byref(n))
         return float(b.value)
 
     @property
@@ -515,11 +479,9 @@ class SparseGP:
             return int(self._state["n_rows"])
         if not self._live:
             return 0
-        be = self._backend()
         n = C.c_int64(0)
-        with be.lock:
-            be.check(be.lib.gpk_sparse_export(be.h, None, None, None, None, None, None, None, None, C.byref(n), None, None,
-                                              None, None))
+        self._backend().call("gpk_sparse_export", None, None, None, None, None, None, None, None, C.byref(n), None, None, None,
+                             None)
         return int(n.value)
 
     def statistics(self):
@@ -531,11 +493,8 @@ class SparseGP:
         m, P = self.inducing_.shape[0], self._P
         G, g, yy = np.empty((m, m)), np.empty((m, P)), np.empty(P)
         n = C.c_int64(0)
-        be = self._backend()
-        with be.lock:
-            be.bind_stream()
-            be.check(be.lib.gpk_sparse_export(be.h, None, None, None, None, None, _ptr(G), _ptr(g), _ptr(yy), C.byref(n), None,
-                                              None, None, None))
+        self._backend().call("gpk_sparse_export", None, None, None, None, None, _ptr(G), _ptr(g), _ptr(yy), C.byref(n), None, None,
+                             None, None)
         return {"G": G, "g": g, "yy": yy, "n_rows": int(n.value)}
 
     # ------------------------------------------------------------------ pickling: Z, the statistics, the hyper-parameters
@@ -552,9 +511,8 @@ class SparseGP:
 
     def __del__(self):
         be = self.__dict__.get("_be")
-        if be is not None and not isinstance(self.__dict__.get("device"), Backend) and be.h:
+        if be is not None and not isinstance(self.__dict__.get("device"), Backend):
             try:
-                be.lib.gpk_destroy(be.h)
+                be.close()
             except Exception:
                 pass
-            be.h = None

@@ -13,6 +13,7 @@ import ctypes as C
 
 import numpy as np
 
+from .device import check_queries
 from .gpr import cholesky_draws
 from .sparse import SparseGP, _ptr
 
@@ -78,12 +79,7 @@ class BatchedSparseGP:
 
     # ------------------------------------------------------------------ serving
     def _queries(self, X):
-        X = np.array(X, dtype=np.float64, ndmin=2)
-        if not np.isfinite(X).all():
-            raise ValueError("Input X contains NaN or infinity.")
-        if X.ndim != 2 or X.shape[1] != self.n_features_in_:
-            raise ValueError(f"queries must be (M, {self.n_features_in_})")
-        return np.ascontiguousarray(X)
+        return check_queries(X, self.n_features_in_)
 
     def _ensure(self):
         """Every model assembled (lazily, as `SparseGP.predict` does); returns the serving backend - the first model's - and
@@ -104,7 +100,6 @@ class BatchedSparseGP:
         with contextlib.ExitStack() as stack:
             for be in bes:      # list order: two batches over the same models take the locks in the same order
                 stack.enter_context(be.lock)
-            bes[0].bind_stream()
             yield bes[0], handles
 
     def predict(self, Xq, return_std=False, return_cov=False):
@@ -121,13 +116,12 @@ class BatchedSparseGP:
             cov = np.full((B, M, M), np.nan)
             if M > 0:
                 with self._serving() as (be, handles):
-                    be.check(be.lib.gpk_sparse_predict_multi_cov(be.h, B, handles, _ptr(X), M, _ptr(mean), _ptr(cov)))
+                    be.call("gpk_sparse_predict_multi_cov", B, handles, _ptr(X), M, _ptr(mean), _ptr(cov))
             return mean, np.ascontiguousarray(np.moveaxis(cov, 0, -1))
         var = np.full((M, B), np.nan) if return_std else None
         if M > 0:
             with self._serving() as (be, handles):
-                be.check(be.lib.gpk_sparse_predict_multi(be.h, B, handles, _ptr(X), M, _ptr(mean),
-                                                         _ptr(var) if return_std else None, 1))
+                be.call("gpk_sparse_predict_multi", B, handles, _ptr(X), M, _ptr(mean), _ptr(var), 1)
         return (mean, np.sqrt(var)) if return_std else mean
 
     def predict_jacobian(self, Xq, return_var=False):
@@ -141,9 +135,8 @@ class BatchedSparseGP:
         dvar = np.full((M, B, D), np.nan) if return_var else None
         if M > 0:
             with self._serving() as (be, handles):
-                be.check(be.lib.gpk_sparse_predict_multi_grad(be.h, B, handles, _ptr(X), M, _ptr(mean),
-                                                              _ptr(var) if return_var else None, _ptr(dmean),
-                                                              _ptr(dvar) if return_var else None, 1))
+                be.call("gpk_sparse_predict_multi_grad", B, handles, _ptr(X), M, _ptr(mean), _ptr(var), _ptr(dmean),
+                        _ptr(dvar), 1)
         return (mean, dmean, var, dvar) if return_var else (mean, dmean)
 
     def sample_y(self, Xq, n_samples=1, random_state=0):

@@ -290,71 +290,102 @@ class PreTrainedGP:
             self._fused_bg = False
             try:
                 names = [n for n in OUTPUT_NAMES if n in self.gp_models]
-                if 2 <= len(names) <= 8 and all(isinstance(self.gp_models[n], SparseGP) for n in names):
-                    sx0 = self.scalers_X[names[0]]
-                    ms = [self.gp_models[n] for n in names]
-                    if all(np.array_equal(self.scalers_X[n].mean_, sx0.mean_) and
-                           np.array_equal(self.scalers_X[n].scale_, sx0.scale_) for n in names) and all(
-                            m.n_outputs_ == 1 and m.inducing_.shape == ms[0].inducing_.shape for m in ms):
-                        from .sparse_batch import BatchedSparseGP
-                        self._fused_bg = (BatchedSparseGP(ms), names)
-                elif 2 <= len(names) <= 8:
-                    sx0 = self.scalers_X[names[0]]
-                    m0 = self.gp_models[names[0]]
-                    x0 = getattr(m0, "X_train_", None)
-                    same = x0 is not None and all(
-                        np.array_equal(self.scalers_X[n].mean_, sx0.mean_) and
-                        np.array_equal(self.scalers_X[n].scale_, sx0.scale_) and
-                        getattr(self.gp_models[n], "X_train_", np.empty(0)).shape == x0.shape and
-                        np.array_equal(self.gp_models[n].X_train_, x0) and
-                        getattr(self.gp_models[n], "_yn", np.empty((0, 0))).shape[1:] == (1,) for n in names)
-                    if same:
-                        from .batched import BatchedARDGP
-                        bg = BatchedARDGP(optimizer=None)
-                        bg.models = [self.gp_models[n] for n in names]
-                        self._fused_bg = (bg, names)
+                ms = [self.gp_models[n] for n in names]
+                if 2 <= len(names) <= 8 and self._one_input_scaler(names):
+                    if all(isinstance(m, SparseGP) for m in ms):
+                        if all(m.n_outputs_ == 1 and m.inducing_.shape == ms[0].inducing_.shape for m in ms):
+                            from .sparse_batch import BatchedSparseGP
+                            self._fused_bg = (BatchedSparseGP(ms), names)
+                    else:
+                        x0 = getattr(ms[0], "X_train_", None)
+                        if x0 is not None and all(
+                                getattr(m, "X_train_", np.empty(0)).shape == x0.shape and np.array_equal(m.X_train_, x0) and
+                                getattr(m, "_yn", np.empty((0, 0))).shape[1:] == (1,) for m in ms):
+                            from .batched import BatchedARDGP
+                            bg = BatchedARDGP(optimizer=None)
+                            bg.models = ms
+                            self._fused_bg = (bg, names)
             except Exception as e:  # noqa: BLE001 - never into the control loop: the per-model path below still serves
                 print(f"fused per-axis prediction unavailable: {e}")
         return self._fused_bg
 
-    def predict_residual_batch(self, X, return_std=True):
-        X = np.atleast_2d(np.asarray(X, dtype=np.float64))
-        if not self.is_loaded:
-            return np.zeros((len(X), 6)), np.ones((len(X), 6)) * 1e6
+    def _one_input_scaler(self, names):
+        sx0 = self.scalers_X[names[0]]
+        return all(np.array_equal(self.scalers_X[n].mean_, sx0.mean_) and np.array_equal(self.scalers_X[n].scale_, sx0.scale_)
+                   for n in names)
+
+    def _serve(self, X, fused_call, model_call, put, fallback):
+        """The skeleton of the three batch surfaces: the fused object (`_fused`) serves all its models in one call on the rows
+        scaled with their shared input scaler (`_serve_fused`); whatever that left - no fused object, a failed call, a
+        component `put` refused - is served model by model with the model's own scaler (`_serve_models`); a component whose
+        own call fails gets `fallback(i)`.  `fused_call(bg, Xs)` returns a tuple of arrays with the models along axis 1 (None:
+        not computed), `model_call(m, Xs)` the same tuple for one model; `put(i, name, sx, result)` undoes the scalers and
+        fills component i of the caller's arrays, or raises.  Failures are printed, never raised."""
+        done, _ = self._serve_fused(X, fused_call, put)
+        self._serve_models(X, model_call, put, fallback, done)
+
+    def _serve_fused(self, X, fused_call, put):
+        """The fused stage of `_serve`: (the names it filled, whether it failed part-way or altogether)."""
+        done = set()
         fused = self._fused()
         if fused:
-            # models written by `GPTrainer` share scaler and inputs: all of them in one call (<= 32 rows: one C call
-            # and two launches for means and stds, `gpk_predict_host_multi`; larger batches: one fused mean launch)
             bg, names = fused
             try:
-                out = bg.predict(self.scalers_X[names[0]].transform(X), return_std=return_std)
-                ms, ss = out if return_std else (out, None)
-                mean = np.zeros((len(X), 6))
-                std = np.full((len(X), 6), 1e6) if return_std else None
+                sx = self.scalers_X[names[0]]
+                out = fused_call(bg, sx.transform(X))
                 for j, n in enumerate(names):
-                    i = OUTPUT_NAMES.index(n)
-                    mean[:, i] = self.scalers_y[n].inverse_transform(ms[:, j].reshape(-1, 1)).ravel()
-                    if return_std:
-                        std[:, i] = np.abs(ss[:, j] * self.scalers_y[n].scale_[0])
-                return mean, std
-            except Exception as e:  # noqa: BLE001
+                    put(OUTPUT_NAMES.index(n), n, sx, tuple(None if o is None else o[:, j] for o in out))
+                    done.add(n)
+            except Exception as e:  # noqa: BLE001 - the per-model stage still serves
                 print(f"GP prediction failed: {e}")
-                if not return_std:
-                    return np.zeros((len(X), 6)), None
-        mean = np.zeros((len(X), 6))
-        std = np.full((len(X), 6), 1e6)
+                return done, True
+        return done, False
+
+    def _serve_models(self, X, model_call, put, fallback, done):
+        """The per-model stage of `_serve`, for every loaded model not in `done`."""
         for i, name in enumerate(OUTPUT_NAMES):
-            if name not in self.gp_models:
+            if name not in self.gp_models or name in done:
                 continue
             try:
-                Xs = self.scalers_X[name].transform(X)
-                m, s = self.gp_models[name].predict(Xs, return_std=True)
-                mean[:, i] = self.scalers_y[name].inverse_transform(m.reshape(-1, 1)).flatten()
-                std[:, i] = np.abs(s * self.scalers_y[name].scale_[0])
+                sx = self.scalers_X[name]
+                put(i, name, sx, model_call(self.gp_models[name], sx.transform(X)))
             except Exception as e:  # noqa: BLE001
                 print(f"GP prediction failed for {name}: {e}")
-                mean[:, i], std[:, i] = 0.0, 1e6
-        return mean, std
+                fallback(i)
+
+    def predict_residual_batch(self, X, return_std=True):
+        X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+        mean, std = np.zeros((len(X), 6)), np.full((len(X), 6), 1e6)
+        if not self.is_loaded:
+            return mean, std
+
+        def put(i, name, sx, result):
+            m, s = result
+            sy = self.scalers_y[name]
+            mean[:, i] = sy.inverse_transform(m.reshape(-1, 1)).ravel()
+            if s is not None:
+                std[:, i] = np.abs(s * sy.scale_[0])
+
+        def fallback(i):
+            mean[:, i], std[:, i] = 0.0, 1e6
+
+        # models written by `GPTrainer` share scaler and inputs: all of them in one call (<= 32 rows: one C call and two
+        # launches for means and stds, `gpk_predict_host_multi`; larger batches: one fused mean launch).  The models' own
+        # calls always compute the stds; they are handed back whenever no fused object stood in front of them.
+        def fused_call(bg, Xs):
+            out = bg.predict(Xs, return_std=return_std)
+            return out if return_std else (out, None)
+
+        done, failed = self._serve_fused(X, fused_call, put)
+        if failed:
+            # Special to this surface, kept as it has always behaved: a fused stage that fails keeps nothing of what it had
+            # filled, and without return_std the call ends here with zeros - the models' own calls are not tried.
+            mean[:], std[:] = 0.0, 1e6
+            if not return_std:
+                return mean, None
+            done = set()
+        self._serve_models(X, lambda m, Xs: m.predict(Xs, return_std=True), put, fallback, done)
+        return mean, (std if return_std or not self._fused() else None)
 
     # ---- input gradients: the first-order terms of the per-axis models in raw units ---------------------------------
     def predict_residual_jacobian_batch(self, X, return_std=False):
@@ -379,9 +410,9 @@ class PreTrainedGP:
             X, M = None, 1
         mean, J = np.zeros((M, 6)), np.zeros((M, 6, 10))
         std, dstd = np.full((M, 6), 1e6), np.zeros((M, 6, 10))
-        done = set()
 
-        def put(i, name, sx, mu, dmu, var, dvar):
+        def put(i, name, sx, result):
+            mu, dmu, var, dvar = (result + (None, None))[:4]
             sy = self.scalers_y[name]
             scale_y = float(np.ravel(sy.scale_)[0])
             m_i = sy.inverse_transform(np.asarray(mu, dtype=np.float64).reshape(-1, 1)).ravel()
@@ -400,31 +431,12 @@ class PreTrainedGP:
             if return_std:
                 std[:, i], dstd[:, i, :] = s_i, ds_i
 
+        def fallback(i):
+            mean[:, i], J[:, i], std[:, i], dstd[:, i] = 0.0, 0.0, 1e6, 0.0
+
         if X is not None and self.is_loaded and X.shape[1] == 10:
-            fused = self._fused()
-            if fused:
-                bg, names = fused
-                try:
-                    sx = self.scalers_X[names[0]]
-                    out = bg.predict_jacobian(sx.transform(X), return_var=return_std)
-                    mu, dmu = out[0], out[1]
-                    var, dvar = (out[2], out[3]) if return_std else (None, None)
-                    for j, n in enumerate(names):
-                        put(OUTPUT_NAMES.index(n), n, sx, mu[:, j], dmu[:, j], var[:, j] if return_std else None,
-                            dvar[:, j] if return_std else None)
-                        done.add(n)
-                except Exception as e:  # noqa: BLE001 - as predict_residual_batch: the per-model loop below still serves
-                    print(f"GP prediction failed: {e}")
-            for i, name in enumerate(OUTPUT_NAMES):
-                if name not in self.gp_models or name in done:
-                    continue
-                try:
-                    sx = self.scalers_X[name]
-                    out = self.gp_models[name].predict_jacobian(sx.transform(X), return_var=return_std)
-                    put(i, name, sx, out[0], out[1], out[2] if return_std else None, out[3] if return_std else None)
-                except Exception as e:  # noqa: BLE001
-                    print(f"GP prediction failed for {name}: {e}")
-                    mean[:, i], J[:, i], std[:, i], dstd[:, i] = 0.0, 0.0, 1e6, 0.0
+            self._serve(X, lambda bg, Xs: tuple(bg.predict_jacobian(Xs, return_var=return_std)),
+                        lambda m, Xs: tuple(m.predict_jacobian(Xs, return_var=return_std)), put, fallback)
         if return_std:
             return mean, J, std, dstd
         return mean, J
@@ -444,7 +456,8 @@ class PreTrainedGP:
         cov = np.repeat((self.FALLBACK_VAR * np.eye(M))[:, :, None], 6, axis=2)
         served = np.zeros(6, dtype=bool)
 
-        def put(i, name, mu, sig):
+        def put(i, name, sx, result):
+            mu, sig = result
             sy = self.scalers_y[name]
             m_i = sy.inverse_transform(np.asarray(mu, dtype=np.float64).reshape(-1, 1)).ravel()
             c_i = float(np.ravel(sy.scale_)[0]) ** 2 * np.asarray(sig, dtype=np.float64).reshape(M, M)
@@ -452,25 +465,15 @@ class PreTrainedGP:
                 raise FloatingPointError("non-finite mean or covariance")
             mean[:, i], cov[:, :, i], served[i] = m_i, c_i, True
 
+        def fallback(i):
+            mean[:, i], cov[:, :, i], served[i] = 0.0, self.FALLBACK_VAR * np.eye(M), False
+
+        def fused_call(bg, Xs):     # (cov (M, M, B): the models along axis 1 for `_serve`)
+            mu, sig = bg.predict(Xs, return_cov=True)
+            return mu, np.moveaxis(sig, 2, 1)
+
         if X is not None and self.is_loaded:
-            fused = self._fused()
-            if fused:
-                bg, names = fused
-                try:
-                    mu, sig = bg.predict(self.scalers_X[names[0]].transform(X), return_cov=True)
-                    for j, n in enumerate(names):
-                        put(OUTPUT_NAMES.index(n), n, mu[:, j], sig[:, :, j])
-                except Exception as e:  # noqa: BLE001 - the per-model loop below still serves
-                    print(f"GP prediction failed: {e}")
-            for i, name in enumerate(OUTPUT_NAMES):
-                if name not in self.gp_models or served[i]:
-                    continue
-                try:
-                    mu, sig = self.gp_models[name].predict(self.scalers_X[name].transform(X), return_cov=True)
-                    put(i, name, mu, sig)
-                except Exception as e:  # noqa: BLE001
-                    print(f"GP prediction failed for {name}: {e}")
-                    mean[:, i], cov[:, :, i], served[i] = 0.0, self.FALLBACK_VAR * np.eye(M), False
+            self._serve(X, fused_call, lambda m, Xs: m.predict(Xs, return_cov=True), put, fallback)
         return mean, cov, served
 
     def predict_residual_cov_batch(self, X):
