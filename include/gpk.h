@@ -841,6 +841,55 @@ GPK_API int gpk_gemm_tiles(gpk_handle h, int dtype, int ta, int tb, const void* 
                    int64_t ldb, void* C, int64_t ldc, int64_t m, int64_t n, int64_t k, double alpha,
                    double beta, int lower_only);
 
+/* ---- K10: posterior function draws (pathwise conditioning) ----------------------------------------------------------
+ * A posterior draw of the exact model as an explicit function (Wilson et al. 2020, "Efficiently sampling functions from
+ * Gaussian process posteriors"), in normalised-target units:
+ *     f_s(x) = phi(x)^T w_s + k(x, X) v_s,   v_s = K^-1 (y_n - Phi w_s - eps_s),   K = k(X, X) + (noise + alpha) I,
+ *     phi_f(x) = sqrt(2 sf2 / F) cos(omega_f . x + phase_f),  omega_f ~ N(0, diag(1 / ls^2)),  phase_f ~ U(0, 2 pi),
+ *     w_s ~ N(0, I_F),  eps_s ~ N(0, (noise + alpha) I);  the only approximation is the finite F of the prior term.
+ * A path set for S paths and P outputs is ONE coefficient matrix Coef: (N + F) rows x C = S P columns, row-major, column
+ * s P + p, leading dimension ldc >= C, NO row padding: rows [0, N) hold v (the weights on k(x, x_j)), rows [N, N + F) hold
+ * sqrt(2 sf2 / F) w (the weights on cos(omega_f . x + phase_f)).  With it go Omega (dev, F x D), phase (dev, F) and the
+ * model's X (dev, N x D), ls (host, D), sf2, y_mean / y_std (host, P).  The value served is y_mean[p] + y_std[p] f_s(x).
+ * Limits of the family: 1 <= D <= GPK_MAX_D_PREDICT, 1 <= P <= GPK_MAX_P, 1 <= S <= 4096, 1 <= F <= 16384, N >= 1,
+ * 1 <= H <= 256 (GPK_BAD_ARG otherwise); fp64; not available in batched mode.  No reference counterpart (the reference
+ * evaluates marginal moments only, sklearn/gaussian_process/_gpr.py:367-496); scikit-learn's sample_y (:498-535) draws at a
+ * fixed batch and cannot follow a rollout whose next query depends on the last draw.
+ *
+ * gpk_rff_features: Phi[n][f] = scale cos(omega_f . x_n + phase_f) for n < N, f < F, zero elsewhere in the
+ *   (gpk_padded(N) x gpk_padded(F)) block that gpk_gemm_tiles takes; Phi dev, ldp >= gpk_padded(F).  Elementwise,
+ *   asynchronous.  Exported so that it can be tested alone.
+ * gpk_paths_prepare: the set-up (not the hot path).  W_rand (dev, F x C) = the w_s, Eps (dev, N x C) = the eps_s, column
+ *   s P + p both; Yn (dev, N x P) the normalised targets; W (dev, Np x ldw) the inverse factor L^-1 of K (gpk_trtri),
+ *   Np = gpk_padded(N).  R = Yn (x) 1_S - Phi W_rand - Eps, V = W^T (W R) - the tile GEMM, three launches - and Coef is
+ *   written as laid out above.  Work area: the handle's scratch ((Np Fp + Fp Cp + 2 Np Cp) doubles).  Asynchronous.
+ *   gpk_padded(N) + gpk_padded(F) <= 65535.
+ * gpk_paths_step: the hot path.  Xq (dev, S x D): path s is evaluated at ITS OWN row s,
+ *     out[s][p] = y_mean[p] + y_std[p] sum_{j < N + F} b_j(xq_s) Coef[j][s P + p]
+ *     b_j(x) = sf2 exp(-0.5 ||(x - x_j) / ls||^2) for j < N (exact differences),  cos(omega_{j-N} . x + phase_{j-N}) above;
+ *   out dev (S x P).  Two launches: a grid of (64-path blocks) x (row chunks) in which every coefficient row is read once, as
+ *   contiguous runs, and the basis value is formed once per (s, j); then the chunks' shares added in chunk order.  No
+ *   floating-point atomics; the chunk count depends on (N + F, S) only: the same bits every call.  Bound by streaming Coef,
+ *   (N + F) S P 8 bytes.  Work area: the handle's scratch.  Asynchronous.
+ * gpk_paths_rollout: a horizon in one call.  Host inputs x0 (x0_rows x P, x0_rows = S or 1: one start for every path),
+ *   U (H x (D - P); NULL if D == P), lin (P x D); the state dimension is P <= D.  Stage h, every path s:
+ *     q_s = [x_s, U[h]],   x_s <- x_s + lin q_s + out_s(q_s)
+ *   with the advance fused into the second launch of gpk_paths_step, so that the next stage's queries never leave the
+ *   device.  traj (host, (H + 1) x S x P) receives the trajectory, stage 0 = x0.  2 H launches, one synchronisation.
+ *   x0, U and lin must be finite (GPK_BAD_ARG: "NaN or infinity").                                                       */
+GPK_API int gpk_rff_features(gpk_handle h, const double* X, int64_t N, int D, const double* Omega, const double* phase,
+                             int64_t F, double scale, double* Phi, int64_t ldp);
+GPK_API int gpk_paths_prepare(gpk_handle h, const double* X, int64_t N, int D, const double* Yn, int P, const double* W,
+                              int64_t Np, int64_t ldw, const double* Omega, const double* phase, int64_t F, double sf2,
+                              const double* W_rand, const double* Eps, int S, double* Coef, int64_t ldc);
+GPK_API int gpk_paths_step(gpk_handle h, const double* X, int64_t N, int D, const double* ls, double sf2, const double* Omega,
+                           const double* phase, int64_t F, const double* Coef, int64_t ldc, int S, int P, const double* y_mean,
+                           const double* y_std, const double* Xq, double* out);
+GPK_API int gpk_paths_rollout(gpk_handle h, const double* X, int64_t N, int D, const double* ls, double sf2, const double* Omega,
+                              const double* phase, int64_t F, const double* Coef, int64_t ldc, int S, int P, const double* y_mean,
+                              const double* y_std, const double* x0, int x0_rows, const double* U, int H, const double* lin,
+                              double* traj);
+
 #ifdef __cplusplus
 }
 #endif

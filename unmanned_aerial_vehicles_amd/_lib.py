@@ -137,6 +137,11 @@ SIGNATURES = {
     "gpk_sparse_import": (_int, [_vp, _dp, _i64, _int, _int, _dp, _int, _dbl, _dbl, _dbl, _dbl, _dp, _dp, _dp, _dp, _dp, _i64]),
     "gpk_gemm_tiles": (_int, [_vp, _int, _int, _int, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _dbl,
                               _dbl, _int]),
+    "gpk_rff_features": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _i64, _dbl, _vp, _i64]),
+    "gpk_paths_prepare": (_int, [_vp, _vp, _i64, _int, _vp, _int, _vp, _i64, _i64, _vp, _vp, _i64, _dbl, _vp, _vp, _int, _vp, _i64]),
+    "gpk_paths_step": (_int, [_vp, _vp, _i64, _int, _dp, _dbl, _vp, _vp, _i64, _vp, _i64, _int, _int, _dp, _dp, _vp, _vp]),
+    "gpk_paths_rollout": (_int, [_vp, _vp, _i64, _int, _dp, _dbl, _vp, _vp, _i64, _vp, _i64, _int, _int, _dp, _dp, _dp, _int, _dp,
+                                 _int, _dp, _dp]),
 }
 
 _lib = None

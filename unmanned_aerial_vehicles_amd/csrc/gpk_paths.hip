@@ -1,0 +1,384 @@
+// K10: posterior function draws by pathwise conditioning (gfx950, fp64).
+//
+// A path set for S paths and P outputs is ONE coefficient matrix Coef ((N + F) x C, C = S P, column s P + p, row-major, no row
+// padding): rows [0, N) weight k(x, x_j), rows [N, N + F) weight cos(omega_f . x + phase_f) - the scale sqrt(2 sf2 / F) of the
+// random Fourier features is folded into those rows.  Path s at a point x, output p:
+//     out = y_mean[p] + y_std[p] sum_j b_j(x) Coef[j][s P + p]
+//
+//   rff_kernel            Phi[n][f] = scale cos(omega_f . x_n + phase_f) in the padded shape of the tile GEMM (zeros in the padding)
+//   paths_pack_kernel     R = Yn (x) 1_S - Eps and the padded copy of W_rand (the operands of the three products of gpk_paths_prepare)
+//   paths_unpack_kernel   Coef from V = K^-1 R and scale W_rand
+//   paths_partial_kernel  the hot path: grid (blocks of 64 paths) x (row chunks).  A workgroup is four waves; lane l of a wave owns
+//                         path 64 block + l while the basis value b_j(xq_s) is formed - once per (s, j), D fused multiply-adds and one
+//                         exp or cos - and leaves it in the wave's own LDS slots; then lane l owns COLUMNS l, l + 64, ... of the
+//                         block's 64 P columns, so every load of a coefficient row is one contiguous run of 64 doubles per wave and
+//                         the row is read exactly once.  The four waves take the chunk's rows four at a time (16 per round), their
+//                         sums meet in LDS in wave order, and the chunk's share goes to partial[chunk][column].
+//   paths_combine_kernel  the shares added in chunk order (no atomics: the same bits every call), un-normalised; in a rollout
+//                         also the advance x <- x + lin [x, u] + out, written as the next stage of the trajectory, which is where
+//                         the next stage's launch reads its queries.
+// The chunk count depends on (N + F, S) only.  The launch is bound by streaming Coef: (N + F) S P 8 bytes per stage.
+#include "gpk_internal.h"
+#include "gpk_math.h"
+
+namespace {
+
+constexpr int PB = 64;        // paths per workgroup: one per lane
+constexpr int PW = 4;         // waves per workgroup
+constexpr int PR = 4;         // rows per wave and round
+constexpr int PATHS_MAX_S = 4096, PATHS_MAX_F = 16384, PATHS_MAX_H = 256;
+constexpr int PATHS_TARGET_WGS = 512;   // two workgroups per CU
+constexpr int PATHS_MAX_CHUNKS = 512;
+
+struct PathsK {
+  double inv_ls[16];
+  double ymean[16], ystd[16];
+};
+
+__global__ __launch_bounds__(256) void rff_kernel(const double* __restrict__ X, long long N, int D,
+                                                  const double* __restrict__ Omega, const double* __restrict__ phase,
+                                                  long long F, double scale, double* __restrict__ Phi, long long Fp,
+                                                  long long ldp) {
+  const long long n = blockIdx.y;
+  const long long f = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (f >= Fp) return;
+  double v = 0.0;
+  if (n < N && f < F) {
+    double t = phase[f];
+    for (int d = 0; d < D; ++d) t = __builtin_fma(Omega[f * D + d], X[n * D + d], t);
+    v = scale * cos(t);
+  }
+  Phi[n * ldp + f] = v;
+}
+
+// R (Np x Cp) = Yn[n][c % P] - Eps[n][c], Wr (Fp x Cp) = W_rand[f][c]; zeros in the padding of both
+__global__ __launch_bounds__(256) void paths_pack_kernel(const double* __restrict__ Yn, const double* __restrict__ Eps,
+                                                         const double* __restrict__ Wrand, long long N, long long Np, long long F,
+                                                         long long C, long long Cp, int P, double* __restrict__ R,
+                                                         double* __restrict__ Wr) {
+  const long long row = blockIdx.y;      // [0, Np): R; [Np, Np + Fp): Wr
+  const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (c >= Cp) return;
+  if (row < Np) {
+    R[row * Cp + c] = (row < N && c < C) ? Yn[row * P + c % P] - Eps[row * C + c] : 0.0;
+  } else {
+    const long long f = row - Np;
+    Wr[f * Cp + c] = (f < F && c < C) ? Wrand[f * C + c] : 0.0;
+  }
+}
+
+__global__ __launch_bounds__(256) void paths_unpack_kernel(const double* __restrict__ V, const double* __restrict__ Wrand,
+                                                           long long N, long long F, long long C, long long Cp, double scale,
+                                                           double* __restrict__ Coef, long long ldc) {
+  const long long row = blockIdx.y;      // [0, N + F)
+  const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (c >= C) return;
+  Coef[row * ldc + c] = row < N ? V[row * Cp + c] : scale * Wrand[(row - N) * C + c];
+}
+
+// The query of path s: its first dx coordinates from xs (S x dx), the others - shared by all paths - from u (D - dx).
+template <int P>
+__global__ __launch_bounds__(256) void paths_partial_kernel(const double* __restrict__ X, int N, int D, double sf2,
+                                                            const double* __restrict__ Omega, const double* __restrict__ phase,
+                                                            int F, const double* __restrict__ Coef, long long ldc, int S,
+                                                            PathsK k, const double* __restrict__ xs, int dx,
+                                                            const double* __restrict__ u, int rows_per_chunk,
+                                                            double* __restrict__ partial) {
+  __shared__ double bs[PW][PR][PB];      // basis values: slot [w] is wave w's own
+  __shared__ double red[PW][P][PB];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int C = S * P, rows = N + F;
+  const int s = min((int)blockIdx.x * PB + lane, S - 1);      // (a lane past the last path repeats it: its columns are never stored)
+  const long long c0 = (long long)blockIdx.x * PB * P;
+  const int r0 = (int)blockIdx.y * rows_per_chunk, r1 = min(r0 + rows_per_chunk, rows);
+  double q[16];
+#pragma unroll
+  for (int d = 0; d < 16; ++d) q[d] = d < dx ? xs[(long long)s * dx + d] : (d < D ? u[d - dx] : 0.0);
+  double acc[P];
+#pragma unroll
+  for (int i = 0; i < P; ++i) acc[i] = 0.0;
+  // every wave runs the same number of rounds; a row past the chunk contributes an exact zero
+  for (int rb = r0; rb < r1; rb += PW * PR) {
+#pragma unroll
+    for (int r = 0; r < PR; ++r) {
+      const int j = rb + r * PW + w;       // wave-uniform
+      double b = 0.0;
+      if (j < r1) {
+        if (j < N) {
+          const double* xj = X + (long long)j * D;
+          double d2 = 0.0;
+#pragma unroll
+          for (int d = 0; d < 16; ++d)
+            if (d < D) {
+              const double t = (q[d] - xj[d]) * k.inv_ls[d];
+              d2 = __builtin_fma(t, t, d2);
+            }
+          b = sf2 * gpk_exp_neg(-0.5 * d2);
+        } else {
+          const double* om = Omega + (long long)(j - N) * D;
+          double t = phase[j - N];
+#pragma unroll
+          for (int d = 0; d < 16; ++d)
+            if (d < D) t = __builtin_fma(om[d], q[d], t);
+          b = cos(t);
+        }
+      }
+      bs[w][r][lane] = b;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();       // the slots are the wave's own: its LDS writes are in order before its reads
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    double cv[PR][P];
+#pragma unroll
+    for (int r = 0; r < PR; ++r) {
+      const int j = rb + r * PW + w;
+#pragma unroll
+      for (int i = 0; i < P; ++i) {
+        const long long c = c0 + lane + 64 * i;
+        cv[r][i] = (j < r1 && c < C) ? Coef[(long long)j * ldc + c] : 0.0;
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < PR; ++r)
+#pragma unroll
+      for (int i = 0; i < P; ++i) acc[i] = __builtin_fma(bs[w][r][(lane + 64 * i) / P], cv[r][i], acc[i]);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();       // ... and its reads before the next round's writes
+  }
+#pragma unroll
+  for (int i = 0; i < P; ++i) red[w][i][lane] = acc[i];
+  __syncthreads();
+  for (int e = tid; e < P * PB; e += 256) {
+    const int i = e >> 6, l = e & 63;
+    const long long c = c0 + l + 64 * i;
+    if (c < C) {
+      double t = red[0][i][l];
+#pragma unroll
+      for (int ww = 1; ww < PW; ++ww) t += red[ww][i][l];
+      partial[(long long)blockIdx.y * C + c] = t;
+    }
+  }
+}
+
+// out[c] = y_mean[p] + y_std[p] sum over the chunks, in chunk order.  With x_next: out is not stored; column c = s P + p of the
+// next stage is x[c] + lin[p] . [x_s, u] + that value (lin: P x D, row-major).
+__global__ __launch_bounds__(256) void paths_combine_kernel(const double* __restrict__ partial, int chunks, int S, int P, int D,
+                                                            PathsK k, double* __restrict__ out, const double* __restrict__ x,
+                                                            const double* __restrict__ u, const double* __restrict__ lin,
+                                                            double* __restrict__ x_next) {
+  const int C = S * P;
+  const int c = (int)blockIdx.x * 256 + threadIdx.x;
+  if (c >= C) return;
+  double t = 0.0;
+#pragma unroll 8
+  for (int ch = 0; ch < chunks; ++ch) t += partial[(long long)ch * C + c];
+  const int p = c % P, s = c / P;
+  const double v = __builtin_fma(k.ystd[p], t, k.ymean[p]);
+  if (!x_next) {
+    out[c] = v;
+    return;
+  }
+  double a = 0.0;
+  for (int d = 0; d < P; ++d) a = __builtin_fma(lin[p * D + d], x[(long long)s * P + d], a);
+  for (int d = P; d < D; ++d) a = __builtin_fma(lin[p * D + d], u[d - P], a);
+  x_next[c] = (x[c] + a) + v;
+}
+
+// rows per chunk and chunk count: a function of (N + F, S) only
+void paths_chunks(long long rows, int S, int* rows_per_chunk, int* chunks) {
+  const int pblocks = (S + PB - 1) / PB;
+  long long want = (PATHS_TARGET_WGS + pblocks - 1) / pblocks;
+  if (want > PATHS_MAX_CHUNKS) want = PATHS_MAX_CHUNKS;
+  const int round = PW * PR;
+  long long rpc = (rows + want - 1) / want;
+  rpc = (rpc + round - 1) / round * round;
+  *rows_per_chunk = (int)rpc;
+  *chunks = (int)((rows + rpc - 1) / rpc);
+}
+
+int paths_fill_k(gpk_handle h, int D, int P, const double* ls, const double* y_mean, const double* y_std, PathsK& k) {
+  GPK_REQUIRE(h, ls && y_mean && y_std, "paths: null length-scale or normalisation array");
+  for (int d = 0; d < 16; ++d) k.inv_ls[d] = 0.0;
+  for (int d = 0; d < D; ++d) {
+    GPK_REQUIRE(h, ls[d] > 0.0, "length-scales must be positive");
+    k.inv_ls[d] = 1.0 / ls[d];
+  }
+  for (int p = 0; p < 16; ++p) {
+    k.ymean[p] = p < P ? y_mean[p] : 0.0;
+    k.ystd[p] = p < P ? y_std[p] : 1.0;
+  }
+  return GPK_OK;
+}
+
+// the shape limits every entry of the family shares
+int paths_check_shape(gpk_handle h, int64_t N, int D, int64_t F, int S, int P, int64_t ldc) {
+  GPK_REQUIRE(h, h->batch == 1, "paths: not available in batched mode");
+  GPK_REQUIRE(h, N >= 1 && N < (1ll << 30), "paths: N must be at least 1");
+  GPK_REQUIRE(h, D >= 1 && D <= GPK_MAX_D_PREDICT, "paths: D must be in [1, 16]");
+  GPK_REQUIRE(h, P >= 1 && P <= GPK_MAX_P, "paths: P must be in [1, 16]");
+  GPK_REQUIRE(h, S >= 1 && S <= PATHS_MAX_S, "paths: S must be in [1, 4096]");
+  GPK_REQUIRE(h, F >= 1 && F <= PATHS_MAX_F, "paths: F must be in [1, 16384]");
+  GPK_REQUIRE(h, ldc >= (int64_t)S * P, "paths: ldc must be >= S * P");
+  return GPK_OK;
+}
+
+struct PathsModel {
+  const double* X;
+  int N, D;
+  double sf2;
+  const double* Omega;
+  const double* phase;
+  int F;
+  const double* Coef;
+  long long ldc;
+  int S, P;
+  PathsK k;
+};
+
+// one stage: the shares of every chunk, then their sum (out) or the advance (x_next)
+int paths_stage(gpk_handle h, const PathsModel& m, const double* xs, int dx, const double* u, int rpc, int chunks, double* partial,
+                double* out, const double* lin, double* x_next) {
+  const dim3 grid((unsigned)((m.S + PB - 1) / PB), (unsigned)chunks);
+#define GPK_PATHS(PP)                                                                                                          \
+  case PP:                                                                                                                     \
+    hipLaunchKernelGGL(paths_partial_kernel<PP>, grid, dim3(256), 0, h->stream, m.X, m.N, m.D, m.sf2, m.Omega, m.phase, m.F,   \
+                       m.Coef, m.ldc, m.S, m.k, xs, dx, u, rpc, partial);                                                      \
+    break
+  switch (m.P) {
+    GPK_PATHS(1); GPK_PATHS(2); GPK_PATHS(3); GPK_PATHS(4); GPK_PATHS(5); GPK_PATHS(6); GPK_PATHS(7); GPK_PATHS(8);
+    GPK_PATHS(9); GPK_PATHS(10); GPK_PATHS(11); GPK_PATHS(12); GPK_PATHS(13); GPK_PATHS(14); GPK_PATHS(15); GPK_PATHS(16);
+  }
+#undef GPK_PATHS
+  GPK_LAUNCH_CHECK(h);
+  const int C = m.S * m.P;
+  hipLaunchKernelGGL(paths_combine_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, h->stream, (const double*)partial,
+                     chunks, m.S, m.P, m.D, m.k, out, xs, u, lin, x_next);
+  GPK_LAUNCH_CHECK(h);
+  return GPK_OK;
+}
+
+bool all_finite(const double* a, long long n) {
+  for (long long i = 0; i < n; ++i)
+    if (!(a[i] - a[i] == 0.0)) return false;
+  return true;
+}
+
+}  // namespace
+
+extern "C" int gpk_rff_features(gpk_handle h, const double* X, int64_t N, int D, const double* Omega, const double* phase,
+                                int64_t F, double scale, double* Phi, int64_t ldp) {
+  if (!h) return GPK_BAD_ARG;
+  GPK_REQUIRE(h, X && Omega && phase && Phi, "rff_features: null pointer");
+  GPK_REQUIRE(h, N >= 1 && N < (1ll << 30), "rff_features: N must be at least 1");
+  GPK_REQUIRE(h, D >= 1 && D <= GPK_MAX_D_PREDICT, "rff_features: D must be in [1, 16]");
+  GPK_REQUIRE(h, F >= 1 && F <= PATHS_MAX_F, "rff_features: F must be in [1, 16384]");
+  const int64_t Np = gpk_padded(N), Fp = gpk_padded(F);
+  GPK_REQUIRE(h, ldp >= Fp, "rff_features: ldp must be >= gpk_padded(F)");
+  // (rows go in the grid's y dimension, 65535 at a time)
+  for (int64_t n0 = 0; n0 < Np; n0 += 65535) {
+    const int64_t nr = Np - n0 < 65535 ? Np - n0 : 65535;
+    hipLaunchKernelGGL(rff_kernel, dim3((unsigned)(Fp / 256 + (Fp % 256 != 0)), (unsigned)nr), dim3(256), 0, h->stream,
+                       X + n0 * D, (long long)(N - n0 > 0 ? N - n0 : 0), D, Omega, phase, (long long)F, scale, Phi + n0 * ldp,
+                       (long long)Fp, (long long)ldp);
+    GPK_LAUNCH_CHECK(h);
+  }
+  return GPK_OK;
+}
+
+extern "C" int gpk_paths_prepare(gpk_handle h, const double* X, int64_t N, int D, const double* Yn, int P, const double* W,
+                                 int64_t Np, int64_t ldw, const double* Omega, const double* phase, int64_t F, double sf2,
+                                 const double* W_rand, const double* Eps, int S, double* Coef, int64_t ldc) {
+  if (!h) return GPK_BAD_ARG;
+  GPK_REQUIRE(h, X && Yn && W && Omega && phase && W_rand && Eps && Coef, "paths_prepare: null pointer");
+  GPK_TRY(paths_check_shape(h, N, D, F, S, P, ldc));
+  GPK_REQUIRE(h, Np == gpk_padded(N) && ldw >= Np, "paths_prepare: Np must equal gpk_padded(N) and ldw >= Np");
+  GPK_REQUIRE(h, sf2 > 0.0, "paths_prepare: sf2 must be positive");
+  const int64_t C = (int64_t)S * P, Cp = gpk_padded(C), Fp = gpk_padded(F);
+  GPK_REQUIRE(h, Np + Fp <= 65535, "paths_prepare: gpk_padded(N) + gpk_padded(F) must not exceed 65535");
+  const double scale = sqrt(2.0 * sf2 / (double)F);
+  // work area: Phi (Np x Fp), Wr (Fp x Cp), R (Np x Cp), T (Np x Cp)
+  void* ws = nullptr;
+  GPK_TRY(gpk_scratch(h, (size_t)(Np * Fp + Fp * Cp + 2 * Np * Cp) * sizeof(double), &ws));
+  double* Phi = (double*)ws;
+  double* Wr = Phi + Np * Fp;
+  double* R = Wr + Fp * Cp;
+  double* T = R + Np * Cp;
+  GPK_TRY(gpk_rff_features(h, X, N, D, Omega, phase, F, scale, Phi, Fp));
+  hipLaunchKernelGGL(paths_pack_kernel, dim3((unsigned)(Cp / 256 + (Cp % 256 != 0)), (unsigned)(Np + Fp)), dim3(256), 0, h->stream,
+                     Yn, Eps, W_rand, (long long)N, (long long)Np, (long long)F, (long long)C, (long long)Cp, P, R, Wr);
+  GPK_LAUNCH_CHECK(h);
+  // R <- R - Phi Wr
+  GPK_TRY(gpk_gemm(h, GPK_F64, gemm_args(Phi, Fp, 0, Wr, Cp, 1, R, Cp, (int)Np, (int)Cp, (int)Fp, -1.0, 1.0)));
+  // V = K^-1 R = W^T (W R) through the inverse factor, as gpk_potrs_inv: T = W R (W lower: k < row-tile end), R <- W^T T
+  // (k >= row-tile start); the identity in W's padding keeps the zero rows of R zero
+  GemmArgs g1 = gemm_args(W, ldw, 0, R, Cp, 1, T, Cp, (int)Np, (int)Cp, (int)Np, 1.0, 0.0);
+  g1.ke0 = GPK_TILE; g1.ke_row = GPK_TILE; g1.heavy_first = 1;
+  GPK_TRY(gpk_gemm(h, GPK_F64, g1));
+  GemmArgs g2 = gemm_args(W, ldw, 1, T, Cp, 1, R, Cp, (int)Np, (int)Cp, (int)Np, 1.0, 0.0);
+  g2.kb_row = GPK_TILE;
+  GPK_TRY(gpk_gemm(h, GPK_F64, g2));
+  hipLaunchKernelGGL(paths_unpack_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)(N + F)), dim3(256), 0, h->stream,
+                     (const double*)R, W_rand, (long long)N, (long long)F, (long long)C, (long long)Cp, scale, Coef, (long long)ldc);
+  GPK_LAUNCH_CHECK(h);
+  return GPK_OK;
+}
+
+extern "C" int gpk_paths_step(gpk_handle h, const double* X, int64_t N, int D, const double* ls, double sf2, const double* Omega,
+                              const double* phase, int64_t F, const double* Coef, int64_t ldc, int S, int P, const double* y_mean,
+                              const double* y_std, const double* Xq, double* out) {
+  if (!h) return GPK_BAD_ARG;
+  GPK_REQUIRE(h, X && Omega && phase && Coef && Xq && out, "paths_step: null pointer");
+  GPK_TRY(paths_check_shape(h, N, D, F, S, P, ldc));
+  PathsModel m{X, (int)N, D, sf2, Omega, phase, (int)F, Coef, (long long)ldc, S, P, {}};
+  GPK_TRY(paths_fill_k(h, D, P, ls, y_mean, y_std, m.k));
+  int rpc = 0, chunks = 0;
+  paths_chunks(N + F, S, &rpc, &chunks);
+  void* ws = nullptr;
+  GPK_TRY(gpk_scratch(h, (size_t)chunks * S * P * sizeof(double), &ws));
+  return paths_stage(h, m, Xq, D, nullptr, rpc, chunks, (double*)ws, out, nullptr, nullptr);
+}
+
+extern "C" int gpk_paths_rollout(gpk_handle h, const double* X, int64_t N, int D, const double* ls, double sf2,
+                                 const double* Omega, const double* phase, int64_t F, const double* Coef, int64_t ldc, int S, int P,
+                                 const double* y_mean, const double* y_std, const double* x0, int x0_rows, const double* U, int H,
+                                 const double* lin, double* traj) {
+  if (!h) return GPK_BAD_ARG;
+  GPK_REQUIRE(h, X && Omega && phase && Coef && x0 && lin && traj, "paths_rollout: null pointer");
+  GPK_TRY(paths_check_shape(h, N, D, F, S, P, ldc));
+  GPK_REQUIRE(h, H >= 1 && H <= PATHS_MAX_H, "paths_rollout: H must be in [1, 256]");
+  GPK_REQUIRE(h, P <= D, "paths_rollout: the state dimension P must not exceed D");
+  GPK_REQUIRE(h, x0_rows == 1 || x0_rows == S, "paths_rollout: x0 must have 1 or S rows");
+  const int du = D - P;
+  GPK_REQUIRE(h, du == 0 || U, "paths_rollout: null controls");
+  GPK_REQUIRE(h, all_finite(x0, (long long)x0_rows * P) && all_finite(lin, (long long)P * D) &&
+                     (du == 0 || all_finite(U, (long long)H * du)),
+              "paths_rollout: x0, U and lin must not contain NaN or infinity");
+  PathsModel m{X, (int)N, D, sf2, Omega, phase, (int)F, Coef, (long long)ldc, S, P, {}};
+  GPK_TRY(paths_fill_k(h, D, P, ls, y_mean, y_std, m.k));
+  int rpc = 0, chunks = 0;
+  paths_chunks(N + F, S, &rpc, &chunks);
+  const size_t C = (size_t)S * P;
+  // device block: the trajectory ((H + 1) x S x P), then [stage 0 | U | lin] as they come from the host in one copy - stage 0
+  // is the trajectory's first slot - and the chunks' shares
+  const size_t n_traj = (size_t)(H + 1) * C, n_u = (size_t)H * du, n_lin = (size_t)P * D;
+  void* ws = nullptr;
+  GPK_TRY(gpk_scratch(h, (n_traj + n_u + n_lin + (size_t)chunks * C) * sizeof(double), &ws));
+  double* d_traj = (double*)ws;
+  double* d_u = d_traj + n_traj;
+  double* d_lin = d_u + n_u;
+  double* partial = d_lin + n_lin;
+  std::vector<double> stage(C + n_u + n_lin);
+  for (int s = 0; s < S; ++s) memcpy(stage.data() + (size_t)s * P, x0 + (x0_rows == 1 ? 0 : (size_t)s * P), sizeof(double) * P);
+  if (n_u) memcpy(stage.data() + C, U, sizeof(double) * n_u);
+  memcpy(stage.data() + C + n_u, lin, sizeof(double) * n_lin);
+  GPK_CHECK_HIP(h, hipMemcpyAsync(d_traj, stage.data(), sizeof(double) * C, hipMemcpyHostToDevice, h->stream));
+  GPK_CHECK_HIP(h, hipMemcpyAsync(d_u, stage.data() + C, sizeof(double) * (n_u + n_lin), hipMemcpyHostToDevice, h->stream));
+  for (int k = 0; k < H; ++k) {
+    const double* xk = d_traj + (size_t)k * C;
+    GPK_TRY(paths_stage(h, m, xk, P, d_u + (size_t)k * du, rpc, chunks, partial, nullptr, d_lin, d_traj + (size_t)(k + 1) * C));
+  }
+  GPK_CHECK_HIP(h, hipMemcpyAsync(traj, d_traj, sizeof(double) * n_traj, hipMemcpyDeviceToHost, h->stream));
+  GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
+  return GPK_OK;
+}

@@ -431,6 +431,21 @@ class GaussianProcessRegressor:
                      for t in range(y_mean.shape[1])]
         return np.hstack(y_samples)
 
+    def sample_paths(self, n_paths, n_features=1024, random_state=0):
+        """`n_paths` posterior function draws as explicit functions (pathwise conditioning, `paths.PosteriorPaths`): unlike
+        `sample_y`, whose draws live on one fixed batch, a path can be evaluated anywhere, call after call, and stays the same
+        function - what a sampled closed-loop rollout needs.  n_features: random Fourier features of the prior term (the only
+        approximation).  random_state as in `sample_y`; the draw order is `paths.draw_path_randomness`'s.  A fitted model
+        only (RuntimeError otherwise); scikit-learn has no such call."""
+        from .paths import PosteriorPaths, check_path_shape, draw_path_randomness
+        self._ensure_device()
+        dev = self._dev
+        check_path_shape(dev.D, dev.P, int(n_paths), int(n_features))
+        comp = self.kernel_.components()
+        r = draw_path_randomness(_rng_from(random_state), dev.N, dev.D, int(n_features), int(n_paths), dev.P,
+                                 comp.ls_vector(dev.D), (comp.noise or 0.0) + float(self.alpha))
+        return PosteriorPaths.from_randomness(self, **r)
+
     # ------------------------------------------------------------------ host views / persistence
     @property
     def alpha_(self):

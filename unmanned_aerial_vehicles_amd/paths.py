@@ -1,0 +1,208 @@
+"""Posterior function draws of the exact GP by pathwise conditioning, on MI355X.
+
+A posterior draw as an explicit function (Wilson et al. 2020), in normalised-target units:
+
+    f_s(x) = phi(x)^T w_s + k(x, X) v_s,    v_s = K^-1 (y_n - Phi w_s - eps_s),    K = k(X, X) + (noise + alpha) I
+    phi_f(x) = sqrt(2 sf2 / F) cos(omega_f . x + b_f),  omega_f ~ N(0, diag(1 / ls^2)),  b_f ~ U(0, 2 pi),
+    w_s ~ N(0, I_F),  eps_s ~ N(0, (noise + alpha) I)
+
+and the value served is y_mean + y_std f_s(x).  After the one-time set-up (`gpk_paths_prepare`: three tile GEMMs through the
+inverse factor the serving path already holds) every path is ONE column block of a coefficient matrix over N + F basis rows, so
+that S paths can each be evaluated at their own point - the state their own last draw produced - in one streaming pass
+(`gpk_paths_step`), and a whole closed-loop horizon in one call (`gpk_paths_rollout`).  A path stays the same function from
+call to call.  The only approximation is the finite F of the prior term.  fp64, one GPU, the exact model only; there is no CPU
+fallback.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _lib
+from .device import DeviceGP, _hp, _p, _torch, _vec, check_queries, padded
+
+MAX_PATHS, MAX_FEATURES, MAX_HORIZON = 4096, 16384, 256
+
+
+def draw_path_randomness(rng, N, D, F, S, P, ls, noise_plus_alpha):
+    """The random numbers of a path set, pure NumPy: dict(omega (F, D), phase (F,), weights (F, S, P), eps (N, S, P)).
+
+    Draw order, from `rng` (a `numpy.random.RandomState` or `Generator`):
+      1. z = rng.standard_normal((F, D));   omega = z / ls           (ls: scalar or (D,))
+      2. phase = rng.uniform(0, 2 pi, F)
+      3. weights = rng.standard_normal((F, S, P))
+      4. eps = sqrt(noise_plus_alpha) * rng.standard_normal((N, S, P))"""
+    N, D, F, S, P = (int(v) for v in (N, D, F, S, P))
+    if min(N, D, F, S, P) < 1:
+        raise ValueError("N, D, F, S and P must be at least 1")
+    if not noise_plus_alpha >= 0.0:
+        raise ValueError("noise_plus_alpha must be non-negative")
+    ls = _vec(ls, D)
+    omega = rng.standard_normal((F, D)) / ls
+    phase = rng.uniform(0.0, 2.0 * np.pi, F)
+    weights = rng.standard_normal((F, S, P))
+    eps = np.sqrt(float(noise_plus_alpha)) * rng.standard_normal((N, S, P))
+    return {"omega": omega, "phase": phase, "weights": weights, "eps": eps}
+
+
+def check_path_shape(D, P, S, F, H=None):
+    """The limits of the family (include/gpk.h, K10) as ValueErrors, before any launch."""
+    if not 1 <= D <= DeviceGP.MAX_FEATURES:
+        raise ValueError(f"D must be in [1, {DeviceGP.MAX_FEATURES}] (got {D})")
+    if not 1 <= P <= _lib.GPK_MAX_P:
+        raise ValueError(f"P must be in [1, {_lib.GPK_MAX_P}] (got {P})")
+    if not 1 <= S <= MAX_PATHS:
+        raise ValueError(f"the number of paths must be in [1, {MAX_PATHS}] (got {S})")
+    if not 1 <= F <= MAX_FEATURES:
+        raise ValueError(f"the number of features must be in [1, {MAX_FEATURES}] (got {F})")
+    if H is not None and not 1 <= H <= MAX_HORIZON:
+        raise ValueError(f"the horizon must be in [1, {MAX_HORIZON}] stages (got {H})")
+
+
+class PosteriorPaths:
+    """S posterior function draws of a fitted `GaussianProcessRegressor`, resident on its GPU.
+
+    paths(X)                    all paths at the same M points: (M, S), or (M, P, S) for P > 1 (`sample_y`'s convention)
+    paths.step(Xs)              Xs (S, D): path s at row s -> (S,) or (S, P); the hot path, two launches
+    paths.rollout(x0, U, lin)   a closed-loop horizon in one call -> (H + 1, S, P)
+    paths.randomness            dict(omega, phase, weights, eps) it was built from
+    paths.coef                  the device coefficient matrix (N + F, S P), column s P + p"""
+
+    def __init__(self):
+        raise TypeError("use GaussianProcessRegressor.sample_paths or PosteriorPaths.from_randomness")
+
+    @classmethod
+    def from_randomness(cls, gp, omega, phase, weights, eps):
+        """The path set of the fitted model `gp` from arrays of the caller's own: omega (F, D), phase (F,), weights (F, S, P)
+        (or (F, S) for one output) = the w_s, eps (N, S, P) (or (N, S)) = the eps_s, already scaled by sqrt(noise + alpha)."""
+        gp._ensure_device()
+        dev = gp._dev
+        if dev.replica:
+            raise RuntimeError("a serving replica holds no fp64 inverse factor: paths are drawn on the rank that fitted the model")
+        N, D, P = dev.N, dev.D, dev.P
+        omega = np.ascontiguousarray(omega, dtype=np.float64)
+        phase = np.ascontiguousarray(phase, dtype=np.float64)
+        weights = np.ascontiguousarray(weights, dtype=np.float64)
+        eps = np.ascontiguousarray(eps, dtype=np.float64)
+        if omega.ndim != 2 or omega.shape[1] != D:
+            raise ValueError(f"omega must be (F, {D})")
+        F = omega.shape[0]
+        if phase.shape != (F,):
+            raise ValueError(f"phase must be ({F},)")
+        if weights.ndim == 2 and P == 1:
+            weights = weights[:, :, None]
+        if eps.ndim == 2 and P == 1:
+            eps = eps[:, :, None]
+        if weights.ndim != 3 or weights.shape[0] != F or weights.shape[2] != P:
+            raise ValueError(f"weights must be ({F}, S, {P})")
+        S = weights.shape[1]
+        if eps.shape != (N, S, P):
+            raise ValueError(f"eps must be ({N}, {S}, {P})")
+        check_path_shape(D, P, S, F)
+        if padded(N) + padded(F) > 65535:
+            raise ValueError("gpk_padded(N) + gpk_padded(F) must not exceed 65535")
+        for name, a in (("omega", omega), ("phase", phase), ("weights", weights), ("eps", eps)):
+            if not np.isfinite(a).all():
+                raise ValueError(f"{name} contains NaN or infinity.")
+        self = object.__new__(cls)
+        torch = _torch()
+        be = dev.be
+        self.gp, self._dev, self.be = gp, dev, be
+        self.N, self.D, self.P, self.F, self.S = N, D, P, F, S
+        self.randomness = {"omega": omega, "phase": phase, "weights": weights, "eps": eps}
+        self._ls = np.ascontiguousarray(dev.ls, dtype=np.float64).copy()
+        self._sf2 = float(dev.sf2)
+        self._y_mean = _vec(gp._y_train_mean, P)
+        self._y_std = _vec(gp._y_train_std, P)
+        self._omega = be.upload(omega)
+        self._phase = be.upload(phase)
+        C = S * P
+        self.coef = be.empty((N + F, C), torch.float64)
+        with be.lock:
+            W = dev.inverse_factor(False)
+            w_d = be.upload(weights.reshape(F, C))
+            e_d = be.upload(eps.reshape(N, C))
+            be.call("gpk_paths_prepare", _p(dev.X), N, D, _p(dev.Yn), P, _p(W), dev.Np, dev.Np, _p(self._omega), _p(self._phase),
+                    F, self._sf2, _p(w_d), _p(e_d), S, _p(self.coef), C)
+            be.sync()       # (w_d and e_d are released here: the set-up is not the hot path)
+        return self
+
+    # ---- the model's side of every call: X, N, D, ls, sf2, Omega, phase, F, Coef, ldc, S, P, y_mean, y_std
+    def _model_args(self):
+        return (_p(self._dev.X), self.N, self.D, _hp(self._ls), self._sf2, _p(self._omega), _p(self._phase), self.F,
+                _p(self.coef), self.S * self.P, self.S, self.P, _hp(self._y_mean), _hp(self._y_std))
+
+    def _squeeze(self, a):
+        return a[..., 0] if self.P == 1 else a
+
+    def __call__(self, X):
+        """Every path at the same M points: (M, S), or (M, P, S) for P > 1.  Built from gpk_cross_gram_t, gpk_rff_features and
+        two gpk_gemm_tiles products; not a hot path."""
+        torch = _torch()
+        X = check_queries(X, self.D)
+        M = X.shape[0]
+        if M == 0:
+            return np.empty((0, self.S) if self.P == 1 else (0, self.P, self.S))
+        be, dev = self.be, self._dev
+        N, F, D, C = self.N, self.F, self.D, self.S * self.P
+        Np, Fp, Mp, Cp = dev.Np, padded(F), padded(M), padded(C)
+        q = be.upload(X)
+        # the two row blocks of Coef in the padded shape of the tile GEMM, zeros in the padding
+        cv = torch.zeros((Np, Cp), dtype=torch.float64, device=be.device)
+        cw = torch.zeros((Fp, Cp), dtype=torch.float64, device=be.device)
+        cv[:N, :C] = self.coef[:N]
+        cw[:F, :C] = self.coef[N:]
+        kt = be.empty((Np, Mp), torch.float64)
+        phi = be.empty((Mp, Fp), torch.float64)
+        out = be.empty((Mp, Cp), torch.float64)
+        with be.lock:
+            be.call("gpk_cross_gram_t", _lib.GPK_F64, _p(dev.X), N, _p(q), M, D, _hp(self._ls), self._sf2, _p(kt), Mp)
+            be.call("gpk_rff_features", _p(q), M, D, _p(self._omega), _p(self._phase), F, 1.0, _p(phi), Fp)
+            # out = K*^T V (kt is stored training-row major: ta = 1) + Phi(Xq) W~
+            be.call("gpk_gemm_tiles", _lib.GPK_F64, 1, 1, _p(kt), Mp, _p(cv), Cp, _p(out), Cp, Mp, Cp, Np, 1.0, 0.0, 0)
+            be.call("gpk_gemm_tiles", _lib.GPK_F64, 0, 1, _p(phi), Fp, _p(cw), Cp, _p(out), Cp, Mp, Cp, Fp, 1.0, 1.0, 0)
+        f = out[:M, :C].reshape(M, self.S, self.P).cpu().numpy()
+        f = self._y_mean + self._y_std * f
+        return f[:, :, 0] if self.P == 1 else np.ascontiguousarray(f.transpose(0, 2, 1))
+
+    def step(self, Xs):
+        """Path s at ITS OWN point Xs[s] (gpk_paths_step): Xs (S, D) -> (S,), or (S, P) for P > 1."""
+        torch = _torch()
+        Xs = check_queries(Xs, self.D)
+        if Xs.shape[0] != self.S:
+            raise ValueError(f"step takes one row per path: ({self.S}, {self.D})")
+        be = self.be
+        q = be.upload(Xs)
+        out = be.empty((self.S, self.P), torch.float64)
+        be.call("gpk_paths_step", *self._model_args(), _p(q), _p(out))
+        return self._squeeze(out.cpu().numpy())
+
+    def rollout(self, x0, U, lin):
+        """A closed-loop horizon in one call (gpk_paths_rollout).  The state has P coordinates - the model's outputs are its
+        residuals - and the query of path s at stage h is q_s = [x_s, U[h]]:
+
+            x_s <- x_s + lin q_s + path_s(q_s)
+
+        x0 (S, P), or (P,) as the start of every path; U (H, D - P); lin (P, D).  Returns the trajectory (H + 1, S, P), stage
+        0 = x0.  The next stage's queries never leave the device: 2 H launches, one synchronisation."""
+        P, D, S = self.P, self.D, self.S
+        if P > D:
+            raise ValueError(f"rollout needs a state of P = {P} <= D = {D} coordinates")
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        if x0.shape not in ((P,), (S, P)):
+            raise ValueError(f"x0 must be ({S}, {P}) or ({P},)")
+        U = np.ascontiguousarray(U, dtype=np.float64)
+        if U.ndim == 1 and D - P == 1:
+            U = U[:, None]
+        if U.ndim != 2 or U.shape[1] != D - P:
+            raise ValueError(f"U must be (H, {D - P})")
+        H = U.shape[0]
+        lin = np.ascontiguousarray(lin, dtype=np.float64)
+        if lin.shape != (P, D):
+            raise ValueError(f"lin must be ({P}, {D})")
+        check_path_shape(D, P, S, self.F, H)
+        if not (np.isfinite(x0).all() and np.isfinite(U).all() and np.isfinite(lin).all()):
+            raise ValueError("Input X contains NaN or infinity.")
+        traj = np.empty((H + 1, S, P))
+        self.be.call("gpk_paths_rollout", *self._model_args(), _hp(x0), 1 if x0.ndim == 1 else S,
+                     _hp(U) if D > P else None, H, _hp(lin), _hp(traj))
+        return traj

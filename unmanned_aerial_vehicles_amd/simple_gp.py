@@ -35,6 +35,12 @@ class SimpleQuadrotorGP:
         self.prediction_count = 0
         self.device = device
         self.predict_dtype = predict_dtype
+        self._paths = None          # sample_rollouts: (key, PosteriorPaths) of the current model
+
+    def __getstate__(self):
+        st = self.__dict__.copy()
+        st["_paths"] = None         # device buffers: drawn again on the first `sample_rollouts` after unpickling
+        return st
 
     # ---- data ---------------------------------------------------------------------------------
     def _to_numpy(self):
@@ -77,6 +83,7 @@ class SimpleQuadrotorGP:
         (simple_gp.py:156-185); failures leave the model untrained instead of raising."""
         if len(self.X_train) < 30:
             return
+        self._paths = None
         try:
             X = np.array(list(self.X_train))
             Y = np.array(list(self.Y_train))
@@ -95,6 +102,7 @@ class SimpleQuadrotorGP:
     def load_model(self, model_path):
         """Reads the `{'gp_model', 'training_count', ...}` pickle of train_gp_offline.py:188-194.
         A scikit-learn regressor inside it is ingested onto the GPU as is."""
+        self._paths = None
         try:
             if not os.path.exists(model_path):
                 print(f"Model file not found: {model_path}")
@@ -235,6 +243,43 @@ class SimpleQuadrotorGP:
         keep = np.sqrt(np.sum(var, axis=1)) < confidence_threshold
         out[keep] = mean[keep, :n_states]
         return out
+
+    def sample_rollouts(self, state, U_guess, dt, n_rollouts=64, n_features=1024, random_state=0):
+        """`n_rollouts` closed-loop rollouts under the model's own uncertainty: rollout r follows ONE posterior function draw
+        along the whole horizon, stage k + 1 evaluated at the state its sampled residual of stage k produced,
+
+            x_{k+1} = x_k + dt [v_k, a_k] + f_r([x_k, u_k])
+
+        in one call for the horizon (`PosteriorPaths.rollout`).  state (6,); U_guess (4, N).  Returns (R, 6, N + 1), the layout
+        `build_gp_residuals` / `linearize_gp_residuals` take as X_guess.  The path set (n_rollouts, n_features, random_state)
+        is drawn once and cached on the object until `train_gp` / `load_model`: the same functions from call to call.
+        Untrained, or on any failure (printed): the nominal trajectory repeated R times - it never raises into the control
+        loop."""
+        state = np.asarray(state, dtype=float).reshape(-1)[:6]
+        U_guess = np.asarray(U_guess, dtype=float)
+        R, N = int(n_rollouts), U_guess.shape[1]
+        nominal = np.empty((6, N + 1))
+        nominal[:, 0] = state
+        for k in range(N):
+            nominal[:, k + 1] = self._nominal_dynamics(nominal[:, k], U_guess[:, k], dt)
+        fallback = np.repeat(nominal[None], max(R, 0), axis=0)
+        if not self.is_trained:
+            return fallback
+        try:
+            key = (R, int(n_features), random_state if isinstance(random_state, (int, np.integer)) else id(random_state),
+                   id(self.gp_model))
+            cached = getattr(self, "_paths", None)      # (an object pickled before the attribute existed has none)
+            if cached is None or cached[0] != key:
+                self._paths = (key, self.gp_model.sample_paths(R, n_features, random_state))
+            lin = np.zeros((6, 10))
+            lin[0:3, 3:6] = dt * np.eye(3)       # the double integrator of `_nominal_dynamics`
+            lin[3:6, 6:9] = dt * np.eye(3)
+            traj = self._paths[1].rollout(state, np.ascontiguousarray(U_guess[:4].T), lin)      # (N + 1, R, 6)
+            self.prediction_count += R * N
+            return np.ascontiguousarray(traj.transpose(1, 2, 0))
+        except Exception as e:  # noqa: BLE001
+            print(f"GP rollout sampling failed: {e}")
+            return fallback
 
     def get_uncertainty(self, state, control):
         _, variance = self.predict_residual(state, control)
