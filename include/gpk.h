@@ -890,6 +890,43 @@ GPK_API int gpk_paths_rollout(gpk_handle h, const double* X, int64_t N, int D, c
                               const double* y_std, const double* x0, int x0_rows, const double* U, int H, const double* lin,
                               double* traj);
 
+/* ---- K10, the per-axis batch: B single-output models on shared inputs X, each with its own kernel ---------------------
+ * A batch path set for B models (1 <= B <= 8), S paths and F features is ONE coefficient matrix Coef: (N + F) rows x ldc
+ * columns, row-major, MODEL-MAJOR columns: model b, path s is column b mstride + s, mstride >= S, ldc >= B mstride (columns
+ * in the padding are never read or written).  Rows [0, N) hold v_b, rows [N, N + F) hold sqrt(2 sf2_b / F) w_b.  With it go
+ * Omega (dev, B x F x D), phase (dev, B x F), the shared X (dev, N x D) and per model ls (host, B x D), sf2 (host, B) and an
+ * output pair shift / scale (host, B): the value served is shift[b] + scale[b] f_{b,s}(x).  The set-up is B calls of
+ * gpk_paths_prepare with P = 1 on Coef + b mstride with the batch's ldc, each with that model's inverse factor, Omega_b,
+ * phase_b and sf2_b: no new device code, and model b's column block has the bits of its own single-model path set.
+ * Limits: those of the family above with 1 <= B <= 8 in the place of P; GPK_BAD_ARG with a message before any launch.
+ *
+ * gpk_paths_step_multi: the hot path.  Xq (dev, S x D): path s of EVERY model is evaluated at row s,
+ *     out[s][b] = shift[b] + scale[b] sum_{j < N + F} b_{j,b}(xq_s) Coef[j][b mstride + s]
+ *     b_{j,b}(x) = sf2_b exp(-0.5 ||(x - x_j) / ls_b||^2) for j < N,  cos(omega_{b,j-N} . x + phase_{b,j-N}) above;
+ *   out dev (S x B).  Two launches: a grid of (64-path blocks) x (row chunks) in which lane l owns path 64 block + l for the
+ *   basis values and the products alike, the difference x - x_j is formed once per (s, j) for all models and every
+ *   coefficient is read once, as B contiguous runs of 64 doubles per wave and row; then the chunks' shares added in chunk
+ *   order.  No floating-point atomics; the chunking is gpk_paths_step's, a function of (N + F, S) only, and so are the
+ *   summation order and the expression forms: column b of out has the BITS of gpk_paths_step on model b's own path set
+ *   (P = 1, y_mean = shift[b], y_std = scale[b]) at the same queries.  Work area: the handle's scratch.  Asynchronous.
+ * gpk_paths_rollout_multi: a horizon in one call, in RAW units.  Host inputs: nx (the state dimension, B <= nx <= D),
+ *   coord (B, distinct, in [0, nx)): the state coordinate model b's output is added to; in_shift / in_scale (D; both NULL:
+ *   identity): the input scaler the models were fitted behind; x0 (x0_rows x nx, x0_rows = S or 1), U (H x (D - nx); NULL
+ *   if D == nx), lin (nx x D).  Stage h, every path s:
+ *     q_s = [x_s, U[h]],   z_s = (q_s - in_shift) / in_scale,   x_s <- x_s + lin q_s + sum_b e_coord[b] out_b(z_s)
+ *   a coordinate without a model advances by lin alone.  The advance is fused into the second launch, which writes the
+ *   next stage of the trajectory where the next stage's first launch reads its queries.  traj (host, (H + 1) x S x nx),
+ *   stage 0 = x0.  2 H launches, one synchronisation.  x0, U, lin and the scaler must be finite, in_scale non-zero.     */
+GPK_API int gpk_paths_step_multi(gpk_handle h, const double* X, int64_t N, int D, int B, const double* ls, const double* sf2,
+                                 const double* Omega, const double* phase, int64_t F, const double* Coef, int64_t ldc,
+                                 int64_t mstride, int S, const double* shift, const double* scale, const double* Xq,
+                                 double* out);
+GPK_API int gpk_paths_rollout_multi(gpk_handle h, const double* X, int64_t N, int D, int B, const double* ls, const double* sf2,
+                                    const double* Omega, const double* phase, int64_t F, const double* Coef, int64_t ldc,
+                                    int64_t mstride, int S, const double* shift, const double* scale, int nx, const int* coord,
+                                    const double* in_shift, const double* in_scale, const double* x0, int x0_rows,
+                                    const double* U, int H, const double* lin, double* traj);
+
 #ifdef __cplusplus
 }
 #endif

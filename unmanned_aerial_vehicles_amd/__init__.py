@@ -10,6 +10,7 @@ kernels).  Public surface mirrors the reference's seams:
     SparseGP                                                      (inducing-point GP: every row, m points; sparse.py)
     BatchedSparseGP                                               (up to eight of them served in one call; sparse_batch.py)
     PosteriorPaths, draw_path_randomness                          (posterior function draws, sampled rollouts; paths.py)
+    BatchedPosteriorPaths, draw_batch_path_randomness             (the same for the per-axis batch, all models in one call)
     evaluate_gp, ShardedPredictor, sharded_gram
 """
 from .kernels import RBF, ConstantKernel, WhiteKernel  # noqa: F401
@@ -20,11 +21,11 @@ from .trainer import GPTrainer, PreTrainedGP  # noqa: F401
 from .batched import BatchedARDGP  # noqa: F401
 from .sparse import SparseGP  # noqa: F401
 from .sparse_batch import BatchedSparseGP  # noqa: F401
-from .paths import PosteriorPaths, draw_path_randomness  # noqa: F401
+from .paths import BatchedPosteriorPaths, PosteriorPaths, draw_batch_path_randomness, draw_path_randomness  # noqa: F401
 from .evaluate import evaluate_gp  # noqa: F401
 from .sharded import ShardedPredictor, gram_slab_bounds, shard_bounds, sharded_gram, sharded_predict  # noqa: F401
 
 __all__ = ["GaussianProcessRegressor", "RBF", "WhiteKernel", "ConstantKernel", "SimpleQuadrotorGP",
            "SimpleGPEnhancedMPC", "GaussianProcess", "GPTrainer", "PreTrainedGP", "evaluate_gp",
            "ShardedPredictor", "shard_bounds", "sharded_predict", "sharded_gram", "gram_slab_bounds", "BatchedARDGP", "SparseGP",
-           "BatchedSparseGP", "PosteriorPaths", "draw_path_randomness"]
+           "BatchedSparseGP", "PosteriorPaths", "draw_path_randomness", "BatchedPosteriorPaths", "draw_batch_path_randomness"]

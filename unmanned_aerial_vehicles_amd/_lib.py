@@ -142,6 +142,9 @@ SIGNATURES = {
     "gpk_paths_step": (_int, [_vp, _vp, _i64, _int, _dp, _dbl, _vp, _vp, _i64, _vp, _i64, _int, _int, _dp, _dp, _vp, _vp]),
     "gpk_paths_rollout": (_int, [_vp, _vp, _i64, _int, _dp, _dbl, _vp, _vp, _i64, _vp, _i64, _int, _int, _dp, _dp, _dp, _int, _dp,
                                  _int, _dp, _dp]),
+    "gpk_paths_step_multi": (_int, [_vp, _vp, _i64, _int, _int, _dp, _dp, _vp, _vp, _i64, _vp, _i64, _i64, _int, _dp, _dp, _vp, _vp]),
+    "gpk_paths_rollout_multi": (_int, [_vp, _vp, _i64, _int, _int, _dp, _dp, _vp, _vp, _i64, _vp, _i64, _i64, _int, _dp, _dp, _int,
+                                       C.POINTER(_int), _dp, _dp, _dp, _int, _dp, _int, _dp, _dp]),
 }
 
 _lib = None

@@ -528,6 +528,26 @@ class BatchedARDGP:
         mean, cov = self.predict(Xq, return_cov=True)
         return cholesky_draws(mean, cov, n_samples, random_state)
 
+    def sample_paths(self, n_paths, n_features=1024, random_state=0):
+        """`n_paths` posterior function draws of EVERY model as explicit functions (`paths.BatchedPosteriorPaths`): evaluated
+        anywhere, call after call, all models in one call - `step` two launches, a closed-loop `rollout` one call per horizon.
+        The draw order is `paths.draw_batch_path_randomness`'s (model by model from the one generator); random_state as in
+        `sample_y`.  Needs what the fused launches need - fitted single-output models of one size on one device and on the same
+        training inputs - at most 8 of them, D <= 16, and no serving replica: a ValueError / RuntimeError names what is missing."""
+        from .gpr import _rng_from
+        from .paths import BatchedPosteriorPaths, check_batch_path_shape, draw_batch_path_randomness
+        if not self.models:
+            raise RuntimeError("this BatchedARDGP is not fitted yet")
+        for m in self.models:
+            m._ensure_device()
+        d0 = self.models[0]._dev
+        check_batch_path_shape(len(self.models), d0.D, int(n_paths), int(n_features))
+        comps = [m.kernel_.components() for m in self.models]
+        r = draw_batch_path_randomness(_rng_from(random_state), d0.N, d0.D, int(n_features), int(n_paths),
+                                       np.stack([c.ls_vector(d0.D) for c in comps]),
+                                       [(c.noise or 0.0) + float(m.alpha) for c, m in zip(comps, self.models)])
+        return BatchedPosteriorPaths.from_randomness(self, **r)
+
     def predict(self, Xq, return_std=False, return_cov=False):
         """Means (M, B); with return_std the standard deviations (M, B); with return_cov=True every model's joint posterior
         covariance over the rows, (mean (M, B), cov (M, M, B)) in target units as scikit-learn scales it

@@ -17,6 +17,9 @@
 //   paths_combine_kernel  the shares added in chunk order (no atomics: the same bits every call), un-normalised; in a rollout
 //                         also the advance x <- x + lin [x, u] + out, written as the next stage of the trajectory, which is where
 //                         the next stage's launch reads its queries.
+//   paths_partial_multi_kernel / paths_combine_multi_kernel / paths_advance_multi_kernel
+//                         the same two launches for the per-axis batch: B single-output models on shared inputs, each with its own
+//                         kernel, Coef model-major (see there)
 // The chunk count depends on (N + F, S) only.  The launch is bound by streaming Coef: (N + F) S P 8 bytes per stage.
 #include "gpk_internal.h"
 #include "gpk_math.h"
@@ -264,6 +267,211 @@ bool all_finite(const double* a, long long n) {
   return true;
 }
 
+// ---- the per-axis batch: B single-output models on shared inputs, each with its own kernel -------------------------------------
+// Coef is model-major: model b, path s is column b mstride + s, so lane l of a wave owns path 64 block + l for the basis value AND
+// for the product - no LDS between the two - and a wave's load of a coefficient row is B contiguous runs of 64 doubles.  The
+// difference q_d - x_jd and the load of x_j are formed once per (s, j) for all B models; everything after that is the
+// single-model kernel's arithmetic in the single-model kernel's order (chunking, rows rb + r PW + w with r ascending, waves in
+// wave order, chunks in chunk order), so column b of the result has the bits of gpk_paths_step on model b's own path set.
+constexpr int PATHS_MAX_B = 8;
+
+struct PathsMultiK {
+  double inv_ls[PATHS_MAX_B][16];
+  double sf2[PATHS_MAX_B], shift[PATHS_MAX_B], scale[PATHS_MAX_B];
+  double in_shift[16], in_scale[16];      // rollout: the shared input scaler, z = (q - in_shift) / in_scale
+  int scaled;                             // 0: the queries are taken as they are
+  int model_of[16];                       // rollout: the model whose output state coordinate i receives, -1: none
+};
+
+// partial[(chunk B + b) S + s]: the share of the chunk's rows in model b's sum for path s
+template <int B>
+__global__ __launch_bounds__(256) void paths_partial_multi_kernel(const double* __restrict__ X, int N, int D,
+                                                                  const double* __restrict__ Omega,
+                                                                  const double* __restrict__ phase, int F,
+                                                                  const double* __restrict__ Coef, long long ldc,
+                                                                  long long mstride, int S, PathsMultiK k,
+                                                                  const double* __restrict__ xs, int dx,
+                                                                  const double* __restrict__ u, int rows_per_chunk,
+                                                                  double* __restrict__ partial) {
+  __shared__ double red[PW][B][PB];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int rows = N + F;
+  const int sp = (int)blockIdx.x * PB + lane;
+  const bool live = sp < S;
+  const int s = min(sp, S - 1);      // (a lane past the last path repeats it: its coefficients are zeros, its sums are never stored)
+  const int r0 = (int)blockIdx.y * rows_per_chunk, r1 = min(r0 + rows_per_chunk, rows);
+  double q[16];
+#pragma unroll
+  for (int d = 0; d < 16; ++d) q[d] = d < dx ? xs[(long long)s * dx + d] : (d < D ? u[d - dx] : 0.0);
+  if (k.scaled) {
+#pragma unroll
+    for (int d = 0; d < 16; ++d)
+      if (d < D) q[d] = (q[d] - k.in_shift[d]) / k.in_scale[d];
+  }
+  double acc[B];
+#pragma unroll
+  for (int b = 0; b < B; ++b) acc[b] = 0.0;
+  const double* cs = Coef + s;
+  // Wave w takes the chunk's rows r0 + w, r0 + w + PW, ... in ascending order - the order of the single-model kernel, whose rounds
+  // of PR rows only keep more loads in flight.  One row at a time here: measured at B = 6, S = 500, rounds of 2 or 4 rows are 5 %
+  // slower (the launch is bound by the B exp / cos per (s, j), and fewer registers give three waves per SIMD instead of two).
+  for (int j = r0 + w; j < r1; j += PW) {      // j is wave-uniform
+    double cv[B];
+#pragma unroll
+    for (int b = 0; b < B; ++b) cv[b] = live ? cs[(long long)j * ldc + b * mstride] : 0.0;
+    double bv[B];
+    if (j < N) {
+      const double* xj = X + (long long)j * D;
+      double df[16];
+#pragma unroll
+      for (int d = 0; d < 16; ++d) df[d] = d < D ? q[d] - xj[d] : 0.0;
+#pragma unroll
+      for (int b = 0; b < B; ++b) {
+        double d2 = 0.0;
+#pragma unroll
+        for (int d = 0; d < 16; ++d)
+          if (d < D) {
+            const double t = df[d] * k.inv_ls[b][d];
+            d2 = __builtin_fma(t, t, d2);
+          }
+        bv[b] = k.sf2[b] * gpk_exp_neg(-0.5 * d2);
+      }
+    } else {
+#pragma unroll
+      for (int b = 0; b < B; ++b) {
+        const long long f = (long long)b * F + (j - N);
+        const double* om = Omega + f * D;
+        double t = phase[f];
+#pragma unroll
+        for (int d = 0; d < 16; ++d)
+          if (d < D) t = __builtin_fma(om[d], q[d], t);
+        bv[b] = cos(t);
+      }
+    }
+#pragma unroll
+    for (int b = 0; b < B; ++b) acc[b] = __builtin_fma(bv[b], cv[b], acc[b]);
+  }
+#pragma unroll
+  for (int b = 0; b < B; ++b) red[w][b][lane] = acc[b];
+  __syncthreads();
+  for (int e = tid; e < B * PB; e += 256) {
+    const int b = e >> 6, l = e & 63;
+    const int sl = (int)blockIdx.x * PB + l;
+    if (sl < S) {
+      double t = red[0][b][l];
+#pragma unroll
+      for (int ww = 1; ww < PW; ++ww) t += red[ww][b][l];
+      partial[((long long)blockIdx.y * B + b) * S + sl] = t;
+    }
+  }
+}
+
+// grid (blocks of 256 paths) x B: out[s][b] = shift[b] + scale[b] sum over the chunks, in chunk order
+__global__ __launch_bounds__(256) void paths_combine_multi_kernel(const double* __restrict__ partial, int chunks, int S, int B,
+                                                                  PathsMultiK k, double* __restrict__ out) {
+  const int b = blockIdx.y;
+  const int s = (int)blockIdx.x * 256 + threadIdx.x;
+  if (s >= S) return;
+  double t = 0.0;
+#pragma unroll 8
+  for (int ch = 0; ch < chunks; ++ch) t += partial[((long long)ch * B + b) * S + s];
+  out[(long long)s * B + b] = __builtin_fma(k.scale[b], t, k.shift[b]);
+}
+
+// grid (blocks of 256 paths) x nx, the advance of a rollout: coordinate i of the next stage is x_i + lin[i] . [x_s, u] plus, where
+// a model feeds that coordinate, its value; x and u in raw units (lin: nx x D, row-major)
+__global__ __launch_bounds__(256) void paths_advance_multi_kernel(const double* __restrict__ partial, int chunks, int S, int B,
+                                                                  int nx, int D, PathsMultiK k, const double* __restrict__ x,
+                                                                  const double* __restrict__ u, const double* __restrict__ lin,
+                                                                  double* __restrict__ x_next) {
+  const int i = blockIdx.y;
+  const int s = (int)blockIdx.x * 256 + threadIdx.x;
+  if (s >= S) return;
+  const double* xr = x + (long long)s * nx;
+  double a = 0.0;
+  for (int d = 0; d < nx; ++d) a = __builtin_fma(lin[i * D + d], xr[d], a);
+  for (int d = nx; d < D; ++d) a = __builtin_fma(lin[i * D + d], u[d - nx], a);
+  double v = xr[i] + a;
+  const int b = k.model_of[i];
+  if (b >= 0) {
+    double t = 0.0;
+#pragma unroll 8
+    for (int ch = 0; ch < chunks; ++ch) t += partial[((long long)ch * B + b) * S + s];
+    v += __builtin_fma(k.scale[b], t, k.shift[b]);
+  }
+  x_next[(long long)s * nx + i] = v;
+}
+
+struct PathsMultiModel {
+  const double* X;
+  int N, D, B;
+  const double* Omega;
+  const double* phase;
+  int F;
+  const double* Coef;
+  long long ldc, mstride;
+  int S;
+  PathsMultiK k;
+};
+
+int paths_check_multi(gpk_handle h, int64_t N, int D, int B, int64_t F, int S, int64_t ldc, int64_t mstride) {
+  GPK_REQUIRE(h, h->batch == 1, "paths: not available in batched mode");
+  GPK_REQUIRE(h, N >= 1 && N < (1ll << 30), "paths: N must be at least 1");
+  GPK_REQUIRE(h, D >= 1 && D <= GPK_MAX_D_PREDICT, "paths: D must be in [1, 16]");
+  GPK_REQUIRE(h, B >= 1 && B <= PATHS_MAX_B, "paths: B must be in [1, 8]");
+  GPK_REQUIRE(h, S >= 1 && S <= PATHS_MAX_S, "paths: S must be in [1, 4096]");
+  GPK_REQUIRE(h, F >= 1 && F <= PATHS_MAX_F, "paths: F must be in [1, 16384]");
+  GPK_REQUIRE(h, mstride >= S, "paths: mstride must be >= S");
+  GPK_REQUIRE(h, ldc >= (int64_t)B * mstride, "paths: ldc must be >= B * mstride");
+  return GPK_OK;
+}
+
+int paths_fill_multi(gpk_handle h, int D, int B, const double* ls, const double* sf2, const double* shift, const double* scale,
+                     PathsMultiK& k) {
+  GPK_REQUIRE(h, ls && sf2 && shift && scale, "paths: null length-scale, sf2, shift or scale array");
+  for (int b = 0; b < PATHS_MAX_B; ++b) {
+    for (int d = 0; d < 16; ++d) k.inv_ls[b][d] = 0.0;
+    k.sf2[b] = 0.0;
+    k.shift[b] = 0.0;
+    k.scale[b] = 1.0;
+  }
+  for (int b = 0; b < B; ++b) {
+    for (int d = 0; d < D; ++d) {
+      GPK_REQUIRE(h, ls[b * D + d] > 0.0, "length-scales must be positive");
+      k.inv_ls[b][d] = 1.0 / ls[b * D + d];
+    }
+    k.sf2[b] = sf2[b];
+    k.shift[b] = shift[b];
+    k.scale[b] = scale[b];
+  }
+  for (int d = 0; d < 16; ++d) {
+    k.in_shift[d] = 0.0;
+    k.in_scale[d] = 1.0;
+    k.model_of[d] = -1;
+  }
+  k.scaled = 0;
+  return GPK_OK;
+}
+
+// the first launch of a stage: the shares of every chunk
+int paths_partial_multi(gpk_handle h, const PathsMultiModel& m, const double* xs, int dx, const double* u, int rpc, int chunks,
+                        double* partial) {
+  const dim3 grid((unsigned)((m.S + PB - 1) / PB), (unsigned)chunks);
+#define GPK_PATHS_MULTI(BB)                                                                                                    \
+  case BB:                                                                                                                     \
+    hipLaunchKernelGGL(paths_partial_multi_kernel<BB>, grid, dim3(256), 0, h->stream, m.X, m.N, m.D, m.Omega, m.phase, m.F,    \
+                       m.Coef, m.ldc, m.mstride, m.S, m.k, xs, dx, u, rpc, partial);                                           \
+    break
+  switch (m.B) {
+    GPK_PATHS_MULTI(1); GPK_PATHS_MULTI(2); GPK_PATHS_MULTI(3); GPK_PATHS_MULTI(4);
+    GPK_PATHS_MULTI(5); GPK_PATHS_MULTI(6); GPK_PATHS_MULTI(7); GPK_PATHS_MULTI(8);
+  }
+#undef GPK_PATHS_MULTI
+  GPK_LAUNCH_CHECK(h);
+  return GPK_OK;
+}
+
 }  // namespace
 
 extern "C" int gpk_rff_features(gpk_handle h, const double* X, int64_t N, int D, const double* Omega, const double* phase,
@@ -377,6 +585,91 @@ extern "C" int gpk_paths_rollout(gpk_handle h, const double* X, int64_t N, int D
   for (int k = 0; k < H; ++k) {
     const double* xk = d_traj + (size_t)k * C;
     GPK_TRY(paths_stage(h, m, xk, P, d_u + (size_t)k * du, rpc, chunks, partial, nullptr, d_lin, d_traj + (size_t)(k + 1) * C));
+  }
+  GPK_CHECK_HIP(h, hipMemcpyAsync(traj, d_traj, sizeof(double) * n_traj, hipMemcpyDeviceToHost, h->stream));
+  GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
+  return GPK_OK;
+}
+
+extern "C" int gpk_paths_step_multi(gpk_handle h, const double* X, int64_t N, int D, int B, const double* ls, const double* sf2,
+                                    const double* Omega, const double* phase, int64_t F, const double* Coef, int64_t ldc,
+                                    int64_t mstride, int S, const double* shift, const double* scale, const double* Xq,
+                                    double* out) {
+  if (!h) return GPK_BAD_ARG;
+  GPK_REQUIRE(h, X && Omega && phase && Coef && Xq && out, "paths_step_multi: null pointer");
+  GPK_TRY(paths_check_multi(h, N, D, B, F, S, ldc, mstride));
+  PathsMultiModel m{X, (int)N, D, B, Omega, phase, (int)F, Coef, (long long)ldc, (long long)mstride, S, {}};
+  GPK_TRY(paths_fill_multi(h, D, B, ls, sf2, shift, scale, m.k));
+  int rpc = 0, chunks = 0;
+  paths_chunks(N + F, S, &rpc, &chunks);
+  void* ws = nullptr;
+  GPK_TRY(gpk_scratch(h, (size_t)chunks * S * B * sizeof(double), &ws));
+  GPK_TRY(paths_partial_multi(h, m, Xq, D, nullptr, rpc, chunks, (double*)ws));
+  hipLaunchKernelGGL(paths_combine_multi_kernel, dim3((unsigned)((S + 255) / 256), (unsigned)B), dim3(256), 0, h->stream,
+                     (const double*)ws, chunks, S, B, m.k, out);
+  GPK_LAUNCH_CHECK(h);
+  return GPK_OK;
+}
+
+extern "C" int gpk_paths_rollout_multi(gpk_handle h, const double* X, int64_t N, int D, int B, const double* ls, const double* sf2,
+                                       const double* Omega, const double* phase, int64_t F, const double* Coef, int64_t ldc,
+                                       int64_t mstride, int S, const double* shift, const double* scale, int nx, const int* coord,
+                                       const double* in_shift, const double* in_scale, const double* x0, int x0_rows,
+                                       const double* U, int H, const double* lin, double* traj) {
+  if (!h) return GPK_BAD_ARG;
+  GPK_REQUIRE(h, X && Omega && phase && Coef && coord && x0 && lin && traj, "paths_rollout_multi: null pointer");
+  GPK_TRY(paths_check_multi(h, N, D, B, F, S, ldc, mstride));
+  GPK_REQUIRE(h, H >= 1 && H <= PATHS_MAX_H, "paths_rollout_multi: H must be in [1, 256]");
+  GPK_REQUIRE(h, nx >= B && nx <= D, "paths_rollout_multi: the state dimension nx must be in [B, D]");
+  GPK_REQUIRE(h, x0_rows == 1 || x0_rows == S, "paths_rollout_multi: x0 must have 1 or S rows");
+  GPK_REQUIRE(h, (in_shift == nullptr) == (in_scale == nullptr), "paths_rollout_multi: in_shift and in_scale go together");
+  const int du = D - nx;
+  GPK_REQUIRE(h, du == 0 || U, "paths_rollout_multi: null controls");
+  PathsMultiModel m{X, (int)N, D, B, Omega, phase, (int)F, Coef, (long long)ldc, (long long)mstride, S, {}};
+  GPK_TRY(paths_fill_multi(h, D, B, ls, sf2, shift, scale, m.k));
+  for (int b = 0; b < B; ++b) {
+    GPK_REQUIRE(h, coord[b] >= 0 && coord[b] < nx, "paths_rollout_multi: coord must be in [0, nx)");
+    GPK_REQUIRE(h, m.k.model_of[coord[b]] < 0, "paths_rollout_multi: coord must be distinct");
+    m.k.model_of[coord[b]] = b;
+  }
+  GPK_REQUIRE(h, all_finite(x0, (long long)x0_rows * nx) && all_finite(lin, (long long)nx * D) &&
+                     (du == 0 || all_finite(U, (long long)H * du)) &&
+                     (!in_shift || (all_finite(in_shift, D) && all_finite(in_scale, D))),
+              "paths_rollout_multi: x0, U, lin and the input scaler must not contain NaN or infinity");
+  if (in_shift) {
+    for (int d = 0; d < D; ++d) {
+      GPK_REQUIRE(h, in_scale[d] != 0.0, "paths_rollout_multi: in_scale must be non-zero");
+      m.k.in_shift[d] = in_shift[d];
+      m.k.in_scale[d] = in_scale[d];
+    }
+    m.k.scaled = 1;
+  }
+  int rpc = 0, chunks = 0;
+  paths_chunks(N + F, S, &rpc, &chunks);
+  const size_t C = (size_t)S * nx;
+  // device block: the trajectory ((H + 1) x S x nx), then [stage 0 | U | lin] as they come from the host in one copy - stage 0
+  // is the trajectory's first slot - and the chunks' shares
+  const size_t n_traj = (size_t)(H + 1) * C, n_u = (size_t)H * du, n_lin = (size_t)nx * D;
+  void* ws = nullptr;
+  GPK_TRY(gpk_scratch(h, (n_traj + n_u + n_lin + (size_t)chunks * S * B) * sizeof(double), &ws));
+  double* d_traj = (double*)ws;
+  double* d_u = d_traj + n_traj;
+  double* d_lin = d_u + n_u;
+  double* partial = d_lin + n_lin;
+  std::vector<double> stage(C + n_u + n_lin);
+  for (int s = 0; s < S; ++s) memcpy(stage.data() + (size_t)s * nx, x0 + (x0_rows == 1 ? 0 : (size_t)s * nx), sizeof(double) * nx);
+  if (n_u) memcpy(stage.data() + C, U, sizeof(double) * n_u);
+  memcpy(stage.data() + C + n_u, lin, sizeof(double) * n_lin);
+  GPK_CHECK_HIP(h, hipMemcpyAsync(d_traj, stage.data(), sizeof(double) * C, hipMemcpyHostToDevice, h->stream));
+  GPK_CHECK_HIP(h, hipMemcpyAsync(d_u, stage.data() + C, sizeof(double) * (n_u + n_lin), hipMemcpyHostToDevice, h->stream));
+  const dim3 agrid((unsigned)((S + 255) / 256), (unsigned)nx);
+  for (int st = 0; st < H; ++st) {
+    const double* xk = d_traj + (size_t)st * C;
+    const double* uk = d_u + (size_t)st * du;
+    GPK_TRY(paths_partial_multi(h, m, xk, nx, uk, rpc, chunks, partial));
+    hipLaunchKernelGGL(paths_advance_multi_kernel, agrid, dim3(256), 0, h->stream, (const double*)partial, chunks, S, B, nx, D,
+                       m.k, xk, uk, (const double*)d_lin, d_traj + (size_t)(st + 1) * C);
+    GPK_LAUNCH_CHECK(h);
   }
   GPK_CHECK_HIP(h, hipMemcpyAsync(traj, d_traj, sizeof(double) * n_traj, hipMemcpyDeviceToHost, h->stream));
   GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));

@@ -12,6 +12,10 @@ that S paths can each be evaluated at their own point - the state their own last
 (`gpk_paths_step`), and a whole closed-loop horizon in one call (`gpk_paths_rollout`).  A path stays the same function from
 call to call.  The only approximation is the finite F of the prior term.  fp64, one GPU, the exact model only; there is no CPU
 fallback.
+
+The per-axis batch (`BatchedARDGP`: B single-output models on shared inputs, each with its own kernel) has the same three
+surfaces in `BatchedPosteriorPaths`: one model-major coefficient matrix, set up by one `gpk_paths_prepare` per model, `step` for all
+models in two launches (`gpk_paths_step_multi`), a horizon in raw units in one call (`gpk_paths_rollout_multi`).
 """
 from __future__ import annotations
 
@@ -205,4 +209,241 @@ class PosteriorPaths:
         traj = np.empty((H + 1, S, P))
         self.be.call("gpk_paths_rollout", *self._model_args(), _hp(x0), 1 if x0.ndim == 1 else S,
                      _hp(U) if D > P else None, H, _hp(lin), _hp(traj))
+        return traj
+
+
+# ---- the per-axis batch: B single-output models on shared inputs, each with its own kernel -------------------------------------
+MAX_BATCH = 8
+
+
+def draw_batch_path_randomness(rng, N, D, F, S, ls, noise_plus_alpha):
+    """The random numbers of a batch path set, pure NumPy: dict(omega (B, F, D), phase (B, F), weights (B, F, S), eps (B, N, S))
+    for B models with length-scales ls (B, D) and noise levels noise_plus_alpha (B,).
+
+    Draw order, from the one `rng`: model 0, 1, ..., B - 1 in turn, each `draw_path_randomness(rng, N, D, F, S, 1, ls[b],
+    noise_plus_alpha[b])` - that is, per model, standard_normal((F, D)) / ls[b], uniform(0, 2 pi, F), standard_normal((F, S, 1)),
+    sqrt(noise_plus_alpha[b]) standard_normal((N, S, 1)) - so that model 0's numbers are the single-model draw's."""
+    ls = np.array(ls, dtype=np.float64, ndmin=2)
+    s2 = np.array(noise_plus_alpha, dtype=np.float64, ndmin=1)
+    B = ls.shape[0]
+    if ls.ndim != 2 or ls.shape[1] != int(D) or s2.shape != (B,):
+        raise ValueError(f"ls must be (B, {int(D)}) and noise_plus_alpha (B,)")
+    if not 1 <= B <= MAX_BATCH:
+        raise ValueError(f"the number of models must be in [1, {MAX_BATCH}] (got {B})")
+    rs = [draw_path_randomness(rng, N, D, F, S, 1, ls[b], s2[b]) for b in range(B)]
+    return {"omega": np.stack([r["omega"] for r in rs]), "phase": np.stack([r["phase"] for r in rs]),
+            "weights": np.stack([r["weights"][:, :, 0] for r in rs]), "eps": np.stack([r["eps"][:, :, 0] for r in rs])}
+
+
+def check_batch_path_shape(B, D, S, F, H=None):
+    """The limits of the batch entries (include/gpk.h, K10, the per-axis batch) as ValueErrors, before any launch."""
+    if not 1 <= B <= MAX_BATCH:
+        raise ValueError(f"the number of models must be in [1, {MAX_BATCH}] (got {B})")
+    check_path_shape(D, 1, S, F, H)
+
+
+class BatchedPosteriorPaths:
+    """S posterior function draws of every model of a fitted `BatchedARDGP` (B models on shared inputs), resident on its GPU.
+
+    paths(X)                            all paths of all models at the same M points: (M, B, S)
+    paths.step(Xs)                      Xs (S, D): path s of every model at row s -> (S, B); the hot path, two launches
+    paths.rollout(x0, U, lin, ...)      a closed-loop horizon in one call -> (H + 1, S, nx)
+    paths.randomness                    dict(omega, phase, weights, eps) it was built from
+    paths.coef                          the device coefficient matrix (N + F, B mstride), model-major: model b, path s is
+                                        column b mstride + s, mstride = S rounded up to a multiple of 8 (`paths.mstride`)
+
+    Column b of `step` and model b's column block of `coef` have the bits of `PosteriorPaths.from_randomness(models[b], ...)` on
+    the same randomness.  The values are in the models' target units, y_mean_b + y_std_b f; `set_output_scaler` puts a further
+    affine map per model behind them (a trainer's target scaler)."""
+
+    def __init__(self):
+        raise TypeError("use BatchedARDGP.sample_paths or BatchedPosteriorPaths.from_randomness")
+
+    @classmethod
+    def from_randomness(cls, bg, omega, phase, weights, eps):
+        """The path set of the fitted batch `bg` from arrays of the caller's own: omega (B, F, D), phase (B, F), weights (B, F, S)
+        = the w_s of every model, eps (B, N, S) = the eps_s, already scaled by sqrt(noise_b + alpha).  The set-up is one
+        `gpk_paths_prepare` (P = 1) per model on that model's own handle, pointed at its column block."""
+        from .device import get_backend
+        import ctypes as C
+        ms = list(getattr(bg, "models", ()))
+        if not ms:
+            raise RuntimeError("this BatchedARDGP is not fitted yet")
+        B = len(ms)
+        if B > MAX_BATCH:
+            raise ValueError(f"a batch path set takes at most {MAX_BATCH} models (got {B})")
+        for m in ms:
+            m._ensure_device()
+        devs = [m._dev for m in ms]
+        if any(d.replica for d in devs):
+            raise RuntimeError("a serving replica holds no fp64 inverse factor: paths are drawn on the rank that fitted the models")
+        if not bg._alike(devs):
+            raise RuntimeError("the models cannot share a launch: single-output models of one size on one device are needed")
+        if not bg._shared_inputs():
+            raise RuntimeError("the models were fitted on different training inputs: a batch path set reads one shared X")
+        d0 = devs[0]
+        N, D = d0.N, d0.D
+        if D > DeviceGP.MAX_FEATURES:
+            raise ValueError(f"D must be in [1, {DeviceGP.MAX_FEATURES}] (got {D})")
+        omega = np.ascontiguousarray(omega, dtype=np.float64)
+        phase = np.ascontiguousarray(phase, dtype=np.float64)
+        weights = np.ascontiguousarray(weights, dtype=np.float64)
+        eps = np.ascontiguousarray(eps, dtype=np.float64)
+        if omega.ndim != 3 or omega.shape[0] != B or omega.shape[2] != D:
+            raise ValueError(f"omega must be ({B}, F, {D})")
+        F = omega.shape[1]
+        if phase.shape != (B, F):
+            raise ValueError(f"phase must be ({B}, {F})")
+        if weights.ndim != 3 or weights.shape[:2] != (B, F):
+            raise ValueError(f"weights must be ({B}, {F}, S)")
+        S = weights.shape[2]
+        if eps.shape != (B, N, S):
+            raise ValueError(f"eps must be ({B}, {N}, {S})")
+        check_batch_path_shape(B, D, S, F)
+        if padded(N) + padded(F) > 65535:
+            raise ValueError("gpk_padded(N) + gpk_padded(F) must not exceed 65535")
+        for name, a in (("omega", omega), ("phase", phase), ("weights", weights), ("eps", eps)):
+            if not np.isfinite(a).all():
+                raise ValueError(f"{name} contains NaN or infinity.")
+        self = object.__new__(cls)
+        torch = _torch()
+        be = get_backend(bg.device)
+        self.bg, self.be, self._devs = bg, be, devs
+        self.N, self.D, self.B, self.F, self.S = N, D, B, F, S
+        self.mstride = (S + 7) // 8 * 8          # every model's run of columns starts 64-byte aligned
+        self.ldc = B * self.mstride
+        self.randomness = {"omega": omega, "phase": phase, "weights": weights, "eps": eps}
+        self._ls = np.ascontiguousarray(np.stack([np.asarray(d.ls, dtype=np.float64) for d in devs]))
+        self._sf2 = np.ascontiguousarray([float(d.sf2) for d in devs], dtype=np.float64)
+        self._y_mean = np.ascontiguousarray([float(np.ravel(m._y_train_mean)[0]) for m in ms], dtype=np.float64)
+        self._y_std = np.ascontiguousarray([float(np.ravel(m._y_train_std)[0]) for m in ms], dtype=np.float64)
+        self._shift, self._scale = self._y_mean.copy(), self._y_std.copy()
+        with torch.cuda.device(be.device):
+            torch.cuda.synchronize()              # the models may have been fitted on their own streams
+            self._X = d0.X.to(be.device)
+            self._omega = be.upload(omega)
+            self._phase = be.upload(phase)
+            self.coef = be.empty((N + F, self.ldc), torch.float64)
+            for b, dev in enumerate(devs):
+                mb = dev.be
+                with mb.lock:
+                    W = dev.inverse_factor(False)
+                    w_d = mb.upload(weights[b])
+                    e_d = mb.upload(eps[b])
+                    block = C.c_void_p(self.coef.data_ptr() + 8 * b * self.mstride)
+                    mb.call("gpk_paths_prepare", _p(dev.X), N, D, _p(dev.Yn), 1, _p(W), dev.Np, dev.Np, _p(self._omega[b]),
+                            _p(self._phase[b]), F, float(self._sf2[b]), _p(w_d), _p(e_d), S, block, self.ldc)
+                    mb.sync()       # (w_d and e_d are released here: the set-up is not the hot path)
+            torch.cuda.synchronize()
+        return self
+
+    def set_output_scaler(self, mean, scale):
+        """Puts the affine map mean[b] + scale[b] y per model behind the values (a trainer's target scaler): folded on the host
+        into the one shift / scale pair the launches apply, shift_b = mean_b + scale_b y_mean_b, scale_b <- scale_b y_std_b."""
+        mean, scale = _vec(mean, self.B), _vec(scale, self.B)
+        if not (np.isfinite(mean).all() and np.isfinite(scale).all()):
+            raise ValueError("the output scaler contains NaN or infinity.")
+        self._shift = np.ascontiguousarray(mean + scale * self._y_mean)
+        self._scale = np.ascontiguousarray(scale * self._y_std)
+        return self
+
+    # ---- the models' side of both calls: X, N, D, B, ls, sf2, Omega, phase, F, Coef, ldc, mstride, S, shift, scale
+    def _model_args(self):
+        return (_p(self._X), self.N, self.D, self.B, _hp(self._ls), _hp(self._sf2), _p(self._omega), _p(self._phase), self.F,
+                _p(self.coef), self.ldc, self.mstride, self.S, _hp(self._shift), _hp(self._scale))
+
+    def __call__(self, X):
+        """Every path of every model at the same M points: (M, B, S).  Per model gpk_cross_gram_t, gpk_rff_features and two
+        gpk_gemm_tiles products; not a hot path."""
+        torch = _torch()
+        X = check_queries(X, self.D)
+        M = X.shape[0]
+        if M == 0:
+            return np.empty((0, self.B, self.S))
+        be = self.be
+        N, F, D, S = self.N, self.F, self.D, self.S
+        Np, Fp, Mp, Sp = padded(N), padded(F), padded(M), padded(S)
+        q = be.upload(X)
+        res = np.empty((M, self.B, S))
+        for b in range(self.B):
+            # the two row blocks of the model's columns in the padded shape of the tile GEMM, zeros in the padding
+            cv = torch.zeros((Np, Sp), dtype=torch.float64, device=be.device)
+            cw = torch.zeros((Fp, Sp), dtype=torch.float64, device=be.device)
+            cols = self.coef[:, b * self.mstride:b * self.mstride + S]
+            cv[:N, :S] = cols[:N]
+            cw[:F, :S] = cols[N:]
+            kt = be.empty((Np, Mp), torch.float64)
+            phi = be.empty((Mp, Fp), torch.float64)
+            out = be.empty((Mp, Sp), torch.float64)
+            with be.lock:
+                be.call("gpk_cross_gram_t", _lib.GPK_F64, _p(self._X), N, _p(q), M, D, _hp(self._ls[b]), float(self._sf2[b]),
+                        _p(kt), Mp)
+                be.call("gpk_rff_features", _p(q), M, D, _p(self._omega[b]), _p(self._phase[b]), F, 1.0, _p(phi), Fp)
+                be.call("gpk_gemm_tiles", _lib.GPK_F64, 1, 1, _p(kt), Mp, _p(cv), Sp, _p(out), Sp, Mp, Sp, Np, 1.0, 0.0, 0)
+                be.call("gpk_gemm_tiles", _lib.GPK_F64, 0, 1, _p(phi), Fp, _p(cw), Sp, _p(out), Sp, Mp, Sp, Fp, 1.0, 1.0, 0)
+            res[:, b, :] = self._shift[b] + self._scale[b] * out[:M, :S].cpu().numpy()
+        return res
+
+    def step(self, Xs):
+        """Path s of every model at ITS OWN point Xs[s] (gpk_paths_step_multi): Xs (S, D) -> (S, B)."""
+        torch = _torch()
+        Xs = check_queries(Xs, self.D)
+        if Xs.shape[0] != self.S:
+            raise ValueError(f"step takes one row per path: ({self.S}, {self.D})")
+        be = self.be
+        q = be.upload(Xs)
+        out = be.empty((self.S, self.B), torch.float64)
+        be.call("gpk_paths_step_multi", *self._model_args(), _p(q), _p(out))
+        return out.cpu().numpy()
+
+    def rollout(self, x0, U, lin, coord=None, in_scaler=None):
+        """A closed-loop horizon in one call (gpk_paths_rollout_multi), in raw units.  The state has nx = len(lin) coordinates,
+        B <= nx <= D; model b's output is added to state coordinate coord[b] (default 0 .. B - 1; distinct); a coordinate
+        without a model advances by `lin` alone.  The models read the scaled query: stage h, path s,
+
+            q_s = [x_s, U[h]];   z_s = (q_s - in_shift) / in_scale;   x_s <- x_s + lin q_s + sum_b e_coord[b] path_{b,s}(z_s)
+
+        x0 (S, nx), or (nx,) as the start of every path; U (H, D - nx); lin (nx, D); in_scaler: None (identity), a pair
+        (shift (D,), scale (D,)) or an object with `mean_` / `scale_`.  Returns the trajectory (H + 1, S, nx), stage 0 = x0.
+        The next stage's queries never leave the device: 2 H launches, one synchronisation."""
+        B, D, S = self.B, self.D, self.S
+        lin = np.ascontiguousarray(lin, dtype=np.float64)
+        if lin.ndim != 2 or lin.shape[1] != D:
+            raise ValueError(f"lin must be (nx, {D})")
+        nx = lin.shape[0]
+        if not B <= nx <= D:
+            raise ValueError(f"rollout needs a state of {B} <= nx <= {D} coordinates (got {nx})")
+        coord = np.arange(B) if coord is None else np.asarray(coord)
+        if coord.shape != (B,) or not np.issubdtype(coord.dtype, np.integer):
+            raise ValueError(f"coord must be {B} integers")
+        if coord.min() < 0 or coord.max() >= nx:
+            raise ValueError(f"coord must be in [0, {nx})")
+        if len(set(coord.tolist())) != B:
+            raise ValueError("coord must be distinct")
+        coord = np.ascontiguousarray(coord, dtype=np.intc)
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        if x0.shape not in ((nx,), (S, nx)):
+            raise ValueError(f"x0 must be ({S}, {nx}) or ({nx},)")
+        U = np.ascontiguousarray(U, dtype=np.float64)
+        if U.ndim == 1 and D - nx == 1:
+            U = U[:, None]
+        if U.ndim != 2 or U.shape[1] != D - nx:
+            raise ValueError(f"U must be (H, {D - nx})")
+        H = U.shape[0]
+        check_batch_path_shape(B, D, S, self.F, H)
+        if not (np.isfinite(x0).all() and np.isfinite(U).all() and np.isfinite(lin).all()):
+            raise ValueError("Input X contains NaN or infinity.")
+        in_shift = in_scale = None
+        if in_scaler is not None:
+            pair = (in_scaler.mean_, in_scaler.scale_) if hasattr(in_scaler, "mean_") else in_scaler
+            in_shift, in_scale = _vec(pair[0], D), _vec(pair[1], D)
+            if not (np.isfinite(in_shift).all() and np.isfinite(in_scale).all()):
+                raise ValueError("the input scaler contains NaN or infinity.")
+            if not in_scale.all():
+                raise ValueError("in_scale must be non-zero")
+        import ctypes as C
+        traj = np.empty((H + 1, S, nx))
+        self.be.call("gpk_paths_rollout_multi", *self._model_args(), nx, coord.ctypes.data_as(C.POINTER(C.c_int)),
+                     _hp(in_shift), _hp(in_scale), _hp(x0), 1 if x0.ndim == 1 else S, _hp(U) if D > nx else None, H, _hp(lin),
+                     _hp(traj))
         return traj

@@ -225,7 +225,13 @@ class PreTrainedGP:
         self.model_path = model_path
         self.gp_models, self.scalers_X, self.scalers_y, self.training_stats = {}, {}, {}, {}
         self.is_loaded = False
+        self._axis_paths = None     # sample_rollouts: (key, BatchedPosteriorPaths) of the loaded models
         self.load_models()
+
+    def __getstate__(self):
+        st = self.__dict__.copy()
+        st["_axis_paths"] = None    # device buffers: drawn again on the first `sample_rollouts` after unpickling
+        return st
 
     def load_models(self):
         if not os.path.exists(self.model_path):
@@ -248,6 +254,7 @@ class PreTrainedGP:
         imported on the device at the first prediction.  A component that cannot be converted is dropped (its prediction is
         then the reference's (0, 1e6) fallback, `pretrained_gp.py:93-96`)."""
         models, sxs, sys_ = {}, {}, {}
+        self._axis_paths = None
         for name, m in d["gp_models"].items():
             try:
                 if not isinstance(m, (GaussianProcessRegressor, SparseGP)):
@@ -499,6 +506,56 @@ class PreTrainedGP:
         except Exception as e:  # noqa: BLE001
             print(f"GP sampling failed: {e}")
             return np.zeros((mean.shape[0], 6, int(n_samples)))
+
+    def sample_rollouts(self, state, U_guess, dt, n_rollouts=64, n_features=1024, random_state=0):
+        """`n_rollouts` closed-loop rollouts under the loaded models' own uncertainty, in raw units: rollout r follows ONE
+        posterior function draw of every per-axis model along the whole horizon, stage k + 1 evaluated at the state its
+        sampled residuals of stage k produced,
+
+            x_{k+1} = x_k + dt [v_k, a_k] + sum_i e_i (sy_i.mean_ + sy_i.scale_ f_{i,r}(([x_k, u_k] - sx.mean_) / sx.scale_))
+
+        in one call for the horizon (`BatchedPosteriorPaths.rollout` on the fused `BatchedARDGP`, its shared input scaler and
+        each model's target scaler).  state (6,); U_guess (4, N).  Returns (R, 6, N + 1), the layout `linearize_residuals`
+        takes as X_guess.  A residual without a model leaves its coordinate nominal.  The path set (n_rollouts, n_features,
+        random_state) is drawn once and cached on the object until `load_dict`: the same functions from call to call.  Not
+        loaded, models that cannot be fused into an exact batch (a sparse batch, a single model, different inputs or scalers),
+        or any failure: the reason is printed and the nominal trajectory is returned R times - it never raises into the
+        control loop."""
+        U_guess = np.asarray(U_guess, dtype=float)
+        state = np.asarray(state, dtype=float).reshape(-1)[:6]
+        R, N = int(n_rollouts), U_guess.shape[1]
+        nominal = np.empty((6, N + 1))
+        nominal[:, 0] = state
+        for k in range(N):
+            nominal[:, k + 1] = GPTrainer._nominal_dynamics(nominal[:, k], U_guess[:, k], dt)
+        fallback = np.repeat(nominal[None], max(R, 0), axis=0)
+        try:
+            if not self.is_loaded:
+                raise RuntimeError("no models are loaded")
+            from .batched import BatchedARDGP
+            fused = self._fused()
+            if not fused or not isinstance(fused[0], BatchedARDGP):
+                raise RuntimeError("the loaded models are not served as one exact per-axis batch")
+            bg, names = fused
+            key = (R, int(n_features), random_state if isinstance(random_state, (int, np.integer)) else id(random_state), id(bg))
+            cached = getattr(self, "_axis_paths", None)     # (an object pickled before the attribute existed has none)
+            if cached is None or cached[0] != key:
+                paths = bg.sample_paths(R, n_features, random_state)
+                sys_ = [self.scalers_y[n] for n in names]
+                paths.set_output_scaler([float(np.ravel(s.mean_)[0]) for s in sys_], [float(np.ravel(s.scale_)[0]) for s in sys_])
+                self._axis_paths = (key, paths)
+            lin = np.zeros((6, 10))
+            lin[0:3, 3:6] = dt * np.eye(3)       # the double integrator of `GPTrainer._nominal_dynamics`
+            lin[3:6, 6:9] = dt * np.eye(3)
+            traj = self._axis_paths[1].rollout(state, np.ascontiguousarray(U_guess[:4].T), lin,
+                                               coord=[OUTPUT_NAMES.index(n) for n in names],
+                                               in_scaler=self.scalers_X[names[0]])      # (N + 1, R, 6)
+            if not np.isfinite(traj).all():
+                raise FloatingPointError("non-finite trajectory")
+            return np.ascontiguousarray(traj.transpose(1, 2, 0))
+        except Exception as e:  # noqa: BLE001
+            print(f"GP rollout sampling failed: {e}")
+            return fallback
 
     def predict_residual_jacobian(self, state, control):
         """One query -> (mean (6,), J (6, 10)), J = d mean / d [state(6), control(4)]; not loaded or failed: zeros."""
