@@ -927,6 +927,47 @@ GPK_API int gpk_paths_rollout_multi(gpk_handle h, const double* X, int64_t N, in
                                     const double* in_shift, const double* in_scale, const double* x0, int x0_rows,
                                     const double* U, int H, const double* lin, double* traj);
 
+/* ---- K10, the sparse models: paths conditioned on the inducing variables ------------------------------------------------
+ * Pathwise conditioning on u = f(Z) (Wilson et al. 2020, the sparse case), in normalised-target units, on the assembled model
+ * of the handle (gpk_sparse_finalize: Wuu = Luu^-1, WS = LB^-1 Wuu, alpha_u; Wuu^T Wuu = (Kuu + jitter_uu I)^-1):
+ *     f_s(x) = phi(x)^T w_s + k_u(x)^T v_s,   v_s = alpha_u + WS^T xi_s - Wuu^T (Wuu Phi_Z w_s),   xi_s ~ N(0, I_m),  w_s ~ N(0, I_F)
+ * phi, omega and phase as above.  With xi = 0 and w = 0 the value is gpk_sparse_predict's mean; the ensemble covariance is
+ * A A^T + B B^T with B = k_u WS^T - exactly the + |WS k*|^2 term of the sparse variance - and A = phi^T - k_u Kuu^-1 Phi_Z,
+ * which tends to K** - |Wuu k*|^2 as F grows.  A sparse path set is therefore the coefficient matrix of the family above with
+ * N := m and X := Z: rows [0, m) hold v, rows [m, m + F) hold sqrt(2 sf2 / F) w, and gpk_paths_step / gpk_paths_rollout serve
+ * it unchanged.  Every output of a multi-output model draws its own xi and w: column s P + p, alpha_u's column p.
+ *
+ * gpk_sparse_paths_prepare: the set-up (not the hot path).  Omega (dev, F x D), phase (dev, F), W_rand (dev, F x C) = the w_s,
+ *   Xi (dev, m x C) = the xi_s, C = S P, column s P + p both.  Coef (dev, (m + F) x ldc, ldc >= C, no row padding) receives
+ *   the matrix; columns [C, ldc) are not written.  Zdst (dev, m x D) receives a copy of the model's inducing inputs: the path
+ *   set owns everything it needs and stays the same function after the model is refitted or freed.  Launches:
+ *   gpk_rff_features on Z, a pack kernel (zero-padded W_rand and Xi), four tile GEMMs with the triangular k-ranges of
+ *   gpk_potrs_inv - T = Phi_Z Wr, T <- Wuu T, R = -Wuu^T T, R += WS^T Xi - and an unpack that adds alpha_u's column p and
+ *   writes the scaled w rows.  Padding: rows [m, mp) of Phi_Z and of the packed Xi are zeros, and Wuu and WS are both the
+ *   IDENTITY on the padding's diagonal with zeros between padding and model (Kuu + jitter_uu I is the identity there, so are
+ *   Luu and Luu^-1; B is, so is LB^-1, and WS = LB^-1 Wuu is the product of the two: the identity, not the zeros of the
+ *   memset it is written over) - so every product's padding rows are exact zeros, nothing of them reaches a row below m,
+ *   and the unpack reads no row at or above m.  Work area: the handle's scratch ((mp Fp + Fp Cp + 3 mp Cp) doubles).
+ *   Asynchronous.  GPK_BAD_ARG with a message before any launch: no assembled model (as gpk_sparse_predict), batched mode,
+ *   gpk_padded(m) + gpk_padded(F) > 65535, S not in [1, 4096], F not in [1, 16384], ldc < C, a null pointer.
+ * gpk_paths_step_multi_z / gpk_paths_rollout_multi_z: gpk_paths_step_multi / gpk_paths_rollout_multi, argument for argument,
+ *   with Zs (dev, B x N x D: model b's basis points at Zs + b N D) in the place of the shared X: the batch of B sparse
+ *   models, each with its own inducing inputs (N = m).  For j < N model b reads its own x_j and the difference is formed per
+ *   model; expression forms, row, wave and chunk order, the chunking (a function of (N + F, S)) and the second launch are
+ *   those of the shared form, so column b of the result has the BITS of gpk_paths_step on model b's own path set
+ *   (X = Zs_b, P = 1, y_mean = shift[b], y_std = scale[b]).  The same limits and refusals.                               */
+GPK_API int gpk_sparse_paths_prepare(gpk_handle h, const double* Omega, const double* phase, int64_t F, const double* W_rand,
+                                     const double* Xi, int S, double* Coef, int64_t ldc, double* Zdst);
+GPK_API int gpk_paths_step_multi_z(gpk_handle h, const double* Zs, int64_t N, int D, int B, const double* ls, const double* sf2,
+                                   const double* Omega, const double* phase, int64_t F, const double* Coef, int64_t ldc,
+                                   int64_t mstride, int S, const double* shift, const double* scale, const double* Xq,
+                                   double* out);
+GPK_API int gpk_paths_rollout_multi_z(gpk_handle h, const double* Zs, int64_t N, int D, int B, const double* ls, const double* sf2,
+                                      const double* Omega, const double* phase, int64_t F, const double* Coef, int64_t ldc,
+                                      int64_t mstride, int S, const double* shift, const double* scale, int nx, const int* coord,
+                                      const double* in_shift, const double* in_scale, const double* x0, int x0_rows,
+                                      const double* U, int H, const double* lin, double* traj);
+
 #ifdef __cplusplus
 }
 #endif

@@ -145,6 +145,10 @@ SIGNATURES = {
     "gpk_paths_step_multi": (_int, [_vp, _vp, _i64, _int, _int, _dp, _dp, _vp, _vp, _i64, _vp, _i64, _i64, _int, _dp, _dp, _vp, _vp]),
     "gpk_paths_rollout_multi": (_int, [_vp, _vp, _i64, _int, _int, _dp, _dp, _vp, _vp, _i64, _vp, _i64, _i64, _int, _dp, _dp, _int,
                                        C.POINTER(_int), _dp, _dp, _dp, _int, _dp, _int, _dp, _dp]),
+    "gpk_sparse_paths_prepare": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _int, _vp, _i64, _vp]),
+    "gpk_paths_step_multi_z": (_int, [_vp, _vp, _i64, _int, _int, _dp, _dp, _vp, _vp, _i64, _vp, _i64, _i64, _int, _dp, _dp, _vp, _vp]),
+    "gpk_paths_rollout_multi_z": (_int, [_vp, _vp, _i64, _int, _int, _dp, _dp, _vp, _vp, _i64, _vp, _i64, _i64, _int, _dp, _dp, _int,
+                                         C.POINTER(_int), _dp, _dp, _dp, _int, _dp, _int, _dp, _dp]),
 }
 
 _lib = None

@@ -132,6 +132,10 @@ int gpk_potrf_ptile_check(gpk_handle h, int gave_up = -1);
 void gpk_model_free(gpk_handle h);   // gpk_model.hip: all three models of the handle
 void gpk_bmodel_free(gpk_handle h);  // gpk_bmodel.hip
 void gpk_sparse_free(gpk_handle h);  // gpk_sparse.hip
+// the body of gpk_sparse_paths_prepare (gpk_paths.hip): a path set from the sparse model's Z, two inverse factors and alpha_u
+int gpk_paths_prepare_two(gpk_handle h, const double* Z, int64_t m, int D, int P, double sf2, const double* Wuu, const double* WS,
+                          int64_t mp, const double* alpha, const double* Omega, const double* phase, int64_t F,
+                          const double* W_rand, const double* Xi, int S, double* Coef, int64_t ldc, double* Zdst);
 // the launches of gpk_potrf / gpk_lml_terms / gpk_lml_grad without their synchronisations (gpk_lml_eval)
 int gpk_potrf_enqueue(gpk_handle h, double* A, int64_t Np, int64_t lda, double* winv);
 int gpk_potrf_finish(gpk_handle h, const int* hinfo_all, int* info, int gave_up = -1);

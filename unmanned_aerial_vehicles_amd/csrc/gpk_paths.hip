@@ -19,7 +19,10 @@
 //                         the next stage's launch reads its queries.
 //   paths_partial_multi_kernel / paths_combine_multi_kernel / paths_advance_multi_kernel
 //                         the same two launches for the per-axis batch: B single-output models on shared inputs, each with its own
-//                         kernel, Coef model-major (see there)
+//                         kernel, Coef model-major (see there); with OWNZ every model has its own basis points (the sparse batch)
+//   sparse_paths_pack_kernel / sparse_paths_unpack_kernel
+//                         the set-up of a sparse model's path set (gpk_paths_prepare_two): N := m, X := Z, rows [0, m) hold
+//                         v = alpha_u + WS^T xi - Wuu^T (Wuu Phi_Z w) from the two inverse factors of the assembled model
 // The chunk count depends on (N + F, S) only.  The launch is bound by streaming Coef: (N + F) S P 8 bytes per stage.
 #include "gpk_internal.h"
 #include "gpk_math.h"
@@ -284,7 +287,10 @@ struct PathsMultiK {
 };
 
 // partial[(chunk B + b) S + s]: the share of the chunk's rows in model b's sum for path s
-template <int B>
+// OWNZ: every model has its own basis points (the sparse models' inducing inputs): X is (B x N x D), model b's x_j at
+// X + (b N + j) D - still a wave-uniform address - and the difference is formed per model; the expression forms
+// (q_d - x_jd) inv_ls, fma(t, t, d2), sf2 exp(-d2 / 2) and every order are those of the shared form and of the single-model kernel.
+template <int B, bool OWNZ>
 __global__ __launch_bounds__(256) void paths_partial_multi_kernel(const double* __restrict__ X, int N, int D,
                                                                   const double* __restrict__ Omega,
                                                                   const double* __restrict__ phase, int F,
@@ -322,20 +328,35 @@ __global__ __launch_bounds__(256) void paths_partial_multi_kernel(const double* 
     for (int b = 0; b < B; ++b) cv[b] = live ? cs[(long long)j * ldc + b * mstride] : 0.0;
     double bv[B];
     if (j < N) {
-      const double* xj = X + (long long)j * D;
-      double df[16];
+      if constexpr (OWNZ) {
 #pragma unroll
-      for (int d = 0; d < 16; ++d) df[d] = d < D ? q[d] - xj[d] : 0.0;
+        for (int b = 0; b < B; ++b) {
+          const double* xj = X + ((long long)b * N + j) * D;
+          double d2 = 0.0;
 #pragma unroll
-      for (int b = 0; b < B; ++b) {
-        double d2 = 0.0;
+          for (int d = 0; d < 16; ++d)
+            if (d < D) {
+              const double t = (q[d] - xj[d]) * k.inv_ls[b][d];
+              d2 = __builtin_fma(t, t, d2);
+            }
+          bv[b] = k.sf2[b] * gpk_exp_neg(-0.5 * d2);
+        }
+      } else {
+        const double* xj = X + (long long)j * D;
+        double df[16];
 #pragma unroll
-        for (int d = 0; d < 16; ++d)
-          if (d < D) {
-            const double t = df[d] * k.inv_ls[b][d];
-            d2 = __builtin_fma(t, t, d2);
-          }
-        bv[b] = k.sf2[b] * gpk_exp_neg(-0.5 * d2);
+        for (int d = 0; d < 16; ++d) df[d] = d < D ? q[d] - xj[d] : 0.0;
+#pragma unroll
+        for (int b = 0; b < B; ++b) {
+          double d2 = 0.0;
+#pragma unroll
+          for (int d = 0; d < 16; ++d)
+            if (d < D) {
+              const double t = df[d] * k.inv_ls[b][d];
+              d2 = __builtin_fma(t, t, d2);
+            }
+          bv[b] = k.sf2[b] * gpk_exp_neg(-0.5 * d2);
+        }
       }
     } else {
 #pragma unroll
@@ -404,7 +425,8 @@ __global__ __launch_bounds__(256) void paths_advance_multi_kernel(const double* 
 }
 
 struct PathsMultiModel {
-  const double* X;
+  const double* X;      // own_z: (B x N x D), every model's own basis points
+  bool own_z;
   int N, D, B;
   const double* Omega;
   const double* phase;
@@ -460,8 +482,12 @@ int paths_partial_multi(gpk_handle h, const PathsMultiModel& m, const double* xs
   const dim3 grid((unsigned)((m.S + PB - 1) / PB), (unsigned)chunks);
 #define GPK_PATHS_MULTI(BB)                                                                                                    \
   case BB:                                                                                                                     \
-    hipLaunchKernelGGL(paths_partial_multi_kernel<BB>, grid, dim3(256), 0, h->stream, m.X, m.N, m.D, m.Omega, m.phase, m.F,    \
-                       m.Coef, m.ldc, m.mstride, m.S, m.k, xs, dx, u, rpc, partial);                                           \
+    if (m.own_z)                                                                                                               \
+      hipLaunchKernelGGL((paths_partial_multi_kernel<BB, true>), grid, dim3(256), 0, h->stream, m.X, m.N, m.D, m.Omega,        \
+                         m.phase, m.F, m.Coef, m.ldc, m.mstride, m.S, m.k, xs, dx, u, rpc, partial);                           \
+    else                                                                                                                       \
+      hipLaunchKernelGGL((paths_partial_multi_kernel<BB, false>), grid, dim3(256), 0, h->stream, m.X, m.N, m.D, m.Omega,       \
+                         m.phase, m.F, m.Coef, m.ldc, m.mstride, m.S, m.k, xs, dx, u, rpc, partial);                           \
     break
   switch (m.B) {
     GPK_PATHS_MULTI(1); GPK_PATHS_MULTI(2); GPK_PATHS_MULTI(3); GPK_PATHS_MULTI(4);
@@ -591,14 +617,14 @@ extern "C" int gpk_paths_rollout(gpk_handle h, const double* X, int64_t N, int D
   return GPK_OK;
 }
 
-extern "C" int gpk_paths_step_multi(gpk_handle h, const double* X, int64_t N, int D, int B, const double* ls, const double* sf2,
-                                    const double* Omega, const double* phase, int64_t F, const double* Coef, int64_t ldc,
-                                    int64_t mstride, int S, const double* shift, const double* scale, const double* Xq,
-                                    double* out) {
+// the bodies of the batch entries; own_z: X is (B x N x D), every model's own basis points (the _z entries)
+static int paths_step_multi(gpk_handle h, bool own_z, const double* X, int64_t N, int D, int B, const double* ls, const double* sf2,
+                            const double* Omega, const double* phase, int64_t F, const double* Coef, int64_t ldc,
+                            int64_t mstride, int S, const double* shift, const double* scale, const double* Xq, double* out) {
   if (!h) return GPK_BAD_ARG;
   GPK_REQUIRE(h, X && Omega && phase && Coef && Xq && out, "paths_step_multi: null pointer");
   GPK_TRY(paths_check_multi(h, N, D, B, F, S, ldc, mstride));
-  PathsMultiModel m{X, (int)N, D, B, Omega, phase, (int)F, Coef, (long long)ldc, (long long)mstride, S, {}};
+  PathsMultiModel m{X, own_z, (int)N, D, B, Omega, phase, (int)F, Coef, (long long)ldc, (long long)mstride, S, {}};
   GPK_TRY(paths_fill_multi(h, D, B, ls, sf2, shift, scale, m.k));
   int rpc = 0, chunks = 0;
   paths_chunks(N + F, S, &rpc, &chunks);
@@ -611,11 +637,11 @@ extern "C" int gpk_paths_step_multi(gpk_handle h, const double* X, int64_t N, in
   return GPK_OK;
 }
 
-extern "C" int gpk_paths_rollout_multi(gpk_handle h, const double* X, int64_t N, int D, int B, const double* ls, const double* sf2,
-                                       const double* Omega, const double* phase, int64_t F, const double* Coef, int64_t ldc,
-                                       int64_t mstride, int S, const double* shift, const double* scale, int nx, const int* coord,
-                                       const double* in_shift, const double* in_scale, const double* x0, int x0_rows,
-                                       const double* U, int H, const double* lin, double* traj) {
+static int paths_rollout_multi(gpk_handle h, bool own_z, const double* X, int64_t N, int D, int B, const double* ls,
+                               const double* sf2, const double* Omega, const double* phase, int64_t F, const double* Coef,
+                               int64_t ldc, int64_t mstride, int S, const double* shift, const double* scale, int nx,
+                               const int* coord, const double* in_shift, const double* in_scale, const double* x0, int x0_rows,
+                               const double* U, int H, const double* lin, double* traj) {
   if (!h) return GPK_BAD_ARG;
   GPK_REQUIRE(h, X && Omega && phase && Coef && coord && x0 && lin && traj, "paths_rollout_multi: null pointer");
   GPK_TRY(paths_check_multi(h, N, D, B, F, S, ldc, mstride));
@@ -625,7 +651,7 @@ extern "C" int gpk_paths_rollout_multi(gpk_handle h, const double* X, int64_t N,
   GPK_REQUIRE(h, (in_shift == nullptr) == (in_scale == nullptr), "paths_rollout_multi: in_shift and in_scale go together");
   const int du = D - nx;
   GPK_REQUIRE(h, du == 0 || U, "paths_rollout_multi: null controls");
-  PathsMultiModel m{X, (int)N, D, B, Omega, phase, (int)F, Coef, (long long)ldc, (long long)mstride, S, {}};
+  PathsMultiModel m{X, own_z, (int)N, D, B, Omega, phase, (int)F, Coef, (long long)ldc, (long long)mstride, S, {}};
   GPK_TRY(paths_fill_multi(h, D, B, ls, sf2, shift, scale, m.k));
   for (int b = 0; b < B; ++b) {
     GPK_REQUIRE(h, coord[b] >= 0 && coord[b] < nx, "paths_rollout_multi: coord must be in [0, nx)");
@@ -673,5 +699,110 @@ extern "C" int gpk_paths_rollout_multi(gpk_handle h, const double* X, int64_t N,
   }
   GPK_CHECK_HIP(h, hipMemcpyAsync(traj, d_traj, sizeof(double) * n_traj, hipMemcpyDeviceToHost, h->stream));
   GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
+  return GPK_OK;
+}
+
+extern "C" int gpk_paths_step_multi(gpk_handle h, const double* X, int64_t N, int D, int B, const double* ls, const double* sf2,
+                                    const double* Omega, const double* phase, int64_t F, const double* Coef, int64_t ldc,
+                                    int64_t mstride, int S, const double* shift, const double* scale, const double* Xq,
+                                    double* out) {
+  return paths_step_multi(h, false, X, N, D, B, ls, sf2, Omega, phase, F, Coef, ldc, mstride, S, shift, scale, Xq, out);
+}
+
+extern "C" int gpk_paths_rollout_multi(gpk_handle h, const double* X, int64_t N, int D, int B, const double* ls, const double* sf2,
+                                       const double* Omega, const double* phase, int64_t F, const double* Coef, int64_t ldc,
+                                       int64_t mstride, int S, const double* shift, const double* scale, int nx, const int* coord,
+                                       const double* in_shift, const double* in_scale, const double* x0, int x0_rows,
+                                       const double* U, int H, const double* lin, double* traj) {
+  return paths_rollout_multi(h, false, X, N, D, B, ls, sf2, Omega, phase, F, Coef, ldc, mstride, S, shift, scale, nx, coord,
+                             in_shift, in_scale, x0, x0_rows, U, H, lin, traj);
+}
+
+// ---- the sparse models: every model has its own basis points (its inducing inputs) -------------------------------------------
+extern "C" int gpk_paths_step_multi_z(gpk_handle h, const double* Zs, int64_t N, int D, int B, const double* ls, const double* sf2,
+                                      const double* Omega, const double* phase, int64_t F, const double* Coef, int64_t ldc,
+                                      int64_t mstride, int S, const double* shift, const double* scale, const double* Xq,
+                                      double* out) {
+  return paths_step_multi(h, true, Zs, N, D, B, ls, sf2, Omega, phase, F, Coef, ldc, mstride, S, shift, scale, Xq, out);
+}
+
+extern "C" int gpk_paths_rollout_multi_z(gpk_handle h, const double* Zs, int64_t N, int D, int B, const double* ls,
+                                         const double* sf2, const double* Omega, const double* phase, int64_t F, const double* Coef,
+                                         int64_t ldc, int64_t mstride, int S, const double* shift, const double* scale, int nx,
+                                         const int* coord, const double* in_shift, const double* in_scale, const double* x0,
+                                         int x0_rows, const double* U, int H, const double* lin, double* traj) {
+  return paths_rollout_multi(h, true, Zs, N, D, B, ls, sf2, Omega, phase, F, Coef, ldc, mstride, S, shift, scale, nx, coord,
+                             in_shift, in_scale, x0, x0_rows, U, H, lin, traj);
+}
+
+namespace {
+
+// Wr (Fp x Cp) = W_rand[f][c], Xp (mp x Cp) = Xi[i][c]; zeros in the padding of both
+__global__ __launch_bounds__(256) void sparse_paths_pack_kernel(const double* __restrict__ Wrand, const double* __restrict__ Xi,
+                                                                long long F, long long Fp, long long m, long long C,
+                                                                long long Cp, double* __restrict__ Wr, double* __restrict__ Xp) {
+  const long long row = blockIdx.y;      // [0, Fp): Wr; [Fp, Fp + mp): Xp
+  const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (c >= Cp) return;
+  if (row < Fp) {
+    Wr[row * Cp + c] = (row < F && c < C) ? Wrand[row * C + c] : 0.0;
+  } else {
+    const long long i = row - Fp;
+    Xp[i * Cp + c] = (i < m && c < C) ? Xi[i * C + c] : 0.0;
+  }
+}
+
+// Coef rows [0, m): alpha_u[i][c % P] + R[i][c]; rows [m, m + F): scale W_rand
+__global__ __launch_bounds__(256) void sparse_paths_unpack_kernel(const double* __restrict__ R, const double* __restrict__ alpha,
+                                                                  const double* __restrict__ Wrand, long long m, long long C,
+                                                                  long long Cp, int P, double scale, double* __restrict__ Coef,
+                                                                  long long ldc) {
+  const long long row = blockIdx.y;      // [0, m + F)
+  const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (c >= C) return;
+  Coef[row * ldc + c] = row < m ? alpha[row * P + c % P] + R[row * Cp + c] : scale * Wrand[(row - m) * C + c];
+}
+
+}  // namespace
+
+// The set-up of a sparse model's path set (gpk_sparse_paths_prepare, gpk_sparse.hip, which takes the model apart): Z (m x D),
+// the inverse factors Wuu and WS (mp x mp, lower tiles) and alpha_u (m x P) are the assembled model's.
+int gpk_paths_prepare_two(gpk_handle h, const double* Z, int64_t m, int D, int P, double sf2, const double* Wuu, const double* WS,
+                          int64_t mp, const double* alpha, const double* Omega, const double* phase, int64_t F,
+                          const double* W_rand, const double* Xi, int S, double* Coef, int64_t ldc, double* Zdst) {
+  GPK_REQUIRE(h, Omega && phase && W_rand && Xi && Coef && Zdst, "sparse_paths_prepare: null pointer");
+  GPK_TRY(paths_check_shape(h, m, D, F, S, P, ldc));
+  const int64_t C = (int64_t)S * P, Cp = gpk_padded(C), Fp = gpk_padded(F);
+  GPK_REQUIRE(h, mp + Fp <= 65535, "sparse_paths_prepare: gpk_padded(m) + gpk_padded(F) must not exceed 65535");
+  const double scale = sqrt(2.0 * sf2 / (double)F);
+  // work area: Phi (mp x Fp), Wr (Fp x Cp), Xp, T, R (mp x Cp each)
+  void* ws = nullptr;
+  GPK_TRY(gpk_scratch(h, (size_t)(mp * Fp + Fp * Cp + 3 * mp * Cp) * sizeof(double), &ws));
+  double* Phi = (double*)ws;
+  double* Wr = Phi + mp * Fp;
+  double* Xp = Wr + Fp * Cp;
+  double* T = Xp + mp * Cp;
+  double* R = T + mp * Cp;
+  GPK_CHECK_HIP(h, hipMemcpyAsync(Zdst, Z, (size_t)m * D * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  GPK_TRY(gpk_rff_features(h, Z, m, D, Omega, phase, F, scale, Phi, Fp));
+  hipLaunchKernelGGL(sparse_paths_pack_kernel, dim3((unsigned)(Cp / 256 + (Cp % 256 != 0)), (unsigned)(Fp + mp)), dim3(256), 0,
+                     h->stream, W_rand, Xi, (long long)F, (long long)Fp, (long long)m, (long long)C, (long long)Cp, Wr, Xp);
+  GPK_LAUNCH_CHECK(h);
+  // R = Phi_Z Wr; T = Wuu R (Wuu lower: k < row-tile end); R = -Wuu^T T (k >= row-tile start); R += WS^T Xp (the same range).
+  // Phi_Z and Xp are zero in the padding rows and both factors are block diagonal there (the identity), so the padding rows
+  // of every product are exact zeros and nothing of the padding reaches a row below m.
+  GPK_TRY(gpk_gemm(h, GPK_F64, gemm_args(Phi, Fp, 0, Wr, Cp, 1, R, Cp, (int)mp, (int)Cp, (int)Fp, 1.0, 0.0)));
+  GemmArgs g1 = gemm_args(Wuu, mp, 0, R, Cp, 1, T, Cp, (int)mp, (int)Cp, (int)mp, 1.0, 0.0);
+  g1.ke0 = GPK_TILE; g1.ke_row = GPK_TILE; g1.heavy_first = 1;
+  GPK_TRY(gpk_gemm(h, GPK_F64, g1));
+  GemmArgs g2 = gemm_args(Wuu, mp, 1, T, Cp, 1, R, Cp, (int)mp, (int)Cp, (int)mp, -1.0, 0.0);
+  g2.kb_row = GPK_TILE;
+  GPK_TRY(gpk_gemm(h, GPK_F64, g2));
+  GemmArgs g3 = gemm_args(WS, mp, 1, Xp, Cp, 1, R, Cp, (int)mp, (int)Cp, (int)mp, 1.0, 1.0);
+  g3.kb_row = GPK_TILE;
+  GPK_TRY(gpk_gemm(h, GPK_F64, g3));
+  hipLaunchKernelGGL(sparse_paths_unpack_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)(m + F)), dim3(256), 0, h->stream,
+                     (const double*)R, alpha, W_rand, (long long)m, (long long)C, (long long)Cp, P, scale, Coef, (long long)ldc);
+  GPK_LAUNCH_CHECK(h);
   return GPK_OK;
 }

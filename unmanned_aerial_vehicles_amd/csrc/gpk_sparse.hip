@@ -1369,3 +1369,14 @@ extern "C" int gpk_sparse_import(gpk_handle h, const double* Z, int64_t m, int D
   s->n_rows = n_rows;
   return GPK_OK;
 }
+
+// The path set of the assembled model (K10, the sparse models): the model taken apart for gpk_paths_prepare_two (gpk_paths.hip).
+extern "C" int gpk_sparse_paths_prepare(gpk_handle h, const double* Omega, const double* phase, int64_t F, const double* W_rand,
+                                        const double* Xi, int S, double* Coef, int64_t ldc, double* Zdst) {
+  if (!h) return GPK_BAD_ARG;
+  gpk_sparse* s = h->sparse;
+  GPK_REQUIRE(h, s && s->finalized, "sparse_paths_prepare: no finalised sparse model (call gpk_sparse_finalize first)");
+  GPK_CHECK_HIP(h, hipSetDevice(h->device));
+  return gpk_paths_prepare_two(h, s->Z, s->m, s->D, s->P, s->sf2, s->Wuu, s->WS, s->mp, s->alpha, Omega, phase, F, W_rand, Xi, S,
+                               Coef, ldc, Zdst);
+}

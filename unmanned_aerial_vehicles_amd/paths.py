@@ -16,6 +16,10 @@ fallback.
 The per-axis batch (`BatchedARDGP`: B single-output models on shared inputs, each with its own kernel) has the same three
 surfaces in `BatchedPosteriorPaths`: one model-major coefficient matrix, set up by one `gpk_paths_prepare` per model, `step` for all
 models in two launches (`gpk_paths_step_multi`), a horizon in raw units in one call (`gpk_paths_rollout_multi`).
+
+The sparse models (`SparseGP`, `BatchedSparseGP`) have them too, conditioned on the inducing variables: `SparsePosteriorPaths` and
+`BatchedSparsePosteriorPaths` at the end of this file - the same coefficient matrix over m + F basis rows, set up by
+`gpk_sparse_paths_prepare`; the batch through `gpk_paths_step_multi_z` / `gpk_paths_rollout_multi_z` (basis points per model).
 """
 from __future__ import annotations
 
@@ -111,6 +115,7 @@ class PosteriorPaths:
         torch = _torch()
         be = dev.be
         self.gp, self._dev, self.be = gp, dev, be
+        self._X = dev.X
         self.N, self.D, self.P, self.F, self.S = N, D, P, F, S
         self.randomness = {"omega": omega, "phase": phase, "weights": weights, "eps": eps}
         self._ls = np.ascontiguousarray(dev.ls, dtype=np.float64).copy()
@@ -132,7 +137,7 @@ class PosteriorPaths:
 
     # ---- the model's side of every call: X, N, D, ls, sf2, Omega, phase, F, Coef, ldc, S, P, y_mean, y_std
     def _model_args(self):
-        return (_p(self._dev.X), self.N, self.D, _hp(self._ls), self._sf2, _p(self._omega), _p(self._phase), self.F,
+        return (_p(self._X), self.N, self.D, _hp(self._ls), self._sf2, _p(self._omega), _p(self._phase), self.F,
                 _p(self.coef), self.S * self.P, self.S, self.P, _hp(self._y_mean), _hp(self._y_std))
 
     def _squeeze(self, a):
@@ -146,9 +151,9 @@ class PosteriorPaths:
         M = X.shape[0]
         if M == 0:
             return np.empty((0, self.S) if self.P == 1 else (0, self.P, self.S))
-        be, dev = self.be, self._dev
+        be = self.be
         N, F, D, C = self.N, self.F, self.D, self.S * self.P
-        Np, Fp, Mp, Cp = dev.Np, padded(F), padded(M), padded(C)
+        Np, Fp, Mp, Cp = padded(N), padded(F), padded(M), padded(C)
         q = be.upload(X)
         # the two row blocks of Coef in the padded shape of the tile GEMM, zeros in the padding
         cv = torch.zeros((Np, Cp), dtype=torch.float64, device=be.device)
@@ -159,7 +164,7 @@ class PosteriorPaths:
         phi = be.empty((Mp, Fp), torch.float64)
         out = be.empty((Mp, Cp), torch.float64)
         with be.lock:
-            be.call("gpk_cross_gram_t", _lib.GPK_F64, _p(dev.X), N, _p(q), M, D, _hp(self._ls), self._sf2, _p(kt), Mp)
+            be.call("gpk_cross_gram_t", _lib.GPK_F64, _p(self._X), N, _p(q), M, D, _hp(self._ls), self._sf2, _p(kt), Mp)
             be.call("gpk_rff_features", _p(q), M, D, _p(self._omega), _p(self._phase), F, 1.0, _p(phi), Fp)
             # out = K*^T V (kt is stored training-row major: ta = 1) + Phi(Xq) W~
             be.call("gpk_gemm_tiles", _lib.GPK_F64, 1, 1, _p(kt), Mp, _p(cv), Cp, _p(out), Cp, Mp, Cp, Np, 1.0, 0.0, 0)
@@ -256,8 +261,14 @@ class BatchedPosteriorPaths:
     the same randomness.  The values are in the models' target units, y_mean_b + y_std_b f; `set_output_scaler` puts a further
     affine map per model behind them (a trainer's target scaler)."""
 
+    _STEP, _ROLLOUT = "gpk_paths_step_multi", "gpk_paths_rollout_multi"
+
     def __init__(self):
         raise TypeError("use BatchedARDGP.sample_paths or BatchedPosteriorPaths.from_randomness")
+
+    def _basis(self, b):
+        """The device basis points model b's kernel rows are formed against (here: the shared training inputs)."""
+        return self._X
 
     @classmethod
     def from_randomness(cls, bg, omega, phase, weights, eps):
@@ -376,7 +387,7 @@ class BatchedPosteriorPaths:
             phi = be.empty((Mp, Fp), torch.float64)
             out = be.empty((Mp, Sp), torch.float64)
             with be.lock:
-                be.call("gpk_cross_gram_t", _lib.GPK_F64, _p(self._X), N, _p(q), M, D, _hp(self._ls[b]), float(self._sf2[b]),
+                be.call("gpk_cross_gram_t", _lib.GPK_F64, _p(self._basis(b)), N, _p(q), M, D, _hp(self._ls[b]), float(self._sf2[b]),
                         _p(kt), Mp)
                 be.call("gpk_rff_features", _p(q), M, D, _p(self._omega[b]), _p(self._phase[b]), F, 1.0, _p(phi), Fp)
                 be.call("gpk_gemm_tiles", _lib.GPK_F64, 1, 1, _p(kt), Mp, _p(cv), Sp, _p(out), Sp, Mp, Sp, Np, 1.0, 0.0, 0)
@@ -393,7 +404,7 @@ class BatchedPosteriorPaths:
         be = self.be
         q = be.upload(Xs)
         out = be.empty((self.S, self.B), torch.float64)
-        be.call("gpk_paths_step_multi", *self._model_args(), _p(q), _p(out))
+        be.call(self._STEP, *self._model_args(), _p(q), _p(out))
         return out.cpu().numpy()
 
     def rollout(self, x0, U, lin, coord=None, in_scaler=None):
@@ -443,7 +454,188 @@ class BatchedPosteriorPaths:
                 raise ValueError("in_scale must be non-zero")
         import ctypes as C
         traj = np.empty((H + 1, S, nx))
-        self.be.call("gpk_paths_rollout_multi", *self._model_args(), nx, coord.ctypes.data_as(C.POINTER(C.c_int)),
+        self.be.call(self._ROLLOUT, *self._model_args(), nx, coord.ctypes.data_as(C.POINTER(C.c_int)),
                      _hp(in_shift), _hp(in_scale), _hp(x0), 1 if x0.ndim == 1 else S, _hp(U) if D > nx else None, H, _hp(lin),
                      _hp(traj))
         return traj
+
+
+# ---- the sparse models: paths conditioned on the inducing variables --------------------------------------------------------------
+#     f_s(x) = phi(x)^T w_s + k_u(x)^T v_s,   v_s = alpha_u + WS^T xi_s - Wuu^T (Wuu Phi_Z w_s),   xi_s ~ N(0, I_m),  w_s ~ N(0, I_F)
+# (include/gpk.h, K10 "the sparse models"): the coefficient matrix of the exact model with N := m and X := Z, so `step`, `rollout`
+# and `__call__` are the exact classes'; only the set-up (`gpk_sparse_paths_prepare`) and, for the batch, the basis points per
+# model (`gpk_paths_step_multi_z`, `gpk_paths_rollout_multi_z`) differ.
+def draw_sparse_path_randomness(rng, m, D, F, S, P, ls):
+    """The random numbers of a sparse model's path set, pure NumPy: dict(omega (F, D), phase (F,), weights (F, S, P),
+    xi (m, S, P)).
+
+    Draw order, from `rng` (a `numpy.random.RandomState` or `Generator`) - `draw_path_randomness`'s with unit noise:
+      1. z = rng.standard_normal((F, D));   omega = z / ls           (ls: scalar or (D,))
+      2. phase = rng.uniform(0, 2 pi, F)
+      3. weights = rng.standard_normal((F, S, P))
+      4. xi = rng.standard_normal((m, S, P))"""
+    r = draw_path_randomness(rng, m, D, F, S, P, ls, 1.0)
+    r["xi"] = r.pop("eps")
+    return r
+
+
+def draw_sparse_batch_path_randomness(rng, m, D, F, S, ls):
+    """The random numbers of a sparse batch path set, pure NumPy: dict(omega (B, F, D), phase (B, F), weights (B, F, S),
+    xi (B, m, S)) for B models with length-scales ls (B, D).
+
+    Draw order, from the one `rng`: model 0, 1, ..., B - 1 in turn, each `draw_sparse_path_randomness(rng, m, D, F, S, 1, ls[b])`,
+    so that model 0's numbers are the single-model draw's."""
+    ls = np.array(ls, dtype=np.float64, ndmin=2)
+    B = ls.shape[0]
+    if ls.ndim != 2 or ls.shape[1] != int(D):
+        raise ValueError(f"ls must be (B, {int(D)})")
+    if not 1 <= B <= MAX_BATCH:
+        raise ValueError(f"the number of models must be in [1, {MAX_BATCH}] (got {B})")
+    rs = [draw_sparse_path_randomness(rng, m, D, F, S, 1, ls[b]) for b in range(B)]
+    return {"omega": np.stack([r["omega"] for r in rs]), "phase": np.stack([r["phase"] for r in rs]),
+            "weights": np.stack([r["weights"][:, :, 0] for r in rs]), "xi": np.stack([r["xi"][:, :, 0] for r in rs])}
+
+
+def check_sparse_randomness(m, D, P, omega, phase, weights, xi, batch=None):
+    """Shapes, limits and finiteness of a sparse path set's randomness as ValueErrors, before any launch; returns the four
+    arrays as contiguous float64 and (F, S).  batch=B: the batch layout (B leading, no output axis)."""
+    omega = np.ascontiguousarray(omega, dtype=np.float64)
+    phase = np.ascontiguousarray(phase, dtype=np.float64)
+    weights = np.ascontiguousarray(weights, dtype=np.float64)
+    xi = np.ascontiguousarray(xi, dtype=np.float64)
+    if batch is None:
+        if omega.ndim != 2 or omega.shape[1] != D:
+            raise ValueError(f"omega must be (F, {D})")
+        F = omega.shape[0]
+        if phase.shape != (F,):
+            raise ValueError(f"phase must be ({F},)")
+        if weights.ndim == 2 and P == 1:
+            weights = weights[:, :, None]
+        if xi.ndim == 2 and P == 1:
+            xi = xi[:, :, None]
+        if weights.ndim != 3 or weights.shape[0] != F or weights.shape[2] != P:
+            raise ValueError(f"weights must be ({F}, S, {P})")
+        S = weights.shape[1]
+        if xi.shape != (m, S, P):
+            raise ValueError(f"xi must be ({m}, {S}, {P})")
+        check_path_shape(D, P, S, F)
+    else:
+        B = batch
+        if omega.ndim != 3 or omega.shape[0] != B or omega.shape[2] != D:
+            raise ValueError(f"omega must be ({B}, F, {D})")
+        F = omega.shape[1]
+        if phase.shape != (B, F):
+            raise ValueError(f"phase must be ({B}, {F})")
+        if weights.ndim != 3 or weights.shape[:2] != (B, F):
+            raise ValueError(f"weights must be ({B}, {F}, S)")
+        S = weights.shape[2]
+        if xi.shape != (B, m, S):
+            raise ValueError(f"xi must be ({B}, {m}, {S})")
+        check_batch_path_shape(B, D, S, F)
+    if padded(m) + padded(F) > 65535:
+        raise ValueError("gpk_padded(m) + gpk_padded(F) must not exceed 65535")
+    for name, a in (("omega", omega), ("phase", phase), ("weights", weights), ("xi", xi)):
+        if not np.isfinite(a).all():
+            raise ValueError(f"{name} contains NaN or infinity.")
+    return omega, phase, weights, xi, F, S
+
+
+class SparsePosteriorPaths(PosteriorPaths):
+    """S posterior function draws of a `SparseGP`, resident on its GPU: `PosteriorPaths` over the m inducing inputs - `__call__`,
+    `step`, `rollout`, `.coef` ((m + F, S P), column s P + p) as there; `.randomness` = dict(omega, phase, weights, xi).  The set
+    is a snapshot: it keeps its own copy of Z and stays the same function when the model takes further rows."""
+
+    def __init__(self):
+        raise TypeError("use SparseGP.sample_paths or SparsePosteriorPaths.from_randomness")
+
+    @classmethod
+    def from_randomness(cls, sp, omega, phase, weights, xi):
+        """The path set of the sparse model `sp` (assembled here if it is not; without rows: the prior) from arrays of the
+        caller's own: omega (F, D), phase (F,), weights (F, S, P) (or (F, S) for one output) = the w_s, xi (m, S, P) (or (m, S))
+        = the xi_s."""
+        m, D = sp.inducing_.shape
+        P = sp.n_outputs_
+        omega, phase, weights, xi, F, S = check_sparse_randomness(m, D, P, omega, phase, weights, xi)
+        sp._ensure()
+        comp = sp.kernel_.components()
+        self = object.__new__(cls)
+        torch = _torch()
+        be = sp._backend()
+        self.gp, self._dev, self.be = sp, None, be
+        self.N, self.D, self.P, self.F, self.S = m, D, P, F, S
+        self.randomness = {"omega": omega, "phase": phase, "weights": weights, "xi": xi}
+        self._ls = np.ascontiguousarray(comp.ls_vector(D), dtype=np.float64).copy()
+        self._sf2 = float(comp.sf2)
+        self._y_mean, self._y_std = sp._ym.copy(), sp._ys.copy()
+        C = S * P
+        with be.lock:
+            self._omega = be.upload(omega)
+            self._phase = be.upload(phase)
+            self._X = be.empty((m, D), torch.float64)
+            self.coef = be.empty((m + F, C), torch.float64)
+            w_d = be.upload(weights.reshape(F, C))
+            x_d = be.upload(xi.reshape(m, C))
+            be.call("gpk_sparse_paths_prepare", _p(self._omega), _p(self._phase), F, _p(w_d), _p(x_d), S, _p(self.coef), C,
+                    _p(self._X))
+            be.sync()       # (w_d and x_d are released here: the set-up is not the hot path)
+        return self
+
+
+class BatchedSparsePosteriorPaths(BatchedPosteriorPaths):
+    """S posterior function draws of every model of a `BatchedSparseGP` (B single-output sparse models of equal m and D, each
+    with its own kernel and inducing inputs): `BatchedPosteriorPaths` with N := m and the basis points per model - `__call__`
+    (M, B, S), `step` (S, B) in two launches (`gpk_paths_step_multi_z`), `rollout` one call per horizon
+    (`gpk_paths_rollout_multi_z`), `set_output_scaler`, `.coef` model-major.  Column b of `step` has the bits of
+    `SparsePosteriorPaths.from_randomness(models[b], ...)` on the same randomness."""
+
+    _STEP, _ROLLOUT = "gpk_paths_step_multi_z", "gpk_paths_rollout_multi_z"
+
+    def __init__(self):
+        raise TypeError("use BatchedSparseGP.sample_paths or BatchedSparsePosteriorPaths.from_randomness")
+
+    def _basis(self, b):
+        return self._X[b]
+
+    @classmethod
+    def from_randomness(cls, bg, omega, phase, weights, xi):
+        """The path set of the sparse batch `bg` from arrays of the caller's own: omega (B, F, D), phase (B, F), weights
+        (B, F, S), xi (B, m, S).  The set-up is one `gpk_sparse_paths_prepare` per model on that model's own handle, pointed at
+        its column block and its slice of the basis points."""
+        import ctypes as C
+        ms = list(bg.models)
+        B = len(ms)
+        m, D = ms[0].inducing_.shape
+        omega, phase, weights, xi, F, S = check_sparse_randomness(m, D, 1, omega, phase, weights, xi, batch=B)
+        bes, _ = bg._ensure()
+        self = object.__new__(cls)
+        torch = _torch()
+        be = bes[0]
+        if any(b.device_index != be.device_index for b in bes):
+            raise RuntimeError("the models of a batch must be on one device")
+        comps = [mm.kernel_.components() for mm in ms]
+        self.bg, self.be, self._devs = bg, be, None
+        self.N, self.D, self.B, self.F, self.S = m, D, B, F, S
+        self.mstride = (S + 7) // 8 * 8          # every model's run of columns starts 64-byte aligned
+        self.ldc = B * self.mstride
+        self.randomness = {"omega": omega, "phase": phase, "weights": weights, "xi": xi}
+        self._ls = np.ascontiguousarray(np.stack([np.asarray(c.ls_vector(D), dtype=np.float64) for c in comps]))
+        self._sf2 = np.ascontiguousarray([float(c.sf2) for c in comps], dtype=np.float64)
+        self._y_mean = np.ascontiguousarray([float(mm._ym[0]) for mm in ms], dtype=np.float64)
+        self._y_std = np.ascontiguousarray([float(mm._ys[0]) for mm in ms], dtype=np.float64)
+        self._shift, self._scale = self._y_mean.copy(), self._y_std.copy()
+        with torch.cuda.device(be.device):
+            torch.cuda.synchronize()              # the models may have been assembled on their own streams
+            self._omega = be.upload(omega)
+            self._phase = be.upload(phase)
+            self._X = be.empty((B, m, D), torch.float64)
+            self.coef = be.empty((m + F, self.ldc), torch.float64)
+            for b, mb in enumerate(bes):
+                with mb.lock:
+                    w_d = mb.upload(weights[b])
+                    x_d = mb.upload(xi[b])
+                    block = C.c_void_p(self.coef.data_ptr() + 8 * b * self.mstride)
+                    mb.call("gpk_sparse_paths_prepare", _p(self._omega[b]), _p(self._phase[b]), F, _p(w_d), _p(x_d), S, block,
+                            self.ldc, _p(self._X[b]))
+                    mb.sync()       # (w_d and x_d are released here: the set-up is not the hot path)
+            torch.cuda.synchronize()
+        return self

@@ -252,7 +252,8 @@ class SimpleQuadrotorGP:
 
         in one call for the horizon (`PosteriorPaths.rollout`).  state (6,); U_guess (4, N).  Returns (R, 6, N + 1), the layout
         `build_gp_residuals` / `linearize_gp_residuals` take as X_guess.  The path set (n_rollouts, n_features, random_state)
-        is drawn once and cached on the object until `train_gp` / `load_model`: the same functions from call to call.
+        is drawn once and cached on the object until `train_gp` / `load_model` - or, for a `SparseGP` as `gp_model`
+        (`SparseGP.sample_paths`), until that model takes rows or is retrained: the same functions from call to call.
         Untrained, or on any failure (printed): the nominal trajectory repeated R times - it never raises into the control
         loop."""
         state = np.asarray(state, dtype=float).reshape(-1)[:6]
@@ -266,8 +267,9 @@ class SimpleQuadrotorGP:
         if not self.is_trained:
             return fallback
         try:
+            # (a path set is a snapshot: a sparse model that has taken rows since it was drawn has a new revision)
             key = (R, int(n_features), random_state if isinstance(random_state, (int, np.integer)) else id(random_state),
-                   id(self.gp_model))
+                   id(self.gp_model), getattr(self.gp_model, "revision_", None))
             cached = getattr(self, "_paths", None)      # (an object pickled before the attribute existed has none)
             if cached is None or cached[0] != key:
                 self._paths = (key, self.gp_model.sample_paths(R, n_features, random_state))

@@ -190,11 +190,13 @@ class SparseGP:
             return self
         self._backend().call("gpk_sparse_update", _ptr(X), _ptr(y2), X.shape[0])
         self._final, self._held = False, False
+        self._touch()
         return self
 
     def fit(self, X, y):
         """Forgets the rows seen so far, then `partial_fit(X, y)`."""
         self._live, self._final, self._P, self._state = False, False, None, None
+        self._touch()
         return self.partial_fit(X, y)
 
     # ------------------------------------------------------------------ training
@@ -206,6 +208,7 @@ class SparseGP:
         if X.shape[0] == 0:
             raise ValueError("hold needs at least one row")
         self._live, self._final, self._P, self._state = False, False, None, None
+        self._touch()
         self._y_1d = y_1d
         self._begin(y2.shape[1])
         self._backend().call("gpk_sparse_hold", _ptr(X), _ptr(y2), X.shape[0])
@@ -248,6 +251,7 @@ class SparseGP:
             self.kernel_ = kern
             if Z is not None:
                 self.inducing_ = Z
+            self._touch()
             if rc == _lib.GPK_NOT_PD:
                 self._final = False
                 if gZ is not None:
@@ -464,6 +468,32 @@ class SparseGP:
         y_samples = [rng.multivariate_normal(y_mean[:, t], y_cov[..., t], n_samples).T[:, np.newaxis]
                      for t in range(y_mean.shape[1])]
         return np.hstack(y_samples)
+
+    def sample_paths(self, n_paths, n_features=1024, random_state=0):
+        """`n_paths` posterior function draws as explicit functions, conditioned on the inducing variables
+        (`paths.SparsePosteriorPaths`; `GaussianProcessRegressor.sample_paths` for the sparse model): evaluated anywhere, call
+        after call, each the same function - `step` two launches over m + n_features basis rows however many rows were fitted, a
+        closed-loop `rollout` one call per horizon.  Every output draws its own numbers; the draw order is
+        `paths.draw_sparse_path_randomness`'s; random_state as in `sample_y`.  A model without rows yields draws of the prior
+        conditioned on nothing, as `predict` yields the prior.  The set is a snapshot of the model as it is now
+        (`revision_`)."""
+        from .gpr import _rng_from
+        from .paths import SparsePosteriorPaths, check_path_shape, draw_sparse_path_randomness
+        m, D = self.inducing_.shape
+        P = self.n_outputs_
+        check_path_shape(D, P, int(n_paths), int(n_features))
+        ls = self.kernel_.components().ls_vector(D)
+        r = draw_sparse_path_randomness(_rng_from(random_state), m, D, int(n_features), int(n_paths), P, ls)
+        return SparsePosteriorPaths.from_randomness(self, **r)
+
+    @property
+    def revision_(self):
+        """A counter that moves whenever the served model may have changed (rows taken, refitted, trained, hyper-parameters or
+        inducing inputs moved): what a cached path set of this model is keyed by."""
+        return self.__dict__.get("_rev", 0)
+
+    def _touch(self):
+        self._rev = self.__dict__.get("_rev", 0) + 1
 
     def bound(self):
         """The collapsed lower bound on the log-marginal likelihood of the rows seen so far, in normalised-target units (the

@@ -145,6 +145,25 @@ class BatchedSparseGP:
         mean, cov = self.predict(Xq, return_cov=True)
         return cholesky_draws(mean, cov, n_samples, random_state)
 
+    def sample_paths(self, n_paths, n_features=1024, random_state=0):
+        """`n_paths` posterior function draws of EVERY model as explicit functions (`paths.BatchedSparsePosteriorPaths`), each
+        conditioned on its model's own inducing variables: evaluated anywhere, call after call, all models in one call - `step`
+        two launches (`gpk_paths_step_multi_z`), a closed-loop `rollout` one call per horizon.  The draw order is
+        `paths.draw_sparse_batch_path_randomness`'s (model by model from the one generator); random_state as in `sample_y`.
+        The set is a snapshot of the models as they are now (`revision_`)."""
+        from .gpr import _rng_from
+        from .paths import BatchedSparsePosteriorPaths, check_batch_path_shape, draw_sparse_batch_path_randomness
+        m, D = self.models[0].inducing_.shape
+        check_batch_path_shape(len(self.models), D, int(n_paths), int(n_features))
+        ls = np.stack([mm.kernel_.components().ls_vector(D) for mm in self.models])
+        r = draw_sparse_batch_path_randomness(_rng_from(random_state), m, D, int(n_features), int(n_paths), ls)
+        return BatchedSparsePosteriorPaths.from_randomness(self, **r)
+
+    @property
+    def revision_(self):
+        """The models' revisions (`SparseGP.revision_`): what a cached path set of the batch is keyed by."""
+        return tuple(mm.revision_ for mm in self.models)
+
     # ------------------------------------------------------------------ pickling: the models' own state
     def __getstate__(self):
         return {"models": self.models}

@@ -514,13 +514,14 @@ class PreTrainedGP:
 
             x_{k+1} = x_k + dt [v_k, a_k] + sum_i e_i (sy_i.mean_ + sy_i.scale_ f_{i,r}(([x_k, u_k] - sx.mean_) / sx.scale_))
 
-        in one call for the horizon (`BatchedPosteriorPaths.rollout` on the fused `BatchedARDGP`, its shared input scaler and
-        each model's target scaler).  state (6,); U_guess (4, N).  Returns (R, 6, N + 1), the layout `linearize_residuals`
-        takes as X_guess.  A residual without a model leaves its coordinate nominal.  The path set (n_rollouts, n_features,
-        random_state) is drawn once and cached on the object until `load_dict`: the same functions from call to call.  Not
-        loaded, models that cannot be fused into an exact batch (a sparse batch, a single model, different inputs or scalers),
-        or any failure: the reason is printed and the nominal trajectory is returned R times - it never raises into the
-        control loop."""
+        in one call for the horizon (`BatchedPosteriorPaths.rollout` on the fused `BatchedARDGP`, or
+        `BatchedSparsePosteriorPaths.rollout` on the fused `BatchedSparseGP` of a `sparsify`-written file; the shared input
+        scaler and each model's target scaler).  state (6,); U_guess (4, N).  Returns (R, 6, N + 1), the layout
+        `linearize_residuals` takes as X_guess.  A residual without a model leaves its coordinate nominal.  The path set
+        (n_rollouts, n_features, random_state) is drawn once and cached on the object until `load_dict` - or until a sparse
+        model takes rows or is retrained (a path set is a snapshot) - the same functions from call to call.  Not loaded, models
+        that cannot be fused into a batch (a single model, different inputs or scalers), or any failure: the reason is printed
+        and the nominal trajectory is returned R times - it never raises into the control loop."""
         U_guess = np.asarray(U_guess, dtype=float)
         state = np.asarray(state, dtype=float).reshape(-1)[:6]
         R, N = int(n_rollouts), U_guess.shape[1]
@@ -532,12 +533,13 @@ class PreTrainedGP:
         try:
             if not self.is_loaded:
                 raise RuntimeError("no models are loaded")
-            from .batched import BatchedARDGP
             fused = self._fused()
-            if not fused or not isinstance(fused[0], BatchedARDGP):
-                raise RuntimeError("the loaded models are not served as one exact per-axis batch")
+            if not fused:
+                raise RuntimeError("the loaded models are not served as one per-axis batch")
             bg, names = fused
-            key = (R, int(n_features), random_state if isinstance(random_state, (int, np.integer)) else id(random_state), id(bg))
+            # (a path set is a snapshot: sparse models that have taken rows since it was drawn have a new revision)
+            key = (R, int(n_features), random_state if isinstance(random_state, (int, np.integer)) else id(random_state), id(bg),
+                   getattr(bg, "revision_", None))
             cached = getattr(self, "_axis_paths", None)     # (an object pickled before the attribute existed has none)
             if cached is None or cached[0] != key:
                 paths = bg.sample_paths(R, n_features, random_state)
