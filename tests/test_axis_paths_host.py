@@ -8,7 +8,8 @@ touched.
 3. tests/golden/make_golden_axis_paths.py regenerates tests/golden/axis_paths_ref.npz bit for bit, and the file holds what the
    GPU tests read.
 4. Error growth: on every rollout case a 1e-12 relative perturbation of x0 grows by less than 100x over the horizon in the NumPy
-   form, so a kernel-value difference of 1e-12 stays two orders under the 1e-8 bar of the GPU tests."""
+   form, so a kernel-value difference of 1e-12 stays two orders under the 1e-8 bar of the GPU tests; on the two generated
+   problems without controls (three stages) by less than 1e3 - measured: at most 7.3x."""
 import ctypes
 import os
 import pickle
@@ -19,7 +20,8 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT
-from test_gpu_axis_paths import CASE_NAMES, ROLLOUT_CASES, axis_paths_numpy_form, load_case
+from test_gpu_axis_paths import (CASE_NAMES, NO_CONTROLS_KINDS, ROLLOUT_CASES, axis_paths_numpy_form, load_case,
+                                 no_controls_problem)
 from test_gpu_paths import paths_numpy_form
 
 NEW_SYMBOLS = ("gpk_paths_step_multi", "gpk_paths_rollout_multi")
@@ -175,3 +177,15 @@ def test_rollout_error_growth_leaves_room(name):
     growth = np.max(np.abs(pert[-1] - base[-1])) / np.max(np.abs(pert[0] - base[0]))
     print(f"case {name}, NumPy form: a 1e-12 relative perturbation of x0 grows {growth:.2f}x over {len(c['U'])} stages")
     assert growth < 100.0       # (two orders under what would bring a 1e-12 kernel-value difference near the 1e-8 bar)
+
+
+@pytest.mark.parametrize("kind", NO_CONTROLS_KINDS)
+def test_rollout_without_controls_error_growth_leaves_room(kind):
+    """The problem of test_rollout_without_controls (tests/test_gpu_axis_paths.py): three stages, no controls."""
+    p, form = no_controls_problem(kind)
+    for tag, x0 in (("S rows", p["x0"]), ("one row", p["x0"][0])):
+        base = form.rollout(x0, p["U"], p["lin"])
+        pert = form.rollout(x0 * (1.0 + 1e-12), p["U"], p["lin"])
+        growth = np.max(np.abs(pert[-1] - base[-1])) / np.max(np.abs(pert[0] - base[0]))
+        print(f"{kind}, no controls, x0 as {tag}, NumPy form: a 1e-12 relative perturbation of x0 grows {growth:.2f}x over 3 stages")
+        assert growth < 1e3     # (a 1e-12 kernel-value difference then stays an order under the 1e-8 bar)

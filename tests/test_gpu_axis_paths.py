@@ -11,7 +11,9 @@ WhiteKernel and distinct length-scales, signal variances and noise levels per mo
 Inputs: tests/golden/axis_paths_ref.npz, cases (N, D, F, S, B) = a (120, 4, 48, 5, 2): nothing a multiple of 64; b (130, 4, 64,
 70, 3): two path blocks, mstride = 72 > S; csv (200, 10, 96, 7, 6): CSV fixture rows behind an input scaler, target scalers,
 nx = 6, H = 25; gap (96, 10, 32, 9, 4): nx = 6, coord = (0, 2, 3, 5), H = 5; one (128, 3, 16, 1, 1); eight (64, 2, 16, 65, 8):
-the largest B (no rollout: B > D).  Error growth of `rollout` in the NumPy form: tests/test_axis_paths_host.py."""
+the largest B (no rollout: B > D).  Generated here, seeded (`no_controls_problem`): (40, 2, 8, 3) with a state of D = 2 coordinates,
+so a rollout without controls - for the batch and for the single-model `PosteriorPaths`.  Error growth of `rollout` in the NumPy
+form: tests/test_axis_paths_host.py."""
 import os
 
 import numpy as np
@@ -389,3 +391,48 @@ def test_the_c_entries_refuse_every_limit_before_any_launch():
     be.sync()
     assert np.isnan(out.cpu().numpy()).all() and np.isnan(traj).all(), "a refused call wrote its output"
     check("step after the refusals", p.step(c["Xs"]), c["step"])
+
+
+# ---- 7. a rollout without controls: D equal to the state width, U (H, 0) - null at the C boundary ------------------------------------
+NO_CONTROLS_KINDS = ("single", "batch")
+
+
+def no_controls_problem(kind):
+    """Seeded, the smallest shapes: N = 40, D = 2, F = 8, S = 3, H = 3, a state of two coordinates - P = 2 outputs of one model
+    (`single`) or B = 2 models (`batch`), nx = 2 - a WhiteKernel of 0.1, `lin` of order 0.1.  Returns the arrays and the NumPy
+    form; its error growth: test_rollout_without_controls_error_growth_leaves_room (tests/test_axis_paths_host.py)."""
+    from unmanned_aerial_vehicles_amd import draw_batch_path_randomness, draw_path_randomness
+    N, D, F, S, H = 40, 2, 8, 3, 3
+    rng = np.random.RandomState(31)
+    X = rng.standard_normal((N, D))
+    Y = np.stack([np.sin(X[:, 0]) + 0.5 * X[:, 1], np.cos(X[:, 1]) - 0.3 * X[:, 0]], axis=1) + 0.1 * rng.standard_normal((N, 2))
+    p = dict(X=X, Y=Y, x0=0.3 * rng.standard_normal((S, 2)), U=np.zeros((H, 0)), lin=0.1 * rng.standard_normal((2, D)),
+             ls=np.array([[1.0, 1.4], [0.8, 1.2]]), hyper=np.array([[1.0, 0.1, 1e-4], [1.5, 0.1, 1e-4]]))
+    if kind == "single":
+        sf2, noise, alpha = p["hyper"][0]
+        p["r"] = draw_path_randomness(np.random.RandomState(32), N, D, F, S, 2, p["ls"][0], noise + alpha)
+        form = paths_numpy_form(X, Y, p["ls"][0], sf2, noise, alpha, **p["r"])
+    else:
+        p["r"] = draw_batch_path_randomness(np.random.RandomState(32), N, D, F, S, p["ls"], p["hyper"][:, 1] + p["hyper"][:, 2])
+        form = axis_paths_numpy_form(X, Y, p["ls"], p["hyper"], **p["r"])
+    return p, form
+
+
+@pytest.mark.parametrize("kind", NO_CONTROLS_KINDS)
+def test_rollout_without_controls(kind):
+    """Both instantiations of the library's rollout driver with D - nx = 0: x0 as S rows and as one row."""
+    from unmanned_aerial_vehicles_amd import (RBF, BatchedPosteriorPaths, ConstantKernel, GaussianProcessRegressor, PosteriorPaths,
+                                              WhiteKernel)
+    p, form = no_controls_problem(kind)
+    if kind == "single":
+        sf2, noise, alpha = p["hyper"][0]
+        gp = GaussianProcessRegressor(ConstantKernel(sf2) * RBF(p["ls"][0]) + WhiteKernel(noise), alpha=alpha, normalize_y=True,
+                                      optimizer=None).fit(p["X"], p["Y"])
+        paths = PosteriorPaths.from_randomness(gp, **p["r"])
+    else:
+        paths = BatchedPosteriorPaths.from_randomness(fit_batch(p), **p["r"])
+    assert paths.D == 2 and paths.S == 3
+    for tag, x0 in (("S rows", p["x0"]), ("one row", p["x0"][0])):
+        got = paths.rollout(x0, p["U"], p["lin"])
+        assert got.shape == (4, 3, 2) and (got[0] == x0).all()
+        check(f"{kind}, no controls, x0 as {tag}: rollout", got, form.rollout(x0, p["U"], p["lin"]))

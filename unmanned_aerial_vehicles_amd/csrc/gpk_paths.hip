@@ -6,8 +6,9 @@
 //     out = y_mean[p] + y_std[p] sum_j b_j(x) Coef[j][s P + p]
 //
 //   rff_kernel            Phi[n][f] = scale cos(omega_f . x_n + phase_f) in the padded shape of the tile GEMM (zeros in the padding)
-//   paths_pack_kernel     R = Yn (x) 1_S - Eps and the padded copy of W_rand (the operands of the three products of gpk_paths_prepare)
-//   paths_unpack_kernel   Coef from V = K^-1 R and scale W_rand
+//   paths_pack_kernel     the operands of a set-up's products in the padded shape: W_rand and one more row block, copied (the
+//                         sparse model's Xi) or as R = Yn (x) 1_S - Eps (the exact model)
+//   paths_unpack_kernel   Coef from V (the exact model: V = K^-1 R; the sparse model: alpha_u + V) and scale W_rand
 //   paths_partial_kernel  the hot path: grid (blocks of 64 paths) x (row chunks).  A workgroup is four waves; lane l of a wave owns
 //                         path 64 block + l while the basis value b_j(xq_s) is formed - once per (s, j), D fused multiply-adds and one
 //                         exp or cos - and leaves it in the wave's own LDS slots; then lane l owns COLUMNS l, l + 64, ... of the
@@ -20,9 +21,9 @@
 //   paths_partial_multi_kernel / paths_combine_multi_kernel / paths_advance_multi_kernel
 //                         the same two launches for the per-axis batch: B single-output models on shared inputs, each with its own
 //                         kernel, Coef model-major (see there); with OWNZ every model has its own basis points (the sparse batch)
-//   sparse_paths_pack_kernel / sparse_paths_unpack_kernel
-//                         the set-up of a sparse model's path set (gpk_paths_prepare_two): N := m, X := Z, rows [0, m) hold
-//                         v = alpha_u + WS^T xi - Wuu^T (Wuu Phi_Z w) from the two inverse factors of the assembled model
+// Host side: paths_setup is the frame of both set-ups (gpk_paths_prepare; gpk_paths_prepare_two for a sparse model: N := m,
+// X := Z, rows [0, m) hold v = alpha_u + WS^T xi - Wuu^T (Wuu Phi_Z w) from the two inverse factors of the assembled model), and
+// paths_rollout_run drives every rollout: one device block, two uploads, H stages of two launches, one download.
 // The chunk count depends on (N + F, S) only.  The launch is bound by streaming Coef: (N + F) S P 8 bytes per stage.
 #include "gpk_internal.h"
 #include "gpk_math.h"
@@ -57,29 +58,36 @@ __global__ __launch_bounds__(256) void rff_kernel(const double* __restrict__ X, 
   Phi[n * ldp + f] = v;
 }
 
-// R (Np x Cp) = Yn[n][c % P] - Eps[n][c], Wr (Fp x Cp) = W_rand[f][c]; zeros in the padding of both
-__global__ __launch_bounds__(256) void paths_pack_kernel(const double* __restrict__ Yn, const double* __restrict__ Eps,
-                                                         const double* __restrict__ Wrand, long long N, long long Np, long long F,
-                                                         long long C, long long Cp, int P, double* __restrict__ R,
+// Ap (np x Cp) = A[i][c], or with Yn: Yn[i][c % P] - A[i][c]; Wr (Fp x Cp) = W_rand[f][c]; zeros in the padding of both
+__global__ __launch_bounds__(256) void paths_pack_kernel(const double* __restrict__ Yn, const double* __restrict__ A,
+                                                         const double* __restrict__ Wrand, long long n, long long np, long long F,
+                                                         long long C, long long Cp, int P, double* __restrict__ Ap,
                                                          double* __restrict__ Wr) {
-  const long long row = blockIdx.y;      // [0, Np): R; [Np, Np + Fp): Wr
+  const long long row = blockIdx.y;      // [0, np): Ap; [np, np + Fp): Wr
   const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
   if (c >= Cp) return;
-  if (row < Np) {
-    R[row * Cp + c] = (row < N && c < C) ? Yn[row * P + c % P] - Eps[row * C + c] : 0.0;
+  if (row < np) {
+    double v = 0.0;
+    if (row < n && c < C) v = Yn ? Yn[row * P + c % P] - A[row * C + c] : A[row * C + c];
+    Ap[row * Cp + c] = v;
   } else {
-    const long long f = row - Np;
+    const long long f = row - np;
     Wr[f * Cp + c] = (f < F && c < C) ? Wrand[f * C + c] : 0.0;
   }
 }
 
-__global__ __launch_bounds__(256) void paths_unpack_kernel(const double* __restrict__ V, const double* __restrict__ Wrand,
-                                                           long long N, long long F, long long C, long long Cp, double scale,
-                                                           double* __restrict__ Coef, long long ldc) {
-  const long long row = blockIdx.y;      // [0, N + F)
+// Coef rows [0, n): V[i][c], or with alpha: alpha[i][c % P] + V[i][c]; rows [n, n + F): scale W_rand
+__global__ __launch_bounds__(256) void paths_unpack_kernel(const double* __restrict__ V, const double* __restrict__ alpha,
+                                                           const double* __restrict__ Wrand, long long n, long long C,
+                                                           long long Cp, int P, double scale, double* __restrict__ Coef,
+                                                           long long ldc) {
+  const long long row = blockIdx.y;      // [0, n + F)
   const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
   if (c >= C) return;
-  Coef[row * ldc + c] = row < N ? V[row * Cp + c] : scale * Wrand[(row - N) * C + c];
+  double v;
+  if (row >= n) v = scale * Wrand[(row - n) * C + c];
+  else v = alpha ? alpha[row * P + c % P] + V[row * Cp + c] : V[row * Cp + c];
+  Coef[row * ldc + c] = v;
 }
 
 // The query of path s: its first dx coordinates from xs (S x dx), the others - shared by all paths - from u (D - dx).
@@ -217,15 +225,29 @@ int paths_fill_k(gpk_handle h, int D, int P, const double* ls, const double* y_m
   return GPK_OK;
 }
 
-// the shape limits every entry of the family shares
-int paths_check_shape(gpk_handle h, int64_t N, int D, int64_t F, int S, int P, int64_t ldc) {
+constexpr int PATHS_MAX_B = 8;      // models of a per-axis batch
+
+// the shape limits every entry of the family shares; `outputs`: the entry's own count (P or B), refused with `outputs_msg`
+int paths_check_shape(gpk_handle h, int64_t N, int D, int64_t F, int S, bool outputs_ok, const char* outputs_msg) {
   GPK_REQUIRE(h, h->batch == 1, "paths: not available in batched mode");
   GPK_REQUIRE(h, N >= 1 && N < (1ll << 30), "paths: N must be at least 1");
   GPK_REQUIRE(h, D >= 1 && D <= GPK_MAX_D_PREDICT, "paths: D must be in [1, 16]");
-  GPK_REQUIRE(h, P >= 1 && P <= GPK_MAX_P, "paths: P must be in [1, 16]");
+  GPK_REQUIRE(h, outputs_ok, outputs_msg);
   GPK_REQUIRE(h, S >= 1 && S <= PATHS_MAX_S, "paths: S must be in [1, 4096]");
   GPK_REQUIRE(h, F >= 1 && F <= PATHS_MAX_F, "paths: F must be in [1, 16384]");
+  return GPK_OK;
+}
+
+int paths_check_single(gpk_handle h, int64_t N, int D, int64_t F, int S, int P, int64_t ldc) {
+  GPK_TRY(paths_check_shape(h, N, D, F, S, P >= 1 && P <= GPK_MAX_P, "paths: P must be in [1, 16]"));
   GPK_REQUIRE(h, ldc >= (int64_t)S * P, "paths: ldc must be >= S * P");
+  return GPK_OK;
+}
+
+int paths_check_multi(gpk_handle h, int64_t N, int D, int B, int64_t F, int S, int64_t ldc, int64_t mstride) {
+  GPK_TRY(paths_check_shape(h, N, D, F, S, B >= 1 && B <= PATHS_MAX_B, "paths: B must be in [1, 8]"));
+  GPK_REQUIRE(h, mstride >= S, "paths: mstride must be >= S");
+  GPK_REQUIRE(h, ldc >= (int64_t)B * mstride, "paths: ldc must be >= B * mstride");
   return GPK_OK;
 }
 
@@ -276,8 +298,6 @@ bool all_finite(const double* a, long long n) {
 // difference q_d - x_jd and the load of x_j are formed once per (s, j) for all B models; everything after that is the
 // single-model kernel's arithmetic in the single-model kernel's order (chunking, rows rb + r PW + w with r ascending, waves in
 // wave order, chunks in chunk order), so column b of the result has the bits of gpk_paths_step on model b's own path set.
-constexpr int PATHS_MAX_B = 8;
-
 struct PathsMultiK {
   double inv_ls[PATHS_MAX_B][16];
   double sf2[PATHS_MAX_B], shift[PATHS_MAX_B], scale[PATHS_MAX_B];
@@ -437,18 +457,6 @@ struct PathsMultiModel {
   PathsMultiK k;
 };
 
-int paths_check_multi(gpk_handle h, int64_t N, int D, int B, int64_t F, int S, int64_t ldc, int64_t mstride) {
-  GPK_REQUIRE(h, h->batch == 1, "paths: not available in batched mode");
-  GPK_REQUIRE(h, N >= 1 && N < (1ll << 30), "paths: N must be at least 1");
-  GPK_REQUIRE(h, D >= 1 && D <= GPK_MAX_D_PREDICT, "paths: D must be in [1, 16]");
-  GPK_REQUIRE(h, B >= 1 && B <= PATHS_MAX_B, "paths: B must be in [1, 8]");
-  GPK_REQUIRE(h, S >= 1 && S <= PATHS_MAX_S, "paths: S must be in [1, 4096]");
-  GPK_REQUIRE(h, F >= 1 && F <= PATHS_MAX_F, "paths: F must be in [1, 16384]");
-  GPK_REQUIRE(h, mstride >= S, "paths: mstride must be >= S");
-  GPK_REQUIRE(h, ldc >= (int64_t)B * mstride, "paths: ldc must be >= B * mstride");
-  return GPK_OK;
-}
-
 int paths_fill_multi(gpk_handle h, int D, int B, const double* ls, const double* sf2, const double* shift, const double* scale,
                      PathsMultiK& k) {
   GPK_REQUIRE(h, ls && sf2 && shift && scale, "paths: null length-scale, sf2, shift or scale array");
@@ -498,6 +506,82 @@ int paths_partial_multi(gpk_handle h, const PathsMultiModel& m, const double* xs
   return GPK_OK;
 }
 
+// One closed-loop horizon, every kind of path set: the refusals the rollouts share, then the device block - the trajectory
+// ((H + 1) x S x w), then [stage 0 | U | lin] as they come from the host in one copy (stage 0 is the trajectory's first slot) and
+// the chunks' shares (n_partial doubles) - two uploads, H stages, one download, one synchronisation.  w: the state width, at most
+// D (the entry's own check); stage(xk, uk, partial, d_lin, x_next) launches one stage; `name` heads the messages.
+template <class Stage>
+int paths_rollout_run(gpk_handle h, const char* name, int w, int D, int S, const double* x0, int x0_rows, const double* U, int H,
+                      const double* lin, double* traj, size_t n_partial, Stage stage) {
+  const std::string who = std::string(name) + ": ";
+  GPK_REQUIRE(h, H >= 1 && H <= PATHS_MAX_H, who + "H must be in [1, 256]");
+  GPK_REQUIRE(h, x0_rows == 1 || x0_rows == S, who + "x0 must have 1 or S rows");
+  const int du = D - w;
+  GPK_REQUIRE(h, du == 0 || U, who + "null controls");
+  GPK_REQUIRE(h, all_finite(x0, (long long)x0_rows * w) && all_finite(lin, (long long)w * D) &&
+                     (du == 0 || all_finite(U, (long long)H * du)),
+              who + "x0, U and lin must not contain NaN or infinity");
+  const size_t C = (size_t)S * w;
+  const size_t n_traj = (size_t)(H + 1) * C, n_u = (size_t)H * du, n_lin = (size_t)w * D;
+  void* ws = nullptr;
+  GPK_TRY(gpk_scratch(h, (n_traj + n_u + n_lin + n_partial) * sizeof(double), &ws));
+  double* d_traj = (double*)ws;
+  double* d_u = d_traj + n_traj;
+  double* d_lin = d_u + n_u;
+  double* partial = d_lin + n_lin;
+  std::vector<double> host(C + n_u + n_lin);
+  for (int s = 0; s < S; ++s) memcpy(host.data() + (size_t)s * w, x0 + (x0_rows == 1 ? 0 : (size_t)s * w), sizeof(double) * w);
+  if (n_u) memcpy(host.data() + C, U, sizeof(double) * n_u);
+  memcpy(host.data() + C + n_u, lin, sizeof(double) * n_lin);
+  GPK_CHECK_HIP(h, hipMemcpyAsync(d_traj, host.data(), sizeof(double) * C, hipMemcpyHostToDevice, h->stream));
+  GPK_CHECK_HIP(h, hipMemcpyAsync(d_u, host.data() + C, sizeof(double) * (n_u + n_lin), hipMemcpyHostToDevice, h->stream));
+  for (int k = 0; k < H; ++k)
+    GPK_TRY(stage(d_traj + (size_t)k * C, d_u + (size_t)k * du, partial, (const double*)d_lin, d_traj + (size_t)(k + 1) * C));
+  GPK_CHECK_HIP(h, hipMemcpyAsync(traj, d_traj, sizeof(double) * n_traj, hipMemcpyDeviceToHost, h->stream));
+  GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
+  return GPK_OK;
+}
+
+// dst (np x Cp) = sign W^T (W src) through a lower inverse factor W (np x np tiles, row stride ldw), as gpk_potrs_inv: T = W src
+// (W lower: k < row-tile end), dst = sign W^T T (k >= row-tile start).  The identity in W's padding keeps zero rows of src zero.
+int paths_inverse_product(gpk_handle h, const double* W, int64_t ldw, int64_t np, int64_t Cp, const double* src, double* T,
+                          double* dst, double sign) {
+  GemmArgs g1 = gemm_args(W, ldw, 0, src, Cp, 1, T, Cp, (int)np, (int)Cp, (int)np, 1.0, 0.0);
+  g1.ke0 = GPK_TILE; g1.ke_row = GPK_TILE; g1.heavy_first = 1;
+  GPK_TRY(gpk_gemm(h, GPK_F64, g1));
+  GemmArgs g2 = gemm_args(W, ldw, 1, T, Cp, 1, dst, Cp, (int)np, (int)Cp, (int)np, sign, 0.0);
+  g2.kb_row = GPK_TILE;
+  return gpk_gemm(h, GPK_F64, g2);
+}
+
+// The frame of both set-ups, over n basis points X (np = gpk_padded(n) rows in every padded shape).  Work area: Phi (np x Fp),
+// Wr (Fp x Cp), then `areas` matrices M[0], M[1], ... of np x Cp.  Phi = the features of X, Wr = W_rand and M[0] = A (or
+// Yn (x) 1_S - A) are filled; products(Phi, Wr, M, Cp, Fp) runs the entry's own GEMMs and leaves V in M[v_area]; Coef rows
+// [0, n) = V (or alpha + V), rows [n, n + F) = scale W_rand.
+template <class Products>
+int paths_setup(gpk_handle h, const char* too_tall, const double* X, int64_t n, int64_t np, int D, int P, double sf2,
+                const double* Omega, const double* phase, int64_t F, const double* W_rand, const double* Yn, const double* A,
+                const double* alpha, int S, double* Coef, int64_t ldc, int areas, int v_area, Products products) {
+  const int64_t C = (int64_t)S * P, Cp = gpk_padded(C), Fp = gpk_padded(F);
+  GPK_REQUIRE(h, np + Fp <= 65535, too_tall);
+  const double scale = sqrt(2.0 * sf2 / (double)F);
+  void* ws = nullptr;
+  GPK_TRY(gpk_scratch(h, (size_t)(np * Fp + Fp * Cp + areas * np * Cp) * sizeof(double), &ws));
+  double* Phi = (double*)ws;
+  double* Wr = Phi + np * Fp;
+  double* M = Wr + Fp * Cp;
+  GPK_TRY(gpk_rff_features(h, X, n, D, Omega, phase, F, scale, Phi, Fp));
+  hipLaunchKernelGGL(paths_pack_kernel, dim3((unsigned)(Cp / 256 + (Cp % 256 != 0)), (unsigned)(np + Fp)), dim3(256), 0, h->stream,
+                     Yn, A, W_rand, (long long)n, (long long)np, (long long)F, (long long)C, (long long)Cp, P, M, Wr);
+  GPK_LAUNCH_CHECK(h);
+  GPK_TRY(products(Phi, Wr, M, Cp, Fp));
+  hipLaunchKernelGGL(paths_unpack_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)(n + F)), dim3(256), 0, h->stream,
+                     (const double*)(M + v_area * np * Cp), alpha, W_rand, (long long)n, (long long)C, (long long)Cp, P, scale, Coef,
+                     (long long)ldc);
+  GPK_LAUNCH_CHECK(h);
+  return GPK_OK;
+}
+
 }  // namespace
 
 extern "C" int gpk_rff_features(gpk_handle h, const double* X, int64_t N, int D, const double* Omega, const double* phase,
@@ -525,37 +609,16 @@ extern "C" int gpk_paths_prepare(gpk_handle h, const double* X, int64_t N, int D
                                  const double* W_rand, const double* Eps, int S, double* Coef, int64_t ldc) {
   if (!h) return GPK_BAD_ARG;
   GPK_REQUIRE(h, X && Yn && W && Omega && phase && W_rand && Eps && Coef, "paths_prepare: null pointer");
-  GPK_TRY(paths_check_shape(h, N, D, F, S, P, ldc));
+  GPK_TRY(paths_check_single(h, N, D, F, S, P, ldc));
   GPK_REQUIRE(h, Np == gpk_padded(N) && ldw >= Np, "paths_prepare: Np must equal gpk_padded(N) and ldw >= Np");
   GPK_REQUIRE(h, sf2 > 0.0, "paths_prepare: sf2 must be positive");
-  const int64_t C = (int64_t)S * P, Cp = gpk_padded(C), Fp = gpk_padded(F);
-  GPK_REQUIRE(h, Np + Fp <= 65535, "paths_prepare: gpk_padded(N) + gpk_padded(F) must not exceed 65535");
-  const double scale = sqrt(2.0 * sf2 / (double)F);
-  // work area: Phi (Np x Fp), Wr (Fp x Cp), R (Np x Cp), T (Np x Cp)
-  void* ws = nullptr;
-  GPK_TRY(gpk_scratch(h, (size_t)(Np * Fp + Fp * Cp + 2 * Np * Cp) * sizeof(double), &ws));
-  double* Phi = (double*)ws;
-  double* Wr = Phi + Np * Fp;
-  double* R = Wr + Fp * Cp;
-  double* T = R + Np * Cp;
-  GPK_TRY(gpk_rff_features(h, X, N, D, Omega, phase, F, scale, Phi, Fp));
-  hipLaunchKernelGGL(paths_pack_kernel, dim3((unsigned)(Cp / 256 + (Cp % 256 != 0)), (unsigned)(Np + Fp)), dim3(256), 0, h->stream,
-                     Yn, Eps, W_rand, (long long)N, (long long)Np, (long long)F, (long long)C, (long long)Cp, P, R, Wr);
-  GPK_LAUNCH_CHECK(h);
-  // R <- R - Phi Wr
-  GPK_TRY(gpk_gemm(h, GPK_F64, gemm_args(Phi, Fp, 0, Wr, Cp, 1, R, Cp, (int)Np, (int)Cp, (int)Fp, -1.0, 1.0)));
-  // V = K^-1 R = W^T (W R) through the inverse factor, as gpk_potrs_inv: T = W R (W lower: k < row-tile end), R <- W^T T
-  // (k >= row-tile start); the identity in W's padding keeps the zero rows of R zero
-  GemmArgs g1 = gemm_args(W, ldw, 0, R, Cp, 1, T, Cp, (int)Np, (int)Cp, (int)Np, 1.0, 0.0);
-  g1.ke0 = GPK_TILE; g1.ke_row = GPK_TILE; g1.heavy_first = 1;
-  GPK_TRY(gpk_gemm(h, GPK_F64, g1));
-  GemmArgs g2 = gemm_args(W, ldw, 1, T, Cp, 1, R, Cp, (int)Np, (int)Cp, (int)Np, 1.0, 0.0);
-  g2.kb_row = GPK_TILE;
-  GPK_TRY(gpk_gemm(h, GPK_F64, g2));
-  hipLaunchKernelGGL(paths_unpack_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)(N + F)), dim3(256), 0, h->stream,
-                     (const double*)R, W_rand, (long long)N, (long long)F, (long long)C, (long long)Cp, scale, Coef, (long long)ldc);
-  GPK_LAUNCH_CHECK(h);
-  return GPK_OK;
+  // areas: R = Yn (x) 1_S - Eps, T.  R <- R - Phi Wr, then V = K^-1 R = W^T (W R), in place
+  return paths_setup(h, "paths_prepare: gpk_padded(N) + gpk_padded(F) must not exceed 65535", X, N, Np, D, P, sf2, Omega, phase, F,
+                     W_rand, Yn, Eps, nullptr, S, Coef, ldc, 2, 0,
+                     [&](const double* Phi, const double* Wr, double* R, int64_t Cp, int64_t Fp) -> int {
+                       GPK_TRY(gpk_gemm(h, GPK_F64, gemm_args(Phi, Fp, 0, Wr, Cp, 1, R, Cp, (int)Np, (int)Cp, (int)Fp, -1.0, 1.0)));
+                       return paths_inverse_product(h, W, ldw, Np, Cp, R, R + Np * Cp, R, 1.0);
+                     });
 }
 
 extern "C" int gpk_paths_step(gpk_handle h, const double* X, int64_t N, int D, const double* ls, double sf2, const double* Omega,
@@ -563,7 +626,7 @@ extern "C" int gpk_paths_step(gpk_handle h, const double* X, int64_t N, int D, c
                               const double* y_std, const double* Xq, double* out) {
   if (!h) return GPK_BAD_ARG;
   GPK_REQUIRE(h, X && Omega && phase && Coef && Xq && out, "paths_step: null pointer");
-  GPK_TRY(paths_check_shape(h, N, D, F, S, P, ldc));
+  GPK_TRY(paths_check_single(h, N, D, F, S, P, ldc));
   PathsModel m{X, (int)N, D, sf2, Omega, phase, (int)F, Coef, (long long)ldc, S, P, {}};
   GPK_TRY(paths_fill_k(h, D, P, ls, y_mean, y_std, m.k));
   int rpc = 0, chunks = 0;
@@ -579,42 +642,16 @@ extern "C" int gpk_paths_rollout(gpk_handle h, const double* X, int64_t N, int D
                                  const double* lin, double* traj) {
   if (!h) return GPK_BAD_ARG;
   GPK_REQUIRE(h, X && Omega && phase && Coef && x0 && lin && traj, "paths_rollout: null pointer");
-  GPK_TRY(paths_check_shape(h, N, D, F, S, P, ldc));
-  GPK_REQUIRE(h, H >= 1 && H <= PATHS_MAX_H, "paths_rollout: H must be in [1, 256]");
+  GPK_TRY(paths_check_single(h, N, D, F, S, P, ldc));
   GPK_REQUIRE(h, P <= D, "paths_rollout: the state dimension P must not exceed D");
-  GPK_REQUIRE(h, x0_rows == 1 || x0_rows == S, "paths_rollout: x0 must have 1 or S rows");
-  const int du = D - P;
-  GPK_REQUIRE(h, du == 0 || U, "paths_rollout: null controls");
-  GPK_REQUIRE(h, all_finite(x0, (long long)x0_rows * P) && all_finite(lin, (long long)P * D) &&
-                     (du == 0 || all_finite(U, (long long)H * du)),
-              "paths_rollout: x0, U and lin must not contain NaN or infinity");
   PathsModel m{X, (int)N, D, sf2, Omega, phase, (int)F, Coef, (long long)ldc, S, P, {}};
   GPK_TRY(paths_fill_k(h, D, P, ls, y_mean, y_std, m.k));
   int rpc = 0, chunks = 0;
   paths_chunks(N + F, S, &rpc, &chunks);
-  const size_t C = (size_t)S * P;
-  // device block: the trajectory ((H + 1) x S x P), then [stage 0 | U | lin] as they come from the host in one copy - stage 0
-  // is the trajectory's first slot - and the chunks' shares
-  const size_t n_traj = (size_t)(H + 1) * C, n_u = (size_t)H * du, n_lin = (size_t)P * D;
-  void* ws = nullptr;
-  GPK_TRY(gpk_scratch(h, (n_traj + n_u + n_lin + (size_t)chunks * C) * sizeof(double), &ws));
-  double* d_traj = (double*)ws;
-  double* d_u = d_traj + n_traj;
-  double* d_lin = d_u + n_u;
-  double* partial = d_lin + n_lin;
-  std::vector<double> stage(C + n_u + n_lin);
-  for (int s = 0; s < S; ++s) memcpy(stage.data() + (size_t)s * P, x0 + (x0_rows == 1 ? 0 : (size_t)s * P), sizeof(double) * P);
-  if (n_u) memcpy(stage.data() + C, U, sizeof(double) * n_u);
-  memcpy(stage.data() + C + n_u, lin, sizeof(double) * n_lin);
-  GPK_CHECK_HIP(h, hipMemcpyAsync(d_traj, stage.data(), sizeof(double) * C, hipMemcpyHostToDevice, h->stream));
-  GPK_CHECK_HIP(h, hipMemcpyAsync(d_u, stage.data() + C, sizeof(double) * (n_u + n_lin), hipMemcpyHostToDevice, h->stream));
-  for (int k = 0; k < H; ++k) {
-    const double* xk = d_traj + (size_t)k * C;
-    GPK_TRY(paths_stage(h, m, xk, P, d_u + (size_t)k * du, rpc, chunks, partial, nullptr, d_lin, d_traj + (size_t)(k + 1) * C));
-  }
-  GPK_CHECK_HIP(h, hipMemcpyAsync(traj, d_traj, sizeof(double) * n_traj, hipMemcpyDeviceToHost, h->stream));
-  GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
-  return GPK_OK;
+  return paths_rollout_run(h, "paths_rollout", P, D, S, x0, x0_rows, U, H, lin, traj, (size_t)chunks * S * P,
+                           [&](const double* xk, const double* uk, double* partial, const double* d_lin, double* x_next) {
+                             return paths_stage(h, m, xk, P, uk, rpc, chunks, partial, nullptr, d_lin, x_next);
+                           });
 }
 
 // the bodies of the batch entries; own_z: X is (B x N x D), every model's own basis points (the _z entries)
@@ -645,12 +682,8 @@ static int paths_rollout_multi(gpk_handle h, bool own_z, const double* X, int64_
   if (!h) return GPK_BAD_ARG;
   GPK_REQUIRE(h, X && Omega && phase && Coef && coord && x0 && lin && traj, "paths_rollout_multi: null pointer");
   GPK_TRY(paths_check_multi(h, N, D, B, F, S, ldc, mstride));
-  GPK_REQUIRE(h, H >= 1 && H <= PATHS_MAX_H, "paths_rollout_multi: H must be in [1, 256]");
   GPK_REQUIRE(h, nx >= B && nx <= D, "paths_rollout_multi: the state dimension nx must be in [B, D]");
-  GPK_REQUIRE(h, x0_rows == 1 || x0_rows == S, "paths_rollout_multi: x0 must have 1 or S rows");
   GPK_REQUIRE(h, (in_shift == nullptr) == (in_scale == nullptr), "paths_rollout_multi: in_shift and in_scale go together");
-  const int du = D - nx;
-  GPK_REQUIRE(h, du == 0 || U, "paths_rollout_multi: null controls");
   PathsMultiModel m{X, own_z, (int)N, D, B, Omega, phase, (int)F, Coef, (long long)ldc, (long long)mstride, S, {}};
   GPK_TRY(paths_fill_multi(h, D, B, ls, sf2, shift, scale, m.k));
   for (int b = 0; b < B; ++b) {
@@ -658,11 +691,9 @@ static int paths_rollout_multi(gpk_handle h, bool own_z, const double* X, int64_
     GPK_REQUIRE(h, m.k.model_of[coord[b]] < 0, "paths_rollout_multi: coord must be distinct");
     m.k.model_of[coord[b]] = b;
   }
-  GPK_REQUIRE(h, all_finite(x0, (long long)x0_rows * nx) && all_finite(lin, (long long)nx * D) &&
-                     (du == 0 || all_finite(U, (long long)H * du)) &&
-                     (!in_shift || (all_finite(in_shift, D) && all_finite(in_scale, D))),
-              "paths_rollout_multi: x0, U, lin and the input scaler must not contain NaN or infinity");
   if (in_shift) {
+    GPK_REQUIRE(h, all_finite(in_shift, D) && all_finite(in_scale, D),
+                "paths_rollout_multi: the input scaler must not contain NaN or infinity");
     for (int d = 0; d < D; ++d) {
       GPK_REQUIRE(h, in_scale[d] != 0.0, "paths_rollout_multi: in_scale must be non-zero");
       m.k.in_shift[d] = in_shift[d];
@@ -672,34 +703,15 @@ static int paths_rollout_multi(gpk_handle h, bool own_z, const double* X, int64_
   }
   int rpc = 0, chunks = 0;
   paths_chunks(N + F, S, &rpc, &chunks);
-  const size_t C = (size_t)S * nx;
-  // device block: the trajectory ((H + 1) x S x nx), then [stage 0 | U | lin] as they come from the host in one copy - stage 0
-  // is the trajectory's first slot - and the chunks' shares
-  const size_t n_traj = (size_t)(H + 1) * C, n_u = (size_t)H * du, n_lin = (size_t)nx * D;
-  void* ws = nullptr;
-  GPK_TRY(gpk_scratch(h, (n_traj + n_u + n_lin + (size_t)chunks * S * B) * sizeof(double), &ws));
-  double* d_traj = (double*)ws;
-  double* d_u = d_traj + n_traj;
-  double* d_lin = d_u + n_u;
-  double* partial = d_lin + n_lin;
-  std::vector<double> stage(C + n_u + n_lin);
-  for (int s = 0; s < S; ++s) memcpy(stage.data() + (size_t)s * nx, x0 + (x0_rows == 1 ? 0 : (size_t)s * nx), sizeof(double) * nx);
-  if (n_u) memcpy(stage.data() + C, U, sizeof(double) * n_u);
-  memcpy(stage.data() + C + n_u, lin, sizeof(double) * n_lin);
-  GPK_CHECK_HIP(h, hipMemcpyAsync(d_traj, stage.data(), sizeof(double) * C, hipMemcpyHostToDevice, h->stream));
-  GPK_CHECK_HIP(h, hipMemcpyAsync(d_u, stage.data() + C, sizeof(double) * (n_u + n_lin), hipMemcpyHostToDevice, h->stream));
   const dim3 agrid((unsigned)((S + 255) / 256), (unsigned)nx);
-  for (int st = 0; st < H; ++st) {
-    const double* xk = d_traj + (size_t)st * C;
-    const double* uk = d_u + (size_t)st * du;
-    GPK_TRY(paths_partial_multi(h, m, xk, nx, uk, rpc, chunks, partial));
-    hipLaunchKernelGGL(paths_advance_multi_kernel, agrid, dim3(256), 0, h->stream, (const double*)partial, chunks, S, B, nx, D,
-                       m.k, xk, uk, (const double*)d_lin, d_traj + (size_t)(st + 1) * C);
-    GPK_LAUNCH_CHECK(h);
-  }
-  GPK_CHECK_HIP(h, hipMemcpyAsync(traj, d_traj, sizeof(double) * n_traj, hipMemcpyDeviceToHost, h->stream));
-  GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
-  return GPK_OK;
+  return paths_rollout_run(h, "paths_rollout_multi", nx, D, S, x0, x0_rows, U, H, lin, traj, (size_t)chunks * S * B,
+                           [&](const double* xk, const double* uk, double* partial, const double* d_lin, double* x_next) -> int {
+                             GPK_TRY(paths_partial_multi(h, m, xk, nx, uk, rpc, chunks, partial));
+                             hipLaunchKernelGGL(paths_advance_multi_kernel, agrid, dim3(256), 0, h->stream, (const double*)partial,
+                                                chunks, S, B, nx, D, m.k, xk, uk, d_lin, x_next);
+                             GPK_LAUNCH_CHECK(h);
+                             return GPK_OK;
+                           });
 }
 
 extern "C" int gpk_paths_step_multi(gpk_handle h, const double* X, int64_t N, int D, int B, const double* ls, const double* sf2,
@@ -735,74 +747,26 @@ extern "C" int gpk_paths_rollout_multi_z(gpk_handle h, const double* Zs, int64_t
                              in_shift, in_scale, x0, x0_rows, U, H, lin, traj);
 }
 
-namespace {
-
-// Wr (Fp x Cp) = W_rand[f][c], Xp (mp x Cp) = Xi[i][c]; zeros in the padding of both
-__global__ __launch_bounds__(256) void sparse_paths_pack_kernel(const double* __restrict__ Wrand, const double* __restrict__ Xi,
-                                                                long long F, long long Fp, long long m, long long C,
-                                                                long long Cp, double* __restrict__ Wr, double* __restrict__ Xp) {
-  const long long row = blockIdx.y;      // [0, Fp): Wr; [Fp, Fp + mp): Xp
-  const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (c >= Cp) return;
-  if (row < Fp) {
-    Wr[row * Cp + c] = (row < F && c < C) ? Wrand[row * C + c] : 0.0;
-  } else {
-    const long long i = row - Fp;
-    Xp[i * Cp + c] = (i < m && c < C) ? Xi[i * C + c] : 0.0;
-  }
-}
-
-// Coef rows [0, m): alpha_u[i][c % P] + R[i][c]; rows [m, m + F): scale W_rand
-__global__ __launch_bounds__(256) void sparse_paths_unpack_kernel(const double* __restrict__ R, const double* __restrict__ alpha,
-                                                                  const double* __restrict__ Wrand, long long m, long long C,
-                                                                  long long Cp, int P, double scale, double* __restrict__ Coef,
-                                                                  long long ldc) {
-  const long long row = blockIdx.y;      // [0, m + F)
-  const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (c >= C) return;
-  Coef[row * ldc + c] = row < m ? alpha[row * P + c % P] + R[row * Cp + c] : scale * Wrand[(row - m) * C + c];
-}
-
-}  // namespace
-
 // The set-up of a sparse model's path set (gpk_sparse_paths_prepare, gpk_sparse.hip, which takes the model apart): Z (m x D),
 // the inverse factors Wuu and WS (mp x mp, lower tiles) and alpha_u (m x P) are the assembled model's.
 int gpk_paths_prepare_two(gpk_handle h, const double* Z, int64_t m, int D, int P, double sf2, const double* Wuu, const double* WS,
                           int64_t mp, const double* alpha, const double* Omega, const double* phase, int64_t F,
                           const double* W_rand, const double* Xi, int S, double* Coef, int64_t ldc, double* Zdst) {
   GPK_REQUIRE(h, Omega && phase && W_rand && Xi && Coef && Zdst, "sparse_paths_prepare: null pointer");
-  GPK_TRY(paths_check_shape(h, m, D, F, S, P, ldc));
-  const int64_t C = (int64_t)S * P, Cp = gpk_padded(C), Fp = gpk_padded(F);
-  GPK_REQUIRE(h, mp + Fp <= 65535, "sparse_paths_prepare: gpk_padded(m) + gpk_padded(F) must not exceed 65535");
-  const double scale = sqrt(2.0 * sf2 / (double)F);
-  // work area: Phi (mp x Fp), Wr (Fp x Cp), Xp, T, R (mp x Cp each)
-  void* ws = nullptr;
-  GPK_TRY(gpk_scratch(h, (size_t)(mp * Fp + Fp * Cp + 3 * mp * Cp) * sizeof(double), &ws));
-  double* Phi = (double*)ws;
-  double* Wr = Phi + mp * Fp;
-  double* Xp = Wr + Fp * Cp;
-  double* T = Xp + mp * Cp;
-  double* R = T + mp * Cp;
-  GPK_CHECK_HIP(h, hipMemcpyAsync(Zdst, Z, (size_t)m * D * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-  GPK_TRY(gpk_rff_features(h, Z, m, D, Omega, phase, F, scale, Phi, Fp));
-  hipLaunchKernelGGL(sparse_paths_pack_kernel, dim3((unsigned)(Cp / 256 + (Cp % 256 != 0)), (unsigned)(Fp + mp)), dim3(256), 0,
-                     h->stream, W_rand, Xi, (long long)F, (long long)Fp, (long long)m, (long long)C, (long long)Cp, Wr, Xp);
-  GPK_LAUNCH_CHECK(h);
-  // R = Phi_Z Wr; T = Wuu R (Wuu lower: k < row-tile end); R = -Wuu^T T (k >= row-tile start); R += WS^T Xp (the same range).
-  // Phi_Z and Xp are zero in the padding rows and both factors are block diagonal there (the identity), so the padding rows
-  // of every product are exact zeros and nothing of the padding reaches a row below m.
-  GPK_TRY(gpk_gemm(h, GPK_F64, gemm_args(Phi, Fp, 0, Wr, Cp, 1, R, Cp, (int)mp, (int)Cp, (int)Fp, 1.0, 0.0)));
-  GemmArgs g1 = gemm_args(Wuu, mp, 0, R, Cp, 1, T, Cp, (int)mp, (int)Cp, (int)mp, 1.0, 0.0);
-  g1.ke0 = GPK_TILE; g1.ke_row = GPK_TILE; g1.heavy_first = 1;
-  GPK_TRY(gpk_gemm(h, GPK_F64, g1));
-  GemmArgs g2 = gemm_args(Wuu, mp, 1, T, Cp, 1, R, Cp, (int)mp, (int)Cp, (int)mp, -1.0, 0.0);
-  g2.kb_row = GPK_TILE;
-  GPK_TRY(gpk_gemm(h, GPK_F64, g2));
-  GemmArgs g3 = gemm_args(WS, mp, 1, Xp, Cp, 1, R, Cp, (int)mp, (int)Cp, (int)mp, 1.0, 1.0);
-  g3.kb_row = GPK_TILE;
-  GPK_TRY(gpk_gemm(h, GPK_F64, g3));
-  hipLaunchKernelGGL(sparse_paths_unpack_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)(m + F)), dim3(256), 0, h->stream,
-                     (const double*)R, alpha, W_rand, (long long)m, (long long)C, (long long)Cp, P, scale, Coef, (long long)ldc);
-  GPK_LAUNCH_CHECK(h);
-  return GPK_OK;
+  GPK_TRY(paths_check_single(h, m, D, F, S, P, ldc));
+  // areas: Xp = Xi, T, R.  R = Phi_Z Wr; R <- -Wuu^T (Wuu R); R += WS^T Xp (k >= row-tile start).  Phi_Z and Xp are zero in the
+  // padding rows and both factors are block diagonal there (the identity), so the padding rows of every product are exact zeros
+  // and nothing of the padding reaches a row below m.
+  return paths_setup(h, "sparse_paths_prepare: gpk_padded(m) + gpk_padded(F) must not exceed 65535", Z, m, mp, D, P, sf2, Omega,
+                     phase, F, W_rand, nullptr, Xi, alpha, S, Coef, ldc, 3, 2,
+                     [&](const double* Phi, const double* Wr, double* Xp, int64_t Cp, int64_t Fp) -> int {
+                       double* T = Xp + mp * Cp;
+                       double* R = T + mp * Cp;
+                       GPK_CHECK_HIP(h, hipMemcpyAsync(Zdst, Z, (size_t)m * D * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+                       GPK_TRY(gpk_gemm(h, GPK_F64, gemm_args(Phi, Fp, 0, Wr, Cp, 1, R, Cp, (int)mp, (int)Cp, (int)Fp, 1.0, 0.0)));
+                       GPK_TRY(paths_inverse_product(h, Wuu, mp, mp, Cp, R, T, R, -1.0));
+                       GemmArgs g3 = gemm_args(WS, mp, 1, Xp, Cp, 1, R, Cp, (int)mp, (int)Cp, (int)mp, 1.0, 1.0);
+                       g3.kb_row = GPK_TILE;
+                       return gpk_gemm(h, GPK_F64, g3);
+                     });
 }

@@ -256,29 +256,17 @@ class SimpleQuadrotorGP:
         (`SparseGP.sample_paths`), until that model takes rows or is retrained: the same functions from call to call.
         Untrained, or on any failure (printed): the nominal trajectory repeated R times - it never raises into the control
         loop."""
+        from .paths import cached_path_set, nominal_rollouts, roll_paths
         state = np.asarray(state, dtype=float).reshape(-1)[:6]
         U_guess = np.asarray(U_guess, dtype=float)
-        R, N = int(n_rollouts), U_guess.shape[1]
-        nominal = np.empty((6, N + 1))
-        nominal[:, 0] = state
-        for k in range(N):
-            nominal[:, k + 1] = self._nominal_dynamics(nominal[:, k], U_guess[:, k], dt)
-        fallback = np.repeat(nominal[None], max(R, 0), axis=0)
+        fallback, lin = nominal_rollouts(self._nominal_dynamics, state, U_guess, dt, n_rollouts)
         if not self.is_trained:
             return fallback
         try:
-            # (a path set is a snapshot: a sparse model that has taken rows since it was drawn has a new revision)
-            key = (R, int(n_features), random_state if isinstance(random_state, (int, np.integer)) else id(random_state),
-                   id(self.gp_model), getattr(self.gp_model, "revision_", None))
-            cached = getattr(self, "_paths", None)      # (an object pickled before the attribute existed has none)
-            if cached is None or cached[0] != key:
-                self._paths = (key, self.gp_model.sample_paths(R, n_features, random_state))
-            lin = np.zeros((6, 10))
-            lin[0:3, 3:6] = dt * np.eye(3)       # the double integrator of `_nominal_dynamics`
-            lin[3:6, 6:9] = dt * np.eye(3)
-            traj = self._paths[1].rollout(state, np.ascontiguousarray(U_guess[:4].T), lin)      # (N + 1, R, 6)
-            self.prediction_count += R * N
-            return np.ascontiguousarray(traj.transpose(1, 2, 0))
+            paths = cached_path_set(self, "_paths", self.gp_model, n_rollouts, n_features, random_state)
+            traj = roll_paths(paths, state, U_guess, lin)
+            self.prediction_count += int(n_rollouts) * U_guess.shape[1]
+            return traj
         except Exception as e:  # noqa: BLE001
             print(f"GP rollout sampling failed: {e}")
             return fallback

@@ -522,14 +522,10 @@ class PreTrainedGP:
         model takes rows or is retrained (a path set is a snapshot) - the same functions from call to call.  Not loaded, models
         that cannot be fused into a batch (a single model, different inputs or scalers), or any failure: the reason is printed
         and the nominal trajectory is returned R times - it never raises into the control loop."""
+        from .paths import cached_path_set, nominal_rollouts, roll_paths
         U_guess = np.asarray(U_guess, dtype=float)
         state = np.asarray(state, dtype=float).reshape(-1)[:6]
-        R, N = int(n_rollouts), U_guess.shape[1]
-        nominal = np.empty((6, N + 1))
-        nominal[:, 0] = state
-        for k in range(N):
-            nominal[:, k + 1] = GPTrainer._nominal_dynamics(nominal[:, k], U_guess[:, k], dt)
-        fallback = np.repeat(nominal[None], max(R, 0), axis=0)
+        fallback, lin = nominal_rollouts(GPTrainer._nominal_dynamics, state, U_guess, dt, n_rollouts)
         try:
             if not self.is_loaded:
                 raise RuntimeError("no models are loaded")
@@ -537,24 +533,17 @@ class PreTrainedGP:
             if not fused:
                 raise RuntimeError("the loaded models are not served as one per-axis batch")
             bg, names = fused
-            # (a path set is a snapshot: sparse models that have taken rows since it was drawn have a new revision)
-            key = (R, int(n_features), random_state if isinstance(random_state, (int, np.integer)) else id(random_state), id(bg),
-                   getattr(bg, "revision_", None))
-            cached = getattr(self, "_axis_paths", None)     # (an object pickled before the attribute existed has none)
-            if cached is None or cached[0] != key:
-                paths = bg.sample_paths(R, n_features, random_state)
+
+            def target_scalers(paths):
                 sys_ = [self.scalers_y[n] for n in names]
                 paths.set_output_scaler([float(np.ravel(s.mean_)[0]) for s in sys_], [float(np.ravel(s.scale_)[0]) for s in sys_])
-                self._axis_paths = (key, paths)
-            lin = np.zeros((6, 10))
-            lin[0:3, 3:6] = dt * np.eye(3)       # the double integrator of `GPTrainer._nominal_dynamics`
-            lin[3:6, 6:9] = dt * np.eye(3)
-            traj = self._axis_paths[1].rollout(state, np.ascontiguousarray(U_guess[:4].T), lin,
-                                               coord=[OUTPUT_NAMES.index(n) for n in names],
-                                               in_scaler=self.scalers_X[names[0]])      # (N + 1, R, 6)
+
+            paths = cached_path_set(self, "_axis_paths", bg, n_rollouts, n_features, random_state, finish=target_scalers)
+            traj = roll_paths(paths, state, U_guess, lin, coord=[OUTPUT_NAMES.index(n) for n in names],
+                              in_scaler=self.scalers_X[names[0]])
             if not np.isfinite(traj).all():
                 raise FloatingPointError("non-finite trajectory")
-            return np.ascontiguousarray(traj.transpose(1, 2, 0))
+            return traj
         except Exception as e:  # noqa: BLE001
             print(f"GP rollout sampling failed: {e}")
             return fallback
