@@ -635,7 +635,7 @@ GPK_API int gpk_lml_batched(gpk_handle h, const double* thetas, int n_theta, dou
  *       mean(x) = y_mean + y_std k_u(x)^T alpha_u,   var_f(x) = sf2 - |Wuu k_u(x)|^2 + |WSigma k_u(x)|^2,
  *   var (M x P: variance times y_std^2; NULL = means only); var_includes_noise != 0: + the WhiteKernel level, clipped at 0;
  *   == 0: floored at 1e-10.  Checks that the queries are finite.  Up to 32 queries (D, P <= 16): the two-factor form of the
- *   small-batch kernels - small_cross_mean_kernel with ONE model (one K*, all P outputs), then small_var2_kernel with the
+ *   small-batch kernels - small_cross_mean_kernel with ONE model (one K*, all P outputs), then small_var_kernel with the
  *   inverse factor (0: Wuu, 1: WSigma) as its second grid dimension; the last workgroup overall adds each factor's shares in the
  *   one-factor kernel's order and writes max((kss - t0) - (0 - t1), floor) y_std[p]^2: the mean one launch, mean + variance
  *   two, one synchronisation, for every P, and the bits of the route it replaces (gpk_predict_host_multi with B = 2, for
@@ -648,7 +648,7 @@ GPK_API int gpk_lml_batched(gpk_handle h, const double* thetas, int n_theta, dou
  *       dvar[m][d]     = -2 sum_j k_mj u_jd (c0 - c1)_jm,   c0 = Wuu^T (Wuu k),  c1 = WSigma^T (WSigma k)
  *   dvar is the gradient of the UNCLIPPED variance; var is clipped as gpk_sparse_predict clips it.  Any M >= 1.  Up to 32
  *   queries: the two-factor small-batch kernels - mean + Jacobian ONE launch (small_cross_mean_jac_kernel), all four results
- *   three (+ small_var2_grad_kernel, small_wtv2_grad_kernel: the factor is blockIdx.y / z, both read the same K*, each keeps
+ *   three (+ small_var_grad_kernel, small_wtv_grad_kernel: the factor is blockIdx.y / z, both read the same K*, each keeps
  *   its own V and shares, one ticket count over both, dvar = -2 / ls_d (s0 - s1) by the last workgroup), one synchronisation,
  *   queries and results through the pinned, mapped block.  More, or option small_path = 0: query panels of gpk_predict_mean,
  *   gpk_predict_mean_grad and gpk_predict_var_grad_inv once per inverse factor (floor -DBL_MAX; kss = 0 for WSigma), combined
@@ -660,7 +660,7 @@ GPK_API int gpk_lml_batched(gpk_handle h, const double* thetas, int n_theta, dou
  *   (P x M x M: output p's block is y_std[p]^2 Sigma),
  *       Sigma = K(Xq, Xq) + noise I - V0^T V0 + V1^T V1,   V0 = Wuu K*^T,  V1 = WSigma K*^T,
  *   the model's WhiteKernel level on the diagonal only, not clipped, symmetric bit for bit.  1 <= M <= 16384.  Up to 32
- *   queries: two launches (small_cross_mean_kernel, small_cov2_kernel: the factor is blockIdx.y, group sums per factor, one top
+ *   queries: two launches (small_cross_mean_kernel, small_cov_kernel: the factor is blockIdx.y, group sums per factor, one top
  *   ticket over the groups of both; (k(a, b) - s0) + s1, mirrored), one synchronisation.  More, or option small_path = 0: the
  *   stacked panel [V0; V1] by two tile GEMMs, its copy [V0; -V1], and ONE symmetric tile GEMM of depth 2 mp with the
  *   covariance epilogue (gpk_predict_cov_inv's).

@@ -1,8 +1,8 @@
 """The device buffers behind the composite C entries (gpk_dev, csrc/gpk_compose.h) over the life of ONE handle, with the
 debug_fill option on (every staging request is overwritten with NaN bytes): staging that grows, grows again and is then
-reused with NaN-filled slack, and models that replace one another.  Every result must equal the same call on a fresh
-handle bit for bit - an owner that frees too early, too late or twice, or a panel that reads beyond what it wrote, shows
-here."""
+reused with NaN-filled slack, models that replace one another, and the work area of the small-batch launches.  Every
+result must equal the same call on a fresh handle bit for bit - an owner that frees too early, too late or twice, or a
+panel or kernel that reads beyond what was written, shows here."""
 import ctypes as C
 
 import numpy as np
@@ -19,12 +19,12 @@ def _dp(a):
 
 
 class _Handle:
-    def __init__(self):
+    def __init__(self, debug_fill=1):
         from unmanned_aerial_vehicles_amd import _lib
         self._lib, self.lib, self.h = _lib, _lib.load(), C.c_void_p()
         assert self.lib.gpk_create(C.byref(self.h), 0) == _lib.GPK_OK
         self.ok(self.lib.gpk_set_stream(self.h, C.c_void_p(-1)))
-        self.ok(self.lib.gpk_set_option(self.h, b"debug_fill", 1))
+        self.ok(self.lib.gpk_set_option(self.h, b"debug_fill", debug_fill))
 
     def ok(self, rc):
         assert rc == self._lib.GPK_OK, self.lib.gpk_last_error(self.h).decode()
@@ -79,6 +79,43 @@ class _Handle:
         mean, var = np.empty((len(Q), 1)), np.empty((len(Q), 1))
         return self.lib.gpk_sparse_predict(self.h, _dp(Q), len(Q), _dp(mean), _dp(var), 1), mean, var
 
+    def fit_sparse_outputs(self, X, Y, m):
+        """m inducing inputs, every column of Y an output with a normalisation of its own."""
+        Z, self.P = np.ascontiguousarray(X[:m]), Y.shape[1]
+        ls = np.ascontiguousarray(1.5 + 0.1 * np.arange(X.shape[1]))
+        self.ok(self.lib.gpk_sparse_begin(self.h, _dp(Z), m, Z.shape[1], self.P, _dp(ls), len(ls), 1.2, 0.05, 1e-6, 1e-6,
+                                          _dp(np.ascontiguousarray(Y.mean(0))), _dp(np.ascontiguousarray(1.0 + 0.5 * np.arange(self.P)))))
+        self.ok(self.lib.gpk_sparse_update(self.h, _dp(X), _dp(Y), len(X)))
+        info = C.c_int()
+        self.ok(self.lib.gpk_sparse_finalize(self.h, C.byref(info)))
+
+    def small_calls(self, sparse, Q):
+        """Every call the small-batch launches serve, on the exact model (gpk_fit) or the sparse one: mean, mean + variance,
+        mean + Jacobian, all four gradient results, mean + covariance.  The outputs start as NaN."""
+        lib, M, P, D = self.lib, len(Q), self.P, Q.shape[1]
+
+        def nan(*shape):
+            return np.full(shape, np.nan)
+
+        results = []
+        for want_var in (False, True):
+            mean, var = nan(M, P), nan(M, P) if want_var else None
+            if sparse:
+                self.ok(lib.gpk_sparse_predict(self.h, _dp(Q), M, _dp(mean), _dp(var), 1))
+            else:
+                self.ok(lib.gpk_predict(self.h, Q.ctypes.data_as(C.c_void_p), M, mean.ctypes.data_as(C.c_void_p),
+                                        None if var is None else var.ctypes.data_as(C.c_void_p), self._lib.GPK_F64, 1))
+            results.append((mean, var))
+            mean, dmean = nan(M, P), nan(M, P, D)
+            var, dvar = (nan(M, P), nan(M, P, D)) if want_var else (None, None)
+            grad = lib.gpk_sparse_predict_grad if sparse else lib.gpk_predict_model_grad
+            self.ok(grad(self.h, _dp(Q), M, _dp(mean), _dp(var), _dp(dmean), _dp(dvar), 1))
+            results.append((mean, var, dmean, dvar))
+        mean, cov = nan(M, P), nan(P, M, M)
+        self.ok((lib.gpk_sparse_predict_cov if sparse else lib.gpk_predict_model_cov)(self.h, _dp(Q), M, _dp(mean), _dp(cov)))
+        results.append((mean, cov))
+        return [a for r in results for a in r if a is not None]
+
 
 def _problem(N, D, P):
     rng = np.random.default_rng(N + P)
@@ -132,3 +169,25 @@ def test_models_replaced_and_released():
         fresh.fit(X, Y)
         want_mean, want_var = fresh.predict(Q[:33])
     assert np.isfinite(var).all() and np.array_equal(mean, want_mean) and np.array_equal(var, want_var)
+
+
+@pytest.mark.parametrize("sparse", (False, True), ids=("exact", "sparse"))
+def test_small_batch_work_area_is_written_before_it_is_read(sparse):
+    """(d) every small-batch call - predict and gradients without and with variances, covariance - at M = 16 and 17 (the
+    two tile forms) on one handle with debug_fill on: the exact model (one inverse factor, N = 200, D = 3, P = 2) and the
+    sparse one (two, m = 130, D = 4, P = 3), both at the smallest padded size, 256.  One launch routine hands every kernel
+    its part of the work area; a kernel that reads what nobody wrote reads NaN.  Every output is finite and has the bits of
+    the same call on a fresh handle with debug_fill off."""
+    X, Y, Q = _problem(200, 4, 3) if sparse else _problem(200, 3, 2)
+    fit = (lambda h: h.fit_sparse_outputs(X, Y, 130)) if sparse else (lambda h: h.fit(X, Y))
+    with _Handle() as h:
+        fit(h)
+        got = {M: h.small_calls(sparse, Q[:M]) for M in (16, 17)}
+    for M, arrays in got.items():
+        with _Handle(debug_fill=0) as fresh:
+            fit(fresh)
+            want = fresh.small_calls(sparse, Q[:M])
+        assert len(arrays) == len(want) == 11
+        for i, (a, w) in enumerate(zip(arrays, want)):
+            assert np.isfinite(a).all(), (M, i)
+            assert np.array_equal(a, w), (M, i)

@@ -155,6 +155,24 @@ class Handle:
         self.ok(self.lib.gpk_sparse_predict(self.h, dp(Q), len(Q), dp(mean), dp(var), vin))
         return mean, var
 
+    def sparse_grad(self, Q, D):
+        M, P = len(Q), self.P
+        mean, var, dmean, dvar = np.empty((M, P)), np.empty((M, P)), np.empty((M, P, D)), np.empty((M, P, D))
+        self.ok(self.lib.gpk_sparse_predict_grad(self.h, dp(Q), M, dp(mean), dp(var), dp(dmean), dp(dvar), 1))
+        return mean, var, dmean, dvar
+
+    def sparse_cov(self, Q):
+        mean, cov = np.empty((len(Q), self.P)), np.empty((self.P, len(Q), len(Q)))
+        self.ok(self.lib.gpk_sparse_predict_cov(self.h, dp(Q), len(Q), dp(mean), dp(cov)))
+        return mean, cov
+
+    def sparse_predict_multi(self, models, Q):
+        """Mean and variance of the single-output sparse models behind `models` (Handles), served by this handle."""
+        B, handles = len(models), (C.c_void_p * len(models))(*[x.h for x in models])
+        mean, var = np.empty((len(Q), B)), np.empty((len(Q), B))
+        self.ok(self.lib.gpk_sparse_predict_multi(self.h, B, handles, dp(Q), len(Q), dp(mean), dp(var), 1))
+        return mean, var
+
     def sparse_export(self, m, D, n_ls):
         P = self.P
         Z, G, g, yy = np.empty((m, D)), np.empty((m, m)), np.empty((m, P)), np.empty(P)
@@ -352,6 +370,10 @@ def run_time():
     hb.fit_batched(X, Y, np.ascontiguousarray(np.tile(1.2 + 0.05 * np.arange(10), (6, 1)) * (1 + 0.1 * np.arange(6))[:, None]),
                    np.full(6, 1.3), np.full(6, 0.05), 1e-6)
     cell("gpk_predict_batched var B=6 N=1000 M=25", lambda: hb.predict_batched(Q[:25], True, 1))
+    cell("gpk_predict_model_grad all four N=1000 P=6 M=25", lambda: h.grad(Q[:25], True, 1))
+    cell("gpk_predict_model_cov N=1000 P=6 M=25", lambda: h.cov(Q[:25]))
+    cell("gpk_predict_batched_grad all four B=6 N=1000 M=25", lambda: hb.grad_batched(Q[:25], True, 1))
+    cell("gpk_predict_batched_cov B=6 N=1000 M=25", lambda: hb.cov_batched(Q[:25]))
     hb.close()
     rng, Xs, Ys, Qs = problem(8192, 3, 1, 5)
     hs = Handle()
@@ -361,6 +383,18 @@ def run_time():
     hs.sparse_finalize()
     for M in (1, 25):
         cell(f"gpk_sparse_predict var m=1024 P=1 M={M}", lambda: hs.sparse_predict(Qs[:M], True, 1))
+    cell("gpk_sparse_predict_grad all four m=1024 P=1 M=25", lambda: hs.sparse_grad(Qs[:25], 3))
+    cell("gpk_sparse_predict_cov m=1024 P=1 M=25", lambda: hs.sparse_cov(Qs[:25]))
+    axes = [hs]
+    for b in range(1, 6):      # five more single-output models on the same inducing inputs, each with its own targets and kernel
+        ha = Handle()
+        ha.sparse_begin(Z, 1, np.array([1.5 + 0.1 * b]), 1.2, 0.05, 1e-6, 1e-6, Ys.mean(0), Ys.std(0))
+        ha.sparse_update(Xs, np.ascontiguousarray(np.roll(Ys, 17 * b, axis=0)))
+        ha.sparse_finalize()
+        axes.append(ha)
+    cell("gpk_sparse_predict_multi var B=6 m=1024 M=25", lambda: hs.sparse_predict_multi(axes, Qs[:25]))
+    for ha in axes[1:]:
+        ha.close()
     hs.close()
     cell(f"gpk_predict f64 var N=1000 P=6 M={BIG}", lambda: h.predict(Q, True, 1), 300, 50)
     h.close()

@@ -7,7 +7,10 @@ equal:
 Models (m, D): (130, 4) - mp = 256: a partial tile plus padding - and (1024, 9) - the control loop's size; P = 1, 3, 6 outputs;
 M = 1, 16, 17, 32 (both tile forms of the small-batch kernels and their edges) and 40 (the panel route); mean only and mean +
 variance, with and without the noise level; option small_path 1 and 0.  A library that exports gpk_sparse_predict_grad and
-gpk_sparse_predict_cov also prints their digests (lines only the new build has).  Plain ctypes on the C ABI: no torch."""
+gpk_sparse_predict_cov also prints their digests (lines only the new build has), and one that exports the per-axis batch
+entries gpk_sparse_predict_multi / _multi_grad / _multi_cov prints theirs: B = 1, 6 and 8 single-output models of either
+shape, each with its own data and kernel, every M and both small_path settings; mean, mean + variance, mean + Jacobian, all
+four gradient results, mean + covariance.  Plain ctypes on the C ABI: no torch."""
 import ctypes as C
 import hashlib
 import os
@@ -18,6 +21,7 @@ import numpy as np  # noqa: E402
 
 MODELS = ((130, 4), (1024, 9))
 OUTPUTS = (1, 3, 6)
+BATCHES = (1, 6, 8)
 ROWS = (1, 16, 17, 32, 40)
 _dp = C.POINTER(C.c_double)
 
@@ -30,7 +34,10 @@ def load_library():
            "gpk_sparse_begin": [vp, _dp, i64, C.c_int, C.c_int, _dp, C.c_int, dbl, dbl, dbl, dbl, _dp, _dp],
            "gpk_sparse_update": [vp, _dp, _dp, i64], "gpk_sparse_finalize": [vp, C.POINTER(C.c_int)],
            "gpk_sparse_predict": [vp, _dp, i64, _dp, _dp, C.c_int],
-           "gpk_sparse_predict_grad": [vp, _dp, i64, _dp, _dp, _dp, _dp, C.c_int], "gpk_sparse_predict_cov": [vp, _dp, i64, _dp, _dp]}
+           "gpk_sparse_predict_grad": [vp, _dp, i64, _dp, _dp, _dp, _dp, C.c_int], "gpk_sparse_predict_cov": [vp, _dp, i64, _dp, _dp],
+           "gpk_sparse_predict_multi": [vp, C.c_int, C.POINTER(vp), _dp, i64, _dp, _dp, C.c_int],
+           "gpk_sparse_predict_multi_grad": [vp, C.c_int, C.POINTER(vp), _dp, i64, _dp, _dp, _dp, _dp, C.c_int],
+           "gpk_sparse_predict_multi_cov": [vp, C.c_int, C.POINTER(vp), _dp, i64, _dp, _dp]}
     for name, args in sig.items():
         if hasattr(lib, name):
             getattr(lib, name).argtypes, getattr(lib, name).restype = args, C.c_int
@@ -51,13 +58,14 @@ def digest(*arrays):
     return h.hexdigest()
 
 
-def sparse_model(lib, m, D, P, N=3000):
-    """A finalised sparse model behind a fresh handle; returns (handle, check, rng)."""
-    rng = np.random.default_rng(1000 * m + P)
+def sparse_model(lib, m, D, P, N=3000, axis=0):
+    """A finalised sparse model behind a fresh handle; returns (handle, check, queries).  axis: the model's place in a per-axis
+    batch - its own data, length-scales, signal variance and noise."""
+    rng = np.random.default_rng(1000 * m + P + 7919 * axis)
     X = rng.standard_normal((N, D))
     Y = np.ascontiguousarray(np.sin(X @ rng.standard_normal((D, P))) + 0.1 * rng.standard_normal((N, P)))
     Z = np.ascontiguousarray(X[:m])
-    ls = np.ascontiguousarray(1.5 * (1.0 + 0.05 * np.arange(D)))
+    ls = np.ascontiguousarray(1.5 * (1.0 + 0.05 * np.arange(D)) * (1.0 + 0.07 * axis))
     ym, ys = np.ascontiguousarray(Y.mean(axis=0)), np.ascontiguousarray(Y.std(axis=0))
     h = C.c_void_p()
     assert lib.gpk_create(C.byref(h), 0) == 0
@@ -67,7 +75,7 @@ def sparse_model(lib, m, D, P, N=3000):
             raise RuntimeError(lib.gpk_last_error(h).decode())
 
     ok(lib.gpk_set_stream(h, C.c_void_p(-1)))      # GPK_OWN_STREAM
-    ok(lib.gpk_sparse_begin(h, ptr(Z), m, D, P, ptr(ls), D, 1.1, 0.02, 1e-6, 1e-6, ptr(ym), ptr(ys)))
+    ok(lib.gpk_sparse_begin(h, ptr(Z), m, D, P, ptr(ls), D, 1.1 + 0.1 * axis, 0.02 * (1 + axis), 1e-6, 1e-6, ptr(ym), ptr(ys)))
     ok(lib.gpk_sparse_update(h, ptr(X), ptr(Y), N))
     info = C.c_int(0)
     ok(lib.gpk_sparse_finalize(h, C.byref(info)))
@@ -101,6 +109,35 @@ def run():
                         ok(lib.gpk_sparse_predict_cov(h, ptr(q), M, ptr(mean), ptr(cov)))
                         print(f"sparse_predict_cov {tag} request=mean+cov", digest(mean, cov))
             lib.gpk_destroy(h)
+    if all(hasattr(lib, "gpk_sparse_predict_multi" + e) for e in ("", "_grad", "_cov")):
+        for m, D in MODELS:
+            run_multi(lib, m, D)
+
+
+def run_multi(lib, m, D):
+    """The per-axis batch entries on the first B of eight single-output models; model 0's handle serves."""
+    models = [sparse_model(lib, m, D, 1, axis=b) for b in range(max(BATCHES))]
+    (h, ok, Q), handles = models[0], (C.c_void_p * max(BATCHES))(*[mod[0] for mod in models])
+    for B in BATCHES:
+        for sp in (1, 0):
+            ok(lib.gpk_set_option(h, b"small_path", sp))
+            for M in ROWS:
+                q = np.ascontiguousarray(Q[:M])
+                tag = f"m={m} D={D} B={B} M={M} small_path={sp}"
+                mean, var, dm, dv = np.empty((M, B)), np.empty((M, B)), np.empty((M, B, D)), np.empty((M, B, D))
+                ok(lib.gpk_sparse_predict_multi(h, B, handles, ptr(q), M, ptr(mean), None, 1))
+                print(f"sparse_predict_multi {tag} request=mean", digest(mean))
+                ok(lib.gpk_sparse_predict_multi(h, B, handles, ptr(q), M, ptr(mean), ptr(var), 1))
+                print(f"sparse_predict_multi {tag} request=mean+var", digest(mean, var))
+                ok(lib.gpk_sparse_predict_multi_grad(h, B, handles, ptr(q), M, ptr(mean), None, ptr(dm), None, 1))
+                print(f"sparse_predict_multi_grad {tag} request=mean+jac", digest(mean, dm))
+                ok(lib.gpk_sparse_predict_multi_grad(h, B, handles, ptr(q), M, ptr(mean), ptr(var), ptr(dm), ptr(dv), 1))
+                print(f"sparse_predict_multi_grad {tag} request=all-four", digest(mean, var, dm, dv))
+                cov = np.empty((B, M, M))
+                ok(lib.gpk_sparse_predict_multi_cov(h, B, handles, ptr(q), M, ptr(mean), ptr(cov)))
+                print(f"sparse_predict_multi_cov {tag} request=mean+cov", digest(mean, cov))
+    for mod in models:
+        lib.gpk_destroy(mod[0])
 
 
 def compare(old, new):

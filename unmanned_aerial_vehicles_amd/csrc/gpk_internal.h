@@ -244,9 +244,7 @@ int gpk_gemm(gpk_handle h, int dtype, const GemmArgs& g);
 int gpk_gemm_tile(gpk_handle h, const GemmArgs& g);   // 128 or 64: the tile edge gpk_gemm will pick
 
 // ---- small-batch serving kernels (gpk_small.hip) -------------------------------------
-// M <= 32 fp64 queries against B models x P outputs each (B > 1: P == 1, the per-axis batch), all models on one query
-// batch.  X / alpha / W: B device pointers; ls: B x D; sf2, kss: B; y_mean, y_std: B * P.  No call synchronises; Xq and
-// the outputs may be pinned, mapped host memory.  Means are un-normalised, variances / covariances in normalised-target units.
+// M <= 32 fp64 queries against B models x P outputs each (B > 1: P == 1, the per-axis batch), all models on one query batch.
 constexpr int GPK_SMALL_MAX_M = 32;          // queries per call
 constexpr int64_t GPK_SMALL_MAX_NP = 16384;  // padded training rows
 constexpr int GPK_SMALL_MAX_MODELS = 8;      // single-output models served by one call
@@ -255,61 +253,52 @@ constexpr int GPK_SMALL_COV_COUNTERS = GPK_SMALL_MAX_MODELS * 129 + GPK_SMALL_MA
                                              // 1 + GPK_SMALL_MAX_NP / 16 / 16 = 65, in the two-factor form 1 + 2 * 64 = 129 (one
                                              // top-level count and the groups of both factors); the last GPK_SMALL_MAX_MODELS are
                                              // small_wtv_grad_kernel's, one per model
+// What a serving call runs on: B <= GPK_SMALL_MAX_MODELS models x P outputs each (B > 1: P == 1) of equal N and D, each with its
+// own inputs, alpha, kernel and normalisation, and F inverse factors per model.  F = 1: the exact GP and the per-axis batch,
+// variance terms kss - |W[0] k*|^2.  F = 2: the sparse model on its inducing inputs (gpk_sparse.hip), kss - |W[0] k*|^2 +
+// |W[1] k*|^2 with W[0] = Wuu, W[1] = WSigma.  A member that the call at hand does not read may be null.
+struct ServeModels {
+  int B, P, F;
+  const double* const* X;         // B device pointers (N x D)
+  const double* const* alpha;     // B device pointers (N x P)
+  int64_t N;
+  int D;
+  const double* ls;               // B x D
+  const double* sf2;              // B
+  const double *y_mean, *y_std;   // B * P
+  const double* const* W[2];      // per factor B device pointers (Np x ldw, 16-byte aligned): variance, gradient, covariance
+  int64_t Np, ldw;                // Np = gpk_padded(N), even ldw >= Np (read with W)
+  const double* kss;              // B: the prior variance the variance starts from
+  double floor_;                  // ... and the level it is clipped at
+  const double* noise;            // B: the level on the covariance's diagonal
+};
+// The results of a call; null: not requested.  mean (B, M, P) and dmean (B, M, P, D) un-normalised.  var: F = 1 (B, M) in
+// normalised-target units, F = 2 (B, M, P) already multiplied by y_std^2.  dvar (B, M, D) and cov (B, M, M): normalised-target
+// units in both forms.  var and dvar come together in a gradient call.
+struct ServeOut {
+  double *mean, *var, *dmean, *dvar, *cov;
+};
 bool gpk_small_ok(int64_t Np, int D, int P, int64_t M);
 // doubles of device work area (`work`) that a call of the given kind needs: per model K* (32 x Np) + the workgroups' shares
+// (F inverse factors per model: K*, the mean and the Jacobian shares stay one set per model)
 enum { GPK_SMALL_PREDICT, GPK_SMALL_COV, GPK_SMALL_GRAD };
-// (F: inverse factors per model - 2 for the two-factor form, whose K*, mean and Jacobian shares stay one set per model)
-size_t gpk_small_work_doubles(int call, int64_t Np, int B, int64_t M, int D, int P, int F = 1);
-// mean (B, M, P) and, if var_out, variance (B, M): one launch, or two (small_cross_mean_kernel + small_var_kernel)
-int gpk_small_predict(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D, int P,
-                      const double* ls, const double* sf2, const double* y_mean, const double* y_std,
-                      const double* const* W, int64_t Np, int64_t ldw, const double* kss, double floor_,
-                      const double* Xq, int64_t M, double* work, double* mean_out, double* var_out);
-// mean (B, M, P) and covariance (B, M, M; noise[b] on model b's diagonal): two launches for all models
-// (small_cross_mean_kernel + small_cov_kernel)
-int gpk_small_cov_multi(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D, int P,
-                        const double* ls, const double* sf2, const double* y_mean, const double* y_std, const double* const* W,
-                        int64_t Np, int64_t ldw, const double* noise, const double* Xq, int64_t M, double* work,
-                        double* mean_out, double* cov_out);
-// mean (B, M, P) and its Jacobian (B, M, P, D; un-normalised) in ONE launch (small_cross_mean_jac_kernel); with var_out /
-// dvar_out also the variance (B, M) and its gradient (B, M, D) in three (+ small_var_grad_kernel, small_wtv_grad_kernel)
-int gpk_small_grad_multi(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D, int P,
-                         const double* ls, const double* sf2, const double* y_mean, const double* y_std, const double* const* W,
-                         int64_t Np, int64_t ldw, const double* kss, double floor_, const double* Xq, int64_t M, double* work,
-                         double* mean_out, double* var_out, double* dmean_out, double* dvar_out);
-// The two-factor form (the sparse model, gpk_sparse.hip): ONE model with P outputs on the inputs X (its inducing inputs) whose
-// variance terms are kss - |W0 k*|^2 + |W1 k*|^2.  One K* and one set of mean (and Jacobian) shares from the first launch -
-// small_cross_mean[_jac]_kernel with one model - then the inverse factor as the grid dimension of the variance, covariance and
-// W^T V launches, the two factors combined by the last workgroup overall: the launch counts of one model whatever P is.
-//   GPK_SMALL_PREDICT  mean (M x P); with var_out the variance (M x P, clipped at floor_, times y_std[p]^2): 1 or 2 launches
-//   GPK_SMALL_GRAD     + dmean (M x P x D); with var_out / dvar_out also dvar (M x D, normalised-target units): 1 or 3 launches
-//   GPK_SMALL_COV      mean and cov (M x M, normalised-target units, noise on the diagonal, not clipped): 2 launches
-// work: gpk_small_work_doubles(call, Np, 1, M, D, P, 2) doubles.
-int gpk_small_two(gpk_handle h, int call, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
-                  double sf2, const double* y_mean, const double* y_std, const double* W0, const double* W1, int64_t Np,
-                  int64_t ldw, double kss, double floor_, double noise, const double* Xq, int64_t M, double* work,
-                  double* mean_out, double* var_out, double* dmean_out, double* dvar_out, double* cov_out);
-// ... with a model dimension: B <= GPK_SMALL_MAX_MODELS such models (B > 1: P == 1) of equal N and D on one query batch, each with
-// its own inputs, alpha, kernel (ls: B x D; sf2, kss, noise: B), normalisation (y_mean, y_std: B * P) and factor pair (W0[b],
-// W1[b]).  The grid dimension that is the factor above is 2 * model + factor; one ticket count per model; the launch counts of
-// one model for every B.  Outputs (B, M, P), (B, M, P), (B, M, P, D), (B, M, D), (B, M, M); block b has the bits of model b
-// served alone.  work: gpk_small_work_doubles(call, Np, B, M, D, P, 2) doubles.  gpk_small_two is B = 1.
-int gpk_small_two_multi(gpk_handle h, int call, int B, const double* const* X, const double* const* alpha, int64_t N, int D, int P,
-                        const double* ls, const double* sf2, const double* y_mean, const double* y_std, const double* const* W0,
-                        const double* const* W1, int64_t Np, int64_t ldw, const double* kss, double floor_, const double* noise,
-                        const double* Xq, int64_t M, double* work, double* mean_out, double* var_out, double* dmean_out,
-                        double* dvar_out, double* cov_out);
-// ... as a one-call serving entry (gpk_serve.hip): host queries in, host results out through the pinned, mapped block, one
-// synchronisation.  Outputs that the call does not produce are NULL.
-int gpk_serve_two(gpk_handle h, int call, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
-                  double sf2, const double* y_mean, const double* y_std, const double* W0, const double* W1, int64_t Np,
-                  int64_t ldw, double kss, double floor_, double noise, const double* Xq_host, int64_t M, double* mean_host,
-                  double* var_host, double* dmean_host, double* dvar_host, double* cov_host);
-int gpk_serve_two_multi(gpk_handle h, int call, int B, const double* const* X, const double* const* alpha, int64_t N, int D, int P,
-                        const double* ls, const double* sf2, const double* y_mean, const double* y_std, const double* const* W0,
-                        const double* const* W1, int64_t Np, int64_t ldw, const double* kss, double floor_, const double* noise,
-                        const double* Xq_host, int64_t M, double* mean_host, double* var_host, double* dmean_host, double* dvar_host,
-                        double* cov_host);
+size_t gpk_small_work_doubles(int call, int64_t Np, int B, int64_t M, int D, int P, int F);
+// The launches of one call on M <= GPK_SMALL_MAX_M queries, no synchronisation; Xq and the outputs may be pinned, mapped host
+// memory.  The launch counts are those of one model with one output for every B, P and F:
+//   GPK_SMALL_PREDICT  mean: 1 launch; with out.var 2
+//   GPK_SMALL_GRAD     mean + dmean: 1 launch; with out.var and out.dvar 3
+//   GPK_SMALL_COV      mean + cov (m.noise on the diagonal, not clipped): 2 launches
+// Block b of every output has the bits of model b served alone.
+int gpk_small_launch(gpk_handle h, int call, const ServeModels& m, const double* Xq, int64_t M, double* work, const ServeOut& out);
+// ... as one-call serving (gpk_serve.hip): host queries in, host results out through the pinned, mapped block, one
+// synchronisation.  small: the launches above (gpk_serve_predict: 33..64 queries the same twice); otherwise, F = 1 only, the
+// general chain, which also reads m.Np / m.ldw only with the inverse factor.
+int gpk_serve_predict(gpk_handle h, const ServeModels& m, bool small, const double* Xq_host, int64_t M, double* mean_host,
+                      double* var_host);
+int gpk_serve_cov(gpk_handle h, const ServeModels& m, bool small, const double* Xq_host, int64_t M, double* mean_host,
+                  double* cov_host);
+int gpk_serve_grad(gpk_handle h, const ServeModels& m, bool small, const double* Xq_host, int64_t M, double* mean_host,
+                   double* var_host, double* dmean_host, double* dvar_host);
 // Sigma (Mp x ldc, symmetric bit for bit) = K(Xq, Xq) + noise I - VA^T VB from two operands (rows x Mp each, ld Mp) whose
 // product is symmetric (gpk_cov.hip: the covariance epilogue of the tile GEMM; VA == VB: the exact model's covariance)
 int gpk_cov_from_v(gpk_handle h, const double* VA, const double* VB, int64_t rows, const double* Xq, int64_t M, int D,

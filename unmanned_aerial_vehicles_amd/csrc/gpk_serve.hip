@@ -3,16 +3,15 @@
 //   gpk_predict_host, gpk_predict_host_multi             mean (+ variance)             of one model / of B per-axis models
 //   gpk_predict_host_cov, gpk_predict_host_multi_cov     mean + covariance             of one model / of B per-axis models
 //   gpk_predict_host_grad, gpk_predict_host_multi_grad   mean + Jacobian (+ variance + its gradient)
-//   gpk_serve_two[_multi] (internal: the sparse model's entries)  any of the three on one model / on B models with two inverse factors each
 //
 // The staging block is pinned, coherent host memory mapped into the device's address space: the kernels write their
 // results straight into it (a few hundred bytes over PCIe) - no download command.  Small batches (<= 32 queries): the
 // kernels read the queries from it as well (gpk_small.hip: one to three launches, no copy command).  Otherwise the
 // queries go to HBM with one async copy (every workgroup re-reads them) ahead of the general chain.
 //
-// An entry checks its arguments, decides the route and calls one of serve_predict / serve_cov / serve_grad.  Those take
-// B models x P outputs each: the single-model entries are B = 1, the per-axis entries P = 1, and the outputs are laid out
-// (B, M, P), (B, M), (B, M, M), (B, M, P, D), (B, M, D) either way.
+// An entry checks its arguments, decides the route and calls one of gpk_serve_predict / gpk_serve_cov / gpk_serve_grad.  Those
+// take a ServeModels (gpk_internal.h): the single-model entries are B = 1, the per-axis entries P = 1, both with one inverse
+// factor; the sparse model's entries (gpk_sparse.hip) call the same three with two, for their small route.
 #include "gpk_internal.h"
 
 namespace {
@@ -93,66 +92,54 @@ struct Serve {
   }
 };
 
-// B models x P outputs each on shared training inputs' shape (B > 1: P == 1): the arguments of the gpk_small_* calls.
-struct ServeModels {
-  int B, P;
-  const double* const* X;
-  const double* const* alpha;
-  int64_t N;
-  int D;
-  const double* ls;            // B x D
-  const double* sf2;           // B
-  const double *y_mean, *y_std;   // B * P
-  const double* const* W;      // null entries / null: no variance
-  int64_t Np, ldw;
-  const double* kss;           // B
-  double floor_;
-};
+}  // namespace
 
-// Mean (B, M, P) and, if var_host, variance (B, M).  small: up to 32 queries the small-batch launches, 33..64 the same
-// twice (4 launches instead of the general chain's 7); otherwise (one model) the general chain.
-int serve_predict(gpk_handle h, const ServeModels& m, bool small, const double* Xq_host, int64_t M, double* mean_host,
-                  double* var_host) {
+// Mean (B, M, P) and, if var_host, the variance.  small: up to 32 queries the small-batch launches, 33..64 (one model, one
+// factor) the same twice (4 launches instead of the general chain's 7); otherwise (one model) the general chain.
+int gpk_serve_predict(gpk_handle h, const ServeModels& m, bool small, const double* Xq_host, int64_t M, double* mean_host,
+                      double* var_host) {
+  GPK_REQUIRE(h, small || m.F == 1, "serving: the general chain takes one inverse factor (the sparse model has panel routes of its own)");
   GPK_REQUIRE(h, small || m.B == 1, "serving: the general chain serves one model per call");
+  GPK_REQUIRE(h, M <= GPK_SMALL_MAX_M || (m.B == 1 && m.F == 1), "serving: more than 32 queries go to one model with one factor");
   const int64_t Npad = gpk_padded(m.N), Mp = gpk_padded(M);
   const size_t nm = (size_t)m.B * M * m.P;
-  double *hmean, *hvar;
+  ServeOut o{};
   Serve s(h, Xq_host, M, m.D);
-  s.out(mean_host, nm, &hmean);
-  s.out(var_host, (size_t)m.B * M, &hvar);
+  s.out(mean_host, nm, &o.mean);
+  s.out(var_host, m.F == 2 ? nm : (size_t)m.B * M, &o.var);
   // work: the small-batch kernels' K* and shares, or the K* panel of the variance GEMM
-  GPK_TRY(s.begin(small ? gpk_small_work_doubles(GPK_SMALL_PREDICT, Npad, m.B, M, m.D, m.P) : (var_host ? (size_t)Mp * Npad : 0)));
+  GPK_TRY(s.begin(small ? gpk_small_work_doubles(GPK_SMALL_PREDICT, Npad, m.B, M, m.D, m.P, m.F) : (var_host ? (size_t)Mp * Npad : 0)));
   if (small) {
     for (int64_t m0 = 0; m0 < M; m0 += GPK_SMALL_MAX_M) {
       const int64_t mc = M - m0 < GPK_SMALL_MAX_M ? M - m0 : GPK_SMALL_MAX_M;
-      GPK_TRY(gpk_small_predict(h, m.B, m.X, m.alpha, m.N, m.D, m.P, m.ls, m.sf2, m.y_mean, m.y_std, m.W, Npad, m.ldw, m.kss,
-                                m.floor_, s.hq + m0 * m.D, mc, s.dwork, hmean + m0 * m.P, var_host ? hvar + m0 : nullptr));
+      const ServeOut chunk{o.mean + m0 * m.P, var_host ? o.var + m0 : nullptr, nullptr, nullptr, nullptr};
+      GPK_TRY(gpk_small_launch(h, GPK_SMALL_PREDICT, m, s.hq + m0 * m.D, mc, s.dwork, chunk));
     }
   } else {
     GPK_TRY(s.upload());
-    GPK_TRY(gpk_predict_mean(h, GPK_F64, m.X[0], m.alpha[0], m.N, m.D, m.P, m.ls, m.sf2[0], m.y_mean, m.y_std, s.dq, M, hmean));
+    GPK_TRY(gpk_predict_mean(h, GPK_F64, m.X[0], m.alpha[0], m.N, m.D, m.P, m.ls, m.sf2[0], m.y_mean, m.y_std, s.dq, M, o.mean));
     if (var_host)
-      GPK_TRY(gpk_predict_var_inv(h, GPK_F64, m.X[0], m.N, m.D, m.ls, m.sf2[0], m.W[0], m.Np, m.ldw, s.dq, M, m.kss[0], m.floor_,
-                                  s.dwork, hvar));
+      GPK_TRY(gpk_predict_var_inv(h, GPK_F64, m.X[0], m.N, m.D, m.ls, m.sf2[0], m.W[0][0], m.Np, m.ldw, s.dq, M, m.kss[0], m.floor_,
+                                  s.dwork, o.var));
   }
   return s.finish();
 }
 
-// Mean (B, M, P) and covariance (B, M, M), noise[b] on model b's diagonal.  small: the two small-batch launches for all
+// Mean (B, M, P) and covariance (B, M, M), m.noise[b] on model b's diagonal.  small: the two small-batch launches for all
 // models, the covariances through the pinned block; otherwise the general blocks model by model: V (Np x Mp) and Sigma
 // (Mp x Mp) in the work area (reused: the stream orders the models) and one strided download per model.
-int serve_cov(gpk_handle h, const ServeModels& m, bool small, const double* noise, const double* Xq_host, int64_t M,
-              double* mean_host, double* cov_host) {
+int gpk_serve_cov(gpk_handle h, const ServeModels& m, bool small, const double* Xq_host, int64_t M, double* mean_host,
+                  double* cov_host) {
+  GPK_REQUIRE(h, small || m.F == 1, "serving: the general chain takes one inverse factor (the sparse model has panel routes of its own)");
   const int64_t Mp = gpk_padded(M);
   const size_t nm = (size_t)M * m.P, nc = (size_t)M * M;       // per model
-  double *hmean, *hcov = nullptr;
+  ServeOut o{};
   Serve s(h, Xq_host, M, m.D);
-  s.out(mean_host, m.B * nm, &hmean);
-  if (small) s.out(cov_host, m.B * nc, &hcov);
-  GPK_TRY(s.begin(small ? gpk_small_work_doubles(GPK_SMALL_COV, m.Np, m.B, M, m.D, m.P) : (size_t)m.Np * Mp + (size_t)Mp * Mp));
+  s.out(mean_host, m.B * nm, &o.mean);
+  if (small) s.out(cov_host, m.B * nc, &o.cov);
+  GPK_TRY(s.begin(small ? gpk_small_work_doubles(GPK_SMALL_COV, m.Np, m.B, M, m.D, m.P, m.F) : (size_t)m.Np * Mp + (size_t)Mp * Mp));
   if (small) {
-    GPK_TRY(gpk_small_cov_multi(h, m.B, m.X, m.alpha, m.N, m.D, m.P, m.ls, m.sf2, m.y_mean, m.y_std, m.W, m.Np, m.ldw, noise, s.hq,
-                                M, s.dwork, hmean, hcov));
+    GPK_TRY(gpk_small_launch(h, GPK_SMALL_COV, m, s.hq, M, s.dwork, o));
   } else {
     double* dV = s.dwork;
     double* dcov = s.dwork + (size_t)m.Np * Mp;
@@ -160,8 +147,9 @@ int serve_cov(gpk_handle h, const ServeModels& m, bool small, const double* nois
     for (int b = 0; b < m.B; ++b) {
       const double* ls = m.ls + b * m.D;
       GPK_TRY(gpk_predict_mean(h, GPK_F64, m.X[b], m.alpha[b], m.N, m.D, m.P, ls, m.sf2[b], m.y_mean + b * m.P, m.y_std + b * m.P,
-                               s.dq, M, hmean + b * nm));
-      GPK_TRY(gpk_predict_cov_inv(h, GPK_F64, m.X[b], m.N, m.D, ls, m.sf2[b], m.W[b], m.Np, m.ldw, s.dq, M, noise[b], dV, dcov, Mp));
+                               s.dq, M, o.mean + b * nm));
+      GPK_TRY(gpk_predict_cov_inv(h, GPK_F64, m.X[b], m.N, m.D, ls, m.sf2[b], m.W[0][b], m.Np, m.ldw, s.dq, M, m.noise[b], dV, dcov,
+                                  Mp));
       GPK_CHECK_HIP(h, hipMemcpy2DAsync(cov_host + b * nc, (size_t)M * sizeof(double), dcov, (size_t)Mp * sizeof(double),
                                         (size_t)M * sizeof(double), (size_t)M, hipMemcpyDeviceToHost, h->stream));
     }
@@ -169,78 +157,44 @@ int serve_cov(gpk_handle h, const ServeModels& m, bool small, const double* nois
   return s.finish();
 }
 
-// Mean (B, M, P) and its Jacobian (B, M, P, D); with var_host / dvar_host (both or neither) also the variance (B, M) and its
+// Mean (B, M, P) and its Jacobian (B, M, P, D); with var_host / dvar_host (both or neither) also the variance and its
 // gradient (B, M, D).  small: all models in one launch, or three.  Otherwise the general building blocks, model by model,
 // the variance gradient on query panels whose three Np x panel work panels stay within 6 GiB (DeviceGP.VAR_PANEL_BYTES).
-int serve_grad(gpk_handle h, const ServeModels& m, bool small, const double* Xq_host, int64_t M, double* mean_host,
-               double* var_host, double* dmean_host, double* dvar_host) {
+int gpk_serve_grad(gpk_handle h, const ServeModels& m, bool small, const double* Xq_host, int64_t M, double* mean_host,
+                   double* var_host, double* dmean_host, double* dvar_host) {
+  GPK_REQUIRE(h, small || m.F == 1, "serving: the general chain takes one inverse factor (the sparse model has panel routes of its own)");
   const bool want_var = var_host != nullptr;
   const int64_t Npad = gpk_padded(m.N);
   int64_t panel = (int64_t)((6ull << 30) / ((size_t)3 * Npad * sizeof(double))) / GPK_TILE * GPK_TILE;
   if (panel < GPK_TILE) panel = GPK_TILE;
   if (panel > gpk_padded(M)) panel = gpk_padded(M);
   const size_t nm = (size_t)M * m.P, njm = nm * m.D, njv = (size_t)M * m.D;     // per model
-  double *hmean, *hvar, *hdm, *hdv;
+  ServeOut o{};
   Serve s(h, Xq_host, M, m.D);
-  s.out(mean_host, m.B * nm, &hmean);
-  s.out(var_host, (size_t)m.B * M, &hvar);
-  s.out(dmean_host, m.B * njm, &hdm);
-  s.out(dvar_host, m.B * njv, &hdv);
-  GPK_TRY(s.begin(small ? gpk_small_work_doubles(GPK_SMALL_GRAD, Npad, m.B, M, m.D, m.P) : (want_var ? (size_t)3 * Npad * panel : 0)));
-  if (small) {
-    GPK_TRY(gpk_small_grad_multi(h, m.B, m.X, m.alpha, m.N, m.D, m.P, m.ls, m.sf2, m.y_mean, m.y_std, want_var ? m.W : nullptr, Npad,
-                                 m.ldw, m.kss, m.floor_, s.hq, M, s.dwork, hmean, want_var ? hvar : nullptr, hdm,
-                                 want_var ? hdv : nullptr));
+  s.out(mean_host, m.B * nm, &o.mean);
+  s.out(var_host, m.F == 2 ? m.B * nm : (size_t)m.B * M, &o.var);
+  s.out(dmean_host, m.B * njm, &o.dmean);
+  s.out(dvar_host, m.B * njv, &o.dvar);
+  GPK_TRY(s.begin(small ? gpk_small_work_doubles(GPK_SMALL_GRAD, Npad, m.B, M, m.D, m.P, m.F) : (want_var ? (size_t)3 * Npad * panel : 0)));
+  if (small) {      // (the slots of var and dvar stay when they are not requested; nothing is written to them)
+    const ServeOut req{o.mean, want_var ? o.var : nullptr, o.dmean, want_var ? o.dvar : nullptr, nullptr};
+    GPK_TRY(gpk_small_launch(h, GPK_SMALL_GRAD, m, s.hq, M, s.dwork, req));
   } else {
     GPK_TRY(s.upload());
     for (int b = 0; b < m.B; ++b) {
       const double* ls = m.ls + b * m.D;
       GPK_TRY(gpk_predict_mean(h, GPK_F64, m.X[b], m.alpha[b], m.N, m.D, m.P, ls, m.sf2[b], m.y_mean + b * m.P, m.y_std + b * m.P,
-                               s.dq, M, hmean + b * nm));
-      GPK_TRY(gpk_predict_mean_grad(h, m.X[b], m.alpha[b], m.N, m.D, m.P, ls, m.sf2[b], m.y_std + b * m.P, s.dq, M, hdm + b * njm));
+                               s.dq, M, o.mean + b * nm));
+      GPK_TRY(gpk_predict_mean_grad(h, m.X[b], m.alpha[b], m.N, m.D, m.P, ls, m.sf2[b], m.y_std + b * m.P, s.dq, M, o.dmean + b * njm));
       if (want_var)
         for (int64_t m0 = 0; m0 < M; m0 += panel) {
           const int64_t mc = M - m0 < panel ? M - m0 : panel;
-          GPK_TRY(gpk_predict_var_grad_inv(h, m.X[b], m.N, m.D, ls, m.sf2[b], m.W[b], m.Np, m.ldw, s.dq + m0 * m.D, mc, m.kss[b],
-                                           m.floor_, s.dwork, hvar + b * M + m0, hdv + b * njv + m0 * m.D));
+          GPK_TRY(gpk_predict_var_grad_inv(h, m.X[b], m.N, m.D, ls, m.sf2[b], m.W[0][b], m.Np, m.ldw, s.dq + m0 * m.D, mc, m.kss[b],
+                                           m.floor_, s.dwork, o.var + b * M + m0, o.dvar + b * njv + m0 * m.D));
         }
     }
   }
   return s.finish();
-}
-
-}  // namespace
-
-int gpk_serve_two_multi(gpk_handle h, int call, int B, const double* const* X, const double* const* alpha, int64_t N, int D, int P,
-                        const double* ls, const double* sf2, const double* y_mean, const double* y_std, const double* const* W0,
-                        const double* const* W1, int64_t Np, int64_t ldw, const double* kss, double floor_, const double* noise,
-                        const double* Xq_host, int64_t M, double* mean_host, double* var_host, double* dmean_host, double* dvar_host,
-                        double* cov_host) {
-  const size_t nm = (size_t)B * M * P;
-  double *hmean, *hvar = nullptr, *hdm = nullptr, *hdv = nullptr, *hcov = nullptr;
-  Serve s(h, Xq_host, M, D);
-  s.out(mean_host, nm, &hmean);
-  if (call == GPK_SMALL_COV) {
-    s.out(cov_host, (size_t)B * M * M, &hcov);
-  } else {
-    s.out(var_host, nm, &hvar);
-    if (call == GPK_SMALL_GRAD) {
-      s.out(dmean_host, nm * D, &hdm);
-      s.out(dvar_host, (size_t)B * M * D, &hdv);
-    }
-  }
-  GPK_TRY(s.begin(gpk_small_work_doubles(call, Np, B, M, D, P, 2)));
-  GPK_TRY(gpk_small_two_multi(h, call, B, X, alpha, N, D, P, ls, sf2, y_mean, y_std, W0, W1, Np, ldw, kss, floor_, noise, s.hq, M,
-                              s.dwork, hmean, var_host ? hvar : nullptr, hdm, dvar_host ? hdv : nullptr, hcov));
-  return s.finish();
-}
-
-int gpk_serve_two(gpk_handle h, int call, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
-                  double sf2, const double* y_mean, const double* y_std, const double* W0, const double* W1, int64_t Np,
-                  int64_t ldw, double kss, double floor_, double noise, const double* Xq_host, int64_t M, double* mean_host,
-                  double* var_host, double* dmean_host, double* dvar_host, double* cov_host) {
-  return gpk_serve_two_multi(h, call, 1, &X, &alpha, N, D, P, ls, &sf2, y_mean, y_std, W0 ? &W0 : nullptr, W1 ? &W1 : nullptr, Np, ldw,
-                             &kss, floor_, &noise, Xq_host, M, mean_host, var_host, dmean_host, dvar_host, cov_host);
 }
 
 extern "C" int gpk_predict_host(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P,
@@ -254,8 +208,8 @@ extern "C" int gpk_predict_host(gpk_handle h, const double* X, const double* alp
   GPK_REQUIRE(h, h->batch == 1, "predict_host: not available in batched mode");
   const bool small = h->small_path && M <= 2 * GPK_SMALL_MAX_M &&
                      gpk_small_ok(gpk_padded(N), D, P, M < GPK_SMALL_MAX_M ? M : GPK_SMALL_MAX_M);
-  const ServeModels m{1, P, &X, &alpha, N, D, ls, &sf2, y_mean, y_std, &W, Np, ldw, &kss, floor_};
-  return serve_predict(h, m, small, Xq_host, M, mean_host, var_host);
+  const ServeModels m{1, P, 1, &X, &alpha, N, D, ls, &sf2, y_mean, y_std, {&W, nullptr}, Np, ldw, &kss, floor_, nullptr};
+  return gpk_serve_predict(h, m, small, Xq_host, M, mean_host, var_host);
 }
 
 extern "C" int gpk_predict_host_multi(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N,
@@ -269,8 +223,8 @@ extern "C" int gpk_predict_host_multi(gpk_handle h, int B, const double* const* 
   GPK_REQUIRE(h, !var_host || (W && kss && Np == gpk_padded(N) && ldw >= Np), "predict_host_multi: variance needs the inverse factors");
   GPK_REQUIRE(h, h->batch == 1, "predict_host_multi: not available in batched mode");
   // (no general route for the batch: the small-batch launches whatever the small_path option says)
-  const ServeModels m{B, 1, X, alpha, N, D, ls, sf2, y_mean, y_std, W, Np, ldw, kss, floor_};
-  return serve_predict(h, m, true, Xq_host, M, mean_host, var_host);
+  const ServeModels m{B, 1, 1, X, alpha, N, D, ls, sf2, y_mean, y_std, {W, nullptr}, Np, ldw, kss, floor_, nullptr};
+  return gpk_serve_predict(h, m, true, Xq_host, M, mean_host, var_host);
 }
 
 extern "C" int gpk_predict_host_cov(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P,
@@ -283,8 +237,8 @@ extern "C" int gpk_predict_host_cov(gpk_handle h, const double* X, const double*
   GPK_REQUIRE(h, Np == gpk_padded(N) && ldw >= Np, "predict_host_cov: Np must equal gpk_padded(N), ldw >= Np");
   GPK_REQUIRE(h, D >= 1 && D <= GPK_MAX_D_PREDICT && P >= 1 && P <= GPK_MAX_P, "predict_host_cov: D <= 16, P <= 16");
   GPK_REQUIRE(h, h->batch == 1, "predict_host_cov: not available in batched mode");
-  const ServeModels m{1, P, &X, &alpha, N, D, ls, &sf2, y_mean, y_std, &W, Np, ldw, nullptr, 0.0};
-  return serve_cov(h, m, h->small_path && gpk_small_ok(Np, D, P, M), &noise, Xq_host, M, mean_host, cov_host);
+  const ServeModels m{1, P, 1, &X, &alpha, N, D, ls, &sf2, y_mean, y_std, {&W, nullptr}, Np, ldw, nullptr, 0.0, &noise};
+  return gpk_serve_cov(h, m, h->small_path && gpk_small_ok(Np, D, P, M), Xq_host, M, mean_host, cov_host);
 }
 
 extern "C" int gpk_predict_host_multi_cov(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N,
@@ -300,8 +254,8 @@ extern "C" int gpk_predict_host_multi_cov(gpk_handle h, int B, const double* con
   GPK_REQUIRE(h, h->batch == 1, "predict_host_multi_cov: not available in batched mode");
   for (int b = 0; b < B; ++b) GPK_REQUIRE(h, X[b] && alpha[b] && W[b], "predict_host_multi_cov: null model pointer");
   // (option small_path = 0, the cross-check of the small-batch kernels: the general building blocks, model by model)
-  const ServeModels m{B, 1, X, alpha, N, D, ls, sf2, y_mean, y_std, W, Np, ldw, nullptr, 0.0};
-  return serve_cov(h, m, h->small_path != 0, noise, Xq_host, M, mean_host, cov_host);
+  const ServeModels m{B, 1, 1, X, alpha, N, D, ls, sf2, y_mean, y_std, {W, nullptr}, Np, ldw, nullptr, 0.0, noise};
+  return gpk_serve_cov(h, m, h->small_path != 0, Xq_host, M, mean_host, cov_host);
 }
 
 extern "C" int gpk_predict_host_grad(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P,
@@ -315,8 +269,8 @@ extern "C" int gpk_predict_host_grad(gpk_handle h, const double* X, const double
   GPK_REQUIRE(h, (var_host == nullptr) == (dvar_host == nullptr), "predict_host_grad: var and dvar come together (both or neither)");
   GPK_REQUIRE(h, !var_host || (W && Np == gpk_padded(N) && ldw >= Np), "predict_host_grad: the variance gradient needs the inverse factor");
   GPK_REQUIRE(h, h->batch == 1, "predict_host_grad: not available in batched mode");
-  const ServeModels m{1, P, &X, &alpha, N, D, ls, &sf2, y_mean, y_std, &W, Np, ldw, &kss, floor_};
-  return serve_grad(h, m, h->small_path && gpk_small_ok(gpk_padded(N), D, P, M), Xq_host, M, mean_host, var_host, dmean_host,
+  const ServeModels m{1, P, 1, &X, &alpha, N, D, ls, &sf2, y_mean, y_std, {&W, nullptr}, Np, ldw, &kss, floor_, nullptr};
+  return gpk_serve_grad(h, m, h->small_path && gpk_small_ok(gpk_padded(N), D, P, M), Xq_host, M, mean_host, var_host, dmean_host,
                     dvar_host);
 }
 
@@ -338,6 +292,6 @@ extern "C" int gpk_predict_host_multi_grad(gpk_handle h, int B, const double* co
   for (int b = 0; b < B; ++b)
     GPK_REQUIRE(h, X[b] && alpha[b] && (!var_host || W[b]), "predict_host_multi_grad: null model pointer");
   // (option small_path = 0, the cross-check of the small-batch kernels: the general building blocks, model by model)
-  const ServeModels m{B, 1, X, alpha, N, D, ls, sf2, y_mean, y_std, W, Np, ldw, kss, floor_};
-  return serve_grad(h, m, h->small_path != 0, Xq_host, M, mean_host, var_host, dmean_host, dvar_host);
+  const ServeModels m{B, 1, 1, X, alpha, N, D, ls, sf2, y_mean, y_std, {W, nullptr}, Np, ldw, kss, floor_, nullptr};
+  return gpk_serve_grad(h, m, h->small_path != 0, Xq_host, M, mean_host, var_host, dmean_host, dvar_host);
 }

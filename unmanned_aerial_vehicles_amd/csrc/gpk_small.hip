@@ -27,23 +27,25 @@
 //                            and, in the last workgroup, -2 / ls_d times the fixed-order sum of the shares.
 //                            All three take the model as a grid dimension (blockIdx.y, y, z) like the mean and the variance:
 //                            the per-axis batch (B <= 8 single-output models on one query batch) gets mean + Jacobian of
-//                            every model in ONE launch and all four results in three (gpk_small_grad_multi), each model
+//                            every model in ONE launch and all four results in three, each model
 //                            with its own shares and its own ticket counters.
 //
 //   two factors (K9)         the sparse model's variance terms are kss - |Wuu k*|^2 + |WSigma k*|^2 on ONE K* with P outputs: the
-//                            first launch runs with one model, and small_var2[_grad]_kernel, small_cov2_kernel and
-//                            small_wtv2_grad_kernel - the same bodies, template parameter TWO - take the inverse FACTOR as the grid
+//                            first launch runs with one model, and small_var[_grad]_kernel, small_cov_kernel and small_wtv_grad_kernel
+//                            with the template parameter TWO - the same bodies - take the inverse FACTOR as the grid
 //                            dimension that is the model elsewhere: shared K*, mean and Jacobian shares, per-factor V and shares, one
-//                            ticket count over the workgroups of both, and the last workgroup overall writes the combination
-//                            (gpk_small_two): any P at the launch counts of one model.
+//                            ticket count over the workgroups of both, and the last workgroup overall writes the combination:
+//                            any P at the launch counts of one model.
 //   ... with a model dimension  the same kernels serve B <= 8 sparse models (P = 1 each, equal m and D, each with its own Z, alpha_u,
 //                            kernel, noise, normalisation and factor pair) on one query batch: that grid dimension is 2 * model +
 //                            factor.  Per model one K* and one set of mean / Jacobian shares (the cross kernels' blockIdx.y), per
 //                            (model, factor) its own V and shares, per model ONE ticket count over the workgroups of both of its
-//                            factors, and that model's last workgroup writes its combination (gpk_small_two_multi; gpk_small_two
-//                            is B = 1).  A model's sums are grouped by (Np, M) alone: its block has the bits of that model served alone.
+//                            factors, and that model's last workgroup writes its combination.  A model's sums are grouped by (Np, M)
+//                            alone: its block has the bits of that model served alone.
 //
-// Both results land in the caller's (pinned, mapped) output block; the queries are read from it as well.
+// The results land in the caller's (pinned, mapped) output block; the queries are read from it as well.  ONE host routine,
+// gpk_small_launch, makes the launches of every call (predict, gradients, covariance) for B models of one or two inverse factors
+// from a ServeModels (gpk_internal.h): its checks, the parameter block, the work area's pointers (small_work) and the grids.
 #include "gpk_internal.h"
 #include "gpk_math.h"
 
@@ -379,7 +381,7 @@ __device__ __forceinline__ double small_v_sum(const double (&red)[VW][NMB][16][1
 // GRAD (small_var_grad_kernel): the launch also stores its rows of V (Vs: per model Np x SQ, columns < 16 NMB written) for
 // small_wtv_grad_kernel, and workgroup 1 adds the mean Jacobian's shares of the previous launch.  The body is shared;
 // small_var_kernel keeps its signature and its launches.
-// TWO (small_var2_kernel, small_var2_grad_kernel; the sparse model): blockIdx.y is 2 * model + the inverse FACTOR (0: Wuu,
+// TWO (the sparse model): blockIdx.y is 2 * model + the inverse FACTOR (0: Wuu,
 // 1: WSigma); one model with P outputs, or B models with one each.  Both factors of a model read its K* and its mean / Jacobian
 // shares (model slot o); each has its own shares (and rows of V, slot 2 o + f); ONE ticket count per model runs over the
 // workgroups of both, and the model's last one adds each factor's shares in the order above and writes
@@ -468,41 +470,23 @@ __device__ __forceinline__ void small_var_body(SmallK k, long long ldw, long lon
   }
 }
 
-template <int NMB>
+// TWO: the two-factor forms (the sparse model: blockIdx.y = 2 * model + inverse factor; var_out is M x P, already times y_std[p]^2)
+template <int NMB, bool TWO>
 __global__ __launch_bounds__(64 * VW) void small_var_kernel(SmallK k, long long ldw, long long Np, const double* Ks,
                                                             int M, int P, double floor_, const double* pmean,
                                                             unsigned mean_shares, double* pvar, unsigned* counter,
                                                             double* mean_out, double* var_out) {
-  small_var_body<NMB, false, false>(k, ldw, Np, Ks, M, P, floor_, pmean, mean_shares, pvar, counter, mean_out, var_out, nullptr, nullptr, 0,
-                             nullptr);
+  small_var_body<NMB, false, TWO>(k, ldw, Np, Ks, M, P, floor_, pmean, mean_shares, pvar, counter, mean_out, var_out, nullptr, nullptr, 0,
+                                  nullptr);
 }
-template <int NMB>
+template <int NMB, bool TWO>
 __global__ __launch_bounds__(64 * VW) void small_var_grad_kernel(SmallK k, long long ldw, long long Np, const double* Ks,
                                                                  int M, int P, double floor_, const double* pmean,
                                                                  unsigned mean_shares, double* pvar, unsigned* counter,
                                                                  double* mean_out, double* var_out, double* Vs,
                                                                  const double* pjac, int D, double* dmean_out) {
-  small_var_body<NMB, true, false>(k, ldw, Np, Ks, M, P, floor_, pmean, mean_shares, pvar, counter, mean_out, var_out, Vs, pjac, D,
-                            dmean_out);
-}
-
-// the two-factor forms (the sparse model: blockIdx.y = inverse factor; var_out is M x P, already times y_std[p]^2)
-template <int NMB>
-__global__ __launch_bounds__(64 * VW) void small_var2_kernel(SmallK k, long long ldw, long long Np, const double* Ks,
-                                                             int M, int P, double floor_, const double* pmean,
-                                                             unsigned mean_shares, double* pvar, unsigned* counter,
-                                                             double* mean_out, double* var_out) {
-  small_var_body<NMB, false, true>(k, ldw, Np, Ks, M, P, floor_, pmean, mean_shares, pvar, counter, mean_out, var_out, nullptr, nullptr,
-                                   0, nullptr);
-}
-template <int NMB>
-__global__ __launch_bounds__(64 * VW) void small_var2_grad_kernel(SmallK k, long long ldw, long long Np, const double* Ks,
-                                                                  int M, int P, double floor_, const double* pmean,
-                                                                  unsigned mean_shares, double* pvar, unsigned* counter,
-                                                                  double* mean_out, double* var_out, double* Vs,
-                                                                  const double* pjac, int D, double* dmean_out) {
-  small_var_body<NMB, true, true>(k, ldw, Np, Ks, M, P, floor_, pmean, mean_shares, pvar, counter, mean_out, var_out, Vs, pjac, D,
-                                  dmean_out);
+  small_var_body<NMB, true, TWO>(k, ldw, Np, Ks, M, P, floor_, pmean, mean_shares, pvar, counter, mean_out, var_out, Vs, pjac, D,
+                                 dmean_out);
 }
 
 constexpr int CG = 16;                   // workgroups per first-level group of the covariance reduction
@@ -523,7 +507,7 @@ __device__ __forceinline__ void tri_index(int t, int& i, int& j) {
 constexpr int COV_GROUPS = (int)(GPK_SMALL_MAX_NP / SR / CG);
 constexpr int COV_COUNTERS = 1 + COV_GROUPS;
 constexpr int COV2_COUNTERS = 1 + 2 * COV_GROUPS;
-// TWO (small_cov2_kernel; the sparse model): blockIdx.y is 2 * model + inverse factor.  Both factors of a model read its K* and
+// TWO (the sparse model): blockIdx.y is 2 * model + inverse factor.  Both factors of a model read its K* and
 // mean shares; each has its own shares, group sums and group counters; per model COV2_COUNTERS counters ([0] the top level,
 // [1 + f * COV_GROUPS + g] group g of factor f): the top level is ONE count over the groups of both factors, and the model's
 // last group writes (k(a, b) - s0) + s1, mirrored.  Two ticket levels, each with its own last_of: a group's last workgroup reads its group's
@@ -606,21 +590,13 @@ __device__ __forceinline__ void small_cov_body(SmallK k, long long ldw, long lon
   }
 }
 
-template <int NMB>
+template <int NMB, bool TWO>
 __global__ __launch_bounds__(64 * VW) void small_cov_kernel(SmallK k, long long ldw, long long Np, const double* Ks, int M,
                                                             int D, int P, const double* Xq,
                                                             const double* pmean, unsigned mean_shares, double* pcov,
                                                             double* gcov, unsigned* counters, double* mean_out,
                                                             double* cov_out) {
-  small_cov_body<NMB, false>(k, ldw, Np, Ks, M, D, P, Xq, pmean, mean_shares, pcov, gcov, counters, mean_out, cov_out);
-}
-template <int NMB>
-__global__ __launch_bounds__(64 * VW) void small_cov2_kernel(SmallK k, long long ldw, long long Np, const double* Ks, int M,
-                                                             int D, int P, const double* Xq,
-                                                             const double* pmean, unsigned mean_shares, double* pcov,
-                                                             double* gcov, unsigned* counters, double* mean_out,
-                                                             double* cov_out) {
-  small_cov_body<NMB, true>(k, ldw, Np, Ks, M, D, P, Xq, pmean, mean_shares, pcov, gcov, counters, mean_out, cov_out);
+  small_cov_body<NMB, TWO>(k, ldw, Np, Ks, M, D, P, Xq, pmean, mean_shares, pcov, gcov, counters, mean_out, cov_out);
 }
 
 // Variance gradient of M <= 32 queries (model = blockIdx.z), after small_cross_mean_kernel (K*: Ks, query-major) and
@@ -630,7 +606,7 @@ __global__ __launch_bounds__(64 * VW) void small_cov2_kernel(SmallK k, long long
 // shares in order and writes dvar[m][d] = -2 / ls_d * sum.  pdv: gridDim.x * gridDim.y shares per model; counter: one per model.
 constexpr unsigned WTV_MAX_ROW_CHUNKS = 4;
 constexpr int GW = 16, GRG = 16, GT = GW * 2 * GRG;      // 512 threads: column jl, query half mh, row group rg
-// TWO (small_wtv2_grad_kernel; the sparse model): blockIdx.z is 2 * model + inverse factor: the model's K*, inputs and
+// TWO (the sparse model): blockIdx.z is 2 * model + inverse factor: the model's K*, inputs and
 // queries, the factor's own V and shares; per model ONE ticket count over the workgroups of both factors, and the model's last
 // one adds each factor's shares as above and writes dvar[m][d] = -2 / ls_d * (s0 - s1).
 template <bool TWO>
@@ -759,17 +735,12 @@ __device__ __forceinline__ void small_wtv_grad_body(SmallK k, long long ldw, lon
   }
 }
 
+template <bool TWO>
 __global__ __launch_bounds__(GT) void small_wtv_grad_kernel(SmallK k, long long ldw, long long N, long long Np, int D,
                                                             const double* __restrict__ Ks_all, const double* __restrict__ Vs_all,
                                                             const double* __restrict__ Xq, int M, double* pdv,
                                                             unsigned* counter, double* dvar_out) {
-  small_wtv_grad_body<false>(k, ldw, N, Np, D, Ks_all, Vs_all, Xq, M, pdv, counter, dvar_out);
-}
-__global__ __launch_bounds__(GT) void small_wtv2_grad_kernel(SmallK k, long long ldw, long long N, long long Np, int D,
-                                                             const double* __restrict__ Ks_all, const double* __restrict__ Vs_all,
-                                                             const double* __restrict__ Xq, int M, double* pdv,
-                                                             unsigned* counter, double* dvar_out) {
-  small_wtv_grad_body<true>(k, ldw, N, Np, D, Ks_all, Vs_all, Xq, M, pdv, counter, dvar_out);
+  small_wtv_grad_body<TWO>(k, ldw, N, Np, D, Ks_all, Vs_all, Xq, M, pdv, counter, dvar_out);
 }
 
 // The device work area of one call: offsets (in doubles) of the sub-buffers the launches below hand to the kernels, and
@@ -807,26 +778,28 @@ SmallWork small_work(int call, int64_t Np, int B, int64_t M, int D, int P, int F
   return w;
 }
 
-// Checks the B models' pointers and length-scales and fills the kernels' parameter block.  W: null when the call forms
-// no V = W K*^T; kss: null when it has no variance; noise: null except for the covariance.  `who` prefixes the messages.
-int small_params(gpk_handle h, const char* who, int B, int D, int P, const double* const* X, const double* const* alpha,
-                 const double* const* W, const double* ls, const double* sf2, const double* kss, const double* y_mean,
-                 const double* y_std, SmallK& k, const double* noise = nullptr) {
-  const std::string name(who);
-  for (int b = 0; b < B; ++b) {
-    GPK_REQUIRE(h, X[b] && alpha[b] && (!W || W[b]), name + ": null model pointer");
-    GPK_REQUIRE(h, !W || ((uintptr_t)W[b] % 16) == 0, name + ": the inverse factor must be 16-byte aligned");
-    k.X[b] = X[b]; k.alpha[b] = alpha[b]; k.W[b] = W ? W[b] : nullptr;
-    for (int d = 0; d < 16; ++d) k.ls[b][d] = 1.0;
-    for (int d = 0; d < D; ++d) {
-      GPK_REQUIRE(h, ls[b * D + d] > 0.0, "length-scales must be positive");
-      k.ls[b][d] = ls[b * D + d];
+// Checks the models' pointers and length-scales and fills the kernels' parameter block.  factors: the call forms V = W K*^T
+// (otherwise the block's W stay null); kss goes in with a variance, noise with the covariance.  `name` prefixes the messages.
+int small_params(gpk_handle h, const std::string& name, const ServeModels& m, bool factors, bool cov, SmallK& k) {
+  for (int b = 0; b < m.B; ++b) {
+    GPK_REQUIRE(h, m.X[b] && m.alpha[b], name + ": null model pointer");
+    k.X[b] = m.X[b]; k.alpha[b] = m.alpha[b];
+    for (int f = 0; factors && f < m.F; ++f) {
+      const double* W = m.W[f][b];
+      GPK_REQUIRE(h, W, name + ": null model pointer");
+      GPK_REQUIRE(h, ((uintptr_t)W % 16) == 0, name + ": the inverse factor must be 16-byte aligned");
+      (f ? k.W2 : k.W)[b] = W;
     }
-    k.sf2[b] = sf2[b];
-    k.kss[b] = kss ? kss[b] : 0.0;
-    k.noise[b] = noise ? noise[b] : 0.0;
+    for (int d = 0; d < 16; ++d) k.ls[b][d] = 1.0;
+    for (int d = 0; d < m.D; ++d) {
+      GPK_REQUIRE(h, m.ls[b * m.D + d] > 0.0, "length-scales must be positive");
+      k.ls[b][d] = m.ls[b * m.D + d];
+    }
+    k.sf2[b] = m.sf2[b];
+    k.kss[b] = (factors && !cov) ? m.kss[b] : 0.0;
+    k.noise[b] = cov ? m.noise[b] : 0.0;
   }
-  for (int o = 0; o < B * P; ++o) { k.ymean[o] = y_mean[o]; k.ystd[o] = y_std[o]; }
+  for (int o = 0; o < m.B * m.P; ++o) { k.ymean[o] = m.y_mean[o]; k.ystd[o] = m.y_std[o]; }
   return GPK_OK;
 }
 
@@ -843,12 +816,27 @@ static_assert(GPK_SMALL_COV_COUNTERS >= GPK_SMALL_MAX_MODELS * COV_COUNTERS, "co
 // the ticket counters of small_wtv_grad_kernel (one per model): the last GPK_SMALL_MAX_MODELS of h->d_cov_count
 constexpr int WTV_COUNTER0 = GPK_SMALL_COV_COUNTERS - GPK_SMALL_MAX_MODELS;
 static_assert(WTV_COUNTER0 >= GPK_SMALL_MAX_MODELS * COV_COUNTERS, "the covariance reduction's counters come first");
-// the two-factor forms (gpk_small_two_multi): model b takes slot b of the parameter block (its second factor: W2[b]), of the
+// the two-factor forms (F = 2): model b takes slot b of the parameter block (its second factor: W2[b]), of the
 // single ticket counts and of the work area's per-model shares; (model b, factor f) takes slot 2 b + f of the per-factor shares
 // and the group counters [b * COV2_COUNTERS + 1 + f * COV_GROUPS + g] of the covariance
 static_assert(WTV_COUNTER0 >= GPK_SMALL_MAX_MODELS * COV2_COUNTERS,
               "per model the top counter and the group counters of both factors, then small_wtv_grad_kernel's");
 static_assert(SR == GW, "small_wtv_grad_kernel takes as many columns of W per workgroup as small_var_kernel takes rows");
+
+// The instantiation a launch takes: one or two 16-query column blocks (M <= 16 or not), one or two inverse factors.
+auto var_kernel(int64_t M, int F) {
+  return M <= 16 ? (F == 2 ? small_var_kernel<1, true> : small_var_kernel<1, false>)
+                 : (F == 2 ? small_var_kernel<2, true> : small_var_kernel<2, false>);
+}
+auto var_grad_kernel(int64_t M, int F) {
+  return M <= 16 ? (F == 2 ? small_var_grad_kernel<1, true> : small_var_grad_kernel<1, false>)
+                 : (F == 2 ? small_var_grad_kernel<2, true> : small_var_grad_kernel<2, false>);
+}
+auto cov_kernel(int64_t M, int F) {
+  return M <= 16 ? (F == 2 ? small_cov_kernel<1, true> : small_cov_kernel<1, false>)
+                 : (F == 2 ? small_cov_kernel<2, true> : small_cov_kernel<2, false>);
+}
+auto wtv_grad_kernel(int F) { return F == 2 ? small_wtv_grad_kernel<true> : small_wtv_grad_kernel<false>; }
 
 }  // namespace
 
@@ -860,198 +848,60 @@ bool gpk_small_ok(int64_t Np, int D, int P, int64_t M) {
   return M >= 1 && M <= SQ && D >= 1 && D <= SD && P >= 1 && P <= SP && Np <= GPK_SMALL_MAX_NP;
 }
 
-int gpk_small_predict(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D, int P,
-                      const double* ls, const double* sf2, const double* y_mean, const double* y_std,
-                      const double* const* W, int64_t Np, int64_t ldw, const double* kss, double floor_,
-                      const double* Xq, int64_t M, double* work, double* mean_out, double* var_out) {
-  GPK_REQUIRE(h, B >= 1 && B <= GPK_SMALL_MAX_MODELS && (B == 1 || P == 1), "small predict: 1 model, or up to 8 single-output models");
-  GPK_REQUIRE(h, gpk_small_ok(Np, D, P, M) && Np == gpk_padded(N), "small predict: shape outside the small-batch path");
-  GPK_REQUIRE(h, !var_out || (W && ldw >= Np && ldw % 2 == 0), "small predict: variance needs the inverse factor");
-  SmallK k{};
-  GPK_TRY(small_params(h, "small predict", B, D, P, X, alpha, var_out ? W : nullptr, ls, sf2, var_out ? kss : nullptr, y_mean,
-                       y_std, k));
-  const unsigned ga = (unsigned)(Np / SJ), gb = (unsigned)(Np / SR);
-  const SmallWork wk = small_work(GPK_SMALL_PREDICT, Np, B, M, D, P);
-  double *Ks = work + wk.Ks, *pmean = work + wk.pmean, *pvar = work + wk.pvar;
-  if (var_out) {
-    hipLaunchKernelGGL(small_cross_mean_kernel<false>, dim3(ga, B), dim3(256), 0, h->stream, k, (long long)N, (long long)Np,
-                       D, P, Xq, (int)M, Ks, pmean, h->d_count, mean_out);
-    GPK_LAUNCH_CHECK(h);
-    if (M <= 16)
-      hipLaunchKernelGGL(small_var_kernel<1>, dim3(gb, B), dim3(64 * VW), 0, h->stream, k, (long long)ldw, (long long)Np, Ks,
-                         (int)M, P, floor_, pmean, ga, pvar, h->d_count + GPK_SMALL_MAX_MODELS, mean_out, var_out);
-    else
-      hipLaunchKernelGGL(small_var_kernel<2>, dim3(gb, B), dim3(64 * VW), 0, h->stream, k, (long long)ldw, (long long)Np, Ks,
-                         (int)M, P, floor_, pmean, ga, pvar, h->d_count + GPK_SMALL_MAX_MODELS, mean_out, var_out);
-  } else {
-    hipLaunchKernelGGL(small_cross_mean_kernel<true>, dim3(ga, B), dim3(256), 0, h->stream, k, (long long)N, (long long)Np,
-                       D, P, Xq, (int)M, (double*)nullptr, pmean, h->d_count, mean_out);
-  }
-  GPK_LAUNCH_CHECK(h);
-  return GPK_OK;
-}
-
-int gpk_small_cov_multi(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D, int P,
-                        const double* ls, const double* sf2, const double* y_mean, const double* y_std, const double* const* W,
-                        int64_t Np, int64_t ldw, const double* noise, const double* Xq, int64_t M, double* work,
-                        double* mean_out, double* cov_out) {
-  GPK_REQUIRE(h, B >= 1 && B <= GPK_SMALL_MAX_MODELS && (B == 1 || P == 1), "small cov: 1 model, or up to 8 single-output models");
-  GPK_REQUIRE(h, gpk_small_ok(Np, D, P, M) && Np == gpk_padded(N), "small cov: shape outside the small-batch path");
-  GPK_REQUIRE(h, X && alpha && noise && mean_out && cov_out, "small cov: null pointer");
-  GPK_REQUIRE(h, W && ldw >= Np && ldw % 2 == 0, "small cov: needs the inverse factor");
-  GPK_TRY(ensure_cov_counters(h));
-  SmallK k{};
-  GPK_TRY(small_params(h, "small cov", B, D, P, X, alpha, W, ls, sf2, nullptr, y_mean, y_std, k, noise));
-  const unsigned ga = (unsigned)(Np / SJ), gb = (unsigned)(Np / SR);
-  const SmallWork wk = small_work(GPK_SMALL_COV, Np, B, M, D, P);
-  double *Ks = work + wk.Ks, *pmean = work + wk.pmean, *pcov = work + wk.pcov, *gcov = work + wk.gcov;
-  hipLaunchKernelGGL(small_cross_mean_kernel<false>, dim3(ga, B), dim3(256), 0, h->stream, k, (long long)N, (long long)Np, D, P,
-                     Xq, (int)M, Ks, pmean, h->d_count, mean_out);
-  GPK_LAUNCH_CHECK(h);
-  if (M <= 16)
-    hipLaunchKernelGGL(small_cov_kernel<1>, dim3(gb, B), dim3(64 * VW), 0, h->stream, k, (long long)ldw, (long long)Np, Ks, (int)M,
-                       D, P, Xq, pmean, ga, pcov, gcov, h->d_cov_count, mean_out, cov_out);
-  else
-    hipLaunchKernelGGL(small_cov_kernel<2>, dim3(gb, B), dim3(64 * VW), 0, h->stream, k, (long long)ldw, (long long)Np, Ks, (int)M,
-                       D, P, Xq, pmean, ga, pcov, gcov, h->d_cov_count, mean_out, cov_out);
-  GPK_LAUNCH_CHECK(h);
-  return GPK_OK;
-}
-
-int gpk_small_grad_multi(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D, int P,
-                         const double* ls, const double* sf2, const double* y_mean, const double* y_std, const double* const* W,
-                         int64_t Np, int64_t ldw, const double* kss, double floor_, const double* Xq, int64_t M, double* work,
-                         double* mean_out, double* var_out, double* dmean_out, double* dvar_out) {
-  GPK_REQUIRE(h, B >= 1 && B <= GPK_SMALL_MAX_MODELS && (B == 1 || P == 1), "small grad: 1 model, or up to 8 single-output models");
-  GPK_REQUIRE(h, gpk_small_ok(Np, D, P, M) && Np == gpk_padded(N), "small grad: shape outside the small-batch path");
-  GPK_REQUIRE(h, X && alpha && mean_out && dmean_out && (var_out == nullptr) == (dvar_out == nullptr), "small grad: null pointer");
-  GPK_REQUIRE(h, !var_out || (W && kss && ldw >= Np && ldw % 2 == 0), "small grad: the variance gradient needs the inverse factor");
-  if (var_out) GPK_TRY(ensure_cov_counters(h));
-  SmallK k{};
-  GPK_TRY(small_params(h, "small grad", B, D, P, X, alpha, var_out ? W : nullptr, ls, sf2, var_out ? kss : nullptr, y_mean, y_std,
-                       k));
-  const unsigned ga = (unsigned)(Np / SJ), gb = (unsigned)(Np / SR);
-  const SmallWork wk = small_work(GPK_SMALL_GRAD, Np, B, M, D, P);
-  double *Ks = work + wk.Ks, *pmean = work + wk.pmean, *pvar = work + wk.pvar, *pjac = work + wk.pjac, *Vs = work + wk.Vs,
-         *pdv = work + wk.pdv;
-  if (!var_out) {
-    hipLaunchKernelGGL((small_cross_mean_jac_kernel<true>), dim3(ga, B), dim3(256), 0, h->stream, k, (long long)N,
-                       (long long)Np, D, P, Xq, (int)M, (double*)nullptr, pmean, h->d_count, mean_out, pjac, dmean_out);
-    GPK_LAUNCH_CHECK(h);
-    return GPK_OK;
-  }
-  hipLaunchKernelGGL(small_cross_mean_jac_kernel<false>, dim3(ga, B), dim3(256), 0, h->stream, k, (long long)N,
-                     (long long)Np, D, P, Xq, (int)M, Ks, pmean, h->d_count, mean_out, pjac, dmean_out);
-  GPK_LAUNCH_CHECK(h);
-  if (M <= 16)
-    hipLaunchKernelGGL(small_var_grad_kernel<1>, dim3(gb, B), dim3(64 * VW), 0, h->stream, k, (long long)ldw, (long long)Np,
-                       (const double*)Ks, (int)M, P, floor_, (const double*)pmean, ga, pvar, h->d_count + GPK_SMALL_MAX_MODELS,
-                       mean_out, var_out, Vs, (const double*)pjac, D, dmean_out);
-  else
-    hipLaunchKernelGGL(small_var_grad_kernel<2>, dim3(gb, B), dim3(64 * VW), 0, h->stream, k, (long long)ldw, (long long)Np,
-                       (const double*)Ks, (int)M, P, floor_, (const double*)pmean, ga, pvar, h->d_count + GPK_SMALL_MAX_MODELS,
-                       mean_out, var_out, Vs, (const double*)pjac, D, dmean_out);
-  GPK_LAUNCH_CHECK(h);
-  // up to 4 row chunks per column block while that keeps the launch within one workgroup per CU (Np = 1024: 64 x 4 for one
-  // model, 64 x 1 x 6 for six)
-  unsigned rc = 256 / (gb * (unsigned)B);
-  rc = rc < 1 ? 1 : (rc > WTV_MAX_ROW_CHUNKS ? WTV_MAX_ROW_CHUNKS : rc);
-  hipLaunchKernelGGL(small_wtv_grad_kernel, dim3(gb, rc, B), dim3(GT), 0, h->stream, k, (long long)ldw, (long long)N, (long long)Np, D,
-                     (const double*)Ks, (const double*)Vs, Xq, (int)M, pdv, h->d_cov_count + WTV_COUNTER0, dvar_out);
-  GPK_LAUNCH_CHECK(h);
-  return GPK_OK;
-}
-
-int gpk_small_two_multi(gpk_handle h, int call, int B, const double* const* X, const double* const* alpha, int64_t N, int D, int P,
-                        const double* ls, const double* sf2, const double* y_mean, const double* y_std, const double* const* W0,
-                        const double* const* W1, int64_t Np, int64_t ldw, const double* kss, double floor_, const double* noise,
-                        const double* Xq, int64_t M, double* work, double* mean_out, double* var_out, double* dmean_out,
-                        double* dvar_out, double* cov_out) {
-  GPK_REQUIRE(h, B >= 1 && B <= GPK_SMALL_MAX_MODELS && (B == 1 || P == 1), "small two-factor: 1 model, or up to 8 single-output models");
-  GPK_REQUIRE(h, gpk_small_ok(Np, D, P, M) && Np == gpk_padded(N), "small two-factor: shape outside the small-batch path");
-  GPK_REQUIRE(h, X && alpha && mean_out, "small two-factor: null pointer");
+int gpk_small_launch(gpk_handle h, int call, const ServeModels& m, const double* Xq, int64_t M, double* work, const ServeOut& out) {
   const bool grad = call == GPK_SMALL_GRAD, cov = call == GPK_SMALL_COV;
-  GPK_REQUIRE(h, call == GPK_SMALL_PREDICT || grad || cov, "small two-factor: unknown call");
-  GPK_REQUIRE(h, !grad || (dmean_out && (var_out == nullptr) == (dvar_out == nullptr)), "small two-factor: null pointer");
-  GPK_REQUIRE(h, !cov || (cov_out && noise), "small two-factor: null pointer");
-  const bool factors = cov || var_out;
-  GPK_REQUIRE(h, !factors || (W0 && W1 && ldw >= Np && ldw % 2 == 0), "small two-factor: needs both inverse factors");
-  GPK_REQUIRE(h, cov || !factors || kss, "small two-factor: null pointer");
+  GPK_REQUIRE(h, call == GPK_SMALL_PREDICT || grad || cov, "small-batch launch: unknown call");
+  const std::string name(cov ? "small cov" : grad ? "small grad" : "small predict");
+  const int B = m.B, D = m.D, P = m.P, F = m.F;
+  const long long N = m.N, Np = gpk_padded(m.N), ldw = m.ldw;
+  GPK_REQUIRE(h, B >= 1 && B <= GPK_SMALL_MAX_MODELS && (B == 1 || P == 1) && (F == 1 || F == 2),
+              name + ": 1 model, or up to 8 single-output models, of one or two inverse factors");
+  GPK_REQUIRE(h, gpk_small_ok(Np, D, P, M), name + ": shape outside the small-batch path");
+  GPK_REQUIRE(h, m.X && m.alpha && m.ls && m.sf2 && m.y_mean && m.y_std && Xq && work && out.mean, name + ": null pointer");
+  GPK_REQUIRE(h, !grad || (out.dmean && (out.var == nullptr) == (out.dvar == nullptr)), name + ": null pointer");
+  GPK_REQUIRE(h, !cov || (out.cov && m.noise), name + ": null pointer");
+  // the inverse factors enter with the variance (and its gradient) and with the covariance: the second and third launches
+  const bool factors = cov || out.var;
+  GPK_REQUIRE(h, !factors || (m.W[0] && (F == 1 || m.W[1]) && m.Np == Np && ldw >= Np && ldw % 2 == 0),
+              name + ": needs the inverse factor of every model (both of the two-factor form), padded, with an even ldw >= Np");
+  GPK_REQUIRE(h, cov || !factors || m.kss, name + ": null pointer");
   if (cov || (grad && factors)) GPK_TRY(ensure_cov_counters(h));
   SmallK k{};
-  GPK_TRY(small_params(h, "small two-factor", B, D, P, X, alpha, factors ? W0 : nullptr, ls, sf2, (factors && !cov) ? kss : nullptr,
-                       y_mean, y_std, k, cov ? noise : nullptr));
-  if (factors)
-    for (int b = 0; b < B; ++b) {
-      GPK_REQUIRE(h, W1[b] && ((uintptr_t)W1[b] % 16) == 0, "small two-factor: the inverse factor must be 16-byte aligned");
-      k.W2[b] = W1[b];
-    }
+  GPK_TRY(small_params(h, name, m, factors, cov, k));
   const unsigned ga = (unsigned)(Np / SJ), gb = (unsigned)(Np / SR);
   // K*, the mean and the Jacobian shares once per model, every other share per (model, factor)
-  const SmallWork wk = small_work(call, Np, B, M, D, P, 2);
-  double *Ks = work + wk.Ks, *pmean = work + wk.pmean;
-  const dim3 g1(ga, B), g2(gb, 2 * B), b1(256), b2(64 * VW);
-  if (!factors) {      // the mean, or the mean and its Jacobian: one launch
-    if (grad)
-      hipLaunchKernelGGL((small_cross_mean_jac_kernel<true>), g1, b1, 0, h->stream, k, (long long)N, (long long)Np, D, P, Xq, (int)M,
-                         (double*)nullptr, pmean, h->d_count, mean_out, work + wk.pjac, dmean_out);
-    else
-      hipLaunchKernelGGL(small_cross_mean_kernel<true>, g1, b1, 0, h->stream, k, (long long)N, (long long)Np, D, P, Xq, (int)M,
-                         (double*)nullptr, pmean, h->d_count, mean_out);
-    GPK_LAUNCH_CHECK(h);
-    return GPK_OK;
-  }
-  unsigned* vcount = h->d_count + GPK_SMALL_MAX_MODELS;
-  if (grad) {
-    double *pvar = work + wk.pvar, *pjac = work + wk.pjac, *Vs = work + wk.Vs, *pdv = work + wk.pdv;
-    hipLaunchKernelGGL(small_cross_mean_jac_kernel<false>, g1, b1, 0, h->stream, k, (long long)N, (long long)Np, D, P, Xq, (int)M, Ks,
-                       pmean, h->d_count, mean_out, pjac, dmean_out);
-    GPK_LAUNCH_CHECK(h);
-    if (M <= 16)
-      hipLaunchKernelGGL(small_var2_grad_kernel<1>, g2, b2, 0, h->stream, k, (long long)ldw, (long long)Np, (const double*)Ks, (int)M,
-                         P, floor_, (const double*)pmean, ga, pvar, vcount, mean_out, var_out, Vs, (const double*)pjac, D, dmean_out);
-    else
-      hipLaunchKernelGGL(small_var2_grad_kernel<2>, g2, b2, 0, h->stream, k, (long long)ldw, (long long)Np, (const double*)Ks, (int)M,
-                         P, floor_, (const double*)pmean, ga, pvar, vcount, mean_out, var_out, Vs, (const double*)pjac, D, dmean_out);
-    GPK_LAUNCH_CHECK(h);
-    // Row chunks: the rule of gpk_small_grad_multi with the two factors of ONE model counted as two models, whatever B is.  A
-    // share is not linear in its chunk's bits (C enters an fma chain), so a count that fell with B would give a model other
-    // bits inside a batch than alone; a function of Np alone keeps every sum's order fixed by (Np, M).
-    unsigned rc = 256 / (gb * 2u);
-    rc = rc < 1 ? 1 : (rc > WTV_MAX_ROW_CHUNKS ? WTV_MAX_ROW_CHUNKS : rc);
-    hipLaunchKernelGGL(small_wtv2_grad_kernel, dim3(gb, rc, 2 * B), dim3(GT), 0, h->stream, k, (long long)ldw, (long long)N, (long long)Np,
-                       D, (const double*)Ks, (const double*)Vs, Xq, (int)M, pdv, h->d_cov_count + WTV_COUNTER0, dvar_out);
-    GPK_LAUNCH_CHECK(h);
-    return GPK_OK;
-  }
-  hipLaunchKernelGGL(small_cross_mean_kernel<false>, g1, b1, 0, h->stream, k, (long long)N, (long long)Np, D, P, Xq, (int)M, Ks, pmean,
-                     h->d_count, mean_out);
+  const SmallWork wk = small_work(call, Np, B, M, D, P, F);
+  double *Ks = work + wk.Ks, *pmean = work + wk.pmean, *pjac = work + wk.pjac;
+  const dim3 g1(ga, B), g2(gb, B * F), b1(256), b2(64 * VW);
+  // The first launch.  Nothing follows (the mean, or the mean and its Jacobian): FINISH, and K* is not stored.
+  if (grad)
+    hipLaunchKernelGGL(factors ? small_cross_mean_jac_kernel<false> : small_cross_mean_jac_kernel<true>, g1, b1, 0, h->stream, k, N, Np,
+                       D, P, Xq, (int)M, factors ? Ks : nullptr, pmean, h->d_count, out.mean, pjac, out.dmean);
+  else
+    hipLaunchKernelGGL(factors ? small_cross_mean_kernel<false> : small_cross_mean_kernel<true>, g1, b1, 0, h->stream, k, N, Np, D, P,
+                       Xq, (int)M, factors ? Ks : nullptr, pmean, h->d_count, out.mean);
   GPK_LAUNCH_CHECK(h);
+  if (!factors) return GPK_OK;
+  unsigned* vcount = h->d_count + GPK_SMALL_MAX_MODELS;
   if (cov) {
-    double *pcov = work + wk.pcov, *gcov = work + wk.gcov;
-    if (M <= 16)
-      hipLaunchKernelGGL(small_cov2_kernel<1>, g2, b2, 0, h->stream, k, (long long)ldw, (long long)Np, (const double*)Ks, (int)M, D, P,
-                         Xq, (const double*)pmean, ga, pcov, gcov, h->d_cov_count, mean_out, cov_out);
-    else
-      hipLaunchKernelGGL(small_cov2_kernel<2>, g2, b2, 0, h->stream, k, (long long)ldw, (long long)Np, (const double*)Ks, (int)M, D, P,
-                         Xq, (const double*)pmean, ga, pcov, gcov, h->d_cov_count, mean_out, cov_out);
+    hipLaunchKernelGGL(cov_kernel(M, F), g2, b2, 0, h->stream, k, ldw, Np, Ks, (int)M, D, P, Xq, pmean, ga, work + wk.pcov,
+                       work + wk.gcov, h->d_cov_count, out.mean, out.cov);
+  } else if (!grad) {
+    hipLaunchKernelGGL(var_kernel(M, F), g2, b2, 0, h->stream, k, ldw, Np, Ks, (int)M, P, m.floor_, pmean, ga, work + wk.pvar, vcount,
+                       out.mean, out.var);
   } else {
-    double* pvar = work + wk.pvar;
-    if (M <= 16)
-      hipLaunchKernelGGL(small_var2_kernel<1>, g2, b2, 0, h->stream, k, (long long)ldw, (long long)Np, (const double*)Ks, (int)M, P,
-                         floor_, (const double*)pmean, ga, pvar, vcount, mean_out, var_out);
-    else
-      hipLaunchKernelGGL(small_var2_kernel<2>, g2, b2, 0, h->stream, k, (long long)ldw, (long long)Np, (const double*)Ks, (int)M, P,
-                         floor_, (const double*)pmean, ga, pvar, vcount, mean_out, var_out);
+    hipLaunchKernelGGL(var_grad_kernel(M, F), g2, b2, 0, h->stream, k, ldw, Np, Ks, (int)M, P, m.floor_, pmean, ga, work + wk.pvar,
+                       vcount, out.mean, out.var, work + wk.Vs, pjac, D, out.dmean);
+    GPK_LAUNCH_CHECK(h);
+    // Row chunks of the W^T V launch: up to 4 per column block while that keeps the launch within one workgroup per CU (Np =
+    // 1024: 64 x 4 for one model, 64 x 1 x 6 for six).  F = 1 counts the B models.  F = 2 counts the two factors of ONE model as
+    // two models, whatever B is: a share is not linear in its chunk's bits (C enters an fma chain), so a count that fell with B
+    // would give a model other bits inside a batch than alone; a function of Np alone keeps every sum's order fixed by (Np, M).
+    unsigned rc = 256 / (gb * (F == 2 ? 2u : (unsigned)B));
+    rc = rc < 1 ? 1 : (rc > WTV_MAX_ROW_CHUNKS ? WTV_MAX_ROW_CHUNKS : rc);
+    hipLaunchKernelGGL(wtv_grad_kernel(F), dim3(gb, rc, B * F), dim3(GT), 0, h->stream, k, ldw, N, Np, D, Ks, work + wk.Vs, Xq, (int)M,
+                       work + wk.pdv, h->d_cov_count + WTV_COUNTER0, out.dvar);
   }
   GPK_LAUNCH_CHECK(h);
   return GPK_OK;
-}
-
-int gpk_small_two(gpk_handle h, int call, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
-                  double sf2, const double* y_mean, const double* y_std, const double* W0, const double* W1, int64_t Np,
-                  int64_t ldw, double kss, double floor_, double noise, const double* Xq, int64_t M, double* work,
-                  double* mean_out, double* var_out, double* dmean_out, double* dvar_out, double* cov_out) {
-  return gpk_small_two_multi(h, call, 1, &X, &alpha, N, D, P, ls, &sf2, y_mean, y_std, W0 ? &W0 : nullptr, W1 ? &W1 : nullptr, Np, ldw,
-                             &kss, floor_, &noise, Xq, M, work, mean_out, var_out, dmean_out, dvar_out, cov_out);
 }

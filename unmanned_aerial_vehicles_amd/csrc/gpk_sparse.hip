@@ -26,8 +26,8 @@
 //
 // The assembly (gpk_sparse_finalize) is host code over entries that exist: gpk_gram / gpk_potrf / gpk_trtri, tile GEMMs with
 // triangular k-ranges, gpk_lml_terms.  The serving (gpk_sparse_predict, gpk_sparse_predict_grad, gpk_sparse_predict_cov): up to
-// 32 queries the two-factor form of the small-batch kernels (gpk_small.hip, gpk_small_two through gpk_serve_two: one K*, P
-// outputs, the inverse factors Wuu and WSigma as a grid dimension, combined by the last workgroup); larger batches the
+// 32 queries the two-factor form of the small-batch kernels (gpk_small.hip, through the serving routines of gpk_serve.hip: one
+// K*, P outputs, the inverse factors Wuu and WSigma as a grid dimension, combined by the last workgroup); larger batches the
 // query-panel loop (gpk_compose.h, shared with gpk_model.hip and gpk_bmodel.hip) over gpk_predict_mean, gpk_predict_var_inv,
 // gpk_predict_mean_grad and gpk_predict_var_grad_inv once per factor with a small combining launch, and for the covariance the
 // stacked panel [Wuu K*; WSigma K*] with ONE symmetric tile GEMM.  The buffers are gpk_dev members of the object.  DESIGN.md, K9.
@@ -1004,6 +1004,56 @@ extern "C" int gpk_sparse_bound(gpk_handle h, double* bound, int64_t* n_rows) {
   return GPK_OK;
 }
 
+namespace {
+
+// The one place that takes sparse models apart for the serving routines (gpk_serve.hip): one model with its P outputs, or B
+// single-output models of equal m and D, as the two-factor description - the inducing inputs as the training inputs, alpha_u,
+// W[0] = Wuu, W[1] = WSigma.  The description points into this object.
+struct SparseServe {
+  int B = 0, D = 0, P = 0;
+  int64_t m = 0, mp = 0;
+  gpk_sparse* s[GPK_SMALL_MAX_MODELS] = {nullptr};
+  const double *Z[GPK_SMALL_MAX_MODELS], *alpha[GPK_SMALL_MAX_MODELS], *W0[GPK_SMALL_MAX_MODELS], *W1[GPK_SMALL_MAX_MODELS];
+  double ls[GPK_SMALL_MAX_MODELS * GPK_MAX_D_PREDICT], sf2[GPK_SMALL_MAX_MODELS], kss[GPK_SMALL_MAX_MODELS],
+      noise[GPK_SMALL_MAX_MODELS], y_mean[GPK_MAX_P], y_std[GPK_MAX_P], floor_ = 0.0;
+  static_assert(GPK_SMALL_MAX_MODELS <= GPK_MAX_P, "y_mean / y_std: P outputs of one model, or one of each of B models");
+
+  void fill(int B_, gpk_sparse* const* models, int var_includes_noise) {
+    B = B_; D = models[0]->D; P = models[0]->P; m = models[0]->m; mp = models[0]->mp;
+    floor_ = gpk_var_floor(var_includes_noise);
+    for (int b = 0; b < B; ++b) {
+      gpk_sparse* sp = s[b] = models[b];
+      Z[b] = sp->Z; alpha[b] = sp->alpha; W0[b] = sp->Wuu; W1[b] = sp->WS;
+      for (int d = 0; d < D; ++d) ls[b * D + d] = sp->ls[d];
+      sf2[b] = sp->sf2; noise[b] = sp->noise; kss[b] = gpk_kss(sp->sf2, sp->noise, var_includes_noise);
+      for (int p = 0; p < P; ++p) { y_mean[b * P + p] = sp->y_mean[p]; y_std[b * P + p] = sp->y_std[p]; }
+    }
+  }
+  ServeModels models() const { return {B, P, 2, Z, alpha, m, D, ls, sf2, y_mean, y_std, {W0, W1}, mp, mp, kss, floor_, noise}; }
+  // up to 32 queries: the two-factor small-batch kernels (gpk_small.hip) - one K* per model, the two inverse factors combined on
+  // the device, the launch counts of one single-output model, one synchronisation
+  bool small(gpk_handle h, int64_t M) const { return h->small_path && M <= GPK_SMALL_MAX_M && gpk_small_ok(mp, D, P, M); }
+  // The small route's dvar (B, M, D), and cov (B, M, M) of either route, come in normalised-target units: output p of model b
+  // carries y_std[b * P + p]^2, as in gpk_predict_model_grad / gpk_predict_model_cov.  dvar (B, M, P, D); cov (B, P, M, M);
+  // P == 1: in place if the caller likes.
+  void scale_dvar(const double* g, int64_t M, double* dvar) const {
+    for (int64_t i = 0; i < B * M; ++i)
+      for (int p = 0; p < P; ++p) {
+        const double s2 = y_std[i / M * P + p] * y_std[i / M * P + p];
+        for (int d = 0; d < D; ++d) dvar[(i * P + p) * D + d] = g[i * D + d] * s2;
+      }
+  }
+  void scale_cov(const double* sig, int64_t M, double* cov) const {
+    const size_t nc = (size_t)M * M;
+    for (int o = 0; o < B * P; ++o) {
+      const double s2 = y_std[o] * y_std[o];
+      for (size_t i = 0; i < nc; ++i) cov[o * nc + i] = sig[o / P * nc + i] * s2;
+    }
+  }
+};
+
+}  // namespace
+
 // The serving bodies take the object apart from the handle: h supplies the stream, the pinned staging block and the work area,
 // s the model and its own panel staging (the single entries: s = h->sparse; the batch entries: one model of the list).
 static int sparse_predict(gpk_handle h, gpk_sparse* s, const double* Xq, int64_t M, double* mean, double* var,
@@ -1016,12 +1066,9 @@ static int sparse_predict(gpk_handle h, gpk_sparse* s, const double* Xq, int64_t
   const double kss = gpk_kss(s->sf2, s->noise, var_includes_noise), floor_ = gpk_var_floor(var_includes_noise);
   const double none = -std::numeric_limits<double>::max();
   const int64_t m = s->m, mp = s->mp;
-  if (h->small_path && M <= GPK_SMALL_MAX_M && gpk_small_ok(mp, D, P, M)) {
-    // the two-factor small-batch kernels (gpk_small.hip): one K*, P outputs, the two inverse factors combined on the device -
-    // the mean one launch, mean + variance two, one synchronisation, whatever P is
-    return gpk_serve_two(h, GPK_SMALL_PREDICT, s->Z, s->alpha, m, D, P, s->ls, s->sf2, s->y_mean, s->y_std, var ? s->Wuu.p : nullptr,
-                         var ? s->WS.p : nullptr, mp, mp, kss, floor_, 0.0, Xq, M, mean, var, nullptr, nullptr, nullptr);
-  }
+  SparseServe sv;
+  sv.fill(1, &s, var_includes_noise);
+  if (sv.small(h, M)) return gpk_serve_predict(h, sv.models(), true, Xq, M, mean, var);      // the mean one launch, mean + variance two
   // query panels: the fused mean and two variance launches (one per inverse factor), combined on the device
   const int64_t panel = gpk_panel_rows(GPK_HOST_MAX_M, 1, M);      // (no byte budget: at most GPK_HOST_MAX_M rows)
   const size_t nq = (size_t)panel * D, nm = (size_t)panel * P;
@@ -1065,18 +1112,12 @@ static int sparse_predict_grad(gpk_handle h, gpk_sparse* s, const double* Xq, in
   const double kss = gpk_kss(s->sf2, s->noise, var_includes_noise), floor_ = gpk_var_floor(var_includes_noise);
   const double none = -std::numeric_limits<double>::max();
   const int64_t m = s->m, mp = s->mp;
-  if (h->small_path && M <= GPK_SMALL_MAX_M && gpk_small_ok(mp, D, P, M)) {
-    // mean + Jacobian one launch, all four results three, one synchronisation (gpk_small.hip, the two-factor kernels)
+  SparseServe sv;
+  sv.fill(1, &s, var_includes_noise);
+  if (sv.small(h, M)) {      // mean + Jacobian one launch, all four results three
     std::vector<double> g1(var ? (size_t)M * D : 0);
-    GPK_TRY(gpk_serve_two(h, GPK_SMALL_GRAD, s->Z, s->alpha, m, D, P, s->ls, s->sf2, s->y_mean, s->y_std, var ? s->Wuu.p : nullptr,
-                          var ? s->WS.p : nullptr, mp, mp, kss, floor_, 0.0, Xq, M, mean, var, dmean, var ? g1.data() : nullptr,
-                          nullptr));
-    if (var)      // output p carries y_std[p]^2, as in gpk_predict_model_grad
-      for (int64_t i = 0; i < M; ++i)
-        for (int p = 0; p < P; ++p) {
-          const double s2 = s->y_std[p] * s->y_std[p];
-          for (int d = 0; d < D; ++d) dvar[(i * P + p) * D + d] = g1[(size_t)i * D + d] * s2;
-        }
+    GPK_TRY(gpk_serve_grad(h, sv.models(), true, Xq, M, mean, var, dmean, var ? g1.data() : nullptr));
+    if (var) sv.scale_dvar(g1.data(), M, dvar);
     return GPK_OK;
   }
   // query panels: the fused mean and its Jacobian, the variance gradient once per inverse factor (three mp x panel work panels
@@ -1124,10 +1165,10 @@ static int sparse_predict_cov(gpk_handle h, gpk_sparse* s, const double* Xq, int
   GPK_TRY(gpk_require_finite(h, Xq, M * D, "sparse_predict_cov", "Xq"));
   const int64_t m = s->m, mp = s->mp;
   std::vector<double> sig((size_t)M * M);
-  if (h->small_path && M <= GPK_SMALL_MAX_M && gpk_small_ok(mp, D, P, M)) {
-    // two launches, one synchronisation (gpk_small.hip, the two-factor kernels)
-    GPK_TRY(gpk_serve_two(h, GPK_SMALL_COV, s->Z, s->alpha, m, D, P, s->ls, s->sf2, s->y_mean, s->y_std, s->Wuu, s->WS, mp, mp, 0.0,
-                          0.0, s->noise, Xq, M, mean, nullptr, nullptr, nullptr, sig.data()));
+  SparseServe sv;
+  sv.fill(1, &s, 1);
+  if (sv.small(h, M)) {      // two launches
+    GPK_TRY(gpk_serve_cov(h, sv.models(), true, Xq, M, mean, sig.data()));
   } else {
     // one panel: K* (training-major), the stacked panel [V0; V1] = [Wuu K*; WSigma K*] by two tile GEMMs (the inverse factors'
     // zero triangles skipped), its copy [V0; -V1], and ONE symmetric product of depth 2 mp whose epilogue forms
@@ -1160,12 +1201,7 @@ static int sparse_predict_cov(gpk_handle h, gpk_sparse* s, const double* Xq, int
       return GPK_OK;
     }));
   }
-  // output p: y_std[p]^2 Sigma, as in gpk_predict_model_cov
-  for (int p = 0; p < P; ++p) {
-    const double s2 = s->y_std[p] * s->y_std[p];
-    double* out = cov + (size_t)p * M * M;
-    for (size_t i = 0; i < (size_t)M * M; ++i) out[i] = sig[i] * s2;
-  }
+  sv.scale_cov(sig.data(), M, cov);
   return GPK_OK;
 }
 
@@ -1179,44 +1215,26 @@ extern "C" int gpk_sparse_predict_cov(gpk_handle h, const double* Xq, int64_t M,
 // ---- the per-axis batch: B single-output sparse models on one query batch ---------------------------------------------------
 namespace {
 
-// The checks the three batch entries share, and the models' parameters in the layout of gpk_serve_two_multi.
-struct SparseBatch {
-  int B = 0, D = 0;
-  int64_t m = 0, mp = 0;
-  gpk_sparse* s[GPK_SMALL_MAX_MODELS] = {nullptr};
-  const double *Z[GPK_SMALL_MAX_MODELS], *alpha[GPK_SMALL_MAX_MODELS], *W0[GPK_SMALL_MAX_MODELS], *W1[GPK_SMALL_MAX_MODELS];
-  double ls[GPK_SMALL_MAX_MODELS * GPK_MAX_D_PREDICT], sf2[GPK_SMALL_MAX_MODELS], kss[GPK_SMALL_MAX_MODELS],
-      noise[GPK_SMALL_MAX_MODELS], y_mean[GPK_SMALL_MAX_MODELS], y_std[GPK_SMALL_MAX_MODELS];
-};
+// The checks the three batch entries share, then the models taken apart.
 int sparse_batch(gpk_handle h, const char* who, int B, const gpk_handle* models, const double* Xq, int64_t M, int64_t max_M,
-                 int var_includes_noise, SparseBatch& sb) {
+                 int var_includes_noise, SparseServe& sb) {
   const std::string name(who);
   GPK_REQUIRE(h, B >= 1 && B <= GPK_SMALL_MAX_MODELS, name + ": 1..8 models");
   GPK_REQUIRE(h, models && Xq && M >= 1, name + ": null pointer or empty batch");
   GPK_REQUIRE(h, max_M <= 0 || M <= max_M, name + ": M outside [1, 16384]");
   GPK_REQUIRE(h, h->batch == 1, "composite calls are not available in batched mode");
+  gpk_sparse* list[GPK_SMALL_MAX_MODELS];
   for (int b = 0; b < B; ++b) {
     GPK_REQUIRE(h, models[b], name + ": null handle in the list of models");
-    gpk_sparse* s = models[b]->sparse;
+    gpk_sparse* s = list[b] = models[b]->sparse;
     GPK_REQUIRE(h, s && s->finalized, name + ": a model is not a finalised sparse model (call gpk_sparse_finalize first)");
     GPK_REQUIRE(h, models[b]->device == h->device, name + ": every model must live on the serving handle's device");
     GPK_REQUIRE(h, s->P == 1, name + ": every model must have one output");
-    GPK_REQUIRE(h, b == 0 || (s->m == sb.s[0]->m && s->D == sb.s[0]->D), name + ": the models must agree in m and D");
-    sb.s[b] = s;
+    GPK_REQUIRE(h, b == 0 || (s->m == list[0]->m && s->D == list[0]->D), name + ": the models must agree in m and D");
   }
-  sb.B = B; sb.D = sb.s[0]->D; sb.m = sb.s[0]->m; sb.mp = sb.s[0]->mp;
-  GPK_TRY(gpk_require_finite(h, Xq, M * sb.D, who, "Xq"));
-  for (int b = 0; b < B; ++b) {
-    const gpk_sparse* s = sb.s[b];
-    sb.Z[b] = s->Z; sb.alpha[b] = s->alpha; sb.W0[b] = s->Wuu; sb.W1[b] = s->WS;
-    for (int d = 0; d < sb.D; ++d) sb.ls[b * sb.D + d] = s->ls[d];
-    sb.sf2[b] = s->sf2; sb.noise[b] = s->noise; sb.kss[b] = gpk_kss(s->sf2, s->noise, var_includes_noise);
-    sb.y_mean[b] = s->y_mean[0]; sb.y_std[b] = s->y_std[0];
-  }
+  GPK_TRY(gpk_require_finite(h, Xq, M * list[0]->D, who, "Xq"));
+  sb.fill(B, list, var_includes_noise);
   return GPK_OK;
-}
-bool sparse_batch_small(gpk_handle h, const SparseBatch& sb, int64_t M) {
-  return h->small_path && M <= GPK_SMALL_MAX_M && gpk_small_ok(sb.mp, sb.D, 1, M);
 }
 
 }  // namespace
@@ -1224,16 +1242,14 @@ bool sparse_batch_small(gpk_handle h, const SparseBatch& sb, int64_t M) {
 extern "C" int gpk_sparse_predict_multi(gpk_handle h, int B, const gpk_handle* models, const double* Xq, int64_t M, double* mean,
                                         double* var, int var_includes_noise) {
   if (!h) return GPK_BAD_ARG;
-  SparseBatch sb;
+  SparseServe sb;
   GPK_TRY(sparse_batch(h, "sparse_predict_multi", B, models, Xq, M, 0, var_includes_noise, sb));
   GPK_REQUIRE(h, mean, "sparse_predict_multi: null pointer");
   GPK_CHECK_HIP(h, hipSetDevice(h->device));
   const size_t n = (size_t)B * M;
   std::vector<double> mn(n), vr(var ? n : 0);
-  if (sparse_batch_small(h, sb, M)) {
-    GPK_TRY(gpk_serve_two_multi(h, GPK_SMALL_PREDICT, B, sb.Z, sb.alpha, sb.m, sb.D, 1, sb.ls, sb.sf2, sb.y_mean, sb.y_std,
-                                var ? sb.W0 : nullptr, var ? sb.W1 : nullptr, sb.mp, sb.mp, sb.kss, gpk_var_floor(var_includes_noise),
-                                sb.noise, Xq, M, mn.data(), var ? vr.data() : nullptr, nullptr, nullptr, nullptr));
+  if (sb.small(h, M)) {
+    GPK_TRY(gpk_serve_predict(h, sb.models(), true, Xq, M, mn.data(), var ? vr.data() : nullptr));
   } else {      // model by model through the panels of the single entry
     for (int b = 0; b < B; ++b)
       GPK_TRY(sparse_predict(h, sb.s[b], Xq, M, mn.data() + (size_t)b * M, var ? vr.data() + (size_t)b * M : nullptr, var_includes_noise));
@@ -1246,7 +1262,7 @@ extern "C" int gpk_sparse_predict_multi(gpk_handle h, int B, const gpk_handle* m
 extern "C" int gpk_sparse_predict_multi_grad(gpk_handle h, int B, const gpk_handle* models, const double* Xq, int64_t M, double* mean,
                                              double* var, double* dmean, double* dvar, int var_includes_noise) {
   if (!h) return GPK_BAD_ARG;
-  SparseBatch sb;
+  SparseServe sb;
   GPK_TRY(sparse_batch(h, "sparse_predict_multi_grad", B, models, Xq, M, 0, var_includes_noise, sb));
   GPK_REQUIRE(h, mean && dmean, "sparse_predict_multi_grad: null pointer");
   GPK_REQUIRE(h, (var == nullptr) == (dvar == nullptr), "sparse_predict_multi_grad: var and dvar come together (both or neither)");
@@ -1254,15 +1270,9 @@ extern "C" int gpk_sparse_predict_multi_grad(gpk_handle h, int B, const gpk_hand
   const int D = sb.D;
   const size_t n = (size_t)B * M, nd = n * D;
   std::vector<double> mn(n), dm(nd), vr(var ? n : 0), dv(var ? nd : 0);
-  if (sparse_batch_small(h, sb, M)) {
-    GPK_TRY(gpk_serve_two_multi(h, GPK_SMALL_GRAD, B, sb.Z, sb.alpha, sb.m, D, 1, sb.ls, sb.sf2, sb.y_mean, sb.y_std,
-                                var ? sb.W0 : nullptr, var ? sb.W1 : nullptr, sb.mp, sb.mp, sb.kss, gpk_var_floor(var_includes_noise),
-                                sb.noise, Xq, M, mn.data(), var ? vr.data() : nullptr, dm.data(), var ? dv.data() : nullptr, nullptr));
-    if (var)      // model b carries y_std[b]^2, as in gpk_sparse_predict_grad
-      for (int b = 0; b < B; ++b) {
-        const double s2 = sb.y_std[b] * sb.y_std[b];
-        for (size_t i = 0; i < (size_t)M * D; ++i) dv[(size_t)b * M * D + i] = dv[(size_t)b * M * D + i] * s2;
-      }
+  if (sb.small(h, M)) {
+    GPK_TRY(gpk_serve_grad(h, sb.models(), true, Xq, M, mn.data(), var ? vr.data() : nullptr, dm.data(), var ? dv.data() : nullptr));
+    if (var) sb.scale_dvar(dv.data(), M, dv.data());
   } else {
     for (int b = 0; b < B; ++b)
       GPK_TRY(sparse_predict_grad(h, sb.s[b], Xq, M, mn.data() + (size_t)b * M, var ? vr.data() + (size_t)b * M : nullptr,
@@ -1280,20 +1290,15 @@ extern "C" int gpk_sparse_predict_multi_grad(gpk_handle h, int B, const gpk_hand
 extern "C" int gpk_sparse_predict_multi_cov(gpk_handle h, int B, const gpk_handle* models, const double* Xq, int64_t M, double* mean,
                                             double* cov) {
   if (!h) return GPK_BAD_ARG;
-  SparseBatch sb;
+  SparseServe sb;
   GPK_TRY(sparse_batch(h, "sparse_predict_multi_cov", B, models, Xq, M, 16384, 1, sb));
   GPK_REQUIRE(h, mean && cov, "sparse_predict_multi_cov: null pointer");
   GPK_CHECK_HIP(h, hipSetDevice(h->device));
   const size_t n = (size_t)B * M, nc = (size_t)M * M;
   std::vector<double> mn(n);
-  if (sparse_batch_small(h, sb, M)) {
-    GPK_TRY(gpk_serve_two_multi(h, GPK_SMALL_COV, B, sb.Z, sb.alpha, sb.m, sb.D, 1, sb.ls, sb.sf2, sb.y_mean, sb.y_std, sb.W0, sb.W1,
-                                sb.mp, sb.mp, nullptr, 0.0, sb.noise, Xq, M, mn.data(), nullptr, nullptr, nullptr, cov));
-    for (int b = 0; b < B; ++b) {      // block b: y_std[b]^2 Sigma_b, as in gpk_sparse_predict_cov
-      const double s2 = sb.y_std[b] * sb.y_std[b];
-      double* out = cov + (size_t)b * nc;
-      for (size_t i = 0; i < nc; ++i) out[i] = out[i] * s2;
-    }
+  if (sb.small(h, M)) {
+    GPK_TRY(gpk_serve_cov(h, sb.models(), true, Xq, M, mn.data(), cov));
+    sb.scale_cov(cov, M, cov);
   } else {
     for (int b = 0; b < B; ++b) GPK_TRY(sparse_predict_cov(h, sb.s[b], Xq, M, mn.data() + (size_t)b * M, cov + (size_t)b * nc));
   }
