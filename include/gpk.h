@@ -73,7 +73,8 @@ GPK_API int64_t gpk_padded(int64_t n);
  * the cross-check.  No reference counterpart (the reference has no instrumentation on this path).        */
 /* gpk_set_option: the handle's tuning knobs (the library reads NOTHING from the environment), settable on a live handle:
  * "k5_split2_tile" (gpk_predict_var_inv_split2: 0 = the tallest of the 512 / 256 / 128 x 128 tiles that still comes in at
- * least 512 tiles, 1 = always 128 x 128, 2 = 512 x 128 whenever Np % 512 == 0), "small_path", "trsm256",
+ * least 512 tiles, 1 = always 128 x 128, 2 = 512 x 128 whenever Np % 512 == 0, 3 = 256 x 128 whenever Np % 256 == 0 and as 0
+ * otherwise), "small_path", "trsm256",
  * "trtri_levels", "gemm_small_tiles" / "gemm_tiny_tiles" (launches of fewer 128 x 128 tiles than these - 1024 / 320 - run on 64 x 64 /,
  * fp64 only, 32 x 32 tiles; bit-identical results), "k3_stream_min_np", "ptile" (gpk_potrf: 1 = the one-launch tile factorisation of
  * gpk_ptile.hip for 512 <= Np <= "ptile_max_np" (24576), 0 = the recursive launch chain), "ptile_prog_max_nt" (that launch:
@@ -87,6 +88,9 @@ GPK_API int64_t gpk_padded(int64_t n);
  * static tile mapping; bit-identical results), "gemm_balanced_max_tiles", "gemm_log" (1: every tile-GEMM launch to stderr),
  * "gram_log" (1: the form of every gpk_gram launch - `GPKGRAM f64|f32 N Np D strip|sym gsG ntT gridNNN` - and of every gpk_predict_mean /
  * gpk_predict_mean_multi launch - `GPKMEAN f64|f32 N M D P|B d4 p4 granG sS chunkC` - to stderr, one line per launch),
+ * "k5_log" (1: the form of every 16-bit variance launch - gpk_predict_var_inv_split2 / gpk_predict_mean_var_split2: `GPKK5 direct rowsR
+ * ntmTA ntnB nstS padP gridG`, gpk_predict_var_inv_split: `GPKK5 split rowsR ntmTA ntnB nstS pad0 gridG`; R the tile's rows, A x B tiles,
+ * S super-tiles, P tile slots per band of the walk - to stderr, one line per launch),
  * "sparse_panel" / "sparse_slabs" (the statistics pass of the sparse model, K9:
  * rows per panel and k-slabs per panel product; 0 = the built-in rule), "debug_fill" (1: the handle's scratch and serving work area are overwritten with NaN bytes at every request - the test
  * suite runs with it).  Used by the A/B timings and by the tests that pin a fast path to its plain form.

@@ -72,7 +72,7 @@ extern "C" int gpk_set_option(gpk_handle h, const char* name, int value) {
   if (!h) return GPK_BAD_ARG;
   GPK_REQUIRE(h, name, "set_option: null name");
   const std::string n(name);
-  if (n == "k5_split2_tile") h->k5_split2_tile = (value >= 0 && value <= 2) ? value : 0;
+  if (n == "k5_split2_tile") h->k5_split2_tile = (value >= 0 && value <= 3) ? value : 0;
   else if (n == "small_path") h->small_path = value;
   else if (n == "trsm256") h->trsm256 = value;
   else if (n == "trtri_levels") h->trtri_levels = value;
@@ -83,6 +83,7 @@ extern "C" int gpk_set_option(gpk_handle h, const char* name, int value) {
   else if (n == "k3_stream_min_np") h->k3_stream_min_np = value;
   else if (n == "gemm_log") h->gemm_log = value;
   else if (n == "gram_log") h->gram_log = value;
+  else if (n == "k5_log") h->k5_log = value;
   else if (n == "debug_fill") h->debug_fill = value ? 1 : 0;
   else if (n == "sparse_panel") h->sparse_panel = value <= 0 ? 0 : value > (1 << 20) ? (1 << 20) : value;
   else if (n == "sparse_slabs") h->sparse_slabs = value <= 0 ? 0 : value > 64 ? 64 : value;

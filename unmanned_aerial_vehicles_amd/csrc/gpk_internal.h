@@ -49,7 +49,7 @@ struct gpk_context {
   int k3_stream_min_np = 512;    // gpk_potrs_inv: streaming matrix-vector passes from this padded size up (P <= 6); measured faster than the two
                                  // 128-column tile GEMMs from there on (N = 4096: 0.11 against 0.35 ms, profiles/r04_k3_ab.log)
   int k5_split2_tile = 0;    // fp16 x 2 variance launch: 0 = the tallest tile (512 / 256 / 128 x 128) that still comes in >= 512
-                             // tiles; 1 = always 128 x 128; 2 = 512 x 128 whenever Np % 512 == 0
+                             // tiles; 1 = always 128 x 128; 2 = 512 x 128 whenever Np % 512 == 0; 3 = 256 x 128 whenever Np % 256 == 0
   int ptile = 1;             // gpk_potrf: one persistent launch (gpk_ptile.hip) for 512 <= Np <= ptile_max_np
   int ptile_max_np = 24576;  // (above, the recursion: halves that are one launch each + GEMMs.  One launch against that at 20 480 rows 46.7 / 48.6 ms,
                              // 24 576 78.6 / 79.2, 32 768 179.4 / 172.5, 40 960 347.4 / 340.6: profiles/r05_ptile_large.log; 16 384 until round 5)
@@ -72,6 +72,7 @@ struct gpk_context {
   int debug_fill = 0;        // option debug_fill: the handle's scratch is overwritten with 0xFF bytes (NaN) at every request
   int gemm_log = 0;          // option gemm_log = 1: log every tile-GEMM launch to stderr (profiling aid)
   int gram_log = 0;          // option gram_log = 1: log the form of every gpk_gram / gpk_predict_mean[_multi] launch to stderr
+  int k5_log = 0;            // option k5_log = 1: log the form of every 16-bit variance launch (gpk_k5split.hip) to stderr
   // gpk_timing: HIP-event brackets around the dominant launches (K5 variance GEMM, K1 Gram kernel), a ring of pairs
   struct TimedLaunch { hipEvent_t e0 = nullptr, e1 = nullptr; int tag = 0; };
   int timing = 0;

@@ -586,6 +586,7 @@ int split2_launch(gpk_handle h, const char* who, const float* X, int64_t N, int 
   if (Np % 512 == 0 && (h->k5_split2_tile == 2 || (Np / 512) * (long long)ntn >= 512)) ab = 4;
   else if (Np % 256 == 0 && (Np / 256) * (long long)ntn >= 512) ab = 2;
   if (h->k5_split2_tile == 1) ab = 1;
+  if (h->k5_split2_tile == 3 && Np % 256 == 0) ab = 2;
   const int ntmT = (int)(Np / (128 * ab)), gsz = 32;
   GPK_TRY(gpk_scratch(h, (size_t)ntmT * Mp * sizeof(double), partial));
   DParams p;
@@ -603,6 +604,8 @@ int split2_launch(gpk_handle h, const char* who, const float* X, int64_t N, int 
     p.nst = (int)(((long long)nfull * p.per_pad + (long long)hlast * ntn + gsz - 1) / gsz);
   }
   const long long nblocks = (long long)((p.nst + 7) / 8) * 8 * gsz;
+  if (h->k5_log)   // option k5_log = 1: the form this launch takes (the tests assert it per case)
+    fprintf(stderr, "GPKK5 direct rows%d ntmT%d ntn%d nst%d pad%d grid%lld\n", 128 * ab, ntmT, ntn, p.nst, p.per_pad, nblocks);
   gpk_time_begin(h, GPK_TIMED_K5);
   if (ab == 4) hipLaunchKernelGGL(k5_direct_kernel<4>, dim3((unsigned)nblocks), dim3(256), 0, h->stream, p);
   else if (ab == 2) hipLaunchKernelGGL(k5_direct_kernel<2>, dim3((unsigned)nblocks), dim3(256), 0, h->stream, p);
@@ -666,6 +669,8 @@ extern "C" int gpk_predict_var_inv_split(gpk_handle h, const float* X, int64_t N
   p.ntm = ntm; p.ntn = ntn;
   p.nst = (int)(((long long)ntmT * ntn + gsz - 1) / gsz);
   const long long nblocks = (long long)((p.nst + 7) / 8) * 8 * gsz;
+  if (h->k5_log)
+    fprintf(stderr, "GPKK5 split rows%d ntmT%d ntn%d nst%d pad0 grid%lld\n", 64 * wr, ntmT, ntn, p.nst, nblocks);
   gpk_time_begin(h, GPK_TIMED_K5);
   if (wr == 4) hipLaunchKernelGGL(k5_split_kernel<4>, dim3((unsigned)nblocks), dim3(512), 0, h->stream, p);
   else hipLaunchKernelGGL(k5_split_kernel<2>, dim3((unsigned)nblocks), dim3(256), 0, h->stream, p);
