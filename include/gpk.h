@@ -87,7 +87,9 @@ GPK_API int64_t gpk_padded(int64_t n);
  * products with triangular operands of gpk_trtri / gpk_wtw / gpk_potrs_inv: 1 = the balanced persistent tile schedule, 0 = the
  * static tile mapping; bit-identical results), "gemm_balanced_max_tiles", "gemm_log" (1: every tile-GEMM launch to stderr),
  * "gram_log" (1: the form of every gpk_gram launch - `GPKGRAM f64|f32 N Np D strip|sym gsG ntT gridNNN` - and of every gpk_predict_mean /
- * gpk_predict_mean_multi launch - `GPKMEAN f64|f32 N M D P|B d4 p4 granG sS chunkC` - to stderr, one line per launch),
+ * gpk_predict_mean_multi launch - `GPKMEAN f64|f32 N M D P|B d4 p4 granG sS chunkC` - and of every gpk_predict_mean_mfma call -
+ * `GPKMEANMM bf16|f32 N M D P qbQ nqbN sS chunkC`: the kernel (bf16 x 3 for D <= 14, fp32 MFMA for D = 15, 16), Q query blocks of 32
+ * per wave, N workgroups of 128 Q queries, S training chunks of C points - to stderr, one line per launch),
  * "k5_log" (1: the form of every 16-bit variance launch - gpk_predict_var_inv_split2 / gpk_predict_mean_var_split2: `GPKK5 direct rowsR
  * ntmTA ntnB nstS padP gridG`, gpk_predict_var_inv_split: `GPKK5 split rowsR ntmTA ntnB nstS pad0 gridG`; R the tile's rows, A x B tiles,
  * S super-tiles, P tile slots per band of the walk - to stderr, one line per launch),

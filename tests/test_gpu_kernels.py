@@ -324,7 +324,8 @@ def test_predict_mean_mfma(be, N, D, P, M, ls):
     """K4 on the matrix cores (fp32, centred expansion of the squared distance) against the fp64 oracle
     and the exact-difference fp32 kernel: same posterior mean within the fp32 tolerance (1e-4 of the
     largest mean; measured ~1e-6), on ragged shapes, every operand-depth variant (D + 1 odd and even) and
-    both query-block layouts (P <= 4, P > 4)."""
+    both query-block layouts (P <= 3: two query blocks per wave, P > 3: one).  Which instantiations there are and
+    a bar at the kernels' own error: tests/test_gpu_mean_mfma_forms.py."""
     from unmanned_aerial_vehicles_amd.device import DeviceGP
     rng = np.random.default_rng(N + D)
     X = rng.standard_normal((N, D)) + 3.0 * np.arange(D)      # off-centre columns: the kernel re-centres them

@@ -198,7 +198,7 @@ __global__ __launch_bounds__(256, 2) void mean_mfma_kernel(const float* __restri
   }
 }
 
-// ---- D <= 15: distances on the bf16 matrix pipe, exact three-way operand split ----------------------------
+// ---- D <= 14: distances on the bf16 matrix pipe, exact three-way operand split ----------------------------
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
@@ -532,6 +532,9 @@ extern "C" int gpk_predict_mean_mfma(gpk_handle h, const float* X, const float* 
   int64_t chunk = (N + S - 1) / S;
   chunk = (chunk + MM_TJ - 1) / MM_TJ * MM_TJ;
   S = (N + chunk - 1) / chunk;
+  if (h->gram_log)   // option gram_log = 1: the form this launch takes (the tests assert it per case)
+    fprintf(stderr, "GPKMEANMM %s %lld %lld %d %d qb%d nqb%lld s%lld chunk%lld\n", D > 14 ? "f32" : "bf16", (long long)N,
+            (long long)M, D, P, QB, (long long)nqb, (long long)S, (long long)chunk);
   const size_t partial_bytes = ((size_t)S * M * P * sizeof(float) + 255) & ~(size_t)255;
   void* partial = nullptr;
   if (D > 14) {
