@@ -974,6 +974,57 @@ GPK_API int gpk_paths_rollout_multi_z(gpk_handle h, const double* Zs, int64_t N,
                                       const double* in_shift, const double* in_scale, const double* x0, int x0_rows,
                                       const double* U, int H, const double* lin, double* traj);
 
+/* ---- K10, path gradients: the input Jacobian of every path beside its value ----------------------------------------------
+ * A path is a closed form, f_s(x) = sum_{j<N} v_js k(x, x_j) + sum_{f<F} c_fs cos(omega_f . x + phase_f), and so is its gradient:
+ *     d b_j / d x_d = -b_j(x) (x_d - x_jd) / ls_d^2   (j < N),     d b_{N+f} / d x_d = -sin(omega_f . x + phase_f) omega_fd
+ * Each entry below is the entry it is named after, argument for argument, plus jac; limits and refusals are the family's,
+ * a null jac is GPK_BAD_ARG with a message, and every refusal happens before any launch.  The served Jacobian carries the
+ * output scale (y_std[p]; scale[b]); y_mean and shift do not enter.
+ * Two launches per stage, as the value entries.  The first has the outputs (up to three p of a model, which share the basis value;
+ * one b of a batch) in the grid's third dimension: lane l owns
+ * path 64 block + l for the basis value, the product and the D derivative sums - RBF rows add e t_d with e = b_j c_j and the
+ * t_d = (x_d - x_jd) / ls_d the value forms, cosine rows add sin(t) c omega_d - over the chunking of gpk_paths_step, rows,
+ * waves and chunks in its order; the second adds the shares in chunk order, RBF and cosine shares apart, and writes
+ * jac = scale * -(sum_rbf / ls_d + sum_cos).  No floating-point atomics: the same bits every call.
+ *   VALUE BITS: out (traj) has the bits of the value entry on the same arguments - the value is formed by the value kernels'
+ *   expressions in their order.
+ *   BATCH BITS: column b of a batch jac has the bits of gpk_paths_step_grad's jac on model b's own path set (P = 1, y_mean =
+ *   shift[b], y_std = scale[b], X = Zs_b for _z) - both layouts run the same kernels.
+ * Work area: the handle's scratch (per stage (chunks + (chunks + 1) D) columns doubles; a rollout's jac H times over).
+ *
+ * gpk_paths_step_grad: jac (dev, S x P x D), jac[s][p][d] = d out[s][p] / d Xq[s][d].
+ * gpk_paths_step_multi_grad / _z: jac (dev, S x B x D), jac[s][b][d] = d out[s][b] / d Xq[s][d] (the query as given: scaled).
+ * gpk_paths_rollout_grad: jac (host, H x S x P x D): jac[h][s][p][d] is the derivative of stage h's residual out_s (evaluated
+ *   at traj[h]) w.r.t. coordinate d of q_s = [x_s, U[h]].  One more copy back, the same one synchronisation.
+ * gpk_paths_rollout_multi_grad / _z: jac (host, H x S x B x D), as above for out_b, in the RAW units of q: it includes the
+ *   input scaler's 1 / in_scale[d].                                                                                       */
+GPK_API int gpk_paths_step_grad(gpk_handle h, const double* X, int64_t N, int D, const double* ls, double sf2, const double* Omega,
+                                const double* phase, int64_t F, const double* Coef, int64_t ldc, int S, int P,
+                                const double* y_mean, const double* y_std, const double* Xq, double* out, double* jac);
+GPK_API int gpk_paths_rollout_grad(gpk_handle h, const double* X, int64_t N, int D, const double* ls, double sf2,
+                                   const double* Omega, const double* phase, int64_t F, const double* Coef, int64_t ldc, int S,
+                                   int P, const double* y_mean, const double* y_std, const double* x0, int x0_rows,
+                                   const double* U, int H, const double* lin, double* traj, double* jac);
+GPK_API int gpk_paths_step_multi_grad(gpk_handle h, const double* X, int64_t N, int D, int B, const double* ls, const double* sf2,
+                                      const double* Omega, const double* phase, int64_t F, const double* Coef, int64_t ldc,
+                                      int64_t mstride, int S, const double* shift, const double* scale, const double* Xq,
+                                      double* out, double* jac);
+GPK_API int gpk_paths_rollout_multi_grad(gpk_handle h, const double* X, int64_t N, int D, int B, const double* ls,
+                                         const double* sf2, const double* Omega, const double* phase, int64_t F, const double* Coef,
+                                         int64_t ldc, int64_t mstride, int S, const double* shift, const double* scale, int nx,
+                                         const int* coord, const double* in_shift, const double* in_scale, const double* x0,
+                                         int x0_rows, const double* U, int H, const double* lin, double* traj, double* jac);
+GPK_API int gpk_paths_step_multi_grad_z(gpk_handle h, const double* Zs, int64_t N, int D, int B, const double* ls,
+                                        const double* sf2, const double* Omega, const double* phase, int64_t F, const double* Coef,
+                                        int64_t ldc, int64_t mstride, int S, const double* shift, const double* scale,
+                                        const double* Xq, double* out, double* jac);
+GPK_API int gpk_paths_rollout_multi_grad_z(gpk_handle h, const double* Zs, int64_t N, int D, int B, const double* ls,
+                                           const double* sf2, const double* Omega, const double* phase, int64_t F,
+                                           const double* Coef, int64_t ldc, int64_t mstride, int S, const double* shift,
+                                           const double* scale, int nx, const int* coord, const double* in_shift,
+                                           const double* in_scale, const double* x0, int x0_rows, const double* U, int H,
+                                           const double* lin, double* traj, double* jac);
+
 #ifdef __cplusplus
 }
 #endif

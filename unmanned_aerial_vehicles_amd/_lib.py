@@ -149,6 +149,18 @@ SIGNATURES = {
     "gpk_paths_step_multi_z": (_int, [_vp, _vp, _i64, _int, _int, _dp, _dp, _vp, _vp, _i64, _vp, _i64, _i64, _int, _dp, _dp, _vp, _vp]),
     "gpk_paths_rollout_multi_z": (_int, [_vp, _vp, _i64, _int, _int, _dp, _dp, _vp, _vp, _i64, _vp, _i64, _i64, _int, _dp, _dp, _int,
                                          C.POINTER(_int), _dp, _dp, _dp, _int, _dp, _int, _dp, _dp]),
+    # the gradient forms: the value entry's arguments, then jac
+    "gpk_paths_step_grad": (_int, [_vp, _vp, _i64, _int, _dp, _dbl, _vp, _vp, _i64, _vp, _i64, _int, _int, _dp, _dp, _vp, _vp, _vp]),
+    "gpk_paths_rollout_grad": (_int, [_vp, _vp, _i64, _int, _dp, _dbl, _vp, _vp, _i64, _vp, _i64, _int, _int, _dp, _dp, _dp, _int,
+                                      _dp, _int, _dp, _dp, _dp]),
+    "gpk_paths_step_multi_grad": (_int, [_vp, _vp, _i64, _int, _int, _dp, _dp, _vp, _vp, _i64, _vp, _i64, _i64, _int, _dp, _dp, _vp,
+                                         _vp, _vp]),
+    "gpk_paths_rollout_multi_grad": (_int, [_vp, _vp, _i64, _int, _int, _dp, _dp, _vp, _vp, _i64, _vp, _i64, _i64, _int, _dp, _dp,
+                                            _int, C.POINTER(_int), _dp, _dp, _dp, _int, _dp, _int, _dp, _dp, _dp]),
+    "gpk_paths_step_multi_grad_z": (_int, [_vp, _vp, _i64, _int, _int, _dp, _dp, _vp, _vp, _i64, _vp, _i64, _i64, _int, _dp, _dp,
+                                           _vp, _vp, _vp]),
+    "gpk_paths_rollout_multi_grad_z": (_int, [_vp, _vp, _i64, _int, _int, _dp, _dp, _vp, _vp, _i64, _vp, _i64, _i64, _int, _dp, _dp,
+                                              _int, C.POINTER(_int), _dp, _dp, _dp, _int, _dp, _int, _dp, _dp, _dp]),
 }
 
 _lib = None

@@ -21,6 +21,9 @@
 //   paths_partial_multi_kernel / paths_combine_multi_kernel / paths_advance_multi_kernel
 //                         the same two launches for the per-axis batch: B single-output models on shared inputs, each with its own
 //                         kernel, Coef model-major (see there); with OWNZ every model has its own basis points (the sparse batch)
+//   paths_partial_grad_kernel / paths_combine_grad_kernel / paths_combine_multi_grad_kernel
+//                         the gradient forms (the *_grad entries): value and input Jacobian of every path in the same two
+//                         launches, one first launch for the single model, the batch and the batch with own basis points (see there)
 // Host side: paths_setup is the frame of both set-ups (gpk_paths_prepare; gpk_paths_prepare_two for a sparse model: N := m,
 // X := Z, rows [0, m) hold v = alpha_u + WS^T xi - Wuu^T (Wuu Phi_Z w) from the two inverse factors of the assembled model), and
 // paths_rollout_run drives every rollout: one device block, two uploads, H stages of two launches, one download.
@@ -226,6 +229,7 @@ int paths_fill_k(gpk_handle h, int D, int P, const double* ls, const double* y_m
 }
 
 constexpr int PATHS_MAX_B = 8;      // models of a per-axis batch
+constexpr int PATHS_GRAD_PG = 3;    // outputs of a single model per workgroup of the gradient kernel
 
 // the shape limits every entry of the family shares; `outputs`: the entry's own count (P or B), refused with `outputs_msg`
 int paths_check_shape(gpk_handle h, int64_t N, int D, int64_t F, int S, bool outputs_ok, const char* outputs_msg) {
@@ -506,13 +510,351 @@ int paths_partial_multi(gpk_handle h, const PathsMultiModel& m, const double* xs
   return GPK_OK;
 }
 
+// ---- the gradient forms: value and input Jacobian of every path in the same two launches ---------------------------------------
+// d/dx_d of sum_j b_j(x) c_j:  RBF rows  -inv_ls_d sum_j e_j t_jd  (e_j = b_j c_j, t_jd = (x_d - x_jd) inv_ls_d, the t the value
+// forms), cosine rows  -sum_f e'_f omega_fd  (e'_f = sin(t_f) c_f).  ONE kernel serves both layouts: the output (p of a single
+// model, b of a batch) is the grid's third dimension, lane l owns path 64 block + l for the basis value, the product and the D
+// derivative sums alike, and the layout is a pair of strides (coefficient column s cs + o co, share column s ps + o po).  A
+// workgroup keeps PG (1 + D) sums per lane whatever P or B is (PG <= 3 outputs of a single model, which share the basis value and
+// the t_d; one model of a batch).  Rows, waves and chunks go in the order of the value kernels and the
+// value is formed by their expressions, so the value shares have the bits of paths_partial_kernel / paths_partial_multi_kernel.
+// The two kinds of row need different factors afterwards, so their derivative shares are kept apart: area ch of gpart holds
+// chunk ch's RBF rows if the chunk starts below N and its cosine rows otherwise; the cosine rows of the one chunk that
+// holds row N and rows above it go to area `chunks`.
+struct PathsGradK {
+  double inv_ls[PATHS_MAX_B][16];
+  double sf2[PATHS_MAX_B];
+  double in_shift[16], in_scale[16];      // as PathsMultiK
+  int scaled;
+  int per_model;                          // 1: output o has its own kernel (row o of inv_ls, sf2), 0: row 0 serves all
+};
+
+struct PathsGradModel {
+  const double* X;
+  int N, D;
+  long long xstride;      // doubles between the basis points of two outputs (0: shared)
+  const double* Omega;
+  const double* phase;
+  int F;
+  long long fstride;      // features between two outputs (0: shared)
+  const double* Coef;
+  long long ldc, cs, co;  // coefficient column of (path s, output o): s cs + o co
+  int S, nout;
+  long long ps, po;       // share column of (s, o): s ps + o po, below C = S nout
+  PathsGradK k;
+};
+
+// the D sums of a workgroup's four waves, added in wave order, to area `area` of gpart ((areas x D x C), column col)
+__device__ __forceinline__ void paths_grad_store(double (*red)[16][PB], const double (&G)[16], int D, int w, int lane, int tid,
+                                                 int S, long long C, long long ps, long long pcol0, long long area,
+                                                 double* __restrict__ gpart) {
+#pragma unroll
+  for (int d = 0; d < 16; ++d)
+    if (d < D) red[w][d][lane] = G[d];
+  __syncthreads();
+  for (int e = tid; e < D * PB; e += 256) {
+    const int d = e >> 6, l = e & 63;
+    const int sl = (int)blockIdx.x * PB + l;
+    if (sl < S) {
+      double t = red[0][d][l];
+#pragma unroll
+      for (int ww = 1; ww < PW; ++ww) t += red[ww][d][l];
+      gpart[(area * D + d) * C + pcol0 + sl * ps] = t;
+    }
+  }
+  __syncthreads();
+}
+
+// PG: the outputs a workgroup serves, o0 = PG blockIdx.z and the next ones (a single model's p share the basis value and the
+// t_d; a batch's models share nothing: PG = 1).  Every output's sums are formed by the same expressions whatever PG is.
+template <int PG>
+__global__ __launch_bounds__(256) void paths_partial_grad_kernel(PathsGradModel m, const double* __restrict__ xs, int dx,
+                                                                 const double* __restrict__ u, int rows_per_chunk, int chunks,
+                                                                 double* __restrict__ partial, double* __restrict__ gpart) {
+  __shared__ double red[PW][16][PB];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int N = m.N, D = m.D, S = m.S, rows = N + m.F;
+  const int o0 = (int)blockIdx.z * PG, mi = m.k.per_model ? o0 : 0;
+  const int sp = (int)blockIdx.x * PB + lane;
+  const bool live = sp < S;
+  const int s = min(sp, S - 1);      // (a lane past the last path repeats it: its coefficients are zeros, its sums are never stored)
+  const int r0 = (int)blockIdx.y * rows_per_chunk, r1 = min(r0 + rows_per_chunk, rows);
+  const long long C = (long long)S * m.nout, pcol0 = o0 * m.po;
+  double q[16];
+#pragma unroll
+  for (int d = 0; d < 16; ++d) q[d] = d < dx ? xs[(long long)s * dx + d] : (d < D ? u[d - dx] : 0.0);
+  if (m.k.scaled) {
+#pragma unroll
+    for (int d = 0; d < 16; ++d)
+      if (d < D) q[d] = (q[d] - m.k.in_shift[d]) / m.k.in_scale[d];
+  }
+  const double* __restrict__ Xo = m.X + o0 * m.xstride;
+  const double* __restrict__ Om = m.Omega + o0 * m.fstride * D;
+  const double* __restrict__ ph = m.phase + o0 * m.fstride;
+  const double* __restrict__ cp = m.Coef + s * m.cs + o0 * m.co;
+  const double sf2 = m.k.sf2[mi];
+  bool on[PG];      // (uniform) the group's last outputs may lie past nout: their coefficients are zeros, their sums are never stored
+#pragma unroll
+  for (int g = 0; g < PG; ++g) on[g] = o0 + g < m.nout;
+  double acc[PG], G[PG][16];
+#pragma unroll
+  for (int g = 0; g < PG; ++g) {
+    acc[g] = 0.0;
+#pragma unroll
+    for (int d = 0; d < 16; ++d) G[g][d] = 0.0;
+  }
+  // wave w takes the chunk's rows r0 + w, r0 + w + PW, ... in ascending order (j is wave-uniform): first those below N ...
+  const int nA = min(r1, N);
+  int j = r0 + w;
+  for (; j < nA; j += PW) {
+    double cv[PG];
+#pragma unroll
+    for (int g = 0; g < PG; ++g) cv[g] = (live && on[g]) ? cp[(long long)j * m.ldc + g * m.co] : 0.0;
+    const double* xj = Xo + (long long)j * D;
+    double t[16], d2 = 0.0;
+#pragma unroll
+    for (int d = 0; d < 16; ++d) {
+      t[d] = 0.0;
+      if (d < D) {
+        t[d] = (q[d] - xj[d]) * m.k.inv_ls[mi][d];
+        d2 = __builtin_fma(t[d], t[d], d2);
+      }
+    }
+    const double b = sf2 * gpk_exp_neg(-0.5 * d2);
+#pragma unroll
+    for (int g = 0; g < PG; ++g) {
+      acc[g] = __builtin_fma(b, cv[g], acc[g]);
+      const double e = b * cv[g];
+#pragma unroll
+      for (int d = 0; d < 16; ++d)
+        if (d < D) G[g][d] = __builtin_fma(e, t[d], G[g][d]);
+    }
+  }
+  if (r0 < N) {      // (uniform over the workgroup)
+#pragma unroll
+    for (int g = 0; g < PG; ++g) {
+      if (on[g]) paths_grad_store(red, G[g], D, w, lane, tid, S, C, m.ps, pcol0 + g * m.po, blockIdx.y, gpart);
+#pragma unroll
+      for (int d = 0; d < 16; ++d) G[g][d] = 0.0;
+    }
+  }
+  // ... then the cosine rows
+  for (; j < r1; j += PW) {
+    double cv[PG];
+#pragma unroll
+    for (int g = 0; g < PG; ++g) cv[g] = (live && on[g]) ? cp[(long long)j * m.ldc + g * m.co] : 0.0;
+    const double* om = Om + (long long)(j - N) * D;
+    double t = ph[j - N];
+#pragma unroll
+    for (int d = 0; d < 16; ++d)
+      if (d < D) t = __builtin_fma(om[d], q[d], t);
+    const double b = cos(t), sn = sin(t);
+#pragma unroll
+    for (int g = 0; g < PG; ++g) {
+      acc[g] = __builtin_fma(b, cv[g], acc[g]);
+      const double e = sn * cv[g];
+#pragma unroll
+      for (int d = 0; d < 16; ++d)
+        if (d < D) G[g][d] = __builtin_fma(e, om[d], G[g][d]);
+    }
+  }
+  if (r1 > N) {
+#pragma unroll
+    for (int g = 0; g < PG; ++g)
+      if (on[g])
+        paths_grad_store(red, G[g], D, w, lane, tid, S, C, m.ps, pcol0 + g * m.po, r0 < N ? chunks : (int)blockIdx.y, gpart);
+  }
+  // the value's shares, as the value kernels form them
+#pragma unroll
+  for (int g = 0; g < PG; ++g) red[w][g][lane] = acc[g];
+  __syncthreads();
+  for (int e = tid; e < PG * PB; e += 256) {
+    const int g = e >> 6, l = e & 63;
+    const int sl = (int)blockIdx.x * PB + l;
+    if (sl < S && o0 + g < m.nout) {
+      double t = red[0][g][l];
+#pragma unroll
+      for (int ww = 1; ww < PW; ++ww) t += red[ww][g][l];
+      partial[(long long)blockIdx.y * C + pcol0 + g * m.po + sl * m.ps] = t;
+    }
+  }
+}
+
+// One entry of the Jacobian from the derivative shares, in chunk order: the RBF areas (chunks that start below N), then the
+// cosine areas - area `chunks` first, the chunk that holds row N, if it also holds rows above it.
+__device__ __forceinline__ double paths_jac_entry(const double* __restrict__ gpart, int chunks, int rows_per_chunk, int N, int D,
+                                                  long long C, long long col, int d, double inv_ls, double scale) {
+  const int nr = (N + rows_per_chunk - 1) / rows_per_chunk;      // chunks that start below N
+  const double* g = gpart + (long long)d * C + col;
+  const long long step = (long long)D * C;
+  double tr = 0.0;
+#pragma unroll 8
+  for (int ch = 0; ch < nr; ++ch) tr += g[ch * step];
+  double tc = 0.0;
+  if (N % rows_per_chunk != 0) tc += g[chunks * step];
+#pragma unroll 8
+  for (int ch = nr; ch < chunks; ++ch) tc += g[ch * step];
+  return scale * -__builtin_fma(inv_ls, tr, tc);
+}
+
+// grid (blocks of 256 columns) x (1 + D): row 0 is paths_combine_kernel, row 1 + d writes jac[c][d]
+__global__ __launch_bounds__(256) void paths_combine_grad_kernel(const double* __restrict__ partial,
+                                                                 const double* __restrict__ gpart, int chunks, int rows_per_chunk,
+                                                                 int N, int S, int P, int D, PathsK k, double* __restrict__ out,
+                                                                 const double* __restrict__ x, const double* __restrict__ u,
+                                                                 const double* __restrict__ lin, double* __restrict__ x_next,
+                                                                 double* __restrict__ jac) {
+  const int C = S * P;
+  const int c = (int)blockIdx.x * 256 + threadIdx.x;
+  if (c >= C) return;
+  const int p = c % P, s = c / P;
+  if (blockIdx.y > 0) {
+    const int d = (int)blockIdx.y - 1;
+    jac[(long long)c * D + d] = paths_jac_entry(gpart, chunks, rows_per_chunk, N, D, C, c, d, k.inv_ls[d], k.ystd[p]);
+    return;
+  }
+  double t = 0.0;
+#pragma unroll 8
+  for (int ch = 0; ch < chunks; ++ch) t += partial[(long long)ch * C + c];
+  const double v = __builtin_fma(k.ystd[p], t, k.ymean[p]);
+  if (!x_next) {
+    out[c] = v;
+    return;
+  }
+  double a = 0.0;
+  for (int d = 0; d < P; ++d) a = __builtin_fma(lin[p * D + d], x[(long long)s * P + d], a);
+  for (int d = P; d < D; ++d) a = __builtin_fma(lin[p * D + d], u[d - P], a);
+  x_next[c] = (x[c] + a) + v;
+}
+
+// grid (blocks of 256 paths) x (nv + B D): rows [0, nv) are paths_combine_multi_kernel (nv = B, x_next null) or
+// paths_advance_multi_kernel (nv = nx); row nv + b D + d writes jac[s][b][d], in a rollout per unit of the RAW query
+__global__ __launch_bounds__(256) void paths_combine_multi_grad_kernel(const double* __restrict__ partial,
+                                                                       const double* __restrict__ gpart, int chunks,
+                                                                       int rows_per_chunk, int N, int S, int B, int nv, int D,
+                                                                       PathsMultiK k, double* __restrict__ out,
+                                                                       const double* __restrict__ x, const double* __restrict__ u,
+                                                                       const double* __restrict__ lin, double* __restrict__ x_next,
+                                                                       double* __restrict__ jac) {
+  const int s = (int)blockIdx.x * 256 + threadIdx.x;
+  if (s >= S) return;
+  if ((int)blockIdx.y >= nv) {
+    const int b = ((int)blockIdx.y - nv) / D, d = ((int)blockIdx.y - nv) % D;
+    double v = paths_jac_entry(gpart, chunks, rows_per_chunk, N, D, (long long)B * S, (long long)b * S + s, d, k.inv_ls[b][d],
+                               k.scale[b]);
+    if (x_next) v /= k.in_scale[d];
+    jac[((long long)s * B + b) * D + d] = v;
+    return;
+  }
+  if (!x_next) {
+    const int b = blockIdx.y;
+    double t = 0.0;
+#pragma unroll 8
+    for (int ch = 0; ch < chunks; ++ch) t += partial[((long long)ch * B + b) * S + s];
+    out[(long long)s * B + b] = __builtin_fma(k.scale[b], t, k.shift[b]);
+    return;
+  }
+  const int i = blockIdx.y, nx = nv;
+  const double* xr = x + (long long)s * nx;
+  double a = 0.0;
+  for (int d = 0; d < nx; ++d) a = __builtin_fma(lin[i * D + d], xr[d], a);
+  for (int d = nx; d < D; ++d) a = __builtin_fma(lin[i * D + d], u[d - nx], a);
+  double v = xr[i] + a;
+  const int b = k.model_of[i];
+  if (b >= 0) {
+    double t = 0.0;
+#pragma unroll 8
+    for (int ch = 0; ch < chunks; ++ch) t += partial[((long long)ch * B + b) * S + s];
+    v += __builtin_fma(k.scale[b], t, k.shift[b]);
+  }
+  x_next[(long long)s * nx + i] = v;
+}
+
+// the first launch of a gradient stage: value shares (chunks x C) and derivative shares ((chunks + 1) x D x C)
+int paths_partial_grad(gpk_handle h, const PathsGradModel& g, const double* xs, int dx, const double* u, int rpc, int chunks,
+                       double* partial, double* gpart) {
+  // a single model's outputs in groups of PATHS_GRAD_PG (they share the basis value); a batch's models one by one
+  const int pg = g.k.per_model ? 1 : (g.nout < PATHS_GRAD_PG ? g.nout : PATHS_GRAD_PG);
+  const dim3 grid((unsigned)((g.S + PB - 1) / PB), (unsigned)chunks, (unsigned)((g.nout + pg - 1) / pg));
+#define GPK_PATHS_GRAD(PGG)                                                                                                    \
+  case PGG:                                                                                                                    \
+    hipLaunchKernelGGL(paths_partial_grad_kernel<PGG>, grid, dim3(256), 0, h->stream, g, xs, dx, u, rpc, chunks, partial,      \
+                       gpart);                                                                                                 \
+    break
+  switch (pg) {
+    GPK_PATHS_GRAD(1); GPK_PATHS_GRAD(2); GPK_PATHS_GRAD(3);
+  }
+#undef GPK_PATHS_GRAD
+  GPK_LAUNCH_CHECK(h);
+  return GPK_OK;
+}
+
+PathsGradModel paths_grad_model(const PathsModel& m) {
+  PathsGradModel g{m.X, m.N, m.D, 0, m.Omega, m.phase, m.F, 0, m.Coef, m.ldc, m.P, 1, m.S, m.P, m.P, 1, {}};
+  for (int d = 0; d < 16; ++d) {
+    g.k.inv_ls[0][d] = m.k.inv_ls[d];
+    g.k.in_shift[d] = 0.0;
+    g.k.in_scale[d] = 1.0;
+  }
+  g.k.sf2[0] = m.sf2;
+  return g;
+}
+
+PathsGradModel paths_grad_model(const PathsMultiModel& m) {
+  PathsGradModel g{m.X, m.N, m.D, m.own_z ? (long long)m.N * m.D : 0, m.Omega, m.phase, m.F, m.F, m.Coef, m.ldc, 1, m.mstride,
+                   m.S, m.B, 1, m.S, {}};
+  for (int b = 0; b < PATHS_MAX_B; ++b) {
+    for (int d = 0; d < 16; ++d) g.k.inv_ls[b][d] = m.k.inv_ls[b][d];
+    g.k.sf2[b] = m.k.sf2[b];
+  }
+  for (int d = 0; d < 16; ++d) {
+    g.k.in_shift[d] = m.k.in_shift[d];
+    g.k.in_scale[d] = m.k.in_scale[d];
+  }
+  g.k.scaled = m.k.scaled;
+  g.k.per_model = 1;
+  return g;
+}
+
+// doubles of a gradient stage's shares: the value's, then the derivatives'
+size_t paths_grad_shares(int chunks, int D, size_t C) { return (size_t)chunks * C + (size_t)(chunks + 1) * D * C; }
+
+// one gradient stage of a single model: as paths_stage, and jac (S x P x D)
+int paths_stage_grad(gpk_handle h, const PathsModel& m, const PathsGradModel& g, const double* xs, int dx, const double* u, int rpc,
+                     int chunks, double* partial, double* out, const double* lin, double* x_next, double* jac) {
+  const int C = m.S * m.P;
+  double* gpart = partial + (size_t)chunks * C;
+  GPK_TRY(paths_partial_grad(h, g, xs, dx, u, rpc, chunks, partial, gpart));
+  hipLaunchKernelGGL(paths_combine_grad_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)(1 + m.D)), dim3(256), 0, h->stream,
+                     (const double*)partial, (const double*)gpart, chunks, rpc, m.N, m.S, m.P, m.D, m.k, out, xs, u, lin, x_next,
+                     jac);
+  GPK_LAUNCH_CHECK(h);
+  return GPK_OK;
+}
+
+// one gradient stage of a batch: nv = B and out (a step) or nv = nx, lin and x_next (a rollout's advance), and jac (S x B x D)
+int paths_stage_multi_grad(gpk_handle h, const PathsMultiModel& m, const PathsGradModel& g, const double* xs, int dx,
+                           const double* u, int rpc, int chunks, double* partial, int nv, double* out, const double* lin,
+                           double* x_next, double* jac) {
+  double* gpart = partial + (size_t)chunks * m.S * m.B;
+  GPK_TRY(paths_partial_grad(h, g, xs, dx, u, rpc, chunks, partial, gpart));
+  hipLaunchKernelGGL(paths_combine_multi_grad_kernel, dim3((unsigned)((m.S + 255) / 256), (unsigned)(nv + m.B * m.D)), dim3(256), 0,
+                     h->stream, (const double*)partial, (const double*)gpart, chunks, rpc, m.N, m.S, m.B, nv, m.D, m.k, out, xs, u,
+                     lin, x_next, jac);
+  GPK_LAUNCH_CHECK(h);
+  return GPK_OK;
+}
+
 // One closed-loop horizon, every kind of path set: the refusals the rollouts share, then the device block - the trajectory
 // ((H + 1) x S x w), then [stage 0 | U | lin] as they come from the host in one copy (stage 0 is the trajectory's first slot) and
 // the chunks' shares (n_partial doubles) - two uploads, H stages, one download, one synchronisation.  w: the state width, at most
-// D (the entry's own check); stage(xk, uk, partial, d_lin, x_next) launches one stage; `name` heads the messages.
+// D (the entry's own check); stage(xk, uk, partial, d_lin, x_next, jac_k) launches one stage; `name` heads the messages.
+// A gradient rollout (jac, host, H x n_jac) adds the Jacobian area to the block - stage k writes its n_jac doubles at jac_k -
+// and one more download before the same synchronisation; without it n_jac = 0 and jac_k is null.
 template <class Stage>
 int paths_rollout_run(gpk_handle h, const char* name, int w, int D, int S, const double* x0, int x0_rows, const double* U, int H,
-                      const double* lin, double* traj, size_t n_partial, Stage stage) {
+                      const double* lin, double* traj, size_t n_partial, size_t n_jac, double* jac, Stage stage) {
   const std::string who = std::string(name) + ": ";
   GPK_REQUIRE(h, H >= 1 && H <= PATHS_MAX_H, who + "H must be in [1, 256]");
   GPK_REQUIRE(h, x0_rows == 1 || x0_rows == S, who + "x0 must have 1 or S rows");
@@ -524,11 +866,12 @@ int paths_rollout_run(gpk_handle h, const char* name, int w, int D, int S, const
   const size_t C = (size_t)S * w;
   const size_t n_traj = (size_t)(H + 1) * C, n_u = (size_t)H * du, n_lin = (size_t)w * D;
   void* ws = nullptr;
-  GPK_TRY(gpk_scratch(h, (n_traj + n_u + n_lin + n_partial) * sizeof(double), &ws));
+  GPK_TRY(gpk_scratch(h, (n_traj + n_u + n_lin + n_partial + (size_t)H * n_jac) * sizeof(double), &ws));
   double* d_traj = (double*)ws;
   double* d_u = d_traj + n_traj;
   double* d_lin = d_u + n_u;
   double* partial = d_lin + n_lin;
+  double* d_jac = n_jac ? partial + n_partial : nullptr;
   std::vector<double> host(C + n_u + n_lin);
   for (int s = 0; s < S; ++s) memcpy(host.data() + (size_t)s * w, x0 + (x0_rows == 1 ? 0 : (size_t)s * w), sizeof(double) * w);
   if (n_u) memcpy(host.data() + C, U, sizeof(double) * n_u);
@@ -536,8 +879,10 @@ int paths_rollout_run(gpk_handle h, const char* name, int w, int D, int S, const
   GPK_CHECK_HIP(h, hipMemcpyAsync(d_traj, host.data(), sizeof(double) * C, hipMemcpyHostToDevice, h->stream));
   GPK_CHECK_HIP(h, hipMemcpyAsync(d_u, host.data() + C, sizeof(double) * (n_u + n_lin), hipMemcpyHostToDevice, h->stream));
   for (int k = 0; k < H; ++k)
-    GPK_TRY(stage(d_traj + (size_t)k * C, d_u + (size_t)k * du, partial, (const double*)d_lin, d_traj + (size_t)(k + 1) * C));
+    GPK_TRY(stage(d_traj + (size_t)k * C, d_u + (size_t)k * du, partial, (const double*)d_lin, d_traj + (size_t)(k + 1) * C,
+                  d_jac ? d_jac + (size_t)k * n_jac : nullptr));
   GPK_CHECK_HIP(h, hipMemcpyAsync(traj, d_traj, sizeof(double) * n_traj, hipMemcpyDeviceToHost, h->stream));
+  if (d_jac) GPK_CHECK_HIP(h, hipMemcpyAsync(jac, d_jac, sizeof(double) * H * n_jac, hipMemcpyDeviceToHost, h->stream));
   GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
   return GPK_OK;
 }
@@ -621,51 +966,103 @@ extern "C" int gpk_paths_prepare(gpk_handle h, const double* X, int64_t N, int D
                      });
 }
 
-extern "C" int gpk_paths_step(gpk_handle h, const double* X, int64_t N, int D, const double* ls, double sf2, const double* Omega,
-                              const double* phase, int64_t F, const double* Coef, int64_t ldc, int S, int P, const double* y_mean,
-                              const double* y_std, const double* Xq, double* out) {
+// the bodies of the single-model entries; grad: the gradient form, which also fills jac
+static int paths_step_single(gpk_handle h, bool grad, const double* X, int64_t N, int D, const double* ls, double sf2,
+                             const double* Omega, const double* phase, int64_t F, const double* Coef, int64_t ldc, int S, int P,
+                             const double* y_mean, const double* y_std, const double* Xq, double* out, double* jac) {
   if (!h) return GPK_BAD_ARG;
   GPK_REQUIRE(h, X && Omega && phase && Coef && Xq && out, "paths_step: null pointer");
+  GPK_REQUIRE(h, !grad || jac, "paths_step_grad: null jac");
   GPK_TRY(paths_check_single(h, N, D, F, S, P, ldc));
   PathsModel m{X, (int)N, D, sf2, Omega, phase, (int)F, Coef, (long long)ldc, S, P, {}};
   GPK_TRY(paths_fill_k(h, D, P, ls, y_mean, y_std, m.k));
   int rpc = 0, chunks = 0;
   paths_chunks(N + F, S, &rpc, &chunks);
   void* ws = nullptr;
+  if (grad) {
+    GPK_TRY(gpk_scratch(h, paths_grad_shares(chunks, D, (size_t)S * P) * sizeof(double), &ws));
+    return paths_stage_grad(h, m, paths_grad_model(m), Xq, D, nullptr, rpc, chunks, (double*)ws, out, nullptr, nullptr, jac);
+  }
   GPK_TRY(gpk_scratch(h, (size_t)chunks * S * P * sizeof(double), &ws));
   return paths_stage(h, m, Xq, D, nullptr, rpc, chunks, (double*)ws, out, nullptr, nullptr);
 }
 
-extern "C" int gpk_paths_rollout(gpk_handle h, const double* X, int64_t N, int D, const double* ls, double sf2,
-                                 const double* Omega, const double* phase, int64_t F, const double* Coef, int64_t ldc, int S, int P,
-                                 const double* y_mean, const double* y_std, const double* x0, int x0_rows, const double* U, int H,
-                                 const double* lin, double* traj) {
+static int paths_rollout_single(gpk_handle h, bool grad, const double* X, int64_t N, int D, const double* ls, double sf2,
+                                const double* Omega, const double* phase, int64_t F, const double* Coef, int64_t ldc, int S, int P,
+                                const double* y_mean, const double* y_std, const double* x0, int x0_rows, const double* U, int H,
+                                const double* lin, double* traj, double* jac) {
   if (!h) return GPK_BAD_ARG;
   GPK_REQUIRE(h, X && Omega && phase && Coef && x0 && lin && traj, "paths_rollout: null pointer");
+  GPK_REQUIRE(h, !grad || jac, "paths_rollout_grad: null jac");
   GPK_TRY(paths_check_single(h, N, D, F, S, P, ldc));
   GPK_REQUIRE(h, P <= D, "paths_rollout: the state dimension P must not exceed D");
   PathsModel m{X, (int)N, D, sf2, Omega, phase, (int)F, Coef, (long long)ldc, S, P, {}};
   GPK_TRY(paths_fill_k(h, D, P, ls, y_mean, y_std, m.k));
   int rpc = 0, chunks = 0;
   paths_chunks(N + F, S, &rpc, &chunks);
-  return paths_rollout_run(h, "paths_rollout", P, D, S, x0, x0_rows, U, H, lin, traj, (size_t)chunks * S * P,
-                           [&](const double* xk, const double* uk, double* partial, const double* d_lin, double* x_next) {
+  if (grad) {
+    const PathsGradModel g = paths_grad_model(m);
+    return paths_rollout_run(h, "paths_rollout", P, D, S, x0, x0_rows, U, H, lin, traj, paths_grad_shares(chunks, D, (size_t)S * P),
+                             (size_t)S * P * D, jac,
+                             [&](const double* xk, const double* uk, double* partial, const double* d_lin, double* x_next,
+                                 double* jac_k) {
+                               return paths_stage_grad(h, m, g, xk, P, uk, rpc, chunks, partial, nullptr, d_lin, x_next, jac_k);
+                             });
+  }
+  return paths_rollout_run(h, "paths_rollout", P, D, S, x0, x0_rows, U, H, lin, traj, (size_t)chunks * S * P, 0, nullptr,
+                           [&](const double* xk, const double* uk, double* partial, const double* d_lin, double* x_next, double*) {
                              return paths_stage(h, m, xk, P, uk, rpc, chunks, partial, nullptr, d_lin, x_next);
                            });
 }
 
-// the bodies of the batch entries; own_z: X is (B x N x D), every model's own basis points (the _z entries)
-static int paths_step_multi(gpk_handle h, bool own_z, const double* X, int64_t N, int D, int B, const double* ls, const double* sf2,
+extern "C" int gpk_paths_step(gpk_handle h, const double* X, int64_t N, int D, const double* ls, double sf2, const double* Omega,
+                              const double* phase, int64_t F, const double* Coef, int64_t ldc, int S, int P, const double* y_mean,
+                              const double* y_std, const double* Xq, double* out) {
+  return paths_step_single(h, false, X, N, D, ls, sf2, Omega, phase, F, Coef, ldc, S, P, y_mean, y_std, Xq, out, nullptr);
+}
+
+extern "C" int gpk_paths_step_grad(gpk_handle h, const double* X, int64_t N, int D, const double* ls, double sf2,
+                                   const double* Omega, const double* phase, int64_t F, const double* Coef, int64_t ldc, int S,
+                                   int P, const double* y_mean, const double* y_std, const double* Xq, double* out, double* jac) {
+  return paths_step_single(h, true, X, N, D, ls, sf2, Omega, phase, F, Coef, ldc, S, P, y_mean, y_std, Xq, out, jac);
+}
+
+extern "C" int gpk_paths_rollout(gpk_handle h, const double* X, int64_t N, int D, const double* ls, double sf2,
+                                 const double* Omega, const double* phase, int64_t F, const double* Coef, int64_t ldc, int S, int P,
+                                 const double* y_mean, const double* y_std, const double* x0, int x0_rows, const double* U, int H,
+                                 const double* lin, double* traj) {
+  return paths_rollout_single(h, false, X, N, D, ls, sf2, Omega, phase, F, Coef, ldc, S, P, y_mean, y_std, x0, x0_rows, U, H, lin,
+                              traj, nullptr);
+}
+
+extern "C" int gpk_paths_rollout_grad(gpk_handle h, const double* X, int64_t N, int D, const double* ls, double sf2,
+                                      const double* Omega, const double* phase, int64_t F, const double* Coef, int64_t ldc, int S,
+                                      int P, const double* y_mean, const double* y_std, const double* x0, int x0_rows,
+                                      const double* U, int H, const double* lin, double* traj, double* jac) {
+  return paths_rollout_single(h, true, X, N, D, ls, sf2, Omega, phase, F, Coef, ldc, S, P, y_mean, y_std, x0, x0_rows, U, H, lin,
+                              traj, jac);
+}
+
+// the bodies of the batch entries; own_z: X is (B x N x D), every model's own basis points (the _z entries); grad: the gradient
+// form, which also fills jac
+static int paths_step_multi(gpk_handle h, bool own_z, bool grad, const double* X, int64_t N, int D, int B, const double* ls, const double* sf2,
                             const double* Omega, const double* phase, int64_t F, const double* Coef, int64_t ldc,
-                            int64_t mstride, int S, const double* shift, const double* scale, const double* Xq, double* out) {
+                            int64_t mstride, int S, const double* shift, const double* scale, const double* Xq, double* out,
+                            double* jac) {
   if (!h) return GPK_BAD_ARG;
   GPK_REQUIRE(h, X && Omega && phase && Coef && Xq && out, "paths_step_multi: null pointer");
+  GPK_REQUIRE(h, !grad || jac, "paths_step_multi_grad: null jac");
   GPK_TRY(paths_check_multi(h, N, D, B, F, S, ldc, mstride));
   PathsMultiModel m{X, own_z, (int)N, D, B, Omega, phase, (int)F, Coef, (long long)ldc, (long long)mstride, S, {}};
   GPK_TRY(paths_fill_multi(h, D, B, ls, sf2, shift, scale, m.k));
   int rpc = 0, chunks = 0;
   paths_chunks(N + F, S, &rpc, &chunks);
   void* ws = nullptr;
+  if (grad) {
+    GPK_TRY(gpk_scratch(h, paths_grad_shares(chunks, D, (size_t)S * B) * sizeof(double), &ws));
+    return paths_stage_multi_grad(h, m, paths_grad_model(m), Xq, D, nullptr, rpc, chunks, (double*)ws, B, out, nullptr, nullptr,
+                                  jac);
+  }
   GPK_TRY(gpk_scratch(h, (size_t)chunks * S * B * sizeof(double), &ws));
   GPK_TRY(paths_partial_multi(h, m, Xq, D, nullptr, rpc, chunks, (double*)ws));
   hipLaunchKernelGGL(paths_combine_multi_kernel, dim3((unsigned)((S + 255) / 256), (unsigned)B), dim3(256), 0, h->stream,
@@ -674,13 +1071,14 @@ static int paths_step_multi(gpk_handle h, bool own_z, const double* X, int64_t N
   return GPK_OK;
 }
 
-static int paths_rollout_multi(gpk_handle h, bool own_z, const double* X, int64_t N, int D, int B, const double* ls,
+static int paths_rollout_multi(gpk_handle h, bool own_z, bool grad, const double* X, int64_t N, int D, int B, const double* ls,
                                const double* sf2, const double* Omega, const double* phase, int64_t F, const double* Coef,
                                int64_t ldc, int64_t mstride, int S, const double* shift, const double* scale, int nx,
                                const int* coord, const double* in_shift, const double* in_scale, const double* x0, int x0_rows,
-                               const double* U, int H, const double* lin, double* traj) {
+                               const double* U, int H, const double* lin, double* traj, double* jac) {
   if (!h) return GPK_BAD_ARG;
   GPK_REQUIRE(h, X && Omega && phase && Coef && coord && x0 && lin && traj, "paths_rollout_multi: null pointer");
+  GPK_REQUIRE(h, !grad || jac, "paths_rollout_multi_grad: null jac");
   GPK_TRY(paths_check_multi(h, N, D, B, F, S, ldc, mstride));
   GPK_REQUIRE(h, nx >= B && nx <= D, "paths_rollout_multi: the state dimension nx must be in [B, D]");
   GPK_REQUIRE(h, (in_shift == nullptr) == (in_scale == nullptr), "paths_rollout_multi: in_shift and in_scale go together");
@@ -704,8 +1102,19 @@ static int paths_rollout_multi(gpk_handle h, bool own_z, const double* X, int64_
   int rpc = 0, chunks = 0;
   paths_chunks(N + F, S, &rpc, &chunks);
   const dim3 agrid((unsigned)((S + 255) / 256), (unsigned)nx);
-  return paths_rollout_run(h, "paths_rollout_multi", nx, D, S, x0, x0_rows, U, H, lin, traj, (size_t)chunks * S * B,
-                           [&](const double* xk, const double* uk, double* partial, const double* d_lin, double* x_next) -> int {
+  if (grad) {
+    const PathsGradModel g = paths_grad_model(m);
+    return paths_rollout_run(h, "paths_rollout_multi", nx, D, S, x0, x0_rows, U, H, lin, traj,
+                             paths_grad_shares(chunks, D, (size_t)S * B), (size_t)S * B * D, jac,
+                             [&](const double* xk, const double* uk, double* partial, const double* d_lin, double* x_next,
+                                 double* jac_k) {
+                               return paths_stage_multi_grad(h, m, g, xk, nx, uk, rpc, chunks, partial, nx, nullptr, d_lin, x_next,
+                                                             jac_k);
+                             });
+  }
+  return paths_rollout_run(h, "paths_rollout_multi", nx, D, S, x0, x0_rows, U, H, lin, traj, (size_t)chunks * S * B, 0, nullptr,
+                           [&](const double* xk, const double* uk, double* partial, const double* d_lin, double* x_next,
+                               double*) -> int {
                              GPK_TRY(paths_partial_multi(h, m, xk, nx, uk, rpc, chunks, partial));
                              hipLaunchKernelGGL(paths_advance_multi_kernel, agrid, dim3(256), 0, h->stream, (const double*)partial,
                                                 chunks, S, B, nx, D, m.k, xk, uk, d_lin, x_next);
@@ -718,7 +1127,7 @@ extern "C" int gpk_paths_step_multi(gpk_handle h, const double* X, int64_t N, in
                                     const double* Omega, const double* phase, int64_t F, const double* Coef, int64_t ldc,
                                     int64_t mstride, int S, const double* shift, const double* scale, const double* Xq,
                                     double* out) {
-  return paths_step_multi(h, false, X, N, D, B, ls, sf2, Omega, phase, F, Coef, ldc, mstride, S, shift, scale, Xq, out);
+  return paths_step_multi(h, false, false, X, N, D, B, ls, sf2, Omega, phase, F, Coef, ldc, mstride, S, shift, scale, Xq, out, nullptr);
 }
 
 extern "C" int gpk_paths_rollout_multi(gpk_handle h, const double* X, int64_t N, int D, int B, const double* ls, const double* sf2,
@@ -726,8 +1135,8 @@ extern "C" int gpk_paths_rollout_multi(gpk_handle h, const double* X, int64_t N,
                                        int64_t mstride, int S, const double* shift, const double* scale, int nx, const int* coord,
                                        const double* in_shift, const double* in_scale, const double* x0, int x0_rows,
                                        const double* U, int H, const double* lin, double* traj) {
-  return paths_rollout_multi(h, false, X, N, D, B, ls, sf2, Omega, phase, F, Coef, ldc, mstride, S, shift, scale, nx, coord,
-                             in_shift, in_scale, x0, x0_rows, U, H, lin, traj);
+  return paths_rollout_multi(h, false, false, X, N, D, B, ls, sf2, Omega, phase, F, Coef, ldc, mstride, S, shift, scale, nx, coord,
+                             in_shift, in_scale, x0, x0_rows, U, H, lin, traj, nullptr);
 }
 
 // ---- the sparse models: every model has its own basis points (its inducing inputs) -------------------------------------------
@@ -735,7 +1144,7 @@ extern "C" int gpk_paths_step_multi_z(gpk_handle h, const double* Zs, int64_t N,
                                       const double* Omega, const double* phase, int64_t F, const double* Coef, int64_t ldc,
                                       int64_t mstride, int S, const double* shift, const double* scale, const double* Xq,
                                       double* out) {
-  return paths_step_multi(h, true, Zs, N, D, B, ls, sf2, Omega, phase, F, Coef, ldc, mstride, S, shift, scale, Xq, out);
+  return paths_step_multi(h, true, false, Zs, N, D, B, ls, sf2, Omega, phase, F, Coef, ldc, mstride, S, shift, scale, Xq, out, nullptr);
 }
 
 extern "C" int gpk_paths_rollout_multi_z(gpk_handle h, const double* Zs, int64_t N, int D, int B, const double* ls,
@@ -743,9 +1152,31 @@ extern "C" int gpk_paths_rollout_multi_z(gpk_handle h, const double* Zs, int64_t
                                          int64_t ldc, int64_t mstride, int S, const double* shift, const double* scale, int nx,
                                          const int* coord, const double* in_shift, const double* in_scale, const double* x0,
                                          int x0_rows, const double* U, int H, const double* lin, double* traj) {
-  return paths_rollout_multi(h, true, Zs, N, D, B, ls, sf2, Omega, phase, F, Coef, ldc, mstride, S, shift, scale, nx, coord,
-                             in_shift, in_scale, x0, x0_rows, U, H, lin, traj);
+  return paths_rollout_multi(h, true, false, Zs, N, D, B, ls, sf2, Omega, phase, F, Coef, ldc, mstride, S, shift, scale, nx, coord,
+                             in_shift, in_scale, x0, x0_rows, U, H, lin, traj, nullptr);
 }
+
+// ---- the gradient forms of the four batch entries ------------------------------------------------------------------------------
+#define GPK_PATHS_MULTI_GRAD(SUFFIX, OWNZ)                                                                                     \
+  extern "C" int gpk_paths_step_multi_grad##SUFFIX(gpk_handle h, const double* X, int64_t N, int D, int B, const double* ls,   \
+                                                   const double* sf2, const double* Omega, const double* phase, int64_t F,     \
+                                                   const double* Coef, int64_t ldc, int64_t mstride, int S,                    \
+                                                   const double* shift, const double* scale, const double* Xq, double* out,    \
+                                                   double* jac) {                                                              \
+    return paths_step_multi(h, OWNZ, true, X, N, D, B, ls, sf2, Omega, phase, F, Coef, ldc, mstride, S, shift, scale, Xq, out, \
+                            jac);                                                                                              \
+  }                                                                                                                            \
+  extern "C" int gpk_paths_rollout_multi_grad##SUFFIX(                                                                         \
+      gpk_handle h, const double* X, int64_t N, int D, int B, const double* ls, const double* sf2, const double* Omega,        \
+      const double* phase, int64_t F, const double* Coef, int64_t ldc, int64_t mstride, int S, const double* shift,            \
+      const double* scale, int nx, const int* coord, const double* in_shift, const double* in_scale, const double* x0,         \
+      int x0_rows, const double* U, int H, const double* lin, double* traj, double* jac) {                                     \
+    return paths_rollout_multi(h, OWNZ, true, X, N, D, B, ls, sf2, Omega, phase, F, Coef, ldc, mstride, S, shift, scale, nx,   \
+                               coord, in_shift, in_scale, x0, x0_rows, U, H, lin, traj, jac);                                  \
+  }
+GPK_PATHS_MULTI_GRAD(, false)
+GPK_PATHS_MULTI_GRAD(_z, true)
+#undef GPK_PATHS_MULTI_GRAD
 
 // The set-up of a sparse model's path set (gpk_sparse_paths_prepare, gpk_sparse.hip, which takes the model apart): Z (m x D),
 // the inverse factors Wuu and WS (mp x mp, lower tiles) and alpha_u (m x P) are the assembled model's.

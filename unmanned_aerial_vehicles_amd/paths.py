@@ -21,6 +21,10 @@ The sparse models (`SparseGP`, `BatchedSparseGP`) have them too, conditioned on 
 `BatchedSparsePosteriorPaths` at the end of this file - the same coefficient matrix over m + F basis rows, set up by
 `gpk_sparse_paths_prepare`; the batch through `gpk_paths_step_multi_z` / `gpk_paths_rollout_multi_z` (basis points per model).
 
+Path gradients: `step` and `rollout` of all four classes take `return_jacobian=True` and then also return the input Jacobian of
+every path at the point it was evaluated at (the `*_grad` entries: closed form, the same two launches per stage; the values keep
+their bits), so that a sampled rollout can be linearised with the function that produced it.
+
 The four classes share their frame: `check_randomness`, `_init_single` / `_init_batch` (+ `_prepare_models`), `_dense_paths`
 behind `__call__`, `check_rollout_args`; a class's own part is its prepare call.
 """
@@ -229,6 +233,8 @@ class PosteriorPaths:
     paths(X)                    all paths at the same M points: (M, S), or (M, P, S) for P > 1 (`sample_y`'s convention)
     paths.step(Xs)              Xs (S, D): path s at row s -> (S,) or (S, P); the hot path, two launches
     paths.rollout(x0, U, lin)   a closed-loop horizon in one call -> (H + 1, S, P)
+                                both with return_jacobian=True: also the input Jacobian of every path, (S, D) / (S, P, D) and
+                                (H, S, P, D), in the same two launches per stage; the values keep their bits
     paths.randomness            dict(omega, phase, weights, eps) it was built from
     paths.coef                  the device coefficient matrix (N + F, S P), column s P + p"""
 
@@ -289,8 +295,10 @@ class PosteriorPaths:
         f = self._y_mean + self._y_std * f
         return f[:, :, 0] if self.P == 1 else np.ascontiguousarray(f.transpose(0, 2, 1))
 
-    def step(self, Xs):
-        """Path s at ITS OWN point Xs[s] (gpk_paths_step): Xs (S, D) -> (S,), or (S, P) for P > 1."""
+    def step(self, Xs, return_jacobian=False):
+        """Path s at ITS OWN point Xs[s] (gpk_paths_step): Xs (S, D) -> (S,), or (S, P) for P > 1.  return_jacobian=True
+        (gpk_paths_step_grad): (values, jac), jac[s, p, d] = d values[s, p] / d Xs[s, d], (S, D) or (S, P, D); the values
+        have the bits of the call without it."""
         torch = _torch()
         Xs = check_queries(Xs, self.D)
         if Xs.shape[0] != self.S:
@@ -298,22 +306,35 @@ class PosteriorPaths:
         be = self.be
         q = be.upload(Xs)
         out = be.empty((self.S, self.P), torch.float64)
+        if return_jacobian:
+            jac = be.empty((self.S, self.P, self.D), torch.float64)
+            be.call("gpk_paths_step_grad", *self._model_args(), _p(q), _p(out), _p(jac))
+            jac = jac.cpu().numpy()
+            return self._squeeze(out.cpu().numpy()), jac[:, 0] if self.P == 1 else jac
         be.call("gpk_paths_step", *self._model_args(), _p(q), _p(out))
         return self._squeeze(out.cpu().numpy())
 
-    def rollout(self, x0, U, lin):
+    def rollout(self, x0, U, lin, return_jacobian=False):
         """A closed-loop horizon in one call (gpk_paths_rollout).  The state has P coordinates - the model's outputs are its
         residuals - and the query of path s at stage h is q_s = [x_s, U[h]]:
 
             x_s <- x_s + lin q_s + path_s(q_s)
 
         x0 (S, P), or (P,) as the start of every path; U (H, D - P); lin (P, D).  Returns the trajectory (H + 1, S, P), stage
-        0 = x0.  The next stage's queries never leave the device: 2 H launches, one synchronisation."""
+        0 = x0.  The next stage's queries never leave the device: 2 H launches, one synchronisation.
+
+        return_jacobian=True (gpk_paths_rollout_grad): (traj, jac), jac (H, S, P, D): jac[h, s] is the Jacobian of path s at
+        its stage-h query [traj[h, s], U[h]], so the sampled closed loop linearises as A_h = I + lin[:, :P] + jac[h, s][:, :P],
+        B_h = lin[:, P:] + jac[h, s][:, P:]; traj has the bits of the call without it."""
         P, D, S = self.P, self.D, self.S
         if P > D:
             raise ValueError(f"rollout needs a state of P = {P} <= D = {D} coordinates")
         x0, rows, U, H, lin = check_rollout_args(S, D, x0, U, lin, nx=P)
         traj = np.empty((H + 1, S, P))
+        if return_jacobian:
+            jac = np.empty((H, S, P, D))
+            self.be.call("gpk_paths_rollout_grad", *self._model_args(), _hp(x0), rows, _hp(U), H, _hp(lin), _hp(traj), _hp(jac))
+            return traj, jac
         self.be.call("gpk_paths_rollout", *self._model_args(), _hp(x0), rows, _hp(U), H, _hp(lin), _hp(traj))
         return traj
 
@@ -325,6 +346,8 @@ class BatchedPosteriorPaths:
     paths(X)                            all paths of all models at the same M points: (M, B, S)
     paths.step(Xs)                      Xs (S, D): path s of every model at row s -> (S, B); the hot path, two launches
     paths.rollout(x0, U, lin, ...)      a closed-loop horizon in one call -> (H + 1, S, nx)
+                                        both with return_jacobian=True: also the input Jacobians, (S, B, D) and - in raw
+                                        units - (H, S, B, D)
     paths.randomness                    dict(omega, phase, weights, eps) it was built from
     paths.coef                          the device coefficient matrix (N + F, B mstride), model-major: model b, path s is
                                         column b mstride + s, mstride = S rounded up to a multiple of 8 (`paths.mstride`)
@@ -334,6 +357,7 @@ class BatchedPosteriorPaths:
     affine map per model behind them (a trainer's target scaler)."""
 
     _STEP, _ROLLOUT = "gpk_paths_step_multi", "gpk_paths_rollout_multi"
+    _STEP_GRAD, _ROLLOUT_GRAD = "gpk_paths_step_multi_grad", "gpk_paths_rollout_multi_grad"
 
     def __init__(self):
         raise TypeError("use BatchedARDGP.sample_paths or BatchedPosteriorPaths.from_randomness")
@@ -443,8 +467,10 @@ class BatchedPosteriorPaths:
             res[:, b, :] = self._shift[b] + self._scale[b] * out.cpu().numpy()
         return res
 
-    def step(self, Xs):
-        """Path s of every model at ITS OWN point Xs[s] (gpk_paths_step_multi): Xs (S, D) -> (S, B)."""
+    def step(self, Xs, return_jacobian=False):
+        """Path s of every model at ITS OWN point Xs[s] (gpk_paths_step_multi): Xs (S, D) -> (S, B).  return_jacobian=True
+        (gpk_paths_step_multi_grad): (values, jac), jac[s, b, d] = d values[s, b] / d Xs[s, d], (S, B, D); the values have the
+        bits of the call without it, and column b of jac those of model b's own `PosteriorPaths.step`."""
         torch = _torch()
         Xs = check_queries(Xs, self.D)
         if Xs.shape[0] != self.S:
@@ -452,10 +478,14 @@ class BatchedPosteriorPaths:
         be = self.be
         q = be.upload(Xs)
         out = be.empty((self.S, self.B), torch.float64)
+        if return_jacobian:
+            jac = be.empty((self.S, self.B, self.D), torch.float64)
+            be.call(self._STEP_GRAD, *self._model_args(), _p(q), _p(out), _p(jac))
+            return out.cpu().numpy(), jac.cpu().numpy()
         be.call(self._STEP, *self._model_args(), _p(q), _p(out))
         return out.cpu().numpy()
 
-    def rollout(self, x0, U, lin, coord=None, in_scaler=None):
+    def rollout(self, x0, U, lin, coord=None, in_scaler=None, return_jacobian=False):
         """A closed-loop horizon in one call (gpk_paths_rollout_multi), in raw units.  The state has nx = len(lin) coordinates,
         B <= nx <= D; model b's output is added to state coordinate coord[b] (default 0 .. B - 1; distinct); a coordinate
         without a model advances by `lin` alone.  The models read the scaled query: stage h, path s,
@@ -464,7 +494,11 @@ class BatchedPosteriorPaths:
 
         x0 (S, nx), or (nx,) as the start of every path; U (H, D - nx); lin (nx, D); in_scaler: None (identity), a pair
         (shift (D,), scale (D,)) or an object with `mean_` / `scale_`.  Returns the trajectory (H + 1, S, nx), stage 0 = x0.
-        The next stage's queries never leave the device: 2 H launches, one synchronisation."""
+        The next stage's queries never leave the device: 2 H launches, one synchronisation.
+
+        return_jacobian=True (gpk_paths_rollout_multi_grad): (traj, jac), jac (H, S, B, D): jac[h, s, b] is the gradient of
+        model b's path s at stage h's query w.r.t. the RAW q_s = [traj[h, s], U[h]] (it includes 1 / in_scale); traj has the
+        bits of the call without it."""
         B, D, S = self.B, self.D, self.S
         x0, rows, U, H, lin = check_rollout_args(S, D, x0, U, lin)
         nx = lin.shape[0]
@@ -487,6 +521,11 @@ class BatchedPosteriorPaths:
             if not in_scale.all():
                 raise ValueError("in_scale must be non-zero")
         traj = np.empty((H + 1, S, nx))
+        if return_jacobian:
+            jac = np.empty((H, S, B, D))
+            self.be.call(self._ROLLOUT_GRAD, *self._model_args(), nx, coord.ctypes.data_as(C.POINTER(C.c_int)),
+                         _hp(in_shift), _hp(in_scale), _hp(x0), rows, _hp(U), H, _hp(lin), _hp(traj), _hp(jac))
+            return traj, jac
         self.be.call(self._ROLLOUT, *self._model_args(), nx, coord.ctypes.data_as(C.POINTER(C.c_int)),
                      _hp(in_shift), _hp(in_scale), _hp(x0), rows, _hp(U), H, _hp(lin), _hp(traj))
         return traj
@@ -534,6 +573,7 @@ class BatchedSparsePosteriorPaths(BatchedPosteriorPaths):
     `SparsePosteriorPaths.from_randomness(models[b], ...)` on the same randomness."""
 
     _STEP, _ROLLOUT = "gpk_paths_step_multi_z", "gpk_paths_rollout_multi_z"
+    _STEP_GRAD, _ROLLOUT_GRAD = "gpk_paths_step_multi_grad_z", "gpk_paths_rollout_multi_grad_z"
 
     def __init__(self):
         raise TypeError("use BatchedSparseGP.sample_paths or BatchedSparsePosteriorPaths.from_randomness")
@@ -578,10 +618,20 @@ def nominal_rollouts(dynamics, state, U_guess, dt, n_rollouts):
     return np.repeat(nominal[None], max(int(n_rollouts), 0), axis=0), lin
 
 
-def roll_paths(paths, state, U_guess, lin, **how):
-    """`paths.rollout` from `state` under U_guess (4+, N), as (R, 6, N + 1) - the layout of the trainers' X_guess."""
-    traj = paths.rollout(state, np.ascontiguousarray(U_guess[:4].T), lin, **how)      # (N + 1, R, 6)
-    return np.ascontiguousarray(traj.transpose(1, 2, 0))
+def roll_paths(paths, state, U_guess, lin, return_jacobian=False, **how):
+    """`paths.rollout` from `state` under U_guess (4+, N), as (R, 6, N + 1) - the layout of the trainers' X_guess.
+    return_jacobian=True: (X, J), J (R, N, 6, 10) the Jacobian of the sampled residual of state coordinate i at stage k of
+    rollout r w.r.t. [x_k, u_k]; a batch's models fill the rows of their `coord` (default 0 .. B - 1), the others stay zero."""
+    U = np.ascontiguousarray(U_guess[:4].T)
+    if not return_jacobian:
+        traj = paths.rollout(state, U, lin, **how)      # (N + 1, R, 6)
+        return np.ascontiguousarray(traj.transpose(1, 2, 0))
+    traj, jac = paths.rollout(state, U, lin, return_jacobian=True, **how)      # (N + 1, R, 6), (N, R, outputs, 10)
+    H, R, n_out, D = jac.shape
+    rows = list(how.get("coord", range(n_out)))
+    J = np.zeros((R, H, traj.shape[2], D))
+    J[:, :, rows, :] = jac.transpose(1, 0, 2, 3)
+    return np.ascontiguousarray(traj.transpose(1, 2, 0)), J
 
 
 def cached_path_set(owner, attr, model, n_rollouts, n_features, random_state, finish=None):

@@ -244,7 +244,7 @@ class SimpleQuadrotorGP:
         out[keep] = mean[keep, :n_states]
         return out
 
-    def sample_rollouts(self, state, U_guess, dt, n_rollouts=64, n_features=1024, random_state=0):
+    def sample_rollouts(self, state, U_guess, dt, n_rollouts=64, n_features=1024, random_state=0, return_jacobian=False):
         """`n_rollouts` closed-loop rollouts under the model's own uncertainty: rollout r follows ONE posterior function draw
         along the whole horizon, stage k + 1 evaluated at the state its sampled residual of stage k produced,
 
@@ -255,16 +255,26 @@ class SimpleQuadrotorGP:
         is drawn once and cached on the object until `train_gp` / `load_model` - or, for a `SparseGP` as `gp_model`
         (`SparseGP.sample_paths`), until that model takes rows or is retrained: the same functions from call to call.
         Untrained, or on any failure (printed): the nominal trajectory repeated R times - it never raises into the control
-        loop."""
+        loop.
+
+        return_jacobian=True: (X, J) in one call (`PosteriorPaths.rollout(..., return_jacobian=True)`); X as above, with the
+        same bits; J (R, N, 6, 10): J[r, k] is the Jacobian of the SAMPLED residual f_r at [x_k, u_k] of rollout r - the
+        function that produced the rollout, not the posterior mean `linearize_gp_residuals` linearises.  With the `lin` of the
+        nominal double integrator (`paths.nominal_rollouts`) the stage matrices of rollout r's closed loop are
+        A_k = I + lin[:, :6] + J[r, k][:, :6] and B_k = lin[:, 6:] + J[r, k][:, 6:] (no gain / dt factor: J already is the
+        derivative of the state increment).  Untrained or failed: the nominal trajectory and a zero J."""
         from .paths import cached_path_set, nominal_rollouts, roll_paths
         state = np.asarray(state, dtype=float).reshape(-1)[:6]
         U_guess = np.asarray(U_guess, dtype=float)
         fallback, lin = nominal_rollouts(self._nominal_dynamics, state, U_guess, dt, n_rollouts)
+        if return_jacobian:
+            fallback = (fallback, np.zeros((fallback.shape[0], U_guess.shape[1], 6, 10)))
         if not self.is_trained:
             return fallback
         try:
             paths = cached_path_set(self, "_paths", self.gp_model, n_rollouts, n_features, random_state)
-            traj = roll_paths(paths, state, U_guess, lin)
+            traj = roll_paths(paths, state, U_guess, lin, return_jacobian=True) if return_jacobian else \
+                roll_paths(paths, state, U_guess, lin)
             self.prediction_count += int(n_rollouts) * U_guess.shape[1]
             return traj
         except Exception as e:  # noqa: BLE001

@@ -507,7 +507,7 @@ class PreTrainedGP:
             print(f"GP sampling failed: {e}")
             return np.zeros((mean.shape[0], 6, int(n_samples)))
 
-    def sample_rollouts(self, state, U_guess, dt, n_rollouts=64, n_features=1024, random_state=0):
+    def sample_rollouts(self, state, U_guess, dt, n_rollouts=64, n_features=1024, random_state=0, return_jacobian=False):
         """`n_rollouts` closed-loop rollouts under the loaded models' own uncertainty, in raw units: rollout r follows ONE
         posterior function draw of every per-axis model along the whole horizon, stage k + 1 evaluated at the state its
         sampled residuals of stage k produced,
@@ -521,11 +521,21 @@ class PreTrainedGP:
         (n_rollouts, n_features, random_state) is drawn once and cached on the object until `load_dict` - or until a sparse
         model takes rows or is retrained (a path set is a snapshot) - the same functions from call to call.  Not loaded, models
         that cannot be fused into a batch (a single model, different inputs or scalers), or any failure: the reason is printed
-        and the nominal trajectory is returned R times - it never raises into the control loop."""
+        and the nominal trajectory is returned R times - it never raises into the control loop.
+
+        return_jacobian=True: (X, J) in one call (`rollout(..., return_jacobian=True)` of the path set); X as above, with the
+        same bits; J (R, N, 6, 10) in raw units: J[r, k, i] is the gradient of the SAMPLED residual of state coordinate i at
+        stage k of rollout r w.r.t. [x_k, u_k] - the function that produced the rollout, not the posterior mean
+        `linearize_residuals` linearises - and a coordinate without a model has a zero row.  With the `lin` of the nominal
+        double integrator (`paths.nominal_rollouts`) the stage matrices of rollout r's closed loop are
+        A_k = I + lin[:, :6] + J[r, k][:, :6] and B_k = lin[:, 6:] + J[r, k][:, 6:] (no gain / dt factor: J already is the
+        derivative of the state increment).  Not loaded or failed: the nominal trajectory and a zero J."""
         from .paths import cached_path_set, nominal_rollouts, roll_paths
         U_guess = np.asarray(U_guess, dtype=float)
         state = np.asarray(state, dtype=float).reshape(-1)[:6]
         fallback, lin = nominal_rollouts(GPTrainer._nominal_dynamics, state, U_guess, dt, n_rollouts)
+        if return_jacobian:
+            fallback = (fallback, np.zeros((fallback.shape[0], U_guess.shape[1], 6, 10)))
         try:
             if not self.is_loaded:
                 raise RuntimeError("no models are loaded")
@@ -539,8 +549,13 @@ class PreTrainedGP:
                 paths.set_output_scaler([float(np.ravel(s.mean_)[0]) for s in sys_], [float(np.ravel(s.scale_)[0]) for s in sys_])
 
             paths = cached_path_set(self, "_axis_paths", bg, n_rollouts, n_features, random_state, finish=target_scalers)
-            traj = roll_paths(paths, state, U_guess, lin, coord=[OUTPUT_NAMES.index(n) for n in names],
-                              in_scaler=self.scalers_X[names[0]])
+            how = dict(coord=[OUTPUT_NAMES.index(n) for n in names], in_scaler=self.scalers_X[names[0]])
+            if return_jacobian:
+                traj, J = roll_paths(paths, state, U_guess, lin, return_jacobian=True, **how)
+                if not (np.isfinite(traj).all() and np.isfinite(J).all()):
+                    raise FloatingPointError("non-finite trajectory")
+                return traj, J
+            traj = roll_paths(paths, state, U_guess, lin, **how)
             if not np.isfinite(traj).all():
                 raise FloatingPointError("non-finite trajectory")
             return traj
