@@ -66,7 +66,8 @@ GPK_API int64_t gpk_padded(int64_t n);
  * (V = W K*^T with the column-norm epilogue); tag GPK_TIMED_GRAM: the Gram kernel of gpk_gram; tag GPK_TIMED_GRAD: the
  * streaming pass of gpk_lml_grad over K^-1; tag GPK_TIMED_POTRF: the launches of one gpk_potrf; tag GPK_TIMED_COV: the
  * symmetric product (K(Xq, Xq) + noise I - V^T V) of gpk_predict_cov_inv / gpk_predict_cov; tag GPK_TIMED_JAC: the second
- * triangular product (C = W^T V) of gpk_predict_var_grad_inv - and keeps the
+ * triangular product (C = W^T V) of gpk_predict_var_grad_inv; tag GPK_TIMED_PROPAGATE: the advance launch of every stage of
+ * gpk_propagate_host[_multi] - and keeps the
  * last 64 pairs.  gpk_kernel_times synchronises the stream and returns the elapsed milliseconds of the bracketed
  * launches with that tag still in the ring, oldest first (*n_out of them, at most max_n).  bench.py uses it to
  * report the dominant kernel's duration over exactly the timed steps; rocprofv3's kernel trace of the same run is
@@ -101,7 +102,7 @@ GPK_API int64_t gpk_padded(int64_t n);
 GPK_API int gpk_set_option(gpk_handle h, const char* name, int value);
 GPK_API int gpk_set_option_str(gpk_handle h, const char* name, const char* value);
 enum { GPK_TIMED_K5 = 1, GPK_TIMED_GRAM = 2, GPK_TIMED_GRAD = 3, GPK_TIMED_POTRF = 4, GPK_TIMED_COV = 5, GPK_TIMED_JAC = 6,
-       GPK_TIMED_SPARSE_STATS = 7, GPK_TIMED_SPARSE_PASS = 8 };
+       GPK_TIMED_SPARSE_STATS = 7, GPK_TIMED_SPARSE_PASS = 8, GPK_TIMED_PROPAGATE = 9 };
 GPK_API int gpk_timing(gpk_handle h, int enable);
 GPK_API int gpk_kernel_times(gpk_handle h, int tag, double* ms, int max_n, int* n_out);
 
@@ -1024,6 +1025,48 @@ GPK_API int gpk_paths_rollout_multi_grad_z(gpk_handle h, const double* Zs, int64
                                            const double* scale, int nx, const int* coord, const double* in_shift,
                                            const double* in_scale, const double* x0, int x0_rows, const double* U, int H,
                                            const double* lin, double* traj, double* jac);
+
+/* ---- K11: horizon propagation - the posterior's mean rollout with the linearised state covariance, one call -------------
+ * The first-order propagation of Hewing, Kabzan and Zeilinger (Cautious MPC using GP regression): state x in R^nx, query
+ * q = [x, u] in R^D, lin (nx x D) the nominal increment as in gpk_paths_rollout[_multi].  For rollout r and stage h:
+ *   z = (q - in_shift) / in_scale;  mu_b, J_b = d mu_b / d q (RAW units: includes 1 / in_scale[d]) and v_b the posterior mean,
+ *   its Jacobian and the variance of output b at z, in target units: v_b = y_std[b]^2 (max(kss - |W k*|^2, floor) [+ noise]);
+ *   x_{h+1}     = x_h + lin q + sum_b e_coord[b] mu_b
+ *   A_h         = I + lin[:, :nx] + sum_b e_coord[b] J_b[:nx]
+ *   Sigma_{h+1} = A_h Sigma_h A_h^T + sum_b v_b e_coord[b] e_coord[b]^T + Q
+ * A coordinate without a model advances by lin alone and receives no variance.  fp64 only.  Host arrays in, host arrays out:
+ *   x0 (x0_rows x nx, rows = R or 1), U (u_rows x H x nu, rows = R or 1, nu = D - nx; NULL if nu = 0), lin (nx x D),
+ *   Sigma0 (s_rows x nx x nx, rows = R or 1; NULL: zero; the LOWER triangle is read and mirrored), Q (nx x nx or NULL: zero;
+ *   the lower triangle is read);  traj ((H + 1) x R x nx), Sigma ((H + 1) x R x nx x nx, every block symmetric bit for bit),
+ *   and optionally (NULL: not wanted) the stage quantities exactly as used: mean and var (H x R x P or B), jac (H x R x P or
+ *   B x D).  var_includes_noise != 0 adds `noise` (normalised-target units, per model in the batch form) to the clipped variance.
+ * Launches: per stage the two small-batch launches "mean + Jacobian + variance" (gpk_small.hip; mean, var and jac of a stage
+ * have the BITS of gpk_predict_host_grad / gpk_predict_host_multi_grad called on the R rows [traj[h], U[h]], scaled) and one
+ * advance launch (one workgroup per rollout, sequential fixed-order sums): 3 H launches, one copy in before the chain, up to five
+ * out after it, ONE stream synchronisation at the end and none between the stages (the caller's arrays are pageable host memory:
+ * the runtime stages the copies to and from them and may wait on them by itself).  Repeatable bit for bit.  Work area: the
+ * handle's scratch.
+ * gpk_propagate_host: one exact model with P outputs; the state is its outputs (nx = P <= D), no input scaler.  Model
+ *   arguments as gpk_predict_host_grad.
+ * gpk_propagate_host_multi: B <= 8 single-output models, model arguments as gpk_predict_host_multi_grad; nx, coord (B distinct
+ *   state coordinates), in_shift / in_scale (D each, both or neither) as gpk_paths_rollout_multi.  RAW units.
+ * GPK_BAD_ARG (with a message, before any launch): R not in [1, 32], H not in [1, 256], nx or D above 16, nx > D, nx < B,
+ *   gpk_padded(N) > 16384, Np != gpk_padded(N), ldw < Np, a wrong row count, NaN or infinity in a host input (the model's ls,
+ *   sf2, y_mean, y_std, kss, floor and noise included), a length-scale that is not positive, in_scale zero,
+ *   coord out of range or repeated, a null pointer, batched mode.                                                          */
+GPK_API int gpk_propagate_host(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
+                               double sf2, const double* y_mean, const double* y_std, const double* W, int64_t Np, int64_t ldw,
+                               double kss, double floor_, int var_includes_noise, double noise, const double* x0, int x0_rows,
+                               const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows, const double* Q,
+                               int R, int H, double* traj, double* Sigma, double* mean, double* var, double* jac);
+GPK_API int gpk_propagate_host_multi(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D,
+                                     const double* ls, const double* sf2, const double* y_mean, const double* y_std,
+                                     const double* const* W, int64_t Np, int64_t ldw, const double* kss, double floor_,
+                                     int var_includes_noise, const double* noise, int nx, const int* coord,
+                                     const double* in_shift, const double* in_scale, const double* x0, int x0_rows,
+                                     const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows,
+                                     const double* Q, int R, int H, double* traj, double* Sigma, double* mean, double* var,
+                                     double* jac);
 
 #ifdef __cplusplus
 }

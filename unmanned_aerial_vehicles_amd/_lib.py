@@ -20,6 +20,7 @@ GPK_TIMED_K5, GPK_TIMED_GRAM, GPK_TIMED_GRAD, GPK_TIMED_POTRF = 1, 2, 3, 4
 GPK_TIMED_COV = 5
 GPK_TIMED_JAC = 6
 GPK_TIMED_SPARSE_STATS, GPK_TIMED_SPARSE_PASS = 7, 8
+GPK_TIMED_PROPAGATE = 9
 
 _vp, _i64, _int, _dbl = C.c_void_p, C.c_int64, C.c_int, C.c_double
 _dp = C.POINTER(C.c_double)
@@ -161,6 +162,13 @@ SIGNATURES = {
                                            _vp, _vp, _vp]),
     "gpk_paths_rollout_multi_grad_z": (_int, [_vp, _vp, _i64, _int, _int, _dp, _dp, _vp, _vp, _i64, _vp, _i64, _i64, _int, _dp, _dp,
                                               _int, C.POINTER(_int), _dp, _dp, _dp, _int, _dp, _int, _dp, _dp, _dp]),
+    # horizon propagation (host pointers as void*, as gpk_predict_host_grad / gpk_predict_host_multi_grad): the model, kss, floor,
+    # var_includes_noise, noise, [nx, coord, in_shift, in_scale,] x0, rows, U, rows, lin, Sigma0, rows, Q, R, H, the five outputs
+    "gpk_propagate_host": (_int, [_vp, _vp, _vp, _i64, _int, _int, _vp, _dbl, _vp, _vp, _vp, _i64, _i64, _dbl, _dbl, _int, _dbl,
+                                  _vp, _int, _vp, _int, _vp, _vp, _int, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp]),
+    "gpk_propagate_host_multi": (_int, [_vp, _int, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _dbl, _int, _vp,
+                                        _int, C.POINTER(_int), _vp, _vp, _vp, _int, _vp, _int, _vp, _vp, _int, _vp, _int, _int,
+                                        _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

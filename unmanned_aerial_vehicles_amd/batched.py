@@ -407,6 +407,54 @@ class BatchedARDGP:
         s2 = sv["ys"] ** 2
         return mean, dmean, (var * s2[:, None]).T, (dvar * s2[:, None, None]).transpose(1, 0, 2)
 
+    # ------------------------------------------------------------------ horizon propagation (K11, per-axis batch)
+    def propagate(self, x0, U, lin, coord=None, in_scaler=None, Sigma0=None, process_noise=None, var_includes_noise=False,
+                  return_stages=False, out_scaler=None, route="auto"):
+        """The batch's own closed-loop horizon in raw units: mean trajectory and linearised state covariance
+        (`propagate`'s module docstring has the recursion), with the conventions of `BatchedPosteriorPaths.rollout`: the state
+        has nx = len(lin) coordinates, B <= nx <= D; model b drives state coordinate coord[b] (default 0 .. B - 1); the models
+        read z = (q - in_shift) / in_scale (in_scaler: None, a pair (shift, scale) or an object with `mean_` / `scale_`);
+        out_scaler (mean (B,), scale (B,)): an affine map mean[b] + scale[b] y behind every model's output (a trainer's target
+        scaler).  x0 (nx,) or (R, nx), U (H, nu) or (R, H, nu), Sigma0 / process_noise as
+        `GaussianProcessRegressor.propagate`.  Returns (traj (H + 1, R, nx), Sigma (H + 1, R, nx, nx)) and, with
+        return_stages=True, {"mean" (H, R, B), "var" (H, R, B), "jac" (H, R, B, D)}: jac per unit of the RAW query.  One C call
+        per horizon (`gpk_propagate_host_multi`, three launches per stage for all models) where `_serve_state` holds; otherwise
+        (or with the backend option small_path=0, or route="host") the same recursion as a host loop over
+        `predict_jacobian`."""
+        from . import propagate as _pg
+        if not self.models:
+            raise RuntimeError("this BatchedARDGP is not fitted yet")
+        B = len(self.models)
+        D = self.models[0].n_features_in_
+        x0, U, lin, S0, Q, R, H, coord, in_shift, in_scale, o_mean, o_scale = _pg.check_batch(
+            B, D, x0, U, lin, coord, in_scaler, out_scaler, Sigma0, process_noise, route)
+        nx = lin.shape[0]
+        sv = self._serve_state(True, any_dtype=True) if route == "auto" else None
+        if sv is not None and int(sv["dev0"].be.options.get("small_path", 1)) != 0:
+            d0 = sv["dev0"]
+            ym, ys = sv["ym"], sv["ys"]
+            if out_scaler is not None:
+                ym, ys = np.ascontiguousarray(o_mean + o_scale * sv["ym"]), np.ascontiguousarray(o_scale * sv["ys"])
+            # (the noise enters through the prior variance the clip starts from, as in predict_host_grad: the same bits)
+            kss = sv["kss"] if var_includes_noise else sv["sf2"]
+            traj, Sigma = np.empty((H + 1, R, nx)), np.empty((H + 1, R, nx, nx))
+            mean, var, jac = (np.empty((H, R, B)), np.empty((H, R, B)), np.empty((H, R, B, D))) if return_stages else (None,) * 3
+            cd = (C.c_int * B)(*coord)
+            try:
+                d0.be.call("gpk_propagate_host_multi", B, sv["X"], sv["alpha"], d0.N, d0.D, _hp(sv["ls"]), _hp(sv["sf2"]), _hp(ym),
+                           _hp(ys), sv["W"], d0.Np, d0.Np, _hp(kss), 0.0, 0, None, nx, cd, _hp(in_shift), _hp(in_scale), _hp(x0),
+                           x0.shape[0], _hp(U) if D > nx else None, U.shape[0], _hp(lin), _hp(S0),
+                           1 if S0 is None else S0.shape[0], _hp(Q), R, H, _hp(traj), _hp(Sigma), _hp(mean), _hp(var), _hp(jac))
+            except _lib.GPKError as e:      # a limit of the entry: the caller's arguments, with the library's message
+                if e.code == _lib.GPK_BAD_ARG:
+                    raise ValueError(str(e)) from None
+                raise
+            return (traj, Sigma, {"mean": mean, "var": var, "jac": jac}) if return_stages else (traj, Sigma)
+        stage = _pg.batch_stage(self.predict_jacobian, _pg.noise_levels(self.models), in_shift, in_scale, o_mean, o_scale,
+                                var_includes_noise)
+        traj, Sigma, stages = _pg.host_loop(stage, coord, x0, U, lin, S0, Q, R, H)
+        return (traj, Sigma, stages) if return_stages else (traj, Sigma)
+
     def _fused64(self):
         """The fp64 buffers of the fused launches (shared X, alpha as one column per model) - `_fused` itself unless the
         batch serves in fp32."""

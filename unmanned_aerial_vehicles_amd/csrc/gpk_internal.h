@@ -282,13 +282,14 @@ struct ServeOut {
 bool gpk_small_ok(int64_t Np, int D, int P, int64_t M);
 // doubles of device work area (`work`) that a call of the given kind needs: per model K* (32 x Np) + the workgroups' shares
 // (F inverse factors per model: K*, the mean and the Jacobian shares stay one set per model)
-enum { GPK_SMALL_PREDICT, GPK_SMALL_COV, GPK_SMALL_GRAD };
+enum { GPK_SMALL_PREDICT, GPK_SMALL_COV, GPK_SMALL_GRAD, GPK_SMALL_JACVAR };
 size_t gpk_small_work_doubles(int call, int64_t Np, int B, int64_t M, int D, int P, int F);
 // The launches of one call on M <= GPK_SMALL_MAX_M queries, no synchronisation; Xq and the outputs may be pinned, mapped host
 // memory.  The launch counts are those of one model with one output for every B, P and F:
 //   GPK_SMALL_PREDICT  mean: 1 launch; with out.var 2
 //   GPK_SMALL_GRAD     mean + dmean: 1 launch; with out.var and out.dvar 3
 //   GPK_SMALL_COV      mean + cov (m.noise on the diagonal, not clipped): 2 launches
+//   GPK_SMALL_JACVAR   mean + dmean + var, F = 1 (a stage of gpk_propagate_host[_multi]): 2 launches, the bits of GPK_SMALL_GRAD's
 // Block b of every output has the bits of model b served alone.
 int gpk_small_launch(gpk_handle h, int call, const ServeModels& m, const double* Xq, int64_t M, double* work, const ServeOut& out);
 // ... as one-call serving (gpk_serve.hip): host queries in, host results out through the pinned, mapped block, one

@@ -1,0 +1,281 @@
+// Horizon propagation (K11): the posterior's own mean rollout with the linearised state covariance, one call per horizon.
+//
+//   q = [x_h, u_h],  z = (q - in_shift) / in_scale
+//   x_{h+1}     = x_h + lin q + sum_b e_coord[b] mu_b(z)
+//   A_h         = I + lin[:, :nx] + sum_b e_coord[b] J_b[:nx]              J_b = d mu_b / d q (raw units)
+//   Sigma_{h+1} = A_h Sigma_h A_h^T + sum_b v_b(z) e_coord[b] e_coord[b]^T + Q
+//
+// Every stage's query is the previous stage's result, so a stage is three launches in stream order and nothing else: the two
+// small-batch launches of GPK_SMALL_JACVAR (gpk_small.hip: mean + Jacobian + variance of the R query rows, the bits of
+// gpk_predict_host[_multi]_grad at those rows) and propagate_advance_kernel below, which composes the stage and writes the next
+// stage's scaled query rows where its first launch reads them.  The state (x, Sigma), the queries, the stage results and the
+// horizon's outputs stay in one device block; ONE upload before the chain ([x | Sigma | q | lin | Q | U] as one block), up to five
+// downloads and ONE stream synchronisation after it.  The caller's arrays are ordinary (pageable) host memory: the runtime stages
+// those copies and may wait on them by itself; nothing waits between the stages.
+#include "gpk_internal.h"
+
+namespace {
+
+constexpr int PROP_MAX_R = GPK_SMALL_MAX_M, PROP_MAX_H = 256, PROP_MAX_NX = 16, PROP_MAX_D = 16;
+
+// The composition's parameters.  Output o of the stage (a single model's output p, or model b of a batch) sits at
+// smean[o * so + m * sm], svar[o * vo + m] (normalised-target units) and sjac[(o * so + m * sm) * D + d] for query row m.
+struct PropK {
+  int nx, D, NO;                     // state width, query width, outputs of a stage
+  int so, sm, vo;
+  int model_of[PROP_MAX_NX];         // state coordinate -> the output that drives it, or -1 (lin alone, no variance)
+  int scaled;                        // the queries go through (q - in_shift) / in_scale, the Jacobians through 1 / in_scale
+  double in_shift[PROP_MAX_D], in_scale[PROP_MAX_D];
+  double ystd2[16];                  // y_std[o]^2: the variance in target units is svar * ystd2, as the Python layer forms it
+  double noise[16];                  // added to svar (normalised units) when the variance is to include the noise level
+  int add_noise;
+};
+
+// One workgroup per rollout r, thread (i, j) = (tid >> 4, tid & 15).  Sequential, fixed-order sums; Sigma in LDS; the lower
+// triangle of T A^T is formed and mirrored, so Sigma is symmetric bit for bit.  x and S are the rollout's state, updated in
+// place (this workgroup alone touches row r of either); qnext: the next stage's scaled queries (R x D), null at the last stage.
+__global__ __launch_bounds__(256) void propagate_advance_kernel(PropK k, int R, const double* __restrict__ smean,
+                                                                const double* __restrict__ svar, const double* __restrict__ sjac,
+                                                                const double* __restrict__ lin, const double* __restrict__ Qn,
+                                                                const double* __restrict__ u, const double* __restrict__ u_next,
+                                                                long long u_row_stride, double* x, double* S, double* qnext,
+                                                                double* traj_next, double* sig_next, double* omean, double* ovar,
+                                                                double* ojac) {
+  __shared__ double A[16][17], Sg[16][17], T[16][17], J[16][17];
+  __shared__ double q[16], mu[16], vv[16], xn[16];
+  const int tid = threadIdx.x, i = tid >> 4, j = tid & 15, r = blockIdx.x;
+  const int nx = k.nx, D = k.D, NO = k.NO;
+  if (tid < D) q[tid] = tid < nx ? x[(long long)r * nx + tid] : u[r * u_row_stride + (tid - nx)];
+  if (i < nx && j < nx) Sg[i][j] = S[((long long)r * nx + i) * nx + j];
+  if (tid < NO) {
+    const double v = svar[tid * k.vo + r];
+    mu[tid] = smean[tid * k.so + r * k.sm];
+    vv[tid] = (k.add_noise ? v + k.noise[tid] : v) * k.ystd2[tid];
+  }
+  if (i < NO && j < D) {
+    const double g = sjac[(long long)(i * k.so + r * k.sm) * D + j];
+    J[i][j] = k.scaled ? g / k.in_scale[j] : g;
+  }
+  __syncthreads();
+  if (i < nx && j < nx) {
+    const int o = k.model_of[i];
+    double a = (i == j ? 1.0 : 0.0) + lin[i * D + j];
+    if (o >= 0) a += J[o][j];
+    A[i][j] = a;
+  }
+  if (tid < nx) {
+    const int o = k.model_of[tid];
+    double a = 0.0;
+    for (int d = 0; d < D; ++d) a = __builtin_fma(lin[tid * D + d], q[d], a);
+    double v = q[tid] + a;
+    if (o >= 0) v += mu[o];
+    xn[tid] = v;
+  }
+  __syncthreads();
+  if (i < nx && j < nx) {
+    double t = 0.0;
+    for (int c = 0; c < nx; ++c) t = __builtin_fma(A[i][c], Sg[c][j], t);
+    T[i][j] = t;
+  }
+  __syncthreads();
+  if (i < nx && j <= i) {
+    double s = 0.0;
+    for (int c = 0; c < nx; ++c) s = __builtin_fma(T[i][c], A[j][c], s);
+    const int o = k.model_of[i];
+    if (i == j && o >= 0) s += vv[o];
+    if (Qn) s += Qn[i * nx + j];
+    const long long at = (long long)r * nx * nx;
+    S[at + i * nx + j] = s;
+    S[at + j * nx + i] = s;
+    sig_next[at + i * nx + j] = s;
+    sig_next[at + j * nx + i] = s;
+  }
+  if (tid < nx) {
+    x[(long long)r * nx + tid] = xn[tid];
+    traj_next[(long long)r * nx + tid] = xn[tid];
+  }
+  if (qnext && tid < D) {
+    const double raw = tid < nx ? xn[tid] : u_next[r * u_row_stride + (tid - nx)];
+    qnext[(long long)r * D + tid] = k.scaled ? (raw - k.in_shift[tid]) / k.in_scale[tid] : raw;
+  }
+  if (tid < NO) {
+    if (omean) omean[(long long)r * NO + tid] = mu[tid];
+    if (ovar) ovar[(long long)r * NO + tid] = vv[tid];
+  }
+  if (ojac && i < NO && j < D) ojac[((long long)r * NO + i) * D + j] = J[i][j];
+}
+
+bool prop_finite(const double* p, size_t n) {
+  for (size_t i = 0; i < n; ++i)
+    if (!(p[i] - p[i] == 0.0)) return false;
+  return true;
+}
+
+// What the two entries share past their model arguments.  k: nx, D, NO, the strides, model_of, the scaler, ystd2 and the noise
+// filled in by the entry.
+struct Horizon {
+  const double *x0, *U, *lin, *Sigma0, *Q;
+  int x0_rows, u_rows, s_rows, R, H;
+  double *traj, *Sigma, *mean, *var, *jac;
+};
+
+int propagate_run(gpk_handle h, const std::string& who, const ServeModels& m, PropK k, const Horizon& z) {
+  const int nx = k.nx, D = k.D, nu = D - nx, NO = k.NO, R = z.R, H = z.H;
+  GPK_REQUIRE(h, h->batch == 1, who + "not available in batched mode");
+  GPK_REQUIRE(h, R >= 1 && R <= PROP_MAX_R, who + "R must be in [1, 32]");
+  GPK_REQUIRE(h, H >= 1 && H <= PROP_MAX_H, who + "H must be in [1, 256]");
+  GPK_REQUIRE(h, D >= 1 && D <= PROP_MAX_D && nx >= 1 && nx <= PROP_MAX_NX && nx <= D, who + "needs 1 <= nx <= D <= 16");
+  GPK_REQUIRE(h, m.N >= 1 && gpk_padded(m.N) <= GPK_SMALL_MAX_NP && m.Np == gpk_padded(m.N) && m.ldw >= m.Np,
+              who + "needs N <= 16384, Np = gpk_padded(N) and ldw >= Np");
+  // the model's host arrays go into the kernels' parameter blocks as they are
+  GPK_REQUIRE(h, prop_finite(m.ls, (size_t)m.B * D) && prop_finite(m.sf2, m.B) && prop_finite(m.y_mean, (size_t)m.B * m.P) &&
+                     prop_finite(m.y_std, (size_t)m.B * m.P),
+              who + "ls, sf2, y_mean and y_std must not contain NaN or infinity");
+  for (int i = 0; i < m.B * D; ++i) GPK_REQUIRE(h, m.ls[i] > 0.0, who + "length-scales must be positive");
+  GPK_REQUIRE(h, z.x0 && z.lin && z.traj && z.Sigma, who + "null pointer");
+  GPK_REQUIRE(h, nu == 0 || z.U, who + "null controls");
+  GPK_REQUIRE(h, z.x0_rows == 1 || z.x0_rows == R, who + "x0 must have 1 or R rows");
+  GPK_REQUIRE(h, nu == 0 || z.u_rows == 1 || z.u_rows == R, who + "U must have 1 or R rows");
+  GPK_REQUIRE(h, !z.Sigma0 || z.s_rows == 1 || z.s_rows == R, who + "Sigma0 must have 1 or R rows");
+  const size_t n_x = (size_t)R * nx, n_s = n_x * nx, n_q = (size_t)R * D, n_lin = (size_t)nx * D, n_Q = (size_t)nx * nx;
+  const int u_rows = nu ? z.u_rows : 0;
+  const size_t n_u = (size_t)u_rows * H * nu;
+  GPK_REQUIRE(h, prop_finite(z.x0, (size_t)z.x0_rows * nx) && prop_finite(z.lin, n_lin) && (!n_u || prop_finite(z.U, n_u)) &&
+                     (!z.Sigma0 || prop_finite(z.Sigma0, (size_t)z.s_rows * n_Q)) && (!z.Q || prop_finite(z.Q, n_Q)),
+              who + "x0, U, lin, Sigma0 and Q must not contain NaN or infinity");
+  // the device block: [x | S | q | lin | Q | U] as they come from the host, the stage's results, the small-batch work area, the
+  // horizon's outputs from slot 1 on (slot 0 of traj and Sigma is the caller's own start)
+  const size_t n_up = n_x + n_s + n_q + n_lin + n_Q + n_u;
+  const size_t n_sm = (size_t)NO * R, n_sj = n_sm * D;
+  const size_t n_work = gpk_small_work_doubles(GPK_SMALL_JACVAR, m.Np, m.B, R, D, m.P, 1);
+  const size_t n_traj = (size_t)H * n_x, n_sig = (size_t)H * n_s, n_om = (size_t)H * n_sm, n_oj = (size_t)H * n_sj;
+  void* ws = nullptr;
+  GPK_TRY(gpk_scratch(h, (n_up + 2 * n_sm + n_sj + n_work + n_traj + n_sig + 2 * n_om + n_oj) * sizeof(double), &ws));
+  double* d_x = (double*)ws;
+  double* d_S = d_x + n_x;
+  double* d_q = d_S + n_s;
+  double* d_lin = d_q + n_q;
+  double* d_Q = d_lin + n_lin;
+  double* d_u = d_Q + n_Q;
+  double* s_mean = d_u + n_u;
+  double* s_var = s_mean + n_sm;
+  double* s_jac = s_var + n_sm;
+  double* work = s_jac + n_sj;
+  double* d_traj = work + n_work;
+  double* d_sig = d_traj + n_traj;
+  double* d_om = d_sig + n_sig;
+  double* d_ov = d_om + n_om;
+  double* d_oj = d_ov + n_om;
+  std::vector<double> host(n_up, 0.0);
+  double* hx = host.data();
+  double* hS = hx + n_x;
+  double* hq = hS + n_s;
+  for (int r = 0; r < R; ++r) {
+    const double* xr = z.x0 + (z.x0_rows == 1 ? 0 : (size_t)r * nx);
+    memcpy(hx + (size_t)r * nx, xr, sizeof(double) * nx);
+    if (z.Sigma0) {
+      // the lower triangle is the matrix: mirrored here as every later stage is
+      const double* s0 = z.Sigma0 + (z.s_rows == 1 ? 0 : (size_t)r * n_Q);
+      for (int i = 0; i < nx; ++i)
+        for (int j = 0; j <= i; ++j) hS[(size_t)r * n_Q + i * nx + j] = hS[(size_t)r * n_Q + j * nx + i] = s0[i * nx + j];
+    }
+    for (int d = 0; d < D; ++d) {
+      const double raw = d < nx ? xr[d] : z.U[(z.u_rows == 1 ? 0 : (size_t)r * H * nu) + (d - nx)];
+      hq[(size_t)r * D + d] = k.scaled ? (raw - k.in_shift[d]) / k.in_scale[d] : raw;
+    }
+  }
+  memcpy(hq + n_q, z.lin, sizeof(double) * n_lin);
+  if (z.Q) memcpy(hq + n_q + n_lin, z.Q, sizeof(double) * n_Q);
+  if (n_u) memcpy(hq + n_q + n_lin + n_Q, z.U, sizeof(double) * n_u);
+  memcpy(z.traj, hx, sizeof(double) * n_x);
+  memcpy(z.Sigma, hS, sizeof(double) * n_s);
+  GPK_CHECK_HIP(h, hipMemcpyAsync(d_x, host.data(), sizeof(double) * n_up, hipMemcpyHostToDevice, h->stream));
+  const ServeOut stage{s_mean, s_var, s_jac, nullptr, nullptr};
+  const long long u_row_stride = (nu && z.u_rows == R) ? (long long)H * nu : 0;
+  for (int s = 0; s < H; ++s) {
+    GPK_TRY(gpk_small_launch(h, GPK_SMALL_JACVAR, m, d_q, R, work, stage));
+    const bool last = s + 1 == H;
+    gpk_time_begin(h, GPK_TIMED_PROPAGATE);
+    hipLaunchKernelGGL(propagate_advance_kernel, dim3((unsigned)R), dim3(256), 0, h->stream, k, R, (const double*)s_mean,
+                       (const double*)s_var, (const double*)s_jac, (const double*)d_lin, z.Q ? (const double*)d_Q : nullptr,
+                       (const double*)(d_u + (size_t)s * nu), (const double*)(d_u + (size_t)(last ? s : s + 1) * nu), u_row_stride,
+                       d_x, d_S, last ? nullptr : d_q, d_traj + (size_t)s * n_x, d_sig + (size_t)s * n_s,
+                       z.mean ? d_om + (size_t)s * n_sm : nullptr, z.var ? d_ov + (size_t)s * n_sm : nullptr,
+                       z.jac ? d_oj + (size_t)s * n_sj : nullptr);
+    gpk_time_end(h);
+    GPK_LAUNCH_CHECK(h);
+  }
+  GPK_CHECK_HIP(h, hipMemcpyAsync(z.traj + n_x, d_traj, sizeof(double) * n_traj, hipMemcpyDeviceToHost, h->stream));
+  GPK_CHECK_HIP(h, hipMemcpyAsync(z.Sigma + n_s, d_sig, sizeof(double) * n_sig, hipMemcpyDeviceToHost, h->stream));
+  if (z.mean) GPK_CHECK_HIP(h, hipMemcpyAsync(z.mean, d_om, sizeof(double) * n_om, hipMemcpyDeviceToHost, h->stream));
+  if (z.var) GPK_CHECK_HIP(h, hipMemcpyAsync(z.var, d_ov, sizeof(double) * n_om, hipMemcpyDeviceToHost, h->stream));
+  if (z.jac) GPK_CHECK_HIP(h, hipMemcpyAsync(z.jac, d_oj, sizeof(double) * n_oj, hipMemcpyDeviceToHost, h->stream));
+  GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
+  return GPK_OK;
+}
+
+}  // namespace
+
+extern "C" int gpk_propagate_host(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
+                                  double sf2, const double* y_mean, const double* y_std, const double* W, int64_t Np, int64_t ldw,
+                                  double kss, double floor_, int var_includes_noise, double noise, const double* x0, int x0_rows,
+                                  const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows, const double* Q,
+                                  int R, int H, double* traj, double* Sigma, double* mean, double* var, double* jac) {
+  if (!h) return GPK_BAD_ARG;
+  const std::string who("propagate_host: ");
+  GPK_REQUIRE(h, X && alpha && ls && y_mean && y_std && W, who + "null pointer");
+  GPK_REQUIRE(h, P >= 1 && P <= GPK_MAX_P && P <= D, who + "the state dimension P must be in [1, 16] and must not exceed D");
+  GPK_REQUIRE(h, prop_finite(&noise, 1) && prop_finite(&kss, 1) && prop_finite(&floor_, 1), who + "kss, floor and noise must be finite");
+  PropK k{};
+  k.nx = P; k.D = D; k.NO = P;
+  k.so = 1; k.sm = P; k.vo = 0;
+  k.add_noise = var_includes_noise != 0;
+  for (int d = 0; d < 16; ++d) { k.in_shift[d] = 0.0; k.in_scale[d] = 1.0; k.model_of[d] = d < P ? d : -1; }
+  for (int p = 0; p < P; ++p) { k.ystd2[p] = y_std[p] * y_std[p]; k.noise[p] = noise; }
+  const ServeModels m{1, P, 1, &X, &alpha, N, D, ls, &sf2, y_mean, y_std, {&W, nullptr}, Np, ldw, &kss, floor_, nullptr};
+  const Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean, var, jac};
+  return propagate_run(h, who, m, k, z);
+}
+
+extern "C" int gpk_propagate_host_multi(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D,
+                                        const double* ls, const double* sf2, const double* y_mean, const double* y_std,
+                                        const double* const* W, int64_t Np, int64_t ldw, const double* kss, double floor_,
+                                        int var_includes_noise, const double* noise, int nx, const int* coord,
+                                        const double* in_shift, const double* in_scale, const double* x0, int x0_rows,
+                                        const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows,
+                                        const double* Q, int R, int H, double* traj, double* Sigma, double* mean, double* var,
+                                        double* jac) {
+  if (!h) return GPK_BAD_ARG;
+  const std::string who("propagate_host_multi: ");
+  GPK_REQUIRE(h, X && alpha && ls && sf2 && y_mean && y_std && W && kss && coord, who + "null pointer");
+  GPK_REQUIRE(h, B >= 1 && B <= GPK_SMALL_MAX_MODELS, who + "1..8 models");
+  GPK_REQUIRE(h, D >= 1 && D <= PROP_MAX_D && nx >= B && nx <= D, who + "the state dimension nx must be in [B, D], D <= 16");
+  GPK_REQUIRE(h, !var_includes_noise || noise, who + "null noise levels");
+  GPK_REQUIRE(h, (in_shift == nullptr) == (in_scale == nullptr), who + "in_shift and in_scale go together");
+  for (int b = 0; b < B; ++b) GPK_REQUIRE(h, X[b] && alpha[b] && W[b], who + "null model pointer");
+  PropK k{};
+  k.nx = nx; k.D = D; k.NO = B;
+  k.so = R; k.sm = 1; k.vo = R;
+  k.add_noise = var_includes_noise != 0;
+  for (int d = 0; d < 16; ++d) { k.in_shift[d] = 0.0; k.in_scale[d] = 1.0; k.model_of[d] = -1; }
+  for (int b = 0; b < B; ++b) {
+    GPK_REQUIRE(h, coord[b] >= 0 && coord[b] < nx, who + "coord must be in [0, nx)");
+    GPK_REQUIRE(h, k.model_of[coord[b]] < 0, who + "coord must be distinct");
+    k.model_of[coord[b]] = b;
+    k.ystd2[b] = y_std[b] * y_std[b];
+    k.noise[b] = var_includes_noise ? noise[b] : 0.0;
+  }
+  GPK_REQUIRE(h, prop_finite(kss, B) && prop_finite(k.noise, B) && prop_finite(&floor_, 1), who + "kss, floor and noise must be finite");
+  if (in_shift) {
+    GPK_REQUIRE(h, prop_finite(in_shift, D) && prop_finite(in_scale, D), who + "the input scaler must not contain NaN or infinity");
+    for (int d = 0; d < D; ++d) {
+      GPK_REQUIRE(h, in_scale[d] != 0.0, who + "in_scale must be non-zero");
+      k.in_shift[d] = in_shift[d];
+      k.in_scale[d] = in_scale[d];
+    }
+    k.scaled = 1;
+  }
+  const ServeModels m{B, 1, 1, X, alpha, N, D, ls, sf2, y_mean, y_std, {W, nullptr}, Np, ldw, kss, floor_, nullptr};
+  const Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean, var, jac};
+  return propagate_run(h, who, m, k, z);
+}

@@ -30,6 +30,11 @@
 //                            every model in ONE launch and all four results in three, each model
 //                            with its own shares and its own ticket counters.
 //
+//   a propagation stage (K11) mean + Jacobian + variance without the variance gradient: small_cross_mean_jac_kernel, then
+//                            small_var_jac_kernel - small_var_grad_kernel's body without its store of V - and no W^T V launch: two
+//                            launches with the bits of the three-launch call (gpk_propagate.hip chains them along a horizon, the
+//                            queries in a device buffer).
+//
 //   two factors (K9)         the sparse model's variance terms are kss - |Wuu k*|^2 + |WSigma k*|^2 on ONE K* with P outputs: the
 //                            first launch runs with one model, and small_var[_grad]_kernel, small_cov_kernel and small_wtv_grad_kernel
 //                            with the template parameter TWO - the same bodies - take the inverse FACTOR as the grid
@@ -386,7 +391,8 @@ __device__ __forceinline__ double small_v_sum(const double (&red)[VW][NMB][16][1
 // shares (model slot o); each has its own shares (and rows of V, slot 2 o + f); ONE ticket count per model runs over the
 // workgroups of both, and the model's last one adds each factor's shares in the order above and writes
 // var[m][p] = max((kss - t0) - (0 - t1), floor) y_std[p]^2.
-template <int NMB, bool GRAD, bool TWO>
+// GRAD = 2 (small_var_jac_kernel, the propagation chain's stage): the Jacobian is finished as with GRAD = 1, V is not stored.
+template <int NMB, int GRAD, bool TWO>
 __device__ __forceinline__ void small_var_body(SmallK k, long long ldw, long long Np, const double* Ks,
                                                             int M, int P, double floor_, const double* pmean,
                                                             unsigned mean_shares, double* pvar, unsigned* counter,
@@ -406,8 +412,8 @@ __device__ __forceinline__ void small_var_body(SmallK k, long long ldw, long lon
   mean_out += (long long)o * M * P;
   var_out += (long long)o * M * (TWO ? P : 1);
   counter += o;
-  if constexpr (GRAD) {
-    Vs += (long long)b * Np * SQ;
+  if constexpr (GRAD == 1) Vs += (long long)b * Np * SQ;
+  if constexpr (GRAD != 0) {
     pjac += (long long)o * mean_shares * (M * P * D);
     dmean_out += (long long)o * M * P * D;
   }
@@ -418,7 +424,7 @@ __device__ __forceinline__ void small_var_body(SmallK k, long long ldw, long lon
     const int mb = e >> 8, r = (e >> 4) & 15, c = e & 15;
     const double v = small_v_sum<NMB>(red, mb, r, c);
     sq[mb][r][c] = v * v;
-    if constexpr (GRAD) Vs[(r0 + r) * SQ + 16 * mb + c] = v;
+    if constexpr (GRAD == 1) Vs[(r0 + r) * SQ + 16 * mb + c] = v;
   }
   __syncthreads();
   if (tid < NMB * 16) {
@@ -432,7 +438,7 @@ __device__ __forceinline__ void small_var_body(SmallK k, long long ldw, long lon
   // the others are still multiplying, off the critical path (scratch: the reduction buffer, free by now).
   static_assert(VW * 16 * 17 >= 4 * SQ * SP, "the reduction buffer doubles as the mean scratch");
   if (blockIdx.x == 0 && lead) finish_means(pmean, mean_shares, M, P, k.ymean + o * P, k.ystd + o * P, mean_out, tid, &red[0][0][0][0]);
-  if constexpr (GRAD) {
+  if constexpr (GRAD != 0) {
     if (blockIdx.x == 1 && lead) finish_jac(pjac, mean_shares, M, P, D, k.ystd + o * P, k.ls[o], dmean_out, tid, 64 * VW);
   }
   if (last_of(counter, (TWO ? 2u : 1u) * gridDim.x, tid)) {
@@ -476,8 +482,8 @@ __global__ __launch_bounds__(64 * VW) void small_var_kernel(SmallK k, long long 
                                                             int M, int P, double floor_, const double* pmean,
                                                             unsigned mean_shares, double* pvar, unsigned* counter,
                                                             double* mean_out, double* var_out) {
-  small_var_body<NMB, false, TWO>(k, ldw, Np, Ks, M, P, floor_, pmean, mean_shares, pvar, counter, mean_out, var_out, nullptr, nullptr, 0,
-                                  nullptr);
+  small_var_body<NMB, 0, TWO>(k, ldw, Np, Ks, M, P, floor_, pmean, mean_shares, pvar, counter, mean_out, var_out, nullptr, nullptr, 0,
+                              nullptr);
 }
 template <int NMB, bool TWO>
 __global__ __launch_bounds__(64 * VW) void small_var_grad_kernel(SmallK k, long long ldw, long long Np, const double* Ks,
@@ -485,8 +491,18 @@ __global__ __launch_bounds__(64 * VW) void small_var_grad_kernel(SmallK k, long 
                                                                  unsigned mean_shares, double* pvar, unsigned* counter,
                                                                  double* mean_out, double* var_out, double* Vs,
                                                                  const double* pjac, int D, double* dmean_out) {
-  small_var_body<NMB, true, TWO>(k, ldw, Np, Ks, M, P, floor_, pmean, mean_shares, pvar, counter, mean_out, var_out, Vs, pjac, D,
-                                 dmean_out);
+  small_var_body<NMB, 1, TWO>(k, ldw, Np, Ks, M, P, floor_, pmean, mean_shares, pvar, counter, mean_out, var_out, Vs, pjac, D,
+                              dmean_out);
+}
+
+// mean + Jacobian + variance without the variance gradient (GPK_SMALL_JACVAR): small_var_grad_kernel without its store of V
+template <int NMB>
+__global__ __launch_bounds__(64 * VW) void small_var_jac_kernel(SmallK k, long long ldw, long long Np, const double* Ks, int M, int P,
+                                                                double floor_, const double* pmean, unsigned mean_shares,
+                                                                double* pvar, unsigned* counter, double* mean_out, double* var_out,
+                                                                const double* pjac, int D, double* dmean_out) {
+  small_var_body<NMB, 2, false>(k, ldw, Np, Ks, M, P, floor_, pmean, mean_shares, pvar, counter, mean_out, var_out, nullptr, pjac, D,
+                                dmean_out);
 }
 
 constexpr int CG = 16;                   // workgroups per first-level group of the covariance reduction
@@ -750,7 +766,7 @@ struct SmallWork {
   size_t Ks;             // B x SQ x Np
   size_t pmean;          // B x ga x (SQ * SP)
   size_t pvar;           // BF x gb x SQ                            (predict, grad)
-  size_t pjac;           // B x ga x (M * P * D)                    (grad)
+  size_t pjac;           // B x ga x (M * P * D)                    (grad, jacvar)
   size_t Vs;             // BF x Np x SQ                            (grad)
   size_t pdv;            // BF x (gb x row chunks) x (M * D)        (grad)
   size_t pcov, gcov;     // BF x gb x CE, BF x (gb / CG rounded up) x CE   (cov)
@@ -773,6 +789,8 @@ SmallWork small_work(int call, int64_t Np, int B, int64_t M, int D, int P, int F
     w.pjac = take((size_t)B * ga * (size_t)(M * P * D));
     w.Vs = take(BF * Np * SQ);
     w.pdv = take(BF * gb * WTV_MAX_ROW_CHUNKS * (size_t)(M * D));
+  } else if (call == GPK_SMALL_JACVAR) {
+    w.pjac = take((size_t)B * ga * (size_t)(M * P * D));
   }
   w.total = at;
   return w;
@@ -849,23 +867,25 @@ bool gpk_small_ok(int64_t Np, int D, int P, int64_t M) {
 }
 
 int gpk_small_launch(gpk_handle h, int call, const ServeModels& m, const double* Xq, int64_t M, double* work, const ServeOut& out) {
-  const bool grad = call == GPK_SMALL_GRAD, cov = call == GPK_SMALL_COV;
+  // jv: the first launch of a gradient call, then the variance launch that also finishes the Jacobian - no W^T V launch
+  const bool jv = call == GPK_SMALL_JACVAR, grad = call == GPK_SMALL_GRAD || jv, cov = call == GPK_SMALL_COV;
   GPK_REQUIRE(h, call == GPK_SMALL_PREDICT || grad || cov, "small-batch launch: unknown call");
-  const std::string name(cov ? "small cov" : grad ? "small grad" : "small predict");
+  const std::string name(cov ? "small cov" : jv ? "small jacvar" : grad ? "small grad" : "small predict");
   const int B = m.B, D = m.D, P = m.P, F = m.F;
   const long long N = m.N, Np = gpk_padded(m.N), ldw = m.ldw;
   GPK_REQUIRE(h, B >= 1 && B <= GPK_SMALL_MAX_MODELS && (B == 1 || P == 1) && (F == 1 || F == 2),
               name + ": 1 model, or up to 8 single-output models, of one or two inverse factors");
   GPK_REQUIRE(h, gpk_small_ok(Np, D, P, M), name + ": shape outside the small-batch path");
   GPK_REQUIRE(h, m.X && m.alpha && m.ls && m.sf2 && m.y_mean && m.y_std && Xq && work && out.mean, name + ": null pointer");
-  GPK_REQUIRE(h, !grad || (out.dmean && (out.var == nullptr) == (out.dvar == nullptr)), name + ": null pointer");
+  GPK_REQUIRE(h, !grad || jv || (out.dmean && (out.var == nullptr) == (out.dvar == nullptr)), name + ": null pointer");
+  GPK_REQUIRE(h, !jv || (out.dmean && out.var && !out.dvar && F == 1), name + ": mean, variance and Jacobian of one-factor models");
   GPK_REQUIRE(h, !cov || (out.cov && m.noise), name + ": null pointer");
   // the inverse factors enter with the variance (and its gradient) and with the covariance: the second and third launches
   const bool factors = cov || out.var;
   GPK_REQUIRE(h, !factors || (m.W[0] && (F == 1 || m.W[1]) && m.Np == Np && ldw >= Np && ldw % 2 == 0),
               name + ": needs the inverse factor of every model (both of the two-factor form), padded, with an even ldw >= Np");
   GPK_REQUIRE(h, cov || !factors || m.kss, name + ": null pointer");
-  if (cov || (grad && factors)) GPK_TRY(ensure_cov_counters(h));
+  if (cov || (grad && !jv && factors)) GPK_TRY(ensure_cov_counters(h));
   SmallK k{};
   GPK_TRY(small_params(h, name, m, factors, cov, k));
   const unsigned ga = (unsigned)(Np / SJ), gb = (unsigned)(Np / SR);
@@ -886,6 +906,9 @@ int gpk_small_launch(gpk_handle h, int call, const ServeModels& m, const double*
   if (cov) {
     hipLaunchKernelGGL(cov_kernel(M, F), g2, b2, 0, h->stream, k, ldw, Np, Ks, (int)M, D, P, Xq, pmean, ga, work + wk.pcov,
                        work + wk.gcov, h->d_cov_count, out.mean, out.cov);
+  } else if (jv) {
+    hipLaunchKernelGGL(M <= 16 ? small_var_jac_kernel<1> : small_var_jac_kernel<2>, g2, b2, 0, h->stream, k, ldw, Np, Ks, (int)M, P,
+                       m.floor_, pmean, ga, work + wk.pvar, vcount, out.mean, out.var, pjac, D, out.dmean);
   } else if (!grad) {
     hipLaunchKernelGGL(var_kernel(M, F), g2, b2, 0, h->stream, k, ldw, Np, Ks, (int)M, P, m.floor_, pmean, ga, work + wk.pvar, vcount,
                        out.mean, out.var);

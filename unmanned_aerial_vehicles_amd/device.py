@@ -53,6 +53,7 @@ class Backend:
             raise GPKError(rc, "gpk_create failed")
         self.h = h
         self.lock = threading.RLock()
+        self.options = {}      # what set_options was given (the Python routes that mirror a library option read it here)
         if os.environ.get("GPK_DEBUG_FILL"):      # debugging aid (the test suite sets it): poison the handle's scratch too
             self.check(self.lib.gpk_set_option(self.h, b"debug_fill", 1))
         self.bind_stream()
@@ -111,6 +112,7 @@ class Backend:
                 self.check(self.lib.gpk_set_option_str(self.h, k.encode(), v.encode()))
             else:
                 self.check(self.lib.gpk_set_option(self.h, k.encode(), int(v)))
+            self.options[k] = v
         return self
 
     def empty(self, shape, dtype):
@@ -887,6 +889,30 @@ class DeviceGP:
         self._host_call("gpk_predict_host_grad", y_mean, y_std, want, float(kss) if want else 0.0, float(floor), _hp(Xq),
                         M, _hp(mean), _hp(var), _hp(dmean), _hp(dvar))
         return mean, var, dmean, dvar
+
+    def propagate_ok(self):
+        """The one-call horizon propagation (gpk_propagate_host) applies: the small-batch path's sizes, not switched off."""
+        return self.factored and self.D <= 16 and self.Np <= 16384 and int(self.be.options.get("small_path", 1)) != 0
+
+    def propagate_host(self, y_mean, y_std, kss, floor, add_noise, noise, x0, U, lin, S0, Q, R, H, stages):
+        """One C call per horizon (gpk_propagate_host; arguments as `propagate.check_horizon` returns them): traj (H + 1, R, P),
+        Sigma (H + 1, R, P, P) and, with `stages`, the stage quantities mean, var (H, R, P) and jac (H, R, P, D) in target
+        units - three launches per stage, one synchronisation.  ValueError, with the library's message, where the entry refuses
+        its arguments."""
+        assert self.factored
+        self._refuse_replica()
+        P, D = self.P, self.D
+        traj, Sigma = np.empty((H + 1, R, P)), np.empty((H + 1, R, P, P))
+        mean, var, jac = (np.empty((H, R, P)), np.empty((H, R, P)), np.empty((H, R, P, D))) if stages else (None, None, None)
+        try:
+            self._host_call("gpk_propagate_host", y_mean, y_std, True, float(kss), float(floor), int(bool(add_noise)),
+                            float(noise), _hp(x0), x0.shape[0], _hp(U) if D > P else None, U.shape[0], _hp(lin), _hp(S0),
+                            1 if S0 is None else S0.shape[0], _hp(Q), R, H, _hp(traj), _hp(Sigma), _hp(mean), _hp(var), _hp(jac))
+        except GPKError as e:      # a limit of the entry: the caller's arguments, with the library's message
+            if e.code == _lib.GPK_BAD_ARG:
+                raise ValueError(str(e)) from None
+            raise
+        return traj, Sigma, mean, var, jac
 
     # ---- gated serving: the one place every fp32 surface (estimator, sharded predictor, package GP, per-axis models) goes
     # through -------------------------------------------------------------------------------------------------------------

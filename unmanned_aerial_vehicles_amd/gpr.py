@@ -419,6 +419,48 @@ class GaussianProcessRegressor:
             y_var, dvar = y_var[:, 0], dvar[:, 0]
         return mean, dmean, y_var, dvar
 
+    def propagate(self, x0, U, lin, Sigma0=None, process_noise=None, var_includes_noise=False, return_stages=False,
+                  route="auto"):
+        """The posterior's own closed-loop horizon: the mean trajectory under the learned dynamics and the state covariance that
+        the model's uncertainty induces along it, to first order (`propagate`'s module docstring has the recursion).  The state
+        is the model's P outputs; a query is q = [x, u] (D = P + nu).  x0 (P,) or (R, P), U (H, nu) or (R, H, nu), lin (P, D) the
+        nominal increment; Sigma0 (P, P) or (R, P, P), symmetric (default zero); process_noise (P, P), symmetric, added at
+        every stage.  var_includes_noise: the stage variances include the WhiteKernel level, as `predict(return_std=True)`'s
+        do (default: the latent function's variance).  Returns (traj (H + 1, R, P), Sigma (H + 1, R, P, P)) - R = 1 keeps its
+        axis - and with return_stages=True also {"mean" (H, R, P), "var" (H, R, P), "jac" (H, R, P, D)}, the stage quantities as
+        used: with var_includes_noise=True they have the bits of `predict_jacobian(q, return_var=True)` at the returned rows.
+        One C call per horizon (three launches per stage, one synchronisation) up to 16 384 training rows; beyond that, or with
+        the backend option small_path=0, or with route="host", the same recursion as a host loop over `predict_jacobian`.
+        A fitted model only (RuntimeError); ValueError for a wrong shape, R > 32, H outside 1 .. 256, non-finite input."""
+        from . import propagate as _pg
+        if not hasattr(self, "X_train_"):
+            raise RuntimeError("This GaussianProcessRegressor instance is not fitted yet.")
+        P, D = self._yn.shape[1], self.n_features_in_
+        x0, U, lin, S0, Q, R, H = _pg.check_horizon(x0, U, lin, P, D, Sigma0, process_noise)
+        self._ensure_device()
+        dev = self._dev
+        comp = self.kernel_.components()
+        noise = comp.noise or 0.0
+        if route not in ("auto", "host"):
+            raise ValueError("route must be 'auto' or 'host'")
+        if route == "auto" and dev.propagate_ok():
+            # (the noise enters through the prior variance the clip starts from, as in predict_jacobian: the same bits)
+            traj, Sigma, mean, var, jac = dev.propagate_host(self._y_train_mean, self._y_train_std,
+                                                             comp.sf2 + (noise if var_includes_noise else 0.0), 0.0, False, 0.0,
+                                                             x0, U, lin, S0, Q, R, H, return_stages)
+            return (traj, Sigma, {"mean": mean, "var": var, "jac": jac}) if return_stages else (traj, Sigma)
+        std2 = self._y_train_std ** 2
+
+        def stage(q):
+            mean, dmean, var, _ = self.predict_jacobian(q, return_var=True)
+            var = var.reshape(R, P)
+            if not var_includes_noise:      # predict's variance carries the noise level: the latent variance, clipped again
+                var = np.maximum(var - noise * std2[None, :], 0.0)
+            return mean.reshape(R, P), dmean.reshape(R, P, D), var
+
+        traj, Sigma, stages = _pg.host_loop(stage, list(range(P)), x0, U, lin, S0, Q, R, H)
+        return (traj, Sigma, stages) if return_stages else (traj, Sigma)
+
     def sample_y(self, X, n_samples=1, random_state=0):
         """`sklearn/gaussian_process/_gpr.py:498-535`: draws from the joint posterior (or the prior, unfitted) at X - the
         mean and covariance from `predict(X, return_cov=True)` (GPU), the draw by NumPy's `multivariate_normal` (an SVD of

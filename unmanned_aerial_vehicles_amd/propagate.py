@@ -1,0 +1,203 @@
+"""Horizon propagation: the posterior's mean rollout with the linearised state covariance (K11).
+
+For a state x in R^nx, a query q = [x, u] in R^D and the nominal increment `lin` (nx x D, as `paths.nominal_rollouts` builds it):
+
+    x_{h+1}     = x_h + lin q + sum_b e_coord[b] mu_b(q)
+    A_h         = I + lin[:, :nx] + sum_b e_coord[b] J_b[:nx]               J_b = d mu_b / d q
+    Sigma_{h+1} = A_h Sigma_h A_h^T + sum_b v_b(q) e_coord[b] e_coord[b]^T + Q
+
+- the first-order propagation of Hewing, Kabzan and Zeilinger (Cautious MPC using GP regression).  The estimators run it as one
+C call per horizon (`gpk_propagate_host`, `gpk_propagate_host_multi`: three launches per stage, one synchronisation); what is
+here is what they share on the host: the argument checks (before any device call), the same recursion as a host loop over a
+model's `predict_jacobian(..., return_var=True)` - the route of the sparse models, of exact models beyond the small-batch
+path and of option small_path=0 - and what the control-loop wrappers (`propagate_horizon`) share, their nominal fallback included.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+MAX_R, MAX_H, MAX_NX = 32, 256, 16
+
+
+def check_horizon(x0, U, lin, nx, D, Sigma0=None, process_noise=None):
+    """The horizon's arguments as contiguous float64 arrays: (x0 (R or 1, nx), U (R or 1, H, nu), lin (nx, D), Sigma0 (R or 1, nx,
+    nx) or None, Q (nx, nx) or None, R, H).  x0 is (nx,) or (R, nx), U (H, nu) or (R, H, nu), Sigma0 (nx, nx) or (R, nx, nx); R is
+    inferred from them.  ValueError on a wrong shape, R > 32, H outside 1 .. 256, NaN or infinity, an asymmetric Sigma0 or
+    process noise."""
+    nx, D = int(nx), int(D)
+    nu = D - nx
+    if not (1 <= nx <= MAX_NX and nx <= D <= 16):
+        raise ValueError(f"propagate: needs 1 <= nx <= D <= 16, got nx = {nx}, D = {D}")
+    x0 = np.array(x0, dtype=np.float64, ndmin=2)
+    if x0.ndim != 2 or x0.shape[1] != nx:
+        raise ValueError(f"propagate: x0 must be ({nx},) or (R, {nx})")
+    U = np.asarray(U, dtype=np.float64)
+    if U.ndim == 2:
+        U = U[None]
+    if U.ndim != 3 or U.shape[2] != nu:
+        raise ValueError(f"propagate: U must be (H, {nu}) or (R, H, {nu})")
+    H = U.shape[1]
+    if not (1 <= H <= MAX_H):
+        raise ValueError(f"propagate: H must be in [1, {MAX_H}], got {H}")
+    lin = np.asarray(lin, dtype=np.float64)
+    if lin.shape != (nx, D):
+        raise ValueError(f"propagate: lin must be ({nx}, {D})")
+    S0 = None
+    if Sigma0 is not None:
+        S0 = np.asarray(Sigma0, dtype=np.float64)
+        if S0.ndim == 2:
+            S0 = S0[None]
+        if S0.ndim != 3 or S0.shape[1:] != (nx, nx):
+            raise ValueError(f"propagate: Sigma0 must be ({nx}, {nx}) or (R, {nx}, {nx})")
+    Q = None
+    if process_noise is not None:
+        Q = np.asarray(process_noise, dtype=np.float64)
+        if Q.shape != (nx, nx):
+            raise ValueError(f"propagate: process_noise must be ({nx}, {nx})")
+    rows = {a.shape[0] for a in (x0, U, S0) if a is not None and a.shape[0] != 1}
+    if len(rows) > 1:
+        raise ValueError(f"propagate: x0, U and Sigma0 disagree on the number of rollouts: {sorted(rows)}")
+    R = rows.pop() if rows else 1
+    if not (1 <= R <= MAX_R):
+        raise ValueError(f"propagate: R must be in [1, {MAX_R}], got {R}")
+    for name, a in (("x0", x0), ("U", U), ("lin", lin), ("Sigma0", S0), ("process_noise", Q)):
+        if a is not None and not np.isfinite(a).all():
+            raise ValueError(f"propagate: {name} contains NaN or infinity")
+    if S0 is not None and not np.array_equal(S0, S0.transpose(0, 2, 1)):
+        raise ValueError("propagate: Sigma0 must be symmetric")
+    if Q is not None and not np.array_equal(Q, Q.T):
+        raise ValueError("propagate: process_noise must be symmetric")
+    c = np.ascontiguousarray
+    return c(x0), c(U), c(lin), (None if S0 is None else c(S0)), (None if Q is None else c(Q)), R, H
+
+
+def check_coord(coord, B, nx):
+    """`coord` (default 0 .. B - 1) as a list of B distinct state coordinates in [0, nx)."""
+    coord = list(range(B)) if coord is None else [int(c) for c in coord]
+    if len(coord) != B or len(set(coord)) != B or not all(0 <= c < nx for c in coord):
+        raise ValueError(f"propagate: coord must name {B} distinct state coordinates in [0, {nx})")
+    return coord
+
+
+def host_loop(stage, coord, x0, U, lin, S0, Q, R, H):
+    """The recursion on the host.  stage(q (R, D) raw) -> (mean (R, NO), jac (R, NO, D) per unit of the raw query, var (R, NO));
+    output o drives state coordinate coord[o].  Returns traj (H + 1, R, nx), Sigma (H + 1, R, nx, nx) and the stage quantities
+    {"mean" (H, R, NO), "var" (H, R, NO), "jac" (H, R, NO, D)}."""
+    nx, D = lin.shape
+    NO = len(coord)
+    traj, Sigma = np.zeros((H + 1, R, nx)), np.zeros((H + 1, R, nx, nx))
+    means, vars_, jacs = np.zeros((H, R, NO)), np.zeros((H, R, NO)), np.zeros((H, R, NO, D))
+    traj[0] = np.broadcast_to(x0, (R, nx))
+    if S0 is not None:
+        Sigma[0] = np.broadcast_to(S0, (R, nx, nx))
+    eye_lin = np.eye(nx) + lin[:, :nx]
+    for h in range(H):
+        q = np.concatenate([traj[h], np.broadcast_to(U[:, h], (R, D - nx))], axis=1)
+        mean, jac, var = stage(np.ascontiguousarray(q))
+        means[h], vars_[h], jacs[h] = mean, var, jac
+        x = traj[h] + q @ lin.T
+        A = np.broadcast_to(eye_lin, (R, nx, nx)).copy()
+        S = np.zeros((R, nx, nx))
+        for o, c in enumerate(coord):
+            x[:, c] += mean[:, o]
+            A[:, c, :] += jac[:, o, :nx]
+            S[:, c, c] = var[:, o]
+        S += A @ Sigma[h] @ A.transpose(0, 2, 1)
+        if Q is not None:
+            S += Q
+        traj[h + 1], Sigma[h + 1] = x, 0.5 * (S + S.transpose(0, 2, 1))
+    return traj, Sigma, {"mean": means, "var": vars_, "jac": jacs}
+
+
+# ---- what the batches (BatchedARDGP, BatchedSparseGP) share: raw units around single-output models --------------------------------
+def check_batch(B, D, x0, U, lin, coord, in_scaler, out_scaler, Sigma0, process_noise, route):
+    """The arguments of a batch's `propagate`: `check_horizon`'s results, then coord (list), in_shift, in_scale ((D,) or None),
+    o_mean, o_scale ((B,): the identity without an out_scaler)."""
+    lin = np.asarray(lin, dtype=np.float64)
+    nx = lin.shape[0] if lin.ndim == 2 else 0
+    if not (B <= nx <= D):
+        raise ValueError(f"propagate needs a state of {B} <= nx <= {D} coordinates (got {nx})")
+    if route not in ("auto", "host"):
+        raise ValueError("route must be 'auto' or 'host'")
+    head = check_horizon(x0, U, lin, nx, D, Sigma0, process_noise)
+    coord = check_coord(coord, B, nx)
+    in_shift = in_scale = None
+    if in_scaler is not None:
+        pair = (in_scaler.mean_, in_scaler.scale_) if hasattr(in_scaler, "mean_") else in_scaler
+        in_shift = np.ascontiguousarray(np.broadcast_to(np.asarray(pair[0], dtype=np.float64), (D,)))
+        in_scale = np.ascontiguousarray(np.broadcast_to(np.asarray(pair[1], dtype=np.float64), (D,)))
+        if not (np.isfinite(in_shift).all() and np.isfinite(in_scale).all()):
+            raise ValueError("the input scaler contains NaN or infinity.")
+        if not in_scale.all():
+            raise ValueError("in_scale must be non-zero")
+    o_mean, o_scale = np.zeros(B), np.ones(B)
+    if out_scaler is not None:
+        o_mean = np.broadcast_to(np.asarray(out_scaler[0], dtype=np.float64), (B,))
+        o_scale = np.broadcast_to(np.asarray(out_scaler[1], dtype=np.float64), (B,))
+        if not (np.isfinite(o_mean).all() and np.isfinite(o_scale).all()):
+            raise ValueError("the output scaler contains NaN or infinity.")
+    return head + (coord, in_shift, in_scale, o_mean, o_scale)
+
+
+def batch_stage(predict_jacobian, level, in_shift, in_scale, o_mean, o_scale, var_includes_noise):
+    """The `host_loop` stage of a batch: predict_jacobian(z, return_var=True) -> (mean (R, B), dmean (R, B, D), var (R, B), _) on
+    the scaled rows; level (B,): the noise level's share of every model's variance, which the served variances carry."""
+    def stage(q):
+        z = q if in_shift is None else (q - in_shift) / in_scale
+        mean, dmean, var, _ = predict_jacobian(z, return_var=True)
+        if not var_includes_noise:      # the latent variance, clipped again
+            var = np.maximum(var - level[None, :], 0.0)
+        if in_scale is not None:
+            dmean = dmean / in_scale[None, None, :]
+        return o_mean + o_scale * mean, o_scale[None, :, None] * dmean, o_scale ** 2 * var
+
+    return stage
+
+
+def noise_levels(models):
+    """noise level times y_std^2 of single-output models: what `var_includes_noise=False` takes off the served variances"""
+    return np.array([(m.kernel_.components().noise or 0.0) * float(np.ravel(m._y_train_std)[0]) ** 2 for m in models])
+
+
+# ---- the control-loop wrappers (SimpleQuadrotorGP / PreTrainedGP .propagate_horizon): 6 states, 4 controls ------------------------
+def horizon_inputs(dynamics, state, U_guess, dt):
+    """state (6,), U_guess (4+, N) or (R, 4+, N) -> (state, U (R, N, 4), lin (6, 10), nominal trajectory (N + 1, R, 6), single):
+    `lin` and the nominal trajectory of `dynamics` as `paths.nominal_rollouts` gives them."""
+    from .paths import nominal_rollouts
+    state = np.asarray(state, dtype=float).reshape(-1)[:6]
+    U_guess = np.asarray(U_guess, dtype=float)
+    single = U_guess.ndim == 2
+    Ug = U_guess[None] if single else U_guess
+    noms = [nominal_rollouts(dynamics, state, Ug[r], dt, 1) for r in range(Ug.shape[0])]
+    nominal = np.stack([n[0][0] for n in noms], axis=0).transpose(2, 0, 1)
+    return state, np.ascontiguousarray(Ug[:, :4, :].transpose(0, 2, 1)), noms[0][1], nominal, single
+
+
+def horizon_layout(traj, Sigma, single):
+    """traj (N + 1, R, 6), Sigma (N + 1, R, 6, 6) -> the trainers' layout X (R, 6, N + 1), Sigma (R, N + 1, 6, 6); `single`
+    drops R."""
+    X, S = np.ascontiguousarray(traj.transpose(1, 2, 0)), np.ascontiguousarray(Sigma.transpose(1, 0, 2, 3))
+    return (X[0], S[0]) if single else (X, S)
+
+
+def nominal_horizon(nominal, lin, Sigma0, process_noise):
+    """The fallback of the wrappers: the nominal trajectory with Sigma_{k+1} = (I + lin_x) Sigma_k (I + lin_x)^T + Q; arguments
+    that cannot be read as (6, 6) count as zero (it must not raise)."""
+    H, R, nx = nominal.shape[0] - 1, nominal.shape[1], nominal.shape[2]
+
+    def mat(a):
+        try:
+            a = np.zeros((nx, nx)) if a is None else np.asarray(a, dtype=float)
+            return a if a.shape[-2:] == (nx, nx) and a.ndim in (2, 3) and np.isfinite(a).all() else np.zeros((nx, nx))
+        except Exception:  # noqa: BLE001
+            return np.zeros((nx, nx))
+
+    S0, Q = mat(Sigma0), mat(process_noise)
+    if Q.ndim != 2:
+        Q = np.zeros((nx, nx))
+    A = np.eye(nx) + lin[:, :nx]
+    Sigma = np.empty((H + 1, R, nx, nx))
+    Sigma[0] = S0
+    for k in range(H):
+        Sigma[k + 1] = A @ Sigma[k] @ A.T + Q
+    return nominal, Sigma

@@ -281,6 +281,33 @@ class SimpleQuadrotorGP:
             print(f"GP rollout sampling failed: {e}")
             return fallback
 
+    def propagate_horizon(self, state, U_guess, dt, Sigma0=None, process_noise=None):
+        """The closed loop of the posterior MEAN with the state covariance the model's uncertainty induces along it, to first
+        order, in one call for the horizon (`GaussianProcessRegressor.propagate`):
+
+            x_{k+1} = x_k + dt [v_k, a_k] + mu([x_k, u_k]),   Sigma_{k+1} = A_k Sigma_k A_k^T + diag(var([x_k, u_k])) + Q
+
+        with A_k = I + lin[:, :6] + d mu / d x - the covariances that tighten a cautious MPC's constraints.  state (6,);
+        U_guess (4, N) -> X (6, N + 1), Sigma (N + 1, 6, 6); U_guess (R, 4, N) -> (R, 6, N + 1), (R, N + 1, 6, 6).  Sigma0
+        (6, 6) (default zero) and process_noise (6, 6), symmetric.  The variances are the latent function's.  Untrained, or on
+        any failure (printed): the nominal trajectory and the nominal propagation Sigma_{k+1} = (I + lin_x) Sigma_k (I +
+        lin_x)^T + Q - it never raises into the control loop."""
+        from . import propagate as _pg
+        state, U, lin, nominal, single = _pg.horizon_inputs(self._nominal_dynamics, state, U_guess, dt)
+        R, N = U.shape[0], U.shape[1]
+        if not self.is_trained:
+            print("GP horizon propagation: the model is not trained - nominal trajectory and covariance")
+            return _pg.horizon_layout(*_pg.nominal_horizon(nominal, lin, Sigma0, process_noise), single)
+        try:
+            traj, Sigma = self.gp_model.propagate(state, U, lin, Sigma0=Sigma0, process_noise=process_noise)
+            if not (np.isfinite(traj).all() and np.isfinite(Sigma).all()):
+                raise FloatingPointError("non-finite trajectory or covariance")
+            self.prediction_count += R * N
+            return _pg.horizon_layout(traj, Sigma, single)
+        except Exception as e:  # noqa: BLE001
+            print(f"GP horizon propagation failed: {e}")
+            return _pg.horizon_layout(*_pg.nominal_horizon(nominal, lin, Sigma0, process_noise), single)
+
     def get_uncertainty(self, state, control):
         _, variance = self.predict_residual(state, control)
         return np.mean(np.sqrt(variance))

@@ -469,6 +469,30 @@ class SparseGP:
                      for t in range(y_mean.shape[1])]
         return np.hstack(y_samples)
 
+    def propagate(self, x0, U, lin, Sigma0=None, process_noise=None, var_includes_noise=False, return_stages=False,
+                  route="auto"):
+        """`GaussianProcessRegressor.propagate` on the sparse posterior: the mean rollout with the linearised state covariance,
+        same arguments and results.  The sparse model has no one-call device chain for it: whatever `route` says ("auto" or
+        "host"), the recursion runs as a host loop over `predict_jacobian(..., return_var=True)`, one call and one
+        synchronisation per stage."""
+        from . import propagate as _pg
+        if route not in ("auto", "host"):
+            raise ValueError("route must be 'auto' or 'host'")
+        P, D = self.n_outputs_, self.n_features_in_
+        x0, U, lin, S0, Q, R, H = _pg.check_horizon(x0, U, lin, P, D, Sigma0, process_noise)
+        noise = self.kernel_.components().noise or 0.0
+        std2 = np.broadcast_to(np.asarray(self._y_train_std, dtype=np.float64).reshape(-1), (P,)) ** 2
+
+        def stage(q):
+            mean, dmean, var, _ = self.predict_jacobian(q, return_var=True)
+            var = var.reshape(R, P)
+            if not var_includes_noise:      # predict's variance carries the noise level: the latent variance, clipped again
+                var = np.maximum(var - noise * std2[None, :], 0.0)
+            return mean.reshape(R, P), dmean.reshape(R, P, D), var
+
+        traj, Sigma, stages = _pg.host_loop(stage, list(range(P)), x0, U, lin, S0, Q, R, H)
+        return (traj, Sigma, stages) if return_stages else (traj, Sigma)
+
     def sample_paths(self, n_paths, n_features=1024, random_state=0):
         """`n_paths` posterior function draws as explicit functions, conditioned on the inducing variables
         (`paths.SparsePosteriorPaths`; `GaussianProcessRegressor.sample_paths` for the sparse model): evaluated anywhere, call

@@ -139,6 +139,21 @@ class BatchedSparseGP:
                         _ptr(dvar), 1)
         return (mean, dmean, var, dvar) if return_var else (mean, dmean)
 
+    def propagate(self, x0, U, lin, coord=None, in_scaler=None, Sigma0=None, process_noise=None, var_includes_noise=False,
+                  return_stages=False, out_scaler=None, route="auto"):
+        """`BatchedARDGP.propagate` on the sparse posteriors: the batch's mean rollout with the linearised state covariance in
+        raw units, same arguments and results.  The sparse models have no one-call device chain for it: whatever `route` says
+        ("auto" or "host"), the recursion runs as a host loop over `predict_jacobian(..., return_var=True)` - one C call for
+        all models and one synchronisation per stage."""
+        from . import propagate as _pg
+        B, D = len(self.models), self.n_features_in_
+        x0, U, lin, S0, Q, R, H, coord, in_shift, in_scale, o_mean, o_scale = _pg.check_batch(
+            B, D, x0, U, lin, coord, in_scaler, out_scaler, Sigma0, process_noise, route)
+        stage = _pg.batch_stage(self.predict_jacobian, _pg.noise_levels(self.models), in_shift, in_scale, o_mean, o_scale,
+                                var_includes_noise)
+        traj, Sigma, stages = _pg.host_loop(stage, coord, x0, U, lin, S0, Q, R, H)
+        return (traj, Sigma, stages) if return_stages else (traj, Sigma)
+
     def sample_y(self, Xq, n_samples=1, random_state=0):
         """Draws from every model's joint posterior at the rows Xq: (M, B, n_samples), through the Cholesky factor of each
         covariance (`gpr.cholesky_draws`), as `BatchedARDGP.sample_y`."""

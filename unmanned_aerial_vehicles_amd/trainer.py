@@ -563,6 +563,54 @@ class PreTrainedGP:
             print(f"GP rollout sampling failed: {e}")
             return fallback
 
+    def propagate_horizon(self, state, U_guess, dt, Sigma0=None, process_noise=None):
+        """`SimpleQuadrotorGP.propagate_horizon` for the per-axis models, in raw units: the closed loop of the posterior MEANS
+        and the state covariance the models' uncertainty induces along it, to first order,
+
+            x_{k+1} = x_k + dt [v_k, a_k] + sum_i e_i mu_i(q_k),   Sigma_{k+1} = A_k Sigma_k A_k^T + sum_i var_i(q_k) e_i e_i^T + Q
+
+        with mu_i = sy_i.mean_ + sy_i.scale_ m_i((q - sx.mean_) / sx.scale_), var_i its variance and A_k = I + lin[:, :6] + the
+        rows d mu_i / d x.  Models that share inputs and scaler (those `GPTrainer` writes): ONE call for the horizon
+        (`BatchedARDGP.propagate`: the shared input scaler and each model's target scaler; a file of sparse models:
+        `BatchedSparseGP.propagate`, a host loop with one call for all models per stage); otherwise the same recursion model by
+        model over `predict_residual_jacobian_batch`.  The variances are the latent functions' on both routes.  state (6,);
+        U_guess (4, N) -> X (6, N + 1), Sigma (N + 1, 6, 6); U_guess (R, 4, N) -> (R, 6, N + 1), (R, N + 1, 6, 6).  A residual
+        without a model leaves its coordinate nominal.  Not loaded, or any failure (printed): the nominal trajectory and
+        Sigma_{k+1} = (I + lin_x) Sigma_k (I + lin_x)^T + Q - it never raises into the control loop."""
+        from . import propagate as _pg
+        state, U, lin, nominal, single = _pg.horizon_inputs(GPTrainer._nominal_dynamics, state, U_guess, dt)
+        try:
+            if not self.is_loaded:
+                raise RuntimeError("no models are loaded")
+            fused = self._fused()
+            if fused:
+                bg, names = fused
+                sys_ = [self.scalers_y[n] for n in names]
+                traj, Sigma = bg.propagate(state, U, lin, coord=[OUTPUT_NAMES.index(n) for n in names],
+                                           in_scaler=self.scalers_X[names[0]], Sigma0=Sigma0, process_noise=process_noise,
+                                           out_scaler=([float(np.ravel(s.mean_)[0]) for s in sys_],
+                                                       [float(np.ravel(s.scale_)[0]) for s in sys_]))
+            else:
+                coord = [i for i, n in enumerate(OUTPUT_NAMES) if n in self.gp_models]
+                x0, Uc, linc, S0, Q, R, H = _pg.check_horizon(state, U, lin, 6, 10, Sigma0, process_noise)
+                # the noise level's share of every model's raw variance: the served variances carry it, the propagation
+                # takes the latent function's
+                lvl = np.array([(self.gp_models[OUTPUT_NAMES[i]].kernel_.components().noise or 0.0) *
+                                (float(np.ravel(self.gp_models[OUTPUT_NAMES[i]]._y_train_std)[0]) *
+                                 float(np.ravel(self.scalers_y[OUTPUT_NAMES[i]].scale_)[0])) ** 2 for i in coord])
+
+                def stage(q):
+                    mean, J, std, _ = self.predict_residual_jacobian_batch(q, return_std=True)
+                    return mean[:, coord], J[:, coord, :], np.maximum(std[:, coord] ** 2 - lvl[None, :], 0.0)
+
+                traj, Sigma, _ = _pg.host_loop(stage, coord, x0, Uc, linc, S0, Q, R, H)
+            if not (np.isfinite(traj).all() and np.isfinite(Sigma).all()):
+                raise FloatingPointError("non-finite trajectory or covariance")
+            return _pg.horizon_layout(traj, Sigma, single)
+        except Exception as e:  # noqa: BLE001
+            print(f"GP horizon propagation failed: {e}")
+            return _pg.horizon_layout(*_pg.nominal_horizon(nominal, lin, Sigma0, process_noise), single)
+
     def predict_residual_jacobian(self, state, control):
         """One query -> (mean (6,), J (6, 10)), J = d mean / d [state(6), control(4)]; not loaded or failed: zeros."""
         try:
