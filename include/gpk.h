@@ -67,7 +67,7 @@ GPK_API int64_t gpk_padded(int64_t n);
  * streaming pass of gpk_lml_grad over K^-1; tag GPK_TIMED_POTRF: the launches of one gpk_potrf; tag GPK_TIMED_COV: the
  * symmetric product (K(Xq, Xq) + noise I - V^T V) of gpk_predict_cov_inv / gpk_predict_cov; tag GPK_TIMED_JAC: the second
  * triangular product (C = W^T V) of gpk_predict_var_grad_inv; tag GPK_TIMED_PROPAGATE: the advance launch of every stage of
- * gpk_propagate_host[_multi] - and keeps the
+ * gpk_propagate_host[_multi] and gpk_sparse_propagate[_multi] - and keeps the
  * last 64 pairs.  gpk_kernel_times synchronises the stream and returns the elapsed milliseconds of the bracketed
  * launches with that tag still in the ring, oldest first (*n_out of them, at most max_n).  bench.py uses it to
  * report the dominant kernel's duration over exactly the timed steps; rocprofv3's kernel trace of the same run is
@@ -1067,6 +1067,35 @@ GPK_API int gpk_propagate_host_multi(gpk_handle h, int B, const double* const* X
                                      const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows,
                                      const double* Q, int R, int H, double* traj, double* Sigma, double* mean, double* var,
                                      double* jac);
+
+/* ... on the sparse posteriors: the same chain - the recursion, the host arrays, 3 H launches, one upload, up to five downloads,
+ * ONE stream synchronisation - on the two-factor small-batch launches (kss - |Wuu k*|^2 + |WSigma k*|^2 on m inducing
+ * points), m in the place of N: R in [1, 32], H in [1, 256], nx <= D <= 16, gpk_padded(m) <= 16384.
+ * gpk_sparse_propagate: the finalised sparse object of h, P outputs; the state is its outputs (nx = P <= D), no scalers.
+ *   Replaces: H calls of gpk_sparse_predict_grad - H synchronisations and H W^T V launches whose result the recursion never
+ *   reads - around the composition on the host; in the reference, nothing (its GP-MPC propagates no covariance).
+ * gpk_sparse_propagate_multi: B <= 8 handles of finalised single-output models of equal m and D, handle rules as
+ *   gpk_sparse_predict_multi_grad (h supplies the stream and the scratch; nothing is synchronised on the models' own
+ *   streams); nx, coord, in_shift / in_scale as gpk_propagate_host_multi; out_shift / out_scale (B each, both or neither): the
+ *   affine map out_shift[b] + out_scale[b] y behind every model's output, folded into the y_mean / y_std the kernels apply.
+ *   RAW units.  Replaces: H calls of gpk_sparse_predict_multi_grad around the composition on the host.
+ * Stage quantities (mean, var: H x R x P or B; jac: H x R x P or B x D) in the units of gpk_sparse_predict[_multi]_grad.  With
+ * var_includes_noise != 0 mean, jac and var have the BITS of that entry (its last argument 1) at the rows [traj[h], U[h]].  With
+ * 0 var is the latent variance of gpk_sparse_predict_grad(..., 0): kss = sf2, clipped at 1e-10 (normalised-target units) -
+ * where a host loop over the noisy entry forms max(noisy - noise y_std^2, 0); the two differ in rounding only while neither
+ * clip is active.
+ * GPK_BAD_ARG (with a message, before any launch): no finalised sparse model (in the batch: any handle), models that disagree
+ *   in m or D or have several outputs, B outside 1..8, the limits above, nx < B, a wrong row count, NaN or infinity in a host
+ *   input, in_scale zero, coord out of range or repeated, a scaler given by half, a null pointer, batched mode, option
+ *   small_path = 0.  Timed under GPK_TIMED_PROPAGATE as the exact entries.                                                  */
+GPK_API int gpk_sparse_propagate(gpk_handle h, int var_includes_noise, const double* x0, int x0_rows, const double* U, int u_rows,
+                                 const double* lin, const double* Sigma0, int s_rows, const double* Q, int R, int H, double* traj,
+                                 double* Sigma, double* mean, double* var, double* jac);
+GPK_API int gpk_sparse_propagate_multi(gpk_handle h, int B, const gpk_handle* models, int var_includes_noise, int nx,
+                                       const int* coord, const double* in_shift, const double* in_scale, const double* out_shift,
+                                       const double* out_scale, const double* x0, int x0_rows, const double* U, int u_rows,
+                                       const double* lin, const double* Sigma0, int s_rows, const double* Q, int R, int H,
+                                       double* traj, double* Sigma, double* mean, double* var, double* jac);
 
 #ifdef __cplusplus
 }

@@ -169,6 +169,10 @@ SIGNATURES = {
     "gpk_propagate_host_multi": (_int, [_vp, _int, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _dbl, _int, _vp,
                                         _int, C.POINTER(_int), _vp, _vp, _vp, _int, _vp, _int, _vp, _vp, _int, _vp, _int, _int,
                                         _vp, _vp, _vp, _vp, _vp]),
+    # ... on the sparse posteriors: var_includes_noise, [nx, coord, in_shift, in_scale, out_shift, out_scale,] then as above
+    "gpk_sparse_propagate": (_int, [_vp, _int, _dp, _int, _dp, _int, _dp, _dp, _int, _dp, _int, _int, _dp, _dp, _dp, _dp, _dp]),
+    "gpk_sparse_propagate_multi": (_int, [_vp, _int, C.POINTER(_vp), _int, _int, C.POINTER(_int), _dp, _dp, _dp, _dp, _dp, _int,
+                                          _dp, _int, _dp, _dp, _int, _dp, _int, _int, _dp, _dp, _dp, _dp, _dp]),
 }
 
 _lib = None

@@ -289,9 +289,34 @@ size_t gpk_small_work_doubles(int call, int64_t Np, int B, int64_t M, int D, int
 //   GPK_SMALL_PREDICT  mean: 1 launch; with out.var 2
 //   GPK_SMALL_GRAD     mean + dmean: 1 launch; with out.var and out.dvar 3
 //   GPK_SMALL_COV      mean + cov (m.noise on the diagonal, not clipped): 2 launches
-//   GPK_SMALL_JACVAR   mean + dmean + var, F = 1 (a stage of gpk_propagate_host[_multi]): 2 launches, the bits of GPK_SMALL_GRAD's
+//   GPK_SMALL_JACVAR   mean + dmean + var (a stage of the propagation chains, gpk_propagate_run): 2 launches, the bits of GPK_SMALL_GRAD's
 // Block b of every output has the bits of model b served alone.
 int gpk_small_launch(gpk_handle h, int call, const ServeModels& m, const double* Xq, int64_t M, double* work, const ServeOut& out);
+// ---- horizon propagation (gpk_propagate.hip): what the entries of the exact models and of the sparse models (gpk_sparse.hip) share
+constexpr int GPK_PROP_MAX_R = GPK_SMALL_MAX_M, GPK_PROP_MAX_H = 256, GPK_PROP_MAX_NX = 16, GPK_PROP_MAX_D = 16;
+// The composition's parameters.  Output o of the stage (a single model's output p, or model b of a batch) sits at
+// smean[o * so + m * sm], svar[o * vo + m * vm] and sjac[(o * so + m * sm) * D + d] for query row m.  One-factor models: svar in
+// normalised-target units (ystd2, noise, add_noise apply); two-factor models: svar is final (ystd2 = 1, add_noise = 0).
+struct PropK {
+  int nx, D, NO;                     // state width, query width, outputs of a stage
+  int so, sm, vo, vm;
+  int model_of[GPK_PROP_MAX_NX];     // state coordinate -> the output that drives it, or -1 (lin alone, no variance)
+  int scaled;                        // the queries go through (q - in_shift) / in_scale, the Jacobians through 1 / in_scale
+  double in_shift[GPK_PROP_MAX_D], in_scale[GPK_PROP_MAX_D];
+  double ystd2[16];                  // y_std[o]^2: the variance in target units is svar * ystd2, as the Python layer forms it
+  double noise[16];                  // added to svar (normalised units) when the variance is to include the noise level
+  int add_noise;
+};
+// What the entries share past their model arguments.
+struct Horizon {
+  const double *x0, *U, *lin, *Sigma0, *Q;
+  int x0_rows, u_rows, s_rows, R, H;
+  double *traj, *Sigma, *mean, *var, *jac;
+};
+// The chain of one horizon on the models m (F = 1 or 2): every check of the limits (GPK_BAD_ARG before anything is launched), one
+// upload, 3 H launches, up to five downloads, one synchronisation.  k: nx, D, NO, the strides, model_of, the scaler, ystd2 and
+// the noise filled in by the entry; `who` prefixes the messages.
+int gpk_propagate_run(gpk_handle h, const std::string& who, const ServeModels& m, PropK k, const Horizon& z);
 // ... as one-call serving (gpk_serve.hip): host queries in, host results out through the pinned, mapped block, one
 // synchronisation.  small: the launches above (gpk_serve_predict: 33..64 queries the same twice); otherwise, F = 1 only, the
 // general chain, which also reads m.Np / m.ldw only with the inverse factor.

@@ -11,25 +11,14 @@
 // stage's scaled query rows where its first launch reads them.  The state (x, Sigma), the queries, the stage results and the
 // horizon's outputs stay in one device block; ONE upload before the chain ([x | Sigma | q | lin | Q | U] as one block), up to five
 // downloads and ONE stream synchronisation after it.  The caller's arrays are ordinary (pageable) host memory: the runtime stages
-// those copies and may wait on them by itself; nothing waits between the stages.
+// those copies and may wait on them by itself; nothing waits between the stages.  gpk_propagate_run is the chain for every entry:
+// the exact models' below, the sparse models' in gpk_sparse.hip (two inverse factors per model: the stage's variance arrives final
+// and in another layout, which PropK's strides describe).
 #include "gpk_internal.h"
 
 namespace {
 
-constexpr int PROP_MAX_R = GPK_SMALL_MAX_M, PROP_MAX_H = 256, PROP_MAX_NX = 16, PROP_MAX_D = 16;
-
-// The composition's parameters.  Output o of the stage (a single model's output p, or model b of a batch) sits at
-// smean[o * so + m * sm], svar[o * vo + m] (normalised-target units) and sjac[(o * so + m * sm) * D + d] for query row m.
-struct PropK {
-  int nx, D, NO;                     // state width, query width, outputs of a stage
-  int so, sm, vo;
-  int model_of[PROP_MAX_NX];         // state coordinate -> the output that drives it, or -1 (lin alone, no variance)
-  int scaled;                        // the queries go through (q - in_shift) / in_scale, the Jacobians through 1 / in_scale
-  double in_shift[PROP_MAX_D], in_scale[PROP_MAX_D];
-  double ystd2[16];                  // y_std[o]^2: the variance in target units is svar * ystd2, as the Python layer forms it
-  double noise[16];                  // added to svar (normalised units) when the variance is to include the noise level
-  int add_noise;
-};
+constexpr int PROP_MAX_R = GPK_PROP_MAX_R, PROP_MAX_H = GPK_PROP_MAX_H, PROP_MAX_NX = GPK_PROP_MAX_NX, PROP_MAX_D = GPK_PROP_MAX_D;
 
 // One workgroup per rollout r, thread (i, j) = (tid >> 4, tid & 15).  Sequential, fixed-order sums; Sigma in LDS; the lower
 // triangle of T A^T is formed and mirrored, so Sigma is symmetric bit for bit.  x and S are the rollout's state, updated in
@@ -48,7 +37,7 @@ __global__ __launch_bounds__(256) void propagate_advance_kernel(PropK k, int R, 
   if (tid < D) q[tid] = tid < nx ? x[(long long)r * nx + tid] : u[r * u_row_stride + (tid - nx)];
   if (i < nx && j < nx) Sg[i][j] = S[((long long)r * nx + i) * nx + j];
   if (tid < NO) {
-    const double v = svar[tid * k.vo + r];
+    const double v = svar[tid * k.vo + r * k.vm];
     mu[tid] = smean[tid * k.so + r * k.sm];
     vv[tid] = (k.add_noise ? v + k.noise[tid] : v) * k.ystd2[tid];
   }
@@ -111,15 +100,9 @@ bool prop_finite(const double* p, size_t n) {
   return true;
 }
 
-// What the two entries share past their model arguments.  k: nx, D, NO, the strides, model_of, the scaler, ystd2 and the noise
-// filled in by the entry.
-struct Horizon {
-  const double *x0, *U, *lin, *Sigma0, *Q;
-  int x0_rows, u_rows, s_rows, R, H;
-  double *traj, *Sigma, *mean, *var, *jac;
-};
+}  // namespace
 
-int propagate_run(gpk_handle h, const std::string& who, const ServeModels& m, PropK k, const Horizon& z) {
+int gpk_propagate_run(gpk_handle h, const std::string& who, const ServeModels& m, PropK k, const Horizon& z) {
   const int nx = k.nx, D = k.D, nu = D - nx, NO = k.NO, R = z.R, H = z.H;
   GPK_REQUIRE(h, h->batch == 1, who + "not available in batched mode");
   GPK_REQUIRE(h, R >= 1 && R <= PROP_MAX_R, who + "R must be in [1, 32]");
@@ -147,7 +130,7 @@ int propagate_run(gpk_handle h, const std::string& who, const ServeModels& m, Pr
   // horizon's outputs from slot 1 on (slot 0 of traj and Sigma is the caller's own start)
   const size_t n_up = n_x + n_s + n_q + n_lin + n_Q + n_u;
   const size_t n_sm = (size_t)NO * R, n_sj = n_sm * D;
-  const size_t n_work = gpk_small_work_doubles(GPK_SMALL_JACVAR, m.Np, m.B, R, D, m.P, 1);
+  const size_t n_work = gpk_small_work_doubles(GPK_SMALL_JACVAR, m.Np, m.B, R, D, m.P, m.F);
   const size_t n_traj = (size_t)H * n_x, n_sig = (size_t)H * n_s, n_om = (size_t)H * n_sm, n_oj = (size_t)H * n_sj;
   void* ws = nullptr;
   GPK_TRY(gpk_scratch(h, (n_up + 2 * n_sm + n_sj + n_work + n_traj + n_sig + 2 * n_om + n_oj) * sizeof(double), &ws));
@@ -214,8 +197,6 @@ int propagate_run(gpk_handle h, const std::string& who, const ServeModels& m, Pr
   return GPK_OK;
 }
 
-}  // namespace
-
 extern "C" int gpk_propagate_host(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
                                   double sf2, const double* y_mean, const double* y_std, const double* W, int64_t Np, int64_t ldw,
                                   double kss, double floor_, int var_includes_noise, double noise, const double* x0, int x0_rows,
@@ -228,13 +209,13 @@ extern "C" int gpk_propagate_host(gpk_handle h, const double* X, const double* a
   GPK_REQUIRE(h, prop_finite(&noise, 1) && prop_finite(&kss, 1) && prop_finite(&floor_, 1), who + "kss, floor and noise must be finite");
   PropK k{};
   k.nx = P; k.D = D; k.NO = P;
-  k.so = 1; k.sm = P; k.vo = 0;
+  k.so = 1; k.sm = P; k.vo = 0; k.vm = 1;
   k.add_noise = var_includes_noise != 0;
   for (int d = 0; d < 16; ++d) { k.in_shift[d] = 0.0; k.in_scale[d] = 1.0; k.model_of[d] = d < P ? d : -1; }
   for (int p = 0; p < P; ++p) { k.ystd2[p] = y_std[p] * y_std[p]; k.noise[p] = noise; }
   const ServeModels m{1, P, 1, &X, &alpha, N, D, ls, &sf2, y_mean, y_std, {&W, nullptr}, Np, ldw, &kss, floor_, nullptr};
   const Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean, var, jac};
-  return propagate_run(h, who, m, k, z);
+  return gpk_propagate_run(h, who, m, k, z);
 }
 
 extern "C" int gpk_propagate_host_multi(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D,
@@ -255,7 +236,7 @@ extern "C" int gpk_propagate_host_multi(gpk_handle h, int B, const double* const
   for (int b = 0; b < B; ++b) GPK_REQUIRE(h, X[b] && alpha[b] && W[b], who + "null model pointer");
   PropK k{};
   k.nx = nx; k.D = D; k.NO = B;
-  k.so = R; k.sm = 1; k.vo = R;
+  k.so = R; k.sm = 1; k.vo = R; k.vm = 1;
   k.add_noise = var_includes_noise != 0;
   for (int d = 0; d < 16; ++d) { k.in_shift[d] = 0.0; k.in_scale[d] = 1.0; k.model_of[d] = -1; }
   for (int b = 0; b < B; ++b) {
@@ -277,5 +258,5 @@ extern "C" int gpk_propagate_host_multi(gpk_handle h, int B, const double* const
   }
   const ServeModels m{B, 1, 1, X, alpha, N, D, ls, sf2, y_mean, y_std, {W, nullptr}, Np, ldw, kss, floor_, nullptr};
   const Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean, var, jac};
-  return propagate_run(h, who, m, k, z);
+  return gpk_propagate_run(h, who, m, k, z);
 }

@@ -33,7 +33,8 @@
 //   a propagation stage (K11) mean + Jacobian + variance without the variance gradient: small_cross_mean_jac_kernel, then
 //                            small_var_jac_kernel - small_var_grad_kernel's body without its store of V - and no W^T V launch: two
 //                            launches with the bits of the three-launch call (gpk_propagate.hip chains them along a horizon, the
-//                            queries in a device buffer).
+//                            queries in a device buffer).  small_var_jac2_kernel is its two-factor form (below: TWO), the sparse
+//                            models' stage: var_out M x P (B x M for a batch), final.
 //
 //   two factors (K9)         the sparse model's variance terms are kss - |Wuu k*|^2 + |WSigma k*|^2 on ONE K* with P outputs: the
 //                            first launch runs with one model, and small_var[_grad]_kernel, small_cov_kernel and small_wtv_grad_kernel
@@ -504,6 +505,16 @@ __global__ __launch_bounds__(64 * VW) void small_var_jac_kernel(SmallK k, long l
   small_var_body<NMB, 2, false>(k, ldw, Np, Ks, M, P, floor_, pmean, mean_shares, pvar, counter, mean_out, var_out, nullptr, pjac, D,
                                 dmean_out);
 }
+// ... its two-factor form (the sparse model's stage): small_var_grad_kernel<NMB, true> without its store of V - blockIdx.y = 2 *
+// model + inverse factor, one ticket count per model, var_out M x P (B x M for a batch) already times y_std^2
+template <int NMB>
+__global__ __launch_bounds__(64 * VW) void small_var_jac2_kernel(SmallK k, long long ldw, long long Np, const double* Ks, int M, int P,
+                                                                 double floor_, const double* pmean, unsigned mean_shares,
+                                                                 double* pvar, unsigned* counter, double* mean_out, double* var_out,
+                                                                 const double* pjac, int D, double* dmean_out) {
+  small_var_body<NMB, 2, true>(k, ldw, Np, Ks, M, P, floor_, pmean, mean_shares, pvar, counter, mean_out, var_out, nullptr, pjac, D,
+                               dmean_out);
+}
 
 constexpr int CG = 16;                   // workgroups per first-level group of the covariance reduction
 constexpr int CE = SQ * (SQ + 1) / 2;    // packed lower-triangle entries of a 32 x 32 share
@@ -854,6 +865,10 @@ auto cov_kernel(int64_t M, int F) {
   return M <= 16 ? (F == 2 ? small_cov_kernel<1, true> : small_cov_kernel<1, false>)
                  : (F == 2 ? small_cov_kernel<2, true> : small_cov_kernel<2, false>);
 }
+auto var_jac_kernel(int64_t M, int F) {
+  return M <= 16 ? (F == 2 ? small_var_jac2_kernel<1> : small_var_jac_kernel<1>)
+                 : (F == 2 ? small_var_jac2_kernel<2> : small_var_jac_kernel<2>);
+}
 auto wtv_grad_kernel(int F) { return F == 2 ? small_wtv_grad_kernel<true> : small_wtv_grad_kernel<false>; }
 
 }  // namespace
@@ -878,7 +893,7 @@ int gpk_small_launch(gpk_handle h, int call, const ServeModels& m, const double*
   GPK_REQUIRE(h, gpk_small_ok(Np, D, P, M), name + ": shape outside the small-batch path");
   GPK_REQUIRE(h, m.X && m.alpha && m.ls && m.sf2 && m.y_mean && m.y_std && Xq && work && out.mean, name + ": null pointer");
   GPK_REQUIRE(h, !grad || jv || (out.dmean && (out.var == nullptr) == (out.dvar == nullptr)), name + ": null pointer");
-  GPK_REQUIRE(h, !jv || (out.dmean && out.var && !out.dvar && F == 1), name + ": mean, variance and Jacobian of one-factor models");
+  GPK_REQUIRE(h, !jv || (out.dmean && out.var && !out.dvar), name + ": mean, variance and Jacobian, no variance gradient");
   GPK_REQUIRE(h, !cov || (out.cov && m.noise), name + ": null pointer");
   // the inverse factors enter with the variance (and its gradient) and with the covariance: the second and third launches
   const bool factors = cov || out.var;
@@ -907,8 +922,8 @@ int gpk_small_launch(gpk_handle h, int call, const ServeModels& m, const double*
     hipLaunchKernelGGL(cov_kernel(M, F), g2, b2, 0, h->stream, k, ldw, Np, Ks, (int)M, D, P, Xq, pmean, ga, work + wk.pcov,
                        work + wk.gcov, h->d_cov_count, out.mean, out.cov);
   } else if (jv) {
-    hipLaunchKernelGGL(M <= 16 ? small_var_jac_kernel<1> : small_var_jac_kernel<2>, g2, b2, 0, h->stream, k, ldw, Np, Ks, (int)M, P,
-                       m.floor_, pmean, ga, work + wk.pvar, vcount, out.mean, out.var, pjac, D, out.dmean);
+    hipLaunchKernelGGL(var_jac_kernel(M, F), g2, b2, 0, h->stream, k, ldw, Np, Ks, (int)M, P, m.floor_, pmean, ga, work + wk.pvar,
+                       vcount, out.mean, out.var, pjac, D, out.dmean);
   } else if (!grad) {
     hipLaunchKernelGGL(var_kernel(M, F), g2, b2, 0, h->stream, k, ldw, Np, Ks, (int)M, P, m.floor_, pmean, ga, work + wk.pvar, vcount,
                        out.mean, out.var);

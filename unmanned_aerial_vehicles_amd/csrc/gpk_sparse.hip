@@ -1215,6 +1215,19 @@ extern "C" int gpk_sparse_predict_cov(gpk_handle h, const double* Xq, int64_t M,
 // ---- the per-axis batch: B single-output sparse models on one query batch ---------------------------------------------------
 namespace {
 
+// The models of a batch entry: B (checked by the caller) finalised single-output sparse models of equal m and D on h's device.
+int sparse_batch_models(gpk_handle h, const std::string& name, int B, const gpk_handle* models, gpk_sparse** list) {
+  for (int b = 0; b < B; ++b) {
+    GPK_REQUIRE(h, models[b], name + ": null handle in the list of models");
+    gpk_sparse* s = list[b] = models[b]->sparse;
+    GPK_REQUIRE(h, s && s->finalized, name + ": a model is not a finalised sparse model (call gpk_sparse_finalize first)");
+    GPK_REQUIRE(h, models[b]->device == h->device, name + ": every model must live on the serving handle's device");
+    GPK_REQUIRE(h, s->P == 1, name + ": every model must have one output");
+    GPK_REQUIRE(h, b == 0 || (s->m == list[0]->m && s->D == list[0]->D), name + ": the models must agree in m and D");
+  }
+  return GPK_OK;
+}
+
 // The checks the three batch entries share, then the models taken apart.
 int sparse_batch(gpk_handle h, const char* who, int B, const gpk_handle* models, const double* Xq, int64_t M, int64_t max_M,
                  int var_includes_noise, SparseServe& sb) {
@@ -1224,14 +1237,7 @@ int sparse_batch(gpk_handle h, const char* who, int B, const gpk_handle* models,
   GPK_REQUIRE(h, max_M <= 0 || M <= max_M, name + ": M outside [1, 16384]");
   GPK_REQUIRE(h, h->batch == 1, "composite calls are not available in batched mode");
   gpk_sparse* list[GPK_SMALL_MAX_MODELS];
-  for (int b = 0; b < B; ++b) {
-    GPK_REQUIRE(h, models[b], name + ": null handle in the list of models");
-    gpk_sparse* s = list[b] = models[b]->sparse;
-    GPK_REQUIRE(h, s && s->finalized, name + ": a model is not a finalised sparse model (call gpk_sparse_finalize first)");
-    GPK_REQUIRE(h, models[b]->device == h->device, name + ": every model must live on the serving handle's device");
-    GPK_REQUIRE(h, s->P == 1, name + ": every model must have one output");
-    GPK_REQUIRE(h, b == 0 || (s->m == list[0]->m && s->D == list[0]->D), name + ": the models must agree in m and D");
-  }
+  GPK_TRY(sparse_batch_models(h, name, B, models, list));
   GPK_TRY(gpk_require_finite(h, Xq, M * list[0]->D, who, "Xq"));
   sb.fill(B, list, var_includes_noise);
   return GPK_OK;
@@ -1304,6 +1310,83 @@ extern "C" int gpk_sparse_predict_multi_cov(gpk_handle h, int B, const gpk_handl
   }
   gpk_interleave(mn.data(), B, M, 1, mean);
   return GPK_OK;
+}
+
+// ---- horizon propagation (K11) on the sparse posteriors: the chain of gpk_propagate.hip on the two-factor description ----------
+// The stage's variance comes out of the two-factor launch final - times y_std^2, the noise level inside kss - in the layout of
+// its var_out (M x P for one model, B x M for a batch): the advance launch takes it as it is (ystd2 = 1, add_noise = 0).
+extern "C" int gpk_sparse_propagate(gpk_handle h, int var_includes_noise, const double* x0, int x0_rows, const double* U, int u_rows,
+                                    const double* lin, const double* Sigma0, int s_rows, const double* Q, int R, int H, double* traj,
+                                    double* Sigma, double* mean, double* var, double* jac) {
+  if (!h) return GPK_BAD_ARG;
+  const std::string who("sparse_propagate: ");
+  gpk_sparse* s = h->sparse;
+  GPK_REQUIRE(h, s && s->finalized, who + "no finalised sparse model (call gpk_sparse_finalize first)");
+  GPK_REQUIRE(h, h->small_path, who + "the small-batch path is switched off (option small_path)");
+  const int D = s->D, P = s->P;
+  GPK_REQUIRE(h, P >= 1 && P <= GPK_PROP_MAX_NX && P <= D, who + "the state dimension P must be in [1, 16] and must not exceed D");
+  GPK_CHECK_HIP(h, hipSetDevice(h->device));
+  SparseServe sv;
+  sv.fill(1, &s, var_includes_noise);
+  PropK k{};
+  k.nx = P; k.D = D; k.NO = P;
+  k.so = 1; k.sm = P; k.vo = 1; k.vm = P;
+  for (int d = 0; d < 16; ++d) { k.in_shift[d] = 0.0; k.in_scale[d] = 1.0; k.model_of[d] = d < P ? d : -1; k.ystd2[d] = 1.0; }
+  const Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean, var, jac};
+  return gpk_propagate_run(h, who, sv.models(), k, z);
+}
+
+extern "C" int gpk_sparse_propagate_multi(gpk_handle h, int B, const gpk_handle* models, int var_includes_noise, int nx,
+                                          const int* coord, const double* in_shift, const double* in_scale, const double* out_shift,
+                                          const double* out_scale, const double* x0, int x0_rows, const double* U, int u_rows,
+                                          const double* lin, const double* Sigma0, int s_rows, const double* Q, int R, int H,
+                                          double* traj, double* Sigma, double* mean, double* var, double* jac) {
+  if (!h) return GPK_BAD_ARG;
+  const std::string who("sparse_propagate_multi: ");
+  GPK_REQUIRE(h, B >= 1 && B <= GPK_SMALL_MAX_MODELS, who + "1..8 models");
+  GPK_REQUIRE(h, models && coord, who + "null pointer");
+  GPK_REQUIRE(h, h->batch == 1, who + "not available in batched mode");
+  GPK_REQUIRE(h, h->small_path, who + "the small-batch path is switched off (option small_path)");
+  GPK_REQUIRE(h, (in_shift == nullptr) == (in_scale == nullptr), who + "in_shift and in_scale go together");
+  GPK_REQUIRE(h, (out_shift == nullptr) == (out_scale == nullptr), who + "out_shift and out_scale go together");
+  gpk_sparse* list[GPK_SMALL_MAX_MODELS];
+  GPK_TRY(sparse_batch_models(h, "sparse_propagate_multi", B, models, list));
+  const int D = list[0]->D;
+  GPK_REQUIRE(h, D >= 1 && D <= GPK_PROP_MAX_D && nx >= B && nx <= D, who + "the state dimension nx must be in [B, D], D <= 16");
+  GPK_CHECK_HIP(h, hipSetDevice(h->device));
+  SparseServe sb;
+  sb.fill(B, list, var_includes_noise);
+  PropK k{};
+  k.nx = nx; k.D = D; k.NO = B;
+  k.so = R; k.sm = 1; k.vo = R; k.vm = 1;
+  for (int d = 0; d < 16; ++d) { k.in_shift[d] = 0.0; k.in_scale[d] = 1.0; k.model_of[d] = -1; k.ystd2[d] = 1.0; }
+  for (int b = 0; b < B; ++b) {
+    GPK_REQUIRE(h, coord[b] >= 0 && coord[b] < nx, who + "coord must be in [0, nx)");
+    GPK_REQUIRE(h, k.model_of[coord[b]] < 0, who + "coord must be distinct");
+    k.model_of[coord[b]] = b;
+  }
+  if (in_shift) {
+    for (int d = 0; d < D; ++d) {
+      GPK_REQUIRE(h, in_shift[d] - in_shift[d] == 0.0 && in_scale[d] - in_scale[d] == 0.0,
+                  who + "the input scaler must not contain NaN or infinity");
+      GPK_REQUIRE(h, in_scale[d] != 0.0, who + "in_scale must be non-zero");
+      k.in_shift[d] = in_shift[d];
+      k.in_scale[d] = in_scale[d];
+    }
+    k.scaled = 1;
+  }
+  // the affine map behind every model's output, folded into the normalisation the kernels apply (as BatchedARDGP.propagate
+  // folds it on the host): out_shift + out_scale (y_mean + y_std s)
+  if (out_shift) {
+    for (int b = 0; b < B; ++b) {
+      GPK_REQUIRE(h, out_shift[b] - out_shift[b] == 0.0 && out_scale[b] - out_scale[b] == 0.0,
+                  who + "the output scaler must not contain NaN or infinity");
+      sb.y_mean[b] = out_shift[b] + out_scale[b] * sb.y_mean[b];
+      sb.y_std[b] = out_scale[b] * sb.y_std[b];
+    }
+  }
+  const Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean, var, jac};
+  return gpk_propagate_run(h, who, sb.models(), k, z);
 }
 
 extern "C" int gpk_sparse_export(gpk_handle h, int64_t* m, int* D, int* P, int* n_ls, double* Z, double* G, double* g, double* yy,

@@ -7,10 +7,11 @@ For a state x in R^nx, a query q = [x, u] in R^D and the nominal increment `lin`
     Sigma_{h+1} = A_h Sigma_h A_h^T + sum_b v_b(q) e_coord[b] e_coord[b]^T + Q
 
 - the first-order propagation of Hewing, Kabzan and Zeilinger (Cautious MPC using GP regression).  The estimators run it as one
-C call per horizon (`gpk_propagate_host`, `gpk_propagate_host_multi`: three launches per stage, one synchronisation); what is
+C call per horizon (`gpk_propagate_host[_multi]`, and `gpk_sparse_propagate[_multi]` for route="chain" of the sparse classes: three
+launches per stage, one synchronisation); what is
 here is what they share on the host: the argument checks (before any device call), the same recursion as a host loop over a
-model's `predict_jacobian(..., return_var=True)` - the route of the sparse models, of exact models beyond the small-batch
-path and of option small_path=0 - and what the control-loop wrappers (`propagate_horizon`) share, their nominal fallback included.
+model's `predict_jacobian(..., return_var=True)` - the "auto" and "host" routes of the sparse models, the route of exact models
+beyond the small-batch path and of option small_path=0 - and what the control-loop wrappers (`propagate_horizon`) share, their nominal fallback included.
 """
 from __future__ import annotations
 
@@ -110,15 +111,38 @@ def host_loop(stage, coord, x0, U, lin, S0, Q, R, H):
 
 
 # ---- what the batches (BatchedARDGP, BatchedSparseGP) share: raw units around single-output models --------------------------------
-def check_batch(B, D, x0, U, lin, coord, in_scaler, out_scaler, Sigma0, process_noise, route):
+def check_route(route, routes=("auto", "host")):
+    """ValueError unless `route` is one of `routes` (the sparse classes add "chain", the one-call device chain)."""
+    if route not in routes:
+        raise ValueError("route must be " + " or ".join(repr(r) for r in routes))
+    return route
+
+
+def wrapper_route(model):
+    """The route a control-loop wrapper asks of its model: the sparse classes' one-call chain where their predicate
+    `propagate_ok()` holds, otherwise "auto" (the exact classes choose by themselves; the sparse ones run the host loop)."""
+    ok = getattr(model, "propagate_ok", None)
+    return "chain" if callable(ok) and ok() else "auto"
+
+
+def chain_sizes_ok(m, D, nx):
+    """The sizes within the limits of gpk_sparse_propagate[_multi]: m inducing points (padded to 128) <= 16 384,
+    1 <= nx <= D <= 16.  Returns the reason as a string where they are not, None where they are."""
+    if not (1 <= nx <= D <= 16):
+        return f"the chain needs 1 <= nx <= D <= 16 (nx = {nx}, D = {D})"
+    if -(-int(m) // 128) * 128 > 16384:
+        return f"the chain needs at most 16384 inducing points after padding (m = {m})"
+    return None
+
+
+def check_batch(B, D, x0, U, lin, coord, in_scaler, out_scaler, Sigma0, process_noise, route, routes=("auto", "host")):
     """The arguments of a batch's `propagate`: `check_horizon`'s results, then coord (list), in_shift, in_scale ((D,) or None),
-    o_mean, o_scale ((B,): the identity without an out_scaler)."""
+    o_mean, o_scale ((B,): the identity without an out_scaler).  routes: what the class accepts for `route`."""
     lin = np.asarray(lin, dtype=np.float64)
     nx = lin.shape[0] if lin.ndim == 2 else 0
     if not (B <= nx <= D):
         raise ValueError(f"propagate needs a state of {B} <= nx <= {D} coordinates (got {nx})")
-    if route not in ("auto", "host"):
-        raise ValueError("route must be 'auto' or 'host'")
+    check_route(route, routes)
     head = check_horizon(x0, U, lin, nx, D, Sigma0, process_noise)
     coord = check_coord(coord, B, nx)
     in_shift = in_scale = None

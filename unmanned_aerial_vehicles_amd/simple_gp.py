@@ -299,7 +299,9 @@ class SimpleQuadrotorGP:
             print("GP horizon propagation: the model is not trained - nominal trajectory and covariance")
             return _pg.horizon_layout(*_pg.nominal_horizon(nominal, lin, Sigma0, process_noise), single)
         try:
-            traj, Sigma = self.gp_model.propagate(state, U, lin, Sigma0=Sigma0, process_noise=process_noise)
+            # (a SparseGP model: its one-call chain where it applies, the host loop otherwise)
+            traj, Sigma = self.gp_model.propagate(state, U, lin, Sigma0=Sigma0, process_noise=process_noise,
+                                                  route=_pg.wrapper_route(self.gp_model))
             if not (np.isfinite(traj).all() and np.isfinite(Sigma).all()):
                 raise FloatingPointError("non-finite trajectory or covariance")
             self.prediction_count += R * N

@@ -472,14 +472,34 @@ class SparseGP:
     def propagate(self, x0, U, lin, Sigma0=None, process_noise=None, var_includes_noise=False, return_stages=False,
                   route="auto"):
         """`GaussianProcessRegressor.propagate` on the sparse posterior: the mean rollout with the linearised state covariance,
-        same arguments and results.  The sparse model has no one-call device chain for it: whatever `route` says ("auto" or
-        "host"), the recursion runs as a host loop over `predict_jacobian(..., return_var=True)`, one call and one
-        synchronisation per stage."""
+        same arguments and results.  route="auto" and "host": the recursion as a host loop over
+        `predict_jacobian(..., return_var=True)`, one call and one synchronisation per stage.  route="chain": ONE C call per
+        horizon (`gpk_sparse_propagate`: three launches per stage, one synchronisation; with var_includes_noise=True the stage
+        quantities have the bits of `predict_jacobian(q, return_var=True)` at the returned rows; with False the latent
+        variance is kss = sf2 clipped at 1e-10 y_std^2 where the loop forms max(noisy - level, 0) - a difference in rounding
+        while neither clip is active).  ValueError where `propagate_ok()` does not hold, with the reason, or where the entry
+        refuses its arguments, with the library's message."""
         from . import propagate as _pg
-        if route not in ("auto", "host"):
-            raise ValueError("route must be 'auto' or 'host'")
+        _pg.check_route(route, ("auto", "host", "chain"))
         P, D = self.n_outputs_, self.n_features_in_
         x0, U, lin, S0, Q, R, H = _pg.check_horizon(x0, U, lin, P, D, Sigma0, process_noise)
+        if route == "chain":
+            why = self._propagate_refusal()
+            if why:
+                raise ValueError(f"route='chain' is not available: {why}")
+            self._ensure()
+            traj, Sigma = np.empty((H + 1, R, P)), np.empty((H + 1, R, P, P))
+            mean, var, jac = (np.empty((H, R, P)), np.empty((H, R, P)), np.empty((H, R, P, D))) if return_stages else (None,) * 3
+            try:
+                self._backend().call("gpk_sparse_propagate", int(bool(var_includes_noise)), _ptr(x0), x0.shape[0],
+                                     _ptr(U) if D > P else None, U.shape[0], _ptr(lin), _ptr(S0),
+                                     1 if S0 is None else S0.shape[0], _ptr(Q), R, H, _ptr(traj), _ptr(Sigma), _ptr(mean),
+                                     _ptr(var), _ptr(jac))
+            except _lib.GPKError as e:      # a limit of the entry: the caller's arguments, with the library's message
+                if e.code == _lib.GPK_BAD_ARG:
+                    raise ValueError(str(e)) from None
+                raise
+            return (traj, Sigma, {"mean": mean, "var": var, "jac": jac}) if return_stages else (traj, Sigma)
         noise = self.kernel_.components().noise or 0.0
         std2 = np.broadcast_to(np.asarray(self._y_train_std, dtype=np.float64).reshape(-1), (P,)) ** 2
 
@@ -492,6 +512,18 @@ class SparseGP:
 
         traj, Sigma, stages = _pg.host_loop(stage, list(range(P)), x0, U, lin, S0, Q, R, H)
         return (traj, Sigma, stages) if return_stages else (traj, Sigma)
+
+    def _propagate_refusal(self):
+        """Why the one-call chain does not apply (a string), or None where it does."""
+        from . import propagate as _pg
+        if int(self._backend().options.get("small_path", 1)) == 0:
+            return "the backend option small_path is 0"
+        return _pg.chain_sizes_ok(self.inducing_.shape[0], self.n_features_in_, self.n_outputs_)
+
+    def propagate_ok(self):
+        """The one-call horizon propagation (`gpk_sparse_propagate`, route="chain") applies: the small-batch path is on and
+        the sizes are within its limits (at most 16 384 padded inducing points, P <= D <= 16)."""
+        return self._propagate_refusal() is None
 
     def sample_paths(self, n_paths, n_features=1024, random_state=0):
         """`n_paths` posterior function draws as explicit functions, conditioned on the inducing variables

@@ -13,6 +13,7 @@ import ctypes as C
 
 import numpy as np
 
+from . import _lib
 from .device import check_queries
 from .gpr import cholesky_draws
 from .sparse import SparseGP, _ptr
@@ -142,17 +143,54 @@ class BatchedSparseGP:
     def propagate(self, x0, U, lin, coord=None, in_scaler=None, Sigma0=None, process_noise=None, var_includes_noise=False,
                   return_stages=False, out_scaler=None, route="auto"):
         """`BatchedARDGP.propagate` on the sparse posteriors: the batch's mean rollout with the linearised state covariance in
-        raw units, same arguments and results.  The sparse models have no one-call device chain for it: whatever `route` says
-        ("auto" or "host"), the recursion runs as a host loop over `predict_jacobian(..., return_var=True)` - one C call for
-        all models and one synchronisation per stage."""
+        raw units, same arguments and results.  route="auto" and "host": the recursion as a host loop over
+        `predict_jacobian(..., return_var=True)` - one C call for all models and one synchronisation per stage.
+        route="chain": ONE C call per horizon for all models (`gpk_sparse_propagate_multi`: three launches per stage, one
+        synchronisation; the scalers go into the call; the latent variance as `SparseGP.propagate` describes it).  ValueError
+        where `propagate_ok()` does not hold, with the reason, or where the entry refuses its arguments."""
         from . import propagate as _pg
         B, D = len(self.models), self.n_features_in_
         x0, U, lin, S0, Q, R, H, coord, in_shift, in_scale, o_mean, o_scale = _pg.check_batch(
-            B, D, x0, U, lin, coord, in_scaler, out_scaler, Sigma0, process_noise, route)
+            B, D, x0, U, lin, coord, in_scaler, out_scaler, Sigma0, process_noise, route, routes=("auto", "host", "chain"))
+        if route == "chain":
+            nx = lin.shape[0]
+            why = self._propagate_refusal(nx)
+            if why:
+                raise ValueError(f"route='chain' is not available: {why}")
+            traj, Sigma = np.empty((H + 1, R, nx)), np.empty((H + 1, R, nx, nx))
+            mean, var, jac = (np.empty((H, R, B)), np.empty((H, R, B)), np.empty((H, R, B, D))) if return_stages else (None,) * 3
+            cd = (C.c_int * B)(*coord)
+            scaled = out_scaler is not None
+            om = np.ascontiguousarray(o_mean, dtype=np.float64) if scaled else None
+            osc = np.ascontiguousarray(o_scale, dtype=np.float64) if scaled else None
+            try:
+                with self._serving() as (be, handles):
+                    be.call("gpk_sparse_propagate_multi", B, handles, int(bool(var_includes_noise)), nx, cd, _ptr(in_shift),
+                            _ptr(in_scale), _ptr(om), _ptr(osc), _ptr(x0), x0.shape[0], _ptr(U) if D > nx else None, U.shape[0],
+                            _ptr(lin), _ptr(S0), 1 if S0 is None else S0.shape[0], _ptr(Q), R, H, _ptr(traj), _ptr(Sigma),
+                            _ptr(mean), _ptr(var), _ptr(jac))
+            except _lib.GPKError as e:      # a limit of the entry: the caller's arguments, with the library's message
+                if e.code == _lib.GPK_BAD_ARG:
+                    raise ValueError(str(e)) from None
+                raise
+            return (traj, Sigma, {"mean": mean, "var": var, "jac": jac}) if return_stages else (traj, Sigma)
         stage = _pg.batch_stage(self.predict_jacobian, _pg.noise_levels(self.models), in_shift, in_scale, o_mean, o_scale,
                                 var_includes_noise)
         traj, Sigma, stages = _pg.host_loop(stage, coord, x0, U, lin, S0, Q, R, H)
         return (traj, Sigma, stages) if return_stages else (traj, Sigma)
+
+    def _propagate_refusal(self, nx=None):
+        """Why the one-call chain does not apply (a string), or None where it does; nx: the state width (default B)."""
+        from . import propagate as _pg
+        if int(self.models[0]._backend().options.get("small_path", 1)) == 0:
+            return "the backend option small_path is 0"
+        return _pg.chain_sizes_ok(self.models[0].inducing_.shape[0], self.n_features_in_, len(self.models) if nx is None else nx)
+
+    def propagate_ok(self):
+        """The one-call horizon propagation (`gpk_sparse_propagate_multi`, route="chain") applies: the small-batch path of the
+        serving backend (the first model's) is on and the sizes are within its limits (at most 16 384 padded inducing points,
+        B <= nx <= D <= 16)."""
+        return self._propagate_refusal() is None
 
     def sample_y(self, Xq, n_samples=1, random_state=0):
         """Draws from every model's joint posterior at the rows Xq: (M, B, n_samples), through the Cholesky factor of each

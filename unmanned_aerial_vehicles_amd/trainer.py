@@ -572,7 +572,8 @@ class PreTrainedGP:
         with mu_i = sy_i.mean_ + sy_i.scale_ m_i((q - sx.mean_) / sx.scale_), var_i its variance and A_k = I + lin[:, :6] + the
         rows d mu_i / d x.  Models that share inputs and scaler (those `GPTrainer` writes): ONE call for the horizon
         (`BatchedARDGP.propagate`: the shared input scaler and each model's target scaler; a file of sparse models:
-        `BatchedSparseGP.propagate`, a host loop with one call for all models per stage); otherwise the same recursion model by
+        `BatchedSparseGP.propagate`, its one-call chain where `propagate_ok()` holds, else a host loop with one call for all
+        models per stage); otherwise the same recursion model by
         model over `predict_residual_jacobian_batch`.  The variances are the latent functions' on both routes.  state (6,);
         U_guess (4, N) -> X (6, N + 1), Sigma (N + 1, 6, 6); U_guess (R, 4, N) -> (R, 6, N + 1), (R, N + 1, 6, 6).  A residual
         without a model leaves its coordinate nominal.  Not loaded, or any failure (printed): the nominal trajectory and
@@ -589,7 +590,8 @@ class PreTrainedGP:
                 traj, Sigma = bg.propagate(state, U, lin, coord=[OUTPUT_NAMES.index(n) for n in names],
                                            in_scaler=self.scalers_X[names[0]], Sigma0=Sigma0, process_noise=process_noise,
                                            out_scaler=([float(np.ravel(s.mean_)[0]) for s in sys_],
-                                                       [float(np.ravel(s.scale_)[0]) for s in sys_]))
+                                                       [float(np.ravel(s.scale_)[0]) for s in sys_]),
+                                           route=_pg.wrapper_route(bg))
             else:
                 coord = [i for i, n in enumerate(OUTPUT_NAMES) if n in self.gp_models]
                 x0, Uc, linc, S0, Q, R, H = _pg.check_horizon(state, U, lin, 6, 10, Sigma0, process_noise)
