@@ -474,6 +474,66 @@ GPK_API int gpk_predict_mean_grad_multi(gpk_handle h, const double* X, const dou
 GPK_API int gpk_predict_batched_grad(gpk_handle h, const double* Xq, int64_t M, double* mean, double* var, double* dmean,
                                      double* dvar, int var_includes_noise);
 
+/* ---- K8, second derivatives: the input Hessian of the posterior mean (fp64) -----------------------------------------------
+ * With q = xq_m / ls, r_j = x_j / ls, delta_j = q - r_j (exact differences, formed before any product) and
+ * k_j = sf2 exp(-|delta_j|^2 / 2) (no White term):
+ *   T_p[d][e] = sum_j k_j alpha[j][p] delta_jd delta_je,   S_p = sum_j k_j alpha[j][p]
+ *   hess[m][p][d][e] = y_std[p] / (ls_d ls_e) (T_p[d][e] - [d = e] S_p)            (un-normalised, the units of dmean)
+ * hess holds the full D x D block per (query, output); both triangles are written from ONE sum: hess[m][p][d][e] and
+ * hess[m][p][e][d] have the same bits.  A null hess is GPK_BAD_ARG; every refusal happens before any launch.
+ * gpk_predict_mean_hess: one fused launch in the tiling of gpk_predict_mean_grad (training rows through LDS already divided
+ *   by ls, one exp per pair) + the fixed-order reduction of the training chunks (no floating-point atomics: bit-identical from
+ *   run to run).  The D (D + 1) / 2 + 1 running sums per (query, output) are split over the third grid dimension into output
+ *   groups and blocks of whole rows of the triangle (<= 64 fp64 accumulators per thread, no scratch); a group recomputes the
+ *   pair's kernel value.  The chunks' partial sums stay within 256 MiB: fewer chunks, then smaller query panels.
+ *   X dev (N x D), alpha dev (N x P), Xq dev (M x D), hess dev (M x P x D x D); ls, y_std host.  D, P <= 16, any M.
+ * gpk_predict_host_hess: the one-call serving form, arguments as gpk_predict_host_grad without the variance ones: host
+ *   queries in (M x D), mean_host (M x P), dmean_host (M x P x D) and hess_host (M x P x D x D) out, one synchronisation,
+ *   queries and results through the handle's pinned, mapped block.  1 <= M <= GPK_HOST_MAX_M.  mean and dmean come from the
+ *   launches of gpk_predict_host_grad and have its bits.  Up to 32 queries (D, P <= 16, N <= 16384): TWO launches and no copy
+ *   command - small_cross_mean_jac_kernel, untouched, then small_hess_kernel: a workgroup forms the share of T and S of its
+ *   max(32, Np / 64) training rows for a slice of about 512 entries, the last workgroup of every slice (its own ticket, left
+ *   at zero) adds that slice of the shares in workgroup order and writes the Hessians straight into the pinned block; the
+ *   grouping depends on (Np, M, P, D) alone.  33 .. GPK_HOST_MAX_M queries, and option small_path = 0 (the cross-check): one
+ *   query upload and the general blocks gpk_predict_mean, gpk_predict_mean_grad, gpk_predict_mean_hess (6 launches).
+ * gpk_predict_host_multi_hess: B (<= 8) single-output ARD models on one query batch, arguments and limits as
+ *   gpk_predict_host_multi_grad without the variance ones; mean_host (B x M), dmean_host (B x M x D), hess_host
+ *   (B x M x D x D).  The two launches of gpk_predict_host_hess with the model as a grid dimension - TWO launches and one
+ *   synchronisation for all models, every model with its own shares and tickets: block b has the bits of model b served alone
+ *   (B = 1: the bits of gpk_predict_host_hess).  Option small_path = 0: the general blocks, model by model (a cross-check).
+ * gpk_predict_model_hess: the composite on the model of gpk_fit / gpk_import, host fp64 buffers: Xq (M x D), mean (M x P),
+ *   dmean (M x P x D), hess (M x P x D x D).  Any M (query blocks whose Hessians stay within 32 MiB of pinned memory).
+ * Replaces: nothing in the reference - scikit-learn has no derivative call.  A caller would difference
+ *   GaussianProcessRegressor.predict (sklearn/gaussian_process/_gpr.py:441-494) twice; within this library, 2 D (fourth
+ *   order: 4 D) gpk_predict_host_grad calls, each with its own synchronisation.                                            */
+GPK_API int gpk_predict_mean_hess(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
+                                  double sf2, const double* y_std, const double* Xq, int64_t M, double* hess);
+GPK_API int gpk_predict_host_hess(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
+                                  double sf2, const double* y_mean, const double* y_std, const double* Xq_host, int64_t M,
+                                  double* mean_host, double* dmean_host, double* hess_host);
+GPK_API int gpk_predict_host_multi_hess(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N,
+                                        int D, const double* ls, const double* sf2, const double* y_mean, const double* y_std,
+                                        const double* Xq_host, int64_t M, double* mean_host, double* dmean_host,
+                                        double* hess_host);
+GPK_API int gpk_predict_model_hess(gpk_handle h, const double* Xq, int64_t M, double* mean, double* dmean, double* hess);
+/* gpk_predict_mean_hess_multi: the Hessian companion of gpk_predict_mean_grad_multi for B (<= 8) single-output ARD models on
+ *   shared inputs, any M, arguments as that entry: X (N x D), alpha (N x B, column b = model b), Xq (M x D) dev; ls host (B x D);
+ *   sf2, y_std host double[B]; hess dev (M x B x D x D).  One fused launch: the raw feature differences of a pair and each
+ *   product of two of them are formed once and serve every model's distance and every model's sums (1 / ls^2 weights in LDS,
+ *   the factor 1 / (ls_bd ls_be) applied by the reduction); the models in groups of two (D <= 4: up to four) and the triangle in
+ *   blocks of whole rows over the third grid dimension (<= 64 fp64 accumulators, no scratch); the training chunks added in
+ *   chunk order, both triangles written from one sum.  One launch pair instead of B - but measured SLOWER than B
+ *   gpk_predict_mean_hess launches at M = 4096 (B = 6, D = 10: 0.90 x at N = 4096, 0.83 x at N = 16384; D = 16: 0.60 x;
+ *   DESIGN.md, K8, second derivatives): every (model group, row block) recomputes the models' distances and exp.
+ * gpk_predict_batched_hess: the composite on the object of gpk_fit_batched, host fp64 buffers: Xq (M x D), mean (M x B), dmean
+ *   (M x B x D), hess (M x B x D x D).  Up to 32 queries (N <= 16384): gpk_predict_host_multi_hess; larger batches in panels:
+ *   gpk_predict_mean_multi + gpk_predict_mean_grad_multi (the bits of gpk_predict_batched_grad) and
+ *   gpk_predict_mean_hess_multi.  Any M.                                                                                   */
+GPK_API int gpk_predict_mean_hess_multi(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int B,
+                                        const double* ls, const double* sf2, const double* y_std, const double* Xq, int64_t M,
+                                        double* hess);
+GPK_API int gpk_predict_batched_hess(gpk_handle h, const double* Xq, int64_t M, double* mean, double* dmean, double* hess);
+
 /* ---- K6a: log-marginal-likelihood terms -----------------------------------------------------
  * terms[0] = sum_{i<N} log L[i][i]; terms[1 + p] = sum_i Y[i][p] * alpha[i][p]  (host doubles).
  * Synchronises.  Replaces: sklearn/gaussian_process/_gpr.py:609-613; gaussian_process.py:250-261. */
@@ -829,6 +889,19 @@ GPK_API int gpk_sparse_predict_multi_grad(gpk_handle h, int B, const gpk_handle*
                                           double* var, double* dmean, double* dvar, int var_includes_noise);
 GPK_API int gpk_sparse_predict_multi_cov(gpk_handle h, int B, const gpk_handle* models, const double* Xq, int64_t M, double* mean,
                                          double* cov);
+/* The input Hessian of the sparse posterior mean (K8, second derivatives).  The sparse mean is that of an exact model over
+ * (Z, alpha_u) and its Hessian involves no inverse factor, so these are gpk_predict_model_hess on the inducing inputs:
+ * gpk_sparse_predict_hess: host fp64 buffers Xq (M x D), mean (M x P), dmean (M x P x D), hess (M x P x D x D); mean and dmean
+ *   have the bits of gpk_sparse_predict_grad.  Up to 32 queries: the two launches of gpk_predict_host_hess on (Z, alpha_u),
+ *   one synchronisation; larger batches in query panels of the general blocks.  Any M.
+ * gpk_sparse_predict_multi_hess: B (<= 8) single-output sparse models as gpk_sparse_predict_multi_grad takes them, each with
+ *   its own inducing inputs; mean (M x B), dmean (M x B x D), hess (M x B x D x D); column b has the bits of models[b] alone.
+ *   Up to 32 queries: the same two launches for all models (the model grid dimension, per-model basis points); larger
+ *   batches model by model.
+ * A null hess is GPK_BAD_ARG.  Replaces: nothing in the reference; within this library 2 D gpk_sparse_predict_grad calls.  */
+GPK_API int gpk_sparse_predict_hess(gpk_handle h, const double* Xq, int64_t M, double* mean, double* dmean, double* hess);
+GPK_API int gpk_sparse_predict_multi_hess(gpk_handle h, int B, const gpk_handle* models, const double* Xq, int64_t M, double* mean,
+                                          double* dmean, double* hess);
 GPK_API int gpk_sparse_bound(gpk_handle h, double* bound, int64_t* n_rows);
 GPK_API int gpk_sparse_export(gpk_handle h, int64_t* m, int* D, int* P, int* n_ls, double* Z, double* G, double* g, double* yy,
                               int64_t* n_rows, double* ls, double* hyper, double* y_mean, double* y_std);

@@ -109,6 +109,15 @@ SIGNATURES = {
                                            _i64, _vp, _vp, _vp, _vp]),
     "gpk_predict_mean_grad_multi": (_int, [_vp, _vp, _vp, _i64, _int, _int, _dp, _dp, _dp, _vp, _i64, _vp]),
     "gpk_predict_batched_grad": (_int, [_vp, _dp, _i64, _dp, _dp, _dp, _dp, _int]),
+    # the mean's input Hessian: the gradient entries' arguments without the variance ones, hess last
+    "gpk_predict_mean_hess": (_int, [_vp, _vp, _vp, _i64, _int, _int, _dp, _dbl, _dp, _vp, _i64, _vp]),
+    "gpk_predict_host_hess": (_int, [_vp, _vp, _vp, _i64, _int, _int, _vp, _dbl, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "gpk_predict_host_multi_hess": (_int, [_vp, _int, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "gpk_predict_mean_hess_multi": (_int, [_vp, _vp, _vp, _i64, _int, _int, _dp, _dp, _dp, _vp, _i64, _vp]),
+    "gpk_predict_model_hess": (_int, [_vp, _dp, _i64, _dp, _dp, _dp]),
+    "gpk_predict_batched_hess": (_int, [_vp, _dp, _i64, _dp, _dp, _dp]),
+    "gpk_sparse_predict_hess": (_int, [_vp, _dp, _i64, _dp, _dp, _dp]),
+    "gpk_sparse_predict_multi_hess": (_int, [_vp, _int, C.POINTER(_vp), _dp, _i64, _dp, _dp, _dp]),
     "gpk_lml_terms": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _int, _dp]),
     "gpk_potri": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),
     "gpk_lml_grad": (_int, [_vp, _vp, _i64, _int, _dp, _dbl, _dbl, _vp, _int, _vp, _i64, _dp]),

@@ -526,6 +526,53 @@ class BatchedARDGP:
             var[:, b], dvar[:, b, :] = v.cpu().numpy() * s2, g.cpu().numpy() * s2
         return mean, dmean, var, dvar
 
+    # ------------------------------------------------------------------ second derivatives of the means (K8, per-axis batch)
+    def predict_host_hess(self, Xq):
+        """<= 32 rows, all models, one C call (`gpk_predict_host_multi_hess`: mean + Jacobian of every model in the one launch
+        of `predict_host_grad`, then the small-batch Hessian launch for all models: two launches, one synchronisation): (mean (M, B), dmean (M, B, D),
+        hess (M, B, D, D)).  None if the models do not qualify (the conditions of `_serve_state`).  Always fp64."""
+        st = self._host_queries(Xq, want_W=False, any_dtype=True, row_gate=True)
+        if st is None:
+            return None
+        sv, Xq, M = st
+        B, d0 = sv["B"], sv["dev0"]
+        D = d0.D
+        mean, dmean, hess = np.empty((B, M)), np.empty((B, M, D)), np.empty((B, M, D, D))
+        d0.be.call("gpk_predict_host_multi_hess", B, sv["X"], sv["alpha"], d0.N, D, sv["ls"].ctypes.data, sv["sf2"].ctypes.data,
+                   sv["ym"].ctypes.data, sv["ys"].ctypes.data, _hp(Xq), M, _hp(mean), _hp(dmean), _hp(hess))
+        return mean.T, dmean.transpose(1, 0, 2), hess.transpose(1, 0, 2, 3)
+
+    def predict_hessian(self, Xq):
+        """Posterior means of all B models with their first and second input derivatives: (mean (M, B), dmean (M, B, D),
+        hess (M, B, D, D)); mean and dmean are those of `predict_jacobian(Xq)` bit for bit, every D x D block of hess is
+        symmetric bit for bit.  Up to 32 rows: one C call (`predict_host_hess`), in which column b has the bits of model b
+        served alone through the same call; larger batches (whose chunking depends on B: column b agrees with model b alone to
+        rounding, not bit for bit): the fused launches of `predict_jacobian` and the fused Hessian launch
+        (`gpk_predict_mean_hess_multi`: the feature differences of a pair and their products formed once for all models).
+        Always fp64, as `GaussianProcessRegressor.predict_hessian`."""
+        Xq = check_queries(Xq)
+        if 1 <= Xq.shape[0] <= self.SERVE_MAX_M:
+            out = self.predict_host_hess(Xq)
+            if out is not None:
+                return out
+        return self._predict_hessian_large(Xq)
+
+    def _predict_hessian_large(self, Xq):
+        mean, dmean = self._predict_jacobian_large(Xq)
+        be = get_backend(self.device)
+        import torch
+        q = be.upload(np.ascontiguousarray(Xq, dtype=np.float64), torch.float64)
+        if not self._shared_inputs():      # nothing to fuse: one call per model on its own inputs
+            hess = np.stack([m._dev.predict_mean_hess_dev(q, m._y_train_std).cpu().numpy()[:, 0] for m in self.models], axis=1)
+            return mean, dmean, hess
+        f = self._fused64()
+        M, B, D = q.shape[0], len(self.models), f["D"]
+        hess_d = be.empty((M, B, D, D), torch.float64)
+        if M > 0:
+            be.call("gpk_predict_mean_hess_multi", _p(f["X"]), _p(f["alpha"]), f["N"], D, B, _hp(f["ls"]), _hp(f["sf2"]),
+                    _hp(f["ys"]), _p(q), M, _p(hess_d))
+        return mean, dmean, hess_d.cpu().numpy()
+
     # ------------------------------------------------------------------ joint posterior (K7, per-axis batch)
     def predict_host_cov(self, Xq):
         """<= 32 rows, all models, one C call (`gpk_predict_host_multi_cov`: two launches and one synchronisation for all of

@@ -267,6 +267,52 @@ extern "C" int gpk_predict_batched_grad(gpk_handle h, const double* Xq, int64_t 
   });
 }
 
+extern "C" int gpk_predict_batched_hess(gpk_handle h, const double* Xq, int64_t M, double* mean, double* dmean, double* hess) {
+  if (!h) return GPK_BAD_ARG;
+  GPK_REQUIRE(h, hess != nullptr, "predict_batched_hess: hess is null");
+  gpk_bmodel* m = h->bmodel;
+  GPK_REQUIRE(h, m && m->fitted, "predict_batched_hess: no model (call gpk_fit_batched first)");
+  GPK_REQUIRE(h, Xq && mean && dmean && M >= 1, "predict_batched_hess: null pointer or empty batch");
+  GPK_CHECK_HIP(h, hipSetDevice(h->device));
+  const int B = m->B, D = m->D;
+  GPK_TRY(gpk_require_finite(h, Xq, M * D, "predict_batched_hess", "Xq"));
+  // control-loop batches: one call for all models
+  if (m->small(M)) {
+    std::vector<double> mb((size_t)B * M), jb((size_t)B * M * D), hb((size_t)B * M * D * D);
+    GPK_TRY(gpk_predict_host_multi_hess(h, B, m->Xs, m->as, m->N, D, m->ls, m->sf2, m->y_mean, m->y_std, Xq, M, mb.data(), jb.data(),
+                                        hb.data()));
+    gpk_interleave(mb.data(), B, M, 1, mean);
+    gpk_interleave(jb.data(), B, M, D, dmean);
+    gpk_interleave(hb.data(), B, M, D * D, hess);
+    return GPK_OK;
+  }
+  // larger batches in the query panels of gpk_predict_batched_grad: its two fused launches for means and Jacobians (their bits);
+  // inside a panel the Hessians of all models in blocks of at most 64 MiB, one fused launch each
+  const int64_t panel = gpk_panel_rows(6ull << 30, (size_t)3 * m->Np * 8, M);
+  int64_t hrows = gpk_panel_rows(64ull << 20, (size_t)B * D * D * 8, M);
+  if (hrows > panel) hrows = panel;
+  const size_t nh1 = (size_t)hrows * D * D;
+  GPK_TRY(m->q.reserve(h, (size_t)panel * D * 8));
+  GPK_TRY(m->mean.reserve(h, ((size_t)panel * B * (D + 1) + (size_t)B * nh1) * 8));
+  const double* dq = (const double*)m->q.p;
+  double* d_mean = (double*)m->mean.p;
+  double* d_dmean = d_mean + (size_t)panel * B;
+  double* d_hess = d_dmean + (size_t)panel * B * D;      // (hrows x B x D x D)
+  return gpk_query_panels(h, Xq, M, (size_t)D * 8, panel, m->q, [&](int64_t m0, int64_t mc) -> int {
+    GPK_TRY(gpk_predict_mean_multi(h, GPK_F64, m->X, m->alphaT, m->N, D, B, m->ls, m->sf2, m->y_mean, m->y_std, dq, mc, d_mean));
+    GPK_TRY(gpk_predict_mean_grad_multi(h, m->X, m->alphaT, m->N, D, B, m->ls, m->sf2, m->y_std, dq, mc, d_dmean));
+    GPK_CHECK_HIP(h, hipMemcpyAsync(mean + (size_t)m0 * B, d_mean, (size_t)mc * B * 8, hipMemcpyDeviceToHost, h->stream));
+    GPK_CHECK_HIP(h, hipMemcpyAsync(dmean + (size_t)m0 * B * D, d_dmean, (size_t)mc * B * D * 8, hipMemcpyDeviceToHost, h->stream));
+    for (int64_t r0 = 0; r0 < mc; r0 += hrows) {
+      const int64_t rc = mc - r0 < hrows ? mc - r0 : hrows;
+      GPK_TRY(gpk_predict_mean_hess_multi(h, m->X, m->alphaT, m->N, D, B, m->ls, m->sf2, m->y_std, dq + r0 * D, rc, d_hess));
+      GPK_CHECK_HIP(h, hipMemcpyAsync(hess + (size_t)(m0 + r0) * B * D * D, d_hess, (size_t)B * rc * D * D * 8, hipMemcpyDeviceToHost,
+                                      h->stream));
+    }
+    return GPK_OK;
+  });
+}
+
 extern "C" int gpk_predict_batched_cov(gpk_handle h, const double* Xq, int64_t M, double* mean, double* cov) {
   if (!h) return GPK_BAD_ARG;
   gpk_bmodel* m = h->bmodel;

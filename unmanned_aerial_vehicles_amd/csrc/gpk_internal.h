@@ -278,11 +278,12 @@ struct ServeModels {
 // units in both forms.  var and dvar come together in a gradient call.
 struct ServeOut {
   double *mean, *var, *dmean, *dvar, *cov;
+  double* hess;      // (B, M, P, D, D) un-normalised, every D x D block symmetric bit for bit (GPK_SMALL_HESS)
 };
 bool gpk_small_ok(int64_t Np, int D, int P, int64_t M);
 // doubles of device work area (`work`) that a call of the given kind needs: per model K* (32 x Np) + the workgroups' shares
 // (F inverse factors per model: K*, the mean and the Jacobian shares stay one set per model)
-enum { GPK_SMALL_PREDICT, GPK_SMALL_COV, GPK_SMALL_GRAD, GPK_SMALL_JACVAR };
+enum { GPK_SMALL_PREDICT, GPK_SMALL_COV, GPK_SMALL_GRAD, GPK_SMALL_JACVAR, GPK_SMALL_HESS };
 size_t gpk_small_work_doubles(int call, int64_t Np, int B, int64_t M, int D, int P, int F);
 // The launches of one call on M <= GPK_SMALL_MAX_M queries, no synchronisation; Xq and the outputs may be pinned, mapped host
 // memory.  The launch counts are those of one model with one output for every B, P and F:
@@ -290,6 +291,8 @@ size_t gpk_small_work_doubles(int call, int64_t Np, int B, int64_t M, int D, int
 //   GPK_SMALL_GRAD     mean + dmean: 1 launch; with out.var and out.dvar 3
 //   GPK_SMALL_COV      mean + cov (m.noise on the diagonal, not clipped): 2 launches
 //   GPK_SMALL_JACVAR   mean + dmean + var (a stage of the propagation chains, gpk_propagate_run): 2 launches, the bits of GPK_SMALL_GRAD's
+//   GPK_SMALL_HESS     mean + dmean + hess (no inverse factor is read; out.var / out.dvar null): GPK_SMALL_GRAD's one launch, untouched
+//                      (its bits), then small_hess_kernel: 2 launches
 // Block b of every output has the bits of model b served alone.
 int gpk_small_launch(gpk_handle h, int call, const ServeModels& m, const double* Xq, int64_t M, double* work, const ServeOut& out);
 // ---- horizon propagation (gpk_propagate.hip): what the entries of the exact models and of the sparse models (gpk_sparse.hip) share
@@ -326,6 +329,11 @@ int gpk_serve_cov(gpk_handle h, const ServeModels& m, bool small, const double* 
                   double* cov_host);
 int gpk_serve_grad(gpk_handle h, const ServeModels& m, bool small, const double* Xq_host, int64_t M, double* mean_host,
                    double* var_host, double* dmean_host, double* dvar_host);
+// mean (B, M, P), dmean (B, M, P, D) with the bits of gpk_serve_grad's, and the mean's input Hessian (B, M, P, D, D).  small:
+// GPK_SMALL_HESS, two launches for all models; otherwise one upload and the general blocks, model by model.  No inverse factor
+// is read (F = 1 or 2)
+int gpk_serve_hess(gpk_handle h, const ServeModels& m, bool small, const double* Xq_host, int64_t M, double* mean_host,
+                   double* dmean_host, double* hess_host);
 // Sigma (Mp x ldc, symmetric bit for bit) = K(Xq, Xq) + noise I - VA^T VB from two operands (rows x Mp each, ld Mp) whose
 // product is symmetric (gpk_cov.hip: the covariance epilogue of the tile GEMM; VA == VB: the exact model's covariance)
 int gpk_cov_from_v(gpk_handle h, const double* VA, const double* VB, int64_t rows, const double* Xq, int64_t M, int D,

@@ -433,6 +433,27 @@ extern "C" int gpk_predict_model_grad(gpk_handle h, const double* Xq, int64_t M,
   return GPK_OK;
 }
 
+extern "C" int gpk_predict_model_hess(gpk_handle h, const double* Xq, int64_t M, double* mean, double* dmean, double* hess) {
+  if (!h) return GPK_BAD_ARG;
+  GPK_REQUIRE(h, hess != nullptr, "predict_model_hess: hess is null");
+  gpk_model* m = h->model;
+  GPK_REQUIRE(h, m && m->fitted, "predict_model_hess: no model (call gpk_fit or gpk_import first)");
+  GPK_REQUIRE(h, Xq && mean && dmean && M >= 1, "predict_model_hess: null pointer or empty batch");
+  GPK_CHECK_HIP(h, hipSetDevice(h->device));
+  const int D = m->D, P = m->P;
+  GPK_TRY(gpk_require_finite(h, Xq, M * D, "predict_model_hess", "Xq"));
+  // query blocks whose Hessians stay within 32 MiB of the pinned block: a multiple of 32 rows, at most GPK_HOST_MAX_M
+  int64_t rows = (int64_t)((32u << 20) / ((size_t)P * D * D * sizeof(double))) / 32 * 32;
+  if (rows > GPK_HOST_MAX_M) rows = GPK_HOST_MAX_M;
+  if (rows < 32) rows = 32;
+  for (int64_t m0 = 0; m0 < M; m0 += rows) {
+    const int64_t mc = M - m0 < rows ? M - m0 : rows;
+    GPK_TRY(gpk_predict_host_hess(h, m->X, m->alpha, m->N, D, P, m->ls, m->sf2, m->y_mean, m->y_std, Xq + m0 * D, mc, mean + m0 * P,
+                                  dmean + m0 * P * D, hess + m0 * P * D * D));
+  }
+  return GPK_OK;
+}
+
 extern "C" int gpk_lml(gpk_handle h, const double* theta, int n_theta, double* lml, double* grad) {
   if (!h) return GPK_BAD_ARG;
   gpk_model* m = h->model;

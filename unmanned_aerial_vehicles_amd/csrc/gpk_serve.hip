@@ -197,6 +197,73 @@ int gpk_serve_grad(gpk_handle h, const ServeModels& m, bool small, const double*
   return s.finish();
 }
 
+// Mean (B, M, P), its Jacobian (B, M, P, D) and its Hessian (B, M, P, D, D).  Mean and Jacobian exactly as gpk_serve_grad forms
+// them without the variance, so they keep its bits.  small: GPK_SMALL_HESS - that one launch for all models, then
+// small_hess_kernel, both reading the queries from the pinned block: two launches, no copy command.  Otherwise the general
+// blocks, model by model, on the queries uploaded once.  Every refusal of the blocks is checked here first: nothing is launched
+// for a call that fails.
+int gpk_serve_hess(gpk_handle h, const ServeModels& m, bool small, const double* Xq_host, int64_t M, double* mean_host,
+                   double* dmean_host, double* hess_host) {
+  GPK_REQUIRE(h, hess_host != nullptr, "serving: hess is null");
+  GPK_REQUIRE(h, m.D >= 1 && m.D <= GPK_MAX_D_PREDICT && m.P >= 1 && m.P <= GPK_MAX_P, "serving: D <= 16, P <= 16");
+  for (int i = 0; i < m.B * m.D; ++i) GPK_REQUIRE(h, m.ls[i] > 0.0, "serving: length-scales must be positive");
+  const int64_t Npad = gpk_padded(m.N);
+  const size_t nm = (size_t)M * m.P, njm = nm * m.D, nh = njm * m.D;     // per model
+  ServeOut o{};
+  double* ohess = nullptr;
+  Serve s(h, Xq_host, M, m.D);
+  s.out(mean_host, m.B * nm, &o.mean);
+  s.out(dmean_host, m.B * njm, &o.dmean);
+  s.out(hess_host, m.B * nh, &ohess);
+  GPK_TRY(s.begin(small ? gpk_small_work_doubles(GPK_SMALL_HESS, Npad, m.B, M, m.D, m.P, m.F) : 0));
+  if (small) {      // two launches for all models, the queries read from the pinned block
+    const ServeOut req{o.mean, nullptr, o.dmean, nullptr, nullptr, ohess};
+    GPK_TRY(gpk_small_launch(h, GPK_SMALL_HESS, m, s.hq, M, s.dwork, req));
+    return s.finish();
+  }
+  GPK_TRY(s.upload());
+  for (int b = 0; b < m.B; ++b) {
+    const double* ls = m.ls + b * m.D;
+    GPK_TRY(gpk_predict_mean(h, GPK_F64, m.X[b], m.alpha[b], m.N, m.D, m.P, ls, m.sf2[b], m.y_mean + b * m.P, m.y_std + b * m.P,
+                             s.dq, M, o.mean + b * nm));
+    GPK_TRY(gpk_predict_mean_grad(h, m.X[b], m.alpha[b], m.N, m.D, m.P, ls, m.sf2[b], m.y_std + b * m.P, s.dq, M, o.dmean + b * njm));
+    GPK_TRY(gpk_predict_mean_hess(h, m.X[b], m.alpha[b], m.N, m.D, m.P, ls, m.sf2[b], m.y_std + b * m.P, s.dq, M, ohess + b * nh));
+  }
+  return s.finish();
+}
+
+extern "C" int gpk_predict_host_hess(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P,
+                                     const double* ls, double sf2, const double* y_mean, const double* y_std,
+                                     const double* Xq_host, int64_t M, double* mean_host, double* dmean_host, double* hess_host) {
+  if (!h) return GPK_BAD_ARG;
+  GPK_REQUIRE(h, hess_host != nullptr, "predict_host_hess: hess is null");
+  GPK_REQUIRE(h, X && alpha && ls && y_mean && y_std && Xq_host && mean_host && dmean_host, "predict_host_hess: null pointer");
+  GPK_REQUIRE(h, N >= 1 && M >= 1 && M <= GPK_HOST_MAX_M, "predict_host_hess: M must be in [1, GPK_HOST_MAX_M]");
+  GPK_REQUIRE(h, D >= 1 && D <= GPK_MAX_D_PREDICT && P >= 1 && P <= GPK_MAX_P, "predict_host_hess: D <= 16, P <= 16");
+  GPK_REQUIRE(h, h->batch == 1, "predict_host_hess: not available in batched mode");
+  const ServeModels m{1, P, 1, &X, &alpha, N, D, ls, &sf2, y_mean, y_std, {nullptr, nullptr}, gpk_padded(N), gpk_padded(N), nullptr,
+                      0.0, nullptr};
+  return gpk_serve_hess(h, m, h->small_path && gpk_small_ok(gpk_padded(N), D, P, M), Xq_host, M, mean_host, dmean_host, hess_host);
+}
+
+extern "C" int gpk_predict_host_multi_hess(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N,
+                                           int D, const double* ls, const double* sf2, const double* y_mean,
+                                           const double* y_std, const double* Xq_host, int64_t M, double* mean_host,
+                                           double* dmean_host, double* hess_host) {
+  if (!h) return GPK_BAD_ARG;
+  GPK_REQUIRE(h, hess_host != nullptr, "predict_host_multi_hess: hess is null");
+  GPK_REQUIRE(h, X && alpha && ls && sf2 && y_mean && y_std && Xq_host && mean_host && dmean_host,
+              "predict_host_multi_hess: null pointer");
+  GPK_REQUIRE(h, B >= 1 && B <= GPK_SMALL_MAX_MODELS, "predict_host_multi_hess: 1..8 models");
+  GPK_REQUIRE(h, N >= 1 && gpk_small_ok(gpk_padded(N), D, 1, M), "predict_host_multi_hess: needs M <= 32, D <= 16, N <= 16384");
+  GPK_REQUIRE(h, h->batch == 1, "predict_host_multi_hess: not available in batched mode");
+  for (int b = 0; b < B; ++b) GPK_REQUIRE(h, X[b] && alpha[b], "predict_host_multi_hess: null model pointer");
+  // (option small_path = 0, the cross-check of the small-batch kernels: the general building blocks, model by model)
+  const ServeModels m{B, 1, 1, X, alpha, N, D, ls, sf2, y_mean, y_std, {nullptr, nullptr}, gpk_padded(N), gpk_padded(N), nullptr, 0.0,
+                      nullptr};
+  return gpk_serve_hess(h, m, h->small_path != 0, Xq_host, M, mean_host, dmean_host, hess_host);
+}
+
 extern "C" int gpk_predict_host(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P,
                                 const double* ls, double sf2, const double* y_mean, const double* y_std,
                                 const double* W, int64_t Np, int64_t ldw, double kss, double floor_,

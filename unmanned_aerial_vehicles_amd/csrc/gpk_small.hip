@@ -30,6 +30,9 @@
 //                            every model in ONE launch and all four results in three, each model
 //                            with its own shares and its own ticket counters.
 //
+//   second derivatives (K8)  mean + Jacobian + the mean's input Hessian: small_cross_mean_jac_kernel, then small_hess_kernel (below,
+//                            with its own description): two launches for any number of models and outputs.
+//
 //   a propagation stage (K11) mean + Jacobian + variance without the variance gradient: small_cross_mean_jac_kernel, then
 //                            small_var_jac_kernel - small_var_grad_kernel's body without its store of V - and no W^T V launch: two
 //                            launches with the bits of the three-launch call (gpk_propagate.hip chains them along a horizon, the
@@ -306,6 +309,105 @@ __global__ __launch_bounds__(256) void small_cross_mean_jac_kernel(SmallK k, lon
                                                                    double* pmean, unsigned* counter, double* mean_out,
                                                                    double* pjac, double* dmean_out) {
   small_cross_mean_body<FINISH, true>(k, N, Np, D, P, Xq, M, Ks, pmean, counter, mean_out, pjac, dmean_out);
+}
+
+// ---- the mean's input Hessian (K8, second derivatives): the second launch of a GPK_SMALL_HESS call ------------------------------
+// With delta_mj = q_m - r_j (queries and rows divided by the length-scales, exact differences) and k*_mj as above:
+//   T[m][p][d][e] = sum_j k*_mj alpha_jp delta_mjd delta_mje  (e <= d),   S[m][p] = sum_j k*_mj alpha_jp
+//   hess[m][p][d][e] = hess[m][p][e][d] = y_std[p] / (ls_d ls_e) (T - [d = e] S)
+// A workgroup takes hess_rows(Np) = max(32, Np / 64) training rows - at most 64 workgroups per model, so that the last one reads
+// at most 64 shares - in rounds of HJ rows staged through LDS (K* recomputed: the first launch stores none without a variance).
+// Its share is M * P * (D (D + 1) / 2 + 1) doubles, entry t = (m * P + p) * TP + (packed (d, e), or TP - 1 for S); every entry is
+// owned by one thread, which carries it from round to round through the share itself.  The (query, output) pairs are cut into
+// slices of hess_slice(D) pairs - about 512 entries - over the third grid dimension: a workgroup forms its slice of its rows'
+// share, and the last workgroup OF A SLICE (last_of on the counter of (model, slice), left at zero) adds that slice of the
+// shares in workgroup order, one thread per (m, p, d, e <= d), and writes both triangles from the one sum - the final sums of a
+// call (2 MB of shares at M = 25, P = 6, D = 10, Np = 1024) are spread over as many workgroups as there are slices instead of
+// queueing in one.  Rows, slices and the order of every sum depend on (Np, M, P, D) alone: block b of a batch has the bits of
+// model b alone.
+constexpr int HJ = 32;
+constexpr int HT_MAX = SD * (SD + 1) / 2;      // 136 packed triangle entries at D = 16
+constexpr int HESS_SLICE_ENTRIES = 512;
+__host__ __device__ inline long long hess_rows(long long Np) { return Np / 64 < 32 ? 32 : Np / 64; }
+// (query, output) pairs per slice: whole pairs, so that a slice holds the S of its own diagonals
+__host__ __device__ inline int hess_slice(int D) { const int n = HESS_SLICE_ENTRIES / (D * (D + 1) / 2 + 1); return n < 1 ? 1 : n; }
+
+__global__ __launch_bounds__(256) void small_hess_kernel(SmallK k, long long N, long long Np, int D, int P,
+                                                         const double* __restrict__ Xq, int M, double* phess, unsigned* counter,
+                                                         double* hess_out) {
+  __shared__ double q[SQ][SD + 1];
+  __shared__ double ks[SQ][HJ + 1];
+  __shared__ double al[HJ][SP + 1];
+  __shared__ double xs[HJ][SD + 1];
+  __shared__ unsigned char td[HT_MAX + 1], te[HT_MAX + 1];
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const double* __restrict__ X = k.X[b];
+  const double* __restrict__ alpha = k.alpha[b];
+  const double* ls = k.ls[b];
+  const double sf2 = k.sf2[b];
+  const int TT = D * (D + 1) / 2, TP = TT + 1, E = M * P * TP;
+  const long long rows = hess_rows(Np);
+  const long long r0 = (long long)blockIdx.x * rows, r1 = min(N, r0 + rows);
+  double* share = phess + ((long long)b * gridDim.x + blockIdx.x) * E;
+  const int mps = hess_slice(D), mp0 = blockIdx.z * mps, mp1 = min(M * P, mp0 + mps);      // this slice's pairs (mp0 < M P)
+  const int m_lo = mp0 / P, m_hi = (mp1 - 1) / P, t0 = mp0 * TP, t1 = mp1 * TP;
+  for (int t = tid; t < TT; t += 256) {
+    int d = 0;
+    while ((d + 1) * (d + 2) / 2 <= t) ++d;
+    td[t] = (unsigned char)d;
+    te[t] = (unsigned char)(t - d * (d + 1) / 2);
+  }
+  for (int e = tid; e < M * D; e += 256) q[e / D][e % D] = Xq[e] / ls[e % D];
+  // (a workgroup past the last training row runs one empty round: its share is zeros and its ticket is taken)
+  for (long long jb = r0; jb < r1 || jb == r0; jb += HJ) {
+    __syncthreads();
+    for (int e = tid; e < HJ * D; e += 256) {
+      const int jj = e / D, d = e - jj * D;
+      xs[jj][d] = (jb + jj < r1) ? X[(jb + jj) * D + d] / ls[d] : 0.0;
+    }
+    for (int e = tid; e < HJ * P; e += 256) {
+      const int jj = e / P, p = e - jj * P;
+      al[jj][p] = (jb + jj < r1) ? alpha[(jb + jj) * P + p] : 0.0;
+    }
+    __syncthreads();
+    for (int e = tid; e < (m_hi - m_lo + 1) * HJ; e += 256) {
+      const int m = m_lo + e / HJ, jj = e % HJ;
+      double d2 = 0.0;
+      for (int d = 0; d < D; ++d) {
+        const double df = q[m][d] - xs[jj][d];
+        d2 = __builtin_fma(df, df, d2);
+      }
+      ks[m][jj] = (jb + jj < r1) ? sf2 * gpk_exp_neg(-0.5 * d2) : 0.0;
+    }
+    __syncthreads();
+    for (int t = t0 + tid; t < t1; t += 256) {
+      const int mp = t / TP, tt = t - mp * TP, m = mp / P, p = mp - m * P;
+      double s = (jb == r0) ? 0.0 : share[t];
+      if (tt == TT) {
+#pragma unroll 8
+        for (int jj = 0; jj < HJ; ++jj) s = __builtin_fma(ks[m][jj], al[jj][p], s);
+      } else {
+        const int d = td[tt], e = te[tt];
+        const double qd = q[m][d], qe = q[m][e];
+#pragma unroll 8
+        for (int jj = 0; jj < HJ; ++jj) s = __builtin_fma(ks[m][jj] * al[jj][p] * (qd - xs[jj][d]), qe - xs[jj][e], s);
+      }
+      share[t] = s;
+    }
+  }
+  if (last_of(counter + b * gridDim.z + blockIdx.z, gridDim.x, tid)) {
+    const double* base = phess + (long long)b * gridDim.x * E;
+    const double* ystd = k.ystd + b * P;
+    double* out = hess_out + (long long)b * M * P * D * D;
+    for (int t = mp0 * TT + tid; t < mp1 * TT; t += 256) {
+      const int mp = t / TT, tt = t - mp * TT, p = mp % P, d = td[tt], e = te[tt];
+      double s = sum_shares(base + (long long)mp * TP + tt, 0, 1, gridDim.x, E);
+      if (d == e) s -= sum_shares(base + (long long)mp * TP + TT, 0, 1, gridDim.x, E);
+      const double v = ystd[p] / (ls[d] * ls[e]) * s;
+      out[((long long)mp * D + d) * D + e] = v;
+      out[((long long)mp * D + e) * D + d] = v;
+    }
+  }
 }
 
 // NMB = 1: up to 16 queries, 2: up to 32.  8 waves: wave w takes the 64-wide k-chunks w, w + 8, ..., the loads of
@@ -781,8 +883,11 @@ struct SmallWork {
   size_t Vs;             // BF x Np x SQ                            (grad)
   size_t pdv;            // BF x (gb x row chunks) x (M * D)        (grad)
   size_t pcov, gcov;     // BF x gb x CE, BF x (gb / CG rounded up) x CE   (cov)
+  size_t phess;          // B x hess_groups(Np) x (M * P * (D (D + 1) / 2 + 1))   (hess)
   size_t total;
 };
+// workgroups per model of small_hess_kernel: at most 64, a function of Np alone
+unsigned hess_groups(int64_t Np) { return (unsigned)((Np + hess_rows(Np) - 1) / hess_rows(Np)); }
 SmallWork small_work(int call, int64_t Np, int B, int64_t M, int D, int P, int F = 1) {
   const size_t ga = (size_t)(Np / SJ), gb = (size_t)(Np / SR), BF = (size_t)B * F;
   SmallWork w{};
@@ -802,6 +907,9 @@ SmallWork small_work(int call, int64_t Np, int B, int64_t M, int D, int P, int F
     w.pdv = take(BF * gb * WTV_MAX_ROW_CHUNKS * (size_t)(M * D));
   } else if (call == GPK_SMALL_JACVAR) {
     w.pjac = take((size_t)B * ga * (size_t)(M * P * D));
+  } else if (call == GPK_SMALL_HESS) {
+    w.pjac = take((size_t)B * ga * (size_t)(M * P * D));
+    w.phess = take((size_t)B * hess_groups(Np) * (size_t)(M * P * (D * (D + 1) / 2 + 1)));
   }
   w.total = at;
   return w;
@@ -883,9 +991,12 @@ bool gpk_small_ok(int64_t Np, int D, int P, int64_t M) {
 
 int gpk_small_launch(gpk_handle h, int call, const ServeModels& m, const double* Xq, int64_t M, double* work, const ServeOut& out) {
   // jv: the first launch of a gradient call, then the variance launch that also finishes the Jacobian - no W^T V launch
-  const bool jv = call == GPK_SMALL_JACVAR, grad = call == GPK_SMALL_GRAD || jv, cov = call == GPK_SMALL_COV;
+  // hs: the gradient call's one launch for mean + Jacobian (no variance), then the Hessian launch
+  const bool jv = call == GPK_SMALL_JACVAR, hs = call == GPK_SMALL_HESS, grad = call == GPK_SMALL_GRAD || jv || hs,
+             cov = call == GPK_SMALL_COV;
   GPK_REQUIRE(h, call == GPK_SMALL_PREDICT || grad || cov, "small-batch launch: unknown call");
-  const std::string name(cov ? "small cov" : jv ? "small jacvar" : grad ? "small grad" : "small predict");
+  const std::string name(cov ? "small cov" : jv ? "small jacvar" : hs ? "small hess" : grad ? "small grad" : "small predict");
+  GPK_REQUIRE(h, !hs || (out.hess && out.dmean && !out.var && !out.dvar), name + ": mean, Jacobian and Hessian, no variance");
   const int B = m.B, D = m.D, P = m.P, F = m.F;
   const long long N = m.N, Np = gpk_padded(m.N), ldw = m.ldw;
   GPK_REQUIRE(h, B >= 1 && B <= GPK_SMALL_MAX_MODELS && (B == 1 || P == 1) && (F == 1 || F == 2),
@@ -900,7 +1011,7 @@ int gpk_small_launch(gpk_handle h, int call, const ServeModels& m, const double*
   GPK_REQUIRE(h, !factors || (m.W[0] && (F == 1 || m.W[1]) && m.Np == Np && ldw >= Np && ldw % 2 == 0),
               name + ": needs the inverse factor of every model (both of the two-factor form), padded, with an even ldw >= Np");
   GPK_REQUIRE(h, cov || !factors || m.kss, name + ": null pointer");
-  if (cov || (grad && !jv && factors)) GPK_TRY(ensure_cov_counters(h));
+  if (cov || hs || (grad && !jv && factors)) GPK_TRY(ensure_cov_counters(h));
   SmallK k{};
   GPK_TRY(small_params(h, name, m, factors, cov, k));
   const unsigned ga = (unsigned)(Np / SJ), gb = (unsigned)(Np / SR);
@@ -916,8 +1027,17 @@ int gpk_small_launch(gpk_handle h, int call, const ServeModels& m, const double*
     hipLaunchKernelGGL(factors ? small_cross_mean_kernel<false> : small_cross_mean_kernel<true>, g1, b1, 0, h->stream, k, N, Np, D, P,
                        Xq, (int)M, factors ? Ks : nullptr, pmean, h->d_count, out.mean);
   GPK_LAUNCH_CHECK(h);
-  if (!factors) return GPK_OK;
   unsigned* vcount = h->d_count + GPK_SMALL_MAX_MODELS;
+  if (hs) {      // (the covariance reduction's ticket counters, all at zero between launches: no covariance launch runs in this call)
+    const unsigned slices = (unsigned)((M * P + hess_slice(D) - 1) / hess_slice(D));
+    static_assert(GPK_SMALL_COV_COUNTERS >= SQ * SP / (HESS_SLICE_ENTRIES / (HT_MAX + 1)) + GPK_SMALL_MAX_MODELS * SQ,
+                  "one counter per (model, slice): at most 171 slices of one model, 11 of each of eight single-output models");
+    hipLaunchKernelGGL(small_hess_kernel, dim3(hess_groups(Np), B, slices), b1, 0, h->stream, k, N, Np, D, P, Xq, (int)M,
+                       work + wk.phess, h->d_cov_count, out.hess);
+    GPK_LAUNCH_CHECK(h);
+    return GPK_OK;
+  }
+  if (!factors) return GPK_OK;
   if (cov) {
     hipLaunchKernelGGL(cov_kernel(M, F), g2, b2, 0, h->stream, k, ldw, Np, Ks, (int)M, D, P, Xq, pmean, ga, work + wk.pcov,
                        work + wk.gcov, h->d_cov_count, out.mean, out.cov);

@@ -1157,6 +1157,48 @@ extern "C" int gpk_sparse_predict_grad(gpk_handle h, const double* Xq, int64_t M
   return sparse_predict_grad(h, s, Xq, M, mean, var, dmean, dvar, var_includes_noise);
 }
 
+// The sparse mean is the mean of an exact model over (Z, alpha_u): its Hessian is gpk_predict_mean_hess on the inducing inputs.
+static int sparse_predict_hess(gpk_handle h, gpk_sparse* s, const double* Xq, int64_t M, double* mean, double* dmean, double* hess) {
+  GPK_REQUIRE(h, hess != nullptr, "sparse_predict_hess: hess is null");
+  GPK_REQUIRE(h, Xq && mean && dmean && M >= 1, "sparse_predict_hess: null pointer or empty batch");
+  GPK_REQUIRE(h, h->batch == 1, "composite calls are not available in batched mode");
+  GPK_CHECK_HIP(h, hipSetDevice(h->device));
+  const int D = s->D, P = s->P;
+  GPK_TRY(gpk_require_finite(h, Xq, M * D, "sparse_predict_hess", "Xq"));
+  const int64_t m = s->m;
+  SparseServe sv;
+  sv.fill(1, &s, 0);
+  if (sv.small(h, M)) return gpk_serve_hess(h, sv.models(), true, Xq, M, mean, dmean, hess);
+  // the query panels of sparse_predict_grad for the fused mean and its Jacobian (their bits); inside a panel the Hessians in
+  // blocks of at most 64 MiB
+  const int64_t panel = gpk_panel_rows(6ull << 30, (size_t)3 * s->mp * sizeof(double), M);
+  int64_t hrows = gpk_panel_rows(64ull << 20, (size_t)P * D * D * sizeof(double), M);
+  if (hrows > panel) hrows = panel;
+  const size_t nq = (size_t)panel * D, nm = (size_t)panel * P, nj = nm * D, nh = (size_t)hrows * P * D * D;
+  GPK_TRY(s->q.reserve(h, (nq + nm + nj + nh) * sizeof(double)));
+  double *dq = s->q, *dmn = dq + nq, *ddm = dmn + nm, *dhs = ddm + nj;
+  return gpk_query_panels(h, Xq, M, D * sizeof(double), panel, dq, [&](int64_t m0, int64_t mc) -> int {
+    GPK_TRY(gpk_predict_mean(h, GPK_F64, s->Z, s->alpha, m, D, P, s->ls, s->sf2, s->y_mean, s->y_std, dq, mc, dmn));
+    GPK_TRY(gpk_predict_mean_grad(h, s->Z, s->alpha, m, D, P, s->ls, s->sf2, s->y_std, dq, mc, ddm));
+    GPK_CHECK_HIP(h, hipMemcpyAsync(mean + m0 * P, dmn, (size_t)mc * P * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    GPK_CHECK_HIP(h, hipMemcpyAsync(dmean + m0 * P * D, ddm, (size_t)mc * P * D * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    for (int64_t r0 = 0; r0 < mc; r0 += hrows) {      // (the stream orders the blocks' launches and downloads on dhs)
+      const int64_t rc = mc - r0 < hrows ? mc - r0 : hrows;
+      GPK_TRY(gpk_predict_mean_hess(h, s->Z, s->alpha, m, D, P, s->ls, s->sf2, s->y_std, dq + r0 * D, rc, dhs));
+      GPK_CHECK_HIP(h, hipMemcpyAsync(hess + (m0 + r0) * P * D * D, dhs, (size_t)rc * P * D * D * sizeof(double), hipMemcpyDeviceToHost,
+                                      h->stream));
+    }
+    return GPK_OK;
+  });
+}
+
+extern "C" int gpk_sparse_predict_hess(gpk_handle h, const double* Xq, int64_t M, double* mean, double* dmean, double* hess) {
+  if (!h) return GPK_BAD_ARG;
+  gpk_sparse* s = h->sparse;
+  GPK_REQUIRE(h, s && s->finalized, "sparse_predict_hess: no finalised sparse model (call gpk_sparse_finalize first)");
+  return sparse_predict_hess(h, s, Xq, M, mean, dmean, hess);
+}
+
 static int sparse_predict_cov(gpk_handle h, gpk_sparse* s, const double* Xq, int64_t M, double* mean, double* cov) {
   GPK_REQUIRE(h, Xq && mean && cov && M >= 1 && M <= 16384, "sparse_predict_cov: null pointer or M outside [1, 16384]");
   GPK_REQUIRE(h, h->batch == 1, "composite calls are not available in batched mode");
@@ -1290,6 +1332,30 @@ extern "C" int gpk_sparse_predict_multi_grad(gpk_handle h, int B, const gpk_hand
     gpk_interleave(vr.data(), B, M, 1, var);
     gpk_interleave(dv.data(), B, M, D, dvar);
   }
+  return GPK_OK;
+}
+
+extern "C" int gpk_sparse_predict_multi_hess(gpk_handle h, int B, const gpk_handle* models, const double* Xq, int64_t M, double* mean,
+                                             double* dmean, double* hess) {
+  if (!h) return GPK_BAD_ARG;
+  GPK_REQUIRE(h, hess != nullptr, "sparse_predict_multi_hess: hess is null");
+  SparseServe sb;
+  GPK_TRY(sparse_batch(h, "sparse_predict_multi_hess", B, models, Xq, M, 0, 0, sb));
+  GPK_REQUIRE(h, mean && dmean, "sparse_predict_multi_hess: null pointer");
+  GPK_CHECK_HIP(h, hipSetDevice(h->device));
+  const int D = sb.D;
+  const size_t n = (size_t)B * M, nd = n * D, nh = nd * D;
+  std::vector<double> mn(n), dm(nd), hs(nh);
+  if (sb.small(h, M)) {      // every model's own inducing inputs: the model is a grid dimension of the first launch
+    GPK_TRY(gpk_serve_hess(h, sb.models(), true, Xq, M, mn.data(), dm.data(), hs.data()));
+  } else {
+    for (int b = 0; b < B; ++b)
+      GPK_TRY(sparse_predict_hess(h, sb.s[b], Xq, M, mn.data() + (size_t)b * M, dm.data() + (size_t)b * M * D,
+                                  hs.data() + (size_t)b * M * D * D));
+  }
+  gpk_interleave(mn.data(), B, M, 1, mean);
+  gpk_interleave(dm.data(), B, M, D, dmean);
+  gpk_interleave(hs.data(), B, M, D * D, hess);
   return GPK_OK;
 }
 

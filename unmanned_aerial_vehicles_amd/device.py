@@ -890,6 +890,34 @@ class DeviceGP:
                         M, _hp(mean), _hp(var), _hp(dmean), _hp(dvar))
         return mean, var, dmean, dvar
 
+    # ---- second derivatives of the mean (K8) ------------------------------------------------------------------------
+    def predict_mean_hess_dev(self, Xq, y_std):
+        """gpk_predict_mean_hess on device tensors: the (M, P, D, D) input Hessian of the un-normalised posterior mean, each
+        D x D block symmetric bit for bit.  Any M (the call panels the queries itself)."""
+        torch = _torch()
+        assert self.factored
+        q = self._as_queries(Xq, torch.float64)
+        M = q.shape[0]
+        hess = self.be.empty((M, self.P, self.D, self.D), torch.float64)
+        if M == 0:
+            return hess
+        self.be.call("gpk_predict_mean_hess", _p(self.X), _p(self.alpha), self.N, self.D, self.P, _hp(self.ls), self.sf2,
+                     _hp(_vec(y_std, self.P)), _p(q), M, _p(hess))
+        return hess
+
+    def predict_hess_host(self, Xq, y_mean, y_std):
+        """One C call (gpk_predict_host_hess) for batches where `host_path_ok(M, False)` holds: host queries (M, D) ->
+        (mean (M, P), dmean (M, P, D), hess (M, P, D, D)) as NumPy arrays, un-normalised.  mean and dmean have the bits of
+        `predict_grad_host`."""
+        assert self.factored
+        Xq, M = self._host_queries(Xq)
+        mean, dmean = np.empty((M, self.P)), np.empty((M, self.P, self.D))
+        hess = np.empty((M, self.P, self.D, self.D))
+        c = self._host_call_args(y_mean, y_std)
+        self.be.call("gpk_predict_host_hess", c[7], c[8], self.N, self.D, self.P, c[9], self.sf2, c[10], c[11], _hp(Xq), M,
+                     _hp(mean), _hp(dmean), _hp(hess))
+        return mean, dmean, hess
+
     def propagate_ok(self):
         """The one-call horizon propagation (gpk_propagate_host) applies: the small-batch path's sizes, not switched off."""
         return self.factored and self.D <= 16 and self.Np <= 16384 and int(self.be.options.get("small_path", 1)) != 0

@@ -419,6 +419,35 @@ class GaussianProcessRegressor:
             y_var, dvar = y_var[:, 0], dvar[:, 0]
         return mean, dmean, y_var, dvar
 
+    def predict_hessian(self, X):
+        """Posterior mean with its first and second input derivatives - what an exact-Hessian SQP step, the second-order mean
+        correction tr(H Sigma) / 2 and the state sensitivity of a linearisation need.  scikit-learn has no such call; the
+        Hessian is the closed form of the RBF kernel, evaluated on the GPU (K8), with delta_j = (x_m - x_j) / ls:
+
+            hess[m, p, d, e] = y_std[p] / (ls_d ls_e) sum_j k(x_m, x_j) alpha_jp (delta_jd delta_je - [d = e])
+
+        Returns (y_mean, dmean, hess): y_mean and dmean exactly as `predict_jacobian(X)` returns them (the same launches, the
+        same bits), hess (M, P, D, D), or (M, D, D) for one target, every D x D block symmetric bit for bit.  Always the fp64
+        kernels.  Same input validation as `predict`; an unfitted model returns the prior mean and zero derivatives."""
+        X = check_queries(X)
+        M, D = X.shape
+        if not hasattr(self, "X_train_"):
+            mean, dmean = self.predict_jacobian(X)
+            return mean, dmean, np.zeros(dmean.shape + (D,))
+        self._ensure_device()
+        dev = self._dev
+        if dev.host_path_ok(M, False):
+            mean, dmean, hess = dev.predict_hess_host(X, self._y_train_mean, self._y_train_std)
+        else:
+            import torch
+            q = dev._as_queries(X, torch.float64)
+            mean = dev.predict_mean_dev(q, self._y_train_mean, self._y_train_std, "float64").cpu().numpy()
+            dmean = dev.predict_mean_grad_dev(q, self._y_train_std).cpu().numpy()
+            hess = dev.predict_mean_hess_dev(q, self._y_train_std).cpu().numpy()
+        if mean.shape[1] == 1:
+            mean, dmean, hess = mean[:, 0], dmean[:, 0], hess[:, 0]
+        return mean, dmean, hess
+
     def propagate(self, x0, U, lin, Sigma0=None, process_noise=None, var_includes_noise=False, return_stages=False,
                   route="auto"):
         """The posterior's own closed-loop horizon: the mean trajectory under the learned dynamics and the state covariance that

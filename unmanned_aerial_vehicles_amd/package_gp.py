@@ -213,6 +213,30 @@ class GaussianProcess:
             self.get_logger().error(f"Error in GP prediction: {e}")
             return prior
 
+    def predict_hessian(self, X_test):
+        """The mean with its first and second input derivatives: (mean (M, P), dmean (M, P, D), hess (M, P, D, D)), mean and
+        dmean as `predict_jacobian` returns them.  The package conventions of `predict`: no target normalisation.  fp64 kernels
+        whatever `predict_dtype`.  Unfitted / failed fit / any error: the prior mean and zero derivatives, never raising."""
+        X_test = np.atleast_2d(np.asarray(X_test, dtype=np.float64))
+        M, D = len(X_test), X_test.shape[1]
+        prior = (np.zeros((M, self.output_dim)), np.zeros((M, self.output_dim, D)), np.zeros((M, self.output_dim, D, D)))
+        if len(self.X_train) == 0 or self.alpha is None:
+            return prior
+        with self._swap:
+            model = self._model
+        if model is None:
+            return prior
+        try:
+            dev, sf2, zeros, ones = model
+            if dev.host_path_ok(M, False) and dev.host_path_ok(M, True):      # (the route `predict_jacobian` takes: its bits)
+                return dev.predict_hess_host(X_test, zeros, ones)
+            mean = dev.predict_mean_dev(X_test, zeros, ones, "float64").cpu().numpy()
+            dmean = dev.predict_mean_grad_dev(X_test, ones).cpu().numpy()
+            return mean, dmean, dev.predict_mean_hess_dev(X_test, ones).cpu().numpy()
+        except Exception as e:  # noqa: BLE001
+            self.get_logger().error(f"Error in GP prediction: {e}")
+            return prior
+
     # ---- LML (gaussian_process.py:243-265) --------------------------------------------------------
     def log_marginal_likelihood(self):
         if len(self.X_train) < 2 or self.L is None:

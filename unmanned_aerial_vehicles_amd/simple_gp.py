@@ -153,6 +153,24 @@ class SimpleQuadrotorGP:
             print(f"GP prediction failed: {e}")
             return np.zeros(6), np.zeros((6, 10))
 
+    def predict_residual_hessian(self, state, control):
+        """One row -> (mean (6,), J (6, 10), H (6, 10, 10)): the residual with its first and second derivatives with respect
+        to [state(6), control(4)], one call (`predict_hessian` of the exact or the sparse model); untrained/failed -> zeros of
+        these shapes and a printed reason, never raising into the control loop."""
+        zeros = np.zeros(6), np.zeros((6, 10)), np.zeros((6, 10, 10))
+        if not self.is_trained:
+            print("GP Hessian unavailable: the model is not trained")
+            return zeros
+        try:
+            x = np.concatenate([state, control]).reshape(1, -1)
+            mean, J, H = self.gp_model.predict_hessian(x)
+            self.prediction_count += 1
+            D = x.shape[1]
+            return mean.reshape(-1), J.reshape(mean.size, D), H.reshape(mean.size, D, D)
+        except Exception as e:  # noqa: BLE001
+            print(f"GP prediction failed: {e}")
+            return zeros
+
     def predict_residual_batch(self, X, return_var=True):
         """M rows [state(6), control(4)] in one kernel call -> (mean (M,P), variance (M,P))."""
         X = np.atleast_2d(np.asarray(X, dtype=float))

@@ -456,6 +456,26 @@ class SparseGP:
                 var, dvar = var[:, 0], dvar[:, 0]
         return (mean, dmean, var, dvar) if return_var else (mean, dmean)
 
+    def predict_hessian(self, X):
+        """Posterior mean with its first and second input derivatives: the call of
+        `GaussianProcessRegressor.predict_hessian` on the sparse posterior (`gpk_sparse_predict_hess`).  The sparse mean is
+        that of an exact model over (Z, alpha_u) and its Hessian involves no inverse factor, with delta_j = (x_m - z_j) / ls:
+
+            hess[m, p, d, e] = y_std[p] / (ls_d ls_e) sum_j k_mj alpha_u[j, p] (delta_jd delta_je - [d = e])
+
+        Returns (y_mean, dmean, hess): y_mean and dmean as `predict_jacobian(X)` returns them, bit for bit; hess (M, P, D, D),
+        or (M, D, D) for one target, every D x D block symmetric bit for bit.  A model without rows returns the prior mean and
+        zero derivatives through the same call."""
+        X = self._queries(X)
+        self._ensure()
+        M, D, P = X.shape[0], X.shape[1], self._P
+        mean, dmean, hess = np.empty((M, P)), np.empty((M, P, D)), np.empty((M, P, D, D))
+        if M > 0:
+            self._backend().call("gpk_sparse_predict_hess", _ptr(X), M, _ptr(mean), _ptr(dmean), _ptr(hess))
+        if P == 1 and self._y_1d:
+            mean, dmean, hess = mean[:, 0], dmean[:, 0], hess[:, 0]
+        return mean, dmean, hess
+
     def sample_y(self, X, n_samples=1, random_state=0):
         """Draws from the joint posterior (the prior, without rows) at X, as `GaussianProcessRegressor.sample_y`: the mean and
         covariance from `predict(X, return_cov=True)` (GPU), the draw by NumPy's `multivariate_normal`, one target at a time.

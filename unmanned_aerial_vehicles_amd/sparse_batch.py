@@ -140,6 +140,18 @@ class BatchedSparseGP:
                         _ptr(dvar), 1)
         return (mean, dmean, var, dvar) if return_var else (mean, dmean)
 
+    def predict_hessian(self, Xq):
+        """(mean (M, B), dmean (M, B, D), hess (M, B, D, D)): `SparseGP.predict_hessian` of every model in one call
+        (`gpk_sparse_predict_multi_hess`, one synchronisation up to 32 rows); mean and dmean are those of `predict_jacobian`
+        bit for bit, column b has the bits of `models[b].predict_hessian`.  The shapes of `BatchedARDGP.predict_hessian`."""
+        X = self._queries(Xq)
+        M, D, B = X.shape[0], X.shape[1], len(self.models)
+        mean, dmean, hess = np.full((M, B), np.nan), np.full((M, B, D), np.nan), np.full((M, B, D, D), np.nan)
+        if M > 0:
+            with self._serving() as (be, handles):
+                be.call("gpk_sparse_predict_multi_hess", B, handles, _ptr(X), M, _ptr(mean), _ptr(dmean), _ptr(hess))
+        return mean, dmean, hess
+
     def propagate(self, x0, U, lin, coord=None, in_scaler=None, Sigma0=None, process_noise=None, var_includes_noise=False,
                   return_stages=False, out_scaler=None, route="auto"):
         """`BatchedARDGP.propagate` on the sparse posteriors: the batch's mean rollout with the linearised state covariance in

@@ -83,6 +83,21 @@ def _r2(y_true, y_pred):
     return 1.0 - ss_res / ss_tot if ss_tot > 0 else 0.0
 
 
+def hessian_to_raw(H_scaled, scale_x, scale_y):
+    """The Hessian of a model behind scalers, in raw units.  The model reads z = (x - shift) / scale_x and its output goes
+    through y = mean + scale_y f, so with H_scaled[..., d, e] = d2 f / dz_d dz_e:
+
+        H_raw[..., d, e] = scale_y / (scale_x[d] scale_x[e]) * H_scaled[..., d, e]
+
+    H_scaled (..., D, D), scale_x (D,), scale_y a scalar.  Both mirror entries get the same factor in the same order of
+    operations, so a bit-symmetric input stays bit-symmetric."""
+    H = np.asarray(H_scaled, dtype=np.float64)
+    sx = np.asarray(scale_x, dtype=np.float64).ravel()
+    if H.ndim < 2 or H.shape[-1] != sx.size or H.shape[-2] != sx.size:
+        raise ValueError(f"H_scaled must be (..., {sx.size}, {sx.size})")
+    return float(scale_y) * H / (sx[:, None] * sx[None, :])
+
+
 class GPTrainer:
     def __init__(self, data_dir="gp_data", model_dir="gp_models", device=None):
         self.data_dir = data_dir
@@ -622,6 +637,57 @@ class PreTrainedGP:
         except Exception as e:  # noqa: BLE001
             print(f"GP prediction failed: {e}")
             return np.zeros(6), np.zeros((6, 10))
+
+    # ---- second derivatives of the residual means in raw units ----------------------------------------------------------
+    def predict_residual_hessian_batch(self, X):
+        """Residual means of a batch of raw [state(6), control(4)] rows with their Jacobians and Hessians with respect to
+        those raw inputs: (mean (M, 6), J (M, 6, 10), H (M, 6, 10, 10)); mean and J as `predict_residual_jacobian_batch`
+        returns them, H by `hessian_to_raw` from model b's Hessian on the scaled inputs:
+
+            H[m, b, d, e] = sy_b.scale_ / (sx.scale_[d] sx.scale_[e]) * d2 mu_b / dz_d dz_e
+
+        Models that share inputs and scaler: ONE call for all of them (`BatchedARDGP.predict_hessian`, or
+        `BatchedSparseGP.predict_hessian` for model files written by `sparsify`); otherwise one `predict_hessian` per model
+        with its own scalers.  The reference has no counterpart.  Missing or failing components: zeros.  Never raises."""
+        try:
+            X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+            M = len(X)
+        except Exception as e:  # noqa: BLE001
+            print(f"GP prediction failed: {e}")
+            X, M = None, 1
+        mean, J, H = np.zeros((M, 6)), np.zeros((M, 6, 10)), np.zeros((M, 6, 10, 10))
+
+        def put(i, name, sx, result):
+            mu, dmu, h = result
+            sy = self.scalers_y[name]
+            scale_y = float(np.ravel(sy.scale_)[0])
+            m_i = sy.inverse_transform(np.asarray(mu, dtype=np.float64).reshape(-1, 1)).ravel()
+            J_i = scale_y * np.asarray(dmu, dtype=np.float64).reshape(M, -1) / sx.scale_[None, :]
+            H_i = hessian_to_raw(np.asarray(h, dtype=np.float64).reshape(M, 10, 10), sx.scale_, scale_y)
+            if not (np.isfinite(m_i).all() and np.isfinite(J_i).all() and np.isfinite(H_i).all()):
+                raise FloatingPointError("non-finite mean, Jacobian or Hessian")
+            mean[:, i], J[:, i, :], H[:, i] = m_i, J_i, H_i
+
+        def fallback(i):
+            mean[:, i], J[:, i], H[:, i] = 0.0, 0.0, 0.0
+
+        if X is not None and self.is_loaded and X.shape[1] == 10:
+            self._serve(X, lambda bg, Xs: tuple(bg.predict_hessian(Xs)), lambda m, Xs: tuple(m.predict_hessian(Xs)), put,
+                        fallback)
+        return mean, J, H
+
+    def predict_residual_hessian(self, state, control):
+        """One query -> (mean (6,), J (6, 10), H (6, 10, 10)), the first and second derivatives of the residual means with
+        respect to [state(6), control(4)]; not loaded or failed: zeros and a printed reason."""
+        try:
+            row = np.concatenate([np.asarray(state, float)[:6], np.asarray(control, float)[:4]]).reshape(1, -1)
+            if not self.is_loaded:
+                print("GP Hessian unavailable: no model loaded")
+            mean, J, H = self.predict_residual_hessian_batch(row)
+            return mean[0], J[0], H[0]
+        except Exception as e:  # noqa: BLE001
+            print(f"GP prediction failed: {e}")
+            return np.zeros(6), np.zeros((6, 10)), np.zeros((6, 10, 10))
 
     def linearize_residuals(self, X_guess, U_guess, dt, gain=0.1, n_states=6):
         """`SimpleQuadrotorGP.linearize_gp_residuals` for the per-axis models: the frozen residual D (6, N) and its
