@@ -1170,6 +1170,49 @@ GPK_API int gpk_sparse_propagate_multi(gpk_handle h, int B, const gpk_handle* mo
                                        const double* lin, const double* Sigma0, int s_rows, const double* Q, int R, int H,
                                        double* traj, double* Sigma, double* mean, double* var, double* jac);
 
+/* ... at second order in the mean: for x ~ N(xbar, Sigma), E[mu(x)] = mu(xbar) + tr(H Sigma) / 2 + O(Sigma^2), H the mean's
+ * input Hessian; the term is of the order of the covariance the chain carries.  The four entries above with two more arguments:
+ * order (1 or 2, anything else GPK_BAD_ARG with a message) and corr (H x R x P or B, may be NULL).  With order = 2
+ *   c_b         = 1/2 sum_{d,e < nx} H_b[d][e] Sigma_h[d][e]      H_b = d^2 mu_b / d q^2 in RAW units at q = [x_h, u_h]
+ *   x_{h+1}     = (x_h + lin q + sum_b e_coord[b] mu_b) + sum_b e_coord[b] c_b      (c added LAST, as one addition)
+ *   A_h, Sigma_{h+1}: as at first order, at the same query
+ * The controls are exact, so only the nx x nx block of H enters; A_h stays the Jacobian at x_h (the derivative of c holds third
+ * derivatives).  No Hessian is formed: with delta_j = (z - X_j) / ls and St[d][e] = Sigma_h[d][e] / (in_scale_d ls_d in_scale_e
+ * ls_e) (model b's own length-scales),
+ *   tr(H_b Sigma_h) = y_std[b] sum_j k*_j alpha_jb (delta_j^T St delta_j - tr St)
+ * R x P (or B) scalars per stage.  Launches: 4 H - per stage the two small-batch launches, unchanged; one trace launch (at most
+ * 64 workgroups per model, each its rows' share of the two sums, K* recomputed from the device queries, Sigma_h read from the
+ * chain's state; no ticket, no atomics); the advance launch, which adds the shares in workgroup order.  One upload, ONE
+ * synchronisation, one more download when corr is given.  traj and Sigma of stage h + 1 and mean, var, jac of stage h are the
+ * first-order quantities at the (corrected) query of stage h: with H = 1 Sigma[1], mean, var and jac have the BITS of order 1
+ * and traj[1] = traj_order1[1] + corr[0] (scattered to coord) exactly.  corr[h] is c of stage h.  With order = 1 the entries
+ * return the bits of their first-order siblings and corr is zero-filled.  The sparse pair takes (Z, alpha_u) as the mean's
+ * model, as gpk_sparse_predict_hess; its batch form folds out_scale into y_std, which scales c as it scales the mean.
+ * Limits, refusals and timing (GPK_TIMED_PROPAGATE brackets the advance launch) as above.                                   */
+GPK_API int gpk_propagate2_host(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
+                                double sf2, const double* y_mean, const double* y_std, const double* W, int64_t Np, int64_t ldw,
+                                double kss, double floor_, int var_includes_noise, double noise, const double* x0, int x0_rows,
+                                const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows, const double* Q,
+                                int R, int H, double* traj, double* Sigma, double* mean, double* var, double* jac, int order,
+                                double* corr);
+GPK_API int gpk_propagate2_host_multi(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D,
+                                      const double* ls, const double* sf2, const double* y_mean, const double* y_std,
+                                      const double* const* W, int64_t Np, int64_t ldw, const double* kss, double floor_,
+                                      int var_includes_noise, const double* noise, int nx, const int* coord,
+                                      const double* in_shift, const double* in_scale, const double* x0, int x0_rows,
+                                      const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows,
+                                      const double* Q, int R, int H, double* traj, double* Sigma, double* mean, double* var,
+                                      double* jac, int order, double* corr);
+GPK_API int gpk_sparse_propagate2(gpk_handle h, int var_includes_noise, const double* x0, int x0_rows, const double* U, int u_rows,
+                                  const double* lin, const double* Sigma0, int s_rows, const double* Q, int R, int H, double* traj,
+                                  double* Sigma, double* mean, double* var, double* jac, int order, double* corr);
+GPK_API int gpk_sparse_propagate2_multi(gpk_handle h, int B, const gpk_handle* models, int var_includes_noise, int nx,
+                                        const int* coord, const double* in_shift, const double* in_scale, const double* out_shift,
+                                        const double* out_scale, const double* x0, int x0_rows, const double* U, int u_rows,
+                                        const double* lin, const double* Sigma0, int s_rows, const double* Q, int R, int H,
+                                        double* traj, double* Sigma, double* mean, double* var, double* jac, int order,
+                                        double* corr);
+
 #ifdef __cplusplus
 }
 #endif

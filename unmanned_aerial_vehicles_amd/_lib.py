@@ -183,6 +183,11 @@ SIGNATURES = {
     "gpk_sparse_propagate_multi": (_int, [_vp, _int, C.POINTER(_vp), _int, _int, C.POINTER(_int), _dp, _dp, _dp, _dp, _dp, _int,
                                           _dp, _int, _dp, _dp, _int, _dp, _int, _int, _dp, _dp, _dp, _dp, _dp]),
 }
+# ... at second order in the mean: the four entries above with (order, corr) appended
+SIGNATURES["gpk_propagate2_host"] = (_int, SIGNATURES["gpk_propagate_host"][1] + [_int, _vp])
+SIGNATURES["gpk_propagate2_host_multi"] = (_int, SIGNATURES["gpk_propagate_host_multi"][1] + [_int, _vp])
+SIGNATURES["gpk_sparse_propagate2"] = (_int, SIGNATURES["gpk_sparse_propagate"][1] + [_int, _dp])
+SIGNATURES["gpk_sparse_propagate2_multi"] = (_int, SIGNATURES["gpk_sparse_propagate_multi"][1] + [_int, _dp])
 
 _lib = None
 

@@ -409,7 +409,7 @@ class BatchedARDGP:
 
     # ------------------------------------------------------------------ horizon propagation (K11, per-axis batch)
     def propagate(self, x0, U, lin, coord=None, in_scaler=None, Sigma0=None, process_noise=None, var_includes_noise=False,
-                  return_stages=False, out_scaler=None, route="auto"):
+                  return_stages=False, out_scaler=None, route="auto", order=1):
         """The batch's own closed-loop horizon in raw units: mean trajectory and linearised state covariance
         (`propagate`'s module docstring has the recursion), with the conventions of `BatchedPosteriorPaths.rollout`: the state
         has nx = len(lin) coordinates, B <= nx <= D; model b drives state coordinate coord[b] (default 0 .. B - 1); the models
@@ -420,8 +420,10 @@ class BatchedARDGP:
         return_stages=True, {"mean" (H, R, B), "var" (H, R, B), "jac" (H, R, B, D)}: jac per unit of the RAW query.  One C call
         per horizon (`gpk_propagate_host_multi`, three launches per stage for all models) where `_serve_state` holds; otherwise
         (or with the backend option small_path=0, or route="host") the same recursion as a host loop over
-        `predict_jacobian`."""
+        `predict_jacobian`.  order=2: the second-order mean of `GaussianProcessRegressor.propagate` (`gpk_propagate2_host_multi`,
+        four launches per stage; the host loop contracts `predict_hessian`); the stages gain "corr" (H, R, B)."""
         from . import propagate as _pg
+        order = _pg.check_order(order)
         if not self.models:
             raise RuntimeError("this BatchedARDGP is not fitted yet")
         B = len(self.models)
@@ -440,19 +442,26 @@ class BatchedARDGP:
             traj, Sigma = np.empty((H + 1, R, nx)), np.empty((H + 1, R, nx, nx))
             mean, var, jac = (np.empty((H, R, B)), np.empty((H, R, B)), np.empty((H, R, B, D))) if return_stages else (None,) * 3
             cd = (C.c_int * B)(*coord)
+            args = (B, sv["X"], sv["alpha"], d0.N, d0.D, _hp(sv["ls"]), _hp(sv["sf2"]), _hp(ym), _hp(ys), sv["W"], d0.Np, d0.Np,
+                    _hp(kss), 0.0, 0, None, nx, cd, _hp(in_shift), _hp(in_scale), _hp(x0), x0.shape[0], _hp(U) if D > nx else None,
+                    U.shape[0], _hp(lin), _hp(S0), 1 if S0 is None else S0.shape[0], _hp(Q), R, H, _hp(traj), _hp(Sigma), _hp(mean),
+                    _hp(var), _hp(jac))
+            stages = {"mean": mean, "var": var, "jac": jac}
             try:
-                d0.be.call("gpk_propagate_host_multi", B, sv["X"], sv["alpha"], d0.N, d0.D, _hp(sv["ls"]), _hp(sv["sf2"]), _hp(ym),
-                           _hp(ys), sv["W"], d0.Np, d0.Np, _hp(kss), 0.0, 0, None, nx, cd, _hp(in_shift), _hp(in_scale), _hp(x0),
-                           x0.shape[0], _hp(U) if D > nx else None, U.shape[0], _hp(lin), _hp(S0),
-                           1 if S0 is None else S0.shape[0], _hp(Q), R, H, _hp(traj), _hp(Sigma), _hp(mean), _hp(var), _hp(jac))
+                if order == 1:
+                    d0.be.call("gpk_propagate_host_multi", *args)
+                else:
+                    stages["corr"] = np.empty((H, R, B)) if return_stages else None
+                    d0.be.call("gpk_propagate2_host_multi", *args, order, _hp(stages["corr"]))
             except _lib.GPKError as e:      # a limit of the entry: the caller's arguments, with the library's message
                 if e.code == _lib.GPK_BAD_ARG:
                     raise ValueError(str(e)) from None
                 raise
-            return (traj, Sigma, {"mean": mean, "var": var, "jac": jac}) if return_stages else (traj, Sigma)
+            return (traj, Sigma, stages) if return_stages else (traj, Sigma)
         stage = _pg.batch_stage(self.predict_jacobian, _pg.noise_levels(self.models), in_shift, in_scale, o_mean, o_scale,
                                 var_includes_noise)
-        traj, Sigma, stages = _pg.host_loop(stage, coord, x0, U, lin, S0, Q, R, H)
+        hess_stage = _pg.batch_hess_stage(self.predict_hessian, in_shift, in_scale, o_scale) if order == 2 else None
+        traj, Sigma, stages = _pg.host_loop(stage, coord, x0, U, lin, S0, Q, R, H, hess_stage)
         return (traj, Sigma, stages) if return_stages else (traj, Sigma)
 
     def _fused64(self):

@@ -295,6 +295,14 @@ size_t gpk_small_work_doubles(int call, int64_t Np, int B, int64_t M, int D, int
 //                      (its bits), then small_hess_kernel: 2 launches
 // Block b of every output has the bits of model b served alone.
 int gpk_small_launch(gpk_handle h, int call, const ServeModels& m, const double* Xq, int64_t M, double* work, const ServeOut& out);
+// The trace launch of a second-order propagation stage (small_hess_trace_kernel): the workgroups' shares of tr(H_o Sg_m) for the
+// M device query rows Xq, each with its own nx x nx covariance Sg[m] (device, raw units; in_scale: D host values, the queries'
+// scaler).  groups = gpk_small_trace_groups(Np) workgroups per model write shares[(g * E + e) * 2 + {0, 1}], E = B M P and
+// e = (b * M + m) * P + p, and trs[b * M + m]; tr(H Sg) = y_std (sum_g shares[..0] - trs * sum_g shares[..1]).  No inverse
+// factor is read (F = 1 or 2), nothing is synchronised, and no other launch's results are read.
+unsigned gpk_small_trace_groups(int64_t Np);
+int gpk_small_trace_launch(gpk_handle h, const ServeModels& m, const double* Xq, int64_t M, const double* Sg, int nx,
+                           const double* in_scale, double* shares, double* trs);
 // ---- horizon propagation (gpk_propagate.hip): what the entries of the exact models and of the sparse models (gpk_sparse.hip) share
 constexpr int GPK_PROP_MAX_R = GPK_SMALL_MAX_M, GPK_PROP_MAX_H = 256, GPK_PROP_MAX_NX = 16, GPK_PROP_MAX_D = 16;
 // The composition's parameters.  Output o of the stage (a single model's output p, or model b of a batch) sits at
@@ -315,10 +323,13 @@ struct Horizon {
   const double *x0, *U, *lin, *Sigma0, *Q;
   int x0_rows, u_rows, s_rows, R, H;
   double *traj, *Sigma, *mean, *var, *jac;
+  int order = 1;                     // 2: the mean takes c_o = tr(H_o Sigma_h) / 2 per stage, added last (see gpk_propagate.hip)
+  double* corr = nullptr;            // (H, R, NO): c of every stage, zeros at order 1; may be null
 };
 // The chain of one horizon on the models m (F = 1 or 2): every check of the limits (GPK_BAD_ARG before anything is launched), one
-// upload, 3 H launches, up to five downloads, one synchronisation.  k: nx, D, NO, the strides, model_of, the scaler, ystd2 and
-// the noise filled in by the entry; `who` prefixes the messages.
+// upload, 3 H launches (order 2: 4 H, the trace launch before the advance), up to five downloads (six with corr), one
+// synchronisation.  k: nx, D, NO, the strides, model_of, the scaler, ystd2 and the noise filled in by the entry; `who` prefixes
+// the messages.
 int gpk_propagate_run(gpk_handle h, const std::string& who, const ServeModels& m, PropK k, const Horizon& z);
 // ... as one-call serving (gpk_serve.hip): host queries in, host results out through the pinned, mapped block, one
 // synchronisation.  small: the launches above (gpk_serve_predict: 33..64 queries the same twice); otherwise, F = 1 only, the

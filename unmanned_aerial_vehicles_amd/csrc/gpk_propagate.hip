@@ -19,19 +19,39 @@
 namespace {
 
 constexpr int PROP_MAX_R = GPK_PROP_MAX_R, PROP_MAX_H = GPK_PROP_MAX_H, PROP_MAX_NX = GPK_PROP_MAX_NX, PROP_MAX_D = GPK_PROP_MAX_D;
+constexpr int PROP_MAX_GROUPS = 64;      // workgroups per model of the trace launch (gpk_small_trace_groups) at most
 
 // One workgroup per rollout r, thread (i, j) = (tid >> 4, tid & 15).  Sequential, fixed-order sums; Sigma in LDS; the lower
 // triangle of T A^T is formed and mirrored, so Sigma is symmetric bit for bit.  x and S are the rollout's state, updated in
 // place (this workgroup alone touches row r of either); qnext: the next stage's scaled queries (R x D), null at the last stage.
-__global__ __launch_bounds__(256) void propagate_advance_kernel(PropK k, int R, const double* __restrict__ smean,
-                                                                const double* __restrict__ svar, const double* __restrict__ sjac,
-                                                                const double* __restrict__ lin, const double* __restrict__ Qn,
-                                                                const double* __restrict__ u, const double* __restrict__ u_next,
-                                                                long long u_row_stride, double* x, double* S, double* qnext,
-                                                                double* traj_next, double* sig_next, double* omean, double* ovar,
-                                                                double* ojac) {
+//
+// SECOND (propagate_advance2_kernel, order 2): the stage's trace launch (small_hess_trace_kernel, gpk_small.hip) has left `groups`
+// shares of T = sum_j k* alpha delta^T St delta and S = sum_j k* alpha per (rollout, output) and tr St per (rollout, model).  The
+// kernel adds them in workgroup order, forms c_o = y_std[o] (T - tr St S) / 2 = tr(H_o Sigma_h) / 2 and adds c to xn LAST, as one
+// addition to the finished first-order value.  A, Sigma and the stage's outputs are the first-order kernel's, bit for bit.
+struct Prop2 {
+  const double* shares;              // groups x (NO R) x 2, entry e = o * so + r * sm
+  const double* trs;                 // tr St of (rollout r, output o) at [o * tro + r]
+  int groups, tro;
+  double ystd[16];
+  double* ocorr;                     // this stage's c (R x NO), or null
+};
+
+template <bool SECOND>
+__device__ __forceinline__ void propagate_advance_body(PropK k, int R, const double* __restrict__ smean,
+                                                       const double* __restrict__ svar, const double* __restrict__ sjac,
+                                                       const double* __restrict__ lin, const double* __restrict__ Qn,
+                                                       const double* __restrict__ u, const double* __restrict__ u_next,
+                                                       long long u_row_stride, double* x, double* S, double* qnext,
+                                                       double* traj_next, double* sig_next, double* omean, double* ovar,
+                                                       double* ojac, const Prop2* p2) {
   __shared__ double A[16][17], Sg[16][17], T[16][17], J[16][17];
   __shared__ double q[16], mu[16], vv[16], xn[16];
+  [[maybe_unused]] double (*cc)[16] = nullptr;
+  if constexpr (SECOND) {
+    __shared__ double cc_s[16];
+    cc = &cc_s;
+  }
   const int tid = threadIdx.x, i = tid >> 4, j = tid & 15, r = blockIdx.x;
   const int nx = k.nx, D = k.D, NO = k.NO;
   if (tid < D) q[tid] = tid < nx ? x[(long long)r * nx + tid] : u[r * u_row_stride + (tid - nx)];
@@ -40,6 +60,26 @@ __global__ __launch_bounds__(256) void propagate_advance_kernel(PropK k, int R, 
     const double v = svar[tid * k.vo + r * k.vm];
     mu[tid] = smean[tid * k.so + r * k.sm];
     vv[tid] = (k.add_noise ? v + k.noise[tid] : v) * k.ystd2[tid];
+  }
+  if constexpr (SECOND) {
+    // the shares of output i: thread (i, j) fetches those of workgroups j, j + 16, .. (all loads in flight together), thread
+    // (i, 0) adds them in workgroup order
+    __shared__ double sh[2][16][PROP_MAX_GROUPS + 1];
+    const long long E = (long long)NO * R, e = i * k.so + r * k.sm;
+    if (i < NO)
+      for (int g = j; g < p2->groups; g += 16) {
+        sh[0][i][g] = p2->shares[(g * E + e) * 2];
+        sh[1][i][g] = p2->shares[(g * E + e) * 2 + 1];
+      }
+    __syncthreads();
+    if (tid < NO) {
+      double t = 0.0, s = 0.0;
+      for (int g = 0; g < p2->groups; ++g) {
+        t += sh[0][tid][g];
+        s += sh[1][tid][g];
+      }
+      (*cc)[tid] = 0.5 * (p2->ystd[tid] * (t - p2->trs[tid * p2->tro + r] * s));
+    }
   }
   if (i < NO && j < D) {
     const double g = sjac[(long long)(i * k.so + r * k.sm) * D + j];
@@ -79,6 +119,13 @@ __global__ __launch_bounds__(256) void propagate_advance_kernel(PropK k, int R, 
     sig_next[at + i * nx + j] = s;
     sig_next[at + j * nx + i] = s;
   }
+  if constexpr (SECOND) {
+    if (tid < nx) {
+      const int o = k.model_of[tid];
+      if (o >= 0) xn[tid] += (*cc)[o];
+    }
+    if (p2->ocorr && tid < NO) p2->ocorr[(long long)r * NO + tid] = (*cc)[tid];
+  }
   if (tid < nx) {
     x[(long long)r * nx + tid] = xn[tid];
     traj_next[(long long)r * nx + tid] = xn[tid];
@@ -94,6 +141,27 @@ __global__ __launch_bounds__(256) void propagate_advance_kernel(PropK k, int R, 
   if (ojac && i < NO && j < D) ojac[((long long)r * NO + i) * D + j] = J[i][j];
 }
 
+__global__ __launch_bounds__(256) void propagate_advance_kernel(PropK k, int R, const double* __restrict__ smean,
+                                                                const double* __restrict__ svar, const double* __restrict__ sjac,
+                                                                const double* __restrict__ lin, const double* __restrict__ Qn,
+                                                                const double* __restrict__ u, const double* __restrict__ u_next,
+                                                                long long u_row_stride, double* x, double* S, double* qnext,
+                                                                double* traj_next, double* sig_next, double* omean, double* ovar,
+                                                                double* ojac) {
+  propagate_advance_body<false>(k, R, smean, svar, sjac, lin, Qn, u, u_next, u_row_stride, x, S, qnext, traj_next, sig_next, omean, ovar,
+                                ojac, nullptr);
+}
+__global__ __launch_bounds__(256) void propagate_advance2_kernel(PropK k, int R, const double* __restrict__ smean,
+                                                                 const double* __restrict__ svar, const double* __restrict__ sjac,
+                                                                 const double* __restrict__ lin, const double* __restrict__ Qn,
+                                                                 const double* __restrict__ u, const double* __restrict__ u_next,
+                                                                 long long u_row_stride, double* x, double* S, double* qnext,
+                                                                 double* traj_next, double* sig_next, double* omean, double* ovar,
+                                                                 double* ojac, Prop2 p2) {
+  propagate_advance_body<true>(k, R, smean, svar, sjac, lin, Qn, u, u_next, u_row_stride, x, S, qnext, traj_next, sig_next, omean, ovar,
+                               ojac, &p2);
+}
+
 bool prop_finite(const double* p, size_t n) {
   for (size_t i = 0; i < n; ++i)
     if (!(p[i] - p[i] == 0.0)) return false;
@@ -105,6 +173,7 @@ bool prop_finite(const double* p, size_t n) {
 int gpk_propagate_run(gpk_handle h, const std::string& who, const ServeModels& m, PropK k, const Horizon& z) {
   const int nx = k.nx, D = k.D, nu = D - nx, NO = k.NO, R = z.R, H = z.H;
   GPK_REQUIRE(h, h->batch == 1, who + "not available in batched mode");
+  GPK_REQUIRE(h, z.order == 1 || z.order == 2, who + "order must be 1 or 2");
   GPK_REQUIRE(h, R >= 1 && R <= PROP_MAX_R, who + "R must be in [1, 32]");
   GPK_REQUIRE(h, H >= 1 && H <= PROP_MAX_H, who + "H must be in [1, 256]");
   GPK_REQUIRE(h, D >= 1 && D <= PROP_MAX_D && nx >= 1 && nx <= PROP_MAX_NX && nx <= D, who + "needs 1 <= nx <= D <= 16");
@@ -132,8 +201,13 @@ int gpk_propagate_run(gpk_handle h, const std::string& who, const ServeModels& m
   const size_t n_sm = (size_t)NO * R, n_sj = n_sm * D;
   const size_t n_work = gpk_small_work_doubles(GPK_SMALL_JACVAR, m.Np, m.B, R, D, m.P, m.F);
   const size_t n_traj = (size_t)H * n_x, n_sig = (size_t)H * n_s, n_om = (size_t)H * n_sm, n_oj = (size_t)H * n_sj;
+  // order 2: the trace launch's shares (groups x NO R x 2), tr St per (model, rollout), and c of every stage
+  const bool second = z.order == 2;
+  const unsigned groups = second ? gpk_small_trace_groups(m.Np) : 0;
+  GPK_REQUIRE(h, groups <= (unsigned)PROP_MAX_GROUPS, who + "more trace workgroups than the advance launch adds");
+  const size_t n_sh = (size_t)groups * n_sm * 2, n_tr = second ? (size_t)m.B * R : 0, n_oc = second ? n_om : 0;
   void* ws = nullptr;
-  GPK_TRY(gpk_scratch(h, (n_up + 2 * n_sm + n_sj + n_work + n_traj + n_sig + 2 * n_om + n_oj) * sizeof(double), &ws));
+  GPK_TRY(gpk_scratch(h, (n_up + 2 * n_sm + n_sj + n_work + n_traj + n_sig + 2 * n_om + n_oj + n_sh + n_tr + n_oc) * sizeof(double), &ws));
   double* d_x = (double*)ws;
   double* d_S = d_x + n_x;
   double* d_q = d_S + n_s;
@@ -149,6 +223,9 @@ int gpk_propagate_run(gpk_handle h, const std::string& who, const ServeModels& m
   double* d_om = d_sig + n_sig;
   double* d_ov = d_om + n_om;
   double* d_oj = d_ov + n_om;
+  double* d_sh = d_oj + n_oj;
+  double* d_tr = d_sh + n_sh;
+  double* d_oc = d_tr + n_tr;
   std::vector<double> host(n_up, 0.0);
   double* hx = host.data();
   double* hS = hx + n_x;
@@ -175,9 +252,28 @@ int gpk_propagate_run(gpk_handle h, const std::string& who, const ServeModels& m
   GPK_CHECK_HIP(h, hipMemcpyAsync(d_x, host.data(), sizeof(double) * n_up, hipMemcpyHostToDevice, h->stream));
   const ServeOut stage{s_mean, s_var, s_jac, nullptr, nullptr};
   const long long u_row_stride = (nu && z.u_rows == R) ? (long long)H * nu : 0;
+  Prop2 p2{};
+  if (second) {
+    p2.shares = d_sh; p2.trs = d_tr; p2.groups = (int)groups; p2.tro = m.B > 1 ? R : 0;
+    for (int o = 0; o < NO; ++o) p2.ystd[o] = m.y_std[o];
+  }
   for (int s = 0; s < H; ++s) {
     GPK_TRY(gpk_small_launch(h, GPK_SMALL_JACVAR, m, d_q, R, work, stage));
     const bool last = s + 1 == H;
+    if (second) {
+      GPK_TRY(gpk_small_trace_launch(h, m, d_q, R, d_S, nx, k.in_scale, d_sh, d_tr));
+      p2.ocorr = z.corr ? d_oc + (size_t)s * n_sm : nullptr;
+      gpk_time_begin(h, GPK_TIMED_PROPAGATE);
+      hipLaunchKernelGGL(propagate_advance2_kernel, dim3((unsigned)R), dim3(256), 0, h->stream, k, R, (const double*)s_mean,
+                         (const double*)s_var, (const double*)s_jac, (const double*)d_lin, z.Q ? (const double*)d_Q : nullptr,
+                         (const double*)(d_u + (size_t)s * nu), (const double*)(d_u + (size_t)(last ? s : s + 1) * nu), u_row_stride,
+                         d_x, d_S, last ? nullptr : d_q, d_traj + (size_t)s * n_x, d_sig + (size_t)s * n_s,
+                         z.mean ? d_om + (size_t)s * n_sm : nullptr, z.var ? d_ov + (size_t)s * n_sm : nullptr,
+                         z.jac ? d_oj + (size_t)s * n_sj : nullptr, p2);
+      gpk_time_end(h);
+      GPK_LAUNCH_CHECK(h);
+      continue;
+    }
     gpk_time_begin(h, GPK_TIMED_PROPAGATE);
     hipLaunchKernelGGL(propagate_advance_kernel, dim3((unsigned)R), dim3(256), 0, h->stream, k, R, (const double*)s_mean,
                        (const double*)s_var, (const double*)s_jac, (const double*)d_lin, z.Q ? (const double*)d_Q : nullptr,
@@ -193,17 +289,20 @@ int gpk_propagate_run(gpk_handle h, const std::string& who, const ServeModels& m
   if (z.mean) GPK_CHECK_HIP(h, hipMemcpyAsync(z.mean, d_om, sizeof(double) * n_om, hipMemcpyDeviceToHost, h->stream));
   if (z.var) GPK_CHECK_HIP(h, hipMemcpyAsync(z.var, d_ov, sizeof(double) * n_om, hipMemcpyDeviceToHost, h->stream));
   if (z.jac) GPK_CHECK_HIP(h, hipMemcpyAsync(z.jac, d_oj, sizeof(double) * n_oj, hipMemcpyDeviceToHost, h->stream));
+  if (z.corr && second) GPK_CHECK_HIP(h, hipMemcpyAsync(z.corr, d_oc, sizeof(double) * n_om, hipMemcpyDeviceToHost, h->stream));
+  if (z.corr && !second) memset(z.corr, 0, sizeof(double) * n_om);
   GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
   return GPK_OK;
 }
 
-extern "C" int gpk_propagate_host(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
-                                  double sf2, const double* y_mean, const double* y_std, const double* W, int64_t Np, int64_t ldw,
-                                  double kss, double floor_, int var_includes_noise, double noise, const double* x0, int x0_rows,
-                                  const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows, const double* Q,
-                                  int R, int H, double* traj, double* Sigma, double* mean, double* var, double* jac) {
+// The single-model entries' body.  `who`: the entry's name in the messages; order and corr as in Horizon.
+static int propagate_host_any(gpk_handle h, const std::string& who, const double* X, const double* alpha, int64_t N, int D, int P,
+                              const double* ls, double sf2, const double* y_mean, const double* y_std, const double* W, int64_t Np,
+                              int64_t ldw, double kss, double floor_, int var_includes_noise, double noise, const double* x0,
+                              int x0_rows, const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows,
+                              const double* Q, int R, int H, double* traj, double* Sigma, double* mean, double* var, double* jac,
+                              int order, double* corr) {
   if (!h) return GPK_BAD_ARG;
-  const std::string who("propagate_host: ");
   GPK_REQUIRE(h, X && alpha && ls && y_mean && y_std && W, who + "null pointer");
   GPK_REQUIRE(h, P >= 1 && P <= GPK_MAX_P && P <= D, who + "the state dimension P must be in [1, 16] and must not exceed D");
   GPK_REQUIRE(h, prop_finite(&noise, 1) && prop_finite(&kss, 1) && prop_finite(&floor_, 1), who + "kss, floor and noise must be finite");
@@ -214,20 +313,39 @@ extern "C" int gpk_propagate_host(gpk_handle h, const double* X, const double* a
   for (int d = 0; d < 16; ++d) { k.in_shift[d] = 0.0; k.in_scale[d] = 1.0; k.model_of[d] = d < P ? d : -1; }
   for (int p = 0; p < P; ++p) { k.ystd2[p] = y_std[p] * y_std[p]; k.noise[p] = noise; }
   const ServeModels m{1, P, 1, &X, &alpha, N, D, ls, &sf2, y_mean, y_std, {&W, nullptr}, Np, ldw, &kss, floor_, nullptr};
-  const Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean, var, jac};
+  const Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean, var, jac, order, corr};
   return gpk_propagate_run(h, who, m, k, z);
 }
 
-extern "C" int gpk_propagate_host_multi(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D,
-                                        const double* ls, const double* sf2, const double* y_mean, const double* y_std,
-                                        const double* const* W, int64_t Np, int64_t ldw, const double* kss, double floor_,
-                                        int var_includes_noise, const double* noise, int nx, const int* coord,
-                                        const double* in_shift, const double* in_scale, const double* x0, int x0_rows,
-                                        const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows,
-                                        const double* Q, int R, int H, double* traj, double* Sigma, double* mean, double* var,
-                                        double* jac) {
+extern "C" int gpk_propagate_host(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
+                                  double sf2, const double* y_mean, const double* y_std, const double* W, int64_t Np, int64_t ldw,
+                                  double kss, double floor_, int var_includes_noise, double noise, const double* x0, int x0_rows,
+                                  const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows, const double* Q,
+                                  int R, int H, double* traj, double* Sigma, double* mean, double* var, double* jac) {
+  return propagate_host_any(h, "propagate_host: ", X, alpha, N, D, P, ls, sf2, y_mean, y_std, W, Np, ldw, kss, floor_, var_includes_noise,
+                            noise, x0, x0_rows, U, u_rows, lin, Sigma0, s_rows, Q, R, H, traj, Sigma, mean, var, jac, 1, nullptr);
+}
+
+extern "C" int gpk_propagate2_host(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
+                                   double sf2, const double* y_mean, const double* y_std, const double* W, int64_t Np, int64_t ldw,
+                                   double kss, double floor_, int var_includes_noise, double noise, const double* x0, int x0_rows,
+                                   const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows, const double* Q,
+                                   int R, int H, double* traj, double* Sigma, double* mean, double* var, double* jac, int order,
+                                   double* corr) {
+  return propagate_host_any(h, "propagate2_host: ", X, alpha, N, D, P, ls, sf2, y_mean, y_std, W, Np, ldw, kss, floor_,
+                            var_includes_noise, noise, x0, x0_rows, U, u_rows, lin, Sigma0, s_rows, Q, R, H, traj, Sigma, mean, var, jac,
+                            order, corr);
+}
+
+// The batch entries' body, as propagate_host_any.
+static int propagate_host_multi_any(gpk_handle h, const std::string& who, int B, const double* const* X, const double* const* alpha,
+                                    int64_t N, int D, const double* ls, const double* sf2, const double* y_mean, const double* y_std,
+                                    const double* const* W, int64_t Np, int64_t ldw, const double* kss, double floor_,
+                                    int var_includes_noise, const double* noise, int nx, const int* coord, const double* in_shift,
+                                    const double* in_scale, const double* x0, int x0_rows, const double* U, int u_rows,
+                                    const double* lin, const double* Sigma0, int s_rows, const double* Q, int R, int H, double* traj,
+                                    double* Sigma, double* mean, double* var, double* jac, int order, double* corr) {
   if (!h) return GPK_BAD_ARG;
-  const std::string who("propagate_host_multi: ");
   GPK_REQUIRE(h, X && alpha && ls && sf2 && y_mean && y_std && W && kss && coord, who + "null pointer");
   GPK_REQUIRE(h, B >= 1 && B <= GPK_SMALL_MAX_MODELS, who + "1..8 models");
   GPK_REQUIRE(h, D >= 1 && D <= PROP_MAX_D && nx >= B && nx <= D, who + "the state dimension nx must be in [B, D], D <= 16");
@@ -257,6 +375,32 @@ extern "C" int gpk_propagate_host_multi(gpk_handle h, int B, const double* const
     k.scaled = 1;
   }
   const ServeModels m{B, 1, 1, X, alpha, N, D, ls, sf2, y_mean, y_std, {W, nullptr}, Np, ldw, kss, floor_, nullptr};
-  const Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean, var, jac};
+  const Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean, var, jac, order, corr};
   return gpk_propagate_run(h, who, m, k, z);
+}
+
+extern "C" int gpk_propagate_host_multi(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D,
+                                        const double* ls, const double* sf2, const double* y_mean, const double* y_std,
+                                        const double* const* W, int64_t Np, int64_t ldw, const double* kss, double floor_,
+                                        int var_includes_noise, const double* noise, int nx, const int* coord,
+                                        const double* in_shift, const double* in_scale, const double* x0, int x0_rows,
+                                        const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows,
+                                        const double* Q, int R, int H, double* traj, double* Sigma, double* mean, double* var,
+                                        double* jac) {
+  return propagate_host_multi_any(h, "propagate_host_multi: ", B, X, alpha, N, D, ls, sf2, y_mean, y_std, W, Np, ldw, kss, floor_,
+                                  var_includes_noise, noise, nx, coord, in_shift, in_scale, x0, x0_rows, U, u_rows, lin, Sigma0, s_rows,
+                                  Q, R, H, traj, Sigma, mean, var, jac, 1, nullptr);
+}
+
+extern "C" int gpk_propagate2_host_multi(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D,
+                                         const double* ls, const double* sf2, const double* y_mean, const double* y_std,
+                                         const double* const* W, int64_t Np, int64_t ldw, const double* kss, double floor_,
+                                         int var_includes_noise, const double* noise, int nx, const int* coord,
+                                         const double* in_shift, const double* in_scale, const double* x0, int x0_rows,
+                                         const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows,
+                                         const double* Q, int R, int H, double* traj, double* Sigma, double* mean, double* var,
+                                         double* jac, int order, double* corr) {
+  return propagate_host_multi_any(h, "propagate2_host_multi: ", B, X, alpha, N, D, ls, sf2, y_mean, y_std, W, Np, ldw, kss, floor_,
+                                  var_includes_noise, noise, nx, coord, in_shift, in_scale, x0, x0_rows, U, u_rows, lin, Sigma0,
+                                  s_rows, Q, R, H, traj, Sigma, mean, var, jac, order, corr);
 }

@@ -39,6 +39,10 @@
 //                            queries in a device buffer).  small_var_jac2_kernel is its two-factor form (below: TWO), the sparse
 //                            models' stage: var_out M x P (B x M for a batch), final.
 //
+//   ... at second order      one more launch per stage, small_hess_trace_kernel (below, with its own description): the workgroups' shares
+//                            of tr(H Sigma) for every (query, output), R x NO scalars instead of R x NO x D x D Hessian entries;
+//                            the chain's advance launch adds them.  gpk_small_trace_launch makes it.
+//
 //   two factors (K9)         the sparse model's variance terms are kss - |Wuu k*|^2 + |WSigma k*|^2 on ONE K* with P outputs: the
 //                            first launch runs with one model, and small_var[_grad]_kernel, small_cov_kernel and small_wtv_grad_kernel
 //                            with the template parameter TWO - the same bodies - take the inverse FACTOR as the grid
@@ -406,6 +410,130 @@ __global__ __launch_bounds__(256) void small_hess_kernel(SmallK k, long long N, 
       const double v = ystd[p] / (ls[d] * ls[e]) * s;
       out[((long long)mp * D + d) * D + e] = v;
       out[((long long)mp * D + e) * D + d] = v;
+    }
+  }
+}
+
+// ---- tr(H Sigma) of the mean's input Hessian (K11, second order): the third launch of a second-order propagation stage ------------
+// The contraction of small_hess_kernel's result with a covariance, formed without the Hessian.  Query m carries its own nx x nx
+// covariance Sg[m] (raw units, the chain's state).  With delta_mj = q_m - r_j as above (d < nx only: the controls are exact) and
+//   St[m][d][e] = Sg[m][d][e] / (in_scale_d ls_d in_scale_e ls_e)       (this model's own length-scales),
+//   tr(H_mp Sg_m) = y_std[p] (T[m][p] - tr St[m] S[m][p]),   T[m][p] = sum_j k*_mj alpha_jp delta_mj^T St[m] delta_mj,
+//                                                            S[m][p] = sum_j k*_mj alpha_jp
+// The workgroups take small_hess_kernel's rows (hess_rows(Np), at most 64 workgroups per model) in its rounds of HJ rows, K*
+// recomputed from the device query rows.  Per (query, row) ONE quadratic form over the packed triangle of St (off-diagonal
+// entries stored doubled), per (query, output) two fixed-order sums carried in registers from round to round; the workgroup
+// writes them to its own slot, shares[(group * E + e) * 2 + {0: T, 1: S}] with e = (model * M + m) * P + p and E = B M P, and
+// workgroup 0 of a model writes tr St[m] to trs[model * M + m].  No ticket and no last workgroup: the chain's advance launch
+// adds the slots in workgroup order.  Rows past N enter as zeros, a workgroup past the last row writes zeros, every slot is
+// written, and rows, rounds and the order of every sum depend on (Np, M, P, D, nx) alone: model b of a batch has the bits of
+// model b alone.
+constexpr int TRACE_PAIRS = SQ * HJ / 256;       // (query, row) pairs per thread and round
+constexpr int TRACE_OUTS = SQ * SP / 256;        // (query, output) sums per thread
+
+__global__ __launch_bounds__(256) void small_hess_trace_kernel(SmallK k, Arr16 in_scale, long long N, long long Np, int D, int P, int nx,
+                                                               const double* __restrict__ Xq, const double* __restrict__ Sg, int M,
+                                                               double* shares, double* trs) {
+  __shared__ double q[SQ][SD + 1];
+  __shared__ double ks[SQ][HJ + 1];
+  __shared__ double kq[SQ][HJ + 1];
+  __shared__ double al[HJ][SP + 1];
+  __shared__ double xs[HJ][SD + 1];
+  __shared__ double St[SQ][HT_MAX];
+  __shared__ double ls[SD], sl[SD];      // the model's length-scales; in_scale * ls
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const double* __restrict__ X = k.X[b];
+  const double* __restrict__ alpha = k.alpha[b];
+  const double sf2 = k.sf2[b];
+  const int TT = nx * (nx + 1) / 2, MP = M * P;
+  const long long rows = hess_rows(Np);
+  const long long r0 = (long long)blockIdx.x * rows, r1 = min(N, r0 + rows);
+  if (tid < SD) {
+    ls[tid] = k.ls[b][tid];
+    sl[tid] = in_scale.v[tid] * k.ls[b][tid];
+  }
+  __syncthreads();
+  // (queries and rows are staged to the full width SD, zeros from D on: the differences below take no select)
+  for (int e = tid; e < M * SD; e += 256) {
+    const int m = e / SD, d = e % SD;
+    q[m][d] = d < D ? Xq[m * D + d] / ls[d] : 0.0;
+  }
+  for (int t = tid; t < M * TT; t += 256) {
+    const int m = t / TT, tt = t - m * TT;
+    int d = 0;
+    while ((d + 1) * (d + 2) / 2 <= tt) ++d;
+    const int e = tt - d * (d + 1) / 2;
+    const double s = Sg[((long long)m * nx + d) * nx + e] / (sl[d] * sl[e]);
+    St[m][tt] = d == e ? s : 2.0 * s;
+  }
+  __syncthreads();
+  if (blockIdx.x == 0 && tid < M) {
+    double t = 0.0;
+    for (int d = 0; d < nx; ++d) t += St[tid][d * (d + 1) / 2 + d];
+    trs[b * M + tid] = t;
+  }
+  double accT[TRACE_OUTS], accS[TRACE_OUTS];
+#pragma unroll
+  for (int u = 0; u < TRACE_OUTS; ++u) accT[u] = accS[u] = 0.0;
+  for (long long jb = r0; jb < r1; jb += HJ) {
+    __syncthreads();
+    for (int e = tid; e < HJ * SD; e += 256) {
+      const int jj = e / SD, d = e % SD;
+      xs[jj][d] = (d < D && jb + jj < r1) ? X[(jb + jj) * D + d] / ls[d] : 0.0;
+    }
+    for (int e = tid; e < HJ * P; e += 256) {
+      const int jj = e / P, p = e - jj * P;
+      al[jj][p] = (jb + jj < r1) ? alpha[(jb + jj) * P + p] : 0.0;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < TRACE_PAIRS; ++u) {
+      const int e = tid + 256 * u, m = e / HJ, jj = e % HJ;
+      if (m < M) {
+        double dl[SD], d2 = 0.0;
+#pragma unroll
+        for (int d = 0; d < SD; ++d) {
+          dl[d] = q[m][d] - xs[jj][d];
+          d2 = __builtin_fma(dl[d], dl[d], d2);
+        }
+        double f = 0.0;
+#pragma unroll
+        for (int d = 0; d < SD; ++d)
+          if (d < nx) {
+            double g = 0.0;
+#pragma unroll
+            for (int c = 0; c <= d; ++c) g = __builtin_fma(St[m][d * (d + 1) / 2 + c], dl[c], g);
+            f = __builtin_fma(g, dl[d], f);
+          }
+        const double v = (jb + jj < r1) ? sf2 * gpk_exp_neg(-0.5 * d2) : 0.0;
+        ks[m][jj] = v;
+        kq[m][jj] = v * f;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < TRACE_OUTS; ++u) {
+      const int t = tid + 256 * u;
+      if (t < MP) {
+        const int m = t / P, p = t - m * P;
+        double sT = accT[u], sS = accS[u];
+#pragma unroll 8
+        for (int jj = 0; jj < HJ; ++jj) {
+          sT = __builtin_fma(kq[m][jj], al[jj][p], sT);
+          sS = __builtin_fma(ks[m][jj], al[jj][p], sS);
+        }
+        accT[u] = sT;
+        accS[u] = sS;
+      }
+    }
+  }
+  double* slot = shares + ((long long)blockIdx.x * gridDim.y * MP + (long long)b * MP) * 2;
+#pragma unroll
+  for (int u = 0; u < TRACE_OUTS; ++u) {
+    const int t = tid + 256 * u;
+    if (t < MP) {
+      slot[2 * t] = accT[u];
+      slot[2 * t + 1] = accS[u];
     }
   }
 }
@@ -1060,6 +1188,26 @@ int gpk_small_launch(gpk_handle h, int call, const ServeModels& m, const double*
     hipLaunchKernelGGL(wtv_grad_kernel(F), dim3(gb, rc, B * F), dim3(GT), 0, h->stream, k, ldw, N, Np, D, Ks, work + wk.Vs, Xq, (int)M,
                        work + wk.pdv, h->d_cov_count + WTV_COUNTER0, out.dvar);
   }
+  GPK_LAUNCH_CHECK(h);
+  return GPK_OK;
+}
+
+unsigned gpk_small_trace_groups(int64_t Np) { return hess_groups(Np); }
+
+int gpk_small_trace_launch(gpk_handle h, const ServeModels& m, const double* Xq, int64_t M, const double* Sg, int nx,
+                           const double* in_scale, double* shares, double* trs) {
+  const std::string name("small hess trace");
+  const long long Np = gpk_padded(m.N);
+  GPK_REQUIRE(h, m.B >= 1 && m.B <= GPK_SMALL_MAX_MODELS && (m.B == 1 || m.P == 1),
+              name + ": 1 model, or up to 8 single-output models");
+  GPK_REQUIRE(h, gpk_small_ok(Np, m.D, m.P, M) && nx >= 1 && nx <= m.D, name + ": shape outside the small-batch path");
+  GPK_REQUIRE(h, m.X && m.alpha && m.ls && m.sf2 && m.y_mean && m.y_std && Xq && Sg && in_scale && shares && trs, name + ": null pointer");
+  SmallK k{};
+  GPK_TRY(small_params(h, name, m, false, false, k));
+  Arr16 sc;
+  for (int d = 0; d < 16; ++d) sc.v[d] = d < m.D ? in_scale[d] : 1.0;
+  hipLaunchKernelGGL(small_hess_trace_kernel, dim3(hess_groups(Np), m.B), dim3(256), 0, h->stream, k, sc, (long long)m.N, Np, m.D, m.P, nx,
+                     Xq, Sg, (int)M, shares, trs);
   GPK_LAUNCH_CHECK(h);
   return GPK_OK;
 }

@@ -1381,11 +1381,11 @@ extern "C" int gpk_sparse_predict_multi_cov(gpk_handle h, int B, const gpk_handl
 // ---- horizon propagation (K11) on the sparse posteriors: the chain of gpk_propagate.hip on the two-factor description ----------
 // The stage's variance comes out of the two-factor launch final - times y_std^2, the noise level inside kss - in the layout of
 // its var_out (M x P for one model, B x M for a batch): the advance launch takes it as it is (ystd2 = 1, add_noise = 0).
-extern "C" int gpk_sparse_propagate(gpk_handle h, int var_includes_noise, const double* x0, int x0_rows, const double* U, int u_rows,
-                                    const double* lin, const double* Sigma0, int s_rows, const double* Q, int R, int H, double* traj,
-                                    double* Sigma, double* mean, double* var, double* jac) {
+static int sparse_propagate_any(gpk_handle h, const std::string& who, int var_includes_noise, const double* x0, int x0_rows,
+                                const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows, const double* Q,
+                                int R, int H, double* traj, double* Sigma, double* mean, double* var, double* jac, int order,
+                                double* corr) {
   if (!h) return GPK_BAD_ARG;
-  const std::string who("sparse_propagate: ");
   gpk_sparse* s = h->sparse;
   GPK_REQUIRE(h, s && s->finalized, who + "no finalised sparse model (call gpk_sparse_finalize first)");
   GPK_REQUIRE(h, h->small_path, who + "the small-batch path is switched off (option small_path)");
@@ -1398,17 +1398,32 @@ extern "C" int gpk_sparse_propagate(gpk_handle h, int var_includes_noise, const 
   k.nx = P; k.D = D; k.NO = P;
   k.so = 1; k.sm = P; k.vo = 1; k.vm = P;
   for (int d = 0; d < 16; ++d) { k.in_shift[d] = 0.0; k.in_scale[d] = 1.0; k.model_of[d] = d < P ? d : -1; k.ystd2[d] = 1.0; }
-  const Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean, var, jac};
+  const Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean, var, jac, order, corr};
   return gpk_propagate_run(h, who, sv.models(), k, z);
 }
 
-extern "C" int gpk_sparse_propagate_multi(gpk_handle h, int B, const gpk_handle* models, int var_includes_noise, int nx,
-                                          const int* coord, const double* in_shift, const double* in_scale, const double* out_shift,
-                                          const double* out_scale, const double* x0, int x0_rows, const double* U, int u_rows,
-                                          const double* lin, const double* Sigma0, int s_rows, const double* Q, int R, int H,
-                                          double* traj, double* Sigma, double* mean, double* var, double* jac) {
+extern "C" int gpk_sparse_propagate(gpk_handle h, int var_includes_noise, const double* x0, int x0_rows, const double* U, int u_rows,
+                                    const double* lin, const double* Sigma0, int s_rows, const double* Q, int R, int H, double* traj,
+                                    double* Sigma, double* mean, double* var, double* jac) {
+  return sparse_propagate_any(h, "sparse_propagate: ", var_includes_noise, x0, x0_rows, U, u_rows, lin, Sigma0, s_rows, Q, R, H, traj,
+                              Sigma, mean, var, jac, 1, nullptr);
+}
+
+// ... at second order (order = 2): the mean's model is (Z, alpha_u), as in gpk_sparse_predict_hess; corr (H, R, P), may be null
+extern "C" int gpk_sparse_propagate2(gpk_handle h, int var_includes_noise, const double* x0, int x0_rows, const double* U, int u_rows,
+                                     const double* lin, const double* Sigma0, int s_rows, const double* Q, int R, int H, double* traj,
+                                     double* Sigma, double* mean, double* var, double* jac, int order, double* corr) {
+  return sparse_propagate_any(h, "sparse_propagate2: ", var_includes_noise, x0, x0_rows, U, u_rows, lin, Sigma0, s_rows, Q, R, H, traj,
+                              Sigma, mean, var, jac, order, corr);
+}
+
+static int sparse_propagate_multi_any(gpk_handle h, const char* entry, int B, const gpk_handle* models, int var_includes_noise, int nx,
+                                      const int* coord, const double* in_shift, const double* in_scale, const double* out_shift,
+                                      const double* out_scale, const double* x0, int x0_rows, const double* U, int u_rows,
+                                      const double* lin, const double* Sigma0, int s_rows, const double* Q, int R, int H,
+                                      double* traj, double* Sigma, double* mean, double* var, double* jac, int order, double* corr) {
   if (!h) return GPK_BAD_ARG;
-  const std::string who("sparse_propagate_multi: ");
+  const std::string who(std::string(entry) + ": ");
   GPK_REQUIRE(h, B >= 1 && B <= GPK_SMALL_MAX_MODELS, who + "1..8 models");
   GPK_REQUIRE(h, models && coord, who + "null pointer");
   GPK_REQUIRE(h, h->batch == 1, who + "not available in batched mode");
@@ -1416,7 +1431,7 @@ extern "C" int gpk_sparse_propagate_multi(gpk_handle h, int B, const gpk_handle*
   GPK_REQUIRE(h, (in_shift == nullptr) == (in_scale == nullptr), who + "in_shift and in_scale go together");
   GPK_REQUIRE(h, (out_shift == nullptr) == (out_scale == nullptr), who + "out_shift and out_scale go together");
   gpk_sparse* list[GPK_SMALL_MAX_MODELS];
-  GPK_TRY(sparse_batch_models(h, "sparse_propagate_multi", B, models, list));
+  GPK_TRY(sparse_batch_models(h, entry, B, models, list));
   const int D = list[0]->D;
   GPK_REQUIRE(h, D >= 1 && D <= GPK_PROP_MAX_D && nx >= B && nx <= D, who + "the state dimension nx must be in [B, D], D <= 16");
   GPK_CHECK_HIP(h, hipSetDevice(h->device));
@@ -1451,8 +1466,30 @@ extern "C" int gpk_sparse_propagate_multi(gpk_handle h, int B, const gpk_handle*
       sb.y_std[b] = out_scale[b] * sb.y_std[b];
     }
   }
-  const Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean, var, jac};
+  const Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean, var, jac, order, corr};
   return gpk_propagate_run(h, who, sb.models(), k, z);
+}
+
+extern "C" int gpk_sparse_propagate_multi(gpk_handle h, int B, const gpk_handle* models, int var_includes_noise, int nx,
+                                          const int* coord, const double* in_shift, const double* in_scale, const double* out_shift,
+                                          const double* out_scale, const double* x0, int x0_rows, const double* U, int u_rows,
+                                          const double* lin, const double* Sigma0, int s_rows, const double* Q, int R, int H,
+                                          double* traj, double* Sigma, double* mean, double* var, double* jac) {
+  return sparse_propagate_multi_any(h, "sparse_propagate_multi", B, models, var_includes_noise, nx, coord, in_shift, in_scale, out_shift,
+                                    out_scale, x0, x0_rows, U, u_rows, lin, Sigma0, s_rows, Q, R, H, traj, Sigma, mean, var, jac, 1,
+                                    nullptr);
+}
+
+// ... at second order: the output scaler folded into y_std scales c as it scales the mean; corr (H, R, B), may be null
+extern "C" int gpk_sparse_propagate2_multi(gpk_handle h, int B, const gpk_handle* models, int var_includes_noise, int nx,
+                                           const int* coord, const double* in_shift, const double* in_scale, const double* out_shift,
+                                           const double* out_scale, const double* x0, int x0_rows, const double* U, int u_rows,
+                                           const double* lin, const double* Sigma0, int s_rows, const double* Q, int R, int H,
+                                           double* traj, double* Sigma, double* mean, double* var, double* jac, int order,
+                                           double* corr) {
+  return sparse_propagate_multi_any(h, "sparse_propagate2_multi", B, models, var_includes_noise, nx, coord, in_shift, in_scale,
+                                    out_shift, out_scale, x0, x0_rows, U, u_rows, lin, Sigma0, s_rows, Q, R, H, traj, Sigma, mean, var,
+                                    jac, order, corr);
 }
 
 extern "C" int gpk_sparse_export(gpk_handle h, int64_t* m, int* D, int* P, int* n_ls, double* Z, double* G, double* g, double* yy,

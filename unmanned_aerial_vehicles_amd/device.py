@@ -922,25 +922,31 @@ class DeviceGP:
         """The one-call horizon propagation (gpk_propagate_host) applies: the small-batch path's sizes, not switched off."""
         return self.factored and self.D <= 16 and self.Np <= 16384 and int(self.be.options.get("small_path", 1)) != 0
 
-    def propagate_host(self, y_mean, y_std, kss, floor, add_noise, noise, x0, U, lin, S0, Q, R, H, stages):
+    def propagate_host(self, y_mean, y_std, kss, floor, add_noise, noise, x0, U, lin, S0, Q, R, H, stages, order=1):
         """One C call per horizon (gpk_propagate_host; arguments as `propagate.check_horizon` returns them): traj (H + 1, R, P),
         Sigma (H + 1, R, P, P) and, with `stages`, the stage quantities mean, var (H, R, P) and jac (H, R, P, D) in target
-        units - three launches per stage, one synchronisation.  ValueError, with the library's message, where the entry refuses
-        its arguments."""
+        units - three launches per stage, one synchronisation.  order=2 (gpk_propagate2_host, four launches per stage): the
+        second-order mean; a sixth result, corr (H, R, P) or None without `stages`.  ValueError, with the library's message,
+        where the entry refuses its arguments."""
         assert self.factored
         self._refuse_replica()
         P, D = self.P, self.D
         traj, Sigma = np.empty((H + 1, R, P)), np.empty((H + 1, R, P, P))
         mean, var, jac = (np.empty((H, R, P)), np.empty((H, R, P)), np.empty((H, R, P, D))) if stages else (None, None, None)
+        tail = (float(kss), float(floor), int(bool(add_noise)), float(noise), _hp(x0), x0.shape[0], _hp(U) if D > P else None,
+                U.shape[0], _hp(lin), _hp(S0), 1 if S0 is None else S0.shape[0], _hp(Q), R, H, _hp(traj), _hp(Sigma), _hp(mean),
+                _hp(var), _hp(jac))
         try:
-            self._host_call("gpk_propagate_host", y_mean, y_std, True, float(kss), float(floor), int(bool(add_noise)),
-                            float(noise), _hp(x0), x0.shape[0], _hp(U) if D > P else None, U.shape[0], _hp(lin), _hp(S0),
-                            1 if S0 is None else S0.shape[0], _hp(Q), R, H, _hp(traj), _hp(Sigma), _hp(mean), _hp(var), _hp(jac))
+            if order == 1:
+                self._host_call("gpk_propagate_host", y_mean, y_std, True, *tail)
+            else:
+                corr = np.empty((H, R, P)) if stages else None
+                self._host_call("gpk_propagate2_host", y_mean, y_std, True, *tail, int(order), _hp(corr))
         except GPKError as e:      # a limit of the entry: the caller's arguments, with the library's message
             if e.code == _lib.GPK_BAD_ARG:
                 raise ValueError(str(e)) from None
             raise
-        return traj, Sigma, mean, var, jac
+        return (traj, Sigma, mean, var, jac) if order == 1 else (traj, Sigma, mean, var, jac, corr)
 
     # ---- gated serving: the one place every fp32 surface (estimator, sharded predictor, package GP, per-axis models) goes
     # through -------------------------------------------------------------------------------------------------------------

@@ -449,7 +449,7 @@ class GaussianProcessRegressor:
         return mean, dmean, hess
 
     def propagate(self, x0, U, lin, Sigma0=None, process_noise=None, var_includes_noise=False, return_stages=False,
-                  route="auto"):
+                  route="auto", order=1):
         """The posterior's own closed-loop horizon: the mean trajectory under the learned dynamics and the state covariance that
         the model's uncertainty induces along it, to first order (`propagate`'s module docstring has the recursion).  The state
         is the model's P outputs; a query is q = [x, u] (D = P + nu).  x0 (P,) or (R, P), U (H, nu) or (R, H, nu), lin (P, D) the
@@ -460,8 +460,13 @@ class GaussianProcessRegressor:
         used: with var_includes_noise=True they have the bits of `predict_jacobian(q, return_var=True)` at the returned rows.
         One C call per horizon (three launches per stage, one synchronisation) up to 16 384 training rows; beyond that, or with
         the backend option small_path=0, or with route="host", the same recursion as a host loop over `predict_jacobian`.
+        order=2: the mean takes the second-order term of E[mu(x)] for x ~ N(x_h, Sigma_h), c = tr(H Sigma_h) / 2 over the state
+        block of the mean's Hessian, added last to each stage's mean; A_h and Sigma are formed as at first order.  Still one C
+        call (`gpk_propagate2_host`: four launches per stage, no Hessian is formed); the host loop contracts `predict_hessian`.
+        The stages gain "corr" (H, R, P).  Any other order: ValueError.
         A fitted model only (RuntimeError); ValueError for a wrong shape, R > 32, H outside 1 .. 256, non-finite input."""
         from . import propagate as _pg
+        order = _pg.check_order(order)
         if not hasattr(self, "X_train_"):
             raise RuntimeError("This GaussianProcessRegressor instance is not fitted yet.")
         P, D = self._yn.shape[1], self.n_features_in_
@@ -474,10 +479,13 @@ class GaussianProcessRegressor:
             raise ValueError("route must be 'auto' or 'host'")
         if route == "auto" and dev.propagate_ok():
             # (the noise enters through the prior variance the clip starts from, as in predict_jacobian: the same bits)
-            traj, Sigma, mean, var, jac = dev.propagate_host(self._y_train_mean, self._y_train_std,
-                                                             comp.sf2 + (noise if var_includes_noise else 0.0), 0.0, False, 0.0,
-                                                             x0, U, lin, S0, Q, R, H, return_stages)
-            return (traj, Sigma, {"mean": mean, "var": var, "jac": jac}) if return_stages else (traj, Sigma)
+            traj, Sigma, mean, var, jac, *corr = dev.propagate_host(self._y_train_mean, self._y_train_std,
+                                                                    comp.sf2 + (noise if var_includes_noise else 0.0), 0.0, False,
+                                                                    0.0, x0, U, lin, S0, Q, R, H, return_stages, order)
+            stages = {"mean": mean, "var": var, "jac": jac}
+            if order == 2:
+                stages["corr"] = corr[0]
+            return (traj, Sigma, stages) if return_stages else (traj, Sigma)
         std2 = self._y_train_std ** 2
 
         def stage(q):
@@ -487,7 +495,8 @@ class GaussianProcessRegressor:
                 var = np.maximum(var - noise * std2[None, :], 0.0)
             return mean.reshape(R, P), dmean.reshape(R, P, D), var
 
-        traj, Sigma, stages = _pg.host_loop(stage, list(range(P)), x0, U, lin, S0, Q, R, H)
+        hess_stage = (lambda q: self.predict_hessian(q)[2]) if order == 2 else None
+        traj, Sigma, stages = _pg.host_loop(stage, list(range(P)), x0, U, lin, S0, Q, R, H, hess_stage)
         return (traj, Sigma, stages) if return_stages else (traj, Sigma)
 
     def sample_y(self, X, n_samples=1, random_state=0):

@@ -12,6 +12,14 @@ launches per stage, one synchronisation); what is
 here is what they share on the host: the argument checks (before any device call), the same recursion as a host loop over a
 model's `predict_jacobian(..., return_var=True)` - the "auto" and "host" routes of the sparse models, the route of exact models
 beyond the small-batch path and of option small_path=0 - and what the control-loop wrappers (`propagate_horizon`) share, their nominal fallback included.
+
+`order=2` on every `propagate` adds the second-order term of E[mu(x)] for x ~ N(x_h, Sigma_h) to the mean,
+
+    c_b = 1/2 sum_{d,e < nx} H_b[d][e] Sigma_h[d][e],      x_{h+1} = (x_h + lin q + sum_b e_coord[b] mu_b) + sum_b e_coord[b] c_b,
+
+H_b = d2 mu_b / dq2; A_h and Sigma_{h+1} stay as above.  The one-call entries (`gpk_propagate2_host[_multi]`,
+`gpk_sparse_propagate2[_multi]`: four launches per stage) contract H with Sigma without forming it; `host_loop` takes a
+second-order stage callback built from the class's own `predict_hessian`.
 """
 from __future__ import annotations
 
@@ -80,14 +88,24 @@ def check_coord(coord, B, nx):
     return coord
 
 
-def host_loop(stage, coord, x0, U, lin, S0, Q, R, H):
+def check_order(order):
+    """`order` as 1 or 2; ValueError for anything else."""
+    if isinstance(order, bool) or order not in (1, 2):
+        raise ValueError(f"propagate: order must be 1 or 2, got {order!r}")
+    return int(order)
+
+
+def host_loop(stage, coord, x0, U, lin, S0, Q, R, H, hess_stage=None):
     """The recursion on the host.  stage(q (R, D) raw) -> (mean (R, NO), jac (R, NO, D) per unit of the raw query, var (R, NO));
     output o drives state coordinate coord[o].  Returns traj (H + 1, R, nx), Sigma (H + 1, R, nx, nx) and the stage quantities
-    {"mean" (H, R, NO), "var" (H, R, NO), "jac" (H, R, NO, D)}."""
+    {"mean" (H, R, NO), "var" (H, R, NO), "jac" (H, R, NO, D)}.
+    hess_stage (second order): hess_stage(q (R, D) raw) -> the mean's Hessian (R, NO, D, D) per unit of the raw query; the
+    stage's mean then takes c_o = tr(H_o[:nx, :nx] Sigma_h) / 2, added last, and the stages gain "corr" (H, R, NO)."""
     nx, D = lin.shape
     NO = len(coord)
     traj, Sigma = np.zeros((H + 1, R, nx)), np.zeros((H + 1, R, nx, nx))
     means, vars_, jacs = np.zeros((H, R, NO)), np.zeros((H, R, NO)), np.zeros((H, R, NO, D))
+    corrs = np.zeros((H, R, NO))
     traj[0] = np.broadcast_to(x0, (R, nx))
     if S0 is not None:
         Sigma[0] = np.broadcast_to(S0, (R, nx, nx))
@@ -106,8 +124,16 @@ def host_loop(stage, coord, x0, U, lin, S0, Q, R, H):
         S += A @ Sigma[h] @ A.transpose(0, 2, 1)
         if Q is not None:
             S += Q
+        if hess_stage is not None:
+            hess = np.asarray(hess_stage(np.ascontiguousarray(q))).reshape(R, NO, D, D)
+            corrs[h] = 0.5 * np.einsum("rode,rde->ro", hess[:, :, :nx, :nx], Sigma[h])
+            for o, c in enumerate(coord):
+                x[:, c] += corrs[h][:, o]
         traj[h + 1], Sigma[h + 1] = x, 0.5 * (S + S.transpose(0, 2, 1))
-    return traj, Sigma, {"mean": means, "var": vars_, "jac": jacs}
+    stages = {"mean": means, "var": vars_, "jac": jacs}
+    if hess_stage is not None:
+        stages["corr"] = corrs
+    return traj, Sigma, stages
 
 
 # ---- what the batches (BatchedARDGP, BatchedSparseGP) share: raw units around single-output models --------------------------------
@@ -176,6 +202,19 @@ def batch_stage(predict_jacobian, level, in_shift, in_scale, o_mean, o_scale, va
         return o_mean + o_scale * mean, o_scale[None, :, None] * dmean, o_scale ** 2 * var
 
     return stage
+
+
+def batch_hess_stage(predict_hessian, in_shift, in_scale, o_scale):
+    """The second-order `host_loop` stage of a batch: predict_hessian(z) -> (_, _, hess (R, B, D, D)) on the scaled rows, returned
+    per unit of the raw query and behind the output scaler, as `batch_stage` returns the Jacobian."""
+    def hess_stage(q):
+        z = q if in_shift is None else (q - in_shift) / in_scale
+        hess = predict_hessian(z)[2]
+        if in_scale is not None:
+            hess = hess / (in_scale[None, None, :, None] * in_scale[None, None, None, :])
+        return o_scale[None, :, None, None] * hess
+
+    return hess_stage
 
 
 def noise_levels(models):

@@ -490,7 +490,7 @@ class SparseGP:
         return np.hstack(y_samples)
 
     def propagate(self, x0, U, lin, Sigma0=None, process_noise=None, var_includes_noise=False, return_stages=False,
-                  route="auto"):
+                  route="auto", order=1):
         """`GaussianProcessRegressor.propagate` on the sparse posterior: the mean rollout with the linearised state covariance,
         same arguments and results.  route="auto" and "host": the recursion as a host loop over
         `predict_jacobian(..., return_var=True)`, one call and one synchronisation per stage.  route="chain": ONE C call per
@@ -498,8 +498,11 @@ class SparseGP:
         quantities have the bits of `predict_jacobian(q, return_var=True)` at the returned rows; with False the latent
         variance is kss = sf2 clipped at 1e-10 y_std^2 where the loop forms max(noisy - level, 0) - a difference in rounding
         while neither clip is active).  ValueError where `propagate_ok()` does not hold, with the reason, or where the entry
-        refuses its arguments, with the library's message."""
+        refuses its arguments, with the library's message.  order=2: the second-order mean, on every route (chain:
+        `gpk_sparse_propagate2`, four launches per stage, the mean's model (Z, alpha_u) as in `predict_hessian`; the host loop
+        contracts `predict_hessian`); the stages gain "corr" (H, R, P)."""
         from . import propagate as _pg
+        order = _pg.check_order(order)
         _pg.check_route(route, ("auto", "host", "chain"))
         P, D = self.n_outputs_, self.n_features_in_
         x0, U, lin, S0, Q, R, H = _pg.check_horizon(x0, U, lin, P, D, Sigma0, process_noise)
@@ -510,16 +513,21 @@ class SparseGP:
             self._ensure()
             traj, Sigma = np.empty((H + 1, R, P)), np.empty((H + 1, R, P, P))
             mean, var, jac = (np.empty((H, R, P)), np.empty((H, R, P)), np.empty((H, R, P, D))) if return_stages else (None,) * 3
+            args = (int(bool(var_includes_noise)), _ptr(x0), x0.shape[0], _ptr(U) if D > P else None, U.shape[0], _ptr(lin),
+                    _ptr(S0), 1 if S0 is None else S0.shape[0], _ptr(Q), R, H, _ptr(traj), _ptr(Sigma), _ptr(mean), _ptr(var),
+                    _ptr(jac))
+            stages = {"mean": mean, "var": var, "jac": jac}
             try:
-                self._backend().call("gpk_sparse_propagate", int(bool(var_includes_noise)), _ptr(x0), x0.shape[0],
-                                     _ptr(U) if D > P else None, U.shape[0], _ptr(lin), _ptr(S0),
-                                     1 if S0 is None else S0.shape[0], _ptr(Q), R, H, _ptr(traj), _ptr(Sigma), _ptr(mean),
-                                     _ptr(var), _ptr(jac))
+                if order == 1:
+                    self._backend().call("gpk_sparse_propagate", *args)
+                else:
+                    stages["corr"] = np.empty((H, R, P)) if return_stages else None
+                    self._backend().call("gpk_sparse_propagate2", *args, order, _ptr(stages["corr"]))
             except _lib.GPKError as e:      # a limit of the entry: the caller's arguments, with the library's message
                 if e.code == _lib.GPK_BAD_ARG:
                     raise ValueError(str(e)) from None
                 raise
-            return (traj, Sigma, {"mean": mean, "var": var, "jac": jac}) if return_stages else (traj, Sigma)
+            return (traj, Sigma, stages) if return_stages else (traj, Sigma)
         noise = self.kernel_.components().noise or 0.0
         std2 = np.broadcast_to(np.asarray(self._y_train_std, dtype=np.float64).reshape(-1), (P,)) ** 2
 
@@ -530,7 +538,8 @@ class SparseGP:
                 var = np.maximum(var - noise * std2[None, :], 0.0)
             return mean.reshape(R, P), dmean.reshape(R, P, D), var
 
-        traj, Sigma, stages = _pg.host_loop(stage, list(range(P)), x0, U, lin, S0, Q, R, H)
+        hess_stage = (lambda q: self.predict_hessian(q)[2]) if order == 2 else None
+        traj, Sigma, stages = _pg.host_loop(stage, list(range(P)), x0, U, lin, S0, Q, R, H, hess_stage)
         return (traj, Sigma, stages) if return_stages else (traj, Sigma)
 
     def _propagate_refusal(self):

@@ -153,14 +153,17 @@ class BatchedSparseGP:
         return mean, dmean, hess
 
     def propagate(self, x0, U, lin, coord=None, in_scaler=None, Sigma0=None, process_noise=None, var_includes_noise=False,
-                  return_stages=False, out_scaler=None, route="auto"):
+                  return_stages=False, out_scaler=None, route="auto", order=1):
         """`BatchedARDGP.propagate` on the sparse posteriors: the batch's mean rollout with the linearised state covariance in
         raw units, same arguments and results.  route="auto" and "host": the recursion as a host loop over
         `predict_jacobian(..., return_var=True)` - one C call for all models and one synchronisation per stage.
         route="chain": ONE C call per horizon for all models (`gpk_sparse_propagate_multi`: three launches per stage, one
         synchronisation; the scalers go into the call; the latent variance as `SparseGP.propagate` describes it).  ValueError
-        where `propagate_ok()` does not hold, with the reason, or where the entry refuses its arguments."""
+        where `propagate_ok()` does not hold, with the reason, or where the entry refuses its arguments.  order=2: the
+        second-order mean on every route (chain: `gpk_sparse_propagate2_multi`, four launches per stage; the host loop contracts
+        `predict_hessian`); the stages gain "corr" (H, R, B)."""
         from . import propagate as _pg
+        order = _pg.check_order(order)
         B, D = len(self.models), self.n_features_in_
         x0, U, lin, S0, Q, R, H, coord, in_shift, in_scale, o_mean, o_scale = _pg.check_batch(
             B, D, x0, U, lin, coord, in_scaler, out_scaler, Sigma0, process_noise, route, routes=("auto", "host", "chain"))
@@ -175,20 +178,26 @@ class BatchedSparseGP:
             scaled = out_scaler is not None
             om = np.ascontiguousarray(o_mean, dtype=np.float64) if scaled else None
             osc = np.ascontiguousarray(o_scale, dtype=np.float64) if scaled else None
+            args = (int(bool(var_includes_noise)), nx, cd, _ptr(in_shift), _ptr(in_scale), _ptr(om), _ptr(osc), _ptr(x0), x0.shape[0],
+                    _ptr(U) if D > nx else None, U.shape[0], _ptr(lin), _ptr(S0), 1 if S0 is None else S0.shape[0], _ptr(Q), R, H,
+                    _ptr(traj), _ptr(Sigma), _ptr(mean), _ptr(var), _ptr(jac))
+            stages = {"mean": mean, "var": var, "jac": jac}
             try:
                 with self._serving() as (be, handles):
-                    be.call("gpk_sparse_propagate_multi", B, handles, int(bool(var_includes_noise)), nx, cd, _ptr(in_shift),
-                            _ptr(in_scale), _ptr(om), _ptr(osc), _ptr(x0), x0.shape[0], _ptr(U) if D > nx else None, U.shape[0],
-                            _ptr(lin), _ptr(S0), 1 if S0 is None else S0.shape[0], _ptr(Q), R, H, _ptr(traj), _ptr(Sigma),
-                            _ptr(mean), _ptr(var), _ptr(jac))
+                    if order == 1:
+                        be.call("gpk_sparse_propagate_multi", B, handles, *args)
+                    else:
+                        stages["corr"] = np.empty((H, R, B)) if return_stages else None
+                        be.call("gpk_sparse_propagate2_multi", B, handles, *args, order, _ptr(stages["corr"]))
             except _lib.GPKError as e:      # a limit of the entry: the caller's arguments, with the library's message
                 if e.code == _lib.GPK_BAD_ARG:
                     raise ValueError(str(e)) from None
                 raise
-            return (traj, Sigma, {"mean": mean, "var": var, "jac": jac}) if return_stages else (traj, Sigma)
+            return (traj, Sigma, stages) if return_stages else (traj, Sigma)
         stage = _pg.batch_stage(self.predict_jacobian, _pg.noise_levels(self.models), in_shift, in_scale, o_mean, o_scale,
                                 var_includes_noise)
-        traj, Sigma, stages = _pg.host_loop(stage, coord, x0, U, lin, S0, Q, R, H)
+        hess_stage = _pg.batch_hess_stage(self.predict_hessian, in_shift, in_scale, o_scale) if order == 2 else None
+        traj, Sigma, stages = _pg.host_loop(stage, coord, x0, U, lin, S0, Q, R, H, hess_stage)
         return (traj, Sigma, stages) if return_stages else (traj, Sigma)
 
     def _propagate_refusal(self, nx=None):

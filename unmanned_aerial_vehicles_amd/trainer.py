@@ -578,7 +578,7 @@ class PreTrainedGP:
             print(f"GP rollout sampling failed: {e}")
             return fallback
 
-    def propagate_horizon(self, state, U_guess, dt, Sigma0=None, process_noise=None):
+    def propagate_horizon(self, state, U_guess, dt, Sigma0=None, process_noise=None, order=1):
         """`SimpleQuadrotorGP.propagate_horizon` for the per-axis models, in raw units: the closed loop of the posterior MEANS
         and the state covariance the models' uncertainty induces along it, to first order,
 
@@ -592,8 +592,11 @@ class PreTrainedGP:
         model over `predict_residual_jacobian_batch`.  The variances are the latent functions' on both routes.  state (6,);
         U_guess (4, N) -> X (6, N + 1), Sigma (N + 1, 6, 6); U_guess (R, 4, N) -> (R, 6, N + 1), (R, N + 1, 6, 6).  A residual
         without a model leaves its coordinate nominal.  Not loaded, or any failure (printed): the nominal trajectory and
-        Sigma_{k+1} = (I + lin_x) Sigma_k (I + lin_x)^T + Q - it never raises into the control loop."""
+        Sigma_{k+1} = (I + lin_x) Sigma_k (I + lin_x)^T + Q - it never raises into the control loop.  order=2: x_{k+1} also takes
+        tr(H_i Sigma_k) / 2 per model, H_i the state block of mu_i's raw Hessian (the batches' `propagate`; model by model over
+        `predict_residual_hessian_batch`); any other order: ValueError."""
         from . import propagate as _pg
+        order = _pg.check_order(order)
         state, U, lin, nominal, single = _pg.horizon_inputs(GPTrainer._nominal_dynamics, state, U_guess, dt)
         try:
             if not self.is_loaded:
@@ -606,7 +609,7 @@ class PreTrainedGP:
                                            in_scaler=self.scalers_X[names[0]], Sigma0=Sigma0, process_noise=process_noise,
                                            out_scaler=([float(np.ravel(s.mean_)[0]) for s in sys_],
                                                        [float(np.ravel(s.scale_)[0]) for s in sys_]),
-                                           route=_pg.wrapper_route(bg))
+                                           route=_pg.wrapper_route(bg), order=order)
             else:
                 coord = [i for i, n in enumerate(OUTPUT_NAMES) if n in self.gp_models]
                 x0, Uc, linc, S0, Q, R, H = _pg.check_horizon(state, U, lin, 6, 10, Sigma0, process_noise)
@@ -620,7 +623,8 @@ class PreTrainedGP:
                     mean, J, std, _ = self.predict_residual_jacobian_batch(q, return_std=True)
                     return mean[:, coord], J[:, coord, :], np.maximum(std[:, coord] ** 2 - lvl[None, :], 0.0)
 
-                traj, Sigma, _ = _pg.host_loop(stage, coord, x0, Uc, linc, S0, Q, R, H)
+                hess_stage = (lambda q: self.predict_residual_hessian_batch(q)[2][:, coord]) if order == 2 else None
+                traj, Sigma, _ = _pg.host_loop(stage, coord, x0, Uc, linc, S0, Q, R, H, hess_stage)
             if not (np.isfinite(traj).all() and np.isfinite(Sigma).all()):
                 raise FloatingPointError("non-finite trajectory or covariance")
             return _pg.horizon_layout(traj, Sigma, single)
