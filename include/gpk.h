@@ -1213,6 +1213,65 @@ GPK_API int gpk_sparse_propagate2_multi(gpk_handle h, int B, const gpk_handle* m
                                         double* traj, double* Sigma, double* mean, double* var, double* jac, int order,
                                         double* corr);
 
+/* ... with the gradient of a horizon cost l(X, Sigma) with respect to the controls, the start state and the start covariance
+ * (order 1 only): the four first-order entries with five more arguments.  The caller supplies the seeds
+ *   gx (H + 1 x R x nx) = dl/dx_h,   gS (H + 1 x R x nx x nx) = dl/dSigma_h, entries taken as independent (NULL: zero); the
+ *   entry uses (gS + gS^T) / 2
+ * and receives dU (R x H x nu; NULL when nu = 0), dx0 (R x nx) and dSigma0 (R x nx x nx, may be NULL) - one row per rollout,
+ * also where x0, U or Sigma0 came as one shared row.  The forward recursion is the one above; the backward sweep starts from
+ * lam_H = gx_H, Lam_H = sym(gS_H) and runs, for h = H - 1 .. 0 and c_b = coord[b],
+ *   F_h   = [I 0] + lin + sum_b e_c J_b                      (nx x D: all D columns of the Jacobian, RAW units)
+ *   G_h   = Lam_{h+1} A_h Sigma_h
+ *   w_b   = [G_h[c_b, :nx], 0 .. 0]
+ *   g_q   = F_h^T lam_{h+1} + sum_b Lam_{h+1}[c_b][c_b] grad_q v_b + 2 sum_b H_b w_b        (H_b = d^2 mu_b / d q^2, RAW units)
+ *   lam_h = gx_h + g_q[:nx],   dU_h = g_q[nx:],   Lam_h = sym(gS_h) + A_h^T Lam_{h+1} A_h   (lower triangle formed and mirrored)
+ * dx0 = lam_0, dSigma0 = Lam_0 (symmetric bit for bit).  grad v_b is the gradient of the unclipped variance, as
+ * gpk_predict_host[_multi]_grad / gpk_sparse_predict[_multi]_grad return it; it does not depend on var_includes_noise.  No
+ * Hessian is formed: with delta_j = (z - X_j) / ls, k_j = sf2 exp(-|delta_j|^2 / 2) and wh_d = w_d / (ls_d in_scale_d) (model b's
+ * own length-scales)
+ *   (H_b w)_e = y_std[b] / (ls_e in_scale_e) (sum_j alpha_jb k_j delta_je (delta_j . wh) - wh_e sum_j alpha_jb k_j)
+ * - D + 1 sums per (rollout, output).  Launches: 6 H.  Forward, per stage: the three small-batch launches of the gradient
+ * entries (mean, Jacobian, variance and its gradient; mean, Jacobian and variance with the bits of the two-launch stage) and
+ * the unchanged advance launch; the scaled queries, Sigma_h, the Jacobians and the variance gradients of every stage stay on
+ * the device, H R (D + nx^2 + outputs 2 D) doubles.  Backward, per stage: one Hessian-vector launch (at most 64 workgroups
+ * per model, each its rows' share of the sums, K* recomputed from the stored queries, its own rows of G_h formed from the
+ * device state; no ticket, no atomics, no inverse factor) and one adjoint launch (one workgroup per rollout; it adds the
+ * shares in workgroup order).  One upload with the seeds included, ONE synchronisation, the downloads after it.  traj, Sigma,
+ * mean, var and jac have the BITS of the first-order sibling on the same arguments.  The sparse pair takes (Z, alpha_u) as the
+ * mean's model, as gpk_sparse_predict_hess.
+ *   Replaces: the reverse sweep on the host around H calls of gpk_predict_host[_multi]_grad and H calls of
+ *   gpk_predict_host[_multi]_hess (the sparse pair: gpk_sparse_predict[_multi]_grad / _hess) - 2 H synchronisations and
+ *   H R outputs D^2 Hessian entries through host memory, of which the sweep reads one contraction per output - or
+ *   2 H nu + 1 calls of the first-order sibling for central differences; in the reference, nothing.
+ * Limits and refusals are the siblings'; also GPK_BAD_ARG (with a message, before any launch, the outputs untouched): NULL gx
+ * or dx0, NULL dU with nu > 0, NaN or infinity in a seed.                                                                  */
+GPK_API int gpk_propagate_grad_host(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
+                                    double sf2, const double* y_mean, const double* y_std, const double* W, int64_t Np,
+                                    int64_t ldw, double kss, double floor_, int var_includes_noise, double noise, const double* x0,
+                                    int x0_rows, const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows,
+                                    const double* Q, int R, int H, double* traj, double* Sigma, double* mean, double* var,
+                                    double* jac, const double* gx, const double* gS, double* dU, double* dx0, double* dSigma0);
+GPK_API int gpk_propagate_grad_host_multi(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D,
+                                          const double* ls, const double* sf2, const double* y_mean, const double* y_std,
+                                          const double* const* W, int64_t Np, int64_t ldw, const double* kss, double floor_,
+                                          int var_includes_noise, const double* noise, int nx, const int* coord,
+                                          const double* in_shift, const double* in_scale, const double* x0, int x0_rows,
+                                          const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows,
+                                          const double* Q, int R, int H, double* traj, double* Sigma, double* mean, double* var,
+                                          double* jac, const double* gx, const double* gS, double* dU, double* dx0,
+                                          double* dSigma0);
+GPK_API int gpk_sparse_propagate_grad(gpk_handle h, int var_includes_noise, const double* x0, int x0_rows, const double* U,
+                                      int u_rows, const double* lin, const double* Sigma0, int s_rows, const double* Q, int R, int H,
+                                      double* traj, double* Sigma, double* mean, double* var, double* jac, const double* gx,
+                                      const double* gS, double* dU, double* dx0, double* dSigma0);
+GPK_API int gpk_sparse_propagate_grad_multi(gpk_handle h, int B, const gpk_handle* models, int var_includes_noise, int nx,
+                                            const int* coord, const double* in_shift, const double* in_scale,
+                                            const double* out_shift, const double* out_scale, const double* x0, int x0_rows,
+                                            const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows,
+                                            const double* Q, int R, int H, double* traj, double* Sigma, double* mean, double* var,
+                                            double* jac, const double* gx, const double* gS, double* dU, double* dx0,
+                                            double* dSigma0);
+
 #ifdef __cplusplus
 }
 #endif

@@ -188,6 +188,11 @@ SIGNATURES["gpk_propagate2_host"] = (_int, SIGNATURES["gpk_propagate_host"][1] +
 SIGNATURES["gpk_propagate2_host_multi"] = (_int, SIGNATURES["gpk_propagate_host_multi"][1] + [_int, _vp])
 SIGNATURES["gpk_sparse_propagate2"] = (_int, SIGNATURES["gpk_sparse_propagate"][1] + [_int, _dp])
 SIGNATURES["gpk_sparse_propagate2_multi"] = (_int, SIGNATURES["gpk_sparse_propagate_multi"][1] + [_int, _dp])
+# ... with the gradient of a horizon cost: the four first-order entries with (gx, gS, dU, dx0, dSigma0) appended
+SIGNATURES["gpk_propagate_grad_host"] = (_int, SIGNATURES["gpk_propagate_host"][1] + [_vp] * 5)
+SIGNATURES["gpk_propagate_grad_host_multi"] = (_int, SIGNATURES["gpk_propagate_host_multi"][1] + [_vp] * 5)
+SIGNATURES["gpk_sparse_propagate_grad"] = (_int, SIGNATURES["gpk_sparse_propagate"][1] + [_dp] * 5)
+SIGNATURES["gpk_sparse_propagate_grad_multi"] = (_int, SIGNATURES["gpk_sparse_propagate_multi"][1] + [_dp] * 5)
 
 _lib = None
 

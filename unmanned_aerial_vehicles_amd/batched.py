@@ -464,6 +464,50 @@ class BatchedARDGP:
         traj, Sigma, stages = _pg.host_loop(stage, coord, x0, U, lin, S0, Q, R, H, hess_stage)
         return (traj, Sigma, stages) if return_stages else (traj, Sigma)
 
+    def propagate_gradient(self, x0, U, lin, grad_traj, grad_Sigma=None, coord=None, in_scaler=None, Sigma0=None,
+                           process_noise=None, var_includes_noise=False, out_scaler=None, route="auto", order=1):
+        """`propagate` with the gradient of a horizon cost, in raw units: `GaussianProcessRegressor.propagate_gradient` with the
+        batch's conventions (coord, in_scaler, out_scaler as `propagate`).  grad_traj (H + 1, R, nx), grad_Sigma (H + 1, R, nx,
+        nx); returns (traj, Sigma, dU (R, H, nu), dx0 (R, nx), dSigma0 (R, nx, nx)), traj and Sigma with the bits of
+        `propagate`.  One C call per horizon for all models (`gpk_propagate_grad_host_multi`, six launches per stage) where
+        `propagate` makes one; otherwise (or route="host") the sweep on the host over `predict_jacobian` and
+        `predict_hessian`.  order: 1 only (ValueError)."""
+        from . import propagate as _pg
+        _pg.check_grad_order(order)
+        if not self.models:
+            raise RuntimeError("this BatchedARDGP is not fitted yet")
+        B = len(self.models)
+        D = self.models[0].n_features_in_
+        x0, U, lin, S0, Q, R, H, coord, in_shift, in_scale, o_mean, o_scale = _pg.check_batch(
+            B, D, x0, U, lin, coord, in_scaler, out_scaler, Sigma0, process_noise, route)
+        nx = lin.shape[0]
+        gx, gS = _pg.check_seeds(grad_traj, grad_Sigma, R, H, nx)
+        sv = self._serve_state(True, any_dtype=True) if route == "auto" else None
+        if sv is not None and int(sv["dev0"].be.options.get("small_path", 1)) != 0:
+            d0 = sv["dev0"]
+            ym, ys = sv["ym"], sv["ys"]
+            if out_scaler is not None:
+                ym, ys = np.ascontiguousarray(o_mean + o_scale * sv["ym"]), np.ascontiguousarray(o_scale * sv["ys"])
+            kss = sv["kss"] if var_includes_noise else sv["sf2"]
+            traj, Sigma = np.empty((H + 1, R, nx)), np.empty((H + 1, R, nx, nx))
+            dU, dx0, dS0 = np.zeros((R, H, D - nx)), np.empty((R, nx)), np.empty((R, nx, nx))
+            cd = (C.c_int * B)(*coord)
+            try:
+                d0.be.call("gpk_propagate_grad_host_multi", B, sv["X"], sv["alpha"], d0.N, d0.D, _hp(sv["ls"]), _hp(sv["sf2"]),
+                           _hp(ym), _hp(ys), sv["W"], d0.Np, d0.Np, _hp(kss), 0.0, 0, None, nx, cd, _hp(in_shift), _hp(in_scale),
+                           _hp(x0), x0.shape[0], _hp(U) if D > nx else None, U.shape[0], _hp(lin), _hp(S0),
+                           1 if S0 is None else S0.shape[0], _hp(Q), R, H, _hp(traj), _hp(Sigma), None, None, None, _hp(gx),
+                           _hp(gS), _hp(dU) if D > nx else None, _hp(dx0), _hp(dS0))
+            except _lib.GPKError as e:
+                if e.code == _lib.GPK_BAD_ARG:
+                    raise ValueError(str(e)) from None
+                raise
+            return traj, Sigma, dU, dx0, dS0
+        stage = _pg.batch_stage(self.predict_jacobian, _pg.noise_levels(self.models), in_shift, in_scale, o_mean, o_scale,
+                                var_includes_noise, with_dvar=True)
+        hess_stage = _pg.batch_hess_stage(self.predict_hessian, in_shift, in_scale, o_scale)
+        return _pg.host_adjoint(stage, hess_stage, coord, x0, U, lin, S0, Q, R, H, gx, gS)
+
     def _fused64(self):
         """The fp64 buffers of the fused launches (shared X, alpha as one column per model) - `_fused` itself unless the
         batch serves in fp32."""

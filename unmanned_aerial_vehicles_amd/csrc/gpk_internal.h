@@ -303,6 +303,21 @@ int gpk_small_launch(gpk_handle h, int call, const ServeModels& m, const double*
 unsigned gpk_small_trace_groups(int64_t Np);
 int gpk_small_trace_launch(gpk_handle h, const ServeModels& m, const double* Xq, int64_t M, const double* Sg, int nx,
                            const double* in_scale, double* shares, double* trs);
+// The Hessian-vector launch of a backward propagation stage (small_hvp_kernel): the workgroups' shares of H_o w_o for the M
+// device query rows Xq, H_o the mean's input Hessian of output o per unit of the RAW query, never formed.  w_o = [G[coord of o,
+// :nx], 0] with G = Lam A Sg per query row, A = I + lin[:, :nx] + the stage's Jacobian rows: the workgroups form their own rows
+// of G from what the chain keeps on the device.  groups = gpk_small_trace_groups(Np) workgroups per model write
+// shares[(g * E + e) * D + d], E = B M P, e = (b * M + m) * P + p; H_o w_o = sum_g shares.  No ticket, no atomics, no inverse
+// factor (F = 1 or 2), nothing is synchronised.
+struct SmallHvp {
+  const double *Lam, *Sg;            // device, M x nx x nx each: the adjoint of the next stage's covariance, this stage's covariance
+  const double *sjac, *lin;          // device: the stage's Jacobians (output o, row m at [(o * so + m * sm) * D + d]), lin (nx x D)
+  int nx, so, sm, scaled;
+  int model_of[16];                  // state coordinate -> output, or -1
+  int coord_of[16];                  // output -> state coordinate
+  double in_scale[16];               // the queries' scaler (ones without)
+};
+int gpk_small_hvp_launch(gpk_handle h, const ServeModels& m, const double* Xq, int64_t M, const SmallHvp& c, double* shares);
 // ---- horizon propagation (gpk_propagate.hip): what the entries of the exact models and of the sparse models (gpk_sparse.hip) share
 constexpr int GPK_PROP_MAX_R = GPK_SMALL_MAX_M, GPK_PROP_MAX_H = 256, GPK_PROP_MAX_NX = 16, GPK_PROP_MAX_D = 16;
 // The composition's parameters.  Output o of the stage (a single model's output p, or model b of a batch) sits at
@@ -318,6 +333,12 @@ struct PropK {
   double noise[16];                  // added to svar (normalised units) when the variance is to include the noise level
   int add_noise;
 };
+// The seeds and results of the adjoint chain: gx (H + 1, R, nx) = dl/dx_h, gS (H + 1, R, nx, nx) = dl/dSigma_h (null: zero; the
+// chain uses (gS + gS^T) / 2); dU (R, H, nu) (null when nu = 0), dx0 (R, nx), dSigma0 (R, nx, nx) (may be null).
+struct HorizonGrad {
+  const double *gx, *gS;
+  double *dU, *dx0, *dSigma0;
+};
 // What the entries share past their model arguments.
 struct Horizon {
   const double *x0, *U, *lin, *Sigma0, *Q;
@@ -325,10 +346,14 @@ struct Horizon {
   double *traj, *Sigma, *mean, *var, *jac;
   int order = 1;                     // 2: the mean takes c_o = tr(H_o Sigma_h) / 2 per stage, added last (see gpk_propagate.hip)
   double* corr = nullptr;            // (H, R, NO): c of every stage, zeros at order 1; may be null
+  const HorizonGrad* grad = nullptr;   // the gradient of a horizon cost (order 1 only): the backward sweep follows the chain
 };
 // The chain of one horizon on the models m (F = 1 or 2): every check of the limits (GPK_BAD_ARG before anything is launched), one
 // upload, 3 H launches (order 2: 4 H, the trace launch before the advance), up to five downloads (six with corr), one
-// synchronisation.  k: nx, D, NO, the strides, model_of, the scaler, ystd2 and the noise filled in by the entry; `who` prefixes
+// synchronisation.  With z.grad: 6 H launches - forward the three of GPK_SMALL_GRAD and the advance, backward the
+// Hessian-vector launch and propagate_adjoint_kernel - the seeds in the one upload, up to three more downloads, still one
+// synchronisation; traj and Sigma keep the bits of the chain without it.
+// k: nx, D, NO, the strides, model_of, the scaler, ystd2 and the noise filled in by the entry; `who` prefixes
 // the messages.
 int gpk_propagate_run(gpk_handle h, const std::string& who, const ServeModels& m, PropK k, const Horizon& z);
 // ... as one-call serving (gpk_serve.hip): host queries in, host results out through the pinned, mapped block, one

@@ -14,6 +14,12 @@
 // those copies and may wait on them by itself; nothing waits between the stages.  gpk_propagate_run is the chain for every entry:
 // the exact models' below, the sparse models' in gpk_sparse.hip (two inverse factors per model: the stage's variance arrives final
 // and in another layout, which PropK's strides describe).
+//
+// The gradient of a horizon cost (Horizon::grad; order 1): the same forward stages on the three launches of GPK_SMALL_GRAD - the
+// variance gradient comes with them, mean, Jacobian and variance keep their bits - with every stage's queries, Jacobians and
+// variance gradients kept in the device block, then per stage, backwards, the Hessian-vector launch (small_hvp_kernel,
+// gpk_small.hip) and propagate_adjoint_kernel below: 6 H launches, the seeds in the one upload, still ONE synchronisation
+// (propagate_run_grad).
 #include "gpk_internal.h"
 
 namespace {
@@ -162,11 +168,118 @@ __global__ __launch_bounds__(256) void propagate_advance2_kernel(PropK k, int R,
                                ojac, &p2);
 }
 
+// The backward stage h of the gradient of a horizon cost (order 1), after the stage's Hessian-vector launch (small_hvp_kernel,
+// gpk_small.hip).  With lam = dl/dx_{h+1} and Lam = dl/dSigma_{h+1} (symmetric) as the stage above left them:
+//   F    = [I 0] + lin + sum_b e_c J_b                                  (nx x D; its first nx columns are A_h, the advance kernel's bits)
+//   g_q  = F^T lam + sum_b Lam[c_b][c_b] grad v_b + 2 sum_b H_b w_b     (w_b: row c_b of Lam A_h Sigma_h; the launch before left the
+//                                                                       workgroups' shares of H_b w_b, added here in workgroup order)
+//   lam  <- gx_h + g_q[:nx],   dU_h = g_q[nx:],   Lam <- sym(gS_h) + A_h^T Lam A_h
+// One workgroup per rollout r, thread (i, j) = (tid >> 4, tid & 15); sequential, fixed-order sums; the lower triangle of the new
+// Lam is formed and mirrored.  lam and Lam are updated in place (this workgroup alone touches row r of either).
+struct PropAdj {
+  const double* shares;              // groups x (NO R) x D, entry e = o * so + r * sm
+  const double* sdvar;               // the stage's variance gradient, normalised-target units, per unit of the scaled query:
+  int groups, dvo;                   // ... output o, rollout r at [(o * dvo + r) * D + d]
+  int coord_of[16];                  // output -> state coordinate
+  double ystd2[16];
+};
+
+__global__ __launch_bounds__(256) void propagate_adjoint_kernel(PropK k, PropAdj a, int R, int H, int h,
+                                                                const double* __restrict__ sjac, const double* __restrict__ lin,
+                                                                const double* __restrict__ gx_h, const double* __restrict__ gS_h,
+                                                                double* lam, double* Lam, double* dU) {
+  __shared__ double A[16][17], L[16][17], T[16][17], J[16][17], GV[16][17], HW[16][17];
+  __shared__ double lm[16];
+  const int tid = threadIdx.x, i = tid >> 4, j = tid & 15, r = blockIdx.x;
+  const int nx = k.nx, D = k.D, NO = k.NO, nu = D - nx;
+  if (i < nx && j < nx) L[i][j] = Lam[((long long)r * nx + i) * nx + j];
+  if (tid < nx) lm[tid] = lam[(long long)r * nx + tid];
+  if (i < NO && j < D) {
+    const long long E = (long long)NO * R, e = i * k.so + r * k.sm;
+    const double g = sjac[e * D + j];
+    J[i][j] = k.scaled ? g / k.in_scale[j] : g;
+    const double dv = a.sdvar[((long long)i * a.dvo + r) * D + j] * a.ystd2[i];
+    GV[i][j] = k.scaled ? dv / k.in_scale[j] : dv;
+    double s = 0.0;
+#pragma unroll 8
+    for (int g2 = 0; g2 < a.groups; ++g2) s += a.shares[(g2 * E + e) * D + j];
+    HW[i][j] = s;
+  }
+  __syncthreads();
+  if (i < nx && j < nx) {
+    const int o = k.model_of[i];
+    double v = (i == j ? 1.0 : 0.0) + lin[i * D + j];
+    if (o >= 0) v += J[o][j];
+    A[i][j] = v;
+  }
+  if (tid < D) {      // thread d forms g_q[d]
+    const int d = tid;
+    double s = 0.0;
+    for (int c = 0; c < nx; ++c) {
+      const int o = k.model_of[c];
+      double f = (c == d ? 1.0 : 0.0) + lin[c * D + d];
+      if (o >= 0) f += J[o][d];
+      s = __builtin_fma(f, lm[c], s);
+    }
+    for (int o = 0; o < NO; ++o) {
+      const int c = a.coord_of[o];
+      s = __builtin_fma(L[c][c], GV[o][d], s);
+      s = __builtin_fma(2.0, HW[o][d], s);
+    }
+    if (d < nx) lam[(long long)r * nx + d] = gx_h[(long long)r * nx + d] + s;
+    else dU[((long long)r * H + h) * nu + (d - nx)] = s;
+  }
+  __syncthreads();
+  if (i < nx && j < nx) {
+    double t = 0.0;
+    for (int c = 0; c < nx; ++c) t = __builtin_fma(L[i][c], A[c][j], t);
+    T[i][j] = t;
+  }
+  __syncthreads();
+  if (i < nx && j <= i) {
+    double s = 0.0;
+    for (int c = 0; c < nx; ++c) s = __builtin_fma(A[c][i], T[c][j], s);
+    const long long at = (long long)r * nx * nx;
+    if (gS_h) s += gS_h[at + i * nx + j];
+    Lam[at + i * nx + j] = s;
+    Lam[at + j * nx + i] = s;
+  }
+}
+
 bool prop_finite(const double* p, size_t n) {
   for (size_t i = 0; i < n; ++i)
     if (!(p[i] - p[i] == 0.0)) return false;
   return true;
 }
+
+// The head of the one upload, [x | S | q | lin | Q | U] (zero-initialised by the caller): the start rows, Sigma0 mirrored from its
+// lower triangle, the first stage's scaled queries and the horizon's constants as they come from the host.
+void prop_pack(const PropK& k, const Horizon& z, double* hx) {
+  const int nx = k.nx, D = k.D, nu = D - nx, R = z.R, H = z.H;
+  const size_t n_x = (size_t)R * nx, n_s = n_x * nx, n_q = (size_t)R * D, n_lin = (size_t)nx * D, n_Q = (size_t)nx * nx;
+  const size_t n_u = nu ? (size_t)z.u_rows * H * nu : 0;
+  double* hS = hx + n_x;
+  double* hq = hS + n_s;
+  for (int r = 0; r < R; ++r) {
+    const double* xr = z.x0 + (z.x0_rows == 1 ? 0 : (size_t)r * nx);
+    memcpy(hx + (size_t)r * nx, xr, sizeof(double) * nx);
+    if (z.Sigma0) {
+      // the lower triangle is the matrix: mirrored here as every later stage is
+      const double* s0 = z.Sigma0 + (z.s_rows == 1 ? 0 : (size_t)r * n_Q);
+      for (int i = 0; i < nx; ++i)
+        for (int j = 0; j <= i; ++j) hS[(size_t)r * n_Q + i * nx + j] = hS[(size_t)r * n_Q + j * nx + i] = s0[i * nx + j];
+    }
+    for (int d = 0; d < D; ++d) {
+      const double raw = d < nx ? xr[d] : z.U[(z.u_rows == 1 ? 0 : (size_t)r * H * nu) + (d - nx)];
+      hq[(size_t)r * D + d] = k.scaled ? (raw - k.in_shift[d]) / k.in_scale[d] : raw;
+    }
+  }
+  memcpy(hq + n_q, z.lin, sizeof(double) * n_lin);
+  if (z.Q) memcpy(hq + n_q + n_lin, z.Q, sizeof(double) * n_Q);
+  if (n_u) memcpy(hq + n_q + n_lin + n_Q, z.U, sizeof(double) * n_u);
+}
+
+int propagate_run_grad(gpk_handle h, const ServeModels& m, const PropK& k, const Horizon& z);
 
 }  // namespace
 
@@ -195,6 +308,15 @@ int gpk_propagate_run(gpk_handle h, const std::string& who, const ServeModels& m
   GPK_REQUIRE(h, prop_finite(z.x0, (size_t)z.x0_rows * nx) && prop_finite(z.lin, n_lin) && (!n_u || prop_finite(z.U, n_u)) &&
                      (!z.Sigma0 || prop_finite(z.Sigma0, (size_t)z.s_rows * n_Q)) && (!z.Q || prop_finite(z.Q, n_Q)),
               who + "x0, U, lin, Sigma0 and Q must not contain NaN or infinity");
+  if (z.grad) {
+    const HorizonGrad& g = *z.grad;
+    GPK_REQUIRE(h, z.order == 1, who + "the gradient is that of the first-order propagation (order = 1)");
+    GPK_REQUIRE(h, g.gx && g.dx0, who + "null seed gx or null result dx0");
+    GPK_REQUIRE(h, nu == 0 || g.dU, who + "null result dU");
+    GPK_REQUIRE(h, prop_finite(g.gx, (size_t)(H + 1) * n_x) && (!g.gS || prop_finite(g.gS, (size_t)(H + 1) * n_s)),
+                who + "the seeds gx and gS must not contain NaN or infinity");
+    return propagate_run_grad(h, m, k, z);
+  }
   // the device block: [x | S | q | lin | Q | U] as they come from the host, the stage's results, the small-batch work area, the
   // horizon's outputs from slot 1 on (slot 0 of traj and Sigma is the caller's own start)
   const size_t n_up = n_x + n_s + n_q + n_lin + n_Q + n_u;
@@ -227,28 +349,9 @@ int gpk_propagate_run(gpk_handle h, const std::string& who, const ServeModels& m
   double* d_tr = d_sh + n_sh;
   double* d_oc = d_tr + n_tr;
   std::vector<double> host(n_up, 0.0);
-  double* hx = host.data();
-  double* hS = hx + n_x;
-  double* hq = hS + n_s;
-  for (int r = 0; r < R; ++r) {
-    const double* xr = z.x0 + (z.x0_rows == 1 ? 0 : (size_t)r * nx);
-    memcpy(hx + (size_t)r * nx, xr, sizeof(double) * nx);
-    if (z.Sigma0) {
-      // the lower triangle is the matrix: mirrored here as every later stage is
-      const double* s0 = z.Sigma0 + (z.s_rows == 1 ? 0 : (size_t)r * n_Q);
-      for (int i = 0; i < nx; ++i)
-        for (int j = 0; j <= i; ++j) hS[(size_t)r * n_Q + i * nx + j] = hS[(size_t)r * n_Q + j * nx + i] = s0[i * nx + j];
-    }
-    for (int d = 0; d < D; ++d) {
-      const double raw = d < nx ? xr[d] : z.U[(z.u_rows == 1 ? 0 : (size_t)r * H * nu) + (d - nx)];
-      hq[(size_t)r * D + d] = k.scaled ? (raw - k.in_shift[d]) / k.in_scale[d] : raw;
-    }
-  }
-  memcpy(hq + n_q, z.lin, sizeof(double) * n_lin);
-  if (z.Q) memcpy(hq + n_q + n_lin, z.Q, sizeof(double) * n_Q);
-  if (n_u) memcpy(hq + n_q + n_lin + n_Q, z.U, sizeof(double) * n_u);
-  memcpy(z.traj, hx, sizeof(double) * n_x);
-  memcpy(z.Sigma, hS, sizeof(double) * n_s);
+  prop_pack(k, z, host.data());
+  memcpy(z.traj, host.data(), sizeof(double) * n_x);
+  memcpy(z.Sigma, host.data() + n_x, sizeof(double) * n_s);
   GPK_CHECK_HIP(h, hipMemcpyAsync(d_x, host.data(), sizeof(double) * n_up, hipMemcpyHostToDevice, h->stream));
   const ServeOut stage{s_mean, s_var, s_jac, nullptr, nullptr};
   const long long u_row_stride = (nu && z.u_rows == R) ? (long long)H * nu : 0;
@@ -295,13 +398,133 @@ int gpk_propagate_run(gpk_handle h, const std::string& who, const ServeModels& m
   return GPK_OK;
 }
 
+namespace {
+
+// The chain with the backward sweep (z.grad; every argument checked by gpk_propagate_run).  Forward, per stage: the three launches
+// of GPK_SMALL_GRAD (mean, Jacobian, variance - the bits of the chain's GPK_SMALL_JACVAR - and the variance gradient) and the
+// unchanged advance kernel; the scaled queries, the Jacobians and the variance gradients of every stage stay in the device block,
+// Sigma_h in the horizon's own output (Sigma_0: a second copy in the upload).  Backward, per stage: the Hessian-vector launch
+// and propagate_adjoint_kernel.  6 H launches, one upload [x | S | q | lin | Q | U | S_0 | lam = gx_H | Lam = sym gS_H | gx | sym gS],
+// one synchronisation, the downloads after the last launch.
+int propagate_run_grad(gpk_handle h, const ServeModels& m, const PropK& k, const Horizon& z) {
+  const HorizonGrad& g = *z.grad;
+  const int nx = k.nx, D = k.D, nu = D - nx, NO = k.NO, R = z.R, H = z.H;
+  const size_t n_x = (size_t)R * nx, n_s = n_x * nx, n_q = (size_t)R * D, n_lin = (size_t)nx * D, n_Q = (size_t)nx * nx;
+  const size_t n_u = nu ? (size_t)z.u_rows * H * nu : 0;
+  const size_t n_head = n_x + n_s + n_q + n_lin + n_Q + n_u;
+  const size_t n_gx = (size_t)H * n_x, n_gS = g.gS ? (size_t)H * n_s : 0;
+  const size_t n_up = n_head + n_s + n_x + n_s + n_gx + n_gS;
+  const size_t n_sm = (size_t)NO * R, n_sj = n_sm * D, n_dv = (size_t)m.B * R * D;
+  const size_t n_work = gpk_small_work_doubles(GPK_SMALL_GRAD, m.Np, m.B, R, D, m.P, m.F);
+  const size_t n_traj = (size_t)H * n_x, n_sig = (size_t)H * n_s, n_om = (size_t)H * n_sm, n_oj = (size_t)H * n_sj;
+  const unsigned groups = gpk_small_trace_groups(m.Np);
+  GPK_REQUIRE(h, groups <= (unsigned)PROP_MAX_GROUPS, "propagate: more Hessian-vector workgroups than the adjoint launch adds");
+  const size_t n_sh = (size_t)groups * n_sj, n_du = (size_t)R * H * nu;
+  void* ws = nullptr;
+  GPK_TRY(gpk_scratch(h, (n_up + 2 * n_sm + n_work + n_traj + n_sig + 2 * n_om + n_oj + (size_t)(H - 1) * n_q + (size_t)H * n_sj +
+                          (size_t)H * n_dv + n_sh + n_du) * sizeof(double), &ws));
+  double* d_x = (double*)ws;
+  double* d_S = d_x + n_x;
+  double* d_q = d_S + n_s;
+  double* d_lin = d_q + n_q;
+  double* d_Q = d_lin + n_lin;
+  double* d_u = d_Q + n_Q;
+  double* d_S0 = d_u + n_u;
+  double* d_lam = d_S0 + n_s;
+  double* d_Lam = d_lam + n_x;
+  double* d_gx = d_Lam + n_s;
+  double* d_gS = d_gx + n_gx;
+  double* s_mean = d_gS + n_gS;
+  double* s_var = s_mean + n_sm;
+  double* work = s_var + n_sm;
+  double* d_traj = work + n_work;
+  double* d_sig = d_traj + n_traj;
+  double* d_om = d_sig + n_sig;
+  double* d_ov = d_om + n_om;
+  double* d_oj = d_ov + n_om;
+  double* d_qs = d_oj + n_oj;            // the scaled queries of stages 1 .. H - 1 (stage 0: d_q)
+  double* d_js = d_qs + (size_t)(H - 1) * n_q;
+  double* d_dv = d_js + (size_t)H * n_sj;
+  double* d_sh = d_dv + (size_t)H * n_dv;
+  double* d_du = d_sh + n_sh;
+  std::vector<double> host(n_up, 0.0);
+  prop_pack(k, z, host.data());
+  double* hS0 = host.data() + n_head;
+  double* hlam = hS0 + n_s;
+  double* hLam = hlam + n_x;
+  double* hgx = hLam + n_s;
+  double* hgS = hgx + n_gx;
+  memcpy(hS0, host.data() + n_x, sizeof(double) * n_s);
+  memcpy(hlam, g.gx + (size_t)H * n_x, sizeof(double) * n_x);
+  memcpy(hgx, g.gx, sizeof(double) * n_gx);
+  if (g.gS) {
+    // (gS + gS^T) / 2, the lower triangle formed and mirrored: stage H is the sweep's first Lam
+    for (size_t t = 0; t < (size_t)(H + 1) * R; ++t) {
+      const double* src = g.gS + t * n_Q;
+      double* dst = t < (size_t)H * R ? hgS + t * n_Q : hLam + (t - (size_t)H * R) * n_Q;
+      for (int i = 0; i < nx; ++i)
+        for (int j = 0; j <= i; ++j) dst[i * nx + j] = dst[j * nx + i] = 0.5 * (src[i * nx + j] + src[j * nx + i]);
+    }
+  }
+  memcpy(z.traj, host.data(), sizeof(double) * n_x);
+  memcpy(z.Sigma, host.data() + n_x, sizeof(double) * n_s);
+  GPK_CHECK_HIP(h, hipMemcpyAsync(d_x, host.data(), sizeof(double) * n_up, hipMemcpyHostToDevice, h->stream));
+  const long long u_row_stride = (nu && z.u_rows == R) ? (long long)H * nu : 0;
+  auto queries = [&](int s) { return s == 0 ? d_q : d_qs + (size_t)(s - 1) * n_q; };
+  for (int s = 0; s < H; ++s) {
+    double* s_jac = d_js + (size_t)s * n_sj;
+    const ServeOut stage{s_mean, s_var, s_jac, d_dv + (size_t)s * n_dv, nullptr};
+    GPK_TRY(gpk_small_launch(h, GPK_SMALL_GRAD, m, queries(s), R, work, stage));
+    const bool last = s + 1 == H;
+    gpk_time_begin(h, GPK_TIMED_PROPAGATE);
+    hipLaunchKernelGGL(propagate_advance_kernel, dim3((unsigned)R), dim3(256), 0, h->stream, k, R, (const double*)s_mean,
+                       (const double*)s_var, (const double*)s_jac, (const double*)d_lin, z.Q ? (const double*)d_Q : nullptr,
+                       (const double*)(d_u + (size_t)s * nu), (const double*)(d_u + (size_t)(last ? s : s + 1) * nu), u_row_stride,
+                       d_x, d_S, last ? nullptr : queries(s + 1), d_traj + (size_t)s * n_x, d_sig + (size_t)s * n_s,
+                       z.mean ? d_om + (size_t)s * n_sm : nullptr, z.var ? d_ov + (size_t)s * n_sm : nullptr,
+                       z.jac ? d_oj + (size_t)s * n_sj : nullptr);
+    gpk_time_end(h);
+    GPK_LAUNCH_CHECK(h);
+  }
+  SmallHvp hv{};
+  PropAdj pa{};
+  hv.Lam = d_Lam; hv.lin = d_lin; hv.nx = nx; hv.so = k.so; hv.sm = k.sm; hv.scaled = k.scaled;
+  pa.shares = d_sh; pa.groups = (int)groups; pa.dvo = m.B > 1 ? R : 0;
+  for (int d = 0; d < 16; ++d) { hv.model_of[d] = k.model_of[d]; hv.in_scale[d] = k.in_scale[d]; hv.coord_of[d] = pa.coord_of[d] = -1; }
+  for (int c = 0; c < nx; ++c)
+    if (k.model_of[c] >= 0) hv.coord_of[k.model_of[c]] = pa.coord_of[k.model_of[c]] = c;
+  for (int o = 0; o < NO; ++o) pa.ystd2[o] = m.y_std[o] * m.y_std[o];
+  for (int s = H - 1; s >= 0; --s) {
+    hv.Sg = s == 0 ? d_S0 : d_sig + (size_t)(s - 1) * n_s;
+    hv.sjac = d_js + (size_t)s * n_sj;
+    pa.sdvar = d_dv + (size_t)s * n_dv;
+    GPK_TRY(gpk_small_hvp_launch(h, m, queries(s), R, hv, d_sh));
+    hipLaunchKernelGGL(propagate_adjoint_kernel, dim3((unsigned)R), dim3(256), 0, h->stream, k, pa, R, H, s, hv.sjac,
+                       (const double*)d_lin, (const double*)(d_gx + (size_t)s * n_x),
+                       g.gS ? (const double*)(d_gS + (size_t)s * n_s) : nullptr, d_lam, d_Lam, d_du);
+    GPK_LAUNCH_CHECK(h);
+  }
+  GPK_CHECK_HIP(h, hipMemcpyAsync(z.traj + n_x, d_traj, sizeof(double) * n_traj, hipMemcpyDeviceToHost, h->stream));
+  GPK_CHECK_HIP(h, hipMemcpyAsync(z.Sigma + n_s, d_sig, sizeof(double) * n_sig, hipMemcpyDeviceToHost, h->stream));
+  if (z.mean) GPK_CHECK_HIP(h, hipMemcpyAsync(z.mean, d_om, sizeof(double) * n_om, hipMemcpyDeviceToHost, h->stream));
+  if (z.var) GPK_CHECK_HIP(h, hipMemcpyAsync(z.var, d_ov, sizeof(double) * n_om, hipMemcpyDeviceToHost, h->stream));
+  if (z.jac) GPK_CHECK_HIP(h, hipMemcpyAsync(z.jac, d_oj, sizeof(double) * n_oj, hipMemcpyDeviceToHost, h->stream));
+  if (n_du) GPK_CHECK_HIP(h, hipMemcpyAsync(g.dU, d_du, sizeof(double) * n_du, hipMemcpyDeviceToHost, h->stream));
+  GPK_CHECK_HIP(h, hipMemcpyAsync(g.dx0, d_lam, sizeof(double) * n_x, hipMemcpyDeviceToHost, h->stream));
+  if (g.dSigma0) GPK_CHECK_HIP(h, hipMemcpyAsync(g.dSigma0, d_Lam, sizeof(double) * n_s, hipMemcpyDeviceToHost, h->stream));
+  GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
+  return GPK_OK;
+}
+
+}  // namespace
+
 // The single-model entries' body.  `who`: the entry's name in the messages; order and corr as in Horizon.
 static int propagate_host_any(gpk_handle h, const std::string& who, const double* X, const double* alpha, int64_t N, int D, int P,
                               const double* ls, double sf2, const double* y_mean, const double* y_std, const double* W, int64_t Np,
                               int64_t ldw, double kss, double floor_, int var_includes_noise, double noise, const double* x0,
                               int x0_rows, const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows,
                               const double* Q, int R, int H, double* traj, double* Sigma, double* mean, double* var, double* jac,
-                              int order, double* corr) {
+                              int order, double* corr, const HorizonGrad* grad = nullptr) {
   if (!h) return GPK_BAD_ARG;
   GPK_REQUIRE(h, X && alpha && ls && y_mean && y_std && W, who + "null pointer");
   GPK_REQUIRE(h, P >= 1 && P <= GPK_MAX_P && P <= D, who + "the state dimension P must be in [1, 16] and must not exceed D");
@@ -313,7 +536,7 @@ static int propagate_host_any(gpk_handle h, const std::string& who, const double
   for (int d = 0; d < 16; ++d) { k.in_shift[d] = 0.0; k.in_scale[d] = 1.0; k.model_of[d] = d < P ? d : -1; }
   for (int p = 0; p < P; ++p) { k.ystd2[p] = y_std[p] * y_std[p]; k.noise[p] = noise; }
   const ServeModels m{1, P, 1, &X, &alpha, N, D, ls, &sf2, y_mean, y_std, {&W, nullptr}, Np, ldw, &kss, floor_, nullptr};
-  const Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean, var, jac, order, corr};
+  const Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean, var, jac, order, corr, grad};
   return gpk_propagate_run(h, who, m, k, z);
 }
 
@@ -344,7 +567,8 @@ static int propagate_host_multi_any(gpk_handle h, const std::string& who, int B,
                                     int var_includes_noise, const double* noise, int nx, const int* coord, const double* in_shift,
                                     const double* in_scale, const double* x0, int x0_rows, const double* U, int u_rows,
                                     const double* lin, const double* Sigma0, int s_rows, const double* Q, int R, int H, double* traj,
-                                    double* Sigma, double* mean, double* var, double* jac, int order, double* corr) {
+                                    double* Sigma, double* mean, double* var, double* jac, int order, double* corr,
+                                    const HorizonGrad* grad = nullptr) {
   if (!h) return GPK_BAD_ARG;
   GPK_REQUIRE(h, X && alpha && ls && sf2 && y_mean && y_std && W && kss && coord, who + "null pointer");
   GPK_REQUIRE(h, B >= 1 && B <= GPK_SMALL_MAX_MODELS, who + "1..8 models");
@@ -375,7 +599,7 @@ static int propagate_host_multi_any(gpk_handle h, const std::string& who, int B,
     k.scaled = 1;
   }
   const ServeModels m{B, 1, 1, X, alpha, N, D, ls, sf2, y_mean, y_std, {W, nullptr}, Np, ldw, kss, floor_, nullptr};
-  const Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean, var, jac, order, corr};
+  const Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean, var, jac, order, corr, grad};
   return gpk_propagate_run(h, who, m, k, z);
 }
 
@@ -403,4 +627,32 @@ extern "C" int gpk_propagate2_host_multi(gpk_handle h, int B, const double* cons
   return propagate_host_multi_any(h, "propagate2_host_multi: ", B, X, alpha, N, D, ls, sf2, y_mean, y_std, W, Np, ldw, kss, floor_,
                                   var_includes_noise, noise, nx, coord, in_shift, in_scale, x0, x0_rows, U, u_rows, lin, Sigma0,
                                   s_rows, Q, R, H, traj, Sigma, mean, var, jac, order, corr);
+}
+
+// ... with the gradient of a horizon cost (order 1): the seeds gx, gS and the results dU, dx0, dSigma0 as HorizonGrad describes them
+extern "C" int gpk_propagate_grad_host(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
+                                       double sf2, const double* y_mean, const double* y_std, const double* W, int64_t Np,
+                                       int64_t ldw, double kss, double floor_, int var_includes_noise, double noise, const double* x0,
+                                       int x0_rows, const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows,
+                                       const double* Q, int R, int H, double* traj, double* Sigma, double* mean, double* var,
+                                       double* jac, const double* gx, const double* gS, double* dU, double* dx0, double* dSigma0) {
+  const HorizonGrad g{gx, gS, dU, dx0, dSigma0};
+  return propagate_host_any(h, "propagate_grad_host: ", X, alpha, N, D, P, ls, sf2, y_mean, y_std, W, Np, ldw, kss, floor_,
+                            var_includes_noise, noise, x0, x0_rows, U, u_rows, lin, Sigma0, s_rows, Q, R, H, traj, Sigma, mean, var, jac,
+                            1, nullptr, &g);
+}
+
+extern "C" int gpk_propagate_grad_host_multi(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D,
+                                             const double* ls, const double* sf2, const double* y_mean, const double* y_std,
+                                             const double* const* W, int64_t Np, int64_t ldw, const double* kss, double floor_,
+                                             int var_includes_noise, const double* noise, int nx, const int* coord,
+                                             const double* in_shift, const double* in_scale, const double* x0, int x0_rows,
+                                             const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows,
+                                             const double* Q, int R, int H, double* traj, double* Sigma, double* mean, double* var,
+                                             double* jac, const double* gx, const double* gS, double* dU, double* dx0,
+                                             double* dSigma0) {
+  const HorizonGrad g{gx, gS, dU, dx0, dSigma0};
+  return propagate_host_multi_any(h, "propagate_grad_host_multi: ", B, X, alpha, N, D, ls, sf2, y_mean, y_std, W, Np, ldw, kss, floor_,
+                                  var_includes_noise, noise, nx, coord, in_shift, in_scale, x0, x0_rows, U, u_rows, lin, Sigma0,
+                                  s_rows, Q, R, H, traj, Sigma, mean, var, jac, 1, nullptr, &g);
 }

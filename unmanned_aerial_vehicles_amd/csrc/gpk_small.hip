@@ -43,6 +43,10 @@
 //                            of tr(H Sigma) for every (query, output), R x NO scalars instead of R x NO x D x D Hessian entries;
 //                            the chain's advance launch adds them.  gpk_small_trace_launch makes it.
 //
+//   ... in a backward stage   the gradient of a horizon cost (K11) needs H w for one vector w per (query, output): small_hvp_kernel (below,
+//                            with its own description) - the workgroups' shares of the D + 1 sums per (query, output), the Hessian never
+//                            formed; the chain's adjoint launch adds them.  gpk_small_hvp_launch makes it.
+//
 //   two factors (K9)         the sparse model's variance terms are kss - |Wuu k*|^2 + |WSigma k*|^2 on ONE K* with P outputs: the
 //                            first launch runs with one model, and small_var[_grad]_kernel, small_cov_kernel and small_wtv_grad_kernel
 //                            with the template parameter TWO - the same bodies - take the inverse FACTOR as the grid
@@ -534,6 +538,171 @@ __global__ __launch_bounds__(256) void small_hess_trace_kernel(SmallK k, Arr16 i
     if (t < MP) {
       slot[2 * t] = accT[u];
       slot[2 * t + 1] = accS[u];
+    }
+  }
+}
+
+// ---- H w of the mean's input Hessian (K11, gradient of a horizon cost): the first launch of a backward propagation stage ----------
+// The product of small_hess_kernel's result (per unit of the RAW query) with one vector per (query, output), formed without the
+// Hessian.  With delta_mj = (z_m - x_j) / ls as above, s_d = in_scale_d ls_d (this model's own length-scales) and wh = w / s:
+//   (H_mp w)_e = y_std[p] / s_e (sum_j k*_mj alpha_jp delta_mje (delta_mj . wh) - wh_e sum_j k*_mj alpha_jp)
+// - D + 1 sums per (query, output).  w is a row of G = Lam A Sg, the sensitivity of the cost to A_h (gpk_propagate.hip): every
+// workgroup forms the rows it needs from the chain's device buffers (SmallHvp), query by query through LDS, so that no launch
+// precedes this one.  The workgroups take small_hess_kernel's rows (hess_rows(Np), at most 64 workgroups per model) in its
+// rounds of HJ rows, K* recomputed from the device query rows.  The outputs are cut into slices of hvp_slice(M, nx, P) over the
+// third grid dimension, so that the slice's wh (M x slice x nx) stays within HVP_W doubles of LDS.  The workgroup writes
+// its finished share y_std / s_e (sum_e - wh_e S) to its own slot, shares[(group * E + e) * D + d] with e = (model * M + m) * P + p
+// and E = B M P.  No ticket and no last workgroup: the chain's adjoint launch adds the slots in workgroup order.  Rows past N
+// enter as zeros, a workgroup past the last row writes zeros, every slot is written, and rows, rounds and the order of every
+// sum depend on (Np, M, P, D, nx) alone.
+constexpr int HVP_W = 4096;
+constexpr int HVP_OUTS = 2;        // (query, output) pairs per thread: M * slice <= 512
+__host__ __device__ inline int hvp_slice(int M, int nx, int P) {
+  const int n = HVP_W / (M * nx);      // M nx <= 512: at least 8
+  return n > P ? P : n;
+}
+
+__global__ __launch_bounds__(256) void small_hvp_kernel(SmallK k, SmallHvp c, long long N, long long Np, int D, int P,
+                                                        const double* __restrict__ Xq, int M, double* shares) {
+  __shared__ double q[SQ][SD + 1];
+  __shared__ double xs[HJ][SD + 1];
+  __shared__ double al[HJ][SP + 1];
+  __shared__ double ks[SQ][HJ + 1];
+  __shared__ double wh[HVP_W];
+  __shared__ double lin_s[SD * SD];
+  __shared__ double ls[SD], sl[SD];
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const double* __restrict__ X = k.X[b];
+  const double* __restrict__ alpha = k.alpha[b];
+  const double sf2 = k.sf2[b];
+  const int nx = c.nx;
+  const int ps = hvp_slice(M, nx, P), p0 = blockIdx.z * ps, np = min(P, p0 + ps) - p0, MPs = M * np;
+  const long long rows = hess_rows(Np);
+  const long long r0 = (long long)blockIdx.x * rows, r1 = min(N, r0 + rows);
+  if (tid < SD) {
+    ls[tid] = k.ls[b][tid];
+    sl[tid] = c.in_scale[tid] * k.ls[b][tid];
+  }
+  for (int e = tid; e < nx * D; e += 256) lin_s[e] = c.lin[e];
+  __syncthreads();
+  for (int e = tid; e < M * SD; e += 256) {
+    const int m = e / SD, d = e % SD;
+    q[m][d] = d < D ? Xq[m * D + d] / ls[d] : 0.0;
+  }
+  // wh of (query m, output p0 + pp): row coord_of[output] of Lam A Sg, divided by s.  One thread per entry (m, pp, j), all
+  // queries at once (the operands come from L2 with many loads in flight, not query by query): first T = Lam[co, :] A into
+  // the buffer, then T Sg over it.  Every sum runs over the coordinates in order.
+  {
+    const int W = MPs * nx, npn = np * nx;
+    for (int e = tid; e < W; e += 256) {
+      const int m = e / npn, rem = e - m * npn, pp = rem / nx, j = rem - pp * nx;
+      const double* Lrow = c.Lam + ((long long)m * nx + c.coord_of[b * P + p0 + pp]) * nx;
+      double t = 0.0;
+      for (int i = 0; i < nx; ++i) {
+        const int o = c.model_of[i];
+        double a = (i == j ? 1.0 : 0.0) + lin_s[i * D + j];
+        if (o >= 0) {
+          const double g = c.sjac[(long long)(o * c.so + m * c.sm) * D + j];
+          a += c.scaled ? g / c.in_scale[j] : g;
+        }
+        t = __builtin_fma(Lrow[i], a, t);
+      }
+      wh[(m * ps + pp) * nx + j] = t;
+    }
+    __syncthreads();
+    double wr[HVP_W / 256];
+#pragma unroll
+    for (int u = 0; u < HVP_W / 256; ++u) {
+      const int e = tid + 256 * u;
+      wr[u] = 0.0;
+      if (e < W) {
+        const int m = e / npn, rem = e - m * npn, pp = rem / nx, j = rem - pp * nx;
+        const double* T = wh + (m * ps + pp) * nx;
+        const double* Sg = c.Sg + (long long)m * nx * nx + j;
+        double w = 0.0;
+        for (int i = 0; i < nx; ++i) w = __builtin_fma(T[i], Sg[i * nx], w);
+        wr[u] = w / sl[j];
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < HVP_W / 256; ++u) {
+      const int e = tid + 256 * u;
+      if (e < W) {
+        const int m = e / npn, rem = e - m * npn, pp = rem / nx, j = rem - pp * nx;
+        wh[(m * ps + pp) * nx + j] = wr[u];
+      }
+    }
+  }
+  __syncthreads();
+  double acc[HVP_OUTS][SD + 1];
+#pragma unroll
+  for (int u = 0; u < HVP_OUTS; ++u)
+#pragma unroll
+    for (int d = 0; d <= SD; ++d) acc[u][d] = 0.0;
+  for (long long jb = r0; jb < r1; jb += HJ) {
+    __syncthreads();
+    for (int e = tid; e < HJ * SD; e += 256) {
+      const int jj = e / SD, d = e % SD;
+      xs[jj][d] = (d < D && jb + jj < r1) ? X[(jb + jj) * D + d] / ls[d] : 0.0;
+    }
+    for (int e = tid; e < HJ * P; e += 256) {
+      const int jj = e / P, p = e - jj * P;
+      al[jj][p] = (jb + jj < r1) ? alpha[(jb + jj) * P + p] : 0.0;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < TRACE_PAIRS; ++u) {
+      const int e = tid + 256 * u, m = e / HJ, jj = e % HJ;
+      if (m < M) {
+        double d2 = 0.0;
+#pragma unroll
+        for (int d = 0; d < SD; ++d) {
+          const double dl = q[m][d] - xs[jj][d];
+          d2 = __builtin_fma(dl, dl, d2);
+        }
+        ks[m][jj] = (jb + jj < r1) ? sf2 * gpk_exp_neg(-0.5 * d2) : 0.0;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < HVP_OUTS; ++u) {
+      const int t = tid + 256 * u;
+      if (t < MPs) {
+        const int m = t / np, pp = t - m * np;
+        double qm[SD], wm[SD];      // (wm: zeros from nx on, so the product below takes no select)
+#pragma unroll
+        for (int d = 0; d < SD; ++d) {
+          qm[d] = q[m][d];
+          wm[d] = d < nx ? wh[(m * ps + pp) * nx + d] : 0.0;
+        }
+        for (int jj = 0; jj < HJ; ++jj) {
+          const double cf = ks[m][jj] * al[jj][p0 + pp];
+          double dl[SD], dot = 0.0;
+#pragma unroll
+          for (int d = 0; d < SD; ++d) {
+            dl[d] = qm[d] - xs[jj][d];
+            dot = __builtin_fma(dl[d], wm[d], dot);
+          }
+          const double cd = cf * dot;
+#pragma unroll
+          for (int d = 0; d < SD; ++d) acc[u][d] = __builtin_fma(cd, dl[d], acc[u][d]);
+          acc[u][SD] += cf;
+        }
+      }
+    }
+  }
+  const long long E = (long long)gridDim.y * M * P;
+#pragma unroll
+  for (int u = 0; u < HVP_OUTS; ++u) {
+    const int t = tid + 256 * u;
+    if (t < MPs) {
+      const int m = t / np, pp = t - m * np, o = b * P + p0 + pp;
+      const double* w = wh + (m * ps + pp) * nx;
+      double* slot = shares + ((long long)blockIdx.x * E + ((long long)b * M + m) * P + p0 + pp) * D;
+#pragma unroll
+      for (int d = 0; d < SD; ++d)
+        if (d < D) slot[d] = k.ystd[o] * (acc[u][d] - (d < nx ? w[d] : 0.0) * acc[u][SD]) / sl[d];
     }
   }
 }
@@ -1208,6 +1377,25 @@ int gpk_small_trace_launch(gpk_handle h, const ServeModels& m, const double* Xq,
   for (int d = 0; d < 16; ++d) sc.v[d] = d < m.D ? in_scale[d] : 1.0;
   hipLaunchKernelGGL(small_hess_trace_kernel, dim3(hess_groups(Np), m.B), dim3(256), 0, h->stream, k, sc, (long long)m.N, Np, m.D, m.P, nx,
                      Xq, Sg, (int)M, shares, trs);
+  GPK_LAUNCH_CHECK(h);
+  return GPK_OK;
+}
+
+int gpk_small_hvp_launch(gpk_handle h, const ServeModels& m, const double* Xq, int64_t M, const SmallHvp& c, double* shares) {
+  const std::string name("small hvp");
+  const long long Np = gpk_padded(m.N);
+  GPK_REQUIRE(h, m.B >= 1 && m.B <= GPK_SMALL_MAX_MODELS && (m.B == 1 || m.P == 1),
+              name + ": 1 model, or up to 8 single-output models");
+  GPK_REQUIRE(h, gpk_small_ok(Np, m.D, m.P, M) && c.nx >= 1 && c.nx <= m.D, name + ": shape outside the small-batch path");
+  GPK_REQUIRE(h, m.X && m.alpha && m.ls && m.sf2 && m.y_mean && m.y_std && Xq && c.Lam && c.Sg && c.sjac && c.lin && shares,
+              name + ": null pointer");
+  for (int o = 0; o < m.B * m.P; ++o)
+    GPK_REQUIRE(h, c.coord_of[o] >= 0 && c.coord_of[o] < c.nx && c.model_of[c.coord_of[o]] == o, name + ": outputs and coordinates disagree");
+  SmallK k{};
+  GPK_TRY(small_params(h, name, m, false, false, k));
+  const int ps = hvp_slice((int)M, c.nx, m.P);
+  hipLaunchKernelGGL(small_hvp_kernel, dim3(hess_groups(Np), m.B, (unsigned)((m.P + ps - 1) / ps)), dim3(256), 0, h->stream, k, c,
+                     (long long)m.N, Np, m.D, m.P, Xq, (int)M, shares);
   GPK_LAUNCH_CHECK(h);
   return GPK_OK;
 }

@@ -1384,7 +1384,7 @@ extern "C" int gpk_sparse_predict_multi_cov(gpk_handle h, int B, const gpk_handl
 static int sparse_propagate_any(gpk_handle h, const std::string& who, int var_includes_noise, const double* x0, int x0_rows,
                                 const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows, const double* Q,
                                 int R, int H, double* traj, double* Sigma, double* mean, double* var, double* jac, int order,
-                                double* corr) {
+                                double* corr, const HorizonGrad* grad = nullptr) {
   if (!h) return GPK_BAD_ARG;
   gpk_sparse* s = h->sparse;
   GPK_REQUIRE(h, s && s->finalized, who + "no finalised sparse model (call gpk_sparse_finalize first)");
@@ -1398,7 +1398,7 @@ static int sparse_propagate_any(gpk_handle h, const std::string& who, int var_in
   k.nx = P; k.D = D; k.NO = P;
   k.so = 1; k.sm = P; k.vo = 1; k.vm = P;
   for (int d = 0; d < 16; ++d) { k.in_shift[d] = 0.0; k.in_scale[d] = 1.0; k.model_of[d] = d < P ? d : -1; k.ystd2[d] = 1.0; }
-  const Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean, var, jac, order, corr};
+  const Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean, var, jac, order, corr, grad};
   return gpk_propagate_run(h, who, sv.models(), k, z);
 }
 
@@ -1421,7 +1421,8 @@ static int sparse_propagate_multi_any(gpk_handle h, const char* entry, int B, co
                                       const int* coord, const double* in_shift, const double* in_scale, const double* out_shift,
                                       const double* out_scale, const double* x0, int x0_rows, const double* U, int u_rows,
                                       const double* lin, const double* Sigma0, int s_rows, const double* Q, int R, int H,
-                                      double* traj, double* Sigma, double* mean, double* var, double* jac, int order, double* corr) {
+                                      double* traj, double* Sigma, double* mean, double* var, double* jac, int order, double* corr,
+                                      const HorizonGrad* grad = nullptr) {
   if (!h) return GPK_BAD_ARG;
   const std::string who(std::string(entry) + ": ");
   GPK_REQUIRE(h, B >= 1 && B <= GPK_SMALL_MAX_MODELS, who + "1..8 models");
@@ -1466,7 +1467,7 @@ static int sparse_propagate_multi_any(gpk_handle h, const char* entry, int B, co
       sb.y_std[b] = out_scale[b] * sb.y_std[b];
     }
   }
-  const Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean, var, jac, order, corr};
+  const Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean, var, jac, order, corr, grad};
   return gpk_propagate_run(h, who, sb.models(), k, z);
 }
 
@@ -1490,6 +1491,30 @@ extern "C" int gpk_sparse_propagate2_multi(gpk_handle h, int B, const gpk_handle
   return sparse_propagate_multi_any(h, "sparse_propagate2_multi", B, models, var_includes_noise, nx, coord, in_shift, in_scale,
                                     out_shift, out_scale, x0, x0_rows, U, u_rows, lin, Sigma0, s_rows, Q, R, H, traj, Sigma, mean, var,
                                     jac, order, corr);
+}
+
+// ... with the gradient of a horizon cost (order 1; gpk_propagate.hip: the adjoint chain): the Hessian-vector launch runs on the
+// mean's model (Z, alpha_u), the variance gradient is the two-factor launch's
+extern "C" int gpk_sparse_propagate_grad(gpk_handle h, int var_includes_noise, const double* x0, int x0_rows, const double* U,
+                                         int u_rows, const double* lin, const double* Sigma0, int s_rows, const double* Q, int R, int H,
+                                         double* traj, double* Sigma, double* mean, double* var, double* jac, const double* gx,
+                                         const double* gS, double* dU, double* dx0, double* dSigma0) {
+  const HorizonGrad g{gx, gS, dU, dx0, dSigma0};
+  return sparse_propagate_any(h, "sparse_propagate_grad: ", var_includes_noise, x0, x0_rows, U, u_rows, lin, Sigma0, s_rows, Q, R, H,
+                              traj, Sigma, mean, var, jac, 1, nullptr, &g);
+}
+
+extern "C" int gpk_sparse_propagate_grad_multi(gpk_handle h, int B, const gpk_handle* models, int var_includes_noise, int nx,
+                                               const int* coord, const double* in_shift, const double* in_scale,
+                                               const double* out_shift, const double* out_scale, const double* x0, int x0_rows,
+                                               const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows,
+                                               const double* Q, int R, int H, double* traj, double* Sigma, double* mean, double* var,
+                                               double* jac, const double* gx, const double* gS, double* dU, double* dx0,
+                                               double* dSigma0) {
+  const HorizonGrad g{gx, gS, dU, dx0, dSigma0};
+  return sparse_propagate_multi_any(h, "sparse_propagate_grad_multi", B, models, var_includes_noise, nx, coord, in_shift, in_scale,
+                                    out_shift, out_scale, x0, x0_rows, U, u_rows, lin, Sigma0, s_rows, Q, R, H, traj, Sigma, mean, var,
+                                    jac, 1, nullptr, &g);
 }
 
 extern "C" int gpk_sparse_export(gpk_handle h, int64_t* m, int* D, int* P, int* n_ls, double* Z, double* G, double* g, double* yy,

@@ -948,6 +948,27 @@ class DeviceGP:
             raise
         return (traj, Sigma, mean, var, jac) if order == 1 else (traj, Sigma, mean, var, jac, corr)
 
+    def propagate_grad_host(self, y_mean, y_std, kss, x0, U, lin, S0, Q, R, H, gx, gS):
+        """One C call per horizon with the gradient of a horizon cost (gpk_propagate_grad_host; arguments as
+        `propagate.check_horizon` and `propagate.check_seeds` return them): traj, Sigma with the bits of `propagate_host`, dU (R,
+        H, nu), dx0 (R, P), dSigma0 (R, P, P) - six launches per stage, one synchronisation.  ValueError, with the library's
+        message, where the entry refuses its arguments."""
+        assert self.factored
+        self._refuse_replica()
+        P, D = self.P, self.D
+        traj, Sigma = np.empty((H + 1, R, P)), np.empty((H + 1, R, P, P))
+        dU, dx0, dS0 = np.zeros((R, H, D - P)), np.empty((R, P)), np.empty((R, P, P))
+        try:
+            self._host_call("gpk_propagate_grad_host", y_mean, y_std, True, float(kss), 0.0, 0, 0.0, _hp(x0), x0.shape[0],
+                            _hp(U) if D > P else None, U.shape[0], _hp(lin), _hp(S0), 1 if S0 is None else S0.shape[0], _hp(Q), R, H,
+                            _hp(traj), _hp(Sigma), None, None, None, _hp(gx), _hp(gS), _hp(dU) if D > P else None, _hp(dx0),
+                            _hp(dS0))
+        except GPKError as e:
+            if e.code == _lib.GPK_BAD_ARG:
+                raise ValueError(str(e)) from None
+            raise
+        return traj, Sigma, dU, dx0, dS0
+
     # ---- gated serving: the one place every fp32 surface (estimator, sharded predictor, package GP, per-axis models) goes
     # through -------------------------------------------------------------------------------------------------------------
     def _rows64(self, Xq, q, rows):

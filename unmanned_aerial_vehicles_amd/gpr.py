@@ -499,6 +499,45 @@ class GaussianProcessRegressor:
         traj, Sigma, stages = _pg.host_loop(stage, list(range(P)), x0, U, lin, S0, Q, R, H, hess_stage)
         return (traj, Sigma, stages) if return_stages else (traj, Sigma)
 
+    def propagate_gradient(self, x0, U, lin, grad_traj, grad_Sigma=None, Sigma0=None, process_noise=None,
+                           var_includes_noise=False, route="auto", order=1):
+        """`propagate` with the gradient of a differentiable horizon cost l(traj, Sigma) with respect to the controls, the start
+        state and the start covariance (`propagate`'s module docstring has the backward sweep).  grad_traj (H + 1, R, P) =
+        dl/dx_h and grad_Sigma (H + 1, R, P, P) = dl/dSigma_h (default zero; entries taken as independent, (g + g^T) / 2 is
+        used); with R = 1 the rollout axis may be left out.  Returns (traj, Sigma, dU (R, H, nu), dx0 (R, P), dSigma0 (R, P, P)):
+        traj and Sigma with the bits of `propagate` on the same arguments, one gradient row per rollout (rollouts that share
+        x0, U or Sigma0: add their rows).  The variance enters through the gradient of the unclipped variance, as
+        `predict_jacobian(return_var=True)` returns it.  One C call per horizon (`gpk_propagate_grad_host`: six launches per
+        stage, one synchronisation, no Hessian formed) where `propagate` makes one; otherwise, or with route="host", the same
+        sweep on the host over `predict_jacobian` and `predict_hessian`.  order: 1 only - the derivative of the second-order
+        mean term needs third derivatives of the mean (ValueError)."""
+        from . import propagate as _pg
+        _pg.check_grad_order(order)
+        if not hasattr(self, "X_train_"):
+            raise RuntimeError("This GaussianProcessRegressor instance is not fitted yet.")
+        P, D = self._yn.shape[1], self.n_features_in_
+        x0, U, lin, S0, Q, R, H = _pg.check_horizon(x0, U, lin, P, D, Sigma0, process_noise)
+        gx, gS = _pg.check_seeds(grad_traj, grad_Sigma, R, H, P)
+        if route not in ("auto", "host"):
+            raise ValueError("route must be 'auto' or 'host'")
+        self._ensure_device()
+        dev = self._dev
+        comp = self.kernel_.components()
+        noise = comp.noise or 0.0
+        if route == "auto" and dev.propagate_ok():
+            return dev.propagate_grad_host(self._y_train_mean, self._y_train_std, comp.sf2 + (noise if var_includes_noise else 0.0),
+                                           x0, U, lin, S0, Q, R, H, gx, gS)
+        std2 = self._y_train_std ** 2
+
+        def stage(q):
+            mean, dmean, var, dvar = self.predict_jacobian(q, return_var=True)
+            var = var.reshape(R, P)
+            if not var_includes_noise:
+                var = np.maximum(var - noise * std2[None, :], 0.0)
+            return mean.reshape(R, P), dmean.reshape(R, P, D), var, dvar.reshape(R, P, D)
+
+        return _pg.host_adjoint(stage, lambda q: self.predict_hessian(q)[2], list(range(P)), x0, U, lin, S0, Q, R, H, gx, gS)
+
     def sample_y(self, X, n_samples=1, random_state=0):
         """`sklearn/gaussian_process/_gpr.py:498-535`: draws from the joint posterior (or the prior, unfitted) at X - the
         mean and covariance from `predict(X, return_cov=True)` (GPU), the draw by NumPy's `multivariate_normal` (an SVD of

@@ -20,6 +20,20 @@ beyond the small-batch path and of option small_path=0 - and what the control-lo
 H_b = d2 mu_b / dq2; A_h and Sigma_{h+1} stay as above.  The one-call entries (`gpk_propagate2_host[_multi]`,
 `gpk_sparse_propagate2[_multi]`: four launches per stage) contract H with Sigma without forming it; `host_loop` takes a
 second-order stage callback built from the class's own `predict_hessian`.
+
+`propagate_gradient` on every class returns, with the horizon itself, the gradient of a differentiable cost l(X, Sigma) with
+respect to the controls, the start state and the start covariance (first order only: the derivative of c_b holds third
+derivatives of the mean).  The caller supplies the seeds gx[h] = dl/dx_h and gS[h] = dl/dSigma_h (entries taken as independent;
+(gS + gS^T) / 2 is used); from lam_H = gx_H, Lam_H = sym(gS_H), for h = H - 1 .. 0 and c_b = coord[b]:
+
+    F_h   = [I 0] + lin + sum_b e_c J_b                     (nx x D, all D columns of the Jacobian)
+    G_h   = Lam_{h+1} A_h Sigma_h,      w_b = [G_h[c_b, :nx], 0 .. 0]
+    g_q   = F_h^T lam_{h+1} + sum_b Lam_{h+1}[c_b, c_b] grad_q v_b + 2 sum_b H_b w_b
+    lam_h = gx_h + g_q[:nx],   dU_h = g_q[nx:],   Lam_h = sym(gS_h) + A_h^T Lam_{h+1} A_h
+
+dx0 = lam_0, dSigma0 = Lam_0.  The one-call entries (`gpk_propagate_grad_host[_multi]`, `gpk_sparse_propagate_grad[_multi]`: six
+launches per stage, one synchronisation) form H_b w_b without the Hessian; `host_adjoint` is the same sweep on the host over the
+class's own `predict_jacobian(..., return_var=True)` and `predict_hessian`.
 """
 from __future__ import annotations
 
@@ -136,6 +150,95 @@ def host_loop(stage, coord, x0, U, lin, S0, Q, R, H, hess_stage=None):
     return traj, Sigma, stages
 
 
+def check_grad_order(order):
+    """`propagate_gradient` differentiates the first-order propagation only: ValueError for any other order."""
+    if isinstance(order, bool) or order != 1:
+        raise ValueError(f"propagate_gradient: order must be 1, got {order!r} (the derivative of the second-order mean term "
+                         "needs third derivatives of the mean, which the kernels do not form)")
+    return 1
+
+
+def check_seeds(grad_traj, grad_Sigma, R, H, nx):
+    """The seeds as contiguous float64 arrays: gx (H + 1, R, nx) and gS (H + 1, R, nx, nx) or None.  With R = 1 the rollout
+    axis may be left out.  ValueError on a wrong shape, NaN or infinity."""
+    gx = np.asarray(grad_traj, dtype=np.float64)
+    if gx.ndim == 2 and R == 1:
+        gx = gx[:, None, :]
+    if gx.shape != (H + 1, R, nx):
+        raise ValueError(f"propagate_gradient: grad_traj must be ({H + 1}, {R}, {nx})" + (f" or ({H + 1}, {nx})" if R == 1 else ""))
+    gS = None
+    if grad_Sigma is not None:
+        gS = np.asarray(grad_Sigma, dtype=np.float64)
+        if gS.ndim == 3 and R == 1:
+            gS = gS[:, None, :, :]
+        if gS.shape != (H + 1, R, nx, nx):
+            raise ValueError(f"propagate_gradient: grad_Sigma must be ({H + 1}, {R}, {nx}, {nx})"
+                             + (f" or ({H + 1}, {nx}, {nx})" if R == 1 else ""))
+    for name, a in (("grad_traj", gx), ("grad_Sigma", gS)):
+        if a is not None and not np.isfinite(a).all():
+            raise ValueError(f"propagate_gradient: {name} contains NaN or infinity")
+    return np.ascontiguousarray(gx), (None if gS is None else np.ascontiguousarray(gS))
+
+
+def _sym(a):
+    """(a + a^T) / 2 over the last two axes, the lower triangle formed and mirrored: symmetric bit for bit"""
+    low = np.tril(0.5 * (a + np.swapaxes(a, -1, -2)))
+    return low + np.swapaxes(np.tril(low, -1), -1, -2)
+
+
+def host_adjoint(stage, hess_stage, coord, x0, U, lin, S0, Q, R, H, gx, gS):
+    """The forward recursion and the backward sweep of the module docstring on the host.  stage(q (R, D) raw) -> (mean (R, NO),
+    jac (R, NO, D), var (R, NO), dvar (R, NO, D)), jac and dvar per unit of the raw query; hess_stage(q) -> the mean's Hessian
+    (R, NO, D, D) per unit of the raw query.  Returns traj, Sigma (as `host_loop`), dU (R, H, nu), dx0 (R, nx), dSigma0 (R, nx,
+    nx)."""
+    nx, D = lin.shape
+    NO = len(coord)
+    kept = []
+
+    def forward(q):
+        mean, jac, var, dvar = stage(q)
+        kept.append((q, np.asarray(jac).reshape(R, NO, D), np.asarray(dvar).reshape(R, NO, D)))
+        return mean, jac, var
+
+    traj, Sigma, _ = host_loop(forward, coord, x0, U, lin, S0, Q, R, H)
+    lam = gx[H].copy()
+    Lam = _sym(gS[H]) if gS is not None else np.zeros((R, nx, nx))
+    dU = np.zeros((R, H, D - nx))
+    F0 = np.concatenate([np.eye(nx), np.zeros((nx, D - nx))], axis=1) + lin
+    for h in range(H - 1, -1, -1):
+        q, jac, dvar = kept[h]
+        hess = np.asarray(hess_stage(q)).reshape(R, NO, D, D)
+        F = np.broadcast_to(F0, (R, nx, D)).copy()
+        for o, c in enumerate(coord):
+            F[:, c, :] += jac[:, o, :]
+        A = F[:, :, :nx]
+        G = Lam @ A @ Sigma[h]
+        gq = np.einsum("rid,ri->rd", F, lam)
+        for o, c in enumerate(coord):
+            gq += Lam[:, c, c][:, None] * dvar[:, o, :] + 2.0 * np.einsum("rde,re->rd", hess[:, o, :, :nx], G[:, c, :])
+        lam = gx[h] + gq[:, :nx]
+        dU[:, h] = gq[:, nx:]
+        Lam = A.transpose(0, 2, 1) @ Lam @ A
+        if gS is not None:
+            Lam = Lam + _sym(gS[h])
+        Lam = _sym(Lam)
+    return traj, Sigma, dU, lam, Lam
+
+
+def nominal_adjoint(lin, R, H, gx, gS):
+    """The sweep through the nominal dynamics alone (A = I + lin_x, F = [I 0] + lin, no variance terms): the wrappers'
+    fallback.  Returns dU (R, H, nu), dx0 (R, nx)."""
+    nx, D = lin.shape
+    F = np.concatenate([np.eye(nx), np.zeros((nx, D - nx))], axis=1) + lin
+    lam = gx[H].copy()
+    dU = np.zeros((R, H, D - nx))
+    for h in range(H - 1, -1, -1):
+        gq = lam @ F
+        lam = gx[h] + gq[:, :nx]
+        dU[:, h] = gq[:, nx:]
+    return dU, lam
+
+
 # ---- what the batches (BatchedARDGP, BatchedSparseGP) share: raw units around single-output models --------------------------------
 def check_route(route, routes=("auto", "host")):
     """ValueError unless `route` is one of `routes` (the sparse classes add "chain", the one-call device chain)."""
@@ -189,17 +292,23 @@ def check_batch(B, D, x0, U, lin, coord, in_scaler, out_scaler, Sigma0, process_
     return head + (coord, in_shift, in_scale, o_mean, o_scale)
 
 
-def batch_stage(predict_jacobian, level, in_shift, in_scale, o_mean, o_scale, var_includes_noise):
-    """The `host_loop` stage of a batch: predict_jacobian(z, return_var=True) -> (mean (R, B), dmean (R, B, D), var (R, B), _) on
-    the scaled rows; level (B,): the noise level's share of every model's variance, which the served variances carry."""
+def batch_stage(predict_jacobian, level, in_shift, in_scale, o_mean, o_scale, var_includes_noise, with_dvar=False):
+    """The `host_loop` stage of a batch: predict_jacobian(z, return_var=True) -> (mean (R, B), dmean (R, B, D), var (R, B), dvar
+    (R, B, D)) on the scaled rows; level (B,): the noise level's share of every model's variance, which the served variances
+    carry.  with_dvar: the stage of `host_adjoint`, with the variance gradient per unit of the raw query as its fourth result."""
     def stage(q):
         z = q if in_shift is None else (q - in_shift) / in_scale
-        mean, dmean, var, _ = predict_jacobian(z, return_var=True)
+        mean, dmean, var, dvar = predict_jacobian(z, return_var=True)
         if not var_includes_noise:      # the latent variance, clipped again
             var = np.maximum(var - level[None, :], 0.0)
         if in_scale is not None:
             dmean = dmean / in_scale[None, None, :]
-        return o_mean + o_scale * mean, o_scale[None, :, None] * dmean, o_scale ** 2 * var
+        head = (o_mean + o_scale * mean, o_scale[None, :, None] * dmean, o_scale ** 2 * var)
+        if not with_dvar:
+            return head
+        if in_scale is not None:
+            dvar = dvar / in_scale[None, None, :]
+        return head + ((o_scale ** 2)[None, :, None] * dvar,)
 
     return stage
 
@@ -264,3 +373,21 @@ def nominal_horizon(nominal, lin, Sigma0, process_noise):
     for k in range(H):
         Sigma[k + 1] = A @ Sigma[k] @ A.T + Q
     return nominal, Sigma
+
+
+def gradient_layout(traj, Sigma, dU, dx0, single):
+    """`horizon_layout` for the wrappers' `horizon_gradient`: X, Sigma as there, dU (R, N, nu), dx0 (R, 6); `single` drops R."""
+    X, S = horizon_layout(traj, Sigma, single)
+    return (X, S, dU[0], dx0[0]) if single else (X, S, dU, dx0)
+
+
+def nominal_gradient(nominal, lin, grad_traj, single):
+    """The fallback of the wrappers' `horizon_gradient`: the nominal horizon (zero covariance) and the sweep through the nominal
+    dynamics; seeds that cannot be read as (N + 1, R, 6) count as zero (it must not raise)."""
+    H, R, nx = nominal.shape[0] - 1, nominal.shape[1], nominal.shape[2]
+    try:
+        gx, _ = check_seeds(grad_traj, None, R, H, nx)
+    except Exception:  # noqa: BLE001
+        gx = np.zeros((H + 1, R, nx))
+    dU, dx0 = nominal_adjoint(lin, R, H, gx, None)
+    return gradient_layout(*nominal_horizon(nominal, lin, None, None), dU, dx0, single)

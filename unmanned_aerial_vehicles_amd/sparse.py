@@ -542,6 +542,48 @@ class SparseGP:
         traj, Sigma, stages = _pg.host_loop(stage, list(range(P)), x0, U, lin, S0, Q, R, H, hess_stage)
         return (traj, Sigma, stages) if return_stages else (traj, Sigma)
 
+    def propagate_gradient(self, x0, U, lin, grad_traj, grad_Sigma=None, Sigma0=None, process_noise=None,
+                           var_includes_noise=False, route="auto", order=1):
+        """`GaussianProcessRegressor.propagate_gradient` on the sparse posterior: `propagate` with the gradient of a horizon cost
+        with respect to the controls, the start state and the start covariance; same arguments and results.  route="auto" and
+        "host": the sweep on the host over `predict_jacobian(..., return_var=True)` and `predict_hessian`.  route="chain": ONE C
+        call per horizon (`gpk_sparse_propagate_grad`: six launches per stage, one synchronisation; traj and Sigma with the
+        bits of `propagate(route="chain")`); ValueError where `propagate_ok()` does not hold.  order: 1 only (ValueError)."""
+        from . import propagate as _pg
+        _pg.check_grad_order(order)
+        _pg.check_route(route, ("auto", "host", "chain"))
+        P, D = self.n_outputs_, self.n_features_in_
+        x0, U, lin, S0, Q, R, H = _pg.check_horizon(x0, U, lin, P, D, Sigma0, process_noise)
+        gx, gS = _pg.check_seeds(grad_traj, grad_Sigma, R, H, P)
+        if route == "chain":
+            why = self._propagate_refusal()
+            if why:
+                raise ValueError(f"route='chain' is not available: {why}")
+            self._ensure()
+            traj, Sigma = np.empty((H + 1, R, P)), np.empty((H + 1, R, P, P))
+            dU, dx0, dS0 = np.zeros((R, H, D - P)), np.empty((R, P)), np.empty((R, P, P))
+            try:
+                self._backend().call("gpk_sparse_propagate_grad", int(bool(var_includes_noise)), _ptr(x0), x0.shape[0],
+                                     _ptr(U) if D > P else None, U.shape[0], _ptr(lin), _ptr(S0), 1 if S0 is None else S0.shape[0],
+                                     _ptr(Q), R, H, _ptr(traj), _ptr(Sigma), None, None, None, _ptr(gx), _ptr(gS),
+                                     _ptr(dU) if D > P else None, _ptr(dx0), _ptr(dS0))
+            except _lib.GPKError as e:
+                if e.code == _lib.GPK_BAD_ARG:
+                    raise ValueError(str(e)) from None
+                raise
+            return traj, Sigma, dU, dx0, dS0
+        noise = self.kernel_.components().noise or 0.0
+        std2 = np.broadcast_to(np.asarray(self._y_train_std, dtype=np.float64).reshape(-1), (P,)) ** 2
+
+        def stage(q):
+            mean, dmean, var, dvar = self.predict_jacobian(q, return_var=True)
+            var = var.reshape(R, P)
+            if not var_includes_noise:
+                var = np.maximum(var - noise * std2[None, :], 0.0)
+            return mean.reshape(R, P), dmean.reshape(R, P, D), var, dvar.reshape(R, P, D)
+
+        return _pg.host_adjoint(stage, lambda q: self.predict_hessian(q)[2], list(range(P)), x0, U, lin, S0, Q, R, H, gx, gS)
+
     def _propagate_refusal(self):
         """Why the one-call chain does not apply (a string), or None where it does."""
         from . import propagate as _pg

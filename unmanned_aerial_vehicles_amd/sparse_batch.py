@@ -200,6 +200,46 @@ class BatchedSparseGP:
         traj, Sigma, stages = _pg.host_loop(stage, coord, x0, U, lin, S0, Q, R, H, hess_stage)
         return (traj, Sigma, stages) if return_stages else (traj, Sigma)
 
+    def propagate_gradient(self, x0, U, lin, grad_traj, grad_Sigma=None, coord=None, in_scaler=None, Sigma0=None,
+                           process_noise=None, var_includes_noise=False, out_scaler=None, route="auto", order=1):
+        """`BatchedARDGP.propagate_gradient` on the sparse posteriors: `propagate` with the gradient of a horizon cost, raw
+        units, same arguments and results.  route="auto" and "host": the sweep on the host over `predict_jacobian` and
+        `predict_hessian` (one C call each for all models per stage).  route="chain": ONE C call per horizon for all models
+        (`gpk_sparse_propagate_grad_multi`: six launches per stage, one synchronisation; traj and Sigma with the bits of
+        `propagate(route="chain")`); ValueError where `propagate_ok()` does not hold.  order: 1 only (ValueError)."""
+        from . import propagate as _pg
+        _pg.check_grad_order(order)
+        B, D = len(self.models), self.n_features_in_
+        x0, U, lin, S0, Q, R, H, coord, in_shift, in_scale, o_mean, o_scale = _pg.check_batch(
+            B, D, x0, U, lin, coord, in_scaler, out_scaler, Sigma0, process_noise, route, routes=("auto", "host", "chain"))
+        nx = lin.shape[0]
+        gx, gS = _pg.check_seeds(grad_traj, grad_Sigma, R, H, nx)
+        if route == "chain":
+            why = self._propagate_refusal(nx)
+            if why:
+                raise ValueError(f"route='chain' is not available: {why}")
+            traj, Sigma = np.empty((H + 1, R, nx)), np.empty((H + 1, R, nx, nx))
+            dU, dx0, dS0 = np.zeros((R, H, D - nx)), np.empty((R, nx)), np.empty((R, nx, nx))
+            cd = (C.c_int * B)(*coord)
+            scaled = out_scaler is not None
+            om = np.ascontiguousarray(o_mean, dtype=np.float64) if scaled else None
+            osc = np.ascontiguousarray(o_scale, dtype=np.float64) if scaled else None
+            try:
+                with self._serving() as (be, handles):
+                    be.call("gpk_sparse_propagate_grad_multi", B, handles, int(bool(var_includes_noise)), nx, cd, _ptr(in_shift),
+                            _ptr(in_scale), _ptr(om), _ptr(osc), _ptr(x0), x0.shape[0], _ptr(U) if D > nx else None, U.shape[0],
+                            _ptr(lin), _ptr(S0), 1 if S0 is None else S0.shape[0], _ptr(Q), R, H, _ptr(traj), _ptr(Sigma), None,
+                            None, None, _ptr(gx), _ptr(gS), _ptr(dU) if D > nx else None, _ptr(dx0), _ptr(dS0))
+            except _lib.GPKError as e:
+                if e.code == _lib.GPK_BAD_ARG:
+                    raise ValueError(str(e)) from None
+                raise
+            return traj, Sigma, dU, dx0, dS0
+        stage = _pg.batch_stage(self.predict_jacobian, _pg.noise_levels(self.models), in_shift, in_scale, o_mean, o_scale,
+                                var_includes_noise, with_dvar=True)
+        hess_stage = _pg.batch_hess_stage(self.predict_hessian, in_shift, in_scale, o_scale)
+        return _pg.host_adjoint(stage, hess_stage, coord, x0, U, lin, S0, Q, R, H, gx, gS)
+
     def _propagate_refusal(self, nx=None):
         """Why the one-call chain does not apply (a string), or None where it does; nx: the state width (default B)."""
         from . import propagate as _pg
