@@ -1272,6 +1272,71 @@ GPK_API int gpk_sparse_propagate_grad_multi(gpk_handle h, int B, const gpk_handl
                                             double* jac, const double* gx, const double* gS, double* dU, double* dx0,
                                             double* dSigma0);
 
+/* ---- K11, exact moment matching: the posterior at GAUSSIAN queries, and the horizon built on it -------------------------
+ * For [C.]RBF[+White] models the posterior's moments at a query q ~ N(m, Sigma) have a closed form (Girard; Quinonero-Candela;
+ * Deisenroth).  Sigma is non-zero in the leading nx x nx (state) block of the query alone; with z = (q - in_shift) / in_scale,
+ * S = Sigma / (in_scale in_scale^T), nu_i = x_i - E[z], Lam_b = diag(ls_b^2), P_b = Lam_b^-1:
+ *   l_i          = sf2_b |I + S P_b|^(-1/2) exp(-nu_i^T (S + Lam_b)^-1 nu_i / 2)
+ *   E[mu_b]      = sum_i alpha_i l_i,       Cov[z, mu_b] = S (S + Lam_b)^-1 sum_i alpha_i l_i nu_i
+ *   L^ab_ij      = |R|^(-1/2) k_a(x_i, m) k_b(x_j, m) exp((P_a nu_i + P_b nu_j)^T R^-1 S (P_a nu_i + P_b nu_j) / 2),  R = S (P_a + P_b) + I
+ *   E[mu_a mu_b] = sum_ij alpha_i^a alpha_j^b L^ab_ij,      E[v_b] = kss_b - sum_ij (K_b^-1)_ij L^bb_ij
+ *   V_ab         = E[mu_a mu_b] - E[mu_a] E[mu_b] + [a == b] (max(E[v_b], floor) [+ noise])
+ * (one exponential per pair of rows, its exponent summed first; L is never stored).  Kinv: dev Np x ldk, the LOWER triangle of the
+ * inverse of the model's Gram matrix with its noise / jitter, as gpk_wtw writes it from the inverse factor; its identity padding
+ * is masked.  Results in RAW units: mean = y_mean + y_std E[mu], cov = y_std y_std^T V (symmetric bit for bit), xcov[o][d] =
+ * Cov[q_d, y_o] = in_scale[d] y_std[o] Cov[z_d, mu_o] (zero for d >= nx).  fp64 only.
+ * gpk_moments_host: one model with P outputs (all output pairs share one L).  M <= 32 host queries Xq (M x D) with covariances
+ *   Sq (M x nx x nx, the lower triangle is read; NULL: zero) -> mean (M x P), cov (M x P x P), xcov (M x P x D).
+ * gpk_moments_host_multi: B <= 8 single-output models, each on its own inputs, model arguments as gpk_predict_host_multi;
+ *   B (B + 1) / 2 pairs -> mean (M x B), cov (M x B x B), xcov (M x B x D).  in_shift / in_scale (D each, both or neither).
+ * Launches (gpk_moments.hip): the set-up (one wave per query and model or pair: the nx <= 16 factorisations), the row pass (two
+ *   launches: l_i with the shares of E[mu] and Cov; w_i and lam_i per pair and side), the pair pass (64 x 64 tiles of the N x N
+ *   pairs, for a == b the lower tiles with the others counted twice; every K^-1 and alpha tile read once for all M queries; sums
+ *   added in a fixed order, no atomics) and the finishing launch: five launches, one upload, three downloads, ONE synchronisation.
+ *   Repeatable bit for bit; query m has the bits of the same query served alone.  Work area: the handle's scratch.
+ * GPK_BAD_ARG (with a message, before any launch, the outputs untouched): M not in [1, 32], nx or D above 16, nx > D,
+ *   gpk_padded(N) > 16384, Np != gpk_padded(N), ldk < Np, a NULL Kinv or any other null pointer, NaN or infinity in a query, a
+ *   covariance or the model's host arrays, a length-scale or sf2 that is not positive, in_scale zero, batched mode.
+ *   The covariances must be positive semi-definite (the Python layer refuses others): the entries do not test it, and an
+ *   indefinite one gives the set-up's factorisations a pivot that is not positive, hence NaN or infinity in the results.
+ *   Replaces: nothing in the reference (its GP-MPC queries deterministic inputs); in the literature an O(N^2 P^2) pass on the CPU. */
+GPK_API int gpk_moments_host(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
+                             double sf2, const double* y_mean, const double* y_std, const double* Kinv, int64_t Np, int64_t ldk,
+                             double kss, double floor_, int var_includes_noise, double noise, int nx, const double* Xq,
+                             const double* Sq, int M, double* mean, double* cov, double* xcov);
+GPK_API int gpk_moments_host_multi(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D,
+                                   const double* ls, const double* sf2, const double* y_mean, const double* y_std,
+                                   const double* const* Kinv, int64_t Np, int64_t ldk, const double* kss, double floor_,
+                                   int var_includes_noise, const double* noise, int nx, const double* in_shift,
+                                   const double* in_scale, const double* Xq, const double* Sq, int M, double* mean, double* cov,
+                                   double* xcov);
+/* The horizon of gpk_propagate_host[_multi] with every stage's moments exact instead of linearised: with A0 = I + lin[:, :nx], E
+ * the selector of coord and Cx the state rows of the stage's xcov,
+ *   x_{h+1}     = x_h + lin q + E mean
+ *   Sigma_{h+1} = A0 Sigma_h A0^T + A0 Cx E^T + E Cx^T A0^T + E cov E^T + Q        (to first order Cx = Sigma_h J_x^T: the sibling's)
+ * The arguments of the siblings with Kinv (as above; per model in the batch form) and ldk in the place of W and ldw, and the
+ * optional stage outputs (NULL: not wanted) mean (H x R x P or B), cov (H x R x P x P or B x B), xcov (H x R x P or B x D) exactly
+ * as used: they have the BITS of gpk_moments_host[_multi] at the R Gaussian queries ([traj[h], U[h]], Sigma[h]).  Per stage the
+ * five launches above, the last of which also composes the stage (GPK_TIMED_PROPAGATE brackets it) and writes the next stage's
+ * queries on the device: 5 H launches, one upload, up to five downloads, ONE synchronisation.  Sigma is symmetric bit for bit;
+ * rollout r of a batch has the bits of that rollout alone.
+ * GPK_BAD_ARG (with a message, before any launch, the outputs untouched): the siblings' refusals (W and ldw apart), a Sigma0 with
+ * a non-finite entry, a NULL Kinv, ldk < Np.                                                                                   */
+GPK_API int gpk_propagate_mm_host(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
+                                  double sf2, const double* y_mean, const double* y_std, const double* Kinv, int64_t Np,
+                                  int64_t ldk, double kss, double floor_, int var_includes_noise, double noise, const double* x0,
+                                  int x0_rows, const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows,
+                                  const double* Q, int R, int H, double* traj, double* Sigma, double* mean, double* cov,
+                                  double* xcov);
+GPK_API int gpk_propagate_mm_host_multi(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D,
+                                        const double* ls, const double* sf2, const double* y_mean, const double* y_std,
+                                        const double* const* Kinv, int64_t Np, int64_t ldk, const double* kss, double floor_,
+                                        int var_includes_noise, const double* noise, int nx, const int* coord,
+                                        const double* in_shift, const double* in_scale, const double* x0, int x0_rows,
+                                        const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows,
+                                        const double* Q, int R, int H, double* traj, double* Sigma, double* mean, double* cov,
+                                        double* xcov);
+
 #ifdef __cplusplus
 }
 #endif

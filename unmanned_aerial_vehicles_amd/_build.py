@@ -12,7 +12,7 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libgpk.so")
 SOURCES = ["gpk_api.hip", "gpk_gram.hip", "gpk_gemm.hip", "gpk_chol.hip", "gpk_ptile.hip", "gpk_grad.hip", "gpk_mean.hip", "gpk_k5split.hip", "gpk_small.hip",
            "gpk_cov.hip", "gpk_jac.hip", "gpk_hess.hip", "gpk_serve.hip", "gpk_model.hip", "gpk_bmodel.hip", "gpk_sparse.hip", "gpk_select.hip", "gpk_paths.hip",
-           "gpk_propagate.hip"]
+           "gpk_propagate.hip", "gpk_moments.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 
 

@@ -193,6 +193,13 @@ SIGNATURES["gpk_propagate_grad_host"] = (_int, SIGNATURES["gpk_propagate_host"][
 SIGNATURES["gpk_propagate_grad_host_multi"] = (_int, SIGNATURES["gpk_propagate_host_multi"][1] + [_vp] * 5)
 SIGNATURES["gpk_sparse_propagate_grad"] = (_int, SIGNATURES["gpk_sparse_propagate"][1] + [_dp] * 5)
 SIGNATURES["gpk_sparse_propagate_grad_multi"] = (_int, SIGNATURES["gpk_sparse_propagate_multi"][1] + [_dp] * 5)
+# exact moment matching: the chain takes the siblings' arguments with (Kinv, Np, ldk) in the place of (W, Np, ldw) and (mean, cov,
+# xcov) in the place of (mean, var, jac); the query entries end with [nx, in_shift, in_scale,] Xq, Sq, M, mean, cov, xcov
+SIGNATURES["gpk_propagate_mm_host"] = (_int, list(SIGNATURES["gpk_propagate_host"][1]))
+SIGNATURES["gpk_propagate_mm_host_multi"] = (_int, list(SIGNATURES["gpk_propagate_host_multi"][1]))
+SIGNATURES["gpk_moments_host"] = (_int, SIGNATURES["gpk_propagate_host"][1][:17] + [_int, _vp, _vp, _int, _vp, _vp, _vp])
+SIGNATURES["gpk_moments_host_multi"] = (_int, SIGNATURES["gpk_propagate_host_multi"][1][:17]
+                                        + [_int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp])
 
 _lib = None
 

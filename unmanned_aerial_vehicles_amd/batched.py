@@ -407,9 +407,55 @@ class BatchedARDGP:
         s2 = sv["ys"] ** 2
         return mean, dmean, (var * s2[:, None]).T, (dvar * s2[:, None, None]).transpose(1, 0, 2)
 
+    # ------------------------------------------------------------------ exact moment matching (K11, per-axis batch)
+    def _moments_state(self):
+        """The serve state of `_serve_state` with every model's K^-1 (`DeviceGP.inverse_gram`, formed once per fit) as the
+        pointer array "Kinv"; ValueError where the models do not qualify for the one-call entries."""
+        import torch
+        sv = self._serve_state(True, any_dtype=True)
+        if sv is None or not all(d.moments_ok() for d in sv["keep"]):
+            raise ValueError("exact moment matching needs the batch's one-call path: at most 8 single-output models of equal "
+                             "size on one device, at most 16384 training rows, D <= 16, small_path != 0")
+        if sv.get("Kinv") is None:
+            Ks = [d.inverse_gram() for d in sv["keep"]]
+            with torch.cuda.device(sv["dev0"].be.device):
+                torch.cuda.synchronize()          # (formed on the models' own streams)
+            sv["Kt"] = Ks
+            sv["Kinv"] = (C.c_void_p * sv["B"])(*[k.data_ptr() for k in Ks])
+        return sv
+
+    def _moments_call(self, entry, sv, ym, ys, kss, *tail):
+        d0 = sv["dev0"]
+        try:
+            d0.be.call(entry, sv["B"], sv["X"], sv["alpha"], d0.N, d0.D, _hp(sv["ls"]), _hp(sv["sf2"]), _hp(ym), _hp(ys), sv["Kinv"],
+                       d0.Np, d0.Np, _hp(kss), 0.0, 0, None, *tail)
+        except _lib.GPKError as e:      # a limit of the entry: the caller's arguments, with the library's message
+            if e.code == _lib.GPK_BAD_ARG:
+                raise ValueError(str(e)) from None
+            raise
+
+    def predict_moments(self, X, Sigma, in_scaler=None, out_scaler=None, var_includes_noise=False):
+        """`GaussianProcessRegressor.predict_moments` for the batch, in raw units: the joint posterior of the B models at GAUSSIAN
+        queries q ~ N(X[m], Sigma[m]), all B (B + 1) / 2 pairs of models included.  X (M, D) raw, M <= 32; Sigma (M, nx, nx) or
+        (nx, nx) the raw covariance of the leading nx coordinates, or None; in_scaler / out_scaler as `propagate`.  Returns
+        (mean (M, B), cov (M, B, B), xcov (M, B, D) = Cov[q_d, y_b] per unit of the raw query and the raw output).  One C call
+        (`gpk_moments_host_multi`, five launches for all models and pairs); ValueError where the models do not qualify for it."""
+        from . import propagate as _pg
+        if not self.models:
+            raise RuntimeError("this BatchedARDGP is not fitted yet")
+        B, D = len(self.models), self.models[0].n_features_in_
+        X, S, M, nx = _pg.check_gaussian_queries(X, Sigma, D)
+        in_shift, in_scale, o_mean, o_scale = _pg.check_scalers(B, D, in_scaler, out_scaler)
+        sv = self._moments_state()
+        ym, ys = np.ascontiguousarray(o_mean + o_scale * sv["ym"]), np.ascontiguousarray(o_scale * sv["ys"])
+        mean, cov, xcov = np.empty((M, B)), np.empty((M, B, B)), np.empty((M, B, D))
+        self._moments_call("gpk_moments_host_multi", sv, ym, ys, sv["kss"] if var_includes_noise else sv["sf2"], nx, _hp(in_shift),
+                           _hp(in_scale), _hp(X), _hp(S), M, _hp(mean), _hp(cov), _hp(xcov))
+        return mean, cov, xcov
+
     # ------------------------------------------------------------------ horizon propagation (K11, per-axis batch)
     def propagate(self, x0, U, lin, coord=None, in_scaler=None, Sigma0=None, process_noise=None, var_includes_noise=False,
-                  return_stages=False, out_scaler=None, route="auto", order=1):
+                  return_stages=False, out_scaler=None, route="auto", order=1, method="linear"):
         """The batch's own closed-loop horizon in raw units: mean trajectory and linearised state covariance
         (`propagate`'s module docstring has the recursion), with the conventions of `BatchedPosteriorPaths.rollout`: the state
         has nx = len(lin) coordinates, B <= nx <= D; model b drives state coordinate coord[b] (default 0 .. B - 1); the models
@@ -421,9 +467,15 @@ class BatchedARDGP:
         per horizon (`gpk_propagate_host_multi`, three launches per stage for all models) where `_serve_state` holds; otherwise
         (or with the backend option small_path=0, or route="host") the same recursion as a host loop over
         `predict_jacobian`.  order=2: the second-order mean of `GaussianProcessRegressor.propagate` (`gpk_propagate2_host_multi`,
-        four launches per stage; the host loop contracts `predict_hessian`); the stages gain "corr" (H, R, B)."""
+        four launches per stage; the host loop contracts `predict_hessian`); the stages gain "corr" (H, R, B).
+        method="moment": every stage's exact moments at the Gaussian query N([x_h, u_h], Sigma_h) (`predict_moments`: the models'
+        cross-covariances through the shared query included) instead of their linearisation - one C call
+        (`gpk_propagate_mm_host_multi`, five launches per stage), route="host" the same recursion as a host loop over
+        `predict_moments`; the stages are {"mean" (H, R, B), "cov" (H, R, B, B), "xcov" (H, R, B, D)}; order=2 with it is a
+        ValueError.  The default method="linear" is the first-order chain above, untouched."""
         from . import propagate as _pg
         order = _pg.check_order(order)
+        _pg.check_method(method, order)
         if not self.models:
             raise RuntimeError("this BatchedARDGP is not fitted yet")
         B = len(self.models)
@@ -431,6 +483,22 @@ class BatchedARDGP:
         x0, U, lin, S0, Q, R, H, coord, in_shift, in_scale, o_mean, o_scale = _pg.check_batch(
             B, D, x0, U, lin, coord, in_scaler, out_scaler, Sigma0, process_noise, route)
         nx = lin.shape[0]
+        if method == "moment":
+            _pg.check_method(method, order, Sigma0=S0, process_noise=Q)
+            if route == "host":
+                traj, Sigma, stages = _pg.host_loop_moments(
+                    lambda q, S: self.predict_moments(q, S, in_scaler=in_scaler, out_scaler=out_scaler,
+                                                      var_includes_noise=var_includes_noise), coord, x0, U, lin, S0, Q, R, H)
+                return (traj, Sigma, stages) if return_stages else (traj, Sigma)
+            sv = self._moments_state()
+            ym, ys = np.ascontiguousarray(o_mean + o_scale * sv["ym"]), np.ascontiguousarray(o_scale * sv["ys"])
+            traj, Sigma = np.empty((H + 1, R, nx)), np.empty((H + 1, R, nx, nx))
+            mean, cov, xcov = (np.empty((H, R, B)), np.empty((H, R, B, B)), np.empty((H, R, B, D))) if return_stages else (None,) * 3
+            self._moments_call("gpk_propagate_mm_host_multi", sv, ym, ys, sv["kss"] if var_includes_noise else sv["sf2"], nx,
+                               (C.c_int * B)(*coord), _hp(in_shift), _hp(in_scale), _hp(x0), x0.shape[0], _hp(U) if D > nx else None,
+                               U.shape[0], _hp(lin), _hp(S0), 1 if S0 is None else S0.shape[0], _hp(Q), R, H, _hp(traj), _hp(Sigma),
+                               _hp(mean), _hp(cov), _hp(xcov))
+            return (traj, Sigma, {"mean": mean, "cov": cov, "xcov": xcov}) if return_stages else (traj, Sigma)
         sv = self._serve_state(True, any_dtype=True) if route == "auto" else None
         if sv is not None and int(sv["dev0"].be.options.get("small_path", 1)) != 0:
             d0 = sv["dev0"]
@@ -465,7 +533,7 @@ class BatchedARDGP:
         return (traj, Sigma, stages) if return_stages else (traj, Sigma)
 
     def propagate_gradient(self, x0, U, lin, grad_traj, grad_Sigma=None, coord=None, in_scaler=None, Sigma0=None,
-                           process_noise=None, var_includes_noise=False, out_scaler=None, route="auto", order=1):
+                           process_noise=None, var_includes_noise=False, out_scaler=None, route="auto", order=1, method="linear"):
         """`propagate` with the gradient of a horizon cost, in raw units: `GaussianProcessRegressor.propagate_gradient` with the
         batch's conventions (coord, in_scaler, out_scaler as `propagate`).  grad_traj (H + 1, R, nx), grad_Sigma (H + 1, R, nx,
         nx); returns (traj, Sigma, dU (R, H, nu), dx0 (R, nx), dSigma0 (R, nx, nx)), traj and Sigma with the bits of
@@ -474,6 +542,7 @@ class BatchedARDGP:
         `predict_hessian`.  order: 1 only (ValueError)."""
         from . import propagate as _pg
         _pg.check_grad_order(order)
+        _pg.refuse_moment(method, "propagate_gradient")
         if not self.models:
             raise RuntimeError("this BatchedARDGP is not fitted yet")
         B = len(self.models)

@@ -1,0 +1,842 @@
+// Exact moment matching (K11, method "moment"): mean, covariance and input-output covariance of the posterior of [C.]RBF[+White]
+// models at a GAUSSIAN query z ~ N(m, S), in closed form (Girard; Quinonero-Candela; Deisenroth), and the horizon chain built on it.
+// S is non-zero only in the nx x nx state block; all of it in normalised model units, nu_i = x_i - m, Lam_b = diag(ls_b^2), P_b = 1 / Lam_b:
+//
+//   l_i        = sf2_b |I + S P_b|^(-1/2) exp(-nu_i^T (S + Lam_b)^-1 nu_i / 2)
+//   E[mu_b]    = sum_i alpha_i l_i,            Cov[z, mu_b] = S (S + Lam_b)^-1 sum_i alpha_i l_i nu_i
+//   pair (a, b):  T = S_x + diag(1 / (P_a + P_b)) = C C^T,  M = S_x T^-1 diag(1 / (P_a + P_b)) = G G^T  (= R^-1 S with R = S (P_a + P_b) + I),
+//                 log |R| = log |T| + sum log (P_a + P_b)
+//   w_i^a      = G^T (P_a nu_i^a)_x,           lam_i^a = log sf2_a - nu_i^a^T P_a nu_i^a / 2 + |w_i^a|^2 / 2
+//   L_ij       = exp(-log|R| / 2 + lam_i^a + lam_j^b + w_i^a . w_j^b)         one exp per pair of rows, never stored
+//   E[mu_a mu_b] = sum_ij alpha_i^a alpha_j^b L_ij,     E[v_b] = kss_b - sum_ij (K_b^-1)_ij L^bb_ij
+//   V_ab       = E[mu_a mu_b] - E[mu_a] E[mu_b] + [a == b] (max(E[v_b], floor) [+ noise])
+//
+// Five launches per batch of R <= 32 Gaussian queries (the rows of a predict_moments call, or the rollouts of one stage of the chain):
+//   moments_setup_kernel     one wave per (query, model or pair): the sequential nx <= 16 factorisations
+//   moments_row_*_kernel     the N rows: l_i and the workgroups' shares of E[mu] and sum alpha l nu;  lam_i, w_i per (pair, side)
+//   moments_pair_kernel<P>   the N x N pairs in 64 x 64 tiles (a == b: the lower tiles, the others counted twice): every K^-1 and alpha
+//                            tile is read ONCE and serves all R queries; the tile's sums are added in a fixed order in LDS and then to
+//                            the workgroup's own slot - no atomics; workgroup g owns tiles g, g + G, ..
+//   moments_finish_kernel    one workgroup per query: the slots added in workgroup order, V, the raw units and - in the chain - the
+//                            stage:  x+ = x + lin q + E E[mu],  Sigma+ = A0 Sigma A0^T + A0 Cx E^T + E Cx^T A0^T + E V E^T + Q  with
+//                            A0 = I + lin[:, :nx] and Cx the state rows of the raw input-output covariance; the lower triangle is formed
+//                            and mirrored.
+// Nothing depends on R or on the other queries: query r of a batch has the bits of the same query served alone.
+#include "gpk_internal.h"
+
+namespace {
+
+constexpr int MM_TILE = 64;        // rows and columns of a pair tile; a thread holds 4 x 4 pairs
+constexpr int MM_CH = 12;          // tile sums reduced per pass through LDS
+constexpr int MM_MAXG = 512;       // workgroups per pair at most (two per CU)
+constexpr int MM_WS = 17;          // doubles per row of the row pass: w (16) and lam
+constexpr int MM_ROWS = 256;       // rows per workgroup of the row pass
+
+struct MomK {
+  int B, P, D, nx, NO, U;            // models, outputs per model, query width, state width, B * P, pairs B (B + 1) / 2
+  long long N, Np, ldk;
+  const double* X[GPK_SMALL_MAX_MODELS];
+  const double* alpha[GPK_SMALL_MAX_MODELS];
+  const double* Kinv[GPK_SMALL_MAX_MODELS];
+  double ls[GPK_SMALL_MAX_MODELS][16], lsf2[GPK_SMALL_MAX_MODELS], kss[GPK_SMALL_MAX_MODELS], noise[GPK_SMALL_MAX_MODELS];
+  double ymean[16], ystd[16];        // per output, the output scaler folded in
+  double in_shift[16], in_scale[16];
+  double floor_;
+  int add_noise, scaled;
+  int model_of[16];                  // state coordinate -> output, or -1
+};
+
+__device__ __forceinline__ void pair_of(int u, int& a, int& b) {
+  a = 0;
+  while ((a + 1) * (a + 2) / 2 <= u) ++a;
+  b = u - a * (a + 1) / 2;
+}
+
+// In-place lower Cholesky factor of the leading n x n block, one wave, row `lane` owned by that lane.  A pivot that is not
+// positive gives a zero column (semi-definite M: what Sigma = 0 or a rank-deficient Sigma produces).
+__device__ __forceinline__ void mm_chol(double (*A)[17], int n, int lane) {
+  for (int c = 0; c < n; ++c) {
+    __syncthreads();
+    const double p = A[c][c];
+    const double d = p > 0.0 ? sqrt(p) : 0.0;
+    __syncthreads();
+    if (lane == c) A[c][c] = d;
+    if (lane > c && lane < n) A[lane][c] = p > 0.0 ? A[lane][c] / d : 0.0;
+    __syncthreads();
+    if (lane > c && lane < n)
+      for (int j = c + 1; j <= lane; ++j) A[lane][j] -= A[lane][c] * A[j][c];
+  }
+  __syncthreads();
+}
+
+// grid (R, B + U), 64 threads.  Units [0, B): model b -> Bm = (S_x + Lam_b,x)^-1 and cm = log sf2_b - log|I + S P_b| / 2; unit 0 also
+// writes S_z.  Units [B, B + U): pair u -> G (lower, zero above) and cl = -log|R| / 2.  Sraw: R x nx x nx raw covariances.
+__global__ __launch_bounds__(64) void moments_setup_kernel(MomK k, const double* __restrict__ Sraw, double* Sz, double* Bm, double* cm,
+                                                           double* G, double* cl) {
+  __shared__ double S[16][17], T[16][17], Ci[16][17], Y[16][17], dd[16];
+  const int lane = threadIdx.x, r = blockIdx.x, unit = blockIdx.y, nx = k.nx;
+  for (int e = lane; e < 256; e += 64) {
+    const int i = e >> 4, j = e & 15;
+    double s = 0.0;
+    if (i < nx && j < nx) {
+      s = Sraw[((long long)r * nx + i) * nx + j];
+      if (k.scaled) s = s / (k.in_scale[i] * k.in_scale[j]);
+    }
+    S[i][j] = s;
+    Ci[i][j] = 0.0;
+    Y[i][j] = 0.0;
+  }
+  int a = 0, b = 0;
+  const bool pair = unit >= k.B;
+  if (pair) pair_of(unit - k.B, a, b); else a = b = unit;
+  if (lane < 16) {
+    double d = 1.0;
+    if (lane < nx) {
+      const double la = k.ls[a][lane], lb = k.ls[b][lane];
+      d = pair ? 1.0 / (1.0 / (la * la) + 1.0 / (lb * lb)) : la * la;
+    }
+    dd[lane] = d;
+  }
+  __syncthreads();
+  for (int e = lane; e < 256; e += 64) {
+    const int i = e >> 4, j = e & 15;
+    T[i][j] = S[i][j] + (i == j ? dd[i] : 0.0);
+  }
+  if (unit == 0)
+    for (int e = lane; e < 256; e += 64) Sz[(long long)r * 256 + e] = S[e >> 4][e & 15];
+  mm_chol(T, nx, lane);
+  // Ci = C^-1, lane j solves column j
+  if (lane < nx) {
+    const int j = lane;
+    for (int i = j; i < nx; ++i) {
+      double s = i == j ? 1.0 : 0.0;
+      for (int c = j; c < i; ++c) s -= T[i][c] * Ci[c][j];
+      Ci[i][j] = s / T[i][i];
+    }
+  }
+  __syncthreads();
+  double logdet = 0.0;
+  for (int c = 0; c < nx; ++c) logdet += 2.0 * log(T[c][c]) - log(dd[c]);
+  if (!pair) {
+    // Bm = Ci^T Ci, the lower triangle formed and mirrored
+    for (int e = lane; e < 256; e += 64) {
+      const int i = e >> 4, j = e & 15;
+      if (i < nx && j <= i) {
+        double s = 0.0;
+        for (int c = i; c < nx; ++c) s = __builtin_fma(Ci[c][i], Ci[c][j], s);
+        Y[i][j] = s;
+        Y[j][i] = s;
+      }
+    }
+    __syncthreads();
+    double* o = Bm + ((long long)r * k.B + unit) * 256;
+    for (int e = lane; e < 256; e += 64) o[e] = Y[e >> 4][e & 15];
+    if (lane == 0) cm[(long long)r * k.B + unit] = k.lsf2[unit] - 0.5 * logdet;
+    return;
+  }
+  // Y = Ci S;  M = Y^T Ci diag(dd) (lower triangle, mirrored) -> T;  G = chol(M)
+  for (int e = lane; e < 256; e += 64) {
+    const int i = e >> 4, j = e & 15;
+    if (i < nx && j < nx) {
+      double s = 0.0;
+      for (int c = 0; c <= i; ++c) s = __builtin_fma(Ci[i][c], S[c][j], s);
+      Y[i][j] = s;
+    }
+  }
+  __syncthreads();
+  for (int e = lane; e < 256; e += 64) {
+    const int i = e >> 4, j = e & 15;
+    if (i < nx && j <= i) {
+      double s = 0.0;
+      for (int c = j; c < nx; ++c) s = __builtin_fma(Y[c][i], Ci[c][j], s);
+      s *= dd[j];
+      T[i][j] = s;
+      T[j][i] = s;
+    }
+  }
+  mm_chol(T, nx, lane);
+  const int u = unit - k.B;
+  double* o = G + ((long long)r * k.U + u) * 256;
+  for (int e = lane; e < 256; e += 64) {
+    const int i = e >> 4, j = e & 15;
+    o[e] = (i < nx && j <= i) ? T[i][j] : 0.0;
+  }
+  if (lane == 0) cl[(long long)r * k.U + u] = -0.5 * logdet;
+}
+
+// grid (ceil(N / 256), R, B), 256 threads.  q: R x D scaled queries.  part[((wg R + r) B + b) P + p][17]: entries d < nx the share of
+// sum_i alpha_ip l_i nu_id, entry 16 that of sum_i alpha_ip l_i; the rows of a workgroup are added in row order.
+__global__ __launch_bounds__(256) void moments_row_mean_kernel(MomK k, const double* __restrict__ q, const double* __restrict__ Bm,
+                                                               const double* __restrict__ cm, double* part) {
+  __shared__ double sB[16][17], lv[MM_ROWS][MM_WS], z[16], ils2[16];
+  const int tid = threadIdx.x, r = blockIdx.y, b = blockIdx.z, R = gridDim.y, D = k.D, nx = k.nx, P = k.P;
+  const long long row = (long long)blockIdx.x * MM_ROWS + tid;
+  sB[tid >> 4][tid & 15] = Bm[((long long)r * k.B + b) * 256 + tid];
+  if (tid < 16) {
+    z[tid] = tid < D ? q[(long long)r * D + tid] : 0.0;
+    ils2[tid] = (tid >= nx && tid < D) ? 1.0 / (k.ls[b][tid] * k.ls[b][tid]) : 0.0;
+  }
+  __syncthreads();
+  const bool live = row < k.N;
+  const double* xr = k.X[b] + row * D;
+  double nu[16];
+#pragma unroll
+  for (int d = 0; d < 16; ++d) nu[d] = (live && d < D) ? xr[d] - z[d] : 0.0;
+  double quad = 0.0;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    if (i < nx) {
+      double t = 0.0;
+#pragma unroll
+      for (int j = 0; j < 16; ++j) t = __builtin_fma(sB[i][j], nu[j], t);      // (columns >= nx of Bm are zero)
+      quad = __builtin_fma(nu[i], t, quad);
+    } else {
+      quad = __builtin_fma(nu[i] * nu[i], ils2[i], quad);
+    }
+  }
+  const double l = live ? exp(cm[(long long)r * k.B + b] - 0.5 * quad) : 0.0;
+#pragma unroll
+  for (int d = 0; d < 16; ++d) lv[tid][d] = l * nu[d];
+  lv[tid][16] = l;
+  __syncthreads();
+  const long long base = (long long)blockIdx.x * MM_ROWS;
+  for (int e = tid; e < P * MM_WS; e += 256) {
+    const int p = e / MM_WS, d = e % MM_WS;
+    if (d >= nx && d != 16) continue;
+    double s = 0.0;
+    for (int t = 0; t < MM_ROWS; ++t) {
+      const double al = base + t < k.N ? k.alpha[b][(base + t) * P + p] : 0.0;
+      s = __builtin_fma(al, lv[t][d], s);
+    }
+    part[((((long long)blockIdx.x * R + r) * k.B + b) * P + p) * MM_WS + d] = s;
+  }
+}
+
+// grid (ceil(N / 256), R, 2 U), 256 threads.  rowq[((a a + 2 b + side) R + r) Np + i][17] = w_i (entries < nx, zero to 16) and lam_i of
+// model a (side 0) or b (side 1) of pair u; a == b has side 0 alone.
+__global__ __launch_bounds__(256) void moments_row_pair_kernel(MomK k, const double* __restrict__ q, const double* __restrict__ G,
+                                                               double* rowq) {
+  __shared__ double sG[16][17], z[16], ip[16];
+  const int tid = threadIdx.x, r = blockIdx.y, u = blockIdx.z >> 1, side = blockIdx.z & 1, R = gridDim.y, D = k.D, nx = k.nx;
+  int a, b;
+  pair_of(u, a, b);
+  if (side == 1 && a == b) return;
+  const int m = side ? b : a;
+  const long long row = (long long)blockIdx.x * MM_ROWS + tid;
+  sG[tid >> 4][tid & 15] = G[((long long)r * k.U + u) * 256 + tid];
+  if (tid < 16) {
+    z[tid] = tid < D ? q[(long long)r * D + tid] : 0.0;
+    ip[tid] = tid < D ? 1.0 / (k.ls[m][tid] * k.ls[m][tid]) : 0.0;
+  }
+  __syncthreads();
+  if (row >= k.N) return;
+  const double* xr = k.X[m] + row * D;
+  double t[16];
+  double e0 = 0.0;
+#pragma unroll
+  for (int d = 0; d < 16; ++d) {
+    const double nu = d < D ? xr[d] - z[d] : 0.0;
+    t[d] = nu * ip[d];
+    e0 = __builtin_fma(nu, t[d], e0);
+  }
+  double* o = rowq + (((long long)(a * a + 2 * b + side) * R + r) * k.Np + row) * MM_WS;
+  double ww = 0.0;
+#pragma unroll
+  for (int c = 0; c < 16; ++c) {
+    double w = 0.0;
+    if (c < nx) {
+#pragma unroll
+      for (int i = c; i < 16; ++i) w = __builtin_fma(sG[i][c], t[i], w);       // (rows >= nx of G are zero)
+    }
+    o[c] = w;
+    ww = __builtin_fma(w, w, ww);
+  }
+  o[16] = k.lsf2[m] - 0.5 * e0 + 0.5 * ww;
+}
+
+// grid (G, U), 256 threads: thread (ty, tx) = (tid >> 4, tid & 15) holds the pairs (ty + 16 ii, tx + 16 jj) of a tile.
+// part[((u G + g) R + r) NV + v], NV = 1 + P (P + 1) / 2: v = 0 the K^-1 sum (a == b), v = 1 + p (p + 1) / 2 + q the alpha sums.
+template <int P>
+__global__ __launch_bounds__(256) void moments_pair_kernel(MomK k, int R, const double* __restrict__ rowq,
+                                                           const double* __restrict__ cl, double* part) {
+  constexpr int NV = 1 + P * (P + 1) / 2;
+  __shared__ double sA[MM_TILE][P], sB[MM_TILE][P], sWa[MM_TILE][MM_WS], sWb[MM_TILE][MM_WS], red[MM_CH][16 * 17], red2[MM_CH][16];
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4, u = blockIdx.y, g = blockIdx.x, G_ = gridDim.x, nx = k.nx;
+  int a, b;
+  pair_of(u, a, b);
+  const bool same = a == b;
+  const long long N = k.N;
+  const int nt = (int)((N + MM_TILE - 1) / MM_TILE);
+  const long long ntiles = same ? (long long)nt * (nt + 1) / 2 : (long long)nt * nt;
+  const double* Wa = rowq + (long long)(a * a + 2 * b) * R * k.Np * MM_WS;      // (pair, side) -> slot a a + 2 b + side: B B slots
+  const double* Wb = same ? Wa : Wa + (long long)R * k.Np * MM_WS;
+  bool first = true;
+  for (long long t = g; t < ntiles; t += G_) {
+    int ti, tj;
+    if (same) {
+      ti = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+      while ((long long)(ti + 1) * (ti + 2) / 2 <= t) ++ti;
+      while ((long long)ti * (ti + 1) / 2 > t) --ti;
+      tj = (int)(t - (long long)ti * (ti + 1) / 2);
+    } else {
+      ti = (int)(t / nt);
+      tj = (int)(t % nt);
+    }
+    const bool sym = same && ti != tj;
+    const double wgt = sym ? 2.0 : 1.0;
+    const long long i0 = (long long)ti * MM_TILE, j0 = (long long)tj * MM_TILE;
+    double kv[4][4];
+#pragma unroll
+    for (int ii = 0; ii < 4; ++ii)
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) {
+        const long long i = i0 + ty + 16 * ii, j = j0 + tx + 16 * jj;
+        // the lower triangle of K^-1 is the matrix; rows and columns >= N (its identity padding) are masked
+        kv[ii][jj] = (same && i < N && j < N) ? k.Kinv[a][(i > j ? i : j) * k.ldk + (i > j ? j : i)] : 0.0;
+      }
+    __syncthreads();
+    for (int e = tid; e < MM_TILE * P; e += 256) {
+      const int row = e / P, p = e % P;
+      sA[row][p] = i0 + row < N ? k.alpha[a][(i0 + row) * P + p] : 0.0;
+      sB[row][p] = j0 + row < N ? k.alpha[b][(j0 + row) * P + p] : 0.0;
+    }
+    for (int r = 0; r < R; ++r) {
+      __syncthreads();
+      for (int e = tid; e < MM_TILE * MM_WS; e += 256) {
+        const int row = e / MM_WS;
+        sWa[row][e % MM_WS] = i0 + row < N ? Wa[((long long)r * k.Np + i0) * MM_WS + e] : 0.0;
+        sWb[row][e % MM_WS] = j0 + row < N ? Wb[((long long)r * k.Np + j0) * MM_WS + e] : 0.0;
+      }
+      __syncthreads();
+      const double c0 = cl[(long long)r * k.U + u];
+      double ex[4][4];
+#pragma unroll
+      for (int ii = 0; ii < 4; ++ii)
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) ex[ii][jj] = (c0 + sWa[ty + 16 * ii][16]) + sWb[tx + 16 * jj][16];
+      for (int c = 0; c < nx; ++c) {
+        double wa[4], wb[4];
+#pragma unroll
+        for (int ii = 0; ii < 4; ++ii) { wa[ii] = sWa[ty + 16 * ii][c]; wb[ii] = sWb[tx + 16 * ii][c]; }
+#pragma unroll
+        for (int ii = 0; ii < 4; ++ii)
+#pragma unroll
+          for (int jj = 0; jj < 4; ++jj) ex[ii][jj] = __builtin_fma(wa[ii], wb[jj], ex[ii][jj]);
+      }
+#pragma unroll
+      for (int ii = 0; ii < 4; ++ii)
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+          const bool live = i0 + ty + 16 * ii < N && j0 + tx + 16 * jj < N;
+          ex[ii][jj] = live ? exp(ex[ii][jj]) : 0.0;
+        }
+      // the tile's sums, MM_CH at a time: every thread's share to LDS, 16 shares per lane group in lane order, the 16 groups in
+      // group order, then thread v adds the sum to the workgroup's slot
+      double* slot = part + (((long long)u * G_ + g) * R + r) * NV;
+      auto flush = [&](int chunk, int nvals) {
+        __syncthreads();
+        if (ty < nvals) {
+          double s = 0.0;
+#pragma unroll
+          for (int c = 0; c < 16; ++c) s += red[ty][tx * 17 + c];
+          red2[ty][tx] = s;
+        }
+        __syncthreads();
+        if (tid < nvals) {
+          double s = 0.0;
+#pragma unroll
+          for (int c = 0; c < 16; ++c) s += red2[tid][c];
+          s *= wgt;
+          double* dst = slot + chunk * MM_CH + tid;
+          *dst = first ? s : *dst + s;
+        }
+      };
+      auto emit = [&](int v, double x) {
+        red[v % MM_CH][ty * 17 + tx] = x;
+        if (v % MM_CH == MM_CH - 1 || v == NV - 1) flush(v / MM_CH, v % MM_CH + 1);
+      };
+      {
+        double s = 0.0;
+#pragma unroll
+        for (int ii = 0; ii < 4; ++ii)
+#pragma unroll
+          for (int jj = 0; jj < 4; ++jj) s = __builtin_fma(ex[ii][jj], kv[ii][jj], s);
+        emit(0, s);
+      }
+      double uu[4][P];
+#pragma unroll
+      for (int qq = 0; qq < P; ++qq) {
+        double bj[4];
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) bj[jj] = sB[tx + 16 * jj][qq];
+#pragma unroll
+        for (int ii = 0; ii < 4; ++ii) {
+          double s = 0.0;
+#pragma unroll
+          for (int jj = 0; jj < 4; ++jj) s = __builtin_fma(ex[ii][jj], bj[jj], s);
+          uu[ii][qq] = s;
+        }
+      }
+#pragma unroll
+      for (int p = 0; p < P; ++p)
+#pragma unroll
+        for (int qq = 0; qq <= p; ++qq) {
+          double s = 0.0;
+#pragma unroll
+          for (int ii = 0; ii < 4; ++ii) s = __builtin_fma(sA[ty + 16 * ii][p], uu[ii][qq], s);
+          if (sym) {      // an off-diagonal tile stands for its mirror image too: alpha_ip alpha_jq + alpha_iq alpha_jp
+            double s2 = 0.0;
+#pragma unroll
+            for (int ii = 0; ii < 4; ++ii) s2 = __builtin_fma(sA[ty + 16 * ii][qq], uu[ii][p], s2);
+            s = 0.5 * (s + s2);      // (the slot takes the sum times wgt = 2)
+          }
+          emit(1 + p * (p + 1) / 2 + qq, s);
+        }
+    }
+    first = false;
+  }
+}
+
+// What the finishing launch does past the moments: the stage of the chain (x null: a predict_moments call, outputs only).
+struct MomAdv {
+  const double *lin, *Qn, *u, *u_next;
+  long long u_row_stride;
+  double *x, *S, *qnext, *traj_next, *sig_next;
+};
+
+// grid R, 256 threads, thread (i, j) = (tid >> 4, tid & 15).  omean (R x NO), ocov (R x NO x NO), oxcov (R x NO x D): raw units.
+__global__ __launch_bounds__(256) void moments_finish_kernel(MomK k, MomAdv v, int R, int G_, int nrw, int NV,
+                                                             const double* __restrict__ Sz, const double* __restrict__ Bm,
+                                                             const double* __restrict__ rowpart, const double* __restrict__ pairpart,
+                                                             double* omean, double* ocov, double* oxcov) {
+  __shared__ double Em[16], Cz[16][17], Tm[16][17], Vr[16][17], Cx[16][17], sS[16][17], pv[160];
+  __shared__ double A[16][17], Sg[16][17], T[16][17], F[16][17], q[16], xn[16], mu[16];
+  const int tid = threadIdx.x, i = tid >> 4, j = tid & 15, r = blockIdx.x;
+  const int nx = k.nx, D = k.D, NO = k.NO, P = k.P, B = k.B;
+  sS[i][j] = Sz[(long long)r * 256 + tid];
+  for (int e = tid; e < NO * MM_WS; e += 256) {
+    const int o = e / MM_WS, d = e % MM_WS;
+    if (d >= nx && d != 16) continue;
+    double s = 0.0;
+    for (int w = 0; w < nrw; ++w) s += rowpart[(((long long)w * R + r) * NO + o) * MM_WS + d];
+    if (d == 16) Em[o] = s; else Cz[o][d] = s;
+  }
+  for (int e = tid; e < k.U * NV; e += 256) {
+    const int u = e / NV, vv = e % NV;
+    const double* p = pairpart + ((long long)u * G_ * R + r) * NV + vv;
+    double s = 0.0;
+#pragma unroll 8
+    for (int g = 0; g < G_; ++g) s += p[(long long)g * R * NV];
+    pv[e] = s;
+  }
+  __syncthreads();
+  // V in raw units, the lower triangle formed and mirrored
+  if (i < NO && j <= i) {
+    const int u = B > 1 ? i * (i + 1) / 2 + j : 0;
+    const int at = B > 1 ? u * NV + 1 : 1 + i * (i + 1) / 2 + j;
+    double s = pv[at] - Em[i] * Em[j];
+    if (i == j) {
+      const int b = B > 1 ? i : 0;
+      const double ev = k.kss[b] - pv[B > 1 ? u * NV : 0];
+      double var = ev > k.floor_ ? ev : k.floor_;
+      if (k.add_noise) var += k.noise[b];
+      s += var;
+    }
+    s *= k.ystd[i] * k.ystd[j];
+    Vr[i][j] = s;
+    Vr[j][i] = s;
+  }
+  // Cov[z, mu_o] = S_z Bm_b (sum alpha l nu_x): Tm = Bm_b Cz[o], then S_z Tm
+  if (i < NO && j < nx) {
+    const double* bm = Bm + ((long long)r * B + i / P) * 256;
+    double s = 0.0;
+    for (int c = 0; c < nx; ++c) s = __builtin_fma(bm[j * 16 + c], Cz[i][c], s);
+    Tm[i][j] = s;
+  }
+  __syncthreads();
+  if (i < NO && j < nx) {
+    double s = 0.0;
+    for (int c = 0; c < nx; ++c) s = __builtin_fma(sS[j][c], Tm[i][c], s);
+    Cx[i][j] = k.ystd[i] * (k.scaled ? k.in_scale[j] * s : s);
+  }
+  if (tid < NO) mu[tid] = k.ymean[tid] + k.ystd[tid] * Em[tid];
+  __syncthreads();
+  if (omean && tid < NO) omean[(long long)r * NO + tid] = mu[tid];
+  if (ocov && i < NO && j < NO) ocov[((long long)r * NO + i) * NO + j] = Vr[i][j];
+  if (oxcov && i < NO && j < D) oxcov[((long long)r * NO + i) * D + j] = j < nx ? Cx[i][j] : 0.0;
+  if (!v.x) return;
+  if (tid < D) q[tid] = tid < nx ? v.x[(long long)r * nx + tid] : v.u[r * v.u_row_stride + (tid - nx)];
+  if (i < nx && j < nx) {
+    Sg[i][j] = v.S[((long long)r * nx + i) * nx + j];
+    A[i][j] = (i == j ? 1.0 : 0.0) + v.lin[i * D + j];
+  }
+  __syncthreads();
+  if (tid < nx) {
+    const int o = k.model_of[tid];
+    double a = 0.0;
+    for (int d = 0; d < D; ++d) a = __builtin_fma(v.lin[tid * D + d], q[d], a);
+    double val = q[tid] + a;
+    if (o >= 0) val += mu[o];
+    xn[tid] = val;
+  }
+  if (i < nx && j < nx) {
+    double t = 0.0;
+    for (int c = 0; c < nx; ++c) t = __builtin_fma(A[i][c], Sg[c][j], t);
+    T[i][j] = t;
+    // F = A0 Cx E^T: column j is A0 times the input-output covariance of the output that drives coordinate j
+    const int o = k.model_of[j];
+    double f = 0.0;
+    if (o >= 0)
+      for (int c = 0; c < nx; ++c) f = __builtin_fma(A[i][c], Cx[o][c], f);
+    F[i][j] = f;
+  }
+  __syncthreads();
+  if (i < nx && j <= i) {
+    double s = 0.0;
+    for (int c = 0; c < nx; ++c) s = __builtin_fma(T[i][c], A[j][c], s);
+    s += F[i][j] + F[j][i];
+    const int oi = k.model_of[i], oj = k.model_of[j];
+    if (oi >= 0 && oj >= 0) s += Vr[oi][oj];
+    if (v.Qn) s += v.Qn[i * nx + j];
+    const long long at = (long long)r * nx * nx;
+    v.S[at + i * nx + j] = s;
+    v.S[at + j * nx + i] = s;
+    v.sig_next[at + i * nx + j] = s;
+    v.sig_next[at + j * nx + i] = s;
+  }
+  if (tid < nx) {
+    v.x[(long long)r * nx + tid] = xn[tid];
+    v.traj_next[(long long)r * nx + tid] = xn[tid];
+  }
+  if (v.qnext && tid < D) {
+    const double raw = tid < nx ? xn[tid] : v.u_next[r * v.u_row_stride + (tid - nx)];
+    v.qnext[(long long)r * D + tid] = k.scaled ? (raw - k.in_shift[tid]) / k.in_scale[tid] : raw;
+  }
+}
+
+bool mm_finite(const double* p, size_t n) {
+  for (size_t i = 0; i < n; ++i)
+    if (!(p[i] - p[i] == 0.0)) return false;
+  return true;
+}
+
+// The device work area of one batch of R queries, carved from `base`.
+struct MomWork {
+  double *Sz, *Bm, *cm, *G, *cl, *rowq, *rowpart, *pairpart;
+  int nrw, G_, NV;
+  size_t doubles;
+};
+MomWork mm_work(const MomK& k, int R, double* base) {
+  MomWork w{};
+  const int nt = (int)((k.N + MM_TILE - 1) / MM_TILE);
+  const long long lower = (long long)nt * (nt + 1) / 2;
+  w.nrw = (int)((k.N + MM_ROWS - 1) / MM_ROWS);
+  w.G_ = (int)(lower < MM_MAXG ? lower : MM_MAXG);
+  w.NV = 1 + k.P * (k.P + 1) / 2;
+  size_t at = 0;
+  auto take = [&](size_t n) { double* p = base ? base + at : nullptr; at += n; return p; };
+  w.Sz = take((size_t)R * 256);
+  w.Bm = take((size_t)R * k.B * 256);
+  w.cm = take((size_t)R * k.B);
+  w.G = take((size_t)R * k.U * 256);
+  w.cl = take((size_t)R * k.U);
+  w.rowq = take((size_t)k.B * k.B * R * k.Np * MM_WS);      // one slot per (pair, side) in use: a == b has side 0 alone
+  w.rowpart = take((size_t)w.nrw * R * k.NO * MM_WS);
+  w.pairpart = take((size_t)k.U * w.G_ * R * w.NV);
+  w.doubles = at;
+  return w;
+}
+
+template <int P>
+void mm_pair_launch(gpk_handle h, const MomK& k, const MomWork& w, int R) {
+  hipLaunchKernelGGL(moments_pair_kernel<P>, dim3((unsigned)w.G_, (unsigned)k.U), dim3(256), 0, h->stream, k, R, (const double*)w.rowq,
+                     (const double*)w.cl, w.pairpart);
+}
+
+// The four launches ahead of the finishing one: d_q (R x D scaled queries) and d_S (R x nx x nx raw covariances) on the device.
+int mm_launch(gpk_handle h, const MomK& k, const MomWork& w, int R, const double* d_q, const double* d_S) {
+  hipLaunchKernelGGL(moments_setup_kernel, dim3((unsigned)R, (unsigned)(k.B + k.U)), dim3(64), 0, h->stream, k, d_S, w.Sz, w.Bm, w.cm,
+                     w.G, w.cl);
+  GPK_LAUNCH_CHECK(h);
+  hipLaunchKernelGGL(moments_row_mean_kernel, dim3((unsigned)w.nrw, (unsigned)R, (unsigned)k.B), dim3(256), 0, h->stream, k, d_q,
+                     (const double*)w.Bm, (const double*)w.cm, w.rowpart);
+  hipLaunchKernelGGL(moments_row_pair_kernel, dim3((unsigned)w.nrw, (unsigned)R, (unsigned)(2 * k.U)), dim3(256), 0, h->stream, k, d_q,
+                     (const double*)w.G, w.rowq);
+  GPK_LAUNCH_CHECK(h);
+  switch (k.P) {
+#define GPK_MM_CASE(p) case p: mm_pair_launch<p>(h, k, w, R); break;
+    GPK_MM_CASE(1) GPK_MM_CASE(2) GPK_MM_CASE(3) GPK_MM_CASE(4) GPK_MM_CASE(5) GPK_MM_CASE(6) GPK_MM_CASE(7) GPK_MM_CASE(8)
+    GPK_MM_CASE(9) GPK_MM_CASE(10) GPK_MM_CASE(11) GPK_MM_CASE(12) GPK_MM_CASE(13) GPK_MM_CASE(14) GPK_MM_CASE(15) GPK_MM_CASE(16)
+#undef GPK_MM_CASE
+  }
+  GPK_LAUNCH_CHECK(h);
+  return GPK_OK;
+}
+
+void mm_finish(gpk_handle h, const MomK& k, const MomWork& w, const MomAdv& v, int R, double* omean, double* ocov, double* oxcov) {
+  hipLaunchKernelGGL(moments_finish_kernel, dim3((unsigned)R), dim3(256), 0, h->stream, k, v, R, w.G_, w.nrw, w.NV, (const double*)w.Sz,
+                     (const double*)w.Bm, (const double*)w.rowpart, (const double*)w.pairpart, omean, ocov, oxcov);
+}
+
+// What the four entries are called with, past the handle.
+struct MomModels {
+  int B, P;
+  const double* const* X;
+  const double* const* alpha;
+  int64_t N;
+  int D;
+  const double *ls, *sf2, *y_mean, *y_std;
+  const double* const* Kinv;
+  int64_t Np, ldk;
+  const double* kss;
+  double floor_;
+  int var_includes_noise;
+  const double* noise;
+  int nx;
+  const int* coord;                  // B state coordinates (batch) or null (single model: output p drives coordinate p)
+  const double *in_shift, *in_scale;
+};
+
+// Every check of the model arguments (GPK_BAD_ARG before anything is launched) and the kernels' parameter block.
+int mm_models(gpk_handle h, const std::string& who, const MomModels& m, bool chain, MomK& k) {
+  GPK_REQUIRE(h, h->batch == 1, who + "not available in batched mode");
+  GPK_REQUIRE(h, m.X && m.alpha && m.ls && m.sf2 && m.y_mean && m.y_std && m.kss, who + "null pointer");
+  GPK_REQUIRE(h, m.Kinv, who + "null K^-1 (gpk_wtw of the model's inverse factor)");
+  GPK_REQUIRE(h, m.B >= 1 && m.B <= GPK_SMALL_MAX_MODELS, who + "1..8 models");
+  GPK_REQUIRE(h, m.P >= 1 && m.P <= GPK_MAX_P && m.P <= 16 && (m.B == 1 || m.P == 1), who + "P must be in [1, 16]");
+  GPK_REQUIRE(h, m.D >= 1 && m.D <= GPK_PROP_MAX_D && m.nx >= 1 && m.nx <= GPK_PROP_MAX_NX && m.nx <= m.D, who + "needs 1 <= nx <= D <= 16");
+  GPK_REQUIRE(h, !chain || m.nx >= m.B * m.P, who + "the state dimension nx must not be below the number of outputs");
+  GPK_REQUIRE(h, m.N >= 1 && gpk_padded(m.N) <= GPK_SMALL_MAX_NP && m.Np == gpk_padded(m.N),
+              who + "needs N <= 16384 and Np = gpk_padded(N)");
+  GPK_REQUIRE(h, m.ldk >= m.Np, who + "needs ldk >= Np");
+  GPK_REQUIRE(h, !m.var_includes_noise || m.noise, who + "null noise levels");
+  GPK_REQUIRE(h, (m.in_shift == nullptr) == (m.in_scale == nullptr), who + "in_shift and in_scale go together");
+  const int NO = m.B * m.P;
+  for (int b = 0; b < m.B; ++b) GPK_REQUIRE(h, m.X[b] && m.alpha[b], who + "null model pointer");
+  for (int b = 0; b < m.B; ++b) GPK_REQUIRE(h, m.Kinv[b], who + "null K^-1 (gpk_wtw of the model's inverse factor)");
+  GPK_REQUIRE(h, mm_finite(m.ls, (size_t)m.B * m.D) && mm_finite(m.sf2, m.B) && mm_finite(m.y_mean, NO) && mm_finite(m.y_std, NO),
+              who + "ls, sf2, y_mean and y_std must not contain NaN or infinity");
+  for (int i = 0; i < m.B * m.D; ++i) GPK_REQUIRE(h, m.ls[i] > 0.0, who + "length-scales must be positive");
+  for (int b = 0; b < m.B; ++b) GPK_REQUIRE(h, m.sf2[b] > 0.0, who + "sf2 must be positive");
+  GPK_REQUIRE(h, mm_finite(m.kss, m.B) && mm_finite(&m.floor_, 1) && (!m.var_includes_noise || mm_finite(m.noise, m.B)),
+              who + "kss, floor and noise must be finite");
+  k = MomK{};
+  k.B = m.B; k.P = m.P; k.D = m.D; k.nx = m.nx; k.NO = NO; k.U = m.B * (m.B + 1) / 2;
+  k.N = m.N; k.Np = m.Np; k.ldk = m.ldk;
+  k.floor_ = m.floor_;
+  k.add_noise = m.var_includes_noise != 0;
+  for (int d = 0; d < 16; ++d) { k.in_shift[d] = 0.0; k.in_scale[d] = 1.0; k.model_of[d] = -1; }
+  for (int b = 0; b < m.B; ++b) {
+    k.X[b] = m.X[b]; k.alpha[b] = m.alpha[b]; k.Kinv[b] = m.Kinv[b];
+    for (int d = 0; d < m.D; ++d) k.ls[b][d] = m.ls[(size_t)b * m.D + d];
+    k.lsf2[b] = log(m.sf2[b]);
+    k.kss[b] = m.kss[b];
+    k.noise[b] = m.var_includes_noise ? m.noise[b] : 0.0;
+  }
+  for (int o = 0; o < NO; ++o) { k.ymean[o] = m.y_mean[o]; k.ystd[o] = m.y_std[o]; }
+  if (m.in_shift) {
+    GPK_REQUIRE(h, mm_finite(m.in_shift, m.D) && mm_finite(m.in_scale, m.D), who + "the input scaler must not contain NaN or infinity");
+    for (int d = 0; d < m.D; ++d) {
+      GPK_REQUIRE(h, m.in_scale[d] != 0.0, who + "in_scale must be non-zero");
+      k.in_shift[d] = m.in_shift[d];
+      k.in_scale[d] = m.in_scale[d];
+    }
+    k.scaled = 1;
+  }
+  if (chain) {
+    for (int o = 0; o < NO; ++o) {
+      const int c = m.coord ? m.coord[o] : o;
+      GPK_REQUIRE(h, c >= 0 && c < m.nx, who + "coord must be in [0, nx)");
+      GPK_REQUIRE(h, k.model_of[c] < 0, who + "coord must be distinct");
+      k.model_of[c] = o;
+    }
+  }
+  return GPK_OK;
+}
+
+// M <= 32 Gaussian queries: one upload [z | S], five launches, three downloads, one synchronisation.
+int mm_query(gpk_handle h, const std::string& who, const MomModels& m, const double* Xq, const double* Sq, int M, double* mean,
+             double* cov, double* xcov) {
+  if (!h) return GPK_BAD_ARG;
+  MomK k;
+  GPK_TRY(mm_models(h, who, m, false, k));
+  GPK_REQUIRE(h, M >= 1 && M <= GPK_SMALL_MAX_M, who + "M must be in [1, 32]");
+  GPK_REQUIRE(h, Xq && mean && cov && xcov, who + "null pointer");
+  const int D = k.D, nx = k.nx, NO = k.NO;
+  const size_t n_q = (size_t)M * D, n_s = (size_t)M * nx * nx;
+  GPK_REQUIRE(h, mm_finite(Xq, n_q), who + "the queries must not contain NaN or infinity");
+  GPK_REQUIRE(h, !Sq || mm_finite(Sq, n_s), who + "the covariances must not contain NaN or infinity");
+  const size_t n_om = (size_t)M * NO, n_oc = n_om * NO, n_ox = n_om * D;
+  const MomWork sizes = mm_work(k, M, nullptr);
+  void* ws = nullptr;
+  GPK_TRY(gpk_scratch(h, (n_q + n_s + n_om + n_oc + n_ox + sizes.doubles) * sizeof(double), &ws));
+  double* d_q = (double*)ws;
+  double* d_S = d_q + n_q;
+  double* d_om = d_S + n_s;
+  double* d_oc = d_om + n_om;
+  double* d_ox = d_oc + n_oc;
+  const MomWork w = mm_work(k, M, d_ox + n_ox);
+  std::vector<double> host(n_q + n_s, 0.0);
+  for (int r = 0; r < M; ++r) {
+    for (int d = 0; d < D; ++d) {
+      const double raw = Xq[(size_t)r * D + d];
+      host[(size_t)r * D + d] = k.scaled ? (raw - k.in_shift[d]) / k.in_scale[d] : raw;
+    }
+    if (Sq)      // the lower triangle is the matrix
+      for (int i = 0; i < nx; ++i)
+        for (int j = 0; j <= i; ++j)
+          host[n_q + ((size_t)r * nx + i) * nx + j] = host[n_q + ((size_t)r * nx + j) * nx + i] = Sq[((size_t)r * nx + i) * nx + j];
+  }
+  GPK_CHECK_HIP(h, hipMemcpyAsync(d_q, host.data(), sizeof(double) * (n_q + n_s), hipMemcpyHostToDevice, h->stream));
+  GPK_TRY(mm_launch(h, k, w, M, d_q, d_S));
+  mm_finish(h, k, w, MomAdv{}, M, d_om, d_oc, d_ox);
+  GPK_LAUNCH_CHECK(h);
+  GPK_CHECK_HIP(h, hipMemcpyAsync(mean, d_om, sizeof(double) * n_om, hipMemcpyDeviceToHost, h->stream));
+  GPK_CHECK_HIP(h, hipMemcpyAsync(cov, d_oc, sizeof(double) * n_oc, hipMemcpyDeviceToHost, h->stream));
+  GPK_CHECK_HIP(h, hipMemcpyAsync(xcov, d_ox, sizeof(double) * n_ox, hipMemcpyDeviceToHost, h->stream));
+  GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
+  return GPK_OK;
+}
+
+// The horizon chain: one upload [x | S | q | lin | Q | U], 5 H launches, up to five downloads, one synchronisation.
+int mm_chain(gpk_handle h, const std::string& who, const MomModels& m, const double* x0, int x0_rows, const double* U, int u_rows,
+             const double* lin, const double* Sigma0, int s_rows, const double* Q, int R, int H, double* traj, double* Sigma,
+             double* mean, double* cov, double* xcov) {
+  if (!h) return GPK_BAD_ARG;
+  MomK k;
+  GPK_TRY(mm_models(h, who, m, true, k));
+  const int D = k.D, nx = k.nx, nu = D - nx, NO = k.NO;
+  GPK_REQUIRE(h, R >= 1 && R <= GPK_PROP_MAX_R, who + "R must be in [1, 32]");
+  GPK_REQUIRE(h, H >= 1 && H <= GPK_PROP_MAX_H, who + "H must be in [1, 256]");
+  GPK_REQUIRE(h, x0 && lin && traj && Sigma, who + "null pointer");
+  GPK_REQUIRE(h, nu == 0 || U, who + "null controls");
+  GPK_REQUIRE(h, x0_rows == 1 || x0_rows == R, who + "x0 must have 1 or R rows");
+  GPK_REQUIRE(h, nu == 0 || u_rows == 1 || u_rows == R, who + "U must have 1 or R rows");
+  GPK_REQUIRE(h, !Sigma0 || s_rows == 1 || s_rows == R, who + "Sigma0 must have 1 or R rows");
+  const size_t n_x = (size_t)R * nx, n_s = n_x * nx, n_q = (size_t)R * D, n_lin = (size_t)nx * D, n_Q = (size_t)nx * nx;
+  const size_t n_u = nu ? (size_t)u_rows * H * nu : 0;
+  GPK_REQUIRE(h, mm_finite(x0, (size_t)x0_rows * nx) && mm_finite(lin, n_lin) && (!n_u || mm_finite(U, n_u)) && (!Q || mm_finite(Q, n_Q)),
+              who + "x0, U, lin and Q must not contain NaN or infinity");
+  GPK_REQUIRE(h, !Sigma0 || mm_finite(Sigma0, (size_t)s_rows * n_Q), who + "Sigma0 must not contain NaN or infinity");
+  const size_t n_up = n_x + n_s + n_q + n_lin + n_Q + n_u;
+  const size_t n_om = (size_t)R * NO, n_oc = n_om * NO, n_ox = n_om * D;
+  const size_t n_traj = (size_t)H * n_x, n_sig = (size_t)H * n_s;
+  const MomWork sizes = mm_work(k, R, nullptr);
+  void* ws = nullptr;
+  GPK_TRY(gpk_scratch(h, (n_up + n_traj + n_sig + (size_t)H * (n_om + n_oc + n_ox) + sizes.doubles) * sizeof(double), &ws));
+  double* d_x = (double*)ws;
+  double* d_S = d_x + n_x;
+  double* d_q = d_S + n_s;
+  double* d_lin = d_q + n_q;
+  double* d_Q = d_lin + n_lin;
+  double* d_u = d_Q + n_Q;
+  double* d_traj = d_u + n_u;
+  double* d_sig = d_traj + n_traj;
+  double* d_om = d_sig + n_sig;
+  double* d_oc = d_om + (size_t)H * n_om;
+  double* d_ox = d_oc + (size_t)H * n_oc;
+  const MomWork w = mm_work(k, R, d_ox + (size_t)H * n_ox);
+  std::vector<double> host(n_up, 0.0);
+  double* hS = host.data() + n_x;
+  double* hq = hS + n_s;
+  for (int r = 0; r < R; ++r) {
+    const double* xr = x0 + (x0_rows == 1 ? 0 : (size_t)r * nx);
+    memcpy(host.data() + (size_t)r * nx, xr, sizeof(double) * nx);
+    if (Sigma0) {      // the lower triangle is the matrix: mirrored here as every later stage is
+      const double* s0 = Sigma0 + (s_rows == 1 ? 0 : (size_t)r * n_Q);
+      for (int i = 0; i < nx; ++i)
+        for (int j = 0; j <= i; ++j) hS[(size_t)r * n_Q + i * nx + j] = hS[(size_t)r * n_Q + j * nx + i] = s0[i * nx + j];
+    }
+    for (int d = 0; d < D; ++d) {
+      const double raw = d < nx ? xr[d] : U[(u_rows == 1 ? 0 : (size_t)r * H * nu) + (d - nx)];
+      hq[(size_t)r * D + d] = k.scaled ? (raw - k.in_shift[d]) / k.in_scale[d] : raw;
+    }
+  }
+  memcpy(hq + n_q, lin, sizeof(double) * n_lin);
+  if (Q)
+    for (int i = 0; i < nx; ++i)
+      for (int j = 0; j <= i; ++j) hq[n_q + n_lin + i * nx + j] = hq[n_q + n_lin + j * nx + i] = Q[i * nx + j];
+  if (n_u) memcpy(hq + n_q + n_lin + n_Q, U, sizeof(double) * n_u);
+  memcpy(traj, host.data(), sizeof(double) * n_x);
+  memcpy(Sigma, hS, sizeof(double) * n_s);
+  GPK_CHECK_HIP(h, hipMemcpyAsync(d_x, host.data(), sizeof(double) * n_up, hipMemcpyHostToDevice, h->stream));
+  MomAdv v{};
+  v.lin = d_lin; v.Qn = Q ? d_Q : nullptr; v.x = d_x; v.S = d_S;
+  v.u_row_stride = (nu && u_rows == R) ? (long long)H * nu : 0;
+  for (int s = 0; s < H; ++s) {
+    const bool last = s + 1 == H;
+    GPK_TRY(mm_launch(h, k, w, R, d_q, d_S));
+    v.u = d_u + (size_t)s * nu;
+    v.u_next = d_u + (size_t)(last ? s : s + 1) * nu;
+    v.qnext = last ? nullptr : d_q;
+    v.traj_next = d_traj + (size_t)s * n_x;
+    v.sig_next = d_sig + (size_t)s * n_s;
+    gpk_time_begin(h, GPK_TIMED_PROPAGATE);
+    mm_finish(h, k, w, v, R, mean ? d_om + (size_t)s * n_om : nullptr, cov ? d_oc + (size_t)s * n_oc : nullptr,
+              xcov ? d_ox + (size_t)s * n_ox : nullptr);
+    gpk_time_end(h);
+    GPK_LAUNCH_CHECK(h);
+  }
+  GPK_CHECK_HIP(h, hipMemcpyAsync(traj + n_x, d_traj, sizeof(double) * n_traj, hipMemcpyDeviceToHost, h->stream));
+  GPK_CHECK_HIP(h, hipMemcpyAsync(Sigma + n_s, d_sig, sizeof(double) * n_sig, hipMemcpyDeviceToHost, h->stream));
+  if (mean) GPK_CHECK_HIP(h, hipMemcpyAsync(mean, d_om, sizeof(double) * H * n_om, hipMemcpyDeviceToHost, h->stream));
+  if (cov) GPK_CHECK_HIP(h, hipMemcpyAsync(cov, d_oc, sizeof(double) * H * n_oc, hipMemcpyDeviceToHost, h->stream));
+  if (xcov) GPK_CHECK_HIP(h, hipMemcpyAsync(xcov, d_ox, sizeof(double) * H * n_ox, hipMemcpyDeviceToHost, h->stream));
+  GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
+  return GPK_OK;
+}
+
+}  // namespace
+
+extern "C" int gpk_moments_host(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls, double sf2,
+                                const double* y_mean, const double* y_std, const double* Kinv, int64_t Np, int64_t ldk, double kss,
+                                double floor_, int var_includes_noise, double noise, int nx, const double* Xq, const double* Sq, int M,
+                                double* mean, double* cov, double* xcov) {
+  if (!h) return GPK_BAD_ARG;
+  const MomModels m{1, P, &X, &alpha, N, D, ls, &sf2, y_mean, y_std, &Kinv, Np, ldk, &kss, floor_, var_includes_noise, &noise, nx,
+                    nullptr, nullptr, nullptr};
+  GPK_REQUIRE(h, X && alpha, "moments_host: null pointer");
+  GPK_REQUIRE(h, Kinv, "moments_host: null K^-1 (gpk_wtw of the model's inverse factor)");
+  return mm_query(h, "moments_host: ", m, Xq, Sq, M, mean, cov, xcov);
+}
+
+extern "C" int gpk_moments_host_multi(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D,
+                                      const double* ls, const double* sf2, const double* y_mean, const double* y_std,
+                                      const double* const* Kinv, int64_t Np, int64_t ldk, const double* kss, double floor_,
+                                      int var_includes_noise, const double* noise, int nx, const double* in_shift,
+                                      const double* in_scale, const double* Xq, const double* Sq, int M, double* mean, double* cov,
+                                      double* xcov) {
+  if (!h) return GPK_BAD_ARG;
+  const MomModels m{B, 1, X, alpha, N, D, ls, sf2, y_mean, y_std, Kinv, Np, ldk, kss, floor_, var_includes_noise, noise, nx,
+                    nullptr, in_shift, in_scale};
+  return mm_query(h, "moments_host_multi: ", m, Xq, Sq, M, mean, cov, xcov);
+}
+
+extern "C" int gpk_propagate_mm_host(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
+                                     double sf2, const double* y_mean, const double* y_std, const double* Kinv, int64_t Np, int64_t ldk,
+                                     double kss, double floor_, int var_includes_noise, double noise, const double* x0, int x0_rows,
+                                     const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows, const double* Q,
+                                     int R, int H, double* traj, double* Sigma, double* mean, double* cov, double* xcov) {
+  if (!h) return GPK_BAD_ARG;
+  const MomModels m{1, P, &X, &alpha, N, D, ls, &sf2, y_mean, y_std, &Kinv, Np, ldk, &kss, floor_, var_includes_noise, &noise, P,
+                    nullptr, nullptr, nullptr};
+  GPK_REQUIRE(h, X && alpha, "propagate_mm_host: null pointer");
+  GPK_REQUIRE(h, Kinv, "propagate_mm_host: null K^-1 (gpk_wtw of the model's inverse factor)");
+  GPK_REQUIRE(h, P >= 1 && P <= D, "propagate_mm_host: the state dimension P must be in [1, 16] and must not exceed D");
+  return mm_chain(h, "propagate_mm_host: ", m, x0, x0_rows, U, u_rows, lin, Sigma0, s_rows, Q, R, H, traj, Sigma, mean, cov, xcov);
+}
+
+extern "C" int gpk_propagate_mm_host_multi(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D,
+                                           const double* ls, const double* sf2, const double* y_mean, const double* y_std,
+                                           const double* const* Kinv, int64_t Np, int64_t ldk, const double* kss, double floor_,
+                                           int var_includes_noise, const double* noise, int nx, const int* coord,
+                                           const double* in_shift, const double* in_scale, const double* x0, int x0_rows,
+                                           const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows,
+                                           const double* Q, int R, int H, double* traj, double* Sigma, double* mean, double* cov,
+                                           double* xcov) {
+  if (!h) return GPK_BAD_ARG;
+  GPK_REQUIRE(h, coord, "propagate_mm_host_multi: null pointer");
+  const MomModels m{B, 1, X, alpha, N, D, ls, sf2, y_mean, y_std, Kinv, Np, ldk, kss, floor_, var_includes_noise, noise, nx, coord,
+                    in_shift, in_scale};
+  return mm_chain(h, "propagate_mm_host_multi: ", m, x0, x0_rows, U, u_rows, lin, Sigma0, s_rows, Q, R, H, traj, Sigma, mean, cov, xcov);
+}

@@ -227,7 +227,7 @@ class DeviceGP:
         self.ls = None
         self.sf2 = None
         self._f32 = None    # dict of fp32 copies: X, alpha [, L, winv]
-        self._Winv = {}     # explicit inverse factor L^-1: {'f64': tensor} and/or {'f32': tensor}
+        self._Winv = {}     # explicit inverse factor L^-1: {'f64': tensor} and/or {'f32': tensor}; 'kinv': K^-1 = W^T W (inverse_gram)
         self._host_args = None   # predict_host: cached argument addresses
         self._amp = self._alpha_sq = None         # fp32 mean gate: cached amplification estimate
         self._Kinv = None
@@ -968,6 +968,57 @@ class DeviceGP:
                 raise ValueError(str(e)) from None
             raise
         return traj, Sigma, dU, dx0, dS0
+
+    # ---- exact moment matching (K11, method="moment") ---------------------------------------------------------------------------
+    def moments_ok(self):
+        """The moment-matching entries (gpk_moments_host, gpk_propagate_mm_host) apply: the sizes of `propagate_ok`, and a
+        factor from which K^-1 can be formed (not a serving replica)."""
+        return self.propagate_ok() and not self.replica
+
+    def inverse_gram(self):
+        """K^-1 (Np x Np, lower tiles; gpk_wtw on the inverse factor), formed on first use and kept beside the inverse factor:
+        it goes wherever that one goes (a new factorisation, new hyper-parameters, an imported factor)."""
+        torch = _torch()
+        assert self.factored
+        self._refuse_replica()
+        Kinv = self._Winv.get("kinv")
+        if Kinv is None:
+            W = self.inverse_factor(False)
+            Kinv = self.be.empty((self.Np, self.Np), torch.float64)
+            self.be.call("gpk_wtw", _p(W), self.Np, self.Np, _p(Kinv), self.Np)
+            self._Winv["kinv"] = Kinv
+        return Kinv
+
+    def _moments_call(self, entry, y_mean, y_std, *tail):
+        Kinv = self.inverse_gram().data_ptr()
+        c = self._host_call_args(y_mean, y_std)
+        try:
+            self.be.call(entry, c[7], c[8], self.N, self.D, self.P, c[9], self.sf2, c[10], c[11], Kinv, self.Np, self.Np, *tail)
+        except GPKError as e:      # a limit of the entry: the caller's arguments, with the library's message
+            if e.code == _lib.GPK_BAD_ARG:
+                raise ValueError(str(e)) from None
+            raise
+
+    def moments_host(self, y_mean, y_std, kss, floor, Xq, Sq):
+        """One C call (gpk_moments_host) on M <= 32 Gaussian queries, arguments as `propagate.check_gaussian_queries` returns them:
+        (mean (M, P), cov (M, P, P), xcov (M, P, D)) in target units - five launches, one synchronisation."""
+        M, nx = Xq.shape[0], Sq.shape[1]
+        mean, cov, xcov = np.empty((M, self.P)), np.empty((M, self.P, self.P)), np.empty((M, self.P, self.D))
+        self._moments_call("gpk_moments_host", y_mean, y_std, float(kss), float(floor), 0, 0.0, nx, _hp(Xq), _hp(Sq), M, _hp(mean),
+                           _hp(cov), _hp(xcov))
+        return mean, cov, xcov
+
+    def propagate_mm_host(self, y_mean, y_std, kss, floor, x0, U, lin, S0, Q, R, H, stages):
+        """One C call per horizon with exact moments (gpk_propagate_mm_host; arguments as `propagate.check_horizon` returns them):
+        traj (H + 1, R, P), Sigma (H + 1, R, P, P) and, with `stages`, mean (H, R, P), cov (H, R, P, P), xcov (H, R, P, D) - five
+        launches per stage, one synchronisation."""
+        P, D = self.P, self.D
+        traj, Sigma = np.empty((H + 1, R, P)), np.empty((H + 1, R, P, P))
+        mean, cov, xcov = (np.empty((H, R, P)), np.empty((H, R, P, P)), np.empty((H, R, P, D))) if stages else (None, None, None)
+        self._moments_call("gpk_propagate_mm_host", y_mean, y_std, float(kss), float(floor), 0, 0.0, _hp(x0), x0.shape[0],
+                           _hp(U) if D > P else None, U.shape[0], _hp(lin), _hp(S0), 1 if S0 is None else S0.shape[0], _hp(Q), R, H,
+                           _hp(traj), _hp(Sigma), _hp(mean), _hp(cov), _hp(xcov))
+        return traj, Sigma, mean, cov, xcov
 
     # ---- gated serving: the one place every fp32 surface (estimator, sharded predictor, package GP, per-axis models) goes
     # through -------------------------------------------------------------------------------------------------------------

@@ -448,8 +448,28 @@ class GaussianProcessRegressor:
             mean, dmean, hess = mean[:, 0], dmean[:, 0], hess[:, 0]
         return mean, dmean, hess
 
+    def predict_moments(self, X, Sigma, var_includes_noise=False):
+        """The posterior at GAUSSIAN queries q ~ N(X[m], Sigma[m]) in closed form (exact moment matching; [C.]RBF[+White] kernels):
+        X (M, D), M <= 32; Sigma (M, nx, nx) or (nx, nx), symmetric, the covariance of the LEADING nx <= D coordinates of the
+        query (the rest are certain), or None (zero).  Returns (mean (M, P) = E[y], cov (M, P, P) = Cov[y] - the variance of the
+        mean under the query plus the expected posterior variance on the diagonal, with the WhiteKernel level when
+        var_includes_noise - and xcov (M, P, D) = Cov[q_d, y_p], zero beyond nx).  One C call (`gpk_moments_host`: five launches,
+        one synchronisation) over K^-1, which the device model forms once per fit.  Up to 16 384 training rows (ValueError
+        beyond, or with the backend option small_path=0); a fitted model only (RuntimeError)."""
+        from . import propagate as _pg
+        if not hasattr(self, "X_train_"):
+            raise RuntimeError("This GaussianProcessRegressor instance is not fitted yet.")
+        X, S, M, nx = _pg.check_gaussian_queries(X, Sigma, self.n_features_in_)
+        self._ensure_device()
+        dev = self._dev
+        if not dev.moments_ok():
+            raise ValueError("predict_moments needs the small-batch path: at most 16384 training rows, D <= 16, small_path != 0")
+        comp = self.kernel_.components()
+        kss = comp.sf2 + ((comp.noise or 0.0) if var_includes_noise else 0.0)
+        return dev.moments_host(self._y_train_mean, self._y_train_std, kss, 0.0, X, S)
+
     def propagate(self, x0, U, lin, Sigma0=None, process_noise=None, var_includes_noise=False, return_stages=False,
-                  route="auto", order=1):
+                  route="auto", order=1, method="linear"):
         """The posterior's own closed-loop horizon: the mean trajectory under the learned dynamics and the state covariance that
         the model's uncertainty induces along it, to first order (`propagate`'s module docstring has the recursion).  The state
         is the model's P outputs; a query is q = [x, u] (D = P + nu).  x0 (P,) or (R, P), U (H, nu) or (R, H, nu), lin (P, D) the
@@ -464,9 +484,15 @@ class GaussianProcessRegressor:
         block of the mean's Hessian, added last to each stage's mean; A_h and Sigma are formed as at first order.  Still one C
         call (`gpk_propagate2_host`: four launches per stage, no Hessian is formed); the host loop contracts `predict_hessian`.
         The stages gain "corr" (H, R, P).  Any other order: ValueError.
+        method="moment": every stage's mean, covariance and input-output covariance are the EXACT moments of the posterior at
+        the Gaussian query N([x_h, u_h], Sigma_h) (`predict_moments`; the module docstring has the recursion) instead of their
+        linearisation: one C call (`gpk_propagate_mm_host`, five launches per stage), route="host" the same recursion as a host
+        loop over `predict_moments`; the stages are {"mean" (H, R, P), "cov" (H, R, P, P), "xcov" (H, R, P, D)}.  order=2 with
+        it is a ValueError.  The default method="linear" is the first-order chain above, untouched.
         A fitted model only (RuntimeError); ValueError for a wrong shape, R > 32, H outside 1 .. 256, non-finite input."""
         from . import propagate as _pg
         order = _pg.check_order(order)
+        _pg.check_method(method, order)
         if not hasattr(self, "X_train_"):
             raise RuntimeError("This GaussianProcessRegressor instance is not fitted yet.")
         P, D = self._yn.shape[1], self.n_features_in_
@@ -477,6 +503,20 @@ class GaussianProcessRegressor:
         noise = comp.noise or 0.0
         if route not in ("auto", "host"):
             raise ValueError("route must be 'auto' or 'host'")
+        if method == "moment":
+            _pg.check_method(method, order, Sigma0=S0, process_noise=Q)
+            if not dev.moments_ok():
+                raise ValueError("method='moment' needs the small-batch path: at most 16384 training rows, small_path != 0")
+            if route == "auto":
+                traj, Sigma, mean, cov, xcov = dev.propagate_mm_host(self._y_train_mean, self._y_train_std,
+                                                                     comp.sf2 + (noise if var_includes_noise else 0.0), 0.0, x0, U,
+                                                                     lin, S0, Q, R, H, return_stages)
+                stages = {"mean": mean, "cov": cov, "xcov": xcov}
+            else:
+                traj, Sigma, stages = _pg.host_loop_moments(
+                    lambda q, S: self.predict_moments(q, S, var_includes_noise=var_includes_noise), list(range(P)), x0, U, lin,
+                    S0, Q, R, H)
+            return (traj, Sigma, stages) if return_stages else (traj, Sigma)
         if route == "auto" and dev.propagate_ok():
             # (the noise enters through the prior variance the clip starts from, as in predict_jacobian: the same bits)
             traj, Sigma, mean, var, jac, *corr = dev.propagate_host(self._y_train_mean, self._y_train_std,
@@ -500,7 +540,7 @@ class GaussianProcessRegressor:
         return (traj, Sigma, stages) if return_stages else (traj, Sigma)
 
     def propagate_gradient(self, x0, U, lin, grad_traj, grad_Sigma=None, Sigma0=None, process_noise=None,
-                           var_includes_noise=False, route="auto", order=1):
+                           var_includes_noise=False, route="auto", order=1, method="linear"):
         """`propagate` with the gradient of a differentiable horizon cost l(traj, Sigma) with respect to the controls, the start
         state and the start covariance (`propagate`'s module docstring has the backward sweep).  grad_traj (H + 1, R, P) =
         dl/dx_h and grad_Sigma (H + 1, R, P, P) = dl/dSigma_h (default zero; entries taken as independent, (g + g^T) / 2 is
@@ -513,6 +553,7 @@ class GaussianProcessRegressor:
         mean term needs third derivatives of the mean (ValueError)."""
         from . import propagate as _pg
         _pg.check_grad_order(order)
+        _pg.refuse_moment(method, "propagate_gradient")
         if not hasattr(self, "X_train_"):
             raise RuntimeError("This GaussianProcessRegressor instance is not fitted yet.")
         P, D = self._yn.shape[1], self.n_features_in_

@@ -34,6 +34,17 @@ derivatives of the mean).  The caller supplies the seeds gx[h] = dl/dx_h and gS[
 dx0 = lam_0, dSigma0 = Lam_0.  The one-call entries (`gpk_propagate_grad_host[_multi]`, `gpk_sparse_propagate_grad[_multi]`: six
 launches per stage, one synchronisation) form H_b w_b without the Hessian; `host_adjoint` is the same sweep on the host over the
 class's own `predict_jacobian(..., return_var=True)` and `predict_hessian`.
+
+`method="moment"` on `propagate` of the exact classes replaces the linearisation of every stage by the exact moments of the
+posterior at the Gaussian query N([x_h, u_h], Sigma_h) (`predict_moments`: mean, covariance V of the outputs and input-output
+covariance; closed forms for RBF kernels):
+
+    x_{h+1} = x_h + lin q + E mean,      Sigma_{h+1} = A0 Sigma_h A0^T + A0 Cx E^T + E Cx^T A0^T + E V E^T + Q
+
+with A0 = I + lin[:, :nx], E the selector of `coord` and Cx the state rows of the input-output covariance (to first order Cx =
+Sigma_h J_x^T, which gives the recursion at the top).  One C call per horizon (`gpk_propagate_mm_host[_multi]`: five launches per
+stage, one synchronisation); `host_loop_moments` is the same recursion over a class's `predict_moments`.  The sparse classes and
+`propagate_gradient` refuse it (`refuse_moment`).
 """
 from __future__ import annotations
 
@@ -148,6 +159,98 @@ def host_loop(stage, coord, x0, U, lin, S0, Q, R, H, hess_stage=None):
     if hess_stage is not None:
         stages["corr"] = corrs
     return traj, Sigma, stages
+
+
+# ---- exact moment matching (method="moment") ---------------------------------------------------------------------------------------
+METHODS = ("linear", "moment")
+
+
+def check_method(method, order=1, what="propagate", Sigma0=None, process_noise=None):
+    """`method` as "linear" or "moment"; ValueError for anything else, and for "moment" with order=2 (the exact moments hold every
+    order of the Taylor series: there is nothing to add to them) or with a Sigma0 or process noise (as `check_horizon` returns
+    them) that is not positive semi-definite (`check_psd`)."""
+    if method not in METHODS:
+        raise ValueError(f"{what}: method must be 'linear' or 'moment', got {method!r}")
+    if method == "moment" and order != 1:
+        raise ValueError(f"{what}: method='moment' takes order=1 (the exact moments already hold the second-order term)")
+    if method == "moment":
+        check_psd(Sigma0, f"{what}: Sigma0")
+        check_psd(process_noise, f"{what}: process_noise")
+    return method
+
+
+def refuse_moment(method, what):
+    """The classes and calls without moment matching (the sparse models, the gradient chain): ValueError naming them."""
+    if method not in METHODS:
+        raise ValueError(f"method must be 'linear' or 'moment', got {method!r}")
+    if method == "moment":
+        raise ValueError(f"method='moment' is not supported by {what}: exact moment matching needs the inverse Gram matrix of an "
+                         "exact RBF model and has no adjoint chain")
+
+
+def check_psd(S, what):
+    """ValueError unless every matrix of S (.., n, n; symmetric) is positive semi-definite up to rounding (smallest eigenvalue >=
+    -1e-12 of the largest entry).  The closed forms factor S + Lambda and R^-1 S: an indefinite S gives them a pivot that is not
+    positive, and NaN or infinity without a message."""
+    if S is not None and S.size and float(np.min(np.linalg.eigvalsh(S))) < -1e-12 * max(float(np.max(np.abs(S))), 1e-300):
+        raise ValueError(f"{what} must be positive semi-definite")
+
+
+def check_gaussian_queries(X, Sigma, D):
+    """The arguments of `predict_moments` as contiguous float64 arrays: X (M, D) and Sigma (M, nx, nx) with nx <= D, the covariance
+    of the leading nx coordinates of every query ((nx, nx): shared by all rows; None: zero, nx = D).  ValueError on a wrong shape,
+    M outside 1 .. 32, NaN or infinity, a Sigma that is asymmetric or not positive semi-definite."""
+    X = np.array(X, dtype=np.float64, ndmin=2)
+    if X.ndim != 2 or X.shape[1] != D:
+        raise ValueError(f"predict_moments: X must be (M, {D})")
+    M = X.shape[0]
+    if not (1 <= M <= MAX_R):
+        raise ValueError(f"predict_moments: M must be in [1, {MAX_R}], got {M}")
+    S = np.zeros((M, D, D)) if Sigma is None else np.asarray(Sigma, dtype=np.float64)
+    if S.ndim == 2:
+        S = np.broadcast_to(S, (M,) + S.shape)
+    if S.ndim != 3 or S.shape[0] != M or S.shape[1] != S.shape[2] or not (1 <= S.shape[1] <= D):
+        raise ValueError(f"predict_moments: Sigma must be (nx, nx) or ({M}, nx, nx) with nx <= {D}")
+    if not (np.isfinite(X).all() and np.isfinite(S).all()):
+        raise ValueError("predict_moments: X or Sigma contains NaN or infinity")
+    if not np.array_equal(S, S.transpose(0, 2, 1)):
+        raise ValueError("predict_moments: Sigma must be symmetric")
+    check_psd(S, "predict_moments: Sigma")
+    return np.ascontiguousarray(X), np.ascontiguousarray(S), M, S.shape[1]
+
+
+def host_loop_moments(stage, coord, x0, U, lin, S0, Q, R, H):
+    """The moment-matching recursion on the host.  stage(q (R, D) raw, Sigma (R, nx, nx)) -> (mean (R, NO), cov (R, NO, NO), xcov
+    (R, NO, D) = Cov[q_d, y_o]) as `predict_moments` returns them; output o drives state coordinate coord[o]:
+
+        x_{h+1}     = x_h + lin q + E mean
+        Sigma_{h+1} = A0 Sigma_h A0^T + A0 Cx E^T + E Cx^T A0^T + E cov E^T + Q,       A0 = I + lin[:, :nx], Cx = xcov[:, :nx]^T
+
+    Returns traj (H + 1, R, nx), Sigma (H + 1, R, nx, nx) and the stage quantities {"mean" (H, R, NO), "cov" (H, R, NO, NO), "xcov"
+    (H, R, NO, D)}."""
+    nx, D = lin.shape
+    NO = len(coord)
+    traj, Sigma = np.zeros((H + 1, R, nx)), np.zeros((H + 1, R, nx, nx))
+    means, covs, xcovs = np.zeros((H, R, NO)), np.zeros((H, R, NO, NO)), np.zeros((H, R, NO, D))
+    traj[0] = np.broadcast_to(x0, (R, nx))
+    if S0 is not None:
+        Sigma[0] = np.broadcast_to(S0, (R, nx, nx))
+    A0 = np.eye(nx) + lin[:, :nx]
+    E = np.zeros((nx, NO))
+    for o, c in enumerate(coord):
+        E[c, o] = 1.0
+    for h in range(H):
+        q = np.concatenate([traj[h], np.broadcast_to(U[:, h], (R, D - nx))], axis=1)
+        mean, cov, xcov = stage(np.ascontiguousarray(q), np.ascontiguousarray(Sigma[h]))
+        mean, cov, xcov = np.reshape(mean, (R, NO)), np.reshape(cov, (R, NO, NO)), np.reshape(xcov, (R, NO, D))
+        means[h], covs[h], xcovs[h] = mean, cov, xcov
+        F = A0 @ xcov[:, :, :nx].transpose(0, 2, 1) @ E.T       # A0 Cx E^T
+        S = A0 @ Sigma[h] @ A0.T + F + F.transpose(0, 2, 1) + E @ cov @ E.T
+        if Q is not None:
+            S = S + Q
+        traj[h + 1] = traj[h] + q @ lin.T + mean @ E.T
+        Sigma[h + 1] = 0.5 * (S + S.transpose(0, 2, 1))
+    return traj, Sigma, {"mean": means, "cov": covs, "xcov": xcovs}
 
 
 def check_grad_order(order):
@@ -274,6 +377,11 @@ def check_batch(B, D, x0, U, lin, coord, in_scaler, out_scaler, Sigma0, process_
     check_route(route, routes)
     head = check_horizon(x0, U, lin, nx, D, Sigma0, process_noise)
     coord = check_coord(coord, B, nx)
+    return head + (coord,) + check_scalers(B, D, in_scaler, out_scaler)
+
+
+def check_scalers(B, D, in_scaler, out_scaler):
+    """A batch's scalers: in_shift, in_scale ((D,) or None), o_mean, o_scale ((B,): the identity without an out_scaler)."""
     in_shift = in_scale = None
     if in_scaler is not None:
         pair = (in_scaler.mean_, in_scaler.scale_) if hasattr(in_scaler, "mean_") else in_scaler
@@ -289,7 +397,7 @@ def check_batch(B, D, x0, U, lin, coord, in_scaler, out_scaler, Sigma0, process_
         o_scale = np.broadcast_to(np.asarray(out_scaler[1], dtype=np.float64), (B,))
         if not (np.isfinite(o_mean).all() and np.isfinite(o_scale).all()):
             raise ValueError("the output scaler contains NaN or infinity.")
-    return head + (coord, in_shift, in_scale, o_mean, o_scale)
+    return in_shift, in_scale, o_mean, o_scale
 
 
 def batch_stage(predict_jacobian, level, in_shift, in_scale, o_mean, o_scale, var_includes_noise, with_dvar=False):

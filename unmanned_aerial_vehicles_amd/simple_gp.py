@@ -299,7 +299,7 @@ class SimpleQuadrotorGP:
             print(f"GP rollout sampling failed: {e}")
             return fallback
 
-    def propagate_horizon(self, state, U_guess, dt, Sigma0=None, process_noise=None, order=1):
+    def propagate_horizon(self, state, U_guess, dt, Sigma0=None, process_noise=None, order=1, method="linear"):
         """The closed loop of the posterior MEAN with the state covariance the model's uncertainty induces along it, to first
         order, in one call for the horizon (`GaussianProcessRegressor.propagate`):
 
@@ -310,9 +310,14 @@ class SimpleQuadrotorGP:
         (6, 6) (default zero) and process_noise (6, 6), symmetric.  The variances are the latent function's.  Untrained, or on
         any failure (printed): the nominal trajectory and the nominal propagation Sigma_{k+1} = (I + lin_x) Sigma_k (I +
         lin_x)^T + Q - it never raises into the control loop.  order=2: x_{k+1} also takes tr(H_b Sigma_k) / 2 per output b, H_b
-        the state block of the mean's Hessian (`GaussianProcessRegressor.propagate`); any other order: ValueError."""
+        the state block of the mean's Hessian (`GaussianProcessRegressor.propagate`); any other order: ValueError.
+        method="moment": the exact moments of the posterior at the Gaussian query of every stage instead of their linearisation
+        (`GaussianProcessRegressor.propagate(method="moment")`); ValueError with order=2 or a sparse model."""
         from . import propagate as _pg
         order = _pg.check_order(order)
+        _pg.check_method(method, order)
+        if method == "moment" and self.is_trained and not hasattr(self.gp_model, "predict_moments"):
+            _pg.refuse_moment(method, type(self.gp_model).__name__)
         state, U, lin, nominal, single = _pg.horizon_inputs(self._nominal_dynamics, state, U_guess, dt)
         R, N = U.shape[0], U.shape[1]
         if not self.is_trained:
@@ -321,7 +326,7 @@ class SimpleQuadrotorGP:
         try:
             # (a SparseGP model: its one-call chain where it applies, the host loop otherwise)
             traj, Sigma = self.gp_model.propagate(state, U, lin, Sigma0=Sigma0, process_noise=process_noise,
-                                                  route=_pg.wrapper_route(self.gp_model), order=order)
+                                                  route=_pg.wrapper_route(self.gp_model), order=order, method=method)
             if not (np.isfinite(traj).all() and np.isfinite(Sigma).all()):
                 raise FloatingPointError("non-finite trajectory or covariance")
             self.prediction_count += R * N

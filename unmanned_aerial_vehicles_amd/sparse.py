@@ -490,7 +490,7 @@ class SparseGP:
         return np.hstack(y_samples)
 
     def propagate(self, x0, U, lin, Sigma0=None, process_noise=None, var_includes_noise=False, return_stages=False,
-                  route="auto", order=1):
+                  route="auto", order=1, method="linear"):
         """`GaussianProcessRegressor.propagate` on the sparse posterior: the mean rollout with the linearised state covariance,
         same arguments and results.  route="auto" and "host": the recursion as a host loop over
         `predict_jacobian(..., return_var=True)`, one call and one synchronisation per stage.  route="chain": ONE C call per
@@ -500,9 +500,11 @@ class SparseGP:
         while neither clip is active).  ValueError where `propagate_ok()` does not hold, with the reason, or where the entry
         refuses its arguments, with the library's message.  order=2: the second-order mean, on every route (chain:
         `gpk_sparse_propagate2`, four launches per stage, the mean's model (Z, alpha_u) as in `predict_hessian`; the host loop
-        contracts `predict_hessian`); the stages gain "corr" (H, R, P)."""
+        contracts `predict_hessian`); the stages gain "corr" (H, R, P).  method: "linear" only - exact moment matching
+        (method="moment") needs the inverse Gram matrix of an exact model: ValueError."""
         from . import propagate as _pg
         order = _pg.check_order(order)
+        _pg.refuse_moment(method, "SparseGP")
         _pg.check_route(route, ("auto", "host", "chain"))
         P, D = self.n_outputs_, self.n_features_in_
         x0, U, lin, S0, Q, R, H = _pg.check_horizon(x0, U, lin, P, D, Sigma0, process_noise)
@@ -543,7 +545,7 @@ class SparseGP:
         return (traj, Sigma, stages) if return_stages else (traj, Sigma)
 
     def propagate_gradient(self, x0, U, lin, grad_traj, grad_Sigma=None, Sigma0=None, process_noise=None,
-                           var_includes_noise=False, route="auto", order=1):
+                           var_includes_noise=False, route="auto", order=1, method="linear"):
         """`GaussianProcessRegressor.propagate_gradient` on the sparse posterior: `propagate` with the gradient of a horizon cost
         with respect to the controls, the start state and the start covariance; same arguments and results.  route="auto" and
         "host": the sweep on the host over `predict_jacobian(..., return_var=True)` and `predict_hessian`.  route="chain": ONE C
@@ -551,6 +553,7 @@ class SparseGP:
         bits of `propagate(route="chain")`); ValueError where `propagate_ok()` does not hold.  order: 1 only (ValueError)."""
         from . import propagate as _pg
         _pg.check_grad_order(order)
+        _pg.refuse_moment(method, "SparseGP.propagate_gradient")
         _pg.check_route(route, ("auto", "host", "chain"))
         P, D = self.n_outputs_, self.n_features_in_
         x0, U, lin, S0, Q, R, H = _pg.check_horizon(x0, U, lin, P, D, Sigma0, process_noise)

@@ -153,7 +153,7 @@ class BatchedSparseGP:
         return mean, dmean, hess
 
     def propagate(self, x0, U, lin, coord=None, in_scaler=None, Sigma0=None, process_noise=None, var_includes_noise=False,
-                  return_stages=False, out_scaler=None, route="auto", order=1):
+                  return_stages=False, out_scaler=None, route="auto", order=1, method="linear"):
         """`BatchedARDGP.propagate` on the sparse posteriors: the batch's mean rollout with the linearised state covariance in
         raw units, same arguments and results.  route="auto" and "host": the recursion as a host loop over
         `predict_jacobian(..., return_var=True)` - one C call for all models and one synchronisation per stage.
@@ -161,9 +161,11 @@ class BatchedSparseGP:
         synchronisation; the scalers go into the call; the latent variance as `SparseGP.propagate` describes it).  ValueError
         where `propagate_ok()` does not hold, with the reason, or where the entry refuses its arguments.  order=2: the
         second-order mean on every route (chain: `gpk_sparse_propagate2_multi`, four launches per stage; the host loop contracts
-        `predict_hessian`); the stages gain "corr" (H, R, B)."""
+        `predict_hessian`); the stages gain "corr" (H, R, B).  method: "linear" only - exact moment matching
+        (method="moment") needs the inverse Gram matrix of an exact model: ValueError."""
         from . import propagate as _pg
         order = _pg.check_order(order)
+        _pg.refuse_moment(method, "BatchedSparseGP")
         B, D = len(self.models), self.n_features_in_
         x0, U, lin, S0, Q, R, H, coord, in_shift, in_scale, o_mean, o_scale = _pg.check_batch(
             B, D, x0, U, lin, coord, in_scaler, out_scaler, Sigma0, process_noise, route, routes=("auto", "host", "chain"))
@@ -201,7 +203,7 @@ class BatchedSparseGP:
         return (traj, Sigma, stages) if return_stages else (traj, Sigma)
 
     def propagate_gradient(self, x0, U, lin, grad_traj, grad_Sigma=None, coord=None, in_scaler=None, Sigma0=None,
-                           process_noise=None, var_includes_noise=False, out_scaler=None, route="auto", order=1):
+                           process_noise=None, var_includes_noise=False, out_scaler=None, route="auto", order=1, method="linear"):
         """`BatchedARDGP.propagate_gradient` on the sparse posteriors: `propagate` with the gradient of a horizon cost, raw
         units, same arguments and results.  route="auto" and "host": the sweep on the host over `predict_jacobian` and
         `predict_hessian` (one C call each for all models per stage).  route="chain": ONE C call per horizon for all models
@@ -209,6 +211,7 @@ class BatchedSparseGP:
         `propagate(route="chain")`); ValueError where `propagate_ok()` does not hold.  order: 1 only (ValueError)."""
         from . import propagate as _pg
         _pg.check_grad_order(order)
+        _pg.refuse_moment(method, "BatchedSparseGP.propagate_gradient")
         B, D = len(self.models), self.n_features_in_
         x0, U, lin, S0, Q, R, H, coord, in_shift, in_scale, o_mean, o_scale = _pg.check_batch(
             B, D, x0, U, lin, coord, in_scaler, out_scaler, Sigma0, process_noise, route, routes=("auto", "host", "chain"))
