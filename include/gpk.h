@@ -1124,9 +1124,12 @@ GPK_API int gpk_paths_rollout_multi_grad_z(gpk_handle h, const double* Zs, int64
  * gpk_propagate_host_multi: B <= 8 single-output models, model arguments as gpk_predict_host_multi_grad; nx, coord (B distinct
  *   state coordinates), in_shift / in_scale (D each, both or neither) as gpk_paths_rollout_multi.  RAW units.
  * GPK_BAD_ARG (with a message, before any launch): R not in [1, 32], H not in [1, 256], nx or D above 16, nx > D, nx < B,
- *   gpk_padded(N) > 16384, Np != gpk_padded(N), ldw < Np, a wrong row count, NaN or infinity in a host input (the model's ls,
- *   sf2, y_mean, y_std, kss, floor and noise included), a length-scale that is not positive, in_scale zero,
- *   coord out of range or repeated, a null pointer, batched mode.                                                          */
+ *   gpk_padded(N) > 16384, Np != gpk_padded(N), ldw < Np, a wrong row count ("x0 / U / Sigma0 must have 1 or R rows"), NaN or
+ *   infinity in a host input ("x0, U, lin and Q must not contain NaN or infinity", "Sigma0 must not contain NaN or infinity";
+ *   the model's ls, sf2, y_mean, y_std, kss, floor and noise included), a length-scale that is not positive, in_scale zero,
+ *   coord out of range or repeated, a null pointer, batched mode.  The checks of R, H, the row counts, the horizon's null
+ *   pointers and its finiteness are the same code, with these messages, for every propagation entry of this header
+ *   (gpk_propagate*, gpk_sparse_propagate*, gpk_propagate_mm_host*).                                                          */
 GPK_API int gpk_propagate_host(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
                                double sf2, const double* y_mean, const double* y_std, const double* W, int64_t Np, int64_t ldw,
                                double kss, double floor_, int var_includes_noise, double noise, const double* x0, int x0_rows,

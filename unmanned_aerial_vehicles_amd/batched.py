@@ -492,13 +492,11 @@ class BatchedARDGP:
                 return (traj, Sigma, stages) if return_stages else (traj, Sigma)
             sv = self._moments_state()
             ym, ys = np.ascontiguousarray(o_mean + o_scale * sv["ym"]), np.ascontiguousarray(o_scale * sv["ys"])
-            traj, Sigma = np.empty((H + 1, R, nx)), np.empty((H + 1, R, nx, nx))
-            mean, cov, xcov = (np.empty((H, R, B)), np.empty((H, R, B, B)), np.empty((H, R, B, D))) if return_stages else (None,) * 3
-            self._moments_call("gpk_propagate_mm_host_multi", sv, ym, ys, sv["kss"] if var_includes_noise else sv["sf2"], nx,
-                               (C.c_int * B)(*coord), _hp(in_shift), _hp(in_scale), _hp(x0), x0.shape[0], _hp(U) if D > nx else None,
-                               U.shape[0], _hp(lin), _hp(S0), 1 if S0 is None else S0.shape[0], _hp(Q), R, H, _hp(traj), _hp(Sigma),
-                               _hp(mean), _hp(cov), _hp(xcov))
-            return (traj, Sigma, {"mean": mean, "cov": cov, "xcov": xcov}) if return_stages else (traj, Sigma)
+            traj, Sigma, more = _pg.horizon_call(
+                lambda *t: self._moments_call("gpk_propagate_mm_host_multi", sv, ym, ys, sv["kss"] if var_includes_noise else sv["sf2"],
+                                              nx, (C.c_int * B)(*coord), _hp(in_shift), _hp(in_scale), *t),
+                x0, U, lin, S0, Q, R, H, ((B,), (B, B), (B, D)) if return_stages else None)
+            return (traj, Sigma, dict(zip(("mean", "cov", "xcov"), more))) if return_stages else (traj, Sigma)
         sv = self._serve_state(True, any_dtype=True) if route == "auto" else None
         if sv is not None and int(sv["dev0"].be.options.get("small_path", 1)) != 0:
             d0 = sv["dev0"]
@@ -507,30 +505,23 @@ class BatchedARDGP:
                 ym, ys = np.ascontiguousarray(o_mean + o_scale * sv["ym"]), np.ascontiguousarray(o_scale * sv["ys"])
             # (the noise enters through the prior variance the clip starts from, as in predict_host_grad: the same bits)
             kss = sv["kss"] if var_includes_noise else sv["sf2"]
-            traj, Sigma = np.empty((H + 1, R, nx)), np.empty((H + 1, R, nx, nx))
-            mean, var, jac = (np.empty((H, R, B)), np.empty((H, R, B)), np.empty((H, R, B, D))) if return_stages else (None,) * 3
-            cd = (C.c_int * B)(*coord)
-            args = (B, sv["X"], sv["alpha"], d0.N, d0.D, _hp(sv["ls"]), _hp(sv["sf2"]), _hp(ym), _hp(ys), sv["W"], d0.Np, d0.Np,
-                    _hp(kss), 0.0, 0, None, nx, cd, _hp(in_shift), _hp(in_scale), _hp(x0), x0.shape[0], _hp(U) if D > nx else None,
-                    U.shape[0], _hp(lin), _hp(S0), 1 if S0 is None else S0.shape[0], _hp(Q), R, H, _hp(traj), _hp(Sigma), _hp(mean),
-                    _hp(var), _hp(jac))
-            stages = {"mean": mean, "var": var, "jac": jac}
-            try:
-                if order == 1:
-                    d0.be.call("gpk_propagate_host_multi", *args)
-                else:
-                    stages["corr"] = np.empty((H, R, B)) if return_stages else None
-                    d0.be.call("gpk_propagate2_host_multi", *args, order, _hp(stages["corr"]))
-            except _lib.GPKError as e:      # a limit of the entry: the caller's arguments, with the library's message
-                if e.code == _lib.GPK_BAD_ARG:
-                    raise ValueError(str(e)) from None
-                raise
-            return (traj, Sigma, stages) if return_stages else (traj, Sigma)
+            traj, Sigma, more = _pg.horizon_call(
+                lambda *t: d0.be.call("gpk_propagate_host_multi" if order == 1 else "gpk_propagate2_host_multi",
+                                      *self._chain_models(sv, ym, ys, kss, nx, coord, in_shift, in_scale), *t),
+                x0, U, lin, S0, Q, R, H, ((B,), (B,), (B, D)) if return_stages else None, None if order == 1 else order)
+            return (traj, Sigma, dict(zip(("mean", "var", "jac", "corr"), more))) if return_stages else (traj, Sigma)
         stage = _pg.batch_stage(self.predict_jacobian, _pg.noise_levels(self.models), in_shift, in_scale, o_mean, o_scale,
                                 var_includes_noise)
         hess_stage = _pg.batch_hess_stage(self.predict_hessian, in_shift, in_scale, o_scale) if order == 2 else None
         traj, Sigma, stages = _pg.host_loop(stage, coord, x0, U, lin, S0, Q, R, H, hess_stage)
         return (traj, Sigma, stages) if return_stages else (traj, Sigma)
+
+    @staticmethod
+    def _chain_models(sv, ym, ys, kss, nx, coord, in_shift, in_scale):
+        """The arguments of the batch's chain entries ahead of the horizon's (`propagate.horizon_call` supplies those)."""
+        d0, B = sv["dev0"], sv["B"]
+        return (B, sv["X"], sv["alpha"], d0.N, d0.D, _hp(sv["ls"]), _hp(sv["sf2"]), _hp(ym), _hp(ys), sv["W"], d0.Np, d0.Np, _hp(kss),
+                0.0, 0, None, nx, (C.c_int * B)(*coord), _hp(in_shift), _hp(in_scale))
 
     def propagate_gradient(self, x0, U, lin, grad_traj, grad_Sigma=None, coord=None, in_scaler=None, Sigma0=None,
                            process_noise=None, var_includes_noise=False, out_scaler=None, route="auto", order=1, method="linear"):
@@ -558,20 +549,11 @@ class BatchedARDGP:
             if out_scaler is not None:
                 ym, ys = np.ascontiguousarray(o_mean + o_scale * sv["ym"]), np.ascontiguousarray(o_scale * sv["ys"])
             kss = sv["kss"] if var_includes_noise else sv["sf2"]
-            traj, Sigma = np.empty((H + 1, R, nx)), np.empty((H + 1, R, nx, nx))
-            dU, dx0, dS0 = np.zeros((R, H, D - nx)), np.empty((R, nx)), np.empty((R, nx, nx))
-            cd = (C.c_int * B)(*coord)
-            try:
-                d0.be.call("gpk_propagate_grad_host_multi", B, sv["X"], sv["alpha"], d0.N, d0.D, _hp(sv["ls"]), _hp(sv["sf2"]),
-                           _hp(ym), _hp(ys), sv["W"], d0.Np, d0.Np, _hp(kss), 0.0, 0, None, nx, cd, _hp(in_shift), _hp(in_scale),
-                           _hp(x0), x0.shape[0], _hp(U) if D > nx else None, U.shape[0], _hp(lin), _hp(S0),
-                           1 if S0 is None else S0.shape[0], _hp(Q), R, H, _hp(traj), _hp(Sigma), None, None, None, _hp(gx),
-                           _hp(gS), _hp(dU) if D > nx else None, _hp(dx0), _hp(dS0))
-            except _lib.GPKError as e:
-                if e.code == _lib.GPK_BAD_ARG:
-                    raise ValueError(str(e)) from None
-                raise
-            return traj, Sigma, dU, dx0, dS0
+            traj, Sigma, more = _pg.horizon_call(
+                lambda *t: d0.be.call("gpk_propagate_grad_host_multi",
+                                      *self._chain_models(sv, ym, ys, kss, nx, coord, in_shift, in_scale), *t),
+                x0, U, lin, S0, Q, R, H, seeds=(gx, gS))
+            return (traj, Sigma, *more)
         stage = _pg.batch_stage(self.predict_jacobian, _pg.noise_levels(self.models), in_shift, in_scale, o_mean, o_scale,
                                 var_includes_noise, with_dvar=True)
         hess_stage = _pg.batch_hess_stage(self.predict_hessian, in_shift, in_scale, o_scale)

@@ -347,7 +347,94 @@ struct Horizon {
   int order = 1;                     // 2: the mean takes c_o = tr(H_o Sigma_h) / 2 per stage, added last (see gpk_propagate.hip)
   double* corr = nullptr;            // (H, R, NO): c of every stage, zeros at order 1; may be null
   const HorizonGrad* grad = nullptr;   // the gradient of a horizon cost (order 1 only): the backward sweep follows the chain
+  double *cov = nullptr, *xcov = nullptr;   // the moment chain's stage outputs (H, R, NO, NO) and (H, R, NO, D); null elsewhere
 };
+// What the host entries of the exact models are called with past the handle and before the horizon (the single-model entries: B = 1
+// and pointers to their scalars).  W, ldw: the inverse factors; in the moment entries (gpk_moments.hip) K^-1 and its leading dimension.
+struct HostModels {
+  int B, P;
+  const double* const* X;
+  const double* const* alpha;
+  int64_t N;
+  int D;
+  const double *ls, *sf2, *y_mean, *y_std;
+  const double* const* W;
+  int64_t Np, ldw;
+  const double* kss;
+  double floor_;
+  int var_includes_noise;
+  const double* noise;
+  int nx;
+  const int* coord;                  // B state coordinates (batch) or null (single model: output p drives coordinate p)
+  const double *in_shift, *in_scale;
+};
+inline bool gpk_finite(const double* p, size_t n) {
+  for (size_t i = 0; i < n; ++i)
+    if (!(p[i] - p[i] == 0.0)) return false;
+  return true;
+}
+// ---- the one skeleton of every horizon chain (gpk_propagate.hip; the moment chain of gpk_moments.hip runs on it too) ----------
+// What a stage's composing launch reads and writes besides the stage's own results, for the workgroup of rollout r: the stage's
+// controls u + r u_row_stride and the next stage's; the state x (R x nx) and S (R x nx x nx), updated in place; qnext, the next
+// stage's scaled queries (R x D), null at the last stage; the horizon's output slots of this stage; the stage's optional outputs
+// out[0..2] - mean, var, jac (the moment chain: mean, cov, xcov) - null where not requested.  x null: no stage to compose.
+struct StageView {
+  const double *lin, *Qn, *u, *u_next;
+  long long u_row_stride;
+  double *x, *S, *qnext, *traj_next, *sig_next;
+  double* out[3];
+};
+// The device block of a horizon, sized and carved by the same calls: with base null, take() only counts.  head(): the one
+// upload's head [x | S | q | lin | Q | U]; outputs(): traj and Sigma from slot 1 on (slot 0 is the caller's own start) and the
+// optional stage outputs, n_out[i] doubles per stage for the caller's host_out[i].  A chain's own buffers are further take()s.
+struct HorizonBlock {
+  int nx, D, nu, R, H;
+  size_t n_x, n_s, n_q, n_lin, n_Q, n_u;
+  long long u_row_stride;            // between the rollouts' control sequences; 0: one sequence serves them all
+  double* base = nullptr;
+  size_t at = 0;
+  double *x, *S, *q, *lin, *Q, *u, *traj, *sig, *out[3];
+  double* qs = nullptr;              // the scaled queries of stages 1 .. H - 1 where a chain keeps them (stage 0: q); null: q is reused
+  size_t n_out[3];
+  double* host_out[3];
+  HorizonBlock(int nx, int D, const Horizon& z);
+  double* take(size_t n) {
+    double* p = base ? base + at : nullptr;
+    at += n;
+    return p;
+  }
+  void head();
+  void outputs(size_t n0, double* h0, size_t n1, double* h1, size_t n2, double* h2);
+  double* queries(int s) const { return s == 0 || !qs ? q : qs + (size_t)(s - 1) * n_q; }
+  size_t n_head() const { return n_x + n_s + n_q + n_lin + n_Q + n_u; }
+};
+// lay(): every take of a chain, run twice - counting, then on the handle's scratch block of that size
+template <class F>
+int gpk_horizon_carve(gpk_handle h, HorizonBlock& b, F&& lay) {
+  lay();
+  void* ws = nullptr;
+  GPK_TRY(gpk_scratch(h, b.at * sizeof(double), &ws));
+  b.base = (double*)ws;
+  b.at = 0;
+  lay();
+  return GPK_OK;
+}
+// Every check past the model's own: R in [1, 32], H in [1, 256], row counts of 1 or R, the null pointers (U null only when nu = 0),
+// NaN or infinity in x0, U, lin, Q or Sigma0.  GPK_BAD_ARG with a message, before anything is launched or written.
+int gpk_horizon_check(gpk_handle h, const std::string& who, int nx, int D, const Horizon& z);
+// The head of the one upload into hx (zero-initialised, n_head() doubles): the start rows (one row serves every rollout), Sigma0
+// mirrored from its lower triangle, the first stage's scaled queries, lin, Q and U as they come from the host.
+void gpk_horizon_pack(const HorizonBlock& b, const Horizon& z, bool scaled, const double* in_shift, const double* in_scale, double* hx);
+// Slot 0 of traj and Sigma from the packed head, and the one upload (host: the head and whatever the chain packed behind it).
+int gpk_horizon_upload(gpk_handle h, const HorizonBlock& b, const Horizon& z, const std::vector<double>& host);
+StageView gpk_horizon_stage(const HorizonBlock& b, const Horizon& z, int s);
+// The downloads of traj, Sigma and the requested stage outputs, then the chain's own, then the one synchronisation.
+struct HorizonCopy {
+  double* dst;
+  const double* src;
+  size_t n;
+};
+int gpk_horizon_finish(gpk_handle h, const HorizonBlock& b, const Horizon& z, std::initializer_list<HorizonCopy> more);
 // The chain of one horizon on the models m (F = 1 or 2): every check of the limits (GPK_BAD_ARG before anything is launched), one
 // upload, 3 H launches (order 2: 4 H, the trace launch before the advance), up to five downloads (six with corr), one
 // synchronisation.  With z.grad: 6 H launches - forward the three of GPK_SMALL_GRAD and the advance, backward the

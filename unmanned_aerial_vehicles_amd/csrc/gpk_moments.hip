@@ -22,7 +22,7 @@
 //                            A0 = I + lin[:, :nx] and Cx the state rows of the raw input-output covariance; the lower triangle is formed
 //                            and mirrored.
 // Nothing depends on R or on the other queries: query r of a batch has the bits of the same query served alone.
-#include "gpk_internal.h"
+#include "gpk_horizon.h"
 
 namespace {
 
@@ -397,18 +397,13 @@ __global__ __launch_bounds__(256) void moments_pair_kernel(MomK k, int R, const 
   }
 }
 
-// What the finishing launch does past the moments: the stage of the chain (x null: a predict_moments call, outputs only).
-struct MomAdv {
-  const double *lin, *Qn, *u, *u_next;
-  long long u_row_stride;
-  double *x, *S, *qnext, *traj_next, *sig_next;
-};
-
-// grid R, 256 threads, thread (i, j) = (tid >> 4, tid & 15).  omean (R x NO), ocov (R x NO x NO), oxcov (R x NO x D): raw units.
-__global__ __launch_bounds__(256) void moments_finish_kernel(MomK k, MomAdv v, int R, int G_, int nrw, int NV,
+// grid R, 256 threads, thread (i, j) = (tid >> 4, tid & 15).  v.out: mean (R x NO), cov (R x NO x NO), xcov (R x NO x D) in raw
+// units, null where not wanted.  Past the moments the launch composes the stage of the chain (gpk_horizon.h; v.x null: a
+// predict_moments call, outputs only).
+__global__ __launch_bounds__(256) void moments_finish_kernel(MomK k, StageView v, int R, int G_, int nrw, int NV,
                                                              const double* __restrict__ Sz, const double* __restrict__ Bm,
-                                                             const double* __restrict__ rowpart, const double* __restrict__ pairpart,
-                                                             double* omean, double* ocov, double* oxcov) {
+                                                             const double* __restrict__ rowpart, const double* __restrict__ pairpart) {
+  double *omean = v.out[0], *ocov = v.out[1], *oxcov = v.out[2];
   __shared__ double Em[16], Cz[16][17], Tm[16][17], Vr[16][17], Cx[16][17], sS[16][17], pv[160];
   __shared__ double A[16][17], Sg[16][17], T[16][17], F[16][17], q[16], xn[16], mu[16];
   const int tid = threadIdx.x, i = tid >> 4, j = tid & 15, r = blockIdx.x;
@@ -465,24 +460,12 @@ __global__ __launch_bounds__(256) void moments_finish_kernel(MomK k, MomAdv v, i
   if (ocov && i < NO && j < NO) ocov[((long long)r * NO + i) * NO + j] = Vr[i][j];
   if (oxcov && i < NO && j < D) oxcov[((long long)r * NO + i) * D + j] = j < nx ? Cx[i][j] : 0.0;
   if (!v.x) return;
-  if (tid < D) q[tid] = tid < nx ? v.x[(long long)r * nx + tid] : v.u[r * v.u_row_stride + (tid - nx)];
-  if (i < nx && j < nx) {
-    Sg[i][j] = v.S[((long long)r * nx + i) * nx + j];
-    A[i][j] = (i == j ? 1.0 : 0.0) + v.lin[i * D + j];
-  }
+  stage_load(v, nx, D, r, tid, q, Sg);
+  if (i < nx && j < nx) A[i][j] = (i == j ? 1.0 : 0.0) + v.lin[i * D + j];
   __syncthreads();
-  if (tid < nx) {
-    const int o = k.model_of[tid];
-    double a = 0.0;
-    for (int d = 0; d < D; ++d) a = __builtin_fma(v.lin[tid * D + d], q[d], a);
-    double val = q[tid] + a;
-    if (o >= 0) val += mu[o];
-    xn[tid] = val;
-  }
+  stage_mean(v, k.model_of, nx, D, tid, q, mu, xn);
+  stage_left(nx, tid, A, Sg, T);
   if (i < nx && j < nx) {
-    double t = 0.0;
-    for (int c = 0; c < nx; ++c) t = __builtin_fma(A[i][c], Sg[c][j], t);
-    T[i][j] = t;
     // F = A0 Cx E^T: column j is A0 times the input-output covariance of the output that drives coordinate j
     const int o = k.model_of[j];
     double f = 0.0;
@@ -491,33 +474,12 @@ __global__ __launch_bounds__(256) void moments_finish_kernel(MomK k, MomAdv v, i
     F[i][j] = f;
   }
   __syncthreads();
-  if (i < nx && j <= i) {
-    double s = 0.0;
-    for (int c = 0; c < nx; ++c) s = __builtin_fma(T[i][c], A[j][c], s);
-    s += F[i][j] + F[j][i];
-    const int oi = k.model_of[i], oj = k.model_of[j];
-    if (oi >= 0 && oj >= 0) s += Vr[oi][oj];
-    if (v.Qn) s += v.Qn[i * nx + j];
-    const long long at = (long long)r * nx * nx;
-    v.S[at + i * nx + j] = s;
-    v.S[at + j * nx + i] = s;
-    v.sig_next[at + i * nx + j] = s;
-    v.sig_next[at + j * nx + i] = s;
-  }
-  if (tid < nx) {
-    v.x[(long long)r * nx + tid] = xn[tid];
-    v.traj_next[(long long)r * nx + tid] = xn[tid];
-  }
-  if (v.qnext && tid < D) {
-    const double raw = tid < nx ? xn[tid] : v.u_next[r * v.u_row_stride + (tid - nx)];
-    v.qnext[(long long)r * D + tid] = k.scaled ? (raw - k.in_shift[tid]) / k.in_scale[tid] : raw;
-  }
-}
-
-bool mm_finite(const double* p, size_t n) {
-  for (size_t i = 0; i < n; ++i)
-    if (!(p[i] - p[i] == 0.0)) return false;
-  return true;
+  stage_right(v, nx, r, tid, T, A, [&](double s, int a, int b) {
+    s += F[a][b] + F[b][a];
+    const int oa = k.model_of[a], ob = k.model_of[b];
+    return oa >= 0 && ob >= 0 ? s + Vr[oa][ob] : s;
+  });
+  stage_store(v, k.scaled, k.in_shift, k.in_scale, nx, D, r, tid, xn);
 }
 
 // The device work area of one batch of R queries, carved from `base`.
@@ -573,61 +535,42 @@ int mm_launch(gpk_handle h, const MomK& k, const MomWork& w, int R, const double
   return GPK_OK;
 }
 
-void mm_finish(gpk_handle h, const MomK& k, const MomWork& w, const MomAdv& v, int R, double* omean, double* ocov, double* oxcov) {
+void mm_finish(gpk_handle h, const MomK& k, const MomWork& w, const StageView& v, int R) {
   hipLaunchKernelGGL(moments_finish_kernel, dim3((unsigned)R), dim3(256), 0, h->stream, k, v, R, w.G_, w.nrw, w.NV, (const double*)w.Sz,
-                     (const double*)w.Bm, (const double*)w.rowpart, (const double*)w.pairpart, omean, ocov, oxcov);
+                     (const double*)w.Bm, (const double*)w.rowpart, (const double*)w.pairpart);
 }
 
-// What the four entries are called with, past the handle.
-struct MomModels {
-  int B, P;
-  const double* const* X;
-  const double* const* alpha;
-  int64_t N;
-  int D;
-  const double *ls, *sf2, *y_mean, *y_std;
-  const double* const* Kinv;
-  int64_t Np, ldk;
-  const double* kss;
-  double floor_;
-  int var_includes_noise;
-  const double* noise;
-  int nx;
-  const int* coord;                  // B state coordinates (batch) or null (single model: output p drives coordinate p)
-  const double *in_shift, *in_scale;
-};
-
 // Every check of the model arguments (GPK_BAD_ARG before anything is launched) and the kernels' parameter block.
-int mm_models(gpk_handle h, const std::string& who, const MomModels& m, bool chain, MomK& k) {
+int mm_models(gpk_handle h, const std::string& who, const HostModels& m, bool chain, MomK& k) {
   GPK_REQUIRE(h, h->batch == 1, who + "not available in batched mode");
   GPK_REQUIRE(h, m.X && m.alpha && m.ls && m.sf2 && m.y_mean && m.y_std && m.kss, who + "null pointer");
-  GPK_REQUIRE(h, m.Kinv, who + "null K^-1 (gpk_wtw of the model's inverse factor)");
+  GPK_REQUIRE(h, m.W, who + "null K^-1 (gpk_wtw of the model's inverse factor)");
   GPK_REQUIRE(h, m.B >= 1 && m.B <= GPK_SMALL_MAX_MODELS, who + "1..8 models");
   GPK_REQUIRE(h, m.P >= 1 && m.P <= GPK_MAX_P && m.P <= 16 && (m.B == 1 || m.P == 1), who + "P must be in [1, 16]");
   GPK_REQUIRE(h, m.D >= 1 && m.D <= GPK_PROP_MAX_D && m.nx >= 1 && m.nx <= GPK_PROP_MAX_NX && m.nx <= m.D, who + "needs 1 <= nx <= D <= 16");
   GPK_REQUIRE(h, !chain || m.nx >= m.B * m.P, who + "the state dimension nx must not be below the number of outputs");
   GPK_REQUIRE(h, m.N >= 1 && gpk_padded(m.N) <= GPK_SMALL_MAX_NP && m.Np == gpk_padded(m.N),
               who + "needs N <= 16384 and Np = gpk_padded(N)");
-  GPK_REQUIRE(h, m.ldk >= m.Np, who + "needs ldk >= Np");
+  GPK_REQUIRE(h, m.ldw >= m.Np, who + "needs ldk >= Np");
   GPK_REQUIRE(h, !m.var_includes_noise || m.noise, who + "null noise levels");
   GPK_REQUIRE(h, (m.in_shift == nullptr) == (m.in_scale == nullptr), who + "in_shift and in_scale go together");
   const int NO = m.B * m.P;
   for (int b = 0; b < m.B; ++b) GPK_REQUIRE(h, m.X[b] && m.alpha[b], who + "null model pointer");
-  for (int b = 0; b < m.B; ++b) GPK_REQUIRE(h, m.Kinv[b], who + "null K^-1 (gpk_wtw of the model's inverse factor)");
-  GPK_REQUIRE(h, mm_finite(m.ls, (size_t)m.B * m.D) && mm_finite(m.sf2, m.B) && mm_finite(m.y_mean, NO) && mm_finite(m.y_std, NO),
+  for (int b = 0; b < m.B; ++b) GPK_REQUIRE(h, m.W[b], who + "null K^-1 (gpk_wtw of the model's inverse factor)");
+  GPK_REQUIRE(h, gpk_finite(m.ls, (size_t)m.B * m.D) && gpk_finite(m.sf2, m.B) && gpk_finite(m.y_mean, NO) && gpk_finite(m.y_std, NO),
               who + "ls, sf2, y_mean and y_std must not contain NaN or infinity");
   for (int i = 0; i < m.B * m.D; ++i) GPK_REQUIRE(h, m.ls[i] > 0.0, who + "length-scales must be positive");
   for (int b = 0; b < m.B; ++b) GPK_REQUIRE(h, m.sf2[b] > 0.0, who + "sf2 must be positive");
-  GPK_REQUIRE(h, mm_finite(m.kss, m.B) && mm_finite(&m.floor_, 1) && (!m.var_includes_noise || mm_finite(m.noise, m.B)),
+  GPK_REQUIRE(h, gpk_finite(m.kss, m.B) && gpk_finite(&m.floor_, 1) && (!m.var_includes_noise || gpk_finite(m.noise, m.B)),
               who + "kss, floor and noise must be finite");
   k = MomK{};
   k.B = m.B; k.P = m.P; k.D = m.D; k.nx = m.nx; k.NO = NO; k.U = m.B * (m.B + 1) / 2;
-  k.N = m.N; k.Np = m.Np; k.ldk = m.ldk;
+  k.N = m.N; k.Np = m.Np; k.ldk = m.ldw;
   k.floor_ = m.floor_;
   k.add_noise = m.var_includes_noise != 0;
   for (int d = 0; d < 16; ++d) { k.in_shift[d] = 0.0; k.in_scale[d] = 1.0; k.model_of[d] = -1; }
   for (int b = 0; b < m.B; ++b) {
-    k.X[b] = m.X[b]; k.alpha[b] = m.alpha[b]; k.Kinv[b] = m.Kinv[b];
+    k.X[b] = m.X[b]; k.alpha[b] = m.alpha[b]; k.Kinv[b] = m.W[b];
     for (int d = 0; d < m.D; ++d) k.ls[b][d] = m.ls[(size_t)b * m.D + d];
     k.lsf2[b] = log(m.sf2[b]);
     k.kss[b] = m.kss[b];
@@ -635,7 +578,7 @@ int mm_models(gpk_handle h, const std::string& who, const MomModels& m, bool cha
   }
   for (int o = 0; o < NO; ++o) { k.ymean[o] = m.y_mean[o]; k.ystd[o] = m.y_std[o]; }
   if (m.in_shift) {
-    GPK_REQUIRE(h, mm_finite(m.in_shift, m.D) && mm_finite(m.in_scale, m.D), who + "the input scaler must not contain NaN or infinity");
+    GPK_REQUIRE(h, gpk_finite(m.in_shift, m.D) && gpk_finite(m.in_scale, m.D), who + "the input scaler must not contain NaN or infinity");
     for (int d = 0; d < m.D; ++d) {
       GPK_REQUIRE(h, m.in_scale[d] != 0.0, who + "in_scale must be non-zero");
       k.in_shift[d] = m.in_shift[d];
@@ -655,7 +598,7 @@ int mm_models(gpk_handle h, const std::string& who, const MomModels& m, bool cha
 }
 
 // M <= 32 Gaussian queries: one upload [z | S], five launches, three downloads, one synchronisation.
-int mm_query(gpk_handle h, const std::string& who, const MomModels& m, const double* Xq, const double* Sq, int M, double* mean,
+int mm_query(gpk_handle h, const std::string& who, const HostModels& m, const double* Xq, const double* Sq, int M, double* mean,
              double* cov, double* xcov) {
   if (!h) return GPK_BAD_ARG;
   MomK k;
@@ -664,8 +607,8 @@ int mm_query(gpk_handle h, const std::string& who, const MomModels& m, const dou
   GPK_REQUIRE(h, Xq && mean && cov && xcov, who + "null pointer");
   const int D = k.D, nx = k.nx, NO = k.NO;
   const size_t n_q = (size_t)M * D, n_s = (size_t)M * nx * nx;
-  GPK_REQUIRE(h, mm_finite(Xq, n_q), who + "the queries must not contain NaN or infinity");
-  GPK_REQUIRE(h, !Sq || mm_finite(Sq, n_s), who + "the covariances must not contain NaN or infinity");
+  GPK_REQUIRE(h, gpk_finite(Xq, n_q), who + "the queries must not contain NaN or infinity");
+  GPK_REQUIRE(h, !Sq || gpk_finite(Sq, n_s), who + "the covariances must not contain NaN or infinity");
   const size_t n_om = (size_t)M * NO, n_oc = n_om * NO, n_ox = n_om * D;
   const MomWork sizes = mm_work(k, M, nullptr);
   void* ws = nullptr;
@@ -689,7 +632,9 @@ int mm_query(gpk_handle h, const std::string& who, const MomModels& m, const dou
   }
   GPK_CHECK_HIP(h, hipMemcpyAsync(d_q, host.data(), sizeof(double) * (n_q + n_s), hipMemcpyHostToDevice, h->stream));
   GPK_TRY(mm_launch(h, k, w, M, d_q, d_S));
-  mm_finish(h, k, w, MomAdv{}, M, d_om, d_oc, d_ox);
+  StageView v{};
+  v.out[0] = d_om; v.out[1] = d_oc; v.out[2] = d_ox;
+  mm_finish(h, k, w, v, M);
   GPK_LAUNCH_CHECK(h);
   GPK_CHECK_HIP(h, hipMemcpyAsync(mean, d_om, sizeof(double) * n_om, hipMemcpyDeviceToHost, h->stream));
   GPK_CHECK_HIP(h, hipMemcpyAsync(cov, d_oc, sizeof(double) * n_oc, hipMemcpyDeviceToHost, h->stream));
@@ -698,92 +643,34 @@ int mm_query(gpk_handle h, const std::string& who, const MomModels& m, const dou
   return GPK_OK;
 }
 
-// The horizon chain: one upload [x | S | q | lin | Q | U], 5 H launches, up to five downloads, one synchronisation.
-int mm_chain(gpk_handle h, const std::string& who, const MomModels& m, const double* x0, int x0_rows, const double* U, int u_rows,
-             const double* lin, const double* Sigma0, int s_rows, const double* Q, int R, int H, double* traj, double* Sigma,
-             double* mean, double* cov, double* xcov) {
+// The horizon chain on the skeleton of gpk_propagate.hip: one upload (the head), 5 H launches - the finishing one composes the
+// stage and is what GPK_TIMED_PROPAGATE brackets - up to five downloads, one synchronisation.
+int mm_chain(gpk_handle h, const std::string& who, const HostModels& m, const Horizon& z) {
   if (!h) return GPK_BAD_ARG;
   MomK k;
   GPK_TRY(mm_models(h, who, m, true, k));
-  const int D = k.D, nx = k.nx, nu = D - nx, NO = k.NO;
-  GPK_REQUIRE(h, R >= 1 && R <= GPK_PROP_MAX_R, who + "R must be in [1, 32]");
-  GPK_REQUIRE(h, H >= 1 && H <= GPK_PROP_MAX_H, who + "H must be in [1, 256]");
-  GPK_REQUIRE(h, x0 && lin && traj && Sigma, who + "null pointer");
-  GPK_REQUIRE(h, nu == 0 || U, who + "null controls");
-  GPK_REQUIRE(h, x0_rows == 1 || x0_rows == R, who + "x0 must have 1 or R rows");
-  GPK_REQUIRE(h, nu == 0 || u_rows == 1 || u_rows == R, who + "U must have 1 or R rows");
-  GPK_REQUIRE(h, !Sigma0 || s_rows == 1 || s_rows == R, who + "Sigma0 must have 1 or R rows");
-  const size_t n_x = (size_t)R * nx, n_s = n_x * nx, n_q = (size_t)R * D, n_lin = (size_t)nx * D, n_Q = (size_t)nx * nx;
-  const size_t n_u = nu ? (size_t)u_rows * H * nu : 0;
-  GPK_REQUIRE(h, mm_finite(x0, (size_t)x0_rows * nx) && mm_finite(lin, n_lin) && (!n_u || mm_finite(U, n_u)) && (!Q || mm_finite(Q, n_Q)),
-              who + "x0, U, lin and Q must not contain NaN or infinity");
-  GPK_REQUIRE(h, !Sigma0 || mm_finite(Sigma0, (size_t)s_rows * n_Q), who + "Sigma0 must not contain NaN or infinity");
-  const size_t n_up = n_x + n_s + n_q + n_lin + n_Q + n_u;
-  const size_t n_om = (size_t)R * NO, n_oc = n_om * NO, n_ox = n_om * D;
-  const size_t n_traj = (size_t)H * n_x, n_sig = (size_t)H * n_s;
-  const MomWork sizes = mm_work(k, R, nullptr);
-  void* ws = nullptr;
-  GPK_TRY(gpk_scratch(h, (n_up + n_traj + n_sig + (size_t)H * (n_om + n_oc + n_ox) + sizes.doubles) * sizeof(double), &ws));
-  double* d_x = (double*)ws;
-  double* d_S = d_x + n_x;
-  double* d_q = d_S + n_s;
-  double* d_lin = d_q + n_q;
-  double* d_Q = d_lin + n_lin;
-  double* d_u = d_Q + n_Q;
-  double* d_traj = d_u + n_u;
-  double* d_sig = d_traj + n_traj;
-  double* d_om = d_sig + n_sig;
-  double* d_oc = d_om + (size_t)H * n_om;
-  double* d_ox = d_oc + (size_t)H * n_oc;
-  const MomWork w = mm_work(k, R, d_ox + (size_t)H * n_ox);
-  std::vector<double> host(n_up, 0.0);
-  double* hS = host.data() + n_x;
-  double* hq = hS + n_s;
-  for (int r = 0; r < R; ++r) {
-    const double* xr = x0 + (x0_rows == 1 ? 0 : (size_t)r * nx);
-    memcpy(host.data() + (size_t)r * nx, xr, sizeof(double) * nx);
-    if (Sigma0) {      // the lower triangle is the matrix: mirrored here as every later stage is
-      const double* s0 = Sigma0 + (s_rows == 1 ? 0 : (size_t)r * n_Q);
-      for (int i = 0; i < nx; ++i)
-        for (int j = 0; j <= i; ++j) hS[(size_t)r * n_Q + i * nx + j] = hS[(size_t)r * n_Q + j * nx + i] = s0[i * nx + j];
-    }
-    for (int d = 0; d < D; ++d) {
-      const double raw = d < nx ? xr[d] : U[(u_rows == 1 ? 0 : (size_t)r * H * nu) + (d - nx)];
-      hq[(size_t)r * D + d] = k.scaled ? (raw - k.in_shift[d]) / k.in_scale[d] : raw;
-    }
-  }
-  memcpy(hq + n_q, lin, sizeof(double) * n_lin);
-  if (Q)
-    for (int i = 0; i < nx; ++i)
-      for (int j = 0; j <= i; ++j) hq[n_q + n_lin + i * nx + j] = hq[n_q + n_lin + j * nx + i] = Q[i * nx + j];
-  if (n_u) memcpy(hq + n_q + n_lin + n_Q, U, sizeof(double) * n_u);
-  memcpy(traj, host.data(), sizeof(double) * n_x);
-  memcpy(Sigma, hS, sizeof(double) * n_s);
-  GPK_CHECK_HIP(h, hipMemcpyAsync(d_x, host.data(), sizeof(double) * n_up, hipMemcpyHostToDevice, h->stream));
-  MomAdv v{};
-  v.lin = d_lin; v.Qn = Q ? d_Q : nullptr; v.x = d_x; v.S = d_S;
-  v.u_row_stride = (nu && u_rows == R) ? (long long)H * nu : 0;
-  for (int s = 0; s < H; ++s) {
-    const bool last = s + 1 == H;
-    GPK_TRY(mm_launch(h, k, w, R, d_q, d_S));
-    v.u = d_u + (size_t)s * nu;
-    v.u_next = d_u + (size_t)(last ? s : s + 1) * nu;
-    v.qnext = last ? nullptr : d_q;
-    v.traj_next = d_traj + (size_t)s * n_x;
-    v.sig_next = d_sig + (size_t)s * n_s;
+  GPK_TRY(gpk_horizon_check(h, who, k.nx, k.D, z));
+  const int R = z.R;
+  const size_t n_om = (size_t)R * k.NO;
+  HorizonBlock b(k.nx, k.D, z);
+  MomWork w{};
+  GPK_TRY(gpk_horizon_carve(h, b, [&] {
+    b.head();
+    b.outputs(n_om, z.mean, n_om * k.NO, z.cov, n_om * k.D, z.xcov);
+    w = mm_work(k, R, b.base ? b.base + b.at : nullptr);
+    b.take(w.doubles);
+  }));
+  std::vector<double> host(b.n_head(), 0.0);
+  gpk_horizon_pack(b, z, k.scaled, k.in_shift, k.in_scale, host.data());
+  GPK_TRY(gpk_horizon_upload(h, b, z, host));
+  for (int s = 0; s < z.H; ++s) {
+    GPK_TRY(mm_launch(h, k, w, R, b.q, b.S));
     gpk_time_begin(h, GPK_TIMED_PROPAGATE);
-    mm_finish(h, k, w, v, R, mean ? d_om + (size_t)s * n_om : nullptr, cov ? d_oc + (size_t)s * n_oc : nullptr,
-              xcov ? d_ox + (size_t)s * n_ox : nullptr);
+    mm_finish(h, k, w, gpk_horizon_stage(b, z, s), R);
     gpk_time_end(h);
     GPK_LAUNCH_CHECK(h);
   }
-  GPK_CHECK_HIP(h, hipMemcpyAsync(traj + n_x, d_traj, sizeof(double) * n_traj, hipMemcpyDeviceToHost, h->stream));
-  GPK_CHECK_HIP(h, hipMemcpyAsync(Sigma + n_s, d_sig, sizeof(double) * n_sig, hipMemcpyDeviceToHost, h->stream));
-  if (mean) GPK_CHECK_HIP(h, hipMemcpyAsync(mean, d_om, sizeof(double) * H * n_om, hipMemcpyDeviceToHost, h->stream));
-  if (cov) GPK_CHECK_HIP(h, hipMemcpyAsync(cov, d_oc, sizeof(double) * H * n_oc, hipMemcpyDeviceToHost, h->stream));
-  if (xcov) GPK_CHECK_HIP(h, hipMemcpyAsync(xcov, d_ox, sizeof(double) * H * n_ox, hipMemcpyDeviceToHost, h->stream));
-  GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
-  return GPK_OK;
+  return gpk_horizon_finish(h, b, z, {});
 }
 
 }  // namespace
@@ -793,7 +680,7 @@ extern "C" int gpk_moments_host(gpk_handle h, const double* X, const double* alp
                                 double floor_, int var_includes_noise, double noise, int nx, const double* Xq, const double* Sq, int M,
                                 double* mean, double* cov, double* xcov) {
   if (!h) return GPK_BAD_ARG;
-  const MomModels m{1, P, &X, &alpha, N, D, ls, &sf2, y_mean, y_std, &Kinv, Np, ldk, &kss, floor_, var_includes_noise, &noise, nx,
+  const HostModels m{1, P, &X, &alpha, N, D, ls, &sf2, y_mean, y_std, &Kinv, Np, ldk, &kss, floor_, var_includes_noise, &noise, nx,
                     nullptr, nullptr, nullptr};
   GPK_REQUIRE(h, X && alpha, "moments_host: null pointer");
   GPK_REQUIRE(h, Kinv, "moments_host: null K^-1 (gpk_wtw of the model's inverse factor)");
@@ -807,7 +694,7 @@ extern "C" int gpk_moments_host_multi(gpk_handle h, int B, const double* const* 
                                       const double* in_scale, const double* Xq, const double* Sq, int M, double* mean, double* cov,
                                       double* xcov) {
   if (!h) return GPK_BAD_ARG;
-  const MomModels m{B, 1, X, alpha, N, D, ls, sf2, y_mean, y_std, Kinv, Np, ldk, kss, floor_, var_includes_noise, noise, nx,
+  const HostModels m{B, 1, X, alpha, N, D, ls, sf2, y_mean, y_std, Kinv, Np, ldk, kss, floor_, var_includes_noise, noise, nx,
                     nullptr, in_shift, in_scale};
   return mm_query(h, "moments_host_multi: ", m, Xq, Sq, M, mean, cov, xcov);
 }
@@ -818,12 +705,14 @@ extern "C" int gpk_propagate_mm_host(gpk_handle h, const double* X, const double
                                      const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows, const double* Q,
                                      int R, int H, double* traj, double* Sigma, double* mean, double* cov, double* xcov) {
   if (!h) return GPK_BAD_ARG;
-  const MomModels m{1, P, &X, &alpha, N, D, ls, &sf2, y_mean, y_std, &Kinv, Np, ldk, &kss, floor_, var_includes_noise, &noise, P,
+  const HostModels m{1, P, &X, &alpha, N, D, ls, &sf2, y_mean, y_std, &Kinv, Np, ldk, &kss, floor_, var_includes_noise, &noise, P,
                     nullptr, nullptr, nullptr};
   GPK_REQUIRE(h, X && alpha, "propagate_mm_host: null pointer");
   GPK_REQUIRE(h, Kinv, "propagate_mm_host: null K^-1 (gpk_wtw of the model's inverse factor)");
   GPK_REQUIRE(h, P >= 1 && P <= D, "propagate_mm_host: the state dimension P must be in [1, 16] and must not exceed D");
-  return mm_chain(h, "propagate_mm_host: ", m, x0, x0_rows, U, u_rows, lin, Sigma0, s_rows, Q, R, H, traj, Sigma, mean, cov, xcov);
+  Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean};
+  z.cov = cov; z.xcov = xcov;
+  return mm_chain(h, "propagate_mm_host: ", m, z);
 }
 
 extern "C" int gpk_propagate_mm_host_multi(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D,
@@ -836,7 +725,9 @@ extern "C" int gpk_propagate_mm_host_multi(gpk_handle h, int B, const double* co
                                            double* xcov) {
   if (!h) return GPK_BAD_ARG;
   GPK_REQUIRE(h, coord, "propagate_mm_host_multi: null pointer");
-  const MomModels m{B, 1, X, alpha, N, D, ls, sf2, y_mean, y_std, Kinv, Np, ldk, kss, floor_, var_includes_noise, noise, nx, coord,
+  const HostModels m{B, 1, X, alpha, N, D, ls, sf2, y_mean, y_std, Kinv, Np, ldk, kss, floor_, var_includes_noise, noise, nx, coord,
                     in_shift, in_scale};
-  return mm_chain(h, "propagate_mm_host_multi: ", m, x0, x0_rows, U, u_rows, lin, Sigma0, s_rows, Q, R, H, traj, Sigma, mean, cov, xcov);
+  Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean};
+  z.cov = cov; z.xcov = xcov;
+  return mm_chain(h, "propagate_mm_host_multi: ", m, z);
 }

@@ -290,12 +290,6 @@ int paths_stage(gpk_handle h, const PathsModel& m, const double* xs, int dx, con
   return GPK_OK;
 }
 
-bool all_finite(const double* a, long long n) {
-  for (long long i = 0; i < n; ++i)
-    if (!(a[i] - a[i] == 0.0)) return false;
-  return true;
-}
-
 // ---- the per-axis batch: B single-output models on shared inputs, each with its own kernel -------------------------------------
 // Coef is model-major: model b, path s is column b mstride + s, so lane l of a wave owns path 64 block + l for the basis value AND
 // for the product - no LDS between the two - and a wave's load of a coefficient row is B contiguous runs of 64 doubles.  The
@@ -860,8 +854,8 @@ int paths_rollout_run(gpk_handle h, const char* name, int w, int D, int S, const
   GPK_REQUIRE(h, x0_rows == 1 || x0_rows == S, who + "x0 must have 1 or S rows");
   const int du = D - w;
   GPK_REQUIRE(h, du == 0 || U, who + "null controls");
-  GPK_REQUIRE(h, all_finite(x0, (long long)x0_rows * w) && all_finite(lin, (long long)w * D) &&
-                     (du == 0 || all_finite(U, (long long)H * du)),
+  GPK_REQUIRE(h, gpk_finite(x0, (long long)x0_rows * w) && gpk_finite(lin, (long long)w * D) &&
+                     (du == 0 || gpk_finite(U, (long long)H * du)),
               who + "x0, U and lin must not contain NaN or infinity");
   const size_t C = (size_t)S * w;
   const size_t n_traj = (size_t)(H + 1) * C, n_u = (size_t)H * du, n_lin = (size_t)w * D;
@@ -1090,7 +1084,7 @@ static int paths_rollout_multi(gpk_handle h, bool own_z, bool grad, const double
     m.k.model_of[coord[b]] = b;
   }
   if (in_shift) {
-    GPK_REQUIRE(h, all_finite(in_shift, D) && all_finite(in_scale, D),
+    GPK_REQUIRE(h, gpk_finite(in_shift, D) && gpk_finite(in_scale, D),
                 "paths_rollout_multi: the input scaler must not contain NaN or infinity");
     for (int d = 0; d < D; ++d) {
       GPK_REQUIRE(h, in_scale[d] != 0.0, "paths_rollout_multi: in_scale must be non-zero");

@@ -1381,10 +1381,7 @@ extern "C" int gpk_sparse_predict_multi_cov(gpk_handle h, int B, const gpk_handl
 // ---- horizon propagation (K11) on the sparse posteriors: the chain of gpk_propagate.hip on the two-factor description ----------
 // The stage's variance comes out of the two-factor launch final - times y_std^2, the noise level inside kss - in the layout of
 // its var_out (M x P for one model, B x M for a batch): the advance launch takes it as it is (ystd2 = 1, add_noise = 0).
-static int sparse_propagate_any(gpk_handle h, const std::string& who, int var_includes_noise, const double* x0, int x0_rows,
-                                const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows, const double* Q,
-                                int R, int H, double* traj, double* Sigma, double* mean, double* var, double* jac, int order,
-                                double* corr, const HorizonGrad* grad = nullptr) {
+static int sparse_propagate_any(gpk_handle h, const std::string& who, int var_includes_noise, const Horizon& z) {
   if (!h) return GPK_BAD_ARG;
   gpk_sparse* s = h->sparse;
   GPK_REQUIRE(h, s && s->finalized, who + "no finalised sparse model (call gpk_sparse_finalize first)");
@@ -1398,76 +1395,77 @@ static int sparse_propagate_any(gpk_handle h, const std::string& who, int var_in
   k.nx = P; k.D = D; k.NO = P;
   k.so = 1; k.sm = P; k.vo = 1; k.vm = P;
   for (int d = 0; d < 16; ++d) { k.in_shift[d] = 0.0; k.in_scale[d] = 1.0; k.model_of[d] = d < P ? d : -1; k.ystd2[d] = 1.0; }
-  const Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean, var, jac, order, corr, grad};
   return gpk_propagate_run(h, who, sv.models(), k, z);
 }
 
 extern "C" int gpk_sparse_propagate(gpk_handle h, int var_includes_noise, const double* x0, int x0_rows, const double* U, int u_rows,
                                     const double* lin, const double* Sigma0, int s_rows, const double* Q, int R, int H, double* traj,
                                     double* Sigma, double* mean, double* var, double* jac) {
-  return sparse_propagate_any(h, "sparse_propagate: ", var_includes_noise, x0, x0_rows, U, u_rows, lin, Sigma0, s_rows, Q, R, H, traj,
-                              Sigma, mean, var, jac, 1, nullptr);
+  return sparse_propagate_any(h, "sparse_propagate: ", var_includes_noise,
+                              Horizon{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean, var, jac});
 }
 
 // ... at second order (order = 2): the mean's model is (Z, alpha_u), as in gpk_sparse_predict_hess; corr (H, R, P), may be null
 extern "C" int gpk_sparse_propagate2(gpk_handle h, int var_includes_noise, const double* x0, int x0_rows, const double* U, int u_rows,
                                      const double* lin, const double* Sigma0, int s_rows, const double* Q, int R, int H, double* traj,
                                      double* Sigma, double* mean, double* var, double* jac, int order, double* corr) {
-  return sparse_propagate_any(h, "sparse_propagate2: ", var_includes_noise, x0, x0_rows, U, u_rows, lin, Sigma0, s_rows, Q, R, H, traj,
-                              Sigma, mean, var, jac, order, corr);
+  return sparse_propagate_any(h, "sparse_propagate2: ", var_includes_noise,
+                              Horizon{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean, var, jac, order, corr});
 }
 
-static int sparse_propagate_multi_any(gpk_handle h, const char* entry, int B, const gpk_handle* models, int var_includes_noise, int nx,
-                                      const int* coord, const double* in_shift, const double* in_scale, const double* out_shift,
-                                      const double* out_scale, const double* x0, int x0_rows, const double* U, int u_rows,
-                                      const double* lin, const double* Sigma0, int s_rows, const double* Q, int R, int H,
-                                      double* traj, double* Sigma, double* mean, double* var, double* jac, int order, double* corr,
-                                      const HorizonGrad* grad = nullptr) {
+// What the batch entries are called with past the handle and before the horizon.
+struct SparseBatchArgs {
+  int B;
+  const gpk_handle* models;
+  int var_includes_noise, nx;
+  const int* coord;
+  const double *in_shift, *in_scale, *out_shift, *out_scale;
+};
+
+static int sparse_propagate_multi_any(gpk_handle h, const char* entry, const SparseBatchArgs& a, const Horizon& z) {
   if (!h) return GPK_BAD_ARG;
   const std::string who(std::string(entry) + ": ");
+  const int B = a.B, nx = a.nx;
   GPK_REQUIRE(h, B >= 1 && B <= GPK_SMALL_MAX_MODELS, who + "1..8 models");
-  GPK_REQUIRE(h, models && coord, who + "null pointer");
+  GPK_REQUIRE(h, a.models && a.coord, who + "null pointer");
   GPK_REQUIRE(h, h->batch == 1, who + "not available in batched mode");
   GPK_REQUIRE(h, h->small_path, who + "the small-batch path is switched off (option small_path)");
-  GPK_REQUIRE(h, (in_shift == nullptr) == (in_scale == nullptr), who + "in_shift and in_scale go together");
-  GPK_REQUIRE(h, (out_shift == nullptr) == (out_scale == nullptr), who + "out_shift and out_scale go together");
+  GPK_REQUIRE(h, (a.in_shift == nullptr) == (a.in_scale == nullptr), who + "in_shift and in_scale go together");
+  GPK_REQUIRE(h, (a.out_shift == nullptr) == (a.out_scale == nullptr), who + "out_shift and out_scale go together");
   gpk_sparse* list[GPK_SMALL_MAX_MODELS];
-  GPK_TRY(sparse_batch_models(h, entry, B, models, list));
+  GPK_TRY(sparse_batch_models(h, entry, B, a.models, list));
   const int D = list[0]->D;
   GPK_REQUIRE(h, D >= 1 && D <= GPK_PROP_MAX_D && nx >= B && nx <= D, who + "the state dimension nx must be in [B, D], D <= 16");
   GPK_CHECK_HIP(h, hipSetDevice(h->device));
   SparseServe sb;
-  sb.fill(B, list, var_includes_noise);
+  sb.fill(B, list, a.var_includes_noise);
   PropK k{};
   k.nx = nx; k.D = D; k.NO = B;
-  k.so = R; k.sm = 1; k.vo = R; k.vm = 1;
+  k.so = z.R; k.sm = 1; k.vo = z.R; k.vm = 1;
   for (int d = 0; d < 16; ++d) { k.in_shift[d] = 0.0; k.in_scale[d] = 1.0; k.model_of[d] = -1; k.ystd2[d] = 1.0; }
   for (int b = 0; b < B; ++b) {
-    GPK_REQUIRE(h, coord[b] >= 0 && coord[b] < nx, who + "coord must be in [0, nx)");
-    GPK_REQUIRE(h, k.model_of[coord[b]] < 0, who + "coord must be distinct");
-    k.model_of[coord[b]] = b;
+    GPK_REQUIRE(h, a.coord[b] >= 0 && a.coord[b] < nx, who + "coord must be in [0, nx)");
+    GPK_REQUIRE(h, k.model_of[a.coord[b]] < 0, who + "coord must be distinct");
+    k.model_of[a.coord[b]] = b;
   }
-  if (in_shift) {
+  if (a.in_shift) {
+    GPK_REQUIRE(h, gpk_finite(a.in_shift, D) && gpk_finite(a.in_scale, D), who + "the input scaler must not contain NaN or infinity");
     for (int d = 0; d < D; ++d) {
-      GPK_REQUIRE(h, in_shift[d] - in_shift[d] == 0.0 && in_scale[d] - in_scale[d] == 0.0,
-                  who + "the input scaler must not contain NaN or infinity");
-      GPK_REQUIRE(h, in_scale[d] != 0.0, who + "in_scale must be non-zero");
-      k.in_shift[d] = in_shift[d];
-      k.in_scale[d] = in_scale[d];
+      GPK_REQUIRE(h, a.in_scale[d] != 0.0, who + "in_scale must be non-zero");
+      k.in_shift[d] = a.in_shift[d];
+      k.in_scale[d] = a.in_scale[d];
     }
     k.scaled = 1;
   }
   // the affine map behind every model's output, folded into the normalisation the kernels apply (as BatchedARDGP.propagate
   // folds it on the host): out_shift + out_scale (y_mean + y_std s)
-  if (out_shift) {
+  if (a.out_shift) {
+    GPK_REQUIRE(h, gpk_finite(a.out_shift, B) && gpk_finite(a.out_scale, B), who + "the output scaler must not contain NaN or infinity");
     for (int b = 0; b < B; ++b) {
-      GPK_REQUIRE(h, out_shift[b] - out_shift[b] == 0.0 && out_scale[b] - out_scale[b] == 0.0,
-                  who + "the output scaler must not contain NaN or infinity");
-      sb.y_mean[b] = out_shift[b] + out_scale[b] * sb.y_mean[b];
-      sb.y_std[b] = out_scale[b] * sb.y_std[b];
+      sb.y_mean[b] = a.out_shift[b] + a.out_scale[b] * sb.y_mean[b];
+      sb.y_std[b] = a.out_scale[b] * sb.y_std[b];
     }
   }
-  const Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean, var, jac, order, corr, grad};
   return gpk_propagate_run(h, who, sb.models(), k, z);
 }
 
@@ -1476,9 +1474,9 @@ extern "C" int gpk_sparse_propagate_multi(gpk_handle h, int B, const gpk_handle*
                                           const double* out_scale, const double* x0, int x0_rows, const double* U, int u_rows,
                                           const double* lin, const double* Sigma0, int s_rows, const double* Q, int R, int H,
                                           double* traj, double* Sigma, double* mean, double* var, double* jac) {
-  return sparse_propagate_multi_any(h, "sparse_propagate_multi", B, models, var_includes_noise, nx, coord, in_shift, in_scale, out_shift,
-                                    out_scale, x0, x0_rows, U, u_rows, lin, Sigma0, s_rows, Q, R, H, traj, Sigma, mean, var, jac, 1,
-                                    nullptr);
+  return sparse_propagate_multi_any(h, "sparse_propagate_multi",
+                                    {B, models, var_includes_noise, nx, coord, in_shift, in_scale, out_shift, out_scale},
+                                    Horizon{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean, var, jac});
 }
 
 // ... at second order: the output scaler folded into y_std scales c as it scales the mean; corr (H, R, B), may be null
@@ -1488,9 +1486,9 @@ extern "C" int gpk_sparse_propagate2_multi(gpk_handle h, int B, const gpk_handle
                                            const double* lin, const double* Sigma0, int s_rows, const double* Q, int R, int H,
                                            double* traj, double* Sigma, double* mean, double* var, double* jac, int order,
                                            double* corr) {
-  return sparse_propagate_multi_any(h, "sparse_propagate2_multi", B, models, var_includes_noise, nx, coord, in_shift, in_scale,
-                                    out_shift, out_scale, x0, x0_rows, U, u_rows, lin, Sigma0, s_rows, Q, R, H, traj, Sigma, mean, var,
-                                    jac, order, corr);
+  return sparse_propagate_multi_any(h, "sparse_propagate2_multi",
+                                    {B, models, var_includes_noise, nx, coord, in_shift, in_scale, out_shift, out_scale},
+                                    Horizon{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean, var, jac, order, corr});
 }
 
 // ... with the gradient of a horizon cost (order 1; gpk_propagate.hip: the adjoint chain): the Hessian-vector launch runs on the
@@ -1500,8 +1498,8 @@ extern "C" int gpk_sparse_propagate_grad(gpk_handle h, int var_includes_noise, c
                                          double* traj, double* Sigma, double* mean, double* var, double* jac, const double* gx,
                                          const double* gS, double* dU, double* dx0, double* dSigma0) {
   const HorizonGrad g{gx, gS, dU, dx0, dSigma0};
-  return sparse_propagate_any(h, "sparse_propagate_grad: ", var_includes_noise, x0, x0_rows, U, u_rows, lin, Sigma0, s_rows, Q, R, H,
-                              traj, Sigma, mean, var, jac, 1, nullptr, &g);
+  return sparse_propagate_any(h, "sparse_propagate_grad: ", var_includes_noise,
+                              Horizon{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean, var, jac, 1, nullptr, &g});
 }
 
 extern "C" int gpk_sparse_propagate_grad_multi(gpk_handle h, int B, const gpk_handle* models, int var_includes_noise, int nx,
@@ -1512,9 +1510,9 @@ extern "C" int gpk_sparse_propagate_grad_multi(gpk_handle h, int B, const gpk_ha
                                                double* jac, const double* gx, const double* gS, double* dU, double* dx0,
                                                double* dSigma0) {
   const HorizonGrad g{gx, gS, dU, dx0, dSigma0};
-  return sparse_propagate_multi_any(h, "sparse_propagate_grad_multi", B, models, var_includes_noise, nx, coord, in_shift, in_scale,
-                                    out_shift, out_scale, x0, x0_rows, U, u_rows, lin, Sigma0, s_rows, Q, R, H, traj, Sigma, mean, var,
-                                    jac, 1, nullptr, &g);
+  return sparse_propagate_multi_any(h, "sparse_propagate_grad_multi",
+                                    {B, models, var_includes_noise, nx, coord, in_shift, in_scale, out_shift, out_scale},
+                                    Horizon{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean, var, jac, 1, nullptr, &g});
 }
 
 extern "C" int gpk_sparse_export(gpk_handle h, int64_t* m, int* D, int* P, int* n_ls, double* Z, double* G, double* g, double* yy,

@@ -20,6 +20,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import GPK_F32, GPK_F64, GPKError, NotPositiveDefinite
+from .propagate import horizon_call
 
 _backends = {}
 _backends_lock = threading.Lock()
@@ -931,22 +932,11 @@ class DeviceGP:
         assert self.factored
         self._refuse_replica()
         P, D = self.P, self.D
-        traj, Sigma = np.empty((H + 1, R, P)), np.empty((H + 1, R, P, P))
-        mean, var, jac = (np.empty((H, R, P)), np.empty((H, R, P)), np.empty((H, R, P, D))) if stages else (None, None, None)
-        tail = (float(kss), float(floor), int(bool(add_noise)), float(noise), _hp(x0), x0.shape[0], _hp(U) if D > P else None,
-                U.shape[0], _hp(lin), _hp(S0), 1 if S0 is None else S0.shape[0], _hp(Q), R, H, _hp(traj), _hp(Sigma), _hp(mean),
-                _hp(var), _hp(jac))
-        try:
-            if order == 1:
-                self._host_call("gpk_propagate_host", y_mean, y_std, True, *tail)
-            else:
-                corr = np.empty((H, R, P)) if stages else None
-                self._host_call("gpk_propagate2_host", y_mean, y_std, True, *tail, int(order), _hp(corr))
-        except GPKError as e:      # a limit of the entry: the caller's arguments, with the library's message
-            if e.code == _lib.GPK_BAD_ARG:
-                raise ValueError(str(e)) from None
-            raise
-        return (traj, Sigma, mean, var, jac) if order == 1 else (traj, Sigma, mean, var, jac, corr)
+        traj, Sigma, more = horizon_call(
+            lambda *t: self._host_call("gpk_propagate_host" if order == 1 else "gpk_propagate2_host", y_mean, y_std, True, float(kss),
+                                       float(floor), int(bool(add_noise)), float(noise), *t),
+            x0, U, lin, S0, Q, R, H, ((P,), (P,), (P, D)) if stages else None, None if order == 1 else order)
+        return (traj, Sigma, *more)
 
     def propagate_grad_host(self, y_mean, y_std, kss, x0, U, lin, S0, Q, R, H, gx, gS):
         """One C call per horizon with the gradient of a horizon cost (gpk_propagate_grad_host; arguments as
@@ -955,19 +945,10 @@ class DeviceGP:
         message, where the entry refuses its arguments."""
         assert self.factored
         self._refuse_replica()
-        P, D = self.P, self.D
-        traj, Sigma = np.empty((H + 1, R, P)), np.empty((H + 1, R, P, P))
-        dU, dx0, dS0 = np.zeros((R, H, D - P)), np.empty((R, P)), np.empty((R, P, P))
-        try:
-            self._host_call("gpk_propagate_grad_host", y_mean, y_std, True, float(kss), 0.0, 0, 0.0, _hp(x0), x0.shape[0],
-                            _hp(U) if D > P else None, U.shape[0], _hp(lin), _hp(S0), 1 if S0 is None else S0.shape[0], _hp(Q), R, H,
-                            _hp(traj), _hp(Sigma), None, None, None, _hp(gx), _hp(gS), _hp(dU) if D > P else None, _hp(dx0),
-                            _hp(dS0))
-        except GPKError as e:
-            if e.code == _lib.GPK_BAD_ARG:
-                raise ValueError(str(e)) from None
-            raise
-        return traj, Sigma, dU, dx0, dS0
+        traj, Sigma, more = horizon_call(
+            lambda *t: self._host_call("gpk_propagate_grad_host", y_mean, y_std, True, float(kss), 0.0, 0, 0.0, *t),
+            x0, U, lin, S0, Q, R, H, seeds=(gx, gS))
+        return (traj, Sigma, *more)
 
     # ---- exact moment matching (K11, method="moment") ---------------------------------------------------------------------------
     def moments_ok(self):
@@ -1013,12 +994,10 @@ class DeviceGP:
         traj (H + 1, R, P), Sigma (H + 1, R, P, P) and, with `stages`, mean (H, R, P), cov (H, R, P, P), xcov (H, R, P, D) - five
         launches per stage, one synchronisation."""
         P, D = self.P, self.D
-        traj, Sigma = np.empty((H + 1, R, P)), np.empty((H + 1, R, P, P))
-        mean, cov, xcov = (np.empty((H, R, P)), np.empty((H, R, P, P)), np.empty((H, R, P, D))) if stages else (None, None, None)
-        self._moments_call("gpk_propagate_mm_host", y_mean, y_std, float(kss), float(floor), 0, 0.0, _hp(x0), x0.shape[0],
-                           _hp(U) if D > P else None, U.shape[0], _hp(lin), _hp(S0), 1 if S0 is None else S0.shape[0], _hp(Q), R, H,
-                           _hp(traj), _hp(Sigma), _hp(mean), _hp(cov), _hp(xcov))
-        return traj, Sigma, mean, cov, xcov
+        traj, Sigma, more = horizon_call(
+            lambda *t: self._moments_call("gpk_propagate_mm_host", y_mean, y_std, float(kss), float(floor), 0, 0.0, *t),
+            x0, U, lin, S0, Q, R, H, ((P,), (P, P), (P, D)) if stages else None)
+        return (traj, Sigma, *more)
 
     # ---- gated serving: the one place every fp32 surface (estimator, sharded predictor, package GP, per-axis models) goes
     # through -------------------------------------------------------------------------------------------------------------

@@ -50,7 +50,39 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import _lib
+
 MAX_R, MAX_H, MAX_NX = 32, 256, 16
+
+
+def horizon_call(call, x0, U, lin, S0, Q, R, H, stages=None, order=None, seeds=None):
+    """The one C call of a horizon, for every class: `call(*tail)` makes it, with the entry's name and the model's arguments bound
+    by the caller; x0 .. H as `check_horizon` returns them.  The tail every entry shares: x0 and its rows, U (null without
+    controls) and its rows, lin, Sigma0 and its rows, Q, R, H, traj (H + 1, R, nx), Sigma (H + 1, R, nx, nx) and three stage
+    arrays - (H, R) + each shape of `stages`, or null pointers with stages=None.  order (the second-order entries): then the
+    order and corr, (H, R) + stages[0] or null.  seeds = (gx, gS) (the gradient entries): then the seeds and dU (R, H, nu), null
+    without controls, dx0 (R, nx), dSigma0 (R, nx, nx).  Returns (traj, Sigma, more): the stage arrays (Nones with stages=None;
+    corr last, given an order), or [dU, dx0, dSigma0].  ValueError, with the library's message, where the entry refuses its
+    arguments."""
+    hp = _lib.host_ptr
+    nx, D = lin.shape
+    traj, Sigma = np.empty((H + 1, R, nx)), np.empty((H + 1, R, nx, nx))
+    more = [None] * 3 if stages is None else [np.empty((H, R) + tuple(s)) for s in stages]
+    tail = [hp(a) for a in more]
+    if order is not None:
+        more.append(None if stages is None else np.empty((H, R) + tuple(stages[0])))
+        tail += [int(order), hp(more[-1])]
+    if seeds is not None:
+        more = [np.zeros((R, H, D - nx)), np.empty((R, nx)), np.empty((R, nx, nx))]
+        tail += [hp(seeds[0]), hp(seeds[1]), hp(more[0]) if D > nx else None, hp(more[1]), hp(more[2])]
+    try:
+        call(hp(x0), x0.shape[0], hp(U) if D > nx else None, U.shape[0], hp(lin), hp(S0), 1 if S0 is None else S0.shape[0], hp(Q), R, H,
+             hp(traj), hp(Sigma), *tail)
+    except _lib.GPKError as e:      # a limit of the entry: the caller's arguments, with the library's message
+        if e.code == _lib.GPK_BAD_ARG:
+            raise ValueError(str(e)) from None
+        raise
+    return traj, Sigma, more
 
 
 def check_horizon(x0, U, lin, nx, D, Sigma0=None, process_noise=None):

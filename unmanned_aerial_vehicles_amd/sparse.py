@@ -513,23 +513,11 @@ class SparseGP:
             if why:
                 raise ValueError(f"route='chain' is not available: {why}")
             self._ensure()
-            traj, Sigma = np.empty((H + 1, R, P)), np.empty((H + 1, R, P, P))
-            mean, var, jac = (np.empty((H, R, P)), np.empty((H, R, P)), np.empty((H, R, P, D))) if return_stages else (None,) * 3
-            args = (int(bool(var_includes_noise)), _ptr(x0), x0.shape[0], _ptr(U) if D > P else None, U.shape[0], _ptr(lin),
-                    _ptr(S0), 1 if S0 is None else S0.shape[0], _ptr(Q), R, H, _ptr(traj), _ptr(Sigma), _ptr(mean), _ptr(var),
-                    _ptr(jac))
-            stages = {"mean": mean, "var": var, "jac": jac}
-            try:
-                if order == 1:
-                    self._backend().call("gpk_sparse_propagate", *args)
-                else:
-                    stages["corr"] = np.empty((H, R, P)) if return_stages else None
-                    self._backend().call("gpk_sparse_propagate2", *args, order, _ptr(stages["corr"]))
-            except _lib.GPKError as e:      # a limit of the entry: the caller's arguments, with the library's message
-                if e.code == _lib.GPK_BAD_ARG:
-                    raise ValueError(str(e)) from None
-                raise
-            return (traj, Sigma, stages) if return_stages else (traj, Sigma)
+            traj, Sigma, more = _pg.horizon_call(
+                lambda *t: self._backend().call("gpk_sparse_propagate" if order == 1 else "gpk_sparse_propagate2",
+                                                int(bool(var_includes_noise)), *t),
+                x0, U, lin, S0, Q, R, H, ((P,), (P,), (P, D)) if return_stages else None, None if order == 1 else order)
+            return (traj, Sigma, dict(zip(("mean", "var", "jac", "corr"), more))) if return_stages else (traj, Sigma)
         noise = self.kernel_.components().noise or 0.0
         std2 = np.broadcast_to(np.asarray(self._y_train_std, dtype=np.float64).reshape(-1), (P,)) ** 2
 
@@ -563,18 +551,10 @@ class SparseGP:
             if why:
                 raise ValueError(f"route='chain' is not available: {why}")
             self._ensure()
-            traj, Sigma = np.empty((H + 1, R, P)), np.empty((H + 1, R, P, P))
-            dU, dx0, dS0 = np.zeros((R, H, D - P)), np.empty((R, P)), np.empty((R, P, P))
-            try:
-                self._backend().call("gpk_sparse_propagate_grad", int(bool(var_includes_noise)), _ptr(x0), x0.shape[0],
-                                     _ptr(U) if D > P else None, U.shape[0], _ptr(lin), _ptr(S0), 1 if S0 is None else S0.shape[0],
-                                     _ptr(Q), R, H, _ptr(traj), _ptr(Sigma), None, None, None, _ptr(gx), _ptr(gS),
-                                     _ptr(dU) if D > P else None, _ptr(dx0), _ptr(dS0))
-            except _lib.GPKError as e:
-                if e.code == _lib.GPK_BAD_ARG:
-                    raise ValueError(str(e)) from None
-                raise
-            return traj, Sigma, dU, dx0, dS0
+            traj, Sigma, more = _pg.horizon_call(
+                lambda *t: self._backend().call("gpk_sparse_propagate_grad", int(bool(var_includes_noise)), *t),
+                x0, U, lin, S0, Q, R, H, seeds=(gx, gS))
+            return (traj, Sigma, *more)
         noise = self.kernel_.components().noise or 0.0
         std2 = np.broadcast_to(np.asarray(self._y_train_std, dtype=np.float64).reshape(-1), (P,)) ** 2
 

@@ -13,7 +13,6 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
 from .device import check_queries
 from .gpr import cholesky_draws
 from .sparse import SparseGP, _ptr
@@ -174,28 +173,11 @@ class BatchedSparseGP:
             why = self._propagate_refusal(nx)
             if why:
                 raise ValueError(f"route='chain' is not available: {why}")
-            traj, Sigma = np.empty((H + 1, R, nx)), np.empty((H + 1, R, nx, nx))
-            mean, var, jac = (np.empty((H, R, B)), np.empty((H, R, B)), np.empty((H, R, B, D))) if return_stages else (None,) * 3
-            cd = (C.c_int * B)(*coord)
-            scaled = out_scaler is not None
-            om = np.ascontiguousarray(o_mean, dtype=np.float64) if scaled else None
-            osc = np.ascontiguousarray(o_scale, dtype=np.float64) if scaled else None
-            args = (int(bool(var_includes_noise)), nx, cd, _ptr(in_shift), _ptr(in_scale), _ptr(om), _ptr(osc), _ptr(x0), x0.shape[0],
-                    _ptr(U) if D > nx else None, U.shape[0], _ptr(lin), _ptr(S0), 1 if S0 is None else S0.shape[0], _ptr(Q), R, H,
-                    _ptr(traj), _ptr(Sigma), _ptr(mean), _ptr(var), _ptr(jac))
-            stages = {"mean": mean, "var": var, "jac": jac}
-            try:
-                with self._serving() as (be, handles):
-                    if order == 1:
-                        be.call("gpk_sparse_propagate_multi", B, handles, *args)
-                    else:
-                        stages["corr"] = np.empty((H, R, B)) if return_stages else None
-                        be.call("gpk_sparse_propagate2_multi", B, handles, *args, order, _ptr(stages["corr"]))
-            except _lib.GPKError as e:      # a limit of the entry: the caller's arguments, with the library's message
-                if e.code == _lib.GPK_BAD_ARG:
-                    raise ValueError(str(e)) from None
-                raise
-            return (traj, Sigma, stages) if return_stages else (traj, Sigma)
+            traj, Sigma, more = _pg.horizon_call(
+                self._chain_call("gpk_sparse_propagate_multi" if order == 1 else "gpk_sparse_propagate2_multi", var_includes_noise, nx,
+                                 coord, in_shift, in_scale, out_scaler, o_mean, o_scale),
+                x0, U, lin, S0, Q, R, H, ((B,), (B,), (B, D)) if return_stages else None, None if order == 1 else order)
+            return (traj, Sigma, dict(zip(("mean", "var", "jac", "corr"), more))) if return_stages else (traj, Sigma)
         stage = _pg.batch_stage(self.predict_jacobian, _pg.noise_levels(self.models), in_shift, in_scale, o_mean, o_scale,
                                 var_includes_noise)
         hess_stage = _pg.batch_hess_stage(self.predict_hessian, in_shift, in_scale, o_scale) if order == 2 else None
@@ -221,27 +203,28 @@ class BatchedSparseGP:
             why = self._propagate_refusal(nx)
             if why:
                 raise ValueError(f"route='chain' is not available: {why}")
-            traj, Sigma = np.empty((H + 1, R, nx)), np.empty((H + 1, R, nx, nx))
-            dU, dx0, dS0 = np.zeros((R, H, D - nx)), np.empty((R, nx)), np.empty((R, nx, nx))
-            cd = (C.c_int * B)(*coord)
-            scaled = out_scaler is not None
-            om = np.ascontiguousarray(o_mean, dtype=np.float64) if scaled else None
-            osc = np.ascontiguousarray(o_scale, dtype=np.float64) if scaled else None
-            try:
-                with self._serving() as (be, handles):
-                    be.call("gpk_sparse_propagate_grad_multi", B, handles, int(bool(var_includes_noise)), nx, cd, _ptr(in_shift),
-                            _ptr(in_scale), _ptr(om), _ptr(osc), _ptr(x0), x0.shape[0], _ptr(U) if D > nx else None, U.shape[0],
-                            _ptr(lin), _ptr(S0), 1 if S0 is None else S0.shape[0], _ptr(Q), R, H, _ptr(traj), _ptr(Sigma), None,
-                            None, None, _ptr(gx), _ptr(gS), _ptr(dU) if D > nx else None, _ptr(dx0), _ptr(dS0))
-            except _lib.GPKError as e:
-                if e.code == _lib.GPK_BAD_ARG:
-                    raise ValueError(str(e)) from None
-                raise
-            return traj, Sigma, dU, dx0, dS0
+            traj, Sigma, more = _pg.horizon_call(
+                self._chain_call("gpk_sparse_propagate_grad_multi", var_includes_noise, nx, coord, in_shift, in_scale, out_scaler,
+                                 o_mean, o_scale),
+                x0, U, lin, S0, Q, R, H, seeds=(gx, gS))
+            return (traj, Sigma, *more)
         stage = _pg.batch_stage(self.predict_jacobian, _pg.noise_levels(self.models), in_shift, in_scale, o_mean, o_scale,
                                 var_includes_noise, with_dvar=True)
         hess_stage = _pg.batch_hess_stage(self.predict_hessian, in_shift, in_scale, o_scale)
         return _pg.host_adjoint(stage, hess_stage, coord, x0, U, lin, S0, Q, R, H, gx, gS)
+
+    def _chain_call(self, entry, var_includes_noise, nx, coord, in_shift, in_scale, out_scaler, o_mean, o_scale):
+        """The call of a chain entry of the batch for `propagate.horizon_call`, which supplies the horizon's arguments."""
+        B = len(self.models)
+        scaled = out_scaler is not None
+        om = np.ascontiguousarray(o_mean, dtype=np.float64) if scaled else None
+        osc = np.ascontiguousarray(o_scale, dtype=np.float64) if scaled else None
+
+        def call(*tail):
+            with self._serving() as (be, handles):
+                be.call(entry, B, handles, int(bool(var_includes_noise)), nx, (C.c_int * B)(*coord), _ptr(in_shift), _ptr(in_scale),
+                        _ptr(om), _ptr(osc), *tail)
+        return call
 
     def _propagate_refusal(self, nx=None):
         """Why the one-call chain does not apply (a string), or None where it does; nx: the state width (default B)."""
