@@ -90,7 +90,10 @@ GPK_API int64_t gpk_padded(int64_t n);
  * "gram_log" (1: the form of every gpk_gram launch - `GPKGRAM f64|f32 N Np D strip|sym gsG ntT gridNNN` - and of every gpk_predict_mean /
  * gpk_predict_mean_multi launch - `GPKMEAN f64|f32 N M D P|B d4 p4 granG sS chunkC` - and of every gpk_predict_mean_mfma call -
  * `GPKMEANMM bf16|f32 N M D P qbQ nqbN sS chunkC`: the kernel (bf16 x 3 for D <= 14, fp32 MFMA for D = 15, 16), Q query blocks of 32
- * per wave, N workgroups of 128 Q queries, S training chunks of C points - to stderr, one line per launch),
+ * per wave, N workgroups of 128 Q queries, S training chunks of C points - and of every small-batch serving call (up to 32 queries) -
+ * `GPKSMALL predict|cov|grad|jacvar|hess B F Np M D P gaA gbB nmbK rcR hgH slS`: models, inverse factors, A and B workgroups of the
+ * first and of the factor launches, K query blocks of 16 (0: no factor launch), R row chunks of the W^T V launch, H x S workgroups x
+ * slices of the Hessian launch (0: not launched) - to stderr, one line per launch),
  * "k5_log" (1: the form of every 16-bit variance launch - gpk_predict_var_inv_split2 / gpk_predict_mean_var_split2: `GPKK5 direct rowsR
  * ntmTA ntnB nstS padP gridG`, gpk_predict_var_inv_split: `GPKK5 split rowsR ntmTA ntnB nstS pad0 gridG`; R the tile's rows, A x B tiles,
  * S super-tiles, P tile slots per band of the walk - to stderr, one line per launch),

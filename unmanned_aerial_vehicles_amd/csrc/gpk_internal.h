@@ -71,7 +71,7 @@ struct gpk_context {
   int sparse_slabs = 0;      // ... k-slabs of a panel's product F^T F (0: a function of (mp, panel rows), gpk_sparse.hip; 1 .. 64)
   int debug_fill = 0;        // option debug_fill: the handle's scratch is overwritten with 0xFF bytes (NaN) at every request
   int gemm_log = 0;          // option gemm_log = 1: log every tile-GEMM launch to stderr (profiling aid)
-  int gram_log = 0;          // option gram_log = 1: log the form of every gpk_gram / gpk_predict_mean[_multi] / gpk_predict_mean_mfma launch to stderr
+  int gram_log = 0;          // option gram_log = 1: log the form of every gpk_gram / gpk_predict_mean[_multi] / gpk_predict_mean_mfma launch and of every small-batch serving call to stderr
   int k5_log = 0;            // option k5_log = 1: log the form of every 16-bit variance launch (gpk_k5split.hip) to stderr
   // gpk_timing: HIP-event brackets around the dominant launches (K5 variance GEMM, K1 Gram kernel), a ring of pairs
   struct TimedLaunch { hipEvent_t e0 = nullptr, e1 = nullptr; int tag = 0; };

@@ -1316,6 +1316,13 @@ int gpk_small_launch(gpk_handle h, int call, const ServeModels& m, const double*
   const SmallWork wk = small_work(call, Np, B, M, D, P, F);
   double *Ks = work + wk.Ks, *pmean = work + wk.pmean, *pjac = work + wk.pjac;
   const dim3 g1(ga, B), g2(gb, B * F), b1(256), b2(64 * VW);
+  if (h->gram_log) {   // option gram_log = 1: the form this call's launches take (the tests assert it per case); 0: not launched
+    const unsigned wtv = 256 / (gb * (F == 2 ? 2u : (unsigned)B));
+    fprintf(stderr, "GPKSMALL %s %d %d %lld %lld %d %d ga%u gb%u nmb%d rc%u hg%u sl%u\n", name.c_str() + 6, B, F, Np, (long long)M, D, P, ga,
+            gb, factors ? (M <= 16 ? 1 : 2) : 0,
+            (call == GPK_SMALL_GRAD && factors) ? (wtv < 1 ? 1u : wtv > WTV_MAX_ROW_CHUNKS ? WTV_MAX_ROW_CHUNKS : wtv) : 0u,
+            hs ? hess_groups(Np) : 0u, hs ? (unsigned)((M * P + hess_slice(D) - 1) / hess_slice(D)) : 0u);
+  }
   // The first launch.  Nothing follows (the mean, or the mean and its Jacobian): FINISH, and K* is not stored.
   if (grad)
     hipLaunchKernelGGL(factors ? small_cross_mean_jac_kernel<false> : small_cross_mean_jac_kernel<true>, g1, b1, 0, h->stream, k, N, Np,
