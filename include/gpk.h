@@ -93,7 +93,12 @@ GPK_API int64_t gpk_padded(int64_t n);
  * per wave, N workgroups of 128 Q queries, S training chunks of C points - and of every small-batch serving call (up to 32 queries) -
  * `GPKSMALL predict|cov|grad|jacvar|hess B F Np M D P gaA gbB nmbK rcR hgH slS`: models, inverse factors, A and B workgroups of the
  * first and of the factor launches, K query blocks of 16 (0: no factor launch), R row chunks of the W^T V launch, H x S workgroups x
- * slices of the Hessian launch (0: not launched) - to stderr, one line per launch),
+ * slices of the Hessian launch (0: not launched) - and of every launch pair (kernel + reduction, one per query panel) of the large-batch
+ * derivative entries gpk_predict_mean_grad[_multi], gpk_predict_var_grad_inv and gpk_predict_mean_hess[_multi] -
+ * `GPKDERIV mean_grad|mean_grad_multi|var_grad|mean_hess|mean_hess_multi N D P|B mc d4K ps|bsG ngN nrbR nqb|ncbQ granG sS chunkC`: mc
+ * queries in the panel, the D4 = K and PS | BS = G instantiation, N output or model groups x R row blocks of the Hessian's triangle
+ * (the third grid dimension), Q query blocks, S training chunks of C rows, C a multiple of G (var_grad: P = 1, ps1 ng1 nrb1,
+ * query blocks of 128 columns, gran 64) - to stderr, one line per launch),
  * "k5_log" (1: the form of every 16-bit variance launch - gpk_predict_var_inv_split2 / gpk_predict_mean_var_split2: `GPKK5 direct rowsR
  * ntmTA ntnB nstS padP gridG`, gpk_predict_var_inv_split: `GPKK5 split rowsR ntmTA ntnB nstS pad0 gridG`; R the tile's rows, A x B tiles,
  * S super-tiles, P tile slots per band of the walk - to stderr, one line per launch),

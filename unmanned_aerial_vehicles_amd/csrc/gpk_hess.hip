@@ -409,6 +409,9 @@ extern "C" int gpk_predict_mean_hess(gpk_handle h, const double* X, const double
     int64_t chunk = (N + S - 1) / S;
     chunk = (chunk + gran - 1) / gran * gran;
     S = (N + chunk - 1) / chunk;
+    if (h->gram_log)   // option gram_log = 1: the form this launch pair takes (the tests assert it per case)
+      fprintf(stderr, "GPKDERIV mean_hess %lld %d %d %lld d4%d ps%d ng%d nrb%d nqb%lld gran%lld s%lld chunk%lld\n", (long long)N, D, P,
+              (long long)mc, d4, ps, npg, nrb, (long long)nqb, (long long)gran, (long long)S, (long long)chunk);
     void* partial = nullptr;
     GPK_TRY(gpk_scratch(h, (size_t)S * mc * P * TP * sizeof(double), &partial));
     hipLaunchKernelGGL(mh_pick(d4, ps), dim3((unsigned)nqb, (unsigned)S, (unsigned)nz), dim3(256), 0, h->stream, X, alpha,
@@ -466,6 +469,9 @@ extern "C" int gpk_predict_mean_hess_multi(gpk_handle h, const double* X, const 
     int64_t chunk = (N + S - 1) / S;
     chunk = (chunk + gran - 1) / gran * gran;
     S = (N + chunk - 1) / chunk;
+    if (h->gram_log)
+      fprintf(stderr, "GPKDERIV mean_hess_multi %lld %d %d %lld d4%d bs%d ng%d nrb%d nqb%lld gran%lld s%lld chunk%lld\n", (long long)N, D,
+              B, (long long)mc, d4, bs, ng, nrb, (long long)nqb, (long long)gran, (long long)S, (long long)chunk);
     void* partial = nullptr;
     GPK_TRY(gpk_scratch(h, (size_t)S * mc * B * TP * sizeof(double), &partial));
     hipLaunchKernelGGL(mhm_pick(d4, bs), dim3((unsigned)nqb, (unsigned)S, (unsigned)nz), dim3(256), 0, h->stream, X, alpha,

@@ -377,6 +377,9 @@ extern "C" int gpk_predict_mean_grad(gpk_handle h, const double* X, const double
     int64_t chunk = (N + S - 1) / S;
     chunk = (chunk + gran - 1) / gran * gran;
     S = (N + chunk - 1) / chunk;
+    if (h->gram_log)   // option gram_log = 1: the form this launch pair takes (the tests assert it per case)
+      fprintf(stderr, "GPKDERIV mean_grad %lld %d %d %lld d4%d ps%d ng%d nrb1 nqb%lld gran%lld s%lld chunk%lld\n", (long long)N, D, P,
+              (long long)mc, d4, ps, npg, (long long)nqb, (long long)gran, (long long)S, (long long)chunk);
     void* partial = nullptr;
     GPK_TRY(gpk_scratch(h, (size_t)S * mc * P * D * sizeof(double), &partial));
     hipLaunchKernelGGL(mg_pick(d4, ps), dim3((unsigned)nqb, (unsigned)S, (unsigned)npg), dim3(256), 0, h->stream, X, alpha,
@@ -421,6 +424,9 @@ extern "C" int gpk_predict_mean_grad_multi(gpk_handle h, const double* X, const 
     int64_t chunk = (N + S - 1) / S;
     chunk = (chunk + gran - 1) / gran * gran;
     S = (N + chunk - 1) / chunk;
+    if (h->gram_log)
+      fprintf(stderr, "GPKDERIV mean_grad_multi %lld %d %d %lld d4%d bs%d ng%d nrb1 nqb%lld gran%lld s%lld chunk%lld\n", (long long)N, D,
+              B, (long long)mc, d4, bs, ng, (long long)nqb, (long long)gran, (long long)S, (long long)chunk);
     void* partial = nullptr;
     GPK_TRY(gpk_scratch(h, (size_t)S * mc * B * D * sizeof(double), &partial));
     hipLaunchKernelGGL(mgm_pick(d4, bs), dim3((unsigned)nqb, (unsigned)S, (unsigned)ng), dim3(256), 0, h->stream, X, alpha,
@@ -473,6 +479,9 @@ extern "C" int gpk_predict_var_grad_inv(gpk_handle h, const double* X, int64_t N
   int64_t chunk = (N + S - 1) / S;
   chunk = (chunk + VG_TJ - 1) / VG_TJ * VG_TJ;
   S = (N + chunk - 1) / chunk;
+  if (h->gram_log)
+    fprintf(stderr, "GPKDERIV var_grad %lld %d 1 %lld d4%d ps1 ng1 nrb1 ncb%lld gran%d s%lld chunk%lld\n", (long long)N, D, (long long)M,
+            (D + 3) / 4, (long long)ncb, VG_TJ, (long long)S, (long long)chunk);
   void* pg = nullptr;
   GPK_TRY(gpk_scratch(h, (size_t)S * M * (D + 1) * sizeof(double), &pg));
   hipLaunchKernelGGL(vg_pick((D + 3) / 4), dim3((unsigned)ncb, (unsigned)S), dim3(VG_COLS), 0, h->stream, X, (long long)N, D, l,
