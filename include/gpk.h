@@ -103,7 +103,9 @@ GPK_API int64_t gpk_padded(int64_t n);
  * ntmTA ntnB nstS padP gridG`, gpk_predict_var_inv_split: `GPKK5 split rowsR ntmTA ntnB nstS pad0 gridG`; R the tile's rows, A x B tiles,
  * S super-tiles, P tile slots per band of the walk - to stderr, one line per launch),
  * "sparse_panel" / "sparse_slabs" (the statistics pass of the sparse model, K9:
- * rows per panel and k-slabs per panel product; 0 = the built-in rule), "debug_fill" (1: the handle's scratch and serving work area are overwritten with NaN bytes at every request - the test
+ * rows per panel and k-slabs per panel product; 0 = the built-in rule), "moments_query_groups" (the pair launch of the moment-matching
+ * entries, K11: 0 = as many groups of queries as bring it to two workgroups per CU, n >= 1 = at most n, 1 = no split; bit-identical
+ * results), "debug_fill" (1: the handle's scratch and serving work area are overwritten with NaN bytes at every request - the test
  * suite runs with it).  Used by the A/B timings and by the tests that pin a fast path to its plain form.
  * gpk_set_option_str: "ptile_trace_path" - the NEXT one-launch factorisation writes its per-task time stamps to that file
  * (debugging aid, tools/exp_ptile_trace.py).                                                                          */
@@ -1347,6 +1349,54 @@ GPK_API int gpk_propagate_mm_host_multi(gpk_handle h, int B, const double* const
                                         const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows,
                                         const double* Q, int R, int H, double* traj, double* Sigma, double* mean, double* cov,
                                         double* xcov);
+
+/* ... on the sparse posteriors.  The sparse posterior is the exact model's form over the m inducing inputs Z:
+ *   mean(x) = y_mean + y_std k_u(x)^T alpha_u,     var_f(x) = sf2 - k_u(x)^T Q k_u(x),
+ *   Q = Wuu^T Wuu - WSigma^T WSigma  ( = (Kuu + jitter_uu I)^-1 - Sigma~ )
+ * so every closed form above carries over with (Z, alpha_u) as the rows and weights and Q where K^-1 stands: E[v_b] = kss_b -
+ * sum_ij Q^b_ij L^bb_ij.  Q (mp x mp, the lower tiles, ld = mp) is formed on the device on the first of these calls after
+ * gpk_sparse_finalize - two gpk_wtw products and one subtraction launch, one synchronisation - kept with the object and dropped
+ * whenever the model is assembled again (gpk_sparse_finalize after more rows, the evaluations of gpk_sparse_eval[_z]).
+ * kss = sf2, plus the model's noise level when var_includes_noise != 0; the clip of E[v] sits at 0.
+ * gpk_sparse_moments: the finalised sparse object of h, P outputs sharing one L; nx <= D the width of the uncertain block.
+ *   M <= 32 host queries Xq (M x D), Sq (M x nx x nx, the lower triangle is read; NULL: zero) -> mean (M x P), cov (M x P x P),
+ *   xcov (M x P x D).
+ * gpk_sparse_moments_multi: B <= 8 handles of finalised single-output models of equal m and D, each with its own Z, kernel, noise
+ *   and normalisation, handle rules and scalers as gpk_sparse_propagate_multi -> mean (M x B), cov (M x B x B), xcov (M x B x D).
+ * gpk_sparse_propagate_mm[_multi]: the horizon of gpk_propagate_mm_host[_multi] with the arguments of
+ *   gpk_sparse_propagate[_multi] (nx = P in the single form) and (mean, cov, xcov) as the optional stage outputs, which have the
+ *   BITS of gpk_sparse_moments[_multi] at the R Gaussian queries ([traj[h], U[h]], Sigma[h]).
+ * Launches: those of the exact entries - five per batch of queries, 5 H and ONE synchronisation per horizon, the last of a stage
+ *   under GPK_TIMED_PROPAGATE.  At the sparse sizes the pair launch has few tiles (m = 256: 10 lower 64 x 64 tiles per pair,
+ *   m = 1024: 136) for 256 CUs, so its grid has a third dimension over groups of queries - as many groups as bring it to two
+ *   workgroups per CU, one from 512 workgroups on (option "moments_query_groups": n >= 1 caps the count, 1 = no split; the exact
+ *   entries take the same launch).  A slot is still summed by one workgroup over the same tiles in the same order: results do
+ *   not depend on the split, are repeatable bit for bit, and query m has the bits of the same query served alone.  Launches of
+ *   one group run the kernel without the dimension.  Measured (profiles/r28_exp_sparse_moments.log; D = 10, nx = 6, H = 25, one
+ *   model with P = 6, R = 32 rollouts, wall time per horizon): m = 256 1.77 ms against 6.78 ms with one group, m = 1024 3.95
+ *   against 6.80 ms, m = 4096 28.2 ms (one group either way); six models at m = 256 6.77 against 10.5 ms.  Registers and LDS of
+ *   the pair kernel are unchanged: 135 (P = 1) .. 200 (P = 6) .. 256 (P >= 12) VGPRs, 46 .. 61 KB of LDS, no scratch.
+ * GPK_BAD_ARG (with a message, before any launch - Q included - and with the outputs untouched): no finalised sparse model (in
+ *   the batch: any handle), option small_path = 0, batched mode, models that disagree in m or D or have several outputs, B
+ *   outside 1..8, M or R outside [1, 32], H outside [1, 256], nx or D above 16, nx > D, gpk_padded(m) > 16384, NaN or infinity
+ *   in a host input, a scaler given by half, in_scale zero, a null pointer; the chains also: nx below the number of outputs,
+ *   coord out of range or repeated, a wrong row count.
+ *   Replaces: nothing in the reference; here, the first-order chain of gpk_sparse_propagate where the Taylor remainder matters. */
+GPK_API int gpk_sparse_moments(gpk_handle h, int var_includes_noise, int nx, const double* Xq, const double* Sq, int M, double* mean,
+                               double* cov, double* xcov);
+GPK_API int gpk_sparse_moments_multi(gpk_handle h, int B, const gpk_handle* models, int var_includes_noise, int nx,
+                                     const double* in_shift, const double* in_scale, const double* out_shift,
+                                     const double* out_scale, const double* Xq, const double* Sq, int M, double* mean, double* cov,
+                                     double* xcov);
+GPK_API int gpk_sparse_propagate_mm(gpk_handle h, int var_includes_noise, const double* x0, int x0_rows, const double* U, int u_rows,
+                                    const double* lin, const double* Sigma0, int s_rows, const double* Q, int R, int H,
+                                    double* traj, double* Sigma, double* mean, double* cov, double* xcov);
+GPK_API int gpk_sparse_propagate_mm_multi(gpk_handle h, int B, const gpk_handle* models, int var_includes_noise, int nx,
+                                          const int* coord, const double* in_shift, const double* in_scale,
+                                          const double* out_shift, const double* out_scale, const double* x0, int x0_rows,
+                                          const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows,
+                                          const double* Q, int R, int H, double* traj, double* Sigma, double* mean, double* cov,
+                                          double* xcov);
 
 #ifdef __cplusplus
 }

@@ -200,6 +200,14 @@ SIGNATURES["gpk_propagate_mm_host_multi"] = (_int, list(SIGNATURES["gpk_propagat
 SIGNATURES["gpk_moments_host"] = (_int, SIGNATURES["gpk_propagate_host"][1][:17] + [_int, _vp, _vp, _int, _vp, _vp, _vp])
 SIGNATURES["gpk_moments_host_multi"] = (_int, SIGNATURES["gpk_propagate_host_multi"][1][:17]
                                         + [_int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp])
+# ... on the sparse posteriors (the engine above on (Z, alpha_u, Q)): the chains take the arguments of gpk_sparse_propagate[_multi]
+# with (mean, cov, xcov) as the stage outputs; the query entries: var_includes_noise, nx, [in_shift, in_scale, out_shift,
+# out_scale,] Xq, Sq, M, mean, cov, xcov
+SIGNATURES["gpk_sparse_propagate_mm"] = (_int, list(SIGNATURES["gpk_sparse_propagate"][1]))
+SIGNATURES["gpk_sparse_propagate_mm_multi"] = (_int, list(SIGNATURES["gpk_sparse_propagate_multi"][1]))
+SIGNATURES["gpk_sparse_moments"] = (_int, [_vp, _int, _int, _dp, _dp, _int, _dp, _dp, _dp])
+SIGNATURES["gpk_sparse_moments_multi"] = (_int, [_vp, _int, C.POINTER(_vp), _int, _int, _dp, _dp, _dp, _dp, _dp, _dp, _int, _dp, _dp,
+                                                 _dp])
 
 _lib = None
 

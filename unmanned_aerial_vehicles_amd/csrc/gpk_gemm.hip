@@ -854,12 +854,7 @@ int launch(gpk_handle h, const GemmArgs& g) {
     const int dr = (g.ke0 < 0 ? 0 : g.ke_row) - g.kb_row, dc = (g.ke0 < 0 ? 0 : g.ke_col) - g.kb_col;
     const long long total = ntiles * ny;
     if (h->gemm_balanced && (dr != 0 || (dc != 0 && !g.lower_only)) && total <= h->gemm_balanced_max_tiles) {
-      if (h->cus <= 0) {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus <= 0) cus = 256;
-        h->cus = cus;
-      }
-      const long long resident = (long long)h->cus * (TS == 128 ? 2 : TS == 64 ? 4 : 8) / 64 * 64;
+      const long long resident = (long long)gpk_cus(h) * (TS == 128 ? 2 : TS == 64 ? 4 : 8) / 64 * 64;
       p.balanced = 1;
       p.bal_wg = (int)(total < resident ? (total + 63) / 64 * 64 : resident);
       p.bal_tiles = (int)ntiles;

@@ -42,7 +42,9 @@ struct gpk_context {
                                  // with 1024 the products of N >= 4096 lose
   int gemm_balanced = 1;         // launches whose tiles differ in k-range: balanced persistent tile schedule
   long long gemm_balanced_max_tiles = 32768;   // ... up to this many tiles per launch (all problems of a batch)
-  int cus = 0;                   // compute units of the device (read once)
+  int cus = 0;                   // compute units of the device (read once: gpk_cus)
+  int moments_query_groups = 0;  // moment matching's pair launch: groups of queries as a grid dimension (0: as many as bring the launch to
+                                 // two workgroups per CU, gpk_moments.hip; n >= 1: at most n, so 1 is the launch without the split)
   int trtri_levels = 1;      // gpk_trtri: one batched launch per level for power-of-two tile counts
   int trsm256 = 1;           // potrf: fused 256-wide base of the triangular solve
   int small_path = 1;        // gpk_predict_host: two-launch small-batch kernels (option small_path = 0 disables)
@@ -119,6 +121,15 @@ struct gpk_context {
   } while (0)
 
 int gpk_scratch(gpk_handle h, size_t bytes, void** out);
+// compute units of the handle's device, read once (256 where the runtime does not say)
+inline int gpk_cus(gpk_handle h) {
+  if (h->cus <= 0) {
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus <= 0) cus = 256;
+    h->cus = cus;
+  }
+  return h->cus;
+}
 
 // ---- one-launch tile Cholesky (gpk_ptile.hip) -----------------------------------------
 constexpr size_t GPK_PTILE_CTRL_INTS = 16 + 8 * 512 + 1024 + 10 * 8 * 512;   // ticket, abort, padding; GPK_MAX_BATCH x (Np / 128 <= 512) row
@@ -443,6 +454,14 @@ int gpk_horizon_finish(gpk_handle h, const HorizonBlock& b, const Horizon& z, st
 // k: nx, D, NO, the strides, model_of, the scaler, ystd2 and the noise filled in by the entry; `who` prefixes
 // the messages.
 int gpk_propagate_run(gpk_handle h, const std::string& who, const ServeModels& m, PropK k, const Horizon& z);
+// Exact moment matching (gpk_moments.hip) on the models m - X, alpha and, as W, the matrix that stands for K^-1 in E[v] (lower
+// tiles as gpk_wtw writes them, ldw its leading dimension): K^-1 of an exact model, Q = Kuu^-1 - Sigma~ of a sparse one on its
+// inducing inputs (gpk_sparse.hip).  Every check of m and of the queries or the horizon (GPK_BAD_ARG before anything is launched),
+// then five launches per batch of M <= 32 Gaussian queries: gpk_mm_query one upload, three downloads and one synchronisation;
+// gpk_mm_chain the horizon on the skeleton above, 5 H launches and one synchronisation (z.cov, z.xcov: the stage outputs).
+int gpk_mm_query(gpk_handle h, const std::string& who, const HostModels& m, const double* Xq, const double* Sq, int M, double* mean,
+                 double* cov, double* xcov);
+int gpk_mm_chain(gpk_handle h, const std::string& who, const HostModels& m, const Horizon& z);
 // ... as one-call serving (gpk_serve.hip): host queries in, host results out through the pinned, mapped block, one
 // synchronisation.  small: the launches above (gpk_serve_predict: 33..64 queries the same twice); otherwise, F = 1 only, the
 // general chain, which also reads m.Np / m.ldw only with the inverse factor.

@@ -16,7 +16,9 @@
 //   moments_row_*_kernel     the N rows: l_i and the workgroups' shares of E[mu] and sum alpha l nu;  lam_i, w_i per (pair, side)
 //   moments_pair_kernel<P>   the N x N pairs in 64 x 64 tiles (a == b: the lower tiles, the others counted twice): every K^-1 and alpha
 //                            tile is read ONCE and serves all R queries; the tile's sums are added in a fixed order in LDS and then to
-//                            the workgroup's own slot - no atomics; workgroup g owns tiles g, g + G, ..
+//                            the workgroup's own slot - no atomics; workgroup g owns tiles g, g + G, ..; where G U leaves the
+//                            card idle (the sparse sizes, small exact models) the R queries are cut into groups, a third grid
+//                            dimension: workgroup (g, u, zq) walks the same tiles for its own queries and re-reads the tile
 //   moments_finish_kernel    one workgroup per query: the slots added in workgroup order, V, the raw units and - in the chain - the
 //                            stage:  x+ = x + lin q + E E[mu],  Sigma+ = A0 Sigma A0^T + A0 Cx E^T + E Cx^T A0^T + E V E^T + Q  with
 //                            A0 = I + lin[:, :nx] and Cx the state rows of the raw input-output covariance; the lower triangle is formed
@@ -254,14 +256,21 @@ __global__ __launch_bounds__(256) void moments_row_pair_kernel(MomK k, const dou
   o[16] = k.lsf2[m] - 0.5 * e0 + 0.5 * ww;
 }
 
-// grid (G, U), 256 threads: thread (ty, tx) = (tid >> 4, tid & 15) holds the pairs (ty + 16 ii, tx + 16 jj) of a tile.
+// grid (G, U, NQ), 256 threads: thread (ty, tx) = (tid >> 4, tid & 15) holds the pairs (ty + 16 ii, tx + 16 jj) of a tile.
 // part[((u G + g) R + r) NV + v], NV = 1 + P (P + 1) / 2: v = 0 the K^-1 sum (a == b), v = 1 + p (p + 1) / 2 + q the alpha sums.
-template <int P>
+// Workgroup (g, u, zq) serves the queries [zq R / NQ, (zq + 1) R / NQ) on the tiles g, g + G, ..: a slot (g, r) is written by one
+// workgroup, over the same tiles in the same order whatever NQ is - the split changes no bit; it costs one more read of the
+// tile of K^-1 (of Q, for a sparse model) and of the alpha tiles per group, outside the query loop as before.  SPLIT = false is
+// the kernel without the dimension (NQ = 1: grid (G, U), every query), instruction for instruction what the large exact shapes
+// have always run - measured, the general loop bounds alone cost those shapes 1 % (profiles/r28_exp_sparse_moments.log).
+template <int P, bool SPLIT>
 __global__ __launch_bounds__(256) void moments_pair_kernel(MomK k, int R, const double* __restrict__ rowq,
                                                            const double* __restrict__ cl, double* part) {
   constexpr int NV = 1 + P * (P + 1) / 2;
   __shared__ double sA[MM_TILE][P], sB[MM_TILE][P], sWa[MM_TILE][MM_WS], sWb[MM_TILE][MM_WS], red[MM_CH][16 * 17], red2[MM_CH][16];
   const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4, u = blockIdx.y, g = blockIdx.x, G_ = gridDim.x, nx = k.nx;
+  const int r0 = SPLIT ? (int)(blockIdx.z * (unsigned)R / gridDim.z) : 0;      // (R, NQ <= 32)
+  const int r1 = SPLIT ? (int)((blockIdx.z + 1) * (unsigned)R / gridDim.z) : R;
   int a, b;
   pair_of(u, a, b);
   const bool same = a == b;
@@ -300,7 +309,7 @@ __global__ __launch_bounds__(256) void moments_pair_kernel(MomK k, int R, const 
       sA[row][p] = i0 + row < N ? k.alpha[a][(i0 + row) * P + p] : 0.0;
       sB[row][p] = j0 + row < N ? k.alpha[b][(j0 + row) * P + p] : 0.0;
     }
-    for (int r = 0; r < R; ++r) {
+    for (int r = r0; r < r1; ++r) {
       __syncthreads();
       for (int e = tid; e < MM_TILE * MM_WS; e += 256) {
         const int row = e / MM_WS;
@@ -485,16 +494,26 @@ __global__ __launch_bounds__(256) void moments_finish_kernel(MomK k, StageView v
 // The device work area of one batch of R queries, carved from `base`.
 struct MomWork {
   double *Sz, *Bm, *cm, *G, *cl, *rowq, *rowpart, *pairpart;
-  int nrw, G_, NV;
+  int nrw, G_, NV, NQ;
   size_t doubles;
 };
-MomWork mm_work(const MomK& k, int R, double* base) {
+// groups of queries of the pair launch: as many as bring G U workgroups to two per CU and no more, at most R; one from G U = 512 on
+// (the large exact shapes: the launch as it always was).  Option moments_query_groups = n >= 1 caps the count (1: no split).
+int mm_query_groups(gpk_handle h, long long wgs, int R) {
+  if (wgs >= MM_MAXG) return 1;
+  long long nq = 2ll * gpk_cus(h) / wgs;
+  if (h->moments_query_groups >= 1 && nq > h->moments_query_groups) nq = h->moments_query_groups;
+  return (int)(nq < 1 ? 1 : nq > R ? R : nq);
+}
+
+MomWork mm_work(gpk_handle h, const MomK& k, int R, double* base) {
   MomWork w{};
   const int nt = (int)((k.N + MM_TILE - 1) / MM_TILE);
   const long long lower = (long long)nt * (nt + 1) / 2;
   w.nrw = (int)((k.N + MM_ROWS - 1) / MM_ROWS);
   w.G_ = (int)(lower < MM_MAXG ? lower : MM_MAXG);
   w.NV = 1 + k.P * (k.P + 1) / 2;
+  w.NQ = mm_query_groups(h, (long long)w.G_ * k.U, R);
   size_t at = 0;
   auto take = [&](size_t n) { double* p = base ? base + at : nullptr; at += n; return p; };
   w.Sz = take((size_t)R * 256);
@@ -511,8 +530,12 @@ MomWork mm_work(const MomK& k, int R, double* base) {
 
 template <int P>
 void mm_pair_launch(gpk_handle h, const MomK& k, const MomWork& w, int R) {
-  hipLaunchKernelGGL(moments_pair_kernel<P>, dim3((unsigned)w.G_, (unsigned)k.U), dim3(256), 0, h->stream, k, R, (const double*)w.rowq,
-                     (const double*)w.cl, w.pairpart);
+  if (w.NQ > 1)
+    hipLaunchKernelGGL((moments_pair_kernel<P, true>), dim3((unsigned)w.G_, (unsigned)k.U, (unsigned)w.NQ), dim3(256), 0, h->stream, k,
+                       R, (const double*)w.rowq, (const double*)w.cl, w.pairpart);
+  else
+    hipLaunchKernelGGL((moments_pair_kernel<P, false>), dim3((unsigned)w.G_, (unsigned)k.U), dim3(256), 0, h->stream, k, R,
+                       (const double*)w.rowq, (const double*)w.cl, w.pairpart);
 }
 
 // The four launches ahead of the finishing one: d_q (R x D scaled queries) and d_S (R x nx x nx raw covariances) on the device.
@@ -544,7 +567,7 @@ void mm_finish(gpk_handle h, const MomK& k, const MomWork& w, const StageView& v
 int mm_models(gpk_handle h, const std::string& who, const HostModels& m, bool chain, MomK& k) {
   GPK_REQUIRE(h, h->batch == 1, who + "not available in batched mode");
   GPK_REQUIRE(h, m.X && m.alpha && m.ls && m.sf2 && m.y_mean && m.y_std && m.kss, who + "null pointer");
-  GPK_REQUIRE(h, m.W, who + "null K^-1 (gpk_wtw of the model's inverse factor)");
+  GPK_REQUIRE(h, m.W, who + "null K^-1 or Q (the lower tiles, as gpk_wtw writes them)");
   GPK_REQUIRE(h, m.B >= 1 && m.B <= GPK_SMALL_MAX_MODELS, who + "1..8 models");
   GPK_REQUIRE(h, m.P >= 1 && m.P <= GPK_MAX_P && m.P <= 16 && (m.B == 1 || m.P == 1), who + "P must be in [1, 16]");
   GPK_REQUIRE(h, m.D >= 1 && m.D <= GPK_PROP_MAX_D && m.nx >= 1 && m.nx <= GPK_PROP_MAX_NX && m.nx <= m.D, who + "needs 1 <= nx <= D <= 16");
@@ -556,7 +579,7 @@ int mm_models(gpk_handle h, const std::string& who, const HostModels& m, bool ch
   GPK_REQUIRE(h, (m.in_shift == nullptr) == (m.in_scale == nullptr), who + "in_shift and in_scale go together");
   const int NO = m.B * m.P;
   for (int b = 0; b < m.B; ++b) GPK_REQUIRE(h, m.X[b] && m.alpha[b], who + "null model pointer");
-  for (int b = 0; b < m.B; ++b) GPK_REQUIRE(h, m.W[b], who + "null K^-1 (gpk_wtw of the model's inverse factor)");
+  for (int b = 0; b < m.B; ++b) GPK_REQUIRE(h, m.W[b], who + "null K^-1 or Q (the lower tiles, as gpk_wtw writes them)");
   GPK_REQUIRE(h, gpk_finite(m.ls, (size_t)m.B * m.D) && gpk_finite(m.sf2, m.B) && gpk_finite(m.y_mean, NO) && gpk_finite(m.y_std, NO),
               who + "ls, sf2, y_mean and y_std must not contain NaN or infinity");
   for (int i = 0; i < m.B * m.D; ++i) GPK_REQUIRE(h, m.ls[i] > 0.0, who + "length-scales must be positive");
@@ -597,9 +620,11 @@ int mm_models(gpk_handle h, const std::string& who, const HostModels& m, bool ch
   return GPK_OK;
 }
 
+}  // namespace
+
 // M <= 32 Gaussian queries: one upload [z | S], five launches, three downloads, one synchronisation.
-int mm_query(gpk_handle h, const std::string& who, const HostModels& m, const double* Xq, const double* Sq, int M, double* mean,
-             double* cov, double* xcov) {
+int gpk_mm_query(gpk_handle h, const std::string& who, const HostModels& m, const double* Xq, const double* Sq, int M, double* mean,
+                 double* cov, double* xcov) {
   if (!h) return GPK_BAD_ARG;
   MomK k;
   GPK_TRY(mm_models(h, who, m, false, k));
@@ -610,7 +635,7 @@ int mm_query(gpk_handle h, const std::string& who, const HostModels& m, const do
   GPK_REQUIRE(h, gpk_finite(Xq, n_q), who + "the queries must not contain NaN or infinity");
   GPK_REQUIRE(h, !Sq || gpk_finite(Sq, n_s), who + "the covariances must not contain NaN or infinity");
   const size_t n_om = (size_t)M * NO, n_oc = n_om * NO, n_ox = n_om * D;
-  const MomWork sizes = mm_work(k, M, nullptr);
+  const MomWork sizes = mm_work(h, k, M, nullptr);
   void* ws = nullptr;
   GPK_TRY(gpk_scratch(h, (n_q + n_s + n_om + n_oc + n_ox + sizes.doubles) * sizeof(double), &ws));
   double* d_q = (double*)ws;
@@ -618,7 +643,7 @@ int mm_query(gpk_handle h, const std::string& who, const HostModels& m, const do
   double* d_om = d_S + n_s;
   double* d_oc = d_om + n_om;
   double* d_ox = d_oc + n_oc;
-  const MomWork w = mm_work(k, M, d_ox + n_ox);
+  const MomWork w = mm_work(h, k, M, d_ox + n_ox);
   std::vector<double> host(n_q + n_s, 0.0);
   for (int r = 0; r < M; ++r) {
     for (int d = 0; d < D; ++d) {
@@ -645,7 +670,7 @@ int mm_query(gpk_handle h, const std::string& who, const HostModels& m, const do
 
 // The horizon chain on the skeleton of gpk_propagate.hip: one upload (the head), 5 H launches - the finishing one composes the
 // stage and is what GPK_TIMED_PROPAGATE brackets - up to five downloads, one synchronisation.
-int mm_chain(gpk_handle h, const std::string& who, const HostModels& m, const Horizon& z) {
+int gpk_mm_chain(gpk_handle h, const std::string& who, const HostModels& m, const Horizon& z) {
   if (!h) return GPK_BAD_ARG;
   MomK k;
   GPK_TRY(mm_models(h, who, m, true, k));
@@ -657,7 +682,7 @@ int mm_chain(gpk_handle h, const std::string& who, const HostModels& m, const Ho
   GPK_TRY(gpk_horizon_carve(h, b, [&] {
     b.head();
     b.outputs(n_om, z.mean, n_om * k.NO, z.cov, n_om * k.D, z.xcov);
-    w = mm_work(k, R, b.base ? b.base + b.at : nullptr);
+    w = mm_work(h, k, R, b.base ? b.base + b.at : nullptr);
     b.take(w.doubles);
   }));
   std::vector<double> host(b.n_head(), 0.0);
@@ -673,8 +698,6 @@ int mm_chain(gpk_handle h, const std::string& who, const HostModels& m, const Ho
   return gpk_horizon_finish(h, b, z, {});
 }
 
-}  // namespace
-
 extern "C" int gpk_moments_host(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls, double sf2,
                                 const double* y_mean, const double* y_std, const double* Kinv, int64_t Np, int64_t ldk, double kss,
                                 double floor_, int var_includes_noise, double noise, int nx, const double* Xq, const double* Sq, int M,
@@ -684,7 +707,7 @@ extern "C" int gpk_moments_host(gpk_handle h, const double* X, const double* alp
                     nullptr, nullptr, nullptr};
   GPK_REQUIRE(h, X && alpha, "moments_host: null pointer");
   GPK_REQUIRE(h, Kinv, "moments_host: null K^-1 (gpk_wtw of the model's inverse factor)");
-  return mm_query(h, "moments_host: ", m, Xq, Sq, M, mean, cov, xcov);
+  return gpk_mm_query(h, "moments_host: ", m, Xq, Sq, M, mean, cov, xcov);
 }
 
 extern "C" int gpk_moments_host_multi(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D,
@@ -696,7 +719,7 @@ extern "C" int gpk_moments_host_multi(gpk_handle h, int B, const double* const* 
   if (!h) return GPK_BAD_ARG;
   const HostModels m{B, 1, X, alpha, N, D, ls, sf2, y_mean, y_std, Kinv, Np, ldk, kss, floor_, var_includes_noise, noise, nx,
                     nullptr, in_shift, in_scale};
-  return mm_query(h, "moments_host_multi: ", m, Xq, Sq, M, mean, cov, xcov);
+  return gpk_mm_query(h, "moments_host_multi: ", m, Xq, Sq, M, mean, cov, xcov);
 }
 
 extern "C" int gpk_propagate_mm_host(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
@@ -712,7 +735,7 @@ extern "C" int gpk_propagate_mm_host(gpk_handle h, const double* X, const double
   GPK_REQUIRE(h, P >= 1 && P <= D, "propagate_mm_host: the state dimension P must be in [1, 16] and must not exceed D");
   Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean};
   z.cov = cov; z.xcov = xcov;
-  return mm_chain(h, "propagate_mm_host: ", m, z);
+  return gpk_mm_chain(h, "propagate_mm_host: ", m, z);
 }
 
 extern "C" int gpk_propagate_mm_host_multi(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D,
@@ -729,5 +752,5 @@ extern "C" int gpk_propagate_mm_host_multi(gpk_handle h, int B, const double* co
                     in_shift, in_scale};
   Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean};
   z.cov = cov; z.xcov = xcov;
-  return mm_chain(h, "propagate_mm_host_multi: ", m, z);
+  return gpk_mm_chain(h, "propagate_mm_host_multi: ", m, z);
 }

@@ -30,7 +30,7 @@
 //                        variance gradients kept in the block, then per stage, backwards, the Hessian-vector launch
 //                        (small_hvp_kernel, gpk_small.hip) and propagate_adjoint_kernel below; the seeds ride behind the head in
 //                        the one upload, three more downloads (propagate_run_grad; 6)
-//   moment               (gpk_moments.hip, mm_chain) the four moment launches and moments_finish_kernel as the composing launch,
+//   moment               (gpk_moments.hip, gpk_mm_chain) the four moment launches and moments_finish_kernel as the composing launch,
 //                        the moment work area in the block (5)
 #include "gpk_horizon.h"
 

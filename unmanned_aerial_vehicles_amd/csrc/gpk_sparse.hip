@@ -517,6 +517,10 @@ struct gpk_sparse {
   // coefficient matrix of the row pass ((mp + 128) x mp) and the per-row sums of sparse_dots_kernel (m x 4)
   // gradient with respect to Z: the column pass' sums (mp x 17), then the Kuu term (m x 16)
   gpk_dev<double> hX, hY, Cm, dots, zg;
+  // moment matching: Q = Wuu^T Wuu - WSigma^T WSigma (mp x mp, the lower tiles), formed on first use after an assembly and
+  // dropped by the next one (sparse_moment_matrix); a buffer of its own - the gradient and the path set-up reuse the others
+  gpk_dev<double> Qm;
+  bool q_ready = false;
   gpk_dev<void> work;
 };
 
@@ -640,6 +644,7 @@ int sparse_assemble(gpk_handle h, gpk_sparse* s, int* info) {
   const double is2 = 1.0 / s->sigma2;
   *info = 0;
   s->finalized = false;
+  s->q_ready = false;      // (Q belongs to the factors this assembly overwrites)
   // Luu Luu^T = Kuu + jitter_uu I (identity in the padding), Wuu = Luu^-1
   GPK_TRY(gpk_gram(h, GPK_F64, s->Z, s->m, s->D, s->ls, s->sf2, s->jitter_uu, s->Kuu, mp));
   int rc = gpk_potrf(h, s->Kuu, mp, mp, s->winv, info);
@@ -1513,6 +1518,168 @@ extern "C" int gpk_sparse_propagate_grad_multi(gpk_handle h, int B, const gpk_ha
   return sparse_propagate_multi_any(h, "sparse_propagate_grad_multi",
                                     {B, models, var_includes_noise, nx, coord, in_shift, in_scale, out_shift, out_scale},
                                     Horizon{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean, var, jac, 1, nullptr, &g});
+}
+
+// ---- exact moment matching (K11) on the sparse posteriors: the engine of gpk_moments.hip on (Z, alpha_u, Q) --------------------
+// The sparse posterior is the exact model's form over the m inducing inputs: mean weights alpha_u, and in the variance
+//   Q = Wuu^T Wuu - WSigma^T WSigma  ( = (Kuu + jitter_uu I)^-1 - Sigma~ )
+// where K^-1 stands, so E[v_b] = kss_b - sum_ij Q_ij L^bb_ij and every other closed form is unchanged.
+namespace {
+
+// Q (i, j) -= T (i, j) over the lower triangle j <= i < mp.  grid (ceil(mp / 256), mp), 256 threads.
+__global__ __launch_bounds__(256) void sparse_q_sub_kernel(double* __restrict__ Q, const double* __restrict__ T, long long mp) {
+  const long long i = blockIdx.y, j = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i < mp && j <= i) Q[i * mp + j] -= T[i * mp + j];
+}
+
+// Q of the assembled model s, formed on first use: two gpk_wtw products (the lower tiles, ld = mp) and the subtraction, on h's
+// stream, which is drained - the next call may come through another serving handle.  Rows and columns >= m hold I - I = 0 and
+// are masked by the pair kernel anyway.
+int sparse_moment_matrix(gpk_handle h, gpk_sparse* s) {
+  if (s->q_ready) return GPK_OK;
+  const int64_t mp = s->mp;
+  const size_t mm = (size_t)mp * mp;
+  if (!s->Qm) GPK_TRY(s->Qm.alloc(h, mm));
+  gpk_dev<double> T;
+  GPK_TRY(T.alloc(h, mm));
+  GPK_TRY(gpk_wtw(h, s->Wuu, mp, mp, s->Qm, mp));
+  GPK_TRY(gpk_wtw(h, s->WS, mp, mp, T, mp));
+  hipLaunchKernelGGL(sparse_q_sub_kernel, dim3((unsigned)((mp + 255) / 256), (unsigned)mp), dim3(256), 0, h->stream, s->Qm.p,
+                     (const double*)T.p, (long long)mp);
+  GPK_LAUNCH_CHECK(h);
+  GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));      // (T leaves scope)
+  s->q_ready = true;
+  return GPK_OK;
+}
+
+// What the four entries share: the handle rules of the sparse propagate siblings, then the models taken apart as the engine's
+// description (sm.m, which points into sm) - kss = sf2 (+ the noise level), floor 0 and no separate noise term, as the exact
+// Python callers pass them; the output scaler folded into y_mean / y_std.  models null: the object of h itself, P outputs.
+// check(D): the entry's own refusals - the engine's, made here as well so that a refused call does not even form Q.
+struct SparseMoments {
+  SparseServe sv;
+  const double* Qp[GPK_SMALL_MAX_MODELS];
+  HostModels m;
+};
+
+template <class Check>
+int sparse_moments_models(gpk_handle h, const std::string& who, int B, const gpk_handle* models, int var_includes_noise, int nx,
+                          const int* coord, const double* in_shift, const double* in_scale, const double* out_shift,
+                          const double* out_scale, bool chain, Check check, SparseMoments& sm) {
+  GPK_REQUIRE(h, h->batch == 1, who + "not available in batched mode");
+  GPK_REQUIRE(h, h->small_path, who + "the small-batch path is switched off (option small_path)");
+  gpk_sparse* list[GPK_SMALL_MAX_MODELS];
+  if (models) {
+    GPK_REQUIRE(h, B >= 1 && B <= GPK_SMALL_MAX_MODELS, who + "1..8 models");
+    GPK_REQUIRE(h, (in_shift == nullptr) == (in_scale == nullptr), who + "in_shift and in_scale go together");
+    GPK_REQUIRE(h, (out_shift == nullptr) == (out_scale == nullptr), who + "out_shift and out_scale go together");
+    GPK_TRY(sparse_batch_models(h, who.substr(0, who.size() - 2), B, models, list));
+  } else {
+    list[0] = h->sparse;
+    GPK_REQUIRE(h, list[0] && list[0]->finalized, who + "no finalised sparse model (call gpk_sparse_finalize first)");
+  }
+  const int D = list[0]->D, NO = B * list[0]->P;
+  GPK_REQUIRE(h, D >= 1 && D <= GPK_PROP_MAX_D && nx >= 1 && nx <= GPK_PROP_MAX_NX && nx <= D, who + "needs 1 <= nx <= D <= 16");
+  GPK_REQUIRE(h, !chain || nx >= NO, who + "the state dimension nx must not be below the number of outputs");
+  GPK_REQUIRE(h, list[0]->mp <= GPK_SMALL_MAX_NP, who + "needs m <= 16384");
+  if (chain && coord) {
+    bool seen[GPK_PROP_MAX_NX] = {false};
+    for (int b = 0; b < B; ++b) {
+      GPK_REQUIRE(h, coord[b] >= 0 && coord[b] < nx, who + "coord must be in [0, nx)");
+      GPK_REQUIRE(h, !seen[coord[b]], who + "coord must be distinct");
+      seen[coord[b]] = true;
+    }
+  }
+  if (in_shift) {
+    GPK_REQUIRE(h, gpk_finite(in_shift, D) && gpk_finite(in_scale, D), who + "the input scaler must not contain NaN or infinity");
+    for (int d = 0; d < D; ++d) GPK_REQUIRE(h, in_scale[d] != 0.0, who + "in_scale must be non-zero");
+  }
+  if (out_shift)
+    GPK_REQUIRE(h, gpk_finite(out_shift, B) && gpk_finite(out_scale, B), who + "the output scaler must not contain NaN or infinity");
+  GPK_TRY(check(D));
+  GPK_CHECK_HIP(h, hipSetDevice(h->device));
+  sm.sv.fill(B, list, var_includes_noise);
+  for (int b = 0; b < B; ++b) {
+    GPK_TRY(sparse_moment_matrix(h, list[b]));
+    sm.Qp[b] = list[b]->Qm;
+    if (out_shift) {
+      sm.sv.y_mean[b] = out_shift[b] + out_scale[b] * sm.sv.y_mean[b];
+      sm.sv.y_std[b] = out_scale[b] * sm.sv.y_std[b];
+    }
+  }
+  const SparseServe& sv = sm.sv;
+  sm.m = HostModels{B, sv.P, sv.Z, sv.alpha, sv.m, D, sv.ls, sv.sf2, sv.y_mean, sv.y_std, sm.Qp, sv.mp, sv.mp, sv.kss, 0.0, 0, nullptr,
+                    nx, coord, in_shift, in_scale};
+  return GPK_OK;
+}
+
+// the query entries' own refusals (those of gpk_mm_query, made before Q is formed)
+int sparse_moments_query_check(gpk_handle h, const std::string& who, int D, int nx, const double* Xq, const double* Sq, int M,
+                               const double* mean, const double* cov, const double* xcov) {
+  GPK_REQUIRE(h, M >= 1 && M <= GPK_SMALL_MAX_M, who + "M must be in [1, 32]");
+  GPK_REQUIRE(h, Xq && mean && cov && xcov, who + "null pointer");
+  GPK_REQUIRE(h, gpk_finite(Xq, (size_t)M * D), who + "the queries must not contain NaN or infinity");
+  GPK_REQUIRE(h, !Sq || gpk_finite(Sq, (size_t)M * nx * nx), who + "the covariances must not contain NaN or infinity");
+  return GPK_OK;
+}
+
+}  // namespace
+
+extern "C" int gpk_sparse_moments(gpk_handle h, int var_includes_noise, int nx, const double* Xq, const double* Sq, int M,
+                                  double* mean, double* cov, double* xcov) {
+  if (!h) return GPK_BAD_ARG;
+  const std::string who("sparse_moments: ");
+  SparseMoments sm;
+  GPK_TRY(sparse_moments_models(h, who, 1, nullptr, var_includes_noise, nx, nullptr, nullptr, nullptr, nullptr, nullptr, false,
+                                [&](int D) { return sparse_moments_query_check(h, who, D, nx, Xq, Sq, M, mean, cov, xcov); }, sm));
+  return gpk_mm_query(h, who, sm.m, Xq, Sq, M, mean, cov, xcov);
+}
+
+extern "C" int gpk_sparse_moments_multi(gpk_handle h, int B, const gpk_handle* models, int var_includes_noise, int nx,
+                                        const double* in_shift, const double* in_scale, const double* out_shift,
+                                        const double* out_scale, const double* Xq, const double* Sq, int M, double* mean,
+                                        double* cov, double* xcov) {
+  if (!h) return GPK_BAD_ARG;
+  const std::string who("sparse_moments_multi: ");
+  GPK_REQUIRE(h, models, who + "null pointer");
+  SparseMoments sm;
+  GPK_TRY(sparse_moments_models(h, who, B, models, var_includes_noise, nx, nullptr, in_shift, in_scale, out_shift, out_scale, false,
+                                [&](int D) { return sparse_moments_query_check(h, who, D, nx, Xq, Sq, M, mean, cov, xcov); }, sm));
+  return gpk_mm_query(h, who, sm.m, Xq, Sq, M, mean, cov, xcov);
+}
+
+extern "C" int gpk_sparse_propagate_mm(gpk_handle h, int var_includes_noise, const double* x0, int x0_rows, const double* U,
+                                       int u_rows, const double* lin, const double* Sigma0, int s_rows, const double* Q, int R, int H,
+                                       double* traj, double* Sigma, double* mean, double* cov, double* xcov) {
+  if (!h) return GPK_BAD_ARG;
+  const std::string who("sparse_propagate_mm: ");
+  Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean};
+  z.cov = cov; z.xcov = xcov;
+  gpk_sparse* s = h->sparse;
+  GPK_REQUIRE(h, s && s->finalized, who + "no finalised sparse model (call gpk_sparse_finalize first)");
+  const int P = s->P;
+  GPK_REQUIRE(h, P >= 1 && P <= GPK_PROP_MAX_NX && P <= s->D, who + "the state dimension P must be in [1, 16] and must not exceed D");
+  SparseMoments sm;
+  GPK_TRY(sparse_moments_models(h, who, 1, nullptr, var_includes_noise, P, nullptr, nullptr, nullptr, nullptr, nullptr, true,
+                                [&](int D) { return gpk_horizon_check(h, who, P, D, z); }, sm));
+  return gpk_mm_chain(h, who, sm.m, z);
+}
+
+extern "C" int gpk_sparse_propagate_mm_multi(gpk_handle h, int B, const gpk_handle* models, int var_includes_noise, int nx,
+                                             const int* coord, const double* in_shift, const double* in_scale,
+                                             const double* out_shift, const double* out_scale, const double* x0, int x0_rows,
+                                             const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows,
+                                             const double* Q, int R, int H, double* traj, double* Sigma, double* mean, double* cov,
+                                             double* xcov) {
+  if (!h) return GPK_BAD_ARG;
+  const std::string who("sparse_propagate_mm_multi: ");
+  GPK_REQUIRE(h, models && coord, who + "null pointer");
+  Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean};
+  z.cov = cov; z.xcov = xcov;
+  SparseMoments sm;
+  GPK_TRY(sparse_moments_models(h, who, B, models, var_includes_noise, nx, coord, in_shift, in_scale, out_shift, out_scale, true,
+                                [&](int D) { return gpk_horizon_check(h, who, nx, D, z); }, sm));
+  return gpk_mm_chain(h, who, sm.m, z);
 }
 
 extern "C" int gpk_sparse_export(gpk_handle h, int64_t* m, int* D, int* P, int* n_ls, double* Z, double* G, double* g, double* yy,

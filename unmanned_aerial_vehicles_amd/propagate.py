@@ -43,8 +43,9 @@ covariance; closed forms for RBF kernels):
 
 with A0 = I + lin[:, :nx], E the selector of `coord` and Cx the state rows of the input-output covariance (to first order Cx =
 Sigma_h J_x^T, which gives the recursion at the top).  One C call per horizon (`gpk_propagate_mm_host[_multi]`: five launches per
-stage, one synchronisation); `host_loop_moments` is the same recursion over a class's `predict_moments`.  The sparse classes and
-`propagate_gradient` refuse it (`refuse_moment`).
+stage, one synchronisation); `host_loop_moments` is the same recursion over a class's `predict_moments`.  The sparse classes
+serve it as `predict_moments` / `propagate_moments` (the engine on (Z, alpha_u, Q = Kuu^-1 - Sigma~), `gpk_sparse_propagate_mm[_multi]`);
+their `propagate(method="moment")` and every `propagate_gradient` refuse it (`refuse_moment`).
 """
 from __future__ import annotations
 
@@ -212,12 +213,13 @@ def check_method(method, order=1, what="propagate", Sigma0=None, process_noise=N
 
 
 def refuse_moment(method, what):
-    """The classes and calls without moment matching (the sparse models, the gradient chain): ValueError naming them."""
+    """The calls without method="moment" (`propagate` of the sparse classes, which spell it `propagate_moments`; the gradient
+    chain of every class): ValueError naming them."""
     if method not in METHODS:
         raise ValueError(f"method must be 'linear' or 'moment', got {method!r}")
     if method == "moment":
-        raise ValueError(f"method='moment' is not supported by {what}: exact moment matching needs the inverse Gram matrix of an "
-                         "exact RBF model and has no adjoint chain")
+        raise ValueError(f"method='moment' is not supported by {what}: the sparse classes serve exact moment matching through "
+                         "predict_moments / propagate_moments, and moment matching has no adjoint chain")
 
 
 def check_psd(S, what):
@@ -387,6 +389,16 @@ def wrapper_route(model):
     `propagate_ok()` holds, otherwise "auto" (the exact classes choose by themselves; the sparse ones run the host loop)."""
     ok = getattr(model, "propagate_ok", None)
     return "chain" if callable(ok) and ok() else "auto"
+
+
+def model_horizon(model, x0, U, lin, order=1, method="linear", **kw):
+    """The horizon a control-loop wrapper asks of its model -> (traj, Sigma).  method="moment": `propagate_moments` of a sparse
+    class (its one-call chain; the model is assembled, and its Q formed, from the rows it has taken so far), `propagate(method=
+    "moment")` of an exact one; otherwise `propagate` on the `wrapper_route`.  kw: Sigma0, process_noise and, for a batch,
+    coord and the scalers."""
+    if method == "moment" and callable(getattr(model, "propagate_moments", None)):
+        return model.propagate_moments(x0, U, lin, **kw)
+    return model.propagate(x0, U, lin, route=wrapper_route(model), order=order, method=method, **kw)
 
 
 def chain_sizes_ok(m, D, nx):

@@ -312,21 +312,21 @@ class SimpleQuadrotorGP:
         lin_x)^T + Q - it never raises into the control loop.  order=2: x_{k+1} also takes tr(H_b Sigma_k) / 2 per output b, H_b
         the state block of the mean's Hessian (`GaussianProcessRegressor.propagate`); any other order: ValueError.
         method="moment": the exact moments of the posterior at the Gaussian query of every stage instead of their linearisation
-        (`GaussianProcessRegressor.propagate(method="moment")`); ValueError with order=2 or a sparse model."""
+        (`GaussianProcessRegressor.propagate(method="moment")`; a SparseGP model: `SparseGP.propagate_moments`, one call for the
+        horizon); ValueError with order=2."""
         from . import propagate as _pg
         order = _pg.check_order(order)
         _pg.check_method(method, order)
-        if method == "moment" and self.is_trained and not hasattr(self.gp_model, "predict_moments"):
-            _pg.refuse_moment(method, type(self.gp_model).__name__)
         state, U, lin, nominal, single = _pg.horizon_inputs(self._nominal_dynamics, state, U_guess, dt)
         R, N = U.shape[0], U.shape[1]
         if not self.is_trained:
             print("GP horizon propagation: the model is not trained - nominal trajectory and covariance")
             return _pg.horizon_layout(*_pg.nominal_horizon(nominal, lin, Sigma0, process_noise), single)
         try:
-            # (a SparseGP model: its one-call chain where it applies, the host loop otherwise)
-            traj, Sigma = self.gp_model.propagate(state, U, lin, Sigma0=Sigma0, process_noise=process_noise,
-                                                  route=_pg.wrapper_route(self.gp_model), order=order, method=method)
+            # (a SparseGP model: its one-call chain where it applies, the host loop otherwise; with method="moment" its
+            # `propagate_moments`)
+            traj, Sigma = _pg.model_horizon(self.gp_model, state, U, lin, order=order, method=method, Sigma0=Sigma0,
+                                            process_noise=process_noise)
             if not (np.isfinite(traj).all() and np.isfinite(Sigma).all()):
                 raise FloatingPointError("non-finite trajectory or covariance")
             self.prediction_count += R * N

@@ -501,7 +501,7 @@ class SparseGP:
         refuses its arguments, with the library's message.  order=2: the second-order mean, on every route (chain:
         `gpk_sparse_propagate2`, four launches per stage, the mean's model (Z, alpha_u) as in `predict_hessian`; the host loop
         contracts `predict_hessian`); the stages gain "corr" (H, R, P).  method: "linear" only - exact moment matching
-        (method="moment") needs the inverse Gram matrix of an exact model: ValueError."""
+        is `propagate_moments` on this class; method="moment" here: ValueError."""
         from . import propagate as _pg
         order = _pg.check_order(order)
         _pg.refuse_moment(method, "SparseGP")
@@ -566,6 +566,68 @@ class SparseGP:
             return mean.reshape(R, P), dmean.reshape(R, P, D), var, dvar.reshape(R, P, D)
 
         return _pg.host_adjoint(stage, lambda q: self.predict_hessian(q)[2], list(range(P)), x0, U, lin, S0, Q, R, H, gx, gS)
+
+    # ------------------------------------------------------------------ exact moment matching (K11, the sparse posterior)
+    def _moments_ready(self, what):
+        """ValueError where `propagate_ok()` does not hold (the limits of the moment entries are the chain's)."""
+        why = self._propagate_refusal()
+        if why:
+            raise ValueError(f"{what} is not available: {why}")
+
+    def _moments_entry(self, entry, *args):
+        try:
+            self._backend().call(entry, *args)
+        except _lib.GPKError as e:      # a limit of the entry: the caller's arguments, with the library's message
+            if e.code == _lib.GPK_BAD_ARG:
+                raise ValueError(str(e)) from None
+            raise
+
+    def predict_moments(self, X, Sigma, var_includes_noise=False):
+        """`GaussianProcessRegressor.predict_moments` on the sparse posterior: its exact moments at GAUSSIAN queries q ~ N(X[m],
+        Sigma[m]).  The sparse posterior is the exact model's form over the inducing inputs - weights alpha_u, and Q = Kuu^-1 -
+        Sigma~ where K^-1 stands - so the closed forms carry over.  X (M, D), M <= 32; Sigma (M, nx, nx) or (nx,
+        nx), symmetric positive semi-definite, over the LEADING nx <= D coordinates, or None.  Returns (mean (M, P), cov (M, P, P),
+        xcov (M, P, D)); var_includes_noise adds the WhiteKernel level to cov's diagonal.  One C call (`gpk_sparse_moments`: five
+        launches, one synchronisation; Q is formed on the device on the first call after the model was assembled, and again
+        after it has taken rows).  RuntimeError without inducing inputs; ValueError where `propagate_ok()` does not hold."""
+        from . import propagate as _pg
+        if getattr(self, "inducing_", None) is None:
+            raise RuntimeError("predict_moments: this SparseGP has no inducing inputs")
+        X, S, M, nx = _pg.check_gaussian_queries(X, Sigma, self.n_features_in_)
+        self._moments_ready("predict_moments")
+        self._ensure()
+        P, D = self._P, self.n_features_in_
+        mean, cov, xcov = np.empty((M, P)), np.empty((M, P, P)), np.empty((M, P, D))
+        self._moments_entry("gpk_sparse_moments", int(bool(var_includes_noise)), nx, _ptr(X), _ptr(S), M, _ptr(mean), _ptr(cov),
+                            _ptr(xcov))
+        return mean, cov, xcov
+
+    def propagate_moments(self, x0, U, lin, Sigma0=None, process_noise=None, var_includes_noise=False, return_stages=False,
+                          route="chain"):
+        """`GaussianProcessRegressor.propagate(method="moment")` on the sparse posterior: the horizon with every stage's EXACT
+        moments at the Gaussian query N([x_h, u_h], Sigma_h) (`predict_moments`), same arguments and results.  route="chain":
+        ONE C call per horizon (`gpk_sparse_propagate_mm`: five launches per stage, one synchronisation); route="host": the same
+        recursion as a host loop over `predict_moments` (`propagate.host_loop_moments`).  With return_stages the stages {"mean"
+        (H, R, P), "cov" (H, R, P, P), "xcov" (H, R, P, D)}, on the chain with the bits of `predict_moments` at the returned
+        rows.  RuntimeError without inducing inputs; ValueError where `propagate_ok()` does not hold or an argument is refused."""
+        from . import propagate as _pg
+        if getattr(self, "inducing_", None) is None:
+            raise RuntimeError("propagate_moments: this SparseGP has no inducing inputs")
+        _pg.check_route(route, ("chain", "host"))
+        P, D = self.n_outputs_, self.n_features_in_
+        x0, U, lin, S0, Q, R, H = _pg.check_horizon(x0, U, lin, P, D, Sigma0, process_noise)
+        _pg.check_method("moment", 1, "propagate_moments", Sigma0=S0, process_noise=Q)
+        self._moments_ready("propagate_moments")
+        if route == "host":
+            traj, Sigma, stages = _pg.host_loop_moments(
+                lambda q, S: self.predict_moments(q, S, var_includes_noise=var_includes_noise), list(range(P)), x0, U, lin, S0, Q, R,
+                H)
+            return (traj, Sigma, stages) if return_stages else (traj, Sigma)
+        self._ensure()
+        traj, Sigma, more = _pg.horizon_call(
+            lambda *t: self._backend().call("gpk_sparse_propagate_mm", int(bool(var_includes_noise)), *t),
+            x0, U, lin, S0, Q, R, H, ((P,), (P, P), (P, D)) if return_stages else None)
+        return (traj, Sigma, dict(zip(("mean", "cov", "xcov"), more))) if return_stages else (traj, Sigma)
 
     def _propagate_refusal(self):
         """Why the one-call chain does not apply (a string), or None where it does."""

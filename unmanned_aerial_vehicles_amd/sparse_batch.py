@@ -13,6 +13,7 @@ import ctypes as C
 
 import numpy as np
 
+from . import _lib
 from .device import check_queries
 from .gpr import cholesky_draws
 from .sparse import SparseGP, _ptr
@@ -161,7 +162,7 @@ class BatchedSparseGP:
         where `propagate_ok()` does not hold, with the reason, or where the entry refuses its arguments.  order=2: the
         second-order mean on every route (chain: `gpk_sparse_propagate2_multi`, four launches per stage; the host loop contracts
         `predict_hessian`); the stages gain "corr" (H, R, B).  method: "linear" only - exact moment matching
-        (method="moment") needs the inverse Gram matrix of an exact model: ValueError."""
+        is `propagate_moments` on this class; method="moment" here: ValueError."""
         from . import propagate as _pg
         order = _pg.check_order(order)
         _pg.refuse_moment(method, "BatchedSparseGP")
@@ -212,6 +213,69 @@ class BatchedSparseGP:
                                 var_includes_noise, with_dvar=True)
         hess_stage = _pg.batch_hess_stage(self.predict_hessian, in_shift, in_scale, o_scale)
         return _pg.host_adjoint(stage, hess_stage, coord, x0, U, lin, S0, Q, R, H, gx, gS)
+
+    # ------------------------------------------------------------------ exact moment matching (K11, the sparse posteriors)
+    def _moments_ready(self, what, nx=None):
+        """ValueError where `propagate_ok()` does not hold (the limits of the moment entries are the chain's)."""
+        why = self._propagate_refusal(nx)
+        if why:
+            raise ValueError(f"{what} is not available: {why}")
+
+    def predict_moments(self, X, Sigma, in_scaler=None, out_scaler=None, var_includes_noise=False):
+        """`BatchedARDGP.predict_moments` on the sparse posteriors, in raw units: the joint posterior of the B models at GAUSSIAN
+        queries q ~ N(X[m], Sigma[m]), all B (B + 1) / 2 pairs of models included, each model on its own inducing inputs with Q =
+        Kuu^-1 - Sigma~ where K^-1 stands (`SparseGP.predict_moments`).  X (M, D) raw, M <= 32; Sigma (M, nx, nx) or (nx, nx) or
+        None; in_scaler / out_scaler as `propagate`.  Returns (mean (M, B), cov (M, B, B), xcov (M, B, D)).  One C call
+        (`gpk_sparse_moments_multi`, five launches for all models and pairs, one synchronisation).  RuntimeError without models;
+        ValueError where `propagate_ok()` does not hold."""
+        from . import propagate as _pg
+        if not getattr(self, "models", None):
+            raise RuntimeError("predict_moments: this BatchedSparseGP has no models (no inducing inputs)")
+        B, D = len(self.models), self.n_features_in_
+        X, S, M, nx = _pg.check_gaussian_queries(X, Sigma, D)
+        in_shift, in_scale, o_mean, o_scale = _pg.check_scalers(B, D, in_scaler, out_scaler)
+        self._moments_ready("predict_moments", nx)
+        scaled = out_scaler is not None
+        om = np.ascontiguousarray(o_mean, dtype=np.float64) if scaled else None
+        osc = np.ascontiguousarray(o_scale, dtype=np.float64) if scaled else None
+        mean, cov, xcov = np.full((M, B), np.nan), np.full((M, B, B), np.nan), np.full((M, B, D), np.nan)
+        try:
+            with self._serving() as (be, handles):
+                be.call("gpk_sparse_moments_multi", B, handles, int(bool(var_includes_noise)), nx, _ptr(in_shift), _ptr(in_scale),
+                        _ptr(om), _ptr(osc), _ptr(X), _ptr(S), M, _ptr(mean), _ptr(cov), _ptr(xcov))
+        except _lib.GPKError as e:      # a limit of the entry: the caller's arguments, with the library's message
+            if e.code == _lib.GPK_BAD_ARG:
+                raise ValueError(str(e)) from None
+            raise
+        return mean, cov, xcov
+
+    def propagate_moments(self, x0, U, lin, coord=None, in_scaler=None, Sigma0=None, process_noise=None, var_includes_noise=False,
+                          return_stages=False, out_scaler=None, route="chain"):
+        """`BatchedARDGP.propagate(method="moment")` on the sparse posteriors: the batch's horizon with every stage's EXACT
+        moments (`predict_moments`), raw units, same arguments and results.  route="chain": ONE C call per horizon for all models
+        (`gpk_sparse_propagate_mm_multi`: five launches per stage, one synchronisation; the scalers go into the call);
+        route="host": the same recursion as a host loop over `predict_moments`.  The stages are {"mean" (H, R, B), "cov" (H, R,
+        B, B), "xcov" (H, R, B, D)}.  RuntimeError without models; ValueError where `propagate_ok()` does not hold or an argument
+        is refused."""
+        from . import propagate as _pg
+        if not getattr(self, "models", None):
+            raise RuntimeError("propagate_moments: this BatchedSparseGP has no models (no inducing inputs)")
+        B, D = len(self.models), self.n_features_in_
+        x0, U, lin, S0, Q, R, H, coord, in_shift, in_scale, o_mean, o_scale = _pg.check_batch(
+            B, D, x0, U, lin, coord, in_scaler, out_scaler, Sigma0, process_noise, route, routes=("chain", "host"))
+        _pg.check_method("moment", 1, "propagate_moments", Sigma0=S0, process_noise=Q)
+        nx = lin.shape[0]
+        self._moments_ready("propagate_moments", nx)
+        if route == "host":
+            traj, Sigma, stages = _pg.host_loop_moments(
+                lambda q, S: self.predict_moments(q, S, in_scaler=in_scaler, out_scaler=out_scaler,
+                                                  var_includes_noise=var_includes_noise), coord, x0, U, lin, S0, Q, R, H)
+            return (traj, Sigma, stages) if return_stages else (traj, Sigma)
+        traj, Sigma, more = _pg.horizon_call(
+            self._chain_call("gpk_sparse_propagate_mm_multi", var_includes_noise, nx, coord, in_shift, in_scale, out_scaler, o_mean,
+                             o_scale),
+            x0, U, lin, S0, Q, R, H, ((B,), (B, B), (B, D)) if return_stages else None)
+        return (traj, Sigma, dict(zip(("mean", "cov", "xcov"), more))) if return_stages else (traj, Sigma)
 
     def _chain_call(self, entry, var_includes_noise, nx, coord, in_shift, in_scale, out_scaler, o_mean, o_scale):
         """The call of a chain entry of the batch for `propagate.horizon_call`, which supplies the horizon's arguments."""

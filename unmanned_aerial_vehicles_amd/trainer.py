@@ -595,13 +595,12 @@ class PreTrainedGP:
         Sigma_{k+1} = (I + lin_x) Sigma_k (I + lin_x)^T + Q - it never raises into the control loop.  order=2: x_{k+1} also takes
         tr(H_i Sigma_k) / 2 per model, H_i the state block of mu_i's raw Hessian (the batches' `propagate`; model by model over
         `predict_residual_hessian_batch`); any other order: ValueError.  method="moment": every stage's exact moments, all
-        pairs of models included (`BatchedARDGP.propagate(method="moment")`: models that share inputs and scaler only, anything
-        else is a failure as above); ValueError with order=2 or a file of sparse models."""
+        pairs of models included (`BatchedARDGP.propagate(method="moment")`; a file of sparse models: `BatchedSparseGP.propagate_moments`, one
+        call for the horizon; models that share inputs and scaler only, anything else is a failure as above); ValueError with
+        order=2."""
         from . import propagate as _pg
         order = _pg.check_order(order)
         _pg.check_method(method, order)
-        if method == "moment" and self.is_loaded and any(not hasattr(m, "predict_moments") for m in self.gp_models.values()):
-            _pg.refuse_moment(method, "a PreTrainedGP that holds sparse models")
         state, U, lin, nominal, single = _pg.horizon_inputs(GPTrainer._nominal_dynamics, state, U_guess, dt)
         try:
             if not self.is_loaded:
@@ -612,11 +611,11 @@ class PreTrainedGP:
             if fused:
                 bg, names = fused
                 sys_ = [self.scalers_y[n] for n in names]
-                traj, Sigma = bg.propagate(state, U, lin, coord=[OUTPUT_NAMES.index(n) for n in names],
-                                           in_scaler=self.scalers_X[names[0]], Sigma0=Sigma0, process_noise=process_noise,
-                                           out_scaler=([float(np.ravel(s.mean_)[0]) for s in sys_],
-                                                       [float(np.ravel(s.scale_)[0]) for s in sys_]),
-                                           route=_pg.wrapper_route(bg), order=order, method=method)
+                traj, Sigma = _pg.model_horizon(bg, state, U, lin, order=order, method=method,
+                                                coord=[OUTPUT_NAMES.index(n) for n in names], in_scaler=self.scalers_X[names[0]],
+                                                Sigma0=Sigma0, process_noise=process_noise,
+                                                out_scaler=([float(np.ravel(s.mean_)[0]) for s in sys_],
+                                                            [float(np.ravel(s.scale_)[0]) for s in sys_]))
             else:
                 coord = [i for i, n in enumerate(OUTPUT_NAMES) if n in self.gp_models]
                 x0, Uc, linc, S0, Q, R, H = _pg.check_horizon(state, U, lin, 6, 10, Sigma0, process_noise)
