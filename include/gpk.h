@@ -1349,6 +1349,58 @@ GPK_API int gpk_propagate_mm_host_multi(gpk_handle h, int B, const double* const
                                         const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows,
                                         const double* Q, int R, int H, double* traj, double* Sigma, double* mean, double* cov,
                                         double* xcov);
+/* The adjoint of the moments: gpk_moments_host[_multi] with, for l = <gmean, mean> + <(gcov + gcov^T) / 2, cov> + <gxcov, xcov>, the
+ * gradients dXq (M x D) = dl/dXq and dSq (M x nx x nx, symmetric bit for bit) = dl/dSq in raw units.  The seeds gmean (M x NO), gcov
+ * (M x NO x NO) and gxcov (M x NO x D; columns >= nx, where xcov is zero, are ignored) are host arrays, NULL: zero.  mean, cov and
+ * xcov have the BITS of gpk_moments_host[_multi].  The clip passes the seed where E[v] > floor and nothing where it is active; the
+ * noise level is a constant.  Closed form (gpk_moments.hip, "the adjoint"): per pair of rows the forward's one exponential, one
+ * scalar weight c_ij and the sums of c_ij L_ij {1, zeta_ij, zeta_ij zeta_ij^T} - 1 + D + nx (nx + 1) / 2 sums whatever P is; S is
+ * never inverted, so Sq = 0 and a rank-deficient Sq stay legal.  Launches: the forward's five, one that keeps E[mu] and the clip
+ * indicators, and four of the adjoint (set-up, row pass, pair pass on the forward's tiles and query groups, finishing launch): ten
+ * launches, one upload, five downloads, ONE synchronisation; no atomics; repeatable bit for bit; query m has the bits of the
+ * same query served alone.
+ * GPK_BAD_ARG (with a message, before any launch, the outputs untouched): the siblings' refusals, a seed with NaN or infinity, a
+ * NULL dXq or dSq.                                                                                                              */
+GPK_API int gpk_moments_vjp_host(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
+                                 double sf2, const double* y_mean, const double* y_std, const double* Kinv, int64_t Np, int64_t ldk,
+                                 double kss, double floor_, int var_includes_noise, double noise, int nx, const double* Xq,
+                                 const double* Sq, int M, double* mean, double* cov, double* xcov, const double* gmean,
+                                 const double* gcov, const double* gxcov, double* dXq, double* dSq);
+GPK_API int gpk_moments_vjp_host_multi(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D,
+                                       const double* ls, const double* sf2, const double* y_mean, const double* y_std,
+                                       const double* const* Kinv, int64_t Np, int64_t ldk, const double* kss, double floor_,
+                                       int var_includes_noise, const double* noise, int nx, const double* in_shift,
+                                       const double* in_scale, const double* Xq, const double* Sq, int M, double* mean, double* cov,
+                                       double* xcov, const double* gmean, const double* gcov, const double* gxcov, double* dXq,
+                                       double* dSq);
+/* gpk_propagate_mm_host[_multi] with the gradient of a horizon cost l(traj, Sigma): the siblings' arguments followed by the seeds
+ * gx (H + 1, R, nx) = dl/dx_h and gS (H + 1, R, nx, nx) = dl/dSigma_h (NULL: zero; (gS + gS^T) / 2 is used) and the results dU (R,
+ * H, nu; NULL only when nu = 0), dx0 (R, nx), dSigma0 (R, nx, nx; may be NULL), as gpk_propagate_grad_host[_multi].  From lam_H =
+ * gx_H, Lam_H = sym gS_H, for h = H - 1 .. 0 the stage's moments are seeded with E^T lam (mean), E^T Lam E (cov) and 2 E^T Lam A0
+ * (the state columns of xcov), and with (m~, S~) their adjoint at ([x_h, u_h], Sigma_h):
+ *   g_q = [I 0]^T lam + lin^T lam + m~,   lam_h = gx_h + g_q[:nx],   dU_h = g_q[nx:],   Lam_h = sym gS_h + A0^T Lam A0 + S~
+ * traj, Sigma and the stage outputs have the BITS of gpk_propagate_mm_host[_multi].  The forward pass keeps the stages' queries,
+ * Sigma_h, E[mu] and the clip indicators on the device; the backward pass recomputes each stage's set-up and row vectors (three
+ * launches) ahead of the adjoint's four and keeps nothing of size N^2 or N R H: 6 H launches forward, 7 H backward, one upload,
+ * ONE synchronisation.  Rollout r of a batch has the bits of that rollout alone; two calls agree bit for bit.
+ * GPK_BAD_ARG (with a message, before any launch, the outputs untouched): the siblings' refusals, a seed with NaN or infinity, a
+ * NULL gx, dx0 or (nu > 0) dU.                                                                                                  */
+GPK_API int gpk_propagate_mm_grad_host(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
+                                       double sf2, const double* y_mean, const double* y_std, const double* Kinv, int64_t Np,
+                                       int64_t ldk, double kss, double floor_, int var_includes_noise, double noise,
+                                       const double* x0, int x0_rows, const double* U, int u_rows, const double* lin,
+                                       const double* Sigma0, int s_rows, const double* Q, int R, int H, double* traj, double* Sigma,
+                                       double* mean, double* cov, double* xcov, const double* gx, const double* gS, double* dU,
+                                       double* dx0, double* dSigma0);
+GPK_API int gpk_propagate_mm_grad_host_multi(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N,
+                                             int D, const double* ls, const double* sf2, const double* y_mean, const double* y_std,
+                                             const double* const* Kinv, int64_t Np, int64_t ldk, const double* kss, double floor_,
+                                             int var_includes_noise, const double* noise, int nx, const int* coord,
+                                             const double* in_shift, const double* in_scale, const double* x0, int x0_rows,
+                                             const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows,
+                                             const double* Q, int R, int H, double* traj, double* Sigma, double* mean, double* cov,
+                                             double* xcov, const double* gx, const double* gS, double* dU, double* dx0,
+                                             double* dSigma0);
 
 /* ... on the sparse posteriors.  The sparse posterior is the exact model's form over the m inducing inputs Z:
  *   mean(x) = y_mean + y_std k_u(x)^T alpha_u,     var_f(x) = sf2 - k_u(x)^T Q k_u(x),

@@ -200,6 +200,12 @@ SIGNATURES["gpk_propagate_mm_host_multi"] = (_int, list(SIGNATURES["gpk_propagat
 SIGNATURES["gpk_moments_host"] = (_int, SIGNATURES["gpk_propagate_host"][1][:17] + [_int, _vp, _vp, _int, _vp, _vp, _vp])
 SIGNATURES["gpk_moments_host_multi"] = (_int, SIGNATURES["gpk_propagate_host_multi"][1][:17]
                                         + [_int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp])
+# ... with the adjoint of the moments: the query entries with (gmean, gcov, gxcov, dXq, dSq) appended, the chains with (gx, gS, dU,
+# dx0, dSigma0) as the linear gradient entries
+SIGNATURES["gpk_moments_vjp_host"] = (_int, SIGNATURES["gpk_moments_host"][1] + [_vp] * 5)
+SIGNATURES["gpk_moments_vjp_host_multi"] = (_int, SIGNATURES["gpk_moments_host_multi"][1] + [_vp] * 5)
+SIGNATURES["gpk_propagate_mm_grad_host"] = (_int, SIGNATURES["gpk_propagate_mm_host"][1] + [_vp] * 5)
+SIGNATURES["gpk_propagate_mm_grad_host_multi"] = (_int, SIGNATURES["gpk_propagate_mm_host_multi"][1] + [_vp] * 5)
 # ... on the sparse posteriors (the engine above on (Z, alpha_u, Q)): the chains take the arguments of gpk_sparse_propagate[_multi]
 # with (mean, cov, xcov) as the stage outputs; the query entries: var_includes_noise, nx, [in_shift, in_scale, out_shift,
 # out_scale,] Xq, Sq, M, mean, cov, xcov

@@ -453,6 +453,58 @@ class BatchedARDGP:
                            _hp(in_scale), _hp(X), _hp(S), M, _hp(mean), _hp(cov), _hp(xcov))
         return mean, cov, xcov
 
+    def predict_moments_vjp(self, X, Sigma, grad_mean=None, grad_cov=None, grad_xcov=None, in_scaler=None, out_scaler=None,
+                            var_includes_noise=False):
+        """`GaussianProcessRegressor.predict_moments_vjp` for the batch, in raw units: `predict_moments` and, for the seeds
+        grad_mean (M, B), grad_cov (M, B, B), grad_xcov (M, B, D) (None: zero), dX (M, D) and dSigma (M, nx, nx) per unit of the
+        raw query and its raw covariance.  Returns (mean, cov, xcov, dX, dSigma), the first three with the bits of
+        `predict_moments`.  One C call (`gpk_moments_vjp_host_multi`: ten launches for all models and pairs)."""
+        from . import propagate as _pg
+        if not self.models:
+            raise RuntimeError("this BatchedARDGP is not fitted yet")
+        B, D = len(self.models), self.models[0].n_features_in_
+        X, S, M, nx = _pg.check_gaussian_queries(X, Sigma, D)
+        gm, gc, gxc = _pg.check_moment_seeds(grad_mean, grad_cov, grad_xcov, M, B, D)
+        in_shift, in_scale, o_mean, o_scale = _pg.check_scalers(B, D, in_scaler, out_scaler)
+        sv = self._moments_state()
+        ym, ys = np.ascontiguousarray(o_mean + o_scale * sv["ym"]), np.ascontiguousarray(o_scale * sv["ys"])
+        mean, cov, xcov = np.empty((M, B)), np.empty((M, B, B)), np.empty((M, B, D))
+        dX, dS = np.empty((M, D)), np.empty((M, nx, nx))
+        self._moments_call("gpk_moments_vjp_host_multi", sv, ym, ys, sv["kss"] if var_includes_noise else sv["sf2"], nx, _hp(in_shift),
+                           _hp(in_scale), _hp(X), _hp(S), M, _hp(mean), _hp(cov), _hp(xcov), _hp(gm), _hp(gc), _hp(gxc), _hp(dX),
+                           _hp(dS))
+        return mean, cov, xcov, dX, dS
+
+    def propagate_moments_gradient(self, x0, U, lin, grad_traj, grad_Sigma=None, coord=None, in_scaler=None, Sigma0=None,
+                                   process_noise=None, var_includes_noise=False, out_scaler=None, route="auto"):
+        """`propagate(method="moment")` with the gradient of a horizon cost, in raw units:
+        `GaussianProcessRegressor.propagate_moments_gradient` with the batch's conventions (coord, in_scaler, out_scaler as
+        `propagate`).  Returns (traj, Sigma, dU (R, H, nu), dx0 (R, nx), dSigma0 (R, nx, nx)), traj and Sigma with the bits of
+        `propagate(method="moment")`.  One C call per horizon for all models and pairs (`gpk_propagate_mm_grad_host_multi`);
+        route="host": the sweep on the host over `predict_moments` and `predict_moments_vjp`."""
+        from . import propagate as _pg
+        if not self.models:
+            raise RuntimeError("this BatchedARDGP is not fitted yet")
+        B = len(self.models)
+        D = self.models[0].n_features_in_
+        x0, U, lin, S0, Q, R, H, coord, in_shift, in_scale, o_mean, o_scale = _pg.check_batch(
+            B, D, x0, U, lin, coord, in_scaler, out_scaler, Sigma0, process_noise, route)
+        nx = lin.shape[0]
+        gx, gS = _pg.check_seeds(grad_traj, grad_Sigma, R, H, nx)
+        _pg.check_method("moment", 1, "propagate_moments_gradient", Sigma0=S0, process_noise=Q)
+        if route == "host":
+            kw = dict(in_scaler=in_scaler, out_scaler=out_scaler, var_includes_noise=var_includes_noise)
+            return _pg.host_adjoint_moments(lambda q, S: self.predict_moments(q, S, **kw),
+                                            lambda q, S, gm, gc, gxc: self.predict_moments_vjp(q, S, gm, gc, gxc, **kw),
+                                            coord, x0, U, lin, S0, Q, R, H, gx, gS)
+        sv = self._moments_state()
+        ym, ys = np.ascontiguousarray(o_mean + o_scale * sv["ym"]), np.ascontiguousarray(o_scale * sv["ys"])
+        traj, Sigma, more = _pg.horizon_call(
+            lambda *t: self._moments_call("gpk_propagate_mm_grad_host_multi", sv, ym, ys, sv["kss"] if var_includes_noise else sv["sf2"],
+                                          nx, (C.c_int * B)(*coord), _hp(in_shift), _hp(in_scale), *t),
+            x0, U, lin, S0, Q, R, H, seeds=(gx, gS))
+        return (traj, Sigma, *more)
+
     # ------------------------------------------------------------------ horizon propagation (K11, per-axis batch)
     def propagate(self, x0, U, lin, coord=None, in_scaler=None, Sigma0=None, process_noise=None, var_includes_noise=False,
                   return_stages=False, out_scaler=None, route="auto", order=1, method="linear"):

@@ -462,6 +462,14 @@ int gpk_propagate_run(gpk_handle h, const std::string& who, const ServeModels& m
 int gpk_mm_query(gpk_handle h, const std::string& who, const HostModels& m, const double* Xq, const double* Sq, int M, double* mean,
                  double* cov, double* xcov);
 int gpk_mm_chain(gpk_handle h, const std::string& who, const HostModels& m, const Horizon& z);
+// ... with the adjoint of the moments (gpk_moments.hip, "the adjoint"), on the same models - exact today, (Z, alpha_u, Q) of a sparse
+// model without new kernels.  gpk_mm_query_vjp: gpk_mm_query (mean, cov, xcov keep its bits) with the seeds gmean (M x NO), gcov (M x
+// NO x NO) and gxcov (M x NO x D), null: zero, and the results dXq (M x D), dSq (M x nx x nx, symmetric bit for bit); ten launches,
+// one upload, one synchronisation.  gpk_mm_chain_grad: gpk_mm_chain (its bits) with z.grad - six launches per stage forward, seven
+// backward, one upload, one synchronisation.  A non-finite seed or a null result: GPK_BAD_ARG before anything is launched.
+int gpk_mm_query_vjp(gpk_handle h, const std::string& who, const HostModels& m, const double* Xq, const double* Sq, int M, double* mean,
+                     double* cov, double* xcov, const double* gmean, const double* gcov, const double* gxcov, double* dXq, double* dSq);
+int gpk_mm_chain_grad(gpk_handle h, const std::string& who, const HostModels& m, const Horizon& z);
 // ... as one-call serving (gpk_serve.hip): host queries in, host results out through the pinned, mapped block, one
 // synchronisation.  small: the launches above (gpk_serve_predict: 33..64 queries the same twice); otherwise, F = 1 only, the
 // general chain, which also reads m.Np / m.ldw only with the inverse factor.

@@ -620,6 +620,637 @@ int mm_models(gpk_handle h, const std::string& who, const HostModels& m, bool ch
   return GPK_OK;
 }
 
+// ---- the adjoint of the moments (K11, "gradient through the moments") ---------------------------------------------------------------
+// Seeds e~ (on E[mu]), V~ (symmetric, on V) and C~ (on Cov[z_x, mu]) in normalised units; results m~ (D) and S~ (nx x nx).  With B =
+// (S + Lam_b)^-1 on the state block and 1 / Lam_b elsewhere, e^_o = e~_o - 2 (V~ E[mu])_o and t~_o = B S C~_o:
+//   mean part, model b:   w_i = l_i sum_o alpha_io (e^_o + t~_o . nu_i,x);   W0, W1, W2 = sum_i w_i {1, nu_i, nu_i,x nu_i,x^T}
+//                         m~ += B W1 - sum_o t~_o E[mu_o],   S~ += B W2 B / 2 - W0 B / 2 + sum_o (C~_o - t~_o) (B sum_i alpha_io l_i nu_i)^T
+//   pair (a, b):          c_ij = alpha_i^T V~ alpha_j - kappa (K^-1)_ij, kappa = sum_p V~_pp [E[v_p] > floor]  (a batch pair: V~_ab
+//                         alpha_i alpha_j, twice for a != b, kappa = V~_bb [..] on a == b);  zeta_ij = P_a nu_i + P_b nu_j
+//                         A0, A1, A2 = sum_ij c_ij L_ij {1, zeta_ij, zeta_ij,x zeta_ij,x^T}:   NV = 1 + D + nx (nx + 1) / 2 sums
+//                         m~_x += R^-T A1_x, m~_u += A1_u,  S~ += R^-T A2 R^-1 / 2 - A0 (S + P_ab^-1)^-1 / 2
+// with R^-T = I - P_ab G G^T and (S + P_ab^-1)^-1 = R^-T P_ab from the forward setup's factor: nothing inverts S.  S~ is symmetrised
+// at the end.  Launches, behind the forward's five:
+//   moments_keep_kernel          E[mu] and the clip indicators [E[v] > floor] of the batch, from the forward's slots
+//   moments_grad_setup_kernel    one wave per (query, model or pair): the normalised seeds, e^, t~, R^-T, kappa
+//   moments_grad_row_kernel      the N rows: w_i and the workgroups' shares of W0, W1, W2;  P_b nu_i per (model, query)
+//   moments_pair_grad_kernel     the forward pair kernel's tiles, masks, query loop and query groups; the exponent from the same row
+//                                vectors; V~ alpha_i of the tile's rows formed in LDS per query; the NV sums through the chunked LDS
+//                                reduction into the workgroup's own slot, c_ij L_ij of the thread's 4 x 4 pairs in registers throughout.
+//                                No atomics.  Templated on the capacity PC >= P of its alpha tiles (1: every batch; 8; 16) - nx and
+//                                D are loop bounds, the sums are indexed at run time
+//   moments_grad_finish_kernel   one workgroup per query: the slots in workgroup order, m~ and S~ (lower triangle, mirrored), the raw
+//                                units dq = dz / in_scale, dSigma = dS / (in_scale in_scale^T) and - in the chain - the adjoint step.
+constexpr int MG_GS = 40;          // doubles per (query, output) of the setup: t~ (16), C~ - t~ (16), e^ (at 32)
+
+struct MomSeeds {
+  const double *gmean, *gcov, *gxcov;      // a query batch: raw seeds R x NO, R x NO x NO, R x NO x D on the device, null: zero
+  const double *lam, *Lam, *lin;           // the chain (lam non-null): the incoming adjoints R x nx, R x nx x nx, and lin
+};
+// the chain's adjoint step of stage h in the finishing launch (lam null: none)
+struct MomAdj {
+  const double *lin, *gx_h, *gS_h;
+  double *lam, *Lam, *dU;
+  int H, h;
+};
+
+// grid R, 64 threads: keepE[r][16] = E[mu_o], keepF[r][U] = [E[v_b] > floor] of the diagonal pairs, the slots added as the finishing
+// launch adds them
+__global__ __launch_bounds__(64) void moments_keep_kernel(MomK k, int R, int G_, int nrw, int NV, const double* __restrict__ rowpart,
+                                                          const double* __restrict__ pairpart, double* keepE, double* keepF) {
+  const int tid = threadIdx.x, r = blockIdx.x;
+  if (tid < 16) {
+    double s = 0.0;
+    if (tid < k.NO)
+      for (int w = 0; w < nrw; ++w) s += rowpart[(((long long)w * R + r) * k.NO + tid) * MM_WS + 16];
+    keepE[r * 16 + tid] = s;
+  }
+  if (tid < k.U) {
+    int a, b;
+    pair_of(tid, a, b);
+    double f = 0.0;
+    if (a == b) {
+      const double* p = pairpart + ((long long)tid * G_ * R + r) * NV;
+      double s = 0.0;
+      for (int g = 0; g < G_; ++g) s += p[(long long)g * R * NV];
+      f = k.kss[b] - s > k.floor_ ? 1.0 : 0.0;
+    }
+    keepF[r * k.U + tid] = f;
+  }
+}
+
+// grid (R, B + U), 64 threads.  Units [0, B): gs[(r NO + o) MG_GS ..] of the model's outputs; unit 0 also gsV[r][16][16] = V~.
+// Units [B, B + U): RiT[(r U + u) 256 ..] = R^-T (zero beyond nx) and kap[r U + u].
+__global__ __launch_bounds__(64) void moments_grad_setup_kernel(MomK k, MomSeeds sd, int R, const double* __restrict__ Sz,
+                                                                const double* __restrict__ Bm, const double* __restrict__ G,
+                                                                const double* __restrict__ keepE, const double* __restrict__ keepF,
+                                                                double* gs, double* gsV, double* RiT, double* kap) {
+  __shared__ double S[16][17], Vb[16][17], Cb[16][17], T[16][17], eb[16], Em[16];
+  __shared__ int cof[16];
+  const int lane = threadIdx.x, r = blockIdx.x, unit = blockIdx.y, nx = k.nx, NO = k.NO, D = k.D, P = k.P;
+  if (lane < 16) {
+    int c = 0;
+    for (int d = 0; d < nx; ++d)
+      if (k.model_of[d] == lane) c = d;
+    cof[lane] = c;
+  }
+  for (int e = lane; e < 256; e += 64) S[e >> 4][e & 15] = Sz[(long long)r * 256 + e];
+  __syncthreads();
+  for (int e = lane; e < 256; e += 64) {
+    const int i = e >> 4, j = e & 15;
+    double v = 0.0, c = 0.0;
+    if (i < NO && j < NO) {
+      double g = 0.0;
+      if (sd.lam) g = sd.Lam[((long long)r * nx + cof[i]) * nx + cof[j]];
+      else if (sd.gcov) g = 0.5 * (sd.gcov[((long long)r * NO + i) * NO + j] + sd.gcov[((long long)r * NO + j) * NO + i]);
+      v = g * (k.ystd[i] * k.ystd[j]);
+    }
+    if (i < NO && j < nx) {
+      double g = 0.0;
+      if (sd.lam) {      // 2 (E^T Lam A0)(o, j)
+        for (int c2 = 0; c2 < nx; ++c2)
+          g = __builtin_fma(sd.Lam[((long long)r * nx + cof[i]) * nx + c2], (c2 == j ? 1.0 : 0.0) + sd.lin[c2 * D + j], g);
+        g *= 2.0;
+      } else if (sd.gxcov) {
+        g = sd.gxcov[((long long)r * NO + i) * D + j];
+      }
+      c = g * k.ystd[i] * (k.scaled ? k.in_scale[j] : 1.0);
+    }
+    Vb[i][j] = v;
+    Cb[i][j] = c;
+  }
+  if (lane < 16) {
+    double g = 0.0;
+    if (lane < NO) g = sd.lam ? sd.lam[(long long)r * nx + cof[lane]] : sd.gmean ? sd.gmean[(long long)r * NO + lane] : 0.0;
+    eb[lane] = lane < NO ? g * k.ystd[lane] : 0.0;
+    Em[lane] = keepE[r * 16 + lane];
+  }
+  __syncthreads();
+  if (unit < k.B) {
+    if (unit == 0)
+      for (int e = lane; e < 256; e += 64) gsV[(long long)r * 256 + e] = Vb[e >> 4][e & 15];
+    // T[p] = S C~_o, then t~_o = Bm T[p]
+    const double* bm = Bm + ((long long)r * k.B + unit) * 256;
+    for (int e = lane; e < P * 16; e += 64) {
+      const int p = e >> 4, i = e & 15, o = unit * P + p;
+      double s = 0.0;
+      for (int c = 0; c < nx; ++c) s = __builtin_fma(S[i][c], Cb[o][c], s);
+      T[p][i] = s;
+    }
+    __syncthreads();
+    for (int e = lane; e < P * 16; e += 64) {
+      const int p = e >> 4, i = e & 15, o = unit * P + p;
+      double s = 0.0;
+      if (i < nx)
+        for (int c = 0; c < nx; ++c) s = __builtin_fma(bm[i * 16 + c], T[p][c], s);
+      double* o_ = gs + ((long long)r * NO + o) * MG_GS;
+      o_[i] = s;
+      o_[16 + i] = i < nx ? Cb[o][i] - s : 0.0;
+      if (i == 0) {
+        double v = 0.0;
+        for (int c = 0; c < NO; ++c) v = __builtin_fma(Vb[o][c], Em[c], v);
+        o_[32] = eb[o] - 2.0 * v;
+      }
+    }
+    return;
+  }
+  const int u = unit - k.B;
+  int a, b;
+  pair_of(u, a, b);
+  const double* g = G + ((long long)r * k.U + u) * 256;
+  for (int e = lane; e < 256; e += 64) T[e >> 4][e & 15] = g[e];
+  __syncthreads();
+  for (int e = lane; e < 256; e += 64) {
+    const int i = e >> 4, j = e & 15;
+    double v = 0.0;
+    if (i < nx && j < nx) {
+      double m = 0.0;
+      for (int c = 0; c < nx; ++c) m = __builtin_fma(T[i][c], T[j][c], m);
+      const double la = k.ls[a][i], lb = k.ls[b][i];
+      v = (i == j ? 1.0 : 0.0) - (1.0 / (la * la) + 1.0 / (lb * lb)) * m;
+    }
+    RiT[((long long)r * k.U + u) * 256 + e] = v;
+  }
+  if (lane == 0) {
+    double v = 0.0;
+    if (a == b) {
+      if (k.B > 1) v = Vb[a][a];
+      else
+        for (int p = 0; p < P; ++p) v += Vb[p][p];
+      v *= keepF[r * k.U + u];
+    }
+    kap[r * k.U + u] = v;
+  }
+}
+
+// grid (ceil(N / 256), R, B), 256 threads.  part[((wg R + r) B + b) NV + v]: the workgroup's shares of W0 (v = 0), W1 (1 + d) and
+// W2 (1 + D + c (c + 1) / 2 + d, d <= c < nx), the rows added in row order;  gp[((b R + r) Np + i) 16 + d] = (P_b nu_i)_d.
+__global__ __launch_bounds__(256) void moments_grad_row_kernel(MomK k, int NV, const double* __restrict__ q, const double* __restrict__ Bm,
+                                                               const double* __restrict__ cm, const double* __restrict__ gs, double* gp,
+                                                               double* part) {
+  __shared__ double sB[16][17], nuS[MM_ROWS][MM_WS], z[16], ip[16], tb[16][17], eh[16];
+  const int tid = threadIdx.x, r = blockIdx.y, b = blockIdx.z, R = gridDim.y, D = k.D, nx = k.nx, P = k.P;
+  const long long row = (long long)blockIdx.x * MM_ROWS + tid;
+  sB[tid >> 4][tid & 15] = Bm[((long long)r * k.B + b) * 256 + tid];
+  if (tid < 16) {
+    z[tid] = tid < D ? q[(long long)r * D + tid] : 0.0;
+    ip[tid] = tid < D ? 1.0 / (k.ls[b][tid] * k.ls[b][tid]) : 0.0;
+    eh[tid] = tid < P ? gs[((long long)r * k.NO + b * P + tid) * MG_GS + 32] : 0.0;
+  }
+  {
+    const int p = tid >> 4, d = tid & 15;
+    tb[p][d] = p < P ? gs[((long long)r * k.NO + b * P + p) * MG_GS + d] : 0.0;
+  }
+  __syncthreads();
+  const bool live = row < k.N;
+  const double* xr = k.X[b] + row * D;
+  double nu[16];
+#pragma unroll
+  for (int d = 0; d < 16; ++d) nu[d] = (live && d < D) ? xr[d] - z[d] : 0.0;
+  double quad = 0.0;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    if (i < nx) {
+      double t = 0.0;
+#pragma unroll
+      for (int j = 0; j < 16; ++j) t = __builtin_fma(sB[i][j], nu[j], t);
+      quad = __builtin_fma(nu[i], t, quad);
+    } else {
+      quad = __builtin_fma(nu[i] * nu[i], ip[i], quad);
+    }
+  }
+  const double l = live ? exp(cm[(long long)r * k.B + b] - 0.5 * quad) : 0.0;
+  double w = 0.0;
+  for (int p = 0; p < P; ++p) {
+    double dot = eh[p];
+#pragma unroll
+    for (int d = 0; d < 16; ++d) dot = __builtin_fma(tb[p][d], nu[d], dot);      // (entries >= nx of t~ are zero)
+    const double al = live ? k.alpha[b][row * P + p] : 0.0;
+    w = __builtin_fma(al, dot, w);
+  }
+#pragma unroll
+  for (int d = 0; d < 16; ++d) nuS[tid][d] = nu[d];
+  nuS[tid][16] = w * l;
+  if (live) {
+    double* o = gp + (((long long)b * R + r) * k.Np + row) * 16;
+#pragma unroll
+    for (int d = 0; d < 16; ++d) o[d] = nu[d] * ip[d];
+  }
+  __syncthreads();
+  if (tid < NV) {
+    int c = 16, d = 16;      // (16: the factor is one)
+    if (tid >= 1 + D) {
+      const int e = tid - 1 - D;
+      c = 0;
+      while ((c + 1) * (c + 2) / 2 <= e) ++c;
+      d = e - c * (c + 1) / 2;
+    } else if (tid >= 1) {
+      c = tid - 1;
+    }
+    double s = 0.0;
+    for (int t = 0; t < MM_ROWS; ++t) {
+      double f = nuS[t][16];
+      if (c < 16) f *= nuS[t][c];
+      if (d < 16) f *= nuS[t][d];
+      s += f;
+    }
+    part[((((long long)blockIdx.x * R + r) * k.B + b)) * NV + tid] = s;
+  }
+}
+
+// grid (G, U, NQ), 256 threads, thread (ty, tx) as in moments_pair_kernel.  part[((u G + g) R + r) NV + v]: v = 0 A0, 1 + d A1,
+// 1 + D + c (c + 1) / 2 + d A2 (d <= c < nx).  An off-diagonal tile of a == b stands for its mirror image too: c_ij, L_ij and
+// zeta_ij are symmetric in (i, j) there, so its sums count twice.
+template <int PC, bool SPLIT>
+__global__ __launch_bounds__(256) void moments_pair_grad_kernel(MomK k, int R, int NV, const double* __restrict__ rowq,
+                                                                const double* __restrict__ cl, const double* __restrict__ gp,
+                                                                const double* __restrict__ gsV, const double* __restrict__ kap,
+                                                                double* part) {
+  __shared__ double sA[MM_TILE][PC], sB[MM_TILE][PC], sVa[MM_TILE][PC], sV[PC][PC], sWa[MM_TILE][MM_WS], sWb[MM_TILE][MM_WS],
+      sPa[MM_TILE][MM_WS], sPb[MM_TILE][MM_WS], red[MM_CH][16 * 17], red2[MM_CH][16];
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4, u = blockIdx.y, g = blockIdx.x, G_ = gridDim.x, nx = k.nx, D = k.D, P = k.P;
+  const int r0 = SPLIT ? (int)(blockIdx.z * (unsigned)R / gridDim.z) : 0;
+  const int r1 = SPLIT ? (int)((blockIdx.z + 1) * (unsigned)R / gridDim.z) : R;
+  int a, b;
+  pair_of(u, a, b);
+  const bool same = a == b;
+  const long long N = k.N;
+  const int nt = (int)((N + MM_TILE - 1) / MM_TILE);
+  const long long ntiles = same ? (long long)nt * (nt + 1) / 2 : (long long)nt * nt;
+  const double* Wa = rowq + (long long)(a * a + 2 * b) * R * k.Np * MM_WS;
+  const double* Wb = same ? Wa : Wa + (long long)R * k.Np * MM_WS;
+  const double* Pa = gp + (long long)a * R * k.Np * 16;
+  const double* Pb = gp + (long long)b * R * k.Np * 16;
+  bool first = true;
+  for (long long t = g; t < ntiles; t += G_) {
+    int ti, tj;
+    if (same) {
+      ti = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+      while ((long long)(ti + 1) * (ti + 2) / 2 <= t) ++ti;
+      while ((long long)ti * (ti + 1) / 2 > t) --ti;
+      tj = (int)(t - (long long)ti * (ti + 1) / 2);
+    } else {
+      ti = (int)(t / nt);
+      tj = (int)(t % nt);
+    }
+    const double wgt = (same && ti != tj) ? 2.0 : 1.0;
+    const long long i0 = (long long)ti * MM_TILE, j0 = (long long)tj * MM_TILE;
+    double kv[4][4];
+#pragma unroll
+    for (int ii = 0; ii < 4; ++ii)
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) {
+        const long long i = i0 + ty + 16 * ii, j = j0 + tx + 16 * jj;
+        kv[ii][jj] = (same && i < N && j < N) ? k.Kinv[a][(i > j ? i : j) * k.ldk + (i > j ? j : i)] : 0.0;
+      }
+    __syncthreads();
+    for (int e = tid; e < MM_TILE * P; e += 256) {
+      const int row = e / P, p = e % P;
+      sA[row][p] = i0 + row < N ? k.alpha[a][(i0 + row) * P + p] : 0.0;
+      sB[row][p] = j0 + row < N ? k.alpha[b][(j0 + row) * P + p] : 0.0;
+    }
+    for (int r = r0; r < r1; ++r) {
+      __syncthreads();
+      for (int e = tid; e < MM_TILE * MM_WS; e += 256) {
+        const int row = e / MM_WS;
+        sWa[row][e % MM_WS] = i0 + row < N ? Wa[((long long)r * k.Np + i0) * MM_WS + e] : 0.0;
+        sWb[row][e % MM_WS] = j0 + row < N ? Wb[((long long)r * k.Np + j0) * MM_WS + e] : 0.0;
+      }
+      for (int e = tid; e < MM_TILE * 16; e += 256) {
+        const int row = e >> 4;
+        sPa[row][e & 15] = i0 + row < N ? Pa[((long long)r * k.Np + i0) * 16 + e] : 0.0;
+        sPb[row][e & 15] = j0 + row < N ? Pb[((long long)r * k.Np + j0) * 16 + e] : 0.0;
+      }
+      // V~ of the pair: the P x P block of one model, or the batch pair's entry (both orders of a != b)
+      if (tid < P * P)
+        sV[tid / P][tid % P] = k.B > 1 ? (same ? 1.0 : 2.0) * gsV[(long long)r * 256 + a * 16 + b]
+                                       : gsV[(long long)r * 256 + (tid / P) * 16 + tid % P];
+      __syncthreads();
+      for (int e = tid; e < MM_TILE * P; e += 256) {
+        const int row = e / P, p = e % P;
+        double s = 0.0;
+        for (int c = 0; c < P; ++c) s = __builtin_fma(sV[p][c], sA[row][c], s);
+        sVa[row][p] = s;
+      }
+      const double c0 = cl[(long long)r * k.U + u];
+      double ex[4][4];
+#pragma unroll
+      for (int ii = 0; ii < 4; ++ii)
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) ex[ii][jj] = (c0 + sWa[ty + 16 * ii][16]) + sWb[tx + 16 * jj][16];
+      for (int c = 0; c < nx; ++c) {
+        double wa[4], wb[4];
+#pragma unroll
+        for (int ii = 0; ii < 4; ++ii) { wa[ii] = sWa[ty + 16 * ii][c]; wb[ii] = sWb[tx + 16 * ii][c]; }
+#pragma unroll
+        for (int ii = 0; ii < 4; ++ii)
+#pragma unroll
+          for (int jj = 0; jj < 4; ++jj) ex[ii][jj] = __builtin_fma(wa[ii], wb[jj], ex[ii][jj]);
+      }
+      __syncthreads();
+      // e_ij = c_ij L_ij of the thread's pairs, kept to the end of the tile's sums
+      const double kp = kap[(long long)r * k.U + u];
+      double cw[4][4];
+#pragma unroll
+      for (int ii = 0; ii < 4; ++ii)
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) cw[ii][jj] = -kp * kv[ii][jj];
+      for (int p = 0; p < P; ++p) {
+        double va[4], bj[4];
+#pragma unroll
+        for (int ii = 0; ii < 4; ++ii) { va[ii] = sVa[ty + 16 * ii][p]; bj[ii] = sB[tx + 16 * ii][p]; }
+#pragma unroll
+        for (int ii = 0; ii < 4; ++ii)
+#pragma unroll
+          for (int jj = 0; jj < 4; ++jj) cw[ii][jj] = __builtin_fma(va[ii], bj[jj], cw[ii][jj]);
+      }
+#pragma unroll
+      for (int ii = 0; ii < 4; ++ii)
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+          const bool live = i0 + ty + 16 * ii < N && j0 + tx + 16 * jj < N;
+          ex[ii][jj] = live ? cw[ii][jj] * exp(ex[ii][jj]) : 0.0;
+        }
+      double er[4], ec[4];      // the block's row and column sums of e
+#pragma unroll
+      for (int ii = 0; ii < 4; ++ii) {
+        er[ii] = (ex[ii][0] + ex[ii][1]) + (ex[ii][2] + ex[ii][3]);
+        ec[ii] = (ex[0][ii] + ex[1][ii]) + (ex[2][ii] + ex[3][ii]);
+      }
+      double* slot = part + (((long long)u * G_ + g) * R + r) * NV;
+      auto flush = [&](int chunk, int nvals) {
+        __syncthreads();
+        if (ty < nvals) {
+          double s = 0.0;
+#pragma unroll
+          for (int c = 0; c < 16; ++c) s += red[ty][tx * 17 + c];
+          red2[ty][tx] = s;
+        }
+        __syncthreads();
+        if (tid < nvals) {
+          double s = 0.0;
+#pragma unroll
+          for (int c = 0; c < 16; ++c) s += red2[tid][c];
+          s *= wgt;
+          double* dst = slot + chunk * MM_CH + tid;
+          *dst = first ? s : *dst + s;
+        }
+      };
+      auto emit = [&](int v, double x) {
+        red[v % MM_CH][ty * 17 + tx] = x;
+        if (v % MM_CH == MM_CH - 1 || v == NV - 1) flush(v / MM_CH, v % MM_CH + 1);
+      };
+      emit(0, (er[0] + er[1]) + (er[2] + er[3]));
+      for (int d = 0; d < D; ++d) {      // A1_d = sum_i p^a_id er_i + sum_j p^b_jd ec_j
+        double s = 0.0;
+#pragma unroll
+        for (int ii = 0; ii < 4; ++ii) s = __builtin_fma(sPa[ty + 16 * ii][d], er[ii], s);
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) s = __builtin_fma(sPb[tx + 16 * jj][d], ec[jj], s);
+        emit(1 + d, s);
+      }
+      int v = 1 + D;
+      for (int c = 0; c < nx; ++c) {
+        // ga_i = sum_j e_ij (p^a_ic + p^b_jc), gb_j = sum_i e_ij (p^a_ic + p^b_jc):  A2_cd = sum_i p^a_id ga_i + sum_j p^b_jd gb_j
+        double pa[4], pb[4], ga[4], gb[4];
+#pragma unroll
+        for (int ii = 0; ii < 4; ++ii) { pa[ii] = sPa[ty + 16 * ii][c]; pb[ii] = sPb[tx + 16 * ii][c]; }
+#pragma unroll
+        for (int ii = 0; ii < 4; ++ii) { ga[ii] = er[ii] * pa[ii]; gb[ii] = ec[ii] * pb[ii]; }
+#pragma unroll
+        for (int ii = 0; ii < 4; ++ii)
+#pragma unroll
+          for (int jj = 0; jj < 4; ++jj) {
+            ga[ii] = __builtin_fma(ex[ii][jj], pb[jj], ga[ii]);
+            gb[jj] = __builtin_fma(ex[ii][jj], pa[ii], gb[jj]);
+          }
+        for (int d = 0; d <= c; ++d) {
+          double s = 0.0;
+#pragma unroll
+          for (int ii = 0; ii < 4; ++ii) s = __builtin_fma(sPa[ty + 16 * ii][d], ga[ii], s);
+#pragma unroll
+          for (int jj = 0; jj < 4; ++jj) s = __builtin_fma(sPb[tx + 16 * jj][d], gb[jj], s);
+          emit(v++, s);
+        }
+      }
+    }
+    first = false;
+  }
+}
+
+// grid R, 256 threads, thread (i, j) = (tid >> 4, tid & 15).  dq (R x D) and dS (R x nx x nx) in raw units, null where not wanted;
+// with ad.lam the adjoint step of the chain's stage:  g_q = [I 0]^T lam + lin^T lam + dq,  lam <- gx_h + g_q[:nx],  dU_h = g_q[nx:],
+// Lam <- gS_h + A0^T Lam A0 + dS (lower triangle formed and mirrored).
+__global__ __launch_bounds__(256) void moments_grad_finish_kernel(MomK k, MomAdj ad, int R, int G_, int nrw, int NV,
+                                                                  const double* __restrict__ Bm, const double* __restrict__ rowpart,
+                                                                  const double* __restrict__ keepE, const double* __restrict__ gs,
+                                                                  const double* __restrict__ RiT, const double* __restrict__ growpart,
+                                                                  const double* __restrict__ gpairpart, double* dq, double* dS) {
+  __shared__ double sv[160], Mt[16][17], W2[16][17], T1[16][17], Cz[16][17], Tm[16][17], Sb[16][17], Sr[16][17], mr[16], lm[16];
+  const int tid = threadIdx.x, i = tid >> 4, j = tid & 15, r = blockIdx.x;
+  const int nx = k.nx, D = k.D, NO = k.NO, P = k.P, B = k.B;
+  double sacc = 0.0, macc = 0.0;      // S~(i, j) before the symmetrisation; m~(tid), tid < D
+  for (int b = 0; b < B; ++b) {
+    if (tid < NV) {
+      double s = 0.0;
+      for (int w = 0; w < nrw; ++w) s += growpart[(((long long)w * R + r) * B + b) * NV + tid];
+      sv[tid] = s;
+    }
+    Mt[i][j] = Bm[((long long)r * B + b) * 256 + tid];
+    if (i < P && j < nx) {
+      double s = 0.0;
+      for (int w = 0; w < nrw; ++w) s += rowpart[(((long long)w * R + r) * NO + b * P + i) * MM_WS + j];
+      Cz[i][j] = s;
+    }
+    __syncthreads();
+    if (i < nx && j < nx) W2[i][j] = sv[1 + D + (i > j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i)];
+    if (i < P && j < nx) {
+      double s = 0.0;
+      for (int c = 0; c < nx; ++c) s = __builtin_fma(Mt[j][c], Cz[i][c], s);
+      Tm[i][j] = s;
+    }
+    __syncthreads();
+    if (i < nx && j < nx) {
+      double s = 0.0;
+      for (int c = 0; c < nx; ++c) s = __builtin_fma(Mt[i][c], W2[c][j], s);
+      T1[i][j] = s;
+    }
+    __syncthreads();
+    if (i < nx && j < nx) {
+      double s = 0.0;
+      for (int c = 0; c < nx; ++c) s = __builtin_fma(T1[i][c], Mt[c][j], s);
+      s = 0.5 * s - 0.5 * sv[0] * Mt[i][j];
+      for (int p = 0; p < P; ++p) s = __builtin_fma(gs[((long long)r * NO + b * P + p) * MG_GS + 16 + i], Tm[p][j], s);
+      sacc += s;
+    }
+    if (tid < D) {
+      double s = 0.0;
+      if (tid < nx) {
+        for (int c = 0; c < nx; ++c) s = __builtin_fma(Mt[tid][c], sv[1 + c], s);
+        for (int p = 0; p < P; ++p) s -= gs[((long long)r * NO + b * P + p) * MG_GS + tid] * keepE[r * 16 + b * P + p];
+      } else {
+        s = sv[1 + tid] / (k.ls[b][tid] * k.ls[b][tid]);
+      }
+      macc += s;
+    }
+    __syncthreads();
+  }
+  for (int u = 0; u < k.U; ++u) {
+    int a, b;
+    pair_of(u, a, b);
+    if (tid < NV) {
+      const double* p = gpairpart + ((long long)u * G_ * R + r) * NV + tid;
+      double s = 0.0;
+#pragma unroll 8
+      for (int g = 0; g < G_; ++g) s += p[(long long)g * R * NV];
+      sv[tid] = s;
+    }
+    Mt[i][j] = RiT[((long long)r * k.U + u) * 256 + tid];
+    __syncthreads();
+    if (i < nx && j < nx) W2[i][j] = sv[1 + D + (i > j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i)];
+    __syncthreads();
+    if (i < nx && j < nx) {
+      double s = 0.0;
+      for (int c = 0; c < nx; ++c) s = __builtin_fma(Mt[i][c], W2[c][j], s);
+      T1[i][j] = s;
+    }
+    __syncthreads();
+    if (i < nx && j < nx) {
+      double s = 0.0;
+      for (int c = 0; c < nx; ++c) s = __builtin_fma(T1[i][c], Mt[j][c], s);
+      const double la = k.ls[a][j], lb = k.ls[b][j];
+      sacc += 0.5 * s - 0.5 * sv[0] * (Mt[i][j] * (1.0 / (la * la) + 1.0 / (lb * lb)));
+    }
+    if (tid < D) {
+      double s = 0.0;
+      if (tid < nx)
+        for (int c = 0; c < nx; ++c) s = __builtin_fma(Mt[tid][c], sv[1 + c], s);
+      else
+        s = sv[1 + tid];
+      macc += s;
+    }
+    __syncthreads();
+  }
+  Sb[i][j] = (i < nx && j < nx) ? sacc : 0.0;
+  if (tid < 16) mr[tid] = tid < D ? (k.scaled ? macc / k.in_scale[tid] : macc) : 0.0;
+  __syncthreads();
+  if (i < nx && j <= i) {
+    double s = 0.5 * (Sb[i][j] + Sb[j][i]);
+    if (k.scaled) s = s / (k.in_scale[i] * k.in_scale[j]);
+    Sr[i][j] = s;
+    Sr[j][i] = s;
+  }
+  __syncthreads();
+  if (dq && tid < D) dq[(long long)r * D + tid] = mr[tid];
+  if (dS && i < nx && j < nx) dS[((long long)r * nx + i) * nx + j] = Sr[i][j];
+  if (!ad.lam) return;
+  // the adjoint step: Mt = Lam, W2 = A0
+  if (i < nx && j < nx) {
+    Mt[i][j] = ad.Lam[((long long)r * nx + i) * nx + j];
+    W2[i][j] = (i == j ? 1.0 : 0.0) + ad.lin[i * D + j];
+  }
+  if (tid < nx) lm[tid] = ad.lam[(long long)r * nx + tid];
+  __syncthreads();
+  if (tid < D) {
+    double s = tid < nx ? lm[tid] : 0.0;
+    for (int c = 0; c < nx; ++c) s = __builtin_fma(ad.lin[c * D + tid], lm[c], s);
+    s += mr[tid];
+    if (tid < nx) ad.lam[(long long)r * nx + tid] = ad.gx_h[(long long)r * nx + tid] + s;
+    else ad.dU[((long long)r * ad.H + ad.h) * (D - nx) + (tid - nx)] = s;
+  }
+  if (i < nx && j < nx) {
+    double t = 0.0;
+    for (int c = 0; c < nx; ++c) t = __builtin_fma(Mt[i][c], W2[c][j], t);
+    T1[i][j] = t;
+  }
+  __syncthreads();
+  if (i < nx && j <= i) {
+    double s = 0.0;
+    for (int c = 0; c < nx; ++c) s = __builtin_fma(W2[c][i], T1[c][j], s);
+    const long long at = (long long)r * nx * nx;
+    if (ad.gS_h) s += ad.gS_h[at + i * nx + j];
+    s += Sr[i][j];
+    ad.Lam[at + i * nx + j] = s;
+    ad.Lam[at + j * nx + i] = s;
+  }
+}
+
+// The adjoint's device work area for one batch of R queries, behind the forward's (MomWork), carved from `base`.
+struct MomGradWork {
+  double *keepE, *keepF, *gs, *gsV, *RiT, *kap, *gp, *rowpart, *pairpart;
+  int NV;
+  size_t doubles;
+};
+
+MomGradWork mg_work(const MomK& k, const MomWork& w, int R, double* base) {
+  MomGradWork g{};
+  g.NV = 1 + k.D + k.nx * (k.nx + 1) / 2;
+  size_t at = 0;
+  auto take = [&](size_t n) { double* p = base ? base + at : nullptr; at += n; return p; };
+  g.keepE = take((size_t)R * 16);
+  g.keepF = take((size_t)R * k.U);
+  g.gs = take((size_t)R * k.NO * MG_GS);
+  g.gsV = take((size_t)R * 256);
+  g.RiT = take((size_t)R * k.U * 256);
+  g.kap = take((size_t)R * k.U);
+  g.gp = take((size_t)k.B * R * k.Np * 16);
+  g.rowpart = take((size_t)w.nrw * R * k.B * g.NV);
+  g.pairpart = take((size_t)k.U * w.G_ * R * g.NV);
+  g.doubles = at;
+  return g;
+}
+
+void mm_keep(gpk_handle h, const MomK& k, const MomWork& w, int R, double* keepE, double* keepF) {
+  hipLaunchKernelGGL(moments_keep_kernel, dim3((unsigned)R), dim3(64), 0, h->stream, k, R, w.G_, w.nrw, w.NV, (const double*)w.rowpart,
+                     (const double*)w.pairpart, keepE, keepF);
+}
+
+template <int PC>
+void mg_pair_launch(gpk_handle h, const MomK& k, const MomWork& w, const MomGradWork& g, int R) {
+  if (w.NQ > 1)
+    hipLaunchKernelGGL((moments_pair_grad_kernel<PC, true>), dim3((unsigned)w.G_, (unsigned)k.U, (unsigned)w.NQ), dim3(256), 0,
+                       h->stream, k, R, g.NV, (const double*)w.rowq, (const double*)w.cl, (const double*)g.gp, (const double*)g.gsV,
+                       (const double*)g.kap, g.pairpart);
+  else
+    hipLaunchKernelGGL((moments_pair_grad_kernel<PC, false>), dim3((unsigned)w.G_, (unsigned)k.U), dim3(256), 0, h->stream, k, R, g.NV,
+                       (const double*)w.rowq, (const double*)w.cl, (const double*)g.gp, (const double*)g.gsV, (const double*)g.kap,
+                       g.pairpart);
+}
+
+// The four launches of the adjoint on a batch whose forward setup and row vectors are in w (Sz, Bm, cm, G, cl, rowq, rowpart) and
+// whose E[mu] and clip indicators are in keepE / keepF: d_q the scaled queries.
+int mg_launch(gpk_handle h, const MomK& k, const MomWork& w, const MomGradWork& g, int R, const double* d_q, const MomSeeds& sd,
+              const MomAdj& ad, const double* keepE, const double* keepF, double* dq, double* dS) {
+  hipLaunchKernelGGL(moments_grad_setup_kernel, dim3((unsigned)R, (unsigned)(k.B + k.U)), dim3(64), 0, h->stream, k, sd, R,
+                     (const double*)w.Sz, (const double*)w.Bm, (const double*)w.G, keepE, keepF, g.gs, g.gsV, g.RiT, g.kap);
+  GPK_LAUNCH_CHECK(h);
+  hipLaunchKernelGGL(moments_grad_row_kernel, dim3((unsigned)w.nrw, (unsigned)R, (unsigned)k.B), dim3(256), 0, h->stream, k, g.NV, d_q,
+                     (const double*)w.Bm, (const double*)w.cm, (const double*)g.gs, g.gp, g.rowpart);
+  GPK_LAUNCH_CHECK(h);
+  if (k.P == 1) mg_pair_launch<1>(h, k, w, g, R);
+  else if (k.P <= 8) mg_pair_launch<8>(h, k, w, g, R);
+  else mg_pair_launch<16>(h, k, w, g, R);
+  GPK_LAUNCH_CHECK(h);
+  hipLaunchKernelGGL(moments_grad_finish_kernel, dim3((unsigned)R), dim3(256), 0, h->stream, k, ad, R, w.G_, w.nrw, g.NV,
+                     (const double*)w.Bm, (const double*)w.rowpart, keepE, (const double*)g.gs, (const double*)g.RiT,
+                     (const double*)g.rowpart, (const double*)g.pairpart, dq, dS);
+  GPK_LAUNCH_CHECK(h);
+  return GPK_OK;
+}
+
+// The forward's setup and row launches alone (the chain's backward sweep recomputes a stage's factors and row vectors with them)
+int mm_launch_rows(gpk_handle h, const MomK& k, const MomWork& w, int R, const double* d_q, const double* d_S) {
+  hipLaunchKernelGGL(moments_setup_kernel, dim3((unsigned)R, (unsigned)(k.B + k.U)), dim3(64), 0, h->stream, k, d_S, w.Sz, w.Bm, w.cm,
+                     w.G, w.cl);
+  GPK_LAUNCH_CHECK(h);
+  hipLaunchKernelGGL(moments_row_mean_kernel, dim3((unsigned)w.nrw, (unsigned)R, (unsigned)k.B), dim3(256), 0, h->stream, k, d_q,
+                     (const double*)w.Bm, (const double*)w.cm, w.rowpart);
+  hipLaunchKernelGGL(moments_row_pair_kernel, dim3((unsigned)w.nrw, (unsigned)R, (unsigned)(2 * k.U)), dim3(256), 0, h->stream, k, d_q,
+                     (const double*)w.G, w.rowq);
+  GPK_LAUNCH_CHECK(h);
+  return GPK_OK;
+}
+
 }  // namespace
 
 // M <= 32 Gaussian queries: one upload [z | S], five launches, three downloads, one synchronisation.
@@ -698,6 +1329,147 @@ int gpk_mm_chain(gpk_handle h, const std::string& who, const HostModels& m, cons
   return gpk_horizon_finish(h, b, z, {});
 }
 
+// gpk_mm_query with the adjoint: one upload [z | S | gmean | gcov | gxcov], the forward's five launches (mean, cov, xcov keep their
+// bits), the keep launch and the adjoint's four, five downloads, one synchronisation.
+int gpk_mm_query_vjp(gpk_handle h, const std::string& who, const HostModels& m, const double* Xq, const double* Sq, int M, double* mean,
+                     double* cov, double* xcov, const double* gmean, const double* gcov, const double* gxcov, double* dXq, double* dSq) {
+  if (!h) return GPK_BAD_ARG;
+  MomK k;
+  GPK_TRY(mm_models(h, who, m, false, k));
+  GPK_REQUIRE(h, M >= 1 && M <= GPK_SMALL_MAX_M, who + "M must be in [1, 32]");
+  GPK_REQUIRE(h, Xq && mean && cov && xcov, who + "null pointer");
+  GPK_REQUIRE(h, dXq && dSq, who + "null result dXq or dSq");
+  const int D = k.D, nx = k.nx, NO = k.NO;
+  const size_t n_q = (size_t)M * D, n_s = (size_t)M * nx * nx;
+  const size_t n_om = (size_t)M * NO, n_oc = n_om * NO, n_ox = n_om * D;
+  GPK_REQUIRE(h, gpk_finite(Xq, n_q), who + "the queries must not contain NaN or infinity");
+  GPK_REQUIRE(h, !Sq || gpk_finite(Sq, n_s), who + "the covariances must not contain NaN or infinity");
+  GPK_REQUIRE(h, (!gmean || gpk_finite(gmean, n_om)) && (!gcov || gpk_finite(gcov, n_oc)) && (!gxcov || gpk_finite(gxcov, n_ox)),
+              who + "the seeds gmean, gcov and gxcov must not contain NaN or infinity");
+  const MomWork sizes = mm_work(h, k, M, nullptr);
+  const MomGradWork gsizes = mg_work(k, sizes, M, nullptr);
+  const size_t n_up = n_q + n_s + n_om + n_oc + n_ox;
+  void* ws = nullptr;
+  GPK_TRY(gpk_scratch(h, (n_up + n_om + n_oc + n_ox + n_q + n_s + sizes.doubles + gsizes.doubles) * sizeof(double), &ws));
+  double* d_q = (double*)ws;
+  double* d_S = d_q + n_q;
+  double* d_gm = d_S + n_s;
+  double* d_gc = d_gm + n_om;
+  double* d_gx = d_gc + n_oc;
+  double* d_om = d_gx + n_ox;
+  double* d_oc = d_om + n_om;
+  double* d_ox = d_oc + n_oc;
+  double* d_dq = d_ox + n_ox;
+  double* d_dS = d_dq + n_q;
+  const MomWork w = mm_work(h, k, M, d_dS + n_s);
+  const MomGradWork g = mg_work(k, w, M, d_dS + n_s + w.doubles);
+  std::vector<double> host(n_up, 0.0);
+  for (int r = 0; r < M; ++r) {
+    for (int d = 0; d < D; ++d) {
+      const double raw = Xq[(size_t)r * D + d];
+      host[(size_t)r * D + d] = k.scaled ? (raw - k.in_shift[d]) / k.in_scale[d] : raw;
+    }
+    if (Sq)
+      for (int i = 0; i < nx; ++i)
+        for (int j = 0; j <= i; ++j)
+          host[n_q + ((size_t)r * nx + i) * nx + j] = host[n_q + ((size_t)r * nx + j) * nx + i] = Sq[((size_t)r * nx + i) * nx + j];
+  }
+  if (gmean) memcpy(host.data() + n_q + n_s, gmean, sizeof(double) * n_om);
+  if (gcov) memcpy(host.data() + n_q + n_s + n_om, gcov, sizeof(double) * n_oc);
+  if (gxcov) memcpy(host.data() + n_q + n_s + n_om + n_oc, gxcov, sizeof(double) * n_ox);
+  GPK_CHECK_HIP(h, hipMemcpyAsync(d_q, host.data(), sizeof(double) * n_up, hipMemcpyHostToDevice, h->stream));
+  GPK_TRY(mm_launch(h, k, w, M, d_q, d_S));
+  StageView v{};
+  v.out[0] = d_om; v.out[1] = d_oc; v.out[2] = d_ox;
+  mm_finish(h, k, w, v, M);
+  GPK_LAUNCH_CHECK(h);
+  mm_keep(h, k, w, M, g.keepE, g.keepF);
+  GPK_LAUNCH_CHECK(h);
+  const MomSeeds sd{d_gm, d_gc, d_gx, nullptr, nullptr, nullptr};
+  GPK_TRY(mg_launch(h, k, w, g, M, d_q, sd, MomAdj{}, g.keepE, g.keepF, d_dq, d_dS));
+  GPK_CHECK_HIP(h, hipMemcpyAsync(mean, d_om, sizeof(double) * n_om, hipMemcpyDeviceToHost, h->stream));
+  GPK_CHECK_HIP(h, hipMemcpyAsync(cov, d_oc, sizeof(double) * n_oc, hipMemcpyDeviceToHost, h->stream));
+  GPK_CHECK_HIP(h, hipMemcpyAsync(xcov, d_ox, sizeof(double) * n_ox, hipMemcpyDeviceToHost, h->stream));
+  GPK_CHECK_HIP(h, hipMemcpyAsync(dXq, d_dq, sizeof(double) * n_q, hipMemcpyDeviceToHost, h->stream));
+  GPK_CHECK_HIP(h, hipMemcpyAsync(dSq, d_dS, sizeof(double) * n_s, hipMemcpyDeviceToHost, h->stream));
+  GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
+  return GPK_OK;
+}
+
+// gpk_mm_chain with the backward sweep (z.grad).  Forward, per stage: the chain's five launches (traj, Sigma and the stage outputs
+// keep their bits) and the keep launch; the scaled queries of every stage, E[mu] and the clip indicators stay in the device block,
+// Sigma_h in the horizon's own output (Sigma_0: a second copy in the upload).  Backward, per stage: the forward's setup and row
+// launches again (three) and the adjoint's four, the last of which makes the adjoint step.  Nothing of size N^2 or N R H is kept.
+// One upload [head | S_0 | lam = gx_H | Lam = sym gS_H | gx | sym gS], 6 H + 7 H launches, one synchronisation.
+int gpk_mm_chain_grad(gpk_handle h, const std::string& who, const HostModels& m, const Horizon& z) {
+  if (!h) return GPK_BAD_ARG;
+  MomK k;
+  GPK_TRY(mm_models(h, who, m, true, k));
+  GPK_TRY(gpk_horizon_check(h, who, k.nx, k.D, z));
+  GPK_REQUIRE(h, z.grad, who + "null gradient block");
+  const HorizonGrad& g = *z.grad;
+  const int R = z.R, H = z.H, nx = k.nx, nu = k.D - k.nx;
+  GPK_REQUIRE(h, g.gx && g.dx0, who + "null seed gx or null result dx0");
+  GPK_REQUIRE(h, nu == 0 || g.dU, who + "null result dU");
+  GPK_REQUIRE(h, gpk_finite(g.gx, (size_t)(H + 1) * R * nx) && (!g.gS || gpk_finite(g.gS, (size_t)(H + 1) * R * nx * nx)),
+              who + "the seeds gx and gS must not contain NaN or infinity");
+  const size_t n_om = (size_t)R * k.NO, n_du = (size_t)R * H * nu;
+  HorizonBlock b(k.nx, k.D, z);
+  const size_t n_x = b.n_x, n_s = b.n_s, n_Q = b.n_Q, n_gx = (size_t)H * n_x, n_gS = g.gS ? (size_t)H * n_s : 0;
+  MomWork w{};
+  MomGradWork gw{};
+  double *d_S0, *d_lam, *d_Lam, *d_gx, *d_gS, *d_kE, *d_kF, *d_du;
+  GPK_TRY(gpk_horizon_carve(h, b, [&] {
+    b.head();
+    d_S0 = b.take(n_s); d_lam = b.take(n_x); d_Lam = b.take(n_s); d_gx = b.take(n_gx); d_gS = b.take(n_gS);      // (uploaded)
+    b.outputs(n_om, z.mean, n_om * k.NO, z.cov, n_om * k.D, z.xcov);
+    b.qs = b.take((size_t)(H - 1) * b.n_q);
+    d_kE = b.take((size_t)H * R * 16);
+    d_kF = b.take((size_t)H * R * k.U);
+    d_du = b.take(n_du);
+    w = mm_work(h, k, R, b.base ? b.base + b.at : nullptr);
+    b.take(w.doubles);
+    gw = mg_work(k, w, R, b.base ? b.base + b.at : nullptr);
+    b.take(gw.doubles);
+  }));
+  std::vector<double> host(b.n_head() + n_s + n_x + n_s + n_gx + n_gS, 0.0);
+  gpk_horizon_pack(b, z, k.scaled, k.in_shift, k.in_scale, host.data());
+  double* hS0 = host.data() + b.n_head();
+  double* hlam = hS0 + n_s;
+  double* hLam = hlam + n_x;
+  double* hgx = hLam + n_s;
+  double* hgS = hgx + n_gx;
+  memcpy(hS0, host.data() + n_x, sizeof(double) * n_s);
+  memcpy(hlam, g.gx + (size_t)H * n_x, sizeof(double) * n_x);
+  memcpy(hgx, g.gx, sizeof(double) * n_gx);
+  if (g.gS) {
+    // (gS + gS^T) / 2, the lower triangle formed and mirrored: stage H is the sweep's first Lam
+    for (size_t t = 0; t < (size_t)(H + 1) * R; ++t) {
+      const double* src = g.gS + t * n_Q;
+      double* dst = t < (size_t)H * R ? hgS + t * n_Q : hLam + (t - (size_t)H * R) * n_Q;
+      for (int i = 0; i < nx; ++i)
+        for (int j = 0; j <= i; ++j) dst[i * nx + j] = dst[j * nx + i] = 0.5 * (src[i * nx + j] + src[j * nx + i]);
+    }
+  }
+  GPK_TRY(gpk_horizon_upload(h, b, z, host));
+  for (int s = 0; s < H; ++s) {
+    GPK_TRY(mm_launch(h, k, w, R, b.queries(s), b.S));
+    gpk_time_begin(h, GPK_TIMED_PROPAGATE);
+    mm_finish(h, k, w, gpk_horizon_stage(b, z, s), R);
+    gpk_time_end(h);
+    GPK_LAUNCH_CHECK(h);
+    mm_keep(h, k, w, R, d_kE + (size_t)s * R * 16, d_kF + (size_t)s * R * k.U);
+    GPK_LAUNCH_CHECK(h);
+  }
+  const MomSeeds sd{nullptr, nullptr, nullptr, d_lam, d_Lam, b.lin};
+  for (int s = H - 1; s >= 0; --s) {
+    GPK_TRY(mm_launch_rows(h, k, w, R, b.queries(s), s == 0 ? d_S0 : b.sig + (size_t)(s - 1) * n_s));
+    const MomAdj ad{b.lin, d_gx + (size_t)s * n_x, g.gS ? d_gS + (size_t)s * n_s : nullptr, d_lam, d_Lam, d_du, H, s};
+    GPK_TRY(mg_launch(h, k, w, gw, R, b.queries(s), sd, ad, d_kE + (size_t)s * R * 16, d_kF + (size_t)s * R * k.U, nullptr, nullptr));
+  }
+  return gpk_horizon_finish(h, b, z, {{g.dU, d_du, n_du}, {g.dx0, d_lam, n_x}, {g.dSigma0, d_Lam, n_s}});
+}
+
 extern "C" int gpk_moments_host(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls, double sf2,
                                 const double* y_mean, const double* y_std, const double* Kinv, int64_t Np, int64_t ldk, double kss,
                                 double floor_, int var_includes_noise, double noise, int nx, const double* Xq, const double* Sq, int M,
@@ -753,4 +1525,71 @@ extern "C" int gpk_propagate_mm_host_multi(gpk_handle h, int B, const double* co
   Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean};
   z.cov = cov; z.xcov = xcov;
   return gpk_mm_chain(h, "propagate_mm_host_multi: ", m, z);
+}
+
+// ... with the adjoint: the seeds gmean (M x NO), gcov (M x NO x NO; (g + g^T) / 2 is used) and gxcov (M x NO x D, columns >= nx
+// ignored), null: zero; the results dXq (M x D) and dSq (M x nx x nx)
+extern "C" int gpk_moments_vjp_host(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
+                                    double sf2, const double* y_mean, const double* y_std, const double* Kinv, int64_t Np, int64_t ldk,
+                                    double kss, double floor_, int var_includes_noise, double noise, int nx, const double* Xq,
+                                    const double* Sq, int M, double* mean, double* cov, double* xcov, const double* gmean,
+                                    const double* gcov, const double* gxcov, double* dXq, double* dSq) {
+  if (!h) return GPK_BAD_ARG;
+  const HostModels m{1, P, &X, &alpha, N, D, ls, &sf2, y_mean, y_std, &Kinv, Np, ldk, &kss, floor_, var_includes_noise, &noise, nx,
+                    nullptr, nullptr, nullptr};
+  GPK_REQUIRE(h, X && alpha, "moments_vjp_host: null pointer");
+  GPK_REQUIRE(h, Kinv, "moments_vjp_host: null K^-1 (gpk_wtw of the model's inverse factor)");
+  return gpk_mm_query_vjp(h, "moments_vjp_host: ", m, Xq, Sq, M, mean, cov, xcov, gmean, gcov, gxcov, dXq, dSq);
+}
+
+extern "C" int gpk_moments_vjp_host_multi(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N, int D,
+                                          const double* ls, const double* sf2, const double* y_mean, const double* y_std,
+                                          const double* const* Kinv, int64_t Np, int64_t ldk, const double* kss, double floor_,
+                                          int var_includes_noise, const double* noise, int nx, const double* in_shift,
+                                          const double* in_scale, const double* Xq, const double* Sq, int M, double* mean, double* cov,
+                                          double* xcov, const double* gmean, const double* gcov, const double* gxcov, double* dXq,
+                                          double* dSq) {
+  if (!h) return GPK_BAD_ARG;
+  const HostModels m{B, 1, X, alpha, N, D, ls, sf2, y_mean, y_std, Kinv, Np, ldk, kss, floor_, var_includes_noise, noise, nx,
+                    nullptr, in_shift, in_scale};
+  return gpk_mm_query_vjp(h, "moments_vjp_host_multi: ", m, Xq, Sq, M, mean, cov, xcov, gmean, gcov, gxcov, dXq, dSq);
+}
+
+// ... with the gradient of a horizon cost: the seeds gx, gS and the results dU, dx0, dSigma0 as HorizonGrad describes them
+extern "C" int gpk_propagate_mm_grad_host(gpk_handle h, const double* X, const double* alpha, int64_t N, int D, int P, const double* ls,
+                                          double sf2, const double* y_mean, const double* y_std, const double* Kinv, int64_t Np,
+                                          int64_t ldk, double kss, double floor_, int var_includes_noise, double noise,
+                                          const double* x0, int x0_rows, const double* U, int u_rows, const double* lin,
+                                          const double* Sigma0, int s_rows, const double* Q, int R, int H, double* traj, double* Sigma,
+                                          double* mean, double* cov, double* xcov, const double* gx, const double* gS, double* dU,
+                                          double* dx0, double* dSigma0) {
+  if (!h) return GPK_BAD_ARG;
+  const HostModels m{1, P, &X, &alpha, N, D, ls, &sf2, y_mean, y_std, &Kinv, Np, ldk, &kss, floor_, var_includes_noise, &noise, P,
+                    nullptr, nullptr, nullptr};
+  GPK_REQUIRE(h, X && alpha, "propagate_mm_grad_host: null pointer");
+  GPK_REQUIRE(h, Kinv, "propagate_mm_grad_host: null K^-1 (gpk_wtw of the model's inverse factor)");
+  GPK_REQUIRE(h, P >= 1 && P <= D, "propagate_mm_grad_host: the state dimension P must be in [1, 16] and must not exceed D");
+  const HorizonGrad g{gx, gS, dU, dx0, dSigma0};
+  Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean};
+  z.cov = cov; z.xcov = xcov; z.grad = &g;
+  return gpk_mm_chain_grad(h, "propagate_mm_grad_host: ", m, z);
+}
+
+extern "C" int gpk_propagate_mm_grad_host_multi(gpk_handle h, int B, const double* const* X, const double* const* alpha, int64_t N,
+                                                int D, const double* ls, const double* sf2, const double* y_mean, const double* y_std,
+                                                const double* const* Kinv, int64_t Np, int64_t ldk, const double* kss, double floor_,
+                                                int var_includes_noise, const double* noise, int nx, const int* coord,
+                                                const double* in_shift, const double* in_scale, const double* x0, int x0_rows,
+                                                const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows,
+                                                const double* Q, int R, int H, double* traj, double* Sigma, double* mean, double* cov,
+                                                double* xcov, const double* gx, const double* gS, double* dU, double* dx0,
+                                                double* dSigma0) {
+  if (!h) return GPK_BAD_ARG;
+  GPK_REQUIRE(h, coord, "propagate_mm_grad_host_multi: null pointer");
+  const HostModels m{B, 1, X, alpha, N, D, ls, sf2, y_mean, y_std, Kinv, Np, ldk, kss, floor_, var_includes_noise, noise, nx, coord,
+                    in_shift, in_scale};
+  const HorizonGrad g{gx, gS, dU, dx0, dSigma0};
+  Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean};
+  z.cov = cov; z.xcov = xcov; z.grad = &g;
+  return gpk_mm_chain_grad(h, "propagate_mm_grad_host_multi: ", m, z);
 }

@@ -999,6 +999,26 @@ class DeviceGP:
             x0, U, lin, S0, Q, R, H, ((P,), (P, P), (P, D)) if stages else None)
         return (traj, Sigma, *more)
 
+    def moments_vjp_host(self, y_mean, y_std, kss, floor, Xq, Sq, gmean, gcov, gxcov):
+        """One C call (gpk_moments_vjp_host): `moments_host` with the seeds on mean, cov and xcov (arrays as
+        `propagate.check_moment_seeds` returns them, None: zero) -> (mean, cov, xcov, dX (M, D), dSigma (M, nx, nx)); the first
+        three with the bits of `moments_host` - ten launches, one synchronisation."""
+        M, nx = Xq.shape[0], Sq.shape[1]
+        mean, cov, xcov = np.empty((M, self.P)), np.empty((M, self.P, self.P)), np.empty((M, self.P, self.D))
+        dX, dS = np.empty((M, self.D)), np.empty((M, nx, nx))
+        self._moments_call("gpk_moments_vjp_host", y_mean, y_std, float(kss), float(floor), 0, 0.0, nx, _hp(Xq), _hp(Sq), M, _hp(mean),
+                           _hp(cov), _hp(xcov), _hp(gmean), _hp(gcov), _hp(gxcov), _hp(dX), _hp(dS))
+        return mean, cov, xcov, dX, dS
+
+    def propagate_mm_grad_host(self, y_mean, y_std, kss, floor, x0, U, lin, S0, Q, R, H, gx, gS):
+        """One C call per horizon with the gradient of a horizon cost through exact moments (gpk_propagate_mm_grad_host): traj,
+        Sigma with the bits of `propagate_mm_host`, dU (R, H, nu), dx0 (R, P), dSigma0 (R, P, P) - six launches per stage forward,
+        seven backward, one synchronisation."""
+        traj, Sigma, more = horizon_call(
+            lambda *t: self._moments_call("gpk_propagate_mm_grad_host", y_mean, y_std, float(kss), float(floor), 0, 0.0, *t),
+            x0, U, lin, S0, Q, R, H, seeds=(gx, gS))
+        return (traj, Sigma, *more)
+
     # ---- gated serving: the one place every fp32 surface (estimator, sharded predictor, package GP, per-axis models) goes
     # through -------------------------------------------------------------------------------------------------------------
     def _rows64(self, Xq, q, rows):

@@ -468,6 +468,57 @@ class GaussianProcessRegressor:
         kss = comp.sf2 + ((comp.noise or 0.0) if var_includes_noise else 0.0)
         return dev.moments_host(self._y_train_mean, self._y_train_std, kss, 0.0, X, S)
 
+    def predict_moments_vjp(self, X, Sigma, grad_mean=None, grad_cov=None, grad_xcov=None, var_includes_noise=False):
+        """`predict_moments` with the vector-Jacobian product of its results: for l = <grad_mean, mean> + <grad_cov, cov> +
+        <grad_xcov, xcov> returns (mean, cov, xcov, dX (M, D) = dl/dX, dSigma (M, nx, nx) = dl/dSigma) - the controls' columns of
+        dX included, dSigma symmetric bit for bit.  grad_mean (M, P), grad_cov (M, P, P), grad_xcov (M, P, D), None: zero; the
+        entries are taken as independent: (g + g^T) / 2 is used for grad_cov, as for `propagate_gradient`'s grad_Sigma, and the
+        columns >= nx of grad_xcov (where xcov is zero) are ignored.  The expected variance enters through the derivative of what
+        is computed: nothing where its clip at zero is active.  mean, cov and xcov have the bits of `predict_moments`.  One C call
+        (`gpk_moments_vjp_host`: ten launches, one synchronisation); limits and errors as `predict_moments`."""
+        from . import propagate as _pg
+        if not hasattr(self, "X_train_"):
+            raise RuntimeError("This GaussianProcessRegressor instance is not fitted yet.")
+        X, S, M, nx = _pg.check_gaussian_queries(X, Sigma, self.n_features_in_)
+        gm, gc, gxc = _pg.check_moment_seeds(grad_mean, grad_cov, grad_xcov, M, self._yn.shape[1], self.n_features_in_)
+        self._ensure_device()
+        dev = self._dev
+        if not dev.moments_ok():
+            raise ValueError("predict_moments_vjp needs the small-batch path: at most 16384 training rows, D <= 16, small_path != 0")
+        comp = self.kernel_.components()
+        kss = comp.sf2 + ((comp.noise or 0.0) if var_includes_noise else 0.0)
+        return dev.moments_vjp_host(self._y_train_mean, self._y_train_std, kss, 0.0, X, S, gm, gc, gxc)
+
+    def propagate_moments_gradient(self, x0, U, lin, grad_traj, grad_Sigma=None, Sigma0=None, process_noise=None,
+                                   var_includes_noise=False, route="auto"):
+        """`propagate(method="moment")` with the gradient of a differentiable horizon cost l(traj, Sigma) with respect to the
+        controls, the start state and the start covariance, through the exact moments of every stage (`propagate`'s module
+        docstring has the sweep).  Arguments and results as `propagate_gradient`: (traj, Sigma, dU (R, H, nu), dx0 (R, P),
+        dSigma0 (R, P, P)), traj and Sigma with the bits of `propagate(method="moment")`.  One C call per horizon
+        (`gpk_propagate_mm_grad_host`: six launches per stage forward, seven backward, one synchronisation); route="host": the
+        same sweep on the host over `predict_moments` and `predict_moments_vjp`.  ValueError where `propagate(method="moment")`
+        raises one, and for seeds of a wrong shape or with NaN or infinity."""
+        from . import propagate as _pg
+        if not hasattr(self, "X_train_"):
+            raise RuntimeError("This GaussianProcessRegressor instance is not fitted yet.")
+        P, D = self._yn.shape[1], self.n_features_in_
+        x0, U, lin, S0, Q, R, H = _pg.check_horizon(x0, U, lin, P, D, Sigma0, process_noise)
+        gx, gS = _pg.check_seeds(grad_traj, grad_Sigma, R, H, P)
+        _pg.check_method("moment", 1, "propagate_moments_gradient", Sigma0=S0, process_noise=Q)
+        _pg.check_route(route)
+        self._ensure_device()
+        dev = self._dev
+        if not dev.moments_ok():
+            raise ValueError("propagate_moments_gradient needs the small-batch path: at most 16384 training rows, small_path != 0")
+        if route == "host":
+            return _pg.host_adjoint_moments(
+                lambda q, S: self.predict_moments(q, S, var_includes_noise=var_includes_noise),
+                lambda q, S, gm, gc, gxc: self.predict_moments_vjp(q, S, gm, gc, gxc, var_includes_noise=var_includes_noise),
+                list(range(P)), x0, U, lin, S0, Q, R, H, gx, gS)
+        comp = self.kernel_.components()
+        kss = comp.sf2 + ((comp.noise or 0.0) if var_includes_noise else 0.0)
+        return dev.propagate_mm_grad_host(self._y_train_mean, self._y_train_std, kss, 0.0, x0, U, lin, S0, Q, R, H, gx, gS)
+
     def propagate(self, x0, U, lin, Sigma0=None, process_noise=None, var_includes_noise=False, return_stages=False,
                   route="auto", order=1, method="linear"):
         """The posterior's own closed-loop horizon: the mean trajectory under the learned dynamics and the state covariance that

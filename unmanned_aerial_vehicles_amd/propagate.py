@@ -46,6 +46,16 @@ Sigma_h J_x^T, which gives the recursion at the top).  One C call per horizon (`
 stage, one synchronisation); `host_loop_moments` is the same recursion over a class's `predict_moments`.  The sparse classes
 serve it as `predict_moments` / `propagate_moments` (the engine on (Z, alpha_u, Q = Kuu^-1 - Sigma~), `gpk_sparse_propagate_mm[_multi]`);
 their `propagate(method="moment")` and every `propagate_gradient` refuse it (`refuse_moment`).
+
+`propagate_moments_gradient` of the exact classes is the gradient of a horizon cost through that recursion.  `predict_moments_vjp`
+returns, with the moments of a batch of Gaussian queries, the products of the seeds (on mean, cov and xcov) with their Jacobians
+with respect to the query and its covariance (m~, S~; DESIGN.md section 4, K11, has the closed form).  With lam_{h+1}, Lam_{h+1} the
+incoming adjoints the stage's seeds are E^T lam on the mean, E^T Lam E on cov and 2 E^T Lam A0 on the state columns of xcov, and
+
+    g_q = [I 0]^T lam + lin^T lam + m~,   lam_h = gx_h + g_q[:nx],   dU_h = g_q[nx:],   Lam_h = sym(gS_h) + A0^T Lam A0 + S~
+
+One C call per horizon (`gpk_propagate_mm_grad_host[_multi]`: six launches per stage forward, seven backward, one
+synchronisation); `host_adjoint_moments` is the same sweep on the host over `predict_moments_vjp`.
 """
 from __future__ import annotations
 
@@ -219,7 +229,8 @@ def refuse_moment(method, what):
         raise ValueError(f"method must be 'linear' or 'moment', got {method!r}")
     if method == "moment":
         raise ValueError(f"method='moment' is not supported by {what}: the sparse classes serve exact moment matching through "
-                         "predict_moments / propagate_moments, and moment matching has no adjoint chain")
+                         "predict_moments / propagate_moments, and the gradient through exact moments is "
+                         "propagate_moments_gradient of the exact classes")
 
 
 def check_psd(S, what):
@@ -362,6 +373,56 @@ def host_adjoint(stage, hess_stage, coord, x0, U, lin, S0, Q, R, H, gx, gS):
     return traj, Sigma, dU, lam, Lam
 
 
+def check_moment_seeds(grad_mean, grad_cov, grad_xcov, M, NO, D):
+    """The seeds of `predict_moments_vjp` as contiguous float64 arrays or None: grad_mean (M, NO), grad_cov (M, NO, NO), grad_xcov
+    (M, NO, D); with M = 1 the leading axis may be left out.  ValueError on a wrong shape, NaN or infinity."""
+    out = []
+    for name, g, shape in (("grad_mean", grad_mean, (NO,)), ("grad_cov", grad_cov, (NO, NO)), ("grad_xcov", grad_xcov, (NO, D))):
+        if g is not None:
+            g = np.asarray(g, dtype=np.float64)
+            if M == 1 and g.shape == shape:
+                g = g[None]
+            if g.shape != (M,) + shape:
+                raise ValueError(f"predict_moments_vjp: {name} must be {(M,) + shape}")
+            if not np.isfinite(g).all():
+                raise ValueError(f"predict_moments_vjp: {name} contains NaN or infinity")
+            g = np.ascontiguousarray(g)
+        out.append(g)
+    return tuple(out)
+
+
+def host_adjoint_moments(stage, stage_vjp, coord, x0, U, lin, S0, Q, R, H, gx, gS):
+    """The moment recursion (`host_loop_moments` over `stage`) and its backward sweep on the host.  stage_vjp(q (R, D) raw, Sigma
+    (R, nx, nx), gmean (R, NO), gcov (R, NO, NO), gxcov (R, NO, D)) -> (.., dq (R, D), dSigma (R, nx, nx)) as `predict_moments_vjp`
+    returns them (its last two results are read).  Returns traj, Sigma (as `host_loop_moments`), dU (R, H, nu), dx0 (R, nx),
+    dSigma0 (R, nx, nx)."""
+    nx, D = lin.shape
+    NO = len(coord)
+    traj, Sigma, _ = host_loop_moments(stage, coord, x0, U, lin, S0, Q, R, H)
+    A0 = np.eye(nx) + lin[:, :nx]
+    E = np.zeros((nx, NO))
+    for o, c in enumerate(coord):
+        E[c, o] = 1.0
+    F0 = np.concatenate([np.eye(nx), np.zeros((nx, D - nx))], axis=1) + lin
+    lam = gx[H].copy()
+    Lam = _sym(gS[H]) if gS is not None else np.zeros((R, nx, nx))
+    dU = np.zeros((R, H, D - nx))
+    for h in range(H - 1, -1, -1):
+        q = np.ascontiguousarray(np.concatenate([traj[h], np.broadcast_to(U[:, h], (R, D - nx))], axis=1))
+        gxcov = np.zeros((R, NO, D))
+        gxcov[:, :, :nx] = 2.0 * (E.T @ Lam @ A0)
+        out = stage_vjp(q, np.ascontiguousarray(Sigma[h]), np.ascontiguousarray(lam @ E), np.ascontiguousarray(E.T @ Lam @ E), gxcov)
+        dq, dS = np.reshape(out[-2], (R, D)), np.reshape(out[-1], (R, nx, nx))
+        gq = lam @ F0 + dq
+        lam = gx[h] + gq[:, :nx]
+        dU[:, h] = gq[:, nx:]
+        Lam = A0.T @ Lam @ A0 + dS
+        if gS is not None:
+            Lam = Lam + _sym(gS[h])
+        Lam = _sym(Lam)
+    return traj, Sigma, dU, lam, Lam
+
+
 def nominal_adjoint(lin, R, H, gx, gS):
     """The sweep through the nominal dynamics alone (A = I + lin_x, F = [I 0] + lin, no variance terms): the wrappers'
     fallback.  Returns dU (R, H, nu), dx0 (R, nx)."""
@@ -399,6 +460,17 @@ def model_horizon(model, x0, U, lin, order=1, method="linear", **kw):
     if method == "moment" and callable(getattr(model, "propagate_moments", None)):
         return model.propagate_moments(x0, U, lin, **kw)
     return model.propagate(x0, U, lin, route=wrapper_route(model), order=order, method=method, **kw)
+
+
+def model_moments_gradient(model, x0, U, lin, grad_traj, grad_Sigma, **kw):
+    """The gradient through exact moments that a control-loop wrapper asks of its model: `propagate_moments_gradient` of an exact
+    class; ValueError for a class without it (the sparse ones: their moments have no adjoint yet).  kw: for a batch, coord and the
+    scalers."""
+    fn = getattr(model, "propagate_moments_gradient", None)
+    if not callable(fn):
+        raise ValueError(f"{type(model).__name__} has no gradient through exact moments (propagate_moments_gradient is a method "
+                         "of the exact classes)")
+    return fn(x0, U, lin, grad_traj, grad_Sigma, **kw)
 
 
 def chain_sizes_ok(m, D, nx):

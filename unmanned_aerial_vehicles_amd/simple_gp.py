@@ -335,13 +335,15 @@ class SimpleQuadrotorGP:
             print(f"GP horizon propagation failed: {e}")
             return _pg.horizon_layout(*_pg.nominal_horizon(nominal, lin, Sigma0, process_noise), single)
 
-    def horizon_gradient(self, state, U_guess, dt, grad_traj, grad_Sigma=None):
+    def horizon_gradient(self, state, U_guess, dt, grad_traj, grad_Sigma=None, method="linear"):
         """`propagate_horizon` (first order, Sigma0 = 0, no process noise) with the gradient of a horizon cost l(X, Sigma) with
         respect to the controls and the start state, in one call (`GaussianProcessRegressor.propagate_gradient`).  grad_traj
         (N + 1, 6) = dl/dx_k, grad_Sigma (N + 1, 6, 6) = dl/dSigma_k (default zero); U_guess (4, N) -> X (6, N + 1), Sigma
         (N + 1, 6, 6), dU (N, 4), dx0 (6,); U_guess (R, 4, N) with seeds (N + 1, R, ...) -> a leading R on every result.
         Untrained, or on any failure (printed): the nominal horizon and the sweep through the nominal dynamics (A = I + lin_x,
-        no variance terms) - it never raises into the control loop."""
+        no variance terms) - it never raises into the control loop.  method="moment": the horizon of `propagate_horizon(method=
+        "moment")` and the gradient through its exact moments (`GaussianProcessRegressor.propagate_moments_gradient`); a SparseGP
+        model has no such gradient: the nominal fallback, with the reason printed."""
         from . import propagate as _pg
         state, U, lin, nominal, single = _pg.horizon_inputs(self._nominal_dynamics, state, U_guess, dt)
         R, N = U.shape[0], U.shape[1]
@@ -349,8 +351,12 @@ class SimpleQuadrotorGP:
             print("GP horizon gradient: the model is not trained - nominal trajectory and sweep")
             return _pg.nominal_gradient(nominal, lin, grad_traj, single)
         try:
-            traj, Sigma, dU, dx0, _ = self.gp_model.propagate_gradient(state, U, lin, grad_traj, grad_Sigma,
-                                                                       route=_pg.wrapper_route(self.gp_model))
+            _pg.check_method(method)
+            if method == "moment":
+                traj, Sigma, dU, dx0, _ = _pg.model_moments_gradient(self.gp_model, state, U, lin, grad_traj, grad_Sigma)
+            else:
+                traj, Sigma, dU, dx0, _ = self.gp_model.propagate_gradient(state, U, lin, grad_traj, grad_Sigma,
+                                                                           route=_pg.wrapper_route(self.gp_model))
             if not all(np.isfinite(a).all() for a in (traj, Sigma, dU, dx0)):
                 raise FloatingPointError("non-finite trajectory, covariance or gradient")
             self.prediction_count += R * N

@@ -638,16 +638,19 @@ class PreTrainedGP:
             print(f"GP horizon propagation failed: {e}")
             return _pg.horizon_layout(*_pg.nominal_horizon(nominal, lin, Sigma0, process_noise), single)
 
-    def horizon_gradient(self, state, U_guess, dt, grad_traj, grad_Sigma=None):
+    def horizon_gradient(self, state, U_guess, dt, grad_traj, grad_Sigma=None, method="linear"):
         """`SimpleQuadrotorGP.horizon_gradient` for the per-axis models, in raw units: `propagate_horizon` (first order, Sigma0 =
         0, no process noise) with the gradient of a horizon cost with respect to the controls and the start state.  Models
         that share inputs and scaler: ONE call for the horizon (`BatchedARDGP.propagate_gradient`; a file of sparse models:
         `BatchedSparseGP.propagate_gradient`, its one-call chain where `propagate_ok()` holds).  Same shapes and results as
         `SimpleQuadrotorGP.horizon_gradient`.  Not loaded, models that do not share inputs and scaler, or any failure
-        (printed): the nominal horizon and the sweep through the nominal dynamics - it never raises into the control loop."""
+        (printed): the nominal horizon and the sweep through the nominal dynamics - it never raises into the control loop.
+        method="moment": the gradient through the exact moments of every stage (`BatchedARDGP.propagate_moments_gradient`, one
+        call); a file of sparse models has no such gradient: the nominal fallback, with the reason printed."""
         from . import propagate as _pg
         state, U, lin, nominal, single = _pg.horizon_inputs(GPTrainer._nominal_dynamics, state, U_guess, dt)
         try:
+            _pg.check_method(method)
             if not self.is_loaded:
                 raise RuntimeError("no models are loaded")
             fused = self._fused()
@@ -655,11 +658,12 @@ class PreTrainedGP:
                 raise RuntimeError("the models do not share inputs and scaler")
             bg, names = fused
             sys_ = [self.scalers_y[n] for n in names]
-            traj, Sigma, dU, dx0, _ = bg.propagate_gradient(
-                state, U, lin, grad_traj, grad_Sigma, coord=[OUTPUT_NAMES.index(n) for n in names],
-                in_scaler=self.scalers_X[names[0]],
-                out_scaler=([float(np.ravel(s.mean_)[0]) for s in sys_], [float(np.ravel(s.scale_)[0]) for s in sys_]),
-                route=_pg.wrapper_route(bg))
+            kw = dict(coord=[OUTPUT_NAMES.index(n) for n in names], in_scaler=self.scalers_X[names[0]],
+                      out_scaler=([float(np.ravel(s.mean_)[0]) for s in sys_], [float(np.ravel(s.scale_)[0]) for s in sys_]))
+            if method == "moment":
+                traj, Sigma, dU, dx0, _ = _pg.model_moments_gradient(bg, state, U, lin, grad_traj, grad_Sigma, **kw)
+            else:
+                traj, Sigma, dU, dx0, _ = bg.propagate_gradient(state, U, lin, grad_traj, grad_Sigma, route=_pg.wrapper_route(bg), **kw)
             if not all(np.isfinite(a).all() for a in (traj, Sigma, dU, dx0)):
                 raise FloatingPointError("non-finite trajectory, covariance or gradient")
             return _pg.gradient_layout(traj, Sigma, dU, dx0, single)
