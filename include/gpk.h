@@ -98,7 +98,12 @@ GPK_API int64_t gpk_padded(int64_t n);
  * `GPKDERIV mean_grad|mean_grad_multi|var_grad|mean_hess|mean_hess_multi N D P|B mc d4K ps|bsG ngN nrbR nqb|ncbQ granG sS chunkC`: mc
  * queries in the panel, the D4 = K and PS | BS = G instantiation, N output or model groups x R row blocks of the Hessian's triangle
  * (the third grid dimension), Q query blocks, S training chunks of C rows, C a multiple of G (var_grad: P = 1, ps1 ng1 nrb1,
- * query blocks of 128 columns, gran 64) - to stderr, one line per launch),
+ * query blocks of 128 columns, gran 64) - and of every batch of Gaussian queries of the moment-matching entries, K11 (a query call, or
+ * one stage of a chain; the backward sweep of a gradient entry writes one `adj` line per stage) -
+ * `GPKMM fwd|adj B P D nx N R cusC gG uU nqQ splitS nrwW nvV pP|pcP`: R queries, C the handle's CU count, G workgroups per pair x U
+ * pairs x Q groups of queries in the pair launch (S = 1: the kernel with the query dimension), W row blocks of 256, V sums per slot
+ * (fwd: 1 + P (P + 1) / 2, adj: 1 + D + nx (nx + 1) / 2), the forward pair kernel's P or the adjoint's alpha-tile capacity PC -
+ * to stderr, one line per launch),
  * "k5_log" (1: the form of every 16-bit variance launch - gpk_predict_var_inv_split2 / gpk_predict_mean_var_split2: `GPKK5 direct rowsR
  * ntmTA ntnB nstS padP gridG`, gpk_predict_var_inv_split: `GPKK5 split rowsR ntmTA ntnB nstS pad0 gridG`; R the tile's rows, A x B tiles,
  * S super-tiles, P tile slots per band of the walk - to stderr, one line per launch),

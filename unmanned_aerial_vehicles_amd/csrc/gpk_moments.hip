@@ -540,6 +540,9 @@ void mm_pair_launch(gpk_handle h, const MomK& k, const MomWork& w, int R) {
 
 // The four launches ahead of the finishing one: d_q (R x D scaled queries) and d_S (R x nx x nx raw covariances) on the device.
 int mm_launch(gpk_handle h, const MomK& k, const MomWork& w, int R, const double* d_q, const double* d_S) {
+  if (h->gram_log)   // option gram_log = 1: the form this batch's launches take (the tests assert it per case)
+    fprintf(stderr, "GPKMM fwd %d %d %d %d %lld %d cus%d g%d u%d nq%d split%d nrw%d nv%d p%d\n", k.B, k.P, k.D, k.nx, k.N, R, gpk_cus(h),
+            w.G_, k.U, w.NQ, w.NQ > 1 ? 1 : 0, w.nrw, w.NV, k.P);
   hipLaunchKernelGGL(moments_setup_kernel, dim3((unsigned)R, (unsigned)(k.B + k.U)), dim3(64), 0, h->stream, k, d_S, w.Sz, w.Bm, w.cm,
                      w.G, w.cl);
   GPK_LAUNCH_CHECK(h);
@@ -1221,14 +1224,18 @@ void mg_pair_launch(gpk_handle h, const MomK& k, const MomWork& w, const MomGrad
 // whose E[mu] and clip indicators are in keepE / keepF: d_q the scaled queries.
 int mg_launch(gpk_handle h, const MomK& k, const MomWork& w, const MomGradWork& g, int R, const double* d_q, const MomSeeds& sd,
               const MomAdj& ad, const double* keepE, const double* keepF, double* dq, double* dS) {
+  const int PC = k.P == 1 ? 1 : k.P <= 8 ? 8 : 16;      // the capacity of the pair kernel's alpha tiles: what is logged is what is launched
+  if (h->gram_log)
+    fprintf(stderr, "GPKMM adj %d %d %d %d %lld %d cus%d g%d u%d nq%d split%d nrw%d nv%d pc%d\n", k.B, k.P, k.D, k.nx, k.N, R, gpk_cus(h),
+            w.G_, k.U, w.NQ, w.NQ > 1 ? 1 : 0, w.nrw, g.NV, PC);
   hipLaunchKernelGGL(moments_grad_setup_kernel, dim3((unsigned)R, (unsigned)(k.B + k.U)), dim3(64), 0, h->stream, k, sd, R,
                      (const double*)w.Sz, (const double*)w.Bm, (const double*)w.G, keepE, keepF, g.gs, g.gsV, g.RiT, g.kap);
   GPK_LAUNCH_CHECK(h);
   hipLaunchKernelGGL(moments_grad_row_kernel, dim3((unsigned)w.nrw, (unsigned)R, (unsigned)k.B), dim3(256), 0, h->stream, k, g.NV, d_q,
                      (const double*)w.Bm, (const double*)w.cm, (const double*)g.gs, g.gp, g.rowpart);
   GPK_LAUNCH_CHECK(h);
-  if (k.P == 1) mg_pair_launch<1>(h, k, w, g, R);
-  else if (k.P <= 8) mg_pair_launch<8>(h, k, w, g, R);
+  if (PC == 1) mg_pair_launch<1>(h, k, w, g, R);
+  else if (PC == 8) mg_pair_launch<8>(h, k, w, g, R);
   else mg_pair_launch<16>(h, k, w, g, R);
   GPK_LAUNCH_CHECK(h);
   hipLaunchKernelGGL(moments_grad_finish_kernel, dim3((unsigned)R), dim3(256), 0, h->stream, k, ad, R, w.G_, w.nrw, g.NV,
