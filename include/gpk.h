@@ -110,7 +110,8 @@ GPK_API int64_t gpk_padded(int64_t n);
  * "sparse_panel" / "sparse_slabs" (the statistics pass of the sparse model, K9:
  * rows per panel and k-slabs per panel product; 0 = the built-in rule), "moments_query_groups" (the pair launch of the moment-matching
  * entries, K11: 0 = as many groups of queries as bring it to two workgroups per CU, n >= 1 = at most n, 1 = no split; bit-identical
- * results), "debug_fill" (1: the handle's scratch and serving work area are overwritten with NaN bytes at every request - the test
+ * results), "moments_tape_mb" (the gradient chains of the sparse moment entries keep every stage's work block while H blocks fit this
+ * many MiB, 9 H launches instead of 13 H: default 1024, 0 = never; bit-identical results), "debug_fill" (1: the handle's scratch and serving work area are overwritten with NaN bytes at every request - the test
  * suite runs with it).  Used by the A/B timings and by the tests that pin a fast path to its plain form.
  * gpk_set_option_str: "ptile_trace_path" - the NEXT one-launch factorisation writes its per-task time stamps to that file
  * (debugging aid, tools/exp_ptile_trace.py).                                                                          */
@@ -1454,6 +1455,50 @@ GPK_API int gpk_sparse_propagate_mm_multi(gpk_handle h, int B, const gpk_handle*
                                           const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows,
                                           const double* Q, int R, int H, double* traj, double* Sigma, double* mean, double* cov,
                                           double* xcov);
+/* ... with the adjoint of the moments, on the same (Z, alpha_u, Q): the gradient of a horizon cost through the exact moments of the
+ * sparse posteriors.  Q is a constant of the adjoint, as K^-1 is for the exact models.
+ * gpk_sparse_moments_vjp[_multi]: the arguments of gpk_sparse_moments[_multi] followed by (gmean, gcov, gxcov, dXq, dSq) with the
+ *   meaning, shapes and NULL rules of gpk_moments_vjp_host[_multi]: host seeds gmean (M x NO), gcov (M x NO x NO; (g + g^T) / 2 is
+ *   used), gxcov (M x NO x D; columns >= nx ignored), NULL: zero; results dXq (M x D) and dSq (M x nx x nx, symmetric bit for bit)
+ *   in raw units.  mean, cov and xcov have the BITS of gpk_sparse_moments[_multi].  Ten launches, one upload, five downloads, ONE
+ *   synchronisation.
+ * gpk_sparse_propagate_mm_grad[_multi]: the arguments of gpk_sparse_propagate_mm[_multi] followed by (gx, gS, dU, dx0, dSigma0) as
+ *   gpk_propagate_mm_grad_host[_multi] has them: gx (H + 1, R, nx), gS (H + 1, R, nx, nx; NULL: zero), dU (R, H, nu; NULL only when
+ *   nu = 0), dx0 (R, nx), dSigma0 (R, nx, nx; may be NULL).  traj, Sigma and the stage outputs have the BITS of
+ *   gpk_sparse_propagate_mm[_multi].
+ * Launches of the chain: at the sparse sizes a horizon is its launches and a stage's work block (the set-up results, the row
+ *   vectors and the slots of the sums; about B^2 R mp 17 doubles and small terms) is a few megabytes, so these entries keep every
+ *   stage's block in a region of its own - the tape - where H blocks fit option "moments_tape_mb" (default 1024 MiB, 0 = never; a
+ *   memory cap): forward the five launches of gpk_sparse_propagate_mm per stage and no keep launch; backward four per stage, the
+ *   set-up launch forming E[mu] and the clip indicators itself from the stage's slots in the keep launch's order
+ *   (moments_grad_setup_taped_kernel: 0 bytes of scratch, no spill, no atomics) - 5 H + 4 H launches.  Beyond the cap: the
+ *   6 H + 7 H sweep of the exact entries.  One upload and ONE synchronisation either way.  The tape moves buffers and fuses one
+ *   reduction in its order; it reorders no sum: results are bit-identical with and without it, repeatable bit for bit, and rollout
+ *   r has the bits of that rollout alone.  Option "gram_log": one line `GPKMT tape<0|1> h<H> stage<doubles> launches<n>` per
+ *   chain, ahead of its GPKMM lines.  The exact entries do not ask for the tape.
+ * GPK_BAD_ARG (with a message, before any launch - Q included - and with the outputs untouched): the refusals of the forward
+ *   siblings, a seed with NaN or infinity, a NULL dXq or dSq, a NULL gx, dx0 or (nu > 0) dU.
+ *   Replaces: nothing in the reference; here, the linearised gradient of gpk_sparse_propagate_grad where the controller optimises
+ *   over the moment-matched horizon.                                                                                            */
+GPK_API int gpk_sparse_moments_vjp(gpk_handle h, int var_includes_noise, int nx, const double* Xq, const double* Sq, int M,
+                                   double* mean, double* cov, double* xcov, const double* gmean, const double* gcov,
+                                   const double* gxcov, double* dXq, double* dSq);
+GPK_API int gpk_sparse_moments_vjp_multi(gpk_handle h, int B, const gpk_handle* models, int var_includes_noise, int nx,
+                                         const double* in_shift, const double* in_scale, const double* out_shift,
+                                         const double* out_scale, const double* Xq, const double* Sq, int M, double* mean,
+                                         double* cov, double* xcov, const double* gmean, const double* gcov, const double* gxcov,
+                                         double* dXq, double* dSq);
+GPK_API int gpk_sparse_propagate_mm_grad(gpk_handle h, int var_includes_noise, const double* x0, int x0_rows, const double* U,
+                                         int u_rows, const double* lin, const double* Sigma0, int s_rows, const double* Q, int R,
+                                         int H, double* traj, double* Sigma, double* mean, double* cov, double* xcov,
+                                         const double* gx, const double* gS, double* dU, double* dx0, double* dSigma0);
+GPK_API int gpk_sparse_propagate_mm_grad_multi(gpk_handle h, int B, const gpk_handle* models, int var_includes_noise, int nx,
+                                               const int* coord, const double* in_shift, const double* in_scale,
+                                               const double* out_shift, const double* out_scale, const double* x0, int x0_rows,
+                                               const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows,
+                                               const double* Q, int R, int H, double* traj, double* Sigma, double* mean,
+                                               double* cov, double* xcov, const double* gx, const double* gS, double* dU,
+                                               double* dx0, double* dSigma0);
 
 #ifdef __cplusplus
 }

@@ -214,6 +214,11 @@ SIGNATURES["gpk_sparse_propagate_mm_multi"] = (_int, list(SIGNATURES["gpk_sparse
 SIGNATURES["gpk_sparse_moments"] = (_int, [_vp, _int, _int, _dp, _dp, _int, _dp, _dp, _dp])
 SIGNATURES["gpk_sparse_moments_multi"] = (_int, [_vp, _int, C.POINTER(_vp), _int, _int, _dp, _dp, _dp, _dp, _dp, _dp, _int, _dp, _dp,
                                                  _dp])
+# ... with their adjoint: (gmean, gcov, gxcov, dXq, dSq) behind the query entries, (gx, gS, dU, dx0, dSigma0) behind the chains
+SIGNATURES["gpk_sparse_moments_vjp"] = (_int, SIGNATURES["gpk_sparse_moments"][1] + [_dp] * 5)
+SIGNATURES["gpk_sparse_moments_vjp_multi"] = (_int, SIGNATURES["gpk_sparse_moments_multi"][1] + [_dp] * 5)
+SIGNATURES["gpk_sparse_propagate_mm_grad"] = (_int, SIGNATURES["gpk_sparse_propagate_mm"][1] + [_dp] * 5)
+SIGNATURES["gpk_sparse_propagate_mm_grad_multi"] = (_int, SIGNATURES["gpk_sparse_propagate_mm_multi"][1] + [_dp] * 5)
 
 _lib = None
 

@@ -45,6 +45,8 @@ struct gpk_context {
   int cus = 0;                   // compute units of the device (read once: gpk_cus)
   int moments_query_groups = 0;  // moment matching's pair launch: groups of queries as a grid dimension (0: as many as bring the launch to
                                  // two workgroups per CU, gpk_moments.hip; n >= 1: at most n, so 1 is the launch without the split)
+  int moments_tape_mb = 1024;    // the moment chain's gradient, where the caller asks for the tape (the sparse entries): the stages' work
+                                 // blocks are kept, 5 H + 4 H launches, while H blocks fit this many MiB (0: never; a memory cap)
   int trtri_levels = 1;      // gpk_trtri: one batched launch per level for power-of-two tile counts
   int trsm256 = 1;           // potrf: fused 256-wide base of the triangular solve
   int small_path = 1;        // gpk_predict_host: two-launch small-batch kernels (option small_path = 0 disables)
@@ -466,10 +468,12 @@ int gpk_mm_chain(gpk_handle h, const std::string& who, const HostModels& m, cons
 // model without new kernels.  gpk_mm_query_vjp: gpk_mm_query (mean, cov, xcov keep its bits) with the seeds gmean (M x NO), gcov (M x
 // NO x NO) and gxcov (M x NO x D), null: zero, and the results dXq (M x D), dSq (M x nx x nx, symmetric bit for bit); ten launches,
 // one upload, one synchronisation.  gpk_mm_chain_grad: gpk_mm_chain (its bits) with z.grad - six launches per stage forward, seven
-// backward, one upload, one synchronisation.  A non-finite seed or a null result: GPK_BAD_ARG before anything is launched.
+// backward, one upload, one synchronisation; with tape (the sparse entries) and H work blocks within option moments_tape_mb every
+// stage keeps its block: five forward, four backward, the same bits.  A non-finite seed or a null result: GPK_BAD_ARG before anything
+// is launched.
 int gpk_mm_query_vjp(gpk_handle h, const std::string& who, const HostModels& m, const double* Xq, const double* Sq, int M, double* mean,
                      double* cov, double* xcov, const double* gmean, const double* gcov, const double* gxcov, double* dXq, double* dSq);
-int gpk_mm_chain_grad(gpk_handle h, const std::string& who, const HostModels& m, const Horizon& z);
+int gpk_mm_chain_grad(gpk_handle h, const std::string& who, const HostModels& m, const Horizon& z, bool tape = false);
 // ... as one-call serving (gpk_serve.hip): host queries in, host results out through the pinned, mapped block, one
 // synchronisation.  small: the launches above (gpk_serve_predict: 33..64 queries the same twice); otherwise, F = 1 only, the
 // general chain, which also reads m.Np / m.ldw only with the inverse factor.

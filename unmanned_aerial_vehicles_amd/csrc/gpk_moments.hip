@@ -682,12 +682,21 @@ __global__ __launch_bounds__(64) void moments_keep_kernel(MomK k, int R, int G_,
   }
 }
 
-// grid (R, B + U), 64 threads.  Units [0, B): gs[(r NO + o) MG_GS ..] of the model's outputs; unit 0 also gsV[r][16][16] = V~.
-// Units [B, B + U): RiT[(r U + u) 256 ..] = R^-T (zero beyond nx) and kap[r U + u].
-__global__ __launch_bounds__(64) void moments_grad_setup_kernel(MomK k, MomSeeds sd, int R, const double* __restrict__ Sz,
-                                                                const double* __restrict__ Bm, const double* __restrict__ G,
-                                                                const double* __restrict__ keepE, const double* __restrict__ keepF,
-                                                                double* gs, double* gsV, double* RiT, double* kap) {
+// What the taped set-up launch reads in the place of keepE / keepF: the stage's forward slots, still in the horizon's block.
+struct MomTape {
+  const double *rowpart, *pairpart;
+  double* keepE;                     // written by unit 0 for the finishing launch
+  int G_, nrw, NV;
+};
+
+// The body of the two set-up kernels below.  TAPED: E[mu_o] and the clip indicators are formed here from the forward's slots, in
+// moments_keep_kernel's order (w ascending; g ascending) - every unit of a query redoes the few sums it needs, unit 0 stores
+// keepE; no atomics, no tickets, no spin.  Not TAPED: they are read from keepE / keepF, instruction for instruction as before.
+template <bool TAPED>
+__device__ __forceinline__ void mg_setup_body(const MomK& k, const MomSeeds& sd, int R, const double* __restrict__ Sz,
+                                              const double* __restrict__ Bm, const double* __restrict__ G,
+                                              const double* __restrict__ keepE, const double* __restrict__ keepF, const MomTape& tp,
+                                              double* gs, double* gsV, double* RiT, double* kap) {
   __shared__ double S[16][17], Vb[16][17], Cb[16][17], T[16][17], eb[16], Em[16];
   __shared__ int cof[16];
   const int lane = threadIdx.x, r = blockIdx.x, unit = blockIdx.y, nx = k.nx, NO = k.NO, D = k.D, P = k.P;
@@ -726,7 +735,15 @@ __global__ __launch_bounds__(64) void moments_grad_setup_kernel(MomK k, MomSeeds
     double g = 0.0;
     if (lane < NO) g = sd.lam ? sd.lam[(long long)r * nx + cof[lane]] : sd.gmean ? sd.gmean[(long long)r * NO + lane] : 0.0;
     eb[lane] = lane < NO ? g * k.ystd[lane] : 0.0;
-    Em[lane] = keepE[r * 16 + lane];
+    if constexpr (TAPED) {
+      double s = 0.0;
+      if (lane < NO)
+        for (int w = 0; w < tp.nrw; ++w) s += tp.rowpart[(((long long)w * R + r) * NO + lane) * MM_WS + 16];
+      Em[lane] = s;
+      if (unit == 0) tp.keepE[r * 16 + lane] = s;
+    } else {
+      Em[lane] = keepE[r * 16 + lane];
+    }
   }
   __syncthreads();
   if (unit < k.B) {
@@ -774,16 +791,51 @@ __global__ __launch_bounds__(64) void moments_grad_setup_kernel(MomK k, MomSeeds
     }
     RiT[((long long)r * k.U + u) * 256 + e] = v;
   }
+  double clip = 0.0;      // [E[v_b] > floor] of a diagonal pair (lane 0)
+  if constexpr (TAPED) {
+    // the pair's G_ <= MM_MAXG slots of the K^-1 sum: loaded side by side, added by lane 0 in workgroup order
+    __shared__ double pg[MM_MAXG];
+    if (a == b) {
+      const double* p = tp.pairpart + ((long long)u * tp.G_ * R + r) * tp.NV;
+      for (int g2 = lane; g2 < tp.G_; g2 += 64) pg[g2] = p[(long long)g2 * R * tp.NV];
+    }
+    __syncthreads();
+    if (lane == 0 && a == b) {
+      double s = 0.0;
+      for (int g2 = 0; g2 < tp.G_; ++g2) s += pg[g2];
+      clip = k.kss[b] - s > k.floor_ ? 1.0 : 0.0;
+    }
+  } else if (lane == 0 && a == b) {
+    clip = keepF[r * k.U + u];
+  }
   if (lane == 0) {
     double v = 0.0;
     if (a == b) {
       if (k.B > 1) v = Vb[a][a];
       else
         for (int p = 0; p < P; ++p) v += Vb[p][p];
-      v *= keepF[r * k.U + u];
+      v *= clip;
     }
     kap[r * k.U + u] = v;
   }
+}
+
+// grid (R, B + U), 64 threads.  Units [0, B): gs[(r NO + o) MG_GS ..] of the model's outputs; unit 0 also gsV[r][16][16] = V~.
+// Units [B, B + U): RiT[(r U + u) 256 ..] = R^-T (zero beyond nx) and kap[r U + u].
+__global__ __launch_bounds__(64) void moments_grad_setup_kernel(MomK k, MomSeeds sd, int R, const double* __restrict__ Sz,
+                                                                const double* __restrict__ Bm, const double* __restrict__ G,
+                                                                const double* __restrict__ keepE, const double* __restrict__ keepF,
+                                                                double* gs, double* gsV, double* RiT, double* kap) {
+  mg_setup_body<false>(k, sd, R, Sz, Bm, G, keepE, keepF, MomTape{}, gs, gsV, RiT, kap);
+}
+
+// The same on a taped stage (gpk_mm_chain_grad with the tape): the keep launch's sums made here, so that the backward sweep of a
+// stage is four launches.  Same grid.
+__global__ __launch_bounds__(64) void moments_grad_setup_taped_kernel(MomK k, MomSeeds sd, int R, MomTape tp,
+                                                                      const double* __restrict__ Sz, const double* __restrict__ Bm,
+                                                                      const double* __restrict__ G, double* gs, double* gsV,
+                                                                      double* RiT, double* kap) {
+  mg_setup_body<true>(k, sd, R, Sz, Bm, G, nullptr, nullptr, tp, gs, gsV, RiT, kap);
 }
 
 // grid (ceil(N / 256), R, B), 256 threads.  part[((wg R + r) B + b) NV + v]: the workgroup's shares of W0 (v = 0), W1 (1 + d) and
@@ -1221,15 +1273,22 @@ void mg_pair_launch(gpk_handle h, const MomK& k, const MomWork& w, const MomGrad
 }
 
 // The four launches of the adjoint on a batch whose forward setup and row vectors are in w (Sz, Bm, cm, G, cl, rowq, rowpart) and
-// whose E[mu] and clip indicators are in keepE / keepF: d_q the scaled queries.
+// whose E[mu] and clip indicators are in keepE / keepF: d_q the scaled queries.  taped: w also holds the forward's slots
+// (rowpart, pairpart) and no keep launch has run - the set-up launch forms keepE (stored) and the indicators from them.
 int mg_launch(gpk_handle h, const MomK& k, const MomWork& w, const MomGradWork& g, int R, const double* d_q, const MomSeeds& sd,
-              const MomAdj& ad, const double* keepE, const double* keepF, double* dq, double* dS) {
+              const MomAdj& ad, double* keepE, const double* keepF, double* dq, double* dS, bool taped = false) {
   const int PC = k.P == 1 ? 1 : k.P <= 8 ? 8 : 16;      // the capacity of the pair kernel's alpha tiles: what is logged is what is launched
   if (h->gram_log)
     fprintf(stderr, "GPKMM adj %d %d %d %d %lld %d cus%d g%d u%d nq%d split%d nrw%d nv%d pc%d\n", k.B, k.P, k.D, k.nx, k.N, R, gpk_cus(h),
             w.G_, k.U, w.NQ, w.NQ > 1 ? 1 : 0, w.nrw, g.NV, PC);
-  hipLaunchKernelGGL(moments_grad_setup_kernel, dim3((unsigned)R, (unsigned)(k.B + k.U)), dim3(64), 0, h->stream, k, sd, R,
-                     (const double*)w.Sz, (const double*)w.Bm, (const double*)w.G, keepE, keepF, g.gs, g.gsV, g.RiT, g.kap);
+  if (taped)
+    hipLaunchKernelGGL(moments_grad_setup_taped_kernel, dim3((unsigned)R, (unsigned)(k.B + k.U)), dim3(64), 0, h->stream, k, sd, R,
+                       MomTape{w.rowpart, w.pairpart, keepE, w.G_, w.nrw, w.NV}, (const double*)w.Sz, (const double*)w.Bm,
+                       (const double*)w.G, g.gs, g.gsV, g.RiT, g.kap);
+  else
+    hipLaunchKernelGGL(moments_grad_setup_kernel, dim3((unsigned)R, (unsigned)(k.B + k.U)), dim3(64), 0, h->stream, k, sd, R,
+                       (const double*)w.Sz, (const double*)w.Bm, (const double*)w.G, (const double*)keepE, keepF, g.gs, g.gsV, g.RiT,
+                       g.kap);
   GPK_LAUNCH_CHECK(h);
   hipLaunchKernelGGL(moments_grad_row_kernel, dim3((unsigned)w.nrw, (unsigned)R, (unsigned)k.B), dim3(256), 0, h->stream, k, g.NV, d_q,
                      (const double*)w.Bm, (const double*)w.cm, (const double*)g.gs, g.gp, g.rowpart);
@@ -1239,7 +1298,7 @@ int mg_launch(gpk_handle h, const MomK& k, const MomWork& w, const MomGradWork& 
   else mg_pair_launch<16>(h, k, w, g, R);
   GPK_LAUNCH_CHECK(h);
   hipLaunchKernelGGL(moments_grad_finish_kernel, dim3((unsigned)R), dim3(256), 0, h->stream, k, ad, R, w.G_, w.nrw, g.NV,
-                     (const double*)w.Bm, (const double*)w.rowpart, keepE, (const double*)g.gs, (const double*)g.RiT,
+                     (const double*)w.Bm, (const double*)w.rowpart, (const double*)keepE, (const double*)g.gs, (const double*)g.RiT,
                      (const double*)g.rowpart, (const double*)g.pairpart, dq, dS);
   GPK_LAUNCH_CHECK(h);
   return GPK_OK;
@@ -1408,7 +1467,12 @@ int gpk_mm_query_vjp(gpk_handle h, const std::string& who, const HostModels& m, 
 // Sigma_h in the horizon's own output (Sigma_0: a second copy in the upload).  Backward, per stage: the forward's setup and row
 // launches again (three) and the adjoint's four, the last of which makes the adjoint step.  Nothing of size N^2 or N R H is kept.
 // One upload [head | S_0 | lam = gx_H | Lam = sym gS_H | gx | sym gS], 6 H + 7 H launches, one synchronisation.
-int gpk_mm_chain_grad(gpk_handle h, const std::string& who, const HostModels& m, const Horizon& z) {
+// tape (the sparse entries ask for it; the exact ones do not): where H work blocks fit option moments_tape_mb, every stage's block
+// (Sz, Bm, cm, G, cl, rowq, rowpart, pairpart) gets a region of its own, mm_work(h, k, R, tape + s w.doubles).  Forward, per stage:
+// gpk_mm_chain's five launches and no keep launch.  Backward, per stage: the adjoint's four, the first of them
+// moments_grad_setup_taped_kernel - nothing is recomputed.  5 H + 4 H launches; the buffers move and one reduction is fused in
+// its order, no sum is reordered: every result has the bits of the sweep without the tape.
+int gpk_mm_chain_grad(gpk_handle h, const std::string& who, const HostModels& m, const Horizon& z, bool tape) {
   if (!h) return GPK_BAD_ARG;
   MomK k;
   GPK_TRY(mm_models(h, who, m, true, k));
@@ -1423,19 +1487,26 @@ int gpk_mm_chain_grad(gpk_handle h, const std::string& who, const HostModels& m,
   const size_t n_om = (size_t)R * k.NO, n_du = (size_t)R * H * nu;
   HorizonBlock b(k.nx, k.D, z);
   const size_t n_x = b.n_x, n_s = b.n_s, n_Q = b.n_Q, n_gx = (size_t)H * n_x, n_gS = g.gS ? (size_t)H * n_s : 0;
-  MomWork w{};
+  MomWork w = mm_work(h, k, R, nullptr);
   MomGradWork gw{};
-  double *d_S0, *d_lam, *d_Lam, *d_gx, *d_gS, *d_kE, *d_kF, *d_du;
+  const bool taped = tape && h->moments_tape_mb > 0 && (size_t)H * w.doubles * sizeof(double) <= ((size_t)h->moments_tape_mb << 20);
+  if (tape && h->gram_log)
+    fprintf(stderr, "GPKMT tape%d h%d stage%zu launches%d\n", taped ? 1 : 0, H, w.doubles, (taped ? 9 : 13) * H);
+  double *d_S0, *d_lam, *d_Lam, *d_gx, *d_gS, *d_kE, *d_kF, *d_du, *d_tape = nullptr;
   GPK_TRY(gpk_horizon_carve(h, b, [&] {
     b.head();
     d_S0 = b.take(n_s); d_lam = b.take(n_x); d_Lam = b.take(n_s); d_gx = b.take(n_gx); d_gS = b.take(n_gS);      // (uploaded)
     b.outputs(n_om, z.mean, n_om * k.NO, z.cov, n_om * k.D, z.xcov);
     b.qs = b.take((size_t)(H - 1) * b.n_q);
-    d_kE = b.take((size_t)H * R * 16);
-    d_kF = b.take((size_t)H * R * k.U);
+    d_kE = b.take(taped ? (size_t)0 : (size_t)H * R * 16);
+    d_kF = b.take(taped ? (size_t)0 : (size_t)H * R * k.U);
     d_du = b.take(n_du);
-    w = mm_work(h, k, R, b.base ? b.base + b.at : nullptr);
-    b.take(w.doubles);
+    if (taped) {
+      d_tape = b.take((size_t)H * w.doubles);
+    } else {
+      w = mm_work(h, k, R, b.base ? b.base + b.at : nullptr);
+      b.take(w.doubles);
+    }
     gw = mg_work(k, w, R, b.base ? b.base + b.at : nullptr);
     b.take(gw.doubles);
   }));
@@ -1459,6 +1530,23 @@ int gpk_mm_chain_grad(gpk_handle h, const std::string& who, const HostModels& m,
     }
   }
   GPK_TRY(gpk_horizon_upload(h, b, z, host));
+  const MomSeeds sd{nullptr, nullptr, nullptr, d_lam, d_Lam, b.lin};
+  if (taped) {
+    for (int s = 0; s < H; ++s) {
+      const MomWork ws = mm_work(h, k, R, d_tape + (size_t)s * w.doubles);
+      GPK_TRY(mm_launch(h, k, ws, R, b.queries(s), b.S));
+      gpk_time_begin(h, GPK_TIMED_PROPAGATE);
+      mm_finish(h, k, ws, gpk_horizon_stage(b, z, s), R);
+      gpk_time_end(h);
+      GPK_LAUNCH_CHECK(h);
+    }
+    for (int s = H - 1; s >= 0; --s) {
+      const MomWork ws = mm_work(h, k, R, d_tape + (size_t)s * w.doubles);
+      const MomAdj ad{b.lin, d_gx + (size_t)s * n_x, g.gS ? d_gS + (size_t)s * n_s : nullptr, d_lam, d_Lam, d_du, H, s};
+      GPK_TRY(mg_launch(h, k, ws, gw, R, b.queries(s), sd, ad, gw.keepE, nullptr, nullptr, nullptr, true));
+    }
+    return gpk_horizon_finish(h, b, z, {{g.dU, d_du, n_du}, {g.dx0, d_lam, n_x}, {g.dSigma0, d_Lam, n_s}});
+  }
   for (int s = 0; s < H; ++s) {
     GPK_TRY(mm_launch(h, k, w, R, b.queries(s), b.S));
     gpk_time_begin(h, GPK_TIMED_PROPAGATE);
@@ -1468,7 +1556,6 @@ int gpk_mm_chain_grad(gpk_handle h, const std::string& who, const HostModels& m,
     mm_keep(h, k, w, R, d_kE + (size_t)s * R * 16, d_kF + (size_t)s * R * k.U);
     GPK_LAUNCH_CHECK(h);
   }
-  const MomSeeds sd{nullptr, nullptr, nullptr, d_lam, d_Lam, b.lin};
   for (int s = H - 1; s >= 0; --s) {
     GPK_TRY(mm_launch_rows(h, k, w, R, b.queries(s), s == 0 ? d_S0 : b.sig + (size_t)(s - 1) * n_s));
     const MomAdj ad{b.lin, d_gx + (size_t)s * n_x, g.gS ? d_gS + (size_t)s * n_s : nullptr, d_lam, d_Lam, d_du, H, s};

@@ -1682,6 +1682,102 @@ extern "C" int gpk_sparse_propagate_mm_multi(gpk_handle h, int B, const gpk_hand
   return gpk_mm_chain(h, who, sm.m, z);
 }
 
+// ---- ... with the adjoint of the moments: gpk_mm_query_vjp / gpk_mm_chain_grad on the same (Z, alpha_u, Q).  The engine's own
+// refusals of the seeds and results are made here as well, ahead of Q; the chains ask for the tape (gpk_moments.hip).
+namespace {
+
+int sparse_moments_vjp_check(gpk_handle h, const std::string& who, int D, int NO, int nx, const double* Xq, const double* Sq, int M,
+                             const double* mean, const double* cov, const double* xcov, const double* gmean, const double* gcov,
+                             const double* gxcov, const double* dXq, const double* dSq) {
+  GPK_TRY(sparse_moments_query_check(h, who, D, nx, Xq, Sq, M, mean, cov, xcov));
+  GPK_REQUIRE(h, dXq && dSq, who + "null result dXq or dSq");
+  const size_t n_om = (size_t)M * NO;
+  GPK_REQUIRE(h, (!gmean || gpk_finite(gmean, n_om)) && (!gcov || gpk_finite(gcov, n_om * NO)) && (!gxcov || gpk_finite(gxcov, n_om * D)),
+              who + "the seeds gmean, gcov and gxcov must not contain NaN or infinity");
+  return GPK_OK;
+}
+
+int sparse_moments_grad_check(gpk_handle h, const std::string& who, int nx, int D, const Horizon& z) {
+  GPK_TRY(gpk_horizon_check(h, who, nx, D, z));
+  const HorizonGrad& g = *z.grad;
+  GPK_REQUIRE(h, g.gx && g.dx0, who + "null seed gx or null result dx0");
+  GPK_REQUIRE(h, D == nx || g.dU, who + "null result dU");
+  GPK_REQUIRE(h, gpk_finite(g.gx, (size_t)(z.H + 1) * z.R * nx) && (!g.gS || gpk_finite(g.gS, (size_t)(z.H + 1) * z.R * nx * nx)),
+              who + "the seeds gx and gS must not contain NaN or infinity");
+  return GPK_OK;
+}
+
+}  // namespace
+
+extern "C" int gpk_sparse_moments_vjp(gpk_handle h, int var_includes_noise, int nx, const double* Xq, const double* Sq, int M,
+                                      double* mean, double* cov, double* xcov, const double* gmean, const double* gcov,
+                                      const double* gxcov, double* dXq, double* dSq) {
+  if (!h) return GPK_BAD_ARG;
+  const std::string who("sparse_moments_vjp: ");
+  SparseMoments sm;
+  GPK_TRY(sparse_moments_models(h, who, 1, nullptr, var_includes_noise, nx, nullptr, nullptr, nullptr, nullptr, nullptr, false,
+                                [&](int D) {
+                                  return sparse_moments_vjp_check(h, who, D, h->sparse->P, nx, Xq, Sq, M, mean, cov, xcov, gmean, gcov,
+                                                                  gxcov, dXq, dSq);
+                                }, sm));
+  return gpk_mm_query_vjp(h, who, sm.m, Xq, Sq, M, mean, cov, xcov, gmean, gcov, gxcov, dXq, dSq);
+}
+
+extern "C" int gpk_sparse_moments_vjp_multi(gpk_handle h, int B, const gpk_handle* models, int var_includes_noise, int nx,
+                                            const double* in_shift, const double* in_scale, const double* out_shift,
+                                            const double* out_scale, const double* Xq, const double* Sq, int M, double* mean,
+                                            double* cov, double* xcov, const double* gmean, const double* gcov, const double* gxcov,
+                                            double* dXq, double* dSq) {
+  if (!h) return GPK_BAD_ARG;
+  const std::string who("sparse_moments_vjp_multi: ");
+  GPK_REQUIRE(h, models, who + "null pointer");
+  SparseMoments sm;
+  GPK_TRY(sparse_moments_models(h, who, B, models, var_includes_noise, nx, nullptr, in_shift, in_scale, out_shift, out_scale, false,
+                                [&](int D) {
+                                  return sparse_moments_vjp_check(h, who, D, B, nx, Xq, Sq, M, mean, cov, xcov, gmean, gcov, gxcov,
+                                                                  dXq, dSq);
+                                }, sm));
+  return gpk_mm_query_vjp(h, who, sm.m, Xq, Sq, M, mean, cov, xcov, gmean, gcov, gxcov, dXq, dSq);
+}
+
+extern "C" int gpk_sparse_propagate_mm_grad(gpk_handle h, int var_includes_noise, const double* x0, int x0_rows, const double* U,
+                                            int u_rows, const double* lin, const double* Sigma0, int s_rows, const double* Q, int R,
+                                            int H, double* traj, double* Sigma, double* mean, double* cov, double* xcov,
+                                            const double* gx, const double* gS, double* dU, double* dx0, double* dSigma0) {
+  if (!h) return GPK_BAD_ARG;
+  const std::string who("sparse_propagate_mm_grad: ");
+  const HorizonGrad g{gx, gS, dU, dx0, dSigma0};
+  Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean};
+  z.cov = cov; z.xcov = xcov; z.grad = &g;
+  gpk_sparse* s = h->sparse;
+  GPK_REQUIRE(h, s && s->finalized, who + "no finalised sparse model (call gpk_sparse_finalize first)");
+  const int P = s->P;
+  GPK_REQUIRE(h, P >= 1 && P <= GPK_PROP_MAX_NX && P <= s->D, who + "the state dimension P must be in [1, 16] and must not exceed D");
+  SparseMoments sm;
+  GPK_TRY(sparse_moments_models(h, who, 1, nullptr, var_includes_noise, P, nullptr, nullptr, nullptr, nullptr, nullptr, true,
+                                [&](int D) { return sparse_moments_grad_check(h, who, P, D, z); }, sm));
+  return gpk_mm_chain_grad(h, who, sm.m, z, true);
+}
+
+extern "C" int gpk_sparse_propagate_mm_grad_multi(gpk_handle h, int B, const gpk_handle* models, int var_includes_noise, int nx,
+                                                  const int* coord, const double* in_shift, const double* in_scale,
+                                                  const double* out_shift, const double* out_scale, const double* x0, int x0_rows,
+                                                  const double* U, int u_rows, const double* lin, const double* Sigma0, int s_rows,
+                                                  const double* Q, int R, int H, double* traj, double* Sigma, double* mean,
+                                                  double* cov, double* xcov, const double* gx, const double* gS, double* dU,
+                                                  double* dx0, double* dSigma0) {
+  if (!h) return GPK_BAD_ARG;
+  const std::string who("sparse_propagate_mm_grad_multi: ");
+  GPK_REQUIRE(h, models && coord, who + "null pointer");
+  const HorizonGrad g{gx, gS, dU, dx0, dSigma0};
+  Horizon z{x0, U, lin, Sigma0, Q, x0_rows, u_rows, s_rows, R, H, traj, Sigma, mean};
+  z.cov = cov; z.xcov = xcov; z.grad = &g;
+  SparseMoments sm;
+  GPK_TRY(sparse_moments_models(h, who, B, models, var_includes_noise, nx, coord, in_shift, in_scale, out_shift, out_scale, true,
+                                [&](int D) { return sparse_moments_grad_check(h, who, nx, D, z); }, sm));
+  return gpk_mm_chain_grad(h, who, sm.m, z, true);
+}
+
 extern "C" int gpk_sparse_export(gpk_handle h, int64_t* m, int* D, int* P, int* n_ls, double* Z, double* G, double* g, double* yy,
                                  int64_t* n_rows, double* ls, double* hyper, double* y_mean, double* y_std) {
   if (!h) return GPK_BAD_ARG;

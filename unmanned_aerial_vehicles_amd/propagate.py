@@ -47,8 +47,9 @@ stage, one synchronisation); `host_loop_moments` is the same recursion over a cl
 serve it as `predict_moments` / `propagate_moments` (the engine on (Z, alpha_u, Q = Kuu^-1 - Sigma~), `gpk_sparse_propagate_mm[_multi]`);
 their `propagate(method="moment")` and every `propagate_gradient` refuse it (`refuse_moment`).
 
-`propagate_moments_gradient` of the exact classes is the gradient of a horizon cost through that recursion.  `predict_moments_vjp`
-returns, with the moments of a batch of Gaussian queries, the products of the seeds (on mean, cov and xcov) with their Jacobians
+`propagate_moments_gradient` (every class; the sparse ones on (Z, alpha_u, Q): `gpk_sparse_propagate_mm_grad[_multi]`, which keeps
+the stages' work blocks and runs five launches per stage forward and four backward) is the gradient of a horizon cost through that
+recursion.  `predict_moments_vjp` returns, with the moments of a batch of Gaussian queries, the products of the seeds (on mean, cov and xcov) with their Jacobians
 with respect to the query and its covariance (m~, S~; DESIGN.md section 4, K11, has the closed form).  With lam_{h+1}, Lam_{h+1} the
 incoming adjoints the stage's seeds are E^T lam on the mean, E^T Lam E on cov and 2 E^T Lam A0 on the state columns of xcov, and
 
@@ -230,7 +231,7 @@ def refuse_moment(method, what):
     if method == "moment":
         raise ValueError(f"method='moment' is not supported by {what}: the sparse classes serve exact moment matching through "
                          "predict_moments / propagate_moments, and the gradient through exact moments is "
-                         "propagate_moments_gradient of the exact classes")
+                         "propagate_moments_gradient on every class")
 
 
 def check_psd(S, what):
@@ -463,14 +464,23 @@ def model_horizon(model, x0, U, lin, order=1, method="linear", **kw):
 
 
 def model_moments_gradient(model, x0, U, lin, grad_traj, grad_Sigma, **kw):
-    """The gradient through exact moments that a control-loop wrapper asks of its model: `propagate_moments_gradient` of an exact
-    class; ValueError for a class without it (the sparse ones: their moments have no adjoint yet).  kw: for a batch, coord and the
-    scalers."""
+    """The gradient through exact moments that a control-loop wrapper asks of its model: `propagate_moments_gradient`, on its
+    default route (an exact class: one call; a sparse class: its one-call chain, the model assembled and its Q formed from the rows
+    it has taken so far).  ValueError "<class> has no gradient through exact moments", with the reason, for a class without the
+    method and for a model that cannot serve the call: not fitted, no inducing inputs, attributes missing.  kw: for a batch,
+    coord and the scalers."""
+    name = type(model).__name__
     fn = getattr(model, "propagate_moments_gradient", None)
     if not callable(fn):
-        raise ValueError(f"{type(model).__name__} has no gradient through exact moments (propagate_moments_gradient is a method "
-                         "of the exact classes)")
-    return fn(x0, U, lin, grad_traj, grad_Sigma, **kw)
+        raise ValueError(f"{name} has no gradient through exact moments (it has no method propagate_moments_gradient)")
+    try:
+        return fn(x0, U, lin, grad_traj, grad_Sigma, **kw)
+    except AttributeError as e:
+        raise ValueError(f"{name} has no gradient through exact moments: the model is not fitted ({e})") from None
+    except RuntimeError as e:
+        if isinstance(e, _lib.GPKError):      # the library's own failures are not the model's state
+            raise
+        raise ValueError(f"{name} has no gradient through exact moments: {e}") from None
 
 
 def chain_sizes_ok(m, D, nx):

@@ -342,8 +342,8 @@ class SimpleQuadrotorGP:
         (N + 1, 6, 6), dU (N, 4), dx0 (6,); U_guess (R, 4, N) with seeds (N + 1, R, ...) -> a leading R on every result.
         Untrained, or on any failure (printed): the nominal horizon and the sweep through the nominal dynamics (A = I + lin_x,
         no variance terms) - it never raises into the control loop.  method="moment": the horizon of `propagate_horizon(method=
-        "moment")` and the gradient through its exact moments (`GaussianProcessRegressor.propagate_moments_gradient`); a SparseGP
-        model has no such gradient: the nominal fallback, with the reason printed."""
+        "moment")` and the gradient through its exact moments (`GaussianProcessRegressor.propagate_moments_gradient`; a SparseGP
+        model: `SparseGP.propagate_moments_gradient`, one call for the horizon)."""
         from . import propagate as _pg
         state, U, lin, nominal, single = _pg.horizon_inputs(self._nominal_dynamics, state, U_guess, dt)
         R, N = U.shape[0], U.shape[1]

@@ -629,6 +629,57 @@ class SparseGP:
             x0, U, lin, S0, Q, R, H, ((P,), (P, P), (P, D)) if return_stages else None)
         return (traj, Sigma, dict(zip(("mean", "cov", "xcov"), more))) if return_stages else (traj, Sigma)
 
+    def predict_moments_vjp(self, X, Sigma, grad_mean=None, grad_cov=None, grad_xcov=None, var_includes_noise=False):
+        """`GaussianProcessRegressor.predict_moments_vjp` on the sparse posterior: `predict_moments` and, for l = <grad_mean, mean>
+        + <grad_cov, cov> + <grad_xcov, xcov>, dX (M, D) = dl/dX and dSigma (M, nx, nx) = dl/dSigma (symmetric bit for bit).  Seeds
+        grad_mean (M, P), grad_cov (M, P, P; (g + g^T) / 2 is used), grad_xcov (M, P, D), None: zero.  Returns (mean, cov, xcov,
+        dX, dSigma), the first three with the bits of `predict_moments`.  One C call (`gpk_sparse_moments_vjp`: ten launches,
+        one synchronisation; Q is a constant of the adjoint).  Limits and errors as `predict_moments`."""
+        from . import propagate as _pg
+        if getattr(self, "inducing_", None) is None:
+            raise RuntimeError("predict_moments_vjp: this SparseGP has no inducing inputs")
+        P, D = self.n_outputs_, self.n_features_in_
+        X, S, M, nx = _pg.check_gaussian_queries(X, Sigma, D)
+        gm, gc, gxc = _pg.check_moment_seeds(grad_mean, grad_cov, grad_xcov, M, P, D)
+        self._moments_ready("predict_moments_vjp")
+        self._ensure()
+        mean, cov, xcov = np.empty((M, P)), np.empty((M, P, P)), np.empty((M, P, D))
+        dX, dS = np.empty((M, D)), np.empty((M, nx, nx))
+        self._moments_entry("gpk_sparse_moments_vjp", int(bool(var_includes_noise)), nx, _ptr(X), _ptr(S), M, _ptr(mean), _ptr(cov),
+                            _ptr(xcov), _ptr(gm), _ptr(gc), _ptr(gxc), _ptr(dX), _ptr(dS))
+        return mean, cov, xcov, dX, dS
+
+    def propagate_moments_gradient(self, x0, U, lin, grad_traj, grad_Sigma=None, Sigma0=None, process_noise=None,
+                                   var_includes_noise=False, route="chain"):
+        """`propagate_moments` with the gradient of a horizon cost l(traj, Sigma) with respect to the controls, the start state
+        and the start covariance, through the exact moments of every stage
+        (`GaussianProcessRegressor.propagate_moments_gradient` on the sparse posterior).  grad_traj (H + 1, R, P), grad_Sigma
+        (H + 1, R, P, P) or None.  Returns (traj, Sigma, dU (R, H, nu), dx0 (R, P), dSigma0 (R, P, P)), traj and Sigma with the
+        bits of `propagate_moments`.  route="chain": ONE C call per horizon (`gpk_sparse_propagate_mm_grad`: every stage's work
+        block kept on the device while the horizon's fit the backend option moments_tape_mb - five launches per stage forward,
+        four backward; beyond it six and seven; the same bits; one synchronisation).  route="host": the sweep on the host over
+        `predict_moments` and `predict_moments_vjp` (`propagate.host_adjoint_moments`).  RuntimeError without inducing inputs;
+        ValueError where `propagate_ok()` does not hold or an argument is refused."""
+        from . import propagate as _pg
+        if getattr(self, "inducing_", None) is None:
+            raise RuntimeError("propagate_moments_gradient: this SparseGP has no inducing inputs")
+        _pg.check_route(route, ("chain", "host"))
+        P, D = self.n_outputs_, self.n_features_in_
+        x0, U, lin, S0, Q, R, H = _pg.check_horizon(x0, U, lin, P, D, Sigma0, process_noise)
+        gx, gS = _pg.check_seeds(grad_traj, grad_Sigma, R, H, P)
+        _pg.check_method("moment", 1, "propagate_moments_gradient", Sigma0=S0, process_noise=Q)
+        self._moments_ready("propagate_moments_gradient")
+        if route == "host":
+            return _pg.host_adjoint_moments(
+                lambda q, S: self.predict_moments(q, S, var_includes_noise=var_includes_noise),
+                lambda q, S, gm, gc, gxc: self.predict_moments_vjp(q, S, gm, gc, gxc, var_includes_noise=var_includes_noise),
+                list(range(P)), x0, U, lin, S0, Q, R, H, gx, gS)
+        self._ensure()
+        traj, Sigma, more = _pg.horizon_call(
+            lambda *t: self._backend().call("gpk_sparse_propagate_mm_grad", int(bool(var_includes_noise)), *t),
+            x0, U, lin, S0, Q, R, H, seeds=(gx, gS))
+        return (traj, Sigma, *more)
+
     def _propagate_refusal(self):
         """Why the one-call chain does not apply (a string), or None where it does."""
         from . import propagate as _pg

@@ -277,6 +277,66 @@ class BatchedSparseGP:
             x0, U, lin, S0, Q, R, H, ((B,), (B, B), (B, D)) if return_stages else None)
         return (traj, Sigma, dict(zip(("mean", "cov", "xcov"), more))) if return_stages else (traj, Sigma)
 
+    def predict_moments_vjp(self, X, Sigma, grad_mean=None, grad_cov=None, grad_xcov=None, in_scaler=None, out_scaler=None,
+                            var_includes_noise=False):
+        """`BatchedARDGP.predict_moments_vjp` on the sparse posteriors, in raw units: `predict_moments` and, for the seeds
+        grad_mean (M, B), grad_cov (M, B, B; (g + g^T) / 2 is used), grad_xcov (M, B, D) (None: zero), dX (M, D) and dSigma (M, nx,
+        nx; symmetric bit for bit) per unit of the raw query and its raw covariance.  Returns (mean, cov, xcov, dX, dSigma), the
+        first three with the bits of `predict_moments`.  One C call (`gpk_sparse_moments_vjp_multi`: ten launches for all models
+        and pairs, one synchronisation).  Limits and errors as `predict_moments`."""
+        from . import propagate as _pg
+        if not getattr(self, "models", None):
+            raise RuntimeError("predict_moments_vjp: this BatchedSparseGP has no models (no inducing inputs)")
+        B, D = len(self.models), self.n_features_in_
+        X, S, M, nx = _pg.check_gaussian_queries(X, Sigma, D)
+        gm, gc, gxc = _pg.check_moment_seeds(grad_mean, grad_cov, grad_xcov, M, B, D)
+        in_shift, in_scale, o_mean, o_scale = _pg.check_scalers(B, D, in_scaler, out_scaler)
+        self._moments_ready("predict_moments_vjp", nx)
+        scaled = out_scaler is not None
+        om = np.ascontiguousarray(o_mean, dtype=np.float64) if scaled else None
+        osc = np.ascontiguousarray(o_scale, dtype=np.float64) if scaled else None
+        mean, cov, xcov = np.full((M, B), np.nan), np.full((M, B, B), np.nan), np.full((M, B, D), np.nan)
+        dX, dS = np.full((M, D), np.nan), np.full((M, nx, nx), np.nan)
+        try:
+            with self._serving() as (be, handles):
+                be.call("gpk_sparse_moments_vjp_multi", B, handles, int(bool(var_includes_noise)), nx, _ptr(in_shift), _ptr(in_scale),
+                        _ptr(om), _ptr(osc), _ptr(X), _ptr(S), M, _ptr(mean), _ptr(cov), _ptr(xcov), _ptr(gm), _ptr(gc), _ptr(gxc),
+                        _ptr(dX), _ptr(dS))
+        except _lib.GPKError as e:      # a limit of the entry: the caller's arguments, with the library's message
+            if e.code == _lib.GPK_BAD_ARG:
+                raise ValueError(str(e)) from None
+            raise
+        return mean, cov, xcov, dX, dS
+
+    def propagate_moments_gradient(self, x0, U, lin, grad_traj, grad_Sigma=None, coord=None, in_scaler=None, Sigma0=None,
+                                   process_noise=None, var_includes_noise=False, out_scaler=None, route="chain"):
+        """`propagate_moments` with the gradient of a horizon cost, in raw units: `BatchedARDGP.propagate_moments_gradient` on the
+        sparse posteriors (coord, in_scaler, out_scaler as `propagate`).  Returns (traj, Sigma, dU (R, H, nu), dx0 (R, nx),
+        dSigma0 (R, nx, nx)), traj and Sigma with the bits of `propagate_moments`.  route="chain": ONE C call per horizon for all
+        models and pairs (`gpk_sparse_propagate_mm_grad_multi`; the launches as `SparseGP.propagate_moments_gradient` describes
+        them); route="host": the sweep on the host over `predict_moments` and `predict_moments_vjp`.  RuntimeError without
+        models; ValueError where `propagate_ok()` does not hold or an argument is refused."""
+        from . import propagate as _pg
+        if not getattr(self, "models", None):
+            raise RuntimeError("propagate_moments_gradient: this BatchedSparseGP has no models (no inducing inputs)")
+        B, D = len(self.models), self.n_features_in_
+        x0, U, lin, S0, Q, R, H, coord, in_shift, in_scale, o_mean, o_scale = _pg.check_batch(
+            B, D, x0, U, lin, coord, in_scaler, out_scaler, Sigma0, process_noise, route, routes=("chain", "host"))
+        nx = lin.shape[0]
+        gx, gS = _pg.check_seeds(grad_traj, grad_Sigma, R, H, nx)
+        _pg.check_method("moment", 1, "propagate_moments_gradient", Sigma0=S0, process_noise=Q)
+        self._moments_ready("propagate_moments_gradient", nx)
+        if route == "host":
+            kw = dict(in_scaler=in_scaler, out_scaler=out_scaler, var_includes_noise=var_includes_noise)
+            return _pg.host_adjoint_moments(lambda q, S: self.predict_moments(q, S, **kw),
+                                            lambda q, S, gm, gc, gxc: self.predict_moments_vjp(q, S, gm, gc, gxc, **kw),
+                                            coord, x0, U, lin, S0, Q, R, H, gx, gS)
+        traj, Sigma, more = _pg.horizon_call(
+            self._chain_call("gpk_sparse_propagate_mm_grad_multi", var_includes_noise, nx, coord, in_shift, in_scale, out_scaler,
+                             o_mean, o_scale),
+            x0, U, lin, S0, Q, R, H, seeds=(gx, gS))
+        return (traj, Sigma, *more)
+
     def _chain_call(self, entry, var_includes_noise, nx, coord, in_shift, in_scale, out_scaler, o_mean, o_scale):
         """The call of a chain entry of the batch for `propagate.horizon_call`, which supplies the horizon's arguments."""
         B = len(self.models)

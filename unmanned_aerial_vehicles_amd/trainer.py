@@ -646,7 +646,7 @@ class PreTrainedGP:
         `SimpleQuadrotorGP.horizon_gradient`.  Not loaded, models that do not share inputs and scaler, or any failure
         (printed): the nominal horizon and the sweep through the nominal dynamics - it never raises into the control loop.
         method="moment": the gradient through the exact moments of every stage (`BatchedARDGP.propagate_moments_gradient`, one
-        call); a file of sparse models has no such gradient: the nominal fallback, with the reason printed."""
+        call; a file of sparse models: `BatchedSparseGP.propagate_moments_gradient`, one call as well)."""
         from . import propagate as _pg
         state, U, lin, nominal, single = _pg.horizon_inputs(GPTrainer._nominal_dynamics, state, U_guess, dt)
         try:
