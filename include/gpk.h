@@ -108,7 +108,8 @@ GPK_API int64_t gpk_padded(int64_t n);
  * ntmTA ntnB nstS padP gridG`, gpk_predict_var_inv_split: `GPKK5 split rowsR ntmTA ntnB nstS pad0 gridG`; R the tile's rows, A x B tiles,
  * S super-tiles, P tile slots per band of the walk - to stderr, one line per launch),
  * "sparse_panel" / "sparse_slabs" (the statistics pass of the sparse model, K9:
- * rows per panel and k-slabs per panel product; 0 = the built-in rule), "moments_query_groups" (the pair launch of the moment-matching
+ * rows per panel and k-slabs per panel product; 0 = the built-in rule), "fitc_fused" (the weighted pass of the FITC model, K9: 1,
+ * the default = the q_i from one tile GEMM on the panel, 0 = from gpk_predict_var_inv on the panel's rows, the check), "moments_query_groups" (the pair launch of the moment-matching
  * entries, K11: 0 = as many groups of queries as bring it to two workgroups per CU, n >= 1 = at most n, 1 = no split; bit-identical
  * results), "moments_tape_mb" (the gradient chains of the sparse moment entries keep every stage's work block while H blocks fit this
  * many MiB, 9 H launches instead of 13 H: default 1024, 0 = never; bit-identical results), "debug_fill" (1: the handle's scratch and serving work area are overwritten with NaN bytes at every request - the test
@@ -755,6 +756,51 @@ GPK_API int gpk_lml_batched(gpk_handle h, const double* thetas, int n_theta, dou
  *   hyper-parameters - ls (n_ls values), hyper = [sf2, noise, jitter, jitter_uu], y_mean, y_std (P) - as host arrays; NULL
  *   outputs are skipped.  The importer then only finalises (and may go on updating).
  *
+ * FITC (Snelson & Ghahramani 2006): the other standard inducing-point posterior.  DTC treats the part of a training row that
+ * the inducing inputs cannot explain, k_ii - k_i^T Kuu^-1 k_i, as zero; FITC gives the row that residual as noise of its own.
+ * It differs from DTC in the statistics only.  With Wuu = Luu^-1 and
+ *       q_i = |Wuu k_u(x_i)|^2,   lambda_i = sigma^2 + max(sf2 - q_i, 0),   w_i = sigma^2 / lambda_i  in (0, 1]
+ * the statistics are S = F^T diag(w) F - G = Kuf diag(w) Kfu, g = Kuf diag(w) Yn, yy[p] = sum w_i Yn[i][p]^2 - and the assembly
+ * of gpk_sparse_finalize, unchanged, yields the FITC posterior: mean k_u^T alpha_u, variance sf2 - |Wuu k_u|^2 + |WSigma k_u|^2,
+ * Q = Kuu^-1 - Sigma~.  Every entry that serves a finalised object (gpk_sparse_predict*, the _multi entries, paths, propagate,
+ * moments) therefore serves a FITC object as it is.  The statistics stay additive over rows at fixed (Z, hyper-parameters);
+ * the likelihood needs one more additive scalar, sum_i log lambda_i.
+ * Replaces: GPflow's GPRFITC, which the reference's GPflow variant (src/px4/gp.py) could have used; nothing in the reference
+ *   serves it.
+ * gpk_sparse_accumulate_fitc: the weighted statistics pass, the device-pointer building block beside gpk_sparse_accumulate: its
+ *   operands, then Wuu (dev, mp x ldw, even ldw >= mp, 16-byte aligned: the inverse factor of Kuu + jitter_uu I in the layout
+ *   gpk_trtri writes), sigma2 = noise + jitter > 0, log_lambda_sum (dev double[1]: sum_i log lambda_i is ADDED to what it
+ *   holds) and w (dev, n doubles, or NULL: receives the weights).  S += F^T diag(w) F.  The panel rule, the k-slab rule, the
+ *   limits and the work area (the handle's scratch) of gpk_sparse_accumulate; the panel is written in whole 128-row blocks.
+ *   Per panel, between the panel kernel and the F^T F launches, which run unchanged on the scaled panel:
+ *     the q_i without storing V = Kfu Wuu^T - ONE tile GEMM Wuu F[:, 0:mp]^T (the k-tiles in the zero triangle of Wuu skipped)
+ *       whose sum-of-squares epilogue leaves one partial per (tile row of Wuu, row of the panel): gpk_predict_var_inv's launch
+ *       with the panel in the place of a second kernel matrix.  Option "fitc_fused" = 0: gpk_predict_var_inv itself on the
+ *       panel's rows (a second kernel-matrix pass and its own finalising launch) - the composed route, kept as the check;
+ *     one launch that adds the partials in tile order, forms lambda_i and w_i, multiplies row i of F (all mp + 128 columns, the
+ *       targets included) by sqrt(w_i) in place and writes one sum of log lambda_i per 64-row workgroup (rows >= n of the last
+ *       block stay zero and contribute nothing);
+ *     one launch that adds those sums in a fixed order onto log_lambda_sum.
+ *   No floating-point atomics, flags or spins: the same sequence of calls gives the same bits, S stays symmetric bit for bit.
+ *   Asynchronous.
+ * gpk_sparse_set_approximation: kind = GPK_SPARSE_DTC (0, what gpk_sparse_begin / gpk_sparse_import create) or GPK_SPARSE_FITC
+ *   (1).  Legal while the object has seen no rows (none updated, held or imported); afterwards GPK_BAD_ARG with a message,
+ *   unless kind repeats the current one (then nothing happens).  Choosing FITC factors Kuu + jitter_uu I and forms Wuu at once -
+ *   the pass needs them before the first row; GPK_NOT_PD with *info = the pivot as in gpk_sparse_finalize, which factors again
+ *   (the same launches: the finalised bits do not depend on it).  On a FITC object gpk_sparse_update and gpk_sparse_hold run
+ *   the weighted pass; gpk_sparse_eval[_z] set the hyper-parameters (and Z), factor Kuu FIRST, accumulate the held rows again
+ *   with the weights and return the value - with grad != NULL or gradZ != NULL they return GPK_BAD_ARG with a message that
+ *   names FITC before anything is launched or changed: where lambda depends on the hyper-parameters and on Z the gradient is a
+ *   different one, and it is not built.  gpk_sparse_finalize and gpk_sparse_bound return, on a FITC object, the FITC
+ *   log-marginal likelihood log N(y | 0, Qff + diag(lambda)) in normalised-target units,
+ *       sum_p [ -N/2 log(2 pi) - 1/2 sum_i log lambda_i - sum log diag LB - yy[p] / (2 sigma^2) + r_p^T B^-1 r_p / 2 ]
+ *   - the DTC formula with -N/2 log sigma^2 replaced and no trace term; it equals the DTC bound, and the exact value, when
+ *   Z = X.  gpk_sparse_select is unaffected.
+ * gpk_sparse_get_approximation: kind and sum_i log lambda_i over the rows seen (0 for DTC; synchronises); NULL outputs are skipped.
+ * gpk_sparse_restore_approximation: beside gpk_sparse_import - sets kind and the sum as gpk_sparse_get_approximation returned
+ *   them for the imported statistics (FITC: factors Kuu as the setter does); the object can then finalise and go on taking
+ *   rows.  GPK_BAD_ARG on an object that holds rows.
+ *
  * Training: the gradient of the bound L with respect to log [ls .., noise, sf2] (jitter and jitter_uu do not depend on them).
  * Replaces: the optimiser loop of GPflow's SGPR behind the reference's src/px4/gp.py (gpflow.optimizers.Scipy().minimize on
  *   model.training_loss, which differentiates the same collapsed bound by reverse mode over the N x m cross-covariance), and
@@ -924,6 +970,14 @@ GPK_API int gpk_sparse_export(gpk_handle h, int64_t* m, int* D, int* P, int* n_l
 GPK_API int gpk_sparse_import(gpk_handle h, const double* Z, int64_t m, int D, int P, const double* ls, int n_ls, double sf2,
                               double noise, double jitter, double jitter_uu, const double* y_mean, const double* y_std,
                               const double* G, const double* g, const double* yy, int64_t n_rows);
+#define GPK_SPARSE_DTC 0
+#define GPK_SPARSE_FITC 1
+GPK_API int gpk_sparse_accumulate_fitc(gpk_handle h, const double* X, const double* Yn, int64_t n, const double* Z, int64_t m, int D,
+                                       int P, const double* ls, double sf2, double* S, int64_t ld, const double* Wuu, int64_t ldw,
+                                       double sigma2, double* log_lambda_sum, double* w);
+GPK_API int gpk_sparse_set_approximation(gpk_handle h, int kind, int* info);
+GPK_API int gpk_sparse_get_approximation(gpk_handle h, int* kind, double* log_lambda_sum);
+GPK_API int gpk_sparse_restore_approximation(gpk_handle h, int kind, double log_lambda_sum, int* info);
 
 /* ---- building block: whole-tile GEMM on the matrix cores ---------------------------------------
  * C[m x n] = alpha * opA(A) * opB(B)^T + beta * C, m and n multiples of 128, k a multiple of 16

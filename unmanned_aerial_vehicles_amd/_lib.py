@@ -124,6 +124,10 @@ SIGNATURES = {
     "gpk_lml_eval": (_int, [_vp, _vp, _i64, _int, _dp, _dbl, _dbl, _dbl, _vp, _int, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _dp, _dp,
                             C.POINTER(C.c_int)]),
     "gpk_sparse_accumulate": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _int, _int, _dp, _dbl, _vp, _i64]),
+    "gpk_sparse_accumulate_fitc": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _int, _int, _dp, _dbl, _vp, _i64, _vp, _i64, _dbl, _vp, _vp]),
+    "gpk_sparse_set_approximation": (_int, [_vp, _int, C.POINTER(_int)]),
+    "gpk_sparse_get_approximation": (_int, [_vp, C.POINTER(_int), _dp]),
+    "gpk_sparse_restore_approximation": (_int, [_vp, _int, _dbl, C.POINTER(_int)]),
     "gpk_sparse_grad_pass": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _int, _int, _dp, _dbl, _vp, _i64, _vp]),
     "gpk_sparse_zgrad_pass": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _int, _int, _dp, _dbl, _vp, _i64, _vp]),
     "gpk_sparse_hold": (_int, [_vp, _dp, _dp, _i64]),

@@ -87,6 +87,7 @@ extern "C" int gpk_set_option(gpk_handle h, const char* name, int value) {
   else if (n == "debug_fill") h->debug_fill = value ? 1 : 0;
   else if (n == "sparse_panel") h->sparse_panel = value <= 0 ? 0 : value > (1 << 20) ? (1 << 20) : value;
   else if (n == "sparse_slabs") h->sparse_slabs = value <= 0 ? 0 : value > 64 ? 64 : value;
+  else if (n == "fitc_fused") h->fitc_fused = value ? 1 : 0;
   else if (n == "moments_query_groups") h->moments_query_groups = value <= 0 ? 0 : value > GPK_SMALL_MAX_M ? GPK_SMALL_MAX_M : value;
   else if (n == "moments_tape_mb") h->moments_tape_mb = value <= 0 ? 0 : value;
   else if (n == "ptile") h->ptile = value;

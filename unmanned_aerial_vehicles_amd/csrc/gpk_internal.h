@@ -73,6 +73,7 @@ struct gpk_context {
   long long ptile_trace_n = 0;
   int sparse_panel = 0;      // gpk_sparse_update / gpk_sparse_accumulate: rows per panel (0: F = [Kfu | Yn] within 128 MiB, 1024 .. 16384 rows)
   int sparse_slabs = 0;      // ... k-slabs of a panel's product F^T F (0: a function of (mp, panel rows), gpk_sparse.hip; 1 .. 64)
+  int fitc_fused = 1;        // the weighted (FITC) pass: q_i from ONE tile GEMM on the panel F (0: gpk_predict_var_inv on the panel's rows, the check)
   int debug_fill = 0;        // option debug_fill: the handle's scratch is overwritten with 0xFF bytes (NaN) at every request
   int gemm_log = 0;          // option gemm_log = 1: log every tile-GEMM launch to stderr (profiling aid)
   int gram_log = 0;          // option gram_log = 1: log the form of every gpk_gram / gpk_predict_mean[_multi] / gpk_predict_mean_mfma launch and of every small-batch serving call to stderr

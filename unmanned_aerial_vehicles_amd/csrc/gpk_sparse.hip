@@ -17,6 +17,13 @@
 // The slab count depends on (mp, panel rows) only (sparse_slabs_for), overridable by option "sparse_slabs"; the panel by
 // option "sparse_panel" (sparse_panel_for: F within half of the 256 MB Infinity Cache).
 //
+// FITC (gpk_sparse_set_approximation): the other standard inducing-point posterior differs in the statistics only, S = F^T diag(w) F
+// with w_i = s2 / (s2 + max(sf2 - |Wuu k_u(x_i)|^2, 0)).  The weighted pass (`accumulate` with FitcArgs) adds three launches per
+// panel between the panel kernel and the F^T F launches: the q_i (gpk_predict_var_inv's tile GEMM with the panel as its second
+// operand, V never stored), sparse_fitc_scale_kernel (lambda, w, F scaled by sqrt(w) in place, partial sums of log lambda) and
+// the fixed-order sum of those onto the running sum_i log lambda_i, the likelihood's one extra scalar.  The assembly and
+// everything that serves the assembled model are the same code for both kinds.
+//
 // Training (gpk_sparse_hold / gpk_sparse_eval): the rows stay on the device, an evaluation accumulates S again, assembles the
 // model and, for the gradient of the bound, runs ONE more pass over the rows (rows_pass: F again, a tile GEMM Q = F C whose
 // epilogue reduces Q o Kfu o ((x - z) / ls)^2 per tile without storing Q, a fixed-order sum of the tiles); the m x m part is
@@ -210,6 +217,67 @@ __global__ void sparse_stack_kernel(const double* __restrict__ VA, long long mp,
 
 int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 
+// FITC ("FITC"): the weights of a panel's rows and the scaled panel, one launch.  Per 64-row block (blockIdx.y) the
+// first 64 threads form, for the row i < n,
+//   q_i = |Wuu k_u(x_i)|^2 = sum over the ntm tile rows of qpart[t * ldq + i], added in tile order (epilogue 1 of the tile GEMM
+//         Wuu F^T left one sum of squares per tile row) - or, ntm == 0, resid[i] = sf2 - q_i as gpk_predict_var_inv left it,
+//   lambda_i = s2 + max(sf2 - q_i, 0),   w_i = s2 / lambda_i in (0, 1],
+// then the workgroup multiplies its rows of F, columns [1024 blockIdx.x, + 1024) of all nt (Kfu and the targets), by
+// sqrt(w_i) in place; the column-0 workgroup writes logpart[blockIdx.y] = sum of log lambda_i over its rows, in row order, and
+// wout[i] = w_i where wout != NULL.  Rows >= n of the last block are zero and stay zero, and contribute no logarithm.
+__global__ __launch_bounds__(256) void sparse_fitc_scale_kernel(double* __restrict__ F, long long ldf, int nt, long long n,
+                                                                const double* __restrict__ qpart, int ntm, long long ldq,
+                                                                const double* __restrict__ resid, double sf2, double s2,
+                                                                double* __restrict__ logpart, double* __restrict__ wout) {
+  __shared__ double sw[SP_TS], lg[SP_TS];
+  const int tid = threadIdx.x;
+  const long long i0 = (long long)blockIdx.y * SP_TS;
+  if (tid < SP_TS) {
+    const long long i = i0 + tid;
+    double w = 0.0, l = 0.0;
+    if (i < n) {
+      double r;
+      if (ntm > 0) {
+        double q = 0.0;
+        for (int t = 0; t < ntm; ++t) q += qpart[(long long)t * ldq + i];
+        r = sf2 - q;
+      } else {
+        r = resid[i];
+      }
+      const double lam = s2 + fmax(r, 0.0);
+      const double wi = s2 / lam;
+      w = __builtin_sqrt(wi);
+      l = log(lam);
+      if (wout && blockIdx.x == 0) wout[i] = wi;
+    }
+    sw[tid] = w;
+    lg[tid] = l;
+  }
+  __syncthreads();
+  if (blockIdx.x == 0 && tid == 0) {
+    double t = 0.0;
+    for (int r = 0; r < SP_TS; ++r) t += lg[r];
+    logpart[blockIdx.y] = t;
+  }
+  const int c0 = blockIdx.x * 1024, c1 = c0 + 1024 < nt ? c0 + 1024 : nt;
+  for (int r = tid >> 6; r < SP_TS; r += 4) {
+    const double w = sw[r];
+    double* row = F + (i0 + r) * ldf;
+    for (int c = c0 + 2 * (tid & 63); c < c1; c += 128) {
+      double2 v = *reinterpret_cast<double2*>(row + c);
+      v.x *= w;
+      v.y *= w;
+      *reinterpret_cast<double2*>(row + c) = v;
+    }
+  }
+}
+
+__global__ void sparse_sum_kernel(const double* __restrict__ partial, long long n, int W, double* __restrict__ out, int accumulate);
+
+// what the weighted pass takes beside the plain one's operands: the inverse factor Wuu (dev, mp x ldw, gpk_trtri's layout),
+// s2 = noise + jitter, loglam (dev double[1]: += sum log lambda_i), wout (dev n doubles or NULL: the weights)
+struct FitcArgs { const double* Wuu; int64_t ldw; double s2; double* loglam; double* wout; };
+
 // Rows of a panel: F = rows x (mp + 128) doubles within 128 MiB - half of the 256 MB Infinity Cache, so that the panel the
 // cross kernel has just written is still on the chip while the (mp / 128 + 1) tile columns of the product read it again -
 // between 1024 and 16384 rows, a multiple of 256.  Measured (N = 262 144, ms at 2048 / 4096 / 8192 / 16384 rows,
@@ -251,8 +319,14 @@ PanelPlan plan_panel(gpk_handle h, int64_t mp, int64_t rows) {
 }
 
 // S (nt x ld, nt = mp + 128; symmetric on entry and on return) += F^T F over the n rows of X / Yn, panel by panel.
+// fitc != NULL: the weighted pass, S += F^T diag(w) F.  Per panel, between the panel kernel and the F^T F launches that run
+// unchanged on the scaled panel: the q_i (option "fitc_fused" = 1: ONE tile GEMM Wuu F[:, 0:mp]^T whose epilogue 1 keeps only
+// the sums of squares per tile row - gpk_predict_var_inv's launch with the panel in the place of a second kernel matrix; 0:
+// gpk_predict_var_inv itself on the panel's rows, the composed route kept as the check of the fused one), the scaling launch,
+// and the sum of the workgroups' log lambda onto fitc->loglam.  The panel is written in whole 128-row blocks (the GEMM's n).
+// Work area: [the head that gpk_predict_var_inv's own request lands in (unfused) | F | partial | the q work | log partials].
 int accumulate(gpk_handle h, const double* X, const double* Yn, int64_t n, const double* Z, int64_t m, int D, int P,
-               const double* ls, double sf2, double* S, int64_t ld) {
+               const double* ls, double sf2, double* S, int64_t ld, const FitcArgs* fitc = nullptr) {
   const int64_t mp = gpk_padded(m), nt = mp + NB;
   SpLs l;
   for (int d = 0; d < D; ++d) {
@@ -268,20 +342,56 @@ int accumulate(gpk_handle h, const double* X, const double* Yn, int64_t n, const
     if (p.rows_p > f_rows) f_rows = p.rows_p;
     if (p.slabs > 1 && p.slabs > max_slabs) max_slabs = p.slabs;
   }
+  const bool fused = fitc && h->fitc_fused;
+  size_t head = 0, qwork = 0;
+  if (fitc) {
+    f_rows = round_up(f_rows, NB);
+    const size_t qpart = (size_t)(mp / 64) * f_rows;      // one sum of squares per (64-row tile row of Wuu, row of the panel)
+    if (!fused) head = qpart;
+    qwork = (fused ? qpart : (size_t)f_rows * mp + f_rows) + (size_t)(f_rows / SP_TS);
+  }
   void* ws = nullptr;
-  GPK_TRY(gpk_scratch(h, ((size_t)f_rows * nt + (size_t)max_slabs * nt * nt) * sizeof(double), &ws));
-  double* F = (double*)ws;
+  GPK_TRY(gpk_scratch(h, (head + (size_t)f_rows * nt + (size_t)max_slabs * nt * nt + qwork) * sizeof(double), &ws));
+  double* F = (double*)ws + head;
   double* partial = F + (size_t)f_rows * nt;
+  double* qw = partial + (size_t)max_slabs * nt * nt;
   const unsigned nb32 = (unsigned)(nt / 32);
   const unsigned red_blocks = nb32 * (nb32 + 1) / 2;
   bool direct = false;
   for (int64_t r0 = 0; r0 < n; r0 += panel) {
     const int64_t nr = n - r0 < panel ? n - r0 : panel;
     const PanelPlan p = plan_panel(h, mp, nr);
-    hipLaunchKernelGGL(sparse_panel_kernel, dim3((unsigned)(nt / SP_TS), (unsigned)(p.rows_p / SP_TS)), dim3(256), 0,
+    const int64_t rows_w = fitc ? round_up(p.rows_p, NB) : p.rows_p;
+    hipLaunchKernelGGL(sparse_panel_kernel, dim3((unsigned)(nt / SP_TS), (unsigned)(rows_w / SP_TS)), dim3(256), 0,
                        h->stream, X + r0 * D, Yn + r0 * P, (long long)nr, Z, (int)m, D, P, l, sf2, F, (long long)nt,
                        (int)mp);
     GPK_LAUNCH_CHECK(h);
+    if (fitc) {
+      const unsigned nblk = (unsigned)(p.rows_p / SP_TS);
+      double* logpart = qw + (fused ? (size_t)(mp / 64) * f_rows : (size_t)f_rows * mp + f_rows);
+      int ntm = 0;
+      const double* resid = nullptr;
+      if (fused) {
+        // V = Wuu F[:, 0:mp]^T tile by tile (Wuu lower: k < row-tile end), never stored: qw[tile_row][i]
+        GemmArgs g = gemm_args(fitc->Wuu, fitc->ldw, 0, F, nt, 0, qw, rows_w, (int)mp, (int)rows_w, (int)mp, 1.0, 0.0);
+        g.ke0 = NB; g.ke_row = NB; g.epilogue = 1; g.k_super = 1; g.heavy_first = 1;
+        ntm = (int)(mp / gpk_gemm_tile(h, g));
+        GPK_TRY(gpk_gemm(h, GPK_F64, g));
+      } else {
+        // (its request for the handle's scratch is smaller than this call's and returns the same block: the head)
+        double* var = qw + (size_t)f_rows * mp;
+        GPK_TRY(gpk_predict_var_inv(h, GPK_F64, Z, m, D, ls, sf2, fitc->Wuu, mp, fitc->ldw, X + r0 * D, nr, sf2,
+                                    -std::numeric_limits<double>::max(), qw, var));
+        resid = var;
+      }
+      hipLaunchKernelGGL(sparse_fitc_scale_kernel, dim3((unsigned)((nt + 1023) / 1024), nblk), dim3(256), 0, h->stream, F,
+                         (long long)nt, (int)nt, (long long)nr, (const double*)qw, ntm, (long long)rows_w, resid, sf2, fitc->s2,
+                         logpart, fitc->wout ? fitc->wout + r0 : nullptr);
+      GPK_LAUNCH_CHECK(h);
+      hipLaunchKernelGGL(sparse_sum_kernel, dim3(1), dim3(256), 0, h->stream, (const double*)logpart, (long long)nblk, 1,
+                         fitc->loglam, 1);
+      GPK_LAUNCH_CHECK(h);
+    }
     if (p.slabs > 1) {
       GemmArgs g = gemm_args(F, nt, 1, F, nt, 1, partial, nt, (int)nt, (int)nt, (int)p.slab_rows, 1.0, 0.0);
       g.lower_only = 1;
@@ -521,6 +631,13 @@ struct gpk_sparse {
   // dropped by the next one (sparse_moment_matrix); a buffer of its own - the gradient and the path set-up reuse the others
   gpk_dev<double> Qm;
   bool q_ready = false;
+  // the approximation: 0 = DTC (Titsias), 1 = FITC - the statistics are then the weighted ones, S = F^T diag(w) F, and loglam
+  // is sum_i log lambda_i over the rows seen (dlog: its running value on the device, which the weighted pass adds to; the
+  // host copy is read back by sparse_read_loglam).  wuu_ready: Wuu is the inverse factor at the current (Z, hyper-parameters)
+  int fitc = 0;
+  double loglam = 0.0;
+  gpk_dev<double> dlog;
+  bool wuu_ready = false;
   gpk_dev<void> work;
 };
 
@@ -572,6 +689,51 @@ int sparse_new(gpk_handle h, const double* Z, int64_t m, int D, int P, const dou
   return GPK_OK;
 }
 
+// Luu Luu^T = Kuu + jitter_uu I (identity in the padding), Wuu = Luu^-1: the first step of the assembly, and under FITC what
+// the weighted pass needs before the first row.  The same launches on the same (Z, hyper-parameters) wherever it is called
+// from, so the finalised bits do not depend on how often it ran.
+int sparse_factor_kuu(gpk_handle h, gpk_sparse* s, int* info) {
+  const int64_t mp = s->mp;
+  s->wuu_ready = false;
+  GPK_TRY(gpk_gram(h, GPK_F64, s->Z, s->m, s->D, s->ls, s->sf2, s->jitter_uu, s->Kuu, mp));
+  int rc = gpk_potrf(h, s->Kuu, mp, mp, s->winv, info);
+  if (rc == GPK_NOT_PD) h->err = "sparse_finalize: Kuu + jitter_uu I is not positive definite; " + h->err;
+  GPK_TRY(rc);
+  GPK_TRY(gpk_trtri(h, s->Kuu, mp, mp, s->winv, s->Wuu, mp, s->T));
+  s->wuu_ready = true;
+  return GPK_OK;
+}
+
+// the statistics pass of the object's kind over n device rows: += F^T F (DTC) or += F^T diag(w) F and dlog += sum log lambda (FITC)
+int sparse_stats(gpk_handle h, gpk_sparse* s, const double* X, const double* Yn, int64_t n) {
+  if (!s->fitc) return accumulate(h, X, Yn, n, s->Z, s->m, s->D, s->P, s->ls, s->sf2, s->S, s->nt);
+  if (!s->wuu_ready) {      // (an evaluation that failed in the factorisation left none)
+    int info = 0;
+    GPK_TRY(sparse_factor_kuu(h, s, &info));
+  }
+  const FitcArgs f{s->Wuu, s->mp, s->sigma2, s->dlog, nullptr};
+  return accumulate(h, X, Yn, n, s->Z, s->m, s->D, s->P, s->ls, s->sf2, s->S, s->nt, &f);
+}
+
+// FITC: the running sum of log lambda_i from the device (synchronises)
+int sparse_read_loglam(gpk_handle h, gpk_sparse* s) {
+  GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
+  GPK_CHECK_HIP(h, hipMemcpy(&s->loglam, s->dlog, sizeof(double), hipMemcpyDeviceToHost));
+  return GPK_OK;
+}
+
+// sets the kind; FITC: allocates the device sum, sets it to loglam and factors Kuu (GPK_NOT_PD with the pivot in *info)
+int sparse_set_kind(gpk_handle h, gpk_sparse* s, int kind, double loglam, int* info) {
+  *info = 0;
+  s->finalized = false;
+  s->fitc = kind;
+  s->loglam = kind ? loglam : 0.0;
+  if (!kind) return GPK_OK;
+  if (!s->dlog) GPK_TRY(s->dlog.alloc(h, 1));
+  GPK_CHECK_HIP(h, hipMemcpy(s->dlog, &s->loglam, sizeof(double), hipMemcpyHostToDevice));
+  return sparse_factor_kuu(h, s, info);
+}
+
 }  // namespace
 
 void gpk_sparse_free(gpk_handle h) {
@@ -590,6 +752,70 @@ extern "C" int gpk_sparse_accumulate(gpk_handle h, const double* X, const double
   GPK_REQUIRE(h, sf2 > 0.0 && std::isfinite(sf2), "sparse_accumulate: sf2 must be positive");
   GPK_REQUIRE(h, h->batch == 1, "sparse_accumulate: not available in batched mode");
   return accumulate(h, X, Yn, n, Z, m, D, P, ls, sf2, S, ld);
+}
+
+extern "C" int gpk_sparse_accumulate_fitc(gpk_handle h, const double* X, const double* Yn, int64_t n, const double* Z, int64_t m,
+                                          int D, int P, const double* ls, double sf2, double* S, int64_t ld, const double* Wuu,
+                                          int64_t ldw, double sigma2, double* log_lambda_sum, double* w) {
+  if (!h) return GPK_BAD_ARG;
+  GPK_REQUIRE(h, X && Yn && Z && ls && S && Wuu && log_lambda_sum, "sparse_accumulate_fitc: null pointer");
+  GPK_REQUIRE(h, n >= 1 && n < (1ll << 40) && m >= 1 && m <= SP_MAX_M, "sparse_accumulate_fitc: need n >= 1, 1 <= m <= 16384");
+  GPK_REQUIRE(h, D >= 1 && D <= GPK_MAX_D_PREDICT && P >= 1 && P <= GPK_MAX_P,
+              "sparse_accumulate_fitc: need 1 <= D <= 16, 1 <= P <= GPK_MAX_P");
+  GPK_REQUIRE(h, ld >= gpk_padded(m) + NB && ld % 2 == 0 && ((uintptr_t)S % 16) == 0,
+              "sparse_accumulate_fitc: S must be 16-byte aligned with an even ld >= gpk_padded(m) + 128");
+  GPK_REQUIRE(h, ldw >= gpk_padded(m) && ldw % 2 == 0 && ((uintptr_t)Wuu % 16) == 0,
+              "sparse_accumulate_fitc: Wuu must be 16-byte aligned with an even ldw >= gpk_padded(m)");
+  GPK_REQUIRE(h, sf2 > 0.0 && std::isfinite(sf2) && sigma2 > 0.0 && std::isfinite(sigma2),
+              "sparse_accumulate_fitc: sf2 and sigma2 must be positive");
+  GPK_REQUIRE(h, h->batch == 1, "sparse_accumulate_fitc: not available in batched mode");
+  const FitcArgs f{Wuu, ldw, sigma2, log_lambda_sum, w};
+  return accumulate(h, X, Yn, n, Z, m, D, P, ls, sf2, S, ld, &f);
+}
+
+extern "C" int gpk_sparse_set_approximation(gpk_handle h, int kind, int* info) {
+  if (!h) return GPK_BAD_ARG;
+  gpk_sparse* s = h->sparse;
+  GPK_REQUIRE(h, s, "sparse_set_approximation: no sparse model (call gpk_sparse_begin first)");
+  GPK_REQUIRE(h, info, "sparse_set_approximation: null pointer");
+  GPK_REQUIRE(h, kind == GPK_SPARSE_DTC || kind == GPK_SPARSE_FITC, "sparse_set_approximation: kind must be 0 (DTC) or 1 (FITC)");
+  *info = 0;
+  if (kind == s->fitc) return GPK_OK;
+  GPK_REQUIRE(h, s->n_rows == 0 && s->held_n == 0,
+              "sparse_set_approximation: the object has seen rows - their statistics are those of the other approximation");
+  GPK_REQUIRE(h, h->batch == 1, "composite calls are not available in batched mode");
+  GPK_CHECK_HIP(h, hipSetDevice(h->device));
+  GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
+  return sparse_set_kind(h, s, kind, 0.0, info);
+}
+
+extern "C" int gpk_sparse_get_approximation(gpk_handle h, int* kind, double* log_lambda_sum) {
+  if (!h) return GPK_BAD_ARG;
+  gpk_sparse* s = h->sparse;
+  GPK_REQUIRE(h, s, "sparse_get_approximation: no sparse model");
+  if (kind) *kind = s->fitc;
+  if (log_lambda_sum) {
+    if (s->fitc) {
+      GPK_CHECK_HIP(h, hipSetDevice(h->device));
+      GPK_TRY(sparse_read_loglam(h, s));
+    }
+    *log_lambda_sum = s->fitc ? s->loglam : 0.0;
+  }
+  return GPK_OK;
+}
+
+extern "C" int gpk_sparse_restore_approximation(gpk_handle h, int kind, double log_lambda_sum, int* info) {
+  if (!h) return GPK_BAD_ARG;
+  gpk_sparse* s = h->sparse;
+  GPK_REQUIRE(h, s, "sparse_restore_approximation: no sparse model (call gpk_sparse_import first)");
+  GPK_REQUIRE(h, info, "sparse_restore_approximation: null pointer");
+  GPK_REQUIRE(h, kind == GPK_SPARSE_DTC || kind == GPK_SPARSE_FITC, "sparse_restore_approximation: kind must be 0 (DTC) or 1 (FITC)");
+  GPK_REQUIRE(h, std::isfinite(log_lambda_sum), "sparse_restore_approximation: the sum of log lambda must be finite");
+  GPK_REQUIRE(h, s->held_n == 0, "sparse_restore_approximation: the object holds rows (their statistics are its own)");
+  GPK_REQUIRE(h, h->batch == 1, "composite calls are not available in batched mode");
+  GPK_CHECK_HIP(h, hipSetDevice(h->device));
+  GPK_CHECK_HIP(h, hipStreamSynchronize(h->stream));
+  return sparse_set_kind(h, s, kind, log_lambda_sum, info);
 }
 
 extern "C" int gpk_sparse_begin(gpk_handle h, const double* Z, int64_t m, int D, int P, const double* ls, int n_ls, double sf2,
@@ -625,7 +851,7 @@ extern "C" int gpk_sparse_update(gpk_handle h, const double* X, const double* Y,
     s->hY.reset();
     s->held_n = 0;
   }
-  int rc = accumulate(h, dX, dY, n, s->Z, s->m, D, P, s->ls, s->sf2, s->S, s->nt);
+  int rc = sparse_stats(h, s, dX, dY, n);
   if (hipStreamSynchronize(h->stream) != hipSuccess && rc == GPK_OK) {     // (yn leaves scope)
     h->err = "sparse_update: the statistics pass failed";
     rc = GPK_HIP_ERROR;
@@ -645,12 +871,8 @@ int sparse_assemble(gpk_handle h, gpk_sparse* s, int* info) {
   *info = 0;
   s->finalized = false;
   s->q_ready = false;      // (Q belongs to the factors this assembly overwrites)
-  // Luu Luu^T = Kuu + jitter_uu I (identity in the padding), Wuu = Luu^-1
-  GPK_TRY(gpk_gram(h, GPK_F64, s->Z, s->m, s->D, s->ls, s->sf2, s->jitter_uu, s->Kuu, mp));
-  int rc = gpk_potrf(h, s->Kuu, mp, mp, s->winv, info);
-  if (rc == GPK_NOT_PD) h->err = "sparse_finalize: Kuu + jitter_uu I is not positive definite; " + h->err;
-  GPK_TRY(rc);
-  GPK_TRY(gpk_trtri(h, s->Kuu, mp, mp, s->winv, s->Wuu, mp, s->T));
+  GPK_TRY(sparse_factor_kuu(h, s, info));
+  int rc;
   // A1 = Wuu G (Wuu lower: k < row-tile end), B = I + A1 Wuu^T / sigma^2 (k < column-tile end; every tile, so that the
   // factorisation finds whole diagonal tiles).  G is zero in the padding, so B is the identity there.
   {
@@ -708,9 +930,16 @@ int sparse_assemble(gpk_handle h, gpk_sparse* s, int* info) {
   GPK_TRY(gpk_lml_terms(h, s->Bm, s->m, mp, s->r, s->c, P, terms));
   const double N = (double)s->n_rows, s2 = s->sigma2;
   double bound = 0.0;
-  for (int p = 0; p < P; ++p)
-    bound += -0.5 * N * std::log(2.0 * M_PI * s2) - terms[0] - 0.5 * (N * s->sf2 - s2 * tr_a) / s2 - 0.5 * yy[p] / s2 +
-             0.5 * terms[1 + p];
+  if (s->fitc) {
+    // log N(y | 0, Qff + diag(lambda)): -N/2 log sigma^2 becomes -1/2 sum log lambda_i, no trace term; yy and r carry the weights
+    GPK_TRY(sparse_read_loglam(h, s));
+    for (int p = 0; p < P; ++p)
+      bound += -0.5 * N * std::log(2.0 * M_PI) - 0.5 * s->loglam - terms[0] - 0.5 * yy[p] / s2 + 0.5 * terms[1 + p];
+  } else {
+    for (int p = 0; p < P; ++p)
+      bound += -0.5 * N * std::log(2.0 * M_PI * s2) - terms[0] - 0.5 * (N * s->sf2 - s2 * tr_a) / s2 - 0.5 * yy[p] / s2 +
+               0.5 * terms[1 + p];
+  }
   s->bound = bound;
   s->yy_sum = 0.0;
   for (int p = 0; p < P; ++p) s->yy_sum += yy[p];
@@ -870,7 +1099,8 @@ extern "C" int gpk_sparse_hold(gpk_handle h, const double* X, const double* Y, i
   s->finalized = false;
   s->n_rows = 0;
   GPK_CHECK_HIP(h, hipMemsetAsync(s->S, 0, (size_t)s->nt * s->nt * sizeof(double), h->stream));
-  int rc = accumulate(h, s->hX, s->hY, n, s->Z, s->m, D, P, s->ls, s->sf2, s->S, s->nt);
+  if (s->fitc) GPK_CHECK_HIP(h, hipMemsetAsync(s->dlog, 0, sizeof(double), h->stream));
+  int rc = sparse_stats(h, s, s->hX, s->hY, n);
   if (hipStreamSynchronize(h->stream) != hipSuccess && rc == GPK_OK) {     // (yn leaves scope)
     h->err = "sparse_hold: the statistics pass failed";
     rc = GPK_HIP_ERROR;
@@ -895,6 +1125,9 @@ int sparse_eval(gpk_handle h, const double* Z, const double* ls, int n_ls, doubl
               "sparse_eval: sf2 and the noise sigma^2 = noise + jitter must be positive");
   for (int d = 0; d < n_ls; ++d) GPK_REQUIRE(h, ls[d] > 0.0 && std::isfinite(ls[d]), "sparse_eval: length-scales must be positive");
   GPK_REQUIRE(h, h->batch == 1, "composite calls are not available in batched mode");
+  GPK_REQUIRE(h, !(s->fitc && (grad || gradZ)),
+              "sparse_eval: the gradient of the FITC likelihood is not available (the object's approximation is FITC: pass grad = "
+              "gradZ = NULL, or train as DTC)");
   if (Z) GPK_TRY(gpk_require_finite(h, Z, s->m * s->D, "sparse_eval", "Z"));
   GPK_CHECK_HIP(h, hipSetDevice(h->device));
   const int D = s->D;
@@ -907,10 +1140,15 @@ int sparse_eval(gpk_handle h, const double* Z, const double* ls, int n_ls, doubl
   s->sf2 = sf2; s->noise = noise; s->sigma2 = noise + s->jitter;
   for (int d = 0; d < D; ++d) s->ls[d] = ls[n_ls == 1 ? 0 : d];
   for (int d = 0; d < n_ls; ++d) s->ls_in[d] = ls[d];
+  s->wuu_ready = false;
+  if (s->fitc) {      // the weights need the inverse factor at these hyper-parameters (and this Z) before the first row
+    GPK_TRY(sparse_factor_kuu(h, s, info));
+    GPK_CHECK_HIP(h, hipMemsetAsync(s->dlog, 0, sizeof(double), h->stream));
+  }
   // the statistics of the held rows at these hyper-parameters
   GPK_CHECK_HIP(h, hipMemsetAsync(s->S, 0, (size_t)s->nt * s->nt * sizeof(double), h->stream));
   gpk_time_begin(h, GPK_TIMED_SPARSE_STATS);
-  int rc = accumulate(h, s->hX, s->hY, s->held_n, s->Z, s->m, D, s->P, s->ls, s->sf2, s->S, s->nt);
+  int rc = sparse_stats(h, s, s->hX, s->hY, s->held_n);
   gpk_time_end(h);
   GPK_TRY(rc);
   s->n_rows = s->held_n;

@@ -15,6 +15,12 @@ an m x m kernel); by default the inducing inputs stay where they are.  Where the
 random subset of the rows, or the rows picked by greedy conditional variance (`select_inducing`, `gpk_sparse_select`:
 `from_exact(selection="greedy")`, `train(select_inducing="greedy")`).
 
+`approximation="fitc"` selects the FITC posterior (Snelson & Ghahramani 2006; GPflow's GPRFITC) instead of the default DTC one:
+every row gets the part of its prior variance that the inducing inputs cannot explain, sf2 - |Wuu k_u(x_i)|^2, as noise of its
+own, through weighted statistics (`gpk_sparse_set_approximation`; DESIGN.md, K9, "FITC").  Fitting, serving, pickling and
+`log_bound(theta)` work unchanged and `bound()` is the FITC log-marginal likelihood; its gradient is not built, so `train` and
+the gradient flags raise a ValueError that names the recipe: train as DTC, then build the FITC model from that kernel and Z.
+
 The class keeps one libgpk handle of its own: the sparse model is the object behind that handle (include/gpk.h), the
 arrays that cross the boundary are host NumPy arrays.
 """
@@ -58,8 +64,25 @@ def unpack_inducing(v, n_theta, shape):
     return v[:n_theta].copy(), v[n_theta:].reshape(shape).copy()
 
 
+APPROXIMATIONS = ("dtc", "fitc")       # the C side's kinds, GPK_SPARSE_DTC = 0 and GPK_SPARSE_FITC = 1, by index
+
+_FITC_NO_GRADIENT = ("the gradient of the FITC likelihood is not available (approximation='fitc'): lambda depends on the "
+                     "hyper-parameters and on the inducing inputs, and that gradient is not built.  Supported recipe: train as DTC "
+                     "(approximation='dtc') or as an exact model, then build the FITC model from that kernel and those inducing "
+                     "inputs (SparseGP(kernel_, inducing_, approximation='fitc'), SparseGP.from_exact(..., approximation='fitc'))")
+
+
+def check_approximation(approximation):
+    """'dtc' or 'fitc' (ValueError otherwise)."""
+    if approximation not in APPROXIMATIONS:
+        raise ValueError(f"approximation must be 'dtc' or 'fitc', got {approximation!r}")
+    return approximation
+
+
 class SparseGP:
-    def __init__(self, kernel, inducing, *, alpha=1e-10, jitter_uu=None, y_mean=None, y_std=None, device=None):
+    def __init__(self, kernel, inducing, *, alpha=1e-10, jitter_uu=None, y_mean=None, y_std=None, device=None,
+                 approximation="dtc"):
+        self.approximation_ = check_approximation(approximation)
         self.kernel = kernel
         self.kernel_ = copy.deepcopy(kernel)
         comp = self.kernel_.components()          # rejects anything but [C *] RBF [+ WhiteKernel], as gpr.py does
@@ -89,12 +112,14 @@ class SparseGP:
 
     # ------------------------------------------------------------------ construction from an exact model
     @classmethod
-    def from_exact(cls, gpr, inducing=None, random_state=0, jitter_uu=None, selection="random"):
+    def from_exact(cls, gpr, inducing=None, random_state=0, jitter_uu=None, selection="random", approximation="dtc"):
         """Kernel, `alpha` and target normalisation of a fitted `GaussianProcessRegressor`; inducing inputs: an array, an
         integer (that many of its training rows, picked by a seeded permutation) or None (all of them).  The sparse model
         starts with no rows: `partial_fit` the flight log (the exact model's own rows included, if they are to count).
         `selection="greedy"` picks the integer's rows by greedy conditional variance under the regressor's kernel instead
-        (`select_inducing`); ValueError if fewer than that many rows are usable (duplicates, say)."""
+        (`select_inducing`); ValueError if fewer than that many rows are usable (duplicates, say).  `approximation`: "dtc" or
+        "fitc", as the constructor takes it (the selection does not depend on it)."""
+        check_approximation(approximation)
         if selection not in ("random", "greedy"):
             raise ValueError(f"selection must be 'random' or 'greedy', got {selection!r}")
         if not hasattr(gpr, "X_train_"):
@@ -108,15 +133,16 @@ class SparseGP:
             if selection == "greedy":
                 probe = cls(gpr.kernel_, X[:1], alpha=gpr.alpha, jitter_uu=jitter_uu, device=gpr.device)
                 Z = X[probe._select_exactly(X, int(inducing))]
-                return cls._like(gpr, Z, jitter_uu)
+                return cls._like(gpr, Z, jitter_uu, approximation)
             Z = X[np.sort(np.random.default_rng(random_state).permutation(len(X))[:int(inducing)])]
         else:
             Z = inducing
-        return cls._like(gpr, Z, jitter_uu)
+        return cls._like(gpr, Z, jitter_uu, approximation)
 
     @classmethod
-    def _like(cls, gpr, Z, jitter_uu):
-        out = cls(gpr.kernel_, Z, alpha=gpr.alpha, jitter_uu=jitter_uu, y_mean=gpr._y_train_mean, y_std=gpr._y_train_std, device=gpr.device)
+    def _like(cls, gpr, Z, jitter_uu, approximation="dtc"):
+        out = cls(gpr.kernel_, Z, alpha=gpr.alpha, jitter_uu=jitter_uu, y_mean=gpr._y_train_mean, y_std=gpr._y_train_std, device=gpr.device,
+                  approximation=approximation)
         out._y_1d = bool(getattr(gpr, "_y_1d", True))
         return out
 
@@ -153,7 +179,18 @@ class SparseGP:
                         self.alpha, self.jitter_uu, _ptr(self._ym), _ptr(self._ys), _ptr(st["G"]), _ptr(st["g"]),
                         _ptr(st["yy"]), int(st["n_rows"]))
                 self._state = None
+            if self._fitc:       # (GPK_NOT_PD - Kuu + jitter_uu I, factored at once - raises LinAlgError as the finalisation does)
+                info = C.c_int(0)
+                if st is None:
+                    be.call("gpk_sparse_set_approximation", 1, C.byref(info))
+                else:
+                    be.call("gpk_sparse_restore_approximation", 1, float(st.get("log_lambda_sum", 0.0)), C.byref(info))
         self._P, self._live, self._final, self._held = P, True, False, False
+
+    @property
+    def _fitc(self):
+        """(objects unpickled from before the attribute existed are DTC)"""
+        return self.__dict__.get("approximation_", "dtc") == "fitc"
 
     def _ensure(self):
         """The assembled model: created (the prior, if no row was ever given) and finalised."""
@@ -222,6 +259,8 @@ class SparseGP:
         `eval_inducing_gradient` returns (value, grad_theta, grad_Z), grad_Z (m, D) in raw coordinates.  A matrix that is not
         positive definite gives -inf and zero gradients.  After the call the object is the model at theta (`kernel_` follows)
         and at these inducing inputs.  Without the two inducing arguments the call is `gpk_sparse_eval`, launch for launch."""
+        if self._fitc and (eval_gradient or eval_inducing_gradient):
+            raise ValueError("log_bound: " + _FITC_NO_GRADIENT)
         if theta is None:
             if eval_gradient or eval_inducing_gradient or inducing is not None:
                 raise ValueError("Gradient can only be evaluated for theta!=None")
@@ -318,6 +357,8 @@ class SparseGP:
         object keeps its number of inducing inputs: a round takes rows below the variance floor too, and raises ValueError
         only if fewer than that many rows have any conditional variance left (exact duplicates)."""
         from .gpr import _rng_from
+        if self._fitc:
+            raise ValueError("train: " + _FITC_NO_GRADIENT)
         if select_inducing not in (None, "greedy"):
             raise ValueError(f"select_inducing must be None or 'greedy', got {select_inducing!r}")
         if select_inducing is not None and int(selection_rounds) < 1:
@@ -720,7 +761,8 @@ class SparseGP:
 
     def bound(self):
         """The collapsed lower bound on the log-marginal likelihood of the rows seen so far, in normalised-target units (the
-        exact log-marginal likelihood when the inducing inputs are the training inputs)."""
+        exact log-marginal likelihood when the inducing inputs are the training inputs).  approximation="fitc": the FITC
+        log-marginal likelihood log N(y | 0, Qff + diag(lambda)) - not a bound on the exact one; equal to it when Z = X."""
         self._ensure()
         b, n = C.c_double(0.0), C.c_int64(0)
         self._backend().call("gpk_sparse_bound", C.byref(b), C.byref(n))
@@ -738,17 +780,23 @@ class SparseGP:
         return int(n.value)
 
     def statistics(self):
-        """The additive statistics as host arrays: {"G" (m, m), "g" (m, P), "yy" (P,), "n_rows"}."""
+        """The additive statistics as host arrays: {"G" (m, m), "g" (m, P), "yy" (P,), "n_rows"}; approximation="fitc": the
+        weighted ones, and "log_lambda_sum" (the sum of log lambda_i over the rows, the likelihood's extra scalar)."""
         if self._state is not None:
             return dict(self._state)
         if not self._live:
             return None
+        extra = {}
+        if self._fitc:
+            kind, lam = C.c_int(0), C.c_double(0.0)
+            self._backend().call("gpk_sparse_get_approximation", C.byref(kind), C.byref(lam))
+            extra["log_lambda_sum"] = float(lam.value)
         m, P = self.inducing_.shape[0], self._P
         G, g, yy = np.empty((m, m)), np.empty((m, P)), np.empty(P)
         n = C.c_int64(0)
         self._backend().call("gpk_sparse_export", None, None, None, None, None, _ptr(G), _ptr(g), _ptr(yy), C.byref(n), None, None,
                              None, None)
-        return {"G": G, "g": g, "yy": yy, "n_rows": int(n.value)}
+        return {"G": G, "g": g, "yy": yy, "n_rows": int(n.value), **extra}
 
     # ------------------------------------------------------------------ pickling: Z, the statistics, the hyper-parameters
     def __getstate__(self):
@@ -761,6 +809,7 @@ class SparseGP:
 
     def __setstate__(self, st):
         self.__dict__.update(st)
+        self.__dict__.setdefault("approximation_", "dtc")      # (pickles written before the attribute existed)
 
     def __del__(self):
         be = self.__dict__.get("_be")

@@ -40,11 +40,18 @@ class BatchedSparseGP:
         self.models = models
 
     @classmethod
-    def from_exact(cls, gprs, inducing=None, selection="random", random_state=0):
+    def from_exact(cls, gprs, inducing=None, selection="random", random_state=0, approximation="dtc"):
         """`SparseGP.from_exact` per model: gprs is a list of fitted single-output `GaussianProcessRegressor`s or a fitted
-        `BatchedARDGP`; `inducing` as there (an integer: that many of each model's own training rows)."""
+        `BatchedARDGP`; `inducing` as there (an integer: that many of each model's own training rows); `approximation`: "dtc"
+        or "fitc" for all of them.  (A batch built from models may mix the two: serving does not depend on the kind.)"""
         gprs = getattr(gprs, "models", gprs)
-        return cls([SparseGP.from_exact(g, inducing, random_state=random_state, selection=selection) for g in gprs])
+        return cls([SparseGP.from_exact(g, inducing, random_state=random_state, selection=selection, approximation=approximation)
+                    for g in gprs])
+
+    @property
+    def approximations_(self):
+        """The models' kinds, "dtc" or "fitc" each."""
+        return [m.approximation_ for m in self.models]
 
     @property
     def n_features_in_(self):

@@ -190,13 +190,17 @@ class GPTrainer:
         self.training_stats = results
         return results
 
-    def sparsify(self, X, y, inducing, selection="greedy", train=False, **train_kw):
+    def sparsify(self, X, y, inducing, selection="greedy", train=False, approximation="dtc", **train_kw):
         """Replaces every trained exact model by a sparse one that has seen ALL rows of X (n, 10), y (n, 6) - the rows a
         `max_samples` cap (`load_training_data`, `src/px4/gp_trainer.py:95-96`) had thrown away included: per model
         `SparseGP.from_exact(model, inducing, selection=...)` on that model's own (scaled) training inputs, then
         `partial_fit` on all rows scaled with the stored scalers and, with train=True, `SparseGP.train(rows, **train_kw)`.
         `save_models()` then writes a file that `PreTrainedGP` loads and serves through `BatchedSparseGP`: all models in one
-        call.  Models that are sparse already are left alone."""
+        call.  Models that are sparse already are left alone.  approximation: "dtc" or "fitc", as `SparseGP` takes it; with
+        "fitc" and train=True the model is trained as DTC (the FITC likelihood has no gradient here) and the FITC model is then
+        built from the trained kernel and inducing inputs and given all rows."""
+        from .sparse import check_approximation
+        check_approximation(approximation)
         X = np.asarray(X, dtype=np.float64)
         y = np.asarray(y, dtype=np.float64)
         for name, model in list(self.gp_models.items()):
@@ -205,9 +209,12 @@ class GPTrainer:
             i = OUTPUT_NAMES.index(name)
             Xs = self.scalers_X[name].transform(X)
             ys = self.scalers_y[name].transform(y[:, i].reshape(-1, 1)).ravel()
-            sp = SparseGP.from_exact(model, inducing, selection=selection)
+            sp = SparseGP.from_exact(model, inducing, selection=selection, approximation="dtc" if train else approximation)
             if train:
                 sp.train(Xs, ys, **train_kw)
+                if approximation == "fitc":
+                    sp = SparseGP(sp.kernel_, sp.inducing_, alpha=sp.alpha, jitter_uu=sp.jitter_uu, y_mean=sp.y_mean, y_std=sp.y_std,
+                                  device=sp.device, approximation="fitc").partial_fit(Xs, ys)
             else:
                 sp.partial_fit(Xs, ys)
             self.gp_models[name] = sp
@@ -330,6 +337,12 @@ class PreTrainedGP:
             except Exception as e:  # noqa: BLE001 - never into the control loop: the per-model path below still serves
                 print(f"fused per-axis prediction unavailable: {e}")
         return self._fused_bg
+
+    @property
+    def approximations_(self):
+        """{output name: "dtc" or "fitc"} for the sparse models of the file (`GPTrainer.sparsify(approximation=...)`); exact
+        models are not listed."""
+        return {n: m.approximation_ for n, m in self.gp_models.items() if isinstance(m, SparseGP)}
 
     def _one_input_scaler(self, names):
         sx0 = self.scalers_X[names[0]]
