@@ -75,7 +75,8 @@ GPK_API int64_t gpk_padded(int64_t n);
 /* gpk_set_option: the handle's tuning knobs (the library reads NOTHING from the environment), settable on a live handle:
  * "k5_split2_tile" (gpk_predict_var_inv_split2: 0 = the tallest of the 512 / 256 / 128 x 128 tiles that still comes in at
  * least 512 tiles, 1 = always 128 x 128, 2 = 512 x 128 whenever Np % 512 == 0, 3 = 256 x 128 whenever Np % 256 == 0 and as 0
- * otherwise), "small_path", "trsm256",
+ * otherwise), "k5_mfma_shape" (the same launch: 1 = on v_mfma_f32_32x32x16_f16, 2 = on v_mfma_f32_16x16x32_f16, 0 or anything else =
+ * the library's default, 16x16x32; with "k5_log" the launch names its shape on a line "GPKSHAPE ..."), "small_path", "trsm256",
  * "trtri_levels", "gemm_small_tiles" / "gemm_tiny_tiles" (launches of fewer 128 x 128 tiles than these - 1024 / 320 - run on 64 x 64 /,
  * fp64 only, 32 x 32 tiles; bit-identical results), "k3_stream_min_np", "ptile" (gpk_potrf: 1 = the one-launch tile factorisation of
  * gpk_ptile.hip for 512 <= Np <= "ptile_max_np" (24576), 0 = the recursive launch chain), "ptile_prog_max_nt" (that launch:

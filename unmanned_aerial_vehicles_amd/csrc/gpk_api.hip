@@ -73,6 +73,7 @@ extern "C" int gpk_set_option(gpk_handle h, const char* name, int value) {
   GPK_REQUIRE(h, name, "set_option: null name");
   const std::string n(name);
   if (n == "k5_split2_tile") h->k5_split2_tile = (value >= 0 && value <= 3) ? value : 0;
+  else if (n == "k5_mfma_shape") h->k5_mfma_shape = (value >= 0 && value <= 2) ? value : 0;
   else if (n == "small_path") h->small_path = value;
   else if (n == "trsm256") h->trsm256 = value;
   else if (n == "trtri_levels") h->trtri_levels = value;

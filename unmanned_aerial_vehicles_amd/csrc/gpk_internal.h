@@ -54,6 +54,7 @@ struct gpk_context {
                                  // 128-column tile GEMMs from there on (N = 4096: 0.11 against 0.35 ms, profiles/r04_k3_ab.log)
   int k5_split2_tile = 0;    // fp16 x 2 variance launch: 0 = the tallest tile (512 / 256 / 128 x 128) that still comes in >= 512
                              // tiles; 1 = always 128 x 128; 2 = 512 x 128 whenever Np % 512 == 0; 3 = 256 x 128 whenever Np % 256 == 0
+  int k5_mfma_shape = 0;     // ... its MFMA shape: 0 = the default (gpk_k5split.hip), 1 = 32x32x16, 2 = 16x16x32
   int ptile = 1;             // gpk_potrf: one persistent launch (gpk_ptile.hip) for 512 <= Np <= ptile_max_np
   int ptile_max_np = 24576;  // (above, the recursion: halves that are one launch each + GEMMs.  One launch against that at 20 480 rows 46.7 / 48.6 ms,
                              // 24 576 78.6 / 79.2, 32 768 179.4 / 172.5, 40 960 347.4 / 340.6: profiles/r05_ptile_large.log; 16 384 until round 5)

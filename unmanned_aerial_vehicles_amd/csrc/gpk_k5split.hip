@@ -2,8 +2,10 @@
 // reduced to per-column sums of squares (fp64) in the epilogue instead of being stored.  Two forms:
 //
 //  * fp16 x 2 (k5_direct_kernel; the fp32 serving default): x s = h0 + h1, two fp16 parts rounded to nearest (s: one power
-//    of two per 128-row block), block products a1 b0 + a0 b1 + a0 b0 on v_mfma_f32_32x32x16_f16, fp32 accumulation.  The
-//    operands are stored in "fragment order" and go from L2 straight into registers: no LDS, no barriers.
+//    of two per 128-row block), block products a1 b0 + a0 b1 + a0 b0, fp32 accumulation.  The operands are stored in
+//    "fragment order" and go from L2 straight into registers: no LDS, no barriers.  One launch in two MFMA shapes - same grid,
+//    tiles, k-ranges and operands -: v_mfma_f32_16x16x32_f16 serves (the chip holds a higher clock on it: K5_MFMA_SHAPE_DEFAULT
+//    below), v_mfma_f32_32x32x16_f16 under option k5_mfma_shape = 1.
 //  * bf16 x 3 (k5_split_kernel): x = x0 + x1 + x2 EXACTLY, three bf16 parts, six products per block (a0 b0, a0 b1, a1 b0,
 //    a1 b1, a0 b2, a2 b0: bf16 x bf16 products are exact, the dropped cross terms are below 2^-24 of |a||b|); twice the
 //    matrix-pipe work of the first form.  Register-staged LDS pipeline on 128 x 128 or 256 x 128 tiles.
@@ -30,6 +32,7 @@ namespace {
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int V16 __attribute__((ext_vector_type(4)));
 typedef float f16v __attribute__((ext_vector_type(16)));
+typedef float f4v __attribute__((ext_vector_type(4)));
 template <int V> struct IntC { static constexpr int value = V; };
 
 constexpr int ROWB = 384;      // bytes of one k-tile (16 k) of a quad of rows: 4 rows x 2 halves x 3 parts x 16 B
@@ -294,7 +297,104 @@ struct DParams {
   int per_pad;          // tile slots per band of the walk (>= band height in tiles x ntn)
 };
 
+// the MFMA shape of the launch where option k5_mfma_shape is 0: 1 = 32x32x16 (the form above), 2 = 16x16x32 (below).  Measured at
+// the headline shape, same box, same process (profiles/r29_k5_shape_ab.log): 93.85 against 82.52 ms per launch - the chip holds
+// 1.71 GHz on the 16x16x32 form against 1.48 GHz at 0.88 against 0.90 MFMA busy (profiles/r29_pmc_k5_fp16x2_*.txt).
+constexpr int K5_MFMA_SHAPE_DEFAULT = 2;
+
+// The same launch on v_mfma_f32_16x16x32_f16 (SHAPE = 2; option k5_mfma_shape): same grid, tile, waves, per-wave k-range,
+// products and operands, the wave's 32 AB x 128 block held as 2 AB x 8 accumulator blocks of 16 x 16.  A 16x16x32 operand comes
+// out of the same fragment order: lane l = 16 q + r (k octet q of the 32-step, row r of the 16-row group g) wants chunk (row
+// 16 g + r, kb = 2 j + (q >> 1), h = q & 1, s), which lies at byte (q >> 1) 2048 + (q & 1) 512 + r 16 - a constant of the lane -
+// plus 4096 j + 1024 s + 256 g inside the 32-row block's strip: one wave load touches four runs of 256 bytes = eight whole
+// cache lines, as above.  Registers: 256 accumulators, the K* fragments of two 32-steps (2 x 64; a fragment is refilled for step
+// j + 2 behind its last MFMA of step j) and the W fragments of one (64; a row group's is refilled for step j + 1 behind the
+// group's last MFMA: it is not needed again before the same place of the next step).  C layout: column = lane & 15, row =
+// 4 (lane >> 4) + register.
 template <int AB>
+__device__ __forceinline__ void direct_tile_16x16x32(const DParams& p, int tm, int row0, int col0, int nkt, double* red) {
+  constexpr int RG = 2 * AB;                     // 16-row groups of this wave
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int nj = nkt >> 1;                       // 32-steps of this wave: nkt = 2 AB (...) is even
+  f4v acc[RG][8];
+#pragma unroll
+  for (int g = 0; g < RG; ++g)
+#pragma unroll
+    for (int b = 0; b < 8; ++b)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) acc[g][b][i] = 0.f;
+
+  const unsigned vo = (lane >> 5) * 2048 + ((lane >> 4) & 1) * 512 + (lane & 15) * 16;
+  const char* ua = p.A + (long long)((row0 >> 5) + AB * wave) * p.rba;
+  const char* ub = p.B + (long long)(col0 >> 5) * p.rbb;
+  const int rba = (int)p.rba, rbb = (int)p.rbb;
+  V16 FA[RG][2], FB[2][8][2];
+  // (a prefetch past the wave's own k-range re-reads its last step: what lies beyond may be unwritten or past the allocation)
+  auto rsrc_at = [&](const char* base, int step) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(base + (long long)min(step, nj - 1) * 4096), 0, 0x7fffffff, 0x00020000);
+  };
+  // 16-row group g of the 32-row blocks that start at rs: block g / 2 (rb bytes apart), its rows 16 (g % 2) ..
+  auto ldf = [&](const __amdgpu_buffer_rsrc_t rs, int g, int rb, V16 (&f)[2]) {
+    f[0] = __builtin_amdgcn_raw_buffer_load_b128(rs, vo, (g >> 1) * rb + (g & 1) * 256, 0);
+    f[1] = __builtin_amdgcn_raw_buffer_load_b128(rs, vo, (g >> 1) * rb + (g & 1) * 256 + 1024, 0);
+  };
+  auto mm = [&](f4v& c, const V16 (&fa)[2], const V16 (&fb)[2]) {
+    const f16x8 a0 = __builtin_bit_cast(f16x8, fa[0]), a1 = __builtin_bit_cast(f16x8, fa[1]);
+    const f16x8 b0 = __builtin_bit_cast(f16x8, fb[0]), b1 = __builtin_bit_cast(f16x8, fb[1]);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, b0, c, 0, 0, 0);       // smallest terms first
+    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, b1, c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, b0, c, 0, 0, 0);
+  };
+  {    // prologue: step 0 in the order the MFMAs will want it, then K* of step 1.  The order is pinned: the wait in front of the
+       // loop's first MFMA is one instruction for the way in and the way round, and counts the loads issued after the oldest it needs
+    const __amdgpu_buffer_rsrc_t ra = rsrc_at(ua, 0), rb0 = rsrc_at(ub, 0), rb1 = rsrc_at(ub, 1);
+    ldf(ra, 0, rba, FA[0]);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int b = 0; b < 8; ++b) { ldf(rb0, b, rbb, FB[0][b]); __builtin_amdgcn_sched_barrier(0); }
+#pragma unroll
+    for (int g = 1; g < RG; ++g) { ldf(ra, g, rba, FA[g]); __builtin_amdgcn_sched_barrier(0); }
+#pragma unroll
+    for (int b = 0; b < 8; ++b) { ldf(rb1, b, rbb, FB[1][b]); __builtin_amdgcn_sched_barrier(0); }
+  }
+  auto body = [&](int js, auto slc) {
+    constexpr int S = decltype(slc)::value;
+    const __amdgpu_buffer_rsrc_t ra = rsrc_at(ua, js + 1), rb = rsrc_at(ub, js + 2);
+#pragma unroll
+    for (int g = 0; g < RG; ++g) {
+#pragma unroll
+      for (int b = 0; b < 8; ++b) {
+        mm(acc[g][b], FA[g], FB[S][b]);
+        if (g == RG - 1) ldf(rb, b, rbb, FB[S][b]);       // last use of this step's K* fragment: refill it (step js + 2)
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      ldf(ra, g, rba, FA[g]);                             // ... and of the row group's W fragment (step js + 1)
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  for (int js = 0; js < nj; js += 2) {
+    body(js, IntC<0>{});
+    if (AB > 1 || js + 1 < nj) body(js + 1, IntC<1>{});
+  }
+
+  // ---- epilogue: per-column sums of squares of the tile (fp64), out[tile row][column]; scales as in the 32x32x16 form
+  const float alpha = (1.0f / p.wscale[(row0 + 32 * AB * wave) >> 7]) * (1.0f / p.kscale);
+#pragma unroll
+  for (int b = 0; b < 8; ++b) {
+    float s = 0.f;
+#pragma unroll
+    for (int g = 0; g < RG; ++g)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { const float v = alpha * acc[g][b][i]; s = __builtin_fmaf(v, v, s); }
+    s += __shfl_xor(s, 16, 64);
+    s += __shfl_xor(s, 32, 64);
+    if (lane < 16) red[wave * 128 + 16 * b + lane] = (double)s;
+  }
+  __syncthreads();
+  if (tid < 128) p.out[(long long)tm * p.Mp + col0 + tid] = (red[tid] + red[128 + tid]) + (red[256 + tid] + red[384 + tid]);
+}
+
+template <int AB, int SHAPE>
 __global__ __launch_bounds__(256, 1) void k5_direct_kernel(DParams p) {
   constexpr int TMR = 128 * AB, GSZ = 32, BH = 1024 / TMR;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -325,6 +425,11 @@ __global__ __launch_bounds__(256, 1) void k5_direct_kernel(DParams p) {
   // k-tiles of 16 of THIS WAVE: W is lower triangular, so its rows row0 + 32 AB wave .. end at column row0 + 32 AB (wave + 1)
   // (the waves of a workgroup do not wait for each other before the epilogue)
   const int nkt = (row0 + 32 * AB * (wave + 1)) / 16;
+  __shared__ double red[4 * 128];
+  if constexpr (SHAPE == 2) {
+    direct_tile_16x16x32<AB>(p, tm, row0, col0, nkt, red);
+    return;
+  }
 
   f16v acc[AB][4];
 #pragma unroll
@@ -392,7 +497,6 @@ __global__ __launch_bounds__(256, 1) void k5_direct_kernel(DParams p) {
   }
 
   // ---- epilogue: per-column sums of squares of the tile (fp64), out[tile row][column]
-  __shared__ double red[4 * 128];
   // powers of two, each reciprocal exact; formed separately so that a large block scale times the K* scale cannot
   // overflow on the way (absmax_to_scale_kernel also keeps block scales at or below 2^100)
   const float alpha = (1.0f / p.wscale[(row0 + 32 * AB * wave) >> 7]) * (1.0f / p.kscale);
@@ -606,10 +710,14 @@ int split2_launch(gpk_handle h, const char* who, const float* X, int64_t N, int 
   const long long nblocks = (long long)((p.nst + 7) / 8) * 8 * gsz;
   if (h->k5_log)   // option k5_log = 1: the form this launch takes (the tests assert it per case)
     fprintf(stderr, "GPKK5 direct rows%d ntmT%d ntn%d nst%d pad%d grid%lld\n", 128 * ab, ntmT, ntn, p.nst, p.per_pad, nblocks);
+  // the MFMA shape (option k5_mfma_shape: 1 = 32x32x16, 2 = 16x16x32, 0 = the default, K5_MFMA_SHAPE_DEFAULT); on a line of its own
+  const int shape = h->k5_mfma_shape ? h->k5_mfma_shape : K5_MFMA_SHAPE_DEFAULT;
+  if (h->k5_log) fprintf(stderr, "GPKSHAPE %s\n", shape == 2 ? "16x16x32" : "32x32x16");
+  void (*kern)(DParams) = nullptr;
+  if (shape == 2) kern = ab == 4 ? k5_direct_kernel<4, 2> : ab == 2 ? k5_direct_kernel<2, 2> : k5_direct_kernel<1, 2>;
+  else kern = ab == 4 ? k5_direct_kernel<4, 1> : ab == 2 ? k5_direct_kernel<2, 1> : k5_direct_kernel<1, 1>;
   gpk_time_begin(h, GPK_TIMED_K5);
-  if (ab == 4) hipLaunchKernelGGL(k5_direct_kernel<4>, dim3((unsigned)nblocks), dim3(256), 0, h->stream, p);
-  else if (ab == 2) hipLaunchKernelGGL(k5_direct_kernel<2>, dim3((unsigned)nblocks), dim3(256), 0, h->stream, p);
-  else hipLaunchKernelGGL(k5_direct_kernel<1>, dim3((unsigned)nblocks), dim3(256), 0, h->stream, p);
+  hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(256), 0, h->stream, p);
   gpk_time_end(h);
   GPK_LAUNCH_CHECK(h);
   *S = ntmT;
